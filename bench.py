@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """Headline benchmark: SVG1 block-sparse attention of one HunyuanVideo 720p / 129-frame layer-call on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload hy720p|hy480p|tiny] [--no-cpu] [--no-dense]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload hy720p|hy480p|tiny] [--dump-outputs DIR] [--full [--no-cpu] [--no-dense] ...]
+
+A plain run sets up, warms up, times the K steps and prints the result line: the headline figures plus what the timed steps' own events
+give (roofline kernel_ms, online_profiler ms, output_checksum).  Everything that takes work of its own (the shader-clock probe, the same-box
+A/B of the other schedules, the fp8 and other-model lines, the dense comparator, the SVG2 / denoise-step / HBM extras blocks, the CPU
+baseline, accuracy checks of --prescaled / --dtype fp8) runs only with --full; the --no-* options switch single blocks of --full off.
+--dump-outputs DIR: after the timed steps, what the last step computed goes to DIR as float32 .npy files — attn_out.npy, the layer-call
+output [H, R, D] on R = min(S, 4096) token rows (all of them when S <= 4096, otherwise a fixed sample: the first R of
+torch.randperm(S, generator=manual_seed(0)), sorted; at N > 1 the gathered output of every head), and sample_mse.npy, the online profiler's
+[2, H] result (N = 1, unless --no-profiler).  The inputs are seeded: the same arguments give the same inputs on every run.
 
 Workload (BASELINE.json configs[1]): q, k, v = randn([1, 24, 119056, 128], bf16) (F=33, P=3600, ctx=256, prompt 64),
 sparsity 0.25 -> band 15616 tokens, half of the heads temporal (fused layout transformation inside the kernel).
@@ -205,6 +214,9 @@ def main():
     ap.add_argument("--chunks", type=int, default=1, help="N = 1 only: split the launch into this many head chunks on two streams")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8"], help="fp8: e4m3 QK^T / PV (svg_band_attention_fp8: quantise + "
                     "placement pre-pass and attention kernel, both inside the timed step; BASELINE.json configs[4]); N = 1 only")
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline figure (clock probe, same-box A/B, fp8 and "
+                    "other-model lines, dense comparator, extras blocks, CPU baseline, accuracy checks); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-dense", action="store_true")
     ap.add_argument("--no-svg2", action="store_true", help="skip the SVG2 (BASELINE.json configs[2]) extras block")
@@ -218,9 +230,12 @@ def main():
                     "svg_sample_mse / svg_band_attention_prescaled on it.  Default since round 4: plain q, the softmax scale applied to the fp32 "
                     "scores inside the kernel (the reference's formulation, svg/models/hyvideo/attention.py:401-403)")
     ap.add_argument("--heads", default="alt", choices=["alt", "spatial", "temporal"], help="best_mask_idx pattern")
-    ap.add_argument("--extras", default="auto", choices=["auto", "small"], help="auto: the SVG2 / denoise-step extras blocks at full size beside the "
-                    "hy720p headline workload and nowhere else; small: the same blocks on reduced geometries beside ANY workload (contract tests)")
+    ap.add_argument("--extras", default="auto", choices=["auto", "small"], help="with --full: auto: the SVG2 / denoise-step extras blocks at full "
+                    "size beside the hy720p headline workload and nowhere else; small: the same blocks on reduced geometries beside ANY workload "
+                    "(contract tests)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -293,7 +308,7 @@ def main():
     o = torch.empty_like(q)
     pat = {"alt": lambda h: h % 2, "spatial": lambda h: 0, "temporal": lambda h: 1}[a.heads]
     best = torch.tensor([[pat(h) for h in my_heads]], device=dev, dtype=torch.int64)  # default: alternate spatial / temporal
-    rows = torch.randint(0, min(10000, V), (64,), device=dev)
+    rows = torch.randint(0, min(10000, V), (64,), device=dev, generator=g)   # (seeded: the default CUDA generator differs from run to run)
     bb = int((P_ * 1.5) // 128)
     prof = nat.ProfileDesc(0, F_, P_, 1)
     prof.variant[0] = nat.ProfileVariant(0, 0, V, bb, 0, V, S)
@@ -341,6 +356,7 @@ def main():
     LN2 = math.log(2.0)
     ev_p0, ev_p1 = [], []
     ev_q0, ev_q1 = [], []
+    last = {}   # the online profiler's result of the latest step (--dump-outputs)
 
     def step(timed: bool):
         if world > 1:   # inbound exchange: token shards -> this rank's heads over the full sequence
@@ -358,6 +374,7 @@ def main():
                 ev_q1.append(torch.cuda.Event(enable_timing=True))
                 ev_q1[-1].record()
             _ = mse.argmin(0)  # best_mask_idx (kept on device; the bench uses the fixed alternating pattern)
+            last["mse"] = mse
         e0 = torch.cuda.Event(enable_timing=True)
         e1 = torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -437,7 +454,7 @@ def main():
     # (N = 1 without side streams only: the probe occupies a hardware queue for the whole span, and a process has few of them — with
     #  the waiter / exchange streams of the N > 1 path a launch could be queued BEHIND the probe that waits for it)
     clock = None
-    if rank == 0 and world == 1 and side is None:
+    if a.full and rank == 0 and world == 1 and side is None:
         try:
             clock = nat.ClockProbe(dev)
         except Exception:  # noqa: BLE001
@@ -507,6 +524,16 @@ def main():
         bits = whole[h].contiguous().view(torch.int16).to(torch.int64)
         acc = (acc * 1000003 + int((bits * (torch.arange(bits.shape[-1], device=dev) + 1)).sum().item()) + 31 * int(bits.sum().item())) % (1 << 64)
     output_checksum = f"{acc:016x}"
+    if a.dump_outputs and rank == 0:   # before anything else of the run writes into `o`
+        import numpy as np
+
+        dump = Path(a.dump_outputs)
+        dump.mkdir(parents=True, exist_ok=True)
+        n_rows = min(S, 4096)
+        sel = torch.arange(S) if n_rows == S else torch.randperm(S, generator=torch.Generator().manual_seed(0))[:n_rows].sort().values
+        np.save(dump / "attn_out.npy", whole.index_select(1, sel.to(dev)).float().cpu().numpy())
+        if "mse" in last and world == 1:
+            np.save(dump / "sample_mse.npy", last["mse"].float().cpu().numpy())
 
     out = None
     if rank == 0:
@@ -584,12 +611,13 @@ def main():
             }
         if a.prescaled:
             out["config"]["q_prescaled"] = "--prescaled: q carries sm_scale * log2(e), as the fused prologue writes it under prescale_q = True (opt-in; default: plain q)"
+        if a.prescaled and a.full:
             ob = nat.band_attention(q[:, :2].contiguous(), k[:, :2].contiguous(), v[:, :2].contiguous(), mask,
                                     head_perm_flag=best[:, :2].contiguous(), vid0=0, num_frame=F_, frame_size=P_).float()
             out["prescaled_rel_l2_vs_default_kernel"] = round(((o[:, :2].float() - ob).norm() / ob.norm()).item(), 6)
             del ob
 
-    if rank == 0 and world == 1 and not fp8 and not a.no_ab and a.workload == "hy720p" and a.variant == 0 and a.chunks == 1:
+    if a.full and rank == 0 and world == 1 and not fp8 and not a.no_ab and a.workload == "hy720p" and a.variant == 0 and a.chunks == 1:
         # In-run calibration: the other schedules of the library — among them the FROZEN reference schedule (variant 6: the two-phase
         # body with the round-1 softmax and operand fetch) — timed beside the default in this process, on this box, same inputs:
         # `default_ms / frozen_ms` shows a schedule gain whatever clock the box settles at.  Attention kernel only, HIP events,
@@ -638,6 +666,7 @@ def main():
             "prepass": "per-head amax + quantise with fused head placement and per-tile V transpose (reads 3 x, writes 1.5 x one bf16 tensor)",
             "accuracy": "tests/test_gpu_fp8.py: rel. L2 5 % vs the fp32 oracle on randn inputs (2.2 % vs the oracle on dequantised inputs)",
         }
+    if a.full and rank == 0 and fp8:
         # accuracy on THIS workload against the bf16 kernel (two heads: a frame-major and a token-major one)
         ob = nat.band_attention(q[:, :2].contiguous(), k[:, :2].contiguous(), v[:, :2].contiguous(), mask,
                                 head_perm_flag=best[:, :2].contiguous(), vid0=0, num_frame=F_, frame_size=P_).float()
@@ -646,7 +675,7 @@ def main():
         out["fp8"]["psnr_db_vs_bf16_kernel_this_workload"] = round((20.0 * torch.log10(ob.abs().max() / df.pow(2).mean().sqrt())).item(), 2)
         del ob, df
 
-    if world == 1 and not fp8 and a.workload == "hy720p" and D == 128:
+    if a.full and world == 1 and not fp8 and a.workload == "hy720p" and D == 128:
         # BASELINE.json configs[4] beside the bf16 headline: the same layer-call with e4m3 QK^T / PV (python bench.py --dtype fp8 is
         # the full line).  Attention only (pre-pass + kernel), HIP events, mean of 3 after one warm-up.
         try:
@@ -678,7 +707,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             out["fp8_hy720p"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
 
-    if world == 1 and not fp8 and a.workload == "hy720p" and not a.no_ab and a.variant == 0:
+    if a.full and world == 1 and not fp8 and a.workload == "hy720p" and not a.no_ab and a.variant == 0:
         # the same kernel on the reference's other SVG1 geometries (production masks of svg/models/{wan,cog}/utils.py, alternating
         # spatial / temporal heads, the processors' default path — plain q — unless --prescaled): Wan 2.1 720p and CogVideoX-v1.5 (head_dim 64)
         try:
@@ -719,7 +748,7 @@ def main():
         torch.cuda.empty_cache()
 
     # ---- extras on rank 0 at N = 1: dense comparator on the same GPU, CPU baseline ----
-    if world == 1 and not a.no_dense:
+    if a.full and world == 1 and not a.no_dense:
         dmask = nat.BandMask(real_len=V + L, band=S + 1, colfull_lo=0, colfull_hi=0, rowfull_lo=0, rowfull_hi=0)
         dense_call = (lambda: nat.band_attention_fp8(q, k, v, dmask, out=o)) if fp8 else \
             (lambda: nat.band_attention(q, k, v, dmask, variant=a.variant, out=o))
@@ -758,8 +787,8 @@ def main():
             out["dense_same_gpu"]["speedup_sparse_vs_torch_sdpa"] = round(sms / ms_step, 3)
         except Exception as e:  # noqa: BLE001
             out["dense_same_gpu"]["torch_sdpa_error"] = str(e)[:200]
-    extras_full = a.workload == "hy720p" and a.extras == "auto"
-    extras_small = a.extras == "small"
+    extras_full = a.full and a.workload == "hy720p" and a.extras == "auto"
+    extras_small = a.full and a.extras == "small"
     failed_extras = []          # an extras block that raises is reported in the line AND fails the run (exit code 3 after the line is printed)
     if world == 1 and not a.no_svg2 and (extras_full or extras_small):
         # BASELINE.json configs[2]: one SVG2 / SAP layer-call of Wan 2.1 720p (k-means, block map, variable-block attention)
@@ -828,7 +857,7 @@ def main():
             out["hbm_kernels"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
             failed_extras.append("hbm_kernels")
         torch.cuda.empty_cache()
-    if world > 1 and not a.no_step and not fp8:
+    if a.full and world > 1 and not a.no_step and not fp8:
         # BASELINE.json configs[3] at N > 1: the denoise step token-sharded over the ranks (bench_step.py: tokens/N for norms, GEMMs,
         # prologue and glue, heads/N for the attention, all-to-all exchanges either side of it, one all-gather of the hidden states per
         # step).  Every rank takes part; rank 0 reports (the step time is the MAX over ranks).
@@ -861,9 +890,9 @@ def main():
             if rank == 0:
                 out["denoise_step_wan720p_svg2"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
             raise
-    if world == 1 and not a.no_cpu:
+    if a.full and world == 1 and not a.no_cpu:
         out["cpu_baseline"] = cpu_baseline(H, D, S)
-    elif rank == 0:
+    elif a.full and rank == 0:
         out["cpu_baseline"] = None
 
     if rank == 0:

@@ -26,7 +26,7 @@ def _last_json(out: str):
 def one_rank_line():
     """the one-rank `bench.py --workload tiny` line, run once per module: the reference `output_checksum` of the N-rank runs (the inputs are
     seeded per global head, so every world size must leave the same bytes) — a fixture, so that any test of this module runs alone or in any order"""
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1", "--no-cpu"],
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1", "--full", "--no-cpu"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     return _last_json(r.stdout)
@@ -43,10 +43,42 @@ def test_bench_single_gpu_json_line(one_rank_line):
     assert len(d["output_checksum"]) == 16
 
 
+FULL_ONLY_KEYS = {"cpu_baseline", "dense_same_gpu", "same_box_ab", "fp8_hy720p", "svg1_other_models", "svg2_wan720p", "denoise_step_hy720p",
+                  "denoise_step_wan720p_svg2", "hbm_kernels"}
+
+
+def test_bench_plain_line_and_dump_outputs(one_rank_line, tmp_path):
+    """a plain run (no --full) times the steps and nothing else; --dump-outputs writes the last step's output, and those bytes are the
+    ones `output_checksum` digests — the same checksum as the --full run of the fixture (same seeded inputs).  A second plain run
+    dumps the same arrays bit for bit."""
+    import numpy as np
+
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1", "--dump-outputs",
+                            str(tmp_path / run)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+    for name in ("attn_out.npy", "sample_mse.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)), name
+    d = _last_json(r.stdout)
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(d) and not FULL_ONLY_KEYS & set(d)
+    assert d["metric"] == one_rank_line["metric"] and d["unit"] == "TFLOP/s" and d["dtype"] == "bf16" and d["steps"] == 3
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["clock"] is None
+    assert d["output_checksum"] == one_rank_line["output_checksum"]
+    o = np.load(tmp_path / "b" / "attn_out.npy")
+    mse = np.load(tmp_path / "b" / "sample_mse.npy")
+    assert o.dtype == np.float32 and o.shape == (4, 5 * 600 + 256, 128) and mse.dtype == np.float32 and mse.shape == (2, 4)
+    assert np.isfinite(o).all() and np.isfinite(mse).all()
+    bits = (o.view(np.uint32) >> 16).astype(np.uint16).view(np.int16).astype(np.int64)   # the bf16 output, exact in float32
+    acc = 0
+    for h in range(bits.shape[0]):
+        acc = (acc * 1000003 + int((bits[h] * (np.arange(bits.shape[-1]) + 1)).sum()) + 31 * int(bits[h].sum())) % (1 << 64)
+    assert f"{acc:016x}" == d["output_checksum"]
+
+
 def test_bench_two_rank_control_flow_smoke(one_rank_line):
     env = dict(os.environ, SVG_BENCH_SMOKE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29541", str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "tiny"]
+           "--master-port", "29541", str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "tiny", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = _last_json(r.stdout)
@@ -80,7 +112,7 @@ def test_bench_two_rank_watchdog_falls_back(one_rank_line):
 
 
 def test_bench_fp8_line():
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1", "--no-cpu",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1", "--full", "--no-cpu",
                         "--dtype", "fp8"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -208,7 +240,7 @@ def test_bench_hbm_measure_small():
 
 def test_bench_line_with_extras_has_no_error_key():
     """bench.py with every extras block switched on (reduced geometries): exit code 0 and no "error" key anywhere in the line."""
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1", "--no-cpu",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1", "--full", "--no-cpu",
                         "--extras", "small"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:] + r.stderr[-1500:])
     d = _last_json(r.stdout)
@@ -229,7 +261,7 @@ def test_bench_line_with_extras_has_no_error_key():
 def test_bench_exits_nonzero_when_an_extras_block_raises():
     """a failing extras block must not vanish silently: the line still carries the error string, and the exit code is 3."""
     env = dict(os.environ, SVG_BENCH_TEST_BREAK_EXTRAS="1")
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "tiny", "--steps", "1", "--warmup", "1", "--no-cpu",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "tiny", "--steps", "1", "--warmup", "1", "--full", "--no-cpu",
                         "--extras", "small", "--no-step"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 3, (r.returncode, r.stderr[-1500:])
     d = _last_json(r.stdout)

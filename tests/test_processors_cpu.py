@@ -159,7 +159,7 @@ def test_switch_generator_follows_seeding():
 
 def test_token_reorder_helpers_match_the_reference():
     """`*_token_reorder_to_token_major / _frame_major` of svg/models/{hyvideo,wan,cog,cosmos}/placement.py: in place on every head, text
-    last (first for CogVideoX); the reference's own torch helpers are run beside them when /root/reference is there (this container)."""
+    last (first for CogVideoX); the CogVideoX pair is also held against what the reference's own torch helpers returned (golden vectors)."""
     import importlib
     import sys
     import types
@@ -178,22 +178,16 @@ def test_token_reorder_helpers_match_the_reference():
         assert to_tok(t, ctx, F_ * P_, F_, P_) is t                      # in place, returns its argument
         x0 = x[:, :, : F_ * P_].contiguous() if not text_first else x[:, :, ctx:].contiguous()
         assert torch.equal(to_frm(to_tok(x0.clone(), 0, F_ * P_, F_, P_), 0, F_ * P_, F_, P_), x0)     # fix_len == 0 works here
-    ref_root = Path("/root/reference")
-    if ref_root.exists():       # the reference's own helpers (torch only; its module imports triton, which this image has)
-        spec = importlib.util.spec_from_file_location("_ref_cog_placement", ref_root / "svg/models/cog/placement.py")
-        ref = importlib.util.module_from_spec(spec)
-        try:
-            spec.loader.exec_module(ref)
-        except Exception:
-            ref = None
-        if ref is not None:
-            from svg.models.cog import placement as mine
+    # the reference's own helpers, executed on a seeded input by tests/golden/make_golden_placement.py
+    import numpy as np
 
-            x = torch.randn(1, 2, F_ * P_ + ctx, 4)
-            assert torch.equal(mine.token_reorder_to_token_major(x.clone(), ctx, F_ * P_, F_, P_),
-                               ref.token_reorder_to_token_major(x.clone(), ctx, F_ * P_, F_, P_))
-            assert torch.equal(mine.token_reorder_to_frame_major(x.clone(), ctx, F_ * P_, F_, P_),
-                               ref.token_reorder_to_frame_major(x.clone(), ctx, F_ * P_, F_, P_))
+    from svg.models.cog import placement as mine
+
+    gold = np.load(Path(__file__).resolve().parent / "golden" / "placement_golden.npz", allow_pickle=False)
+    assert gold["geometry"].tolist() == [F_, P_, ctx]
+    x = torch.from_numpy(gold["x"])
+    assert torch.equal(mine.token_reorder_to_token_major(x.clone(), ctx, F_ * P_, F_, P_), torch.from_numpy(gold["cog_to_token_major"]))
+    assert torch.equal(mine.token_reorder_to_frame_major(x.clone(), ctx, F_ * P_, F_, P_), torch.from_numpy(gold["cog_to_frame_major"]))
 
 
 def test_wan_bsr_backend_helpers_layout(monkeypatch):

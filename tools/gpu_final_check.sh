@@ -3,7 +3,7 @@
 tag=${1:-r04zx}; O=gpurun_out/$tag; mkdir -p $O
 timeout 1500 python -m pytest tests -q -m gpu > $O/pytest_gpu.txt 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.txt; tail -3 $O/pytest_gpu.txt
 timeout 400 python tools/clock_by_variant.py 6 2>&1 | grep -v amdgpu.ids | tee $O/clock_by_variant.txt
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 python - <<PY
 import json
 d=json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

@@ -14,7 +14,7 @@ if has tests; then
 fi
 if has bench; then
   t1=$(date +%s)
-  timeout 1200 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$? $(( $(date +%s) - t1 )) s"; tail -2 $O/bench.err
+  timeout 1200 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$? $(( $(date +%s) - t1 )) s"; tail -2 $O/bench.err
   python3 - "$O" <<'PY'
 import json, sys
 O = sys.argv[1]

@@ -17,11 +17,11 @@ PORT=29600
 for N in $NS; do
   PORT=$((PORT + 2))
   if [ "$N" = 1 ]; then
-    python bench.py --gpus 1 --steps 10 --warmup 3 --no-svg2 --no-hbm > "$OUT/bench_$N.json" 2> "$OUT/bench_$N.err"
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full --no-svg2 --no-hbm > "$OUT/bench_$N.json" 2> "$OUT/bench_$N.err"
     python bench_step.py --steps 3 --warmup 1 > "$OUT/step_$N.json" 2> "$OUT/step_$N.err"
     python bench_step.py --model wan720p --steps 2 --warmup 1 > "$OUT/step_wan_$N.json" 2> "$OUT/step_wan_$N.err"
   else
-    python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus "$N" --steps 10 --warmup 3 \
+    python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus "$N" --steps 10 --warmup 3 --full \
       > "$OUT/bench_$N.json" 2> "$OUT/bench_$N.err"
     python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port $((PORT + 1)) bench_step.py --gpus "$N" --steps 3 --warmup 1 \
       > "$OUT/step_$N.json" 2> "$OUT/step_$N.err"
