@@ -401,6 +401,36 @@ int svg_qk_norm_rope_transpose_qscale(const void* q_in, const void* k_in, void* 
                                       const float* cos_or_real, const float* sin_or_imag, int32_t rope_lo, int32_t rope_hi,
                                       float q_scale, void* stream);
 
+/* Joint (MMDiT) form of svg_qk_norm_rope_transpose: two streams with their own projections and norms meet in ONE sequence.  Segment i
+ * fills joint rows [sum(rows[0..i)), sum(rows[0..i])) of the head-major outputs [bsz, H, sum(rows), D] from its own token-major sources
+ * [bsz, rows, H * D] with its own norm (norm_kind / weights / eps as in svg_qk_norm_rope, weights and biases of the tensor dtype, NULL =
+ * ones / zeros); RoPE applies to JOINT positions [rope_lo, rope_hi) with table row (position - rope_lo); q_scale folds into the last
+ * rounding of q as in svg_qk_norm_rope_transpose_qscale; v is a plain transpose.  One launch; n_seg 1 or 2.
+ * Bit-identical to svg_qk_norm_rope_transpose_qscale per segment (with the rope rows that fall into it) plus the plain transpose of v,
+ * concatenated along the rows.
+ * ref: replaces the text-stream projection transposes, norm_added_q / norm_added_k and the three `torch.cat` of
+ *      svg/models/hyvideo/attention.py:288-306 (get_encoder_condition_and_concat), after the video stream's :268-286.
+ * Any output may be NULL (that tensor is not produced); every segment with rows > 0 supplies exactly the inputs whose outputs are given
+ * (a segment with rows = 0 reads nothing and may pass NULL).  SVG_ERR_BAD_ARG: n_seg outside {1, 2}, an input without its output or the
+ * reverse, an input equal to an output, rows < 0, a total of 0 or above INT32_MAX / (H * D), a norm / rope kind outside 0..2, a RoPE
+ * range outside [0, total], q_scale <= 0.  SVG_ERR_UNSUPPORTED: D outside {32, 64, 128, 256}, a dtype other than bf16 / fp16. */
+typedef struct svg_prologue_segment {
+    const void* q_in;                  /* token-major [bsz, rows, H * D] of this stream */
+    const void* k_in;
+    const void* v_in;
+    int32_t rows;
+    int32_t norm_kind;                 /* 0 none / 1 rms / 2 layer, as svg_qk_norm_rope */
+    const void* q_weight;
+    const void* q_bias;
+    const void* k_weight;
+    const void* k_bias;
+    float eps;
+} svg_prologue_segment_t;
+
+int svg_qk_norm_rope_transpose_joint(const svg_prologue_segment_t* seg, int32_t n_seg, void* q_out, void* k_out, void* v_out,
+                                     int32_t bsz, int32_t H, int32_t D, int32_t dtype, int32_t rope_kind, const float* cos_or_real,
+                                     const float* sin_or_imag, int32_t rope_lo, int32_t rope_hi, float q_scale, void* stream);
+
 /* The Wan 2.1 prologue in ONE pass (round 6): RMSNorm across ALL heads in the reference's Triton form (svg_rmsnorm_forward's arithmetic over
  * the H * D row) -> rotary embedding of positions [rope_lo, rope_hi) -> head-major transpose for q and k, and the plain transpose of v, in one
  * launch.  Replaces, bit for bit, svg_rmsnorm_forward(q), svg_rmsnorm_forward(k), svg_qk_norm_rope_transpose(q, k, norm 0, rope), the transpose

@@ -54,6 +54,86 @@ __device__ __forceinline__ auto scaled_round(float v, float oscale) {
     return E::from_float(t);
 }
 
+// The arithmetic of one lane's 8 channels of one (batch, head, position) row: normalisation over the LPR lanes of the row, rotary
+// embedding (rope = kRopeNone for a position outside the rotated range), and the last rounding with q's factor folded in — the statements of
+// qk_prologue_kernel's inner loop, which keeps its own copy: routed through this function its code generation changes (branch structure,
+// registers) and it is the kernel every existing caller runs.  tests/test_gpu_joint_prologue.py holds the two to the same bits.
+template <typename E, int LPR, int D>
+__device__ __forceinline__ typename E::v8 norm_rope_round(float (&x)[8], int norm, const float (&w)[8], const float (&bs)[8], float eps,
+                                                          int rope, const float (&cs)[8], const float (&sn)[8], float oscale) {
+    if (norm == kNormRms) {
+        // diffusers RMSNorm / the reference's "replica": fp32 variance, normalised value rounded to the tensor
+        // dtype, THEN multiplied by the weight (rounded again)
+        float ss = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) ss += x[j] * x[j];
+        ss = group_sum<LPR>(ss);
+        const float inv = 1.0f / sqrtf(ss / (float)D + eps);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float n = E::to_float(E::from_float(x[j] * inv));
+            x[j] = E::to_float(E::from_float(w[j] * n));
+        }
+    } else if (norm == kNormLayer) {
+        // torch layer_norm: fp32 statistics (biased variance), one rounding at the end
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s += x[j];
+        const float mean = group_sum<LPR>(s) / (float)D;
+        float vs = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) vs += (x[j] - mean) * (x[j] - mean);
+        const float inv = 1.0f / sqrtf(group_sum<LPR>(vs) / (float)D + eps);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = E::to_float(E::from_float((x[j] - mean) * inv * w[j] + bs[j]));
+    }
+    typename E::v8 out;
+    if (rope == kRopeCosSin) {
+        // out = x * cos + rotate(x) * sin in fp32, rotate(x)[2i] = -x[2i+1], rotate(x)[2i+1] = x[2i]
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float a = x[2 * i], bq = x[2 * i + 1];
+            out[2 * i] = scaled_round<E>(a * cs[2 * i] + (-bq) * sn[2 * i], oscale);
+            out[2 * i + 1] = scaled_round<E>(bq * cs[2 * i + 1] + a * sn[2 * i + 1], oscale);
+        }
+    } else if (rope == kRopeComplex) {
+        // (x[2i] + i x[2i+1]) * (fr + i fi) in fp64 (the reference multiplies complex128 by complex64)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const double a = (double)x[2 * i], bq = (double)x[2 * i + 1];
+            const double fr = (double)cs[i], fi = (double)sn[i];
+            out[2 * i] = E::from_double((a * fr - bq * fi) * (double)oscale);
+            out[2 * i + 1] = E::from_double((a * fi + bq * fr) * (double)oscale);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) out[j] = scaled_round<E>(x[j], oscale);
+    }
+    return out;
+}
+
+// The rotary table values of one lane (8 channels starting at c * 8) for table row r: cos / sin, or (complex) 4 (real, imag) pairs;
+// cos = 1, sin = 0 where the position is not rotated
+template <int D>
+__device__ __forceinline__ void load_rope_row(bool rot, int rope, const float* tc, const float* ts, size_t r, int c, float (&cs)[8],
+                                              float (&sn)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) cs[j] = 1.f, sn[j] = 0.f;
+    if (!rot) return;
+    if (rope == kRopeCosSin) {
+        const f32x4* pc = (const f32x4*)(tc + r * D + c * 8);
+        const f32x4* ps = (const f32x4*)(ts + r * D + c * 8);
+        const f32x4 c0 = pc[0], c1 = pc[1], s0 = ps[0], s1 = ps[1];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cs[j] = c0[j], cs[4 + j] = c1[j], sn[j] = s0[j], sn[4 + j] = s1[j];
+    } else {
+        const f32x4 fr = *(const f32x4*)(tc + r * (D / 2) + c * 4);
+        const f32x4 fi = *(const f32x4*)(ts + r * (D / 2) + c * 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cs[j] = fr[j], sn[j] = fi[j];
+    }
+}
+
 // One lane = 8 consecutive channels of one (batch, head, position) row; a wave covers 64 / (D / 8) consecutive positions;
 // the workgroup (4 waves) walks over all heads of Q and then of K for its positions, kUnroll rows in flight per lane.
 template <typename T, int D>
@@ -200,6 +280,128 @@ static int launch_prologue(const PrologueParams& p, int bsz, int D, int dtype, h
     if (dtype == SVG_DTYPE_BF16) return launch_prologue_t<__bf16>(p, bsz, D, st);
     if (dtype == SVG_DTYPE_F16) return launch_prologue_t<_Float16>(p, bsz, D, st);
     return SVG_ERR_UNSUPPORTED;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Joint (MMDiT) prologue: up to two token-major streams with their own norms meet in ONE head-major sequence — segment 0 fills joint rows
+// [0, rows0), segment 1 rows [rows0, rows0 + rows1) — with q and k normalised and rotated (joint positions [rope_lo, rope_hi)) and v
+// transposed, in one launch.  The layout and arithmetic of qk_prologue_kernel (norm_rope_round): the result equals the per-segment calls of
+// svg_qk_norm_rope_transpose_qscale concatenated along the rows, bit for bit.  A segment boundary may fall inside a wave: every lane picks
+// its segment (source, source row, norm) from its own position — the LPR lanes of one row always agree, so the norm's shuffles stay inside
+// one branch.  v goes through unchanged (a copy, not a rounding).  HBM traffic: each of q, k, v read once and written once.
+// ref: svg/models/hyvideo/attention.py:288-306 (get_encoder_condition_and_concat: text projections, norm_added_q / _k, three torch.cat).
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct JointParams {
+    svg_prologue_segment_t seg[2];   // seg[1].rows == 0 when there is one segment
+    void* q_out;                     // [bsz, H, S, D], S = seg[0].rows + seg[1].rows; each may be null (that tensor is not produced)
+    void* k_out;
+    void* v_out;
+    int H, S;
+    int rope;
+    const float* cs;
+    const float* sn;
+    int rope_lo, rope_hi;
+    float q_scale;
+};
+
+template <typename T, int D>
+__global__ __launch_bounds__(256) void joint_prologue_kernel(JointParams p) {
+    using E = Elt<T>;
+    using V8 = typename E::v8;
+    constexpr int LPR = D / 8;
+    constexpr int RPW = 64 / LPR;
+    constexpr int kUnroll = 4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int sub = lane / LPR, c = lane - sub * LPR;
+    const int pos = (blockIdx.x * 4 + wave) * RPW + sub;
+    const int b = blockIdx.y;
+    const bool valid = pos < p.S;
+    const int spos = valid ? pos : 0;   // invalid lanes load row 0 and store nothing (the shuffles need every lane)
+    // the lane's segment, selected field by field (no dynamic index into the kernel arguments)
+    const bool second = spos >= p.seg[0].rows;
+    const int srows = second ? p.seg[1].rows : p.seg[0].rows;
+    const int srow = second ? spos - p.seg[0].rows : spos;
+    const int norm = second ? p.seg[1].norm_kind : p.seg[0].norm_kind;
+    const float eps = second ? p.seg[1].eps : p.seg[0].eps;
+
+    const bool rot = p.rope != kRopeNone && pos >= p.rope_lo && pos < p.rope_hi;
+    float cs[8], sn[8];
+    load_rope_row<D>(rot, p.rope, p.cs, p.sn, (size_t)(pos - p.rope_lo), c, cs, sn);
+
+    const size_t hstride = (size_t)p.S * D;
+    const size_t out_off = (((size_t)b * p.H) * p.S + spos) * D + c * 8;
+    // token-major [bsz, rows, H, D] source of the segment: the heads of one position are D apart
+    const size_t in_off = (((size_t)b * srows + srow) * p.H) * D + c * 8;
+    const int H = p.H;
+
+    auto run = [&](T* out, const void* src_a, const void* src_b, const void* wa, const void* wb, const void* ba, const void* bb,
+                   const float oscale) {
+        const T* wgt = (const T*)(second ? wb : wa);
+        const T* bias = (const T*)(second ? bb : ba);
+        float w[8], bs[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) w[j] = 1.f, bs[j] = 0.f;
+        if (norm != kNormNone) {
+            if (wgt) {
+                const V8 wv = *(const V8*)(wgt + c * 8);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) w[j] = E::to_float(wv[j]);
+            }
+            if (bias) {
+                const V8 bv = *(const V8*)(bias + c * 8);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) bs[j] = E::to_float(bv[j]);
+            }
+        }
+        T* row0 = out + out_off;
+        const T* in0 = (const T*)(second ? src_b : src_a) + in_off;
+        for (int h0 = 0; h0 < H; h0 += kUnroll) {
+            V8 xin[kUnroll];
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u)   // (heads past H re-read the last head; nothing is stored for them)
+                xin[u] = *(const V8*)(in0 + (size_t)min(h0 + u, H - 1) * D);
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u) {
+                float x[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) x[j] = E::to_float(xin[u][j]);
+                const V8 o = norm_rope_round<E, LPR, D>(x, norm, w, bs, eps, rot ? p.rope : kRopeNone, cs, sn, oscale);
+                if (valid && h0 + u < H) *(V8*)(row0 + (size_t)(h0 + u) * hstride) = o;
+            }
+        }
+    };
+    const svg_prologue_segment_t &A = p.seg[0], &B = p.seg[1];
+    if (p.q_out) run((T*)p.q_out, A.q_in, B.q_in, A.q_weight, B.q_weight, A.q_bias, B.q_bias, p.q_scale);
+    if (p.k_out) run((T*)p.k_out, A.k_in, B.k_in, A.k_weight, B.k_weight, A.k_bias, B.k_bias, 1.f);
+    if (p.v_out) {   // plain transpose
+        T* row0 = (T*)p.v_out + out_off;
+        const T* in0 = (const T*)(second ? B.v_in : A.v_in) + in_off;
+        for (int h0 = 0; h0 < H; h0 += kUnroll) {
+            V8 xin[kUnroll];
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u) xin[u] = *(const V8*)(in0 + (size_t)min(h0 + u, H - 1) * D);
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u)
+                if (valid && h0 + u < H) *(V8*)(row0 + (size_t)(h0 + u) * hstride) = xin[u];
+        }
+    }
+}
+
+template <typename T>
+static int launch_joint_t(const JointParams& p, int bsz, int D, hipStream_t st) {
+    auto go = [&](auto d_c) -> int {
+        constexpr int DD = decltype(d_c)::value;
+        constexpr int RPB = 4 * (64 / (DD / 8));
+        hipLaunchKernelGGL((joint_prologue_kernel<T, DD>), dim3((p.S + RPB - 1) / RPB, bsz), dim3(256), 0, st, p);
+        return launch_status();
+    };
+    switch (D) {
+        case 32: return go(std::integral_constant<int, 32>{});
+        case 64: return go(std::integral_constant<int, 64>{});
+        case 128: return go(std::integral_constant<int, 128>{});
+        case 256: return go(std::integral_constant<int, 256>{});
+        default: return SVG_ERR_UNSUPPORTED;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -463,6 +665,48 @@ extern "C" int svg_qk_norm_rope_transpose(const void* q_in, const void* k_in, vo
                                           int32_t rope_lo, int32_t rope_hi, void* stream) {
     return svg_qk_norm_rope_transpose_qscale(q_in, k_in, q_out, k_out, bsz, Hq, Hkv, S, D, dtype, norm_kind, q_weight, q_bias,
                                              k_weight, k_bias, eps, rope_kind, cos_or_real, sin_or_imag, rope_lo, rope_hi, 1.f, stream);
+}
+
+extern "C" int svg_qk_norm_rope_transpose_joint(const svg_prologue_segment_t* seg, int32_t n_seg, void* q_out, void* k_out, void* v_out,
+                                                int32_t bsz, int32_t H, int32_t D, int32_t dtype, int32_t rope_kind,
+                                                const float* cos_or_real, const float* sin_or_imag, int32_t rope_lo, int32_t rope_hi,
+                                                float q_scale, void* stream) {
+    if (!seg || n_seg < 1 || n_seg > 2) return SVG_ERR_BAD_ARG;
+    if (!q_out && !k_out && !v_out) return SVG_ERR_BAD_ARG;
+    if (bsz <= 0 || H <= 0 || !(q_scale > 0.f)) return SVG_ERR_BAD_ARG;
+    if (rope_kind < 0 || rope_kind > 2) return SVG_ERR_BAD_ARG;
+    int64_t total = 0;
+    const void* outs[3] = {q_out, k_out, v_out};
+    for (int i = 0; i < n_seg; ++i) {
+        const svg_prologue_segment_t& s = seg[i];
+        if (s.rows < 0 || s.norm_kind < 0 || s.norm_kind > 2) return SVG_ERR_BAD_ARG;
+        const void* ins[3] = {s.q_in, s.k_in, s.v_in};
+        for (int t = 0; t < 3; ++t) {
+            // an input without its output, or (rows to read) an output without its input
+            if ((ins[t] && !outs[t]) || (outs[t] && !ins[t] && s.rows > 0)) return SVG_ERR_BAD_ARG;
+            for (int o = 0; o < 3; ++o)   // the layouts differ: not an in-place operation
+                if (ins[t] && outs[o] && ins[t] == outs[o]) return SVG_ERR_BAD_ARG;
+        }
+        total += s.rows;
+    }
+    if (total <= 0 || total > (int64_t)0x7fffffff / ((int64_t)H * D > 0 ? (int64_t)H * D : 1)) return SVG_ERR_BAD_ARG;
+    if (rope_kind != kRopeNone && (!cos_or_real || !sin_or_imag || rope_lo < 0 || rope_hi > total || rope_lo > rope_hi)) return SVG_ERR_BAD_ARG;
+    if (D != 32 && D != 64 && D != 128 && D != 256) return SVG_ERR_UNSUPPORTED;
+    if (dtype != SVG_DTYPE_BF16 && dtype != SVG_DTYPE_F16) return SVG_ERR_UNSUPPORTED;
+    if (bsz > 65535) return SVG_ERR_UNSUPPORTED;
+    JointParams p;
+    p.seg[0] = seg[0];
+    if (n_seg == 2) {
+        p.seg[1] = seg[1];
+    } else {
+        p.seg[1] = svg_prologue_segment_t{};
+        p.seg[1].rows = 0;
+    }
+    p.q_out = q_out, p.k_out = k_out, p.v_out = v_out, p.H = H, p.S = (int)total;
+    p.rope = rope_kind, p.cs = cos_or_real, p.sn = sin_or_imag, p.rope_lo = rope_lo, p.rope_hi = rope_hi, p.q_scale = q_scale;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == SVG_DTYPE_BF16) return launch_joint_t<__bf16>(p, bsz, D, st);
+    return launch_joint_t<_Float16>(p, bsz, D, st);
 }
 
 // Rows of a flat [m, n] tensor are independent: view it as [H, S, n] with the largest H in {16, 8, 4, 2, 1} dividing m so that

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from pathlib import Path
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
@@ -76,6 +76,12 @@ class ProfileDesc(C.Structure):
 _I32, _I64, _F32, _VP, _SZ = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
 
 
+class PrologueSegment(C.Structure):
+    """svg_prologue_segment_t (include/svg_attn.h): one stream of svg_qk_norm_rope_transpose_joint."""
+    _fields_ = [("q_in", C.c_void_p), ("k_in", C.c_void_p), ("v_in", C.c_void_p), ("rows", C.c_int32), ("norm_kind", C.c_int32),
+                ("q_weight", C.c_void_p), ("q_bias", C.c_void_p), ("k_weight", C.c_void_p), ("k_bias", C.c_void_p), ("eps", C.c_float)]
+
+
 class TensorStrides(C.Structure):
     """svg_tensor_strides_t: element strides of a [B, H, S, D] view whose last dimension is contiguous."""
     _fields_ = [("batch", C.c_int64), ("head", C.c_int64), ("row", C.c_int64)]
@@ -118,6 +124,8 @@ SIGNATURES = {
                                           _VP, _I32, _I32, C.c_float, _VP]),
     "svg_qk_norm_rope_transpose_qscale": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP,
                                                     C.c_float, _I32, _VP, _VP, _I32, _I32, C.c_float, _VP]),
+    "svg_qk_norm_rope_transpose_joint": (C.c_int, [C.POINTER(PrologueSegment), _I32, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP,
+                                                   _I32, _I32, C.c_float, _VP]),
     "svg_rmsnorm_rope_transpose": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _I32, C.c_float, _I32, _VP,
                                              _VP, _I32, _I32, C.c_float, _VP]),
     "svg_head_placement": (C.c_int, [_VP, _VP, _I32, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP]),
@@ -1031,6 +1039,59 @@ def qk_norm_rope_transpose(q_in, k_in, heads_q: int, heads_k: int, norm_kind: in
                                                  _ptr(k_bias), float(eps), int(rope_kind), _ptr(cos), _ptr(sin), int(rope_lo),
                                                  int(rope_hi), float(q_scale), _stream()), "svg_qk_norm_rope_transpose")
     return q_out, k_out
+
+
+class JointSegment(NamedTuple):
+    """One stream of qk_norm_rope_transpose_joint: token-major projections [bsz, rows, heads * D] (k / v may be None when no segment has
+    them) and the stream's own norm over head_dim (norm_kind 0 none / 1 rms / 2 layer; weights / biases [D] of the tensor dtype or None)."""
+    q: Optional[torch.Tensor]
+    k: Optional[torch.Tensor] = None
+    v: Optional[torch.Tensor] = None
+    norm_kind: int = 0
+    q_weight: Optional[torch.Tensor] = None
+    q_bias: Optional[torch.Tensor] = None
+    k_weight: Optional[torch.Tensor] = None
+    k_bias: Optional[torch.Tensor] = None
+    eps: float = 1e-6
+
+
+def qk_norm_rope_transpose_joint(segments: Sequence[JointSegment], heads: int, rope_kind: int = 0, cos=None, sin=None, rope_lo: int = 0,
+                                 rope_hi: Optional[int] = None, q_scale: float = 1.0, with_v: bool = True):
+    """Joint (MMDiT) prologue in one launch (svg_qk_norm_rope_transpose_joint): one or two token-major streams -> head-major
+    (q, k, v) [bsz, heads, sum(rows), D], segment i filling its rows in order, each with its own norm; RoPE on JOINT positions
+    [rope_lo, rope_hi) (tables [rope_hi - rope_lo, D], complex: [.., D / 2]); q_scale folded into q's last rounding; v transposed.
+    Bit-identical to qk_norm_rope_transpose per segment + the transpose of v, concatenated along the rows.  Outputs of tensors the
+    segments do not supply (and v when with_v is False) are None."""
+    lib = load()
+    segs = list(segments)
+    if not 1 <= len(segs) <= 2:
+        raise ValueError(f"qk_norm_rope_transpose_joint takes 1 or 2 segments, got {len(segs)}")
+    ref = segs[0].q if segs[0].q is not None else segs[0].k
+    bsz, _, HD = ref.shape
+    D = HD // heads
+    for sg in segs:
+        _dev(sg.q, sg.k, sg.v if with_v else None, sg.q_weight, sg.q_bias, sg.k_weight, sg.k_bias)
+        for t in (sg.q, sg.k, sg.v):
+            assert t is None or (t.dim() == 3 and t.shape[0] == bsz and t.shape[2] == HD and t.dtype == ref.dtype), "segment tensors disagree"
+    rows = [(sg.q if sg.q is not None else sg.k).shape[1] for sg in segs]
+    S = sum(rows)
+    mk = lambda on: torch.empty((bsz, heads, S, D), dtype=ref.dtype, device=ref.device) if on else None  # noqa: E731
+    q_out, k_out = mk(segs[0].q is not None), mk(segs[0].k is not None)
+    v_out = mk(with_v and segs[0].v is not None)
+    rope_hi = S if rope_hi is None else rope_hi
+    if rope_kind:
+        _dev(cos, sin)
+        cols = D // 2 if rope_kind == 2 else D
+        assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.shape == (rope_hi - rope_lo, cols) and sin.shape == cos.shape
+    arr = (PrologueSegment * len(segs))()
+    for a, sg, n in zip(arr, segs, rows):
+        a.q_in, a.k_in, a.v_in = _ptr(sg.q), _ptr(sg.k), _ptr(sg.v) if with_v else None
+        a.rows, a.norm_kind, a.eps = n, int(sg.norm_kind), float(sg.eps)
+        a.q_weight, a.q_bias, a.k_weight, a.k_bias = _ptr(sg.q_weight), _ptr(sg.q_bias), _ptr(sg.k_weight), _ptr(sg.k_bias)
+    _check(lib.svg_qk_norm_rope_transpose_joint(arr, len(segs), _ptr(q_out), _ptr(k_out), _ptr(v_out), bsz, heads, D, _dtype_code(ref),
+                                                int(rope_kind), _ptr(cos), _ptr(sin), int(rope_lo), int(rope_hi), float(q_scale), _stream()),
+           "svg_qk_norm_rope_transpose_joint")
+    return q_out, k_out, v_out
 
 
 def rmsnorm_rope_transpose(q_in, k_in, v_in, heads: int, q_weight=None, k_weight=None, eps: float = 1e-6, rope_kind: int = 0, cos=None,

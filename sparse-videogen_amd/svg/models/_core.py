@@ -561,3 +561,62 @@ def qkv_from_projections(query, key, value, heads: int, norm_q, norm_k, cos, sin
     if v is None:
         v, _ = _native.qk_norm_rope_transpose(value, None, heads, 0)
     return q, k, v
+
+
+def _seg_norm(norm_q, norm_k, D: int, dtype, device):
+    """(kind, q weight, q bias, k weight, k bias, eps) of one stream's QK norms for the joint prologue: both absent -> kind 0; both
+    recognised with the same kind and eps -> theirs; anything else -> None (the fused path does not apply)."""
+    if norm_q is None and norm_k is None:
+        return 0, None, None, None, None, 1e-6
+    dq, dk = _norm_desc(norm_q, D, dtype, device), _norm_desc(norm_k, D, dtype, device)
+    if dq is None or dk is None or dq[0] != dk[0] or dq[3] != dk[3]:
+        return None
+    return dq[0], dq[1], dq[2], dk[1], dk[2], dq[3]
+
+
+def joint_qkv_from_projections(video_qkv, text_qkv, heads: int, norm_q, norm_k, norm_added_q, norm_added_k, cos, sin, rope_lo: int,
+                               rope_hi: int, q_scale: float = 1.0, complex_pairs: bool = False):
+    """MMDiT joint prologue: the video stream's projection outputs (q, k, v) [bsz, S_v, heads * D] and the text stream's [bsz, T, heads * D]
+    -> head-major q, k, v [bsz, heads, S_v + T, D], rows [video, text], each stream with its own QK norm (text norms may be None: no norm),
+    RoPE on joint positions [rope_lo, rope_hi), q_scale folded into q's last rounding — ONE launch (svg_qk_norm_rope_transpose_joint).
+    Replaces qkv_from_projections on the video stream + the text stream's transposes / norm_added_q / norm_added_k + three torch.cat
+    (ref: hyvideo/attention.py:268-306).  None: not applicable (the conditions of qkv_from_projections) — the caller takes the staged path."""
+    ts = tuple(video_qkv) + tuple(text_qkv)
+    if len(ts) != 6 or not all(t.is_cuda for t in ts):
+        return None
+    _native.load()
+    if not all(t.dim() == 3 and t.is_contiguous() and t.dtype in (torch.bfloat16, torch.float16) for t in ts):
+        return None
+    vq, tq = video_qkv[0], text_qkv[0]
+    D = vq.shape[-1] // heads
+    if D not in _FAST_DIMS or D * heads != vq.shape[-1] or any(t.dtype != vq.dtype for t in ts):
+        return None
+    if any(t.shape != vq.shape for t in video_qkv) or any(t.shape != tq.shape for t in text_qkv) or tq.shape[0] != vq.shape[0] \
+            or tq.shape[2] != vq.shape[2]:
+        return None
+    nv = _seg_norm(norm_q, norm_k, D, vq.dtype, vq.device)
+    nt = _seg_norm(norm_added_q, norm_added_k, D, vq.dtype, vq.device)
+    if nv is None or nt is None:
+        return None
+    rk, tb = 0, (None, None)
+    if cos is not None:
+        tb = _tables(cos, sin, rope_hi - rope_lo, D // 2 if complex_pairs else D, vq.device)
+        if tb is None:
+            return None
+        rk = 2 if complex_pairs else 1
+    segs = [_native.JointSegment(*qkv, kind, qw, qb, kw, kb, eps) for qkv, (kind, qw, qb, kw, kb, eps) in ((video_qkv, nv), (text_qkv, nt))]
+    return _native.qk_norm_rope_transpose_joint(segs, heads, rk, tb[0], tb[1], rope_lo, rope_hi, q_scale=q_scale)
+
+
+def joined_rows(a: torch.Tensor, b: torch.Tensor) -> Optional[torch.Tensor]:
+    """`torch.cat([a, b], dim=1)` as a VIEW when b starts exactly where a ends in the same storage with the same strides (two adjacent row
+    slices of one [B, S, N] tensor, e.g. the single-stream blocks' `norm_hidden_states[:, :-T]` and `[:, -T:]`); None otherwise."""
+    if a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0] or a.shape[2] != b.shape[2]:
+        return None
+    if a.dtype != b.dtype or a.device != b.device or a.stride() != b.stride():
+        return None
+    if a.untyped_storage().data_ptr() != b.untyped_storage().data_ptr():
+        return None
+    if b.storage_offset() != a.storage_offset() + a.shape[1] * a.stride(1):
+        return None
+    return a.as_strided((a.shape[0], a.shape[1] + b.shape[1], a.shape[2]), a.stride(), a.storage_offset())

@@ -70,6 +70,12 @@ class _HunyuanProcessorBase:
     # tests/test_gpu_prescaled.py::test_prescaled_vs_reference_formulation_on_large_logits.  OFF by default since round 4 (parity first);
     # only when the fused HIP prologue applies (GPU tensors, head_dim 128); q never leaves the processor, so nothing outside sees it.
     prescale_q = False
+    # True: the joint sequence [video, text] is built without copies — double-stream blocks project the text stream and run ONE joint
+    # prologue launch (svg_qk_norm_rope_transpose_joint: both streams' norms, RoPE on the video rows, the head-major transposes) instead of
+    # the video prologue + get_encoder_condition_and_concat's three torch.cat; single-stream blocks take the two adjacent row slices the
+    # block passes as one view (_core.joined_rows) instead of torch.cat.  The text rows then get the HIP RMSNorm arithmetic (the video rows'
+    # and the reference's `_kernels` path) instead of the torch module's.  False: the staged path, bit for bit as before.
+    joint_prologue = True
     _valid_len_cache: dict = {}
 
     def __init__(self, layer_idx: int = 0):
@@ -124,6 +130,20 @@ class _HunyuanProcessorBase:
         cos, sin = image_rotary_emb
         return _core.qk_rope_inplace(query, key, cos, sin, 0, hi, norm_q=nq, norm_k=nk)
 
+    @time_logging_decorator("Level 2 - get_joint_prologue")
+    def get_joint_prologue(self, attn, query, key, value, image_rotary_emb, encoder_hidden_states, q_scale: float = 1.0):
+        """Double-stream blocks: text projections + get_transpose_norm_rope + get_encoder_condition_and_concat in one joint prologue
+        launch (_core.joint_qkv_from_projections); None when it does not apply (the caller takes the staged path)."""
+        if not (self.joint_prologue and self.fused_prologue and query.is_cuda):
+            return None
+        if getattr(attn, "add_q_proj", None) is None or encoder_hidden_states is None:
+            return None
+        text = (attn.add_q_proj(encoder_hidden_states), attn.add_k_proj(encoder_hidden_states), attn.add_v_proj(encoder_hidden_states))
+        cos, sin = image_rotary_emb if image_rotary_emb is not None else (None, None)
+        return _core.joint_qkv_from_projections((query, key, value), text, attn.heads, getattr(attn, "norm_q", None),
+                                                getattr(attn, "norm_k", None), getattr(attn, "norm_added_q", None),
+                                                getattr(attn, "norm_added_k", None), cos, sin, 0, query.shape[1], q_scale=q_scale)
+
     @time_logging_decorator("Level 2 - get_encoder_condition_and_concat")
     def get_encoder_condition_and_concat(self, attn, query, key, value, encoder_hidden_states, q_scale: float = 1.0):
         if getattr(attn, "add_q_proj", None) is not None and encoder_hidden_states is not None:
@@ -177,22 +197,28 @@ class _HunyuanProcessorBase:
 
             timestep = current_timestep()
         if getattr(attn, "add_q_proj", None) is None and encoder_hidden_states is not None:
-            hidden_states = torch.cat([hidden_states, encoder_hidden_states], dim=1)
+            # (the single-stream blocks pass two adjacent row slices of one tensor: joined as a view, no copy)
+            joined = _core.joined_rows(hidden_states, encoder_hidden_states) if self.joint_prologue else None
+            hidden_states = joined if joined is not None else torch.cat([hidden_states, encoder_hidden_states], dim=1)
         query, key, value = self.get_qkv(attn, hidden_states)
         q_scale = 1.0
         if self.prescale_q and self.fused_prologue and query.is_cuda and query.shape[-1] == attn.heads * 128 \
                 and query.dtype in (torch.bfloat16, torch.float16):
             q_scale = _core._native.softmax_q_scale(128)
-        fused = self.get_transpose_norm_rope(attn, query, key, value, image_rotary_emb, encoder_hidden_states, q_scale=q_scale)
-        if fused is not None:
-            query, key, value = fused
+        joint = self.get_joint_prologue(attn, query, key, value, image_rotary_emb, encoder_hidden_states, q_scale=q_scale)
+        if joint is not None:
+            query, key, value = joint
         else:
-            q_scale = 1.0   # the staged prologue (torch modules or the in-place HIP ops) delivers a plain q
-            query, key, value = self.get_transpose_qkv(attn, query, key, value)
-            if not self.get_fused_prologue(attn, query, key, image_rotary_emb, encoder_hidden_states):
-                query, key = self.get_qk_norm(attn, query, key)
-                query, key = self.get_rotary_emb(attn, query, key, image_rotary_emb, encoder_hidden_states)
-        query, key, value = self.get_encoder_condition_and_concat(attn, query, key, value, encoder_hidden_states, q_scale=q_scale)
+            fused = self.get_transpose_norm_rope(attn, query, key, value, image_rotary_emb, encoder_hidden_states, q_scale=q_scale)
+            if fused is not None:
+                query, key, value = fused
+            else:
+                q_scale = 1.0   # the staged prologue (torch modules or the in-place HIP ops) delivers a plain q
+                query, key, value = self.get_transpose_qkv(attn, query, key, value)
+                if not self.get_fused_prologue(attn, query, key, image_rotary_emb, encoder_hidden_states):
+                    query, key = self.get_qk_norm(attn, query, key)
+                    query, key = self.get_rotary_emb(attn, query, key, image_rotary_emb, encoder_hidden_states)
+            query, key, value = self.get_encoder_condition_and_concat(attn, query, key, value, encoder_hidden_states, q_scale=q_scale)
         cu_max_seqlens = self.get_cu_max_seqlen(attention_mask, query.device)
         self._q_prescaled = q_scale != 1.0
         try:
