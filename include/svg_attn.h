@@ -318,6 +318,22 @@ int svg_kmeans_loop_strided(const void* x, int64_t x_batch_stride, const void* c
                             int32_t* counts, int32_t* sorted_idx, void* centroids_out, int32_t* n_iters, int32_t B, int32_t N,
                             int32_t K, int32_t D, int32_t dtype, int32_t max_iters, float tol, void* workspace,
                             size_t workspace_bytes, void* stream);
+/* svg_kmeans_loop[_strided] with one stopping rule per GROUP of batches: the B batches form G = B / group groups of `group` consecutive
+ * batches (B % group == 0, group >= 1, otherwise SVG_ERR_BAD_ARG), e.g. the H heads of each video of a [cfg, H] batch.  Group g (batches
+ * [g * group, (g + 1) * group)) follows the rule of svg_kmeans_loop on its own batches only: it stops once the largest shift of ITS batches
+ * is < tol (a NaN shift never converges), and then keeps the labels / sizes / sorted indices of that iteration and the OLD centroids;
+ * another group's shifts never change its result.  n_iters: device int32 [G], the iterations each group's loop would have run.
+ * workspace: svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, group) (0 for a bad group).  With group == B the result is
+ * bit-identical to svg_kmeans_loop[_strided], which are these entry points with group = B (and the same workspace size). */
+size_t svg_kmeans_loop_grouped_workspace_bytes(int32_t B, int32_t N, int32_t K, int32_t D, int32_t group);
+int svg_kmeans_loop_grouped(const void* x, const float* xsq, const void* c_init, void* c_work_a, void* c_work_b, int32_t* labels,
+                            int32_t* counts, int32_t* sorted_idx, void* centroids_out, int32_t* n_iters, int32_t B, int32_t N, int32_t K,
+                            int32_t D, int32_t dtype, int32_t group, int32_t max_iters, float tol, void* workspace, size_t workspace_bytes,
+                            void* stream);
+int svg_kmeans_loop_grouped_strided(const void* x, int64_t x_batch_stride, const void* c_init, void* c_work_a, void* c_work_b,
+                                    int32_t* labels, int32_t* counts, int32_t* sorted_idx, void* centroids_out, int32_t* n_iters, int32_t B,
+                                    int32_t N, int32_t K, int32_t D, int32_t dtype, int32_t group, int32_t max_iters, float tol,
+                                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Top-p block selection.

@@ -402,51 +402,60 @@ static int run_kmeans_iter(const void* x, const float* xsq, const void* c_in, vo
     return run_kmeans_update<T, D>(x, c_in, c_out, labels, counts, sorted_idx, shift, B, N, K, ws, st, x_bs);
 }
 
-// ---- the Lloyd loop on the device (svg_kmeans_loop): commit of one iteration's result under the reference's stopping rule ----
-// state[0..1]: "the reference's loop has left" before iteration `it` (ping-pong by iteration parity: every thread of the commit
-// kernel reads the flag of the iterations before, one thread writes the flag for the next), state[2]: n_iters, state[3]: which
-// centroid buffer holds the result (0 initial, 1 / 2 the two work buffers).
+// ---- the Lloyd loop on the device (svg_kmeans_loop[_grouped]): commit of one iteration's result under the reference's stopping rule ----
+// The B batches form G stopping groups of `group` consecutive batches each (svg_kmeans_loop: one group of all B).  State words, G of
+// each kind: state[0 .. 2G): "the reference's loop has left" before iteration `it` (ping-pong by iteration parity: every thread of the
+// commit kernel reads the flags of the iteration before, one thread per group writes the flag for the next), state[2G + g]: n_iters of
+// group g, state[3G + g]: which centroid buffer holds group g's result (0 initial, 1 / 2 the two work buffers).  With G = 1 this is the
+// layout of the ungrouped loop: [flag0, flag1, n_iters, selector].
 __global__ __launch_bounds__(256) void kmeans_commit_kernel(const int32_t* __restrict__ labels, const int32_t* __restrict__ sorted_idx,
                                                             const int32_t* __restrict__ counts, int32_t* __restrict__ labels_r,
                                                             int32_t* __restrict__ sorted_r, int32_t* __restrict__ counts_r,
-                                                            const float* __restrict__ shift, int32_t* __restrict__ state, long long bn,
-                                                            long long bk, int B, float tol, int it, int sel_cur, int sel_out) {
-    const bool stopped = state[it & 1] != 0;
-    if (!stopped) {   // ref svg/kmeans_utils.py:716-733: the labels / sizes of the iteration the loop is in are the result
-        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < bn; i += (long long)gridDim.x * 256) {
-            labels_r[i] = labels[i];
-            sorted_r[i] = sorted_idx[i];
+                                                            const float* __restrict__ shift, int32_t* __restrict__ state, long long gn,
+                                                            long long gk, int group, float tol, int it, int sel_cur, int sel_out) {
+    const int G = gridDim.y, gy = blockIdx.y;   // blockIdx.y: the group whose rows this workgroup copies
+    const int32_t* stopped_in = state + (it & 1) * G;
+    if (stopped_in[gy] == 0) {   // ref svg/kmeans_utils.py:716-733: the labels / sizes of the iteration a group's loop is in are its result
+        const long long n0 = gy * gn, k0 = gy * gk;
+        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < gn; i += (long long)gridDim.x * 256) {
+            labels_r[n0 + i] = labels[n0 + i];
+            sorted_r[n0 + i] = sorted_idx[n0 + i];
         }
-        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < bk; i += (long long)gridDim.x * 256) counts_r[i] = counts[i];
+        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < gk; i += (long long)gridDim.x * 256) counts_r[k0 + i] = counts[k0 + i];
     }
-    if (blockIdx.x == 0 && threadIdx.x < 64) {
-        float mx = 0.f;
-        bool nan = false;   // fmaxf drops a NaN operand; the reference's `shift.max()` propagates it, and `NaN < tol` is False (:723)
-        for (int b = threadIdx.x; b < B; b += 64) {
-            const float sft = shift[b];
-            nan |= sft != sft;
-            mx = fmaxf(mx, sft);
-        }
-        mx = wave_max(mx);
-        nan = __builtin_amdgcn_ballot_w64(nan) != 0ull;
-        if (threadIdx.x == 0) {
-            const bool conv = !nan && mx < tol;   // `center_shift < tol` (:723): a NaN shift never converges, the loop runs to max_iters
-            if (!stopped) {
-                state[2] += 1;
-                state[3] = conv ? sel_cur : sel_out;   // converged: the OLD centroids are returned; otherwise the new ones become current
+    if (blockIdx.x == 0 && gy == 0) {   // the stopping rule, one wave per group (waves take groups w, w + 4, ...)
+        const int lane = threadIdx.x & 63;
+        for (int g = threadIdx.x >> 6; g < G; g += 4) {
+            float mx = 0.f;
+            bool nan = false;   // fmaxf drops a NaN operand; the reference's `shift.max()` propagates it, and `NaN < tol` is False (:723)
+            for (int b = g * group + lane; b < (g + 1) * group; b += 64) {
+                const float sft = shift[b];
+                nan |= sft != sft;
+                mx = fmaxf(mx, sft);
             }
-            state[(it + 1) & 1] = (stopped || conv) ? 1 : 0;
+            mx = wave_max(mx);
+            nan = __builtin_amdgcn_ballot_w64(nan) != 0ull;
+            if (lane == 0) {
+                const bool stopped = stopped_in[g] != 0;
+                const bool conv = !nan && mx < tol;   // `center_shift < tol` (:723): a NaN shift never converges, the loop runs to max_iters
+                if (!stopped) {
+                    state[2 * G + g] += 1;
+                    state[3 * G + g] = conv ? sel_cur : sel_out;   // converged: the OLD centroids are returned; otherwise the new ones become current
+                }
+                state[((it + 1) & 1) * G + g] = (stopped || conv) ? 1 : 0;
+            }
         }
     }
 }
 template <typename T>
 __global__ __launch_bounds__(256) void kmeans_select_kernel(const T* __restrict__ c0, const T* __restrict__ c1, const T* __restrict__ c2,
-                                                            T* __restrict__ out, const int32_t* __restrict__ state, long long n8) {
-    const int sel = state[3];
+                                                            T* __restrict__ out, const int32_t* __restrict__ sel_g, long long group_n8) {
+    const int sel = sel_g[blockIdx.y];   // blockIdx.y: the group (its rows are group_n8 8-element vectors)
     const T* src = sel == 0 ? c0 : (sel == 1 ? c1 : c2);
     using V8 = typename Elt<T>::v8;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long long)gridDim.x * 256)
-        ((V8*)out)[i] = ((const V8*)src)[i];
+    const long long o = blockIdx.y * group_n8;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < group_n8; i += (long long)gridDim.x * 256)
+        ((V8*)out)[o + i] = ((const V8*)src)[o + i];
 }
 
 }  // namespace svg
@@ -557,27 +566,34 @@ extern "C" int svg_kmeans_update(const void* x, const int32_t* labels, const voi
 }
 #undef SVG_KM_DISPATCH
 
-extern "C" size_t svg_kmeans_loop_workspace_bytes(int32_t B, int32_t N, int32_t K, int32_t D) {
+// scratch of svg_kmeans_loop_grouped: per-iteration scratch of svg_kmeans_iter + scratch labels / sorted indices / counts / shift of one
+// iteration + 4 state words per stopping group (one 256-byte block for up to 16 groups: the ungrouped loop's size)
+extern "C" size_t svg_kmeans_loop_grouped_workspace_bytes(int32_t B, int32_t N, int32_t K, int32_t D, int32_t group) {
     const size_t it = svg_kmeans_workspace_bytes(B, N, K, D);
-    if (it == 0) return 0;
-    // per-iteration scratch of svg_kmeans_iter + scratch labels / sorted indices / counts / shift of one iteration + the state words
+    if (it == 0 || group <= 0 || B % group != 0) return 0;
     const size_t a = ((size_t)B * N * 4 + 255) / 256 * 256, c = ((size_t)B * K * 4 + 255) / 256 * 256, sh = ((size_t)B * 4 + 255) / 256 * 256;
-    return (it + 255) / 256 * 256 + 2 * a + c + sh + 256;
+    const size_t st = ((size_t)(B / group) * 4 * sizeof(int32_t) + 255) / 256 * 256;
+    return (it + 255) / 256 * 256 + 2 * a + c + sh + st;
 }
 
-// svg_kmeans_loop (x_bs = N * D) and svg_kmeans_loop_strided
+extern "C" size_t svg_kmeans_loop_workspace_bytes(int32_t B, int32_t N, int32_t K, int32_t D) {
+    return B > 0 ? svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, B) : 0;
+}
+
+// svg_kmeans_loop (x_bs = N * D, group = B), svg_kmeans_loop_strided (group = B) and their grouped forms
 static int kmeans_loop_impl(const void* x, long long x_bs, const float* xsq, const void* c_init, void* c_work_a, void* c_work_b, int32_t* labels,
                             int32_t* counts, int32_t* sorted_idx, void* centroids_out, int32_t* n_iters, int32_t B, int32_t N,
-                            int32_t K, int32_t D, int32_t dtype, int32_t max_iters, float tol, void* workspace,
+                            int32_t K, int32_t D, int32_t dtype, int32_t group, int32_t max_iters, float tol, void* workspace,
                             size_t workspace_bytes, void* stream) {
     if (!x || !c_init || !c_work_a || !c_work_b || !labels || !counts || !sorted_idx || !centroids_out || !n_iters || !workspace)
         return SVG_ERR_BAD_ARG;   // (xsq may be NULL, see svg_kmeans_iter)
-    if (B <= 0 || N <= 0 || K <= 0 || max_iters <= 0) return SVG_ERR_BAD_ARG;
+    if (B <= 0 || N <= 0 || K <= 0 || max_iters <= 0 || group <= 0 || B % group != 0) return SVG_ERR_BAD_ARG;
     if (K > 8192 || (D != 64 && D != 128) || (dtype != SVG_DTYPE_BF16 && dtype != SVG_DTYPE_F16)) return SVG_ERR_UNSUPPORTED;
-    if (workspace_bytes < svg_kmeans_loop_workspace_bytes(B, N, K, D)) return SVG_ERR_WORKSPACE;
+    if (workspace_bytes < svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, group)) return SVG_ERR_WORKSPACE;
     if (c_init == c_work_a || c_init == c_work_b || c_work_a == c_work_b || centroids_out == c_work_a || centroids_out == c_work_b)
         return SVG_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
+    const int G = B / group;
     const size_t it_bytes = (svg_kmeans_workspace_bytes(B, N, K, D) + 255) / 256 * 256;
     const size_t a = ((size_t)B * N * 4 + 255) / 256 * 256, c = ((size_t)B * K * 4 + 255) / 256 * 256, sh = ((size_t)B * 4 + 255) / 256 * 256;
     char* w = (char*)workspace;
@@ -587,30 +603,37 @@ static int kmeans_loop_impl(const void* x, long long x_bs, const float* xsq, con
     int32_t* t_counts = (int32_t*)(w + it_bytes + 2 * a);
     float* t_shift = (float*)(w + it_bytes + 2 * a + c);
     int32_t* state = (int32_t*)(w + it_bytes + 2 * a + c + sh);
-    if (hipMemsetAsync(state, 0, 4 * sizeof(int32_t), st) != hipSuccess) return SVG_ERR_LAUNCH;
+    if (hipMemsetAsync(state, 0, (size_t)4 * G * sizeof(int32_t), st) != hipSuccess) return SVG_ERR_LAUNCH;
     const void* cur = c_init;
     int sel_cur = 0;
-    const long long bn = (long long)B * N, bk = (long long)B * K;
-    const unsigned grid = (unsigned)std::min<long long>(2048, (bn + 255) / 256);
+    const long long gn = (long long)group * N, gk = (long long)group * K;
+    // (G = 1: the grid of the ungrouped loop; more groups share about as many workgroups, a stopped group's return at once)
+    const dim3 grid((unsigned)std::min<long long>((2048 + G - 1) / G, (gn + 255) / 256), (unsigned)G);
     for (int it = 0; it < max_iters; ++it) {
         void* out = (it & 1) ? c_work_b : c_work_a;
         const int sel_out = (it & 1) ? 2 : 1;
         const int rc = kmeans_iter_impl(x, x_bs, xsq, cur, out, t_labels, t_counts, t_sorted, t_shift, B, N, K, D, dtype, it_ws, it_bytes, stream);
         if (rc != SVG_OK) return rc;
-        hipLaunchKernelGGL(kmeans_commit_kernel, dim3(grid), dim3(256), 0, st, t_labels, t_sorted, t_counts, labels, sorted_idx, counts,
-                           t_shift, state, bn, bk, B, tol, it, sel_cur, sel_out);
+        hipLaunchKernelGGL(kmeans_commit_kernel, grid, dim3(256), 0, st, t_labels, t_sorted, t_counts, labels, sorted_idx, counts,
+                           t_shift, state, gn, gk, (int)group, tol, it, sel_cur, sel_out);
         cur = out, sel_cur = sel_out;
     }
-    const long long n8 = bk * D / 8;
-    const unsigned g2 = (unsigned)std::min<long long>(1024, (n8 + 255) / 256);
+    const long long gn8 = gk * D / 8;
+    const dim3 g2((unsigned)std::min<long long>((1024 + G - 1) / G, (gn8 + 255) / 256), (unsigned)G);
     if (dtype == SVG_DTYPE_BF16)
-        hipLaunchKernelGGL((kmeans_select_kernel<__bf16>), dim3(g2), dim3(256), 0, st, (const __bf16*)c_init, (const __bf16*)c_work_a,
-                           (const __bf16*)c_work_b, (__bf16*)centroids_out, state, n8);
+        hipLaunchKernelGGL((kmeans_select_kernel<__bf16>), g2, dim3(256), 0, st, (const __bf16*)c_init, (const __bf16*)c_work_a,
+                           (const __bf16*)c_work_b, (__bf16*)centroids_out, state + 3 * G, gn8);
     else
-        hipLaunchKernelGGL((kmeans_select_kernel<_Float16>), dim3(g2), dim3(256), 0, st, (const _Float16*)c_init, (const _Float16*)c_work_a,
-                           (const _Float16*)c_work_b, (_Float16*)centroids_out, state, n8);
-    if (hipMemcpyAsync(n_iters, state + 2, sizeof(int32_t), hipMemcpyDeviceToDevice, st) != hipSuccess) return SVG_ERR_LAUNCH;
+        hipLaunchKernelGGL((kmeans_select_kernel<_Float16>), g2, dim3(256), 0, st, (const _Float16*)c_init, (const _Float16*)c_work_a,
+                           (const _Float16*)c_work_b, (_Float16*)centroids_out, state + 3 * G, gn8);
+    if (hipMemcpyAsync(n_iters, state + 2 * G, (size_t)G * sizeof(int32_t), hipMemcpyDeviceToDevice, st) != hipSuccess) return SVG_ERR_LAUNCH;
     return launch_status();
+}
+
+static int check_strided(const void* x, int64_t x_batch_stride, int32_t N, int32_t D) {
+    if (x_batch_stride < (int64_t)N * D) return SVG_ERR_BAD_ARG;
+    if (x_batch_stride % 8 != 0 || ((size_t)x & 15) != 0) return SVG_ERR_UNSUPPORTED;
+    return SVG_OK;
 }
 
 extern "C" int svg_kmeans_loop(const void* x, const float* xsq, const void* c_init, void* c_work_a, void* c_work_b, int32_t* labels,
@@ -618,14 +641,31 @@ extern "C" int svg_kmeans_loop(const void* x, const float* xsq, const void* c_in
                                int32_t K, int32_t D, int32_t dtype, int32_t max_iters, float tol, void* workspace,
                                size_t workspace_bytes, void* stream) {
     return kmeans_loop_impl(x, (long long)N * D, xsq, c_init, c_work_a, c_work_b, labels, counts, sorted_idx, centroids_out, n_iters, B, N, K, D,
-                            dtype, max_iters, tol, workspace, workspace_bytes, stream);
+                            dtype, B, max_iters, tol, workspace, workspace_bytes, stream);
 }
 
 extern "C" int svg_kmeans_loop_strided(const void* x, int64_t x_batch_stride, const void* c_init, void* c_work_a, void* c_work_b,
                                        int32_t* labels, int32_t* counts, int32_t* sorted_idx, void* centroids_out, int32_t* n_iters,
                                        int32_t B, int32_t N, int32_t K, int32_t D, int32_t dtype, int32_t max_iters, float tol,
                                        void* workspace, size_t workspace_bytes, void* stream) {
-    if (x_batch_stride < (int64_t)N * D || x_batch_stride % 8 != 0 || ((size_t)x & 15) != 0) return x_batch_stride < (int64_t)N * D ? SVG_ERR_BAD_ARG : SVG_ERR_UNSUPPORTED;
+    if (const int rc = check_strided(x, x_batch_stride, N, D); rc != SVG_OK) return rc;
     return kmeans_loop_impl(x, (long long)x_batch_stride, nullptr, c_init, c_work_a, c_work_b, labels, counts, sorted_idx, centroids_out, n_iters,
-                            B, N, K, D, dtype, max_iters, tol, workspace, workspace_bytes, stream);
+                            B, N, K, D, dtype, B, max_iters, tol, workspace, workspace_bytes, stream);
+}
+
+extern "C" int svg_kmeans_loop_grouped(const void* x, const float* xsq, const void* c_init, void* c_work_a, void* c_work_b, int32_t* labels,
+                                       int32_t* counts, int32_t* sorted_idx, void* centroids_out, int32_t* n_iters, int32_t B, int32_t N,
+                                       int32_t K, int32_t D, int32_t dtype, int32_t group, int32_t max_iters, float tol, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    return kmeans_loop_impl(x, (long long)N * D, xsq, c_init, c_work_a, c_work_b, labels, counts, sorted_idx, centroids_out, n_iters, B, N, K, D,
+                            dtype, group, max_iters, tol, workspace, workspace_bytes, stream);
+}
+
+extern "C" int svg_kmeans_loop_grouped_strided(const void* x, int64_t x_batch_stride, const void* c_init, void* c_work_a, void* c_work_b,
+                                               int32_t* labels, int32_t* counts, int32_t* sorted_idx, void* centroids_out, int32_t* n_iters,
+                                               int32_t B, int32_t N, int32_t K, int32_t D, int32_t dtype, int32_t group, int32_t max_iters,
+                                               float tol, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = check_strided(x, x_batch_stride, N, D); rc != SVG_OK) return rc;
+    return kmeans_loop_impl(x, (long long)x_batch_stride, nullptr, c_init, c_work_a, c_work_b, labels, counts, sorted_idx, centroids_out, n_iters,
+                            B, N, K, D, dtype, group, max_iters, tol, workspace, workspace_bytes, stream);
 }

@@ -181,6 +181,11 @@ SIGNATURES = {
     "svg_kmeans_loop_workspace_bytes": (_SZ, [_I32, _I32, _I32, _I32]),
     "svg_kmeans_loop": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _F32, _VP, _SZ, _VP]),
     "svg_kmeans_loop_strided": (C.c_int, [_VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _F32, _VP, _SZ, _VP]),
+    "svg_kmeans_loop_grouped_workspace_bytes": (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    "svg_kmeans_loop_grouped": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F32, _VP, _SZ,
+                                          _VP]),
+    "svg_kmeans_loop_grouped_strided": (C.c_int, [_VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F32,
+                                                  _VP, _SZ, _VP]),
     "svg_identify_dynamic_map": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _F32, _I32, _VP]),
     "svg_map_density": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _VP]),
 }
@@ -850,43 +855,54 @@ def kmeans_update(x: torch.Tensor, labels: torch.Tensor, centroids_in: torch.Ten
     return cent, counts, sorted_idx, shift
 
 
-def kmeans_loop(x: torch.Tensor, xsq: Optional[torch.Tensor], c_init: torch.Tensor, max_iters: int, tol: float, work=None):
+def kmeans_loop(x: torch.Tensor, xsq: Optional[torch.Tensor], c_init: torch.Tensor, max_iters: int, tol: float, work=None,
+                group: Optional[int] = None):
     """The whole Lloyd loop as one library call without host synchronisation (svg_kmeans_loop) -> (labels int32 [B, N], centroids
     [B, K, D], counts int32 [B, K], n_iters int32 [] on the device, sorted_idx int32 [B, N]).  `work`: a WorkspaceCache (or None: fresh
-    scratch per call) that keeps the scratch tensors of a (B, N, K, D) shape per device AND stream between calls."""
+    scratch per call) that keeps the scratch tensors of a (B, N, K, D) shape per device AND stream between calls.
+    group: None — one stopping rule over all B batches; an integer dividing B — one stopping rule per `group` consecutive batches
+    (svg_kmeans_loop_grouped), n_iters is then int32 [B // group]."""
     lib = load()
     _dev(xsq, c_init)
     _gpu(x)
     B, N, D = x.shape
     K = c_init.shape[1]
     assert c_init.shape == (B, K, D) and c_init.dtype == x.dtype and c_init.is_contiguous()
+    if group is not None:
+        group = int(group)
+        assert group >= 1 and B % group == 0, f"kmeans_loop: group = {group} must divide B = {B}"
     # x: contiguous, or batches further apart than N * D with contiguous rows inside (the video tokens `q[:, :V]` of a [H, S, D] tensor):
     # svg_kmeans_loop_strided reads them in place
     batch_strided = (not x.is_contiguous()) and x.stride(2) == 1 and x.stride(1) == D and x.stride(0) >= N * D and x.stride(0) % 8 == 0 \
         and x.data_ptr() % 16 == 0
     if not x.is_contiguous() and not batch_strided:
         x = x.contiguous()
-    key = WorkspaceCache.key("kmeans", B, N, K, D, x.dtype, device=x.device)
+    key = WorkspaceCache.key("kmeans", B, N, K, D, x.dtype, group, device=x.device)
     w = None if work is None else work.get(key)
     if w is None:
-        w = dict(ca=torch.empty_like(c_init), cb=torch.empty_like(c_init),
-                 ws=torch.empty(lib.svg_kmeans_loop_workspace_bytes(B, N, K, D), dtype=torch.uint8, device=x.device))
+        nb = lib.svg_kmeans_loop_workspace_bytes(B, N, K, D) if group is None else lib.svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, group)
+        w = dict(ca=torch.empty_like(c_init), cb=torch.empty_like(c_init), ws=torch.empty(nb, dtype=torch.uint8, device=x.device))
         if work is not None:
             work[key] = w
     labels = torch.empty((B, N), dtype=torch.int32, device=x.device)
     sorted_idx = torch.empty((B, N), dtype=torch.int32, device=x.device)
     counts = torch.empty((B, K), dtype=torch.int32, device=x.device)
     cent = torch.empty_like(c_init)
-    n_it = torch.zeros((), dtype=torch.int32, device=x.device)
+    n_it = torch.zeros(() if group is None else (B // group,), dtype=torch.int32, device=x.device)
+    outs = (labels.data_ptr(), counts.data_ptr(), sorted_idx.data_ptr(), cent.data_ptr(), n_it.data_ptr(), B, N, K, D, _dtype_code(x))
+    tail = (int(max_iters), float(tol), w["ws"].data_ptr(), w["ws"].numel(), _stream())
+    cs = (c_init.data_ptr(), w["ca"].data_ptr(), w["cb"].data_ptr())
+    if group is not None:
+        if batch_strided:
+            _check(lib.svg_kmeans_loop_grouped_strided(x.data_ptr(), int(x.stride(0)), *cs, *outs, group, *tail), "svg_kmeans_loop_grouped_strided")
+        else:
+            _check(lib.svg_kmeans_loop_grouped(x.data_ptr(), _ptr(xsq), *cs, *outs, group, *tail), "svg_kmeans_loop_grouped")
+        return labels, cent, counts, n_it, sorted_idx
     if batch_strided:
-        rc = lib.svg_kmeans_loop_strided(x.data_ptr(), int(x.stride(0)), c_init.data_ptr(), w["ca"].data_ptr(), w["cb"].data_ptr(),
-                                         labels.data_ptr(), counts.data_ptr(), sorted_idx.data_ptr(), cent.data_ptr(), n_it.data_ptr(), B, N, K, D,
-                                         _dtype_code(x), int(max_iters), float(tol), w["ws"].data_ptr(), w["ws"].numel(), _stream())
+        rc = lib.svg_kmeans_loop_strided(x.data_ptr(), int(x.stride(0)), *cs, *outs, *tail)
         _check(rc, "svg_kmeans_loop_strided")
         return labels, cent, counts, n_it, sorted_idx
-    rc = lib.svg_kmeans_loop(x.data_ptr(), _ptr(xsq), c_init.data_ptr(), w["ca"].data_ptr(), w["cb"].data_ptr(), labels.data_ptr(),
-                             counts.data_ptr(), sorted_idx.data_ptr(), cent.data_ptr(), n_it.data_ptr(), B, N, K, D, _dtype_code(x),
-                             int(max_iters), float(tol), w["ws"].data_ptr(), w["ws"].numel(), _stream())
+    rc = lib.svg_kmeans_loop(x.data_ptr(), _ptr(xsq), *cs, *outs, *tail)
     _check(rc, "svg_kmeans_loop")
     return labels, cent, counts, n_it, sorted_idx
 

@@ -55,7 +55,7 @@ _LOOP_WORK = _native._KMEANS_WS   # scratch of svg_kmeans_loop per (B, N, K, D, 
 
 @time_logging_decorator("Level 4 - batch kmeans euclid")
 def batch_kmeans_Euclid(x, n_clusters, max_iters=100, tol=1e-4, init_centroids=None, verbose=False, check_every=1,
-                        return_sorted_indices=False, shift_reduce=None):
+                        return_sorted_indices=False, shift_reduce=None, group=None):
     """ref: batch_kmeans_Euclid, svg/kmeans_utils.py:684-733.
 
     x: [B, N, D] bf16/fp16 GPU tensor.  Returns (cluster_ids int64 [B, N], centroids [B, K, D], cluster_sizes int32 [B, K],
@@ -74,11 +74,20 @@ def batch_kmeans_Euclid(x, n_clusters, max_iters=100, tol=1e-4, init_centroids=N
         labels, centroids and sizes as check_every = 1; n_iters is then a 0-dim int64 GPU tensor instead of an int.
     shift_reduce: optional callable applied in place to the 0-dim maximum centre shift before it is compared with `tol` — the
         head-sharded layer-call (svg.distributed) passes an all-reduce(MAX) so that the stopping rule stays the reference's
-        maximum over ALL heads."""
+        maximum over ALL heads.
+    group: None — the rule above over all B batches.  An integer dividing B — the batches form B // group stopping groups of `group`
+        consecutive batches (e.g. the heads of each video of a [cfg, H] batch), and each group follows the rule above on its own
+        batches only: its result never depends on the other groups.  n_iters is then per group: int64 [B // group] (a GPU tensor with
+        check_every = 0, a list of ints otherwise); shift_reduce receives the [B // group] vector of per-group maxima.  The per-group
+        rule is evaluated after every iteration on the device; check_every >= 1 only sets how often the host reads back whether every
+        group has stopped (no overshoot)."""
     _red = shift_reduce if shift_reduce is not None else (lambda t: t)
     assert x.is_cuda, "batch_kmeans_Euclid requires GPU tensors"
     assert max_iters >= 1, "max_iters must be >= 1 (the reference raises NameError for 0)"
     B, N, D = x.shape
+    if group is not None:
+        group = int(group)
+        assert group >= 1 and B % group == 0, f"batch_kmeans_Euclid: group = {group} must divide B = {B}"
     loop_in_library = not check_every and shift_reduce is None and not verbose
     # (the library loop reads batches that lie further apart than N * D in place — svg_kmeans_loop_strided: the video tokens of a
     #  [H, S, D] tensor with text rows behind them; every other path takes the contiguous copy the reference makes)
@@ -98,7 +107,7 @@ def batch_kmeans_Euclid(x, n_clusters, max_iters=100, tol=1e-4, init_centroids=N
     else:
         c_in = init_centroids.reshape(B, n_clusters, D).contiguous()
     cur = c_in
-    if check_every:
+    if check_every and group is None:
         n_done = 0
         for it in range(max_iters):
             c_out = st.c[it & 1]
@@ -118,32 +127,66 @@ def batch_kmeans_Euclid(x, n_clusters, max_iters=100, tol=1e-4, init_centroids=N
         # the whole loop inside the library (svg_kmeans_loop): the iterations and a commit kernel that applies the stopping rule on the
         # device — the same result as the torch statement below (kept for the sharded path, whose stopping rule needs an all-reduce
         # between the iterations), without its ~10 framework launches per iteration
-        labels_r, cent_r, counts_r, n_r, sorted_r = _native.kmeans_loop(x, xsq, c_in, max_iters, tol, work=_LOOP_WORK)
+        labels_r, cent_r, counts_r, n_r, sorted_r = _native.kmeans_loop(x, xsq, c_in, max_iters, tol, work=_LOOP_WORK, group=group)
         out = (labels_r.to(torch.int64), cent_r, counts_r, n_r.to(torch.int64))
         return out + (sorted_r,) if return_sorted_indices else out
-    labels_r = cent_r = counts_r = sorted_r = None
-    stopped = torch.zeros((), dtype=torch.bool, device=x.device)   # the reference's loop has left at an earlier iteration
-    n_r = torch.zeros((), dtype=torch.int64, device=x.device)
-    for it in range(max_iters):
+
+    def step(cur_, it):
         c_out = st.c[it & 1]
-        _native.kmeans_iter(x, xsq, cur, c_out, st.buf)
-        conv_now = _red(st.buf.shift.max()) < tol
-        if it == 0:
-            labels_r, counts_r, sorted_r = st.buf.labels.clone(), st.buf.counts.clone(), st.buf.sorted_idx.clone()
-            cent_r = torch.where(conv_now, c_in, c_out)
-        else:
-            run = ~stopped
-            labels_r = torch.where(run, st.buf.labels, labels_r)
-            counts_r = torch.where(run, st.buf.counts, counts_r)
-            sorted_r = torch.where(run, st.buf.sorted_idx, sorted_r)
-            cent_r = torch.where(run & ~conv_now, c_out, cent_r)
-        n_r = n_r + (~stopped).to(torch.int64)
-        stopped = stopped | conv_now
-        cur = c_out
+        _native.kmeans_iter(x, xsq, cur_, c_out, st.buf)
+        if verbose and check_every:
+            print(f"Iter {it}, center shift: {st.buf.shift.max().item():.6f}")
+        return c_out, st.buf.labels, st.buf.counts, st.buf.sorted_idx, st.buf.shift
+
+    labels_r, cent_r, counts_r, sorted_r, n_r = lloyd_device_rule(step, c_in, max_iters, tol, group=group, shift_reduce=shift_reduce,
+                                                                  check_every=check_every)
+    if check_every:   # (group is not None here)
+        n_r = [int(n) for n in n_r.tolist()]
     out = (labels_r.to(torch.int64), cent_r, counts_r, n_r)
     if return_sorted_indices:
         return out + (sorted_r,)
     return out
+
+
+def lloyd_device_rule(step, c_in, max_iters, tol, group=None, shift_reduce=None, check_every=0):
+    """The torch statement of the Lloyd loop under the reference's stopping rule (svg/kmeans_utils.py:716-733) evaluated on the device —
+    what svg_kmeans_loop[_grouped] does in its commit kernel.  Device-agnostic: `step(cur, it)` runs one iteration from the centroids
+    `cur` -> (new centroids [B, K, D], labels [B, N], counts [B, K], sorted indices [B, N], shift float [B]); the tensors it returns may
+    be overwritten by the next step.  group: see batch_kmeans_Euclid (None: one rule over all B batches, n_iters 0-dim; otherwise
+    n_iters [B // group]).  shift_reduce: applied in place to the maxima before the comparison with tol.  check_every >= 1: read back
+    every check_every iterations whether every group has stopped, and leave the loop then (the result is the same).
+    -> (labels, centroids, counts, sorted indices, n_iters int64)."""
+    _red = shift_reduce if shift_reduce is not None else (lambda t: t)
+    B = c_in.shape[0]
+    G = 1 if group is None else B // group
+
+    def per_batch(t, nd):   # a per-group flag as a mask over the batches of a [B, ...] tensor of nd dimensions
+        return t if group is None else t.repeat_interleave(group).view((B,) + (1,) * (nd - 1))
+
+    labels_r = cent_r = counts_r = sorted_r = None
+    shape = () if group is None else (G,)
+    stopped = torch.zeros(shape, dtype=torch.bool, device=c_in.device)   # the reference's loop has left at an earlier iteration
+    n_r = torch.zeros(shape, dtype=torch.int64, device=c_in.device)
+    cur = c_in
+    for it in range(max_iters):
+        c_out, labels, counts, sorted_idx, shift = step(cur, it)
+        mx = shift.max() if group is None else shift.view(G, group).max(dim=1).values   # (max propagates a NaN: `NaN < tol` is False)
+        conv_now = _red(mx) < tol
+        if it == 0:
+            labels_r, counts_r, sorted_r = labels.clone(), counts.clone(), sorted_idx.clone()
+            cent_r = torch.where(per_batch(conv_now, 3), c_in, c_out)
+        else:
+            run = ~stopped
+            labels_r = torch.where(per_batch(run, 2), labels, labels_r)
+            counts_r = torch.where(per_batch(run, 2), counts, counts_r)
+            sorted_r = torch.where(per_batch(run, 2), sorted_idx, sorted_r)
+            cent_r = torch.where(per_batch(run & ~conv_now, 3), c_out, cent_r)
+        n_r = n_r + (~stopped).to(torch.int64)
+        stopped = stopped | conv_now
+        cur = c_out
+        if check_every and (it + 1) % check_every == 0 and bool(stopped.all()):
+            break
+    return labels_r, cent_r, counts_r, sorted_r, n_r
 
 
 @time_logging_decorator("Level 4 - weighted softmax")

@@ -229,18 +229,33 @@ def svg1_sparse_attention(q, k, v, geo: Geometry, mask: "_native.BandMask", prof
 # ---------------------------------------------------------------------------------------------------------------
 class CentroidStore:
     """Per-layer k-means state (ref: class-level dicts of Hunyuan_SAPAttn_Processor2_0, hyvideo/attention.py:566-568).
-    Unlike the reference it can be reset between videos (`clear()`)."""
+    Unlike the reference it can be reset between videos (`clear()`).
+    Stored centroids carry the batch size (cfg, the number of videos) of the call that produced them: a layer-call with a different
+    cfg is a first call of that layer — random initial points and `iter_init` iterations — and never warm-starts from centroids of
+    the wrong shape (`has(layer_idx, cfg, heads)`).  Centroids written into `q` / `k` directly carry it in their shape, [cfg * H, K, D]."""
 
     def __init__(self):
         self.q = {}
         self.k = {}
+        self.cfg = {}
 
-    def has(self, layer_idx):
-        return layer_idx in self.q
+    def has(self, layer_idx, cfg=None, heads=None):
+        if layer_idx not in self.q:
+            return False
+        if cfg is None:
+            return True
+        if heads:   # (the shape decides: it is right for centroids written directly as well)
+            c = self.q[layer_idx]
+            return c.reshape(-1, *c.shape[-2:]).shape[0] == cfg * heads
+        return self.cfg.get(layer_idx) == cfg
+
+    def put(self, layer_idx, q, k, cfg):
+        self.q[layer_idx], self.k[layer_idx], self.cfg[layer_idx] = q, k, cfg
 
     def clear(self):
         self.q.clear()
         self.k.clear()
+        self.cfg.clear()
 
 
 KMEANS_TWO_STREAMS = True    # q-side and k-side k-means loops on two streams (kmeans_clustering below); False: one after the other
@@ -262,30 +277,38 @@ def kmeans_clustering(store: CentroidStore, layer_idx: int, q_video, k_video, nu
     first call of a layer, warm start from the previous denoise step's centroids afterwards.
     head_shard = (h0, h1, H): q_video / k_video hold heads [h0, h1) of H (svg.distributed) — the random initial points are drawn
     for all H heads, in the order of the unsharded call, and this rank keeps its rows; the stopping rule's maximum centre shift is
-    all-reduced — so that the result does not depend on the sharding."""
+    all-reduced — so that the result does not depend on the sharding.
+    cfg > 1: one stopping rule per video (the loops run with group = H, the heads of one video; sharded: this rank's heads of one
+    video, the per-video maxima all-reduced), so that each video's clustering is the one it gets alone."""
     cfg, H, N, D = q_video.shape
-    first = not store.has(layer_idx)
+    first = not store.has(layer_idx, cfg, H)
     iters = iter_init if first else iter_step
     qi = None if first else store.q[layer_idx]
     ki = None if first else store.k[layer_idx]
     red = _dist.all_reduce_max_ if head_shard is not None else None
-    if first and head_shard is not None:
-        h0, h1, H_all = head_shard
-        rows = (torch.arange(cfg, device=q_video.device)[:, None] * H_all + torch.arange(h0, h1, device=q_video.device)[None]).reshape(-1)
+    if first and (head_shard is not None or cfg > 1):
+        # ref svg/kmeans_utils.py:706-709, drawn here video by video (q side, then k side, of all H heads) in the order of a cfg = 1 call:
+        # video 0 gets the initial points a call on it alone gets at the same seed; a head-sharded rank keeps its rows of each draw
+        h0, h1, H_all = head_shard if head_shard is not None else (0, H, H)
+        qd, kd = [], []
+        for _ in range(cfg):
+            qd.append(torch.randint(0, N, (H_all, num_q_centroids), device=q_video.device)[h0:h1])
+            kd.append(torch.randint(0, N, (H_all, num_k_centroids), device=k_video.device)[h0:h1])
 
-        def draw(x, n_clusters):   # ref svg/kmeans_utils.py:706-709 for all cfg * H heads, then this rank's rows
-            idx = torch.randint(0, N, (cfg * H_all, n_clusters), device=x.device).index_select(0, rows)
-            return torch.gather(x.reshape(cfg * H, N, D), 1, idx[..., None].expand(-1, -1, D)).contiguous()
+        def draw(x, idx):
+            return torch.gather(x.reshape(cfg * H, N, D), 1, torch.cat(idx)[..., None].expand(-1, -1, D)).contiguous()
 
-        qi, ki = draw(q_video, num_q_centroids), draw(k_video, num_k_centroids)
+        qi, ki = draw(q_video, qd), draw(k_video, kd)
     # (check_every=0: the reference's stopping rule evaluated on the device — same result, no read-back per iteration)
+    grp = None if cfg == 1 else H   # (cfg == 1: the ungrouped loop, exactly as before)
+
     def run_q():
         return batch_kmeans_Euclid(q_video.reshape(cfg * H, N, D), num_q_centroids, max_iters=iters, init_centroids=qi,
-                                   return_sorted_indices=True, check_every=0, shift_reduce=red)
+                                   return_sorted_indices=True, check_every=0, shift_reduce=red, group=grp)
 
     def run_k():
         return batch_kmeans_Euclid(k_video.reshape(cfg * H, N, D), num_k_centroids, max_iters=iters, init_centroids=ki,
-                                   return_sorted_indices=True, check_every=0, shift_reduce=red)
+                                   return_sorted_indices=True, check_every=0, shift_reduce=red, group=grp)
 
     if KMEANS_TWO_STREAMS and red is None and q_video.is_cuda:
         # The two Lloyd loops are independent until the block map: the q side runs on a side stream beside the k side, so that the
@@ -305,8 +328,7 @@ def kmeans_clustering(store: CentroidStore, layer_idx: int, q_video, k_video, nu
     else:
         ql, qc, qs, qit, qidx = run_q()
         kl, kc, ks, kit, kidx = run_k()
-    store.q[layer_idx] = qc
-    store.k[layer_idx] = kc
+    store.put(layer_idx, qc, kc, cfg)
     if first:
         print(f"Centroids initialized at layer {layer_idx}. Init step: {iter_init}")
     return (ql, qc, qs, qit, qidx), (kl, kc, ks, kit, kidx)
@@ -317,7 +339,10 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
                           prompt_length: int = 0, logging_file: Optional[str] = None, timestep=None, _head_shard=None):
     """The sparse branch of the SAP processors (ref: hyvideo/attention.py:747-804, wan/attention.py:529-559):
     k-means on the video tokens -> top-p block map -> (Hunyuan) two pseudo clusters for prompt / unused prompt ->
-    variable-block attention with the token permutation fused in (the result is already in the original order)."""
+    variable-block attention with the token permutation fused in (the result is already in the original order).
+    q, k, v: [cfg, H, S, D]; cfg > 1 (several videos: a list of prompts, num_videos_per_prompt > 1) clusters each video with its own
+    stopping rule, so every video's output, labels and block map are the ones a cfg = 1 call on that video alone gives.  All videos share
+    the text layout (`prompt_length` is one integer)."""
     _require_gpu(q, "SVG2 sparse attention")
     if _dist.active() and _head_shard is None:   # svg.distributed.enable(): this rank's heads only, outputs all-gathered
         grp = _dist.current_group()
@@ -327,13 +352,13 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
             qh, kh, vh, geo, store, layer_idx, num_q_centroids, num_k_centroids, top_p, min_kc_ratio, iter_init, iter_step,
             prompt_length, logging_file, timestep, _head_shard=shard), (q, k, v), grp)
     cfg, H, S, D = q.shape
-    assert cfg == 1, "Batch size must be 1 for kmeans block sparse attention"
     assert not geo.text_first, "SVG2 is defined for text-last models (Hunyuan, Wan)"
     V, ctx = geo.video_length, geo.context_length
     q, k = q.contiguous(), k.contiguous()   # (the k-means reads them as [H, N, D]; v may stay a strided view: only the attention kernel reads it)
-    # the video tokens as VIEWS when the loop runs inside the library (svg_kmeans_loop_strided reads heads S * D apart in place); the
-    # head-sharded path (torch statement of the loop, all-reduced stopping rule) takes the copies the reference makes
-    in_place = ctx and cfg == 1 and _head_shard is None and not _dist.active()
+    # the video tokens as VIEWS when the loop runs inside the library (svg_kmeans_loop[_grouped]_strided reads heads S * D apart in place:
+    # the cfg * H heads of a contiguous [cfg, H, S, D] are uniformly S * D apart); the head-sharded path (torch statement of the loop,
+    # all-reduced stopping rule) takes the copies the reference makes
+    in_place = ctx and _head_shard is None and not _dist.active()
     qv = (q[:, :, :V] if in_place else q[:, :, :V].contiguous()) if ctx else q
     kv = (k[:, :, :V] if in_place else k[:, :, :V].contiguous()) if ctx else k
     with time_logging_decorator("Level 3 - semantic aware permutation"):
@@ -352,8 +377,9 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
     f8 = _use_fp8(q)
     # (rows_covered: the cluster sizes of every head add up to S — k-means counts over the V video tokens plus the text pseudo-clusters of
     #  dynamic_map_post_processing — so the kernel writes every output row and the wrapper skips the zero fill)
-    out = _native.varblock_attention(q, k, v, dyn_map.view(H, QB, KB).contiguous(),
-                                     q_sizes.view(H, QB).contiguous(), k_sizes.view(H, KB).contiguous(),
+    # (one launch over the cfg * H heads; the token-major output is [cfg, S, H, D] in memory: svg_attn_layout_t with heads_per_batch = H)
+    out = _native.varblock_attention(q, k, v, dyn_map.view(cfg * H, QB, KB).contiguous(),
+                                     q_sizes.view(cfg * H, QB).contiguous(), k_sizes.view(cfg * H, KB).contiguous(),
                                      q_row_idx=qidx.contiguous(), kv_row_idx=kidx.contiguous(), fp8=f8,
                                      token_major_out=TOKEN_MAJOR_IO and _head_shard is None, rows_covered=True)
     if logging_file is not None:
@@ -365,7 +391,7 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
         if _head_shard is None or torch.distributed.get_rank(_dist.current_group()) == 0:
             DENSITY_LOG.push(logging_file, {"timestep": timestep_value(timestep) if timestep is not None else None,
                                             "layer": layer_idx}, densities)
-    return out.reshape(cfg, H, S, D)   # (a view in either storage order: cfg == 1)
+    return out.reshape(cfg, H, S, D)   # (out is [cfg, H, S, D] already, in either storage order: a view)
 
 
 class _DensityLog:
@@ -397,6 +423,8 @@ class _DensityLog:
                 elif not ev.query():
                     return
             entry = dict(meta, avg_density=float(host.mean()), density=host.tolist())
+            if host.dim() == 2 and host.shape[0] > 1:   # several videos: their own averages too (a cfg == 1 entry is unchanged)
+                entry["video_avg_density"] = [float(r.mean()) for r in host]
             with open(path, "a") as f:
                 f.write(json.dumps(entry) + "\n")
             self.pending.pop(0)

@@ -318,7 +318,11 @@ def prepare_flexattention(cfg_size, num_head, head_dim, dtype, device, context_l
 
 
 class Hunyuan_SAPAttn_Processor2_0(Hunyuan_SVGAttn_Processor2_0):
-    """Sparse VideoGen 2 — semantic-aware permutation (ref: hyvideo/attention.py:555-804)."""
+    """Sparse VideoGen 2 — semantic-aware permutation (ref: hyvideo/attention.py:555-804).
+    Takes a batch of videos (cfg > 1: a list of prompts, num_videos_per_prompt > 1): each video is clustered with its own stopping
+    rule and gets the output a call on it alone gives.  `prompt_length` stays one class-level integer, as in the reference: all
+    videos of a batch share the text layout (per-video prompt lengths are not supported).  A layer called with another cfg than its
+    stored centroids starts over from random initial points (see CentroidStore)."""
 
     num_q_centroids = 0
     num_k_centroids = 0
@@ -341,7 +345,6 @@ class Hunyuan_SAPAttn_Processor2_0(Hunyuan_SVGAttn_Processor2_0):
     @time_logging_decorator("Level 2 - attention core logic")
     def attention_core_logic(self, query, key, value, timestep, layer_idx, cu_max_seqlens):
         cfg, num_heads, seq_len, dim = query.size()
-        assert cfg == 1, "Batch size must be 1 for kmeans block sparse attention"
         geo = self.geometry()
         assert seq_len == geo.seq_len, (
             f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")

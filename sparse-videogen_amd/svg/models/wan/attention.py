@@ -284,7 +284,8 @@ def prepare_flashinfer_attention(cfg_size, num_head, head_dim, dtype, device, co
 
 class WanAttn_SAPAttn_Processor(WanAttn_SVGAttn_Processor2_0):
     """Sparse VideoGen 2 for Wan 2.1 (ref: wan/attention.py:379-559).  Centroids are kept per processor instance (one
-    per layer), as in the reference."""
+    per layer), as in the reference.  Takes a batch of videos (cfg > 1): each video is clustered with its own stopping rule and gets the
+    output a call on it alone gives; a call with another cfg than the stored centroids starts over from random initial points."""
 
     num_layers = 0
     num_q_centroids = 0
@@ -309,16 +310,14 @@ class WanAttn_SAPAttn_Processor(WanAttn_SVGAttn_Processor2_0):
     @time_logging_decorator("Level 2 - attention core logic")
     def attention_core_logic(self, query, key, value, timestep):
         cfg, num_heads, seq_len, dim = query.size()
-        assert cfg == 1, "Batch size must be 1 for kmeans block sparse attention"
         geo = self.geometry()
         assert seq_len == geo.seq_len, (
             f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
         if _core.is_full_attention(self.layer_idx, timestep, self.first_layers_fp, self.first_times_fp):
             if self.zero_step_kmeans_init and query.is_cuda:
                 V = geo.video_length
-                _core.kmeans_clustering(self.centroid_store, self.layer_idx, query[:, :, :V].contiguous(),
-                                        key[:, :, :V].contiguous(), self.num_q_centroids, self.num_k_centroids,
-                                        self.kmeans_iter_init, self.kmeans_iter_step)
+                _core.kmeans_clustering(self.centroid_store, self.layer_idx, query[:, :, :V], key[:, :, :V],   # (views: read in place)
+                                        self.num_q_centroids, self.num_k_centroids, self.kmeans_iter_init, self.kmeans_iter_step)
             return self.flash_attention(query, key, value).reshape(cfg, num_heads, seq_len, dim)
         out = _core.svg2_sparse_attention(query, key, value, geo, self.centroid_store, self.layer_idx, self.num_q_centroids,
                                           self.num_k_centroids, self.top_p_kmeans, self.min_kc_ratio, self.kmeans_iter_init,
