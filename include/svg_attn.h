@@ -91,6 +91,8 @@ int svg_argsort_labels(const int32_t* labels, int32_t* sorted_idx, int32_t* coun
  *   dense   : band = S + 1 (two segments when real_len < S, i.e. cu_seqlens [0, real_len, S])
  * Rows with no allowed key produce zeros.  The mask is evaluated element-wise on band-edge tiles, exactly as
  * flex_attention applies mask_mod inside partial blocks.
+ * Sizes (every svg_band_attention* entry): S < 2^24 and S * D * 2 < 2^32 (the LDS-DMA requests carry 32-bit byte offsets per head and
+ * compute a row's offset with a 24-bit multiply), BH * S * D < 2^40; larger calls return SVG_ERR_UNSUPPORTED.
  *
  * Fused layout transformation: when head_perm_flag != NULL, heads with head_perm_flag[bh] != 0 are processed
  * in token-major order *without* materialising the permuted tensors: logical row i (< perm_V, offset by
@@ -189,7 +191,8 @@ int svg_band_attention_switch_prescaled(const void* q_scaled, const void* k, con
  *      active key (and rows of empty blocks) give zeros.
  * q/o: [Hq, Sq, D], k/v: [Hkv, Skv, D] (Hq % Hkv == 0: GQA group shares map/sizes of its kv head).
  * block_map: device uint8/bool [Hkv, QB, KB]; q_sizes int32 [Hkv, QB]; k_sizes int32 [Hkv, KB].  KB <= 4032 (the compacted key-block list of a
- * block-row lives in LDS beside the K / V stages; more returns SVG_ERR_UNSUPPORTED).
+ * block-row lives in LDS beside the K / V stages; more returns SVG_ERR_UNSUPPORTED).  Sq and Skv < 2^24, Sq * D * 2 and Skv * D * 2
+ * < 2^32 (every svg_varblock_attention* entry, as for svg_band_attention), otherwise SVG_ERR_UNSUPPORTED.
  * Fused token permutation: q_row_idx (int32 [Hq, Sq]) / kv_row_idx (int32 [Hkv, Skv]) map a *permuted* position
  * to the physical row of q,o / k,v (the `sorted_indices` of permute_tensor_by_labels); NULL = tensors are
  * already permuted.  With both given the call equals permute(q,k,v) -> attention -> inverse_permute(o)
@@ -230,7 +233,8 @@ int svg_varblock_attention_strided(const void* q, const void* k, const void* v, 
  * ref: sample_mse, svg/models/hyvideo/attention.py:376-399 (wan :211-234, cog :120-145) with the profiling masks
  *      of get_attention_mask, svg/models/hyvideo/utils.py:47-93 (wan/utils.py:63-110, cog/utils.py:61-88),
  *      evaluated analytically instead of from two materialised [10000, S] fp32 masks.
- * rows: device int64 [R] sampled query rows (R <= 64 multiple-of-anything; padded internally).
+ * rows: device int64 [R] sampled query rows (R <= 64 multiple-of-anything; padded internally).  S < 2^24 (every svg_sample_mse* entry,
+ * as for svg_band_attention), otherwise SVG_ERR_UNSUPPORTED.
  * profile mask (block = 128): |floor(x/128) - floor(y/128)| < band_blocks with x, y the row / column index in
  * frame-major order (mask 0, "spatial") or in token-major order (mask 1, "temporal"); the per-model quirks of
  * the reference masks (Wan sink columns, Cog's un-offset spatial band and text-less temporal mask) are expressed

@@ -808,39 +808,6 @@ int band_waves_per_tile(int variant) {
     return v == kBandW4 ? 4 : ((v == kBandPingPong || v == kBandM16) ? 8 : -1);   // waves that report per 256-row q-tile; -1: no counters
 }
 
-template <typename T, int D>
-static int run_band_lockstep4(const void* q, const void* k, const void* v, void* o, int BH, int S, float sm_scale,
-                              const svg_band_mask_t* mask, const svg_perm_desc_t* perm, hipStream_t st) {
-    using Pol = BandPolicy<T, D, 4, false>;
-    const typename Pol::Params p = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm);
-    return launch_attn(band_attn_kernel<T, D, 4>, p, dim3(p.nqt * BH), 256, attn_lds_bytes<D, 4, 2>(), st);
-}
-
-template <typename T, int D>
-static int run_band_pp2(const void* q, const void* k, const void* v, void* o, int BH, int S, float sm_scale,
-                        const svg_band_mask_t* mask, const svg_perm_desc_t* perm, const BandOpts& opts, int trace_abl,
-                        hipStream_t st) {
-    using Pol = BandPolicy<T, D, 8, false>;
-    const typename Pol::Params p = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
-#ifdef SVG_ABLATIONS
-    if constexpr (D == 128 && std::is_same<T, __bf16>::value) {
-        if (trace_abl >= 0) {
-#define SVG_PP_TRACE(A) case A: return launch_attn(band_attn_pp2_trace_kernel<T, D, A>, p, dim3(p.nqt * BH), 512, attn_pp2_lds_bytes<D>(), st);
-            switch (trace_abl) {
-                SVG_PP_TRACE(0) SVG_PP_TRACE(1) SVG_PP_TRACE(2) SVG_PP_TRACE(4) SVG_PP_TRACE(5) SVG_PP_TRACE(6) SVG_PP_TRACE(7) SVG_PP_TRACE(8)
-                case 3: return launch_attn(band_attn_pp2q_trace_kernel<T, D>, p, dim3(p.nqt * BH), 512, attn_pp2_lds_bytes<D>(), st);
-                case 9: return launch_attn(band_attn_m16_trace_kernel<T>, p, dim3(p.nqt * BH), 512, attn_m16_lds_bytes(), st);
-                default: return SVG_ERR_UNSUPPORTED;
-            }
-#undef SVG_PP_TRACE
-        }
-    }
-#endif
-    if (trace_abl >= 0) return SVG_ERR_UNSUPPORTED;   // the trace / ablation kernels exist in -DSVG_ABLATIONS builds only
-    if (opts.prescaled) return launch_attn(band_attn_pp2q_kernel<T, D>, p, dim3(p.nqt * BH), 512, attn_pp2_lds_bytes<D>(), st);
-    return launch_attn(band_attn_pp2_kernel<T, D>, p, dim3(p.nqt * BH), 512, attn_pp2_lds_bytes<D>(), st);
-}
-
 }  // namespace svg
 
 using namespace svg;
@@ -871,31 +838,33 @@ __global__ __launch_bounds__(64) void wait_counters_deadline_kernel(const int32_
 
 static bool g_trace_is_w4 = false;   // diagnostics only: which translation unit holds the last cycle trace
 
+// pointers, mask, head permutation and sizes: the checks every svg_band_attention* entry shares
 static int band_check_args(const void* q, const void* k, const void* v, const void* o, int32_t BH, int32_t S, int32_t D,
                            const svg_band_mask_t* mask, const svg_perm_desc_t* perm) {
     if (!q || !k || !v || !o || !mask || BH <= 0 || S <= 0) return SVG_ERR_BAD_ARG;
-    if (mask->real_len < 0 || mask->real_len > S || mask->band < 0 || mask->band > S + 1) return SVG_ERR_BAD_ARG;
-    if (mask->colfull_lo > mask->colfull_hi || mask->rowfull_lo > mask->rowfull_hi) return SVG_ERR_BAD_ARG;
-    if (perm && perm->head_perm_flag) {
-        if (perm->num_frame <= 0 || perm->frame_size <= 0 || perm->vid0 < 0 ||
-            (int64_t)perm->vid0 + (int64_t)perm->num_frame * perm->frame_size > S)
-            return SVG_ERR_BAD_ARG;
-    }
+    if (const int rc = check_band_mask(S, mask, perm); rc != SVG_OK) return rc;
     if ((int64_t)BH * S * D >= (1ll << 40)) return SVG_ERR_UNSUPPORTED;
-    if ((int64_t)S * D * 2 >= (1ll << 32)) return SVG_ERR_UNSUPPORTED;   // the LDS-DMA requests carry 32-bit byte offsets per head
-    return SVG_OK;
+    return check_rows(S, D);
 }
 
+// Every svg_band_attention* entry, after the null checks of its own arguments: validation, then the kernel of `variant` for
+// (dtype, D).  opts carries what the entry adds: pre-scaled q, completion counters (`done_words` of them), the device switch (its
+// alternate mask is checked here too) and strided tensors (opts.strided: `layout` describes them).
 static int band_dispatch(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t S, int32_t D, int32_t dtype,
-                         float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm, int32_t variant,
-                         const BandOpts& opts, hipStream_t st) {
+                         float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm, int32_t variant, BandOpts opts,
+                         int32_t done_words, const svg_attn_layout_t* layout, void* stream) {
+    int rc = band_check_args(q, k, v, o, BH, S, D, mask, perm);
+    if (rc == SVG_OK && opts.alt_mask) rc = check_band_mask(S, opts.alt_mask, nullptr);
+    if (rc != SVG_OK) return rc;
+    if (opts.done && (int64_t)done_words < (int64_t)BH * (opts.done_nseg + 1)) return SVG_ERR_WORKSPACE;   // segment counters + one hidden counter per head
+    if (opts.strided && (rc = layout_from_abi(layout, BH, BH, S, S, D, q, k, v, o, opts.lay)) != SVG_OK) return rc;
+    const hipStream_t st = (hipStream_t)stream;
     int trace_abl = -1;
     if ((variant & 0xFF) == 32) {   // diagnostics builds: traced one-wave-per-SIMD kernel, bits 8..11 = its timing ablation
-        BandOpts o2 = opts;
-        o2.trace = true;
-        o2.trace_abl = (variant >> 8) & 15;
+        opts.trace = true;
+        opts.trace_abl = (variant >> 8) & 15;
         g_trace_is_w4 = true;
-        return run_band_w4(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, o2, st);
+        return run_band_w4(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, opts, st);
     }
     if (variant & 64) {   // diagnostics builds: bit 6 = traced two-phase kernel, bits 8..11 = its timing ablation
         trace_abl = (variant >> 8) & 15;
@@ -905,82 +874,91 @@ static int band_dispatch(const void* q, const void* k, const void* v, void* o, i
     if (variant == kBandAuto) variant = band_default(D);
     if (opts.done && band_waves_per_tile(variant) < 0) return SVG_ERR_UNSUPPORTED;
     if (opts.strided && variant != kBandM16 && variant != kBandPingPong) return SVG_ERR_UNSUPPORTED;   // strided tensors: the two-phase bodies only (see svg_attn_layout_t)
-#define SVG_BAND_TD(FN, ...)                                                                    \
-    if (dtype == SVG_DTYPE_BF16 && D == 128) return FN<__bf16, 128>(__VA_ARGS__);               \
-    if (dtype == SVG_DTYPE_BF16 && D == 64) return FN<__bf16, 64>(__VA_ARGS__);                 \
-    if (dtype == SVG_DTYPE_F16 && D == 128) return FN<_Float16, 128>(__VA_ARGS__);              \
-    if (dtype == SVG_DTYPE_F16 && D == 64) return FN<_Float16, 64>(__VA_ARGS__);                \
-    return SVG_ERR_UNSUPPORTED;
-    switch (variant) {
-        case kBandW4: return run_band_w4(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, opts, st);
-        case kBandPingPong: { SVG_BAND_TD(run_band_pp2, q, k, v, o, BH, S, sm_scale, mask, perm, opts, trace_abl, st) }
-        case kBandLockstep4: { SVG_BAND_TD(run_band_lockstep4, q, k, v, o, BH, S, sm_scale, mask, perm, st) }
-        case kBandFrozen: {
-            if (dtype != SVG_DTYPE_BF16 || D != 128 || opts.done || opts.prescaled) return SVG_ERR_UNSUPPORTED;
-            using Pol = BandPolicy<__bf16, 128, 8, false>;
-            const typename Pol::Params p = make_band_params<Pol, __bf16>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
-            return launch_attn(band_attn_pp2_frozen_kernel, p, dim3(p.nqt * BH), 512, attn_pp2_lds_bytes<128>(), st);
-        }
-        case kBandM16: {   // two-phase body on 16x16x32 MFMAs (attn_m16.h): head_dim 128
-            if (D != 128) return SVG_ERR_UNSUPPORTED;
-            if (opts.prescaled) {   // PRE form: q carries the softmax scale
-                if (dtype == SVG_DTYPE_BF16) {
-                    using Pol = BandPolicy<__bf16, 128, 8, false>;
-                    const typename Pol::Params p = make_band_params<Pol, __bf16>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
-                    return launch_attn(band_attn_m16q_kernel<__bf16, false>, p, dim3(p.nqt * BH), 512, attn_m16_lds_bytes(), st);
+    if (variant == kBandW4) return run_band_w4(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, opts, st);
+    if (variant != kBandLockstep4 && variant != kBandPingPong && variant != kBandFrozen && variant != kBandM16) return SVG_ERR_BAD_ARG;
+    return dispatch_td(dtype, D, [&](auto t, auto d) -> int {
+        using T = decltype(t);
+        constexpr int DD = decltype(d)::value;
+        using Pol = BandPolicy<T, DD, 8, false>;
+        auto launch = [&](auto kern, int lds) {   // 8 waves over the q-tiles of every head
+            const typename Pol::Params p = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
+            return launch_attn(kern, p, dim3(p.nqt * BH), 512, lds, st);
+        };
+        // a device-switch kernel: the parameters of both masks (the alternate one without the head permutation) and the flag, over
+        // the q-tiles of the larger of the two
+        auto launch_switch = [&](auto kern, int lds) {
+            const typename Pol::Params a = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
+            const typename Pol::Params b = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, opts.alt_mask, nullptr, opts);
+            if (const int r2 = configure_lds((const void*)kern, lds); r2 != SVG_OK) return r2;
+            hipLaunchKernelGGL(kern, dim3(std::max(a.nqt, b.nqt) * BH), dim3(512), lds, st, a, b, opts.use_alt);
+            return launch_status();
+        };
+        switch (variant) {
+            case kBandLockstep4: {
+                using Pol4 = BandPolicy<T, DD, 4, false>;
+                const typename Pol4::Params p = make_band_params<Pol4, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
+                return launch_attn(band_attn_kernel<T, DD, 4>, p, dim3(p.nqt * BH), 256, attn_lds_bytes<DD, 4, 2>(), st);
+            }
+            case kBandPingPong:
+#ifdef SVG_ABLATIONS
+                if constexpr (DD == 128 && std::is_same<T, __bf16>::value) {
+                    switch (trace_abl) {
+#define SVG_PP_TRACE(A) case A: return launch(band_attn_pp2_trace_kernel<T, DD, A>, attn_pp2_lds_bytes<DD>());
+                        SVG_PP_TRACE(0) SVG_PP_TRACE(1) SVG_PP_TRACE(2) SVG_PP_TRACE(4) SVG_PP_TRACE(5) SVG_PP_TRACE(6) SVG_PP_TRACE(7) SVG_PP_TRACE(8)
+#undef SVG_PP_TRACE
+                        case -1: break;
+                        case 3: return launch(band_attn_pp2q_trace_kernel<T, DD>, attn_pp2_lds_bytes<DD>());
+                        case 9: return launch(band_attn_m16_trace_kernel<T>, attn_m16_lds_bytes());
+                        default: return SVG_ERR_UNSUPPORTED;
+                    }
                 }
-                if (dtype == SVG_DTYPE_F16) {
-                    using Pol = BandPolicy<_Float16, 128, 8, false>;
-                    const typename Pol::Params p = make_band_params<Pol, _Float16>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
-                    return launch_attn(band_attn_m16q_kernel<_Float16, false>, p, dim3(p.nqt * BH), 512, attn_m16_lds_bytes(), st);
+#endif
+                if (trace_abl >= 0) return SVG_ERR_UNSUPPORTED;   // the trace / ablation kernels exist in -DSVG_ABLATIONS builds only
+                if (opts.use_alt) {
+                    if (opts.prescaled) return launch_switch(band_attn_pp2q_switch_kernel<T, DD>, attn_pp2_lds_bytes<DD>());
+                    if constexpr (DD == 64) return launch_switch(band_attn_pp2_switch64_kernel<T>, attn_pp2_lds_bytes<64>());
+                    return SVG_ERR_UNSUPPORTED;
+                }
+                return launch(opts.prescaled ? band_attn_pp2q_kernel<T, DD> : band_attn_pp2_kernel<T, DD>, attn_pp2_lds_bytes<DD>());
+            case kBandFrozen:   // bf16 / head_dim 128 only
+                if constexpr (DD == 128 && std::is_same<T, __bf16>::value) {
+                    if (opts.done || opts.prescaled) return SVG_ERR_UNSUPPORTED;
+                    return launch(band_attn_pp2_frozen_kernel, attn_pp2_lds_bytes<128>());
                 }
                 return SVG_ERR_UNSUPPORTED;
-            }
-            if (dtype == SVG_DTYPE_BF16) {
-                using Pol = BandPolicy<__bf16, 128, 8, false>;
-                const typename Pol::Params p = make_band_params<Pol, __bf16>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
-                return launch_attn(band_attn_m16_kernel<__bf16>, p, dim3(p.nqt * BH), 512, attn_m16_lds_bytes(), st);
-            }
-            if (dtype == SVG_DTYPE_F16) {
-                using Pol = BandPolicy<_Float16, 128, 8, false>;
-                const typename Pol::Params p = make_band_params<Pol, _Float16>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
-                return launch_attn(band_attn_m16_kernel<_Float16>, p, dim3(p.nqt * BH), 512, attn_m16_lds_bytes(), st);
-            }
-            return SVG_ERR_UNSUPPORTED;
+            default:   // kBandM16: two-phase body on 16x16x32 MFMAs (attn_m16.h), head_dim 128; PRE forms for a q that carries the scale
+                if constexpr (DD == 128) {
+                    if (opts.use_alt)
+                        return launch_switch(opts.prescaled ? band_attn_m16_switch_kernel<T, true, false> : band_attn_m16_switch_kernel<T>,
+                                             attn_m16_lds_bytes());
+                    return launch(opts.prescaled ? band_attn_m16q_kernel<T, false> : band_attn_m16_kernel<T>, attn_m16_lds_bytes());
+                }
+                return SVG_ERR_UNSUPPORTED;
         }
-        default: return SVG_ERR_BAD_ARG;
-    }
-#undef SVG_BAND_TD
+    });
 }
 
 extern "C" int svg_band_attention(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t S, int32_t D,
                                   int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
                                   const svg_perm_desc_t* perm, int32_t variant, void* stream) {
-    const int rc = band_check_args(q, k, v, o, BH, S, D, mask, perm);
-    if (rc != SVG_OK) return rc;
-    return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, variant, BandOpts(), (hipStream_t)stream);
+    return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, variant, BandOpts(), 0, nullptr, stream);
 }
 
 extern "C" int svg_band_attention_strided(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t S, int32_t D,
                                           int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
                                           const svg_attn_layout_t* layout, void* stream) {
-    int rc = band_check_args(q, k, v, o, BH, S, D, mask, perm);
-    if (rc != SVG_OK) return rc;
     BandOpts opts;
     opts.strided = true;
-    if (rc = layout_from_abi(layout, BH, BH, S, S, D, q, k, v, o, opts.lay); rc != SVG_OK) return rc;
-    return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, (hipStream_t)stream);
+    return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, 0, layout, stream);
 }
 
+// (head_dim 128: the PRE form of the 16x16x32 body — 33.0 - 33.3 ms against 33.6 - 34.2 for the 32x32x16 one, same box, profiles/r04k_ab_m16_prescaled.txt)
 extern "C" int svg_band_attention_prescaled(const void* q_scaled, const void* k, const void* v, void* o, int32_t BH, int32_t S,
                                             int32_t D, int32_t dtype, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
                                             void* stream) {
-    const int rc = band_check_args(q_scaled, k, v, o, BH, S, D, mask, perm);
-    if (rc != SVG_OK) return rc;
     BandOpts opts;
     opts.prescaled = true;
-    // (head_dim 128: the PRE form of the 16x16x32 body — 33.0 - 33.3 ms against 33.6 - 34.2 for the 32x32x16 one, same box, profiles/r04k_ab_m16_prescaled.txt)
-    return band_dispatch(q_scaled, k, v, o, BH, S, D, dtype, 1.f, mask, perm, kBandAuto, opts, (hipStream_t)stream);
+    return band_dispatch(q_scaled, k, v, o, BH, S, D, dtype, 1.f, mask, perm, kBandAuto, opts, 0, nullptr, stream);
 }
 
 extern "C" int32_t svg_band_attention_notify_target(int32_t S, const svg_band_mask_t* mask) {
@@ -1024,12 +1002,9 @@ extern "C" int svg_band_attention_notify_seg(const void* q, const void* k, const
                                              const svg_perm_desc_t* perm, int32_t* done, int32_t done_words, int32_t nseg,
                                              void* stream) {
     if (!done || nseg <= 0) return SVG_ERR_BAD_ARG;
-    const int rc = band_check_args(q, k, v, o, BH, S, D, mask, perm);
-    if (rc != SVG_OK) return rc;
-    if ((int64_t)done_words < (int64_t)BH * (nseg + 1)) return SVG_ERR_WORKSPACE;   // segment counters + one hidden counter per head
     BandOpts opts;
     opts.done = done, opts.done_nseg = nseg;
-    return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, (hipStream_t)stream);
+    return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, done_words, nullptr, stream);
 }
 
 extern "C" int svg_band_attention_prescaled_notify_seg(const void* q_scaled, const void* k, const void* v, void* o, int32_t BH,
@@ -1037,12 +1012,9 @@ extern "C" int svg_band_attention_prescaled_notify_seg(const void* q_scaled, con
                                                        const svg_perm_desc_t* perm, int32_t* done, int32_t done_words, int32_t nseg,
                                                        void* stream) {
     if (!done || nseg <= 0) return SVG_ERR_BAD_ARG;
-    const int rc = band_check_args(q_scaled, k, v, o, BH, S, D, mask, perm);
-    if (rc != SVG_OK) return rc;
-    if ((int64_t)done_words < (int64_t)BH * (nseg + 1)) return SVG_ERR_WORKSPACE;
     BandOpts opts;
     opts.done = done, opts.done_nseg = nseg, opts.prescaled = true;
-    return band_dispatch(q_scaled, k, v, o, BH, S, D, dtype, 1.f, mask, perm, kBandAuto, opts, (hipStream_t)stream);
+    return band_dispatch(q_scaled, k, v, o, BH, S, D, dtype, 1.f, mask, perm, kBandAuto, opts, done_words, nullptr, stream);
 }
 
 extern "C" int svg_wait_counters(const int32_t* counters, int32_t n, int32_t target, void* stream) {
@@ -1059,92 +1031,39 @@ extern "C" int svg_wait_counters_deadline(const int32_t* counters, int32_t n, in
     return launch_status();
 }
 
-// svg_band_attention_switch (layout == nullptr: contiguous [BH, S, D] tensors) and svg_band_attention_switch_strided
-static int band_switch_entry(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t S, int32_t D, int32_t dtype,
-                             float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm, const svg_band_mask_t* alt_mask,
-                             const int32_t* use_alt_flag, const svg_attn_layout_t* layout, void* stream) {
-    if (!alt_mask || !use_alt_flag) return SVG_ERR_BAD_ARG;
-    int rc = band_check_args(q, k, v, o, BH, S, D, mask, perm);
-    if (rc == SVG_OK) rc = band_check_args(q, k, v, o, BH, S, D, alt_mask, nullptr);
-    if (rc != SVG_OK) return rc;
+// the device switch runs on the default schedule of the head size: the 16x16x32 body at head_dim 128 (attn_m16.h), the LEAN 32x32x16
+// one at 64 (band_attn_pp2_kernel<T, 64>); strided tensors as in svg_band_attention_strided
+static BandOpts switch_opts(const svg_band_mask_t* alt_mask, const int32_t* use_alt_flag) {
     BandOpts opts;
-    if (layout) {   // (both switch kernels run a two-phase body: strides as in svg_band_attention_strided)
-        opts.strided = true;
-        if (rc = layout_from_abi(layout, BH, BH, S, S, D, q, k, v, o, opts.lay); rc != SVG_OK) return rc;
-    }
-    if (D == 128 && (dtype == SVG_DTYPE_BF16 || dtype == SVG_DTYPE_F16)) {   // the default schedule of this head size (attn_m16.h)
-        auto go = [&](auto t_c) -> int {
-            using T = decltype(t_c);
-            using Pol = BandPolicy<T, 128, 8, false>;
-            const typename Pol::Params a = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
-            const typename Pol::Params b = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, alt_mask, nullptr, opts);
-            auto kern = band_attn_m16_switch_kernel<T>;
-            if (const int r2 = configure_lds((const void*)kern, attn_m16_lds_bytes()); r2 != SVG_OK) return r2;
-            hipLaunchKernelGGL(kern, dim3(std::max(a.nqt, b.nqt) * BH), dim3(512), attn_m16_lds_bytes(), (hipStream_t)stream, a, b, use_alt_flag);
-            return launch_status();
-        };
-        return dtype == SVG_DTYPE_BF16 ? go(__bf16{}) : go(_Float16{});
-    }
-    if (D == 64 && (dtype == SVG_DTYPE_BF16 || dtype == SVG_DTYPE_F16)) {    // ... and of this one (band_attn_pp2_kernel<T, 64>)
-        auto go = [&](auto t_c) -> int {
-            using T = decltype(t_c);
-            using Pol = BandPolicy<T, 64, 8, false>;
-            const typename Pol::Params a = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
-            const typename Pol::Params b = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, alt_mask, nullptr, opts);
-            auto kern = band_attn_pp2_switch64_kernel<T>;
-            if (const int r2 = configure_lds((const void*)kern, attn_pp2_lds_bytes<64>()); r2 != SVG_OK) return r2;
-            hipLaunchKernelGGL(kern, dim3(std::max(a.nqt, b.nqt) * BH), dim3(512), attn_pp2_lds_bytes<64>(), (hipStream_t)stream, a, b, use_alt_flag);
-            return launch_status();
-        };
-        return dtype == SVG_DTYPE_BF16 ? go(__bf16{}) : go(_Float16{});
-    }
-    return SVG_ERR_UNSUPPORTED;
+    opts.alt_mask = alt_mask, opts.use_alt = use_alt_flag;
+    return opts;
 }
 
 extern "C" int svg_band_attention_switch(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t S, int32_t D,
                                          int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
                                          const svg_band_mask_t* alt_mask, const int32_t* use_alt_flag, void* stream) {
-    return band_switch_entry(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, alt_mask, use_alt_flag, nullptr, stream);
+    if (!alt_mask || !use_alt_flag) return SVG_ERR_BAD_ARG;
+    return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, switch_opts(alt_mask, use_alt_flag), 0, nullptr,
+                         stream);
 }
 
 extern "C" int svg_band_attention_switch_strided(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t S, int32_t D,
                                                  int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
                                                  const svg_band_mask_t* alt_mask, const int32_t* use_alt_flag,
                                                  const svg_attn_layout_t* layout, void* stream) {
-    if (!layout) return SVG_ERR_BAD_ARG;
-    return band_switch_entry(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, alt_mask, use_alt_flag, layout, stream);
+    if (!layout || !alt_mask || !use_alt_flag) return SVG_ERR_BAD_ARG;
+    BandOpts opts = switch_opts(alt_mask, use_alt_flag);
+    opts.strided = true;
+    return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, 0, layout, stream);
 }
 
 extern "C" int svg_band_attention_switch_prescaled(const void* q_scaled, const void* k, const void* v, void* o, int32_t BH, int32_t S,
                                                    int32_t D, int32_t dtype, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
                                                    const svg_band_mask_t* alt_mask, const int32_t* use_alt_flag, void* stream) {
     if (!alt_mask || !use_alt_flag) return SVG_ERR_BAD_ARG;
-    int rc = band_check_args(q_scaled, k, v, o, BH, S, D, mask, perm);
-    if (rc == SVG_OK) rc = band_check_args(q_scaled, k, v, o, BH, S, D, alt_mask, nullptr);
-    if (rc != SVG_OK) return rc;
-    auto go = [&](auto t_c, auto d_c) -> int {
-        using T = decltype(t_c);
-        constexpr int DD = decltype(d_c)::value;
-        using Pol = BandPolicy<T, DD, 8, false>;
-        const typename Pol::Params a = make_band_params<Pol, T>(q_scaled, k, v, o, BH, S, 1.f, mask, perm);
-        const typename Pol::Params b = make_band_params<Pol, T>(q_scaled, k, v, o, BH, S, 1.f, alt_mask, nullptr);
-        if constexpr (DD == 128) {   // the PRE form of the 16x16x32 body, like svg_band_attention_prescaled at this head size
-            auto kern16 = band_attn_m16_switch_kernel<T, true, false>;
-            if (const int r2 = configure_lds((const void*)kern16, attn_m16_lds_bytes()); r2 != SVG_OK) return r2;
-            hipLaunchKernelGGL(kern16, dim3(std::max(a.nqt, b.nqt) * BH), dim3(512), attn_m16_lds_bytes(), (hipStream_t)stream, a, b, use_alt_flag);
-            return launch_status();
-        }
-        auto kern = band_attn_pp2q_switch_kernel<T, DD>;
-        if (const int r2 = configure_lds((const void*)kern, attn_pp2_lds_bytes<DD>()); r2 != SVG_OK) return r2;
-        hipLaunchKernelGGL(kern, dim3(std::max(a.nqt, b.nqt) * BH), dim3(512), attn_pp2_lds_bytes<DD>(), (hipStream_t)stream, a, b,
-                           use_alt_flag);
-        return launch_status();
-    };
-    if (dtype == SVG_DTYPE_BF16 && D == 128) return go(__bf16{}, std::integral_constant<int, 128>{});
-    if (dtype == SVG_DTYPE_BF16 && D == 64) return go(__bf16{}, std::integral_constant<int, 64>{});
-    if (dtype == SVG_DTYPE_F16 && D == 128) return go(_Float16{}, std::integral_constant<int, 128>{});
-    if (dtype == SVG_DTYPE_F16 && D == 64) return go(_Float16{}, std::integral_constant<int, 64>{});
-    return SVG_ERR_UNSUPPORTED;
+    BandOpts opts = switch_opts(alt_mask, use_alt_flag);
+    opts.prescaled = true;
+    return band_dispatch(q_scaled, k, v, o, BH, S, D, dtype, 1.f, mask, perm, kBandAuto, opts, 0, nullptr, stream);
 }
 
 extern "C" int svg_debug_wg_trace(uint64_t* out, int n_workgroups) {
@@ -1189,130 +1108,151 @@ extern "C" size_t svg_varblock_workspace_bytes(int32_t Hq, int32_t Hkv, int32_t 
 }
 
 namespace svg {
-// NW = 4 / 8: uniform tiling (128- / 256-row q tiles).  NW = 0: mixed tiling — the full 256-row tiles of every block-row run
-// on the 8-wave kernel, its remaining rows on 128-row tiles of the 4-wave kernel (two workgroups per CU).  k-means clusters are
-// ragged (Wan 720p bench: mean 252 rows, sigma 161): uniform 256-row tiles keep 68 % of the processed rows real, uniform
-// 128-row tiles 79 % but run the slower 4-wave schedule everywhere; mixed keeps 79 % with most rows on the 8-wave kernel.
-template <typename T, int D, int NW>
-static int run_varblock(const void* q, const void* k, const void* v, void* o, int Hq, int Hkv, int Sq, int Skv,
-                        float sm_scale, const uint8_t* block_map, const int32_t* q_sizes, const int32_t* k_sizes, int QB,
-                        int KB, const int32_t* q_row_idx, const int32_t* kv_row_idx, void* ws, bool block_row_order, bool trace,
-                        hipStream_t st, const F8GArgs* f8 = nullptr, int order_mode = 0, bool body_m16 = false,
-                        const AttnLayout* lay = nullptr) {
-    // body_m16 (NW == -8, head_dim 128): the two-phase body on 16x16x32 MFMAs (attn_m16.h) instead of the 32x32x16 one
-    int32_t* q_off = (int32_t*)ws;
-    int32_t* tile_off = q_off + (size_t)Hkv * (QB + 1);
-    int32_t* k_off = tile_off + (size_t)Hkv * (QB + 1);
-    int32_t* tile_off2 = k_off + (size_t)Hkv * (KB + 1);
-    hipLaunchKernelGGL(varblock_plan_kernel, dim3(Hkv), dim3(256), 0, st, q_sizes, k_sizes, q_off, k_off, tile_off, tile_off2, QB,
-                       KB, (NW == -9 ? kVbF8Waves : NW < 0 ? 8 : NW) * 32);
-    auto launch = [&](auto nw_c, int mode, const int32_t* toff, int max_tiles) -> int {
-        constexpr int W = decltype(nw_c)::value;
-        using Pol = VarblockPolicy<T, D, W>;
-        typename Pol::Params p;
+// The bodies of svg_varblock_attention* (`variant` picks one, include/svg_attn.h).  k-means clusters are ragged (Wan 720p bench: mean
+// 252 rows, sigma 161): uniform 256-row tiles keep 68 % of the processed rows real, uniform 128-row tiles 79 % but run the slower
+// 4-wave schedule everywhere; mixed keeps 79 % with most rows on the 8-wave kernel.
+enum class VbBody {
+    kLockstep128,   // lock-step body, 4 waves, 128-row q tiles (2-D grid)
+    kLockstep256,   // lock-step body, 8 waves, 256-row q tiles (2-D grid)
+    kMixed,         // the full 256-row tiles of every block-row on the 8-wave lock-step kernel, its remaining rows on 128-row tiles of the 4-wave one
+    kPP2,           // two-phase body on 32x32x16 MFMAs, 256-row q tiles (launch order, 1-D grid)
+    kM16,           // two-phase body on 16x16x32 MFMAs (attn_m16.h; head_dim 128), 256-row q tiles (launch order)
+    kF8,            // fp8 gathering body (attn_f8.h; head_dim 128), kVbF8Waves x 32-row q tiles (launch order)
+};
+
+// The workspace of a call (svg_varblock_workspace_bytes; _native.varblock_launch_order / varblock_partners read it at fixed offsets):
+// plan prefix sums, two buckets and the packing partner per block-row, the bucket histogram, the launch order (count, pad,
+// entries[3 * max workgroups]), then the bitmap rows of remainder packing (16-byte aligned).
+struct VbWs {
+    int32_t *q_off, *tile_off, *k_off, *tile_off2, *work, *partner, *hist, *order;
+    uint32_t* bits;
+};
+static VbWs vb_ws(void* ws, int Hq, int Hkv, int Sq, int QB, int KB) {
+    VbWs w;
+    w.q_off = (int32_t*)ws;
+    w.tile_off = w.q_off + (size_t)Hkv * (QB + 1);
+    w.k_off = w.tile_off + (size_t)Hkv * (QB + 1);
+    w.tile_off2 = w.k_off + (size_t)Hkv * (KB + 1);
+    w.work = w.tile_off2 + (size_t)Hkv * (QB + 1);   // [2 * Hkv * QB]
+    w.partner = w.work + 2 * (size_t)Hkv * QB;       // [Hkv * QB]
+    w.hist = w.partner + (size_t)Hkv * QB;           // [Hkv * kVbBuckets]
+    w.order = w.hist + (size_t)Hkv * kVbBuckets;
+    w.bits = (uint32_t*)(((uintptr_t)(w.order + 2 + 3 * ((size_t)Sq / 64 + QB) * Hq) + 15) & ~(uintptr_t)15);
+    return w;
+}
+
+// Launch order of the ordered bodies (BM-row q tiles) into w.order: the similarity order (order_mode 2), or longest-first inside every
+// kv head with the ragged last tiles packed in pairs (order_mode 0) or not (1).
+static int vb_launch_order(const VbWs& w, const uint8_t* block_map, const int32_t* q_sizes, const int32_t* k_sizes, int Hq, int Hkv,
+                           int QB, int KB, int BM, int order_mode, hipStream_t st) {
+    const int group = Hq / Hkv, nb = Hkv * kVbBuckets;
+    const size_t chain_lds = vb_chain_lds(QB, KB);
+    if (order_mode == 2 && chain_lds <= 64 * 1024 && QB <= 4096) {   // similarity order, consecutive workgroups on one XCD (variant 7)
+        hipLaunchKernelGGL(varblock_chain_kernel, dim3(Hkv), dim3(kVbChainThreads), chain_lds, st, block_map, k_sizes, w.tile_off,
+                           w.order, Hkv, QB, KB, group);
+        return SVG_OK;
+    }
+    const size_t pair_lds = vb_pair_lds(QB, KB);
+    const bool pack = order_mode == 0 && pair_lds <= 64 * 1024 && QB <= 4095 && KB <= 1024;   // (bitmap row in registers; 12-bit index in the arg-max key)
+    if (pack) {   // bitmap rows once, then kVbPairRounds x (score, match); scratch: the bitmap area behind the order, and the bucket
+                  // array `work` (free until varblock_work_kernel runs) for the remainders and choices
+        const int WSp = vb_pair_ws(KB);
+        int32_t* rem = w.work;
+        int32_t* best = w.work + (size_t)Hkv * QB;
+        const long long nw = (long long)Hkv * QB * WSp;
+        hipLaunchKernelGGL(varblock_bitmap_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, block_map, k_sizes, w.bits, Hkv,
+                           QB, KB, WSp);
+        for (int round = 0; round < kVbPairRounds; ++round) {
+            hipLaunchKernelGGL(varblock_pair_score_kernel, dim3((QB + kVbPairRows - 1) / kVbPairRows, Hkv), dim3(kVbPairThreads), pair_lds,
+                               st, w.bits, q_sizes, rem, best, QB, WSp, BM, round);
+            hipLaunchKernelGGL(varblock_pair_match_kernel, dim3((Hkv * QB + 255) / 256), dim3(256), 0, st, q_sizes, best, rem, w.partner,
+                               Hkv * QB, QB, BM, round);
+        }
+    }
+    if (hipMemsetAsync(w.hist, 0, (size_t)nb * sizeof(int32_t), st) != hipSuccess) return SVG_ERR_LAUNCH;
+    hipLaunchKernelGGL(varblock_work_kernel, dim3((Hkv * QB + 3) / 4), dim3(256), 0, st, block_map, q_sizes, k_sizes,
+                       pack ? w.partner : nullptr, w.work, w.hist, Hkv, QB, KB, group, BM);
+    hipLaunchKernelGGL(varblock_scan_kernel, dim3(1), dim3(256), 0, st, w.hist, w.order, nb);
+    hipLaunchKernelGGL(varblock_scatter_kernel, dim3((Hkv * QB + 255) / 256), dim3(256), 0, st, q_sizes, pack ? w.partner : nullptr,
+                       w.work, w.hist, w.order, Hkv, QB, group, BM);
+    return SVG_OK;
+}
+
+// One variable-block call in three steps: the plan (prefix sums), the launch order of the ordered bodies, the body.
+// block_row_order: the ordered bodies take the 2-D grid instead; trace: the two-phase body with the launch timeline (diagnostics builds).
+template <typename T, int D>
+static int run_varblock(VbBody body, const void* q, const void* k, const void* v, void* o, int Hq, int Hkv, int Sq, int Skv,
+                        float sm_scale, const uint8_t* block_map, const int32_t* q_sizes, const int32_t* k_sizes, int QB, int KB,
+                        const int32_t* q_row_idx, const int32_t* kv_row_idx, void* ws, bool block_row_order, bool trace, int order_mode,
+                        const AttnLayout* lay, const F8GArgs* f8, hipStream_t st) {
+    const VbWs w = vb_ws(ws, Hq, Hkv, Sq, QB, KB);
+    const bool ordered_body = body == VbBody::kPP2 || body == VbBody::kM16 || body == VbBody::kF8;
+    const int BM = body == VbBody::kMixed ? 0 : body == VbBody::kLockstep128 ? 128 : body == VbBody::kF8 ? kVbF8Waves * 32 : 256;
+    hipLaunchKernelGGL(varblock_plan_kernel, dim3(Hkv), dim3(256), 0, st, q_sizes, k_sizes, w.q_off, w.k_off, w.tile_off, w.tile_off2, QB,
+                       KB, BM);
+    const int32_t* order = nullptr;
+    if (ordered_body && !block_row_order && QB < 32768 && Sq / 256 + 1 < 65536) {   // packing of (block-row, sub-tile) in one word
+        if (const int rc = vb_launch_order(w, block_map, q_sizes, k_sizes, Hq, Hkv, QB, KB, BM, order_mode, st); rc != SVG_OK) return rc;
+        order = w.order;
+    }
+    const int kb_cap = (KB + 63) / 64 * 64, lds_vb = vb_policy_lds(kb_cap);
+    auto params = [&](auto nw_c, int mode, const int32_t* toff, int max_tiles) {
+        typename VarblockPolicy<T, D, decltype(nw_c)::value>::Params p;
         p.q = (const T*)q, p.k = (const T*)k, p.v = (const T*)v, p.o = (T*)o;
         p.Hq = Hq, p.Hkv = Hkv, p.group = Hq / Hkv, p.Sq = Sq, p.Skv = Skv, p.QB = QB, p.KB = KB;
         p.max_tiles = max_tiles;
         p.tile_mode = mode;
-        p.kb_cap = (KB + 63) / 64 * 64;
+        p.kb_cap = kb_cap;
         p.scale_log2 = sm_scale * 1.4426950408889634f;
-        p.block_map = block_map, p.q_off = q_off, p.k_off = k_off, p.tile_off = toff;
+        p.block_map = block_map, p.q_off = w.q_off, p.k_off = w.k_off, p.tile_off = toff;
         p.q_row_idx = q_row_idx, p.kv_row_idx = kv_row_idx;
         p.lay = lay ? *lay : contiguous_layout(Hq, Hkv, Sq, Skv, D);
-        p.order = nullptr;
-        if constexpr (NW == -8 || NW == -9) {
-            const int group = Hq / Hkv;
-            if (!block_row_order && QB < 32768 && Sq / 256 + 1 < 65536) {   // packing of (block-row, sub-tile) in one word
-                int32_t* work = tile_off2 + (size_t)Hkv * (QB + 1);          // [2 * Hkv * QB]
-                int32_t* partner = work + 2 * (size_t)Hkv * QB;              // [Hkv * QB]
-                int32_t* hist = partner + (size_t)Hkv * QB;
-                const int nb = Hkv * kVbBuckets;
-                int32_t* order = hist + nb;
-                constexpr int BMo = W * 32;
-                const size_t chain_lds = vb_chain_lds(QB, KB);
-                if (order_mode == 2 && chain_lds <= 64 * 1024 && QB <= 4096) {   // similarity order, consecutive workgroups on one XCD (variant 7)
-                    hipLaunchKernelGGL(varblock_chain_kernel, dim3(Hkv), dim3(kVbChainThreads), chain_lds, st, block_map, k_sizes, toff,
-                                       order, Hkv, QB, KB, group);
-                } else {   // longest-first inside every kv head, ragged last tiles packed in pairs (order_mode 0) or not (1)
-                    const size_t pair_lds = vb_pair_lds(QB, KB);
-                    const bool pack = order_mode == 0 && pair_lds <= 64 * 1024 && QB <= 4095 && KB <= 1024;   // (bitmap row in registers; 12-bit index in the arg-max key)
-                    if (pack) {   // bitmap rows once, then kVbPairRounds x (score, match); scratch: the bitmap area behind the order, and
-                                  // the bucket array `work` (free until varblock_work_kernel runs) for the remainders and choices
-                        const int WSp = vb_pair_ws(KB);
-                        uint32_t* bits = (uint32_t*)(((uintptr_t)(order + 2 + 3 * ((size_t)Sq / 64 + QB) * Hq) + 15) & ~(uintptr_t)15);
-                        int32_t* rem = work;
-                        int32_t* best = work + (size_t)Hkv * QB;
-                        const long long nw = (long long)Hkv * QB * WSp;
-                        hipLaunchKernelGGL(varblock_bitmap_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, block_map, k_sizes,
-                                           bits, Hkv, QB, KB, WSp);
-                        for (int round = 0; round < kVbPairRounds; ++round) {
-                            hipLaunchKernelGGL(varblock_pair_score_kernel, dim3((QB + kVbPairRows - 1) / kVbPairRows, Hkv),
-                                               dim3(kVbPairThreads), pair_lds, st, bits, q_sizes, rem, best, QB, WSp, BMo, round);
-                            hipLaunchKernelGGL(varblock_pair_match_kernel, dim3((Hkv * QB + 255) / 256), dim3(256), 0, st, q_sizes, best, rem,
-                                               partner, Hkv * QB, QB, BMo, round);
-                        }
-                    }
-                    if (hipMemsetAsync(hist, 0, (size_t)nb * sizeof(int32_t), st) != hipSuccess) return SVG_ERR_LAUNCH;
-                    hipLaunchKernelGGL(varblock_work_kernel, dim3((Hkv * QB + 3) / 4), dim3(256), 0, st, block_map, q_sizes, k_sizes,
-                                       pack ? partner : nullptr, work, hist, Hkv, QB, KB, group, BMo);
-                    hipLaunchKernelGGL(varblock_scan_kernel, dim3(1), dim3(256), 0, st, hist, order, nb);
-                    hipLaunchKernelGGL(varblock_scatter_kernel, dim3((Hkv * QB + 255) / 256), dim3(256), 0, st, q_sizes,
-                                       pack ? partner : nullptr, work, hist, order, Hkv, QB, group, BMo);
-                }
-                p.order = order;
-                if constexpr (NW == -9) {
-                    if constexpr (D == 128) {
-                        auto kern = varblock_attn_f8_kernel<T>;
-                        const int lds = attn_f8_lds_bytes<128, kVbF8Waves>() + vb_policy_lds(p.kb_cap);
-                        if (const int rc = configure_lds((const void*)kern, lds); rc != SVG_OK) return rc;
-                        hipLaunchKernelGGL(kern, dim3(p.max_tiles * Hq), dim3(kVbF8Waves * 64), lds, st, p, *f8);
-                        return launch_status();
-                    }
-                    return SVG_ERR_UNSUPPORTED;
-                } else {
-#ifdef SVG_ABLATIONS
-                    if constexpr (D == 128 && std::is_same<T, __bf16>::value) {
-                        if (trace)
-                            return launch_attn(varblock_attn_pp2_trace_kernel<T, D>, p, dim3(p.max_tiles * Hq), 512,
-                                               attn_pp2_lds_bytes<D>() + vb_policy_lds(p.kb_cap), st);
-                    }
-#endif
-                    if (trace) return SVG_ERR_UNSUPPORTED;   // diagnostics builds only (-DSVG_ABLATIONS)
-                    if constexpr (D == 128) {
-                        if (body_m16)
-                            return launch_attn(varblock_attn_m16_kernel<T>, p, dim3(p.max_tiles * Hq), 512,
-                                               attn_m16_lds_bytes() + vb_policy_lds(p.kb_cap), st);
-                    }
-                    return launch_attn(varblock_attn_pp2_kernel<T, D>, p, dim3(p.max_tiles * Hq), 512,
-                                       attn_pp2_lds_bytes<D>() + vb_policy_lds(p.kb_cap), st);
-                }
-            }
-            if constexpr (NW == -9)
-                return SVG_ERR_UNSUPPORTED;   // (the fp8 kernel takes the ordered 1-D launch only)
-            else {
-                if constexpr (D == 128) {
-                    if (body_m16)
-                        return launch_attn(varblock_attn_m16_kernel<T>, p, dim3(p.max_tiles, Hq), 512,
-                                           attn_m16_lds_bytes() + vb_policy_lds(p.kb_cap), st);
-                }
-                return launch_attn(varblock_attn_pp2_kernel<T, D>, p, dim3(p.max_tiles, Hq), 512,
-                                   attn_pp2_lds_bytes<D>() + vb_policy_lds(p.kb_cap), st);
-            }
-        } else
-            return launch_attn(varblock_attn_kernel<T, D, W>, p, dim3(p.max_tiles, Hq), W * 64,
-                               attn_lds_bytes<D, W>() + vb_policy_lds(p.kb_cap), st);
+        p.order = order;
+        return p;
     };
-    if constexpr (NW == 0) {
-        int rc = SVG_OK;
-        if (Sq >= kVbFull) rc = launch(std::integral_constant<int, 8>{}, 1, tile_off, Sq / kVbFull);
-        if (rc != SVG_OK) return rc;
-        return launch(std::integral_constant<int, 4>{}, 2, tile_off2, 2 * QB);
-    } else if constexpr (NW == -9) {   // fp8 body
-        return launch(std::integral_constant<int, kVbF8Waves>{}, 0, tile_off, Sq / (kVbF8Waves * 32) + QB);
-    } else if constexpr (NW == -8) {   // two-phase ping-pong body, 256-row q tiles
-        return launch(std::integral_constant<int, 8>{}, 0, tile_off, Sq / 256 + QB);
-    } else {
-        return launch(std::integral_constant<int, NW>{}, 0, tile_off, Sq / (NW * 32) + QB);
+    auto lockstep = [&](auto nw_c, int mode, const int32_t* toff, int max_tiles) {
+        constexpr int W = decltype(nw_c)::value;
+        return launch_attn(varblock_attn_kernel<T, D, W>, params(nw_c, mode, toff, max_tiles), dim3(max_tiles, Hq), W * 64,
+                           attn_lds_bytes<D, W>() + lds_vb, st);
+    };
+    using W4 = std::integral_constant<int, 4>;
+    using W8 = std::integral_constant<int, 8>;
+    switch (body) {
+        case VbBody::kLockstep128: return lockstep(W4{}, 0, w.tile_off, Sq / 128 + QB);
+        case VbBody::kLockstep256: return lockstep(W8{}, 0, w.tile_off, Sq / 256 + QB);
+        case VbBody::kMixed:
+            if (Sq >= kVbFull) {
+                if (const int rc = lockstep(W8{}, 1, w.tile_off, Sq / kVbFull); rc != SVG_OK) return rc;
+            }
+            return lockstep(W4{}, 2, w.tile_off2, 2 * QB);
+        case VbBody::kF8:
+            if constexpr (D == 128) {
+                if (!order) return SVG_ERR_UNSUPPORTED;   // (the fp8 kernel takes the ordered 1-D launch only)
+                const int max_tiles = Sq / (kVbF8Waves * 32) + QB;
+                const auto p = params(std::integral_constant<int, kVbF8Waves>{}, 0, w.tile_off, max_tiles);
+                auto kern = varblock_attn_f8_kernel<T>;
+                const int lds = attn_f8_lds_bytes<128, kVbF8Waves>() + lds_vb;
+                if (const int rc = configure_lds((const void*)kern, lds); rc != SVG_OK) return rc;
+                hipLaunchKernelGGL(kern, dim3(max_tiles * Hq), dim3(kVbF8Waves * 64), lds, st, p, *f8);
+                return launch_status();
+            }
+            return SVG_ERR_UNSUPPORTED;
+        default: {   // the two-phase bodies
+            const int max_tiles = Sq / 256 + QB;
+            const auto p = params(W8{}, 0, w.tile_off, max_tiles);
+            const dim3 grid = order ? dim3(max_tiles * Hq) : dim3(max_tiles, Hq);
+            if (order && trace) {
+#ifdef SVG_ABLATIONS
+                if constexpr (D == 128 && std::is_same<T, __bf16>::value)
+                    return launch_attn(varblock_attn_pp2_trace_kernel<T, D>, p, grid, 512, attn_pp2_lds_bytes<D>() + lds_vb, st);
+#endif
+                return SVG_ERR_UNSUPPORTED;   // diagnostics builds only (-DSVG_ABLATIONS)
+            }
+            if constexpr (D == 128) {
+                if (body == VbBody::kM16) return launch_attn(varblock_attn_m16_kernel<T>, p, grid, 512, attn_m16_lds_bytes() + lds_vb, st);
+            }
+            return launch_attn(varblock_attn_pp2_kernel<T, D>, p, grid, 512, attn_pp2_lds_bytes<D>() + lds_vb, st);
+        }
     }
 }
 }  // namespace svg
@@ -1325,7 +1265,7 @@ static int varblock_entry(const void* q, const void* k, const void* v, void* o, 
     if (!q || !k || !v || !o || !block_map || !q_sizes || !k_sizes || !workspace) return SVG_ERR_BAD_ARG;
     if (Hq <= 0 || Hkv <= 0 || Hq % Hkv != 0 || Sq <= 0 || Skv <= 0 || QB <= 0 || KB <= 0) return SVG_ERR_BAD_ARG;
     if (KB > kVbMaxKB) return SVG_ERR_UNSUPPORTED;
-    if ((int64_t)Skv * D * 2 >= (1ll << 32) || (int64_t)Sq * D * 2 >= (1ll << 32)) return SVG_ERR_UNSUPPORTED;
+    if (check_rows(Sq, D) != SVG_OK || check_rows(Skv, D) != SVG_OK) return SVG_ERR_UNSUPPORTED;
     if (workspace_bytes < svg_varblock_workspace_bytes(Hq, Hkv, QB, KB, Sq)) return SVG_ERR_WORKSPACE;
     AttnLayout lay_storage;
     const AttnLayout* lay = nullptr;
@@ -1333,7 +1273,6 @@ static int varblock_entry(const void* q, const void* k, const void* v, void* o, 
         if (const int rc = layout_from_abi(abi_layout, Hq, Hkv, Sq, Skv, D, q, k, v, o, lay_storage); rc != SVG_OK) return rc;
         lay = &lay_storage;
     }
-    hipStream_t st = (hipStream_t)stream;
     // variant 0: 4 waves, 128-row q tiles; 1: 8 waves, 256-row q tiles; 2: mixed (full 256-row tiles on 8 waves, rest on 4)
     // (6 = 3: the longest-first order is the default again — the similarity order, variant 7, raised the L2 hit rate from 31 % to 48 %
     //  and cut the L2 <-> fabric traffic by a quarter but not the kernel time, and its chain kernel costs 0.7 - 1.0 ms per call)
@@ -1343,32 +1282,21 @@ static int varblock_entry(const void* q, const void* k, const void* v, void* o, 
     if (variant == 8 || variant == 9) variant = 3;
     const bool block_row_order = (variant == 4), trace = (variant == 5);
     const int order_mode = variant == 7 ? 2 : (variant == 6 ? 1 : 0);   // 0: longest-first + remainder packing, 1: longest-first, 2: similarity order
-#define SVG_VB_ARGS q, k, v, o, Hq, Hkv, Sq, Skv, sm_scale, block_map, q_sizes, k_sizes, QB, KB, q_row_idx, kv_row_idx, workspace, block_row_order, trace, st, nullptr, order_mode, body_m16, lay
-#define SVG_VB_DISPATCH(T)                                                                       \
-    if (D == 128) {                                                                              \
-        if (variant == 2) return run_varblock<T, 128, 0>(SVG_VB_ARGS);                           \
-        if (variant >= 3) return run_varblock<T, 128, -8>(SVG_VB_ARGS);                          \
-        return variant == 1 ? run_varblock<T, 128, 8>(SVG_VB_ARGS) : run_varblock<T, 128, 4>(SVG_VB_ARGS); \
-    }                                                                                            \
-    if (D == 64) {                                                                               \
-        if (variant == 2) return run_varblock<T, 64, 0>(SVG_VB_ARGS);                            \
-        if (variant >= 3) return run_varblock<T, 64, -8>(SVG_VB_ARGS);                           \
-        return variant == 1 ? run_varblock<T, 64, 8>(SVG_VB_ARGS) : run_varblock<T, 64, 4>(SVG_VB_ARGS);   \
-    }
     if (variant < -1 || variant > 7) return SVG_ERR_BAD_ARG;
     // -1 (auto): 256-row q tiles with the two-phase ping-pong body once the average block-row is large enough to fill them
     // (Wan 720p, 252-row clusters: 40.4 ms; lock-step 8 waves 45.5, 4 waves 47.7, mixed 46.9), 128-row tiles otherwise
     if (variant == -1) variant = ((int64_t)Sq >= (int64_t)160 * QB) ? 3 : 0;
-    const bool body_m16 = (variant >= 3 && D == 128 && !force_pp2);
     if (lay && !(variant >= 3 && !trace)) return SVG_ERR_UNSUPPORTED;   // strided tensors: the two-phase bodies only (see svg_attn_layout_t)
-    if (dtype == SVG_DTYPE_BF16) {
-        SVG_VB_DISPATCH(__bf16)
-    } else if (dtype == SVG_DTYPE_F16) {
-        SVG_VB_DISPATCH(_Float16)
-    }
-#undef SVG_VB_ARGS
-#undef SVG_VB_DISPATCH
-    return SVG_ERR_UNSUPPORTED;
+    const VbBody body = variant == 0   ? VbBody::kLockstep128
+                        : variant == 1 ? VbBody::kLockstep256
+                        : variant == 2 ? VbBody::kMixed
+                        : (D == 128 && !force_pp2) ? VbBody::kM16
+                                                   : VbBody::kPP2;
+    return dispatch_td(dtype, D, [&](auto t, auto d) {
+        return run_varblock<decltype(t), decltype(d)::value>(body, q, k, v, o, Hq, Hkv, Sq, Skv, sm_scale, block_map, q_sizes, k_sizes, QB,
+                                                             KB, q_row_idx, kv_row_idx, workspace, block_row_order, trace, order_mode, lay,
+                                                             nullptr, (hipStream_t)stream);
+    });
 }
 
 extern "C" int svg_varblock_attention(const void* q, const void* k, const void* v, void* o, int32_t Hq, int32_t Hkv,
@@ -1405,20 +1333,15 @@ extern "C" int svg_varblock_attention_fp8(const void* q, const void* k, const vo
                                           void* stream) {
     if (!q || !k || !v || !o || !block_map || !q_sizes || !k_sizes || !workspace) return SVG_ERR_BAD_ARG;
     if (Hq <= 0 || Hkv <= 0 || Hq % Hkv != 0 || Sq <= 0 || Skv <= 0 || QB <= 0 || KB <= 0) return SVG_ERR_BAD_ARG;
-    if (D != 128 || KB > kVbMaxKB || QB >= 32768 || Sq / 256 + 1 >= 65536) return SVG_ERR_UNSUPPORTED;
-    if ((int64_t)Skv * D >= (1ll << 31) || (int64_t)Sq * D * 2 >= (1ll << 32)) return SVG_ERR_UNSUPPORTED;
+    if (D != 128 || KB > kVbMaxKB || QB >= 32768 || Sq / 256 + 1 >= 65536) return SVG_ERR_UNSUPPORTED;   // (e4m3 body: head_dim 128 only)
+    if (check_rows(Sq, D) != SVG_OK || check_rows(Skv, D) != SVG_OK) return SVG_ERR_UNSUPPORTED;
     if (workspace_bytes < svg_varblock_attention_fp8_workspace_bytes(Hq, Hkv, QB, KB, Sq, Skv, D)) return SVG_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const size_t plan = (svg_varblock_workspace_bytes(Hq, Hkv, QB, KB, Sq) + 255) & ~(size_t)255;
     F8GArgs fa;
-    int rc = f8g_quantize(q, k, v, Hq, Hkv, Sq, Skv, dtype, sm_scale, (char*)workspace + plan, &fa, st);
-    if (rc != SVG_OK) return rc;
-    if (dtype == SVG_DTYPE_BF16)
-        return run_varblock<__bf16, 128, -9>(q, k, v, o, Hq, Hkv, Sq, Skv, sm_scale, block_map, q_sizes, k_sizes, QB, KB, q_row_idx,
-                                            kv_row_idx, workspace, false, false, st, &fa);
-    if (dtype == SVG_DTYPE_F16)
-        return run_varblock<_Float16, 128, -9>(q, k, v, o, Hq, Hkv, Sq, Skv, sm_scale, block_map, q_sizes, k_sizes, QB, KB, q_row_idx,
-                                              kv_row_idx, workspace, false, false, st, &fa);
-    return SVG_ERR_UNSUPPORTED;
+    if (const int rc = f8g_quantize(q, k, v, Hq, Hkv, Sq, Skv, dtype, sm_scale, (char*)workspace + plan, &fa, st); rc != SVG_OK) return rc;
+    return dispatch_td(dtype, D, [&](auto t, auto d) {
+        return run_varblock<decltype(t), decltype(d)::value>(VbBody::kF8, q, k, v, o, Hq, Hkv, Sq, Skv, sm_scale, block_map, q_sizes, k_sizes,
+                                                             QB, KB, q_row_idx, kv_row_idx, workspace, false, false, 0, nullptr, &fa, st);
+    });
 }
-

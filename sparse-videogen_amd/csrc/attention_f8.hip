@@ -276,18 +276,13 @@ static int f8_entry(const void* q, const void* k, const void* v, void* o, int32_
                     const svg_band_mask_t* mask, const svg_perm_desc_t* perm, void* workspace, size_t workspace_bytes, int what,
                     void* stream) {
     if (!q || !k || !v || !o || !mask || !workspace || BH <= 0 || S <= 0) return SVG_ERR_BAD_ARG;
-    if (D != 128) return SVG_ERR_UNSUPPORTED;
-    if (mask->real_len < 0 || mask->real_len > S || mask->band < 0 || mask->band > S + 1) return SVG_ERR_BAD_ARG;
-    if (mask->colfull_lo > mask->colfull_hi || mask->rowfull_lo > mask->rowfull_hi) return SVG_ERR_BAD_ARG;
-    if (perm && perm->head_perm_flag) {
-        if (perm->num_frame <= 0 || perm->frame_size <= 0 || perm->vid0 < 0 ||
-            (int64_t)perm->vid0 + (int64_t)perm->num_frame * perm->frame_size > S)
-            return SVG_ERR_BAD_ARG;
-    }
+    if (D != 128) return SVG_ERR_UNSUPPORTED;   // (e4m3 bodies: head_dim 128 only)
+    if (const int rc = check_band_mask(S, mask, perm); rc != SVG_OK) return rc;
+    if (const int rc = check_rows(S, D); rc != SVG_OK) return rc;
     if (workspace_bytes < f8_ws_bytes(BH, S)) return SVG_ERR_WORKSPACE;
-    if (dtype == SVG_DTYPE_BF16) return run_f8<__bf16>(q, k, v, o, BH, S, sm_scale, mask, perm, workspace, BandOpts(), what, (hipStream_t)stream);
-    if (dtype == SVG_DTYPE_F16) return run_f8<_Float16>(q, k, v, o, BH, S, sm_scale, mask, perm, workspace, BandOpts(), what, (hipStream_t)stream);
-    return SVG_ERR_UNSUPPORTED;
+    return dispatch_td(dtype, D, [&](auto t, auto) {
+        return run_f8<decltype(t)>(q, k, v, o, BH, S, sm_scale, mask, perm, workspace, BandOpts(), what, (hipStream_t)stream);
+    });
 }
 
 extern "C" int svg_band_attention_fp8(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t S, int32_t D,

@@ -45,19 +45,12 @@ static int run_w4(const void* q, const void* k, const void* v, void* o, int BH, 
     return launch_attn(band_attn_w4_kernel<T, D>, p, dim3(p.nqt * BH), 256, attn_w4_lds_bytes<D>(), st);
 }
 
-#define SVG_W4_TD(FN, ...)                                                                      \
-    if (dtype == SVG_DTYPE_BF16 && D == 128) return FN<__bf16, 128>(__VA_ARGS__);               \
-    if (dtype == SVG_DTYPE_BF16 && D == 64) return FN<__bf16, 64>(__VA_ARGS__);                 \
-    if (dtype == SVG_DTYPE_F16 && D == 128) return FN<_Float16, 128>(__VA_ARGS__);              \
-    if (dtype == SVG_DTYPE_F16 && D == 64) return FN<_Float16, 64>(__VA_ARGS__);                \
-    return SVG_ERR_UNSUPPORTED;
-
 int run_band_w4(const void* q, const void* k, const void* v, void* o, int BH, int S, int D, int dtype, float sm_scale,
                 const svg_band_mask_t* mask, const svg_perm_desc_t* perm, const BandOpts& opts, hipStream_t st) {
-    SVG_W4_TD(run_w4, q, k, v, o, BH, S, sm_scale, mask, perm, opts, st)
+    return dispatch_td(dtype, D, [&](auto t, auto d) {
+        return run_w4<decltype(t), decltype(d)::value>(q, k, v, o, BH, S, sm_scale, mask, perm, opts, st);
+    });
 }
-
-#undef SVG_W4_TD
 
 int w4_read_trace(uint64_t* out104) {
 #ifdef SVG_ABLATIONS

@@ -17,7 +17,22 @@ struct BandOpts {
     int trace_abl = 0;         // ... and its timing ablation
     bool strided = false;      // `lay` describes the tensors (svg_band_attention_strided); otherwise contiguous [BH, S, D]
     AttnLayout lay{};
+    // device switch (svg_band_attention_switch*): `*use_alt != 0` on the device selects alt_mask without the layout permutation
+    const svg_band_mask_t* alt_mask = nullptr;
+    const int32_t* use_alt = nullptr;
 };
+
+// the mask and the head permutation of a band call over S rows (mask != nullptr)
+inline int check_band_mask(int S, const svg_band_mask_t* mask, const svg_perm_desc_t* perm) {
+    if (mask->real_len < 0 || mask->real_len > S || mask->band < 0 || mask->band > S + 1) return SVG_ERR_BAD_ARG;
+    if (mask->colfull_lo > mask->colfull_hi || mask->rowfull_lo > mask->rowfull_hi) return SVG_ERR_BAD_ARG;
+    if (perm && perm->head_perm_flag) {
+        if (perm->num_frame <= 0 || perm->frame_size <= 0 || perm->vid0 < 0 ||
+            (int64_t)perm->vid0 + (int64_t)perm->num_frame * perm->frame_size > S)
+            return SVG_ERR_BAD_ARG;
+    }
+    return SVG_OK;
+}
 
 // =====================================================================================================
 // Band policy: analytic mask family (see svg_band_mask_t in svg_attn.h)

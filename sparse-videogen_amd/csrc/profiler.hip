@@ -881,14 +881,10 @@ static int sample_mse_entry(const void* q, const void* k, const void* v, const i
         if (const int rc = layout_from_abi(&a, BH, BH, S, S, D, q, k, v, q, lay_storage); rc != SVG_OK) return rc;
         lay = &lay_storage;
     }
-    if (dtype == SVG_DTYPE_BF16) {
-        if (D == 128) return run_profile<__bf16, 128>(q, k, v, rows, R, BH, S, sm_scale, prof, out_mse, workspace, skip_flag, lay, st);
-        if (D == 64) return run_profile<__bf16, 64>(q, k, v, rows, R, BH, S, sm_scale, prof, out_mse, workspace, skip_flag, lay, st);
-    } else if (dtype == SVG_DTYPE_F16) {
-        if (D == 128) return run_profile<_Float16, 128>(q, k, v, rows, R, BH, S, sm_scale, prof, out_mse, workspace, skip_flag, lay, st);
-        if (D == 64) return run_profile<_Float16, 64>(q, k, v, rows, R, BH, S, sm_scale, prof, out_mse, workspace, skip_flag, lay, st);
-    }
-    return SVG_ERR_UNSUPPORTED;
+    return dispatch_td(dtype, D, [&](auto t, auto d) {
+        if (const int rc = check_rows(S, d); rc != SVG_OK) return rc;
+        return run_profile<decltype(t), decltype(d)::value>(q, k, v, rows, R, BH, S, sm_scale, prof, out_mse, workspace, skip_flag, lay, st);
+    });
 }
 
 extern "C" int svg_sample_mse_flagged(const void* q, const void* k, const void* v, const int64_t* rows, int32_t R, int32_t BH,

@@ -141,6 +141,25 @@ inline int layout_from_abi(const svg_attn_layout_t* a, int Hq, int Hkv, long lon
     l.o_bs = a->o.batch, l.o_hs = a->o.head, l.o_rs = (int)a->o.row;
     return SVG_OK;
 }
+// Rows of one head the attention and profiler kernels can address: the LDS-DMA requests carry 32-bit byte offsets per head
+// (S * D * 2 < 2^32) and compute a row's offset as __umul24(row, row stride in bytes) (S < 2^24).
+inline int check_rows(long long S, int D) {
+    return (S >= (1ll << 24) || S * D * 2 >= (1ll << 32)) ? SVG_ERR_UNSUPPORTED : SVG_OK;
+}
+
+// fn(T{}, std::integral_constant<int, D>{}) for the element types and head sizes the attention kernels are built for
+// (bf16 / fp16 x 64 / 128); SVG_ERR_UNSUPPORTED for any other pair.
+template <typename F>
+inline int dispatch_td(int dtype, int D, F&& fn) {
+    using D64 = std::integral_constant<int, 64>;
+    using D128 = std::integral_constant<int, 128>;
+    if (dtype == SVG_DTYPE_BF16 && D == 128) return fn(__bf16{}, D128{});
+    if (dtype == SVG_DTYPE_BF16 && D == 64) return fn(__bf16{}, D64{});
+    if (dtype == SVG_DTYPE_F16 && D == 128) return fn(_Float16{}, D128{});
+    if (dtype == SVG_DTYPE_F16 && D == 64) return fn(_Float16{}, D64{});
+    return SVG_ERR_UNSUPPORTED;
+}
+
 __device__ __forceinline__ size_t layout_head_off(long long bs, long long hs, int hpb, int head) {
     const int b = head / hpb;   // (wave-uniform: scalar unit, once per workgroup)
     return (size_t)b * (size_t)bs + (size_t)(head - b * hpb) * (size_t)hs;

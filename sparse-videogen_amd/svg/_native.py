@@ -315,6 +315,33 @@ def strided_attention_supported(q: torch.Tensor, variant: int = 0) -> bool:
     return q.shape[-1] in (64, 128) and variant == 0 and q.dtype in (torch.bfloat16, torch.float16)
 
 
+def _try_strided(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: Optional[torch.Tensor], token_major_out: bool, name: str,
+                 call) -> Optional[torch.Tensor]:
+    """Run the *_strided entry point `name` as call(o4, layout) on [B, H, S, D] views of q, k, v and of the output (`out`, or a new
+    tensor, token-major when asked) and return the output; None when the views cannot be read / written in place."""
+    q4, k4, v4 = _view4(q), _view4(k), _view4(v)
+    o4 = _view4(out) if out is not None else (token_major_empty(q4) if token_major_out else torch.empty(q4.shape, dtype=q.dtype, device=q.device))
+    if not (_strided_ok(q4) and _strided_ok(k4, True) and _strided_ok(v4, True) and _strided_ok(o4) and o4.shape == q4.shape):
+        return None
+    _check(call(o4, attn_layout(q4, k4, v4, o4)), name)
+    return out if out is not None else (o4 if q.dim() == 4 else o4.squeeze(0))
+
+
+def _sm_scale(sm_scale: Optional[float], D: int) -> float:
+    return float(sm_scale) if sm_scale is not None else 1.0 / (D ** 0.5)
+
+
+def _perm_arg(head_perm_flag: Optional[torch.Tensor], BH: int, vid0: int, num_frame: int, frame_size: int):
+    """The svg_perm_desc_t argument of the fused head placement (None without flags); it keeps its int64 flag tensor alive."""
+    if head_perm_flag is None:
+        return None
+    flag = head_perm_flag.to(torch.int64).contiguous()
+    assert flag.numel() == BH
+    perm = PermDesc(flag.data_ptr(), vid0, num_frame, frame_size)
+    perm.flag = flag
+    return C.byref(perm)
+
+
 # ------------------------------------------------------------------------------------------------------
 # typed wrappers (torch tensors in, torch tensors out)
 # ------------------------------------------------------------------------------------------------------
@@ -379,65 +406,77 @@ def band_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Band
     done: int32 [BH * (done_nseg + 1)] zeroed completion counters (svg_band_attention_notify[_seg]; see band_notify_target /
     band_notify_layout / wait_counters / notify_counters): counter (h, s) at done[h * done_nseg + s], the last BH words are scratch
     of the library (hidden per-head counters of heads that run with the fused layout permutation)."""
+    return _band_attention(q, k, v, mask, None, None, sm_scale, head_perm_flag, vid0, num_frame, frame_size, variant, out, done, done_nseg,
+                           q_prescaled, token_major_out)
+
+
+def _band_attention(q, k, v, mask, alt_mask, use_alt_flag, sm_scale, head_perm_flag, vid0, num_frame, frame_size, variant, out, done,
+                    done_nseg, q_prescaled, token_major_out):
+    """band_attention, and band_attention_switch when use_alt_flag is given"""
     lib = load()
     _dev(head_perm_flag)
     _gpu(q, k, v, out)
     assert q.shape == k.shape == v.shape and q.dtype == k.dtype == v.dtype
     S, D = q.shape[-2], q.shape[-1]
     BH = q.numel() // (S * D)
-    scale = float(sm_scale) if sm_scale is not None else 1.0 / (D ** 0.5)
-    perm = None
-    if head_perm_flag is not None:
-        flag = head_perm_flag.to(torch.int64).contiguous()
-        assert flag.numel() == BH
-        perm = PermDesc(flag.data_ptr(), vid0, num_frame, frame_size)
+    scale = _sm_scale(sm_scale, D)
+    perm = _perm_arg(head_perm_flag, BH, vid0, num_frame, frame_size)
+    switch = use_alt_flag is not None
     dense_in = q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and (out is None or out.is_contiguous())
     if (not dense_in or (token_major_out and out is None)) and done is None and not q_prescaled and strided_attention_supported(q, variant):
-        q4, k4, v4 = _view4(q), _view4(k), _view4(v)
-        o4 = _view4(out) if out is not None else (token_major_empty(q4) if token_major_out else torch.empty(q4.shape, dtype=q.dtype, device=q.device))
-        if _strided_ok(q4) and _strided_ok(k4, True) and _strided_ok(v4, True) and _strided_ok(o4) and o4.shape == q4.shape:
-            lay = attn_layout(q4, k4, v4, o4)
-            rc = lib.svg_band_attention_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), BH, S, D, _dtype_code(q), scale,
-                                                C.byref(mask), C.byref(perm) if perm is not None else None, C.byref(lay), _stream())
-            _check(rc, "svg_band_attention_strided")
-            return out if out is not None else (o4 if q.dim() == 4 else o4.squeeze(0))
+        if switch:
+            o = _try_strided(q, k, v, out, token_major_out, "svg_band_attention_switch_strided", lambda o4, lay: lib.svg_band_attention_switch_strided(
+                q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), BH, S, D, _dtype_code(q), scale, C.byref(mask), perm,
+                C.byref(alt_mask), use_alt_flag.data_ptr(), C.byref(lay), _stream()))
+        else:
+            o = _try_strided(q, k, v, out, token_major_out, "svg_band_attention_strided", lambda o4, lay: lib.svg_band_attention_strided(
+                q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), BH, S, D, _dtype_code(q), scale, C.byref(mask), perm, C.byref(lay),
+                _stream()))
+        if o is not None:
+            return o
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()   # (what no strided entry point takes is copied, as the reference does)
     if out is not None and not out.is_contiguous():
-        out.copy_(band_attention(q, k, v, mask, sm_scale, head_perm_flag, vid0, num_frame, frame_size, variant, None, done, done_nseg,
-                                 q_prescaled))
+        out.copy_(_band_attention(q, k, v, mask, alt_mask, use_alt_flag, sm_scale, head_perm_flag, vid0, num_frame, frame_size, variant,
+                                  None, done, done_nseg, q_prescaled, False))
         return out
     o = torch.empty_like(q) if out is None else out
-    if q_prescaled and done is not None:
-        _dev(done)
-        assert done.dtype == torch.int32 and done.is_contiguous() and variant == 0 and sm_scale is None
-        rc = lib.svg_band_attention_prescaled_notify_seg(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), BH, S, D,
-                                                         _dtype_code(q), C.byref(mask), C.byref(perm) if perm is not None else None,
-                                                         done.data_ptr(), int(done.numel()), int(done_nseg), _stream())
-        _check(rc, "svg_band_attention_prescaled_notify_seg")
-        return o
-    if q_prescaled:
-        assert variant == 0 and sm_scale is None, "q_prescaled: default-schedule call, the scale lives in q"
-        rc = lib.svg_band_attention_prescaled(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), BH, S, D, _dtype_code(q),
-                                              C.byref(mask), C.byref(perm) if perm is not None else None, _stream())
-        _check(rc, "svg_band_attention_prescaled")
-        return o
     if done is not None:
         _dev(done)
         assert done.dtype == torch.int32 and done.is_contiguous() and variant == 0
+    if q_prescaled:
+        assert variant == 0 and sm_scale is None, "q_prescaled: default-schedule call, the scale lives in q"
+    if switch and q_prescaled:
+        rc = lib.svg_band_attention_switch_prescaled(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), BH, S, D, _dtype_code(q),
+                                                     C.byref(mask), perm, C.byref(alt_mask), use_alt_flag.data_ptr(), _stream())
+        _check(rc, "svg_band_attention_switch_prescaled")
+    elif switch:
+        rc = lib.svg_band_attention_switch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), BH, S, D, _dtype_code(q), scale,
+                                           C.byref(mask), perm, C.byref(alt_mask), use_alt_flag.data_ptr(), _stream())
+        _check(rc, "svg_band_attention_switch")
+    elif q_prescaled and done is not None:
+        rc = lib.svg_band_attention_prescaled_notify_seg(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), BH, S, D,
+                                                         _dtype_code(q), C.byref(mask), perm, done.data_ptr(), int(done.numel()),
+                                                         int(done_nseg), _stream())
+        _check(rc, "svg_band_attention_prescaled_notify_seg")
+    elif q_prescaled:
+        rc = lib.svg_band_attention_prescaled(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), BH, S, D, _dtype_code(q),
+                                              C.byref(mask), perm, _stream())
+        _check(rc, "svg_band_attention_prescaled")
+    elif done is not None:
         rc = lib.svg_band_attention_notify_seg(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), BH, S, D, _dtype_code(q),
-                                               scale, C.byref(mask), C.byref(perm) if perm is not None else None, done.data_ptr(),
-                                               int(done.numel()), int(done_nseg), _stream())   # too small: SVG_ERR_WORKSPACE
+                                               scale, C.byref(mask), perm, done.data_ptr(), int(done.numel()), int(done_nseg),
+                                               _stream())   # too small: SVG_ERR_WORKSPACE
         _check(rc, "svg_band_attention_notify_seg")
-        return o
-    rc = lib.svg_band_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), BH, S, D, _dtype_code(q), scale,
-                                C.byref(mask), C.byref(perm) if perm is not None else None, variant, _stream())
-    _check(rc, "svg_band_attention")
+    else:
+        rc = lib.svg_band_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), BH, S, D, _dtype_code(q), scale,
+                                    C.byref(mask), perm, variant, _stream())
+        _check(rc, "svg_band_attention")
     return o
 
 
 def softmax_q_scale(D: int, sm_scale: Optional[float] = None) -> float:
     """The factor a pre-scaled q carries: sm_scale * log2(e) (default sm_scale = 1 / sqrt(D))."""
-    return (float(sm_scale) if sm_scale is not None else 1.0 / (D ** 0.5)) * 1.4426950408889634
+    return _sm_scale(sm_scale, D) * 1.4426950408889634
 
 
 class WorkspaceCache:
@@ -491,12 +530,8 @@ def band_attention_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: 
     BH = q.numel() // (S * D)
     o = torch.empty_like(q) if out is None else out
     _dev(o)
-    scale = float(sm_scale) if sm_scale is not None else 1.0 / (D ** 0.5)
-    perm = None
-    if head_perm_flag is not None:
-        flag = head_perm_flag.to(torch.int64).contiguous()
-        assert flag.numel() == BH
-        perm = PermDesc(flag.data_ptr(), vid0, num_frame, frame_size)
+    scale = _sm_scale(sm_scale, D)
+    perm = _perm_arg(head_perm_flag, BH, vid0, num_frame, frame_size)
     need = int(lib.svg_band_attention_fp8_workspace_bytes(BH, S, D))
     if need == 0:
         raise RuntimeError(f"svg_band_attention_fp8: unsupported shape (D = {D}; only 128)")
@@ -507,8 +542,8 @@ def band_attention_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: 
             workspace = _F8_WS[key] = torch.empty(need, dtype=torch.uint8, device=q.device)
     _dev(workspace)
     assert workspace.dtype == torch.uint8 and workspace.numel() >= need
-    args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), BH, S, D, _dtype_code(q), scale, C.byref(mask),
-            C.byref(perm) if perm is not None else None, workspace.data_ptr(), workspace.numel())
+    args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), BH, S, D, _dtype_code(q), scale, C.byref(mask), perm,
+            workspace.data_ptr(), workspace.numel())
     if stage:
         _check(lib.svg_band_attention_fp8_stage(*args, int(stage), _stream()), "svg_band_attention_fp8_stage")
     else:
@@ -563,48 +598,10 @@ def band_attention_switch(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
     placement, otherwise `mask` with it (svg_band_attention_switch) — no host read of the flag.
     q_prescaled: q carries sm_scale * log2(e) (svg_band_attention_switch_prescaled, D = 128).
     Strided views / token_major_out: as band_attention (svg_band_attention_switch_strided: head_dim 128, plain q)."""
-    lib = load()
-    _dev(head_perm_flag, use_alt_flag)
-    _gpu(q, k, v, out)
-    assert q.shape == k.shape == v.shape and q.dtype == k.dtype == v.dtype
+    _dev(use_alt_flag)
     assert use_alt_flag.dtype == torch.int32 and use_alt_flag.numel() >= 1
-    S, D = q.shape[-2], q.shape[-1]
-    BH = q.numel() // (S * D)
-    scale = float(sm_scale) if sm_scale is not None else 1.0 / (D ** 0.5)
-    perm = None
-    if head_perm_flag is not None:
-        flag = head_perm_flag.to(torch.int64).contiguous()
-        assert flag.numel() == BH
-        perm = PermDesc(flag.data_ptr(), vid0, num_frame, frame_size)
-    dense_in = q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and (out is None or out.is_contiguous())
-    if (not dense_in or (token_major_out and out is None)) and not q_prescaled and strided_attention_supported(q):
-        q4, k4, v4 = _view4(q), _view4(k), _view4(v)
-        o4 = _view4(out) if out is not None else (token_major_empty(q4) if token_major_out else torch.empty(q4.shape, dtype=q.dtype, device=q.device))
-        if _strided_ok(q4) and _strided_ok(k4, True) and _strided_ok(v4, True) and _strided_ok(o4) and o4.shape == q4.shape:
-            lay = attn_layout(q4, k4, v4, o4)
-            rc = lib.svg_band_attention_switch_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), BH, S, D, _dtype_code(q),
-                                                       scale, C.byref(mask), C.byref(perm) if perm is not None else None,
-                                                       C.byref(alt_mask), use_alt_flag.data_ptr(), C.byref(lay), _stream())
-            _check(rc, "svg_band_attention_switch_strided")
-            return out if out is not None else (o4 if q.dim() == 4 else o4.squeeze(0))
-    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-    if out is not None and not out.is_contiguous():
-        out.copy_(band_attention_switch(q, k, v, mask, alt_mask, use_alt_flag, sm_scale, head_perm_flag, vid0, num_frame, frame_size, None,
-                                        q_prescaled))
-        return out
-    o = torch.empty_like(q) if out is None else out
-    if q_prescaled:
-        assert sm_scale is None, "q_prescaled: the scale lives in q"
-        rc = lib.svg_band_attention_switch_prescaled(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), BH, S, D, _dtype_code(q),
-                                                     C.byref(mask), C.byref(perm) if perm is not None else None, C.byref(alt_mask),
-                                                     use_alt_flag.data_ptr(), _stream())
-        _check(rc, "svg_band_attention_switch_prescaled")
-        return o
-    rc = lib.svg_band_attention_switch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), BH, S, D, _dtype_code(q), scale,
-                                       C.byref(mask), C.byref(perm) if perm is not None else None, C.byref(alt_mask),
-                                       use_alt_flag.data_ptr(), _stream())
-    _check(rc, "svg_band_attention_switch")
-    return o
+    return _band_attention(q, k, v, mask, alt_mask, use_alt_flag, sm_scale, head_perm_flag, vid0, num_frame, frame_size, 0, out, None, 1,
+                           q_prescaled, token_major_out)
 
 
 def varblock_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_map: torch.Tensor, q_sizes: torch.Tensor,
@@ -634,25 +631,24 @@ def varblock_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_
         assert q_row_idx.dtype == torch.int32 and q_row_idx.shape == (Hq, Sq)
     if kv_row_idx is not None:
         assert kv_row_idx.dtype == torch.int32 and kv_row_idx.shape == (Hkv, Skv)
-    scale = float(sm_scale) if sm_scale is not None else 1.0 / (D ** 0.5)
+    scale = _sm_scale(sm_scale, D)
     dense_in = q.is_contiguous() and k.is_contiguous() and v.is_contiguous()
     if (not dense_in or token_major_out) and not fp8 and variant == -1 and strided_attention_supported(q) and Sq >= 160 * QB:
-        q4, k4, v4 = _view4(q), _view4(k), _view4(v)
-        o4 = token_major_empty(q4) if token_major_out else torch.empty(q4.shape, dtype=q.dtype, device=q.device)
-        if _strided_ok(q4) and _strided_ok(k4, True) and _strided_ok(v4, True) and _strided_ok(o4):
+        def call(o4, lay):
             if not rows_covered:
                 o4.zero_()
             need = int(lib.svg_varblock_workspace_bytes(Hq, Hkv, QB, KB, Sq))
             ws = torch.empty(need, dtype=torch.uint8, device=q.device) if workspace is None else workspace
             _dev(ws)
             assert ws.dtype == torch.uint8 and ws.numel() >= need
-            lay = attn_layout(q4, k4, v4, o4)
-            rc = lib.svg_varblock_attention_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), Hq, Hkv, Sq, Skv, D,
-                                                    _dtype_code(q), scale, block_map.data_ptr(), q_sizes.data_ptr(), k_sizes.data_ptr(),
-                                                    QB, KB, _ptr(q_row_idx), _ptr(kv_row_idx), ws.data_ptr(), ws.numel(), C.byref(lay),
-                                                    _stream())
-            _check(rc, "svg_varblock_attention_strided")
-            return o4 if q.dim() == 4 else o4.squeeze(0)
+            return lib.svg_varblock_attention_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), Hq, Hkv, Sq, Skv, D,
+                                                      _dtype_code(q), scale, block_map.data_ptr(), q_sizes.data_ptr(), k_sizes.data_ptr(),
+                                                      QB, KB, _ptr(q_row_idx), _ptr(kv_row_idx), ws.data_ptr(), ws.numel(), C.byref(lay),
+                                                      _stream())
+
+        o = _try_strided(q, k, v, None, token_major_out, "svg_varblock_attention_strided", call)
+        if o is not None:
+            return o
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()   # (what the strided entry point does not take is copied)
     o = torch.empty_like(q) if rows_covered else torch.zeros_like(q)
     if fp8:
@@ -687,7 +683,7 @@ def varblock_workspace(Hq: int, Hkv: int, QB: int, KB: int, Sq: int, device) -> 
 def varblock_launch_order(workspace: torch.Tensor, Hkv: int, QB: int, KB: int):
     """The launch order a 256-row variable-block call (variants 3 / 6 / 7) left in its workspace: int32 [n, 3] rows of
     (q head, block-row << 16 | sub-tile, partner) in dispatch order — partner >= 0: the tile also carries the ragged last tile of
-    that block-row (remainder packing) — (layout: csrc/attention.hip run_varblock: plan prefix sums, two buckets + the partner per
+    that block-row (remainder packing) — (layout: csrc/attention.hip VbWs: plan prefix sums, two buckets + the partner per
     block-row, histogram, then [count, pad, entries])."""
     w = workspace.view(torch.int32)
     off = Hkv * (3 * (QB + 1) + (KB + 1)) + 3 * Hkv * QB + Hkv * 64
@@ -759,7 +755,7 @@ def sample_mse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rows: torch.Te
     R = rows.numel()
     out = torch.empty((2, BH), dtype=torch.float32, device=q.device)
     ws = torch.empty(lib.svg_sample_mse_workspace_bytes(BH, R, D, S), dtype=torch.uint8, device=q.device)
-    scale = float(sm_scale) if sm_scale is not None else 1.0 / (D ** 0.5)
+    scale = _sm_scale(sm_scale, D)
     if not (q.is_contiguous() and k.is_contiguous() and v.is_contiguous()) and q.dtype == torch.bfloat16:
         q4, k4, v4 = _view4(q), _view4(k), _view4(v)
         if _strided_ok(q4) and _strided_ok(k4, True) and _strided_ok(v4, True):
