@@ -13,9 +13,9 @@ namespace svg {
 // lock-step schedule, NW waves x 32 rows (attn_body): every wave runs QK^T -> softmax -> PV per tile.  The reference schedule of
 // the test-suite (variant 1, 4 waves: two workgroups per CU) and the body of the 128-row variable-block kernel and the profiler.
 template <typename T, int D, int NW>
-__global__ __launch_bounds__(NW * 64, 2) void band_attn_kernel(typename BandPolicy<T, D, NW, false>::Params prm) {
+__global__ __launch_bounds__(NW * 64, 2) void band_attn_kernel(typename BandPolicy<T, D, NW>::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_body<T, D, NW, BandPolicy<T, D, NW, false>>(prm, smem, nullptr);
+    attn_body<T, D, NW, BandPolicy<T, D, NW>>(prm, smem, nullptr);
 }
 
 // two-phase ping-pong schedule, 8 waves x 32 rows (attn_body_pp2): variant 2
@@ -25,91 +25,88 @@ __global__ __launch_bounds__(NW * 64, 2) void band_attn_kernel(typename BandPoli
 // four 49 % — 18 % fewer cycles per launch; the chip then meets its power limit at head_dim 64 too and gives back part of it: −10.7 % in
 // time on CogVideoX-v1.5, bit-identical output (profiles/r04zr_ab_d64_four_waves.txt, r04zs_*).
 template <typename T, int D>
-__global__ __launch_bounds__(512, (D == 64 ? 4 : 2)) void band_attn_pp2_kernel(typename BandPolicy<T, D, 8, false>::Params prm) {
+__global__ __launch_bounds__(512, (D == 64 ? 4 : 2)) void band_attn_pp2_kernel(typename BandPolicy<T, D, 8>::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_body_pp2<T, D, BandPolicy<T, D, 8, false>, false, 0, false, D == 64>(prm, smem, nullptr);
+    attn_body_pp2<T, D, BandPolicy<T, D, 8>, false, 0, false, D == 64>(prm, smem, nullptr);
 }
 // svg_band_attention_switch at head_dim 64: band_attn_pp2_kernel<T, 64> — four waves per SIMD, the LEAN form of the body — with the
 // device-side choice between two parameter blocks in front of it (`flag[0] != 0` selects prm_alt, the dense warm-up mask without the
 // layout transformation — the dense / sparse decision of attention_core_logic, hyvideo/attention.py:491-496, without reading the timestep
 // back to the host; a one-wave-per-SIMD switch kernel served this head size until the end of round 4)
 template <typename T>
-__global__ __launch_bounds__(512, 4) void band_attn_pp2_switch64_kernel(typename BandPolicy<T, 64, 8, false>::Params prm,
-                                                                        typename BandPolicy<T, 64, 8, false>::Params prm_alt,
+__global__ __launch_bounds__(512, 4) void band_attn_pp2_switch64_kernel(typename BandPolicy<T, 64, 8>::Params prm,
+                                                                        typename BandPolicy<T, 64, 8>::Params prm_alt,
                                                                         const int32_t* __restrict__ flag) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (flag[0] != 0) attn_body_pp2<T, 64, BandPolicy<T, 64, 8, false>, false, 0, false, true>(prm_alt, smem, nullptr);
-    else attn_body_pp2<T, 64, BandPolicy<T, 64, 8, false>, false, 0, false, true>(prm, smem, nullptr);
+    if (flag[0] != 0) attn_body_pp2<T, 64, BandPolicy<T, 64, 8>, false, 0, false, true>(prm_alt, smem, nullptr);
+    else attn_body_pp2<T, 64, BandPolicy<T, 64, 8>, false, 0, false, true>(prm, smem, nullptr);
 }
 // Device-side switch between two masks on the pre-scaled two-phase body (svg_band_attention_switch_prescaled): `flag[0] != 0`
 // selects prm_alt — the dense warm-up mask without the layout transformation — otherwise prm (see band_attn_pp2_switch64_kernel)
 template <typename T, int D>
-__global__ __launch_bounds__(512, 2) void band_attn_pp2q_switch_kernel(typename BandPolicy<T, D, 8, false>::Params prm,
-                                                                       typename BandPolicy<T, D, 8, false>::Params prm_alt,
+__global__ __launch_bounds__(512, 2) void band_attn_pp2q_switch_kernel(typename BandPolicy<T, D, 8>::Params prm,
+                                                                       typename BandPolicy<T, D, 8>::Params prm_alt,
                                                                        const int32_t* __restrict__ flag) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (flag[0] != 0) attn_body_pp2<T, D, BandPolicy<T, D, 8, false>, false, 0, true>(prm_alt, smem, nullptr);
-    else attn_body_pp2<T, D, BandPolicy<T, D, 8, false>, false, 0, true>(prm, smem, nullptr);
+    if (flag[0] != 0) attn_body_pp2<T, D, BandPolicy<T, D, 8>, false, 0, true>(prm_alt, smem, nullptr);
+    else attn_body_pp2<T, D, BandPolicy<T, D, 8>, false, 0, true>(prm, smem, nullptr);
 }
 
 // Frozen reference schedule (variant 6; bf16 / D = 128 only): the two-phase body as it stood at the end of round 1 — running row
 // maximum with a deferred rescale, one probability step in the shadow of the PV MFMAs, operands fetched at the start of the matrix
 // phase.  Kept so that ONE bench run can time it beside the default on the same box (bench.py `same_box_ab`): box-to-box clock
 // spread (+-4 %) is as large as a typical schedule gain.
-__global__ __launch_bounds__(512, 2) void band_attn_pp2_frozen_kernel(typename BandPolicy<__bf16, 128, 8, false>::Params prm) {
+__global__ __launch_bounds__(512, 2) void band_attn_pp2_frozen_kernel(typename BandPolicy<__bf16, 128, 8>::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_body_pp2<__bf16, 128, BandPolicy<__bf16, 128, 8, false>, false, 8>(prm, smem, nullptr);
+    attn_body_pp2<__bf16, 128, BandPolicy<__bf16, 128, 8>, false, 8>(prm, smem, nullptr);
 }
 // the two-phase schedule on v_mfma_f32_16x16x32 (attn_m16.h): head_dim 128; variant 8
 // (issue priority in the matrix phase, ONE barrier per tile: 32.55 ms against 33.1 with two — profiles/r04g_ab_m16_cfg.txt; the 32x32x16
 //  body gained nothing from the single barrier because the clock took it back, this one runs ~300 MHz further from the power limit)
-#ifndef SVG_M16_PRIO
-#define SVG_M16_PRIO 1
-#endif
-template <typename T, int PRIO = SVG_M16_PRIO, int ONEBAR = 1>
-__global__ __launch_bounds__(512, 2) void band_attn_m16_kernel(typename BandPolicy<T, 128, 8, false>::Params prm) {
+template <typename T>
+__global__ __launch_bounds__(512, 2) void band_attn_m16_kernel(typename BandPolicy<T, 128, 8>::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_body_m16<T, BandPolicy<T, 128, 8, false>, false, PRIO, ONEBAR>(prm, smem, nullptr);
+    attn_body_m16<T, BandPolicy<T, 128, 8>, false, 1>(prm, smem, nullptr);
 }
-// pre-scaled q on the 16x16x32 body (PRE form of attn_body_m16).  QKF16 = true (q and k as fp16 carriers with S^T on the f16 MFMA) was
-// built and measured in round 4 and is not instantiated: see the note at attn_body_m16.
-template <typename T, bool QKF16>
-__global__ __launch_bounds__(512, 2) void band_attn_m16q_kernel(typename BandPolicy<T, 128, 8, false>::Params prm) {
+// pre-scaled q on the 16x16x32 body (PRE form of attn_body_m16)
+template <typename T>
+__global__ __launch_bounds__(512, 2) void band_attn_m16q_kernel(typename BandPolicy<T, 128, 8>::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_body_m16<T, BandPolicy<T, 128, 8, false>, false, 1, 1, true, QKF16>(prm, smem, nullptr);
+    attn_body_m16<T, BandPolicy<T, 128, 8>, false, 1, true>(prm, smem, nullptr);
 }
 // device-side switch between two masks on the 16x16x32 body (svg_band_attention_switch[_prescaled] at head_dim 128): `flag[0] != 0` selects prm_alt
-template <typename T, bool PRE = false, bool QKF16 = false>
-__global__ __launch_bounds__(512, 2) void band_attn_m16_switch_kernel(typename BandPolicy<T, 128, 8, false>::Params prm,
-                                                                      typename BandPolicy<T, 128, 8, false>::Params prm_alt,
+template <typename T, bool PRE = false>
+__global__ __launch_bounds__(512, 2) void band_attn_m16_switch_kernel(typename BandPolicy<T, 128, 8>::Params prm,
+                                                                      typename BandPolicy<T, 128, 8>::Params prm_alt,
                                                                       const int32_t* __restrict__ flag) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (flag[0] != 0) attn_body_m16<T, BandPolicy<T, 128, 8, false>, false, 1, 1, PRE, QKF16>(prm_alt, smem, nullptr);
-    else attn_body_m16<T, BandPolicy<T, 128, 8, false>, false, 1, 1, PRE, QKF16>(prm, smem, nullptr);
+    if (flag[0] != 0) attn_body_m16<T, BandPolicy<T, 128, 8>, false, 1, PRE>(prm_alt, smem, nullptr);
+    else attn_body_m16<T, BandPolicy<T, 128, 8>, false, 1, PRE>(prm, smem, nullptr);
 }
 // the same for q that carries sm_scale * log2(e) (svg_band_attention_prescaled): no scale-and-shift per score
 template <typename T, int D>
-__global__ __launch_bounds__(512, 2) void band_attn_pp2q_kernel(typename BandPolicy<T, D, 8, false>::Params prm) {
+__global__ __launch_bounds__(512, 2) void band_attn_pp2q_kernel(typename BandPolicy<T, D, 8>::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_body_pp2<T, D, BandPolicy<T, D, 8, false>, false, 0, true>(prm, smem, nullptr);
+    attn_body_pp2<T, D, BandPolicy<T, D, 8>, false, 0, true>(prm, smem, nullptr);
 }
 #ifdef SVG_ABLATIONS
 // Diagnostics build only (python sparse-videogen_amd/build.py --ablations): the two-phase kernel with the per-phase cycle trace
 // and the launch timeline, and its timing ablations (ABL > 0: results are wrong by construction).  Not in the product library.
 template <typename T, int D, int ABL>
-__global__ __launch_bounds__(512, 2) void band_attn_pp2_trace_kernel(typename BandPolicy<T, D, 8, false>::Params prm) {
+__global__ __launch_bounds__(512, 2) void band_attn_pp2_trace_kernel(typename BandPolicy<T, D, 8>::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_body_pp2<T, D, BandPolicy<T, D, 8, false>, true, ABL>(prm, smem, nullptr);
+    attn_body_pp2<T, D, BandPolicy<T, D, 8>, true, ABL>(prm, smem, nullptr);
 }
-template <typename T>   // trace code 9: the 16x16x32 body (attn_m16.h) with the cycle trace
-__global__ __launch_bounds__(512, 2) void band_attn_m16_trace_kernel(typename BandPolicy<T, 128, 8, false>::Params prm) {
+template <typename T>   // trace code 9: the 16x16x32 body (attn_m16.h) with the cycle trace — and two barriers per tile (the policy's
+                        // default), where the product kernel keeps one: not quite the shipped schedule
+__global__ __launch_bounds__(512, 2) void band_attn_m16_trace_kernel(typename BandPolicy<T, 128, 8>::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_body_m16<T, BandPolicy<T, 128, 8, false>, true>(prm, smem, nullptr);
+    attn_body_m16<T, BandPolicy<T, 128, 8>, true>(prm, smem, nullptr);
 }
 template <typename T, int D>   // trace code 3: the pre-scaled-q body (svg_band_attention_prescaled) with the cycle trace
-__global__ __launch_bounds__(512, 2) void band_attn_pp2q_trace_kernel(typename BandPolicy<T, D, 8, false>::Params prm) {
+__global__ __launch_bounds__(512, 2) void band_attn_pp2q_trace_kernel(typename BandPolicy<T, D, 8>::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_body_pp2<T, D, BandPolicy<T, D, 8, false>, true, 0, true>(prm, smem, nullptr);
+    attn_body_pp2<T, D, BandPolicy<T, D, 8>, true, 0, true>(prm, smem, nullptr);
 }
 #endif
 
@@ -130,12 +127,7 @@ struct VarblockPolicy {
     static constexpr bool kFastPartial = false;
     static constexpr int kShadow128 = 2;   // the vector phase also resolves rows through the run list and the index arrays
     static constexpr bool kOneBarrier = true;   // two-phase body: one barrier per tile (attn_core.h kOneBar: -1.7 % at Wan 720p)
-    static constexpr int kAbl = 0;
-    static constexpr bool kSetPrio = false;
-    static constexpr bool kSkew = false;
     static constexpr int kRowBlocks = 1;
-    static constexpr int kSubTiles = 1;
-    static constexpr int kPrefetch = 1;
     static constexpr int BM = NW * 32;
 
     struct Params {
@@ -388,10 +380,7 @@ __global__ __launch_bounds__(512, 2) void varblock_attn_pp2_trace_kernel(typenam
 // of this lock-step body are independent between barriers, so a tile's time follows its ACTIVE waves and smaller tiles only cost
 // more K / V staging per row: the ragged q-clusters of SVG2 (252 +- 160 rows) fill 69 % of 256-row tiles, 80 % of 128-row tiles,
 // 89 % of 64-row tiles (tools/vb_stats.py).
-#ifndef SVG_VB_F8_WAVES
-#define SVG_VB_F8_WAVES 4
-#endif
-constexpr int kVbF8Waves = SVG_VB_F8_WAVES;
+constexpr int kVbF8Waves = 4;
 template <typename T>
 __global__ __launch_bounds__(kVbF8Waves * 64, 2) void varblock_attn_f8_kernel(typename VarblockPolicy<T, 128, kVbF8Waves>::Params prm,
                                                                               F8GArgs fa) {
@@ -879,7 +868,7 @@ static int band_dispatch(const void* q, const void* k, const void* v, void* o, i
     return dispatch_td(dtype, D, [&](auto t, auto d) -> int {
         using T = decltype(t);
         constexpr int DD = decltype(d)::value;
-        using Pol = BandPolicy<T, DD, 8, false>;
+        using Pol = BandPolicy<T, DD, 8>;
         auto launch = [&](auto kern, int lds) {   // 8 waves over the q-tiles of every head
             const typename Pol::Params p = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
             return launch_attn(kern, p, dim3(p.nqt * BH), 512, lds, st);
@@ -895,9 +884,9 @@ static int band_dispatch(const void* q, const void* k, const void* v, void* o, i
         };
         switch (variant) {
             case kBandLockstep4: {
-                using Pol4 = BandPolicy<T, DD, 4, false>;
+                using Pol4 = BandPolicy<T, DD, 4>;
                 const typename Pol4::Params p = make_band_params<Pol4, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
-                return launch_attn(band_attn_kernel<T, DD, 4>, p, dim3(p.nqt * BH), 256, attn_lds_bytes<DD, 4, 2>(), st);
+                return launch_attn(band_attn_kernel<T, DD, 4>, p, dim3(p.nqt * BH), 256, attn_lds_bytes<DD, 4>(), st);
             }
             case kBandPingPong:
 #ifdef SVG_ABLATIONS
@@ -929,9 +918,9 @@ static int band_dispatch(const void* q, const void* k, const void* v, void* o, i
             default:   // kBandM16: two-phase body on 16x16x32 MFMAs (attn_m16.h), head_dim 128; PRE forms for a q that carries the scale
                 if constexpr (DD == 128) {
                     if (opts.use_alt)
-                        return launch_switch(opts.prescaled ? band_attn_m16_switch_kernel<T, true, false> : band_attn_m16_switch_kernel<T>,
+                        return launch_switch(opts.prescaled ? band_attn_m16_switch_kernel<T, true> : band_attn_m16_switch_kernel<T>,
                                              attn_m16_lds_bytes());
-                    return launch(opts.prescaled ? band_attn_m16q_kernel<T, false> : band_attn_m16_kernel<T>, attn_m16_lds_bytes());
+                    return launch(opts.prescaled ? band_attn_m16q_kernel<T> : band_attn_m16_kernel<T>, attn_m16_lds_bytes());
                 }
                 return SVG_ERR_UNSUPPORTED;
         }
@@ -963,7 +952,7 @@ extern "C" int svg_band_attention_prescaled(const void* q_scaled, const void* k,
 
 extern "C" int32_t svg_band_attention_notify_target(int32_t S, const svg_band_mask_t* mask) {
     if (!mask || S <= 0) return -1;
-    using Pol = svg::BandPolicy<__bf16, 128, 8, false>;
+    using Pol = svg::BandPolicy<__bf16, 128, 8>;
     const auto p = svg::make_band_params<Pol, __bf16>(nullptr, nullptr, nullptr, nullptr, 1, S, 1.f, mask, nullptr);
     return p.nqt * band_waves_per_tile(kBandAuto);   // every wave of every q-tile of a head reports once
 }
@@ -971,7 +960,7 @@ extern "C" int32_t svg_band_attention_notify_target(int32_t S, const svg_band_ma
 extern "C" int32_t svg_band_attention_notify_layout(int32_t S, const svg_band_mask_t* mask, int32_t nseg, int32_t* row_bounds,
                                                     int32_t* targets) {
     if (!mask || S <= 0 || nseg <= 0 || !row_bounds || !targets) return -1;
-    using Pol = svg::BandPolicy<__bf16, 128, 8, false>;   // (q-tiles are 256 rows in every schedule that counts)
+    using Pol = svg::BandPolicy<__bf16, 128, 8>;   // (q-tiles are 256 rows in every schedule that counts)
     BandOpts opts;
     opts.done_nseg = nseg;
     const auto p = svg::make_band_params<Pol, __bf16>(nullptr, nullptr, nullptr, nullptr, 1, S, 1.f, mask, nullptr, opts);

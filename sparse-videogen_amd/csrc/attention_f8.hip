@@ -1,4 +1,4 @@
-// fp8 (e4m3) SVG1 band / dense attention: quantise + placement pre-pass, kernel on attn_body_f8, C entry points.
+// fp8 (e4m3) SVG1 band / dense attention: quantise + placement pre-pass, kernel on attn_body_f8pp, C entry points.
 // BASELINE.json configs[4]; no reference implementation exists (README.md:117), see attn_f8.h.
 #include "attn_f8.h"
 #include "band_policy.h"
@@ -6,19 +6,12 @@
 namespace svg {
 
 template <typename T>
-using BandF8 = BandPolicy<T, 128, 8, false>;   // 8 waves x 32 rows: 256-row q-tiles (the tiling of the two-phase 16-bit kernel)
+using BandF8 = BandPolicy<T, 128, 8>;   // 8 waves x 32 rows: 256-row q-tiles (the tiling of the two-phase 16-bit kernel)
 
-#ifndef SVG_F8_PINGPONG
-#define SVG_F8_PINGPONG 1     // 1: two-phase ping-pong body (attn_body_f8pp), 0: lock-step body (attn_body_f8)
-#endif
 template <typename T>
 __global__ __launch_bounds__(512, 2) void band_attn_f8_kernel(typename BandF8<T>::Params prm, F8Args fa) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-#if SVG_F8_PINGPONG
     attn_body_f8pp<T, BandF8<T>>(prm, fa, smem);
-#else
-    attn_body_f8<T, BandF8<T>>(prm, fa, smem);
-#endif
 }
 
 // ---- pre-pass 1: per-head absolute maxima of q, k, v (float bits of non-negative values order like unsigned integers) ----
@@ -84,7 +77,7 @@ __global__ __launch_bounds__(256) void f8_quantize_kernel(const T* __restrict__ 
     const float sk = ak > 0.f ? kF8Max / ak : 1.f, sv = av > 0.f ? kF8Max / av : 1.f;
     // q carries the whole softmax scale: q8 = q * (scale_log2 / sk) * 2^-e, with the power of two e chosen so that the head's largest
     // |q8| lands in (224, 448] — then sum(k8 q8) * 2^e IS the exponent argument scale_log2 * q.k, and 2^e is an E8M0 block scale of the
-    // MFMA (two-phase body) or one multiply (lock-step body): no per-element scale-and-shift on the VALU
+    // MFMA (attn_body_f8pp): no per-element scale-and-shift on the VALU
     const float mq_ideal = scale_log2 / sk;
     int e = aq > 0.f ? (int)ceilf(log2f(aq * mq_ideal / kF8Max)) : 0;
     e = max(-120, min(120, e));

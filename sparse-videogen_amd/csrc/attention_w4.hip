@@ -7,7 +7,7 @@
 namespace svg {
 
 template <typename T, int D>
-using BandW4 = BandPolicy<T, D, 4, false, 0, 2>;   // 4 waves x 2 row blocks: 256-row q-tiles
+using BandW4 = BandPolicy<T, D, 4, 2>;   // 4 waves x 2 row blocks: 256-row q-tiles
 
 template <typename T, int D>
 __global__ __launch_bounds__(256, 1) void band_attn_w4_kernel(typename BandW4<T, D>::Params prm) {

@@ -44,17 +44,11 @@ struct LdsLayout {
     static __device__ __forceinline__ int v_off(int row, int c) { return (c >> 2) * (kBN * 64) + row * 64 + ((c & 3) << 4); }
 };
 
-// number of LDS stages: 3 when the policy asks for the skewed two-group schedule (8 waves, one workgroup per CU)
-template <int NW, typename P>
-constexpr int attn_stages() {
-    return (P::kSkew && NW == 8) ? 3 : 2;
-}
-
-template <int D, int NW, int NS = 2, int RB = 1, int SUBS = 1>
+template <int D, int NW>
 constexpr int attn_lds_bytes() {
-    // NS stages of SUBS tiles, or the epilogue staging of NW*32*RB rows with an 8-byte row pad, whichever is larger
-    constexpr int stages = NS * SUBS * LdsLayout<D>::kStageBytes;
-    constexpr int epi = NW * 32 * RB * (D * 2 + 8);
+    // two stages, or the epilogue staging of NW*32 rows with an 8-byte row pad, whichever is larger
+    constexpr int stages = 2 * LdsLayout<D>::kStageBytes;
+    constexpr int epi = NW * 32 * (D * 2 + 8);
     return stages > epi ? stages : epi;
 }
 
@@ -76,18 +70,21 @@ __device__ __forceinline__ i16x4 lds_read_tr16(const char* p) {
 //   void notify(prm, ctx)                                        called by every wave of the two-phase body after its last store
 //   float score_fixup(float raw)                                 (profiler: dtype rounding emulation)
 //   epilogue: store(prm, ctx, ...) handled here through P::kPartialOut
+// Lock-step schedule: every wave runs QK -> softmax -> PV per tile.  (The skewed two-group schedule and the timing ablations of this
+// body are in the history of this file; profiles/r01_ablation.md has their measurements.)
 template <typename T, int D, int NW, typename P>
 __device__ __forceinline__ void attn_body(const typename P::Params& prm, char* smem, char* policy_lds) {
     using E = Elt<T>;
     using V8 = typename E::v8;
     using L = LdsLayout<D>;
-    constexpr int RB = P::kRowBlocks;   // 32-row query blocks per wave (2 => 64 rows per wave: every K / V fragment read
-                                        // from LDS feeds two MFMAs, halving LDS operand traffic per FLOP)
+    constexpr int RB = P::kRowBlocks;   // 32-row query blocks per wave (1 for every policy of this body)
     constexpr int WR = 32 * RB;         // query rows per wave
     constexpr int NT = NW * 64;
     constexpr int KS = D / 16;          // k-steps of the S^T GEMM
     constexpr int DB = D / 32;          // 32-wide d blocks of O^T
-    constexpr int SUBS = P::kSubTiles;  // 64-key tiles per LDS stage (2 => one barrier / one staging round per 128 keys)
+    // 64-key tiles per LDS stage.  One; the row-block and sub-tile form of the code below stays because hipcc emits different code
+    // for the lock-step kernels when it is written out for one row block and one tile per stage.
+    constexpr int SUBS = 1;
     constexpr int NCH = (SUBS * kBN * L::kCPR) / NT;  // 16-B chunks per thread per tensor per stage
     constexpr int kStage = SUBS * L::kStageBytes;     // a stage is SUBS x [K image | V image]
     static_assert((SUBS * kBN * L::kCPR) % NT == 0, "stage chunks must divide evenly");
@@ -207,11 +204,9 @@ __device__ __forceinline__ void attn_body(const typename P::Params& prm, char* s
     }
     __syncthreads();
 
-    // The two GEMM phases as lambdas so that the "skewed" schedule below can place them differently per wave group.
-    V8 pf[RB][2][2];  // P^T operand of the current tile (kept across the barrier by the lagging wave group)
+    V8 pf[RB][2][2];  // P^T operand of the current tile
     auto qk_softmax = [&](const char* kbuf, int tk0, int cls) {
         // ---------------- S^T = K Q^T ----------------
-        if constexpr (P::kSetPrio) __builtin_amdgcn_s_setprio(1);
         f32x16 s[RB][2];
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb)
@@ -219,51 +214,23 @@ __device__ __forceinline__ void attn_body(const typename P::Params& prm, char* s
             for (int b = 0; b < 2; ++b)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) s[rb][b][r] = 0.f;
-        if constexpr (P::kAbl == 10) __builtin_amdgcn_iglp_opt(0);
-        if constexpr (P::kAbl == 11) __builtin_amdgcn_iglp_opt(1);
-        if constexpr (P::kAbl == 6 || P::kAbl == 8 || P::kAbl == 9) {  // ablation: MFMAs without the K-fragment LDS reads
+        // K fragments through a register ring, one k-step ahead of the MFMAs that consume them
+        auto kfrag = [&](int b, int ks) -> V8 {
+            return *(const V8*)(kbuf + (32 * b + ql) * L::kRowBytes + (((2 * ks + g) ^ ksw0) << 4));
+        };
+        V8 ring[2][2];
+        ring[0][0] = kfrag(0, 0);
+        ring[0][1] = kfrag(1, 0);
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int rb = 0; rb < RB; ++rb) s[rb][b] = E::mfma(qf[rb][(ks + b) % KS], qf[rb][ks], s[rb][b]);
-        } else if constexpr (P::kAbl != 3) {
-            // K fragments through a register ring, kPF k-steps ahead of the MFMAs that consume them
-            constexpr int kPF = P::kPrefetch;
-            auto kfrag = [&](int b, int ks) -> V8 {
-                return *(const V8*)(kbuf + (32 * b + ql) * L::kRowBytes + (((2 * ks + g) ^ ksw0) << 4));
-            };
-            V8 ring[kPF + 1][2];
-#pragma unroll
-            for (int i = 0; i < kPF; ++i) {
-                ring[i][0] = kfrag(0, i);
-                ring[i][1] = kfrag(1, i);
+        for (int ks = 0; ks < KS; ++ks) {
+            if (ks + 1 < KS) {
+                ring[(ks + 1) % 2][0] = kfrag(0, ks + 1);
+                ring[(ks + 1) % 2][1] = kfrag(1, ks + 1);
             }
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                if (ks + kPF < KS) {
-                    ring[(ks + kPF) % (kPF + 1)][0] = kfrag(0, ks + kPF);
-                    ring[(ks + kPF) % (kPF + 1)][1] = kfrag(1, ks + kPF);
-                }
+            for (int b = 0; b < 2; ++b)
 #pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int rb = 0; rb < RB; ++rb) s[rb][b] = E::mfma(ring[ks % (kPF + 1)][b], qf[rb][ks], s[rb][b]);
-            }
-        } else {  // ablation: no QK^T (keep the values opaque so that the softmax is not folded away)
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb) asm volatile("" : "+v"(s[rb][0]), "+v"(s[rb][1]));
-        }
-        if constexpr (P::kSetPrio) __builtin_amdgcn_s_setprio(0);
-        if constexpr (P::kAbl == 1 || P::kAbl == 9) {  // ablation: no softmax VALU
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) pf[rb][b][r >> 3][r & 7] = E::from_float(s[rb][b][r]);
-            return;
+                for (int rb = 0; rb < RB; ++rb) s[rb][b] = E::mfma(ring[ks % 2][b], qf[rb][ks], s[rb][b]);
         }
         // ---------------- mask + online softmax (lane-local rows) ----------------
 #pragma unroll
@@ -321,62 +288,32 @@ __device__ __forceinline__ void attn_body(const typename P::Params& prm, char* s
         }
     };
     auto pv = [&](const char* kbuf) {
-        if constexpr (P::kAbl == 2) {  // ablation: no PV (keep P alive)
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb)
-                asm volatile("" ::"v"(pf[rb][0][0]), "v"(pf[rb][0][1]), "v"(pf[rb][1][0]), "v"(pf[rb][1][1]));
-            return;
-        }
         // ---------------- O^T += V^T P^T ----------------
-        if constexpr (P::kSetPrio) __builtin_amdgcn_s_setprio(1);
-        if constexpr (P::kAbl == 10) __builtin_amdgcn_iglp_opt(0);
-        if constexpr (P::kAbl == 11) __builtin_amdgcn_iglp_opt(1);
         const char* vbase = kbuf + v_lane_off;
         constexpr int NPV = DB * 4;  // MFMA steps: idx = db * 4 + b * 2 + h
-        if constexpr (P::kAbl == 7 || P::kAbl == 8 || P::kAbl == 9) {  // ablation: MFMAs without the V transpose reads
+        auto vfrag = [&](int idx) -> V8 {
+            const int db = idx >> 2, kb0 = 32 * ((idx >> 1) & 1) + 16 * (idx & 1);
+            const i16x4 lo = lds_read_tr16(vbase + db * (kBN * 64) + kb0 * 64);
+            const i16x4 hi = lds_read_tr16(vbase + db * (kBN * 64) + (kb0 + 8) * 64);
+            i16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            return __builtin_bit_cast(V8, both);
+        };
+        V8 ring[2];   // one step ahead
+        ring[0] = vfrag(0);
 #pragma unroll
-            for (int idx = 0; idx < NPV; ++idx)
+        for (int idx = 0; idx < NPV; ++idx) {
+            if (idx + 1 < NPV) ring[(idx + 1) % 2] = vfrag(idx + 1);
 #pragma unroll
-                for (int rb = 0; rb < RB; ++rb)
-                    acc_o[rb][idx >> 2] = E::mfma(qf[rb][idx % KS], pf[rb][(idx >> 1) & 1][idx & 1], acc_o[rb][idx >> 2]);
-        } else {
-            constexpr int kPF = P::kPrefetch;
-            auto vfrag = [&](int idx) -> V8 {
-                const int db = idx >> 2, kb0 = 32 * ((idx >> 1) & 1) + 16 * (idx & 1);
-                const i16x4 lo = lds_read_tr16(vbase + db * (kBN * 64) + kb0 * 64);
-                const i16x4 hi = lds_read_tr16(vbase + db * (kBN * 64) + (kb0 + 8) * 64);
-                i16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                return __builtin_bit_cast(V8, both);
-            };
-            V8 ring[kPF + 1];
-#pragma unroll
-            for (int i = 0; i < kPF; ++i) ring[i] = vfrag(i);
-#pragma unroll
-            for (int idx = 0; idx < NPV; ++idx) {
-                if (idx + kPF < NPV) ring[(idx + kPF) % (kPF + 1)] = vfrag(idx + kPF);
-#pragma unroll
-                for (int rb = 0; rb < RB; ++rb)
-                    acc_o[rb][idx >> 2] = E::mfma(ring[idx % (kPF + 1)], pf[rb][(idx >> 1) & 1][idx & 1], acc_o[rb][idx >> 2]);
-            }
+            for (int rb = 0; rb < RB; ++rb)
+                acc_o[rb][idx >> 2] = E::mfma(ring[idx % 2], pf[rb][(idx >> 1) & 1][idx & 1], acc_o[rb][idx >> 2]);
         }
-        if constexpr (P::kSetPrio) __builtin_amdgcn_s_setprio(0);
     };
 
-    // Schedule.  Lock-step (kStages == 2): every wave runs QK -> softmax -> PV per tile; the two waves that share a
-    // SIMD then fight for the matrix pipe in the GEMM phases and for the VALU in the softmax phase (time ~ 4M + 2V).
-    // Skewed (kStages == 3): the second half of the waves (one per SIMD) runs PV one tile late, at the top of the
-    // next iteration — while group A is in its softmax (VALU) group B is in QK (MFMA) and vice versa (time ~ 4M).
-    // The third LDS stage keeps V(t-1) alive for the lagging group while tile t+1 is being written.
-    constexpr int NS = attn_stages<NW, P>();
-    const bool lag = (NS == 3) && (wave >= NW / 2);
-    bool pending = false;
-    int buf = 0, pend_buf = 0;
+    // Schedule: every wave runs QK -> softmax -> PV per tile; two LDS stages, one barrier per tile.
+    constexpr int NS = 2;
+    int buf = 0;
     for (int t = 0; t < nT; ++t) {
         const char* sbuf = smem + buf * kStage;
-        if (NS == 3 && lag && pending) {
-            pv(smem + pend_buf * kStage);
-            pending = false;
-        }
 #pragma unroll
         for (int sub = 0; sub < SUBS; ++sub) {
             const int t64 = t * SUBS + sub;
@@ -386,25 +323,14 @@ __device__ __forceinline__ void attn_body(const typename P::Params& prm, char* s
             const int cls = P::classify(prm, ctx, tk0, wave * WR);
             if (cls != TILE_SKIP) {
                 qk_softmax(kbuf, tk0, cls);
-                if (NS == 3 && lag) {
-                    pending = true;
-                    pend_buf = buf;
-                } else {
-                    pv(kbuf);
-                }
+                pv(kbuf);
             }
         }
         const int nbuf = (buf + 1 == NS) ? 0 : buf + 1;
-        if constexpr (P::kAbl != 4 && P::kAbl != 8 && P::kAbl != 9) {
-            if (t + 1 < nT) stage_write(nbuf);
-            if (t + 2 < nT) stage_issue(t + 2);
-        }
-        if constexpr (P::kAbl != 5 && P::kAbl != 8 && P::kAbl != 9) __syncthreads();
+        if (t + 1 < nT) stage_write(nbuf);
+        if (t + 2 < nT) stage_issue(t + 2);
+        __syncthreads();
         buf = nbuf;
-    }
-    if (NS == 3) {
-        if (lag && pending) pv(smem + pend_buf * kStage);
-        __syncthreads();  // the epilogue below reuses the stage buffers
     }
 
     // ---------------- epilogue ----------------
@@ -518,7 +444,7 @@ static __device__ unsigned long long g_wg_trace[kWgTraceMax * 6];
 //     N(t+1)  mask, all 64 probabilities of tile t+1 against the row's reference, the check of their sum and — rarely — the exact
 //             path (row maximum, new reference, rescale of O and l, probabilities again): kMaxFree, the shipped softmax;
 //             LDS-DMA requests; DMA wait.  (The earlier softmax — row maximum of every tile with a deferred rescale, probabilities
-//             of keys 16..63 in the shadow of the PV MFMAs — is kept behind SVG_PP2_MAXFREE=0 and for the timing ablations.)
+//             of keys 16..63 in the shadow of the PV MFMAs — is kept for the frozen schedule, ABL == 8, and the timing ablations.)
 // In M the wave has the matrix pipe to itself (its partner is in N and issues no MFMA), in N it has the VALU to itself.
 // profiles/r01_ablation.md: in the lock-step body both waves of a SIMD sit in the same phase and the phases add up; the
 // four-cluster attn_body_pp separates them but pays four barriers per tile and serialises the LDS operand reads.
@@ -543,35 +469,25 @@ __device__ __forceinline__ void attn_body_pp2(const typename P::Params& prm, cha
     constexpr int NW = 8;
     constexpr int KS = D / 16;
     constexpr int DB = D / 32;
-    constexpr bool kDma = true;             // true: LDS-DMA staging (4 stages); false: register staging (3 stages), measured 15 % slower
-#ifndef SVG_PP2_MAXFREE
-#define SVG_PP2_MAXFREE 1
-#endif
-    // Softmax without a running maximum (the scheme of attn_body_w4 / attn_body_f8): probabilities are taken relative to a per-row
+    // Softmax without a running maximum (the scheme of attn_body_w4 / attn_body_f8pp): probabilities are taken relative to a per-row
     // reference that only changes on the exact path; the common path checks that a lane's 32 probabilities of the tile sum to
     // <= 2^11 (one compare instead of the 16-instruction maximum chain + lane exchange) and otherwise takes the exact path — row
     // maximum, new reference, O and l rescaled, probabilities recomputed — BEFORE any PV MFMA has consumed them, which is why all
     // four 16-key steps are computed in the vector phase then (kShadow = 0).
     // (ABL == 8 is not an ablation: the frozen reference schedule of svg_band_attention variant 6 — correct results)
-    constexpr bool kMaxFree = (SVG_PP2_MAXFREE != 0 && ABL == 0) || PRE;
+    constexpr bool kMaxFree = ABL == 0 || PRE;
     // PRE: q arrives multiplied by sm_scale * log2(e) (svg_band_attention_prescaled; the prologue folds the factor into its single
     // rounding of q), and the S^T accumulators start at minus the row's reference instead of zero — a 16-register tuple that only
     // the exact path rewrites — so what the MFMAs deliver IS the exponent argument: no scale-and-shift FMA per score (the scheme
     // of the fp8 bodies, attn_f8.h).
-    static_assert(!PRE || (SVG_PP2_MAXFREE != 0 && ABL == 0), "pre-scaled q: max-free softmax only");
-#ifndef SVG_PP2_CARRY
-#define SVG_PP2_CARRY 8
-#endif
+    static_assert(!PRE || ABL == 0, "pre-scaled q: max-free softmax only");
     // V operands of the first kCarry MFMAs of a matrix phase are read in the tail of the PREVIOUS matrix phase (tile t + 1 has been
     // in LDS since the barrier in front of M(t)) and carried through the vector phase in registers: the phase opens with MFMAs
     // instead of with an LDS round trip.
     // LEAN: the register diet of the instance that runs FOUR waves per SIMD (two workgroups per CU; band_attn_pp2_kernel at head_dim 64,
     // attention.hip): no carried operands, operand ring 4 instead of 8 fragments ahead — with a second workgroup on the CU the latency the
     // deep ring hides is hidden by the other workgroup's waves, and 128 registers hold the body without a spill.
-    constexpr int kCarry = (ABL == 0 && !LEAN) ? SVG_PP2_CARRY : 0;
-#ifndef SVG_PP2_ONEBAR
-#define SVG_PP2_ONEBAR -1   // -1: as the policy says (P::kOneBarrier); 0 / 1: force (A/B builds)
-#endif
+    constexpr int kCarry = (ABL == 0 && !LEAN) ? 8 : 0;
     // ONE workgroup barrier per tile instead of two.  Of the two barriers of a tile only the one in front of the leading waves'
     // matrix phase (= in front of the lagging waves' vector phase) carries data: it publishes the DMA pieces the leading waves have
     // just waited for (tile t + 1, read by their M(t) right behind it) and orders every request of a stage behind the last read of
@@ -581,22 +497,15 @@ __device__ __forceinline__ void attn_body_pp2(const typename P::Params& prm, cha
     // Measured (round 3, same box): band kernel 32.06 vs 32.13 ms — nothing: at the power limit the clock takes back what a schedule
     // saves without saving energy —, variable-block kernel (whose vector phase, with the gather, is the longer one) 28.07 vs 28.62 ms:
     // on for the variable-block policy, off for the band policy.
-    constexpr bool kOneBar = (SVG_PP2_ONEBAR < 0 ? P::kOneBarrier : SVG_PP2_ONEBAR != 0) && ABL == 0;
+    constexpr bool kOneBar = P::kOneBarrier && ABL == 0;
     constexpr int kShadow = kMaxFree ? 0 : (D == 64) ? 2 : P::kShadow128;   // 16-key probability steps computed in the shadow of the PV MFMAs (0..3); the rest in the vector phase
-    constexpr int NS = kDma ? 4 : 3;
+    constexpr int NS = 4;                   // LDS stages (LDS-DMA staging)
     constexpr int kImg = kBN * D * 2;       // bytes of a K or V image
     constexpr int kStage = 2 * kImg;
     constexpr int NP = DB / 2;              // DMA pieces per wave per tensor per tile
-#ifndef SVG_PP2_PRIO
-#define SVG_PP2_PRIO 1
-#endif
-    // 1: priority 1 in the matrix phase (shipped); 0: none (+1.1 %); 2: priority 1 in the vector phase (+0.4 %) — max-free body, same box
-    constexpr bool kPrioM = SVG_PP2_PRIO == 1;
-    constexpr bool kPrioV = SVG_PP2_PRIO == 2;
-    constexpr bool kPrioStatic = false;  // true: static priority 1 for the lagging half instead of a flip around every matrix phase — measured 4 % slower (38.6 vs 37.0 ms)
     constexpr float kDefer = 8.f;
     static_assert(D == 64 || D == 128, "head dim");
-    static_assert(P::kRowBlocks == 1 && P::kSubTiles == 1, "ping-pong body: 32 rows per wave, one tile per stage");
+    static_assert(P::kRowBlocks == 1, "ping-pong body: 32 rows per wave");
 
     unsigned long long wg_t0 = 0;
     if constexpr (TRACE) wg_t0 = __builtin_amdgcn_s_memtime();
@@ -668,30 +577,10 @@ __device__ __forceinline__ void attn_body_pp2(const typename P::Params& prm, cha
         dma_piece(t, std::integral_constant<int, 0>{});
         if constexpr (NP > 1) dma_piece(t, std::integral_constant<int, 1>{});
     };
-    // Register staging (kDma = false, kept for comparison): loads for tile w are issued in N(w - dist) and written in the
-    // following vector phase: slot 2w-1 (leading) / 2w-2 (lagging), after the last read of the stage's previous tenant
-    // (slot 2(w-3)+3) and before the first read of tile w (slot 2w).  Measured 51.0 ms vs 44.7 ms with LDS-DMA: the
-    // ds_write_b128 traffic of the vector phase collides with the operand streaming of the partner's matrix phase.
-    u32x4 kreg[NP], vreg[NP];
-    auto stage_load = [&](int t) {
-        resolve(t, kGuarded);
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            kreg[j] = *(const u32x4*)((const char*)kb + (size_t)nnext * k_rsb + (col_k + (unsigned)(j * 64)));
-            vreg[j] = *(const u32x4*)((const char*)vb + (size_t)nnext * v_rsb + (col_v + (unsigned)(j * 64)));
-        }
-    };
-    char* const piece_ptr = smem + dma_db0 * (kBN * 64) + dma_kg * 1024 + lane * 16;
-    auto stage_store = [&](int t) {
-        char* st = piece_ptr + (t % NS) * kStage;
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            *(u32x4*)(st + j * (kBN * 64)) = kreg[j];
-            *(u32x4*)(st + j * (kBN * 64) + kImg) = vreg[j];
-        }
-    };
-    const int dist = kDma ? (lagging ? 3 : 2) : (lagging ? 3 : 2);   // tile u + dist is requested in N(u)
-    if constexpr (kDma) {
+    // (Register staging instead of LDS-DMA measured 51.0 ms vs 44.7 ms: the ds_write_b128 traffic of the vector phase collides with
+    //  the operand streaming of the partner's matrix phase.  Removed; it is in the history of this file.)
+    const int dist = lagging ? 3 : 2;   // tile u + dist is requested in N(u)
+    {
         // (ablation 6 — no DMA inside the loop — fills all four stages here so that the loop computes on finite stale data)
         const int npro = (ABL == 6) ? NS : dist;
         for (int t = 0; t < npro; ++t) {
@@ -700,14 +589,6 @@ __device__ __forceinline__ void attn_body_pp2(const typename P::Params& prm, cha
             if (t < nT) dma_issue(t);
         }
         resolve(npro, kGuarded);   // requested in N(0)
-    } else {
-        // tiles 0 .. dist-2 go to LDS here, tile dist-1 stays in the staging registers (written in N(0))
-        if (nT > 0) { stage_load(0); stage_store(0); }
-        if (nT > 1) stage_load(1);
-        if (lagging) {
-            if (nT > 1) stage_store(1);
-            if (nT > 2) stage_load(2);
-        }
     }
 
     const int q_phys = P::q_phys(prm, ctx, row_in_wg);
@@ -799,28 +680,21 @@ __device__ __forceinline__ void attn_body_pp2(const typename P::Params& prm, cha
     // staging half of a vector phase: resolve the rows of tile t+dist+1 (index loads first: they are older than the DMA
     // requests below, so the counted wait at the end retires them too), request tile t+dist, wait for tile t+dist-1
     auto stage_resolve_next = [&](int t, auto guard_c) {
-        if constexpr (kDma) {
-            take();
-            resolve(t + dist + 1, guard_c);
-        }
+        take();
+        resolve(t + dist + 1, guard_c);
     };
     auto stage_request = [&](int t) {
         const bool more = t + dist < nT;
-        if constexpr (kDma) {
-            if (ABL != 6 && more) dma_issue(t + dist);
-            // pieces requested in the previous vector phase have to be in LDS; the ones just requested may stay in flight
-            if (ABL != 6 && more) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NP) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else if constexpr (ABL != 6) {
-            if (t + dist - 1 < nT) stage_store(t + dist - 1);   // loaded in the previous vector phase (or the prologue)
-            if (more) stage_load(t + dist);
-        }
+        if (ABL != 6 && more) dma_issue(t + dist);
+        // pieces requested in the previous vector phase have to be in LDS; the ones just requested may stay in flight
+        if (ABL != 6 && more) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NP) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     };
     // vector phase of tile t on sc: mask, maximum, (rare) rescale, probabilities of keys 0..15, DMA requests, DMA wait
     auto vector_phase = [&](int t, auto guard_c) {
         constexpr bool guard = decltype(guard_c)::value;
         stage_resolve_next(t, guard_c);
-        constexpr bool kSpread = kDma && ABL != 6;   // requests spread over the phase instead of back to back at its end
+        constexpr bool kSpread = ABL != 6;   // requests spread over the phase instead of back to back at its end
         const bool more = !guard || t + dist < nT;
         if (kSpread && more) dma_piece(t + dist, std::integral_constant<int, 0>{});
         const int tk0 = P::tile_key0(ctx, t);
@@ -1062,18 +936,17 @@ __device__ __forceinline__ void attn_body_pp2(const typename P::Params& prm, cha
         if constexpr (kOneBar) pp_barrier_if(bar_n);
         else pp_barrier();
         tick(std::integral_constant<int, 1>{});
-        if (kPrioV) __builtin_amdgcn_s_setprio(1);
         vector_phase(t, guard_c);
-        if (kPrioV) __builtin_amdgcn_s_setprio(0);
         tick(std::integral_constant<int, 2>{});
         if constexpr (kOneBar) pp_barrier_if(bar_m);
         else pp_barrier();
         tick(std::integral_constant<int, 3>{});
-        if (kPrioM && !kPrioStatic) __builtin_amdgcn_s_setprio(1);   // the matrix phase wins the VALU / MFMA issue arbitration against the partner's vector phase
+        // the matrix phase wins the VALU / MFMA issue arbitration against the partner's vector phase.  (Measured, max-free body, same
+        // box: no priority +1.1 %, priority 1 in the vector phase instead +0.4 %, a static priority 1 for the lagging half +4 %.)
+        __builtin_amdgcn_s_setprio(1);
         matrix_phase(t, has_next_c);
-        if (kPrioM && !kPrioStatic) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
     };
-    if (kPrioM && kPrioStatic && lagging) __builtin_amdgcn_s_setprio(1);
     // steady state: every tile a phase of tile t touches (t + dist + 1 at most) exists; then the guarded tail; then the peeled last tile
     int t = 0;
     for (const int n_main = nT - dist - 1; t < n_main; ++t) tile(t, std::true_type{}, std::false_type{});

@@ -20,9 +20,10 @@
 // 16-bit kernels'.  Probabilities are scaled by 2^8 before the conversion (e4m3 tops out at 448; the scale cancels in O / l): a
 // probability of 2^-14 relative to the row maximum is still a normal number.
 //
-// Schedule: 8 waves x 32 rows (256-row q-tiles), two waves per SIMD, lock-step over 64-key tiles with two register-staged LDS
-// stages and one barrier per tile.  With a quarter of the MFMA issues the matrix pipe is
-// no longer what a tile waits for; the softmax VALU and the LDS operand reads are.
+// Schedule (attn_body_f8pp): 8 waves x 32 rows (256-row q-tiles), two waves per SIMD in opposite phases over 64-key tiles.  With a
+// quarter of the MFMA issues the matrix pipe is no longer what a tile waits for; the softmax VALU and the LDS operand reads are.
+// (The lock-step form of this body, two register-staged LDS stages and one barrier per tile, measured 4 - 6 % slower; it is in the
+//  history of this file.)
 #pragma once
 #include "attn_core.h"
 
@@ -55,242 +56,21 @@ constexpr int attn_f8_lds_bytes() {
 // byte offset of 16-B chunk c of key row `row` inside the K image ([64][128] bytes): the XOR makes the b128 reads of 16
 // consecutive rows hit 16 different 16-byte bank groups
 __device__ __forceinline__ int f8_k_off(int row, int c) { return row * 128 + ((c ^ ((row >> 1) & 7)) << 4); }
-// byte offset of 16-B chunk c of row d inside the V^T image ([128][64] bytes)
-__device__ __forceinline__ int f8_v_off(int d, int c) { return d * 64 + ((c ^ ((d >> 2) & 3)) << 4); }
-
-template <typename T, typename P>
-__device__ __forceinline__ void attn_body_f8(const typename P::Params& prm, const F8Args& fa, char* smem) {
-    using E = Elt<T>;
-    constexpr int D = 128, DB = D / 32, KS = D / 64, NT = 512;
-    constexpr int kKBytes = kBN * D, kStage = 2 * kBN * D;
-    static_assert(P::kRowBlocks == 1 && P::BM == 256, "fp8 body: 8 waves x 32 rows");
-
-    typename P::Ctx ctx;
-    if (!P::init(prm, ctx, nullptr)) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = wave_id(), g = lane >> 5, ql = lane & 31;
-    const uint8_t* __restrict__ q8 = fa.q8 + (size_t)ctx.head * fa.S_pad * D;
-    const uint8_t* __restrict__ k8 = fa.k8 + (size_t)ctx.head * fa.S_pad * D;
-    const uint8_t* __restrict__ vt8 = fa.vt8 + (size_t)ctx.head * fa.S_pad * D;   // (S_pad / 64) tiles of 64 * D bytes
-    const float two_e = fa.scales[4 * ctx.head], inv_v = fa.scales[4 * ctx.head + 1];
-
-    // ---- Q fragments (B operand of S^T): rows are in logical order in q8; a row that does not exist reads row 0 (never stored) ----
-    const int row_in_wg = wave * 32 + ql;
-    const int q_log = P::q_logical(ctx, row_in_wg);
-    const bool q_exists = P::q_phys(prm, ctx, row_in_wg) >= 0;
-    i32x8 qf[KS];
-    {
-        const uint8_t* qrow = q8 + (size_t)(q_exists ? q_log : 0) * D + g * 32;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) qf[ks] = *(const i32x8*)(qrow + ks * 64);
-    }
-
-    // ---- staging: one 16-B chunk of the K tile and one of the V^T tile per thread ----
-    const int kr = tid >> 3, kc = tid & 7;          // K: row, chunk
-    const int vd = tid >> 2, vc = tid & 3;          // V^T: row (= d), chunk
-    const int k_dst = f8_k_off(kr, kc), v_dst = kKBytes + f8_v_off(vd, vc);
-    u32x4 kreg, vreg;
-    auto issue = [&](int k0) {   // k0: first key of the tile (a multiple of 64; rows behind S are zero in the padded images)
-        kreg = *(const u32x4*)(k8 + (size_t)(k0 + kr) * D + kc * 16);
-        vreg = *(const u32x4*)(vt8 + (size_t)(k0 >> 6) * (kBN * D) + tid * 16);
-    };
-    auto stage_write = [&](int buf) {
-        char* base = smem + buf * kStage;
-        *(u32x4*)(base + k_dst) = kreg;
-        *(u32x4*)(base + v_dst) = vreg;
-    };
-
-    // per-lane operand offsets: K fragment (block b, step ks) = chunks 4 ks + 2 g, +1 of row 32 b + ql (32 % 16 == 0: same swizzle
-    // for both blocks); V^T fragment (d block db) = chunks 2 g, 2 g + 1 of row 32 db + ql
-    const int ksw = (ql >> 1) & 7;
-    const int vsw = (ql >> 2) & 3;                  // (32 db + ql) >> 2 & 3 == ql >> 2 & 3
-    const int k_lane = ql * 128, v_lane = kKBytes + ql * 64;
-
-    float m_run = -INFINITY, l_run = 0.f;
-    f32x16 acc_o[DB];
-#pragma unroll
-    for (int db = 0; db < DB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc_o[db][r] = 0.f;
-
-    const float c_log2 = two_e;      // (q8 carries the softmax scale up to this power of two)
-    const int nT = ctx.nT;
-
-    // S^T of one tile: 4 MFMAs (2 key blocks x 2 contraction steps of 64)
-    auto qk = [&](const char* kbuf, f32x16 (&s)[2]) {
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[b][r] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const char* rowp = kbuf + k_lane + b * (32 * 128);
-                const u32x4 lo = *(const u32x4*)(rowp + (((4 * ks + 2 * g) ^ ksw) << 4));
-                const u32x4 hi = *(const u32x4*)(rowp + (((4 * ks + 2 * g + 1) ^ ksw) << 4));
-                const i32x8 kf = {(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-                s[b] = mfma_f8(kf, qf[ks], s[b]);
-            }
-    };
-
-    // Two LDS stages, register-staged: iteration t computes tile t from stage t & 1, then writes tile t + 1 (registers loaded
-    // during t - 1) into the other stage and requests tile t + 2; one barrier per tile.
-    typename P::TileCur tc;          // walks two tiles ahead of the tile being processed
-    P::tile_cur_init(ctx, tc);
-    int f0 = tc.k0;                  // first key of tile t, t + 1 (f1 is what `issue` reads next)
-    P::tile_cur_next(ctx, tc);
-    int f1 = tc.k0;
-    P::tile_cur_next(ctx, tc);
-    if (nT > 0) {
-        issue(f0);
-        stage_write(0);
-        if (nT > 1) issue(f1);
-    }
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[ks]));   // Q has landed before the loop (see attn_body)
-    __syncthreads();
-
-    // Softmax without a running maximum (the scheme of attn_body_w4): probabilities are taken relative to a per-row reference
-    // m_ref that only changes on the exact path, p = 2^(s c - m_ref + 4); as long as a lane's 32 probabilities of a tile sum to
-    // <= 448 every one of them fits e4m3 and nothing else has to be checked.  A violation (normally also the first tile, whose
-    // reference is the pseudo-reference 0) sends the WAVE through the exact path: row maximum, new reference, O and l rescaled, probabilities
-    // recomputed.  On random data that is the first tile of a q-tile and a handful of later ones.
-    constexpr float kPShift = 4.f, kPSumMax = 448.f;
-    float m_ref = -INFINITY, m_off = -kPShift;    // m_off = (m_ref finite ? m_ref : 0) - kPShift
-    float psum_thr = -1.f;   // kPSumMax once every row of the wave has a finite reference (see attn_body_pp2)
-    // Packed probabilities.  Lives outside the loop on purpose: v_cvt_pk_fp8_f32 writes one half of its destination and keeps the
-    // other, so the builtin takes the destination's old value — a literal 0 there costs a v_mov per word and tile (8 of the ~100
-    // VALU instructions of a tile), the word's own stale contents cost nothing, and both halves are rewritten anyway.
-    i32x8 pf = {0, 0, 0, 0, 0, 0, 0, 0};
-    int buf = 0;
-    for (int t = 0; t < nT; ++t) {
-        const char* kbuf = smem + buf * kStage;
-        const int tk0 = f0;
-        f0 = f1, f1 = tc.k0;
-        P::tile_cur_next(ctx, tc);
-        const int cls = P::fast_full(ctx, tk0) ? (int)TILE_FULL : P::classify(prm, ctx, tk0, wave * 32);
-        if (cls != TILE_SKIP) {
-            f32x16 s_cur[2];
-            qk(kbuf, s_cur);
-            if (cls == TILE_PARTIAL) {
-                asm volatile("; element-wise mask of a partial tile" ::: "memory");   // (keeps hipcc from if-converting the 32 predicates
-                                                                                      //  into code that every tile executes)
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int key = 32 * b + (r & 3) + 8 * (r >> 2) + 4 * g;
-                        s_cur[b][r] = P::allowed(prm, ctx, q_log, tk0 + key) ? s_cur[b][r] : -INFINITY;
-                    }
-            }
-            // probabilities of this lane's 32 keys at reference offset `off`: packed e4m3 operand + their fp32 sum
-            float psum;
-            auto probs = [&](float off) {
-                psum = 0.f;
-#pragma unroll
-                for (int w8 = 0; w8 < 8; ++w8) {
-                    float p4[4];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const int e = 4 * w8 + i;
-                        p4[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(s_cur[e >> 4][e & 15], c_log2, -off));
-                        psum += p4[i];
-                    }
-                    const int w = __builtin_amdgcn_cvt_pk_fp8_f32(p4[0], p4[1], pf[w8], false);   // (old = the word's stale contents: see pf)
-                    pf[w8] = __builtin_amdgcn_cvt_pk_fp8_f32(p4[2], p4[3], w, true);
-                }
-            };
-            probs(m_off);
-            if (__any(!(psum <= psum_thr))) {      // exact path (rare; always until every row has a finite reference: see attn_body_pp2)
-                float mx = s_cur[0][0];
-#pragma unroll
-                for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s_cur[0][r]);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s_cur[1][r]);
-                mx = fmaxf(mx, __shfl_xor(mx, 32));
-                // (until a row has seen a finite score its reference is the pseudo-reference 0 that m_off starts with: whatever was
-                //  accumulated under it is rescaled like under any other reference; the clamp keeps alpha finite when nothing was)
-                const float m_prev = m_off + kPShift;
-                const float m_new = fmaxf(m_ref, mx * c_log2);
-                const float m_use = (m_new == -INFINITY) ? m_prev : m_new;
-                const float alpha = __builtin_amdgcn_exp2f(fminf(m_prev - m_use, 126.f));
-                m_ref = m_new;
-                psum_thr = __any(m_new == -INFINITY) ? -1.f : kPSumMax;
-                m_off = m_use - kPShift;
-                probs(m_off);
-                l_run *= alpha;
-#pragma unroll
-                for (int db = 0; db < DB; ++db)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc_o[db][r] *= alpha;
-            }
-            l_run += psum;
-            // ---------------- O^T += V^T P^T: 4 MFMAs ----------------
-#pragma unroll
-            for (int db = 0; db < DB; ++db) {
-                const char* rowp = kbuf + v_lane + db * (32 * 64);
-                const u32x4 lo = *(const u32x4*)(rowp + (((2 * g) ^ vsw) << 4));
-                const u32x4 hi = *(const u32x4*)(rowp + (((2 * g + 1) ^ vsw) << 4));
-                const i32x8 vf = {(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-                acc_o[db] = mfma_f8(vf, pf, acc_o[db]);
-            }
-        }
-        if (t + 1 < nT) stage_write(buf ^ 1);
-        if (t + 2 < nT) issue(f1);
-        __syncthreads();
-        buf ^= 1;
-    }
-
-    // ---------------- epilogue: O^T -> LDS -> whole rows (inverse placement through q_phys), as attn_body ----------------
-    const float l_tot = l_run + __shfl_xor(l_run, 32);
-    constexpr int kEpiStride = D * 2 + 8;
-    char* erow = smem + (size_t)(wave * 32) * kEpiStride;
-    {
-        const float inv = l_tot > 0.f ? inv_v / l_tot : 0.f;
-#pragma unroll
-        for (int db = 0; db < DB; ++db)
-#pragma unroll
-            for (int rq = 0; rq < 4; ++rq) {
-                typename E::v4 o4;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) o4[j] = E::from_float(acc_o[db][rq * 4 + j] * inv);
-                const int d0 = 32 * db + 8 * rq + 4 * g;
-                *(typename E::v4*)(erow + ql * kEpiStride + d0 * 2) = o4;
-            }
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-    T* __restrict__ ob = P::o_base(prm, ctx);
-    constexpr int kLanesPerRow = D * 2 / 8, kRowsPerPass = 64 / kLanesPerRow, kPasses = 32 / kRowsPerPass;
-    const int sub = lane / kLanesPerRow, colb = (lane - sub * kLanesPerRow) * 8;
-    int ephys[kPasses];
-#pragma unroll
-    for (int i = 0; i < kPasses; ++i) ephys[i] = P::q_phys(prm, ctx, wave * 32 + i * kRowsPerPass + sub);
-#pragma unroll
-    for (int i = 0; i < kPasses; ++i) {
-        const int rr = i * kRowsPerPass + sub;
-        const u32x2 val = *(const u32x2*)(erow + rr * kEpiStride + colb);
-        if (ephys[i] >= 0) *(u32x2*)((char*)(ob + (size_t)ephys[i] * D) + colb) = val;
-    }
-    P::notify(prm, ctx);
-}
-
 
 // =====================================================================================================================
 // Two-phase ping-pong form of the fp8 band body: the schedule of attn_body_pp2 (attn_core.h) on e4m3 operands.  Per tile every wave
 // runs ONE matrix phase — O^T += V(t)^T P(t)^T (4 MFMAs), S(t+1)^T = K(t+1) Q^T (4 MFMAs), operands streamed from LDS ahead of
 // their MFMA — and ONE vector phase — mask, softmax numerators without a running maximum, LDS-DMA request of a later tile, DMA
 // wait; waves 4..7 run one phase behind waves 0..3 (two barriers per tile), so a SIMD always pairs the matrix phase of one wave
-// with the vector phase of the other.  In the lock-step body
-// (attn_body_f8) both waves of a SIMD are in the same part of the tile at the same time: they stall on their MFMAs together, then
-// share the VALU.
+// with the vector phase of the other.  In a lock-step schedule both waves of a SIMD are in the same part of the tile at the same
+// time: they stall on their MFMAs together, then share the VALU.
 //   slot         2t      2t+1    2t+2     2t+3
 //   waves 0-3    M(t)    N(t)    M(t+1)   N(t+1)          M(t) reads V(t-1) and K(t)
 //   waves 4-7    N(t-1)  M(t)    N(t)     M(t+1)
 // LDS: four stages of [K image 8 KiB | V^T image 8 KiB]; K / V^T arrive by LDS-DMA (one 1-KiB piece of each per wave and tile:
 // 8 key rows / 16 d rows, the XOR swizzle of the images applied to the per-lane SOURCE address); tile w is requested in N(w - 2)
 // (leading waves) / N(w - 3) (lagging waves), and every wave waits at the end of a vector phase for what it requested in the
-// previous one.  Inputs are those of attn_body_f8 (pre-pass images in logical token order: nothing is gathered).
+// previous one.  Inputs are the pre-pass images of the file header (logical token order: nothing is gathered).
 // =====================================================================================================================
 template <typename T, typename P>
 __device__ __forceinline__ void attn_body_f8pp(const typename P::Params& prm, const F8Args& fa, char* smem) {
@@ -361,14 +141,11 @@ __device__ __forceinline__ void attn_body_f8pp(const typename P::Params& prm, co
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[ks]));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifndef SVG_F8PP_ONEBAR
-#define SVG_F8PP_ONEBAR 0
-#endif
     // one barrier per tile (attn_core.h kOneBar: only the barrier in front of the leading waves' matrix phase carries data) — measured
     // for this body and NOT shipped: 22.55 vs 21.98 ms (same box, round 3).  Its phases are unbalanced (matrix ~550, vector ~1000
     // cycles), so without the second barrier the two vector phases of a SIMD overlap for half a tile, and unlike the 16-bit kernel
     // this one is not at the power limit (2.33 GHz sustained): the strict opposition of the phases is worth more than the barrier.
-    constexpr bool kOneBar = SVG_F8PP_ONEBAR != 0;
+    constexpr bool kOneBar = false;
     const int bar_n = lagging ? 1 : 0, bar_m = lagging ? 0 : 1;
     pp_barrier();
     if (!kOneBar && lagging) pp_barrier();      // waves 4..7 run one phase behind
@@ -395,9 +172,16 @@ __device__ __forceinline__ void attn_body_f8pp(const typename P::Params& prm, co
     }
 
     f32x16 sc[2];          // S(t) until the vector phase has turned it into pf, then S(t + 1) accumulates here
-    i32x8 pf = {0, 0, 0, 0, 0, 0, 0, 0};   // probabilities of tile t (e4m3, slot order of the file header); every word is rewritten
-                                           // per tile with its own stale contents as the conversions' "old" operand (see attn_body_f8)
-    constexpr float kPShift = 4.f, kPSumMax = 448.f;     // softmax without a running maximum: see attn_body_f8
+    // Probabilities of tile t (e4m3, slot order of the file header).  Lives outside the loop on purpose: v_cvt_pk_fp8_f32 writes one
+    // half of its destination and keeps the other, so the builtin takes the destination's old value — a literal 0 there costs a v_mov
+    // per word and tile, the word's own stale contents cost nothing, and both halves are rewritten anyway.
+    i32x8 pf = {0, 0, 0, 0, 0, 0, 0, 0};
+    // Softmax without a running maximum (the scheme of attn_body_w4): probabilities are taken relative to a per-row reference m_ref
+    // that only changes on the exact path, p = 2^(s c - m_ref + 4); as long as a lane's 32 probabilities of a tile sum to <= 448
+    // every one of them fits e4m3 and nothing else has to be checked.  A violation (normally also the first tile, whose reference is
+    // the pseudo-reference 0) sends the WAVE through the exact path: row maximum, new reference, O and l rescaled, probabilities
+    // recomputed.  On random data that is the first tile of a q-tile and a handful of later ones.
+    constexpr float kPShift = 4.f, kPSumMax = 448.f;
     float m_ref = -INFINITY, m_off = -kPShift, psum = 0.f;
     float psum_thr = -1.f;   // kPSumMax once every row of the wave has a finite reference (see attn_body_pp2)
     f32x16 cneg;           // -m_off in every register: the C operand of the first QK MFMA of a tile
@@ -559,7 +343,7 @@ __device__ __forceinline__ void attn_body_f8pp(const typename P::Params& prm, co
     pp_barrier();
     if (!kOneBar && !lagging) pp_barrier();
 
-    // ---------------- epilogue: as attn_body_f8 ----------------
+    // ---------------- epilogue: O^T -> LDS -> whole rows (inverse placement through q_phys), as attn_body ----------------
     float l_tot = l_run + __shfl_xor(l_run, 32);
     constexpr int kEpiStride = D * 2 + 8;
     char* erow = smem + (size_t)(wave * 32) * kEpiStride;
@@ -706,7 +490,7 @@ __device__ __forceinline__ void attn_body_f8g(const typename P::Params& prm, con
     for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[ks]));
     __syncthreads();
 
-    constexpr float kPShift = 4.f, kPSumMax = 448.f;     // softmax without a running maximum: see attn_body_f8
+    constexpr float kPShift = 4.f, kPSumMax = 448.f;     // softmax without a running maximum: see attn_body_f8pp
     float m_ref = -INFINITY, m_off = -kPShift;
     float psum_thr = -1.f;   // kPSumMax once every row of the wave has a finite reference (see attn_body_pp2)
     f32x16 cneg;           // -m_off in every register
@@ -739,7 +523,7 @@ __device__ __forceinline__ void attn_body_f8g(const typename P::Params& prm, con
                      : "v"(a), "v"(b), "v"(cneg), "v"(scale_a_v), "v"(scale_q_v));
         return d;
     };
-    i32x8 pf = {0, 0, 0, 0, 0, 0, 0, 0};   // (outside the loop: its stale words are the conversions' "old" operand, see attn_body_f8)
+    i32x8 pf = {0, 0, 0, 0, 0, 0, 0, 0};   // (outside the loop: its stale words are the conversions' "old" operand, see attn_body_f8pp)
     int buf = 0;
     for (int t = 0; t < nT; ++t) {
         const char* kbuf = smem + buf * kStage;

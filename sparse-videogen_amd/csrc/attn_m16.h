@@ -75,29 +75,17 @@ __device__ __forceinline__ float quad_group_sum(float x) {
     return x + __shfl_xor(x, 32);
 }
 
-// PRIO: which phase raises the wave's issue priority (1: matrix phase, as attn_body_pp2; 0: none; 2: vector phase).  ONEBAR: -1 as the
-// policy says, 0 / 1 forced.
+// ONEBAR: -1 as the policy says, 0 / 1 forced.  The matrix phase runs at issue priority 1, as in attn_body_pp2.
 // PRE: q arrives multiplied by sm_scale * log2(e) and the S^T accumulators start at minus the row's reference, so the MFMAs deliver the
-// exponent argument (no scale-and-shift FMA per score; the scheme of attn_body_pp2's PRE form).  QKF16 (with PRE): the q and k pointers
-// hold IEEE fp16 bit patterns whatever T is — q' = fp16(c * q), k16 = fp16(k), written by svg_qk_to_f16 — and S^T runs on the f16 MFMA
-// while P, V and O stay T: for T = bf16 the scale then rides in 11 mantissa bits instead of 8 (2^-12 instead of 2^-9 relative rounding
-// of c * q; a bf16 k converts to fp16 exactly inside fp16's range), which keeps the pre-scaled form inside the plain kernel's distance
-// to the reference's formulation.  MEASURED in round 4 and NOT shipped (an entry point svg_band_attention_f16qk with a conversion pass and a
-// device-side overflow fallback to the plain body was built, tested and removed within the session; what is left are the numbers): parity as intended — 1.95 - 2.33e-3 rel. L2 to the reference's formulation on
-// |score| up to 80, the plain kernel's 1.85 - 2.32e-3, where the bf16 pre-scaled form reaches 6.4e-3 (profiles/r04l_pytest_f16qk.txt) — but
-// no time: the kernel took 33.8 ms where the bf16 PRE form takes 32.8 and the plain body 34.5 under the same profiler run, plus 0.58 ms
-// for the conversion pass (profiles/r04m_f16qk_kernel_trace.txt, r04l_ab_m16_f16qk.txt: 32.9 vs 33.4 ms end to end, -1.4 %).  The f16
-// MFMA's wider multipliers take back in clock what the missing FMAs save — the power limit once more.  The template flag stays (it is
-// four lines of the body); nothing instantiates it.
-template <typename T, typename P, bool TRACE = false, int PRIO = 1, int ONEBAR = -1, bool PRE = false, bool QKF16 = false>
+// exponent argument (no scale-and-shift FMA per score; the scheme of attn_body_pp2's PRE form).
+// (Round 4 measured a PRE form with q and k as fp16 carriers and S^T on the f16 MFMA: the plain kernel's distance to the reference's
+//  formulation, but no time — 33.8 ms against 32.8 for the bf16 PRE form, plus 0.58 ms for the conversion pass; profiles/r04l_*,
+//  r04m_f16qk_kernel_trace.txt.  Removed with the template flag that kept it.)
+template <typename T, typename P, bool TRACE = false, int ONEBAR = -1, bool PRE = false>
 __device__ __forceinline__ void attn_body_m16(const typename P::Params& prm, char* smem, char* policy_lds) {
     using E = Elt<T>;
-    using M = Mfma16<T>;                                                  // PV
-    using TQ = std::conditional_t<QKF16, _Float16, T>;                    // element type of the q / k bits
-    using MQ = Mfma16<TQ>;                                                // QK^T
+    using M = Mfma16<T>;
     using V8 = typename E::v8;
-    using Q8 = typename Elt<TQ>::v8;
-    static_assert(!QKF16 || PRE, "fp16 q / k carriers exist for the pre-scaled form only");
     constexpr int D = 128;
     constexpr int NW = 8;
     constexpr int KS = D / 32;              // 32-wide contraction steps of S^T
@@ -106,11 +94,11 @@ __device__ __forceinline__ void attn_body_m16(const typename P::Params& prm, cha
     constexpr int kImg = kBN * D * 2;       // bytes of a K or V image
     constexpr int kStage = 2 * kImg;
     constexpr int NP = 2;                   // DMA pieces (16 keys x 64 B) per wave per tensor per tile
-    constexpr int kCarry = 8;               // V fragments of the next matrix phase read in the tail of this one (attn_body_pp2: SVG_PP2_CARRY)
+    constexpr int kCarry = 8;               // V fragments of the next matrix phase read in the tail of this one (attn_body_pp2: kCarry)
     constexpr int kPF = 8;                  // operand fragments in flight ahead of their MFMAs
     constexpr bool kOneBar = ONEBAR < 0 ? P::kOneBarrier : (ONEBAR != 0);   // one workgroup barrier per tile instead of two (attn_body_pp2: on for the variable-block policy)
-    static_assert(P::kRowBlocks == 1 && P::kSubTiles == 1 && !P::kPartialOut && !P::kFixup && P::kIntervalMask, "band / variable-block policy");
-    // MSUM (SVG_M16_MFMASUM, bf16, plain form): the row sum on the matrix pipe.  Four extra MFMAs per tile (A = a fragment of ones, B = the
+    static_assert(P::kRowBlocks == 1 && !P::kPartialOut && !P::kFixup && P::kIntervalMask, "band / variable-block policy");
+    // MSUM (bf16, plain form): the row sum on the matrix pipe.  Four extra MFMAs per tile (A = a fragment of ones, B = the
     // P fragment: every accumulator of a lane receives the COMPLETE sum of its query row over the chunk's 32 keys) replace the 32 v_add of
     // the vector phase; the overflow test of the max-free softmax — a probability above the reference by more than 2^kBias — becomes a bit
     // test on the packed bf16 probabilities: with the exponent argument lowered by kBias a probability reaches 2.0 (exponent field >= 128,
@@ -119,11 +107,7 @@ __device__ __forceinline__ void attn_body_m16(const typename P::Params& prm, cha
     // Measured (profiles/r05a_ab_m16_msum_prio3.txt, same box, HunyuanVideo 720p): 64.1 instead of 65.1 Mcycles per launch, of which the power
     // management returns half as clock (1985 vs 2000 MHz): 32.3 against 32.55 ms; with the sum MFMAs after the chunk's LAST PV step instead of
     // its first the gain is gone (65.4 Mcycles).  fp16 keeps the vector-phase sum: 2^-10 would push small probabilities into fp16's subnormals.
-#ifdef SVG_M16_NO_MFMASUM
-    constexpr bool MSUM = false;
-#else
     constexpr bool MSUM = std::is_same_v<T, __bf16> && !PRE;
-#endif
     constexpr float kBias = MSUM ? 10.f : 0.f;
 
     typename P::Ctx ctx;
@@ -194,7 +178,7 @@ __device__ __forceinline__ void attn_body_m16(const typename P::Params& prm, cha
 
     // ---- Q fragments, mask intervals and softmax state of the lane's two query rows ----
     int q_log[2];
-    Q8 qf[2][KS];
+    V8 qf[2][KS];
     int m_a0[2], m_b0[2];
     unsigned m_alen[2], m_blen[2];
 #pragma unroll
@@ -204,7 +188,7 @@ __device__ __forceinline__ void attn_body_m16(const typename P::Params& prm, cha
         q_log[rb] = P::q_logical(ctx, row_in_wg);
         const T* qrow = qb + (size_t)(qp >= 0 ? qp : 0) * P::q_rs(prm) + g4 * 8;
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) qf[rb][ks] = *(const Q8*)(qrow + ks * 32);
+        for (int ks = 0; ks < KS; ++ks) qf[rb][ks] = *(const V8*)(qrow + ks * 32);
         P::row_intervals(prm, ctx, q_log[rb], m_a0[rb], m_alen[rb], m_b0[rb], m_blen[rb]);
     }
 
@@ -258,7 +242,7 @@ __device__ __forceinline__ void attn_body_m16(const typename P::Params& prm, cha
     V8 pf[2][2];           // probabilities [32-key chunk][row block]
     float psum_thr = -1.f; // (wave-uniform) 2048 once every row of the wave has a finite reference; until then every tile takes the exact path
 
-    // operand fragments travel as raw bits (the ring holds V fragments of type T and K fragments of type TQ)
+    // operand fragments travel as raw bits
     auto kfrag = [&](const char* st, int kblk, int ks) -> i16x8 { return *(const i16x8*)(st + k_lane + ks * (kBN * 64) + kblk * 1024); };
     auto vfrag = [&](const char* st, int kc, int db) -> i16x8 {
         const char* vbase = st + ((db & 1) ? v_lane1 : v_lane0) + (db >> 1) * (kBN * 64) + (32 * kc) * 64;
@@ -410,11 +394,7 @@ __device__ __forceinline__ void attn_body_m16(const typename P::Params& prm, cha
     // Matrix phase: O^T += V(t)^T P(t)^T (16 fragments, 32 MFMAs), then S(t+1)^T = K(t+1) Q^T (16 fragments, 32 MFMAs).  One step =
     // { LDS read of the fragment kPF steps ahead; the fragment's two MFMAs (row blocks 0 and 1) }, fenced with sched_barrier.
     constexpr int NPV = 2 * NDB;
-#ifdef SVG_M16_MSUM_AT
-    constexpr int kMsumAt = SVG_M16_MSUM_AT;
-#else
     constexpr int kMsumAt = 0;         // the d block after whose MFMAs the chunk's two row-sum MFMAs are issued
-#endif
     i16x8 ring[kPF + 1];
     i16x8 carry[kCarry];
     auto carry_load = [&](int t, int i) { carry[i] = vfrag(smem + (t % NS) * kStage, i / NDB, i % NDB); };
@@ -457,15 +437,15 @@ __device__ __forceinline__ void attn_body_m16(const typename P::Params& prm, cha
                 }
             } else {
                 const int j = i - NPV, ks = j >> 2, b = j & 3;
-                const Q8 a = __builtin_bit_cast(Q8, ring[i % (kPF + 1)]);
+                const V8 a = __builtin_bit_cast(V8, ring[i % (kPF + 1)]);
                 // (PRE, first step: D = A B + neg_ref with neg_ref left where it is.  Its result is read by the next step's MFMA of the same
                 //  key block only, as C, same tuple; neg_ref is written on the exact path of a vector phase, a barrier away.)
                 if constexpr (PRE) {
-                    sc[b][0] = ks == 0 ? MQ::mfma_keep_c(a, qf[0][ks], neg_ref[0]) : MQ::mfma(a, qf[0][ks], sc[b][0]);
-                    sc[b][1] = ks == 0 ? MQ::mfma_keep_c(a, qf[1][ks], neg_ref[1]) : MQ::mfma(a, qf[1][ks], sc[b][1]);
+                    sc[b][0] = ks == 0 ? M::mfma_keep_c(a, qf[0][ks], neg_ref[0]) : M::mfma(a, qf[0][ks], sc[b][0]);
+                    sc[b][1] = ks == 0 ? M::mfma_keep_c(a, qf[1][ks], neg_ref[1]) : M::mfma(a, qf[1][ks], sc[b][1]);
                 } else {
-                    sc[b][0] = MQ::mfma(a, qf[0][ks], ks == 0 ? zero : sc[b][0]);
-                    sc[b][1] = MQ::mfma(a, qf[1][ks], ks == 0 ? zero : sc[b][1]);
+                    sc[b][0] = M::mfma(a, qf[0][ks], ks == 0 ? zero : sc[b][0]);
+                    sc[b][1] = M::mfma(a, qf[1][ks], ks == 0 ? zero : sc[b][1]);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -496,9 +476,9 @@ __device__ __forceinline__ void attn_body_m16(const typename P::Params& prm, cha
         for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
-                const Q8 a = __builtin_bit_cast(Q8, kfrag(smem, b, ks));
-                sc[b][0] = MQ::mfma(a, qf[0][ks], ks == 0 ? zero : sc[b][0]);   // (reference 0 so far, also for PRE)
-                sc[b][1] = MQ::mfma(a, qf[1][ks], ks == 0 ? zero : sc[b][1]);
+                const V8 a = __builtin_bit_cast(V8, kfrag(smem, b, ks));
+                sc[b][0] = M::mfma(a, qf[0][ks], ks == 0 ? zero : sc[b][0]);   // (reference 0 so far, also for PRE)
+                sc[b][1] = M::mfma(a, qf[1][ks], ks == 0 ? zero : sc[b][1]);
             }
 #pragma unroll
         for (int b = 0; b < 4; ++b) asm volatile("" : "+v"(sc[b][0]), "+v"(sc[b][1]));
@@ -513,20 +493,15 @@ __device__ __forceinline__ void attn_body_m16(const typename P::Params& prm, cha
         if constexpr (kOneBar) pp_barrier_if(bar_n);
         else pp_barrier();
         tick(std::integral_constant<int, 1>{});
-        if constexpr (PRIO == 2) __builtin_amdgcn_s_setprio(1);
         vector_phase(t, guard_c);
-        if constexpr (PRIO == 2) __builtin_amdgcn_s_setprio(0);
         tick(std::integral_constant<int, 2>{});
         if constexpr (kOneBar) pp_barrier_if(bar_m);
         else pp_barrier();
         tick(std::integral_constant<int, 3>{});
-        if constexpr (PRIO == 1) __builtin_amdgcn_s_setprio(1);   // the matrix phase wins the issue arbitration against the partner's vector phase
+        __builtin_amdgcn_s_setprio(1);   // the matrix phase wins the issue arbitration against the partner's vector phase
         matrix_phase(t, has_next_c);
-        if constexpr (PRIO == 1) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
     };
-    if constexpr (PRIO == 3) {   // static priority for the younger half (cdna_hip_programming.md T5, static form): no per-phase flips
-        if (lagging) __builtin_amdgcn_s_setprio(1);
-    }
     // steady state: every tile a phase of tile t touches (t + dist + 1 at most) exists; then the guarded tail; then the peeled last tile
     int t = 0;
     for (const int n_main = nT - dist - 1; t < n_main; ++t) tile(t, std::true_type{}, std::false_type{});

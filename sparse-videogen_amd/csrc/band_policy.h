@@ -37,20 +37,15 @@ inline int check_band_mask(int S, const svg_band_mask_t* mask, const svg_perm_de
 // =====================================================================================================
 // Band policy: analytic mask family (see svg_band_mask_t in svg_attn.h)
 // =====================================================================================================
-template <typename T, int D, int NW, bool SKEW, int ABL = 0, int RB = 1, int SUBS = 1>
+template <typename T, int D, int NW, int RB = 1>
 struct BandPolicy {
     static constexpr int kHeadDim = D;
-    static constexpr int kSubTiles = SUBS;   // 64-key tiles per LDS stage / barrier
-    static constexpr int kPrefetch = (ABL == 12) ? 3 : (ABL == 13 ? 2 : 1);  // operand ring depth (k-steps / MFMA steps ahead)
     static constexpr bool kFixup = false;
     static constexpr bool kPartialOut = false;
     static constexpr bool kIntervalMask = true;   // row_intervals() describes the mask (two-phase body)
     static constexpr bool kFastPartial = false;
     static constexpr int kShadow128 = 1;   // two-phase body, D = 128: probability steps in the MFMA shadow (measured best)
-    static constexpr int kAbl = ABL;  // > 0 only for the ablation variants (timing experiments)
-    static constexpr bool kSetPrio = false;  // measured: s_setprio around the MFMA clusters costs 2 % here
     static constexpr bool kOneBarrier = false;   // two-phase body: two barriers per tile (one measured neutral for this policy)
-    static constexpr bool kSkew = SKEW;
     static constexpr int kRowBlocks = RB;    // 32-row blocks per wave
     static constexpr int kWR = 32 * RB;      // rows per wave
     static constexpr int BM = NW * kWR;
@@ -66,7 +61,7 @@ struct BandPolicy {
         const int64_t* head_flag;
         int vid0, F, P, V;
         int q64, r64;          // 64 / F, 64 % F: tile-to-tile step of the (patch, frame) decomposition
-        int q128, r128;        // the same for a 128-row step (two tiles per stage)
+        int q128, r128;        // the same for a 128-row step (unused since the two-tiles-per-stage schedule went; kept: argument layout)
         int sp64, sp128;       // physical-row step of a token-major head: q + r * P (the patch index advances by q, the frame by r)
         int wrap_phys;         // 1 - F * P: correction when the frame index wraps
         int heavy_lo, n_heavy; // q-tiles [heavy_lo, heavy_lo + n_heavy) of every head see ALL keys (text rows): scheduled first
@@ -122,11 +117,7 @@ struct BandPolicy {
             const int b2 = b - nh;
             const int full = ((p.nqt * p.BH - nh) / (kNumXCD * 32)) * (kNumXCD * 32);
             int w2 = b2;
-#ifdef SVG_BAND_NO_XCD_SWIZZLE      // A/B builds: dispatch id = work id (the hardware's round-robin then hands NEIGHBOURING q-tiles to DIFFERENT XCDs)
-            if (false) {
-#else
-            if (b2 < full) {
-#endif
+            if (b2 < full) {   // (dispatch id = work id instead measured 5 % slower: profiles/r06e_*)
                 const int xcd = b2 % kNumXCD, s = b2 / kNumXCD;
                 w2 = (s / 32) * (kNumXCD * 32) + xcd * 32 + (s % 32);
             }
@@ -294,12 +285,11 @@ struct BandPolicy {
         // so the frame and the physical row are stepped (5 VALU, no multiply) instead of divided (~30 VALU); segment jumps re-divide.
         // A tile that lies inside the video range (scalar test) needs neither the range selects nor the bounds test.
         int f, physv;
-        // a cursor advances by one stage per call: 64 keys, or 128 with two tiles per stage (each chunk keeps its sub-tile)
-        constexpr int kStep = kBN * SUBS;
+        // a cursor advances by one tile (64 keys) per call
         const int delta = __builtin_amdgcn_readfirstlane(k0 - cu.prev_k0);
-        if (delta == kStep) {
-            f = cu.f + (SUBS == 1 ? p.r64 : p.r128);
-            physv = cu.physv + (SUBS == 1 ? p.sp64 : p.sp128);
+        if (delta == kBN) {
+            f = cu.f + p.r64;
+            physv = cu.physv + p.sp64;
             const bool wrap = f >= p.F;
             f = wrap ? f - p.F : f;
             physv = wrap ? physv + p.wrap_phys : physv;
@@ -312,7 +302,7 @@ struct BandPolicy {
             physv = p.vid0 + f * p.P + pp;
         }
         cu.physv = physv, cu.f = f, cu.prev_k0 = k0;
-        if (k0 >= p.vid0 && k0 + kStep <= p.vid0 + p.V) return physv;
+        if (k0 >= p.vid0 && k0 + kBN <= p.vid0 + p.V) return physv;
         const bool in_video = (unsigned)(l - p.vid0) < (unsigned)p.V;
         const int phys = in_video ? physv : l;
         return l < p.S ? phys : 0;

@@ -67,9 +67,6 @@ __global__ __launch_bounds__(kDynThreads) void dynmap_kernel(const T* __restrict
 #pragma unroll
                 for (int u = 0; u < kJB; ++u) acc[u] = __builtin_fma(qd, (double)Elt<T>::to_float(v[u][e]), acc[u]);
             }
-#ifdef SVG_DYN_ABL
-            if ((SVG_DYN_ABL) & 1) break;
-#endif
         }
 #pragma unroll
         for (int u = 0; u < kJB; ++u) {
@@ -111,9 +108,6 @@ __global__ __launch_bounds__(kDynThreads) void dynmap_kernel(const T* __restrict
         keys[j] = key;
     }
     __syncthreads();
-#ifdef SVG_DYN_ABL
-    if (!((SVG_DYN_ABL) & 2))
-#endif
     for (int k = 2; k <= N2; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
             for (int t = tid; t < N2 / 2; t += kDynThreads) {
@@ -137,9 +131,6 @@ __global__ __launch_bounds__(kDynThreads) void dynmap_kernel(const T* __restrict
         // (the same sequence of fp32 additions as a one-by-one walk; the keys of a block of 8 are loaded together, so the walk pays
         //  one LDS round trip per 8 positions instead of one per position — N2 is a power of two >= 2, entries behind KC hold the
         //  probability 0 sentinel and are never reached: the r < KC test comes first)
-#ifdef SVG_DYN_ABL
-        if ((SVG_DYN_ABL) & 4) done = true, r = KC / 4;
-#endif
         for (int r0 = 0; r0 < KC && !done; r0 += 8) {
             unsigned long long kq[8];
 #pragma unroll
@@ -180,10 +171,7 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 constexpr int kDyn2Rows = 16;
 constexpr int kDyn2E = 16;                  // keys per lane
 constexpr int kDyn2N = 64 * kDyn2E;         // 1024
-#ifndef SVG_DYN2_WAVES
-#define SVG_DYN2_WAVES 8
-#endif
-constexpr int kDyn2Waves = SVG_DYN2_WAVES;   // waves per workgroup: the key blocks of step 1 and the rows of step 2 are dealt round-robin
+constexpr int kDyn2Waves = 8;   // waves per workgroup: the key blocks of step 1 and the rows of step 2 are dealt round-robin
 
 template <int E>
 __device__ __forceinline__ void wave_bitonic_sort(unsigned (&key)[E], int lane) {
@@ -356,7 +344,6 @@ extern "C" int svg_identify_dynamic_map(const void* qc, const void* kc, const in
     dim3 grid(QC, BH);
     hipStream_t st = (hipStream_t)stream;
     // 256 < KC <= 1024: the second form (dynmap16_kernel); smaller and larger maps keep the first one
-#ifndef SVG_DYNMAP_FIRST_FORM
     if (KC > 256 && KC <= kDyn2N) {   // (small maps: the first form sorts the next power of two of KC, this one always 1024 keys)
         dim3 grid16((QC + kDyn2Rows - 1) / kDyn2Rows, BH);
 #define SVG_DYN16(T, DD) \
@@ -369,7 +356,6 @@ extern "C" int svg_identify_dynamic_map(const void* qc, const void* kc, const in
 #undef SVG_DYN16
         return launch_status();
     }
-#endif
 #define SVG_DYN(T, DD)                                                                                                   \
     hipLaunchKernelGGL((dynmap_kernel<T, DD>), grid, dim3(kDynThreads), lds, st, (const T*)qc, (const T*)kc, k_sizes, out_map, \
                        QC, KC, inv, top_p, preserve_length)

@@ -383,11 +383,8 @@ static int run_kmeans_update(const void* x, const void* c_in, void* c_out, const
     const int nchunks = (N + 1023) / 1024;
     // workgroups per batch: three per CU over the whole launch.  Measured at Wan 720p (40 heads, K = 300 and 1000 on two streams, the 2-iteration
     // stage): 6 per head 3.49 ms, 8 3.27, 12 3.14, 16 3.05, 20 3.02, 26 3.13, 32 3.17, 52 3.22, 100 3.36, one per cluster 3.37; the kernel of
-    // round 4 (one workgroup per cluster, no prefetch) 3.39 (profiles/r05zw_kmeans_update_groups.txt).  SVG_KMEANS_UPDATE_GROUPS: A/B builds
-    int groups = std::max(1, std::min(K, (3 * kNumCU + B - 1) / B));
-#ifdef SVG_KMEANS_UPDATE_GROUPS_ENV
-    if (const char* e = getenv("SVG_KMEANS_UPDATE_GROUPS")) groups = std::max(1, std::min(K, atoi(e)));
-#endif
+    // round 4 (one workgroup per cluster, no prefetch) 3.39 (profiles/r05zw_kmeans_update_groups.txt).
+    const int groups = std::max(1, std::min(K, (3 * kNumCU + B - 1) / B));
     hipLaunchKernelGGL((kmeans_update_kernel<T, D>), dim3(groups, B), dim3(256), 0, st, (const T*)x, (const T*)c_in, (T*)c_out,
                        sorted_idx, (const int32_t*)sort_ws, counts, shift, N, K, (size_t)nchunks * K, x_bs);
     return launch_status();

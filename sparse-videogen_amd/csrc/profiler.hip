@@ -10,7 +10,7 @@
 // Two forms of the attention kernel:
 //   profile16_kernel     (bf16, round 5)  ONE score tile for the golden rows and both masks, 4 waves x 16 rows on 16x16x32 MFMAs, two
 //                        workgroups per CU — see the note above the kernel;
-//   profile_attn_kernel  (fp16; -DSVG_PROF_FIRST_FORM: both types)  the three outputs as three wave roles of one workgroup on attn_core.h's
+//   profile_attn_kernel  (fp16)  the three outputs as three wave roles of one workgroup on attn_core.h's
 //                        lock-step body: waves 0-1 the golden rows, 2-3 the rows under mask 1, 4-5 under mask 0 on the SAME staged K / V
 //                        tiles, each role its own scores.  (Before that: three workgroups, grid.z = 3, K / V staged three times, 1.26 ms per
 //                        call at HunyuanVideo 720p; the role form 0.78 -> 0.60 ms; the shipped one 0.32.)
@@ -40,12 +40,7 @@ struct ProfilePolicy {
     static constexpr bool kIntervalMask = false;
     static constexpr int kShadow128 = 1;
     static constexpr bool kFastPartial = true;     // token-major mask: tiles inside one frame row block, see classify()   // the profiling masks are general element predicates (allowed())
-    static constexpr int kAbl = 0;
-    static constexpr bool kSetPrio = false;
-    static constexpr bool kSkew = false;
     static constexpr int kRowBlocks = 1;
-    static constexpr int kSubTiles = 1;
-    static constexpr int kPrefetch = 1;
     // (225 registers: ONE workgroup per CU, so the 504 workgroups of a HunyuanVideo call run in two rounds of ~0.25 ms, each tile waiting out the
     //  latency of loads issued one tile ahead.  Round 5 tried a second staging register set (loads of tile t + 3 in flight during tile t, 241
     //  registers): as plain loads hipcc's waitcnt pass drains both sets (vmcnt(0)) in front of the older set's LDS writes — nothing gained —, and
@@ -298,11 +293,6 @@ __global__ __launch_bounds__(kProfNW * 64, 2) void profile_attn_kernel(typename 
 // exponentials, the QK or the P V MFMAs changes nothing, removing the loads gives 0.18 ms, the loads without any arithmetic take 0.309 ms whether
 // an instruction moves 16 x 64 B or 1 KiB contiguous, and two tiles of K in flight instead of one gain 1.4 % (profiles/r05zj_profiler_bound_ablations.txt).
 // Partials (O, m, l per sampled row, output and KV chunk) in the layout of the first form: profile_combine_kernel is unchanged.
-// -DSVG_P16_ABL=<bits> (timing only, results wrong by construction): 1 no mask predicates, 2 no P V of the masked outputs, 4 no wait on the staged
-// tile, 8 no loads, 16 no arithmetic in the tile loop.
-#ifndef SVG_P16_ABL
-#define SVG_P16_ABL 0
-#endif
 using p16_i32x4 = int __attribute__((ext_vector_type(4)));
 constexpr int kP16Win = 128;                                          // tiles per fill of a wave's class table
 constexpr int p16_lds_bytes(int D) { return 2 * 2 * kBN * D * 2 + 4 * kP16Win * 16; }   // two stages of a K and a V image + the four waves' tables
@@ -493,7 +483,7 @@ __global__ __launch_bounds__(256, 2) void profile16_kernel(typename ProfilePolic
     __syncthreads();
     for (int t = 0; t < nT; ++t) {
         P16_MARK(tr_wait)
-        if (!(SVG_P16_ABL & 8) && t + 1 < nT) dma_tile(t + 1);      // into the stage every wave finished reading one barrier ago
+        if (t + 1 < nT) dma_tile(t + 1);      // into the stage every wave finished reading one barrier ago
         const char* st = smem + (t & 1) * kStage;
         const int k0 = (t0 + t) * kBN;
         if ((t & (kP16Win - 1)) == 0) fill_classes(t);
@@ -504,7 +494,7 @@ __global__ __launch_bounds__(256, 2) void profile16_kernel(typename ProfilePolic
             cls[1] = __builtin_amdgcn_readfirstlane(e[0]), mc[0].ybase = __builtin_amdgcn_readfirstlane(e[1]);
             cls[2] = __builtin_amdgcn_readfirstlane(e[2]), mc[1].ybase = __builtin_amdgcn_readfirstlane(e[3]);
         }
-        if (!(SVG_P16_ABL & 16)) {
+        {
             // ---- S^T = K Q^T (lane: query row n16, keys 16 kb + 4 g4 + [0, 4)) ----
             f32x4 sc[4];
 #pragma unroll
@@ -590,9 +580,7 @@ __global__ __launch_bounds__(256, 2) void profile16_kernel(typename ProfilePolic
                             pf[v + 1][b >> 1][4 * (b & 1) + j] = E::from_float(pm);
                         }
                 };
-                if (SVG_P16_ABL & 1) {
-                    if (cls[v + 1] != TILE_SKIP) select([&](int) { return true; });
-                } else if (cls[v + 1] == TILE_PARTIAL_FAST) {
+                if (cls[v + 1] == TILE_PARTIAL_FAST) {
                     // allowed_fast with the lane's part hoisted; a mask without sink columns (every model but the 5-D Cog masks) has one interval
                     const int yb = mc[v].ybase + mc[v].g4F - mc[v].fa0, ys = mc[v].ystride;
                     const unsigned fal = mc[v].falen, fbl = mc[v].fblen;
@@ -614,7 +602,7 @@ __global__ __launch_bounds__(256, 2) void profile16_kernel(typename ProfilePolic
             {   // V^T fragments in groups of four 16-wide d-blocks, two groups in flight; a masked output's MFMAs of a group behind ONE uniform branch
                 // (if-then around in-place accumulators: no copies.  Whole-pass forms per combination cost 40 register moves per tile and spills.)
                 constexpr int G = 4, NG = 2 * NDB / G;
-                const bool s1 = !(SVG_P16_ABL & 2) && cls[1] != TILE_SKIP, s2 = !(SVG_P16_ABL & 2) && cls[2] != TILE_SKIP;
+                const bool s1 = cls[1] != TILE_SKIP, s2 = cls[2] != TILE_SKIP;
                 V8 vf[2][G];
 #pragma unroll
                 for (int i = 0; i < G; ++i) vf[0][i] = vfrag(st, 0, i);
@@ -643,7 +631,7 @@ __global__ __launch_bounds__(256, 2) void profile16_kernel(typename ProfilePolic
             }
             P16_MARK(tr_pv)
         }
-        if (!(SVG_P16_ABL & 4)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
 #ifdef SVG_PROF_TRACE
@@ -772,9 +760,6 @@ static int prof_chunks(int BH, int S) {
     n = n < 1 ? 1 : n;
     n = n > ntiles ? ntiles : n;
     n = n > 64 ? 64 : n;
-#ifdef SVG_PROF_CHUNKS_ENV
-    if (const char* e = getenv("SVG_PROF_CHUNKS")) n = std::max(1, std::min(std::min(atoi(e), ntiles), 64));   // (A/B builds only)
-#endif
     return n;
 }
 
@@ -808,12 +793,8 @@ static int run_profile(const void* q, const void* k, const void* v, const int64_
     // bf16: the second form.  fp16: the first form — the second one exponentiates the masked rows against the golden rows' maximum, and an fp16
     // probability only reaches 39 binades (27 in logit) below it: a sampled row whose best in-mask key sits further down would lose its row sum
     // (NaN for the whole head, where the reference is finite).  bf16 probabilities reach 186 binades (129 in logit); the first form keeps a
-    // running maximum per output.  -DSVG_PROF_FIRST_FORM: the first form for both (A/B builds).
-#ifdef SVG_PROF_FIRST_FORM
-    constexpr bool kSecondForm = false;
-#else
+    // running maximum per output.
     constexpr bool kSecondForm = std::is_same_v<T, __bf16>;
-#endif
     if (!kSecondForm && !p.lay.rows_contiguous(D)) return SVG_ERR_UNSUPPORTED;   // row strides: the second form only (svg_attn_layout_t)
     if constexpr (kSecondForm) {   // one score tile for the three outputs, two workgroups per CU
         constexpr int lds16 = p16_lds_bytes(D);

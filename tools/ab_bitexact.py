@@ -134,7 +134,8 @@ def main():
 
     if "--kmeans" in sys.argv:
         # flash-kmeans loop at the Wan 720p geometry (8 of the 40 heads): labels, counts and centroids of two builds must be identical
-        # (e.g. B = `SVG_EXTRA_HIPCC_FLAGS=-DSVG_KMEANS_V2=1 python sparse-videogen_amd/build.py --tag km2` -> lib/libsvgattn_km2.so)
+        # (e.g. B = the library of another checkout, or `SVG_EXTRA_HIPCC_FLAGS=-DSVG_KMEANS_TRACE python sparse-videogen_amd/build.py --tag kmtrace`
+        #  -> lib/libsvgattn_kmtrace.so; the kernels take no other -D switches)
         from tests.test_gpu_fullsize_svg2 import clustered
 
         gen = torch.Generator(device="cuda").manual_seed(3)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # same-box A/B of the default band schedule at HunyuanVideo 720p (kernel ms, HIP events; pre-scaled q as bench.py runs it):
-# libsvgattn.so vs comparison builds lib/libsvgattn_<tag>.so given as arguments (python sparse-videogen_amd/build.py --tag <tag> with
-# SVG_EXTRA_HIPCC_FLAGS="-DSVG_PP2_...")
+# libsvgattn.so vs comparison builds lib/libsvgattn_<tag>.so given as arguments (python sparse-videogen_amd/build.py --tag <tag> on a
+# source tree that carries the change under test; the kernels have no -DSVG_PP2_... switches any more)
 for i in 1 2 3; do
   for t in cur "$@"; do
     [ "$t" = "cur" ] && f=libsvgattn.so || f=libsvgattn_$t.so
