@@ -589,6 +589,29 @@ int svg_band_attention_prescaled_notify_seg(const void* q_scaled, const void* k,
                                             int32_t D, int32_t dtype, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
                                             int32_t* done, int32_t done_words, int32_t nseg, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Work order of the band kernels at head_dim 128 (default schedule; csrc/band_policy.h, BandQueue).
+ * With more q-tiles (over all heads) than compute units, svg_band_attention, _strided and _prescaled launch one resident workgroup
+ * per compute unit, and the workgroups take (head, q-tile) pairs from a queue: text-row q-tiles first, then the full-length band q-tiles, the shortened band-edge q-tiles
+ * last and longest first; every XCD works through a list of its own (32 neighbouring q-tiles at a time) and, when that is dry,
+ * through the others'; the shortest q-tiles of all heads, one per compute unit, form a tail that is handed out chip-wide one at a
+ * time, longest first.  The counters of the queue live in a pool the LIBRARY owns — no workspace argument: one block per (device,
+ * stream), allocated (hipMalloc, once per device, synchronising) at the first such call on a device and never freed; a launch
+ * leaves its block zeroed, so back-to-back calls need nothing from the host.  A stream that is being captured into a graph, the
+ * 65th stream of a device, and every call that counts completions (svg_band_attention_notify*: consumers rely on heads finishing
+ * in order) or switches masks on the device (svg_band_attention_switch*) run the static mapping — one workgroup per q-tile, head
+ * after head.  Outputs are bit-identical either way.  (A stream destroyed while its last band launch is still running must not
+ * have its handle reused for another band launch before that one has finished: the two would share a block.)
+ *
+ * svg_band_queue_order: the lists, on the host (no GPU needed).  out == NULL: returns the number of work items (BH * q-tiles per
+ * head).  Otherwise writes, list after list (XCD 0 .. 7, then the tail as list 8) and in the order a list hands them out, one triple per work item
+ * { list, head * tiles_per_head + q-tile (row order), key tiles of the q-tile } and returns the number of triples; -1: bad
+ * arguments or out_words < 3 * work items.
+ * svg_debug_band_queue_cap: at most max_workgroups resident workgroups per queue launch from now on, and the queue also for
+ * launches of fewer q-tiles than compute units (0: no cap) — tests of the queue's independence of how many workgroups are resident. */
+int32_t svg_band_queue_order(int32_t BH, int32_t S, const svg_band_mask_t* mask, int32_t* out, int32_t out_words);
+int svg_debug_band_queue_cap(int32_t max_workgroups);
+
 /* Diagnostics (not part of the reference's interface; -DSVG_ABLATIONS builds, otherwise SVG_ERR_UNSUPPORTED): cycle trace of
  * the two-phase attention schedule.  After a svg_band_attention call with variant 64 (bf16, D = 128) and a synchronised
  * stream, copies 104 counters to the host: out[8 * wave + i] = s_memtime ticks wave `wave` of one workgroup spent in

@@ -2,6 +2,8 @@
 // The MFMA / LDS / online-softmax machinery is attn_core.h; this file supplies the two scheduling policies
 // (which KV tiles a workgroup visits, where rows live in HBM, which elements are masked) and the C ABI.
 #include <algorithm>
+#include <atomic>
+#include <mutex>
 
 #include "attn_core.h"
 #include "attn_f8.h"
@@ -74,6 +76,36 @@ __global__ __launch_bounds__(512, 2) void band_attn_m16q_kernel(typename BandPol
     extern __shared__ __attribute__((aligned(16))) char smem[];
     attn_body_m16<T, BandPolicy<T, 128, 8>, false, 1, true>(prm, smem, nullptr);
 }
+// The same two kernels as resident workgroups on a work queue (BandQueue, band_policy.h): min(work items, CUs) workgroups, each
+// running one q-tile after another until the queue is dry.  What band_dispatch launches for head_dim 128 when there are more q-tiles
+// than compute units, unless the call counts completions (those rely on the head-major order of the static mapping) or no counter
+// block is to be had; the device-switched kernel below keeps the static mapping.  Per row the same keys in the same order with the same arithmetic: bit-identical output.
+template <typename T, bool PRE = false>
+__global__ __launch_bounds__(512, 2) void band_attn_m16_queue_kernel(typename BandPolicy<T, 128, 8>::Params prm, BandQueue qd) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    using Pol = BandPolicy<T, 128, 8>;
+    int* const slot = (int*)(smem + attn_m16_lds_bytes());   // (head, q-tile) of the next work item, from lane 0 to the workgroup
+    int dry = 0;
+    for (;;) {
+        if (threadIdx.x == 0) {
+            const int xcd = __builtin_amdgcn_s_getreg((31 << 11) | 20) & (kNumXCD - 1);   // HW_REG_XCC_ID
+            int head = -1, qt = 0;
+            const int w = qd.take(xcd, dry);
+            if (w >= 0) qd.decode(w, head, qt);
+            slot[0] = head, slot[1] = qt;
+        }
+        // Every wave is through the LDS reads of its last epilogue before any wave requests K / V of the next q-tile; and the slot
+        // is not rewritten before every wave has read it: lane 0 comes back here through the barriers of a q-tile (two at least).
+        __syncthreads();
+        const int head = __builtin_amdgcn_readfirstlane(slot[0]), qt = __builtin_amdgcn_readfirstlane(slot[1]);
+        if (head < 0) break;
+        typename Pol::Ctx ctx;
+        Pol::init_tile(prm, ctx, head, qt);
+        attn_m16_tile<T, Pol, false, 1, PRE>(prm, ctx, smem);
+    }
+    if (threadIdx.x == 0) qd.leave(gridDim.x);
+}
+constexpr int kQueueLds = 16;   // bytes of the slot behind the stages
 // device-side switch between two masks on the 16x16x32 body (svg_band_attention_switch[_prescaled] at head_dim 128): `flag[0] != 0` selects prm_alt
 template <typename T, bool PRE = false>
 __global__ __launch_bounds__(512, 2) void band_attn_m16_switch_kernel(typename BandPolicy<T, 128, 8>::Params prm,
@@ -827,6 +859,61 @@ __global__ __launch_bounds__(64) void wait_counters_deadline_kernel(const int32_
 
 static bool g_trace_is_w4 = false;   // diagnostics only: which translation unit holds the last cycle trace
 
+// ---- counter blocks of the queue launches (band_queue_block, band_policy.h) ----
+namespace {
+constexpr int kQueueBlocks = 64;    // streams per device that can hold a block
+constexpr int kQueueDevices = 16;
+struct QueuePool {
+    int device = -1, n_cu = 0, n_used = 0;
+    int32_t* base = nullptr;        // kQueueBlocks * kQueueWords zeroed words, never freed (the process ends with them)
+    hipStream_t owner[kQueueBlocks];
+};
+std::mutex g_queue_mu;
+QueuePool g_queue_pool[kQueueDevices];
+int g_queue_pools = 0;
+std::atomic<int> g_queue_cap{0};
+}  // namespace
+
+int32_t* svg::band_queue_block(hipStream_t st, int& n_cu) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+    std::lock_guard<std::mutex> lock(g_queue_mu);
+    QueuePool* pool = nullptr;
+    for (int i = 0; i < g_queue_pools; ++i)
+        if (g_queue_pool[i].device == dev) pool = &g_queue_pool[i];
+    if (!pool) {
+        if (g_queue_pools == kQueueDevices) return nullptr;
+        int n = 0;
+        void* mem = nullptr;
+        const size_t bytes = (size_t)kQueueBlocks * kQueueWords * sizeof(int32_t);
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0 ||
+            hipMalloc(&mem, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return nullptr;
+        }
+        if (hipMemset(mem, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(mem);
+            return nullptr;
+        }
+        pool = &g_queue_pool[g_queue_pools++];
+        pool->device = dev, pool->n_cu = n, pool->base = (int32_t*)mem;
+    }
+    n_cu = pool->n_cu;
+    for (int i = 0; i < pool->n_used; ++i)
+        if (pool->owner[i] == st) return pool->base + (size_t)i * kQueueWords;
+    if (pool->n_used == kQueueBlocks) return nullptr;
+    pool->owner[pool->n_used] = st;
+    return pool->base + (size_t)(pool->n_used++) * kQueueWords;
+}
+
+int svg::band_queue_cap() { return g_queue_cap.load(std::memory_order_relaxed); }
+
 // pointers, mask, head permutation and sizes: the checks every svg_band_attention* entry shares
 static int band_check_args(const void* q, const void* k, const void* v, const void* o, int32_t BH, int32_t S, int32_t D,
                            const svg_band_mask_t* mask, const svg_perm_desc_t* perm) {
@@ -872,6 +959,24 @@ static int band_dispatch(const void* q, const void* k, const void* v, void* o, i
         auto launch = [&](auto kern, int lds) {   // 8 waves over the q-tiles of every head
             const typename Pol::Params p = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
             return launch_attn(kern, p, dim3(p.nqt * BH), 512, lds, st);
+        };
+        // the 16x16x32 kernels: resident workgroups on a work queue (band_attn_m16_queue_kernel), or `kern` on the static mapping
+        // where the call counts completions or no counter block is to be had
+        auto launch_queue = [&](auto kern_q, auto kern, int lds) {
+            const typename Pol::Params p = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
+            int n_cu = 0;
+            int32_t* const block = opts.done ? nullptr : band_queue_block(st, n_cu);
+            const int cap = band_queue_cap();
+            // (a launch of one round has nothing to balance, and a workgroup pays nine atomics to find the queue dry: 0.068 against
+            //  0.064 ms on the 52 q-tiles of the benchmark's tiny workload)
+            if (!block || (p.nqt * BH <= n_cu && cap == 0)) return launch_attn(kern, p, dim3(p.nqt * BH), 512, lds, st);
+            BandQueue qd = make_band_queue<Pol>(p);
+            qd.ctr = block;
+            int n_wg = std::min(qd.n_items, n_cu);
+            if (cap > 0) n_wg = std::min(n_wg, cap);
+            if (const int r2 = configure_lds((const void*)kern_q, lds + kQueueLds); r2 != SVG_OK) return r2;
+            hipLaunchKernelGGL(kern_q, dim3(n_wg), dim3(512), lds + kQueueLds, st, p, qd);
+            return launch_status();
         };
         // a device-switch kernel: the parameters of both masks (the alternate one without the head permutation) and the flag, over
         // the q-tiles of the larger of the two
@@ -920,7 +1025,8 @@ static int band_dispatch(const void* q, const void* k, const void* v, void* o, i
                     if (opts.use_alt)
                         return launch_switch(opts.prescaled ? band_attn_m16_switch_kernel<T, true> : band_attn_m16_switch_kernel<T>,
                                              attn_m16_lds_bytes());
-                    return launch(opts.prescaled ? band_attn_m16q_kernel<T> : band_attn_m16_kernel<T>, attn_m16_lds_bytes());
+                    if (opts.prescaled) return launch_queue(band_attn_m16_queue_kernel<T, true>, band_attn_m16q_kernel<T>, attn_m16_lds_bytes());
+                    return launch_queue(band_attn_m16_queue_kernel<T>, band_attn_m16_kernel<T>, attn_m16_lds_bytes());
                 }
                 return SVG_ERR_UNSUPPORTED;
         }
@@ -1053,6 +1159,34 @@ extern "C" int svg_band_attention_switch_prescaled(const void* q_scaled, const v
     BandOpts opts = switch_opts(alt_mask, use_alt_flag);
     opts.prescaled = true;
     return band_dispatch(q_scaled, k, v, o, BH, S, D, dtype, 1.f, mask, perm, kBandAuto, opts, 0, nullptr, stream);
+}
+
+extern "C" int32_t svg_band_queue_order(int32_t BH, int32_t S, const svg_band_mask_t* mask, int32_t* out, int32_t out_words) {
+    if (!mask || BH <= 0 || S <= 0 || check_band_mask(S, mask, nullptr) != SVG_OK) return -1;
+    using Pol = svg::BandPolicy<__bf16, 128, 8>;
+    const auto p = svg::make_band_params<Pol, __bf16>(nullptr, nullptr, nullptr, nullptr, BH, S, 1.f, mask, nullptr);
+    const BandQueue qd = svg::make_band_queue<Pol>(p);
+    if (!out) return qd.n_items;
+    int n = 0;
+    for (int x = 0; x <= kNumXCD; ++x)   // the eight lists, then the tail
+        for (unsigned i = 0;; ++i) {
+            const int w = x < kNumXCD ? qd.item(x, i) : qd.tail_item(i);
+            if (w < 0) break;
+            if (3 * (n + 1) > out_words) return -1;
+            int head, qt;
+            qd.decode(w, head, qt);
+            Pol::Ctx c;
+            Pol::kv_schedule(p, c, qt);
+            out[3 * n] = x, out[3 * n + 1] = head * p.nqt + qt, out[3 * n + 2] = c.nT;
+            ++n;
+        }
+    return n;
+}
+
+extern "C" int svg_debug_band_queue_cap(int32_t max_workgroups) {
+    if (max_workgroups < 0) return SVG_ERR_BAD_ARG;
+    g_queue_cap.store(max_workgroups, std::memory_order_relaxed);
+    return SVG_OK;
 }
 
 extern "C" int svg_debug_wg_trace(uint64_t* out, int n_workgroups) {

@@ -81,8 +81,12 @@ __device__ __forceinline__ float quad_group_sum(float x) {
 // (Round 4 measured a PRE form with q and k as fp16 carriers and S^T on the f16 MFMA: the plain kernel's distance to the reference's
 //  formulation, but no time — 33.8 ms against 32.8 for the bf16 PRE form, plus 0.58 ms for the conversion pass; profiles/r04l_*,
 //  r04m_f16qk_kernel_trace.txt.  Removed with the template flag that kept it.)
+// attn_m16_tile: one q-tile, described by `ctx` (P::init or, for a workgroup that takes its q-tiles from a queue, P::init_tile).  Every
+// wave of the workgroup passes the same number of workgroup barriers whatever its role (leading, lagging, idle: nT + 2 with one
+// barrier per tile) and leaves with no LDS-DMA request in flight, so a workgroup may run one q-tile after another: it needs one
+// workgroup barrier between two of them (the epilogue of the first reads the stages the second fills).
 template <typename T, typename P, bool TRACE = false, int ONEBAR = -1, bool PRE = false>
-__device__ __forceinline__ void attn_body_m16(const typename P::Params& prm, char* smem, char* policy_lds) {
+__device__ __forceinline__ void attn_m16_tile(const typename P::Params& prm, const typename P::Ctx& ctx, char* smem) {
     using E = Elt<T>;
     using M = Mfma16<T>;
     using V8 = typename E::v8;
@@ -110,9 +114,8 @@ __device__ __forceinline__ void attn_body_m16(const typename P::Params& prm, cha
     constexpr bool MSUM = std::is_same_v<T, __bf16> && !PRE;
     constexpr float kBias = MSUM ? 10.f : 0.f;
 
-    typename P::Ctx ctx;
-    if (!P::init(prm, ctx, policy_lds)) return;
-
+    unsigned long long wg_t0 = 0, wg_t2 = 0;   // launch timeline (diagnostics builds, svg_debug_wg_trace): entry, end of the tile loop
+    if constexpr (TRACE) wg_t0 = __builtin_amdgcn_s_memtime();
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = wave_id();
@@ -516,6 +519,7 @@ __device__ __forceinline__ void attn_body_m16(const typename P::Params& prm, cha
             for (int j = 0; j < 4; ++j) g_pp_trace[wave * 8 + j] = tr_acc[j];
             if (wave == 0) g_pp_trace[64] = (unsigned long long)nT, g_pp_trace[65] = tr_last - tr_first;
         }
+        wg_t2 = __builtin_amdgcn_s_memtime();
     }
 
     // ---------------- epilogue: O^T -> LDS -> whole rows ----------------
@@ -551,6 +555,23 @@ __device__ __forceinline__ void attn_body_m16(const typename P::Params& prm, cha
         if (ephys[i] >= 0) *(u32x2*)((char*)(ob + (size_t)ephys[i] * o_rs) + colb) = val;
     }
     P::notify(prm, ctx);
+    if constexpr (TRACE) {   // the four stamps and the hardware ids of attn_body_pp2's timeline, one record per workgroup (wave 0)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (wave == 0 && lane == 0 && blockIdx.x < (unsigned)kWgTraceMax) {
+            unsigned long long* w = g_wg_trace + (size_t)blockIdx.x * 6;
+            w[0] = wg_t0, w[1] = tr_first, w[2] = wg_t2, w[3] = __builtin_amdgcn_s_memtime();
+            w[4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_REG_HW_ID
+            w[5] = __builtin_amdgcn_s_getreg((31 << 11) | 20);   // HW_REG_XCC_ID
+        }
+    }
+}
+
+// the workgroup's one q-tile is the one its dispatch id maps to (P::init)
+template <typename T, typename P, bool TRACE = false, int ONEBAR = -1, bool PRE = false>
+__device__ __forceinline__ void attn_body_m16(const typename P::Params& prm, char* smem, char* policy_lds) {
+    typename P::Ctx ctx;
+    if (!P::init(prm, ctx, policy_lds)) return;
+    attn_m16_tile<T, P, TRACE, ONEBAR, PRE>(prm, ctx, smem);
 }
 
 }  // namespace svg

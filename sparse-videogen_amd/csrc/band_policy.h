@@ -126,6 +126,33 @@ struct BandPolicy {
             const int r = w2 - c.head * nl;
             qt = r < p.heavy_lo ? r : r + p.n_heavy;
         }
+        init_tile(p, c, c.head, qt);
+        return true;
+    }
+
+    // the rows, the KV schedule and the fast-path interval of q-tile `qt` (row order) of head `head`: everything of Ctx.  Split from
+    // init() for the kernels that take their (head, q-tile) pairs from a work queue (BandQueue below) instead of blockIdx.
+    static __device__ __forceinline__ void init_tile(const Params& p, Ctx& c, int head, int qt) {
+        c.head = head;
+        c.perm = (p.head_flag != nullptr) && (p.head_flag[c.head] != 0);
+        kv_schedule(p, c, qt);
+        const int real = p.real_len;
+        // fast-path classification: inside the band, away from its edges, every (row, key) pair of a wave x tile
+        // rectangle is allowed; those tiles (98-99 % of all) are recognised with two scalar compares.
+        const int w0 = c.q0 + wave_id() * kWR, w1 = min(w0 + kWR, c.q_end);
+        c.fk_lo = 1, c.fk_hi = 0;
+        if (w0 < c.q_end && w1 <= real) {
+            const bool full_rows = w0 >= p.rf_lo && w1 <= p.rf_hi;   // a wave of full (text) rows: every key tile below real_len
+            c.fk_lo = full_rows ? 0 : max(w1 - p.band, 0);
+            c.fk_hi = min(full_rows ? real : w0 + p.band - kBN, min(real, p.S) - kBN);
+        }
+    }
+
+    // rows [q0, q_end) and key-tile segments of q-tile `qt` (row order); the same for every head.  Also evaluated on the host:
+    // make_band_queue sorts the q-tiles of a launch by c.nT.
+    static __host__ __device__ __forceinline__ void kv_schedule(const Params& p, Ctx& c, int qt) {
+        using std::max;
+        using std::min;
         // (explicit selects: a run-time index into the kernel-argument arrays would go through scratch)
         const bool r1 = qt >= p.reg_t0[1], r2 = qt >= p.reg_t0[2], r3 = qt >= p.reg_t0[3];
         const int rlo = r3 ? p.reg_lo[3] : r2 ? p.reg_lo[2] : r1 ? p.reg_lo[1] : p.reg_lo[0];
@@ -134,7 +161,6 @@ struct BandPolicy {
         c.qt = qt;
         c.q0 = rlo + (qt - rt0) * BM;
         c.q_end = min(rhi, c.q0 + BM);
-        c.perm = (p.head_flag != nullptr) && (p.head_flag[c.head] != 0);
 
         // ---- KV schedule: up to three key intervals -> sorted, merged, tile-aligned ranges ----
         // (explicit scalars, no runtime-indexed arrays: keeps everything in SGPRs, no scratch)
@@ -173,16 +199,6 @@ struct BandPolicy {
         c.seg_lo[1] = blo, c.seg_n[1] = bhi - blo;
         c.seg_lo[2] = clo, c.seg_n[2] = chi - clo;
         c.nT = c.seg_n[0] + c.seg_n[1] + c.seg_n[2];
-        // fast-path classification: inside the band, away from its edges, every (row, key) pair of a wave x tile
-        // rectangle is allowed; those tiles (98-99 % of all) are recognised with two scalar compares.
-        const int w0 = c.q0 + wave_id() * kWR, w1 = min(w0 + kWR, c.q_end);
-        c.fk_lo = 1, c.fk_hi = 0;
-        if (w0 < c.q_end && w1 <= real) {
-            const bool full_rows = w0 >= p.rf_lo && w1 <= p.rf_hi;   // a wave of full (text) rows: every key tile below real_len
-            c.fk_lo = full_rows ? 0 : max(w1 - p.band, 0);
-            c.fk_hi = min(full_rows ? real : w0 + p.band - kBN, min(real, p.S) - kBN);
-        }
-        return true;
     }
 
     static __device__ __forceinline__ const T* q_base(const Params& p, const Ctx& c) { return p.q + layout_head_off(p.lay.q_bs, p.lay.q_hs, p.lay.hpb_q, c.head); }
@@ -391,6 +407,155 @@ struct BandPolicy {
         }
     }
 };
+
+// =====================================================================================================
+// Work queue of the resident band kernels (band_attn_m16_queue_kernel in attention.hip): min(work items, CUs) workgroups, each
+// taking (head, q-tile) pairs until the queue is dry, instead of one workgroup per pair bound to an XCD by its dispatch id.
+//
+// Order of the work items (index w):
+//   [0, nh)   the q-tiles of text rows, head-major (they visit every key tile: first, as in BandPolicy::init);
+//   bulk      the full-length band q-tiles, head-major in row order; then the shortened q-tiles — the band-edge tiles at both ends of
+//             a head and the rows behind real_len — by their RANK (0 = next to the full-length ones, growing towards the first / the
+//             last row of the head: the higher the rank, the fewer key tiles) in tiers of 32 ranks: tier t holds, head by head, ranks
+//             32 t .. 32 t + 31 at the front of the head and then the same ranks at its back;
+//   tail      the highest ranks of all heads, about kQueueTail work items (one per CU), strictly rank-major: rank by rank, head by
+//             head, front then back — the shortest q-tiles of the launch, longest first.
+// Who takes what: the bulk is cut into chunks of 32 neighbours; chunk j belongs to the list of XCD j % 8 and text-row item w to list
+// w % 8.  A workgroup reads its XCD from the hardware and takes from that XCD's list (one atomicAdd), so the 32 CUs of an XCD work on
+// neighbouring q-tiles of one head as they did under the static mapping (their KV windows overlap in the XCD's L2).  A workgroup
+// that finds its list dry takes from the next XCD's list, and so on round the chip; when all eight are dry, from the tail, which has
+// one chip-wide counter: the last round of a launch is handed out one q-tile at a time in descending length to whichever CU is
+// free (tools/band_queue_sim.py: makespan over ideal 1.005 / 1.015 / 1.044 for HunyuanVideo 720p, 480p and a 3-head launch, against
+// 1.012 / 1.052 / 1.173 of the static mapping; without the tail the chunk granularity leaves 1.009 / 1.030 / 1.083).  No workgroup
+// ever waits for another one.  An index behind a list's end means dry whatever the counter held, so a counter block with arbitrary
+// contents costs work items, never a hang.  The last workgroup to leave zeroes the block for the next launch.
+// =====================================================================================================
+constexpr int kQueueChunk = 32;
+constexpr int kQueueTail = 256;                               // work items of the tail, rounded up to whole ranks
+constexpr int kQueueStride = 16;                              // int32 words from one counter to the next: a 64-byte line each
+constexpr int kQueueCounters = kNumXCD + 2;                   // the eight list counters, the tail counter, the workgroups that left
+constexpr int kQueueWords = kQueueCounters * kQueueStride;    // a counter block
+
+struct BandQueue {
+    int32_t* ctr;             // device, kQueueWords zeroed words owned by this launch (band_queue_block)
+    int n_items;              // BH * nqt
+    int BH, nh, n_heavy, heavy_lo;
+    int nl;                   // light q-tiles per head (all but the text-row tiles); light index r -> q-tile r (+ n_heavy behind heavy_lo)
+    int e_lo, e_hi;           // shortened light tiles at the front / at the back of a head; [e_lo, nl - e_hi) are the full-length ones
+    int r0;                   // ranks [0, r0) are bulk, ranks from r0 on tail
+    int n_tail;               // work items of the tail: the last n_tail indices
+
+    // light index of the tile of rank `rank` at the front (back = false) or at the back of a head
+    __host__ __device__ int edge_tile(int rank, bool back) const { return back ? nl - e_hi + rank : e_lo - 1 - rank; }
+    // work item w -> (head, q-tile in row order)
+    __host__ __device__ void decode(int w, int& head, int& qt) const {
+        if (w < nh) {
+            head = w / n_heavy;
+            qt = heavy_lo + (w - head * n_heavy);
+            return;
+        }
+        int w2 = w - nh, r = 0;
+        const int nf = nl - e_lo - e_hi;
+        head = 0;
+        if (w >= n_items - n_tail) {
+            w2 = w - (n_items - n_tail);
+            const int m = e_lo < e_hi ? e_lo : e_hi;          // ranks below m exist on both sides of a head
+            const int both = m > r0 ? (m - r0) * 2 * BH : 0;
+            if (w2 < both) {
+                const int rank = r0 + w2 / (2 * BH), j = w2 % (2 * BH);
+                head = j >> 1;
+                r = edge_tile(rank, j & 1);
+            } else {
+                w2 -= both;
+                head = w2 % BH;
+                r = edge_tile((m > r0 ? m : r0) + w2 / BH, e_hi > e_lo);
+            }
+        } else if (w2 < BH * nf) {
+            head = w2 / nf;
+            r = e_lo + (w2 - head * nf);
+        } else {
+            w2 -= BH * nf;
+            const int b_lo = e_lo < r0 ? e_lo : r0, b_hi = e_hi < r0 ? e_hi : r0;   // bulk ranks at the front / at the back
+            for (int t0 = 0; t0 < r0; t0 += kQueueChunk) {   // tier of ranks [t0, t0 + 32)
+                const int cl = b_lo - t0 < 0 ? 0 : (b_lo - t0 > kQueueChunk ? kQueueChunk : b_lo - t0);
+                const int ct = b_hi - t0 < 0 ? 0 : (b_hi - t0 > kQueueChunk ? kQueueChunk : b_hi - t0);
+                const int c = cl + ct;
+                if (w2 < BH * c) {
+                    head = w2 / c;
+                    const int j = w2 - head * c;
+                    r = j < cl ? edge_tile(t0 + j, false) : edge_tile(t0 + j - cl, true);
+                    break;
+                }
+                w2 -= BH * c;
+            }
+        }
+        qt = r < heavy_lo ? r : r + n_heavy;
+    }
+    // entry i of XCD xcd's list, or -1 behind its end
+    __host__ __device__ int item(int xcd, unsigned i) const {
+        if (i >= (unsigned)n_items) return -1;
+        const int nhx = nh > xcd ? (nh - xcd + kNumXCD - 1) / kNumXCD : 0;
+        if ((int)i < nhx) return xcd + kNumXCD * (int)i;
+        const int i2 = (int)i - nhx;
+        const int w = nh + ((i2 / kQueueChunk) * kNumXCD + xcd) * kQueueChunk + i2 % kQueueChunk;
+        return w < n_items - n_tail ? w : -1;
+    }
+    // entry i of the tail, or -1 behind its end
+    __host__ __device__ int tail_item(unsigned i) const { return i < (unsigned)n_tail ? n_items - n_tail + (int)i : -1; }
+    // One lane of a workgroup: the next work item for a workgroup on XCD `xcd`, -1 when the queue is dry.  `k` (0 at entry of the
+    // kernel) counts the lists this workgroup has found dry: a dry list stays dry.
+    __device__ int take(int xcd, int& k) const {
+        for (; k < kNumXCD; ++k) {
+            const int x = (xcd + k) & (kNumXCD - 1);
+            const int w = item(x, (unsigned)atomicAdd(ctr + x * kQueueStride, 1));
+            if (w >= 0) return w;
+        }
+        if (k == kNumXCD) {
+            const int w = tail_item((unsigned)atomicAdd(ctr + kNumXCD * kQueueStride, 1));
+            if (w >= 0) return w;
+            ++k;
+        }
+        return -1;
+    }
+    // One lane of a workgroup that takes no more work: the last of `n_wg` to leave hands the block back zeroed.
+    __device__ void leave(int n_wg) const {
+        __threadfence();
+        if (atomicAdd(ctr + (kQueueCounters - 1) * kQueueStride, 1) == n_wg - 1) {
+            for (int x = 0; x < kQueueCounters; ++x) atomicExch(ctr + x * kQueueStride, 0);
+        }
+    }
+};
+
+// the queue of a launch with parameters p (ctr is left null: band_queue_block)
+template <typename Pol>
+inline BandQueue make_band_queue(const typename Pol::Params& p) {
+    BandQueue qd{};
+    qd.n_items = p.BH * p.nqt, qd.BH = p.BH;
+    qd.n_heavy = p.n_heavy, qd.heavy_lo = p.heavy_lo, qd.nh = p.BH * p.n_heavy, qd.nl = p.nqt - p.n_heavy;
+    // the shortened tiles: what lies in front of the first / behind the last light tile with the largest number of key tiles
+    int longest = -1, first = 0, last = -1;
+    for (int r = 0; r < qd.nl; ++r) {
+        typename Pol::Ctx c;
+        Pol::kv_schedule(p, c, r < p.heavy_lo ? r : r + p.n_heavy);
+        if (c.nT > longest) longest = c.nT, first = r;
+        if (c.nT == longest) last = r;
+    }
+    qd.e_lo = first, qd.e_hi = qd.nl - 1 - last;
+    if (qd.nl == 0) qd.e_lo = qd.e_hi = 0;
+    const int ranks = std::max(qd.e_lo, qd.e_hi);
+    qd.r0 = std::max(0, ranks - (kQueueTail + 2 * p.BH - 1) / (2 * p.BH));
+    qd.n_tail = p.BH * (std::max(0, qd.e_lo - qd.r0) + std::max(0, qd.e_hi - qd.r0));
+    return qd;
+}
+
+// A zeroed counter block for a queue launch on `st` of the current device, or nullptr (the caller then launches the statically
+// mapped kernel).  The library owns one pool per device and gives every stream a block of its own: launches on one stream run one
+// after the other and each leaves the block zeroed, launches on different streams never share one.  nullptr: the stream is being
+// captured into a graph (a replay can run beside a launch on the same stream), the pool cannot be allocated, or more streams
+// than the pool has blocks have launched band attention on this device.
+int32_t* band_queue_block(hipStream_t st, int& n_cu);   // n_cu: compute units of the device
+// diagnostics (svg_debug_band_queue_cap): at most this many resident workgroups per queue launch; 0 = as many as the device has CUs
+int band_queue_cap();
 
 // hipFuncAttributeMaxDynamicSharedMemorySize of `kernel` on the CURRENT device raised to at least `lds` bytes.  A cache of the
 // driver call, keyed by (device, kernel) and remembering the largest size configured so far: the variable-block kernels ask for

@@ -101,6 +101,8 @@ SIGNATURES = {
     "svg_build_info": (C.c_char_p, []),
     "svg_debug_pp_trace": (C.c_int, [_VP]),
     "svg_debug_wg_trace": (C.c_int, [_VP, _I32]),
+    "svg_band_queue_order": (_I32, [_I32, _I32, C.POINTER(BandMask), _VP, _I32]),
+    "svg_debug_band_queue_cap": (C.c_int, [_I32]),
     "svg_rms_norm_forward": (C.c_int, [_VP, _VP, C.c_int64, _I32, _I32, C.c_float, _VP]),
     "svg_layer_norm_forward": (C.c_int, [_VP, _VP, _VP, C.c_int64, _I32, _I32, _VP]),
     "svg_apply_qk_rope_inplace_cossin": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP]),

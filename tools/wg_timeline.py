@@ -2,7 +2,9 @@
 """Where a launch of the band-attention kernel spends its time outside the tile loops: per-workgroup s_memtime stamps
 (entry, loop start, loop end, exit) and hardware ids of the traced two-phase kernel (variant 64, diagnostics library: build.py --ablations + SVG_ATTN_LIB), folded into
 per-CU occupancy, prologue / epilogue durations and the gap between consecutive workgroups on the same CU.
-python tools/wg_timeline.py [band] [heads: spatial|temporal|alt] [H]"""
+python tools/wg_timeline.py [--m16] [band] [heads: spatial|temporal|alt] [H] [XCD to list]
+--m16: the traced 16x16x32 body (trace code 9: band_attn_m16_trace_kernel, the default schedule's body on the static one-workgroup-per-
+q-tile mapping, two barriers per tile) instead of the 32x32x16 one."""
 import sys
 from pathlib import Path
 
@@ -13,6 +15,9 @@ sys.path.insert(0, str(ROOT / "sparse-videogen_amd"))
 import torch  # noqa: E402
 from svg import _native as nat  # noqa: E402
 
+M16 = "--m16" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--m16"]
+VARIANT = 64 | (9 << 8) if M16 else 64
 band = int(sys.argv[1]) if len(sys.argv) > 1 else 15616
 heads = sys.argv[2] if len(sys.argv) > 2 else "spatial"
 H = int(sys.argv[3]) if len(sys.argv) > 3 else 24
@@ -26,11 +31,11 @@ pat = {"alt": lambda h: h % 2, "spatial": lambda h: 0, "temporal": lambda h: 1}[
 best = torch.tensor([[pat(h) for h in range(H)]], device=dev, dtype=torch.int64)
 kw = dict(head_perm_flag=best, vid0=0, num_frame=F_, frame_size=P_)
 for _ in range(2):
-    nat.band_attention(q, k, v, mask, variant=64, **kw)
+    nat.band_attention(q, k, v, mask, variant=VARIANT, **kw)
 torch.cuda.synchronize()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record()
-nat.band_attention(q, k, v, mask, variant=64, **kw)
+nat.band_attention(q, k, v, mask, variant=VARIANT, **kw)
 e1.record()
 torch.cuda.synchronize()
 ms = e0.elapsed_time(e1)
@@ -45,7 +50,7 @@ keys = np.unique(cu[ok])
 spans = np.array([t3[ok & (cu == c)].max() - t0[ok & (cu == c)].min() for c in keys], dtype=np.float64)
 span = float(spans.max())
 tick_ns = ms * 1e6 / span
-print(f"band {band} heads {heads}: {ms:.3f} ms, {ok.sum()} / {nwg} workgroups traced, median per-CU span {span:.0f} ticks -> {tick_ns:.3f} ns/tick")
+print(f"{'16x16x32' if M16 else '32x32x16'} body, band {band} heads {heads}: {ms:.3f} ms, {ok.sum()} / {nwg} workgroups traced, median per-CU span {span:.0f} ticks -> {tick_ns:.3f} ns/tick")
 pro, loop, epi = (t1 - t0)[ok], (t2 - t1)[ok], (t3 - t2)[ok]
 for name, a in (("prologue", pro), ("tile loop", loop), ("epilogue", epi)):
     print(f"  {name:9s}: mean {a.mean() * tick_ns / 1e3:8.2f} us  median {np.median(a) * tick_ns / 1e3:8.2f}  p95 {np.percentile(a, 95) * tick_ns / 1e3:8.2f}"
