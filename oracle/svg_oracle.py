@@ -576,7 +576,7 @@ def modulate_gate_residual(residual: torch.Tensor, x: torch.Tensor, gate: torch.
 def varblock_pair_partners(block_map: torch.Tensor, q_sizes: torch.Tensor, k_sizes: torch.Tensor, tile_rows: int = 256,
                            rounds: int = 3, min_common: int = 8) -> torch.Tensor:
     """block_map bool [H, QB, KB], q_sizes [H, QB], k_sizes [H, KB] -> int32 [H, QB]: the partner array of
-    csrc/attention.hip varblock_pair_score_kernel / varblock_pair_match_kernel.  Per head and round every block-row with an unmatched
+    csrc/attention_varblock.hip varblock_pair_score_kernel / varblock_pair_match_kernel.  Per head and round every block-row with an unmatched
     ragged last tile (q_size % tile_rows > 0) chooses, among the other unmatched ones whose remainder fits beside its own, the one
     with the most active non-empty key blocks in common (at least `min_common`; ties: the lowest index); mutual choices become pairs
     (partner[i] = j for the lower index i, -2 for j); -1: alone."""

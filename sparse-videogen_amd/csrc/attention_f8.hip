@@ -186,8 +186,8 @@ size_t f8g_ws_bytes(int Hq, int Hkv, int Sq, int Skv) {
     return (size_t)Hq * Sq * 128 + 2 * (size_t)Hkv * Skv * 128 + (size_t)(Hq + 2 * Hkv) * (sizeof(unsigned) + sizeof(float)) + 512;
 }
 
-// quantise q [Hq, Sq, 128], k, v [Hkv, Skv, 128] into `ws` and fill `fa` (declared in band_policy.h; the kernel that consumes it
-// lives in attention.hip next to the variable-block policy)
+// quantise q [Hq, Sq, 128], k, v [Hkv, Skv, 128] into `ws` and fill `fa` (declared in attn_f8.h; the kernel that consumes it
+// lives in attention_varblock.hip)
 template <typename T>
 static int f8g_quantize_t(const void* q, const void* k, const void* v, int Hq, int Hkv, int Sq, int Skv, float sm_scale, void* ws,
                           F8GArgs* fa, hipStream_t st) {
@@ -249,11 +249,7 @@ static int run_f8(const void* q, const void* k, const void* v, void* o, int BH, 
     if (!(what & 2)) return launch_status();
     const typename Pol::Params p = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
     F8Args fa{q8, k8, vt8, scales, S_pad};
-    auto kern = band_attn_f8_kernel<T>;
-    if (const int rc = configure_lds((const void*)kern, attn_f8_lds_bytes<D, 8, 4>()); rc != SVG_OK) return rc;
-    constexpr int kLds = attn_f8_lds_bytes<D, 8, 4>();
-    hipLaunchKernelGGL(kern, dim3(p.nqt * BH), dim3(512), kLds, st, p, fa);
-    return launch_status();
+    return launch_attn(band_attn_f8_kernel<T>, dim3(p.nqt * BH), 512, attn_f8_lds_bytes<D, 8, 4>(), st, p, fa);
 }
 
 }  // namespace svg

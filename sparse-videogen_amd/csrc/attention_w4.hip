@@ -1,6 +1,6 @@
 // SVG1 band attention / dense attention on the one-wave-per-SIMD body (attn_w4.h): kernels and launchers.
 // A translation unit of its own: the body is large (two unrolled tile iterations x three instantiations) and compiles in
-// parallel with attention.hip.
+// parallel with attention.hip (the other band kernels) and attention_varblock.hip.
 #include "attn_w4.h"
 #include "band_policy.h"
 
@@ -32,7 +32,8 @@ static int run_w4(const void* q, const void* k, const void* v, void* o, int BH, 
     if (opts.trace) {
 #ifdef SVG_ABLATIONS
         if constexpr (D == 128 && std::is_same<T, __bf16>::value) {
-#define SVG_W4_TRACE(A) case A: return launch_attn(band_attn_w4_trace_kernel<T, D, A>, p, dim3(p.nqt * BH), 256, attn_w4_lds_bytes<D>(), st);
+            g_trace_reader = read_trace_here;
+#define SVG_W4_TRACE(A) case A: return launch_attn(band_attn_w4_trace_kernel<T, D, A>, dim3(p.nqt * BH), 256, attn_w4_lds_bytes<D>(), st, p);
             switch (opts.trace_abl) {
                 SVG_W4_TRACE(0) SVG_W4_TRACE(1) SVG_W4_TRACE(2) SVG_W4_TRACE(3) SVG_W4_TRACE(4) SVG_W4_TRACE(5) SVG_W4_TRACE(6)
                 default: return SVG_ERR_UNSUPPORTED;
@@ -42,7 +43,7 @@ static int run_w4(const void* q, const void* k, const void* v, void* o, int BH, 
 #endif
         return SVG_ERR_UNSUPPORTED;   // diagnostics builds only (-DSVG_ABLATIONS), bf16 / D = 128
     }
-    return launch_attn(band_attn_w4_kernel<T, D>, p, dim3(p.nqt * BH), 256, attn_w4_lds_bytes<D>(), st);
+    return launch_attn(band_attn_w4_kernel<T, D>, dim3(p.nqt * BH), 256, attn_w4_lds_bytes<D>(), st, p);
 }
 
 int run_band_w4(const void* q, const void* k, const void* v, void* o, int BH, int S, int D, int dtype, float sm_scale,
@@ -50,20 +51,6 @@ int run_band_w4(const void* q, const void* k, const void* v, void* o, int BH, in
     return dispatch_td(dtype, D, [&](auto t, auto d) {
         return run_w4<decltype(t), decltype(d)::value>(q, k, v, o, BH, S, sm_scale, mask, perm, opts, st);
     });
-}
-
-int w4_read_trace(uint64_t* out104) {
-#ifdef SVG_ABLATIONS
-    hipError_t e = hipMemcpyFromSymbol(out104, HIP_SYMBOL(g_pp_trace), 104 * sizeof(uint64_t));
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return SVG_ERR_LAUNCH;
-    }
-    return SVG_OK;
-#else
-    (void)out104;
-    return SVG_ERR_UNSUPPORTED;
-#endif
 }
 
 }  // namespace svg

@@ -427,13 +427,29 @@ __device__ __forceinline__ void lds_dma16(unsigned lds, unsigned voff, const voi
 
 
 // cycle trace of the two-phase body (diagnostics, -DSVG_ABLATIONS builds): per wave sums of s_memtime ticks per phase of
-// workgroup blockIdx.x == kPpTraceBlock (static: one copy per translation unit, read with hipMemcpyFromSymbol in attention.hip)
+// workgroup blockIdx.x == kPpTraceBlock (static: one copy per translation unit, see g_trace_reader below)
 static __device__ unsigned long long g_pp_trace[8 * 8 + 8 + 8 * 4];
 constexpr int kPpTraceBlock = 1000;
 // Launch timeline of the traced two-phase kernel: per workgroup [s_memtime at entry, at loop start, at loop end, at exit, HW_ID, XCC_ID]
 // (wave 0), read with svg_debug_wg_trace; tools/wg_timeline.py turns it into per-CU occupancy and launch gaps.
 constexpr int kWgTraceMax = 16384;
 static __device__ unsigned long long g_wg_trace[kWgTraceMax * 6];
+// Both traces exist once per translation unit.  A traced launch names its unit by storing the unit's own read_trace_here (static:
+// one per unit, reading that unit's copies) in g_trace_reader (attention.hip); svg_debug_wg_trace / svg_debug_pp_trace call it.
+// wg: n_workgroups rows of g_wg_trace into `out`; otherwise the 104 words of g_pp_trace.
+extern int (*g_trace_reader)(uint64_t* out, bool wg, int n_workgroups);
+static inline int read_trace_here(uint64_t* out, bool wg, int n_workgroups) {
+#ifdef SVG_ABLATIONS
+    if (!out || n_workgroups < 0 || n_workgroups > kWgTraceMax) return SVG_ERR_BAD_ARG;
+    const hipError_t e = wg ? hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wg_trace), (size_t)n_workgroups * 6 * sizeof(uint64_t))
+                            : hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pp_trace), 104 * sizeof(uint64_t));
+    if (e == hipSuccess) return SVG_OK;
+    g_last_hip_error = (int)e;
+    return SVG_ERR_LAUNCH;
+#else
+    return SVG_ERR_UNSUPPORTED;   // diagnostics builds only (-DSVG_ABLATIONS)
+#endif
+}
 
 
 // =====================================================================================================================

@@ -393,6 +393,10 @@ struct F8GArgs {
     const float* q_inv;    // [Hq]   E8M0 scale word of the q head, (127 + e) * 0x01010101, as float bits (q carries the softmax scale)
     const float* kv_inv;   // [Hkv, 2]: amax / 448 of k, v
 };
+// its quantiser (attention_f8.hip; the kernel is attention_varblock.hip's): bytes of `ws`, and q, k, v -> `ws` and `fa`
+size_t f8g_ws_bytes(int Hq, int Hkv, int Sq, int Skv);
+int f8g_quantize(const void* q, const void* k, const void* v, int Hq, int Hkv, int Sq, int Skv, int dtype, float sm_scale, void* ws,
+                 F8GArgs* fa, hipStream_t st);
 
 // chunk c (16 B) of V row `row` inside the row-major V image ([64][128] bytes): the XOR keeps the transpose reads conflict-free
 __device__ __forceinline__ int f8_vrow_off(int row, int c) { return row * 128 + ((c ^ ((row & 2) | ((row >> 1) & 4))) << 4); }

@@ -1,6 +1,7 @@
 // SVG1 band policy (analytic mask family, see svg_band_mask_t in svg_attn.h) for the attention bodies of attn_core.h / attn_w4.h:
-// which KV tiles a workgroup visits, where rows live in HBM, which elements are masked — plus the host-side parameter builder and
-// the launch helper shared by the translation units that instantiate band kernels (attention.hip, attention_w4.hip).
+// which KV tiles a workgroup visits, where rows live in HBM, which elements are masked — plus the work queue of the resident
+// kernels and the host-side parameter builder, for the translation units that instantiate band kernels (attention.hip,
+// attention_w4.hip, attention_f8.hip).  The launch helpers are svg_common.h; the variable-block policy is varblock_policy.h.
 #pragma once
 #include <algorithm>
 
@@ -557,40 +558,6 @@ int32_t* band_queue_block(hipStream_t st, int& n_cu);   // n_cu: compute units o
 // diagnostics (svg_debug_band_queue_cap): at most this many resident workgroups per queue launch; 0 = as many as the device has CUs
 int band_queue_cap();
 
-// hipFuncAttributeMaxDynamicSharedMemorySize of `kernel` on the CURRENT device raised to at least `lds` bytes.  A cache of the
-// driver call, keyed by (device, kernel) and remembering the largest size configured so far: the variable-block kernels ask for
-// more LDS when KB grows, and a second GPU driven from the same thread needs its own attribute.
-inline int configure_lds(const void* kernel, int lds) {
-    struct Entry {
-        const void* kernel;
-        int device, lds;
-    };
-    static thread_local Entry table[64];
-    static thread_local int n = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    Entry* e = nullptr;
-    for (int i = 0; i < n; ++i)
-        if (table[i].kernel == kernel && table[i].device == dev) e = &table[i];
-    if (e && e->lds >= lds) return SVG_OK;
-    const hipError_t err = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (err != hipSuccess) {
-        g_last_hip_error = (int)err;
-        return SVG_ERR_LAUNCH;
-    }
-    if (e) e->lds = lds;
-    else if (n < 64) table[n++] = Entry{kernel, dev, lds};   // (a full table only costs the driver call again)
-    return SVG_OK;
-}
-
-template <typename K, typename Prm>
-inline int launch_attn(K kernel, const Prm& prm, dim3 grid, int threads, int lds, hipStream_t st) {
-    const int rc = configure_lds((const void*)kernel, lds);
-    if (rc != SVG_OK) return rc;
-    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, st, prm);
-    return launch_status();
-}
-
 template <typename Pol, typename T>
 inline typename Pol::Params make_band_params(const void* q, const void* k, const void* v, void* o, int BH, int S, float sm_scale,
                                              const svg_band_mask_t* mask, const svg_perm_desc_t* perm, const BandOpts& opts = BandOpts()) {
@@ -641,16 +608,9 @@ inline typename Pol::Params make_band_params(const void* q, const void* k, const
     return p;
 }
 
-// fp8 gathering body (attn_f8.h): quantiser in attention_f8.hip, kernel next to the variable-block policy in attention.hip
-struct F8GArgs;
-size_t f8g_ws_bytes(int Hq, int Hkv, int Sq, int Skv);
-int f8g_quantize(const void* q, const void* k, const void* v, int Hq, int Hkv, int Sq, int Skv, int dtype, float sm_scale, void* ws,
-                 F8GArgs* fa, hipStream_t st);
-
 // 4 waves x 64 rows, one wave per SIMD (attn_body_w4, attention_w4.hip)
 int run_band_w4(const void* q, const void* k, const void* v, void* o, int BH, int S, int D, int dtype, float sm_scale,
                 const svg_band_mask_t* mask, const svg_perm_desc_t* perm, const BandOpts& opts, hipStream_t st);
-int w4_read_trace(uint64_t* out104);   // per-phase cycle trace of the last traced w4 launch (diagnostics builds)
 // waves that report per 256-row q-tile of the kernel `variant` selects (completion-counter targets); -1: no counters
 int band_waves_per_tile(int variant);
 

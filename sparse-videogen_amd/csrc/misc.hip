@@ -3,6 +3,8 @@
 
 namespace svg {
 
+thread_local int g_last_hip_error = 0;
+
 // ref: density_calculation, svg/kmeans_utils.py:13-31.  One workgroup per head.
 __global__ __launch_bounds__(256) void map_density_kernel(const uint8_t* __restrict__ map, const int32_t* __restrict__ q_sizes,
                                                           const int32_t* __restrict__ k_sizes, float* __restrict__ out, int QB,

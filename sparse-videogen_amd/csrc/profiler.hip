@@ -799,20 +799,12 @@ static int run_profile(const void* q, const void* k, const void* v, const int64_
     if constexpr (kSecondForm) {   // one score tile for the three outputs, two workgroups per CU
         constexpr int lds16 = p16_lds_bytes(D);
         auto kern16 = profile16_kernel<T, D>;
-        hipError_t e16 = hipFuncSetAttribute((const void*)kern16, hipFuncAttributeMaxDynamicSharedMemorySize, lds16);
-        if (e16 != hipSuccess) {
-            g_last_hip_error = (int)e16;
-            return SVG_ERR_LAUNCH;
-        }
+        if (const int rc = configure_lds((const void*)kern16, lds16); rc != SVG_OK) return rc;
         hipLaunchKernelGGL(kern16, dim3(BH, p.n_chunks), dim3(256), lds16, st, p);
     } else {   // three roles x two waves of the lock-step body, each role its own scores and running maximum
         const int lds = attn_lds_bytes<D, kProfNW>();
         auto kern = profile_attn_kernel<T, D>;
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) {
-            g_last_hip_error = (int)e;
-            return SVG_ERR_LAUNCH;
-        }
+        if (const int rc = configure_lds((const void*)kern, lds); rc != SVG_OK) return rc;
         hipLaunchKernelGGL(kern, dim3(BH, p.n_chunks), dim3(kProfNW * 64), lds, st, p);
     }
     float* sq_part = (float*)ws + (size_t)3 * BH * p.n_chunks * kProfMaxRows * (D + 4);

@@ -20,7 +20,7 @@ using i16x8 = short __attribute__((ext_vector_type(8)));
 using u32x4 = unsigned __attribute__((ext_vector_type(4)));
 using u32x2 = unsigned __attribute__((ext_vector_type(2)));
 
-extern thread_local int g_last_hip_error;
+extern thread_local int g_last_hip_error;   // misc.hip (svg_last_hip_error)
 
 inline int launch_status() {
     hipError_t e = hipGetLastError();
@@ -29,6 +29,41 @@ inline int launch_status() {
         return SVG_ERR_LAUNCH;
     }
     return SVG_OK;
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize of `kernel` on the CURRENT device raised to at least `lds` bytes.  A cache of the
+// driver call, keyed by (device, kernel) and remembering the largest size configured so far: the variable-block kernels ask for
+// more LDS when KB grows, and a second GPU driven from the same thread needs its own attribute.
+inline int configure_lds(const void* kernel, int lds) {
+    struct Entry {
+        const void* kernel;
+        int device, lds;
+    };
+    static thread_local Entry table[64];
+    static thread_local int n = 0;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    Entry* e = nullptr;
+    for (int i = 0; i < n; ++i)
+        if (table[i].kernel == kernel && table[i].device == dev) e = &table[i];
+    if (e && e->lds >= lds) return SVG_OK;
+    const hipError_t err = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (err != hipSuccess) {
+        g_last_hip_error = (int)err;
+        return SVG_ERR_LAUNCH;
+    }
+    if (e) e->lds = lds;
+    else if (n < 64) table[n++] = Entry{kernel, dev, lds};   // (a full table only costs the driver call again)
+    return SVG_OK;
+}
+
+// one attention launch: `lds` bytes of dynamic LDS made available (configure_lds), the launch, its status
+template <typename K, typename... Args>
+inline int launch_attn(K kernel, dim3 grid, int threads, int lds, hipStream_t st, const Args&... args) {
+    const int rc = configure_lds((const void*)kernel, lds);
+    if (rc != SVG_OK) return rc;
+    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, st, args...);
+    return launch_status();
 }
 
 // Element-type traits: storage vectors + the MFMA builtin for that type.

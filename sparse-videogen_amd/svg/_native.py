@@ -685,7 +685,7 @@ def varblock_workspace(Hq: int, Hkv: int, QB: int, KB: int, Sq: int, device) -> 
 def varblock_launch_order(workspace: torch.Tensor, Hkv: int, QB: int, KB: int):
     """The launch order a 256-row variable-block call (variants 3 / 6 / 7) left in its workspace: int32 [n, 3] rows of
     (q head, block-row << 16 | sub-tile, partner) in dispatch order — partner >= 0: the tile also carries the ragged last tile of
-    that block-row (remainder packing) — (layout: csrc/attention.hip VbWs: plan prefix sums, two buckets + the partner per
+    that block-row (remainder packing) — (layout: csrc/attention_varblock.hip vb_ws: plan prefix sums, two buckets + the partner per
     block-row, histogram, then [count, pad, entries])."""
     w = workspace.view(torch.int32)
     off = Hkv * (3 * (QB + 1) + (KB + 1)) + 3 * Hkv * QB + Hkv * 64
@@ -695,7 +695,7 @@ def varblock_launch_order(workspace: torch.Tensor, Hkv: int, QB: int, KB: int):
 
 def varblock_partners(workspace: torch.Tensor, Hkv: int, QB: int, KB: int) -> torch.Tensor:
     """The remainder-packing partners a variant-3 call left in its workspace: int32 [Hkv, QB]; j >= 0: block-row i's ragged last tile
-    also carries block-row j's, -2: carried by its partner, -1: alone (csrc/attention.hip varblock_pair_*_kernel)."""
+    also carries block-row j's, -2: carried by its partner, -1: alone (csrc/attention_varblock.hip varblock_pair_*_kernel)."""
     w = workspace.view(torch.int32)
     off = Hkv * (3 * (QB + 1) + (KB + 1)) + 2 * Hkv * QB
     return w[off: off + Hkv * QB].view(Hkv, QB).clone()

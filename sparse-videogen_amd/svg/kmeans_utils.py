@@ -1,6 +1,6 @@
 """SVG2 operators — same module path and function names as the reference `svg/kmeans_utils.py`, backed by the HIP
 kernels of libsvgattn (flash-kmeans: csrc/kmeans.hip, top-p block selection: csrc/dynmap.hip, variable-block attention:
-csrc/attention.hip).  No Triton, no flashinfer, no cuVS.
+csrc/attention_varblock.hip).  No Triton, no flashinfer, no cuVS.
 
 Differences that are deliberate and documented:
   * batch_kmeans_Euclid(check_every=0) runs without any host synchronisation: the reference's stopping rule

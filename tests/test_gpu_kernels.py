@@ -603,6 +603,32 @@ def test_varblock_fused_permutation(nat):
         check_attn(o[h], ref, torch.bfloat16)
 
 
+def test_debug_wg_trace_follows_the_last_traced_launch(nat):
+    """The launch timeline is kept once per translation unit; svg_debug_wg_trace has to read the copy of the unit that holds the
+    kernel of the LAST traced launch.  A traced band launch of 64 workgroups, then a traced variable-block launch of at most 8: the
+    second read shows at most 8 stamped rows.  (Diagnostics library only: build.py --ablations, selected with SVG_ATTN_LIB.)"""
+    if nat.load().svg_debug_wg_trace(None, 0) == -2:   # SVG_ERR_UNSUPPORTED: the product library has no traced kernels
+        pytest.skip("needs the diagnostics library (build.py --ablations)")
+    torch.manual_seed(11)
+    BH, S, D = 4, 4096, 128
+    q, k, v = (dev(torch.randn(BH, S, D).to(torch.bfloat16)) for _ in range(3))
+    mask = nat.BandMask(real_len=S, band=S + 1, colfull_lo=0, colfull_hi=0, rowfull_lo=0, rowfull_hi=0)
+    n_band = BH * (S // 256)
+    nat.band_attention(q, k, v, mask, variant=64)
+    band = nat.debug_wg_trace(n_band)
+    assert (band[:, 3] > 0).all(), "every workgroup of the traced band launch stamps its exit"
+    Sv, QB, KB = 1024, 4, 8   # one head: at most Sv / 256 + QB = 8 workgroups
+    sizes = lambda n: dev(torch.full((1, n), Sv // n, dtype=torch.int32))
+    nat.varblock_attention(dev(q[:1, :Sv]), dev(k[:1, :Sv]), dev(v[:1, :Sv]), dev(torch.ones(1, QB, KB, dtype=torch.bool)), sizes(QB),
+                           sizes(KB), variant=5)
+    vb = nat.debug_wg_trace(n_band)
+    stamped = vb[:, 3] > 0
+    assert 1 <= int(stamped.sum()) <= Sv // 256 + QB, (int(stamped.sum()), n_band)
+    assert (vb[stamped, 0] != band[stamped, 0]).all()
+    nat.band_attention(q, k, v, mask, variant=64)   # and back: the band unit's copy again
+    assert (nat.debug_wg_trace(n_band)[:, 3] > 0).all()
+
+
 # ---------------------------------------------------------------------------------------------------------
 # online profiler
 # ---------------------------------------------------------------------------------------------------------

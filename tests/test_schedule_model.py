@@ -1,7 +1,7 @@
 """CPU checks of the *scheduling logic* the HIP kernels use (which KV tiles a workgroup visits, how a tile is
 classified, the analytic profiler predicates).  The device code is mirrored line by line in Python here and checked
 exhaustively against the oracle's dense masks on small geometries — this catches logic errors without a GPU.
-Mirrors: BandPolicy::init / classify / allowed (csrc/attention.hip), ProfilePolicy::allowed (csrc/profiler.hip)."""
+Mirrors: BandPolicy::init / classify / allowed (csrc/band_policy.h), VarblockPolicy (csrc/varblock_policy.h), ProfilePolicy::allowed (csrc/profiler.hip)."""
 import math
 
 import pytest
@@ -267,7 +267,7 @@ def test_profile_tile_classes_against_reference_masks(model, ctx, F_, P_, R, see
     assert n_fast > 0
 
 
-# ---- variable-block policy: run list and row cursor (csrc/attention.hip VarblockPolicy::init / kv_phys_at) ----
+# ---- variable-block policy: run list and row cursor (csrc/varblock_policy.h VarblockPolicy::init / kv_phys_at) ----
 def vb_run_list(map_row, k_off):
     """host model of the LDS run list of one block-row: the active non-empty key blocks in ascending order as
     (end in compact coordinates, permuted start - compact start) pairs, two sentinels behind the last run"""
@@ -320,7 +320,7 @@ def test_varblock_run_cursor_model(seed):
 
 
 # ---- remainder packing (round 3): a tile shared by the ragged last tiles of two block-rows (VarblockPolicy::init / classify /
-#      allowed / row_intervals, csrc/attention.hip) ----
+#      allowed / row_intervals, csrc/varblock_policy.h) ----
 def vb_packed_run_list(row_a, row_b, k_off):
     """host model of the three-class run list: key blocks both members attend, then only A's, then only B's (each class in
     ascending block order); returns (runs, kC, kCA, total)"""

@@ -57,14 +57,20 @@ def test_no_mfma_hazards_no_spills(listing, capsys):
         assert " 0 hazards, 0 spill moves" in l, l
 
 
-F8_LISTINGS = [PKG / "build" / f"{stem}-hip-amdgcn-amd-amdhsa-gfx950.s" for stem in ("attention", "attention_f8")]
+def _listing(stem):
+    return PKG / "build" / f"{stem}-hip-amdgcn-amd-amdhsa-gfx950.s"
+
+
+F8_LISTINGS = [_listing("attention_varblock"), _listing("attention_f8")]   # the fp8 bodies: variable-block, band
+BAND_LISTING = _listing("attention")                                       # the pre-scaled-q band bodies
 
 
 @pytest.fixture(scope="module")
 def f8_listings():
-    srcs = [PKG / "csrc" / n for n in ("attention.hip", "attention_f8.hip", "attn_f8.h", "attn_core.h", "band_policy.h")]
+    srcs = [PKG / "csrc" / n for n in ("attention.hip", "attention_varblock.hip", "attention_f8.hip", "attn_f8.h", "attn_m16.h", "attn_core.h",
+                                       "band_policy.h", "varblock_policy.h", "svg_common.h")]
     newest = max(s.stat().st_mtime for s in srcs)
-    if any(not f.exists() or f.stat().st_mtime < newest for f in F8_LISTINGS):
+    if any(not f.exists() or f.stat().st_mtime < newest for f in F8_LISTINGS + [BAND_LISTING]):
         _load(PKG / "build.py", "svg_build").build(force=False, asm=False, verbose=False)
     return F8_LISTINGS
 
@@ -86,7 +92,7 @@ def test_first_step_mfmas_have_no_hazards(f8_listings, capsys):
     may write one of its operands — A, B, C or the block-scale words — within two wait states in front of it, and nothing but the
     next step's MFMA (as C, same tuple) may touch its destination inside the MFMA's latency."""
     audit = _load(ROOT / "tools" / "asm_hazards.py", "asm_hazards")
-    for f in f8_listings:
+    for f in f8_listings + [BAND_LISTING]:
         assert f.exists(), f"build.py keeps the assembly of {f.name}"
     seen = 0
     for f in f8_listings:                                    # {band, varblock} x {bf16, f16}: 2 asm MFMAs each
@@ -97,7 +103,7 @@ def test_first_step_mfmas_have_no_hazards(f8_listings, capsys):
             assert "2 asm MFMAs, 0 hazards" in l, l
     assert seen == 4, seen
     # pre-scaled kernels: band {plain, switch} x dtype x head_dim
-    rc, out, kernels = _audit(audit, capsys, "pp2q", f8_listings[0])
+    rc, out, kernels = _audit(audit, capsys, "pp2q", BAND_LISTING)
     assert rc == 0, out
     assert not any("trace" in l for l in kernels), "the kept listing is the PRODUCT build's (an -DSVG_ABLATIONS build has the trace kernels)"
     assert len(kernels) == 8 and not any("varblock" in l for l in kernels), out
@@ -105,7 +111,7 @@ def test_first_step_mfmas_have_no_hazards(f8_listings, capsys):
         assert (" 8 asm MFMAs, 0 hazards" if "switch" in l else " 4 asm MFMAs, 0 hazards") in l, l
     # the PRE form of the 16x16x32 body (attn_m16.h, Mfma16::mfma_keep_c): 8 first contraction steps per tile x two copies of the loop;
     # the switch kernels hold the body twice
-    rc, out, kernels = _audit(audit, capsys, "band_attn_m16", f8_listings[0])
+    rc, out, kernels = _audit(audit, capsys, "band_attn_m16", BAND_LISTING)
     assert rc == 0, out
     assert kernels and all("0 hazards" in l for l in kernels), out
     assert any(" 16 asm MFMAs" in l for l in kernels) and any(" 32 asm MFMAs" in l for l in kernels), out
