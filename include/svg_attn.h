@@ -228,6 +228,18 @@ int svg_varblock_attention_strided(const void* q, const void* k, const void* v, 
                                    const int32_t* q_row_idx, const int32_t* kv_row_idx, void* workspace,
                                    size_t workspace_bytes, const svg_attn_layout_t* layout, void* stream);
 
+/* Dense attention of Sq query rows over Skv keys (Sq != Skv allowed): softmax(q k^T * sm_scale) v per head.
+ * ref: the cross-attention branch of the Wan / Cosmos processors, F.scaled_dot_product_attention with attn_mask None
+ *      (svg/models/wan/attention.py:174-188,198-201, svg/models/cosmos/attention.py:104-107).
+ * head_dim 128, bf16 / fp16 (the two-phase 16x16x32 body of csrc/attn_m16.h on csrc/cross_policy.h: resident workgroups over the
+ * 256-row q-tiles of every head, no workspace, no planning pass); anything else SVG_ERR_UNSUPPORTED, and the caller keeps its own
+ * dense path.  Sq and Skv < 2^24, the key / value rows of one head within 2^32 bytes, BH * Sq * D < 2^40.  Key rows at or behind Skv
+ * are never read.  layout: svg_attn_layout_t above (q / o described with Sq rows, k / v with Skv), faults reported as by the
+ * *_strided entries; results are bit-identical to the contiguous call on the same values. */
+int svg_cross_attention(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t Sq, int32_t Skv, int32_t D,
+                        int32_t dtype, float sm_scale, const svg_attn_layout_t* layout /* NULL: contiguous [BH,Sq,D] / [BH,Skv,D] */,
+                        void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Online profiler (SVG1): mean-squared error of the two candidate masks on sampled query rows.
  * ref: sample_mse, svg/models/hyvideo/attention.py:376-399 (wan :211-234, cog :120-145) with the profiling masks

@@ -1,0 +1,80 @@
+// Cross-attention policy for attn_m16_tile (attn_m16.h): Sq query rows over ONE dense segment of Skv keys starting at key 0, Sq != Skv
+// allowed — the text / image-token attention of the Wan and Cosmos blocks (svg_cross_attention in svg_attn.h).  No row permutation, no
+// mask but the end of the key set: only the ragged last key tile takes the per-element path.  Modelled on BandPolicy (band_policy.h).
+#pragma once
+#include "attn_core.h"
+
+namespace svg {
+
+template <typename T>
+struct CrossPolicy {
+    static constexpr int kHeadDim = 128;
+    static constexpr bool kFixup = false;
+    static constexpr bool kPartialOut = false;
+    static constexpr bool kIntervalMask = true;   // row_intervals() describes the mask (two-phase body)
+    static constexpr bool kFastPartial = false;
+    static constexpr bool kOneBarrier = false;    // as BandPolicy; the kernel forces one barrier per tile as band_attn_m16_kernel does
+    static constexpr int kRowBlocks = 1;
+    static constexpr int kWR = 32;                // rows per wave
+    static constexpr int BM = 8 * kWR;            // rows per q-tile
+
+    struct Params {
+        const T* q;
+        const T* k;
+        const T* v;
+        T* o;
+        int Sq, Skv, BH, nqt;
+        float scale_log2;
+        AttnLayout lay;   // strides of q, k, v, o (contiguous [BH, Sq, D] / [BH, Skv, D] unless the caller passed a layout)
+    };
+    struct Ctx {
+        int head, qt, q0, q_end, nT;
+    };
+    struct KvCursor {};
+
+    // work item w of a launch -> (head, q-tile), head-major
+    static __device__ __forceinline__ void init_tile(const Params& p, Ctx& c, int head, int qt) {
+        c.head = head, c.qt = qt;
+        c.q0 = qt * BM;
+        c.q_end = min(c.q0 + BM, p.Sq);
+        c.nT = (p.Skv + kBN - 1) / kBN;
+    }
+
+    static __device__ __forceinline__ const T* q_base(const Params& p, const Ctx& c) { return p.q + layout_head_off(p.lay.q_bs, p.lay.q_hs, p.lay.hpb_q, c.head); }
+    static __device__ __forceinline__ const T* k_base(const Params& p, const Ctx& c) { return p.k + layout_head_off(p.lay.k_bs, p.lay.k_hs, p.lay.hpb_kv, c.head); }
+    static __device__ __forceinline__ const T* v_base(const Params& p, const Ctx& c) { return p.v + layout_head_off(p.lay.v_bs, p.lay.v_hs, p.lay.hpb_kv, c.head); }
+    static __device__ __forceinline__ T* o_base(const Params& p, const Ctx& c) { return p.o + layout_head_off(p.lay.o_bs, p.lay.o_hs, p.lay.hpb_q, c.head); }
+    static __device__ __forceinline__ int q_rs(const Params& p) { return p.lay.q_rs; }
+    static __device__ __forceinline__ int k_rs(const Params& p) { return p.lay.k_rs; }
+    static __device__ __forceinline__ int v_rs(const Params& p) { return p.lay.v_rs; }
+    static __device__ __forceinline__ int o_rs(const Params& p) { return p.lay.o_rs; }
+
+    static __device__ __forceinline__ int q_logical(const Ctx& c, int row) { return c.q0 + row; }
+    static __device__ __forceinline__ bool wave_active(const Ctx& c, int wrow0) { return c.q0 + wrow0 < c.q_end; }
+    static __device__ __forceinline__ int q_phys(const Params&, const Ctx& c, int row) {
+        const int l = c.q0 + row;
+        return l < c.q_end ? l : -1;
+    }
+    static __device__ __forceinline__ int tile_key0(const Ctx&, int t) { return t * kBN; }
+    static __device__ __forceinline__ void kv_cursor_init(const Params&, const Ctx&, KvCursor&, int) {}
+    // rows at or behind Skv are never read: their lanes fetch row 0, and row_intervals masks what they deliver
+    static __device__ __forceinline__ int kv_phys(const Params& p, const Ctx&, KvCursor&, int t, int row) {
+        const int l = t * kBN + row;
+        return l < p.Skv ? l : 0;
+    }
+    // wave-uniform: every key of the tile at key k0 exists
+    static __device__ __forceinline__ bool fast_full(const Params& p, int k0) { return k0 + kBN <= p.Skv; }
+    static __device__ __forceinline__ int classify(const Params& p, const Ctx& c, int k0, int wrow0) {
+        if (fast_full(p, k0)) return TILE_FULL;
+        return wave_active(c, wrow0) ? TILE_PARTIAL : TILE_SKIP;
+    }
+    // the keys of a row: [0, Skv), no second interval
+    static __device__ __forceinline__ void row_intervals(const Params& p, const Ctx&, int, int& a0, unsigned& alen, int& b0, unsigned& blen) {
+        a0 = 0, alen = (unsigned)p.Skv;
+        b0 = 0, blen = 0u;
+    }
+    static __device__ __forceinline__ float score_fixup(const Params&, float s) { return s; }
+    static __device__ __forceinline__ void notify(const Params&, const Ctx&) {}
+};
+
+}  // namespace svg

@@ -143,6 +143,7 @@ SIGNATURES = {
                                                     C.POINTER(PermDesc), C.POINTER(BandMask), _VP, C.POINTER(AttnLayout), _VP]),
     "svg_varblock_attention_strided": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _F32, _VP, _VP, _VP,
                                                  _I32, _I32, _VP, _VP, _VP, _SZ, C.POINTER(AttnLayout), _VP]),
+    "svg_cross_attention": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _F32, C.POINTER(AttnLayout), _VP]),
     "svg_sample_mse_strided": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _F32, C.POINTER(ProfileDesc), _VP, _VP,
                                          _SZ, _VP, C.POINTER(AttnLayout), _VP]),
     "svg_band_attention_prescaled": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, C.POINTER(BandMask), C.POINTER(PermDesc), _VP]),
@@ -604,6 +605,39 @@ def band_attention_switch(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
     assert use_alt_flag.dtype == torch.int32 and use_alt_flag.numel() >= 1
     return _band_attention(q, k, v, mask, alt_mask, use_alt_flag, sm_scale, head_perm_flag, vid0, num_frame, frame_size, 0, out, None, 1,
                            q_prescaled, token_major_out)
+
+
+def cross_attention_supported(q: torch.Tensor, k: torch.Tensor) -> bool:
+    """svg_cross_attention exists for 16-bit GPU tensors of head_dim 128 (q and k of one dtype)."""
+    return (q.is_cuda and k.is_cuda and q.dtype in (torch.bfloat16, torch.float16) and k.dtype == q.dtype
+            and q.shape[-1] == 128 and k.shape[-1] == 128)
+
+
+def cross_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, sm_scale: Optional[float] = None, token_major_out: bool = False,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Dense attention of q [B, H, Sq, D] over k, v [B, H, Skv, D] (or [BH, S, D]; Sq != Skv allowed) -> o of q's shape: softmax(q k^T
+    * sm_scale) v per head (svg_cross_attention: head_dim 128, bf16 / fp16).  Strided views with stride(-1) == 1 (projection outputs,
+    slices of a fused k/v projection) are read in place; views the layout cannot describe are copied.  token_major_out: as band_attention."""
+    lib = load()
+    _gpu(q, k, v, out)
+    assert k.shape == v.shape and q.shape[:-2] == k.shape[:-2] and q.shape[-1] == k.shape[-1] and q.dtype == k.dtype == v.dtype
+    Sq, D = q.shape[-2], q.shape[-1]
+    Skv = k.shape[-2]
+    BH = q.numel() // (Sq * D)
+    scale = _sm_scale(sm_scale, D)
+
+    def run(q, k, v, out):
+        return _try_strided(q, k, v, out, token_major_out, "svg_cross_attention", lambda o4, lay: lib.svg_cross_attention(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), BH, Sq, Skv, D, _dtype_code(q), scale, C.byref(lay), _stream()))
+
+    o = run(q, k, v, out)
+    if o is None:   # (what the layout cannot describe is copied, as the reference does)
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        o = run(q, k, v, out)
+    if o is None:   # ... and so is an output it cannot describe
+        out.copy_(run(q, k, v, None))
+        o = out
+    return o
 
 
 def varblock_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_map: torch.Tensor, q_sizes: torch.Tensor,

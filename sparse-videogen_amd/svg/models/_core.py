@@ -104,6 +104,17 @@ def dense_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, valid_len
     return o
 
 
+@time_logging_decorator("Level 3 - Cross Attention")
+def cross_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Dense attention of q [cfg, H, Sq, D] over a short key set k, v [cfg, H, Skv, D] — the text / image-token cross attention of the
+    Wan and Cosmos blocks (ref: wan/attention.py:174-188,198-201, cosmos/attention.py:104-107).  Without a mask, on the GPU, 16-bit, head_dim
+    128: svg_cross_attention on the views as they are.  Anything else (CPU tensors, head_dim 64, fp32, any mask) is the reference's
+    scaled_dot_product_attention call."""
+    if attention_mask is None and _native.cross_attention_supported(q, k) and v.is_cuda and v.dtype == q.dtype:
+        return _native.cross_attention(q, k, v, token_major_out=TOKEN_MAJOR_IO)
+    return F.scaled_dot_product_attention(q, k, v, attn_mask=attention_mask, dropout_p=0.0, is_causal=False)
+
+
 def _require_gpu(t: torch.Tensor, what: str) -> None:
     if not t.is_cuda:
         raise RuntimeError(f"{what}: the sparse path runs only on the GPU through libsvgattn (no CPU fallback); "

@@ -201,8 +201,8 @@ class WanAttn_SVGAttn_Processor2_0:
         else:
             query, key = self.get_qk_norm(attn, query, key)
             if cross and rotary_emb is None and query.is_cuda:
-                # cross attention (512 text keys, torch SDPA below): head views instead of three contiguous copies — the q copy alone is
-                # 2 x 774 MB of traffic per layer at Wan 2.1 720p; SDPA takes strided operands and returns q's layout
+                # cross attention (512 text keys, _core.cross_attention below): head views instead of three contiguous copies — the q copy
+                # alone is 2 x 774 MB of traffic per layer at Wan 2.1 720p; svg_cross_attention and SDPA both take strided operands
                 query, key, value = (x.unflatten(2, (attn.heads, -1)).transpose(1, 2) for x in (query, key, value))
             else:
                 query, key, value = self.get_transpose_qkv(attn, query, key, value)
@@ -213,10 +213,11 @@ class WanAttn_SVGAttn_Processor2_0:
             value_img = attn.add_v_proj(encoder_hidden_states_img)
             key_img = key_img.unflatten(2, (attn.heads, -1)).transpose(1, 2)
             value_img = value_img.unflatten(2, (attn.heads, -1)).transpose(1, 2)
-            hidden_states_img = F.scaled_dot_product_attention(query, key_img, value_img, attn_mask=None, dropout_p=0.0,
-                                                               is_causal=False)
+            hidden_states_img = _core.cross_attention(query, key_img, value_img)
             hidden_states_img = hidden_states_img.transpose(1, 2).flatten(2, 3).type_as(query)
-        if timestep is None or cross:  # cross attention in Wan (ref :198-201)
+        if cross:  # cross attention in Wan (ref :198-201): svg_cross_attention on the head views, SDPA where that does not apply
+            hidden_states = _core.cross_attention(query, key, value, attention_mask)
+        elif timestep is None:
             hidden_states = F.scaled_dot_product_attention(query, key, value, attn_mask=attention_mask, dropout_p=0.0,
                                                            is_causal=False)
         else:
