@@ -239,6 +239,19 @@ int svg_varblock_attention_strided(const void* q, const void* k, const void* v, 
 int svg_cross_attention(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t Sq, int32_t Skv, int32_t D,
                         int32_t dtype, float sm_scale, const svg_attn_layout_t* layout /* NULL: contiguous [BH,Sq,D] / [BH,Skv,D] */,
                         void* stream);
+/* svg_cross_attention over one key window per group of heads — a text key-padding mask, a batch of prompts of different lengths:
+ * heads [w * heads_per_window, (w + 1) * heads_per_window) attend to the keys [kv_begin[w], kv_end[w]) only.
+ * ref: the same branch with the bool [B, 1, 1, S_text] mask the Cosmos transformer builds (svg/models/cosmos/custom_models.py:85-86,
+ *      cosmos/attention.py:104-110), for masks whose True entries are one contiguous run per video.
+ * kv_begin, kv_end: DEVICE int32 arrays of BH / heads_per_window entries; kv_begin NULL: all zeros.  kv_end NULL, heads_per_window <= 0 or
+ * BH % heads_per_window != 0: SVG_ERR_BAD_ARG; every check of svg_cross_attention applies, all on the host before any launch.  The window
+ * VALUES are device data: the host does not read or validate them, the kernel clamps them to 0 <= begin <= end <= Skv.  Key rows
+ * outside a window are never read (a NaN in a padded embedding cannot reach the output) and not paid for: a window costs the 64-key
+ * tiles it touches.  An empty window gives zeros in every output row of its heads.  For kv_begin a multiple of 64 the result is
+ * bit-identical to svg_cross_attention on the key rows [kv_begin, kv_end) alone. */
+int svg_cross_attention_keyrange(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t Sq, int32_t Skv, int32_t D,
+                                 int32_t dtype, float sm_scale, const int32_t* kv_begin, const int32_t* kv_end,
+                                 int32_t heads_per_window, const svg_attn_layout_t* layout, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Online profiler (SVG1): mean-squared error of the two candidate masks on sampled query rows.

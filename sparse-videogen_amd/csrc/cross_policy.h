@@ -1,12 +1,31 @@
 // Cross-attention policy for attn_m16_tile (attn_m16.h): Sq query rows over ONE dense segment of Skv keys starting at key 0, Sq != Skv
 // allowed — the text / image-token attention of the Wan and Cosmos blocks (svg_cross_attention in svg_attn.h).  No row permutation, no
 // mask but the end of the key set: only the ragged last key tile takes the per-element path.  Modelled on BandPolicy (band_policy.h).
+// Windowed form (svg_cross_attention_keyrange): the segment is [begin, end) of the head's video, read from two device arrays — a text
+// key-padding mask.  Logical key tile t is key tile t0 + t with t0 = begin / 64, so a left-padded window walks no masked tile; the (at
+// most two) edge tiles take the per-element path; nT == 0 for an empty window, whose rows come out as zeros.  The plain form's members are
+// empty bases and compile-time branches: its kernel is the one it was.
 #pragma once
 #include "attn_core.h"
 
 namespace svg {
 
-template <typename T>
+template <bool Windowed>
+struct CrossWindowArgs {};
+template <>
+struct CrossWindowArgs<true> {
+    const int* kv_begin;   // [BH / heads_per_window] device; nullptr: all zeros
+    const int* kv_end;     // [BH / heads_per_window] device
+    int heads_per_window;
+};
+template <bool Windowed>
+struct CrossWindowCtx {};
+template <>
+struct CrossWindowCtx<true> {
+    int kbegin, kend, t0;  // the window clamped to 0 <= kbegin <= kend <= Skv; its first key tile
+};
+
+template <typename T, bool Windowed = false>
 struct CrossPolicy {
     static constexpr int kHeadDim = 128;
     static constexpr bool kFixup = false;
@@ -18,7 +37,7 @@ struct CrossPolicy {
     static constexpr int kWR = 32;                // rows per wave
     static constexpr int BM = 8 * kWR;            // rows per q-tile
 
-    struct Params {
+    struct Params : CrossWindowArgs<Windowed> {
         const T* q;
         const T* k;
         const T* v;
@@ -27,7 +46,7 @@ struct CrossPolicy {
         float scale_log2;
         AttnLayout lay;   // strides of q, k, v, o (contiguous [BH, Sq, D] / [BH, Skv, D] unless the caller passed a layout)
     };
-    struct Ctx {
+    struct Ctx : CrossWindowCtx<Windowed> {
         int head, qt, q0, q_end, nT;
     };
     struct KvCursor {};
@@ -37,7 +56,17 @@ struct CrossPolicy {
         c.head = head, c.qt = qt;
         c.q0 = qt * BM;
         c.q_end = min(c.q0 + BM, p.Sq);
-        c.nT = (p.Skv + kBN - 1) / kBN;
+        if constexpr (Windowed) {
+            // wave-uniform loads (head comes from the workgroup id), moved to scalar registers: the window, and with it nT, stay scalar
+            const int w = head / p.heads_per_window;
+            const int e = min(max(__builtin_amdgcn_readfirstlane(p.kv_end[w]), 0), p.Skv);
+            const int b = min(max(p.kv_begin ? __builtin_amdgcn_readfirstlane(p.kv_begin[w]) : 0, 0), e);
+            c.kbegin = b, c.kend = e;
+            c.t0 = b / kBN;
+            c.nT = e > b ? (e - 1) / kBN - c.t0 + 1 : 0;
+        } else {
+            c.nT = (p.Skv + kBN - 1) / kBN;
+        }
     }
 
     static __device__ __forceinline__ const T* q_base(const Params& p, const Ctx& c) { return p.q + layout_head_off(p.lay.q_bs, p.lay.q_hs, p.lay.hpb_q, c.head); }
@@ -55,22 +84,36 @@ struct CrossPolicy {
         const int l = c.q0 + row;
         return l < c.q_end ? l : -1;
     }
-    static __device__ __forceinline__ int tile_key0(const Ctx&, int t) { return t * kBN; }
+    static __device__ __forceinline__ int tile_key0(const Ctx& c, int t) {
+        if constexpr (Windowed) return (c.t0 + t) * kBN;
+        else return t * kBN;
+    }
     static __device__ __forceinline__ void kv_cursor_init(const Params&, const Ctx&, KvCursor&, int) {}
     // rows at or behind Skv are never read: their lanes fetch row 0, and row_intervals masks what they deliver
-    static __device__ __forceinline__ int kv_phys(const Params& p, const Ctx&, KvCursor&, int t, int row) {
-        const int l = t * kBN + row;
-        return l < p.Skv ? l : 0;
+    // (windowed: rows outside [kbegin, kend) likewise — their lanes fetch row kbegin, a row of the window: nT > 0 only if it has one)
+    static __device__ __forceinline__ int kv_phys(const Params& p, const Ctx& c, KvCursor&, int t, int row) {
+        if constexpr (Windowed) {
+            const int l = (c.t0 + t) * kBN + row;
+            return (l >= c.kbegin && l < c.kend) ? l : c.kbegin;
+        } else {
+            const int l = t * kBN + row;
+            return l < p.Skv ? l : 0;
+        }
     }
     // wave-uniform: every key of the tile at key k0 exists
     static __device__ __forceinline__ bool fast_full(const Params& p, int k0) { return k0 + kBN <= p.Skv; }
     static __device__ __forceinline__ int classify(const Params& p, const Ctx& c, int k0, int wrow0) {
-        if (fast_full(p, k0)) return TILE_FULL;
+        if constexpr (Windowed) {   // full only if the tile lies wholly inside the window
+            if (k0 >= c.kbegin && k0 + kBN <= c.kend) return TILE_FULL;
+        } else {
+            if (fast_full(p, k0)) return TILE_FULL;
+        }
         return wave_active(c, wrow0) ? TILE_PARTIAL : TILE_SKIP;
     }
-    // the keys of a row: [0, Skv), no second interval
-    static __device__ __forceinline__ void row_intervals(const Params& p, const Ctx&, int, int& a0, unsigned& alen, int& b0, unsigned& blen) {
-        a0 = 0, alen = (unsigned)p.Skv;
+    // the keys of a row: [0, Skv) — windowed: [kbegin, kend) — no second interval
+    static __device__ __forceinline__ void row_intervals(const Params& p, const Ctx& c, int, int& a0, unsigned& alen, int& b0, unsigned& blen) {
+        if constexpr (Windowed) a0 = c.kbegin, alen = (unsigned)(c.kend - c.kbegin);
+        else a0 = 0, alen = (unsigned)p.Skv;
         b0 = 0, blen = 0u;
     }
     static __device__ __forceinline__ float score_fixup(const Params&, float s) { return s; }

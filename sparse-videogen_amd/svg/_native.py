@@ -144,6 +144,8 @@ SIGNATURES = {
     "svg_varblock_attention_strided": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _F32, _VP, _VP, _VP,
                                                  _I32, _I32, _VP, _VP, _VP, _SZ, C.POINTER(AttnLayout), _VP]),
     "svg_cross_attention": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _F32, C.POINTER(AttnLayout), _VP]),
+    "svg_cross_attention_keyrange": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _F32, _VP, _VP, _I32, C.POINTER(AttnLayout),
+                                               _VP]),
     "svg_sample_mse_strided": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _F32, C.POINTER(ProfileDesc), _VP, _VP,
                                          _SZ, _VP, C.POINTER(AttnLayout), _VP]),
     "svg_band_attention_prescaled": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, C.POINTER(BandMask), C.POINTER(PermDesc), _VP]),
@@ -618,6 +620,21 @@ def cross_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, sm_scale:
     """Dense attention of q [B, H, Sq, D] over k, v [B, H, Skv, D] (or [BH, S, D]; Sq != Skv allowed) -> o of q's shape: softmax(q k^T
     * sm_scale) v per head (svg_cross_attention: head_dim 128, bf16 / fp16).  Strided views with stride(-1) == 1 (projection outputs,
     slices of a fused k/v projection) are read in place; views the layout cannot describe are copied.  token_major_out: as band_attention."""
+    return _cross_attention(q, k, v, None, None, sm_scale, token_major_out, out)
+
+
+def cross_attention_keyrange(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_end: torch.Tensor, kv_begin: Optional[torch.Tensor] = None,
+                             sm_scale: Optional[float] = None, token_major_out: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cross_attention over one key window per group of heads (svg_cross_attention_keyrange): kv_end / kv_begin are int32 GPU tensors of n
+    entries, BH % n == 0 (n = B: one window per video, the key-padding mask of a batch of prompts); heads [i * BH / n, (i + 1) * BH / n)
+    attend to the keys [kv_begin[i], kv_end[i]) (kv_begin None: from key 0).  The kernel clamps the windows to 0 <= begin <= end <= Skv,
+    reads no key row outside a window and writes zeros for an empty one.  Layouts, token_major_out, out: as cross_attention."""
+    assert kv_end is not None
+    return _cross_attention(q, k, v, kv_begin, kv_end, sm_scale, token_major_out, out)
+
+
+def _cross_attention(q, k, v, kv_begin, kv_end, sm_scale, token_major_out, out):
+    """cross_attention (kv_end None), and cross_attention_keyrange"""
     lib = load()
     _gpu(q, k, v, out)
     assert k.shape == v.shape and q.shape[:-2] == k.shape[:-2] and q.shape[-1] == k.shape[-1] and q.dtype == k.dtype == v.dtype
@@ -625,10 +642,19 @@ def cross_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, sm_scale:
     Skv = k.shape[-2]
     BH = q.numel() // (Sq * D)
     scale = _sm_scale(sm_scale, D)
+    if kv_end is not None:
+        _dev(kv_end, kv_begin)
+        n = kv_end.numel()
+        assert kv_end.dtype == torch.int32 and n > 0 and BH % n == 0, "kv_end: int32, BH % numel == 0"
+        assert kv_begin is None or (kv_begin.dtype == torch.int32 and kv_begin.numel() == n), "kv_begin: int32, as many entries as kv_end"
 
     def run(q, k, v, out):
-        return _try_strided(q, k, v, out, token_major_out, "svg_cross_attention", lambda o4, lay: lib.svg_cross_attention(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), BH, Sq, Skv, D, _dtype_code(q), scale, C.byref(lay), _stream()))
+        if kv_end is None:
+            return _try_strided(q, k, v, out, token_major_out, "svg_cross_attention", lambda o4, lay: lib.svg_cross_attention(
+                q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), BH, Sq, Skv, D, _dtype_code(q), scale, C.byref(lay), _stream()))
+        return _try_strided(q, k, v, out, token_major_out, "svg_cross_attention_keyrange", lambda o4, lay: lib.svg_cross_attention_keyrange(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), BH, Sq, Skv, D, _dtype_code(q), scale, _ptr(kv_begin), kv_end.data_ptr(),
+            BH // n, C.byref(lay), _stream()))
 
     o = run(q, k, v, out)
     if o is None:   # (what the layout cannot describe is copied, as the reference does)

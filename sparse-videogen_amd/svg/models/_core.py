@@ -8,6 +8,7 @@ branch raises: there is no CPU fallback for the sparse hot path.
 from __future__ import annotations
 
 import json
+import weakref
 from dataclasses import dataclass
 from typing import Optional
 
@@ -113,6 +114,56 @@ def cross_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attention
     if attention_mask is None and _native.cross_attention_supported(q, k) and v.is_cuda and v.dtype == q.dtype:
         return _native.cross_attention(q, k, v, token_major_out=TOKEN_MAJOR_IO)
     return F.scaled_dot_product_attention(q, k, v, attn_mask=attention_mask, dropout_p=0.0, is_causal=False)
+
+
+_KEY_WINDOW_CACHE = {}   # id(mask) -> (weak reference, mask._version, batch, Skv, windows or None)
+
+
+def key_windows(attention_mask, batch: int, Skv: int):
+    """The key windows of a key-padding mask: (begin, end) int32 [batch] on the mask's device when `attention_mask` is a BOOL tensor
+    [batch, 1, 1, Skv] or [1, 1, 1, Skv] (broadcast over the batch) whose True entries form ONE non-empty contiguous run in every video —
+    what the Cosmos transformer makes of the pipeline's text mask (ref: cosmos/custom_models.py:85-86); None for anything else (another
+    dtype or shape, a hole, a video without a True: that video's rows are NaN in the reference, and stay so on its SDPA call).
+    The hole test reads one flag back: once per mask object, which the model hands to every layer of a forward — keyed by object identity,
+    guarded by a weak reference and the in-place version counter, as _HunyuanProcessorBase.get_cu_max_seqlen."""
+    m = attention_mask
+    if not torch.is_tensor(m) or m.dtype != torch.bool or m.dim() != 4 or Skv <= 0:
+        return None
+    if tuple(m.shape[1:]) != (1, 1, Skv) or m.shape[0] not in (1, batch):
+        return None
+    ent = _KEY_WINDOW_CACHE.get(id(m))
+    if ent is not None and ent[0]() is m and ent[1:4] == (m._version, batch, Skv):
+        return ent[4]
+    if len(_KEY_WINDOW_CACHE) > 8:
+        _KEY_WINDOW_CACHE.clear()
+    rows = m.reshape(m.shape[0], Skv)
+    pos = torch.arange(Skv, device=m.device, dtype=torch.int32)
+    begin = torch.where(rows, pos, Skv).amin(dim=1).to(torch.int32)        # first True (Skv: none)
+    end = (torch.where(rows, pos, -1).amax(dim=1) + 1).to(torch.int32)     # one behind the last True (0: none)
+    one_run = _all_true((rows.sum(dim=1) == end - begin) & (end > begin))  # no hole, at least one key: the read-back
+    win = None
+    if one_run:
+        win = (begin.expand(batch).contiguous(), end.expand(batch).contiguous())
+    _KEY_WINDOW_CACHE[id(m)] = (weakref.ref(m), m._version, batch, Skv, win)
+    return win
+
+
+def _all_true(flags: torch.Tensor) -> bool:
+    """the host read-back of key_windows (its own function: the tests count its calls)"""
+    return bool(flags.all())
+
+
+def cross_attention_key_masked(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attention_mask: Optional[torch.Tensor]) -> torch.Tensor:
+    """cross_attention with a key-padding mask (the Cosmos blocks, ref: cosmos/attention.py:104-110): where key_windows describes the mask
+    and the kernel takes the tensors (GPU, 16-bit, head_dim 128), svg_cross_attention_keyrange over each video's window — keys outside it
+    are neither read nor paid for; anything else is cross_attention(q, k, v, attention_mask), i.e. the reference's SDPA call."""
+    if attention_mask is not None and _native.cross_attention_supported(q, k) and v.is_cuda and v.dtype == q.dtype \
+            and attention_mask.device == q.device:
+        win = key_windows(attention_mask, q.shape[0], k.shape[-2])
+        if win is not None:
+            with time_logging_decorator("Level 3 - Cross Attention"):
+                return _native.cross_attention_keyrange(q, k, v, win[1], win[0], token_major_out=TOKEN_MAJOR_IO)
+    return cross_attention(q, k, v, attention_mask)
 
 
 def _require_gpu(t: torch.Tensor, what: str) -> None:

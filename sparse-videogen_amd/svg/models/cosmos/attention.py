@@ -71,7 +71,9 @@ class _CosmosPlumbing:
         query, key = self.get_qk_norm(attn, query, key)
         query, key = self.get_rotary_emb(query, key, image_rotary_emb)
         assert query.shape[3] == key.shape[3] == value.shape[3], "Does not support GQA"
-        if cross:   # cross attention in Cosmos (ref :104-107): svg_cross_attention, SDPA where that does not apply
+        if cross and attention_mask is not None:   # ... with the text key-padding mask (ref :104-110): each video's key window, else SDPA
+            hidden_states = _core.cross_attention_key_masked(query, key, value, attention_mask)
+        elif cross:   # cross attention in Cosmos (ref :104-107): svg_cross_attention, SDPA where that does not apply
             hidden_states = _core.cross_attention(query, key, value, attention_mask)
         elif timestep is None:
             hidden_states = F.scaled_dot_product_attention(query, key, value, attn_mask=attention_mask, dropout_p=0.0,
