@@ -633,9 +633,14 @@ int svg_band_attention_prescaled_notify_seg(const void* q_scaled, const void* k,
  * { list, head * tiles_per_head + q-tile (row order), key tiles of the q-tile } and returns the number of triples; -1: bad
  * arguments or out_words < 3 * work items.
  * svg_debug_band_queue_cap: at most max_workgroups resident workgroups per queue launch from now on, and the queue also for
- * launches of fewer q-tiles than compute units (0: no cap) — tests of the queue's independence of how many workgroups are resident. */
+ * launches of fewer q-tiles than compute units (0: no cap) — tests of the queue's independence of how many workgroups are resident.
+ * svg_debug_band_replays: the bf16 band kernels at head_dim 128 test for an overflowing probability on every eighth key tile and
+ * validate a q-tile's sums after its loop; a q-tile that fails is computed once more with the test on every tile.  Synchronises the
+ * current device and returns how many q-tiles were replayed on it since the library was loaded or the counter was last reset
+ * (reset != 0 zeroes it after reading); -1: a HIP error. */
 int32_t svg_band_queue_order(int32_t BH, int32_t S, const svg_band_mask_t* mask, int32_t* out, int32_t out_words);
 int svg_debug_band_queue_cap(int32_t max_workgroups);
+int64_t svg_debug_band_replays(int32_t reset);
 
 /* Diagnostics (not part of the reference's interface; -DSVG_ABLATIONS builds, otherwise SVG_ERR_UNSUPPORTED): cycle trace of
  * the two-phase attention schedule.  After a svg_band_attention call with variant 64 (bf16, D = 128) and a synchronised

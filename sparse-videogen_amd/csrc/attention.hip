@@ -64,10 +64,14 @@ __global__ __launch_bounds__(512, 2) void band_attn_pp2_frozen_kernel(typename B
 // the two-phase schedule on v_mfma_f32_16x16x32 (attn_m16.h): head_dim 128; variant 8
 // (issue priority in the matrix phase, ONE barrier per tile: 32.55 ms against 33.1 with two — profiles/r04g_ab_m16_cfg.txt; the 32x32x16
 //  body gained nothing from the single barrier because the clock took it back, this one runs ~300 MHz further from the power limit)
+// The plain bf16 forms of this kernel, of the queue kernel and of the device-switched kernel run the overflow test of the max-free
+// softmax on every eighth tile and validate the q-tile after its loop (SPEC, attn_m16.h); fp16 and the pre-scaled forms do not.
+static __device__ unsigned g_band_replays;   // q-tiles that failed the validation and were replayed (svg_debug_band_replays)
+constexpr int kTailLds = 16;                 // bytes behind the stages: the queue's slot (two words), the word of the validation, one free
 template <typename T>
 __global__ __launch_bounds__(512, 2) void band_attn_m16_kernel(typename BandPolicy<T, 128, 8>::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_body_m16<T, BandPolicy<T, 128, 8>, false, 1>(prm, smem, nullptr);
+    attn_body_m16<T, BandPolicy<T, 128, 8>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
 }
 // pre-scaled q on the 16x16x32 body (PRE form of attn_body_m16)
 template <typename T>
@@ -84,14 +88,29 @@ __global__ __launch_bounds__(512, 2) void band_attn_m16_queue_kernel(typename Ba
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using Pol = BandPolicy<T, 128, 8>;
     int* const slot = (int*)(smem + attn_m16_lds_bytes());   // (head, q-tile) of the next work item, from lane 0 to the workgroup
+    // SPEC of attn_m16_tile (plain bf16): a q-tile whose validation failed leaves slot[2] = 1 and stores nothing.  Lane 0 then takes no
+    // new work item and marks the slot 2 — the same (head, q-tile) once more, with the overflow test on every tile — and after that
+    // pass 0 again.  (Waves that still read the verdict of the first pass see 1 or 2, non-zero either way; no wave reads slot[2] between
+    // the barrier below and the end of a second pass.)
+    constexpr bool kSpec = !PRE && std::is_same_v<T, __bf16>;
     int dry = 0;
+    if constexpr (kSpec) {
+        if (threadIdx.x == 0) slot[2] = 0;
+    }
     for (;;) {
         if (threadIdx.x == 0) {
-            const int xcd = __builtin_amdgcn_s_getreg((31 << 11) | 20) & (kNumXCD - 1);   // HW_REG_XCC_ID
-            int head = -1, qt = 0;
-            const int w = qd.take(xcd, dry);
-            if (w >= 0) qd.decode(w, head, qt);
-            slot[0] = head, slot[1] = qt;
+            bool fresh = true;
+            if constexpr (kSpec) {
+                fresh = __builtin_amdgcn_readfirstlane(slot[2]) != 1;   // (a scalar: one lane is active here)
+                slot[2] = fresh ? 0 : 2;
+            }
+            if (fresh) {
+                const int xcd = __builtin_amdgcn_s_getreg((31 << 11) | 20) & (kNumXCD - 1);   // HW_REG_XCC_ID
+                int head = -1, qt = 0;
+                const int w = qd.take(xcd, dry);
+                if (w >= 0) qd.decode(w, head, qt);
+                slot[0] = head, slot[1] = qt;
+            }
         }
         // Every wave is through the LDS reads of its last epilogue before any wave requests K / V of the next q-tile; and the slot
         // is not rewritten before every wave has read it: lane 0 comes back here through the barriers of a q-tile (two at least).
@@ -100,19 +119,23 @@ __global__ __launch_bounds__(512, 2) void band_attn_m16_queue_kernel(typename Ba
         if (head < 0) break;
         typename Pol::Ctx ctx;
         Pol::init_tile(prm, ctx, head, qt);
-        attn_m16_tile<T, Pol, false, 1, PRE>(prm, ctx, smem);
+        if constexpr (kSpec) {
+            const int check_mask = __builtin_amdgcn_readfirstlane(slot[2]) == 2 ? 0 : kCheckEvery - 1;
+            attn_m16_tile<T, Pol, false, 1, PRE, true>(prm, ctx, smem, check_mask, &g_band_replays);
+        } else {
+            attn_m16_tile<T, Pol, false, 1, PRE>(prm, ctx, smem);
+        }
     }
     if (threadIdx.x == 0) qd.leave(gridDim.x);
 }
-constexpr int kQueueLds = 16;   // bytes of the slot behind the stages
 // device-side switch between two masks on the 16x16x32 body (svg_band_attention_switch[_prescaled] at head_dim 128): `flag[0] != 0` selects prm_alt
 template <typename T, bool PRE = false>
 __global__ __launch_bounds__(512, 2) void band_attn_m16_switch_kernel(typename BandPolicy<T, 128, 8>::Params prm,
                                                                       typename BandPolicy<T, 128, 8>::Params prm_alt,
                                                                       const int32_t* __restrict__ flag) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (flag[0] != 0) attn_body_m16<T, BandPolicy<T, 128, 8>, false, 1, PRE>(prm_alt, smem, nullptr);
-    else attn_body_m16<T, BandPolicy<T, 128, 8>, false, 1, PRE>(prm, smem, nullptr);
+    if (flag[0] != 0) attn_body_m16<T, BandPolicy<T, 128, 8>, false, 1, PRE, !PRE>(prm_alt, smem, nullptr, &g_band_replays);
+    else attn_body_m16<T, BandPolicy<T, 128, 8>, false, 1, PRE, !PRE>(prm, smem, nullptr, &g_band_replays);
 }
 // the same for q that carries sm_scale * log2(e) (svg_band_attention_prescaled): no scale-and-shift per score
 template <typename T, int D>
@@ -299,7 +322,7 @@ static int band_dispatch(const void* q, const void* k, const void* v, void* o, i
             qd.ctr = block;
             int n_wg = std::min(qd.n_items, n_cu);
             if (cap > 0) n_wg = std::min(n_wg, cap);
-            return launch_attn(kern_q, dim3(n_wg), 512, lds + kQueueLds, st, p, qd);
+            return launch_attn(kern_q, dim3(n_wg), 512, lds, st, p, qd);
         };
         // a device-switch kernel: the parameters of both masks (the alternate one without the head permutation) and the flag, over
         // the q-tiles of the larger of the two
@@ -345,9 +368,10 @@ static int band_dispatch(const void* q, const void* k, const void* v, void* o, i
                 if constexpr (DD == 128) {
                     if (opts.use_alt)
                         return launch_switch(opts.prescaled ? band_attn_m16_switch_kernel<T, true> : band_attn_m16_switch_kernel<T>,
-                                             attn_m16_lds_bytes());
-                    if (opts.prescaled) return launch_queue(band_attn_m16_queue_kernel<T, true>, band_attn_m16q_kernel<T>, attn_m16_lds_bytes());
-                    return launch_queue(band_attn_m16_queue_kernel<T>, band_attn_m16_kernel<T>, attn_m16_lds_bytes());
+                                             attn_m16_lds_bytes() + kTailLds);
+                    if (opts.prescaled)
+                        return launch_queue(band_attn_m16_queue_kernel<T, true>, band_attn_m16q_kernel<T>, attn_m16_lds_bytes() + kTailLds);
+                    return launch_queue(band_attn_m16_queue_kernel<T>, band_attn_m16_kernel<T>, attn_m16_lds_bytes() + kTailLds);
                 }
                 return SVG_ERR_UNSUPPORTED;
         }
@@ -508,6 +532,14 @@ extern "C" int svg_debug_band_queue_cap(int32_t max_workgroups) {
     if (max_workgroups < 0) return SVG_ERR_BAD_ARG;
     g_queue_cap.store(max_workgroups, std::memory_order_relaxed);
     return SVG_OK;
+}
+
+extern "C" int64_t svg_debug_band_replays(int32_t reset) {
+    unsigned n = 0;
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(&n, HIP_SYMBOL(g_band_replays), sizeof n) != hipSuccess) return -1;
+    const unsigned zero = 0;
+    if (reset && hipMemcpyToSymbol(HIP_SYMBOL(g_band_replays), &zero, sizeof zero) != hipSuccess) return -1;
+    return (int64_t)n;
 }
 
 // the traces of the last traced launch (diagnostics builds; SVG_ERR_UNSUPPORTED otherwise)

@@ -85,8 +85,24 @@ __device__ __forceinline__ float quad_group_sum(float x) {
 // wave of the workgroup passes the same number of workgroup barriers whatever its role (leading, lagging, idle: nT + 2 with one
 // barrier per tile) and leaves with no LDS-DMA request in flight, so a workgroup may run one q-tile after another: it needs one
 // workgroup barrier between two of them (the epilogue of the first reads the stages the second fills).
-template <typename T, typename P, bool TRACE = false, int ONEBAR = -1, bool PRE = false>
-__device__ __forceinline__ void attn_m16_tile(const typename P::Params& prm, const typename P::Ctx& ctx, char* smem) {
+//
+// SPEC (honoured where MSUM is on: bf16, plain form): the overflow test of the max-free softmax runs on every kCheckEvery-th tile only,
+// and the q-tile is validated once, after the tile loop.  The per-tile test serves two ends: the reference follows the row maximum, and
+// no probability overflows.  The first needs no tile granularity — P is floating point, O and l accumulate in fp32, so a reference that
+// lags by up to kCheckEvery - 1 tiles changes the rounding, not the accuracy — and the second is checked where it would show: an
+// overflowed probability leaves an infinity or a NaN in the lane's row sums or O accumulators.  After the loop every lane tests them with
+// !(|x| < 2^120), the wave votes, lane 0 of a wave that saw one sets a word in LDS behind the stages (smem + attn_m16_lds_bytes() + 8:
+// the launch provides 16 bytes there, the caller zeroes the word before the first pass and no pass with check_mask = 0 touches it),
+// ONE workgroup barrier follows that every wave passes, idle waves included, and a non-zero word
+// makes every wave return true without storing anything: the caller then runs the same q-tile once more with check_mask = 0 — the test
+// on every tile, the body without SPEC tile for tile, no validation — and that pass stores.  At most one replay per q-tile, no waiting
+// on another workgroup; the stages are quiescent at the barrier as they are between two q-tiles of a queue kernel, and no epilogue has
+// read them, so the second pass needs no further barrier in front.  `replay_ctr` (or nullptr) counts replayed q-tiles
+// (svg_debug_band_replays).  Without SPEC the function returns false.
+constexpr int kCheckEvery = 8;
+template <typename T, typename P, bool TRACE = false, int ONEBAR = -1, bool PRE = false, bool SPEC = false>
+__device__ __forceinline__ bool attn_m16_tile(const typename P::Params& prm, const typename P::Ctx& ctx, char* smem,
+                                              int check_mask = kCheckEvery - 1, unsigned* replay_ctr = nullptr) {
     using E = Elt<T>;
     using M = Mfma16<T>;
     using V8 = typename E::v8;
@@ -113,6 +129,8 @@ __device__ __forceinline__ void attn_m16_tile(const typename P::Params& prm, con
     // its first the gain is gone (65.4 Mcycles).  fp16 keeps the vector-phase sum: 2^-10 would push small probabilities into fp16's subnormals.
     constexpr bool MSUM = std::is_same_v<T, __bf16> && !PRE;
     constexpr float kBias = MSUM ? 10.f : 0.f;
+    constexpr bool kSpec = SPEC && MSUM;
+    static_assert(!(SPEC && TRACE) && (kCheckEvery & (kCheckEvery - 1)) == 0, "SPEC: product kernels; a power of two");
 
     unsigned long long wg_t0 = 0, wg_t2 = 0;   // launch timeline (diagnostics builds, svg_debug_wg_trace): entry, end of the tile loop
     if constexpr (TRACE) wg_t0 = __builtin_amdgcn_s_memtime();
@@ -123,6 +141,8 @@ __device__ __forceinline__ void attn_m16_tile(const typename P::Params& prm, con
     const int n16 = lane & 15;
     const bool lagging = wave >= NW / 2;
     const int nT = ctx.nT;
+    // SPEC: tiles with (t & check_mask) == 0 run the overflow test (0 on the replay: every tile); the word the validation votes into
+    volatile int* const spec_word = (volatile int*)(smem + attn_m16_lds_bytes() + 8);
 
     const T* __restrict__ qb = P::q_base(prm, ctx);
     const T* __restrict__ kb_ = P::k_base(prm, ctx);
@@ -206,6 +226,7 @@ __device__ __forceinline__ void attn_m16_tile(const typename P::Params& prm, con
 #pragma unroll
     for (int j = 0; j < 8; ++j) ones8[j] = E::from_float(1.f);
     bool force_exact = true;                                           // MSUM: psum_thr < 0
+    int spec_mode = -1;                                                // SPEC: -1 while force_exact holds, then check_mask
     f32x4 acc_o[NDB][2];
 #pragma unroll
     for (int db = 0; db < NDB; ++db)
@@ -320,8 +341,16 @@ __device__ __forceinline__ void attn_m16_tile(const typename P::Params& prm, con
             const u32x4_t w2 = __builtin_bit_cast(u32x4_t, pf[1][0]), w3 = __builtin_bit_cast(u32x4_t, pf[1][1]);
             const unsigned o0 = w0[0] | w0[1] | w0[2], o1 = w0[3] | w1[0] | w1[1], o2 = w1[2] | w1[3] | w2[0];   // (v_or3_b32, depth 3)
             const unsigned o3 = w2[1] | w2[2] | w2[3], o4 = w3[0] | w3[1] | w3[2];
-            const unsigned bits = (o0 | o1 | o2) | (o3 | o4 | w3[3]);
-            exact = force_exact || __any((bits & 0x40004000u) != 0u);
+            if constexpr (kSpec) {
+                exact = spec_mode < 0;
+                if (spec_mode >= 0 && (t & spec_mode) == 0) {   // wave-uniform: a scalar branch around the OR chain and the vote
+                    const unsigned bits = (o0 | o1 | o2) | (o3 | o4 | w3[3]);
+                    exact = __builtin_amdgcn_readfirstlane((int)__any((bits & 0x40004000u) != 0u)) != 0;   // (a scalar on both paths)
+                }
+            } else {
+                const unsigned bits = (o0 | o1 | o2) | (o3 | o4 | w3[3]);
+                exact = force_exact || __any((bits & 0x40004000u) != 0u);
+            }
         } else {
             exact = !__all(psum[0] + psum[1] <= psum_thr);
         }
@@ -374,6 +403,7 @@ __device__ __forceinline__ void attn_m16_tile(const typename P::Params& prm, con
             }
             psum_thr = __all(all_finite) ? 2048.f : -1.f;
             force_exact = !__all(all_finite);
+            if constexpr (kSpec) spec_mode = force_exact ? -1 : check_mask;
 #pragma unroll
             for (int db = 0; db < NDB; ++db)
 #pragma unroll
@@ -459,6 +489,15 @@ __device__ __forceinline__ void attn_m16_tile(const typename P::Params& prm, con
         }
     };
 
+    // SPEC, first pass: the vote of this wave (`bad`: a lane holds an overflowed sum or accumulator), the barrier, the verdict
+    auto spec_replay = [&](bool bad) -> bool {
+        if (__any(bad) && lane == 0) *spec_word = 1;
+        pp_barrier();
+        if (__builtin_amdgcn_readfirstlane(*spec_word) == 0) return false;
+        if (replay_ctr && tid == 0) atomicAdd(replay_ctr, 1u);
+        return true;
+    };
+
     if (idle) {
         for (int t = 0; t < nT; ++t) {
             if (!kOneBar || lagging) pp_barrier();
@@ -468,8 +507,11 @@ __device__ __forceinline__ void attn_m16_tile(const typename P::Params& prm, con
         }
         pp_barrier();
         if (!kOneBar && !lagging) pp_barrier();
+        if constexpr (kSpec) {
+            if (check_mask != 0 && spec_replay(false)) return true;
+        }
         P::notify(prm, ctx);
-        return;
+        return false;
     }
 
     // ---- M(0): only S(0) ----
@@ -521,6 +563,18 @@ __device__ __forceinline__ void attn_m16_tile(const typename P::Params& prm, con
         }
         wg_t2 = __builtin_amdgcn_s_memtime();
     }
+    if constexpr (kSpec) {
+        if (check_mask != 0) {
+            bool bad = !(fabsf(acc_l[0][0]) < 0x1p120f) || !(fabsf(acc_l[1][0]) < 0x1p120f);   // (also true of a NaN)
+#pragma unroll
+            for (int db = 0; db < NDB; ++db)
+#pragma unroll
+                for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) bad = bad || !(fabsf(acc_o[db][rb][r]) < 0x1p120f);
+            if (spec_replay(bad)) return true;
+        }
+    }
 
     // ---------------- epilogue: O^T -> LDS -> whole rows ----------------
     constexpr int kEpiStride = D * 2 + 8;
@@ -564,14 +618,22 @@ __device__ __forceinline__ void attn_m16_tile(const typename P::Params& prm, con
             w[5] = __builtin_amdgcn_s_getreg((31 << 11) | 20);   // HW_REG_XCC_ID
         }
     }
+    return false;
 }
 
-// the workgroup's one q-tile is the one its dispatch id maps to (P::init)
-template <typename T, typename P, bool TRACE = false, int ONEBAR = -1, bool PRE = false>
-__device__ __forceinline__ void attn_body_m16(const typename P::Params& prm, char* smem, char* policy_lds) {
+// the workgroup's one q-tile is the one its dispatch id maps to (P::init); SPEC: and once more if its validation failed
+template <typename T, typename P, bool TRACE = false, int ONEBAR = -1, bool PRE = false, bool SPEC = false>
+__device__ __forceinline__ void attn_body_m16(const typename P::Params& prm, char* smem, char* policy_lds, unsigned* replay_ctr = nullptr) {
     typename P::Ctx ctx;
     if (!P::init(prm, ctx, policy_lds)) return;
-    attn_m16_tile<T, P, TRACE, ONEBAR, PRE>(prm, ctx, smem);
+    if constexpr (SPEC && std::is_same_v<T, __bf16> && !PRE) {   // (where attn_m16_tile honours it)
+        if (threadIdx.x == 0) *(volatile int*)(smem + attn_m16_lds_bytes() + 8) = 0;   // (ordered by the first barrier of the q-tile)
+#pragma nounroll
+        for (int check_mask = kCheckEvery - 1;; check_mask = 0)
+            if (!attn_m16_tile<T, P, TRACE, ONEBAR, PRE, SPEC>(prm, ctx, smem, check_mask, replay_ctr)) break;
+    } else {
+        attn_m16_tile<T, P, TRACE, ONEBAR, PRE>(prm, ctx, smem);
+    }
 }
 
 }  // namespace svg

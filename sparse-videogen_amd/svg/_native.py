@@ -103,6 +103,7 @@ SIGNATURES = {
     "svg_debug_wg_trace": (C.c_int, [_VP, _I32]),
     "svg_band_queue_order": (_I32, [_I32, _I32, C.POINTER(BandMask), _VP, _I32]),
     "svg_debug_band_queue_cap": (C.c_int, [_I32]),
+    "svg_debug_band_replays": (C.c_int64, [_I32]),
     "svg_rms_norm_forward": (C.c_int, [_VP, _VP, C.c_int64, _I32, _I32, C.c_float, _VP]),
     "svg_layer_norm_forward": (C.c_int, [_VP, _VP, _VP, C.c_int64, _I32, _I32, _VP]),
     "svg_apply_qk_rope_inplace_cossin": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP]),
@@ -566,6 +567,15 @@ def band_notify_target(S: int, mask: BandMask) -> int:
     t = load().svg_band_attention_notify_target(int(S), C.byref(mask))
     assert t > 0
     return int(t)
+
+
+def band_replays(reset: bool = False) -> int:
+    """q-tiles the bf16 band kernels at head_dim 128 computed a second time because the validation of their sums failed
+    (svg_debug_band_replays): synchronises the current device; reset=True zeroes the counter after reading."""
+    n = int(load().svg_debug_band_replays(1 if reset else 0))
+    if n < 0:
+        raise RuntimeError("svg_debug_band_replays failed")
+    return n
 
 
 def band_notify_layout(S: int, mask: BandMask, nseg: int):
