@@ -252,6 +252,22 @@ int svg_cross_attention(const void* q, const void* k, const void* v, void* o, in
 int svg_cross_attention_keyrange(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t Sq, int32_t Skv, int32_t D,
                                  int32_t dtype, float sm_scale, const int32_t* kv_begin, const int32_t* kv_end,
                                  int32_t heads_per_window, const svg_attn_layout_t* layout, void* stream);
+/* svg_cross_attention over TWO key sets in one launch, the results added: o = T(float(T(o_a)) + float(T(o_b))) with o_x =
+ * softmax(q k_x^T * sm_scale) v_x — each branch normalised and rounded to the 16-bit type on its own, then one fp32 add and one
+ * conversion, what torch's add of two 16-bit tensors does: bit-identical to svg_cross_attention(q, k_a, v_a) + svg_cross_attention(q,
+ * k_b, v_b) followed by that add.
+ * ref: the text and the CLIP image branch of a Wan I2V block and the `hidden_states + hidden_states_img` behind them
+ *      (svg/models/wan/attention.py:174-188,198-201,210-229).
+ * Per q-tile the kernel stores T(o_a), then runs set B and adds on the final store: q is read twice and o written twice by one launch,
+ * no workspace, no atomics.  o MUST NOT OVERLAP q, k_a, v_a, k_b or v_b: q is read again after the first store to o.
+ * layout describes q, o and set A (k_a, v_a with Skv_a rows); of layout_b ONLY the k and v strides are read — they describe k_b, v_b
+ * with Skv_b rows; heads per batch are those of `layout`.  Either may be NULL: contiguous ([BH, Sq, D], [BH, Skv_x, D]).  Every check of
+ * svg_cross_attention applies to both sets, all on the host before any launch: a NULL pointer or a non-positive size SVG_ERR_BAD_ARG,
+ * D != 128 or rows the kernels cannot address SVG_ERR_UNSUPPORTED, layout faults as by the *_strided entries.  Key rows at or behind a
+ * set's Skv are never read. */
+int svg_cross_attention_pair(const void* q, const void* k_a, const void* v_a, const void* k_b, const void* v_b, void* o, int32_t BH,
+                             int32_t Sq, int32_t Skv_a, int32_t Skv_b, int32_t D, int32_t dtype, float sm_scale,
+                             const svg_attn_layout_t* layout, const svg_attn_layout_t* layout_b, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Online profiler (SVG1): mean-squared error of the two candidate masks on sampled query rows.

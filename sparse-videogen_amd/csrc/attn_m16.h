@@ -75,6 +75,24 @@ __device__ __forceinline__ float quad_group_sum(float x) {
     return x + __shfl_xor(x, 32);
 }
 
+// Add-on-store (detected: a policy with a static add_on_store(prm), cross_policy.h CrossPairPolicy; every other policy compiles the row
+// store it had): where add_on_store(prm) holds, the final row store ADDS the q-tile's rounded result to the 16-bit values already in o —
+// T(float(o) + float(T(result))), one fp32 add and one conversion per element, what torch's add of two 16-bit tensors does.
+template <typename P, typename = void>
+struct HasAddOnStore : std::false_type {};
+template <typename P>
+struct HasAddOnStore<P, std::void_t<decltype(&P::add_on_store)>> : std::true_type {};
+
+template <typename T>
+__device__ __forceinline__ u32x2 add_rounded16(u32x2 a, u32x2 b) {
+    using E = Elt<T>;
+    const typename E::v4 x = __builtin_bit_cast(typename E::v4, a), y = __builtin_bit_cast(typename E::v4, b);
+    typename E::v4 s;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s[j] = E::from_float(E::to_float(x[j]) + E::to_float(y[j]));
+    return __builtin_bit_cast(u32x2, s);
+}
+
 // ONEBAR: -1 as the policy says, 0 / 1 forced.  The matrix phase runs at issue priority 1, as in attn_body_pp2.
 // PRE: q arrives multiplied by sm_scale * log2(e) and the S^T accumulators start at minus the row's reference, so the MFMAs deliver the
 // exponent argument (no scale-and-shift FMA per score; the scheme of attn_body_pp2's PRE form).
@@ -605,8 +623,16 @@ __device__ __forceinline__ bool attn_m16_tile(const typename P::Params& prm, con
 #pragma unroll
     for (int i = 0; i < 32 / kRowsPerPass; ++i) {
         const int rr = i * kRowsPerPass + sub;
-        const u32x2 val = *(const u32x2*)(erow + rr * kEpiStride + colb);
-        if (ephys[i] >= 0) *(u32x2*)((char*)(ob + (size_t)ephys[i] * o_rs) + colb) = val;
+        u32x2 val = *(const u32x2*)(erow + rr * kEpiStride + colb);
+        if (ephys[i] >= 0) {
+            u32x2* const dst = (u32x2*)((char*)(ob + (size_t)ephys[i] * o_rs) + colb);
+            // (which lane stores which 8 bytes of o depends on wave, lane and the q-tile only — never on the keys: a lane that adds
+            //  here reads back what IT stored in an earlier pass over the same q-tile, program order, no fence; see cross_attn_pair_kernel)
+            if constexpr (HasAddOnStore<P>::value) {
+                if (P::add_on_store(prm)) val = add_rounded16<T>(*dst, val);
+            }
+            *dst = val;
+        }
     }
     P::notify(prm, ctx);
     if constexpr (TRACE) {   // the four stamps and the hardware ids of attn_body_pp2's timeline, one record per workgroup (wave 0)

@@ -120,4 +120,27 @@ struct CrossPolicy {
     static __device__ __forceinline__ void notify(const Params&, const Ctx&) {}
 };
 
+// Pair form (svg_cross_attention_pair): the plain policy run twice per q-tile, over key set A and then over key set B, the second pass
+// adding its rounded rows to what the first stored (attn_m16.h: add-on-store, switched on by add_on_store below).  The kernel hands
+// attn_m16_tile one Params per pass — the plain Params of that pass's key set plus the flag — so every member above serves both.
+template <typename T>
+struct CrossPairPolicy : CrossPolicy<T, false> {
+    using Base = CrossPolicy<T, false>;
+    struct Params : Base::Params {
+        int add_to_o;   // 0: store the rows (pass A); 1: add them to the rows in o (pass B)
+    };
+    static __device__ __forceinline__ bool add_on_store(const Params& p) { return p.add_to_o != 0; }
+};
+// what the pair kernel takes: the plain Params of key set A, and of key set B whatever differs — its tensors, its length and its strides
+// (the batch stride of a [B, Skv, H * D] projection view depends on Skv: one AttnLayout cannot describe both sets)
+template <typename T>
+struct CrossPairArgs {
+    typename CrossPolicy<T, false>::Params a;
+    const T* k_b;
+    const T* v_b;
+    int Skv_b, hpb_kv_b;
+    long long k_bs_b, k_hs_b, v_bs_b, v_hs_b;
+    int k_rs_b, v_rs_b;
+};
+
 }  // namespace svg

@@ -147,6 +147,8 @@ SIGNATURES = {
     "svg_cross_attention": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _F32, C.POINTER(AttnLayout), _VP]),
     "svg_cross_attention_keyrange": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _F32, _VP, _VP, _I32, C.POINTER(AttnLayout),
                                                _VP]),
+    "svg_cross_attention_pair": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _F32, C.POINTER(AttnLayout),
+                                           C.POINTER(AttnLayout), _VP]),
     "svg_sample_mse_strided": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _F32, C.POINTER(ProfileDesc), _VP, _VP,
                                          _SZ, _VP, C.POINTER(AttnLayout), _VP]),
     "svg_band_attention_prescaled": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, C.POINTER(BandMask), C.POINTER(PermDesc), _VP]),
@@ -666,14 +668,47 @@ def _cross_attention(q, k, v, kv_begin, kv_end, sm_scale, token_major_out, out):
             q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), BH, Sq, Skv, D, _dtype_code(q), scale, _ptr(kv_begin), kv_end.data_ptr(),
             BH // n, C.byref(lay), _stream()))
 
-    o = run(q, k, v, out)
+    return _run_or_copy(run, (q, k, v), out)
+
+
+def _run_or_copy(run, tensors, out):
+    """run(*tensors, out) -> o, or None where a layout cannot describe a view: the fall-backs of the cross-attention entries"""
+    o = run(*tensors, out)
     if o is None:   # (what the layout cannot describe is copied, as the reference does)
-        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        o = run(q, k, v, out)
+        tensors = tuple(t.contiguous() for t in tensors)
+        o = run(*tensors, out)
     if o is None:   # ... and so is an output it cannot describe
-        out.copy_(run(q, k, v, None))
+        out.copy_(run(*tensors, None))
         o = out
     return o
+
+
+def cross_attention_pair(q: torch.Tensor, k_a: torch.Tensor, v_a: torch.Tensor, k_b: torch.Tensor, v_b: torch.Tensor,
+                         sm_scale: Optional[float] = None, token_major_out: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cross_attention(q, k_a, v_a) + cross_attention(q, k_b, v_b) in ONE launch (svg_cross_attention_pair: the text and the image keys
+    of a Wan I2V block), bit for bit: each branch is rounded to the 16-bit type, then added as torch adds two 16-bit tensors.  The two key
+    sets have their own lengths and their own strides.  Layouts, token_major_out, out: as cross_attention; out must not overlap an input."""
+    lib = load()
+    _gpu(q, k_a, v_a, k_b, v_b, out)
+    for k, v in ((k_a, v_a), (k_b, v_b)):
+        assert k.shape == v.shape and q.shape[:-2] == k.shape[:-2] and q.shape[-1] == k.shape[-1] and q.dtype == k.dtype == v.dtype
+    Sq, D = q.shape[-2], q.shape[-1]
+    BH = q.numel() // (Sq * D)
+    scale = _sm_scale(sm_scale, D)
+
+    def run(q, k_a, v_a, k_b, v_b, out):
+        kb4, vb4 = _view4(k_b), _view4(v_b)
+        if not (_strided_ok(kb4, True) and _strided_ok(vb4, True)):
+            return None
+
+        def call(o4, lay):
+            lay_b = attn_layout(_view4(q), kb4, vb4, o4)   # (its k / v strides are what the entry reads)
+            return lib.svg_cross_attention_pair(q.data_ptr(), k_a.data_ptr(), v_a.data_ptr(), k_b.data_ptr(), v_b.data_ptr(), o4.data_ptr(), BH,
+                                                Sq, k_a.shape[-2], k_b.shape[-2], D, _dtype_code(q), scale, C.byref(lay), C.byref(lay_b), _stream())
+
+        return _try_strided(q, k_a, v_a, out, token_major_out, "svg_cross_attention_pair", call)
+
+    return _run_or_copy(run, (q, k_a, v_a, k_b, v_b), out)
 
 
 def varblock_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_map: torch.Tensor, q_sizes: torch.Tensor,

@@ -116,6 +116,19 @@ def cross_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attention
     return F.scaled_dot_product_attention(q, k, v, attn_mask=attention_mask, dropout_p=0.0, is_causal=False)
 
 
+def cross_attention_pair(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_img: torch.Tensor, v_img: torch.Tensor,
+                         attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cross_attention(q, k, v, attention_mask) + cross_attention(q, k_img, v_img), head layout [cfg, H, Sq, D] — the text and the image
+    branch of a Wan I2V block and the add behind them (ref: wan/attention.py:174-188,198-201).  Without a mask, on the GPU, 16-bit, head_dim
+    128: ONE svg_cross_attention_pair launch, bit for bit the sum of the two calls; anything else is exactly those two calls and the add."""
+    ts = (q, k, v, k_img, v_img)
+    if attention_mask is None and _native.cross_attention_supported(q, k) and _native.cross_attention_supported(q, k_img) \
+            and all(t.is_cuda and t.dtype == q.dtype for t in ts):
+        with time_logging_decorator("Level 3 - Cross Attention"):
+            return _native.cross_attention_pair(q, k, v, k_img, v_img, token_major_out=TOKEN_MAJOR_IO)
+    return cross_attention(q, k, v, attention_mask) + cross_attention(q, k_img, v_img)
+
+
 _KEY_WINDOW_CACHE = {}   # id(mask) -> (weak reference, mask._version, batch, Skv, windows or None)
 
 

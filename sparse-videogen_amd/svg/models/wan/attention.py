@@ -134,6 +134,9 @@ class WanAttn_SVGAttn_Processor2_0:
         return query, key
 
     fused_prologue = True    # self attention on the GPU: qk_norm + transpose + rotary_emb as ONE pass over q, k, v (svg_rmsnorm_rope_transpose)
+    # opt-in: the text and the image cross attention of an I2V block and the add of get_o as ONE launch (_core.cross_attention_pair,
+    # svg_cross_attention_pair) instead of two launches and a torch add; the output is bit-identical in both positions
+    i2v_pair_launch = False
 
     @time_logging_decorator("Level 2 - qk_norm + transpose + rotary_emb (fused)")
     def get_fused_prologue(self, attn, query, key, value, rotary_emb, q_scale: float = 1.0):
@@ -213,9 +216,13 @@ class WanAttn_SVGAttn_Processor2_0:
             value_img = attn.add_v_proj(encoder_hidden_states_img)
             key_img = key_img.unflatten(2, (attn.heads, -1)).transpose(1, 2)
             value_img = value_img.unflatten(2, (attn.heads, -1)).transpose(1, 2)
-            hidden_states_img = _core.cross_attention(query, key_img, value_img)
-            hidden_states_img = hidden_states_img.transpose(1, 2).flatten(2, 3).type_as(query)
-        if cross:  # cross attention in Wan (ref :198-201): svg_cross_attention on the head views, SDPA where that does not apply
+            if not self.i2v_pair_launch:
+                hidden_states_img = _core.cross_attention(query, key_img, value_img)
+                hidden_states_img = hidden_states_img.transpose(1, 2).flatten(2, 3).type_as(query)
+        if encoder_hidden_states_img is not None and self.i2v_pair_launch:   # (an I2V call is a cross call)
+            # both branches and the add of get_o in one launch (svg_cross_attention_pair), the two calls and the add where that does not apply
+            hidden_states = _core.cross_attention_pair(query, key, value, key_img, value_img, attention_mask)
+        elif cross:  # cross attention in Wan (ref :198-201): svg_cross_attention on the head views, SDPA where that does not apply
             hidden_states = _core.cross_attention(query, key, value, attention_mask)
         elif timestep is None:
             hidden_states = F.scaled_dot_product_attention(query, key, value, attn_mask=attention_mask, dropout_p=0.0,
