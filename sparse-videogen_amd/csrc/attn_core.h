@@ -55,6 +55,9 @@ constexpr int attn_lds_bytes() {
 __device__ __forceinline__ i16x4 lds_read_tr16(const char* p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4*)(p));
 }
+__device__ __forceinline__ i16x8 lds_read_tr16x2(const char* p_lo, const char* p_hi) {   // two of them: elements 0..3, 4..7
+    return __builtin_shufflevector(lds_read_tr16(p_lo), lds_read_tr16(p_hi), 0, 1, 2, 3, 4, 5, 6, 7);
+}
 
 // The attention kernel body.  Policy P supplies (all functions static __device__):
 //   struct Params; struct Ctx (workgroup-uniform);
@@ -293,10 +296,7 @@ __device__ __forceinline__ void attn_body(const typename P::Params& prm, char* s
         constexpr int NPV = DB * 4;  // MFMA steps: idx = db * 4 + b * 2 + h
         auto vfrag = [&](int idx) -> V8 {
             const int db = idx >> 2, kb0 = 32 * ((idx >> 1) & 1) + 16 * (idx & 1);
-            const i16x4 lo = lds_read_tr16(vbase + db * (kBN * 64) + kb0 * 64);
-            const i16x4 hi = lds_read_tr16(vbase + db * (kBN * 64) + (kb0 + 8) * 64);
-            i16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-            return __builtin_bit_cast(V8, both);
+            return __builtin_bit_cast(V8, lds_read_tr16x2(vbase + db * (kBN * 64) + kb0 * 64, vbase + db * (kBN * 64) + (kb0 + 8) * 64));
         };
         V8 ring[2];   // one step ahead
         ring[0] = vfrag(0);
@@ -383,14 +383,14 @@ __device__ __forceinline__ void attn_body(const typename P::Params& prm, char* s
 
 
 // =====================================================================================================================
-// Helpers of the LDS-DMA bodies (attn_body_pp2 below, attn_body_w4 in attn_w4.h).
+// Helpers of the LDS-DMA bodies (attn_body_pp2 below, attn_body_w4 in attn_w4.h, attn_m16_tile in attn_m16.h).
 // K / V tiles arrive by LDS-DMA (global_load_lds_dwordx4: no staging registers, no ds_write).  The DMAs are inline asm: hipcc's
 // waitcnt pass would drain a builtin LDS-DMA (vmcnt(0)) in front of the next ds_read; compiler-inserted vmcnt(N) waits stay
 // safe (loads retire in order, extra outstanding requests only make vmcnt(N) stricter).
 // Images (16-B slots): both are sub-tiled [D/32][64 keys][4 slots] so that one DMA piece = 16 keys x 64 B = 1 KiB lands
 // lane-linear; K stores chunk c at slot (c & 3) ^ ((key >> 2) & 3) (conflict-free ds_read_b128 for the 32x32x16 A operand),
 // V stores it at slot c & 3 (ds_read_b64_tr_b16 wants 4 keys x 32 columns contiguous).  The swizzle is applied to the
-// per-lane SOURCE address.
+// per-lane SOURCE address.  KvImage32 below is this image in code; the 16x16x32 bodies have KvImage16 (attn_m16.h).
 // (The earlier schedules of this core — intra-wave pipelining on 8 waves, the four-cluster ping-pong — are in the history of
 //  this file; profiles/r01_ablation.md has their measurements.)
 // =====================================================================================================================
@@ -424,7 +424,78 @@ __device__ __forceinline__ void lds_dma16(unsigned lds, unsigned voff, const voi
     const unsigned lds_u = __builtin_amdgcn_readfirstlane(lds);   // wave-uniform by construction; make it so for the compiler
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_u), "v"(voff), "s"(base) : "memory");
 }
+// One piece of K and the same piece of V, kImg bytes further on, in one asm block (`st` wave-uniform: the caller's
+// readfirstlane): the V request reuses M0 + kImg, each s_nop is the wait state M0 needs after an SALU write; 6 issue slots per
+// tile less than two lds_dma16 calls.  ko / vo: byte offset of the lane's 16 bytes inside the head = row * row stride in bytes
+// (svg_attn_layout_t; 2 D for contiguous heads) + the lane's column.
+template <int kImg>
+__device__ __forceinline__ void lds_dma16_kv(unsigned st, unsigned ko, unsigned vo, const void* kbase, const void* vbase) {
+    asm volatile("s_mov_b32 m0, %0\n\t"
+                 "s_nop 0\n\t"
+                 "global_load_lds_dwordx4 %1, %3\n\t"
+                 "s_add_u32 m0, m0, %5\n\t"
+                 "s_nop 0\n\t"
+                 "global_load_lds_dwordx4 %2, %4"
+                 :
+                 : "s"(st), "v"(ko), "v"(vo), "s"(kbase), "s"(vbase), "n"(kImg)
+                 : "memory", "scc");
+}
+// ds_read_b64_tr_b16 (lds_read_tr16), per group of 16 lanes: element e of lane l is read at the address that lane tr16_src_lane(l, e)
+// supplied, + 2 (l & 3) bytes (lane 4 q + p of the group supplies row q, columns 4 p .. 4 p + 3 of a 4 x 16 block; lane i receives column i)
+constexpr int tr16_src_lane(int lane, int e) { return (lane & ~15) | (4 * e + ((lane & 15) >> 2)); }
+// An image is consistent if every fragment read takes its data from the slot the LDS-DMA put it in.  Write side: slot l (16 bytes) of an image
+// [D/32][64 keys][4 slots] is filled by lane l & 63 of the piece of d-block l >> 8, 16-key group (l >> 6) & 3, with the 16 bytes at column
+// Img::col_k / col_v of the lane's key.  Read side: Img::k_read(key, c) / v_read(key, d): where the lane that needs chunk c / column d reads it.
+template <typename Img, int D>
+constexpr bool kv_image_consistent() {
+    for (int l = 0; l < kBN * D / 8; ++l) {
+        const int j = l >> 8, lane = l & 63, key = (l >> 2) & 63;
+        if (Img::k_read(key, 4 * j + (int)Img::col_k(lane) / 16) != 16 * l) return false;
+        for (int i = 0; i < 8; ++i)
+            if (Img::v_read(key, 32 * j + (int)Img::col_v(lane) / 2 + i) != Img::kImg + 16 * l + 2 * i) return false;
+    }
+    return true;
+}
 
+// The K / V image of the 32x32x16 bodies (attn_body_pp2, attn_body_w4), see "Images" above: the single definition of its write side (the
+// source column a lane hands the LDS-DMA) and its read side (the fragment addresses); the static_assert below ties the two.
+template <int D>
+struct KvImage32 {
+    static constexpr int kImg = kBN * D * 2, kStage = 2 * kImg;   // bytes of a K or V image / of a stage: [K image | V image]
+    static constexpr int col_v(int lane) { return (lane & 3) * 16; }
+    static constexpr unsigned k_xor(int lane) { return (unsigned)(((lane >> 4) & 3) << 4); }
+    static constexpr unsigned col_k(int lane) { return (unsigned)col_v(lane) ^ k_xor(lane); }
+    // read side, lane (g, ql) = (lane >> 5, lane & 31): the lane's part of the K fragment address (even k-steps; odd ones: ^ 32) / the V^T one
+    static constexpr int k_lane0(int g, int ql) { return (ql << 6) | ((g ^ ((ql >> 2) & 3)) << 4); }
+    static constexpr int v_lane_off(int g, int ql) { return kImg + (4 * g + ((ql & 15) >> 2)) * 64 + (16 * (ql >> 4) + 4 * (ql & 3)) * 2; }
+    // Address of the K fragment of 32-key block b, k-step ks (key 32 b + ql, chunk 2 ks + g) / of half h of the V^T fragment of
+    // 16-key step kk, d-block db (column 32 db + ql; element j = 4 h + e: key 16 kk + 8 h + 4 g + e, the key order of the lane's
+    // S^T accumulators).  `st`: the stage, or 0 for the offset; a + chain on the pointer, as the bodies had it (offsets summed
+    // first change attn_body_w4's code).
+    template <typename A>
+    static constexpr A k_at(A st, int k_lane0, int k_lane1, int b, int ks) {
+        return st + ((ks & 1) ? k_lane1 : k_lane0) + (ks >> 1) * (kBN * 64) + b * (32 * 64);
+    }
+    template <typename A>
+    static constexpr A v_at(A st, int v_lane_off, int kk, int db, int h) {
+        return st + v_lane_off + db * (kBN * 64) + (16 * kk + 8 * h) * 64;
+    }
+    template <typename V8>
+    static __device__ __forceinline__ V8 kfrag(const char* st, int k_lane0, int k_lane1, int b, int ks) {
+        return *(const V8*)k_at(st, k_lane0, k_lane1, b, ks);
+    }
+    template <typename V8>
+    static __device__ __forceinline__ V8 vfrag(const char* st, int v_lane_off, int kk, int db) {
+        return __builtin_bit_cast(V8, lds_read_tr16x2(v_at(st, v_lane_off, kk, db, 0), v_at(st, v_lane_off, kk, db, 1)));
+    }
+    static constexpr int k_read(int key, int c) { return k_at(0, k_lane0(c & 1, key & 31), k_lane0(c & 1, key & 31) ^ 32, key >> 5, c >> 1); }
+    static constexpr int v_read(int key, int d) {
+        const int lane = 32 * ((key >> 2) & 1) + (d & 31);
+        return v_at(0, v_lane_off(lane >> 5, tr16_src_lane(lane, key & 3) & 31), key >> 4, d >> 5, (key >> 3) & 1) + 2 * (lane & 3);
+    }
+};
+static_assert(kv_image_consistent<KvImage32<64>, 64>() && kv_image_consistent<KvImage32<128>, 128>(),
+              "KvImage32: DMA columns and fragment reads disagree");
 
 // cycle trace of the two-phase body (diagnostics, -DSVG_ABLATIONS builds): per wave sums of s_memtime ticks per phase of
 // workgroup blockIdx.x == kPpTraceBlock (static: one copy per translation unit, see g_trace_reader below)
@@ -515,9 +586,9 @@ __device__ __forceinline__ void attn_body_pp2(const typename P::Params& prm, cha
     // on for the variable-block policy, off for the band policy.
     constexpr bool kOneBar = P::kOneBarrier && ABL == 0;
     constexpr int kShadow = kMaxFree ? 0 : (D == 64) ? 2 : P::kShadow128;   // 16-key probability steps computed in the shadow of the PV MFMAs (0..3); the rest in the vector phase
+    using Img = KvImage32<D>;               // the K / V image of a stage
     constexpr int NS = 4;                   // LDS stages (LDS-DMA staging)
-    constexpr int kImg = kBN * D * 2;       // bytes of a K or V image
-    constexpr int kStage = 2 * kImg;
+    constexpr int kImg = Img::kImg, kStage = Img::kStage;
     constexpr int NP = DB / 2;              // DMA pieces per wave per tensor per tile
     constexpr float kDefer = 8.f;
     static_assert(D == 64 || D == 128, "head dim");
@@ -542,16 +613,15 @@ __device__ __forceinline__ void attn_body_pp2(const typename P::Params& prm, cha
     const T* __restrict__ vb = P::v_base(prm, ctx);
     const unsigned lds0 = (unsigned)(size_t)smem;
 
-    // ---- DMA bookkeeping (same images as attn_body_pp).  A wave's NP pieces per tensor are the d-blocks dma_db0 .. + NP - 1 of
+    // ---- DMA bookkeeping.  A wave's NP pieces per tensor are the d-blocks dma_db0 .. + NP - 1 of
     //      ONE 16-key group: every lane resolves a single key row per tile (one cursor, one index load) ----
     const int dma_kg = wave / 2;
     const int dma_db0 = (wave % 2) * NP;
     const int krow = 16 * dma_kg + (lane >> 2);
     typename P::KvCursor cur;
     P::kv_cursor_init(prm, ctx, cur, krow);
-    const unsigned col_v = (unsigned)(dma_db0 * 64 + (lane & 3) * 16);
-    const unsigned k_xor = (unsigned)(((lane >> 4) & 3) << 4);
-    const unsigned col_k = col_v ^ k_xor;
+    const unsigned col_v = (unsigned)(dma_db0 * 64 + Img::col_v(lane));
+    const unsigned col_k = col_v ^ Img::k_xor(lane);
     const unsigned k_rsb = (unsigned)P::k_rs(prm) * 2u, v_rsb = (unsigned)P::v_rs(prm) * 2u;
     const unsigned lds_piece = lds0 + (unsigned)(dma_db0 * (kBN * 64) + dma_kg * 1024);
     // Physical rows are resolved one vector phase before they are requested (nnext -> nphys): for the variable-block policy
@@ -565,29 +635,15 @@ __device__ __forceinline__ void attn_body_pp2(const typename P::Params& prm, cha
     };
     constexpr std::true_type kGuarded{};
     auto take = [&]() { nphys = nnext; };
-    // One piece = the K and the V request of d-block dma_db0 + j.  (One asm block per pair: the swizzle XOR of the K source
-    // address doubles as the wait state M0 needs after an SALU write and the V request reuses M0 + kImg: 6 issue slots per
-    // tile less than two independent lds_dma16 calls.)
+    // One piece = the K and the V request of d-block dma_db0 + j (lds_dma16_kv).
     auto dma_piece = [&](int t, auto j_c) {
         constexpr int j = decltype(j_c)::value;
         static_assert(2 * D >= 256 || NP == 1, "row offset | column offset");
         const unsigned st = __builtin_amdgcn_readfirstlane(lds_piece + (unsigned)((t % NS) * kStage) + j * (kBN * 64));
-        // byte offset of the key row inside its head = row * (row stride in bytes, a kernel argument: svg_attn_layout_t — 2 D for contiguous
-        // heads) + the lane's 16-byte column (K: swizzled): one v_mad_u32_u24 per tensor (rows, strides < 2^24, products < 2^32: layout_from_abi)
         const unsigned ko = __umul24((unsigned)nphys, k_rsb) + col_k;
         const unsigned vo = __umul24((unsigned)nphys, v_rsb) + col_v;
         // (the d-block offset goes into the scalar base, loop-invariant — an instruction offset would also move the LDS address)
-        const char* const kbp = (const char*)kb + j * 64;
-        const char* const vbp = (const char*)vb + j * 64;
-        asm volatile("s_mov_b32 m0, %0\n\t"
-                     "s_nop 0\n\t"
-                     "global_load_lds_dwordx4 %1, %3\n\t"
-                     "s_add_u32 m0, m0, %5\n\t"
-                     "s_nop 0\n\t"
-                     "global_load_lds_dwordx4 %2, %4"
-                     :
-                     : "s"(st), "v"(ko), "v"(vo), "s"(kbp), "s"(vbp), "n"(kImg)
-                     : "memory", "scc");
+        lds_dma16_kv<kImg>(st, ko, vo, (const char*)kb + j * 64, (const char*)vb + j * 64);
     };
     auto dma_issue = [&](int t) {  // request this wave's pieces of tile t (t < nT, rows in nphys) into stage t % NS
         dma_piece(t, std::integral_constant<int, 0>{});
@@ -616,10 +672,9 @@ __device__ __forceinline__ void attn_body_pp2(const typename P::Params& prm, cha
         for (int ks = 0; ks < KS; ++ks) qf[ks] = *(const V8*)(qrow + ks * 16);
     }
 
-    const int k_lane0 = ql * 64 + (((g) ^ ((ql >> 2) & 3)) << 4);   // even k-steps
-    const int k_lane1 = k_lane0 ^ 32;                               // odd k-steps
-    const int vi = lane & 15;
-    const int v_lane_off = kImg + (4 * g + (vi >> 2)) * 64 + (16 * ((lane >> 4) & 1) + 4 * (vi & 3)) * 2;
+    const int k_lane0 = Img::k_lane0(g, ql);   // even k-steps
+    const int k_lane1 = k_lane0 ^ 32;          // odd k-steps
+    const int v_lane_off = Img::v_lane_off(g, ql);
 
     int m_a0 = 0, m_b0 = 0;
     unsigned m_alen = 0, m_blen = 0;
@@ -663,16 +718,8 @@ __device__ __forceinline__ void attn_body_pp2(const typename P::Params& prm, cha
     float psum_thr = -1.f;        // (wave-uniform) max-free softmax: 2048 once every row of the wave has a finite reference; until
                                   // then no sum passes the check and every tile takes the exact path
 
-    auto kfrag = [&](const char* st, int b, int ks) -> V8 {
-        return *(const V8*)(st + ((ks & 1) ? k_lane1 : k_lane0) + (ks >> 1) * (kBN * 64) + b * (32 * 64));
-    };
-    auto vfrag = [&](const char* st, int kk, int db) -> V8 {
-        const char* vbase = st + v_lane_off;
-        const i16x4 lo = lds_read_tr16(vbase + db * (kBN * 64) + (16 * kk) * 64);
-        const i16x4 hi = lds_read_tr16(vbase + db * (kBN * 64) + (16 * kk + 8) * 64);
-        i16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(V8, both);
-    };
+    auto kfrag = [&](const char* st, int b, int ks) -> V8 { return Img::template kfrag<V8>(st, k_lane0, k_lane1, b, ks); };
+    auto vfrag = [&](const char* st, int kk, int db) -> V8 { return Img::template vfrag<V8>(st, v_lane_off, kk, db); };
     // probabilities of keys 16 kk + [lo, hi) of the tile in sc
     // (scalar f32 on purpose: the packed forms v_pk_fma_f32 / v_pk_add_f32 measured 48.2 ms vs 42.3 ms here)
     float pre_shift = 0.f;   // PRE, exact path only: old reference minus new reference (the scores in sc are relative to the old one)

@@ -39,7 +39,7 @@ inline int check_band_mask(int S, const svg_band_mask_t* mask, const svg_perm_de
 // Band policy: analytic mask family (see svg_band_mask_t in svg_attn.h)
 // =====================================================================================================
 template <typename T, int D, int NW, int RB = 1>
-struct BandPolicy {
+struct BandPolicy : LayoutAccess<BandPolicy<T, D, NW, RB>> {
     static constexpr int kHeadDim = D;
     static constexpr bool kFixup = false;
     static constexpr bool kPartialOut = false;
@@ -201,16 +201,6 @@ struct BandPolicy {
         c.seg_lo[2] = clo, c.seg_n[2] = chi - clo;
         c.nT = c.seg_n[0] + c.seg_n[1] + c.seg_n[2];
     }
-
-    static __device__ __forceinline__ const T* q_base(const Params& p, const Ctx& c) { return p.q + layout_head_off(p.lay.q_bs, p.lay.q_hs, p.lay.hpb_q, c.head); }
-    static __device__ __forceinline__ const T* k_base(const Params& p, const Ctx& c) { return p.k + layout_head_off(p.lay.k_bs, p.lay.k_hs, p.lay.hpb_kv, c.head); }
-    static __device__ __forceinline__ const T* v_base(const Params& p, const Ctx& c) { return p.v + layout_head_off(p.lay.v_bs, p.lay.v_hs, p.lay.hpb_kv, c.head); }
-    static __device__ __forceinline__ T* o_base(const Params& p, const Ctx& c) { return p.o + layout_head_off(p.lay.o_bs, p.lay.o_hs, p.lay.hpb_q, c.head); }
-    // row strides in elements (attn_m16.h; every other body addresses rows at stride D and the host refuses anything else for it)
-    static __device__ __forceinline__ int q_rs(const Params& p) { return p.lay.q_rs; }
-    static __device__ __forceinline__ int k_rs(const Params& p) { return p.lay.k_rs; }
-    static __device__ __forceinline__ int v_rs(const Params& p) { return p.lay.v_rs; }
-    static __device__ __forceinline__ int o_rs(const Params& p) { return p.lay.o_rs; }
 
     static __device__ __forceinline__ int q_logical(const Ctx& c, int row) { return c.q0 + row; }
     static __device__ __forceinline__ bool wave_active(const Ctx& c, int wrow0) { return c.q0 + wrow0 < c.q_end; }

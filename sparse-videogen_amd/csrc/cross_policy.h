@@ -26,7 +26,7 @@ struct CrossWindowCtx<true> {
 };
 
 template <typename T, bool Windowed = false>
-struct CrossPolicy {
+struct CrossPolicy : LayoutAccess<CrossPolicy<T, Windowed>> {
     static constexpr int kHeadDim = 128;
     static constexpr bool kFixup = false;
     static constexpr bool kPartialOut = false;
@@ -68,15 +68,6 @@ struct CrossPolicy {
             c.nT = (p.Skv + kBN - 1) / kBN;
         }
     }
-
-    static __device__ __forceinline__ const T* q_base(const Params& p, const Ctx& c) { return p.q + layout_head_off(p.lay.q_bs, p.lay.q_hs, p.lay.hpb_q, c.head); }
-    static __device__ __forceinline__ const T* k_base(const Params& p, const Ctx& c) { return p.k + layout_head_off(p.lay.k_bs, p.lay.k_hs, p.lay.hpb_kv, c.head); }
-    static __device__ __forceinline__ const T* v_base(const Params& p, const Ctx& c) { return p.v + layout_head_off(p.lay.v_bs, p.lay.v_hs, p.lay.hpb_kv, c.head); }
-    static __device__ __forceinline__ T* o_base(const Params& p, const Ctx& c) { return p.o + layout_head_off(p.lay.o_bs, p.lay.o_hs, p.lay.hpb_q, c.head); }
-    static __device__ __forceinline__ int q_rs(const Params& p) { return p.lay.q_rs; }
-    static __device__ __forceinline__ int k_rs(const Params& p) { return p.lay.k_rs; }
-    static __device__ __forceinline__ int v_rs(const Params& p) { return p.lay.v_rs; }
-    static __device__ __forceinline__ int o_rs(const Params& p) { return p.lay.o_rs; }
 
     static __device__ __forceinline__ int q_logical(const Ctx& c, int row) { return c.q0 + row; }
     static __device__ __forceinline__ bool wave_active(const Ctx& c, int wrow0) { return c.q0 + wrow0 < c.q_end; }

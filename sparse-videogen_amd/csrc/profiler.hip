@@ -34,9 +34,9 @@ constexpr int kProfMaxRows = 64;
 constexpr int kProfRoleRows = 3 * kProfMaxRows;   // workgroup rows [64 v, 64 v + 64) belong to role v
 
 template <typename T, int D>
-struct ProfilePolicy {
+struct ProfilePolicy : LayoutAccess<ProfilePolicy<T, D>> {
     static constexpr bool kFixup = true;
-    static constexpr bool kPartialOut = true;
+    static constexpr bool kPartialOut = true;      // (store_partial; Params has no o: the inherited o_base / o_rs are never instantiated)
     static constexpr bool kIntervalMask = false;
     static constexpr int kShadow128 = 1;
     static constexpr bool kFastPartial = true;     // token-major mask: tiles inside one frame row block, see classify()   // the profiling masks are general element predicates (allowed())
@@ -136,9 +136,6 @@ struct ProfilePolicy {
         }
         return true;
     }
-    static __device__ __forceinline__ const T* q_base(const Params& p, const Ctx& c) { return p.q + layout_head_off(p.lay.q_bs, p.lay.q_hs, p.lay.hpb_q, c.head); }
-    static __device__ __forceinline__ const T* k_base(const Params& p, const Ctx& c) { return p.k + layout_head_off(p.lay.k_bs, p.lay.k_hs, p.lay.hpb_kv, c.head); }
-    static __device__ __forceinline__ const T* v_base(const Params& p, const Ctx& c) { return p.v + layout_head_off(p.lay.v_bs, p.lay.v_hs, p.lay.hpb_kv, c.head); }
 
     // workgroup row -> sampled row of its role
     static __device__ __forceinline__ bool exists(const Params& p, int row) {
@@ -244,7 +241,6 @@ struct ProfilePolicy {
             dst[D + 1] = l;
         }
     }
-    static __device__ __forceinline__ T* o_base(const Params&, const Ctx&) { return nullptr; }
     static __device__ __forceinline__ void notify(const Params&, const Ctx&) {}
 };
 
@@ -323,7 +319,8 @@ __global__ __launch_bounds__(256, 2) void profile16_kernel(typename ProfilePolic
     using M = Mfma16<T>;
     using V8 = typename E::v8;
     constexpr int KS = D / 32, NDB = D / 16;
-    constexpr int kImg = kBN * D * 2, kStage = 2 * kImg;
+    using Img = KvImage16<D>;
+    constexpr int kImg = Img::kImg, kStage = Img::kStage;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (prm.skip && prm.skip[0] != 0) return;
 #ifdef SVG_PROF_TRACE
@@ -339,9 +336,9 @@ __global__ __launch_bounds__(256, 2) void profile16_kernel(typename ProfilePolic
     const int ntiles = (prm.S + kBN - 1) / kBN;
     const int t0 = chunk * prm.tiles_per_chunk;
     const int nT = max(0, min(prm.tiles_per_chunk, ntiles - t0));
-    const T* __restrict__ qb = prm.q + layout_head_off(prm.lay.q_bs, prm.lay.q_hs, prm.lay.hpb_q, head);
-    const T* __restrict__ kb_ = prm.k + layout_head_off(prm.lay.k_bs, prm.lay.k_hs, prm.lay.hpb_kv, head);
-    const T* __restrict__ vb = prm.v + layout_head_off(prm.lay.v_bs, prm.lay.v_hs, prm.lay.hpb_kv, head);
+    const T* __restrict__ qb = Pol::q_at(prm, head);
+    const T* __restrict__ kb_ = Pol::k_at(prm, head);
+    const T* __restrict__ vb = Pol::v_at(prm, head);
 
     // The sampled rows in the order of their coordinate under the second mask (token-major in every model of the reference).  The squared
     // errors are summed over the rows: their order is free.  Rank by counting, through LDS.
@@ -364,7 +361,7 @@ __global__ __launch_bounds__(256, 2) void profile16_kernel(typename ProfilePolic
     __syncthreads();    // (the staging below reuses the bytes)
     V8 qf[KS];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) qf[ks] = *(const V8*)(qb + (size_t)qrow * prm.lay.q_rs + ks * 32 + g4 * 8);
+    for (int ks = 0; ks < KS; ++ks) qf[ks] = *(const V8*)(qb + (size_t)qrow * Pol::q_rs(prm) + ks * 32 + g4 * 8);
 
     // the two masks' per-lane / per-wave state, as ProfilePolicy::init computes it (output 1 <- var[0], output 2 <- var[1])
     typename Pol::Ctx mc[2];
@@ -399,41 +396,25 @@ __global__ __launch_bounds__(256, 2) void profile16_kernel(typename ProfilePolic
 
     // ---- LDS-DMA staging: wave w moves key group w (16 keys) of a tile, every 64-byte d-block, K and V ----
     const unsigned lds0 = (unsigned)(size_t)smem;
-    const unsigned vsw = (unsigned)((lane >> 4) & 1) << 1;
-    const unsigned col_v = ((lane & 3) ^ vsw) * 16u;
+    const unsigned col_v = Img::col_v(lane);
     const int krow = 16 * wave + (lane >> 2);
-    const unsigned k_rsb = (unsigned)prm.lay.k_rs * 2u, v_rsb = (unsigned)prm.lay.v_rs * 2u;
+    const unsigned k_rsb = (unsigned)Pol::k_rs(prm) * 2u, v_rsb = (unsigned)Pol::v_rs(prm) * 2u;
     auto dma_tile = [&](int t) {
         const int l = (t0 + t) * kBN + krow;
         const unsigned nphys = (unsigned)(l < prm.S ? l : 0);    // rows behind the sequence: masked below (the last tile is never FULL)
 #pragma unroll
         for (int j = 0; j < D / 32; ++j) {
             const unsigned st = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)((t & 1) * kStage) + (unsigned)(j * (kBN * 64) + wave * 1024));
-            // row * (row stride in bytes, a kernel argument: svg_attn_layout_t) + the d-block + the lane's 16-byte column
             const unsigned ko = __umul24(nphys, k_rsb) + ((unsigned)(j * 64) | col_v);
             const unsigned vo = __umul24(nphys, v_rsb) + ((unsigned)(j * 64) | col_v);
-            asm volatile("s_mov_b32 m0, %0\n\t"
-                         "s_nop 0\n\t"
-                         "global_load_lds_dwordx4 %1, %3\n\t"
-                         "s_add_u32 m0, m0, %5\n\t"
-                         "s_nop 0\n\t"
-                         "global_load_lds_dwordx4 %2, %4"
-                         :
-                         : "s"(st), "v"(ko), "v"(vo), "s"(kb_), "s"(vb), "n"(kImg)
-                         : "memory", "scc");
+            lds_dma16_kv<kImg>(st, ko, vo, kb_, vb);
         }
     };
-    const int k_lane = n16 * 64 + ((g4 ^ (((n16 >> 2) & 1) << 1)) << 4);
-    const int v_lane0 = kImg + (4 * g4 + (n16 >> 2)) * 64 + (((g4 & 1) * 16) + 4 * (n16 & 3)) * 2;
+    const int k_lane = Img::k_lane(g4, n16);
+    const int v_lane0 = Img::v_lane0(g4, n16);
     const int v_lane1 = v_lane0 ^ 32;
-    auto kfrag = [&](const char* st, int kblk, int ks) -> V8 { return *(const V8*)(st + k_lane + ks * (kBN * 64) + kblk * 1024); };
-    auto vfrag = [&](const char* st, int kc, int db) -> V8 {
-        const char* vbase = st + ((db & 1) ? v_lane1 : v_lane0) + (db >> 1) * (kBN * 64) + (32 * kc) * 64;
-        const i16x4 lo = lds_read_tr16(vbase);
-        const i16x4 hi = lds_read_tr16(vbase + 16 * 64);
-        const i16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(V8, both);
-    };
+    auto kfrag = [&](const char* st, int kblk, int ks) -> V8 { return __builtin_bit_cast(V8, Img::kfrag(st, k_lane, kblk, ks)); };
+    auto vfrag = [&](const char* st, int kc, int db) -> V8 { return __builtin_bit_cast(V8, Img::vfrag(st, v_lane0, v_lane1, kc, db)); };
 
     // ---- the wave's class table: { class under mask 0, first coordinate, class under mask 1, first coordinate } per tile of the window ----
     int* const tab = (int*)(smem + 2 * kStage) + wave * (kP16Win * 4);

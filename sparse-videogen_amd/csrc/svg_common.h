@@ -200,4 +200,37 @@ __device__ __forceinline__ size_t layout_head_off(long long bs, long long hs, in
     return (size_t)b * (size_t)bs + (size_t)(head - b * hpb) * (size_t)hs;
 }
 
+// Layout access of the attention policies (AttnLayout above), from Params { q, k, v, o, lay }: the tensor base of head h (x_at) or of the
+// head a policy's Ctx means (x_base: ctx.head, unless the policy — deriving from LayoutAccess<itself> — has its own q_head / kv_head), x_rs.
+template <typename P>
+struct LayoutAccess {
+    template <typename Ctx>
+    static __device__ __forceinline__ int q_head(const Ctx& c) { return c.head; }
+    template <typename Ctx>
+    static __device__ __forceinline__ int kv_head(const Ctx& c) { return c.head; }
+    template <typename Prm>
+    static __device__ __forceinline__ auto q_at(const Prm& p, int h) { return p.q + layout_head_off(p.lay.q_bs, p.lay.q_hs, p.lay.hpb_q, h); }
+    template <typename Prm>
+    static __device__ __forceinline__ auto k_at(const Prm& p, int h) { return p.k + layout_head_off(p.lay.k_bs, p.lay.k_hs, p.lay.hpb_kv, h); }
+    template <typename Prm>
+    static __device__ __forceinline__ auto v_at(const Prm& p, int h) { return p.v + layout_head_off(p.lay.v_bs, p.lay.v_hs, p.lay.hpb_kv, h); }
+    template <typename Prm>
+    static __device__ __forceinline__ auto o_at(const Prm& p, int h) { return p.o + layout_head_off(p.lay.o_bs, p.lay.o_hs, p.lay.hpb_q, h); }
+    template <typename Prm, typename Ctx>
+    static __device__ __forceinline__ auto q_base(const Prm& p, const Ctx& c) { return q_at(p, P::q_head(c)); }
+    template <typename Prm, typename Ctx>
+    static __device__ __forceinline__ auto k_base(const Prm& p, const Ctx& c) { return k_at(p, P::kv_head(c)); }
+    template <typename Prm, typename Ctx>
+    static __device__ __forceinline__ auto v_base(const Prm& p, const Ctx& c) { return v_at(p, P::kv_head(c)); }
+    template <typename Prm, typename Ctx>
+    static __device__ __forceinline__ auto o_base(const Prm& p, const Ctx& c) { return o_at(p, P::q_head(c)); }
+    template <typename Prm>
+    static __device__ __forceinline__ int q_rs(const Prm& p) { return p.lay.q_rs; }
+    template <typename Prm>
+    static __device__ __forceinline__ int k_rs(const Prm& p) { return p.lay.k_rs; }
+    template <typename Prm>
+    static __device__ __forceinline__ int v_rs(const Prm& p) { return p.lay.v_rs; }
+    template <typename Prm>
+    static __device__ __forceinline__ int o_rs(const Prm& p) { return p.lay.o_rs; }
+};
 }  // namespace svg

@@ -15,7 +15,7 @@ constexpr int kVbMaxKB = 4032;   // the run list of a block-row ((KB rounded up 
 constexpr int kVbFull = 256;   // mixed tiling: full 256-row tiles go to the 8-wave kernel, the rest of a block-row to 128-row tiles
 
 template <typename T, int D, int NW>
-struct VarblockPolicy {
+struct VarblockPolicy : LayoutAccess<VarblockPolicy<T, D, NW>> {
     static constexpr bool kFixup = false;
     static constexpr bool kPartialOut = false;
     static constexpr bool kIntervalMask = true;
@@ -172,14 +172,8 @@ struct VarblockPolicy {
         return true;
     }
 
-    static __device__ __forceinline__ const T* q_base(const Params& p, const Ctx& c) { return p.q + layout_head_off(p.lay.q_bs, p.lay.q_hs, p.lay.hpb_q, c.hq); }
-    static __device__ __forceinline__ const T* k_base(const Params& p, const Ctx& c) { return p.k + layout_head_off(p.lay.k_bs, p.lay.k_hs, p.lay.hpb_kv, c.hkv); }
-    static __device__ __forceinline__ const T* v_base(const Params& p, const Ctx& c) { return p.v + layout_head_off(p.lay.v_bs, p.lay.v_hs, p.lay.hpb_kv, c.hkv); }
-    static __device__ __forceinline__ T* o_base(const Params& p, const Ctx& c) { return p.o + layout_head_off(p.lay.o_bs, p.lay.o_hs, p.lay.hpb_q, c.hq); }
-    static __device__ __forceinline__ int q_rs(const Params& p) { return p.lay.q_rs; }   // row strides in elements (attn_m16.h only, see BandPolicy)
-    static __device__ __forceinline__ int k_rs(const Params& p) { return p.lay.k_rs; }
-    static __device__ __forceinline__ int v_rs(const Params& p) { return p.lay.v_rs; }
-    static __device__ __forceinline__ int o_rs(const Params& p) { return p.lay.o_rs; }
+    static __device__ __forceinline__ int q_head(const Ctx& c) { return c.hq; }    // LayoutAccess: q_base .. o_base, q_rs .. o_rs
+    static __device__ __forceinline__ int kv_head(const Ctx& c) { return c.hkv; }
 
     // (the "logical" index of a query row is its row inside the tile here: all the mask needs is which member it belongs to)
     static __device__ __forceinline__ int q_logical(const Ctx&, int row) { return row; }
