@@ -147,8 +147,9 @@ __device__ __forceinline__ u32x2 add_rounded16(u32x2 a, u32x2 b) {
 // !(|x| < 2^120), the wave votes, lane 0 of a wave that saw one sets a word in LDS behind the stages (smem + attn_m16_lds_bytes() + 8:
 // the launch provides 16 bytes there, the caller zeroes the word before the first pass and no pass with check_mask = 0 touches it),
 // ONE workgroup barrier follows that every wave passes, idle waves included, and a non-zero word
-// makes every wave return true without storing anything: the caller then runs the same q-tile once more with check_mask = 0 — the test
-// on every tile, the body without SPEC tile for tile, no validation — and that pass stores.  At most one replay per q-tile, no waiting
+// makes every wave return true without storing anything (a check point that is about to rescale a large sum by a factor that has
+// underflowed to zero makes the sum infinite instead, so that it fails here — see the exact path): the caller then runs the same
+// q-tile once more with check_mask = 0 — the test on every tile, the body without SPEC tile for tile, no validation — and that pass stores.  At most one replay per q-tile, no waiting
 // on another workgroup; the stages are quiescent at the barrier as they are between two q-tiles of a queue kernel, and no epilogue has
 // read them, so the second pass needs no further barrier in front.  `replay_ctr` (or nullptr) counts replayed q-tiles
 // (svg_debug_band_replays).  Without SPEC the function returns false.
@@ -409,6 +410,14 @@ __device__ __forceinline__ bool attn_m16_tile(const typename P::Params& prm, con
                 m_sub[rb] = m_use[rb] + kBias;
                 float a = __builtin_amdgcn_exp2f(fminf(m_prev - m_use[rb], 126.f));
                 asm volatile("s_nop 1" : "+v"(a));  // v_exp_f32 -> inline-asm consumer: hipcc does not insert the wait state
+                // SPEC, first pass: between two check points a sum may grow to 2^120 under a reference that lags, and a new reference
+                // 126 or more above the old one makes `a` zero (v_exp_f32 flushes): the rescale would wipe a sum that is NOT negligible
+                // beside the new tile's probabilities, the sums would look valid after the loop, and the row would lose keys.  (With the test
+                // on every tile a sum stays below 2^7 per tile, and what a zero `a` drops is below 2^-100 of the row.)  A sum of 2^64 and more
+                // under a reference that rises by more than 120 is rescaled by infinity instead: the validation then sees the row and the
+                // q-tile is replayed.  Below 2^64 the dropped part is under 2^-52 of the new tile's largest probability (2^-10).
+                // (No pass with the test on every tile holds such a sum, so the replay needs no exemption.)
+                if constexpr (kSpec) a = (m_prev - m_use[rb] < -120.f && !(fabsf(acc_l[rb][0]) < 0x1p64f)) ? INFINITY : a;
                 alpha[rb] = a;
                 m_run[rb] = m_new;
                 all_finite = all_finite && (m_new != -INFINITY);

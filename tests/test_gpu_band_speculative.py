@@ -14,7 +14,6 @@ are zero except for the spikes: spike i lives in dimension 118 + i alone (one qu
 Every launch case runs on the static mapping (14 work items: one workgroup per q-tile, band_attn_m16_kernel) and through the work queue
 (band_attn_m16_queue_kernel, svg_debug_band_queue_cap as in tests/test_gpu_band_queue.py): the two kernels replay by different means.
 Nothing here provokes a fault: an overflow is an arithmetic infinity inside fp32 registers."""
-import math
 from pathlib import Path
 
 import numpy as np
@@ -23,49 +22,19 @@ import torch
 
 from oracle import svg_oracle as O
 from svg import _native as nat
+from band_replay_cases import BEST, GEO_A, SPIKE_DIM0, bool_mask, build, q_tiles_of, reference, replay_everywhere_spikes  # noqa: F401
 from test_gpu_kernels import check_attn
 
 pytestmark = pytest.mark.gpu
 
-D, H, F_, P_, CTX, L, BAND = 128, 2, 2, 640, 64, 40, 512
-V = F_ * P_
-S = V + CTX                      # 1344 = 21 key tiles
-REAL = V + L
-BEST = torch.tensor([[0, 1]])    # head 0 contiguous, head 1 token-major
-SPIKE_DIM0 = 118
+D, H, F_, P_, CTX, L, BAND = GEO_A
+V, S, REAL = GEO_A.V, GEO_A.S, GEO_A.REAL     # S = 1344 = 21 key tiles
 NO_CAP = 1 << 20
 GOLDEN = Path(__file__).resolve().parent / "golden" / "band_replay_golden.npz"
 
 
 def mask_params(kind):
-    if kind == "dense":
-        return O.dense_band_params(S)
-    return dict(real_len=REAL, band=BAND, colfull_lo=V, colfull_hi=REAL, rowfull_lo=V, rowfull_hi=REAL)
-
-
-_MASKS = {}
-
-
-def bool_mask(kind):
-    if kind not in _MASKS:
-        _MASKS[kind] = O.band_mask(S, **mask_params(kind))
-    return _MASKS[kind]
-
-
-def build(kind, spikes, seed):
-    """spikes: per head the same list of (query row, key row, mag) in logical order -> logical q, k, v (bf16, CPU)"""
-    g = torch.Generator().manual_seed(seed)
-    q, k, v = (torch.randn(1, H, S, D, generator=g) for _ in range(3))
-    q[..., SPIKE_DIM0:] = 0
-    k[..., SPIKE_DIM0:] = 0
-    assert len(spikes) <= D - SPIKE_DIM0
-    allowed = bool_mask(kind)
-    c = (1.0 / math.sqrt(D)) * math.log2(math.e)
-    for i, (row, key, mag) in enumerate(spikes):
-        assert allowed[row, key], (row, key)
-        q[0, :, row, SPIKE_DIM0 + i] = 4.0
-        k[0, :, key, SPIKE_DIM0 + i] = mag / (4.0 * c)
-    return tuple(x.to(torch.bfloat16) for x in (q, k, v))
+    return GEO_A.mask_params(kind)
 
 
 def launch(kind, q, k, v, path, done=None):
@@ -87,17 +56,6 @@ def launch(kind, q, k, v, path, done=None):
     return O.head_placement(out.cpu(), BEST, CTX, F_, P_)
 
 
-_REFS = {}
-
-
-def reference(kind, spikes, seed):
-    key = (kind, tuple(spikes), seed)
-    if key not in _REFS:
-        q, k, v = build(kind, spikes, seed)
-        _REFS[key] = O.masked_attention(q, k, v, bool_mask(kind))
-    return _REFS[key]
-
-
 def run_checked(kind, spikes, seed, path):
     """-> (logical output, replays of the launch); the output is checked against the oracle"""
     q, k, v = build(kind, spikes, seed)
@@ -108,16 +66,6 @@ def run_checked(kind, spikes, seed, path):
     check_attn(o, reference(kind, spikes, seed), torch.bfloat16)
     print(f"{kind} {path} spikes={len(spikes)} replays={n}")
     return o, n
-
-
-def q_tiles_of(kind, rows):
-    """q-tiles (256 rows, cut at the row regions of the mask) that contain one of `rows`"""
-    cuts = [0, S] if kind == "dense" else [0, V, REAL, S]
-    tiles = set()
-    for r in rows:
-        reg = max(i for i, c in enumerate(cuts[:-1]) if r >= c)
-        tiles.add((reg, (r - cuts[reg]) // 256))
-    return len(tiles)
 
 
 # Late spikes: key tile index 1 (just after a check), 7 (just before one), 8 (on one), 9 and the last tile of the q-tile, for a row of
@@ -193,14 +141,6 @@ def test_two_launches_are_equal(path):
     a, na = run_checked("band", sp, 2, path)
     b, nb = run_checked("band", sp, 2, path)
     assert torch.equal(a, b) and na == nb
-
-
-def replay_everywhere_spikes():
-    """one +400 spike in every q-tile of real rows, off the check points (key tile index 3 of the band q-tiles 0 .. 4, whose
-    schedules start at key tile max(0, 256 j - 511) // 64; index 5 of the text q-tile): each of them is replayed"""
-    sp = [(256 * j + 40, (max(0, 256 * j - 511) // 64 + 3) * 64 + 5, 400.0) for j in range(5)]
-    sp.append((V + 3, 64 * 5 + 1, 400.0))
-    return sp
 
 
 @pytest.mark.parametrize("path", PATHS)
