@@ -416,6 +416,10 @@ int svg_map_density(const uint8_t* block_map, const int32_t* q_sizes, const int3
  *   rope cos/sin ("interleaved pairs"): out = T(x * cos + rotate(x) * sin) in fp32, rotate(x)[2i] = -x[2i+1],
  *               rotate(x)[2i+1] = x[2i]; cos, sin: [S - len_text_prompt, D]
  *   rope complex: (x[2i] + i x[2i+1]) * (real + i imag) in fp64; real, imag: [S - len_text_prompt, D / 2]
+ *   rope half-split (rope_kind 3 of the fused entry points below; diffusers apply_rotary_emb(use_real_unbind_dim=-2), ref:
+ *               svg/models/cosmos/attention.py:61-66): channel i pairs with i + D/2.  out = T(x * cos + rotate(x) * sin) in fp32, every
+ *               product rounded before the add, rotate(x)[i] = -x[i + D/2], rotate(x)[i + D/2] = x[i] for i < D/2; cos, sin:
+ *               [rope_hi - rope_lo, D], ALL D columns are read (cos[:, i] need not equal cos[:, i + D/2])
  *   the first (`cossin`, `complex`) or the last (`txtlast`) len_text_prompt positions are left untouched.
  * ---------------------------------------------------------------------------------------------- */
 int svg_rms_norm_forward(void* x, const void* weight, int64_t m, int32_t n, int32_t dtype, float eps, void* stream);
@@ -431,8 +435,12 @@ int svg_apply_qk_rope_inplace_cossin_complex(void* q, void* k, const float* freq
                                              int32_t bsz, int32_t Hq, int32_t Hkv, int32_t S, int32_t D, int32_t dtype,
                                              int32_t len_text_prompt, void* stream);
 /* Fused form: normalisation (norm_kind 0 none / 1 rms / 2 layer) followed by rotary embedding (rope_kind 0 none / 1 cos-sin /
- * 2 complex) of positions [rope_lo, rope_hi) with table row (position - rope_lo), ONE pass over q and k (either may be NULL).
- * Bit-identical to the corresponding sequence of the entry points above (the intermediate rounding is kept). */
+ * 2 complex / 3 half-split) of positions [rope_lo, rope_hi) with table row (position - rope_lo), ONE pass over q and k (either may be
+ * NULL).  Bit-identical to the corresponding sequence of the entry points above (the intermediate rounding is kept); kind 3 is
+ * bit-identical to the norm followed by torch's `(x.float() * cos + rotate(x).float() * sin).to(T)`.
+ * rope_kind 3 exists on svg_qk_norm_rope, svg_qk_norm_rope_transpose and their _qscale forms only: svg_qk_norm_rope_transpose_joint and
+ * svg_rmsnorm_rope_transpose return SVG_ERR_BAD_ARG for it.  SVG_ERR_BAD_ARG: a norm kind outside 0..2, a rope kind outside 0..3, a rope
+ * kind != 0 with a NULL table or a range outside [0, S]; SVG_ERR_UNSUPPORTED: D outside {32, 64, 128, 256} — decided before any launch. */
 int svg_qk_norm_rope(void* q, void* k, int32_t bsz, int32_t Hq, int32_t Hkv, int32_t S, int32_t D, int32_t dtype,
                      int32_t norm_kind, const void* q_weight, const void* q_bias, const void* k_weight, const void* k_bias,
                      float eps, int32_t rope_kind, const float* cos_or_real, const float* sin_or_imag, int32_t rope_lo,

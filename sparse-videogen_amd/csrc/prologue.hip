@@ -14,7 +14,7 @@
 namespace svg {
 
 enum : int { kNormNone = 0, kNormRms = 1, kNormLayer = 2 };
-enum : int { kRopeNone = 0, kRopeCosSin = 1, kRopeComplex = 2 };
+enum : int { kRopeNone = 0, kRopeCosSin = 1, kRopeComplex = 2, kRopeHalf = 3 };
 
 struct PrologueParams {
     void* q;
@@ -28,7 +28,7 @@ struct PrologueParams {
     const void* kw;
     const void* kb;
     float eps;
-    const float* cs;  // cos [rope_hi - rope_lo, D]   (complex: real part [.., D/2])
+    const float* cs;  // cos [rope_hi - rope_lo, D]   (complex: real part [.., D/2]; half-split: all D columns are read)
     const float* sn;  // sin                           (complex: imaginary part)
     int rope_lo, rope_hi;  // positions [rope_lo, rope_hi) are rotated with table row (pos - rope_lo)
     float q_scale;         // factor folded into the LAST rounding of q (1: none; an exact no-op then).  The attention kernels take a q
@@ -136,7 +136,12 @@ __device__ __forceinline__ void load_rope_row(bool rot, int rope, const float* t
 
 // One lane = 8 consecutive channels of one (batch, head, position) row; a wave covers 64 / (D / 8) consecutive positions;
 // the workgroup (4 waves) walks over all heads of Q and then of K for its positions, kUnroll rows in flight per lane.
-template <typename T, int D>
+// HALF (p.rope == kRopeHalf, the only kind that variant is launched for): half-split RoPE, channel i rotates against i + D / 2 (diffusers
+// apply_rotary_emb(use_real_unbind_dim=-2), ref: svg/models/cosmos/attention.py:61-66).  The partner channels of lane c are the 8 registers of
+// lane c ^ (LPR / 2) of the same row: one __shfl_xor per register behind the norm — by every lane of the wave, rotated position or not — and
+// then out = x * cos + (lower half: -partner, upper half: partner) * sin with the lane's own D-column table entries.  HALF = false is the
+// kernel of kinds 0 - 2, statement for statement what it was before the flag: its listings did not change.
+template <typename T, int D, bool HALF>
 __global__ __launch_bounds__(256) void qk_prologue_kernel(PrologueParams p) {
     using E = Elt<T>;
     using V8 = typename E::v8;
@@ -156,7 +161,7 @@ __global__ __launch_bounds__(256) void qk_prologue_kernel(PrologueParams p) {
     for (int j = 0; j < 8; ++j) cs[j] = 1.f, sn[j] = 0.f;
     if (rot) {
         const size_t r = (size_t)(pos - p.rope_lo);
-        if (p.rope == kRopeCosSin) {
+        if (HALF || p.rope == kRopeCosSin) {
             const f32x4* pc = (const f32x4*)(p.cs + r * D + c * 8);
             const f32x4* ps = (const f32x4*)(p.sn + r * D + c * 8);
             const f32x4 c0 = pc[0], c1 = pc[1], s0 = ps[0], s1 = ps[1];
@@ -228,7 +233,22 @@ __global__ __launch_bounds__(256) void qk_prologue_kernel(PrologueParams p) {
                     for (int j = 0; j < 8; ++j) x[j] = E::to_float(E::from_float((x[j] - mean) * inv * w[j] + bs[j]));
                 }
                 V8 out;
-                if (rot && p.rope == kRopeCosSin) {
+                if constexpr (HALF) {
+                    // rotate(x)[i] = -x[i + D/2], rotate(x)[i + D/2] = x[i]: the partner lane's registers, fetched by all 64 lanes
+                    float xr[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const float xp = __shfl_xor(x[j], LPR / 2);
+                        xr[j] = c < LPR / 2 ? -xp : xp;
+                    }
+                    if (rot) {
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) out[j] = scaled_round<E>(x[j] * cs[j] + xr[j] * sn[j], oscale);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) out[j] = scaled_round<E>(x[j], oscale);
+                    }
+                } else if (rot && p.rope == kRopeCosSin) {
                     // out = x * cos + rotate(x) * sin in fp32, rotate(x)[2i] = -x[2i+1], rotate(x)[2i+1] = x[2i]
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
@@ -262,7 +282,11 @@ static int launch_prologue_t(const PrologueParams& p, int bsz, int D, hipStream_
     auto go = [&](auto d_c) -> int {
         constexpr int DD = decltype(d_c)::value;
         constexpr int RPB = 4 * (64 / (DD / 8));
-        hipLaunchKernelGGL((qk_prologue_kernel<T, DD>), dim3((p.S + RPB - 1) / RPB, bsz), dim3(256), 0, st, p);
+        const dim3 grid((p.S + RPB - 1) / RPB, bsz);
+        if (p.rope == kRopeHalf)
+            hipLaunchKernelGGL((qk_prologue_kernel<T, DD, true>), grid, dim3(256), 0, st, p);
+        else
+            hipLaunchKernelGGL((qk_prologue_kernel<T, DD, false>), grid, dim3(256), 0, st, p);
         return launch_status();
     };
     switch (D) {
@@ -615,7 +639,7 @@ extern "C" int svg_qk_norm_rope_qscale(void* q, void* k, int32_t bsz, int32_t Hq
                                        const float* sin_or_imag, int32_t rope_lo, int32_t rope_hi, float q_scale, void* stream) {
     if (!(q_scale > 0.f)) return SVG_ERR_BAD_ARG;
     if ((!q && !k) || (q && Hq <= 0) || (k && Hkv <= 0)) return SVG_ERR_BAD_ARG;
-    if (norm_kind < 0 || norm_kind > 2 || rope_kind < 0 || rope_kind > 2) return SVG_ERR_BAD_ARG;
+    if (norm_kind < 0 || norm_kind > 2 || rope_kind < 0 || rope_kind > kRopeHalf) return SVG_ERR_BAD_ARG;
     if (rope_kind != kRopeNone) {
         if (!cos_or_real || !sin_or_imag || rope_lo < 0 || rope_hi > S || rope_lo > rope_hi) return SVG_ERR_BAD_ARG;
     }
@@ -645,7 +669,7 @@ extern "C" int svg_qk_norm_rope_transpose_qscale(const void* q_in, const void* k
     if (!(q_scale > 0.f)) return SVG_ERR_BAD_ARG;
     if ((!q_in && !k_in) || (q_in && (!q_out || Hq <= 0)) || (k_in && (!k_out || Hkv <= 0))) return SVG_ERR_BAD_ARG;
     if (q_in == q_out || (k_in && k_in == k_out)) return SVG_ERR_BAD_ARG;   // the layouts differ: not an in-place operation
-    if (norm_kind < 0 || norm_kind > 2 || rope_kind < 0 || rope_kind > 2) return SVG_ERR_BAD_ARG;
+    if (norm_kind < 0 || norm_kind > 2 || rope_kind < 0 || rope_kind > kRopeHalf) return SVG_ERR_BAD_ARG;
     if (rope_kind != kRopeNone) {
         if (!cos_or_real || !sin_or_imag || rope_lo < 0 || rope_hi > S || rope_lo > rope_hi) return SVG_ERR_BAD_ARG;
     }

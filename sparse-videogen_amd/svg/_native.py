@@ -1115,6 +1115,8 @@ def qk_norm_rope(q, k=None, norm_kind: int = 0, q_weight=None, q_bias=None, k_we
                  rope_kind: int = 0, cos=None, sin=None, rope_lo: int = 0, rope_hi: Optional[int] = None,
                  q_scale: float = 1.0) -> None:
     """Fused in-place normalisation + rotary embedding of q and (optionally) k in one pass (svg_qk_norm_rope).
+    rope_kind 0 none / 1 interleaved pairs / 2 complex pairs (tables [.., D / 2]) / 3 half-split (channel i against i + D / 2; tables
+    [.., D] like kind 1, every column read).
     q_scale != 1: folded into the last rounding of q (svg_qk_norm_rope_qscale; softmax_q_scale(D) for band_attention(q_prescaled=True))."""
     lib = load()
     _dev(q, k, q_weight, q_bias, k_weight, k_bias, cos, sin)
@@ -1139,7 +1141,7 @@ def qk_norm_rope_transpose(q_in, k_in, heads_q: int, heads_k: int, norm_kind: in
                            k_bias=None, eps: float = 1e-5, rope_kind: int = 0, cos=None, sin=None, rope_lo: int = 0,
                            rope_hi: Optional[int] = None, q_scale: float = 1.0):
     """q_in [bsz, S, Hq * D] (k_in [bsz, S, Hkv * D] or None) token-major -> new head-major tensors [bsz, H, S, D] with
-    normalisation + rotary embedding applied in the same pass (svg_qk_norm_rope_transpose); q_scale as in qk_norm_rope."""
+    normalisation + rotary embedding applied in the same pass (svg_qk_norm_rope_transpose); rope_kind and q_scale as in qk_norm_rope."""
     lib = load()
     _dev(q_in, k_in, q_weight, q_bias, k_weight, k_bias, cos, sin)
     bsz, S, HD = q_in.shape

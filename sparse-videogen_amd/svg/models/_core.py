@@ -596,11 +596,19 @@ def _tables(a, b, rows: int, cols: int, device):
     return (a, b) if a.shape == (rows, cols) and b.shape == (rows, cols) else None
 
 
+def _rope_kind(complex_pairs: bool, half_split: bool) -> int:
+    """rope_kind of include/svg_attn.h: 1 interleaved pairs, 2 complex pairs, 3 half-split (channel i against i + D / 2)"""
+    assert not (complex_pairs and half_split), "complex_pairs and half_split are mutually exclusive"
+    return 2 if complex_pairs else 3 if half_split else 1
+
+
 def qk_rope_inplace(query, key, cos, sin, rope_lo: int, rope_hi: int, complex_pairs: bool = False, norm_q=None,
-                    norm_k=None, q_scale: float = 1.0) -> bool:
+                    norm_k=None, q_scale: float = 1.0, half_split: bool = False) -> bool:
     """In-place rotary embedding of positions [rope_lo, rope_hi) — optionally fused with the QK normalisation (one pass over
     q and k instead of three).  cos / sin: [rope_hi - rope_lo, D] fp32 (complex_pairs: real / imag [.., D / 2]).
+    half_split: the two channel halves rotate against each other (Cosmos; tables [.., D], every column read) instead of neighbours.
     q_scale != 1: folded into the pass's last rounding of q (the attention core then runs its pre-scaled kernels)."""
+    rk = _rope_kind(complex_pairs, half_split)
     if not _fast_ok(query, key) or rope_hi <= rope_lo:
         return False
     D = query.shape[-1]
@@ -613,8 +621,7 @@ def qk_rope_inplace(query, key, cos, sin, rope_lo: int, rope_hi: int, complex_pa
         if dq is None or dk is None or dq[0] != dk[0] or dq[3] != dk[3]:
             return False
         kind, qw, qb, kw, kb, eps = dq[0], dq[1], dq[2], dk[1], dk[2], dq[3]
-    _native.qk_norm_rope(query, key, kind, qw, qb, kw, kb, eps, 2 if complex_pairs else 1, tb[0], tb[1], rope_lo, rope_hi,
-                         q_scale=q_scale)
+    _native.qk_norm_rope(query, key, kind, qw, qb, kw, kb, eps, rk, tb[0], tb[1], rope_lo, rope_hi, q_scale=q_scale)
     return True
 
 
@@ -634,9 +641,11 @@ def value_in_place(value: torch.Tensor, heads: int):
 
 
 def qkv_from_projections(query, key, value, heads: int, norm_q, norm_k, cos, sin, rope_lo: int, rope_hi: int,
-                         complex_pairs: bool = False, q_scale: float = 1.0):
+                         complex_pairs: bool = False, q_scale: float = 1.0, half_split: bool = False):
     """Projection outputs [bsz, S, heads * D] -> head-major q, k, v [bsz, heads, S, D] with QK-norm + RoPE applied to q, k in
-    the same pass (svg_qk_norm_rope_transpose): replaces three transpose copies + norm + norm + rope.  None: not applicable."""
+    the same pass (svg_qk_norm_rope_transpose): replaces three transpose copies + norm + norm + rope.  None: not applicable.
+    half_split: half-split RoPE (rope_kind 3, tables [rope_hi - rope_lo, D]) instead of interleaved pairs."""
+    rope_kind = _rope_kind(complex_pairs, half_split)
     ts = (query, key, value)
     if not all(t.is_cuda for t in ts):
         return None
@@ -657,7 +666,7 @@ def qkv_from_projections(query, key, value, heads: int, norm_q, norm_k, cos, sin
         tb = _tables(cos, sin, rope_hi - rope_lo, D // 2 if complex_pairs else D, query.device)
         if tb is None:
             return None
-        rk = 2 if complex_pairs else 1
+        rk = rope_kind
     q, k = _native.qk_norm_rope_transpose(query, key, heads, heads, kind, qw, qb, kw, kb, eps, rk, tb[0], tb[1], rope_lo, rope_hi,
                                           q_scale=q_scale)   # q_scale != 1: q leaves the prologue carrying the softmax scale
     v = value_in_place(value, heads) if q_scale == 1.0 else None   # (a pre-scaled q takes the entry points without strides)

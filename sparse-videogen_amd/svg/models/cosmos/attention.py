@@ -53,6 +53,44 @@ class _CosmosPlumbing:
             query, key = apply_rotary_emb_half(query, image_rotary_emb), apply_rotary_emb_half(key, image_rotary_emb)
         return query, key
 
+    # on the GPU: transpose + qk_norm + rotary_emb as ONE pass over q and k (svg_qk_norm_rope_transpose, rope_kind 3), v read in place where
+    # to_v wrote it; the cross call: one norm-only transpose pass per tensor.  False: the staged steps above, as the reference runs them
+    fused_prologue = True
+
+    @time_logging_decorator("Level 2 - transpose + qk_norm + rotary_emb (fused)")
+    def get_fused_prologue(self, attn, query, key, value, image_rotary_emb, cross: bool):
+        """get_transpose_qkv -> get_qk_norm -> get_rotary_emb in one kernel (bit-identical to the three steps; ref :40-124): returns
+        (q, k, v) head-major — q and k contiguous, v possibly the head view of the projection's output — or None when the pass does not
+        apply (CPU tensors, a norm module _norm_desc does not recognise, a table of another shape, ...): the caller runs the three steps."""
+        if not self.fused_prologue or not all(t.is_cuda for t in (query, key, value)):
+            return None
+        nq, nk = getattr(attn, "norm_q", None), getattr(attn, "norm_k", None)
+        if nq is None or nk is None:
+            return None
+        H = attn.heads
+        if not cross:
+            if image_rotary_emb is None:
+                return None
+            cos, sin = image_rotary_emb
+            # (q_scale stays 1: prescale_q is not wired for Cosmos)
+            return _core.qkv_from_projections(query, key, value, H, nq, nk, cos, sin, 0, query.shape[1], half_split=True)
+        # cross call: Sq != Skv, one pass per tensor; the conditions under which the staged steps run the in-place HIP norm (qk_norm_inplace)
+        if image_rotary_emb is not None:
+            return None
+        ts = (query, key, value)
+        if not all(t.dim() == 3 and t.is_contiguous() and t.dtype == query.dtype and t.shape[-1] == query.shape[-1] for t in ts):
+            return None
+        D = query.shape[-1] // H
+        if query.dtype not in (torch.bfloat16, torch.float16) or D not in _core._FAST_DIMS or H * D != query.shape[-1]:
+            return None
+        dq, dk = _core._norm_desc(nq, D, query.dtype, query.device), _core._norm_desc(nk, D, key.dtype, key.device)
+        if dq is None or dk is None or dq[0] != dk[0] or dq[3] != dk[3]:
+            return None
+        q, _ = _core._native.qk_norm_rope_transpose(query, None, H, 0, dq[0], dq[1], dq[2], None, None, dq[3])
+        k, _ = _core._native.qk_norm_rope_transpose(key, None, H, 0, dk[0], dk[1], dk[2], None, None, dk[3])
+        # v as a head view: svg_cross_attention* and SDPA both take strided operands (as the Wan cross branch passes it)
+        return q, k, value.unflatten(2, (H, -1)).transpose(1, 2)
+
     @time_logging_decorator("Level 2 - output")
     def get_o(self, attn, query, hidden_states):
         return attn.to_out[1](attn.to_out[0](hidden_states))
@@ -67,9 +105,13 @@ class _CosmosPlumbing:
         if encoder_hidden_states is None:
             encoder_hidden_states = hidden_states
         query, key, value = self.get_qkv(attn, hidden_states, encoder_hidden_states)
-        query, key, value = self.get_transpose_qkv(attn, query, key, value)
-        query, key = self.get_qk_norm(attn, query, key)
-        query, key = self.get_rotary_emb(query, key, image_rotary_emb)
+        fused = self.get_fused_prologue(attn, query, key, value, image_rotary_emb, cross)
+        if fused is not None:
+            query, key, value = fused
+        else:
+            query, key, value = self.get_transpose_qkv(attn, query, key, value)
+            query, key = self.get_qk_norm(attn, query, key)
+            query, key = self.get_rotary_emb(query, key, image_rotary_emb)
         assert query.shape[3] == key.shape[3] == value.shape[3], "Does not support GQA"
         if cross and attention_mask is not None:   # ... with the text key-padding mask (ref :104-110): each video's key window, else SDPA
             hidden_states = _core.cross_attention_key_masked(query, key, value, attention_mask)
@@ -79,7 +121,8 @@ class _CosmosPlumbing:
             hidden_states = F.scaled_dot_product_attention(query, key, value, attn_mask=attention_mask, dropout_p=0.0,
                                                            is_causal=False)
         else:
-            assert query.is_contiguous() and key.is_contiguous() and value.is_contiguous(), "Query, key, value must be contiguous"
+            # (v may be the head view of to_v's output: the attention kernels read it in place, as from the Wan processors)
+            assert query.is_contiguous() and key.is_contiguous() and value.stride(-1) == 1, "Query, key must be contiguous, value row-contiguous"
             hidden_states = self.attention_core_logic(query, key, value, timestep)
         hidden_states = hidden_states.transpose(1, 2).flatten(2, 3).type_as(query)
         return self.get_o(attn, query, hidden_states)
