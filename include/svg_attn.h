@@ -661,10 +661,18 @@ int svg_band_attention_prescaled_notify_seg(const void* q_scaled, const void* k,
  * svg_debug_band_replays: the bf16 band kernels at head_dim 128 test for an overflowing probability on every eighth key tile and
  * validate a q-tile's sums after its loop; a q-tile that fails is computed once more with the test on every tile.  Synchronises the
  * current device and returns how many q-tiles were replayed on it since the library was loaded or the counter was last reset
- * (reset != 0 zeroes it after reading); -1: a HIP error. */
+ * (reset != 0 zeroes it after reading); -1: a HIP error.
+ * svg_debug_band_row_cursor: the row cursor of the 16x16x32 band kernels, walked on the host (no GPU needed).  For a head over S rows
+ * whose video rows are [vid0, vid0 + num_frame * frame_size), token-major (token_major != 0) or contiguous, the key tiles with first
+ * keys k0[0 .. n) are resolved in this order as a wave of the kernel resolves them — a tile that follows the latest one by 64 keys and
+ * lies wholly inside the range takes the stepped form, every other tile the division — and out[64 * i + r] receives the physical row of
+ * row r of tile i (0 for rows behind S); cheap (or NULL) receives per tile whether the stepped form was taken.  Returns n; -1: bad
+ * arguments or out_words < 64 * n. */
 int32_t svg_band_queue_order(int32_t BH, int32_t S, const svg_band_mask_t* mask, int32_t* out, int32_t out_words);
 int svg_debug_band_queue_cap(int32_t max_workgroups);
 int64_t svg_debug_band_replays(int32_t reset);
+int32_t svg_debug_band_row_cursor(int32_t S, int32_t vid0, int32_t num_frame, int32_t frame_size, int32_t token_major,
+                                  const int32_t* k0, int32_t n, int32_t* out, int32_t out_words, int32_t* cheap);
 
 /* Diagnostics (not part of the reference's interface; -DSVG_ABLATIONS builds, otherwise SVG_ERR_UNSUPPORTED): cycle trace of
  * the two-phase attention schedule.  After a svg_band_attention call with variant 64 (bf16, D = 128) and a synchronised

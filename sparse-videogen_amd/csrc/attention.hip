@@ -542,6 +542,32 @@ extern "C" int64_t svg_debug_band_replays(int32_t reset) {
     return (int64_t)n;
 }
 
+// the row cursor of the 16x16x32 band body walked on the host, with the parameters a launch would build (see include/svg_attn.h)
+extern "C" int32_t svg_debug_band_row_cursor(int32_t S, int32_t vid0, int32_t num_frame, int32_t frame_size, int32_t token_major,
+                                             const int32_t* k0, int32_t n, int32_t* out, int32_t out_words, int32_t* cheap) {
+    using Pol = svg::BandPolicy<__bf16, 128, 8>;
+    if (S <= 0 || n < 0 || !k0 || !out || (int64_t)out_words < (int64_t)n * kBN) return -1;
+    const svg_band_mask_t mask{S, S, 0, 0, 0, 0};
+    const int64_t flag = 1;   // (never read: the builder only asks whether the call names token-major heads)
+    const svg_perm_desc_t perm{&flag, vid0, num_frame, frame_size};
+    if (check_band_mask(S, &mask, &perm) != SVG_OK) return -1;
+    const Pol::Params p = svg::make_band_params<Pol, __bf16>(nullptr, nullptr, nullptr, nullptr, 1, S, 1.f, &mask, &perm);
+    Pol::Ctx c{};
+    c.perm = token_major != 0;
+    for (int row = 0; row < kBN; ++row) {   // one lane's walk over the tiles, as the kernel does it
+        Pol::RowWalk w;
+        Pol::row_walk_init(p, c, w);
+        int phys = 0;
+        for (int i = 0; i < n; ++i) {
+            Pol::RowWalk probe = w;
+            if (cheap) cheap[i] = Pol::row_walk_cheap(probe, k0[i]) ? 1 : 0;
+            Pol::row_walk_next(p, w, phys, k0[i], row);
+            out[(size_t)i * kBN + row] = phys;
+        }
+    }
+    return n;
+}
+
 // the traces of the last traced launch (diagnostics builds; SVG_ERR_UNSUPPORTED otherwise)
 extern "C" int svg_debug_wg_trace(uint64_t* out, int n_workgroups) { return g_trace_reader(out, true, n_workgroups); }
 extern "C" int svg_debug_pp_trace(uint64_t* out104) { return g_trace_reader(out104, false, 0); }

@@ -66,6 +66,8 @@ __device__ __forceinline__ i16x8 lds_read_tr16x2(const char* p_lo, const char* p
 //   int  q_logical(ctx, row_in_wg)  / int q_phys(prm, ctx, row_in_wg)            (-1 = row does not exist)
 //   struct KvCursor; kv_cursor_init(prm, ctx, cur, row_in_tile); int kv_phys(prm, ctx, cur, t, row_in_tile)
 //        (physical row >= 0; rows that do not exist return 0 and MUST be masked by classify/allowed)
+//   optional, kRowCursor (attn_m16.h HasRowCursor): struct RowWalk; row_walk_init(prm, ctx, walk);
+//        row_walk_next(prm, walk, phys, tile_key0, row_in_tile) steps the lane's row in place — tiles in increasing order, as kv_phys
 //   int  tile_key0(ctx, t)                                       logical index of the first key of tile t
 //   int  classify(prm, ctx, tile_key0, wave_row0)                wave-uniform TileClass
 //   bool allowed(prm, ctx, q_logical, k_logical)                 element predicate for PARTIAL tiles

@@ -118,6 +118,24 @@ struct HasAddOnStore : std::false_type {};
 template <typename P>
 struct HasAddOnStore<P, std::void_t<decltype(&P::add_on_store)>> : std::true_type {};
 
+// Row cursor (detected: a policy with kRowCursor, band_policy.h BandPolicy; every other policy keeps kv_cursor_init / kv_phys and compiles
+// the request pipeline it had): the lane's key row is ONE variable stepped in place by P::row_walk_next, the decision between the
+// cheap step and the exact path is scalar, and the two byte offsets of a request are formed when the request pipeline takes the row.
+template <typename P, typename = void>
+struct HasRowCursor : std::false_type {};
+template <typename P>
+struct HasRowCursor<P, std::void_t<decltype(P::kRowCursor)>> : std::true_type {};
+
+// pp_barrier_if for a predicate that is already a scalar: the workgroup barrier where (flag != 0) == when_set.  One scalar serves
+// both barriers of a tile (leading / lagging waves keep opposite ones), and nothing is fetched from a VGPR.
+template <bool when_set>
+__device__ __forceinline__ void pp_barrier_sel(int flag) {
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (when_set) asm volatile("s_cmp_eq_u32 %0, 0\n\ts_cbranch_scc1 1f\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier\n1:" ::"s"(flag) : "memory", "scc");
+    else asm volatile("s_cmp_lg_u32 %0, 0\n\ts_cbranch_scc1 1f\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier\n1:" ::"s"(flag) : "memory", "scc");
+    __builtin_amdgcn_sched_barrier(0);
+}
+
 template <typename T>
 __device__ __forceinline__ u32x2 add_rounded16(u32x2 a, u32x2 b) {
     using E = Elt<T>;
@@ -207,24 +225,48 @@ __device__ __forceinline__ bool attn_m16_tile(const typename P::Params& prm, con
     const int dma_kg = wave / 2;
     const int dma_db0 = (wave % 2) * NP;
     const int krow = 16 * dma_kg + (lane >> 2);
-    typename P::KvCursor cur;
-    P::kv_cursor_init(prm, ctx, cur, krow);
+    constexpr bool kCursor = HasRowCursor<P>::value;
+    auto cur = [&] {
+        if constexpr (kCursor) {
+            typename P::RowWalk w;
+            P::row_walk_init(prm, ctx, w);
+            return w;
+        } else {
+            typename P::KvCursor c;
+            P::kv_cursor_init(prm, ctx, c, krow);
+            return c;
+        }
+    }();
     const unsigned col_v = (unsigned)(dma_db0 * 64 + Img::col_v(lane));            // the source column of BOTH tensors
     const unsigned lds_piece = lds0 + (unsigned)(dma_db0 * (kBN * 64) + dma_kg * 1024);
-    int nphys = 0, nnext = 0;
-    auto resolve = [&](int t, auto guard_c) {
-        if constexpr (decltype(guard_c)::value) nnext = (t < nT) ? P::kv_phys(prm, ctx, cur, t, krow) : 0;
-        else nnext = P::kv_phys(prm, ctx, cur, t, krow);
-    };
-    constexpr std::true_type kGuarded{};
-    auto take = [&]() { nphys = nnext; };
     // (row strides: 2 D bytes for contiguous heads, H * D or 3 * H * D elements for k / v read in place from a projection's output)
     const unsigned k_rsb = (unsigned)P::k_rs(prm) * 2u, v_rsb = (unsigned)P::v_rs(prm) * 2u;
+    int nphys = 0, nnext = 0;
+    unsigned req_ko = 0, req_vo = 0;   // row cursor: the byte offsets of the taken row (nphys is not used)
+    auto resolve = [&](int t, auto guard_c) {
+        if constexpr (kCursor) {   // in place; behind the last tile the cursor stays where it is (nothing requests that row)
+            if (!decltype(guard_c)::value || t < nT) P::row_walk_next(prm, cur, nnext, P::tile_key0(ctx, t), krow);
+        } else if constexpr (decltype(guard_c)::value) {
+            nnext = (t < nT) ? P::kv_phys(prm, ctx, cur, t, krow) : 0;
+        } else {
+            nnext = P::kv_phys(prm, ctx, cur, t, krow);
+        }
+    };
+    constexpr std::true_type kGuarded{};
+    auto take = [&]() {
+        if constexpr (kCursor) {
+            req_ko = __umul24((unsigned)nnext, k_rsb) + col_v;
+            req_vo = __umul24((unsigned)nnext, v_rsb) + col_v;
+            asm volatile("" : "+v"(req_ko), "+v"(req_vo));   // formed here, before the cursor moves (P::row_walk_next steps it in place)
+        } else {
+            nphys = nnext;
+        }
+    };
     auto dma_piece = [&](int t, auto j_c) {
         constexpr int j = decltype(j_c)::value;
         const unsigned st = __builtin_amdgcn_readfirstlane(lds_piece + (unsigned)((t % NS) * kStage) + j * (kBN * 64));
-        const unsigned ko = __umul24((unsigned)nphys, k_rsb) + col_v;
-        const unsigned vo = __umul24((unsigned)nphys, v_rsb) + col_v;
+        const unsigned ko = kCursor ? req_ko : __umul24((unsigned)nphys, k_rsb) + col_v;
+        const unsigned vo = kCursor ? req_vo : __umul24((unsigned)nphys, v_rsb) + col_v;
         lds_dma16_kv<kImg>(st, ko, vo, (const char*)kb_ + j * 64, (const char*)vb + j * 64);
     };
     auto dma_issue = [&](int t) {
@@ -575,14 +617,17 @@ __device__ __forceinline__ bool attn_m16_tile(const typename P::Params& prm, con
     // (kOneBar: which of the two barriers of a tile a wave keeps is a run-time property of the wave — the skip is a branch inside the asm
     //  block of pp_barrier_if, one copy of the loop.  Leading waves: [N(t), barrier, M(t)]; lagging waves: [barrier, N(t), M(t)].)
     const int bar_n = lagging ? 1 : 0, bar_m = lagging ? 0 : 1;
+    const int lag_s = __builtin_amdgcn_readfirstlane(bar_n);   // row-cursor policies: `lagging` as ONE scalar for both barriers (pp_barrier_sel)
     auto tile = [&](int t, auto has_next_c, auto guard_c) {
         tick(std::integral_constant<int, 0>{});
-        if constexpr (kOneBar) pp_barrier_if(bar_n);
+        if constexpr (kOneBar && kCursor) pp_barrier_sel<true>(lag_s);
+        else if constexpr (kOneBar) pp_barrier_if(bar_n);
         else pp_barrier();
         tick(std::integral_constant<int, 1>{});
         vector_phase(t, guard_c);
         tick(std::integral_constant<int, 2>{});
-        if constexpr (kOneBar) pp_barrier_if(bar_m);
+        if constexpr (kOneBar && kCursor) pp_barrier_sel<false>(lag_s);
+        else if constexpr (kOneBar) pp_barrier_if(bar_m);
         else pp_barrier();
         tick(std::integral_constant<int, 3>{});
         __builtin_amdgcn_s_setprio(1);   // the matrix phase wins the issue arbitration against the partner's vector phase

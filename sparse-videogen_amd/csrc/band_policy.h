@@ -315,6 +315,86 @@ struct BandPolicy : LayoutAccess<BandPolicy<T, D, NW, RB>> {
         return l < p.S ? phys : 0;
     }
 
+    // Row cursor of the 16x16x32 body (attn_m16.h picks it by HasRowCursor): ONE per-lane variable, the physical row of the lane's key
+    // row in the latest resolved tile, stepped in place.  Everything that decides how a tile is resolved is wave-uniform and stays
+    // on the scalar unit (RowWalk: loop constants of the q-tile and the first key of the latest resolved tile).
+    //   cheap step   the tile follows the latest one (first key + kBN) and lies wholly inside [lo, hi + kBN): no bounds select.
+    //                contiguous head: [lo, hi + kBN) = [.., S) and phys += kBN: one VALU instruction.
+    //                token-major head: the tile AND the one before it lie inside the video (so every lane holds a video row), and with
+    //                phys - vid0 = f * P + pp, x = phys + sp64 has left the video, x - vid0 >= F * P, exactly when the frame index
+    //                wrapped (pp < P for a row inside the video): x += 1 - V then.  The frame index is no state.  Four instructions.
+    //   exact        every other tile — the first of a q-tile, a segment jump, a tile that straddles an end of the video or S:
+    //                row_exact, the division of kv_phys_at.
+    static constexpr bool kRowCursor = true;
+    struct RowWalk {
+        int perm, lo, hi;        // token-major head?; first keys in [lo, hi] admit the cheap step
+        int step, end, unwrap;   // physical-row step of a tile (sp64 or kBN); token-major head: vid0 + V, 1 - V (step and unwrap per lane on the device, see row_walk_init)
+        int vlen;                // rows that are permuted: V or 0 (exact path)
+        int prev_k0;             // first key of the latest resolved tile
+    };
+    static __host__ __device__ __forceinline__ void row_walk_init(const Params& p, const Ctx& c, RowWalk& w) {
+        const bool perm = c.perm != 0;
+        w.perm = perm;
+        w.lo = perm ? p.vid0 + kBN : -(1 << 30);
+        w.hi = (perm ? p.vid0 + p.V : p.S) - kBN;
+        w.step = perm ? p.sp64 : kBN, w.end = p.vid0 + p.V, w.unwrap = 1 - p.V;
+        w.vlen = perm ? p.V : 0;
+        w.prev_k0 = -(1 << 30);
+#ifdef __HIP_DEVICE_COMPILE__
+        // the two addends of the token-major step live in VGPRs (opaque: not rematerialised from the arguments): the kernels are short
+        // of SGPRs, not of VGPRs, and a constant that the allocator keeps in a spill lane costs a v_readlane per tile
+        asm volatile("" : "+v"(w.step), "+v"(w.unwrap));
+        // (and the head kind as an integer of its own: tested as the lane mask it was derived from, the compiler carries it into the
+        //  exact path through a VGPR, two VALU instructions on every tile)
+        w.perm = __builtin_amdgcn_readfirstlane(w.perm);
+        asm volatile("" : "+s"(w.perm));
+#endif
+    }
+    // wave-uniform: the tile at k0 takes the cheap step; records k0 as the latest resolved tile
+    static __host__ __device__ __forceinline__ bool row_walk_cheap(RowWalk& w, int k0) {
+        const bool cheap = (k0 == w.prev_k0 + kBN) & (k0 >= w.lo) & (k0 <= w.hi);
+        w.prev_k0 = k0;
+        return cheap;
+    }
+    // (device: every write of the cursor is one instruction with a tied operand, so the row stays in the register it lives in; as
+    //  plain C++ the allocator keeps the old and the new row apart and copies one into the other on every tile)
+    static __host__ __device__ __forceinline__ void row_add(int& phys, int d) {
+#ifdef __HIP_DEVICE_COMPILE__
+        asm("v_add_u32 %0, %0, %1" : "+v"(phys) : "v"(d));
+#else
+        phys += d;
+#endif
+    }
+    static __host__ __device__ __forceinline__ void row_set(int& phys, int x) {
+#ifdef __HIP_DEVICE_COMPILE__
+        asm("v_mov_b32 %0, %1" : "+v"(phys) : "v"(x));
+#else
+        phys = x;
+#endif
+    }
+    // (`vlen`: V on a token-major head, 0 on a contiguous one — no row is a video row there.  The head kind reaches this path as a
+    //  number, not as a condition: a condition that is also live here is rebuilt through a VGPR at the head of every tile.)
+    static __host__ __device__ __forceinline__ int row_exact(const Params& p, int vlen, int l) {
+        const int i = l - p.vid0;
+        const int a = i >= 0 ? i : -i - 1;              // floor division also for rows in front of the video
+        const int qd = (int)((unsigned)a / (unsigned)p.F);
+        const int pp = i >= 0 ? qd : -qd - 1;
+        const int f = i - pp * p.F;
+        const int physv = p.vid0 + f * p.P + pp;
+        const bool in_video = (unsigned)i < (unsigned)vlen;
+        const int phys = in_video ? physv : l;
+        return l < p.S ? phys : 0;
+    }
+    // `phys`, the row of the lane (row `row` of a tile) in the latest resolved tile, becomes its row in the tile at k0.  (One-armed
+    // branches on scalars, each around in-place writes: with the exact path as the else-arm of the step, the merge of "stepped" and
+    // "divided" costs two copies of the cursor per tile.  A tile of the exact path steps first and overwrites the result.)
+    static __host__ __device__ __forceinline__ void row_walk_next(const Params& p, RowWalk& w, int& phys, int k0, int row) {
+        const bool cheap = row_walk_cheap(w, k0);
+        row_add(phys, w.step);
+        if (w.perm) row_add(phys, phys >= w.end ? w.unwrap : 0);
+        if (__builtin_expect(!cheap, 0)) row_set(phys, row_exact(p, w.vlen, k0 + row));
+    }
+
     static __device__ __forceinline__ int classify(const Params& p, const Ctx& c, int k0, int wrow0) {
         if (k0 >= c.fk_lo && k0 <= c.fk_hi) return TILE_FULL;
         const int w0 = c.q0 + wrow0;
