@@ -569,6 +569,28 @@ int svg_sample_mse_flagged(const void* q, const void* k, const void* v, const in
                            int32_t D, int32_t dtype, float sm_scale, const svg_profile_desc_t* prof, float* out_mse,
                            void* workspace, size_t workspace_bytes, const int32_t* skip_flag, void* stream);
 
+/* Band attention over groups of heads, each under a mask of its own: the videos of a batch whose text lengths differ (HunyuanVideo keeps
+ * its padded text inside the self-attention sequence, so a list of prompts of different lengths is a list of different masks; the
+ * reference sums the lengths over the batch, svg/models/hyvideo/attention.py:308-316, and runs one mask).
+ * Group g is the group_heads[g] consecutive heads behind those of groups 0..g-1 (group_heads: HOST memory, n_groups entries, read before
+ * the call returns); it runs under masks[g], and under alt_masks[g] when use_alt_flag[0] != 0 on the device.  The result is, bit for bit,
+ * one call per group — on that group's heads, with perm->head_perm_flag and the tensor bases advanced to the group's first head, byte
+ * offsets in 64 bits — of the single-mask entry the arguments select:
+ *   alt_masks == NULL: svg_band_attention (variant 0); with layout: svg_band_attention_strided; q_prescaled != 0 (sm_scale is then
+ *       ignored): svg_band_attention_prescaled;
+ *   alt_masks != NULL: svg_band_attention_switch, _switch_strided, _switch_prescaled.
+ * They are launches on `stream`, one group after the other, and not a mask per head inside one launch.  n_groups == 1 is
+ * the single-mask entry itself.  No completion counters: the notify forms stay single-mask.
+ * ALL groups are checked on the host before the first launch.  SVG_ERR_BAD_ARG: a NULL tensor, masks or group_heads; n_groups < 1; a
+ * group_heads[g] < 1 or a sum other than BH; alt_masks without use_alt_flag or the reverse; a mask or alternate mask of any group that
+ * the single-mask entries refuse; with layout, a group that is not a whole number of videos (group_heads[g] % heads_per_batch != 0: a
+ * group's base moves by batch strides).  SVG_ERR_UNSUPPORTED: what the single-mask entries do not have — a dtype / head_dim outside
+ * bf16, fp16 x 64, 128, rows they cannot address, a layout they refuse, a pre-scaled q with a layout. */
+int svg_band_groups_attention(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t S, int32_t D, int32_t dtype,
+                              float sm_scale, const svg_band_mask_t* masks, const svg_band_mask_t* alt_masks,
+                              const int32_t* group_heads, int32_t n_groups, const svg_perm_desc_t* perm,
+                              const int32_t* use_alt_flag, int32_t q_prescaled, const svg_attn_layout_t* layout, void* stream);
+
 /* fp8 (OCP e4m3) QK^T and PV for the same mask family (BASELINE.json configs[4]; the reference has NO fp8 attention —
  * /root/reference/README.md:117 "[ ] Support FP8 attention" — so there is no interface to cite: this entry point is
  * svg_band_attention with a workspace).  q, k, v, o are the 16-bit tensors of svg_band_attention (D = 128 only); the call runs

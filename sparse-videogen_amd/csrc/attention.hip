@@ -506,6 +506,75 @@ extern "C" int svg_band_attention_switch_prescaled(const void* q_scaled, const v
     return band_dispatch(q_scaled, k, v, o, BH, S, D, dtype, 1.f, mask, perm, kBandAuto, opts, 0, nullptr, stream);
 }
 
+// svg_band_groups_attention: the heads of one call in groups of consecutive heads, each under a mask (and an alternate mask) of its
+// own — the videos of a batch whose text lengths differ.  Every group is checked before the first launches; the launches are those of
+// the single-mask entry the arguments select, one pass through band_dispatch per group.  (One launch per group and not a mask per head
+// inside one launch: DESIGN §3.1.3.)
+namespace {
+struct BandGroup {
+    const void *q, *k, *v;
+    void* o;
+    svg_perm_desc_t perm;
+};
+// tensor bases and head-permutation flags of the group behind `h0` heads (byte offsets in 64 bits; 16-bit elements)
+BandGroup band_group_at(const void* q, const void* k, const void* v, void* o, int64_t h0, int32_t S, int32_t D, const svg_perm_desc_t* perm,
+                        const svg_attn_layout_t* layout) {
+    auto at = [](const void* p, int64_t elements) -> const void* { return (const char*)p + elements * 2; };
+    BandGroup g;
+    if (layout) {   // whole videos: the base moves by batch strides
+        const int64_t b0 = h0 / layout->heads_per_batch;
+        g.q = at(q, b0 * layout->q.batch), g.k = at(k, b0 * layout->k.batch), g.v = at(v, b0 * layout->v.batch);
+        g.o = (void*)at(o, b0 * layout->o.batch);
+    } else {
+        const int64_t off = h0 * (int64_t)S * D;
+        g.q = at(q, off), g.k = at(k, off), g.v = at(v, off), g.o = (void*)at(o, off);
+    }
+    g.perm = perm ? *perm : svg_perm_desc_t{nullptr, 0, 1, 1};
+    if (g.perm.head_perm_flag) g.perm.head_perm_flag += h0;
+    return g;
+}
+}  // namespace
+
+extern "C" int svg_band_groups_attention(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t S, int32_t D,
+                                         int32_t dtype, float sm_scale, const svg_band_mask_t* masks, const svg_band_mask_t* alt_masks,
+                                         const int32_t* group_heads, int32_t n_groups, const svg_perm_desc_t* perm,
+                                         const int32_t* use_alt_flag, int32_t q_prescaled, const svg_attn_layout_t* layout,
+                                         void* stream) {
+    if (!q || !k || !v || !o || !masks || !group_heads || n_groups < 1 || BH <= 0 || S <= 0) return SVG_ERR_BAD_ARG;
+    if ((alt_masks != nullptr) != (use_alt_flag != nullptr)) return SVG_ERR_BAD_ARG;
+    int64_t heads = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        if (group_heads[g] < 1) return SVG_ERR_BAD_ARG;
+        if (layout && (layout->heads_per_batch <= 0 || group_heads[g] % layout->heads_per_batch != 0)) return SVG_ERR_BAD_ARG;
+        heads += group_heads[g];
+    }
+    if (heads != BH) return SVG_ERR_BAD_ARG;
+    BandOpts opts = alt_masks ? switch_opts(nullptr, use_alt_flag) : BandOpts();
+    opts.prescaled = q_prescaled != 0, opts.strided = layout != nullptr;
+    const float scale = opts.prescaled ? 1.f : sm_scale;
+    // what the single-mask entries check, for every group, before anything is launched
+    int64_t h0 = 0;
+    for (int g = 0; g < n_groups; h0 += group_heads[g++]) {
+        const BandGroup gr = band_group_at(q, k, v, o, h0, S, D, perm, layout);
+        int rc = band_check_args(gr.q, gr.k, gr.v, gr.o, group_heads[g], S, D, masks + g, perm ? &gr.perm : nullptr);
+        if (rc == SVG_OK && alt_masks) rc = check_band_mask(S, alt_masks + g, nullptr);
+        AttnLayout lay;
+        if (rc == SVG_OK && layout) rc = layout_from_abi(layout, group_heads[g], group_heads[g], S, S, D, gr.q, gr.k, gr.v, gr.o, lay);
+        if (rc != SVG_OK) return rc;
+    }
+    if (opts.prescaled && opts.strided) return SVG_ERR_UNSUPPORTED;   // (no single-mask entry takes a pre-scaled q with a layout)
+    if (const int rc = dispatch_td(dtype, D, [](auto, auto) { return (int)SVG_OK; }); rc != SVG_OK) return rc;
+    h0 = 0;
+    for (int g = 0; g < n_groups; h0 += group_heads[g++]) {
+        const BandGroup gr = band_group_at(q, k, v, o, h0, S, D, perm, layout);
+        if (alt_masks) opts.alt_mask = alt_masks + g;
+        const int rc = band_dispatch(gr.q, gr.k, gr.v, gr.o, group_heads[g], S, D, dtype, scale, masks + g, perm ? &gr.perm : nullptr,
+                                     kBandAuto, opts, 0, layout, stream);
+        if (rc != SVG_OK) return rc;   // (a failed launch: SVG_ERR_LAUNCH)
+    }
+    return SVG_OK;
+}
+
 extern "C" int32_t svg_band_queue_order(int32_t BH, int32_t S, const svg_band_mask_t* mask, int32_t* out, int32_t out_words) {
     if (!mask || BH <= 0 || S <= 0 || check_band_mask(S, mask, nullptr) != SVG_OK) return -1;
     using Pol = svg::BandPolicy<__bf16, 128, 8>;

@@ -174,6 +174,8 @@ SIGNATURES = {
                                                 C.POINTER(PermDesc), _VP, _I32, _I32, _VP]),
     "svg_band_attention_switch": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _F32, C.POINTER(BandMask),
                                             C.POINTER(PermDesc), C.POINTER(BandMask), _VP, _VP]),
+    "svg_band_groups_attention": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _F32, C.POINTER(BandMask), C.POINTER(BandMask),
+                                            C.POINTER(_I32), _I32, C.POINTER(PermDesc), _VP, _I32, C.POINTER(AttnLayout), _VP]),
     "svg_sample_mse_flagged": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _F32, C.POINTER(ProfileDesc), _VP, _VP,
                                          _SZ, _VP, _VP]),
     "svg_varblock_workspace_bytes": (_SZ, [_I32, _I32, _I32, _I32, _I32]),
@@ -620,6 +622,50 @@ def band_attention_switch(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
     assert use_alt_flag.dtype == torch.int32 and use_alt_flag.numel() >= 1
     return _band_attention(q, k, v, mask, alt_mask, use_alt_flag, sm_scale, head_perm_flag, vid0, num_frame, frame_size, 0, out, None, 1,
                            q_prescaled, token_major_out)
+
+
+def band_attention_groups(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, masks: Sequence[BandMask], group_heads: Sequence[int],
+                          alt_masks: Optional[Sequence[BandMask]] = None, use_alt_flag: Optional[torch.Tensor] = None,
+                          head_perm_flag: Optional[torch.Tensor] = None, vid0: int = 0, num_frame: int = 1, frame_size: int = 1,
+                          out: Optional[torch.Tensor] = None, q_prescaled: bool = False, token_major_out: bool = False) -> torch.Tensor:
+    """band_attention / band_attention_switch (use_alt_flag given, with alt_masks) over groups of consecutive heads, group g —
+    group_heads[g] heads — under masks[g] (alt_masks[g]): svg_band_groups_attention, bit for bit the single-mask call on each group's
+    heads.  q, k, v: [B, H, S, D] (or [BH, S, D]), default schedule, default softmax scale.  Strided views, `out` and token_major_out as in
+    band_attention: read / written in place where the single-mask strided entry would (plain q, every group a whole number of the H
+    heads of a video), copied otherwise."""
+    lib = load()
+    _dev(head_perm_flag, use_alt_flag)
+    _gpu(q, k, v, out)
+    assert q.shape == k.shape == v.shape and q.dtype == k.dtype == v.dtype
+    n = len(masks)
+    assert n >= 1 and len(group_heads) == n and (alt_masks is None or len(alt_masks) == n)
+    assert (alt_masks is None) == (use_alt_flag is None)
+    S, D = q.shape[-2], q.shape[-1]
+    BH = q.numel() // (S * D)
+    perm = _perm_arg(head_perm_flag, BH, vid0, num_frame, frame_size)
+    marr = (BandMask * n)(*masks)
+    aarr = None if alt_masks is None else (BandMask * n)(*alt_masks)
+    garr = (_I32 * n)(*[int(g) for g in group_heads])
+    flag = _ptr(use_alt_flag)
+
+    def call(qq, kk, vv, o, lay):
+        return lib.svg_band_groups_attention(qq.data_ptr(), kk.data_ptr(), vv.data_ptr(), o.data_ptr(), BH, S, D, _dtype_code(q), _sm_scale(None, D),
+                                             marr, aarr, garr, n, perm, flag, int(q_prescaled), lay, _stream())
+
+    dense_in = q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and (out is None or out.is_contiguous())
+    H = _view4(q).shape[1]
+    if (not dense_in or (token_major_out and out is None)) and not q_prescaled and strided_attention_supported(q) \
+            and all(int(g) % H == 0 for g in group_heads):
+        o = _try_strided(q, k, v, out, token_major_out, "svg_band_groups_attention", lambda o4, lay: call(q, k, v, o4, C.byref(lay)))
+        if o is not None:
+            return o
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()   # (what no strided entry point takes is copied, as the reference does)
+    o = torch.empty_like(q) if out is None or not out.is_contiguous() else out
+    _check(call(q, k, v, o, None), "svg_band_groups_attention")
+    if out is not None and o is not out:
+        out.copy_(o)
+        return out
+    return o
 
 
 def cross_attention_supported(q: torch.Tensor, k: torch.Tensor) -> bool:

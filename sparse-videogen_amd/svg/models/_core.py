@@ -84,18 +84,55 @@ LN2 = 0.6931471805599453   # sm_scale of a kernel that applies sm_scale * log2(e
 TOKEN_MAJOR_IO = True
 
 
-@time_logging_decorator("Level 3 - Dense Flash Attention")
-def dense_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, valid_len: Optional[int] = None,
-                    q_prescaled: bool = False) -> torch.Tensor:
-    """Dense attention [cfg, H, S, D].  valid_len < S: two independent segments [0, valid) and [valid, S) — what the
-    reference gets from flash_attn_varlen_func with cu_seqlens [0, valid, S] (hyvideo/attention.py:452-470).
-    q_prescaled: q carries sm_scale * log2(e) (see qkv_from_projections(q_scale=...)); GPU only."""
+# ---------------------------------------------------------------------------------------------------------------
+# Batches whose videos differ in their text length (HunyuanVideo: a list of prompts).  A length, or a mask built from one, may be given
+# per video; neighbouring videos with equal values run as one group of heads, and a batch of equal values is ONE group and takes the
+# single-mask path — the same entry point, the same launch.  Several groups are one svg_band_groups_attention call: a launch per group
+# (DESIGN §3.1.3).
+# ---------------------------------------------------------------------------------------------------------------
+def _group_key(x):
+    if isinstance(x, (tuple, list)):
+        return tuple(_group_key(y) for y in x)
+    return x.as_tuple() if hasattr(x, "as_tuple") else x
+
+
+def video_groups(per_video, heads: int = 1):
+    """(values, heads_per_group): neighbouring videos with equal values (ints, BandMasks, tuples of them) merged into one group of
+    `heads` heads per video.  Equal NEIGHBOURS only — a group is a run of consecutive heads: (a, a, b, a) is three groups."""
+    values, counts = [], []
+    for x in per_video:
+        if values and _group_key(values[-1]) == _group_key(x):
+            counts[-1] += heads
+        else:
+            values.append(x)
+            counts.append(heads)
+    return values, counts
+
+
+def per_video(x, cfg: int, what: str):
+    """None when x is one value for the whole batch; otherwise the list of its `cfg` per-video values (ValueError for another count)."""
+    if torch.is_tensor(x) and x.dim() >= 1:
+        x = x.tolist()
+    if not isinstance(x, (list, tuple)):
+        return None
+    if len(x) != cfg:
+        raise ValueError(f"{what}: {len(x)} per-video values for a batch of {cfg} videos")
+    return list(x)
+
+
+def _no_sharding_of_groups(what: str) -> None:
+    if _dist.active():
+        raise NotImplementedError(f"{what}: head sharding (svg.distributed) with per-video lengths that differ is not implemented; "
+                                  f"run the batch on one GPU or give every video the same length")
+
+
+def _dense_band_mask(S: int, valid_len) -> "_native.BandMask":
+    real = S if valid_len is None else int(valid_len)
+    return _native.BandMask(real_len=real, band=S + 1, colfull_lo=0, colfull_hi=0, rowfull_lo=0, rowfull_hi=0)
+
+
+def _dense_sdpa(q, k, v, valid_len):
     S = q.shape[2]
-    if q.is_cuda:
-        real = S if valid_len is None else int(valid_len)
-        mask = _native.BandMask(real_len=real, band=S + 1, colfull_lo=0, colfull_hi=0, rowfull_lo=0, rowfull_hi=0)
-        return _native.band_attention(q, k, v, mask, q_prescaled=q_prescaled, token_major_out=TOKEN_MAJOR_IO and not _dist.active())
-    assert not q_prescaled, "a pre-scaled q only exists on the GPU path"
     if valid_len is None or valid_len >= S:
         return F.scaled_dot_product_attention(q, k, v, dropout_p=0.0, is_causal=False)
     vl = int(valid_len)
@@ -103,6 +140,29 @@ def dense_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, valid_len
     o[:, :, :vl] = F.scaled_dot_product_attention(q[:, :, :vl], k[:, :, :vl], v[:, :, :vl])
     o[:, :, vl:] = F.scaled_dot_product_attention(q[:, :, vl:], k[:, :, vl:], v[:, :, vl:])
     return o
+
+
+@time_logging_decorator("Level 3 - Dense Flash Attention")
+def dense_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, valid_len=None, q_prescaled: bool = False) -> torch.Tensor:
+    """Dense attention [cfg, H, S, D].  valid_len < S: two independent segments [0, valid) and [valid, S) — what the
+    reference gets from flash_attn_varlen_func with cu_seqlens [0, valid, S] (hyvideo/attention.py:452-470).
+    valid_len: one int for the batch, or a sequence of cfg ints, one per video (see video_groups).
+    q_prescaled: q carries sm_scale * log2(e) (see qkv_from_projections(q_scale=...)); GPU only."""
+    S = q.shape[2]
+    lens = per_video(valid_len, q.shape[0], "dense_attention(valid_len)")
+    if lens is not None:
+        vals, heads = video_groups([int(x) for x in lens], q.shape[1])
+        if len(vals) > 1:
+            if q.is_cuda:
+                return _native.band_attention_groups(q, k, v, [_dense_band_mask(S, x) for x in vals], heads, q_prescaled=q_prescaled,
+                                                     token_major_out=TOKEN_MAJOR_IO and not _dist.active())
+            assert not q_prescaled, "a pre-scaled q only exists on the GPU path"
+            return torch.cat([_dense_sdpa(q[b:b + 1], k[b:b + 1], v[b:b + 1], x) for b, x in enumerate(lens)])
+        valid_len = vals[0]
+    if q.is_cuda:
+        return _native.band_attention(q, k, v, _dense_band_mask(S, valid_len), q_prescaled=q_prescaled, token_major_out=TOKEN_MAJOR_IO and not _dist.active())
+    assert not q_prescaled, "a pre-scaled q only exists on the GPU path"
+    return _dense_sdpa(q, k, v, valid_len)
 
 
 @time_logging_decorator("Level 3 - Cross Attention")
@@ -248,8 +308,18 @@ def svg1_attention_device_switch(q, k, v, geo: Geometry, mask: "_native.BandMask
     """Dense warm-up step or sparse step, decided on the device: the profiler and the attention kernel read
     `dense_flag`; on a dense step the profiler returns at once and the kernel runs `dense_mask` without the head placement.
     Same attention results as the host-side branch of attention_core_logic (ref: hyvideo/attention.py:491-524) for the same sampled
-    rows; the rows come from a dedicated CPU generator (`_switch_generator`).  The returned best_mask_idx is -1 on a dense step."""
+    rows; the rows come from a dedicated CPU generator (`_switch_generator`).  The returned best_mask_idx is -1 on a dense step.
+    mask, dense_mask: one BandMask for the batch, or a sequence of cfg of them, one per video (see video_groups)."""
     _require_gpu(q, "SVG1 attention")
+    cfg, H = q.shape[0], q.shape[1]
+    pm, pd = per_video(mask, cfg, "svg1_attention_device_switch(mask)"), per_video(dense_mask, cfg, "svg1_attention_device_switch(dense_mask)")
+    groups = None
+    if pm is not None or pd is not None:
+        pairs, heads = video_groups(list(zip(pm or [mask] * cfg, pd or [dense_mask] * cfg)), H)
+        mask, dense_mask = pairs[0]
+        if len(pairs) > 1:
+            _no_sharding_of_groups("SVG1 attention")
+            groups = ([m for m, _ in pairs], [d for _, d in pairs], heads)
     if _dist.active() and not _local:   # svg.distributed.enable(): this rank's heads only, outputs all-gathered
         return _dist.run_sharded(lambda qh, kh, vh: svg1_attention_device_switch(
             qh, kh, vh, geo, mask, dense_mask, prof, num_sampled_rows, sample_max_row, dense_flag, _local=True,
@@ -257,9 +327,14 @@ def svg1_attention_device_switch(q, k, v, geo: Geometry, mask: "_native.BandMask
     mses = sample_mse(q, k, v, geo, prof, num_sampled_rows, sample_max_row, skip_flag=dense_flag, generator=_switch_generator(),
                       q_prescaled=q_prescaled)
     best_mask_idx = torch.argmin(mses, dim=0)
-    out = _native.band_attention_switch(q, k, v, mask, dense_mask, dense_flag, head_perm_flag=best_mask_idx, vid0=geo.vid0,
-                                        num_frame=geo.num_frame, frame_size=geo.frame_size, q_prescaled=q_prescaled,
-                                        token_major_out=TOKEN_MAJOR_IO and not _local)
+    if groups is not None:
+        out = _native.band_attention_groups(q, k, v, groups[0], groups[2], alt_masks=groups[1], use_alt_flag=dense_flag,
+                                            head_perm_flag=best_mask_idx, vid0=geo.vid0, num_frame=geo.num_frame,
+                                            frame_size=geo.frame_size, q_prescaled=q_prescaled, token_major_out=TOKEN_MAJOR_IO)
+    else:
+        out = _native.band_attention_switch(q, k, v, mask, dense_mask, dense_flag, head_perm_flag=best_mask_idx, vid0=geo.vid0,
+                                            num_frame=geo.num_frame, frame_size=geo.frame_size, q_prescaled=q_prescaled,
+                                            token_major_out=TOKEN_MAJOR_IO and not _local)
     return out, torch.where(dense_flag.reshape(()) != 0, torch.full_like(best_mask_idx, -1), best_mask_idx)
 
 
@@ -269,8 +344,18 @@ def svg1_sparse_attention(q, k, v, geo: Geometry, mask: "_native.BandMask", prof
     """The sparse branch of attention_core_logic (ref: hyvideo/attention.py:507-524):
     online profiling -> best_mask_idx -> placement -> block-sparse attention -> inverse placement.
     fused=True folds both placements into the attention kernel (bit-identical result, ~5.9 GB less HBM traffic at
-    Hunyuan 720p); fused=False runs the three kernels of the reference pipeline."""
+    Hunyuan 720p); fused=False runs the three kernels of the reference pipeline.
+    mask: one BandMask for the batch, or a sequence of cfg of them, one per video (see video_groups); the profiler's masks do not depend
+    on the prompt length, so the profiling pass is the same either way."""
     _require_gpu(q, "SVG1 sparse attention")
+    groups = None
+    pm = per_video(mask, q.shape[0], "svg1_sparse_attention(mask)")
+    if pm is not None:
+        masks, heads = video_groups(pm, q.shape[1])
+        mask = masks[0]
+        if len(masks) > 1:
+            _no_sharding_of_groups("SVG1 sparse attention")
+            groups = (masks, heads)
     if _dist.active() and not _local:   # svg.distributed.enable(): this rank's heads only, outputs all-gathered
         return _dist.run_sharded(lambda qh, kh, vh: svg1_sparse_attention(
             qh, kh, vh, geo, mask, prof, num_sampled_rows, sample_max_row, fused, _local=True, q_prescaled=q_prescaled), (q, k, v),
@@ -280,7 +365,11 @@ def svg1_sparse_attention(q, k, v, geo: Geometry, mask: "_native.BandMask", prof
     pk = dict(head_perm_flag=best_mask_idx, vid0=geo.vid0, num_frame=geo.num_frame, frame_size=geo.frame_size)
     if fused:
         with time_logging_decorator("Level 3 - sparse_flex_attention"):
-            if _use_fp8(q):   # (the fp8 pre-pass folds whatever scale it is given into its quantisation of q)
+            if groups is not None:
+                if _use_fp8(q):
+                    raise NotImplementedError("SVG1 sparse attention: fp8 attention with per-video lengths that differ is not implemented")
+                out = _native.band_attention_groups(q, k, v, groups[0], groups[1], q_prescaled=q_prescaled, token_major_out=TOKEN_MAJOR_IO, **pk)
+            elif _use_fp8(q):   # (the fp8 pre-pass folds whatever scale it is given into its quantisation of q)
                 out = _native.band_attention_fp8(q.contiguous(), k.contiguous(), v.contiguous(), mask, sm_scale=LN2 if q_prescaled else None, **pk)
             else:
                 out = _native.band_attention(q, k, v, mask, q_prescaled=q_prescaled, token_major_out=TOKEN_MAJOR_IO and not _local, **pk)
@@ -291,7 +380,10 @@ def svg1_sparse_attention(q, k, v, geo: Geometry, mask: "_native.BandMask", prof
         _native.head_placement([q, k, v], [qo, ko, vo], best_mask_idx, geo.context_length, geo.num_frame, geo.frame_size,
                                geo.text_first, inverse=False)
     with time_logging_decorator("Level 3 - sparse_flex_attention"):
-        hs = _native.band_attention(qo, ko, vo, mask, q_prescaled=q_prescaled)
+        if groups is not None:
+            hs = _native.band_attention_groups(qo, ko, vo, groups[0], groups[1], q_prescaled=q_prescaled)
+        else:
+            hs = _native.band_attention(qo, ko, vo, mask, q_prescaled=q_prescaled)
     out = torch.empty_like(hs)
     with time_logging_decorator("Level 3 - fast_hidden_states_placement"):
         _native.head_placement([hs], [out], best_mask_idx, geo.context_length, geo.num_frame, geo.frame_size, geo.text_first,
@@ -411,14 +503,21 @@ def kmeans_clustering(store: CentroidStore, layer_idx: int, q_video, k_video, nu
 
 def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_idx: int, num_q_centroids: int,
                           num_k_centroids: int, top_p: float, min_kc_ratio: float, iter_init: int, iter_step: int,
-                          prompt_length: int = 0, logging_file: Optional[str] = None, timestep=None, _head_shard=None):
+                          prompt_length=0, logging_file: Optional[str] = None, timestep=None, _head_shard=None):
     """The sparse branch of the SAP processors (ref: hyvideo/attention.py:747-804, wan/attention.py:529-559):
     k-means on the video tokens -> top-p block map -> (Hunyuan) two pseudo clusters for prompt / unused prompt ->
     variable-block attention with the token permutation fused in (the result is already in the original order).
     q, k, v: [cfg, H, S, D]; cfg > 1 (several videos: a list of prompts, num_videos_per_prompt > 1) clusters each video with its own
-    stopping rule, so every video's output, labels and block map are the ones a cfg = 1 call on that video alone gives.  All videos share
-    the text layout (`prompt_length` is one integer)."""
+    stopping rule, so every video's output, labels and block map are the ones a cfg = 1 call on that video alone gives.
+    prompt_length: one int for the batch, or a sequence of cfg ints, one per video — the sizes of the two text pseudo-clusters are per
+    head in the kernel already, so the videos still share one launch."""
     _require_gpu(q, "SVG2 sparse attention")
+    pl = per_video(prompt_length, q.shape[0], "svg2_sparse_attention(prompt_length)")
+    if pl is not None:
+        pl = [int(x) for x in pl]
+        prompt_length = pl[0] if len(set(pl)) == 1 else tuple(pl)
+        if isinstance(prompt_length, tuple):
+            _no_sharding_of_groups("SVG2 sparse attention")
     if _dist.active() and _head_shard is None:   # svg.distributed.enable(): this rank's heads only, outputs all-gathered
         grp = _dist.current_group()
         mine = _dist.shard_heads(q.shape[1], torch.distributed.get_rank(grp), torch.distributed.get_world_size(grp))
@@ -518,15 +617,31 @@ import atexit  # noqa: E402
 atexit.register(flush_density_log)
 
 
+_SMALL_TENSORS = {}   # (values, dtype, device) -> tensor: a batch's prompt lengths, uploaded once and not once per layer-call
+
+
+def _small_tensor(values: tuple, dtype, device) -> torch.Tensor:
+    key = (values, dtype, str(device))
+    if key not in _SMALL_TENSORS:
+        if len(_SMALL_TENSORS) > 8:
+            _SMALL_TENSORS.clear()
+        _SMALL_TENSORS[key] = torch.tensor(values, dtype=dtype, device=device)
+    return _SMALL_TENSORS[key]
+
+
 def dynamic_map_post_processing(dyn_map, qc_sz, kc_sz, q_sorted_indices, k_sorted_indices, video_length, context_length,
                                 prompt_length):
-    """ref: hyvideo/attention.py:657-702 — append the prompt / unused-prompt pseudo clusters.  The q,k,v write-back of
+    """ref: hyvideo/attention.py:657-702 — append the prompt / unused-prompt pseudo clusters (prompt_length: one int, or a sequence of
+    cfg ints: the two sizes are then per video).  The q,k,v write-back of
     the reference (permuted video tokens copied in front of the text tokens) is not needed: the attention kernel
     gathers rows through the (identity-padded) sorted indices."""
     dyn_map = F.pad(dyn_map, (0, 2, 0, 2), value=0)
     dyn_map[:, :, -2, :-1] = True
     dyn_map[:, :, :-1, -2] = True
     dyn_map[:, :, -1, -1] = True
+    pl = per_video(prompt_length, qc_sz.shape[0], "dynamic_map_post_processing(prompt_length)")
+    if pl is not None:   # per video: [cfg, 1] against the [cfg, H] columns of the sizes
+        prompt_length = _small_tensor(tuple(int(x) for x in pl), qc_sz.dtype, qc_sz.device).view(-1, 1)
     unprompt = context_length - prompt_length
     qc_sz = F.pad(qc_sz, (0, 2), value=0)
     qc_sz[:, :, -2] = prompt_length

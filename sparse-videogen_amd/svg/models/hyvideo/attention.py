@@ -56,6 +56,11 @@ def apply_qk_rope_double(query, key, image_rotary_emb):
     return apply_rotary_emb(query, image_rotary_emb), apply_rotary_emb(key, image_rotary_emb)
 
 
+def _row_sums(rows: torch.Tensor) -> tuple:
+    """the host read-back of a several-row mask in get_cu_max_seqlen (its own function: the tests count its calls)"""
+    return tuple(int(x) for x in rows.sum(dim=1).tolist())
+
+
 class _HunyuanProcessorBase:
     """QKV projection / norm / RoPE / text concat / output projection shared by the three Hunyuan processors
     (ref: hyvideo/attention.py:252-373)."""
@@ -163,21 +168,36 @@ class _HunyuanProcessorBase:
 
     @time_logging_decorator("Level 2 - get_cu_max_seqlen")
     def get_cu_max_seqlen(self, attention_mask, device):
-        """ref :308-316.  Returns (valid_len, seq_len): the two dense segments are [0, valid) and [valid, S)."""
+        """ref :308-316.  Returns (valid_len, seq_len): the two dense segments are [0, valid) and [valid, S).
+        A mask with several rows ([B, S] or [B, 1, 1, S]: a batch of prompts) gives (tuple of the B per-row sums, S): every video its own
+        valid length.  (The reference sums over the whole batch, which is only a length when B = 1.)"""
         if attention_mask is None:
             return None, None
+        rows = attention_mask.numel() // attention_mask.shape[-1] if attention_mask.dim() >= 2 and attention_mask.numel() else 1
         # The mask is the same tensor object for every layer of a forward pass: its popcount is read back to the host once per
         # tensor object (the reference synchronises on it in every layer-call).  Keyed by object identity, guarded by a weak
         # reference and the in-place version counter, so a recycled address or an edited mask never hits.
         cache = _HunyuanProcessorBase._valid_len_cache
         ent = cache.get(id(attention_mask))
         if ent is not None and ent[0]() is attention_mask and ent[1] == attention_mask._version:
-            return ent[2], attention_mask.numel()
+            return ent[2], attention_mask.numel() // rows
         if len(cache) > 8:
             cache.clear()
-        n = int(attention_mask.sum())
+        n = int(attention_mask.sum()) if rows == 1 else _row_sums(attention_mask.reshape(rows, -1))
         cache[id(attention_mask)] = (weakref.ref(attention_mask), attention_mask._version, n)
-        return n, attention_mask.numel()
+        return n, attention_mask.numel() // rows
+
+    def video_valid_lens(self, cu_max_seqlens, cfg: int, video_length: int):
+        """The dense `valid` of a call on cfg videos: the mask's (an int, or a tuple with one entry per mask row), else video_length +
+        prompt_length (per video when prompt_length is a tuple).  A tuple of another length than cfg is a ValueError, here, before anything
+        runs — for the mask rows and for prompt_length alike."""
+        pl = getattr(self, "prompt_length", 0)
+        for what, x in (("attention_mask rows", cu_max_seqlens[0] if cu_max_seqlens is not None else None), ("prompt_length", pl)):
+            if isinstance(x, tuple) and len(x) != cfg:
+                raise ValueError(f"{type(self).__name__}: {what} has {len(x)} entries for a batch of {cfg} videos")
+        if cu_max_seqlens is not None and cu_max_seqlens[0] is not None:
+            return cu_max_seqlens[0]
+        return tuple(video_length + p for p in pl) if isinstance(pl, tuple) else video_length + pl
 
     @time_logging_decorator("Level 2 - get_o")
     def get_o(self, attn, hidden_states, encoder_hidden_states):
@@ -237,7 +257,7 @@ class HunyuanVideoAttnProcessor2_0_FlashAttention(_HunyuanProcessorBase):
 
     @time_logging_decorator("Level 2 - attention core logic")
     def attention_core_logic(self, query, key, value, timestep, layer_idx, cu_max_seqlens):
-        valid = cu_max_seqlens[0] if cu_max_seqlens is not None else None
+        valid = cu_max_seqlens[0] if cu_max_seqlens is not None else None   # (a tuple: one valid length per video)
         return _core.dense_attention(query, key, value, valid)
 
 
@@ -283,8 +303,7 @@ class Hunyuan_SVGAttn_Processor2_0(_HunyuanProcessorBase):
         geo = self.geometry()
         assert seq_len == geo.seq_len, (
             f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
-        valid = cu_max_seqlens[0] if cu_max_seqlens is not None and cu_max_seqlens[0] is not None else (
-            geo.video_length + self.prompt_length)
+        valid = self.video_valid_lens(cu_max_seqlens, cfg, geo.video_length)
         # the layer test is host data; the timestep test stays on the device when the timestep is a GPU tensor (device_switch)
         dense_flag = None
         if self.device_switch and _core.attention_dtype() == "bf16" and self.fused_placement and self.layer_idx >= self.first_layers_fp and self.block_mask is not None \
@@ -293,12 +312,15 @@ class Hunyuan_SVGAttn_Processor2_0(_HunyuanProcessorBase):
         pre = self._q_prescaled
         if dense_flag is None and _core.is_full_attention(self.layer_idx, timestep, self.first_layers_fp, self.first_times_fp):
             return _core.dense_attention(query, key, value, valid, q_prescaled=pre).reshape(cfg, num_heads, seq_len, dim)
-        mask = self.block_mask
+        mask = self.block_mask   # (a tuple: one mask per video, as prompt_length)
         if mask is None:
             raise RuntimeError("Hunyuan_SVGAttn_Processor2_0.block_mask is not set: call replace_hyvideo_attention first")
+        if isinstance(mask, tuple) and len(mask) != cfg:
+            raise ValueError(f"Hunyuan_SVGAttn_Processor2_0: block_mask has {len(mask)} entries for a batch of {cfg} videos")
         prof = profile_desc(geo.context_length, geo.num_frame, geo.frame_size)
         if dense_flag is not None:
-            out, best = _core.svg1_attention_device_switch(query, key, value, geo, mask, dense_mask(seq_len, int(valid)), prof,
+            dense = tuple(dense_mask(seq_len, int(x)) for x in valid) if isinstance(valid, tuple) else dense_mask(seq_len, int(valid))
+            out, best = _core.svg1_attention_device_switch(query, key, value, geo, mask, dense, prof,
                                                            self.num_sampled_rows, min(self.sample_mse_max_row, seq_len), dense_flag,
                                                            q_prescaled=pre)
             self.last_best_mask_idx = best
@@ -320,9 +342,9 @@ def prepare_flexattention(cfg_size, num_head, head_dim, dtype, device, context_l
 class Hunyuan_SAPAttn_Processor2_0(Hunyuan_SVGAttn_Processor2_0):
     """Sparse VideoGen 2 — semantic-aware permutation (ref: hyvideo/attention.py:555-804).
     Takes a batch of videos (cfg > 1: a list of prompts, num_videos_per_prompt > 1): each video is clustered with its own stopping
-    rule and gets the output a call on it alone gives.  `prompt_length` stays one class-level integer, as in the reference: all
-    videos of a batch share the text layout (per-video prompt lengths are not supported).  A layer called with another cfg than its
-    stored centroids starts over from random initial points (see CentroidStore)."""
+    rule and gets the output a call on it alone gives.  `prompt_length` is one class-level integer, as in the reference, or a tuple
+    with one entry per video (replace_hyvideo_attention(prompt_length=[...])): every video its own text pseudo-clusters and its own dense
+    warm-up segments.  A layer called with another cfg than its stored centroids starts over from random initial points (see CentroidStore)."""
 
     num_q_centroids = 0
     num_k_centroids = 0
@@ -348,18 +370,17 @@ class Hunyuan_SAPAttn_Processor2_0(Hunyuan_SVGAttn_Processor2_0):
         geo = self.geometry()
         assert seq_len == geo.seq_len, (
             f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
+        valid = self.video_valid_lens(cu_max_seqlens, cfg, geo.video_length)
         if _core.is_full_attention(self.layer_idx, timestep, self.first_layers_fp, self.first_times_fp):
             if self.zero_step_kmeans_init and query.is_cuda:
                 V = geo.video_length
                 _core.kmeans_clustering(self.centroid_store, layer_idx, query[:, :, :V], key[:, :, :V],   # (views: read in place)
                                         self.num_q_centroids, self.num_k_centroids,
                                         self.kmeans_iter_init, self.kmeans_iter_step)
-            valid = cu_max_seqlens[0] if cu_max_seqlens is not None and cu_max_seqlens[0] is not None else (
-                geo.video_length + self.prompt_length)
             return _core.dense_attention(query, key, value, valid).reshape(cfg, num_heads, seq_len, dim)
         out = _core.svg2_sparse_attention(query, key, value, geo, self.centroid_store, layer_idx, self.num_q_centroids,
                                           self.num_k_centroids, self.top_p_kmeans, self.min_kc_ratio, self.kmeans_iter_init,
-                                          self.kmeans_iter_step, prompt_length=int(self.prompt_length),
+                                          self.kmeans_iter_step, prompt_length=self.prompt_length if isinstance(self.prompt_length, tuple) else int(self.prompt_length),
                                           logging_file=self.logging_file, timestep=timestep)
         return out.reshape(cfg, num_heads, seq_len, dim)
 

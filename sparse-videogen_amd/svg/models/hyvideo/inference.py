@@ -61,7 +61,11 @@ def replace_hyvideo_attention(
     # geometry exactly as the reference derives it (:57-59)
     cfg_size, num_head, head_dim, dtype = 1, 24, 128, torch.bfloat16
     context_length, num_frame, frame_size = 256, 1 + num_frames // 4, height * width // 256
-    prompt_length = int(prompt_length)
+    # one text length for the batch, or one per video (a list of prompts: utils.get_prompt_lengths) — then a tuple, and a tuple of masks
+    if torch.is_tensor(prompt_length) and prompt_length.dim() >= 1:
+        prompt_length = prompt_length.tolist()
+    per_video = isinstance(prompt_length, (list, tuple))
+    prompt_length = tuple(int(p) for p in prompt_length) if per_video else int(prompt_length)
 
     if pattern == "SVG":
         AttnModule = Hunyuan_SVGAttn_Processor2_0
@@ -72,10 +76,11 @@ def replace_hyvideo_attention(
             get_attention_mask(name, AttnModule.sample_mse_max_row, context_length, num_frame, frame_size)
             for name in ("spatial", "temporal")
         ]
-        AttnModule.block_mask = prepare_flexattention(cfg_size, num_head, head_dim, dtype, "cuda", context_length,
-                                                      prompt_length, num_frame, frame_size, diag_width=diag_width,
-                                                      multiplier=multiplier)
-        logger.info(f"SVG: sparsity {sparsity} -> width {multiplier:.4f} frames -> band {AttnModule.block_mask.band} tokens")
+        masks = tuple(prepare_flexattention(cfg_size, num_head, head_dim, dtype, "cuda", context_length, p, num_frame, frame_size,
+                                            diag_width=diag_width, multiplier=multiplier)
+                      for p in (prompt_length if per_video else (prompt_length,)))
+        AttnModule.block_mask = masks if per_video else masks[0]
+        logger.info(f"SVG: sparsity {sparsity} -> width {multiplier:.4f} frames -> band {masks[0].band} tokens")
     elif pattern in ["SAP"]:
         logger.info(f"Configuring KMEANS_BLOCK attention with QC: {num_q_centroids}, KC: {num_k_centroids}, P: {top_p_kmeans}, "
                     f"min_kc_ratio: {min_kc_ratio}")

@@ -69,6 +69,11 @@ def get_prompt_length(pipe, prompt, prompt_template=DEFAULT_PROMPT_TEMPLATE, max
     reference."""
     if prompt_template is None:
         raise RuntimeError("get_prompt_length: diffusers is not installed, pass prompt_template explicitly")
+    return _prompt_attention_mask(pipe, prompt, prompt_template, max_sequence_length, device).sum()
+
+
+def _prompt_attention_mask(pipe, prompt, prompt_template, max_sequence_length, device):
+    """the tokenizer's attention mask of the templated prompts behind the template prefix, [len(prompt), max_sequence_length]"""
     prompt = [prompt] if isinstance(prompt, str) else prompt
     prompt = [prompt_template["template"].format(p) for p in prompt]
     crop_start = prompt_template.get("crop_start", None)
@@ -83,4 +88,13 @@ def get_prompt_length(pipe, prompt, prompt_template=DEFAULT_PROMPT_TEMPLATE, max
     prompt_attention_mask = text_inputs.attention_mask.to(device=device)
     if crop_start is not None and crop_start > 0:
         prompt_attention_mask = prompt_attention_mask[:, crop_start:]
-    return prompt_attention_mask.sum()
+    return prompt_attention_mask
+
+
+def get_prompt_lengths(pipe, prompts, prompt_template=DEFAULT_PROMPT_TEMPLATE, max_sequence_length=256, device="cuda"):
+    """get_prompt_length per prompt: a list of ints, one per entry of `prompts` — what replace_hyvideo_attention(prompt_length=[...])
+    takes for a batch of prompts of different lengths.  The same tokenizer logic with the mask summed per row (`sum(dim=1)`);
+    get_prompt_length itself stays the reference's and returns the sum over the list."""
+    if prompt_template is None:
+        raise RuntimeError("get_prompt_lengths: diffusers is not installed, pass prompt_template explicitly")
+    return [int(n) for n in _prompt_attention_mask(pipe, prompts, prompt_template, max_sequence_length, device).sum(dim=1).tolist()]
