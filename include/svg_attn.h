@@ -268,6 +268,36 @@ int svg_cross_attention_keyrange(const void* q, const void* k, const void* v, vo
 int svg_cross_attention_pair(const void* q, const void* k_a, const void* v_a, const void* k_b, const void* v_b, void* o, int32_t BH,
                              int32_t Sq, int32_t Skv_a, int32_t Skv_b, int32_t D, int32_t dtype, float sm_scale,
                              const svg_attn_layout_t* layout, const svg_attn_layout_t* layout_b, void* stream);
+/* svg_cross_attention (kv_end NULL) or svg_cross_attention_keyrange (kv_end given) that also returns the softmax state of every query
+ * row: lse[bh, s] = log sum_j exp(sm_scale * q[bh, s] . k[bh, j]) over the keys the row attends to, natural logarithm, fp32, CONTIGUOUS
+ * [BH, Sq] whatever the layout of q / o.  With it a result computed over a part of the keys can be combined with others later
+ * (svg_merge_attention_states below): dense attention with the keys sharded over GPUs, a ring of key shards.
+ * ref: flashinfer's `run(..., return_lse=True)` + `flashinfer.merge_state`, svg/kernels/ops/attention_ops.py:178-188; the
+ *      context-parallel dense attention of svg/models/wan_orig/distributed/xdit_context_parallel.py:120-169 (xfuser ring / Ulysses).
+ * o has the bits of the entry without lse (same kernel body; the epilogue stores one more fp32 per row).  A row without keys (an empty
+ * window) has lse = -inf and o = 0.  lse NULL: SVG_ERR_BAD_ARG; kv_end given with heads_per_window <= 0 or BH % heads_per_window != 0:
+ * SVG_ERR_BAD_ARG (kv_end NULL: kv_begin and heads_per_window are ignored); every other check is that of svg_cross_attention, all on the
+ * host before any launch.  The band, variable-block and pair entries do not return lse. */
+int svg_cross_attention_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t Sq, int32_t Skv, int32_t D,
+                            int32_t dtype, float sm_scale, const int32_t* kv_begin, const int32_t* kv_end /* NULL: all keys */,
+                            int32_t heads_per_window, const svg_attn_layout_t* layout, void* stream);
+/* N-way merge of attention states: n_parts partial results of the SAME query rows over disjoint parts of the keys — o_parts[i] 16-bit
+ * contiguous [BH, Sq, D], lse_parts[i] fp32 contiguous [BH, Sq] (svg_cross_attention_lse) — combined into the result over all the keys.
+ * Per row, in fp32, parts in index order: m = max_i lse_i, w_i = exp(lse_i - m), o = sum_i w_i o_i / sum_i w_i rounded once to the 16-bit
+ * type, lse = m + log sum_i w_i.  A part with lse_i = -inf (or whose weight underflows to zero) contributes nothing and its o_i is not
+ * looked at; all parts -inf: o = 0, lse = -inf; n_parts == 1 copies the bits.
+ * ref: flashinfer.merge_state, svg/kernels/ops/attention_ops.py:178-188; the step merge of the ring attention behind
+ *      svg/models/wan_orig/distributed/xdit_context_parallel.py:120-169.
+ * 1 <= n_parts <= 8 (the pointers travel by value in the kernel arguments; all parts in ONE pass because a chain of pairwise merges
+ * rounds every intermediate o to 16 bits — 3.8e-3 instead of 2.35e-3 rel. L2 at 8 bf16 parts): anything else SVG_ERR_BAD_ARG, as are a
+ * NULL o_parts / lse_parts / o, a NULL among the first n_parts entries of either array (HOST arrays of DEVICE pointers, as
+ * svg_head_placement takes them) and a non-positive size.  D other than 64 / 128, a dtype other than bf16 / fp16, rows the attention
+ * kernels cannot address (Sq >= 2^24, BH * Sq * D >= 2^40) or a part / o not 16-byte aligned: SVG_ERR_UNSUPPORTED.  lse (merged, [BH, Sq])
+ * may be NULL.  layout: NULL for a contiguous o; otherwise ONLY heads_per_batch and the o strides are read (token-major o for the output
+ * projection), with the checks of the *_strided entries.  o must not overlap a part. */
+int svg_merge_attention_states(const void* const* o_parts, const float* const* lse_parts, int32_t n_parts, void* o, float* lse /* may be NULL */,
+                               int32_t BH, int32_t Sq, int32_t D, int32_t dtype, const svg_attn_layout_t* layout /* o strides only; NULL: contiguous */,
+                               void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Online profiler (SVG1): mean-squared error of the two candidate masks on sampled query rows.

@@ -1,5 +1,6 @@
 // Cross attention for gfx950: dense attention of Sq query rows over a short key set (Sq != Skv), the two-phase 16x16x32 body of
-// attn_m16.h on the policy of cross_policy.h, and the svg_cross_attention / svg_cross_attention_keyrange / svg_cross_attention_pair entries.  (Band family: attention.hip; SVG2: attention_varblock.hip.)
+// attn_m16.h on the policy of cross_policy.h, and the svg_cross_attention / svg_cross_attention_keyrange / svg_cross_attention_pair /
+// svg_cross_attention_lse entries.  (Band family: attention.hip; SVG2: attention_varblock.hip.)
 #include <algorithm>
 
 #include "attn_m16.h"
@@ -17,6 +18,22 @@ template <typename T, bool Windowed = false>
 __global__ __launch_bounds__(512, 2) void cross_attn_m16_kernel(typename CrossPolicy<T, Windowed>::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using Pol = CrossPolicy<T, Windowed>;
+    const int n_items = prm.BH * prm.nqt;
+    for (int w = blockIdx.x; w < n_items; w += gridDim.x) {
+        if (w != (int)blockIdx.x) __syncthreads();
+        const int head = w / prm.nqt;
+        typename Pol::Ctx ctx;
+        Pol::init_tile(prm, ctx, head, w - head * prm.nqt);
+        attn_m16_tile<T, Pol, false, 1>(prm, ctx, smem);
+    }
+}
+
+// LSE form (svg_cross_attention_lse): the loop above on CrossLsePolicy — the epilogue of attn_m16_tile also stores one fp32 per query row.
+// (Its own kernel template, not a third argument of the one above: the plain and windowed kernels keep their symbols and their listings.)
+template <typename T, bool Windowed>
+__global__ __launch_bounds__(512, 2) void cross_attn_lse_m16_kernel(typename CrossLsePolicy<T, Windowed>::Params prm) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    using Pol = CrossLsePolicy<T, Windowed>;
     const int n_items = prm.BH * prm.nqt;
     for (int w = blockIdx.x; w < n_items; w += gridDim.x) {
         if (w != (int)blockIdx.x) __syncthreads();
@@ -85,8 +102,8 @@ static int device_cus() {
 
 using namespace svg;
 
-// the checks and the launch of both entries; kv_end == nullptr: the plain kernel
-static int cross_attention_launch(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t Sq, int32_t Skv, int32_t D, int32_t dtype,
+// the checks and the launch of the plain, keyrange and LSE entries; kv_end == nullptr: the plain kernel; lse != nullptr: the LSE form
+static int cross_attention_launch(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t Sq, int32_t Skv, int32_t D, int32_t dtype,
                                   float sm_scale, const int32_t* kv_begin, const int32_t* kv_end, int32_t heads_per_window,
                                   const svg_attn_layout_t* layout, void* stream) {
     if (!q || !k || !v || !o || BH <= 0 || Sq <= 0 || Skv <= 0) return SVG_ERR_BAD_ARG;
@@ -102,26 +119,30 @@ static int cross_attention_launch(const void* q, const void* k, const void* v, v
         if constexpr (decltype(d)::value != 128) {
             return SVG_ERR_UNSUPPORTED;
         } else {
-            auto launch = [&](auto windowed_c) -> int {
+            auto launch = [&](auto windowed_c, auto lse_c) -> int {
                 constexpr bool kWindowed = decltype(windowed_c)::value;
-                using Pol = CrossPolicy<T, kWindowed>;
+                constexpr bool kLse = decltype(lse_c)::value;
+                using Pol = std::conditional_t<kLse, CrossLsePolicy<T, kWindowed>, CrossPolicy<T, kWindowed>>;
                 typename Pol::Params p;
+                if constexpr (kLse) p.lse = lse;
                 if constexpr (kWindowed) p.kv_begin = kv_begin, p.kv_end = kv_end, p.heads_per_window = heads_per_window;
                 p.q = (const T*)q, p.k = (const T*)k, p.v = (const T*)v, p.o = (T*)o;
                 p.Sq = Sq, p.Skv = Skv, p.BH = BH, p.nqt = (Sq + Pol::BM - 1) / Pol::BM;
                 p.scale_log2 = sm_scale * 1.4426950408889634f;
                 p.lay = lay;
                 const int n_wg = (int)std::min<int64_t>((int64_t)BH * p.nqt, device_cus());
-                return launch_attn(cross_attn_m16_kernel<T, kWindowed>, dim3(n_wg), 512, attn_m16_lds_bytes(), (hipStream_t)stream, p);
+                if constexpr (kLse) return launch_attn(cross_attn_lse_m16_kernel<T, kWindowed>, dim3(n_wg), 512, attn_m16_lds_bytes(), (hipStream_t)stream, p);
+                else return launch_attn(cross_attn_m16_kernel<T, kWindowed>, dim3(n_wg), 512, attn_m16_lds_bytes(), (hipStream_t)stream, p);
             };
-            return kv_end ? launch(std::true_type{}) : launch(std::false_type{});
+            if (lse) return kv_end ? launch(std::true_type{}, std::true_type{}) : launch(std::false_type{}, std::true_type{});
+            return kv_end ? launch(std::true_type{}, std::false_type{}) : launch(std::false_type{}, std::false_type{});
         }
     });
 }
 
 extern "C" int svg_cross_attention(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t Sq, int32_t Skv, int32_t D,
                                    int32_t dtype, float sm_scale, const svg_attn_layout_t* layout, void* stream) {
-    return cross_attention_launch(q, k, v, o, BH, Sq, Skv, D, dtype, sm_scale, nullptr, nullptr, 1, layout, stream);
+    return cross_attention_launch(q, k, v, o, nullptr, BH, Sq, Skv, D, dtype, sm_scale, nullptr, nullptr, 1, layout, stream);
 }
 
 extern "C" int svg_cross_attention_pair(const void* q, const void* k_a, const void* v_a, const void* k_b, const void* v_b, void* o, int32_t BH,
@@ -168,5 +189,13 @@ extern "C" int svg_cross_attention_keyrange(const void* q, const void* k, const 
                                             int32_t heads_per_window, const svg_attn_layout_t* layout, void* stream) {
     if (!kv_end || heads_per_window <= 0) return SVG_ERR_BAD_ARG;
     if (BH > 0 && BH % heads_per_window != 0) return SVG_ERR_BAD_ARG;
-    return cross_attention_launch(q, k, v, o, BH, Sq, Skv, D, dtype, sm_scale, kv_begin, kv_end, heads_per_window, layout, stream);
+    return cross_attention_launch(q, k, v, o, nullptr, BH, Sq, Skv, D, dtype, sm_scale, kv_begin, kv_end, heads_per_window, layout, stream);
+}
+
+extern "C" int svg_cross_attention_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t Sq, int32_t Skv,
+                                       int32_t D, int32_t dtype, float sm_scale, const int32_t* kv_begin, const int32_t* kv_end,
+                                       int32_t heads_per_window, const svg_attn_layout_t* layout, void* stream) {
+    if (!lse) return SVG_ERR_BAD_ARG;
+    if (kv_end && (heads_per_window <= 0 || (BH > 0 && BH % heads_per_window != 0))) return SVG_ERR_BAD_ARG;
+    return cross_attention_launch(q, k, v, o, lse, BH, Sq, Skv, D, dtype, sm_scale, kv_end ? kv_begin : nullptr, kv_end, heads_per_window, layout, stream);
 }

@@ -118,6 +118,17 @@ struct HasAddOnStore : std::false_type {};
 template <typename P>
 struct HasAddOnStore<P, std::void_t<decltype(&P::add_on_store)>> : std::true_type {};
 
+// Row log-sum-exp (detected: a policy with a static lse_base(prm, ctx), cross_policy.h CrossLsePolicy; every other policy
+// compiles the epilogue it had): the epilogue also stores, per query row, lse = log sum_j exp(sm_scale * q.k_j) over the keys the row saw,
+// natural log, fp32, at lse_base(prm, ctx)[physical q row].  At the end of the tile loop the probabilities of a row are
+// 2^(s * scale_log2 - m_use - kBias) and l_tot is their sum, so lse = ln2 * (m_use + kBias + log2(l_tot)); a row without keys (l_tot == 0)
+// gives -inf.  Lanes 0..15 of a wave store (one lane per row, 2 x 16 stores per wave and q-tile), rows behind the q-tile's end are not
+// written; no LDS, no barrier.
+template <typename P, typename = void>
+struct HasRowLse : std::false_type {};
+template <typename P>
+struct HasRowLse<P, std::void_t<decltype(&P::lse_base)>> : std::true_type {};
+
 // Row cursor (detected: a policy with kRowCursor, band_policy.h BandPolicy; every other policy keeps kv_cursor_init / kv_phys and compiles
 // the request pipeline it had): the lane's key row is ONE variable stepped in place by P::row_walk_next, the decision between the
 // cheap step and the exact path is scalar, and the two byte offsets of a request are formed when the request pipeline takes the row.
@@ -670,6 +681,11 @@ __device__ __forceinline__ bool attn_m16_tile(const typename P::Params& prm, con
     for (int rb = 0; rb < 2; ++rb) {
         const float l_tot = MSUM ? acc_l[rb][0] : quad_group_sum(l_run[rb]);
         const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
+        if constexpr (HasRowLse<P>::value) {   // every lane of a row's quad group holds m_use and l_tot: the one with g4 == 0 stores
+            const int qp = P::q_phys(prm, ctx, wave * 32 + rb * 16 + n16);
+            if (g4 == 0 && qp >= 0)
+                P::lse_base(prm, ctx)[qp] = l_tot > 0.f ? 0.6931471805599453f * (m_use[rb] + kBias + __builtin_amdgcn_logf(l_tot)) : -INFINITY;
+        }
 #pragma unroll
         for (int db = 0; db < NDB; ++db) {
             typename E::v4 o4;

@@ -5,6 +5,7 @@
 // key-padding mask.  Logical key tile t is key tile t0 + t with t0 = begin / 64, so a left-padded window walks no masked tile; the (at
 // most two) edge tiles take the per-element path; nT == 0 for an empty window, whose rows come out as zeros.  The plain form's members are
 // empty bases and compile-time branches: its kernel is the one it was.
+// LSE form (svg_cross_attention_lse, CrossLsePolicy below): either of the two plus one fp32 per query row, the log-sum-exp of its scores.
 #pragma once
 #include "attn_core.h"
 
@@ -109,6 +110,18 @@ struct CrossPolicy : LayoutAccess<CrossPolicy<T, Windowed>> {
     }
     static __device__ __forceinline__ float score_fixup(const Params&, float s) { return s; }
     static __device__ __forceinline__ void notify(const Params&, const Ctx&) {}
+};
+
+// LSE form (svg_cross_attention_lse): the plain or windowed policy plus the row log-sum-exp (attn_m16.h: HasRowLse, switched on by
+// lse_base below) — what a caller needs to merge results computed over parts of the keys (svg_merge_attention_states).  lse is a
+// contiguous fp32 [BH, Sq] whatever the layout of q / o: it is small, and the merge reads it linearly.
+template <typename T, bool Windowed = false>
+struct CrossLsePolicy : CrossPolicy<T, Windowed> {
+    using Base = CrossPolicy<T, Windowed>;
+    struct Params : Base::Params {
+        float* lse;   // [BH, Sq]
+    };
+    static __device__ __forceinline__ float* lse_base(const Params& p, const typename Base::Ctx& c) { return p.lse + (size_t)c.head * (size_t)p.Sq; }
 };
 
 // Pair form (svg_cross_attention_pair): the plain policy run twice per q-tile, over key set A and then over key set B, the second pass

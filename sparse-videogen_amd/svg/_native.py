@@ -150,6 +150,9 @@ SIGNATURES = {
                                                _VP]),
     "svg_cross_attention_pair": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _F32, C.POINTER(AttnLayout),
                                            C.POINTER(AttnLayout), _VP]),
+    "svg_cross_attention_lse": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _F32, _VP, _VP, _I32, C.POINTER(AttnLayout),
+                                          _VP]),
+    "svg_merge_attention_states": (C.c_int, [_VP, _VP, _I32, _VP, _VP, _I32, _I32, _I32, _I32, C.POINTER(AttnLayout), _VP]),
     "svg_sample_mse_strided": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _F32, C.POINTER(ProfileDesc), _VP, _VP,
                                          _SZ, _VP, C.POINTER(AttnLayout), _VP]),
     "svg_band_attention_prescaled": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, C.POINTER(BandMask), C.POINTER(PermDesc), _VP]),
@@ -675,24 +678,28 @@ def cross_attention_supported(q: torch.Tensor, k: torch.Tensor) -> bool:
 
 
 def cross_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, sm_scale: Optional[float] = None, token_major_out: bool = False,
-                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    out: Optional[torch.Tensor] = None, return_lse: bool = False):
     """Dense attention of q [B, H, Sq, D] over k, v [B, H, Skv, D] (or [BH, S, D]; Sq != Skv allowed) -> o of q's shape: softmax(q k^T
     * sm_scale) v per head (svg_cross_attention: head_dim 128, bf16 / fp16).  Strided views with stride(-1) == 1 (projection outputs,
-    slices of a fused k/v projection) are read in place; views the layout cannot describe are copied.  token_major_out: as band_attention."""
-    return _cross_attention(q, k, v, None, None, sm_scale, token_major_out, out)
+    slices of a fused k/v projection) are read in place; views the layout cannot describe are copied.  token_major_out: as band_attention.
+    return_lse: (o, lse) with lse the row log-sum-exp of the scaled scores (natural log), contiguous fp32 of shape q.shape[:-1] — what
+    merge_attention_states takes (svg_cross_attention_lse); o has the same bits as without."""
+    return _cross_attention(q, k, v, None, None, sm_scale, token_major_out, out, return_lse)
 
 
 def cross_attention_keyrange(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_end: torch.Tensor, kv_begin: Optional[torch.Tensor] = None,
-                             sm_scale: Optional[float] = None, token_major_out: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                             sm_scale: Optional[float] = None, token_major_out: bool = False, out: Optional[torch.Tensor] = None,
+                             return_lse: bool = False):
     """cross_attention over one key window per group of heads (svg_cross_attention_keyrange): kv_end / kv_begin are int32 GPU tensors of n
     entries, BH % n == 0 (n = B: one window per video, the key-padding mask of a batch of prompts); heads [i * BH / n, (i + 1) * BH / n)
     attend to the keys [kv_begin[i], kv_end[i]) (kv_begin None: from key 0).  The kernel clamps the windows to 0 <= begin <= end <= Skv,
-    reads no key row outside a window and writes zeros for an empty one.  Layouts, token_major_out, out: as cross_attention."""
+    reads no key row outside a window and writes zeros for an empty one.  Layouts, token_major_out, out: as cross_attention.
+    return_lse: as cross_attention, over the window's keys; -inf for an empty window."""
     assert kv_end is not None
-    return _cross_attention(q, k, v, kv_begin, kv_end, sm_scale, token_major_out, out)
+    return _cross_attention(q, k, v, kv_begin, kv_end, sm_scale, token_major_out, out, return_lse)
 
 
-def _cross_attention(q, k, v, kv_begin, kv_end, sm_scale, token_major_out, out):
+def _cross_attention(q, k, v, kv_begin, kv_end, sm_scale, token_major_out, out, return_lse=False):
     """cross_attention (kv_end None), and cross_attention_keyrange"""
     lib = load()
     _gpu(q, k, v, out)
@@ -701,13 +708,20 @@ def _cross_attention(q, k, v, kv_begin, kv_end, sm_scale, token_major_out, out):
     Skv = k.shape[-2]
     BH = q.numel() // (Sq * D)
     scale = _sm_scale(sm_scale, D)
+    n = 1
     if kv_end is not None:
         _dev(kv_end, kv_begin)
         n = kv_end.numel()
         assert kv_end.dtype == torch.int32 and n > 0 and BH % n == 0, "kv_end: int32, BH % numel == 0"
         assert kv_begin is None or (kv_begin.dtype == torch.int32 and kv_begin.numel() == n), "kv_begin: int32, as many entries as kv_end"
+    # (contiguous [BH, Sq] whatever the layout of q / o; written whole by every launch, so a retry after a layout fall-back reuses it)
+    lse = torch.empty(q.shape[:-1], dtype=torch.float32, device=q.device) if return_lse else None
 
     def run(q, k, v, out):
+        if return_lse:
+            return _try_strided(q, k, v, out, token_major_out, "svg_cross_attention_lse", lambda o4, lay: lib.svg_cross_attention_lse(
+                q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), lse.data_ptr(), BH, Sq, Skv, D, _dtype_code(q), scale, _ptr(kv_begin),
+                _ptr(kv_end), BH // n, C.byref(lay), _stream()))
         if kv_end is None:
             return _try_strided(q, k, v, out, token_major_out, "svg_cross_attention", lambda o4, lay: lib.svg_cross_attention(
                 q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), BH, Sq, Skv, D, _dtype_code(q), scale, C.byref(lay), _stream()))
@@ -715,7 +729,50 @@ def _cross_attention(q, k, v, kv_begin, kv_end, sm_scale, token_major_out, out):
             q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), BH, Sq, Skv, D, _dtype_code(q), scale, _ptr(kv_begin), kv_end.data_ptr(),
             BH // n, C.byref(lay), _stream()))
 
-    return _run_or_copy(run, (q, k, v), out)
+    o = _run_or_copy(run, (q, k, v), out)
+    return (o, lse) if return_lse else o
+
+
+MERGE_MAX_PARTS = 8   # svg_merge_attention_states: the part pointers travel in the kernel arguments
+
+
+def merge_attention_states(o_parts: Sequence[torch.Tensor], lse_parts: Sequence[torch.Tensor], out: Optional[torch.Tensor] = None,
+                           token_major_out: bool = False, return_lse: bool = False):
+    """Combine n partial attention results of the SAME query rows over disjoint parts of the keys into the result over all of them
+    (svg_merge_attention_states): o_parts[i] [B, H, Sq, D] or [BH, Sq, D] (16-bit, D 64 / 128), lse_parts[i] fp32 of shape o.shape[:-1], as
+    cross_attention(..., return_lse=True) returns them.  All parts in one pass, fp32, one rounding: o = sum_i w_i o_i / sum_i w_i with w_i =
+    exp(lse_i - max lse).  At most MERGE_MAX_PARTS parts (ValueError).  out / token_major_out: as cross_attention; return_lse: (o, lse) with
+    the merged log-sum-exp."""
+    lib = load()
+    n = len(o_parts)
+    if not 1 <= n <= MERGE_MAX_PARTS or len(lse_parts) != n:
+        raise ValueError(f"merge_attention_states takes 1 to {MERGE_MAX_PARTS} parts with one lse each, got {n} and {len(lse_parts)}")
+    _gpu(*o_parts, *lse_parts, out)
+    x = o_parts[0]
+    Sq, D = x.shape[-2], x.shape[-1]
+    BH = x.numel() // (Sq * D)
+    for o_i, l_i in zip(o_parts, lse_parts):
+        assert o_i.shape == x.shape and o_i.dtype == x.dtype and l_i.shape == x.shape[:-1] and l_i.dtype == torch.float32
+    # (parts are contiguous by contract; one that is not — or not 16-byte aligned — is copied, as the cross-attention entries copy)
+    o_c = [t if t.is_contiguous() and t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format) for t in o_parts]
+    l_c = [t.contiguous() for t in lse_parts]
+    x4 = _view4(x)
+    if out is not None:
+        assert out.shape == x.shape and out.dtype == x.dtype
+    o4 = _view4(out) if out is not None else (token_major_empty(x4) if token_major_out else torch.empty(x4.shape, dtype=x.dtype, device=x.device))
+    direct = _strided_ok(o4)
+    dst4 = o4 if direct else torch.empty(x4.shape, dtype=x.dtype, device=x.device)
+    lse = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device) if return_lse else None
+    op = (C.c_void_p * MERGE_MAX_PARTS)(*[t.data_ptr() for t in o_c], *([None] * (MERGE_MAX_PARTS - n)))
+    lp = (C.c_void_p * MERGE_MAX_PARTS)(*[t.data_ptr() for t in l_c], *([None] * (MERGE_MAX_PARTS - n)))
+    lay = attn_layout(x4, x4, x4, dst4)
+    rc = lib.svg_merge_attention_states(C.cast(op, _VP), C.cast(lp, _VP), n, dst4.data_ptr(), _ptr(lse), BH, Sq, D, _dtype_code(x), C.byref(lay),
+                                        _stream())
+    _check(rc, "svg_merge_attention_states")
+    if not direct:   # an output the layout cannot describe
+        o4.copy_(dst4)
+    o = out if out is not None else (o4 if x.dim() == 4 else o4.squeeze(0))
+    return (o, lse) if return_lse else o
 
 
 def _run_or_copy(run, tensors, out):

@@ -7,6 +7,10 @@ exchange is the one the next operator needs: `to_out` consumes all heads of a to
 7 x 91 MB inbound per GPU, spread over the 7 xGMI links of the full mesh).  The reference has no multi-GPU version of
 this path (its deprecated forks use xfuser ring/Ulysses with dense attention); parity is defined as equality with the
 single-GPU result, which is bitwise because per-head arithmetic does not change.
+
+Dense attention can also stay TOKEN-sharded (`token_sharded_dense_attention`): every rank keeps all heads of its tokens, sees the
+other ranks' keys shard by shard and merges the partial results with their row log-sum-exp — any head count, every rank busy, the
+exchange of the next shard behind the compute of this one; equal to the single-GPU result to rounding, not bitwise.
 """
 from __future__ import annotations
 
@@ -217,6 +221,109 @@ def heads_to_tokens(o_local: torch.Tensor, num_heads: int, group=None, unit: int
         inv[torch.tensor(order)] = torch.arange(num_heads)
         out = out.index_select(0, inv.to(out.device))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# token-sharded DENSE attention: no exchange of q or o at all — every rank keeps all heads of its own tokens and sees the other ranks'
+# keys shard by shard, merging the partial results with their row log-sum-exp (svg_cross_attention_lse + svg_merge_attention_states).
+# ref: the context-parallel dense attention of svg/models/wan_orig/distributed/xdit_context_parallel.py:120-169 (xfuser ring / Ulysses),
+#      flashinfer's run(..., return_lse=True) + merge_state in svg/kernels/ops/attention_ops.py:178-188
+# ---------------------------------------------------------------------------------------------------------------
+MERGE_MAX_PARTS = 8   # svg_merge_attention_states (include/svg_attn.h): parts of one N-way merge
+
+
+def _native_attn(q, k, v, return_lse=False):
+    from . import _native
+
+    return _native.cross_attention(q, k, v, return_lse=return_lse)
+
+
+def _native_merge(o_parts, lse_parts):
+    from . import _native
+
+    return _native.merge_attention_states(o_parts, lse_parts)
+
+
+def token_sharded_dense_attention(q_local: torch.Tensor, k_local: torch.Tensor, v_local: torch.Tensor, num_tokens: int, group=None,
+                                  unit: int = 1, overlap: bool = True, attn_fn: Optional[Callable] = None,
+                                  merge_fn: Optional[Callable] = None) -> torch.Tensor:
+    """Dense attention over a sequence that lives token-sharded: q_local, k_local, v_local [..., H, S_r, D] are ALL heads of this rank's
+    tokens `token_range(num_tokens, rank, world, unit)` (ragged shards allowed); returns the attention output of this rank's rows over
+    ALL num_tokens keys, [..., H, S_r, D].  Nothing is sharded by heads, so it works for any head count (12 heads on 8 GPUs) and leaves
+    no rank idle.
+    overlap=False (the baseline): k and v are all-gathered, then ONE attn_fn(q, k, v) launch.
+    overlap=True: world steps; at step j the rank computes (o_j, lse_j) = attn_fn(q, k_s, v_s, True) of its rows over the shard of rank
+    s = (rank - j) mod world while the shard of step j + 1 is already in flight — every rank sends its OWN shard directly to the rank
+    that needs it next (all_to_all_single with one non-empty split: a shift by j; no forwarding around a ring, every link carries a
+    shard once).  At the end ONE merge_fn(o_parts, lse_parts) over the parts ordered by SOURCE rank, so the arithmetic of a row does not
+    depend on the rank that computed it.  world > MERGE_MAX_PARTS: ValueError (the N-way merge takes at most 8 parts).
+    attn_fn(q, k, v, return_lse=False) -> o or (o, lse) and merge_fn(o_parts, lse_parts) -> o default to the native calls
+    (_native.cross_attention, _native.merge_attention_states); they exist so that the schedule can be tested without a GPU.
+    Unlike head sharding, the result equals the single-GPU one TO ROUNDING, not bit for bit: with overlap=True every part is rounded to
+    the 16-bit type before the merge rounds once more (rel. L2 sqrt(2) times that of one call); overlap=False runs the
+    single-GPU arithmetic on this rank's rows."""
+    attn_fn = attn_fn or _native_attn
+    merge_fn = merge_fn or _native_merge
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    tr = [token_range(num_tokens, r, world, unit) for r in range(world)]
+    n_tok = [b - a for a, b in tr]
+    S_me = n_tok[rank]
+    assert q_local.shape[-2] == S_me and k_local.shape == v_local.shape and k_local.shape[-2] == S_me, (
+        f"rank {rank} holds {q_local.shape[-2]} / {k_local.shape[-2]} tokens, token_range says {S_me}")
+    if overlap and world > MERGE_MAX_PARTS:
+        raise ValueError(f"token_sharded_dense_attention(overlap=True): {world} ranks, but merge_attention_states takes at most "
+                         f"{MERGE_MAX_PARTS} parts — use a group of at most {MERGE_MAX_PARTS} ranks or overlap=False")
+    if world == 1:
+        return attn_fn(q_local, k_local, v_local)
+    lead = tuple(k_local.shape[:-2])
+    D = k_local.shape[-1]
+    per_tok = 2 * D
+    for x in lead:
+        per_tok *= x
+    kv_shape = lambda n: (2,) + lead + (n, D)   # noqa: E731  (k and v of a shard travel as one message)
+
+    if not overlap:
+        mx = max(n_tok)
+        pad = torch.zeros(kv_shape(mx), dtype=k_local.dtype, device=k_local.device)
+        pad[0][..., :S_me, :] = k_local
+        pad[1][..., :S_me, :] = v_local
+        full = torch.empty((world * 2,) + kv_shape(mx)[1:], dtype=k_local.dtype, device=k_local.device)   # concatenated along dim 0
+        dist.all_gather_into_tensor(full, pad, group=group, async_op=True).wait()
+        full = full.view((world,) + kv_shape(mx))
+        if S_me == 0:
+            return torch.empty_like(q_local)
+        k_all = torch.cat([full[r, 0][..., :n_tok[r], :] for r in range(world)], dim=-2)
+        v_all = torch.cat([full[r, 1][..., :n_tok[r], :] for r in range(world)], dim=-2)
+        return attn_fn(q_local, k_all, v_all)
+
+    send = torch.stack([k_local, v_local]).contiguous().view(-1)
+    empty = send[:0]
+
+    def shift(j):
+        """this rank's shard to rank + j, the shard of rank - j from its owner: (source rank, receive buffer, work handle)"""
+        dst, src = (rank + j) % world, (rank - j) % world
+        recv = torch.empty(n_tok[src] * per_tok, dtype=send.dtype, device=send.device)
+        ins, outs = [0] * world, [0] * world
+        ins[dst], outs[src] = send.numel(), recv.numel()
+        work = dist.all_to_all_single(recv, send, output_split_sizes=outs, input_split_sizes=ins, group=group, async_op=True)
+        return src, recv, work
+
+    parts = {}
+    nxt = shift(1)
+    for j in range(world):
+        if j == 0:
+            src, k_s, v_s = rank, k_local, v_local
+        else:
+            src, recv, work = nxt
+            work.wait()
+            nxt = shift(j + 1) if j + 1 < world else None     # in flight while step j computes
+            k_s, v_s = recv.view(kv_shape(n_tok[src])).unbind(0)
+        if S_me > 0 and n_tok[src] > 0:                        # (an empty shard has no keys: no part)
+            parts[src] = attn_fn(q_local, k_s, v_s, True)
+    if S_me == 0:
+        return torch.empty_like(q_local)
+    order = sorted(parts)
+    return merge_fn([parts[r][0] for r in order], [parts[r][1] for r in order])
 
 
 class ExchangeBuffers:
