@@ -277,7 +277,8 @@ int svg_cross_attention_pair(const void* q, const void* k_a, const void* v_a, co
  * o has the bits of the entry without lse (same kernel body; the epilogue stores one more fp32 per row).  A row without keys (an empty
  * window) has lse = -inf and o = 0.  lse NULL: SVG_ERR_BAD_ARG; kv_end given with heads_per_window <= 0 or BH % heads_per_window != 0:
  * SVG_ERR_BAD_ARG (kv_end NULL: kv_begin and heads_per_window are ignored); every other check is that of svg_cross_attention, all on the
- * host before any launch.  The band, variable-block and pair entries do not return lse. */
+ * host before any launch.  Band and variable-block attention: include/svg_attn_sparse_lse.h (included at the end of this file); the pair entry
+ * does not return lse. */
 int svg_cross_attention_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t Sq, int32_t Skv, int32_t D,
                             int32_t dtype, float sm_scale, const int32_t* kv_begin, const int32_t* kv_end /* NULL: all keys */,
                             int32_t heads_per_window, const svg_attn_layout_t* layout, void* stream);
@@ -747,4 +748,7 @@ int svg_debug_wg_trace(uint64_t* out, int32_t n_workgroups);
 #ifdef __cplusplus
 }
 #endif
+
+/* the row log-sum-exp forms of band and variable-block attention: declared in a header of their own, part of this interface */
+#include "svg_attn_sparse_lse.h"
 #endif /* SVG_ATTN_H_ */

@@ -1,6 +1,7 @@
 // SVG1 band (block-sparse) and dense attention for gfx950: the kernels that run the bodies of attn_core.h / attn_m16.h on the band
 // policy (band_policy.h), the counter pool of the queue launches, the svg_band_attention* entries, the completion-counter waiters and
-// the svg_debug_* trace readers.  (One-wave-per-SIMD body: attention_w4.hip; fp8: attention_f8.hip; SVG2: attention_varblock.hip.)
+// the svg_debug_* trace readers; svg_band_attention_lse (row log-sum-exp output).  (One-wave-per-SIMD body: attention_w4.hip; fp8:
+// attention_f8.hip; SVG2: attention_varblock.hip.)
 #include <algorithm>
 #include <atomic>
 #include <mutex>
@@ -72,6 +73,15 @@ template <typename T>
 __global__ __launch_bounds__(512, 2) void band_attn_m16_kernel(typename BandPolicy<T, 128, 8>::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     attn_body_m16<T, BandPolicy<T, 128, 8>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
+}
+// LSE form (svg_band_attention_lse): band_attn_m16_kernel on BandLsePolicy — the same template arguments, SPEC and the replay counter
+// included, so o keeps the bits of the plain entry; the epilogue of attn_m16_tile also stores one fp32 per query row.  A q-tile that fails
+// its validation returns before the epilogue and stores neither o nor lse; its replay stores both.  Static mapping only (the queue kernel
+// is bit-identical to it).  (Its own kernel template: the kernels above and below keep their symbols and their listings.)
+template <typename T>
+__global__ __launch_bounds__(512, 2) void band_attn_lse_m16_kernel(typename BandLsePolicy<T>::Params prm) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    attn_body_m16<T, BandLsePolicy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
 }
 // pre-scaled q on the 16x16x32 body (PRE form of attn_body_m16)
 template <typename T>
@@ -284,6 +294,20 @@ static int band_dispatch(const void* q, const void* k, const void* v, void* o, i
     if (opts.done && (int64_t)done_words < (int64_t)BH * (opts.done_nseg + 1)) return SVG_ERR_WORKSPACE;   // segment counters + one hidden counter per head
     if (opts.strided && (rc = layout_from_abi(layout, BH, BH, S, S, D, q, k, v, o, opts.lay)) != SVG_OK) return rc;
     const hipStream_t st = (hipStream_t)stream;
+    if (opts.lse) {   // svg_band_attention_lse: the default head_dim-128 body only, on the static mapping
+        if (D != 128 || variant != kBandAuto || opts.done || opts.prescaled || opts.use_alt) return SVG_ERR_UNSUPPORTED;
+        return dispatch_td(dtype, D, [&](auto t, auto d) -> int {
+            using T = decltype(t);
+            if constexpr (decltype(d)::value != 128) {
+                return SVG_ERR_UNSUPPORTED;
+            } else {
+                using Pol = BandLsePolicy<T>;
+                typename Pol::Params p = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
+                p.lse = opts.lse;
+                return launch_attn(band_attn_lse_m16_kernel<T>, dim3(p.nqt * BH), 512, attn_m16_lds_bytes() + kTailLds, st, p);
+            }
+        });
+    }
     int trace_abl = -1;
     if ((variant & 0xFF) == 32) {   // diagnostics builds: traced one-wave-per-SIMD kernel, bits 8..11 = its timing ablation
         opts.trace = true;
@@ -389,6 +413,16 @@ extern "C" int svg_band_attention_strided(const void* q, const void* k, const vo
                                           const svg_attn_layout_t* layout, void* stream) {
     BandOpts opts;
     opts.strided = true;
+    return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, 0, layout, stream);
+}
+
+extern "C" int svg_band_attention_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S, int32_t D,
+                                      int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
+                                      const svg_attn_layout_t* layout, void* stream) {
+    if (!lse) return SVG_ERR_BAD_ARG;
+    BandOpts opts;
+    opts.lse = lse;
+    opts.strided = layout != nullptr;
     return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, 0, layout, stream);
 }
 

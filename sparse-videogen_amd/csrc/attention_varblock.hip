@@ -1,5 +1,6 @@
 // SVG2 variable-block attention for gfx950: the kernels that run the bodies of attn_core.h / attn_m16.h / attn_f8.h on the policy of
-// varblock_policy.h, the planning / launch-order kernels in front of them, the svg_varblock_* entries.  (Band family: attention.hip.)
+// varblock_policy.h, the planning / launch-order kernels in front of them, the svg_varblock_* entries (svg_varblock_attention_lse: row
+// log-sum-exp output).  (Band family: attention.hip.)
 #include <utility>
 
 #include "attn_f8.h"
@@ -26,6 +27,14 @@ template <typename T>
 __global__ __launch_bounds__(512, 2) void varblock_attn_m16_kernel(typename VarblockPolicy<T, 128, 8>::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     attn_body_m16<T, VarblockPolicy<T, 128, 8>>(prm, smem, smem + attn_m16_lds_bytes());
+}
+
+// LSE form (svg_varblock_attention_lse): the kernel above on VarblockLsePolicy — the epilogue of attn_m16_tile also stores one fp32 per
+// query row.  (Its own kernel template: varblock_attn_m16_kernel keeps its symbol and its listing.)
+template <typename T>
+__global__ __launch_bounds__(512, 2) void varblock_attn_lse_m16_kernel(typename VarblockLsePolicy<T>::Params prm) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    attn_body_m16<T, VarblockLsePolicy<T>>(prm, smem, smem + attn_m16_lds_bytes());
 }
 
 #ifdef SVG_ABLATIONS
@@ -470,6 +479,7 @@ struct VbCall {
     int order_mode = 0;                             // 0: longest-first + remainder packing, 1: longest-first, 2: similarity order
     const AttnLayout* lay = nullptr;                // strided tensors (svg_varblock_attention_strided); nullptr: contiguous [H, S, D]
     F8GArgs f8{};                                   // kF8: the quantised tensors and scales of f8g_quantize
+    float* lse = nullptr;                           // kM16: row log-sum-exp output, contiguous fp32 [Hq, Sq] (svg_varblock_attention_lse), or nullptr
 };
 
 // The workspace of a call, and the one definition of its layout (_native.varblock_launch_order / varblock_partners read it at fixed
@@ -605,8 +615,15 @@ static int run_varblock(const VbCall& c) {
                 return SVG_ERR_UNSUPPORTED;   // diagnostics builds only (-DSVG_ABLATIONS)
             }
             if constexpr (D == 128) {
+                if (body == VbBody::kM16 && c.lse) {   // the same plan, launch order and grid; the policy that also stores lse
+                    typename VarblockLsePolicy<T>::Params pl;
+                    static_cast<typename VarblockPolicy<T, 128, 8>::Params&>(pl) = p;
+                    pl.lse = c.lse;
+                    return launch_attn(varblock_attn_lse_m16_kernel<T>, grid, 512, attn_m16_lds_bytes() + lds_vb, st, pl);
+                }
                 if (body == VbBody::kM16) return launch_attn(varblock_attn_m16_kernel<T>, grid, 512, attn_m16_lds_bytes() + lds_vb, st, p);
             }
+            if (c.lse) return SVG_ERR_UNSUPPORTED;
             return launch_attn(varblock_attn_pp2_kernel<T, D>, grid, 512, attn_pp2_lds_bytes<D>() + lds_vb, st, p);
         }
     }
@@ -674,6 +691,7 @@ static int varblock_entry(VbCall& c, int variant, const svg_attn_layout_t* layou
         c.lay = &lay;
     }
     if (!vb_decode_variant(variant, c)) return SVG_ERR_BAD_ARG;
+    if (c.lse && (c.D != 128 || c.body != VbBody::kM16 || c.trace || c.block_row_order)) return SVG_ERR_UNSUPPORTED;   // (fp32 etc.: dispatch_td)
     const bool two_phase = c.body == VbBody::kM16 || c.body == VbBody::kPP2;
     if (c.lay && !(two_phase && !c.trace)) return SVG_ERR_UNSUPPORTED;   // strided tensors: the two-phase bodies only (see svg_attn_layout_t)
     return dispatch_td(c.dtype, c.D, [&](auto t, auto d) { return run_varblock<decltype(t), decltype(d)::value>(c); });
@@ -698,6 +716,19 @@ extern "C" int svg_varblock_attention_strided(const void* q, const void* k, cons
     VbCall c{q, k, v, o, Hq, Hkv, Sq, Skv, D, dtype, sm_scale, block_map, q_sizes, k_sizes, QB, KB, q_row_idx, kv_row_idx, workspace,
              workspace_bytes, (hipStream_t)stream};
     return varblock_entry(c, -1, layout);
+}
+
+// always the two-phase 16x16x32 body in its default launch order: what variant 3 selects, also where -1 would pick 128-row tiles
+extern "C" int svg_varblock_attention_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t Hq, int32_t Hkv,
+                                          int32_t Sq, int32_t Skv, int32_t D, int32_t dtype, float sm_scale, const uint8_t* block_map,
+                                          const int32_t* q_sizes, const int32_t* k_sizes, int32_t QB, int32_t KB,
+                                          const int32_t* q_row_idx, const int32_t* kv_row_idx, void* workspace, size_t workspace_bytes,
+                                          const svg_attn_layout_t* layout, void* stream) {
+    if (!lse) return SVG_ERR_BAD_ARG;
+    VbCall c{q, k, v, o, Hq, Hkv, Sq, Skv, D, dtype, sm_scale, block_map, q_sizes, k_sizes, QB, KB, q_row_idx, kv_row_idx, workspace,
+             workspace_bytes, (hipStream_t)stream};
+    c.lse = lse;
+    return varblock_entry(c, 3, layout);
 }
 
 extern "C" int svg_varblock_attention_fp8(const void* q, const void* k, const void* v, void* o, int32_t Hq, int32_t Hkv, int32_t Sq,

@@ -21,6 +21,7 @@ struct BandOpts {
     // device switch (svg_band_attention_switch*): `*use_alt != 0` on the device selects alt_mask without the layout permutation
     const svg_band_mask_t* alt_mask = nullptr;
     const int32_t* use_alt = nullptr;
+    float* lse = nullptr;      // row log-sum-exp output, contiguous fp32 [BH, S] (svg_band_attention_lse: BandLsePolicy), or nullptr
 };
 
 // the mask and the head permutation of a band call over S rows (mask != nullptr)
@@ -477,6 +478,18 @@ struct BandPolicy : LayoutAccess<BandPolicy<T, D, NW, RB>> {
             }
         }
     }
+};
+
+// LSE form (svg_band_attention_lse): the head_dim-128 band policy of the 16x16x32 body plus the row log-sum-exp (attn_m16.h: HasRowLse,
+// switched on by lse_base below), as CrossLsePolicy adds it to the cross policy.  lse is a contiguous fp32 [BH, S] whatever the layout of
+// q / o; the index inside a head is the physical q row q_phys returns — the row o is written to, also on a token-major head.
+template <typename T>
+struct BandLsePolicy : BandPolicy<T, 128, 8> {
+    using Base = BandPolicy<T, 128, 8>;
+    struct Params : Base::Params {
+        float* lse;   // [BH, S]
+    };
+    static __device__ __forceinline__ float* lse_base(const Params& p, const typename Base::Ctx& c) { return p.lse + (size_t)c.head * (size_t)p.S; }
 };
 
 // =====================================================================================================

@@ -236,6 +236,19 @@ struct VarblockPolicy : LayoutAccess<VarblockPolicy<T, D, NW>> {
     static __device__ __forceinline__ float score_fixup(const Params&, float s) { return s; }
 };
 
+// LSE form (svg_varblock_attention_lse): the head_dim-128 policy of the 16x16x32 body plus the row log-sum-exp (attn_m16.h: HasRowLse,
+// switched on by lse_base below), as CrossLsePolicy adds it to the cross policy.  lse is a contiguous fp32 [Hq, Sq] whatever the layout
+// of q / o, one row per q head (GQA: not per kv head); the index inside a head is the row q_phys returns — the caller's row order under
+// q_row_idx, for both members of a packed q-tile.  A row whose block-row has no key (or only empty key clusters) gets -inf.
+template <typename T>
+struct VarblockLsePolicy : VarblockPolicy<T, 128, 8> {
+    using Base = VarblockPolicy<T, 128, 8>;
+    struct Params : Base::Params {
+        float* lse;   // [Hq, Sq]
+    };
+    static __device__ __forceinline__ float* lse_base(const Params& p, const typename Base::Ctx& c) { return p.lse + (size_t)c.hq * (size_t)p.Sq; }
+};
+
 static inline int vb_policy_lds(int kb_cap) { return (2 * (kb_cap + 2) + 32) * (int)sizeof(int32_t); }
 
 }  // namespace svg

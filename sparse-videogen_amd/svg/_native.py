@@ -208,6 +208,17 @@ SIGNATURES = {
 SVG_ABI_VERSION = 4   # include/svg_attn.h
 
 
+# include/svg_attn_sparse_lse.h: the row log-sum-exp forms of band and variable-block attention.  A table of their own, as the header is:
+# tests/test_entry_validation_cpu.py pins a validation table to every svg_band_attention* / svg_varblock_attention* name of SIGNATURES; the
+# table (and the prototype check) of these two is tests/test_sparse_attention_lse_cpu.py.  load() types both tables.
+SPARSE_LSE_SIGNATURES = {
+    "svg_band_attention_lse": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _F32, C.POINTER(BandMask), C.POINTER(PermDesc),
+                                         C.POINTER(AttnLayout), _VP]),
+    "svg_varblock_attention_lse": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _F32, _VP, _VP, _VP, _I32, _I32,
+                                             _VP, _VP, _VP, _SZ, C.POINTER(AttnLayout), _VP]),
+}
+
+
 def lib_path() -> Path:
     return Path(os.environ.get("SVG_ATTN_LIB", str(_LIB_PATH)))
 
@@ -220,7 +231,7 @@ def load(strict: bool = True) -> Optional[C.CDLL]:
     p = lib_path()
     try:
         lib = C.CDLL(str(p))
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **SPARSE_LSE_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -409,7 +420,7 @@ def band_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Band
                    head_perm_flag: Optional[torch.Tensor] = None, vid0: int = 0, num_frame: int = 1,
                    frame_size: int = 1, variant: int = 0, out: Optional[torch.Tensor] = None,
                    done: Optional[torch.Tensor] = None, done_nseg: int = 1, q_prescaled: bool = False,
-                   token_major_out: bool = False) -> torch.Tensor:
+                   token_major_out: bool = False, return_lse: bool = False):
     """q, k, v: [B, H, S, D] (or [BH, S, D]) bf16/fp16 GPU tensors -> o of the same shape.
     Strided views (last dimension contiguous — e.g. `proj(x).unflatten(2, (H, -1)).transpose(1, 2)`, or a slice of a fused QKV
     projection) are read in place by svg_band_attention_strided where it exists (head_dim 128, default schedule, plain q, no completion
@@ -419,9 +430,45 @@ def band_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Band
     writes): svg_band_attention_prescaled, default schedule only.
     done: int32 [BH * (done_nseg + 1)] zeroed completion counters (svg_band_attention_notify[_seg]; see band_notify_target /
     band_notify_layout / wait_counters / notify_counters): counter (h, s) at done[h * done_nseg + s], the last BH words are scratch
-    of the library (hidden per-head counters of heads that run with the fused layout permutation)."""
+    of the library (hidden per-head counters of heads that run with the fused layout permutation).
+    return_lse: (o, lse) with lse the row log-sum-exp of the scaled scores over the keys the mask gives the row (natural log), contiguous
+    fp32 of shape q.shape[:-1], in the caller's row order — what merge_attention_states takes (svg_band_attention_lse: head_dim 128,
+    default schedule, plain q, no completion counters; anything else raises ValueError); o has the same bits as without."""
+    if return_lse:
+        if variant != 0 or done is not None or q_prescaled or q.shape[-1] != 128:
+            raise ValueError("band_attention(return_lse=True): head_dim 128 on the default schedule (variant 0) with a plain q and no "
+                             f"completion counters; got D = {q.shape[-1]}, variant = {variant}, done = {done is not None}, "
+                             f"q_prescaled = {q_prescaled}")
+        return _band_attention_lse(q, k, v, mask, sm_scale, head_perm_flag, vid0, num_frame, frame_size, out, token_major_out)
     return _band_attention(q, k, v, mask, None, None, sm_scale, head_perm_flag, vid0, num_frame, frame_size, variant, out, done, done_nseg,
                            q_prescaled, token_major_out)
+
+
+def _band_attention_lse(q, k, v, mask, sm_scale, head_perm_flag, vid0, num_frame, frame_size, out, token_major_out):
+    """band_attention(return_lse=True): svg_band_attention_lse — without a layout for contiguous tensors, on views otherwise; what the
+    layout cannot describe is copied.  Never the entry without lse."""
+    lib = load()
+    _dev(head_perm_flag)
+    _gpu(q, k, v, out)
+    assert q.shape == k.shape == v.shape and q.dtype == k.dtype == v.dtype
+    S, D = q.shape[-2], q.shape[-1]
+    BH = q.numel() // (S * D)
+    scale = _sm_scale(sm_scale, D)
+    perm = _perm_arg(head_perm_flag, BH, vid0, num_frame, frame_size)
+    # (contiguous [BH, S] whatever the layout of q / o; written whole by every launch, so a retry after a layout fall-back reuses it)
+    lse = torch.empty(q.shape[:-1], dtype=torch.float32, device=q.device)
+
+    def run(q, k, v, out):
+        if q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and (out.is_contiguous() if out is not None else not token_major_out):
+            o = torch.empty_like(q) if out is None else out
+            _check(lib.svg_band_attention_lse(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), BH, S, D, _dtype_code(q),
+                                              scale, C.byref(mask), perm, None, _stream()), "svg_band_attention_lse")
+            return o
+        return _try_strided(q, k, v, out, token_major_out, "svg_band_attention_lse", lambda o4, lay: lib.svg_band_attention_lse(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), lse.data_ptr(), BH, S, D, _dtype_code(q), scale, C.byref(mask), perm,
+            C.byref(lay), _stream()))
+
+    return _run_or_copy(run, (q, k, v), out), lse
 
 
 def _band_attention(q, k, v, mask, alt_mask, use_alt_flag, sm_scale, head_perm_flag, vid0, num_frame, frame_size, variant, out, done,
@@ -819,7 +866,7 @@ def varblock_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_
                        k_sizes: torch.Tensor, sm_scale: Optional[float] = None, q_row_idx: Optional[torch.Tensor] = None,
                        kv_row_idx: Optional[torch.Tensor] = None, variant: int = -1, fp8: bool = False,
                        workspace: Optional[torch.Tensor] = None, token_major_out: bool = False,
-                       rows_covered: bool = False) -> torch.Tensor:
+                       rows_covered: bool = False, return_lse: bool = False):
     """q: [Hq, Sq, D], k/v: [Hkv, Skv, D] (or [B, H, S, D]: heads = B * H); block_map bool [Hkv, QB, KB]; sizes int32 [Hkv, QB] /
     [Hkv, KB].  -> o of q's shape.
     fp8=True: e4m3 QK^T / PV (svg_varblock_attention_fp8, D = 128, default schedule only).
@@ -828,7 +875,17 @@ def varblock_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_
     Strided views / token_major_out: as band_attention (svg_varblock_attention_strided: head_dim 128, variant -1 on block-rows large
     enough for the default body, 16-bit).
     rows_covered: the caller guarantees sum(q_sizes[h]) == Sq for every head (k-means cluster sizes do), so every output row is
-    written by the kernel and the output is not zero-filled first (a 2 S H D-byte memset per call otherwise)."""
+    written by the kernel and the output is not zero-filled first (a 2 S H D-byte memset per call otherwise).
+    return_lse: (o, lse) with lse the row log-sum-exp of the scaled scores over the keys the block map gives the row (natural log),
+    contiguous fp32 of shape q.shape[:-1] (per q head), in the caller's row order; -inf for a row that sees no key and, without
+    rows_covered, for a row no block-row covers (svg_varblock_attention_lse: head_dim 128, 16-bit, ALWAYS the two-phase body of variant
+    3 — variant -1, 3 or 8; anything else raises ValueError); o has the bits of variant 3."""
+    if return_lse:
+        if fp8 or variant not in (-1, 3, 8) or q.shape[-1] != 128:
+            raise ValueError("varblock_attention(return_lse=True): head_dim 128, 16-bit, variant -1 / 3 / 8 (the two-phase 16x16x32 body); "
+                             f"got D = {q.shape[-1]}, variant = {variant}, fp8 = {fp8}")
+        return _varblock_attention_lse(q, k, v, block_map, q_sizes, k_sizes, sm_scale, q_row_idx, kv_row_idx, workspace, token_major_out,
+                                       rows_covered)
     lib = load()
     _dev(block_map, q_sizes, k_sizes, q_row_idx, kv_row_idx)
     _gpu(q, k, v)
@@ -885,6 +942,49 @@ def varblock_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_
                                     _stream())
     _check(rc, "svg_varblock_attention")
     return o
+
+
+def _varblock_attention_lse(q, k, v, block_map, q_sizes, k_sizes, sm_scale, q_row_idx, kv_row_idx, workspace, token_major_out, rows_covered):
+    """varblock_attention(return_lse=True): svg_varblock_attention_lse — without a layout for contiguous tensors, on views otherwise; what
+    the layout cannot describe is copied.  Never an entry without lse."""
+    lib = load()
+    _dev(block_map, q_sizes, k_sizes, q_row_idx, kv_row_idx)
+    _gpu(q, k, v)
+    Sq, D = q.shape[-2], q.shape[-1]
+    Skv = k.shape[-2]
+    Hq, Hkv = q.numel() // (Sq * D), k.numel() // (Skv * D)
+    QB, KB = q_sizes.shape[-1], k_sizes.shape[-1]
+    assert block_map.shape == (Hkv, QB, KB) and block_map.dtype in (torch.bool, torch.uint8)
+    assert q_sizes.dtype == torch.int32 and k_sizes.dtype == torch.int32
+    if q_row_idx is not None:
+        assert q_row_idx.dtype == torch.int32 and q_row_idx.shape == (Hq, Sq)
+    if kv_row_idx is not None:
+        assert kv_row_idx.dtype == torch.int32 and kv_row_idx.shape == (Hkv, Skv)
+    scale = _sm_scale(sm_scale, D)
+    need = int(lib.svg_varblock_workspace_bytes(Hq, Hkv, QB, KB, Sq))
+    ws = torch.empty(need, dtype=torch.uint8, device=q.device) if workspace is None else workspace
+    _dev(ws)
+    assert ws.dtype == torch.uint8 and ws.numel() >= need
+    # (contiguous [Hq, Sq] whatever the layout of q / o; rows the kernel does not write: -inf where o holds zeros)
+    lse = torch.empty(q.shape[:-1], dtype=torch.float32, device=q.device)
+    if not rows_covered:
+        lse.fill_(float("-inf"))
+
+    def launch(q, k, v, o, lay):
+        if not rows_covered:
+            o.zero_()
+        return lib.svg_varblock_attention_lse(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), Hq, Hkv, Sq, Skv, D,
+                                              _dtype_code(q), scale, block_map.data_ptr(), q_sizes.data_ptr(), k_sizes.data_ptr(), QB, KB,
+                                              _ptr(q_row_idx), _ptr(kv_row_idx), ws.data_ptr(), ws.numel(), lay, _stream())
+
+    def run(q, k, v, out):
+        if q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and not token_major_out:
+            o = torch.empty_like(q)
+            _check(launch(q, k, v, o, None), "svg_varblock_attention_lse")
+            return o
+        return _try_strided(q, k, v, None, token_major_out, "svg_varblock_attention_lse", lambda o4, lay: launch(q, k, v, o4, C.byref(lay)))
+
+    return _run_or_copy(run, (q, k, v), None), lse
 
 
 def varblock_workspace(Hq: int, Hkv: int, QB: int, KB: int, Sq: int, device) -> torch.Tensor:

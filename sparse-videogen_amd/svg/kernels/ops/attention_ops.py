@@ -71,8 +71,11 @@ def init_sparse_attn(len_text_prompt: int, num_frames: int, num_tokens_per_frame
 
 
 def sparse_attn_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, metadata: FAMetadata,
-                        sparse_pattern: str = "temporal") -> torch.Tensor:
-    """ref: attention_ops.py:139-197"""
+                        sparse_pattern: str = "temporal", return_lse: bool = False):
+    """ref: attention_ops.py:139-197
+    return_lse: also the row log-sum-exp of the scaled scores, fp32 [seq_len, num_heads] (head_dim 128) — what the reference's
+    `run(..., return_lse=True)` hands merge_state (attention_ops.py:178-188), except that it is the NATURAL logarithm where flashinfer's
+    is base 2 (lse_flashinfer = lse / ln 2); _native.merge_attention_states takes it as it is."""
     assert sparse_pattern in ["temporal", "spatial"]
     indptr, indices, (R, Cb) = metadata.temporal_mask_metadata if sparse_pattern == "temporal" else metadata.spatial_mask_metadata
     L = metadata.len_text_promt
@@ -83,5 +86,8 @@ def sparse_attn_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, metad
     MB, NB = video // R, video // Cb
     bm, qs, ks = _native.bsr_to_block_map(indptr, indices, MB, NB, R, Cb, L, Hkv)
     qh, kh, vh = (x.permute(1, 0, 2).contiguous() for x in (q, k, v))
+    if return_lse:
+        o, lse = _native.varblock_attention(qh, kh, vh, bm, qs, ks, return_lse=True)
+        return o.permute(1, 0, 2).contiguous(), lse.permute(1, 0).contiguous()
     o = _native.varblock_attention(qh, kh, vh, bm, qs, ks)
     return o.permute(1, 0, 2).contiguous()

@@ -52,8 +52,10 @@ class WanFAMetadata:
     workspace: Optional[torch.Tensor] = None   # unused here (flashinfer's workspace in the reference)
 
 
-def wan_sparse_attn_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, metadata: WanFAMetadata) -> torch.Tensor:
-    """ref: attention_ops_wan.py:141-184"""
+def wan_sparse_attn_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, metadata: WanFAMetadata, return_lse: bool = False):
+    """ref: attention_ops_wan.py:141-184
+    return_lse: also the row log-sum-exp of the scaled scores, fp32 [seq_len, num_heads] (head_dim 128): the NATURAL logarithm where
+    flashinfer's `run(..., return_lse=True)` is base 2 (lse_flashinfer = lse / ln 2); _native.merge_attention_states takes it as it is."""
     indptr, indices, (R, Cb) = metadata.temporal_mask_metadata
     assert q.shape[0] % R == 0, f"Query length {q.shape[0]} % block_size {R} != 0"
     assert k.shape[0] % Cb == 0, f"Key length {k.shape[0]} % block_size {Cb} != 0"
@@ -61,4 +63,7 @@ def wan_sparse_attn_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, m
     Hkv = k.shape[1]
     bm, qs, ks = _native.bsr_to_block_map(indptr, indices, q.shape[0] // R, k.shape[0] // Cb, R, Cb, 0, Hkv)
     qh, kh, vh = (x.permute(1, 0, 2).contiguous() for x in (q, k, v))
+    if return_lse:
+        o, lse = _native.varblock_attention(qh, kh, vh, bm, qs, ks, return_lse=True)
+        return o.permute(1, 0, 2).contiguous(), lse.permute(1, 0).contiguous()
     return _native.varblock_attention(qh, kh, vh, bm, qs, ks).permute(1, 0, 2).contiguous()
