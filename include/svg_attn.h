@@ -299,6 +299,27 @@ int svg_cross_attention_lse(const void* q, const void* k, const void* v, void* o
 int svg_merge_attention_states(const void* const* o_parts, const float* const* lse_parts, int32_t n_parts, void* o, float* lse /* may be NULL */,
                                int32_t BH, int32_t Sq, int32_t D, int32_t dtype, const svg_attn_layout_t* layout /* o strides only; NULL: contiguous */,
                                void* stream);
+/* svg_cross_attention_lse that hands out every row BEFORE its rounding: o32 fp32 CONTIGUOUS [BH, Sq, D] whatever the layout of q, the value
+ * the 16-bit store of svg_cross_attention_lse rounds (o32 rounded to nearest even IS that o, bit for bit, and lse is bit-identical; fp16: where that store
+ * rounded the exact product past what the fp32 product would round to, o32 is one fp32 step off acc * inv, about 3e-5 of the elements).  No 16-bit o
+ * is written.  A part for svg_merge_attention_states_f32 below: the merge's rounding is then the only one between the accumulators and the
+ * merged result, so a result computed in parts meets the tolerance of one call over all keys.  Twice the output bytes of the 16-bit form.
+ * ref: flashinfer's run(..., return_lse=True) + merge_state, svg/kernels/ops/attention_ops.py:178-188 (whose parts are 16-bit).
+ * Plain (kv_end NULL) and key-window forms as in svg_cross_attention_lse.  o32 or lse NULL: SVG_ERR_BAD_ARG; o32 not 16-byte aligned:
+ * SVG_ERR_UNSUPPORTED; every other check is that of svg_cross_attention_lse (D other than 128: SVG_ERR_UNSUPPORTED), all on the host before
+ * any launch.  layout describes q, k and v; its o member is not read.  A row without keys has o32 = 0 and lse = -inf.  Band and
+ * variable-block attention: include/svg_attn_f32_parts.h (included at the end of this file). */
+int svg_cross_attention_lse_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t BH, int32_t Sq, int32_t Skv,
+                                int32_t D, int32_t dtype, float sm_scale, const int32_t* kv_begin, const int32_t* kv_end /* NULL: all keys */,
+                                int32_t heads_per_window, const svg_attn_layout_t* layout, void* stream);
+/* svg_merge_attention_states over fp32 parts: o_parts[i] fp32 contiguous [BH, Sq, D] as the *_lse_f32 entries write them, lse_parts[i] as
+ * there.  The same statement, visiting order and rules for -inf / underflowing parts; the parts enter the fp32 arithmetic as they are and
+ * the result is rounded ONCE to `dtype` (bf16 / fp16, the type of o).  n_parts == 1 rounds the part (the bits of the 16-bit attention
+ * entry).  Every check and code of svg_merge_attention_states: 1 <= n_parts <= 8, D 64 / 128, parts and o 16-byte aligned, layout read for
+ * heads_per_batch and the o strides only.  Reads twice the bytes per part. */
+int svg_merge_attention_states_f32(const float* const* o_parts, const float* const* lse_parts, int32_t n_parts, void* o, float* lse /* may be NULL */,
+                                   int32_t BH, int32_t Sq, int32_t D, int32_t dtype /* of o */,
+                                   const svg_attn_layout_t* layout /* o strides only; NULL: contiguous */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Online profiler (SVG1): mean-squared error of the two candidate masks on sampled query rows.
@@ -751,4 +772,6 @@ int svg_debug_wg_trace(uint64_t* out, int32_t n_workgroups);
 
 /* the row log-sum-exp forms of band and variable-block attention: declared in a header of their own, part of this interface */
 #include "svg_attn_sparse_lse.h"
+/* ... and their fp32-row forms (parts for svg_merge_attention_states_f32), likewise */
+#include "svg_attn_f32_parts.h"
 #endif /* SVG_ATTN_H_ */

@@ -1,6 +1,6 @@
 // SVG1 band (block-sparse) and dense attention for gfx950: the kernels that run the bodies of attn_core.h / attn_m16.h on the band
 // policy (band_policy.h), the counter pool of the queue launches, the svg_band_attention* entries, the completion-counter waiters and
-// the svg_debug_* trace readers; svg_band_attention_lse (row log-sum-exp output).  (One-wave-per-SIMD body: attention_w4.hip; fp8:
+// the svg_debug_* trace readers; svg_band_attention_lse (row log-sum-exp output) and svg_band_attention_lse_f32 (fp32 rows).  (One-wave-per-SIMD body: attention_w4.hip; fp8:
 // attention_f8.hip; SVG2: attention_varblock.hip.)
 #include <algorithm>
 #include <atomic>
@@ -82,6 +82,14 @@ template <typename T>
 __global__ __launch_bounds__(512, 2) void band_attn_lse_m16_kernel(typename BandLsePolicy<T>::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     attn_body_m16<T, BandLsePolicy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
+}
+// fp32 form (svg_band_attention_lse_f32): the LSE kernel on BandF32Policy — the same template arguments, SPEC and the replay counter
+// included; the epilogue stores the rows as fp32, before their rounding, and no 16-bit o.  A q-tile that fails its validation stores
+// nothing; its replay stores o32 and lse.  (Its own kernel template: the other kernels keep their symbols and their listings.)
+template <typename T>
+__global__ __launch_bounds__(512, 2) void band_attn_f32_m16_kernel(typename BandF32Policy<T>::Params prm) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    attn_body_m16<T, BandF32Policy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
 }
 // pre-scaled q on the 16x16x32 body (PRE form of attn_body_m16)
 template <typename T>
@@ -296,11 +304,18 @@ static int band_dispatch(const void* q, const void* k, const void* v, void* o, i
     const hipStream_t st = (hipStream_t)stream;
     if (opts.lse) {   // svg_band_attention_lse: the default head_dim-128 body only, on the static mapping
         if (D != 128 || variant != kBandAuto || opts.done || opts.prescaled || opts.use_alt) return SVG_ERR_UNSUPPORTED;
+        if (opts.o32 && ((size_t)opts.o32 & 15) != 0) return SVG_ERR_UNSUPPORTED;   // 16-byte stores
         return dispatch_td(dtype, D, [&](auto t, auto d) -> int {
             using T = decltype(t);
             if constexpr (decltype(d)::value != 128) {
                 return SVG_ERR_UNSUPPORTED;
             } else {
+                if (opts.o32) {   // svg_band_attention_lse_f32: `o` is o32 here, the kernel gets no 16-bit o
+                    using Pol = BandF32Policy<T>;
+                    typename Pol::Params p = make_band_params<Pol, T>(q, k, v, nullptr, BH, S, sm_scale, mask, perm, opts);
+                    p.lse = opts.lse, p.o32 = opts.o32;
+                    return launch_attn(band_attn_f32_m16_kernel<T>, dim3(p.nqt * BH), 512, attn_m16_lds_bytes() + kTailLds, st, p);
+                }
                 using Pol = BandLsePolicy<T>;
                 typename Pol::Params p = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
                 p.lse = opts.lse;
@@ -424,6 +439,20 @@ extern "C" int svg_band_attention_lse(const void* q, const void* k, const void* 
     opts.lse = lse;
     opts.strided = layout != nullptr;
     return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, 0, layout, stream);
+}
+
+// o32 travels in the place of o through band_dispatch (its null check); of `layout` the o member is not read: it takes q's strides
+extern "C" int svg_band_attention_lse_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t BH, int32_t S,
+                                          int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
+                                          const svg_perm_desc_t* perm, const svg_attn_layout_t* layout, void* stream) {
+    if (!o32 || !lse) return SVG_ERR_BAD_ARG;
+    BandOpts opts;
+    opts.lse = lse, opts.o32 = o32;
+    opts.strided = layout != nullptr;
+    svg_attn_layout_t abi{};
+    if (layout) abi = *layout, abi.o = abi.q;
+    return band_dispatch(q, k, v, layout ? const_cast<void*>(q) : (void*)o32, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, 0,
+                         layout ? &abi : nullptr, stream);
 }
 
 // (head_dim 128: the PRE form of the 16x16x32 body — 33.0 - 33.3 ms against 33.6 - 34.2 for the 32x32x16 one, same box, profiles/r04k_ab_m16_prescaled.txt)

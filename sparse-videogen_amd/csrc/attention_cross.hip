@@ -1,6 +1,6 @@
 // Cross attention for gfx950: dense attention of Sq query rows over a short key set (Sq != Skv), the two-phase 16x16x32 body of
 // attn_m16.h on the policy of cross_policy.h, and the svg_cross_attention / svg_cross_attention_keyrange / svg_cross_attention_pair /
-// svg_cross_attention_lse entries.  (Band family: attention.hip; SVG2: attention_varblock.hip.)
+// svg_cross_attention_lse / svg_cross_attention_lse_f32 entries.  (Band family: attention.hip; SVG2: attention_varblock.hip.)
 #include <algorithm>
 
 #include "attn_m16.h"
@@ -34,6 +34,22 @@ template <typename T, bool Windowed>
 __global__ __launch_bounds__(512, 2) void cross_attn_lse_m16_kernel(typename CrossLsePolicy<T, Windowed>::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using Pol = CrossLsePolicy<T, Windowed>;
+    const int n_items = prm.BH * prm.nqt;
+    for (int w = blockIdx.x; w < n_items; w += gridDim.x) {
+        if (w != (int)blockIdx.x) __syncthreads();
+        const int head = w / prm.nqt;
+        typename Pol::Ctx ctx;
+        Pol::init_tile(prm, ctx, head, w - head * prm.nqt);
+        attn_m16_tile<T, Pol, false, 1>(prm, ctx, smem);
+    }
+}
+
+// fp32 form (svg_cross_attention_lse_f32): the LSE kernel on CrossF32Policy — the epilogue stores the rows as fp32, before their rounding,
+// and no 16-bit o.  (Its own kernel template: the kernels above keep their symbols and their listings.)
+template <typename T, bool Windowed>
+__global__ __launch_bounds__(512, 2) void cross_attn_f32_m16_kernel(typename CrossF32Policy<T, Windowed>::Params prm) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    using Pol = CrossF32Policy<T, Windowed>;
     const int n_items = prm.BH * prm.nqt;
     for (int w = blockIdx.x; w < n_items; w += gridDim.x) {
         if (w != (int)blockIdx.x) __syncthreads();
@@ -180,6 +196,46 @@ extern "C" int svg_cross_attention_pair(const void* q, const void* k_a, const vo
             p.v_bs_b = lay_b.v_bs, p.v_hs_b = lay_b.v_hs, p.v_rs_b = lay_b.v_rs;
             const int n_wg = (int)std::min<int64_t>((int64_t)BH * p.a.nqt, device_cus());
             return launch_attn(cross_attn_pair_m16_kernel<T>, dim3(n_wg), 512, attn_m16_lds_bytes(), (hipStream_t)stream, p);
+        }
+    });
+}
+
+// the checks of cross_attention_launch (o32 in the place of o: 16-byte aligned; the o member of `layout` is not read) and the fp32 kernel
+extern "C" int svg_cross_attention_lse_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t BH, int32_t Sq,
+                                           int32_t Skv, int32_t D, int32_t dtype, float sm_scale, const int32_t* kv_begin,
+                                           const int32_t* kv_end, int32_t heads_per_window, const svg_attn_layout_t* layout, void* stream) {
+    if (!o32 || !lse) return SVG_ERR_BAD_ARG;
+    if (kv_end && (heads_per_window <= 0 || (BH > 0 && BH % heads_per_window != 0))) return SVG_ERR_BAD_ARG;
+    if (!q || !k || !v || BH <= 0 || Sq <= 0 || Skv <= 0) return SVG_ERR_BAD_ARG;
+    if (D != 128) return SVG_ERR_UNSUPPORTED;
+    if (check_rows(Sq, D) != SVG_OK || check_rows(Skv, D) != SVG_OK) return SVG_ERR_UNSUPPORTED;
+    if ((int64_t)BH * Sq * D >= (1ll << 40)) return SVG_ERR_UNSUPPORTED;
+    if (((size_t)o32 & 15) != 0) return SVG_ERR_UNSUPPORTED;
+    AttnLayout lay = contiguous_layout(BH, BH, Sq, Skv, D);
+    if (layout) {
+        svg_attn_layout_t abi = *layout;
+        abi.o = abi.q;
+        if (const int rc = layout_from_abi(&abi, BH, BH, Sq, Skv, D, q, k, v, q, lay); rc != SVG_OK) return rc;
+    }
+    return dispatch_td(dtype, D, [&](auto t, auto d) -> int {
+        using T = decltype(t);
+        if constexpr (decltype(d)::value != 128) {
+            return SVG_ERR_UNSUPPORTED;
+        } else {
+            auto launch = [&](auto windowed_c) -> int {
+                constexpr bool kWindowed = decltype(windowed_c)::value;
+                using Pol = CrossF32Policy<T, kWindowed>;
+                typename Pol::Params p;
+                p.lse = lse, p.o32 = o32;
+                if constexpr (kWindowed) p.kv_begin = kv_begin, p.kv_end = kv_end, p.heads_per_window = heads_per_window;
+                p.q = (const T*)q, p.k = (const T*)k, p.v = (const T*)v, p.o = nullptr;
+                p.Sq = Sq, p.Skv = Skv, p.BH = BH, p.nqt = (Sq + Pol::BM - 1) / Pol::BM;
+                p.scale_log2 = sm_scale * 1.4426950408889634f;
+                p.lay = lay;
+                const int n_wg = (int)std::min<int64_t>((int64_t)BH * p.nqt, device_cus());
+                return launch_attn(cross_attn_f32_m16_kernel<T, kWindowed>, dim3(n_wg), 512, attn_m16_lds_bytes(), (hipStream_t)stream, p);
+            };
+            return kv_end ? launch(std::true_type{}) : launch(std::false_type{});
         }
     });
 }

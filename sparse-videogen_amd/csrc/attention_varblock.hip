@@ -1,6 +1,6 @@
 // SVG2 variable-block attention for gfx950: the kernels that run the bodies of attn_core.h / attn_m16.h / attn_f8.h on the policy of
 // varblock_policy.h, the planning / launch-order kernels in front of them, the svg_varblock_* entries (svg_varblock_attention_lse: row
-// log-sum-exp output).  (Band family: attention.hip.)
+// log-sum-exp output; svg_varblock_attention_lse_f32: fp32 rows).  (Band family: attention.hip.)
 #include <utility>
 
 #include "attn_f8.h"
@@ -35,6 +35,14 @@ template <typename T>
 __global__ __launch_bounds__(512, 2) void varblock_attn_lse_m16_kernel(typename VarblockLsePolicy<T>::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     attn_body_m16<T, VarblockLsePolicy<T>>(prm, smem, smem + attn_m16_lds_bytes());
+}
+
+// fp32 form (svg_varblock_attention_lse_f32): the LSE kernel on VarblockF32Policy — the epilogue stores the rows as fp32, before their
+// rounding, and no 16-bit o.  (Its own kernel template: the kernels above keep their symbols and their listings.)
+template <typename T>
+__global__ __launch_bounds__(512, 2) void varblock_attn_f32_m16_kernel(typename VarblockF32Policy<T>::Params prm) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    attn_body_m16<T, VarblockF32Policy<T>>(prm, smem, smem + attn_m16_lds_bytes());
 }
 
 #ifdef SVG_ABLATIONS
@@ -480,6 +488,7 @@ struct VbCall {
     const AttnLayout* lay = nullptr;                // strided tensors (svg_varblock_attention_strided); nullptr: contiguous [H, S, D]
     F8GArgs f8{};                                   // kF8: the quantised tensors and scales of f8g_quantize
     float* lse = nullptr;                           // kM16: row log-sum-exp output, contiguous fp32 [Hq, Sq] (svg_varblock_attention_lse), or nullptr
+    float* o32 = nullptr;                           // with lse: fp32 rows, contiguous [Hq, Sq, 128], instead of o (svg_varblock_attention_lse_f32)
 };
 
 // The workspace of a call, and the one definition of its layout (_native.varblock_launch_order / varblock_partners read it at fixed
@@ -615,6 +624,12 @@ static int run_varblock(const VbCall& c) {
                 return SVG_ERR_UNSUPPORTED;   // diagnostics builds only (-DSVG_ABLATIONS)
             }
             if constexpr (D == 128) {
+                if (body == VbBody::kM16 && c.lse && c.o32) {   // ... and the policy that stores fp32 rows and no 16-bit o
+                    typename VarblockF32Policy<T>::Params pf;
+                    static_cast<typename VarblockPolicy<T, 128, 8>::Params&>(pf) = p;
+                    pf.o = nullptr, pf.lse = c.lse, pf.o32 = c.o32;
+                    return launch_attn(varblock_attn_f32_m16_kernel<T>, grid, 512, attn_m16_lds_bytes() + lds_vb, st, pf);
+                }
                 if (body == VbBody::kM16 && c.lse) {   // the same plan, launch order and grid; the policy that also stores lse
                     typename VarblockLsePolicy<T>::Params pl;
                     static_cast<typename VarblockPolicy<T, 128, 8>::Params&>(pl) = p;
@@ -692,6 +707,7 @@ static int varblock_entry(VbCall& c, int variant, const svg_attn_layout_t* layou
     }
     if (!vb_decode_variant(variant, c)) return SVG_ERR_BAD_ARG;
     if (c.lse && (c.D != 128 || c.body != VbBody::kM16 || c.trace || c.block_row_order)) return SVG_ERR_UNSUPPORTED;   // (fp32 etc.: dispatch_td)
+    if (c.o32 && ((size_t)c.o32 & 15) != 0) return SVG_ERR_UNSUPPORTED;   // 16-byte stores
     const bool two_phase = c.body == VbBody::kM16 || c.body == VbBody::kPP2;
     if (c.lay && !(two_phase && !c.trace)) return SVG_ERR_UNSUPPORTED;   // strided tensors: the two-phase bodies only (see svg_attn_layout_t)
     return dispatch_td(c.dtype, c.D, [&](auto t, auto d) { return run_varblock<decltype(t), decltype(d)::value>(c); });
@@ -729,6 +745,21 @@ extern "C" int svg_varblock_attention_lse(const void* q, const void* k, const vo
              workspace_bytes, (hipStream_t)stream};
     c.lse = lse;
     return varblock_entry(c, 3, layout);
+}
+
+// o32 travels in the place of o through varblock_entry (its null check); of `layout` the o member is not read: it takes q's strides
+extern "C" int svg_varblock_attention_lse_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t Hq, int32_t Hkv,
+                                              int32_t Sq, int32_t Skv, int32_t D, int32_t dtype, float sm_scale, const uint8_t* block_map,
+                                              const int32_t* q_sizes, const int32_t* k_sizes, int32_t QB, int32_t KB,
+                                              const int32_t* q_row_idx, const int32_t* kv_row_idx, void* workspace, size_t workspace_bytes,
+                                              const svg_attn_layout_t* layout, void* stream) {
+    if (!o32 || !lse) return SVG_ERR_BAD_ARG;
+    VbCall c{q, k, v, layout ? const_cast<void*>(q) : (void*)o32, Hq, Hkv, Sq, Skv, D, dtype, sm_scale, block_map, q_sizes, k_sizes, QB, KB,
+             q_row_idx, kv_row_idx, workspace, workspace_bytes, (hipStream_t)stream};
+    c.lse = lse, c.o32 = o32;
+    svg_attn_layout_t abi{};
+    if (layout) abi = *layout, abi.o = abi.q;
+    return varblock_entry(c, 3, layout ? &abi : nullptr);
 }
 
 extern "C" int svg_varblock_attention_fp8(const void* q, const void* k, const void* v, void* o, int32_t Hq, int32_t Hkv, int32_t Sq,

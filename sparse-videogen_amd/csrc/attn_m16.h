@@ -129,6 +129,52 @@ struct HasRowLse : std::false_type {};
 template <typename P>
 struct HasRowLse<P, std::void_t<decltype(&P::lse_base)>> : std::true_type {};
 
+// fp32 rows (detected: a policy with a static o32_base(prm, ctx), the *F32Policy of cross_policy.h / band_policy.h / varblock_policy.h;
+// every other policy compiles the epilogue it had): the epilogue stores acc_o * inv — the value the 16-bit store rounds — as fp32 at
+// o32_base(prm, ctx)[physical q row * D + column], a contiguous [heads, rows, D] in the caller's row order (the row index of the lse
+// store), and writes no 16-bit o.  What a merge over parts of the keys takes without a rounding per part (svg_merge_attention_states_f32).
+// Straight from the accumulator registers: a lane holds four consecutive floats per (db, rb) at column 16 * db + 4 * g4, so one 16-byte
+// store per (db, rb) — the four lanes of a row's quad group fill one 64-byte run; no LDS (the staging region holds 16-bit rows) and no
+// barrier.  Rows behind the q-tile's end (q_phys < 0) store nothing, a row without keys stores zeros (inv == 0).
+template <typename P, typename = void>
+struct HasRowO32 : std::false_type {};
+template <typename P>
+struct HasRowO32<P, std::void_t<decltype(&P::o32_base)>> : std::true_type {};
+// The four fp32 values of one (db, rb).  bf16: the 16-bit store rounds the fp32 product, so the product is the value.  fp16: the 16-bit
+// store of the same accumulators is compiled (-ffast-math contraction) to a mix of v_fma_mixlo_f16 — the exact product rounded once — and
+// v_pk_mul_f32 + v_cvt_pk_f16_f32 — rounded twice — so the fp32 product rounded again by the caller differs from it where the product lies
+// exactly on the midpoint of two fp16 values and the store took the other neighbour (about 3e-5 of the elements).  So the fp16 form
+// also evaluates the 16-bit store's own expression, and where the fp32 product does not round to that value it moves ONE fp32 step
+// towards it: o32 rounded to nearest even is then the 16-bit o, and o32 stays within one fp32 step of acc * inv.  (The empty asm
+// statements keep the two evaluations apart: without them the compiler folds both into one and the comparison is always true.)
+template <typename T, typename E>
+__device__ __forceinline__ f32x4 o32_values(const f32x4& acc, float inv) {
+    f32x4 o4;
+    if constexpr (std::is_same_v<T, _Float16>) {
+        typename E::v4 h4;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) h4[j] = E::from_float(acc[j] * inv);   // the expression of the 16-bit store
+        u32x2 hb = __builtin_bit_cast(u32x2, h4);
+        asm("" : "+v"(hb));
+        h4 = __builtin_bit_cast(typename E::v4, hb);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float a = acc[j];
+            asm("" : "+v"(a));
+            float p = a * inv;
+            asm("" : "+v"(p));
+            const float h = (float)h4[j];
+            if ((float)(_Float16)p != h)   // p is a midpoint and the store took the other neighbour (false for 0 against -0; a NaN stays one)
+                p = __uint_as_float(fabsf(h) > fabsf(p) ? __float_as_uint(p) + 1u : __float_as_uint(p) - 1u);
+            o4[j] = p;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o4[j] = acc[j] * inv;
+    }
+    return o4;
+}
+
 // Row cursor (detected: a policy with kRowCursor, band_policy.h BandPolicy; every other policy keeps kv_cursor_init / kv_phys and compiles
 // the request pipeline it had): the lane's key row is ONE variable stepped in place by P::row_walk_next, the decision between the
 // cheap step and the exact path is scalar, and the two byte offsets of a request are formed when the request pipeline takes the row.
@@ -686,6 +732,17 @@ __device__ __forceinline__ bool attn_m16_tile(const typename P::Params& prm, con
             if (g4 == 0 && qp >= 0)
                 P::lse_base(prm, ctx)[qp] = l_tot > 0.f ? 0.6931471805599453f * (m_use[rb] + kBias + __builtin_amdgcn_logf(l_tot)) : -INFINITY;
         }
+        if constexpr (HasRowO32<P>::value) {   // fp32 rows: the lane stores its four floats of every 16-column block itself
+            const int qp = P::q_phys(prm, ctx, wave * 32 + rb * 16 + n16);
+            if (qp >= 0) {
+                float* const dst = P::o32_base(prm, ctx) + (size_t)qp * D + 4 * g4;
+#pragma unroll
+                for (int db = 0; db < NDB; ++db) {
+                    *(f32x4*)(dst + 16 * db) = o32_values<T, E>(acc_o[db][rb], inv);
+                }
+            }
+            continue;
+        }
 #pragma unroll
         for (int db = 0; db < NDB; ++db) {
             typename E::v4 o4;
@@ -693,6 +750,10 @@ __device__ __forceinline__ bool attn_m16_tile(const typename P::Params& prm, con
             for (int j = 0; j < 4; ++j) o4[j] = E::from_float(acc_o[db][rb][j] * inv);
             *(typename E::v4*)(erow + (rb * 16 + n16) * kEpiStride + (16 * db + 4 * g4) * 2) = o4;
         }
+    }
+    if constexpr (HasRowO32<P>::value) {   // (no 16-bit row store; the trace stamps below are not built for these policies)
+        P::notify(prm, ctx);
+        return false;
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();

@@ -22,6 +22,7 @@ struct BandOpts {
     const svg_band_mask_t* alt_mask = nullptr;
     const int32_t* use_alt = nullptr;
     float* lse = nullptr;      // row log-sum-exp output, contiguous fp32 [BH, S] (svg_band_attention_lse: BandLsePolicy), or nullptr
+    float* o32 = nullptr;      // with lse: fp32 rows, contiguous [BH, S, 128], instead of o (svg_band_attention_lse_f32: BandF32Policy)
 };
 
 // the mask and the head permutation of a band call over S rows (mask != nullptr)
@@ -490,6 +491,20 @@ struct BandLsePolicy : BandPolicy<T, 128, 8> {
         float* lse;   // [BH, S]
     };
     static __device__ __forceinline__ float* lse_base(const Params& p, const typename Base::Ctx& c) { return p.lse + (size_t)c.head * (size_t)p.S; }
+};
+
+// fp32 form (svg_band_attention_lse_f32): the LSE policy plus the rows before their rounding (attn_m16.h: HasRowO32, switched on by
+// o32_base below), as CrossF32Policy adds them to the cross policy.  o32 is a contiguous fp32 [BH, S, 128] whatever the layout of q, the
+// row inside a head the one lse uses; Params::o is not used.
+template <typename T>
+struct BandF32Policy : BandLsePolicy<T> {
+    using Base = BandLsePolicy<T>;
+    struct Params : Base::Params {
+        float* o32;   // [BH, S, 128]
+    };
+    static __device__ __forceinline__ float* o32_base(const Params& p, const typename Base::Ctx& c) {
+        return p.o32 + (size_t)c.head * (size_t)p.S * 128;
+    }
 };
 
 // =====================================================================================================

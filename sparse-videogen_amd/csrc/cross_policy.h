@@ -6,6 +6,7 @@
 // most two) edge tiles take the per-element path; nT == 0 for an empty window, whose rows come out as zeros.  The plain form's members are
 // empty bases and compile-time branches: its kernel is the one it was.
 // LSE form (svg_cross_attention_lse, CrossLsePolicy below): either of the two plus one fp32 per query row, the log-sum-exp of its scores.
+// fp32 form (svg_cross_attention_lse_f32, CrossF32Policy below): the LSE form with its rows stored as fp32, before the 16-bit rounding.
 #pragma once
 #include "attn_core.h"
 
@@ -122,6 +123,20 @@ struct CrossLsePolicy : CrossPolicy<T, Windowed> {
         float* lse;   // [BH, Sq]
     };
     static __device__ __forceinline__ float* lse_base(const Params& p, const typename Base::Ctx& c) { return p.lse + (size_t)c.head * (size_t)p.Sq; }
+};
+
+// fp32 form (svg_cross_attention_lse_f32): the LSE policy plus the rows before their rounding (attn_m16.h: HasRowO32, switched on by
+// o32_base below) — a part for svg_merge_attention_states_f32, whose rounding is then the only one.  o32 is a contiguous fp32 [BH, Sq, 128]
+// whatever the layout of q; Params::o is not used.
+template <typename T, bool Windowed = false>
+struct CrossF32Policy : CrossLsePolicy<T, Windowed> {
+    using Base = CrossLsePolicy<T, Windowed>;
+    struct Params : Base::Params {
+        float* o32;   // [BH, Sq, 128]
+    };
+    static __device__ __forceinline__ float* o32_base(const Params& p, const typename Base::Ctx& c) {
+        return p.o32 + (size_t)c.head * (size_t)p.Sq * 128;
+    }
 };
 
 // Pair form (svg_cross_attention_pair): the plain policy run twice per q-tile, over key set A and then over key set B, the second pass

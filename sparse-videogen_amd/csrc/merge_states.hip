@@ -13,6 +13,7 @@
 // by value in the kernel arguments.
 // Pure HBM-bandwidth work: every part is read once, o written once, 16 bytes per lane; a wave owns whole rows (D / 8 lanes each), so the
 // weights are computed by the lanes that use them: no LDS, no shuffles, no atomics.
+// svg_merge_attention_states_f32 (merge_states_f32_kernel below) takes the parts as fp32 rows, before any rounding.
 #include "svg_common.h"
 
 namespace svg {
@@ -92,12 +93,81 @@ __global__ __launch_bounds__(kMergeThreads) void merge_states_kernel(MergeArgs a
     if (a.lse && col == 0) a.lse[row] = sw > 0.f ? m + 0.6931471805599453f * __builtin_amdgcn_logf(sw) : -INFINITY;
 }
 
+// fp32 parts (svg_merge_attention_states_f32): o_i is the fp32 row the attention kernels hand out BEFORE their rounding
+// (svg_cross_attention_lse_f32 and its band / variable-block siblings), so the rounding below is the only one between the accumulators and
+// the merged o: exact parts merged this way sit at the 1.66e-3 (bf16) / 2.07e-4 (fp16) of one rounding instead of 2.35e-3 / 2.94e-4.
+// The statement, the visiting order and the -inf / underflow rules are those of merge_states_kernel with xf read directly; the lane owns
+// the same 8 columns and reads them as two 16-byte loads (twice the bytes per part).  n == 1 rounds the part once.
+template <typename T, int D>
+__global__ __launch_bounds__(kMergeThreads) void merge_states_f32_kernel(MergeArgs a) {
+    using E = Elt<T>;
+    using V8 = typename E::v8;
+    constexpr int kLanesPerRow = D / 8;
+    constexpr int kRowsPerWg = kMergeThreads / kLanesPerRow;
+    const int sub = threadIdx.x / kLanesPerRow;
+    const int col = (threadIdx.x - sub * kLanesPerRow) * 8;
+    const long long row = (long long)blockIdx.x * kRowsPerWg + sub;
+    if (row >= a.rows) return;
+
+    float l[kMergeMaxParts];
+    f32x4 x[kMergeMaxParts][2];
+#pragma unroll
+    for (int i = 0; i < kMergeMaxParts; ++i)
+        if (i < a.n) {
+            l[i] = a.lse_part[i][row];
+            const f32x4* const src = (const f32x4*)((const float*)a.o_part[i] + row * D + col);
+            x[i][0] = src[0], x[i][1] = src[1];
+        }
+
+    const int head = (int)(row / a.Sq);
+    const int s = (int)(row - (long long)head * a.Sq);
+    T* const dst = (T*)a.o + layout_head_off(a.o_bs, a.o_hs, a.hpb, head) + (size_t)s * a.o_rs + col;
+    V8 out;
+    if (a.n == 1) {   // one part: its rows rounded once, its lse as it is (no weight, no division)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) out[j] = E::from_float(x[0][j >> 2][j & 3]);
+        *(V8*)dst = out;
+        if (a.lse && col == 0) a.lse[row] = l[0];
+        return;
+    }
+
+    float m = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < kMergeMaxParts; ++i)
+        if (i < a.n) m = fmaxf(m, l[i]);
+    float acc[8], sw = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+    bool first = true;
+#pragma unroll
+    for (int i = 0; i < kMergeMaxParts; ++i)
+        if (i < a.n) {
+            const float w = (l[i] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((l[i] - m) * 1.4426950408889634f);
+            if (w > 0.f) {   // (false for a NaN too)
+                sw += w;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float xf = x[i][j >> 2][j & 3];
+                    acc[j] = first ? w * xf : fmaf(w, xf, acc[j]);   // the first part sets (a -0 stays one), the others add
+                }
+                first = false;
+            }
+        }
+    const float inv = sw > 0.f ? 1.f / sw : 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) out[j] = E::from_float(acc[j] * inv);
+    *(V8*)dst = out;
+    if (a.lse && col == 0) a.lse[row] = sw > 0.f ? m + 0.6931471805599453f * __builtin_amdgcn_logf(sw) : -INFINITY;
+}
+
 }  // namespace svg
 
 using namespace svg;
 
-extern "C" int svg_merge_attention_states(const void* const* o_parts, const float* const* lse_parts, int32_t n_parts, void* o, float* lse,
-                                          int32_t BH, int32_t Sq, int32_t D, int32_t dtype, const svg_attn_layout_t* layout, void* stream) {
+// the checks and the launch of both entries; F32: the parts are fp32 rows (merge_states_f32_kernel), `dtype` is that of o either way
+template <bool F32>
+static int merge_states_launch(const void* const* o_parts, const float* const* lse_parts, int32_t n_parts, void* o, float* lse, int32_t BH,
+                               int32_t Sq, int32_t D, int32_t dtype, const svg_attn_layout_t* layout, void* stream) {
     if (!o_parts || !lse_parts || !o || n_parts < 1 || n_parts > kMergeMaxParts || BH <= 0 || Sq <= 0 || D <= 0) return SVG_ERR_BAD_ARG;
     for (int i = 0; i < n_parts; ++i)
         if (!o_parts[i] || !lse_parts[i]) return SVG_ERR_BAD_ARG;
@@ -124,7 +194,18 @@ extern "C" int svg_merge_attention_states(const void* const* o_parts, const floa
         a.hpb = lay.hpb_q, a.o_rs = lay.o_rs, a.o_bs = lay.o_bs, a.o_hs = lay.o_hs;
         constexpr int kRowsPerWg = kMergeThreads / (kD / 8);
         const long long n_wg = (a.rows + kRowsPerWg - 1) / kRowsPerWg;
-        hipLaunchKernelGGL((merge_states_kernel<T, kD>), dim3((unsigned)n_wg), dim3(kMergeThreads), 0, (hipStream_t)stream, a);
+        if constexpr (F32) hipLaunchKernelGGL((merge_states_f32_kernel<T, kD>), dim3((unsigned)n_wg), dim3(kMergeThreads), 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL((merge_states_kernel<T, kD>), dim3((unsigned)n_wg), dim3(kMergeThreads), 0, (hipStream_t)stream, a);
         return launch_status();
     });
+}
+
+extern "C" int svg_merge_attention_states(const void* const* o_parts, const float* const* lse_parts, int32_t n_parts, void* o, float* lse,
+                                          int32_t BH, int32_t Sq, int32_t D, int32_t dtype, const svg_attn_layout_t* layout, void* stream) {
+    return merge_states_launch<false>(o_parts, lse_parts, n_parts, o, lse, BH, Sq, D, dtype, layout, stream);
+}
+
+extern "C" int svg_merge_attention_states_f32(const float* const* o_parts, const float* const* lse_parts, int32_t n_parts, void* o, float* lse,
+                                              int32_t BH, int32_t Sq, int32_t D, int32_t dtype, const svg_attn_layout_t* layout, void* stream) {
+    return merge_states_launch<true>((const void* const*)o_parts, lse_parts, n_parts, o, lse, BH, Sq, D, dtype, layout, stream);
 }

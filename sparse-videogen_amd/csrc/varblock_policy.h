@@ -249,6 +249,20 @@ struct VarblockLsePolicy : VarblockPolicy<T, 128, 8> {
     static __device__ __forceinline__ float* lse_base(const Params& p, const typename Base::Ctx& c) { return p.lse + (size_t)c.hq * (size_t)p.Sq; }
 };
 
+// fp32 form (svg_varblock_attention_lse_f32): the LSE policy plus the rows before their rounding (attn_m16.h: HasRowO32, switched on by
+// o32_base below), as CrossF32Policy adds them to the cross policy.  o32 is a contiguous fp32 [Hq, Sq, 128] whatever the layout of q, the
+// row inside a head the one lse uses; Params::o is not used.
+template <typename T>
+struct VarblockF32Policy : VarblockLsePolicy<T> {
+    using Base = VarblockLsePolicy<T>;
+    struct Params : Base::Params {
+        float* o32;   // [Hq, Sq, 128]
+    };
+    static __device__ __forceinline__ float* o32_base(const Params& p, const typename Base::Ctx& c) {
+        return p.o32 + (size_t)c.hq * (size_t)p.Sq * 128;
+    }
+};
+
 static inline int vb_policy_lds(int kb_cap) { return (2 * (kb_cap + 2) + 32) * (int)sizeof(int32_t); }
 
 }  // namespace svg

@@ -153,6 +153,9 @@ SIGNATURES = {
     "svg_cross_attention_lse": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _F32, _VP, _VP, _I32, C.POINTER(AttnLayout),
                                           _VP]),
     "svg_merge_attention_states": (C.c_int, [_VP, _VP, _I32, _VP, _VP, _I32, _I32, _I32, _I32, C.POINTER(AttnLayout), _VP]),
+    "svg_cross_attention_lse_f32": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _F32, _VP, _VP, _I32, C.POINTER(AttnLayout),
+                                              _VP]),
+    "svg_merge_attention_states_f32": (C.c_int, [_VP, _VP, _I32, _VP, _VP, _I32, _I32, _I32, _I32, C.POINTER(AttnLayout), _VP]),
     "svg_sample_mse_strided": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _F32, C.POINTER(ProfileDesc), _VP, _VP,
                                          _SZ, _VP, C.POINTER(AttnLayout), _VP]),
     "svg_band_attention_prescaled": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, C.POINTER(BandMask), C.POINTER(PermDesc), _VP]),
@@ -218,6 +221,12 @@ SPARSE_LSE_SIGNATURES = {
                                              _VP, _VP, _VP, _SZ, C.POINTER(AttnLayout), _VP]),
 }
 
+# include/svg_attn_f32_parts.h: their fp32-row forms, in a table of their own for the same reason (tests/test_attention_f32_parts_cpu.py)
+SPARSE_F32_SIGNATURES = {
+    "svg_band_attention_lse_f32": SPARSE_LSE_SIGNATURES["svg_band_attention_lse"],
+    "svg_varblock_attention_lse_f32": SPARSE_LSE_SIGNATURES["svg_varblock_attention_lse"],
+}
+
 
 def lib_path() -> Path:
     return Path(os.environ.get("SVG_ATTN_LIB", str(_LIB_PATH)))
@@ -231,7 +240,7 @@ def load(strict: bool = True) -> Optional[C.CDLL]:
     p = lib_path()
     try:
         lib = C.CDLL(str(p))
-        for name, (res, args) in {**SIGNATURES, **SPARSE_LSE_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **SPARSE_LSE_SIGNATURES, **SPARSE_F32_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -416,11 +425,34 @@ def argsort_labels(labels: torch.Tensor, K: int):
     return sidx, counts
 
 
+def _want_f32_parts(what: str, out_dtype, return_lse: bool, out, token_major_out: bool) -> bool:
+    """out_dtype of the attention wrappers: None (q's dtype), or torch.float32 — the rows before their rounding, parts for
+    merge_attention_states — which goes with return_lse=True and without out / token_major_out only."""
+    if out_dtype is None:
+        return False
+    if out_dtype != torch.float32:
+        raise ValueError(f"{what}: out_dtype is None (q's dtype) or torch.float32, got {out_dtype}")
+    if not return_lse or out is not None or token_major_out:
+        raise ValueError(f"{what}(out_dtype=torch.float32): fp32 rows are parts for merge_attention_states — with return_lse=True and without "
+                         f"out / token_major_out; got return_lse = {return_lse}, out = {out is not None}, token_major_out = {token_major_out}")
+    return True
+
+
+def _q_views(q, k, v, name: str, call):
+    """The fp32-row entries on [B, H, S, D] views of q, k, v (their output is contiguous whatever q is): call(layout) -> rc, checked;
+    False where the layout cannot describe a view."""
+    q4, k4, v4 = _view4(q), _view4(k), _view4(v)
+    if not (_strided_ok(q4) and _strided_ok(k4, True) and _strided_ok(v4, True)):
+        return False
+    _check(call(attn_layout(q4, k4, v4, q4)), name)
+    return True
+
+
 def band_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: BandMask, sm_scale: Optional[float] = None,
                    head_perm_flag: Optional[torch.Tensor] = None, vid0: int = 0, num_frame: int = 1,
                    frame_size: int = 1, variant: int = 0, out: Optional[torch.Tensor] = None,
                    done: Optional[torch.Tensor] = None, done_nseg: int = 1, q_prescaled: bool = False,
-                   token_major_out: bool = False, return_lse: bool = False):
+                   token_major_out: bool = False, return_lse: bool = False, out_dtype: Optional[torch.dtype] = None):
     """q, k, v: [B, H, S, D] (or [BH, S, D]) bf16/fp16 GPU tensors -> o of the same shape.
     Strided views (last dimension contiguous — e.g. `proj(x).unflatten(2, (H, -1)).transpose(1, 2)`, or a slice of a fused QKV
     projection) are read in place by svg_band_attention_strided where it exists (head_dim 128, default schedule, plain q, no completion
@@ -433,20 +465,24 @@ def band_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Band
     of the library (hidden per-head counters of heads that run with the fused layout permutation).
     return_lse: (o, lse) with lse the row log-sum-exp of the scaled scores over the keys the mask gives the row (natural log), contiguous
     fp32 of shape q.shape[:-1], in the caller's row order — what merge_attention_states takes (svg_band_attention_lse: head_dim 128,
-    default schedule, plain q, no completion counters; anything else raises ValueError); o has the same bits as without."""
+    default schedule, plain q, no completion counters; anything else raises ValueError); o has the same bits as without.
+    out_dtype=torch.float32 (with return_lse=True, without out / token_major_out; ValueError otherwise): (o32, lse) with o32 the rows
+    before their rounding, contiguous fp32 of q's shape (svg_band_attention_lse_f32) — parts for merge_attention_states, which then rounds
+    once; o32.to(q.dtype) is the o of return_lse=True."""
+    f32 = _want_f32_parts("band_attention", out_dtype, return_lse, out, token_major_out)
     if return_lse:
         if variant != 0 or done is not None or q_prescaled or q.shape[-1] != 128:
             raise ValueError("band_attention(return_lse=True): head_dim 128 on the default schedule (variant 0) with a plain q and no "
                              f"completion counters; got D = {q.shape[-1]}, variant = {variant}, done = {done is not None}, "
                              f"q_prescaled = {q_prescaled}")
-        return _band_attention_lse(q, k, v, mask, sm_scale, head_perm_flag, vid0, num_frame, frame_size, out, token_major_out)
+        return _band_attention_lse(q, k, v, mask, sm_scale, head_perm_flag, vid0, num_frame, frame_size, out, token_major_out, f32)
     return _band_attention(q, k, v, mask, None, None, sm_scale, head_perm_flag, vid0, num_frame, frame_size, variant, out, done, done_nseg,
                            q_prescaled, token_major_out)
 
 
-def _band_attention_lse(q, k, v, mask, sm_scale, head_perm_flag, vid0, num_frame, frame_size, out, token_major_out):
-    """band_attention(return_lse=True): svg_band_attention_lse — without a layout for contiguous tensors, on views otherwise; what the
-    layout cannot describe is copied.  Never the entry without lse."""
+def _band_attention_lse(q, k, v, mask, sm_scale, head_perm_flag, vid0, num_frame, frame_size, out, token_major_out, f32=False):
+    """band_attention(return_lse=True): svg_band_attention_lse (f32: svg_band_attention_lse_f32) — without a layout for contiguous tensors,
+    on views otherwise; what the layout cannot describe is copied.  Never the entry without lse."""
     lib = load()
     _dev(head_perm_flag)
     _gpu(q, k, v, out)
@@ -457,6 +493,18 @@ def _band_attention_lse(q, k, v, mask, sm_scale, head_perm_flag, vid0, num_frame
     perm = _perm_arg(head_perm_flag, BH, vid0, num_frame, frame_size)
     # (contiguous [BH, S] whatever the layout of q / o; written whole by every launch, so a retry after a layout fall-back reuses it)
     lse = torch.empty(q.shape[:-1], dtype=torch.float32, device=q.device)
+    if f32:
+        o32 = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+
+        def call(q, k, v, lay):
+            return lib.svg_band_attention_lse_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), o32.data_ptr(), lse.data_ptr(), BH, S, D,
+                                                  _dtype_code(q), scale, C.byref(mask), perm, lay, _stream())
+
+        if q.is_contiguous() and k.is_contiguous() and v.is_contiguous():
+            _check(call(q, k, v, None), "svg_band_attention_lse_f32")
+        elif not _q_views(q, k, v, "svg_band_attention_lse_f32", lambda lay: call(q, k, v, C.byref(lay))):
+            _check(call(q.contiguous(), k.contiguous(), v.contiguous(), None), "svg_band_attention_lse_f32")
+        return o32, lse
 
     def run(q, k, v, out):
         if q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and (out.is_contiguous() if out is not None else not token_major_out):
@@ -725,29 +773,35 @@ def cross_attention_supported(q: torch.Tensor, k: torch.Tensor) -> bool:
 
 
 def cross_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, sm_scale: Optional[float] = None, token_major_out: bool = False,
-                    out: Optional[torch.Tensor] = None, return_lse: bool = False):
+                    out: Optional[torch.Tensor] = None, return_lse: bool = False, out_dtype: Optional[torch.dtype] = None):
     """Dense attention of q [B, H, Sq, D] over k, v [B, H, Skv, D] (or [BH, S, D]; Sq != Skv allowed) -> o of q's shape: softmax(q k^T
     * sm_scale) v per head (svg_cross_attention: head_dim 128, bf16 / fp16).  Strided views with stride(-1) == 1 (projection outputs,
     slices of a fused k/v projection) are read in place; views the layout cannot describe are copied.  token_major_out: as band_attention.
     return_lse: (o, lse) with lse the row log-sum-exp of the scaled scores (natural log), contiguous fp32 of shape q.shape[:-1] — what
-    merge_attention_states takes (svg_cross_attention_lse); o has the same bits as without."""
-    return _cross_attention(q, k, v, None, None, sm_scale, token_major_out, out, return_lse)
+    merge_attention_states takes (svg_cross_attention_lse); o has the same bits as without.
+    out_dtype=torch.float32 (with return_lse=True, without out / token_major_out; ValueError otherwise): (o32, lse) with o32 the rows
+    before their rounding, contiguous fp32 of q's shape (svg_cross_attention_lse_f32) — parts for merge_attention_states, which then rounds
+    once; o32.to(q.dtype) is the o of return_lse=True."""
+    f32 = _want_f32_parts("cross_attention", out_dtype, return_lse, out, token_major_out)
+    return _cross_attention(q, k, v, None, None, sm_scale, token_major_out, out, return_lse, f32)
 
 
 def cross_attention_keyrange(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_end: torch.Tensor, kv_begin: Optional[torch.Tensor] = None,
                              sm_scale: Optional[float] = None, token_major_out: bool = False, out: Optional[torch.Tensor] = None,
-                             return_lse: bool = False):
+                             return_lse: bool = False, out_dtype: Optional[torch.dtype] = None):
     """cross_attention over one key window per group of heads (svg_cross_attention_keyrange): kv_end / kv_begin are int32 GPU tensors of n
     entries, BH % n == 0 (n = B: one window per video, the key-padding mask of a batch of prompts); heads [i * BH / n, (i + 1) * BH / n)
     attend to the keys [kv_begin[i], kv_end[i]) (kv_begin None: from key 0).  The kernel clamps the windows to 0 <= begin <= end <= Skv,
     reads no key row outside a window and writes zeros for an empty one.  Layouts, token_major_out, out: as cross_attention.
-    return_lse: as cross_attention, over the window's keys; -inf for an empty window."""
+    return_lse: as cross_attention, over the window's keys; -inf for an empty window.  out_dtype: as cross_attention (zeros for an
+    empty window)."""
     assert kv_end is not None
-    return _cross_attention(q, k, v, kv_begin, kv_end, sm_scale, token_major_out, out, return_lse)
+    f32 = _want_f32_parts("cross_attention_keyrange", out_dtype, return_lse, out, token_major_out)
+    return _cross_attention(q, k, v, kv_begin, kv_end, sm_scale, token_major_out, out, return_lse, f32)
 
 
-def _cross_attention(q, k, v, kv_begin, kv_end, sm_scale, token_major_out, out, return_lse=False):
-    """cross_attention (kv_end None), and cross_attention_keyrange"""
+def _cross_attention(q, k, v, kv_begin, kv_end, sm_scale, token_major_out, out, return_lse=False, f32=False):
+    """cross_attention (kv_end None), and cross_attention_keyrange; f32: svg_cross_attention_lse_f32, (o32, lse)"""
     lib = load()
     _gpu(q, k, v, out)
     assert k.shape == v.shape and q.shape[:-2] == k.shape[:-2] and q.shape[-1] == k.shape[-1] and q.dtype == k.dtype == v.dtype
@@ -763,6 +817,18 @@ def _cross_attention(q, k, v, kv_begin, kv_end, sm_scale, token_major_out, out, 
         assert kv_begin is None or (kv_begin.dtype == torch.int32 and kv_begin.numel() == n), "kv_begin: int32, as many entries as kv_end"
     # (contiguous [BH, Sq] whatever the layout of q / o; written whole by every launch, so a retry after a layout fall-back reuses it)
     lse = torch.empty(q.shape[:-1], dtype=torch.float32, device=q.device) if return_lse else None
+    if f32:
+        o32 = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+
+        def call(q, k, v):
+            return _q_views(q, k, v, "svg_cross_attention_lse_f32", lambda lay: lib.svg_cross_attention_lse_f32(
+                q.data_ptr(), k.data_ptr(), v.data_ptr(), o32.data_ptr(), lse.data_ptr(), BH, Sq, Skv, D, _dtype_code(q), scale, _ptr(kv_begin),
+                _ptr(kv_end), BH // n, C.byref(lay), _stream()))
+
+        if not call(q, k, v):   # (what the layout cannot describe is copied)
+            ok = call(q.contiguous(), k.contiguous(), v.contiguous())
+            assert ok
+        return o32, lse
 
     def run(q, k, v, out):
         if return_lse:
@@ -784,38 +850,59 @@ MERGE_MAX_PARTS = 8   # svg_merge_attention_states: the part pointers travel in 
 
 
 def merge_attention_states(o_parts: Sequence[torch.Tensor], lse_parts: Sequence[torch.Tensor], out: Optional[torch.Tensor] = None,
-                           token_major_out: bool = False, return_lse: bool = False):
+                           token_major_out: bool = False, return_lse: bool = False, out_dtype: Optional[torch.dtype] = None):
     """Combine n partial attention results of the SAME query rows over disjoint parts of the keys into the result over all of them
     (svg_merge_attention_states): o_parts[i] [B, H, Sq, D] or [BH, Sq, D] (16-bit, D 64 / 128), lse_parts[i] fp32 of shape o.shape[:-1], as
     cross_attention(..., return_lse=True) returns them.  All parts in one pass, fp32, one rounding: o = sum_i w_i o_i / sum_i w_i with w_i =
     exp(lse_i - max lse).  At most MERGE_MAX_PARTS parts (ValueError).  out / token_major_out: as cross_attention; return_lse: (o, lse) with
-    the merged log-sum-exp."""
+    the merged log-sum-exp.
+    fp32 parts (o_parts[0].dtype == torch.float32: what the attention wrappers return with out_dtype=torch.float32) are merged by
+    svg_merge_attention_states_f32: the same statement, the parts unrounded, so the rounding to the output dtype is the only one.  The
+    output dtype is then out_dtype (bf16 / fp16) or that of `out` — one of them is required; parts of mixed dtype: ValueError."""
     lib = load()
     n = len(o_parts)
     if not 1 <= n <= MERGE_MAX_PARTS or len(lse_parts) != n:
         raise ValueError(f"merge_attention_states takes 1 to {MERGE_MAX_PARTS} parts with one lse each, got {n} and {len(lse_parts)}")
-    _gpu(*o_parts, *lse_parts, out)
     x = o_parts[0]
+    if any(t.dtype != x.dtype for t in o_parts):
+        raise ValueError(f"merge_attention_states: parts of one dtype, got {[t.dtype for t in o_parts]}")
+    f32 = x.dtype == torch.float32
+    if f32:
+        if out is not None and out_dtype is not None and out.dtype != out_dtype:
+            raise ValueError(f"merge_attention_states: out is {out.dtype}, out_dtype {out_dtype}")
+        odt = out.dtype if out is not None else out_dtype
+        if odt not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"merge_attention_states of fp32 parts: out_dtype (torch.bfloat16 / torch.float16) or a 16-bit out, got {odt}")
+    else:
+        if out_dtype is not None and out_dtype != x.dtype:
+            raise ValueError(f"merge_attention_states of {x.dtype} parts returns {x.dtype}, got out_dtype = {out_dtype}")
+        odt = x.dtype
+    _gpu(*o_parts, *lse_parts, out)
     Sq, D = x.shape[-2], x.shape[-1]
     BH = x.numel() // (Sq * D)
     for o_i, l_i in zip(o_parts, lse_parts):
-        assert o_i.shape == x.shape and o_i.dtype == x.dtype and l_i.shape == x.shape[:-1] and l_i.dtype == torch.float32
+        assert o_i.shape == x.shape and l_i.shape == x.shape[:-1] and l_i.dtype == torch.float32
     # (parts are contiguous by contract; one that is not — or not 16-byte aligned — is copied, as the cross-attention entries copy)
     o_c = [t if t.is_contiguous() and t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format) for t in o_parts]
     l_c = [t.contiguous() for t in lse_parts]
     x4 = _view4(x)
     if out is not None:
-        assert out.shape == x.shape and out.dtype == x.dtype
-    o4 = _view4(out) if out is not None else (token_major_empty(x4) if token_major_out else torch.empty(x4.shape, dtype=x.dtype, device=x.device))
+        assert out.shape == x.shape and out.dtype == odt
+    if out is not None:
+        o4 = _view4(out)
+    elif token_major_out:   # (token_major_empty, in the output dtype)
+        o4 = torch.empty((x4.shape[0], x4.shape[2], x4.shape[1], x4.shape[3]), dtype=odt, device=x.device).permute(0, 2, 1, 3)
+    else:
+        o4 = torch.empty(x4.shape, dtype=odt, device=x.device)
     direct = _strided_ok(o4)
-    dst4 = o4 if direct else torch.empty(x4.shape, dtype=x.dtype, device=x.device)
+    dst4 = o4 if direct else torch.empty(x4.shape, dtype=odt, device=x.device)
     lse = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device) if return_lse else None
     op = (C.c_void_p * MERGE_MAX_PARTS)(*[t.data_ptr() for t in o_c], *([None] * (MERGE_MAX_PARTS - n)))
     lp = (C.c_void_p * MERGE_MAX_PARTS)(*[t.data_ptr() for t in l_c], *([None] * (MERGE_MAX_PARTS - n)))
     lay = attn_layout(x4, x4, x4, dst4)
-    rc = lib.svg_merge_attention_states(C.cast(op, _VP), C.cast(lp, _VP), n, dst4.data_ptr(), _ptr(lse), BH, Sq, D, _dtype_code(x), C.byref(lay),
-                                        _stream())
-    _check(rc, "svg_merge_attention_states")
+    name = "svg_merge_attention_states_f32" if f32 else "svg_merge_attention_states"
+    rc = getattr(lib, name)(C.cast(op, _VP), C.cast(lp, _VP), n, dst4.data_ptr(), _ptr(lse), BH, Sq, D, _dtype_code(dst4), C.byref(lay), _stream())
+    _check(rc, name)
     if not direct:   # an output the layout cannot describe
         o4.copy_(dst4)
     o = out if out is not None else (o4 if x.dim() == 4 else o4.squeeze(0))
@@ -866,7 +953,7 @@ def varblock_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_
                        k_sizes: torch.Tensor, sm_scale: Optional[float] = None, q_row_idx: Optional[torch.Tensor] = None,
                        kv_row_idx: Optional[torch.Tensor] = None, variant: int = -1, fp8: bool = False,
                        workspace: Optional[torch.Tensor] = None, token_major_out: bool = False,
-                       rows_covered: bool = False, return_lse: bool = False):
+                       rows_covered: bool = False, return_lse: bool = False, out_dtype: Optional[torch.dtype] = None):
     """q: [Hq, Sq, D], k/v: [Hkv, Skv, D] (or [B, H, S, D]: heads = B * H); block_map bool [Hkv, QB, KB]; sizes int32 [Hkv, QB] /
     [Hkv, KB].  -> o of q's shape.
     fp8=True: e4m3 QK^T / PV (svg_varblock_attention_fp8, D = 128, default schedule only).
@@ -879,13 +966,17 @@ def varblock_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_
     return_lse: (o, lse) with lse the row log-sum-exp of the scaled scores over the keys the block map gives the row (natural log),
     contiguous fp32 of shape q.shape[:-1] (per q head), in the caller's row order; -inf for a row that sees no key and, without
     rows_covered, for a row no block-row covers (svg_varblock_attention_lse: head_dim 128, 16-bit, ALWAYS the two-phase body of variant
-    3 — variant -1, 3 or 8; anything else raises ValueError); o has the bits of variant 3."""
+    3 — variant -1, 3 or 8; anything else raises ValueError); o has the bits of variant 3.
+    out_dtype=torch.float32 (with return_lse=True, without token_major_out; ValueError otherwise): (o32, lse) with o32 the rows before
+    their rounding, contiguous fp32 of q's shape (svg_varblock_attention_lse_f32), zero-filled first unless rows_covered — parts for
+    merge_attention_states, which then rounds once; o32.to(q.dtype) is the o of return_lse=True."""
+    f32 = _want_f32_parts("varblock_attention", out_dtype, return_lse, None, token_major_out)
     if return_lse:
         if fp8 or variant not in (-1, 3, 8) or q.shape[-1] != 128:
             raise ValueError("varblock_attention(return_lse=True): head_dim 128, 16-bit, variant -1 / 3 / 8 (the two-phase 16x16x32 body); "
                              f"got D = {q.shape[-1]}, variant = {variant}, fp8 = {fp8}")
         return _varblock_attention_lse(q, k, v, block_map, q_sizes, k_sizes, sm_scale, q_row_idx, kv_row_idx, workspace, token_major_out,
-                                       rows_covered)
+                                       rows_covered, f32)
     lib = load()
     _dev(block_map, q_sizes, k_sizes, q_row_idx, kv_row_idx)
     _gpu(q, k, v)
@@ -944,8 +1035,9 @@ def varblock_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_
     return o
 
 
-def _varblock_attention_lse(q, k, v, block_map, q_sizes, k_sizes, sm_scale, q_row_idx, kv_row_idx, workspace, token_major_out, rows_covered):
-    """varblock_attention(return_lse=True): svg_varblock_attention_lse — without a layout for contiguous tensors, on views otherwise; what
+def _varblock_attention_lse(q, k, v, block_map, q_sizes, k_sizes, sm_scale, q_row_idx, kv_row_idx, workspace, token_major_out, rows_covered,
+                            f32=False):
+    """varblock_attention(return_lse=True): svg_varblock_attention_lse (f32: svg_varblock_attention_lse_f32) — without a layout for contiguous tensors, on views otherwise; what
     the layout cannot describe is copied.  Never an entry without lse."""
     lib = load()
     _dev(block_map, q_sizes, k_sizes, q_row_idx, kv_row_idx)
@@ -969,6 +1061,22 @@ def _varblock_attention_lse(q, k, v, block_map, q_sizes, k_sizes, sm_scale, q_ro
     lse = torch.empty(q.shape[:-1], dtype=torch.float32, device=q.device)
     if not rows_covered:
         lse.fill_(float("-inf"))
+
+    if f32:
+        o32 = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+        if not rows_covered:
+            o32.zero_()
+
+        def call(q, k, v, lay):
+            return lib.svg_varblock_attention_lse_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), o32.data_ptr(), lse.data_ptr(), Hq, Hkv, Sq, Skv,
+                                                      D, _dtype_code(q), scale, block_map.data_ptr(), q_sizes.data_ptr(), k_sizes.data_ptr(),
+                                                      QB, KB, _ptr(q_row_idx), _ptr(kv_row_idx), ws.data_ptr(), ws.numel(), lay, _stream())
+
+        if q.is_contiguous() and k.is_contiguous() and v.is_contiguous():
+            _check(call(q, k, v, None), "svg_varblock_attention_lse_f32")
+        elif not _q_views(q, k, v, "svg_varblock_attention_lse_f32", lambda lay: call(q, k, v, C.byref(lay))):
+            _check(call(q.contiguous(), k.contiguous(), v.contiguous(), None), "svg_varblock_attention_lse_f32")
+        return o32, lse
 
     def launch(q, k, v, o, lay):
         if not rows_covered:

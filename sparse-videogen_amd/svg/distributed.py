@@ -244,9 +244,18 @@ def _native_merge(o_parts, lse_parts):
     return _native.merge_attention_states(o_parts, lse_parts)
 
 
+def _native_attn_f32(q, k, v, return_lse=False):
+    """the step of fp32_parts=True: the part before its rounding; the calls without lse (world == 1, overlap=False) are the plain ones"""
+    from . import _native
+
+    if not return_lse:
+        return _native.cross_attention(q, k, v)
+    return _native.cross_attention(q, k, v, return_lse=True, out_dtype=torch.float32)
+
+
 def token_sharded_dense_attention(q_local: torch.Tensor, k_local: torch.Tensor, v_local: torch.Tensor, num_tokens: int, group=None,
                                   unit: int = 1, overlap: bool = True, attn_fn: Optional[Callable] = None,
-                                  merge_fn: Optional[Callable] = None) -> torch.Tensor:
+                                  merge_fn: Optional[Callable] = None, fp32_parts: bool = False) -> torch.Tensor:
     """Dense attention over a sequence that lives token-sharded: q_local, k_local, v_local [..., H, S_r, D] are ALL heads of this rank's
     tokens `token_range(num_tokens, rank, world, unit)` (ragged shards allowed); returns the attention output of this rank's rows over
     ALL num_tokens keys, [..., H, S_r, D].  Nothing is sharded by heads, so it works for any head count (12 heads on 8 GPUs) and leaves
@@ -259,9 +268,22 @@ def token_sharded_dense_attention(q_local: torch.Tensor, k_local: torch.Tensor, 
     depend on the rank that computed it.  world > MERGE_MAX_PARTS: ValueError (the N-way merge takes at most 8 parts).
     attn_fn(q, k, v, return_lse=False) -> o or (o, lse) and merge_fn(o_parts, lse_parts) -> o default to the native calls
     (_native.cross_attention, _native.merge_attention_states); they exist so that the schedule can be tested without a GPU.
-    Unlike head sharding, the result equals the single-GPU one TO ROUNDING, not bit for bit: with overlap=True every part is rounded to
-    the 16-bit type before the merge rounds once more (rel. L2 sqrt(2) times that of one call); overlap=False runs the
-    single-GPU arithmetic on this rank's rows."""
+    fp32_parts (the native default functions with overlap=True; nothing else changes): the steps return their rows BEFORE the rounding
+    (_native.cross_attention(..., out_dtype=torch.float32)) and the merge takes them as they are
+    (_native.merge_attention_states(..., out_dtype=q's dtype)); the output has q's dtype.  Twice the bytes of every part.  A caller's own
+    attn_fn / merge_fn are called as without it — they decide what a part is.
+    Unlike head sharding, the result equals the single-GPU one TO ROUNDING, not bit for bit.  overlap=True, fp32_parts=False: the output
+    is rounded twice, once per part and once in the merge — rel. L2 against the exact result 2.84e-3 on bf16 where one call has 2.35e-3
+    and one rounding 1.66e-3 (the two roundings add in quadrature).  overlap=True, fp32_parts=True: the merge's rounding is
+    the only one, and the result meets the tolerance of one call.  overlap=False runs the single-GPU arithmetic on this rank's rows."""
+    if fp32_parts:
+        from functools import partial
+
+        attn_fn = attn_fn or _native_attn_f32
+        if merge_fn is None:
+            from . import _native
+
+            merge_fn = partial(_native.merge_attention_states, out_dtype=q_local.dtype)
     attn_fn = attn_fn or _native_attn
     merge_fn = merge_fn or _native_merge
     rank, world = dist.get_rank(group), dist.get_world_size(group)
