@@ -774,4 +774,6 @@ int svg_debug_wg_trace(uint64_t* out, int32_t n_workgroups);
 #include "svg_attn_sparse_lse.h"
 /* ... and their fp32-row forms (parts for svg_merge_attention_states_f32), likewise */
 #include "svg_attn_f32_parts.h"
+/* ... and the LSE / fp32 forms of the device-switch and groups launches of band attention, likewise */
+#include "svg_attn_band_lse_forms.h"
 #endif /* SVG_ATTN_H_ */

@@ -23,7 +23,8 @@ extern "C" {
  * written in neither.  layout: NULL for contiguous q, k, v; otherwise it describes q, k and v, its o member is not read.
  * Return codes, all decided on the host before any launch: o32 or lse NULL: SVG_ERR_BAD_ARG; then every argument fault of the _lse entry
  * with its code and in its order; D != 128, a dtype other than bf16 / fp16 or an o32 that is not 16-byte aligned: SVG_ERR_UNSUPPORTED.
- * The pair, pre-scaled, fp8, device-switch, notify and groups entries and head_dim 64 have no fp32 form. */
+ * The pair, pre-scaled, fp8 and notify entries and head_dim 64 have no fp32 form; the device-switch and groups forms of the band entry
+ * are include/svg_attn_band_lse_forms.h. */
 int svg_band_attention_lse_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t BH, int32_t S, int32_t D,
                                int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
                                const svg_attn_layout_t* layout /* NULL: contiguous */, void* stream);

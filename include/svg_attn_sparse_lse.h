@@ -29,8 +29,9 @@ extern "C" {
  * 16x16x32 body in its default launch order (variant 3), also where variant -1 would pick 128-row tiles (Sq < 160 * QB).
  * Return codes, all decided on the host before any launch: lse NULL: SVG_ERR_BAD_ARG; then every argument fault of the plain entry with
  * the code and in the order of the plain entry (pointers and sizes, mask / head permutation, workspace, layout); then D != 128 or a dtype
- * other than bf16 / fp16: SVG_ERR_UNSUPPORTED.  The pre-scaled, fp8, device-switch, notify and groups entries, the explicit schedule
- * variants and head_dim 64 have no lse form. */
+ * other than bf16 / fp16: SVG_ERR_UNSUPPORTED.  The pre-scaled, fp8 and notify entries, the explicit schedule variants and head_dim 64
+ * have no lse form; the device-switch and groups forms of the band entry are include/svg_attn_band_lse_forms.h.  svg_band_attention_lse
+ * runs the work queue where svg_band_attention does (bit-identical to the static mapping). */
 int svg_band_attention_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S, int32_t D, int32_t dtype,
                            float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
                            const svg_attn_layout_t* layout /* NULL: contiguous */, void* stream);

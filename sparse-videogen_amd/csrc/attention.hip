@@ -1,6 +1,7 @@
 // SVG1 band (block-sparse) and dense attention for gfx950: the kernels that run the bodies of attn_core.h / attn_m16.h on the band
 // policy (band_policy.h), the counter pool of the queue launches, the svg_band_attention* entries, the completion-counter waiters and
-// the svg_debug_* trace readers; svg_band_attention_lse (row log-sum-exp output) and svg_band_attention_lse_f32 (fp32 rows).  (One-wave-per-SIMD body: attention_w4.hip; fp8:
+// the svg_debug_* trace readers; svg_band_attention_lse (row log-sum-exp output) and svg_band_attention_lse_f32 (fp32 rows) and their
+// device-switch and groups forms (include/svg_attn_band_lse_forms.h).  (One-wave-per-SIMD body: attention_w4.hip; fp8:
 // attention_f8.hip; SVG2: attention_varblock.hip.)
 #include <algorithm>
 #include <atomic>
@@ -76,8 +77,8 @@ __global__ __launch_bounds__(512, 2) void band_attn_m16_kernel(typename BandPoli
 }
 // LSE form (svg_band_attention_lse): band_attn_m16_kernel on BandLsePolicy — the same template arguments, SPEC and the replay counter
 // included, so o keeps the bits of the plain entry; the epilogue of attn_m16_tile also stores one fp32 per query row.  A q-tile that fails
-// its validation returns before the epilogue and stores neither o nor lse; its replay stores both.  Static mapping only (the queue kernel
-// is bit-identical to it).  (Its own kernel template: the kernels above and below keep their symbols and their listings.)
+// its validation returns before the epilogue and stores neither o nor lse; its replay stores both.  The static mapping; the queue form is
+// band_attn_lse_m16_queue_kernel below.  (Its own kernel template: the kernels above and below keep their symbols and their listings.)
 template <typename T>
 __global__ __launch_bounds__(512, 2) void band_attn_lse_m16_kernel(typename BandLsePolicy<T>::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -146,6 +147,51 @@ __global__ __launch_bounds__(512, 2) void band_attn_m16_queue_kernel(typename Ba
     }
     if (threadIdx.x == 0) qd.leave(gridDim.x);
 }
+// LSE form of the queue kernel (svg_band_attention_lse where band_dispatch takes the queue): the loop of band_attn_m16_queue_kernel<T, false>
+// on BandLsePolicy — the same slot protocol, take / decode / leave and replay; bit-identical to band_attn_lse_m16_kernel.  (A copy of
+// the loop, not a function both kernels share: with the loop factored out the listings of the kernel above came out different.  The
+// fp32 policy has no queue form: its instantiation reserved 36 bytes of scratch per lane, so svg_band_attention_lse_f32 keeps the static
+// mapping.)
+template <typename T>
+__global__ __launch_bounds__(512, 2) void band_attn_lse_m16_queue_kernel(typename BandLsePolicy<T>::Params prm, BandQueue qd) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    using Pol = BandLsePolicy<T>;
+    int* const slot = (int*)(smem + attn_m16_lds_bytes());   // (head, q-tile) of the next work item, from lane 0 to the workgroup
+    // (slot[2]: the verdict of the validation, 0 / 1 / 2 as in band_attn_m16_queue_kernel)
+    constexpr bool kSpec = std::is_same_v<T, __bf16>;
+    int dry = 0;
+    if constexpr (kSpec) {
+        if (threadIdx.x == 0) slot[2] = 0;
+    }
+    for (;;) {
+        if (threadIdx.x == 0) {
+            bool fresh = true;
+            if constexpr (kSpec) {
+                fresh = __builtin_amdgcn_readfirstlane(slot[2]) != 1;   // (a scalar: one lane is active here)
+                slot[2] = fresh ? 0 : 2;
+            }
+            if (fresh) {
+                const int xcd = __builtin_amdgcn_s_getreg((31 << 11) | 20) & (kNumXCD - 1);   // HW_REG_XCC_ID
+                int head = -1, qt = 0;
+                const int w = qd.take(xcd, dry);
+                if (w >= 0) qd.decode(w, head, qt);
+                slot[0] = head, slot[1] = qt;
+            }
+        }
+        __syncthreads();
+        const int head = __builtin_amdgcn_readfirstlane(slot[0]), qt = __builtin_amdgcn_readfirstlane(slot[1]);
+        if (head < 0) break;
+        typename Pol::Ctx ctx;
+        Pol::init_tile(prm, ctx, head, qt);
+        if constexpr (kSpec) {
+            const int check_mask = __builtin_amdgcn_readfirstlane(slot[2]) == 2 ? 0 : kCheckEvery - 1;
+            attn_m16_tile<T, Pol, false, 1, false, true>(prm, ctx, smem, check_mask, &g_band_replays);
+        } else {
+            attn_m16_tile<T, Pol, false, 1, false>(prm, ctx, smem);
+        }
+    }
+    if (threadIdx.x == 0) qd.leave(gridDim.x);
+}
 // device-side switch between two masks on the 16x16x32 body (svg_band_attention_switch[_prescaled] at head_dim 128): `flag[0] != 0` selects prm_alt
 template <typename T, bool PRE = false>
 __global__ __launch_bounds__(512, 2) void band_attn_m16_switch_kernel(typename BandPolicy<T, 128, 8>::Params prm,
@@ -154,6 +200,25 @@ __global__ __launch_bounds__(512, 2) void band_attn_m16_switch_kernel(typename B
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (flag[0] != 0) attn_body_m16<T, BandPolicy<T, 128, 8>, false, 1, PRE, !PRE>(prm_alt, smem, nullptr, &g_band_replays);
     else attn_body_m16<T, BandPolicy<T, 128, 8>, false, 1, PRE, !PRE>(prm, smem, nullptr, &g_band_replays);
+}
+// LSE / fp32 forms of the device switch (svg_band_attention_switch_lse[_f32]): band_attn_m16_switch_kernel<T, false> on BandLsePolicy /
+// BandF32Policy — static mapping over the q-tiles of the larger mask, SPEC and the replay counter as there.  lse (and o32) are indexed by
+// the physical q row under the parameter block the flag selects: prm_alt carries no head permutation, so its rows are the logical ones.
+template <typename T>
+__global__ __launch_bounds__(512, 2) void band_attn_lse_m16_switch_kernel(typename BandLsePolicy<T>::Params prm,
+                                                                          typename BandLsePolicy<T>::Params prm_alt,
+                                                                          const int32_t* __restrict__ flag) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (flag[0] != 0) attn_body_m16<T, BandLsePolicy<T>, false, 1, false, true>(prm_alt, smem, nullptr, &g_band_replays);
+    else attn_body_m16<T, BandLsePolicy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
+}
+template <typename T>
+__global__ __launch_bounds__(512, 2) void band_attn_f32_m16_switch_kernel(typename BandF32Policy<T>::Params prm,
+                                                                          typename BandF32Policy<T>::Params prm_alt,
+                                                                          const int32_t* __restrict__ flag) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (flag[0] != 0) attn_body_m16<T, BandF32Policy<T>, false, 1, false, true>(prm_alt, smem, nullptr, &g_band_replays);
+    else attn_body_m16<T, BandF32Policy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
 }
 // the same for q that carries sm_scale * log2(e) (svg_band_attention_prescaled): no scale-and-shift per score
 template <typename T, int D>
@@ -290,6 +355,33 @@ static int band_check_args(const void* q, const void* k, const void* v, const vo
     return check_rows(S, D);
 }
 
+// The 16x16x32 kernels of a single-mask launch: resident workgroups on a work queue (kern_q), or `kern` on the static mapping where the
+// call counts completions (`counts`), no counter block is to be had, or one round of workgroups covers the launch.
+template <typename Pol, typename KQ, typename K>
+static int launch_band_queue(KQ kern_q, K kern, const typename Pol::Params& p, int lds, bool counts, hipStream_t st) {
+    int n_cu = 0;
+    int32_t* const block = counts ? nullptr : band_queue_block(st, n_cu);
+    const int cap = band_queue_cap();
+    // (a launch of one round has nothing to balance, and a workgroup pays nine atomics to find the queue dry: 0.068 against
+    //  0.064 ms on the 52 q-tiles of the benchmark's tiny workload)
+    if (!block || (p.nqt * p.BH <= n_cu && cap == 0)) return launch_attn(kern, dim3(p.nqt * p.BH), 512, lds, st, p);
+    BandQueue qd = make_band_queue<Pol>(p);
+    qd.ctr = block;
+    int n_wg = std::min(qd.n_items, n_cu);
+    if (cap > 0) n_wg = std::min(n_wg, cap);
+    return launch_attn(kern_q, dim3(n_wg), 512, lds, st, p, qd);
+}
+
+// parameters of an LSE / fp32 launch: those of the band policy plus lse (and o32, in the place of the 16-bit o)
+template <typename Pol, typename T>
+static typename Pol::Params band_lse_params(const void* q, const void* k, const void* v, void* o, int BH, int S, float sm_scale,
+                                            const svg_band_mask_t* mask, const svg_perm_desc_t* perm, const BandOpts& opts) {
+    typename Pol::Params p = make_band_params<Pol, T>(q, k, v, opts.o32 ? nullptr : o, BH, S, sm_scale, mask, perm, opts);
+    p.lse = opts.lse;
+    if constexpr (HasRowO32<Pol>::value) p.o32 = opts.o32;
+    return p;
+}
+
 // Every svg_band_attention* entry, after the null checks of its own arguments: validation, then the kernel of `variant` for
 // (dtype, D).  opts carries what the entry adds: pre-scaled q, completion counters (`done_words` of them), the device switch (its
 // alternate mask is checked here too) and strided tensors (opts.strided: `layout` describes them).
@@ -302,24 +394,31 @@ static int band_dispatch(const void* q, const void* k, const void* v, void* o, i
     if (opts.done && (int64_t)done_words < (int64_t)BH * (opts.done_nseg + 1)) return SVG_ERR_WORKSPACE;   // segment counters + one hidden counter per head
     if (opts.strided && (rc = layout_from_abi(layout, BH, BH, S, S, D, q, k, v, o, opts.lay)) != SVG_OK) return rc;
     const hipStream_t st = (hipStream_t)stream;
-    if (opts.lse) {   // svg_band_attention_lse: the default head_dim-128 body only, on the static mapping
-        if (D != 128 || variant != kBandAuto || opts.done || opts.prescaled || opts.use_alt) return SVG_ERR_UNSUPPORTED;
+    if (opts.lse) {   // the LSE / fp32 forms: the default head_dim-128 body — single mask (queue or static mapping) or device switch
+        if (D != 128 || variant != kBandAuto || opts.done || opts.prescaled) return SVG_ERR_UNSUPPORTED;
         if (opts.o32 && ((size_t)opts.o32 & 15) != 0) return SVG_ERR_UNSUPPORTED;   // 16-byte stores
         return dispatch_td(dtype, D, [&](auto t, auto d) -> int {
             using T = decltype(t);
             if constexpr (decltype(d)::value != 128) {
                 return SVG_ERR_UNSUPPORTED;
             } else {
-                if (opts.o32) {   // svg_band_attention_lse_f32: `o` is o32 here, the kernel gets no 16-bit o
+                const int lds = attn_m16_lds_bytes() + kTailLds;
+                auto run_switch = [&](auto pol, auto kern_sw) -> int {
+                    using Pol = decltype(pol);
+                    const typename Pol::Params a = band_lse_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
+                    const typename Pol::Params b = band_lse_params<Pol, T>(q, k, v, o, BH, S, sm_scale, opts.alt_mask, nullptr, opts);
+                    return launch_attn(kern_sw, dim3(std::max(a.nqt, b.nqt) * BH), 512, lds, st, a, b, opts.use_alt);
+                };
+                if (opts.o32) {   // the *_f32 entries: `o` is o32 here, the kernel gets no 16-bit o; static mapping only
                     using Pol = BandF32Policy<T>;
-                    typename Pol::Params p = make_band_params<Pol, T>(q, k, v, nullptr, BH, S, sm_scale, mask, perm, opts);
-                    p.lse = opts.lse, p.o32 = opts.o32;
-                    return launch_attn(band_attn_f32_m16_kernel<T>, dim3(p.nqt * BH), 512, attn_m16_lds_bytes() + kTailLds, st, p);
+                    if (opts.use_alt) return run_switch(Pol(), band_attn_f32_m16_switch_kernel<T>);
+                    const typename Pol::Params p = band_lse_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
+                    return launch_attn(band_attn_f32_m16_kernel<T>, dim3(p.nqt * BH), 512, lds, st, p);
                 }
                 using Pol = BandLsePolicy<T>;
-                typename Pol::Params p = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
-                p.lse = opts.lse;
-                return launch_attn(band_attn_lse_m16_kernel<T>, dim3(p.nqt * BH), 512, attn_m16_lds_bytes() + kTailLds, st, p);
+                if (opts.use_alt) return run_switch(Pol(), band_attn_lse_m16_switch_kernel<T>);
+                const typename Pol::Params p = band_lse_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
+                return launch_band_queue<Pol>(band_attn_lse_m16_queue_kernel<T>, band_attn_lse_m16_kernel<T>, p, lds, false, st);
             }
         });
     }
@@ -351,17 +450,7 @@ static int band_dispatch(const void* q, const void* k, const void* v, void* o, i
         // where the call counts completions or no counter block is to be had
         auto launch_queue = [&](auto kern_q, auto kern, int lds) {
             const typename Pol::Params p = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
-            int n_cu = 0;
-            int32_t* const block = opts.done ? nullptr : band_queue_block(st, n_cu);
-            const int cap = band_queue_cap();
-            // (a launch of one round has nothing to balance, and a workgroup pays nine atomics to find the queue dry: 0.068 against
-            //  0.064 ms on the 52 q-tiles of the benchmark's tiny workload)
-            if (!block || (p.nqt * BH <= n_cu && cap == 0)) return launch_attn(kern, dim3(p.nqt * BH), 512, lds, st, p);
-            BandQueue qd = make_band_queue<Pol>(p);
-            qd.ctr = block;
-            int n_wg = std::min(qd.n_items, n_cu);
-            if (cap > 0) n_wg = std::min(n_wg, cap);
-            return launch_attn(kern_q, dim3(n_wg), 512, lds, st, p, qd);
+            return launch_band_queue<Pol>(kern_q, kern, p, lds, opts.done != nullptr, st);
         };
         // a device-switch kernel: the parameters of both masks (the alternate one without the head permutation) and the flag, over
         // the q-tiles of the larger of the two
@@ -569,6 +658,37 @@ extern "C" int svg_band_attention_switch_prescaled(const void* q_scaled, const v
     return band_dispatch(q_scaled, k, v, o, BH, S, D, dtype, 1.f, mask, perm, kBandAuto, opts, 0, nullptr, stream);
 }
 
+// LSE / fp32 forms of the device switch (include/svg_attn_band_lse_forms.h): the null checks of the plain switch entry behind the one of
+// lse / o32, then band_dispatch with opts.lse (and opts.o32).  o32 travels in the place of o as in svg_band_attention_lse_f32.
+static int band_switch_lse(const void* q, const void* k, const void* v, void* o, float* o32, float* lse, int32_t BH, int32_t S, int32_t D,
+                           int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
+                           const svg_band_mask_t* alt_mask, const int32_t* use_alt_flag, const svg_attn_layout_t* layout, void* stream) {
+    if (!alt_mask || !use_alt_flag) return SVG_ERR_BAD_ARG;
+    BandOpts opts = switch_opts(alt_mask, use_alt_flag);
+    opts.lse = lse, opts.o32 = o32;
+    opts.strided = layout != nullptr;
+    svg_attn_layout_t abi{};
+    if (layout && o32) abi = *layout, abi.o = abi.q, layout = &abi;
+    if (o32) o = layout ? const_cast<void*>(q) : (void*)o32;
+    return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, 0, layout, stream);
+}
+
+extern "C" int svg_band_attention_switch_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S,
+                                             int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
+                                             const svg_perm_desc_t* perm, const svg_band_mask_t* alt_mask, const int32_t* use_alt_flag,
+                                             const svg_attn_layout_t* layout, void* stream) {
+    if (!lse) return SVG_ERR_BAD_ARG;
+    return band_switch_lse(q, k, v, o, nullptr, lse, BH, S, D, dtype, sm_scale, mask, perm, alt_mask, use_alt_flag, layout, stream);
+}
+
+extern "C" int svg_band_attention_switch_lse_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t BH, int32_t S,
+                                                 int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
+                                                 const svg_perm_desc_t* perm, const svg_band_mask_t* alt_mask,
+                                                 const int32_t* use_alt_flag, const svg_attn_layout_t* layout, void* stream) {
+    if (!o32 || !lse) return SVG_ERR_BAD_ARG;
+    return band_switch_lse(q, k, v, nullptr, o32, lse, BH, S, D, dtype, sm_scale, mask, perm, alt_mask, use_alt_flag, layout, stream);
+}
+
 // svg_band_groups_attention: the heads of one call in groups of consecutive heads, each under a mask (and an alternate mask) of its
 // own — the videos of a batch whose text lengths differ.  Every group is checked before the first launches; the launches are those of
 // the single-mask entry the arguments select, one pass through band_dispatch per group.  (One launch per group and not a mask per head
@@ -598,11 +718,17 @@ BandGroup band_group_at(const void* q, const void* k, const void* v, void* o, in
 }
 }  // namespace
 
-extern "C" int svg_band_groups_attention(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t S, int32_t D,
-                                         int32_t dtype, float sm_scale, const svg_band_mask_t* masks, const svg_band_mask_t* alt_masks,
-                                         const int32_t* group_heads, int32_t n_groups, const svg_perm_desc_t* perm,
-                                         const int32_t* use_alt_flag, int32_t q_prescaled, const svg_attn_layout_t* layout,
-                                         void* stream) {
+// every groups entry.  lse (and o32): the LSE / fp32 forms — o32 then stands in for o as in svg_band_attention_lse_f32, and both
+// advance to a group's first head as contiguous [BH, S] / [BH, S, D] fp32 whatever the layout.
+static int band_groups_run(const void* q, const void* k, const void* v, void* o, float* o32, float* lse, int32_t BH, int32_t S, int32_t D,
+                           int32_t dtype, float sm_scale, const svg_band_mask_t* masks, const svg_band_mask_t* alt_masks,
+                           const int32_t* group_heads, int32_t n_groups, const svg_perm_desc_t* perm, const int32_t* use_alt_flag,
+                           int32_t q_prescaled, const svg_attn_layout_t* layout, void* stream) {
+    svg_attn_layout_t abi{};
+    if (o32) {
+        if (layout) abi = *layout, abi.o = abi.q, layout = &abi;
+        o = layout ? const_cast<void*>(q) : (void*)o32;
+    }
     if (!q || !k || !v || !o || !masks || !group_heads || n_groups < 1 || BH <= 0 || S <= 0) return SVG_ERR_BAD_ARG;
     if ((alt_masks != nullptr) != (use_alt_flag != nullptr)) return SVG_ERR_BAD_ARG;
     int64_t heads = 0;
@@ -627,15 +753,47 @@ extern "C" int svg_band_groups_attention(const void* q, const void* k, const voi
     }
     if (opts.prescaled && opts.strided) return SVG_ERR_UNSUPPORTED;   // (no single-mask entry takes a pre-scaled q with a layout)
     if (const int rc = dispatch_td(dtype, D, [](auto, auto) { return (int)SVG_OK; }); rc != SVG_OK) return rc;
+    if (lse && (D != 128 || ((size_t)o32 & 15) != 0)) return SVG_ERR_UNSUPPORTED;
     h0 = 0;
     for (int g = 0; g < n_groups; h0 += group_heads[g++]) {
         const BandGroup gr = band_group_at(q, k, v, o, h0, S, D, perm, layout);
         if (alt_masks) opts.alt_mask = alt_masks + g;
+        if (lse) opts.lse = lse + (size_t)h0 * (size_t)S;
+        if (o32) opts.o32 = o32 + (size_t)h0 * (size_t)S * (size_t)D;
         const int rc = band_dispatch(gr.q, gr.k, gr.v, gr.o, group_heads[g], S, D, dtype, scale, masks + g, perm ? &gr.perm : nullptr,
                                      kBandAuto, opts, 0, layout, stream);
         if (rc != SVG_OK) return rc;   // (a failed launch: SVG_ERR_LAUNCH)
     }
     return SVG_OK;
+}
+
+extern "C" int svg_band_groups_attention(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t S, int32_t D,
+                                         int32_t dtype, float sm_scale, const svg_band_mask_t* masks, const svg_band_mask_t* alt_masks,
+                                         const int32_t* group_heads, int32_t n_groups, const svg_perm_desc_t* perm,
+                                         const int32_t* use_alt_flag, int32_t q_prescaled, const svg_attn_layout_t* layout,
+                                         void* stream) {
+    return band_groups_run(q, k, v, o, nullptr, nullptr, BH, S, D, dtype, sm_scale, masks, alt_masks, group_heads, n_groups, perm,
+                           use_alt_flag, q_prescaled, layout, stream);
+}
+
+extern "C" int svg_band_groups_attention_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S,
+                                             int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* masks,
+                                             const svg_band_mask_t* alt_masks, const int32_t* group_heads, int32_t n_groups,
+                                             const svg_perm_desc_t* perm, const int32_t* use_alt_flag, const svg_attn_layout_t* layout,
+                                             void* stream) {
+    if (!lse) return SVG_ERR_BAD_ARG;
+    return band_groups_run(q, k, v, o, nullptr, lse, BH, S, D, dtype, sm_scale, masks, alt_masks, group_heads, n_groups, perm,
+                           use_alt_flag, 0, layout, stream);
+}
+
+extern "C" int svg_band_groups_attention_lse_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t BH, int32_t S,
+                                                 int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* masks,
+                                                 const svg_band_mask_t* alt_masks, const int32_t* group_heads, int32_t n_groups,
+                                                 const svg_perm_desc_t* perm, const int32_t* use_alt_flag,
+                                                 const svg_attn_layout_t* layout, void* stream) {
+    if (!o32 || !lse) return SVG_ERR_BAD_ARG;
+    return band_groups_run(q, k, v, nullptr, o32, lse, BH, S, D, dtype, sm_scale, masks, alt_masks, group_heads, n_groups, perm,
+                           use_alt_flag, 0, layout, stream);
 }
 
 extern "C" int32_t svg_band_queue_order(int32_t BH, int32_t S, const svg_band_mask_t* mask, int32_t* out, int32_t out_words) {

@@ -228,6 +228,18 @@ SPARSE_F32_SIGNATURES = {
 }
 
 
+# include/svg_attn_band_lse_forms.h: the LSE / fp32 forms of the device-switch and groups launches of band attention, in a table of their own
+# for the same reason (tests/test_band_lse_forms_cpu.py)
+BAND_LSE_FORM_SIGNATURES = {
+    "svg_band_attention_switch_lse": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _F32, C.POINTER(BandMask), C.POINTER(PermDesc),
+                                                C.POINTER(BandMask), _VP, C.POINTER(AttnLayout), _VP]),
+    "svg_band_groups_attention_lse": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _F32, C.POINTER(BandMask), C.POINTER(BandMask),
+                                                C.POINTER(_I32), _I32, C.POINTER(PermDesc), _VP, C.POINTER(AttnLayout), _VP]),
+}
+BAND_LSE_FORM_SIGNATURES["svg_band_attention_switch_lse_f32"] = BAND_LSE_FORM_SIGNATURES["svg_band_attention_switch_lse"]
+BAND_LSE_FORM_SIGNATURES["svg_band_groups_attention_lse_f32"] = BAND_LSE_FORM_SIGNATURES["svg_band_groups_attention_lse"]
+
+
 def lib_path() -> Path:
     return Path(os.environ.get("SVG_ATTN_LIB", str(_LIB_PATH)))
 
@@ -240,7 +252,7 @@ def load(strict: bool = True) -> Optional[C.CDLL]:
     p = lib_path()
     try:
         lib = C.CDLL(str(p))
-        for name, (res, args) in {**SIGNATURES, **SPARSE_LSE_SIGNATURES, **SPARSE_F32_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **SPARSE_LSE_SIGNATURES, **SPARSE_F32_SIGNATURES, **BAND_LSE_FORM_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -519,6 +531,41 @@ def _band_attention_lse(q, k, v, mask, sm_scale, head_perm_flag, vid0, num_frame
     return _run_or_copy(run, (q, k, v), out), lse
 
 
+def _band_form_lse(q, k, v, out, token_major_out, f32, name, call, views_ok=True):
+    """The LSE (f32: fp32-row) form `name` of a device-switch or groups launch: call(q, k, v, o, lse, layout) -> rc, with o the 16-bit
+    output or o32 — without a layout for contiguous tensors, on views where the layout describes them (views_ok: the entry takes one for
+    this call), copied otherwise.  Never the entry without lse.  -> (o | o32, lse)"""
+    # (contiguous [BH, S] whatever the layout of q / o; written whole by every launch, so a retry after a layout fall-back reuses it)
+    lse = torch.empty(q.shape[:-1], dtype=torch.float32, device=q.device)
+    if f32:
+        o32 = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+        if q.is_contiguous() and k.is_contiguous() and v.is_contiguous():
+            _check(call(q, k, v, o32, lse, None), name)
+        elif not (views_ok and _q_views(q, k, v, name, lambda lay: call(q, k, v, o32, lse, C.byref(lay)))):
+            _check(call(q.contiguous(), k.contiguous(), v.contiguous(), o32, lse, None), name)
+        return o32, lse
+
+    def run(q, k, v, out):
+        dense = q.is_contiguous() and k.is_contiguous() and v.is_contiguous()
+        if dense and (out.is_contiguous() if out is not None else not (token_major_out and views_ok)):
+            o = torch.empty_like(q) if out is None else out
+            _check(call(q, k, v, o, lse, None), name)
+            return o
+        if not views_ok:
+            return None
+        return _try_strided(q, k, v, out, token_major_out, name, lambda o4, lay: call(q, k, v, o4, lse, C.byref(lay)))
+
+    return _run_or_copy(run, (q, k, v), out), lse
+
+
+def _band_form_checks(what, q, k, v, out, q_prescaled, return_lse, out_dtype, token_major_out) -> bool:
+    """return_lse / out_dtype of band_attention_switch and band_attention_groups, before anything is loaded: -> fp32 rows?"""
+    f32 = _want_f32_parts(what, out_dtype, return_lse, out, token_major_out)
+    if return_lse and (q_prescaled or q.shape[-1] != 128):
+        raise ValueError(f"{what}(return_lse=True): head_dim 128 with a plain q; got D = {q.shape[-1]}, q_prescaled = {q_prescaled}")
+    return f32
+
+
 def _band_attention(q, k, v, mask, alt_mask, use_alt_flag, sm_scale, head_perm_flag, vid0, num_frame, frame_size, variant, out, done,
                     done_nseg, q_prescaled, token_major_out):
     """band_attention, and band_attention_switch when use_alt_flag is given"""
@@ -711,13 +758,34 @@ def wait_counters(counters: torch.Tensor, target: int, timeout_ms: int = 0, time
 def band_attention_switch(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: BandMask, alt_mask: BandMask,
                           use_alt_flag: torch.Tensor, sm_scale: Optional[float] = None,
                           head_perm_flag: Optional[torch.Tensor] = None, vid0: int = 0, num_frame: int = 1, frame_size: int = 1,
-                          out: Optional[torch.Tensor] = None, q_prescaled: bool = False, token_major_out: bool = False) -> torch.Tensor:
+                          out: Optional[torch.Tensor] = None, q_prescaled: bool = False, token_major_out: bool = False,
+                          return_lse: bool = False, out_dtype: Optional[torch.dtype] = None):
     """band_attention with a device-side switch: `use_alt_flag` (int32 [1] on the GPU) != 0 selects `alt_mask` without the head
     placement, otherwise `mask` with it (svg_band_attention_switch) — no host read of the flag.
     q_prescaled: q carries sm_scale * log2(e) (svg_band_attention_switch_prescaled, D = 128).
-    Strided views / token_major_out: as band_attention (svg_band_attention_switch_strided: head_dim 128, plain q)."""
+    Strided views / token_major_out: as band_attention (svg_band_attention_switch_strided: head_dim 128, plain q).
+    return_lse / out_dtype=torch.float32: (o, lse) / (o32, lse) as in band_attention, lse under the mask the flag selects and in the row
+    order that mask runs in (svg_band_attention_switch_lse[_f32]: head_dim 128, plain q; anything else raises ValueError); o has the
+    same bits as without."""
+    f32 = _band_form_checks("band_attention_switch", q, k, v, out, q_prescaled, return_lse, out_dtype, token_major_out)
     _dev(use_alt_flag)
     assert use_alt_flag.dtype == torch.int32 and use_alt_flag.numel() >= 1
+    if return_lse:
+        lib = load()
+        _dev(head_perm_flag)
+        _gpu(q, k, v, out)
+        assert q.shape == k.shape == v.shape and q.dtype == k.dtype == v.dtype
+        S, D = q.shape[-2], q.shape[-1]
+        BH = q.numel() // (S * D)
+        perm = _perm_arg(head_perm_flag, BH, vid0, num_frame, frame_size)
+        args = (BH, S, D, _dtype_code(q), _sm_scale(sm_scale, D), C.byref(mask), perm, C.byref(alt_mask), use_alt_flag.data_ptr())
+        if f32:
+            return _band_form_lse(q, k, v, out, token_major_out, True, "svg_band_attention_switch_lse_f32", lambda q, k, v, o, lse, lay:
+                                  lib.svg_band_attention_switch_lse_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(),
+                                                                        *args, lay, _stream()))
+        return _band_form_lse(q, k, v, out, token_major_out, False, "svg_band_attention_switch_lse", lambda q, k, v, o, lse, lay:
+                              lib.svg_band_attention_switch_lse(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), *args,
+                                                                lay, _stream()))
     return _band_attention(q, k, v, mask, alt_mask, use_alt_flag, sm_scale, head_perm_flag, vid0, num_frame, frame_size, 0, out, None, 1,
                            q_prescaled, token_major_out)
 
@@ -725,12 +793,16 @@ def band_attention_switch(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
 def band_attention_groups(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, masks: Sequence[BandMask], group_heads: Sequence[int],
                           alt_masks: Optional[Sequence[BandMask]] = None, use_alt_flag: Optional[torch.Tensor] = None,
                           head_perm_flag: Optional[torch.Tensor] = None, vid0: int = 0, num_frame: int = 1, frame_size: int = 1,
-                          out: Optional[torch.Tensor] = None, q_prescaled: bool = False, token_major_out: bool = False) -> torch.Tensor:
+                          out: Optional[torch.Tensor] = None, q_prescaled: bool = False, token_major_out: bool = False,
+                          return_lse: bool = False, out_dtype: Optional[torch.dtype] = None):
     """band_attention / band_attention_switch (use_alt_flag given, with alt_masks) over groups of consecutive heads, group g —
     group_heads[g] heads — under masks[g] (alt_masks[g]): svg_band_groups_attention, bit for bit the single-mask call on each group's
     heads.  q, k, v: [B, H, S, D] (or [BH, S, D]), default schedule, default softmax scale.  Strided views, `out` and token_major_out as in
     band_attention: read / written in place where the single-mask strided entry would (plain q, every group a whole number of the H
-    heads of a video), copied otherwise."""
+    heads of a video), copied otherwise.
+    return_lse / out_dtype=torch.float32: (o, lse) / (o32, lse) as in band_attention / band_attention_switch, bit for bit that call on
+    each group's heads (svg_band_groups_attention_lse[_f32]: head_dim 128, plain q; anything else raises ValueError)."""
+    f32 = _band_form_checks("band_attention_groups", q, k, v, out, q_prescaled, return_lse, out_dtype, token_major_out)
     lib = load()
     _dev(head_perm_flag, use_alt_flag)
     _gpu(q, k, v, out)
@@ -750,8 +822,18 @@ def band_attention_groups(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
         return lib.svg_band_groups_attention(qq.data_ptr(), kk.data_ptr(), vv.data_ptr(), o.data_ptr(), BH, S, D, _dtype_code(q), _sm_scale(None, D),
                                              marr, aarr, garr, n, perm, flag, int(q_prescaled), lay, _stream())
 
-    dense_in = q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and (out is None or out.is_contiguous())
     H = _view4(q).shape[1]
+    if return_lse:
+        args = (BH, S, D, _dtype_code(q), _sm_scale(None, D), marr, aarr, garr, n, perm, flag)
+        whole = all(int(g) % H == 0 for g in group_heads)
+        if f32:
+            return _band_form_lse(q, k, v, out, token_major_out, True, "svg_band_groups_attention_lse_f32", lambda q, k, v, o, lse, lay:
+                                  lib.svg_band_groups_attention_lse_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(),
+                                                                        *args, lay, _stream()), whole)
+        return _band_form_lse(q, k, v, out, token_major_out, False, "svg_band_groups_attention_lse", lambda q, k, v, o, lse, lay:
+                              lib.svg_band_groups_attention_lse(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), *args,
+                                                                lay, _stream()), whole)
+    dense_in = q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and (out is None or out.is_contiguous())
     if (not dense_in or (token_major_out and out is None)) and not q_prescaled and strided_attention_supported(q) \
             and all(int(g) % H == 0 for g in group_heads):
         o = _try_strided(q, k, v, out, token_major_out, "svg_band_groups_attention", lambda o4, lay: call(q, k, v, o4, C.byref(lay)))

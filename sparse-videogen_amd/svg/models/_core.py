@@ -142,25 +142,44 @@ def _dense_sdpa(q, k, v, valid_len):
     return o
 
 
+def _state_kw(what: str, return_lse: bool, out_dtype, q_prescaled: bool, token_major_out: bool, fp8: bool = False, fused: bool = True) -> dict:
+    """The keywords that ask a _native band call for the softmax state as well — (o, lse), or (o32, lse) with out_dtype=torch.float32: parts
+    for merge_attention_states — or just the output layout without return_lse.  What has no such form raises here, before anything runs:
+    there is no fall-back to a path without lse."""
+    if not return_lse:
+        if out_dtype is not None:
+            raise ValueError(f"{what}(out_dtype={out_dtype}): fp32 rows go with return_lse=True")
+        return dict(token_major_out=token_major_out)
+    if q_prescaled or fp8 or not fused:
+        raise ValueError(f"{what}(return_lse=True): the fused 16-bit path with a plain q; got q_prescaled = {q_prescaled}, fp8 = {fp8}, "
+                         f"fused = {fused}")
+    if _dist.active():
+        raise NotImplementedError(f"{what}(return_lse=True): head sharding (svg.distributed) gathers o only")
+    return dict(return_lse=True, out_dtype=out_dtype, token_major_out=token_major_out and out_dtype is None)
+
+
 @time_logging_decorator("Level 3 - Dense Flash Attention")
-def dense_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, valid_len=None, q_prescaled: bool = False) -> torch.Tensor:
+def dense_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, valid_len=None, q_prescaled: bool = False, return_lse: bool = False,
+                    out_dtype=None):
     """Dense attention [cfg, H, S, D].  valid_len < S: two independent segments [0, valid) and [valid, S) — what the
     reference gets from flash_attn_varlen_func with cu_seqlens [0, valid, S] (hyvideo/attention.py:452-470).
     valid_len: one int for the batch, or a sequence of cfg ints, one per video (see video_groups).
-    q_prescaled: q carries sm_scale * log2(e) (see qkv_from_projections(q_scale=...)); GPU only."""
+    q_prescaled: q carries sm_scale * log2(e) (see qkv_from_projections(q_scale=...)); GPU only.
+    return_lse: (out, lse), the softmax state of every row as _native.band_attention returns it; out_dtype=torch.float32: fp32 rows.  GPU,
+    head_dim 128, plain q (ValueError), not under svg.distributed (NotImplementedError)."""
     S = q.shape[2]
+    kw = _state_kw("dense_attention", return_lse, out_dtype, q_prescaled, TOKEN_MAJOR_IO and not _dist.active())
     lens = per_video(valid_len, q.shape[0], "dense_attention(valid_len)")
     if lens is not None:
         vals, heads = video_groups([int(x) for x in lens], q.shape[1])
         if len(vals) > 1:
-            if q.is_cuda:
-                return _native.band_attention_groups(q, k, v, [_dense_band_mask(S, x) for x in vals], heads, q_prescaled=q_prescaled,
-                                                     token_major_out=TOKEN_MAJOR_IO and not _dist.active())
+            if q.is_cuda or return_lse:
+                return _native.band_attention_groups(q, k, v, [_dense_band_mask(S, x) for x in vals], heads, q_prescaled=q_prescaled, **kw)
             assert not q_prescaled, "a pre-scaled q only exists on the GPU path"
             return torch.cat([_dense_sdpa(q[b:b + 1], k[b:b + 1], v[b:b + 1], x) for b, x in enumerate(lens)])
         valid_len = vals[0]
-    if q.is_cuda:
-        return _native.band_attention(q, k, v, _dense_band_mask(S, valid_len), q_prescaled=q_prescaled, token_major_out=TOKEN_MAJOR_IO and not _dist.active())
+    if q.is_cuda or return_lse:   # (return_lse on CPU tensors: refused by the wrapper, never the SDPA call)
+        return _native.band_attention(q, k, v, _dense_band_mask(S, valid_len), q_prescaled=q_prescaled, **kw)
     assert not q_prescaled, "a pre-scaled q only exists on the GPU path"
     return _dense_sdpa(q, k, v, valid_len)
 
@@ -304,12 +323,16 @@ def dense_flag_on_device(timestep, first_times_fp):
 
 def svg1_attention_device_switch(q, k, v, geo: Geometry, mask: "_native.BandMask", dense_mask: "_native.BandMask",
                                  prof: "_native.ProfileDesc", num_sampled_rows: int, sample_max_row: int, dense_flag,
-                                 _local: bool = False, q_prescaled: bool = False):
+                                 _local: bool = False, q_prescaled: bool = False, return_lse: bool = False, out_dtype=None):
     """Dense warm-up step or sparse step, decided on the device: the profiler and the attention kernel read
     `dense_flag`; on a dense step the profiler returns at once and the kernel runs `dense_mask` without the head placement.
     Same attention results as the host-side branch of attention_core_logic (ref: hyvideo/attention.py:491-524) for the same sampled
     rows; the rows come from a dedicated CPU generator (`_switch_generator`).  The returned best_mask_idx is -1 on a dense step.
-    mask, dense_mask: one BandMask for the batch, or a sequence of cfg of them, one per video (see video_groups)."""
+    mask, dense_mask: one BandMask for the batch, or a sequence of cfg of them, one per video (see video_groups).
+    return_lse: (out, best_mask_idx, lse) with the softmax state of every row under the mask the flag selects, as
+    _native.band_attention_switch returns it — the layer-call as one part of a partitioned attention (merge_attention_states);
+    out_dtype=torch.float32: fp32 rows.  Plain q only (ValueError), not under svg.distributed (NotImplementedError)."""
+    kw = _state_kw("svg1_attention_device_switch", return_lse, out_dtype, q_prescaled, TOKEN_MAJOR_IO)
     _require_gpu(q, "SVG1 attention")
     cfg, H = q.shape[0], q.shape[1]
     pm, pd = per_video(mask, cfg, "svg1_attention_device_switch(mask)"), per_video(dense_mask, cfg, "svg1_attention_device_switch(dense_mask)")
@@ -330,23 +353,29 @@ def svg1_attention_device_switch(q, k, v, geo: Geometry, mask: "_native.BandMask
     if groups is not None:
         out = _native.band_attention_groups(q, k, v, groups[0], groups[2], alt_masks=groups[1], use_alt_flag=dense_flag,
                                             head_perm_flag=best_mask_idx, vid0=geo.vid0, num_frame=geo.num_frame,
-                                            frame_size=geo.frame_size, q_prescaled=q_prescaled, token_major_out=TOKEN_MAJOR_IO)
+                                            frame_size=geo.frame_size, q_prescaled=q_prescaled, **kw)
     else:
+        if _local:
+            kw["token_major_out"] = False
         out = _native.band_attention_switch(q, k, v, mask, dense_mask, dense_flag, head_perm_flag=best_mask_idx, vid0=geo.vid0,
-                                            num_frame=geo.num_frame, frame_size=geo.frame_size, q_prescaled=q_prescaled,
-                                            token_major_out=TOKEN_MAJOR_IO and not _local)
-    return out, torch.where(dense_flag.reshape(()) != 0, torch.full_like(best_mask_idx, -1), best_mask_idx)
+                                            num_frame=geo.num_frame, frame_size=geo.frame_size, q_prescaled=q_prescaled, **kw)
+    best = torch.where(dense_flag.reshape(()) != 0, torch.full_like(best_mask_idx, -1), best_mask_idx)
+    return (out[0], best, out[1]) if return_lse else (out, best)
 
 
 def svg1_sparse_attention(q, k, v, geo: Geometry, mask: "_native.BandMask", prof: "_native.ProfileDesc",
                           num_sampled_rows: int, sample_max_row: int, fused: bool = True, _local: bool = False,
-                          q_prescaled: bool = False):
+                          q_prescaled: bool = False, return_lse: bool = False, out_dtype=None):
     """The sparse branch of attention_core_logic (ref: hyvideo/attention.py:507-524):
     online profiling -> best_mask_idx -> placement -> block-sparse attention -> inverse placement.
     fused=True folds both placements into the attention kernel (bit-identical result, ~5.9 GB less HBM traffic at
     Hunyuan 720p); fused=False runs the three kernels of the reference pipeline.
     mask: one BandMask for the batch, or a sequence of cfg of them, one per video (see video_groups); the profiler's masks do not depend
-    on the prompt length, so the profiling pass is the same either way."""
+    on the prompt length, so the profiling pass is the same either way.
+    return_lse: (out, best_mask_idx, lse) with the softmax state of every row, as _native.band_attention returns it;
+    out_dtype=torch.float32: fp32 rows.  The fused 16-bit path with a plain q only (ValueError), not under svg.distributed
+    (NotImplementedError)."""
+    kw = _state_kw("svg1_sparse_attention", return_lse, out_dtype, q_prescaled, TOKEN_MAJOR_IO, fp8=_use_fp8(q), fused=fused)
     _require_gpu(q, "SVG1 sparse attention")
     groups = None
     pm = per_video(mask, q.shape[0], "svg1_sparse_attention(mask)")
@@ -368,12 +397,14 @@ def svg1_sparse_attention(q, k, v, geo: Geometry, mask: "_native.BandMask", prof
             if groups is not None:
                 if _use_fp8(q):
                     raise NotImplementedError("SVG1 sparse attention: fp8 attention with per-video lengths that differ is not implemented")
-                out = _native.band_attention_groups(q, k, v, groups[0], groups[1], q_prescaled=q_prescaled, token_major_out=TOKEN_MAJOR_IO, **pk)
+                out = _native.band_attention_groups(q, k, v, groups[0], groups[1], q_prescaled=q_prescaled, **kw, **pk)
             elif _use_fp8(q):   # (the fp8 pre-pass folds whatever scale it is given into its quantisation of q)
                 out = _native.band_attention_fp8(q.contiguous(), k.contiguous(), v.contiguous(), mask, sm_scale=LN2 if q_prescaled else None, **pk)
             else:
-                out = _native.band_attention(q, k, v, mask, q_prescaled=q_prescaled, token_major_out=TOKEN_MAJOR_IO and not _local, **pk)
-        return out, best_mask_idx
+                if _local:
+                    kw["token_major_out"] = False
+                out = _native.band_attention(q, k, v, mask, q_prescaled=q_prescaled, **kw, **pk)
+        return (out[0], best_mask_idx, out[1]) if return_lse else (out, best_mask_idx)
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     qo, ko, vo = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
     with time_logging_decorator("Level 3 - fast_sparse_head_placement"):
