@@ -776,4 +776,6 @@ int svg_debug_wg_trace(uint64_t* out, int32_t n_workgroups);
 #include "svg_attn_f32_parts.h"
 /* ... and the LSE / fp32 forms of the device-switch and groups launches of band attention, likewise */
 #include "svg_attn_band_lse_forms.h"
+/* ... and band attention over a row window and a key window of the mask (token-sharded and key-partitioned callers), likewise */
+#include "svg_attn_band_window.h"
 #endif /* SVG_ATTN_H_ */

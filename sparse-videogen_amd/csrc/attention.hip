@@ -1,7 +1,8 @@
 // SVG1 band (block-sparse) and dense attention for gfx950: the kernels that run the bodies of attn_core.h / attn_m16.h on the band
 // policy (band_policy.h), the counter pool of the queue launches, the svg_band_attention* entries, the completion-counter waiters and
 // the svg_debug_* trace readers; svg_band_attention_lse (row log-sum-exp output) and svg_band_attention_lse_f32 (fp32 rows) and their
-// device-switch and groups forms (include/svg_attn_band_lse_forms.h).  (One-wave-per-SIMD body: attention_w4.hip; fp8:
+// device-switch and groups forms (include/svg_attn_band_lse_forms.h); their window forms svg_band_window_attention_lse[_f32]
+// (include/svg_attn_band_window.h).  (One-wave-per-SIMD body: attention_w4.hip; fp8:
 // attention_f8.hip; SVG2: attention_varblock.hip.)
 #include <algorithm>
 #include <atomic>
@@ -91,6 +92,20 @@ template <typename T>
 __global__ __launch_bounds__(512, 2) void band_attn_f32_m16_kernel(typename BandF32Policy<T>::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     attn_body_m16<T, BandF32Policy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
+}
+// Window forms (svg_band_window_attention_lse[_f32]): the two kernels above on BandWindowLsePolicy / BandWindowF32Policy (band_policy.h) —
+// a row window of q / o / lse and a key window of k / v under the mask at its global coordinates; the same template arguments, SPEC and
+// the replay counter included, so a window that is the whole sequence keeps the siblings' bits.  Static mapping over the q-tiles of the
+// row window.  (Their own kernel templates: the other kernels keep their symbols and their listings.)
+template <typename T>
+__global__ __launch_bounds__(512, 2) void band_window_lse_m16_kernel(typename BandWindowLsePolicy<T>::Params prm) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    attn_body_m16<T, BandWindowLsePolicy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
+}
+template <typename T>
+__global__ __launch_bounds__(512, 2) void band_window_f32_m16_kernel(typename BandWindowF32Policy<T>::Params prm) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    attn_body_m16<T, BandWindowF32Policy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
 }
 // pre-scaled q on the 16x16x32 body (PRE form of attn_body_m16)
 template <typename T>
@@ -346,13 +361,18 @@ int32_t* svg::band_queue_block(hipStream_t st, int& n_cu) {
 
 int svg::band_queue_cap() { return g_queue_cap.load(std::memory_order_relaxed); }
 
+// the sizes a band launch can address (SVG_ERR_UNSUPPORTED beyond them)
+static int band_check_size(int32_t BH, int32_t S, int32_t D) {
+    if ((int64_t)BH * S * D >= (1ll << 40)) return SVG_ERR_UNSUPPORTED;
+    return check_rows(S, D);
+}
+
 // pointers, mask, head permutation and sizes: the checks every svg_band_attention* entry shares
 static int band_check_args(const void* q, const void* k, const void* v, const void* o, int32_t BH, int32_t S, int32_t D,
                            const svg_band_mask_t* mask, const svg_perm_desc_t* perm) {
     if (!q || !k || !v || !o || !mask || BH <= 0 || S <= 0) return SVG_ERR_BAD_ARG;
     if (const int rc = check_band_mask(S, mask, perm); rc != SVG_OK) return rc;
-    if ((int64_t)BH * S * D >= (1ll << 40)) return SVG_ERR_UNSUPPORTED;
-    return check_rows(S, D);
+    return band_check_size(BH, S, D);
 }
 
 // The 16x16x32 kernels of a single-mask launch: resident workgroups on a work queue (kern_q), or `kern` on the static mapping where the
@@ -542,6 +562,63 @@ extern "C" int svg_band_attention_lse_f32(const void* q, const void* k, const vo
     if (layout) abi = *layout, abi.o = abi.q;
     return band_dispatch(q, k, v, layout ? const_cast<void*>(q) : (void*)o32, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, 0,
                          layout ? &abi : nullptr, stream);
+}
+
+// The window entries (include/svg_attn_band_window.h): a sibling of band_dispatch for the LSE / fp32 forms over a row window and a key
+// window — its checks in its order (check_band_mask and the size limits against S, the layout against the windows), then the window
+// kernels on the static mapping.  `o32` (or nullptr) stands in for o as in svg_band_attention_lse_f32.
+static int band_window_dispatch(const void* q, const void* k, const void* v, void* o, float* o32, float* lse, int32_t BH, int32_t S,
+                                int32_t q_begin, int32_t Sq, int32_t k_begin, int32_t Sk, int32_t D, int32_t dtype, float sm_scale,
+                                const svg_band_mask_t* mask, const svg_attn_layout_t* layout, void* stream) {
+    if (!q || !k || !v || !(o32 ? (void*)o32 : o) || !lse || !mask) return SVG_ERR_BAD_ARG;
+    if (BH <= 0 || S <= 0 || Sq <= 0 || Sk <= 0 || q_begin < 0 || k_begin < 0 || (int64_t)q_begin + Sq > S || (int64_t)k_begin + Sk > S)
+        return SVG_ERR_BAD_ARG;
+    int rc = check_band_mask(S, mask, nullptr);
+    if (rc != SVG_OK) return rc;
+    BandOpts opts;
+    opts.lse = lse, opts.o32 = o32;
+    opts.strided = layout != nullptr;
+    if (layout) {   // (of a layout the o member is not read by the fp32 form: it takes q's strides)
+        svg_attn_layout_t abi = *layout;
+        if (o32) abi.o = abi.q;
+        if ((rc = layout_from_abi(&abi, BH, BH, Sq, Sk, D, q, k, v, o32 ? q : o, opts.lay)) != SVG_OK) return rc;
+    }
+    if (D != 128 || k_begin % kBN != 0) return SVG_ERR_UNSUPPORTED;   // key tiles stay aligned to the mask's coordinates
+    if ((rc = band_check_size(BH, S, D)) != SVG_OK) return rc;
+    if (o32 && ((size_t)o32 & 15) != 0) return SVG_ERR_UNSUPPORTED;   // 16-byte stores
+    const hipStream_t st = (hipStream_t)stream;
+    return dispatch_td(dtype, D, [&](auto t, auto d) -> int {
+        using T = decltype(t);
+        if constexpr (decltype(d)::value != 128) {
+            return SVG_ERR_UNSUPPORTED;
+        } else {
+            const int lds = attn_m16_lds_bytes() + kTailLds;
+            if (o32) {
+                using Pol = BandWindowF32Policy<T>;
+                typename Pol::Params p = make_band_window_params<Pol, T>(q, k, v, nullptr, BH, S, q_begin, Sq, k_begin, Sk, sm_scale, mask, opts);
+                p.o32 = o32;
+                return launch_attn(band_window_f32_m16_kernel<T>, dim3(p.nqt * BH), 512, lds, st, p);
+            }
+            using Pol = BandWindowLsePolicy<T>;
+            const typename Pol::Params p = make_band_window_params<Pol, T>(q, k, v, o, BH, S, q_begin, Sq, k_begin, Sk, sm_scale, mask, opts);
+            return launch_attn(band_window_lse_m16_kernel<T>, dim3(p.nqt * BH), 512, lds, st, p);
+        }
+    });
+}
+
+extern "C" int svg_band_window_attention_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S,
+                                             int32_t q_begin, int32_t Sq, int32_t k_begin, int32_t Sk, int32_t D, int32_t dtype,
+                                             float sm_scale, const svg_band_mask_t* mask, const svg_attn_layout_t* layout, void* stream) {
+    if (!o) return SVG_ERR_BAD_ARG;
+    return band_window_dispatch(q, k, v, o, nullptr, lse, BH, S, q_begin, Sq, k_begin, Sk, D, dtype, sm_scale, mask, layout, stream);
+}
+
+extern "C" int svg_band_window_attention_lse_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t BH, int32_t S,
+                                                 int32_t q_begin, int32_t Sq, int32_t k_begin, int32_t Sk, int32_t D, int32_t dtype,
+                                                 float sm_scale, const svg_band_mask_t* mask, const svg_attn_layout_t* layout,
+                                                 void* stream) {
+    if (!o32) return SVG_ERR_BAD_ARG;
+    return band_window_dispatch(q, k, v, nullptr, o32, lse, BH, S, q_begin, Sq, k_begin, Sk, D, dtype, sm_scale, mask, layout, stream);
 }
 
 // (head_dim 128: the PRE form of the 16x16x32 body — 33.0 - 33.3 ms against 33.6 - 34.2 for the 32x32x16 one, same box, profiles/r04k_ab_m16_prescaled.txt)

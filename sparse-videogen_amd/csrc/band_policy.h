@@ -507,6 +507,93 @@ struct BandF32Policy : BandLsePolicy<T> {
     }
 };
 
+// Window forms (svg_band_window_attention_lse[_f32], include/svg_attn_band_window.h): the LSE / fp32 policy over a ROW window and a KEY
+// window of the mask — q / o / lse / o32 hold the rows [q_begin, q_begin + Sq), k / v the keys [k_begin, k_end) of a sequence of S rows, and
+// the mask is evaluated at the global coordinates.  A window is a clip, not a new mask:
+//   rows     the host intersects the row regions with the row window (make_band_window_params), so q0 / q_end, the mask intervals and the
+//            per-wave fast-path interval stay global; q_phys — the row q is read from and o / lse / o32 are written to — subtracts q_begin.
+//   keys     the key-tile segments of kv_schedule are clipped to the tiles of the key window (k_begin is a multiple of kBN: tiles stay
+//            aligned to the mask's coordinates, so no tile starts in front of the window); wherever S bounds the keys — the partial last
+//            tile (classify, row_intervals), the redirect of rows behind the sequence (row_exact), the cheap step of the row cursor and
+//            fk_hi — k_end does.  A key behind the window is masked, and its row is never read: the redirect goes to the window's first row.
+//            The row the cursor holds is relative to k_begin.
+// The element predicate allowed() is NOT clipped: the 16x16x32 body, the only one these policies are built for, masks through
+// row_intervals (kIntervalMask).
+// No head permutation (the kernels are launched without one).  With the whole sequence as both windows every value above is the one the
+// base policy computes, so the kernels keep the bits of their siblings.
+template <typename BasePol>
+struct BandWindowOf : BasePol {
+    using Ctx = typename BasePol::Ctx;
+    using RowWalk = typename BasePol::RowWalk;
+    struct Params : BasePol::Params {
+        int q_begin, Sq;       // row window [q_begin, q_begin + Sq): what q / o / lse / o32 hold
+        int k_begin, k_end;    // key window [k_begin, k_end): what k / v hold; k_begin % kBN == 0
+    };
+    static __host__ __device__ __forceinline__ void clip_keys(const Params& p, Ctx& c) {
+        using std::max;
+        using std::min;
+        const int t_lo = p.k_begin / kBN, t_hi = (p.k_end + kBN - 1) / kBN;
+        // (written out per segment: a loop index into the arrays of Ctx could send them through scratch)
+#define SVG_CLIP_SEG(i)                                                                  \
+    {                                                                                    \
+        const int lo = max(c.seg_lo[i], t_lo), hi = min(c.seg_lo[i] + c.seg_n[i], t_hi); \
+        c.seg_lo[i] = lo, c.seg_n[i] = max(hi - lo, 0);                                  \
+    }
+        SVG_CLIP_SEG(0) SVG_CLIP_SEG(1) SVG_CLIP_SEG(2)
+#undef SVG_CLIP_SEG
+        c.nT = c.seg_n[0] + c.seg_n[1] + c.seg_n[2];
+    }
+    static __host__ __device__ __forceinline__ void kv_schedule(const Params& p, Ctx& c, int qt) {
+        BasePol::kv_schedule(p, c, qt);
+        clip_keys(p, c);
+    }
+    static __device__ __forceinline__ void init_tile(const Params& p, Ctx& c, int head, int qt) {
+        BasePol::init_tile(p, c, head, qt);
+        clip_keys(p, c);
+        c.fk_hi = min(c.fk_hi, p.k_end - kBN);
+    }
+    static __device__ __forceinline__ bool init(const Params& p, Ctx& c, char* lds) {
+        if (!BasePol::init(p, c, lds)) return false;
+        clip_keys(p, c);
+        c.fk_hi = min(c.fk_hi, p.k_end - kBN);
+        return true;
+    }
+    static __device__ __forceinline__ int q_phys(const Params& p, const Ctx& c, int row) {
+        const int l = c.q0 + row;
+        return l < c.q_end ? l - p.q_begin : -1;
+    }
+    static __host__ __device__ __forceinline__ void row_walk_init(const Params& p, const Ctx& c, RowWalk& w) {
+        BasePol::row_walk_init(p, c, w);
+        w.hi = p.k_end - kBN;
+    }
+    static __host__ __device__ __forceinline__ int row_exact(const Params& p, int l) { return l < p.k_end ? l - p.k_begin : 0; }
+    static __host__ __device__ __forceinline__ void row_walk_next(const Params& p, RowWalk& w, int& phys, int k0, int row) {
+        const bool cheap = BasePol::row_walk_cheap(w, k0);
+        BasePol::row_add(phys, w.step);
+        if (__builtin_expect(!cheap, 0)) BasePol::row_set(phys, row_exact(p, k0 + row));
+    }
+    static __device__ __forceinline__ int classify(const Params& p, const Ctx& c, int k0, int wrow0) {
+        const int cls = BasePol::classify(p, c, k0, wrow0);
+        return (cls == TILE_FULL && k0 + kBN > p.k_end) ? TILE_PARTIAL : cls;   // (never through the fast-path interval: fk_hi is clipped)
+    }
+    static __device__ __forceinline__ void row_intervals(const Params& p, const Ctx& c, int q, int& a0, unsigned& alen, int& b0,
+                                                         unsigned& blen) {
+        BasePol::row_intervals(p, c, q, a0, alen, b0, blen);
+        alen = (unsigned)max(min(a0 + (int)alen, p.k_end) - a0, 0);
+        blen = (unsigned)max(min(b0 + (int)blen, p.k_end) - b0, 0);
+    }
+    static __device__ __forceinline__ float* lse_base(const Params& p, const Ctx& c) { return p.lse + (size_t)c.head * (size_t)p.Sq; }
+};
+template <typename T>
+using BandWindowLsePolicy = BandWindowOf<BandLsePolicy<T>>;
+template <typename T>
+struct BandWindowF32Policy : BandWindowOf<BandF32Policy<T>> {
+    using Base = BandWindowOf<BandF32Policy<T>>;
+    static __device__ __forceinline__ float* o32_base(const typename Base::Params& p, const typename Base::Ctx& c) {
+        return p.o32 + (size_t)c.head * (size_t)p.Sq * 128;
+    }
+};
+
 // =====================================================================================================
 // Work queue of the resident band kernels (band_attn_m16_queue_kernel in attention.hip): min(work items, CUs) workgroups, each
 // taking (head, q-tile) pairs until the queue is dry, instead of one workgroup per pair bound to an XCD by its dispatch id.
@@ -656,6 +743,38 @@ int32_t* band_queue_block(hipStream_t st, int& n_cu);   // n_cu: compute units o
 // diagnostics (svg_debug_band_queue_cap): at most this many resident workgroups per queue launch; 0 = as many as the device has CUs
 int band_queue_cap();
 
+// Row regions of a launch (see BandPolicy::Params): the rows [row_lo, row_hi) of a sequence of S rows — the whole sequence, or the row
+// window of a window launch — cut at rowfull_lo, rowfull_hi (inside [0, real_len)) and real_len; unused slots are empty regions behind
+// the last tile.  A q-tile of full rows visits every key tile on the unmasked fast path (with the text rows sharing a tile with band rows
+// or rows behind real_len, all 1861 tiles of it took the per-element masked path: 9.5 ms instead of 3.2).  Also nqt, the heavy q-tiles
+// and the segments of the completion counters.
+template <typename Pol>
+inline void band_row_regions(typename Pol::Params& p, int S, int row_lo, int row_hi, int done_nseg) {
+    const int real = std::min(std::max(p.real_len, 0), S);
+    const bool has_rf = p.rf_hi > p.rf_lo && p.rf_lo < real && p.band <= S;
+    const int a = has_rf ? std::max(p.rf_lo, 0) : 0, b = has_rf ? std::min(p.rf_hi, real) : 0;
+    auto clip = [&](int x) { return std::min(std::max(x, row_lo), row_hi); };
+    const int cuts[5] = {clip(0), clip(a), clip(b), clip(real), clip(S)};
+    int nreg = 0, t0 = 0, heavy_reg = -1;
+    for (int i = 0; i < 4; ++i) {
+        if (cuts[i + 1] <= cuts[i]) continue;
+        p.reg_lo[nreg] = cuts[i], p.reg_hi[nreg] = cuts[i + 1], p.reg_t0[nreg] = t0;
+        if (has_rf && i == 1) heavy_reg = nreg;
+        t0 += (cuts[i + 1] - cuts[i] + Pol::BM - 1) / Pol::BM;
+        ++nreg;
+    }
+    p.nqt = t0;
+    p.done_nseg = std::max(1, std::min(done_nseg, t0));
+    p.done_tps = (t0 + p.done_nseg - 1) / p.done_nseg;
+    for (int i = nreg; i < 4; ++i) p.reg_lo[i] = S, p.reg_hi[i] = S, p.reg_t0[i] = 1 << 30;
+    p.heavy_lo = 0, p.n_heavy = 0;
+    if (heavy_reg >= 0) {
+        p.heavy_lo = p.reg_t0[heavy_reg];
+        p.n_heavy = (heavy_reg + 1 < nreg ? p.reg_t0[heavy_reg + 1] : p.nqt) - p.heavy_lo;
+        if (p.n_heavy >= p.nqt) p.heavy_lo = 0, p.n_heavy = 0;
+    }
+}
+
 template <typename Pol, typename T>
 inline typename Pol::Params make_band_params(const void* q, const void* k, const void* v, void* o, int BH, int S, float sm_scale,
                                              const svg_band_mask_t* mask, const svg_perm_desc_t* perm, const BandOpts& opts = BandOpts()) {
@@ -676,33 +795,22 @@ inline typename Pol::Params make_band_params(const void* q, const void* k, const
     p.q128 = 2 * kBN / p.F, p.r128 = 2 * kBN % p.F;
     p.sp64 = p.q64 + p.r64 * p.P, p.sp128 = p.q128 + p.r128 * p.P;
     p.wrap_phys = 1 - p.F * p.P;
-    // row regions (see Params): cut at rowfull_lo, rowfull_hi (inside [0, real_len)) and real_len; unused slots are empty regions
-    // behind the last tile.  A q-tile of full rows visits every key tile on the unmasked fast path (with the text rows sharing a
-    // tile with band rows or rows behind real_len, all 1861 tiles of it took the per-element masked path: 9.5 ms instead of 3.2).
-    {
-        const int real = std::min(std::max(p.real_len, 0), S);
-        const bool has_rf = p.rf_hi > p.rf_lo && p.rf_lo < real && p.band <= S;
-        const int a = has_rf ? std::max(p.rf_lo, 0) : 0, b = has_rf ? std::min(p.rf_hi, real) : 0;
-        const int cuts[5] = {0, a, b, real, S};
-        int nreg = 0, t0 = 0, heavy_reg = -1;
-        for (int i = 0; i < 4; ++i) {
-            if (cuts[i + 1] <= cuts[i]) continue;
-            p.reg_lo[nreg] = cuts[i], p.reg_hi[nreg] = cuts[i + 1], p.reg_t0[nreg] = t0;
-            if (has_rf && i == 1) heavy_reg = nreg;
-            t0 += (cuts[i + 1] - cuts[i] + Pol::BM - 1) / Pol::BM;
-            ++nreg;
-        }
-        p.nqt = t0;
-        p.done_nseg = std::max(1, std::min(opts.done_nseg, t0));
-        p.done_tps = (t0 + p.done_nseg - 1) / p.done_nseg;
-        for (int i = nreg; i < 4; ++i) p.reg_lo[i] = S, p.reg_hi[i] = S, p.reg_t0[i] = 1 << 30;
-        p.heavy_lo = 0, p.n_heavy = 0;
-        if (heavy_reg >= 0) {
-            p.heavy_lo = p.reg_t0[heavy_reg];
-            p.n_heavy = (heavy_reg + 1 < nreg ? p.reg_t0[heavy_reg + 1] : p.nqt) - p.heavy_lo;
-            if (p.n_heavy >= p.nqt) p.heavy_lo = 0, p.n_heavy = 0;
-        }
-    }
+    band_row_regions<Pol>(p, S, 0, S, opts.done_nseg);
+    return p;
+}
+
+// parameters of a window launch (BandWindowOf): those of the sequence of S rows, the row regions intersected with the row window — heavy_lo,
+// n_heavy and nqt follow the clipped regions — and the tensors as [BH, Sq | Sk, D] (or `opts.lay`); lse (and o32) from opts
+template <typename Pol, typename T>
+inline typename Pol::Params make_band_window_params(const void* q, const void* k, const void* v, void* o, int BH, int S, int q_begin, int Sq,
+                                                    int k_begin, int Sk, float sm_scale, const svg_band_mask_t* mask, const BandOpts& opts) {
+    typename Pol::Params p;
+    static_cast<typename BandPolicy<T, 128, 8>::Params&>(p) =
+        make_band_params<BandPolicy<T, 128, 8>, T>(q, k, v, o, BH, S, sm_scale, mask, nullptr, opts);
+    if (!opts.strided) p.lay = contiguous_layout(BH, BH, Sq, Sk, Pol::kHeadDim);
+    p.q_begin = q_begin, p.Sq = Sq, p.k_begin = k_begin, p.k_end = k_begin + Sk;
+    band_row_regions<Pol>(p, S, q_begin, q_begin + Sq, 1);
+    p.lse = opts.lse;
     return p;
 }
 

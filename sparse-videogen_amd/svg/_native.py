@@ -240,6 +240,15 @@ BAND_LSE_FORM_SIGNATURES["svg_band_attention_switch_lse_f32"] = BAND_LSE_FORM_SI
 BAND_LSE_FORM_SIGNATURES["svg_band_groups_attention_lse_f32"] = BAND_LSE_FORM_SIGNATURES["svg_band_groups_attention_lse"]
 
 
+# include/svg_attn_band_window.h: band attention over a row window and a key window of the mask, in a table of its own for the same reason
+# (tests/test_band_window_cpu.py)
+BAND_WINDOW_SIGNATURES = {
+    "svg_band_window_attention_lse": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F32,
+                                                C.POINTER(BandMask), C.POINTER(AttnLayout), _VP]),
+}
+BAND_WINDOW_SIGNATURES["svg_band_window_attention_lse_f32"] = BAND_WINDOW_SIGNATURES["svg_band_window_attention_lse"]
+
+
 def lib_path() -> Path:
     return Path(os.environ.get("SVG_ATTN_LIB", str(_LIB_PATH)))
 
@@ -252,7 +261,8 @@ def load(strict: bool = True) -> Optional[C.CDLL]:
     p = lib_path()
     try:
         lib = C.CDLL(str(p))
-        for name, (res, args) in {**SIGNATURES, **SPARSE_LSE_SIGNATURES, **SPARSE_F32_SIGNATURES, **BAND_LSE_FORM_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **SPARSE_LSE_SIGNATURES, **SPARSE_F32_SIGNATURES, **BAND_LSE_FORM_SIGNATURES,
+                                   **BAND_WINDOW_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -846,6 +856,102 @@ def band_attention_groups(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
         out.copy_(o)
         return out
     return o
+
+
+def band_window_has_keys(mask: BandMask, num_tokens: int, q_range, k_range) -> bool:
+    """Does the band mask over a sequence of num_tokens rows allow ANY (row, key) pair of the rectangle rows [q0, q1) x keys [k0, k1)?
+    Host only, closed form (no element is enumerated): the predicate of svg_band_mask_t (include/svg_attn.h) on intervals — what
+    svg.distributed.band_exchange_plan asks for every pair of shards."""
+    real, band, cf_lo, cf_hi, rf_lo, rf_hi = mask.as_tuple()
+    S = int(num_tokens)
+    q0, q1 = max(int(q_range[0]), 0), min(int(q_range[1]), S)
+    k0, k1 = max(int(k_range[0]), 0), min(int(k_range[1]), S)
+    if q1 <= q0 or k1 <= k0:
+        return False
+    real = min(max(real, 0), S)
+    qa, qb, ka, kb = q0, min(q1, real), k0, min(k1, real)      # the real rows and the real keys of the rectangle
+    if qb > qa and kb > ka:
+        if band > 0 and ka - (qb - 1) < band and qa - (kb - 1) < band:   # the closest pair of the two intervals lies inside the band
+            return True
+        if min(kb, cf_hi) > max(ka, cf_lo) or min(qb, rf_hi) > max(qa, rf_lo):   # a full column / a full row
+            return True
+    return q1 > max(q0, real) and k1 > max(k0, real)           # rows behind real_len see the keys behind real_len
+
+
+def band_window_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: BandMask, num_tokens: int, q_begin: int, k_begin: int,
+                          out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None):
+    """Band attention of a ROW window over a KEY window of the mask (svg_band_window_attention_lse[_f32]) -> (o, lse): q [cfg, H, Sq, D]
+    (or [BH, Sq, D]) holds the rows [q_begin, q_begin + Sq), k / v [cfg, H, Sk, D] the rows [k_begin, k_begin + Sk) of a sequence of
+    num_tokens rows, in the LOGICAL order of the mask; row i sees key j where the mask allows (q_begin + i, k_begin + j).  o has q's shape
+    and dtype, lse is contiguous fp32 of shape q.shape[:-1] (natural log; a row that sees no key of the window: o = 0, lse = -inf) — parts
+    for merge_attention_states: the parts of one row window over disjoint key windows covering the sequence merge to band_attention's
+    result.  Views (stride(-1) == 1) are read in place; what the layout cannot describe is copied.
+    out_dtype=torch.float32 (without out): (o32, lse), the rows before their rounding, contiguous fp32.
+    Sq == 0 or Sk == 0 is answered without a launch.  head_dim 128, bf16 / fp16, GPU tensors, k_begin a multiple of 64: anything else
+    raises before anything runs — there is no fall-back and no head permutation (token-major heads need their placement first)."""
+    if out_dtype not in (None, torch.float32):
+        raise ValueError(f"band_window_attention: out_dtype is None (q's dtype) or torch.float32, got {out_dtype}")
+    f32 = out_dtype == torch.float32
+    if f32 and out is not None:
+        raise ValueError("band_window_attention(out_dtype=torch.float32): fp32 rows are parts for merge_attention_states, without out")
+    _gpu(q, k, v, out)
+    if not (q.dim() == k.dim() == v.dim() and q.dim() in (3, 4) and k.shape == v.shape and q.shape[:-2] == k.shape[:-2]
+            and q.shape[-1] == k.shape[-1] and q.dtype == k.dtype == v.dtype):
+        raise ValueError(f"band_window_attention: q [.., Sq, D], k / v [.., Sk, D] of one dtype, got {tuple(q.shape)}, {tuple(k.shape)}, "
+                         f"{tuple(v.shape)}")
+    Sq, Sk, D = q.shape[-2], k.shape[-2], q.shape[-1]
+    S, q_begin, k_begin = int(num_tokens), int(q_begin), int(k_begin)
+    if D != 128 or q.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"band_window_attention: head_dim 128, bfloat16 / float16; got D = {D}, {q.dtype} (no window form, no fall-back)")
+    if k_begin % 64 != 0:
+        raise ValueError(f"band_window_attention: k_begin must be a multiple of 64 (key tiles stay aligned to the mask), got {k_begin}")
+    if q_begin < 0 or k_begin < 0 or q_begin + Sq > S or k_begin + Sk > S:
+        raise ValueError(f"band_window_attention: rows [{q_begin}, {q_begin + Sq}) / keys [{k_begin}, {k_begin + Sk}) outside [0, {S})")
+    if out is not None and (out.shape != q.shape or out.dtype != q.dtype):
+        raise ValueError(f"band_window_attention: out must have q's shape and dtype, got {tuple(out.shape)} {out.dtype}")
+    lse = torch.empty(q.shape[:-1], dtype=torch.float32, device=q.device)
+    if Sq == 0 or Sk == 0:   # no row, or no key: nothing to launch
+        o = out if out is not None else torch.empty(q.shape, dtype=torch.float32 if f32 else q.dtype, device=q.device)
+        o.zero_()
+        lse.fill_(float("-inf"))
+        return o, lse
+    lib = load()
+    BH = q.numel() // (Sq * D)
+    geom = (BH, S, q_begin, Sq, k_begin, Sk, D, _dtype_code(q), _sm_scale(None, D), C.byref(mask))
+    if f32:
+        o32 = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+
+        def call32(q, k, v, lay):
+            return lib.svg_band_window_attention_lse_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), o32.data_ptr(), lse.data_ptr(), *geom, lay,
+                                                         _stream())
+
+        if q.is_contiguous() and k.is_contiguous() and v.is_contiguous():
+            _check(call32(q, k, v, None), "svg_band_window_attention_lse_f32")
+        elif not _window_views(q, k, v, q, "svg_band_window_attention_lse_f32", lambda lay: call32(q, k, v, C.byref(lay))):
+            _check(call32(q.contiguous(), k.contiguous(), v.contiguous(), None), "svg_band_window_attention_lse_f32")
+        return o32, lse
+
+    def run(q, k, v, out):
+        o = torch.empty_like(q, memory_format=torch.contiguous_format) if out is None else out
+        if q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and o.is_contiguous():
+            _check(lib.svg_band_window_attention_lse(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), *geom, None,
+                                                     _stream()), "svg_band_window_attention_lse")
+            return o
+        ok = _window_views(q, k, v, o, "svg_band_window_attention_lse", lambda lay: lib.svg_band_window_attention_lse(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), *geom, C.byref(lay), _stream()))
+        return o if ok else None
+
+    return _run_or_copy(run, (q, k, v), out), lse
+
+
+def _window_views(q, k, v, o, name: str, call) -> bool:
+    """a window entry on [B, H, S, D] views (q / o with Sq rows, k / v with Sk): call(layout) -> rc, checked; False where the layout
+    cannot describe a view"""
+    q4, k4, v4, o4 = _view4(q), _view4(k), _view4(v), _view4(o)
+    if not (_strided_ok(q4) and _strided_ok(k4, True) and _strided_ok(v4, True) and _strided_ok(o4)):
+        return False
+    _check(call(attn_layout(q4, k4, v4, o4)), name)
+    return True
 
 
 def cross_attention_supported(q: torch.Tensor, k: torch.Tensor) -> bool:

@@ -11,6 +11,8 @@ single-GPU result, which is bitwise because per-head arithmetic does not change.
 Dense attention can also stay TOKEN-sharded (`token_sharded_dense_attention`): every rank keeps all heads of its tokens, sees the
 other ranks' keys shard by shard and merges the partial results with their row log-sum-exp — any head count, every rank busy, the
 exchange of the next shard behind the compute of this one; equal to the single-GPU result to rounding, not bitwise.
+`token_sharded_band_attention` is the same schedule for band (SVG1) attention in logical order: each step is one window of the mask at
+the global coordinates of the two shards, and pairs of shards the mask rules out exchange and compute nothing.
 """
 from __future__ import annotations
 
@@ -344,6 +346,101 @@ def token_sharded_dense_attention(q_local: torch.Tensor, k_local: torch.Tensor, 
             parts[src] = attn_fn(q_local, k_s, v_s, True)
     if S_me == 0:
         return torch.empty_like(q_local)
+    order = sorted(parts)
+    return merge_fn([parts[r][0] for r in order], [parts[r][1] for r in order])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# token-sharded BAND (SVG1) attention: the schedule above with the band mask evaluated at the global coordinates of the two shards
+# (svg_band_window_attention_lse[_f32]) — and only the shards a rank's rows can see travel at all.
+# ---------------------------------------------------------------------------------------------------------------
+def band_exchange_plan(mask, num_tokens: int, world: int, unit: int = 128) -> List[List[bool]]:
+    """plan[r][s]: do the rows of rank r (`token_range(num_tokens, r, world, unit)`) see any key of rank s's shard under the band mask
+    `mask` (_native.BandMask) over num_tokens rows?  Host only, closed form (_native.band_window_has_keys); the same table on every rank.
+    A pair that is False exchanges nothing and computes nothing in token_sharded_band_attention."""
+    from . import _native
+
+    tr = [token_range(num_tokens, r, world, unit) for r in range(world)]
+    return [[_native.band_window_has_keys(mask, num_tokens, tr[r], tr[s]) for s in range(world)] for r in range(world)]
+
+
+def token_sharded_band_attention(q_local: torch.Tensor, k_local: torch.Tensor, v_local: torch.Tensor, num_tokens: int, mask, group=None,
+                                 unit: int = 128, fp32_parts: bool = True, attn_fn: Optional[Callable] = None,
+                                 merge_fn: Optional[Callable] = None) -> torch.Tensor:
+    """Band (SVG1) attention over a sequence that lives token-sharded, in the LOGICAL order of the mask: q_local, k_local, v_local
+    [..., H, S_r, D] are ALL heads of this rank's tokens `token_range(num_tokens, rank, world, unit)` (ragged shards allowed); returns this
+    rank's rows of band attention under `mask` (_native.BandMask over num_tokens rows), [..., H, S_r, D].  Any head count, no rank idle.
+    The overlap schedule of token_sharded_dense_attention: at step j the rank attends over the shard of rank s = (rank - j) mod world —
+    attn_fn(q, k_s, v_s, (q0, q1), (k0, k1)) -> (o, lse) with the two token ranges — while the shard of the next step is in flight; at
+    the end ONE merge_fn(o_parts, lse_parts) over the parts in SOURCE-rank order.  What the mask rules out does not happen: a pair
+    (rank, s) whose window holds no allowed element (band_exchange_plan) sends nothing and computes nothing — every rank still enters
+    the collective of a step, with zero-size splits — and a step in which no pair has keys is skipped by all ranks.
+    attn_fn and merge_fn default to the native calls (_native.band_window_attention, _native.merge_attention_states; fp32_parts: the
+    parts travel to the merge before their rounding, so the result is rounded once); they exist so that the schedule can be tested
+    on gloo without a GPU.  unit must be a multiple of 64 (ValueError): the key windows start on the mask's key tiles.  More ranks than
+    MERGE_MAX_PARTS are refused only when some rank really has more than MERGE_MAX_PARTS non-empty parts (ValueError on every rank).
+    What this does NOT do: there is no head permutation — token-major heads (the frame-major placement of the temporal heads) need their
+    placement first, since a window of such a head is not a window of physical rows — and nothing is wired into the processors or
+    bench_step.py.  Equal to the single-GPU result to rounding, not bit for bit."""
+    if unit <= 0 or unit % 64 != 0:
+        raise ValueError(f"token_sharded_band_attention: unit must be a positive multiple of 64 (key windows start on key tiles), got {unit}")
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    tr = [token_range(num_tokens, r, world, unit) for r in range(world)]
+    n_tok = [b - a for a, b in tr]
+    S_me = n_tok[rank]
+    assert q_local.shape[-2] == S_me and k_local.shape == v_local.shape and k_local.shape[-2] == S_me, (
+        f"rank {rank} holds {q_local.shape[-2]} / {k_local.shape[-2]} tokens, token_range says {S_me}")
+    plan = band_exchange_plan(mask, num_tokens, world, unit)
+    most = max(sum(row) for row in plan)
+    if most > MERGE_MAX_PARTS:
+        raise ValueError(f"token_sharded_band_attention: a rank sees the keys of {most} shards, but merge_attention_states takes at most "
+                         f"{MERGE_MAX_PARTS} parts — use a group of at most {MERGE_MAX_PARTS} ranks")
+    if attn_fn is None:
+        from . import _native
+
+        def attn_fn(q, k, v, q_range, k_range):
+            return _native.band_window_attention(q, k, v, mask, num_tokens, q_range[0], k_range[0],
+                                                 out_dtype=torch.float32 if fp32_parts else None)
+    if merge_fn is None:
+        from . import _native
+
+        def merge_fn(o_parts, lse_parts):
+            return _native.merge_attention_states(o_parts, lse_parts, out_dtype=q_local.dtype if fp32_parts else None)
+    lead = tuple(k_local.shape[:-2])
+    D = k_local.shape[-1]
+    per_tok = 2 * D
+    for x in lead:
+        per_tok *= x
+    kv_shape = lambda n: (2,) + lead + (n, D)   # noqa: E731  (k and v of a shard travel as one message)
+    # the steps in which some rank receives keys, the same list on every rank
+    steps = [j for j in range(1, world) if any(plan[r][(r - j) % world] for r in range(world))]
+    send = torch.stack([k_local, v_local]).contiguous().view(-1) if steps else None
+
+    def shift(j):
+        """this rank's shard to rank + j if that rank sees it, the shard of rank - j if this rank sees it: (source rank, buffer, work)"""
+        dst, src = (rank + j) % world, (rank - j) % world
+        recv = torch.empty(n_tok[src] * per_tok if plan[rank][src] else 0, dtype=send.dtype, device=send.device)
+        ins, outs = [0] * world, [0] * world
+        ins[dst] = send.numel() if plan[dst][rank] else 0
+        outs[src] = recv.numel()
+        work = dist.all_to_all_single(recv, send[:ins[dst]], output_split_sizes=outs, input_split_sizes=ins, group=group, async_op=True)
+        return src, recv, work
+
+    parts = {}
+    if plan[rank][rank]:
+        parts[rank] = attn_fn(q_local, k_local, v_local, tr[rank], tr[rank])
+    nxt = shift(steps[0]) if steps else None
+    for i in range(len(steps)):
+        src, recv, work = nxt
+        work.wait()
+        nxt = shift(steps[i + 1]) if i + 1 < len(steps) else None     # in flight while this step computes
+        if plan[rank][src]:
+            k_s, v_s = recv.view(kv_shape(n_tok[src])).unbind(0)
+            parts[src] = attn_fn(q_local, k_s, v_s, tr[rank], tr[src])
+    if S_me == 0:
+        return torch.empty_like(q_local)
+    if not parts:   # (a mask that gives these rows no key at all)
+        return torch.zeros_like(q_local)
     order = sorted(parts)
     return merge_fn([parts[r][0] for r in order], [parts[r][1] for r in order])
 
