@@ -20,6 +20,46 @@ _load_error: Optional[str] = None
 SVG_DTYPE_BF16, SVG_DTYPE_F16 = 0, 1
 
 
+# ------------------------------------------------------------------------------------------------------
+# the ONE allocation path of the package: every uninitialised tensor (outputs, workspaces, receive buffers) of svg/_native.py,
+# svg/distributed.py, svg/kmeans_utils.py and svg/models/_core.py comes from these two callables — torch's own functions unless
+# poison_allocations(True) swapped them (tests/test_poison_cpu.py walks the sources for calls that go round them)
+# ------------------------------------------------------------------------------------------------------
+POISON_BYTE = 0xFF   # bf16 / fp16 / fp32: a NaN, int32 / int64: -1, uint8: 255
+
+
+def poison_storage(t: torch.Tensor) -> torch.Tensor:
+    """Fill the WHOLE storage behind t with POISON_BYTE (a permuted or sliced view: every byte of what was allocated)."""
+    st = t.untyped_storage()
+    if st.nbytes():
+        torch.zeros(0, dtype=torch.uint8, device=t.device).set_(st).fill_(POISON_BYTE)
+    return t
+
+
+def _poisoned_empty(*args, **kwargs) -> torch.Tensor:
+    return poison_storage(torch.empty(*args, **kwargs))
+
+
+def _poisoned_empty_like(*args, **kwargs) -> torch.Tensor:
+    return poison_storage(torch.empty_like(*args, **kwargs))
+
+
+empty = torch.empty
+empty_like = torch.empty_like
+
+
+def poison_allocations(on: bool) -> None:
+    """on: every allocation of the package is followed by a fill of its storage with POISON_BYTE, so that what a launch leaves unwritten
+    reads as NaN / -1 / 255 instead of what the memory held before (the GPU suite runs this way, tests/poisoned.py).  off (the default):
+    torch.empty / torch.empty_like themselves.  Tensors a caller passes in (out=, workspace=) are never touched."""
+    global empty, empty_like
+    empty, empty_like = (_poisoned_empty, _poisoned_empty_like) if on else (torch.empty, torch.empty_like)
+
+
+def allocations_poisoned() -> bool:
+    return empty is _poisoned_empty
+
+
 class BandMask(C.Structure):
     """svg_band_mask_t"""
 
@@ -363,7 +403,7 @@ def token_major_empty(like4: torch.Tensor) -> torch.Tensor:
     """An uninitialised [B, H, S, D] tensor stored token-major ([B, S, H, D] in memory): `out.transpose(1, 2).flatten(2, 3)` — what
     every processor of the reference does with the attention output before the output projection — is then a view, not a copy."""
     B, H, S, D = like4.shape
-    return torch.empty((B, S, H, D), dtype=like4.dtype, device=like4.device).permute(0, 2, 1, 3)
+    return empty((B, S, H, D), dtype=like4.dtype, device=like4.device).permute(0, 2, 1, 3)
 
 
 def strided_attention_supported(q: torch.Tensor, variant: int = 0) -> bool:
@@ -376,7 +416,7 @@ def _try_strided(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: Optiona
     """Run the *_strided entry point `name` as call(o4, layout) on [B, H, S, D] views of q, k, v and of the output (`out`, or a new
     tensor, token-major when asked) and return the output; None when the views cannot be read / written in place."""
     q4, k4, v4 = _view4(q), _view4(k), _view4(v)
-    o4 = _view4(out) if out is not None else (token_major_empty(q4) if token_major_out else torch.empty(q4.shape, dtype=q.dtype, device=q.device))
+    o4 = _view4(out) if out is not None else (token_major_empty(q4) if token_major_out else empty(q4.shape, dtype=q.dtype, device=q.device))
     if not (_strided_ok(q4) and _strided_ok(k4, True) and _strided_ok(v4, True) and _strided_ok(o4) and o4.shape == q4.shape):
         return None
     _check(call(o4, attn_layout(q4, k4, v4, o4)), name)
@@ -426,7 +466,7 @@ def permute_rows(x: torch.Tensor, idx: torch.Tensor, inverse: bool = False) -> t
     _dev(x, idx)
     BH, S, D = x.shape
     assert idx.dtype == torch.int32 and idx.shape == (BH, S)
-    y = torch.empty_like(x)
+    y = empty_like(x)
     fn = lib.svg_inverse_permute_rows if inverse else lib.svg_permute_rows
     _check(fn(x.data_ptr(), idx.data_ptr(), y.data_ptr(), BH, S, D, _dtype_code(x), _stream()), "svg_permute_rows")
     return y
@@ -438,9 +478,9 @@ def argsort_labels(labels: torch.Tensor, K: int):
     _dev(labels)
     assert labels.dtype == torch.int32 and labels.dim() == 2
     B, N = labels.shape
-    ws = torch.empty(lib.svg_argsort_workspace_bytes(B, N, K), dtype=torch.uint8, device=labels.device)
-    sidx = torch.empty((B, N), dtype=torch.int32, device=labels.device)
-    counts = torch.empty((B, K), dtype=torch.int32, device=labels.device)
+    ws = empty(lib.svg_argsort_workspace_bytes(B, N, K), dtype=torch.uint8, device=labels.device)
+    sidx = empty((B, N), dtype=torch.int32, device=labels.device)
+    counts = empty((B, K), dtype=torch.int32, device=labels.device)
     rc = lib.svg_argsort_labels(labels.data_ptr(), sidx.data_ptr(), counts.data_ptr(), B, N, K, ws.data_ptr(),
                                 ws.numel(), _stream())
     _check(rc, "svg_argsort_labels")
@@ -514,9 +554,9 @@ def _band_attention_lse(q, k, v, mask, sm_scale, head_perm_flag, vid0, num_frame
     scale = _sm_scale(sm_scale, D)
     perm = _perm_arg(head_perm_flag, BH, vid0, num_frame, frame_size)
     # (contiguous [BH, S] whatever the layout of q / o; written whole by every launch, so a retry after a layout fall-back reuses it)
-    lse = torch.empty(q.shape[:-1], dtype=torch.float32, device=q.device)
+    lse = empty(q.shape[:-1], dtype=torch.float32, device=q.device)
     if f32:
-        o32 = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+        o32 = empty(q.shape, dtype=torch.float32, device=q.device)
 
         def call(q, k, v, lay):
             return lib.svg_band_attention_lse_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), o32.data_ptr(), lse.data_ptr(), BH, S, D,
@@ -530,7 +570,7 @@ def _band_attention_lse(q, k, v, mask, sm_scale, head_perm_flag, vid0, num_frame
 
     def run(q, k, v, out):
         if q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and (out.is_contiguous() if out is not None else not token_major_out):
-            o = torch.empty_like(q) if out is None else out
+            o = empty_like(q) if out is None else out
             _check(lib.svg_band_attention_lse(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), BH, S, D, _dtype_code(q),
                                               scale, C.byref(mask), perm, None, _stream()), "svg_band_attention_lse")
             return o
@@ -546,9 +586,9 @@ def _band_form_lse(q, k, v, out, token_major_out, f32, name, call, views_ok=True
     output or o32 — without a layout for contiguous tensors, on views where the layout describes them (views_ok: the entry takes one for
     this call), copied otherwise.  Never the entry without lse.  -> (o | o32, lse)"""
     # (contiguous [BH, S] whatever the layout of q / o; written whole by every launch, so a retry after a layout fall-back reuses it)
-    lse = torch.empty(q.shape[:-1], dtype=torch.float32, device=q.device)
+    lse = empty(q.shape[:-1], dtype=torch.float32, device=q.device)
     if f32:
-        o32 = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+        o32 = empty(q.shape, dtype=torch.float32, device=q.device)
         if q.is_contiguous() and k.is_contiguous() and v.is_contiguous():
             _check(call(q, k, v, o32, lse, None), name)
         elif not (views_ok and _q_views(q, k, v, name, lambda lay: call(q, k, v, o32, lse, C.byref(lay)))):
@@ -558,7 +598,7 @@ def _band_form_lse(q, k, v, out, token_major_out, f32, name, call, views_ok=True
     def run(q, k, v, out):
         dense = q.is_contiguous() and k.is_contiguous() and v.is_contiguous()
         if dense and (out.is_contiguous() if out is not None else not (token_major_out and views_ok)):
-            o = torch.empty_like(q) if out is None else out
+            o = empty_like(q) if out is None else out
             _check(call(q, k, v, o, lse, None), name)
             return o
         if not views_ok:
@@ -605,7 +645,7 @@ def _band_attention(q, k, v, mask, alt_mask, use_alt_flag, sm_scale, head_perm_f
         out.copy_(_band_attention(q, k, v, mask, alt_mask, use_alt_flag, sm_scale, head_perm_flag, vid0, num_frame, frame_size, variant,
                                   None, done, done_nseg, q_prescaled, False))
         return out
-    o = torch.empty_like(q) if out is None else out
+    o = empty_like(q) if out is None else out
     if done is not None:
         _dev(done)
         assert done.dtype == torch.int32 and done.is_contiguous() and variant == 0
@@ -694,7 +734,7 @@ def band_attention_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: 
     assert q.shape == k.shape == v.shape and q.dtype == k.dtype == v.dtype
     S, D = q.shape[-2], q.shape[-1]
     BH = q.numel() // (S * D)
-    o = torch.empty_like(q) if out is None else out
+    o = empty_like(q) if out is None else out
     _dev(o)
     scale = _sm_scale(sm_scale, D)
     perm = _perm_arg(head_perm_flag, BH, vid0, num_frame, frame_size)
@@ -705,7 +745,7 @@ def band_attention_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: 
         key = WorkspaceCache.key("band", BH, S, device=q.device)
         workspace = _F8_WS.get(key)
         if workspace is None or workspace.numel() < need:
-            workspace = _F8_WS[key] = torch.empty(need, dtype=torch.uint8, device=q.device)
+            workspace = _F8_WS[key] = empty(need, dtype=torch.uint8, device=q.device)
     _dev(workspace)
     assert workspace.dtype == torch.uint8 and workspace.numel() >= need
     args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), BH, S, D, _dtype_code(q), scale, C.byref(mask), perm,
@@ -850,7 +890,7 @@ def band_attention_groups(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
         if o is not None:
             return o
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()   # (what no strided entry point takes is copied, as the reference does)
-    o = torch.empty_like(q) if out is None or not out.is_contiguous() else out
+    o = empty_like(q) if out is None or not out.is_contiguous() else out
     _check(call(q, k, v, o, None), "svg_band_groups_attention")
     if out is not None and o is not out:
         out.copy_(o)
@@ -909,9 +949,9 @@ def band_window_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
         raise ValueError(f"band_window_attention: rows [{q_begin}, {q_begin + Sq}) / keys [{k_begin}, {k_begin + Sk}) outside [0, {S})")
     if out is not None and (out.shape != q.shape or out.dtype != q.dtype):
         raise ValueError(f"band_window_attention: out must have q's shape and dtype, got {tuple(out.shape)} {out.dtype}")
-    lse = torch.empty(q.shape[:-1], dtype=torch.float32, device=q.device)
+    lse = empty(q.shape[:-1], dtype=torch.float32, device=q.device)
     if Sq == 0 or Sk == 0:   # no row, or no key: nothing to launch
-        o = out if out is not None else torch.empty(q.shape, dtype=torch.float32 if f32 else q.dtype, device=q.device)
+        o = out if out is not None else empty(q.shape, dtype=torch.float32 if f32 else q.dtype, device=q.device)
         o.zero_()
         lse.fill_(float("-inf"))
         return o, lse
@@ -919,7 +959,7 @@ def band_window_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
     BH = q.numel() // (Sq * D)
     geom = (BH, S, q_begin, Sq, k_begin, Sk, D, _dtype_code(q), _sm_scale(None, D), C.byref(mask))
     if f32:
-        o32 = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+        o32 = empty(q.shape, dtype=torch.float32, device=q.device)
 
         def call32(q, k, v, lay):
             return lib.svg_band_window_attention_lse_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), o32.data_ptr(), lse.data_ptr(), *geom, lay,
@@ -932,7 +972,7 @@ def band_window_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
         return o32, lse
 
     def run(q, k, v, out):
-        o = torch.empty_like(q, memory_format=torch.contiguous_format) if out is None else out
+        o = empty_like(q, memory_format=torch.contiguous_format) if out is None else out
         if q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and o.is_contiguous():
             _check(lib.svg_band_window_attention_lse(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), *geom, None,
                                                      _stream()), "svg_band_window_attention_lse")
@@ -1004,9 +1044,9 @@ def _cross_attention(q, k, v, kv_begin, kv_end, sm_scale, token_major_out, out, 
         assert kv_end.dtype == torch.int32 and n > 0 and BH % n == 0, "kv_end: int32, BH % numel == 0"
         assert kv_begin is None or (kv_begin.dtype == torch.int32 and kv_begin.numel() == n), "kv_begin: int32, as many entries as kv_end"
     # (contiguous [BH, Sq] whatever the layout of q / o; written whole by every launch, so a retry after a layout fall-back reuses it)
-    lse = torch.empty(q.shape[:-1], dtype=torch.float32, device=q.device) if return_lse else None
+    lse = empty(q.shape[:-1], dtype=torch.float32, device=q.device) if return_lse else None
     if f32:
-        o32 = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+        o32 = empty(q.shape, dtype=torch.float32, device=q.device)
 
         def call(q, k, v):
             return _q_views(q, k, v, "svg_cross_attention_lse_f32", lambda lay: lib.svg_cross_attention_lse_f32(
@@ -1079,12 +1119,12 @@ def merge_attention_states(o_parts: Sequence[torch.Tensor], lse_parts: Sequence[
     if out is not None:
         o4 = _view4(out)
     elif token_major_out:   # (token_major_empty, in the output dtype)
-        o4 = torch.empty((x4.shape[0], x4.shape[2], x4.shape[1], x4.shape[3]), dtype=odt, device=x.device).permute(0, 2, 1, 3)
+        o4 = empty((x4.shape[0], x4.shape[2], x4.shape[1], x4.shape[3]), dtype=odt, device=x.device).permute(0, 2, 1, 3)
     else:
-        o4 = torch.empty(x4.shape, dtype=odt, device=x.device)
+        o4 = empty(x4.shape, dtype=odt, device=x.device)
     direct = _strided_ok(o4)
-    dst4 = o4 if direct else torch.empty(x4.shape, dtype=odt, device=x.device)
-    lse = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device) if return_lse else None
+    dst4 = o4 if direct else empty(x4.shape, dtype=odt, device=x.device)
+    lse = empty(x.shape[:-1], dtype=torch.float32, device=x.device) if return_lse else None
     op = (C.c_void_p * MERGE_MAX_PARTS)(*[t.data_ptr() for t in o_c], *([None] * (MERGE_MAX_PARTS - n)))
     lp = (C.c_void_p * MERGE_MAX_PARTS)(*[t.data_ptr() for t in l_c], *([None] * (MERGE_MAX_PARTS - n)))
     lay = attn_layout(x4, x4, x4, dst4)
@@ -1185,7 +1225,7 @@ def varblock_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_
             if not rows_covered:
                 o4.zero_()
             need = int(lib.svg_varblock_workspace_bytes(Hq, Hkv, QB, KB, Sq))
-            ws = torch.empty(need, dtype=torch.uint8, device=q.device) if workspace is None else workspace
+            ws = empty(need, dtype=torch.uint8, device=q.device) if workspace is None else workspace
             _dev(ws)
             assert ws.dtype == torch.uint8 and ws.numel() >= need
             return lib.svg_varblock_attention_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), Hq, Hkv, Sq, Skv, D,
@@ -1197,7 +1237,7 @@ def varblock_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_
         if o is not None:
             return o
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()   # (what the strided entry point does not take is copied)
-    o = torch.empty_like(q) if rows_covered else torch.zeros_like(q)
+    o = empty_like(q) if rows_covered else torch.zeros_like(q)
     if fp8:
         need = int(lib.svg_varblock_attention_fp8_workspace_bytes(Hq, Hkv, QB, KB, Sq, Skv, D))
         if need == 0:
@@ -1205,14 +1245,14 @@ def varblock_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_
         key = WorkspaceCache.key("vb", Hq, Hkv, Sq, Skv, QB, KB, device=q.device)
         ws = _F8_WS.get(key)
         if ws is None or ws.numel() < need:
-            ws = _F8_WS[key] = torch.empty(need, dtype=torch.uint8, device=q.device)
+            ws = _F8_WS[key] = empty(need, dtype=torch.uint8, device=q.device)
         rc = lib.svg_varblock_attention_fp8(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), Hq, Hkv, Sq, Skv, D, _dtype_code(q),
                                             scale, block_map.data_ptr(), q_sizes.data_ptr(), k_sizes.data_ptr(), QB, KB,
                                             _ptr(q_row_idx), _ptr(kv_row_idx), ws.data_ptr(), ws.numel(), _stream())
         _check(rc, "svg_varblock_attention_fp8")
         return o
     need = int(lib.svg_varblock_workspace_bytes(Hq, Hkv, QB, KB, Sq))
-    ws = torch.empty(need, dtype=torch.uint8, device=q.device) if workspace is None else workspace
+    ws = empty(need, dtype=torch.uint8, device=q.device) if workspace is None else workspace
     _dev(ws)
     assert ws.dtype == torch.uint8 and ws.numel() >= need
     rc = lib.svg_varblock_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), Hq, Hkv, Sq, Skv, D,
@@ -1242,16 +1282,16 @@ def _varblock_attention_lse(q, k, v, block_map, q_sizes, k_sizes, sm_scale, q_ro
         assert kv_row_idx.dtype == torch.int32 and kv_row_idx.shape == (Hkv, Skv)
     scale = _sm_scale(sm_scale, D)
     need = int(lib.svg_varblock_workspace_bytes(Hq, Hkv, QB, KB, Sq))
-    ws = torch.empty(need, dtype=torch.uint8, device=q.device) if workspace is None else workspace
+    ws = empty(need, dtype=torch.uint8, device=q.device) if workspace is None else workspace
     _dev(ws)
     assert ws.dtype == torch.uint8 and ws.numel() >= need
     # (contiguous [Hq, Sq] whatever the layout of q / o; rows the kernel does not write: -inf where o holds zeros)
-    lse = torch.empty(q.shape[:-1], dtype=torch.float32, device=q.device)
+    lse = empty(q.shape[:-1], dtype=torch.float32, device=q.device)
     if not rows_covered:
         lse.fill_(float("-inf"))
 
     if f32:
-        o32 = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+        o32 = empty(q.shape, dtype=torch.float32, device=q.device)
         if not rows_covered:
             o32.zero_()
 
@@ -1275,7 +1315,7 @@ def _varblock_attention_lse(q, k, v, block_map, q_sizes, k_sizes, sm_scale, q_ro
 
     def run(q, k, v, out):
         if q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and not token_major_out:
-            o = torch.empty_like(q)
+            o = empty_like(q)
             _check(launch(q, k, v, o, None), "svg_varblock_attention_lse")
             return o
         return _try_strided(q, k, v, None, token_major_out, "svg_varblock_attention_lse", lambda o4, lay: launch(q, k, v, o4, C.byref(lay)))
@@ -1360,8 +1400,8 @@ def sample_mse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rows: torch.Te
     S, D = q.shape[-2], q.shape[-1]
     BH = q.numel() // (S * D)
     R = rows.numel()
-    out = torch.empty((2, BH), dtype=torch.float32, device=q.device)
-    ws = torch.empty(lib.svg_sample_mse_workspace_bytes(BH, R, D, S), dtype=torch.uint8, device=q.device)
+    out = empty((2, BH), dtype=torch.float32, device=q.device)
+    ws = empty(lib.svg_sample_mse_workspace_bytes(BH, R, D, S), dtype=torch.uint8, device=q.device)
     scale = _sm_scale(sm_scale, D)
     if not (q.is_contiguous() and k.is_contiguous() and v.is_contiguous()) and q.dtype == torch.bfloat16:
         q4, k4, v4 = _view4(q), _view4(k), _view4(v)
@@ -1394,7 +1434,7 @@ def kmeans_xsq(x: torch.Tensor) -> torch.Tensor:
     lib = load()
     _dev(x)
     B, N, D = x.shape
-    xsq = torch.empty((B, N), dtype=torch.float32, device=x.device)
+    xsq = empty((B, N), dtype=torch.float32, device=x.device)
     _check(lib.svg_kmeans_xsq(x.data_ptr(), xsq.data_ptr(), B, N, D, _dtype_code(x), _stream()), "svg_kmeans_xsq")
     return xsq
 
@@ -1404,11 +1444,11 @@ class KmeansBuffers:
 
     def __init__(self, B: int, N: int, K: int, D: int, device):
         lib = load()
-        self.labels = torch.empty((B, N), dtype=torch.int32, device=device)
-        self.counts = torch.empty((B, K), dtype=torch.int32, device=device)
-        self.sorted_idx = torch.empty((B, N), dtype=torch.int32, device=device)
-        self.shift = torch.empty((B,), dtype=torch.float32, device=device)
-        self.ws = torch.empty(lib.svg_kmeans_workspace_bytes(B, N, K, D), dtype=torch.uint8, device=device)
+        self.labels = empty((B, N), dtype=torch.int32, device=device)
+        self.counts = empty((B, K), dtype=torch.int32, device=device)
+        self.sorted_idx = empty((B, N), dtype=torch.int32, device=device)
+        self.shift = empty((B,), dtype=torch.float32, device=device)
+        self.ws = empty(lib.svg_kmeans_workspace_bytes(B, N, K, D), dtype=torch.uint8, device=device)
 
 
 def kmeans_iter(x: torch.Tensor, xsq: Optional[torch.Tensor], c_in: torch.Tensor, c_out: torch.Tensor, buf: KmeansBuffers) -> None:
@@ -1431,8 +1471,8 @@ def kmeans_assign(x: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
     B, N, D = x.shape
     K = centroids.shape[1]
     assert centroids.shape == (B, K, D) and centroids.dtype == x.dtype and x.is_contiguous() and centroids.is_contiguous()
-    labels = torch.empty((B, N), dtype=torch.int32, device=x.device)
-    ws = torch.empty(lib.svg_kmeans_workspace_bytes(B, N, K, D), dtype=torch.uint8, device=x.device)
+    labels = empty((B, N), dtype=torch.int32, device=x.device)
+    ws = empty(lib.svg_kmeans_workspace_bytes(B, N, K, D), dtype=torch.uint8, device=x.device)
     _check(lib.svg_kmeans_assign(x.data_ptr(), centroids.data_ptr(), labels.data_ptr(), B, N, K, D, _dtype_code(x), ws.data_ptr(),
                                  ws.numel(), _stream()), "svg_kmeans_assign")
     return labels
@@ -1447,11 +1487,11 @@ def kmeans_update(x: torch.Tensor, labels: torch.Tensor, centroids_in: torch.Ten
     K = centroids_in.shape[1]
     assert labels.dtype == torch.int32 and labels.shape == (B, N) and labels.is_contiguous()
     assert centroids_in.shape == (B, K, D) and centroids_in.dtype == x.dtype and x.is_contiguous() and centroids_in.is_contiguous()
-    cent = torch.empty_like(centroids_in)
-    counts = torch.empty((B, K), dtype=torch.int32, device=x.device)
-    sorted_idx = torch.empty((B, N), dtype=torch.int32, device=x.device)
-    shift = torch.empty((B,), dtype=torch.float32, device=x.device)
-    ws = torch.empty(lib.svg_kmeans_workspace_bytes(B, N, K, D), dtype=torch.uint8, device=x.device)
+    cent = empty_like(centroids_in)
+    counts = empty((B, K), dtype=torch.int32, device=x.device)
+    sorted_idx = empty((B, N), dtype=torch.int32, device=x.device)
+    shift = empty((B,), dtype=torch.float32, device=x.device)
+    ws = empty(lib.svg_kmeans_workspace_bytes(B, N, K, D), dtype=torch.uint8, device=x.device)
     _check(lib.svg_kmeans_update(x.data_ptr(), labels.data_ptr(), centroids_in.data_ptr(), cent.data_ptr(), counts.data_ptr(),
                                  sorted_idx.data_ptr(), shift.data_ptr(), B, N, K, D, _dtype_code(x), ws.data_ptr(), ws.numel(), _stream()),
            "svg_kmeans_update")
@@ -1484,14 +1524,14 @@ def kmeans_loop(x: torch.Tensor, xsq: Optional[torch.Tensor], c_init: torch.Tens
     w = None if work is None else work.get(key)
     if w is None:
         nb = lib.svg_kmeans_loop_workspace_bytes(B, N, K, D) if group is None else lib.svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, group)
-        w = dict(ca=torch.empty_like(c_init), cb=torch.empty_like(c_init), ws=torch.empty(nb, dtype=torch.uint8, device=x.device))
+        w = dict(ca=empty_like(c_init), cb=empty_like(c_init), ws=empty(nb, dtype=torch.uint8, device=x.device))
         if work is not None:
             work[key] = w
-    labels = torch.empty((B, N), dtype=torch.int32, device=x.device)
-    sorted_idx = torch.empty((B, N), dtype=torch.int32, device=x.device)
-    counts = torch.empty((B, K), dtype=torch.int32, device=x.device)
-    cent = torch.empty_like(c_init)
-    n_it = torch.zeros(() if group is None else (B // group,), dtype=torch.int32, device=x.device)
+    labels = empty((B, N), dtype=torch.int32, device=x.device)
+    sorted_idx = empty((B, N), dtype=torch.int32, device=x.device)
+    counts = empty((B, K), dtype=torch.int32, device=x.device)
+    cent = empty_like(c_init)
+    n_it = empty(() if group is None else (B // group,), dtype=torch.int32, device=x.device)   # (copied from the loop's state by every call)
     outs = (labels.data_ptr(), counts.data_ptr(), sorted_idx.data_ptr(), cent.data_ptr(), n_it.data_ptr(), B, N, K, D, _dtype_code(x))
     tail = (int(max_iters), float(tol), w["ws"].data_ptr(), w["ws"].numel(), _stream())
     cs = (c_init.data_ptr(), w["ca"].data_ptr(), w["cb"].data_ptr())
@@ -1518,7 +1558,7 @@ def identify_dynamic_map(qc: torch.Tensor, kc: torch.Tensor, k_sizes: torch.Tens
     BH, QC, D = qc.shape
     KC = kc.shape[1]
     assert k_sizes.dtype == torch.int32 and k_sizes.shape == (BH, KC)
-    out = torch.empty((BH, QC, KC), dtype=torch.uint8, device=qc.device)
+    out = empty((BH, QC, KC), dtype=torch.uint8, device=qc.device)
     rc = lib.svg_identify_dynamic_map(qc.data_ptr(), kc.data_ptr(), k_sizes.data_ptr(), out.data_ptr(), BH, QC, KC, D,
                                       _dtype_code(qc), float(top_p), int(preserve_length), _stream())
     _check(rc, "svg_identify_dynamic_map")
@@ -1529,7 +1569,7 @@ def map_density(block_map: torch.Tensor, q_sizes: torch.Tensor, k_sizes: torch.T
     lib = load()
     _dev(block_map, q_sizes, k_sizes)
     BH, QB, KB = block_map.shape
-    out = torch.empty((BH,), dtype=torch.float32, device=block_map.device)
+    out = empty((BH,), dtype=torch.float32, device=block_map.device)
     rc = lib.svg_map_density(block_map.data_ptr(), q_sizes.data_ptr(), k_sizes.data_ptr(), out.data_ptr(), BH, QB, KB,
                              _stream())
     _check(rc, "svg_map_density")
@@ -1646,11 +1686,11 @@ def qk_norm_rope_transpose(q_in, k_in, heads_q: int, heads_k: int, norm_kind: in
     _dev(q_in, k_in, q_weight, q_bias, k_weight, k_bias, cos, sin)
     bsz, S, HD = q_in.shape
     D = HD // heads_q
-    q_out = torch.empty((bsz, heads_q, S, D), dtype=q_in.dtype, device=q_in.device)
+    q_out = empty((bsz, heads_q, S, D), dtype=q_in.dtype, device=q_in.device)
     k_out = None
     if k_in is not None:
         assert k_in.shape == (bsz, S, heads_k * D) and k_in.dtype == q_in.dtype
-        k_out = torch.empty((bsz, heads_k, S, D), dtype=q_in.dtype, device=q_in.device)
+        k_out = empty((bsz, heads_k, S, D), dtype=q_in.dtype, device=q_in.device)
     rope_hi = S if rope_hi is None else rope_hi
     if rope_kind:
         cols = D // 2 if rope_kind == 2 else D
@@ -1696,7 +1736,7 @@ def qk_norm_rope_transpose_joint(segments: Sequence[JointSegment], heads: int, r
             assert t is None or (t.dim() == 3 and t.shape[0] == bsz and t.shape[2] == HD and t.dtype == ref.dtype), "segment tensors disagree"
     rows = [(sg.q if sg.q is not None else sg.k).shape[1] for sg in segs]
     S = sum(rows)
-    mk = lambda on: torch.empty((bsz, heads, S, D), dtype=ref.dtype, device=ref.device) if on else None  # noqa: E731
+    mk = lambda on: empty((bsz, heads, S, D), dtype=ref.dtype, device=ref.device) if on else None  # noqa: E731
     q_out, k_out = mk(segs[0].q is not None), mk(segs[0].k is not None)
     v_out = mk(with_v and segs[0].v is not None)
     rope_hi = S if rope_hi is None else rope_hi
@@ -1725,7 +1765,7 @@ def rmsnorm_rope_transpose(q_in, k_in, v_in, heads: int, q_weight=None, k_weight
     bsz, S, HD = q_in.shape
     D = HD // heads
     assert q_in.is_contiguous() and all(t is None or (t.shape == q_in.shape and t.dtype == q_in.dtype and t.is_contiguous()) for t in (k_in, v_in))
-    mk = lambda t: None if t is None else torch.empty((bsz, heads, S, D), dtype=q_in.dtype, device=q_in.device)  # noqa: E731
+    mk = lambda t: None if t is None else empty((bsz, heads, S, D), dtype=q_in.dtype, device=q_in.device)  # noqa: E731
     q_out, k_out, v_out = mk(q_in), mk(k_in), mk(v_in)
     w = q_weight if q_weight is not None else k_weight
     wdt = _GLUE_DT[w.dtype] if w is not None else 2
@@ -1767,7 +1807,7 @@ def layernorm_forward(x, weight=None, bias=None, eps: float = 1e-5, out_dtype=to
     lib = load()
     _dev(x, weight, bias)
     M, N, _ = _rows(x)
-    y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    y = empty(x.shape, dtype=out_dtype, device=x.device)
     wdt = _GLUE_DT[weight.dtype] if weight is not None else 2
     if weight is not None:
         assert bias is not None and weight.shape == (N,) and bias.shape == (N,) and bias.dtype == weight.dtype
@@ -1784,7 +1824,7 @@ def rmsnorm_forward(x, weight=None, eps: float = 1e-6, out_dtype=None) -> torch.
     _dev(x, weight)
     M, N, _ = _rows(x)
     out_dtype = x.dtype if out_dtype is None else out_dtype
-    y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    y = empty(x.shape, dtype=out_dtype, device=x.device)
     wdt = _GLUE_DT[weight.dtype] if weight is not None else 2
     if weight is not None:
         assert weight.shape == (N,) and weight.is_contiguous()
@@ -1799,7 +1839,7 @@ def modulate_shift_forward(x, scale, shift, out_dtype=torch.float32) -> torch.Te
     M, N, rpb = _rows(x)
     sc, sh = _per_batch(scale, x, N), _per_batch(shift, x, N)
     _dev(sc, sh)
-    y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    y = empty(x.shape, dtype=out_dtype, device=x.device)
     _check(lib.svg_modulate_shift_forward(x.data_ptr(), y.data_ptr(), sc.data_ptr(), sh.data_ptr(), M, N, rpb, _GLUE_DT[x.dtype],
                                           _GLUE_DT[out_dtype], _stream()), "svg_modulate_shift_forward")
     return y
@@ -1813,7 +1853,7 @@ def modulate_gate_residual_forward(residual, x, gate, out_dtype=torch.float32) -
     _rows(residual)
     g = _per_batch(gate, x, N)
     _dev(g)
-    y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    y = empty(x.shape, dtype=out_dtype, device=x.device)
     _check(lib.svg_modulate_gate_residual_forward(residual.data_ptr(), x.data_ptr(), g.data_ptr(), y.data_ptr(), M, N, rpb,
                                                   _GLUE_DT[residual.dtype], _GLUE_DT[x.dtype], _GLUE_DT[out_dtype], _stream()),
            "svg_modulate_gate_residual_forward")
@@ -1832,7 +1872,7 @@ def layernorm_modulate_forward(x, weight=None, bias=None, scale=None, shift=None
     sh = _per_batch(shift, x, N) if shift is not None else None
     _dev(sc, sh)
     wdt = _GLUE_DT[weight.dtype] if weight is not None else 2
-    y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    y = empty(x.shape, dtype=out_dtype, device=x.device)
     _check(lib.svg_layernorm_modulate_forward_ex(x.data_ptr(), y.data_ptr(), _ptr(weight), _ptr(bias), _ptr(sc), _ptr(sh), M, N, rpb,
                                                  _GLUE_DT[x.dtype], _GLUE_DT[out_dtype], wdt, float(eps), int(bool(reference_padding)),
                                                  _stream()),
@@ -1848,9 +1888,9 @@ def bsr_to_block_map(indptr: torch.Tensor, indices: torch.Tensor, MB: int, NB: i
     _dev(indptr, indices)
     assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == MB + 1
     dev = indptr.device
-    bm = torch.empty((heads, MB + 1, NB + 1), dtype=torch.uint8, device=dev)
-    qs = torch.empty((heads, MB + 1), dtype=torch.int32, device=dev)
-    ks = torch.empty((heads, NB + 1), dtype=torch.int32, device=dev)
+    bm = empty((heads, MB + 1, NB + 1), dtype=torch.uint8, device=dev)
+    qs = empty((heads, MB + 1), dtype=torch.int32, device=dev)
+    ks = empty((heads, NB + 1), dtype=torch.int32, device=dev)
     _check(lib.svg_bsr_to_block_map(indptr.data_ptr(), indices.data_ptr(), MB, NB, row_block, col_block, len_text, heads,
                                     bm.data_ptr(), qs.data_ptr(), ks.data_ptr(), _stream()), "svg_bsr_to_block_map")
     return bm, qs, ks

@@ -21,6 +21,8 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
+from . import _native
+
 # ---------------------------------------------------------------------------------------------------------------
 # opt-in switch for the processors (svg/models/_core.py): svg.distributed.enable(group) makes every SVG1 / SVG2 layer-call run
 # this rank's heads only and all-gather the result; nothing changes for a process that never calls it.
@@ -95,14 +97,14 @@ def all_gather_heads(o_local: torch.Tensor, num_heads: int, group=None) -> torch
     counts = head_counts(num_heads, world)
     cfg, _, S, D = o_local.shape
     if len(set(counts)) == 1:
-        out = torch.empty((world * cfg, counts[0], S, D), dtype=o_local.dtype, device=o_local.device)
+        out = _native.empty((world * cfg, counts[0], S, D), dtype=o_local.dtype, device=o_local.device)
         dist.all_gather_into_tensor(out, o_local.contiguous(), group=group)  # concatenated along dim 0
         return out.view(world, cfg, counts[0], S, D).permute(1, 0, 2, 3, 4).reshape(cfg, num_heads, S, D)
     # ragged split: pad every shard to the largest one
     mx = max(counts)
     pad = torch.zeros((cfg, mx, S, D), dtype=o_local.dtype, device=o_local.device)
     pad[:, : o_local.shape[1]] = o_local
-    out = torch.empty((world * cfg, mx, S, D), dtype=o_local.dtype, device=o_local.device)
+    out = _native.empty((world * cfg, mx, S, D), dtype=o_local.dtype, device=o_local.device)
     dist.all_gather_into_tensor(out, pad, group=group)
     out = out.view(world, cfg, mx, S, D)
     return torch.cat([out[r, :, : counts[r]] for r in range(world)], dim=1)
@@ -167,14 +169,14 @@ def tokens_to_heads(x_local: torch.Tensor, num_tokens: int, group=None, unit: in
     send = x_local.contiguous().view(-1)   # (no copy for the head-major tensor the fused prologue writes)
     # recv: optional caller-owned staging buffer (a step that runs this exchange 180 times allocates nothing: ExchangeBuffers)
     if recv is None:
-        recv = torch.empty(Hl * num_tokens * E, dtype=x_local.dtype, device=x_local.device)
+        recv = _native.empty(Hl * num_tokens * E, dtype=x_local.dtype, device=x_local.device)
     else:
         assert recv.dtype == x_local.dtype and recv.numel() >= Hl * num_tokens * E
         recv = recv.view(-1)[: Hl * num_tokens * E]
     dist.all_to_all_single(recv, send, output_split_sizes=[Hl * (b - a) * E for a, b in tr],
                            input_split_sizes=[len(o) * S_me * E for o in owners], group=group)
     if out is None:
-        out = torch.empty((Hl, num_tokens) + rest, dtype=x_local.dtype, device=x_local.device)
+        out = _native.empty((Hl, num_tokens) + rest, dtype=x_local.dtype, device=x_local.device)
     off = 0
     for a, b in tr:
         n = Hl * (b - a) * E
@@ -210,7 +212,7 @@ def heads_to_tokens(o_local: torch.Tensor, num_heads: int, group=None, unit: int
             send[off:off + n].view((Hl, b - a) + rest).copy_(o_local[:, a:b])
             off += n
     if recv is None:
-        recv = torch.empty(num_heads * S_me * E, dtype=o_local.dtype, device=o_local.device)
+        recv = _native.empty(num_heads * S_me * E, dtype=o_local.dtype, device=o_local.device)
     else:
         assert recv.dtype == o_local.dtype and recv.numel() >= num_heads * S_me * E
         recv = recv.view(-1)[: num_heads * S_me * E]
@@ -219,7 +221,7 @@ def heads_to_tokens(o_local: torch.Tensor, num_heads: int, group=None, unit: int
     out = recv.view((num_heads, S_me) + rest)
     order = [h for o in owners for h in o]
     if order != list(range(num_heads)):
-        inv = torch.empty(num_heads, dtype=torch.long)
+        inv = _native.empty(num_heads, dtype=torch.long)
         inv[torch.tensor(order)] = torch.arange(num_heads)
         out = out.index_select(0, inv.to(out.device))
     return out
@@ -235,21 +237,15 @@ MERGE_MAX_PARTS = 8   # svg_merge_attention_states (include/svg_attn.h): parts o
 
 
 def _native_attn(q, k, v, return_lse=False):
-    from . import _native
-
     return _native.cross_attention(q, k, v, return_lse=return_lse)
 
 
 def _native_merge(o_parts, lse_parts):
-    from . import _native
-
     return _native.merge_attention_states(o_parts, lse_parts)
 
 
 def _native_attn_f32(q, k, v, return_lse=False):
     """the step of fp32_parts=True: the part before its rounding; the calls without lse (world == 1, overlap=False) are the plain ones"""
-    from . import _native
-
     if not return_lse:
         return _native.cross_attention(q, k, v)
     return _native.cross_attention(q, k, v, return_lse=True, out_dtype=torch.float32)
@@ -283,8 +279,6 @@ def token_sharded_dense_attention(q_local: torch.Tensor, k_local: torch.Tensor, 
 
         attn_fn = attn_fn or _native_attn_f32
         if merge_fn is None:
-            from . import _native
-
             merge_fn = partial(_native.merge_attention_states, out_dtype=q_local.dtype)
     attn_fn = attn_fn or _native_attn
     merge_fn = merge_fn or _native_merge
@@ -311,11 +305,11 @@ def token_sharded_dense_attention(q_local: torch.Tensor, k_local: torch.Tensor, 
         pad = torch.zeros(kv_shape(mx), dtype=k_local.dtype, device=k_local.device)
         pad[0][..., :S_me, :] = k_local
         pad[1][..., :S_me, :] = v_local
-        full = torch.empty((world * 2,) + kv_shape(mx)[1:], dtype=k_local.dtype, device=k_local.device)   # concatenated along dim 0
+        full = _native.empty((world * 2,) + kv_shape(mx)[1:], dtype=k_local.dtype, device=k_local.device)   # concatenated along dim 0
         dist.all_gather_into_tensor(full, pad, group=group, async_op=True).wait()
         full = full.view((world,) + kv_shape(mx))
         if S_me == 0:
-            return torch.empty_like(q_local)
+            return _native.empty_like(q_local)
         k_all = torch.cat([full[r, 0][..., :n_tok[r], :] for r in range(world)], dim=-2)
         v_all = torch.cat([full[r, 1][..., :n_tok[r], :] for r in range(world)], dim=-2)
         return attn_fn(q_local, k_all, v_all)
@@ -326,7 +320,7 @@ def token_sharded_dense_attention(q_local: torch.Tensor, k_local: torch.Tensor, 
     def shift(j):
         """this rank's shard to rank + j, the shard of rank - j from its owner: (source rank, receive buffer, work handle)"""
         dst, src = (rank + j) % world, (rank - j) % world
-        recv = torch.empty(n_tok[src] * per_tok, dtype=send.dtype, device=send.device)
+        recv = _native.empty(n_tok[src] * per_tok, dtype=send.dtype, device=send.device)
         ins, outs = [0] * world, [0] * world
         ins[dst], outs[src] = send.numel(), recv.numel()
         work = dist.all_to_all_single(recv, send, output_split_sizes=outs, input_split_sizes=ins, group=group, async_op=True)
@@ -345,7 +339,7 @@ def token_sharded_dense_attention(q_local: torch.Tensor, k_local: torch.Tensor, 
         if S_me > 0 and n_tok[src] > 0:                        # (an empty shard has no keys: no part)
             parts[src] = attn_fn(q_local, k_s, v_s, True)
     if S_me == 0:
-        return torch.empty_like(q_local)
+        return _native.empty_like(q_local)
     order = sorted(parts)
     return merge_fn([parts[r][0] for r in order], [parts[r][1] for r in order])
 
@@ -358,8 +352,6 @@ def band_exchange_plan(mask, num_tokens: int, world: int, unit: int = 128) -> Li
     """plan[r][s]: do the rows of rank r (`token_range(num_tokens, r, world, unit)`) see any key of rank s's shard under the band mask
     `mask` (_native.BandMask) over num_tokens rows?  Host only, closed form (_native.band_window_has_keys); the same table on every rank.
     A pair that is False exchanges nothing and computes nothing in token_sharded_band_attention."""
-    from . import _native
-
     tr = [token_range(num_tokens, r, world, unit) for r in range(world)]
     return [[_native.band_window_has_keys(mask, num_tokens, tr[r], tr[s]) for s in range(world)] for r in range(world)]
 
@@ -396,14 +388,10 @@ def token_sharded_band_attention(q_local: torch.Tensor, k_local: torch.Tensor, v
         raise ValueError(f"token_sharded_band_attention: a rank sees the keys of {most} shards, but merge_attention_states takes at most "
                          f"{MERGE_MAX_PARTS} parts — use a group of at most {MERGE_MAX_PARTS} ranks")
     if attn_fn is None:
-        from . import _native
-
         def attn_fn(q, k, v, q_range, k_range):
             return _native.band_window_attention(q, k, v, mask, num_tokens, q_range[0], k_range[0],
                                                  out_dtype=torch.float32 if fp32_parts else None)
     if merge_fn is None:
-        from . import _native
-
         def merge_fn(o_parts, lse_parts):
             return _native.merge_attention_states(o_parts, lse_parts, out_dtype=q_local.dtype if fp32_parts else None)
     lead = tuple(k_local.shape[:-2])
@@ -419,7 +407,7 @@ def token_sharded_band_attention(q_local: torch.Tensor, k_local: torch.Tensor, v
     def shift(j):
         """this rank's shard to rank + j if that rank sees it, the shard of rank - j if this rank sees it: (source rank, buffer, work)"""
         dst, src = (rank + j) % world, (rank - j) % world
-        recv = torch.empty(n_tok[src] * per_tok if plan[rank][src] else 0, dtype=send.dtype, device=send.device)
+        recv = _native.empty(n_tok[src] * per_tok if plan[rank][src] else 0, dtype=send.dtype, device=send.device)
         ins, outs = [0] * world, [0] * world
         ins[dst] = send.numel() if plan[dst][rank] else 0
         outs[src] = recv.numel()
@@ -438,7 +426,7 @@ def token_sharded_band_attention(q_local: torch.Tensor, k_local: torch.Tensor, v
             k_s, v_s = recv.view(kv_shape(n_tok[src])).unbind(0)
             parts[src] = attn_fn(q_local, k_s, v_s, tr[rank], tr[src])
     if S_me == 0:
-        return torch.empty_like(q_local)
+        return _native.empty_like(q_local)
     if not parts:   # (a mask that gives these rows no key at all)
         return torch.zeros_like(q_local)
     order = sorted(parts)
@@ -458,7 +446,7 @@ class ExchangeBuffers:
         self.Hl = num_heads // world
         a, b = token_range(num_tokens, rank, world, unit)
         self.S_me = b - a
-        mk = lambda *shape: torch.empty(shape, dtype=dtype, device=device)   # noqa: E731
+        mk = lambda *shape: _native.empty(shape, dtype=dtype, device=device)   # noqa: E731
         self.qkv = [mk(self.Hl, num_tokens, head_dim) for _ in range(3)]
         self.recv_in = mk(self.Hl * num_tokens * head_dim)
         self.send_out = mk(self.Hl * num_tokens * head_dim)
@@ -521,7 +509,7 @@ def overlapped_sharded_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tens
     cfg, H, S, D = q.shape
     assert cfg == 1, "overlapped_sharded_attention: cfg must be 1 (use sharded_attention otherwise)"
     n_chunks, n_per, _ = chunked_head_layout(H, rank, world, max_chunks)
-    full = torch.empty((H, S, D), dtype=q.dtype, device=q.device)
+    full = _native.empty((H, S, D), dtype=q.dtype, device=q.device)
     cuda = q.is_cuda
     main = torch.cuda.current_stream() if cuda else None
     side = side_streams(q.device) if cuda and n_chunks > 1 else None

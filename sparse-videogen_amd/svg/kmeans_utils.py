@@ -40,7 +40,7 @@ class KMeansState:
         B, N, D = x.shape
         self.shape = (B, N, n_clusters, D, x.dtype, x.device)
         self.buf = _native.KmeansBuffers(B, N, n_clusters, D, x.device)
-        self.c = [torch.empty((B, n_clusters, D), dtype=x.dtype, device=x.device) for _ in range(2)]
+        self.c = [_native.empty((B, n_clusters, D), dtype=x.dtype, device=x.device) for _ in range(2)]
 
     def matches(self, x, n_clusters):
         B, N, D = x.shape

@@ -136,7 +136,7 @@ def _dense_sdpa(q, k, v, valid_len):
     if valid_len is None or valid_len >= S:
         return F.scaled_dot_product_attention(q, k, v, dropout_p=0.0, is_causal=False)
     vl = int(valid_len)
-    o = torch.empty_like(q)
+    o = _native.empty_like(q)
     o[:, :, :vl] = F.scaled_dot_product_attention(q[:, :, :vl], k[:, :, :vl], v[:, :, :vl])
     o[:, :, vl:] = F.scaled_dot_product_attention(q[:, :, vl:], k[:, :, vl:], v[:, :, vl:])
     return o
@@ -406,7 +406,7 @@ def svg1_sparse_attention(q, k, v, geo: Geometry, mask: "_native.BandMask", prof
                 out = _native.band_attention(q, k, v, mask, q_prescaled=q_prescaled, **kw, **pk)
         return (out[0], best_mask_idx, out[1]) if return_lse else (out, best_mask_idx)
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-    qo, ko, vo = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    qo, ko, vo = _native.empty_like(q), _native.empty_like(k), _native.empty_like(v)
     with time_logging_decorator("Level 3 - fast_sparse_head_placement"):
         _native.head_placement([q, k, v], [qo, ko, vo], best_mask_idx, geo.context_length, geo.num_frame, geo.frame_size,
                                geo.text_first, inverse=False)
@@ -415,7 +415,7 @@ def svg1_sparse_attention(q, k, v, geo: Geometry, mask: "_native.BandMask", prof
             hs = _native.band_attention_groups(qo, ko, vo, groups[0], groups[1], q_prescaled=q_prescaled)
         else:
             hs = _native.band_attention(qo, ko, vo, mask, q_prescaled=q_prescaled)
-    out = torch.empty_like(hs)
+    out = _native.empty_like(hs)
     with time_logging_decorator("Level 3 - fast_hidden_states_placement"):
         _native.head_placement([hs], [out], best_mask_idx, geo.context_length, geo.num_frame, geo.frame_size, geo.text_first,
                                inverse=True)
@@ -610,7 +610,7 @@ class _DensityLog:
         self.pending = []   # (path, meta, pinned host tensor, event)
 
     def push(self, path: str, meta: dict, densities: torch.Tensor) -> None:
-        host = torch.empty(densities.shape, dtype=torch.float32, pin_memory=densities.is_cuda)
+        host = _native.empty(densities.shape, dtype=torch.float32, pin_memory=densities.is_cuda)
         host.copy_(densities.float(), non_blocking=True)
         ev = None
         if densities.is_cuda:

@@ -30,6 +30,7 @@ from lse_ops_torch import attention_lse, merge_states
 from oracle import svg_oracle as O
 from sparse_lse_cases import DTYPES, T_SINGLE, check_lse, rel_l2
 from test_gpu_kernels import dev
+from poisoned import poisoned_like
 
 ROOT = Path(__file__).resolve().parent.parent
 pytestmark = pytest.mark.gpu
@@ -39,11 +40,9 @@ F32 = dict(return_lse=True, out_dtype=torch.float32)
 
 @pytest.fixture(scope="module")
 def nat():
-    from svg import _native
+    from poisoned import load_native
 
-    _native.load()
-    assert torch.cuda.is_available()
-    return _native
+    return load_native()
 
 
 def _ordinal(x):
@@ -123,7 +122,7 @@ def test_cross_c_entry_does_not_read_the_o_member_of_the_layout(nat):
     lay = nat.attn_layout(q, k, v, q)
     lay.o = nat.TensorStrides(-3, 5, 1)
     o32 = torch.full_like(ref32, float("nan"))
-    lse = torch.empty_like(ref_lse)
+    lse = poisoned_like(ref_lse)
     rc = nat.load().svg_cross_attention_lse_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), o32.data_ptr(), lse.data_ptr(), B * H, Sq, Skv, 128, 0,
                                                 1.0 / math.sqrt(128), None, None, 1, C_.byref(lay), torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
@@ -437,6 +436,7 @@ def _worker(rank, world, port, ret):
             sys.path.insert(0, p)
     from oracle import svg_oracle as O_
     from svg import _native as nat_
+    nat_.poison_allocations(True)   # (a spawned process: the switch of tests/poisoned.py does not reach it)
     from svg import distributed as sd
 
     dist.init_process_group("gloo", rank=rank, world_size=world)

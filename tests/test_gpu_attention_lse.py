@@ -19,6 +19,7 @@ import torch.multiprocessing as mp
 from lse_ops_torch import attention_lse, merge_states
 from oracle import svg_oracle as O
 from test_gpu_kernels import check_attn, dev, rel_l2
+from poisoned import poisoned_like
 
 ROOT = Path(__file__).resolve().parent.parent
 pytestmark = pytest.mark.gpu
@@ -31,11 +32,9 @@ T_SINGLE = {torch.bfloat16: 3e-3, torch.float16: 1e-3}   # check_attn's rel. L2 
 
 @pytest.fixture(scope="module")
 def nat():
-    from svg import _native
+    from poisoned import load_native
 
-    _native.load()
-    assert torch.cuda.is_available()
-    return _native
+    return load_native()
 
 
 def _qkv(B, H, Sq, Skv, dtype, seed, D=128):
@@ -90,7 +89,7 @@ def test_lse_layouts_equal_contiguous(nat, dtype):
     assert not q.is_contiguous() and not k.is_contiguous()
     o_ref, lse_ref_ = nat.cross_attention(q.contiguous(), k.contiguous(), v.contiguous(), return_lse=True)
     check_lse(lse_ref_, lse_ref(q.cpu(), k.cpu()), dtype)
-    for kw in ({}, {"token_major_out": True}, {"out": torch.empty_like(o_ref)}):
+    for kw in ({}, {"token_major_out": True}, {"out": poisoned_like(o_ref)}):
         o, lse = nat.cross_attention(q, k, v, return_lse=True, **kw)
         assert lse.dtype == torch.float32 and lse.is_contiguous() and torch.equal(lse, lse_ref_), kw
         assert torch.equal(o, o_ref), kw
@@ -261,7 +260,7 @@ def test_merge_of_nine_parts_raises(nat):
 
     arr_o = (C.c_void_p * 9)(*[o_parts[0].data_ptr()] * 9)
     arr_l = (C.c_void_p * 9)(*[lse_parts[0].data_ptr()] * 9)
-    out = torch.empty_like(o_parts[0])
+    out = poisoned_like(o_parts[0])
     rc = lib.svg_merge_attention_states(C.cast(arr_o, C.c_void_p), C.cast(arr_l, C.c_void_p), 9, out.data_ptr(), None, 6, 1, 128, 0, None, None)
     assert rc == -1                                                    # SVG_ERR_BAD_ARG, before any launch
 
@@ -306,6 +305,7 @@ def _worker(rank, world, port, ret):
             sys.path.insert(0, p)
     from oracle import svg_oracle as O_
     from svg import _native as nat_
+    nat_.poison_allocations(True)   # (a spawned process: the switch of tests/poisoned.py does not reach it)
     from svg import distributed as sd
 
     dist.init_process_group("gloo", rank=rank, world_size=world)

@@ -11,6 +11,7 @@ import torch
 
 from oracle import svg_oracle as O
 from standins import Attention
+from poisoned import poisoned_like
 
 pytestmark = pytest.mark.gpu
 
@@ -24,10 +25,9 @@ PERM = dict(vid0=0, num_frame=F_, frame_size=P_)
 
 @pytest.fixture(scope="module")
 def nat():
-    from svg import _native
+    from poisoned import load_native
 
-    _native.load()
-    return _native
+    return load_native()
 
 
 def hy_mask(nat, p):
@@ -145,7 +145,7 @@ def test_grouped_call_into_out_and_from_views_it_cannot_take(nat):
     vals, heads = heads_of(LENS)
     masks = [hy_mask(nat, p) for p in vals]
     want = nat.band_attention_groups(q, k, v, masks, heads)
-    out = torch.empty_like(q)
+    out = poisoned_like(q)
     assert nat.band_attention_groups(q, k, v, masks, heads, out=out) is out and torch.equal(out, want)
     out_tm = nat.token_major_empty(q)
     assert nat.band_attention_groups(q, k, v, masks, heads, out=out_tm) is out_tm and torch.equal(out_tm, want)

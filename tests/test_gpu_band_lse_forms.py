@@ -32,11 +32,9 @@ CTX_OF = {"hy": CTX, "wan": 0, "cog": CTX}
 
 @pytest.fixture(scope="module")
 def nat():
-    from svg import _native
+    from poisoned import load_native
 
-    _native.load()
-    assert torch.cuda.is_available()
-    return _native
+    return load_native()
 
 
 def flag_of(x):

@@ -14,6 +14,8 @@ import torch
 
 from svg import _native as nat
 
+from poisoned import poison_on  # noqa: E402,F401  (the suite runs on poisoned allocations)
+
 pytestmark = pytest.mark.gpu
 
 D = 128

@@ -28,6 +28,8 @@ from oracle import svg_oracle as O
 from svg import _native as nat
 from test_gpu_kernels import check_attn
 
+from poisoned import poison_on  # noqa: E402,F401  (the suite runs on poisoned allocations)
+
 pytestmark = pytest.mark.gpu
 
 D = 128

@@ -25,6 +25,8 @@ from svg import _native as nat
 from band_replay_cases import BEST, GEO_A, SPIKE_DIM0, bool_mask, build, q_tiles_of, reference, replay_everywhere_spikes  # noqa: F401
 from test_gpu_kernels import check_attn
 
+from poisoned import poison_on  # noqa: E402,F401  (the suite runs on poisoned allocations)
+
 pytestmark = pytest.mark.gpu
 
 D, H, F_, P_, CTX, L, BAND = GEO_A

@@ -48,11 +48,9 @@ def row_windows(S):
 
 @pytest.fixture(scope="module")
 def nat():
-    from svg import _native
+    from poisoned import load_native
 
-    _native.load()
-    assert torch.cuda.is_available()
-    return _native
+    return load_native()
 
 
 @functools.lru_cache(maxsize=None)
@@ -296,6 +294,7 @@ def _worker(rank, world, port, ret):
             sys.path.insert(0, p)
     import sparse_lse_cases as SC_
     from svg import _native as nat_
+    nat_.poison_allocations(True)   # (a spawned process: the switch of tests/poisoned.py does not reach it)
     from svg import distributed as sd
 
     dist.init_process_group("gloo", rank=rank, world_size=world)

@@ -9,6 +9,8 @@ import torch
 
 from oracle import svg_oracle as O
 
+from poisoned import poison_on  # noqa: E402,F401  (the suite runs on poisoned allocations)
+
 pytestmark = pytest.mark.gpu
 GOLD = np.load(str(Path(__file__).parent / "golden" / "bsr_golden.npz"))
 P = 40

@@ -10,6 +10,8 @@ import torch.nn as nn
 
 from standins import Attention
 
+from poisoned import poison_on  # noqa: E402,F401  (the suite runs on poisoned allocations)
+
 pytestmark = pytest.mark.gpu
 DT = torch.bfloat16
 HEADS, HD, F_, P_ = 2, 128, 5, 160

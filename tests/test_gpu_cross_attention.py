@@ -10,6 +10,7 @@ import torch.nn.functional as F
 
 from oracle import svg_oracle as O
 from test_gpu_kernels import check_attn, dev, rel_l2
+from poisoned import poisoned_like
 
 pytestmark = pytest.mark.gpu
 DT = torch.bfloat16
@@ -17,11 +18,9 @@ DT = torch.bfloat16
 
 @pytest.fixture(scope="module")
 def nat():
-    from svg import _native
+    from poisoned import load_native
 
-    _native.load()
-    assert torch.cuda.is_available()
-    return _native
+    return load_native()
 
 
 def _qkv(B, H, Sq, Skv, dtype, seed, D=128):
@@ -82,7 +81,7 @@ def test_cross_attention_strided_equals_contiguous(nat, Sq, Skv, dtype):
     ref2 = nat.cross_attention(q.contiguous(), k2.contiguous(), v2.contiguous())
     o3 = nat.cross_attention(q, k2, v2, token_major_out=True)
     assert _is_token_major(o3) and torch.equal(o3, ref2)
-    out = torch.empty_like(ref)                                        # a caller's buffer
+    out = poisoned_like(ref)                                          # a caller's buffer
     assert nat.cross_attention(q, k, v, out=out) is out and torch.equal(out, ref)
 
 

@@ -11,6 +11,7 @@ import torch.nn.functional as F
 
 from oracle import svg_oracle as O
 from test_gpu_kernels import check_attn, dev, rel_l2
+from poisoned import poisoned_like
 
 pytestmark = pytest.mark.gpu
 DT = torch.bfloat16
@@ -19,11 +20,9 @@ D = 128
 
 @pytest.fixture(scope="module")
 def nat():
-    from svg import _native
+    from poisoned import load_native
 
-    _native.load()
-    assert torch.cuda.is_available()
-    return _native
+    return load_native()
 
 
 def _qkv(B, H, Sq, Skv, dtype, seed):
@@ -195,7 +194,7 @@ def test_keyrange_strided_equals_contiguous(nat, Sq, Skv, dtype):
     ref2 = _run(nat, q.contiguous(), k2.contiguous(), v2.contiguous(), windows)
     o3 = _run(nat, q, k2, v2, windows, token_major_out=True)
     assert _is_token_major(o3) and torch.equal(o3, ref2)
-    out = torch.empty_like(ref)                                        # a caller's buffer
+    out = poisoned_like(ref)                                          # a caller's buffer
     assert _run(nat, q, k, v, windows, out=out) is out and torch.equal(out, ref)
 
 

@@ -6,6 +6,7 @@ That path is the reference of every test here; no tolerance is involved.
 ref: svg/models/wan/attention.py:174-188,198-201 (the two scaled_dot_product_attention calls) and :210-229 (the add)."""
 import pytest
 import torch
+from poisoned import poisoned_like
 
 pytestmark = pytest.mark.gpu
 DT = torch.bfloat16
@@ -14,11 +15,9 @@ D = 128
 
 @pytest.fixture(scope="module")
 def nat():
-    from svg import _native
+    from poisoned import load_native
 
-    _native.load()
-    assert torch.cuda.is_available()
-    return _native
+    return load_native()
 
 
 def _rand(shape, dtype, g, scale=1.0):
@@ -97,7 +96,7 @@ def test_pair_strided_equals_contiguous(nat, Sq, Skv_a, Skv_b, dtype):
     assert _is_token_major(o3) and torch.equal(o3, ref_a)
     ref_b = two_launches(nat, cont[0], cont[1], cont[2], kb2.contiguous(), vb2.contiguous())
     assert torch.equal(nat.cross_attention_pair(q, ka, va, kb2, vb2, token_major_out=True), ref_b)
-    out = torch.empty_like(ref)                                                            # a caller's buffer
+    out = poisoned_like(ref)                                                              # a caller's buffer
     assert nat.cross_attention_pair(q, ka, va, kb, vb, out=out) is out and torch.equal(out, ref)
     out_tm = nat.token_major_empty(ref)
     assert nat.cross_attention_pair(q, ka, va, kb, vb, out=out_tm) is out_tm and torch.equal(out_tm, ref)

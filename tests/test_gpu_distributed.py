@@ -12,6 +12,8 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 ROOT = Path(__file__).resolve().parent.parent
+from poisoned import poison_on  # noqa: E402,F401  (the suite runs on poisoned allocations)
+
 pytestmark = pytest.mark.gpu
 
 
@@ -19,6 +21,7 @@ def _worker(rank, world, port, ret):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     sys.path.insert(0, str(ROOT / "sparse-videogen_amd"))
     from svg import _native as nat
+    nat.poison_allocations(True)   # (a spawned process: the switch of tests/poisoned.py does not reach it)
     from svg import distributed as sd
     from svg.models import _core
 

@@ -13,11 +13,9 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def nat():
-    from svg import _native
+    from poisoned import load_native
 
-    _native.load()
-    assert torch.cuda.is_available()
-    return _native
+    return load_native()
 
 
 def rel_l2(a, b):

@@ -7,6 +7,9 @@ import torch
 
 from oracle import svg_oracle as O
 
+from poisoned import poison_on  # noqa: E402,F401  (the suite runs on poisoned allocations)
+from poisoned import poisoned_like
+
 pytestmark = pytest.mark.gpu
 
 H, D, F_, P_, CTX, L = 2, 128, 33, 3600, 256, 64
@@ -50,10 +53,10 @@ def test_fullsize_spot_rows_and_fused_equals_materialised(setup):
     mask = nat.BandMask(**prm)
     o = nat.band_attention(q, k, v, mask, head_perm_flag=best, vid0=0, num_frame=F_, frame_size=P_)
     # (1) fused layout transformation is bit-identical to placement -> attention -> inverse placement
-    qp, kp, vp = (torch.empty_like(x) for x in (q, k, v))
+    qp, kp, vp = (poisoned_like(x) for x in (q, k, v))
     nat.head_placement([q, k, v], [qp, kp, vp], best, CTX, F_, P_, False, False)
     om = nat.band_attention(qp, kp, vp, mask)
-    oi = torch.empty_like(om)
+    oi = poisoned_like(om)
     nat.head_placement([om], [oi], best, CTX, F_, P_, False, True)
     assert torch.equal(oi, o)
     # (2) spot rows (band interior, both band edges, sequence ends, prompt rows, pad rows) against the oracle
@@ -127,10 +130,10 @@ def test_fullsize_spot_rows_wan_cog(model):
     best = torch.tensor([[0, 1]], device="cuda")
     mask = nat.BandMask(**prm)
     o = nat.band_attention(q, k, v, mask, head_perm_flag=best, vid0=vid0, num_frame=F2, frame_size=P2)
-    qp, kp, vp = (torch.empty_like(x) for x in (q, k, v))
+    qp, kp, vp = (poisoned_like(x) for x in (q, k, v))
     nat.head_placement([q, k, v], [qp, kp, vp], best, ctx, F2, P2, text_first, False)
     om = nat.band_attention(qp, kp, vp, mask)
-    oi = torch.empty_like(om)
+    oi = poisoned_like(om)
     nat.head_placement([om], [oi], best, ctx, F2, P2, text_first, True)
     assert torch.equal(oi, o)
     rows = [0, 1, vid0, vid0 + 1, P2 - 1, P2, P2 + 1, vid0 + edge - 1, vid0 + edge, vid0 + edge + 1, S2 // 2, S2 // 2 + 1,

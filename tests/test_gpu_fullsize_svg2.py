@@ -17,6 +17,8 @@ import torch
 
 from oracle import svg_oracle as O
 
+from poisoned import poison_on  # noqa: E402,F401  (the suite runs on poisoned allocations)
+
 pytestmark = pytest.mark.gpu
 
 CASES = {

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from oracle import svg_oracle as O
+from poisoned import poisoned_like
 
 TRIALS = int(os.environ.get("SVG_FUZZ", "4") or 4)     # default run: 4 seeded trials per kernel family; SVG_FUZZ=<n> for more
 pytestmark = pytest.mark.gpu
@@ -18,11 +19,9 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def nat():
-    from svg import _native
+    from poisoned import load_native
 
-    _native.load()
-    assert torch.cuda.is_available()
-    return _native
+    return load_native()
 
 
 def dev(t):
@@ -164,7 +163,7 @@ def test_fuzz_kmeans_iter(nat, trial):
     xd = dev(x)
     xsq = nat.kmeans_xsq(xd)
     buf = nat.KmeansBuffers(B, N, K, D, xd.device)
-    c_out = torch.empty_like(dev(c0))
+    c_out = poisoned_like(dev(c0))
     nat.kmeans_iter(xd, xsq, dev(c0), c_out, buf)
     dist = O.kmeans_distances(x, xsq.cpu(), c0)
     lab = buf.labels.cpu().long()

@@ -13,11 +13,9 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def nat():
-    import sys
-    sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "sparse-videogen_amd"))
-    from svg import _native
-    _native.load()
-    return _native
+    from poisoned import load_native
+
+    return load_native()
 
 
 SHAPES = [(1, 37, 512), (2, 129, 1536), (1, 333, 3072), (2, 77, 5120), (1, 50, 8192), (1, 19, 40)]

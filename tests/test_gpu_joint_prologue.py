@@ -5,14 +5,15 @@ import torch
 
 from standins import Attention, Block, Pipe, Transformer
 
+from poisoned import poison_on  # noqa: E402,F401  (the suite runs on poisoned allocations)
+
 pytestmark = pytest.mark.gpu
 
 
 def _nat():
-    from svg import _native
+    from poisoned import load_native
 
-    _native.load()
-    return _native
+    return load_native()
 
 
 def _tables(n, d, kind):

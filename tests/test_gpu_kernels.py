@@ -13,17 +13,16 @@ import pytest
 import torch
 
 from oracle import svg_oracle as O
+from poisoned import poisoned_like
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def nat():
-    from svg import _native
+    from poisoned import load_native
 
-    _native.load()  # raises loudly if the HIP library is missing
-    assert torch.cuda.is_available()
-    return _native
+    return load_native()
 
 
 def dev(t):
@@ -62,7 +61,7 @@ def test_placement_bit_exact(nat, text_first, ctx, D, dtype):
     # reference self-test geometry (svg/models/hyvideo/placement.py:187-221), single tensor
     x = torch.randn(1, 2, 226 + 3 * 4080, 64).to(torch.bfloat16)
     b = torch.tensor([[1, 0]])
-    o = torch.empty_like(x).cuda()
+    o = poisoned_like(x.cuda())
     nat.head_placement([dev(x)], [o], dev(b), 226, 3, 4080, False, False)
     assert torch.equal(o.cpu(), O.head_placement(x, b, 226, 3, 4080))
 
@@ -393,10 +392,10 @@ def test_band_attention_fused_placement(nat, model):
     ref = O.head_placement(refp, best, cl, F_, P_, text_first=tf, inverse=True)
     check_attn(o, ref, torch.bfloat16)
     # and bit-identical to running the materialised pipeline through the same kernels
-    dq, dk, dv = (torch.empty_like(x).cuda() for x in (q, k, v))
+    dq, dk, dv = (poisoned_like(x.cuda()) for x in (q, k, v))
     nat.head_placement([dev(q), dev(k), dev(v)], [dq, dk, dv], dev(best), cl, F_, P_, tf, False)
     om = nat.band_attention(dq, dk, dv, nat.BandMask(**prm))
-    oi = torch.empty_like(om)
+    oi = poisoned_like(om)
     nat.head_placement([om], [oi], dev(best), cl, F_, P_, tf, True)
     assert torch.equal(oi, o)
 
@@ -764,7 +763,7 @@ def test_kmeans_iter(nat, N, K, D):
     xsq = nat.kmeans_xsq(xd)
     torch.testing.assert_close(xsq.cpu(), xsq_ref, rtol=1e-2, atol=0)  # bf16-rounded sums: at most 1 ulp apart
     buf = nat.KmeansBuffers(B, N, K, D, xd.device)
-    c_out = torch.empty_like(dev(c0))
+    c_out = poisoned_like(dev(c0))
     nat.kmeans_iter(xd, xsq, dev(c0), c_out, buf)
     dist = O.kmeans_distances(x, xsq.cpu(), c0)
     lab = buf.labels.cpu().long()

@@ -15,10 +15,9 @@ M16 = 8
 
 @pytest.fixture(scope="module")
 def nat():
-    from svg import _native
+    from poisoned import load_native
 
-    _native.load()
-    return _native
+    return load_native()
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])

@@ -17,10 +17,9 @@ LN2 = math.log(2.0)
 
 @pytest.fixture(scope="module")
 def nat():
-    from svg import _native
+    from poisoned import load_native
 
-    _native.load()
-    return _native
+    return load_native()
 
 
 def rel_l2(a, b):

@@ -8,6 +8,8 @@ import torch
 from oracle import svg_oracle as O
 from standins import Attention, Block, Pipe, Transformer
 
+from poisoned import poison_on  # noqa: E402,F401  (the suite runs on poisoned allocations)
+
 pytestmark = pytest.mark.gpu
 DT = torch.bfloat16
 

@@ -18,11 +18,9 @@ TOL = {torch.float16: (5e-3, 5e-3), torch.bfloat16: (3e-2, 2e-2)}
 
 @pytest.fixture(scope="module")
 def nat():
-    import sys
-    sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "sparse-videogen_amd"))
-    from svg import _native
-    _native.load()
-    return _native
+    from poisoned import load_native
+
+    return load_native()
 
 
 def dev(t):

@@ -21,10 +21,9 @@ BAD = -1
 
 @pytest.fixture(scope="module")
 def nat():
-    from svg import _native
+    from poisoned import load_native
 
-    _native.load()
-    return _native
+    return load_native()
 
 
 def make_case(D, dtype, norm_kind, seed=0):

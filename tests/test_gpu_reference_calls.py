@@ -10,17 +10,16 @@ import pytest
 import torch
 
 from oracle import svg_oracle as O
+from poisoned import poisoned_like
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def nat():
-    import sys
-    sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "sparse-videogen_amd"))
-    from svg import _native
-    _native.load()
-    return _native
+    from poisoned import load_native
+
+    return load_native()
 
 
 @pytest.mark.parametrize("tag", ["as_c", "as_d"])
@@ -42,7 +41,7 @@ def test_euclid_assign_under_the_references_name(nat, tag):
     assert ((d.gather(2, lab[..., None]) - d.gather(2, mine[..., None]))[..., 0][dif].abs() <= 1e-3 * d.abs().max()).all()
     assert (lab != ids.long()).float().mean().item() < 0.2          # the Triton kernel's fp16 norms re-label near-ties
     buf = nat.KmeansBuffers(*x.shape[:2], c.shape[1], x.shape[2], "cuda")
-    nat.kmeans_iter(x.cuda(), None, c.cuda(), torch.empty_like(c).cuda(), buf)
+    nat.kmeans_iter(x.cuda(), None, c.cuda(), poisoned_like(c.cuda()), buf)
     assert torch.equal(buf.labels.cpu().long(), lab), "the half is the whole iteration's assignment"
 
 

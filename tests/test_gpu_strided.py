@@ -18,10 +18,9 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def nat():
-    from svg import _native
+    from poisoned import load_native
 
-    _native.load()
-    return _native
+    return load_native()
 
 
 def _proj_views(B, H, S, D, dtype, fused_qkv, seed):

@@ -14,6 +14,9 @@ import torch.multiprocessing as mp
 from oracle import svg_oracle as O
 
 ROOT = Path(__file__).resolve().parent.parent
+from poisoned import poison_on  # noqa: E402,F401  (the suite runs on poisoned allocations)
+from poisoned import poisoned, poisoned_like
+
 pytestmark = pytest.mark.gpu
 
 
@@ -96,15 +99,15 @@ def test_grouped_loop_bad_arguments():
     B, N, K, D = 4, 512, 8, 64
     x = torch.randn(B, N, D, dtype=torch.bfloat16, device="cuda")
     init = x[:, :K].contiguous()
-    ca, cb, cent = (torch.empty_like(init) for _ in range(3))
-    labels = torch.empty(B, N, dtype=torch.int32, device="cuda")
-    sorted_idx = torch.empty_like(labels)
-    counts = torch.empty(B, K, dtype=torch.int32, device="cuda")
+    ca, cb, cent = (poisoned_like(init) for _ in range(3))
+    labels = poisoned(B, N, dtype=torch.int32)
+    sorted_idx = poisoned_like(labels)
+    counts = poisoned(B, K, dtype=torch.int32)
     n_it = torch.zeros(B, dtype=torch.int32, device="cuda")
     need = lib.svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, 2)
     assert need > 0 and lib.svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, 3) == 0
     assert lib.svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, B) == lib.svg_kmeans_loop_workspace_bytes(B, N, K, D)
-    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    ws = poisoned(need, dtype=torch.uint8)
 
     def call(group, ws_bytes, strided=False):
         ptrs = (init.data_ptr(), ca.data_ptr(), cb.data_ptr(), labels.data_ptr(), counts.data_ptr(), sorted_idx.data_ptr(), cent.data_ptr(),
@@ -497,7 +500,9 @@ def test_wan720p_layer_call_cfg2():
 def _worker(rank, world, port, ret):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     sys.path.insert(0, str(ROOT / "sparse-videogen_amd"))
+    from svg import _native as nat_
     from svg import distributed as sd
+    nat_.poison_allocations(True)   # (a spawned process: the switch of tests/poisoned.py does not reach it)
     from svg.models import _core
 
     dist.init_process_group("gloo", rank=rank, world_size=world)

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from oracle import svg_oracle as O
+from poisoned import poisoned_like
 
 pytestmark = pytest.mark.gpu
 G = Path(__file__).resolve().parent / "golden" / "triton_golden.npz"
@@ -16,11 +17,9 @@ G = Path(__file__).resolve().parent / "golden" / "triton_golden.npz"
 
 @pytest.fixture(scope="module")
 def nat():
-    import sys
-    sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "sparse-videogen_amd"))
-    from svg import _native
-    _native.load()
-    return _native
+    from poisoned import load_native
+
+    return load_native()
 
 
 @pytest.fixture(scope="module")
@@ -97,7 +96,7 @@ def test_kmeans_assignment_against_the_references_triton_kernel(nat, g, tag):
     B, N, D = x.shape
     K = c.shape[1]
     buf = nat.KmeansBuffers(B, N, K, D, "cuda")
-    c_out = torch.empty_like(c).cuda()
+    c_out = poisoned_like(c.cuda())
     nat.kmeans_iter(x.cuda(), None, c.cuda(), c_out, buf)
     lab = buf.labels.cpu().long()
     d = O.kmeans_distances(x, O.kmeans_xsq(x), c)
