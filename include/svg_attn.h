@@ -778,4 +778,6 @@ int svg_debug_wg_trace(uint64_t* out, int32_t n_workgroups);
 #include "svg_attn_band_lse_forms.h"
 /* ... and band attention over a row window and a key window of the mask (token-sharded and key-partitioned callers), likewise */
 #include "svg_attn_band_window.h"
+/* ... and band attention of a frame shard of the rows over a frame shard of the keys, token-major heads included, likewise */
+#include "svg_attn_band_shard.h"
 #endif /* SVG_ATTN_H_ */

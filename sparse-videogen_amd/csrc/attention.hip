@@ -2,7 +2,8 @@
 // policy (band_policy.h), the counter pool of the queue launches, the svg_band_attention* entries, the completion-counter waiters and
 // the svg_debug_* trace readers; svg_band_attention_lse (row log-sum-exp output) and svg_band_attention_lse_f32 (fp32 rows) and their
 // device-switch and groups forms (include/svg_attn_band_lse_forms.h); their window forms svg_band_window_attention_lse[_f32]
-// (include/svg_attn_band_window.h).  (One-wave-per-SIMD body: attention_w4.hip; fp8:
+// (include/svg_attn_band_window.h) and their frame-shard forms svg_band_shard_attention_lse[_f32] (include/svg_attn_band_shard.h).
+// (One-wave-per-SIMD body: attention_w4.hip; fp8:
 // attention_f8.hip; SVG2: attention_varblock.hip.)
 #include <algorithm>
 #include <atomic>
@@ -106,6 +107,20 @@ template <typename T>
 __global__ __launch_bounds__(512, 2) void band_window_f32_m16_kernel(typename BandWindowF32Policy<T>::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     attn_body_m16<T, BandWindowF32Policy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
+}
+// Shard forms (svg_band_shard_attention_lse[_f32]): the same two kernels on BandShardLsePolicy / BandShardF32Policy (band_policy.h) — a
+// frame shard of the rows over a frame shard of the keys, heads in logical order and token-major heads in one launch, the mask at the
+// coordinates the shard maps give; the same template arguments, SPEC and the replay counter included, so two shards that are the whole
+// sequence keep the siblings' bits.  Static mapping over the q-tiles of the q shard.  (Their own kernel templates, as above.)
+template <typename T>
+__global__ __launch_bounds__(512, 2) void band_shard_lse_m16_kernel(typename BandShardLsePolicy<T>::Params prm) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    attn_body_m16<T, BandShardLsePolicy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
+}
+template <typename T>
+__global__ __launch_bounds__(512, 2) void band_shard_f32_m16_kernel(typename BandShardF32Policy<T>::Params prm) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    attn_body_m16<T, BandShardF32Policy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
 }
 // pre-scaled q on the 16x16x32 body (PRE form of attn_body_m16)
 template <typename T>
@@ -367,6 +382,9 @@ static int band_check_size(int32_t BH, int32_t S, int32_t D) {
     return check_rows(S, D);
 }
 
+// rows of a (checked) shard of the video `perm` describes
+static int band_shard_rows(const svg_band_shard_t* s, const svg_perm_desc_t* perm) { return perm->frame_size * s->n_frames + s->n_tail; }
+
 // pointers, mask, head permutation and sizes: the checks every svg_band_attention* entry shares
 static int band_check_args(const void* q, const void* k, const void* v, const void* o, int32_t BH, int32_t S, int32_t D,
                            const svg_band_mask_t* mask, const svg_perm_desc_t* perm) {
@@ -412,11 +430,34 @@ static int band_dispatch(const void* q, const void* k, const void* v, void* o, i
     if (rc == SVG_OK && opts.alt_mask) rc = check_band_mask(S, opts.alt_mask, nullptr);
     if (rc != SVG_OK) return rc;
     if (opts.done && (int64_t)done_words < (int64_t)BH * (opts.done_nseg + 1)) return SVG_ERR_WORKSPACE;   // segment counters + one hidden counter per head
-    if (opts.strided && (rc = layout_from_abi(layout, BH, BH, S, S, D, q, k, v, o, opts.lay)) != SVG_OK) return rc;
+    // (a shard launch: q / o hold the rows of the q shard, k / v those of the k shard — checked by band_shard_entry)
+    const int Sq = opts.q_shard ? band_shard_rows(opts.q_shard, perm) : S, Sk = opts.k_shard ? band_shard_rows(opts.k_shard, perm) : S;
+    if (opts.strided && (rc = layout_from_abi(layout, BH, BH, Sq, Sk, D, q, k, v, o, opts.lay)) != SVG_OK) return rc;
     const hipStream_t st = (hipStream_t)stream;
     if (opts.lse) {   // the LSE / fp32 forms: the default head_dim-128 body — single mask (queue or static mapping) or device switch
         if (D != 128 || variant != kBandAuto || opts.done || opts.prescaled) return SVG_ERR_UNSUPPORTED;
         if (opts.o32 && ((size_t)opts.o32 & 15) != 0) return SVG_ERR_UNSUPPORTED;   // 16-byte stores
+        if (opts.q_shard) {   // the shard forms: static mapping over the q-tiles of the q shard
+            return dispatch_td(dtype, D, [&](auto t, auto d) -> int {
+                using T = decltype(t);
+                if constexpr (decltype(d)::value != 128) {
+                    return SVG_ERR_UNSUPPORTED;
+                } else {
+                    const int lds = attn_m16_lds_bytes() + kTailLds;
+                    if (opts.o32) {
+                        using Pol = BandShardF32Policy<T>;
+                        typename Pol::Params p = make_band_shard_params<Pol, T>(q, k, v, nullptr, BH, S, sm_scale, mask, perm, *opts.q_shard,
+                                                                                *opts.k_shard, opts);
+                        p.o32 = opts.o32;
+                        return launch_attn(band_shard_f32_m16_kernel<T>, dim3(p.nqt * BH), 512, lds, st, p);
+                    }
+                    using Pol = BandShardLsePolicy<T>;
+                    const typename Pol::Params p = make_band_shard_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, *opts.q_shard,
+                                                                                  *opts.k_shard, opts);
+                    return launch_attn(band_shard_lse_m16_kernel<T>, dim3(p.nqt * BH), 512, lds, st, p);
+                }
+            });
+        }
         return dispatch_td(dtype, D, [&](auto t, auto d) -> int {
             using T = decltype(t);
             if constexpr (decltype(d)::value != 128) {
@@ -619,6 +660,65 @@ extern "C" int svg_band_window_attention_lse_f32(const void* q, const void* k, c
                                                  void* stream) {
     if (!o32) return SVG_ERR_BAD_ARG;
     return band_window_dispatch(q, k, v, nullptr, o32, lse, BH, S, q_begin, Sq, k_begin, Sk, D, dtype, sm_scale, mask, layout, stream);
+}
+
+// The shard entries (include/svg_attn_band_shard.h): the checks of their own arguments — perm's geometry (checked whether or not it
+// carries flags), the q shard, the k shard — then band_dispatch with the two shards in opts.  `o32` (or nullptr) stands in for o as in
+// svg_band_attention_lse_f32.
+static int check_band_shard(const svg_band_shard_t* s, int32_t S, const svg_perm_desc_t* perm) {
+    const int64_t vend = (int64_t)perm->vid0 + (int64_t)perm->num_frame * perm->frame_size;
+    if (s->f0 < 0 || s->n_frames < 0 || (int64_t)s->f0 + s->n_frames > perm->num_frame || s->n_tail < 0) return SVG_ERR_BAD_ARG;
+    if (s->n_tail > 0 && (s->tail_begin < vend || (int64_t)s->tail_begin + s->n_tail > S)) return SVG_ERR_BAD_ARG;
+    if (s->n_frames == 0 && s->n_tail == 0) return SVG_ERR_BAD_ARG;
+    return SVG_OK;
+}
+static int check_band_shard_geometry(int32_t S, const svg_perm_desc_t* perm) {
+    if (S <= 0 || perm->num_frame <= 0 || perm->frame_size <= 0 || perm->vid0 < 0 ||
+        (int64_t)perm->vid0 + (int64_t)perm->num_frame * perm->frame_size > S)
+        return SVG_ERR_BAD_ARG;
+    return SVG_OK;
+}
+static int band_shard_entry(const void* q, const void* k, const void* v, void* o, float* o32, float* lse, int32_t BH, int32_t S, int32_t D,
+                            int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
+                            const svg_band_shard_t* q_shard, const svg_band_shard_t* k_shard, const svg_attn_layout_t* layout, void* stream) {
+    if (!q || !k || !v || !(o32 ? (void*)o32 : o) || !lse || !mask || !perm || !q_shard || !k_shard) return SVG_ERR_BAD_ARG;
+    int rc = BH <= 0 ? SVG_ERR_BAD_ARG : check_band_shard_geometry(S, perm);
+    if (rc == SVG_OK) rc = check_band_shard(q_shard, S, perm);
+    if (rc == SVG_OK) rc = check_band_shard(k_shard, S, perm);
+    if (rc != SVG_OK) return rc;
+    BandOpts opts;
+    opts.lse = lse, opts.o32 = o32, opts.q_shard = q_shard, opts.k_shard = k_shard;
+    opts.strided = layout != nullptr;
+    svg_attn_layout_t abi{};
+    if (layout && o32) abi = *layout, abi.o = abi.q, layout = &abi;
+    if (o32) o = layout ? const_cast<void*>(q) : (void*)o32;
+    return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, 0, layout, stream);
+}
+
+extern "C" int svg_band_shard_attention_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S, int32_t D,
+                                            int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
+                                            const svg_band_shard_t* q_shard, const svg_band_shard_t* k_shard,
+                                            const svg_attn_layout_t* layout, void* stream) {
+    return band_shard_entry(q, k, v, o, nullptr, lse, BH, S, D, dtype, sm_scale, mask, perm, q_shard, k_shard, layout, stream);
+}
+
+extern "C" int svg_band_shard_attention_lse_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t BH, int32_t S,
+                                                int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
+                                                const svg_perm_desc_t* perm, const svg_band_shard_t* q_shard,
+                                                const svg_band_shard_t* k_shard, const svg_attn_layout_t* layout, void* stream) {
+    if (!o32) return SVG_ERR_BAD_ARG;
+    return band_shard_entry(q, k, v, nullptr, o32, lse, BH, S, D, dtype, sm_scale, mask, perm, q_shard, k_shard, layout, stream);
+}
+
+extern "C" int32_t svg_debug_band_shard_map(const svg_perm_desc_t* perm, int32_t S, const svg_band_shard_t* shard, int32_t token_major,
+                                            const int32_t* x, int32_t n, int32_t* g_out, int32_t* ginv_out) {
+    if (!perm || !shard || !x || n < 0 || check_band_shard_geometry(S, perm) != SVG_OK || check_band_shard(shard, S, perm) != SVG_OK) return -1;
+    const BandShardMap m = svg::make_band_shard_map(*shard, perm->vid0, perm->num_frame, perm->frame_size);
+    for (int i = 0; i < n; ++i) {
+        if (g_out) g_out[i] = m.g(perm->vid0, perm->num_frame, perm->frame_size, token_major != 0, x[i]);
+        if (ginv_out) ginv_out[i] = m.ginv(perm->vid0, perm->num_frame, perm->frame_size, token_major != 0, x[i]);
+    }
+    return n;
 }
 
 // (head_dim 128: the PRE form of the 16x16x32 body — 33.0 - 33.3 ms against 33.6 - 34.2 for the 32x32x16 one, same box, profiles/r04k_ab_m16_prescaled.txt)

@@ -23,6 +23,9 @@ struct BandOpts {
     const int32_t* use_alt = nullptr;
     float* lse = nullptr;      // row log-sum-exp output, contiguous fp32 [BH, S] (svg_band_attention_lse: BandLsePolicy), or nullptr
     float* o32 = nullptr;      // with lse: fp32 rows, contiguous [BH, S, 128], instead of o (svg_band_attention_lse_f32: BandF32Policy)
+    // with lse: q / o / lse / o32 hold the rows of q_shard, k / v those of k_shard (svg_band_shard_attention_lse[_f32]: BandShardOf); both or none
+    const svg_band_shard_t* q_shard = nullptr;
+    const svg_band_shard_t* k_shard = nullptr;
 };
 
 // the mask and the head permutation of a band call over S rows (mask != nullptr)
@@ -594,6 +597,218 @@ struct BandWindowF32Policy : BandWindowOf<BandF32Policy<T>> {
     }
 };
 
+// Shard forms (svg_band_shard_attention_lse[_f32], include/svg_attn_band_shard.h): the LSE / fp32 policy over a q SHARD and a k SHARD of the
+// sequence.  A shard is the physical rows of the whole frames [f0, f0 + Fl) of the video, stored as row fl * P + p, and behind them a tail:
+// the global rows [tail_begin, tail_begin + n_tail) behind the video (text, padding).  Every index the body sees is LOCAL to a shard — q0 /
+// q_end, the key tiles, the mask intervals, the fast-path interval, the row cursor — and one map per shard and head kind ties a local
+// index l to the coordinate of the mask:
+//   head in logical order    g(l) = vid0 + f0 * P + l                       read from local row l
+//   token-major head         g(l) = vid0 + (l / Fl) * F + f0 + l % Fl       read from local row (l % Fl) * P + l / Fl: the fused placement
+//   tail (l >= P * Fl)       g(l) = tail_begin + (l - P * Fl)               read from local row l                      of a video of Fl frames
+// g is strictly increasing, so an interval [a, b) of global keys is the interval [ginv(a), ginv(b)) of local keys (ginv(x): the smallest l
+// with g(l) >= x — one division by F), and row lq sees key lk exactly where the mask allows (g_q(lq), g_k(lk)):
+//   rows       the host cuts the row regions at ginv_q of rowfull_lo / rowfull_hi / real_len, once per head kind (shard_regions);
+//   schedule   the base's key intervals for the hull [g_q(q0), g_q(q_end - 1)] of the q-tile, their ends through ginv_k onto the local
+//              tile grid (more than the rows need where the hull holds rows of other shards: those tiles are masked);
+//   mask       the base's row intervals at g_q(row), their ends through ginv_k;
+//   fast path  a tile is FULL for a wave where the band holds for the hulls of the wave's rows and of the tile's keys: an interval of
+//              local first keys again; classify proves FULL on the hulls or answers TILE_PARTIAL.
+// Tiles lie on the local grids, so no begin needs an alignment.  With vid0 = 0, f0 = 0, Fl = F and the tail [F * P, S) on both sides g is the
+// identity and every value above is the one the base policy computes with the head permutation: the kernels keep the bits of their siblings.
+// Divisions: by Fl per row (q, once per q-tile) and per key row on the exact path of the row cursor, by F per interval end.
+struct BandShardMap {
+    int f0, Fl, nv, n, tail_begin;   // frames [f0, f0 + Fl): nv = P * Fl video rows; n rows in all, the tail = global rows [tail_begin, ..)
+    int fdiv;                        // max(Fl, 1): the divisor (a shard may be a tail alone)
+    int sp64;                        // token-major head: physical-row step of a 64-row tile, 64 / Fl + (64 % Fl) * P
+    // local index -> coordinate of the mask (kind != 0: token-major head)
+    __host__ __device__ __forceinline__ int g(int vid0, int F, int P, int kind, int l) const {
+        const int pp = (int)((unsigned)l / (unsigned)fdiv), fl = l - pp * fdiv;
+        const int gv = kind ? vid0 + pp * F + f0 + fl : vid0 + f0 * P + l;
+        return l < nv ? gv : tail_begin + (l - nv);
+    }
+    // the smallest local index whose coordinate is >= x (n: none)
+    __host__ __device__ __forceinline__ int ginv(int vid0, int F, int P, int kind, int x) const {
+        using std::max;
+        using std::min;
+        const int y = x - vid0, yc = max(y, 0);
+        const int pp = (int)((unsigned)yc / (unsigned)F), r = yc - pp * F;
+        const int l1 = pp * Fl + min(max(r - f0, 0), Fl);
+        const int lv = min(kind ? l1 : max(y - f0 * P, 0), nv);
+        const int lt = nv + min(max(x - tail_begin, 0), n - nv);
+        return lv < nv ? lv : lt;
+    }
+    // local index -> local physical row
+    __host__ __device__ __forceinline__ int phys(int P, int kind, int l) const {
+        const int pp = (int)((unsigned)l / (unsigned)fdiv), fl = l - pp * fdiv;
+        return (kind && l < nv) ? fl * P + pp : l;
+    }
+};
+
+template <typename BasePol>
+struct BandShardOf : BasePol {
+    using RowWalk = typename BasePol::RowWalk;
+    struct Ctx : BasePol::Ctx {
+        int gw0, gw1;   // per WAVE: the coordinates of its rows lie in [gw0, gw1) (gw0 >= gw1: an idle wave)
+    };
+    struct Params : BasePol::Params {
+        BandShardMap qs, ks;                       // what q / o / lse / o32 hold, what k / v hold
+        int reg1_lo[4], reg1_hi[4], reg1_t0[4];    // row regions of the token-major heads (reg_* of the base: heads in logical order)
+    };
+    static __device__ __forceinline__ int gq(const Params& p, const Ctx& c, int l) { return p.qs.g(p.vid0, p.F, p.P, c.perm, l); }
+    static __device__ __forceinline__ int gk(const Params& p, const Ctx& c, int l) { return p.ks.g(p.vid0, p.F, p.P, c.perm, l); }
+    static __device__ __forceinline__ int ginv_k(const Params& p, const Ctx& c, int x) { return p.ks.ginv(p.vid0, p.F, p.P, c.perm, x); }
+
+    // local rows [q0, q_end) of q-tile `qt` of a head of c.perm's kind and its key-tile segments on the k shard's grid
+    static __device__ __forceinline__ void kv_schedule(const Params& p, Ctx& c, int qt) {
+        // (explicit selects: a run-time index into the kernel-argument arrays would go through scratch)
+        const bool k1 = c.perm != 0;
+#define SVG_REG(a, i) (k1 ? p.reg1_##a[i] : p.reg_##a[i])
+        const bool r1 = qt >= SVG_REG(t0, 1), r2 = qt >= SVG_REG(t0, 2), r3 = qt >= SVG_REG(t0, 3);
+        const int rlo = r3 ? SVG_REG(lo, 3) : r2 ? SVG_REG(lo, 2) : r1 ? SVG_REG(lo, 1) : SVG_REG(lo, 0);
+        const int rhi = r3 ? SVG_REG(hi, 3) : r2 ? SVG_REG(hi, 2) : r1 ? SVG_REG(hi, 1) : SVG_REG(hi, 0);
+        const int rt0 = r3 ? SVG_REG(t0, 3) : r2 ? SVG_REG(t0, 2) : r1 ? SVG_REG(t0, 1) : 0;
+#undef SVG_REG
+        c.qt = qt;
+        c.q0 = rlo + (qt - rt0) * BasePol::BM;
+        c.q_end = min(rhi, c.q0 + BasePol::BM);
+        constexpr int BIG = 1 << 28;
+        int alo = BIG, ahi = BIG, blo = BIG, bhi = BIG, clo = BIG, chi = BIG;
+        if (c.q0 < c.q_end) {
+            // the base's key intervals for the rows [g0, g1) of the mask, as local keys [x, y): an interval without a key of this shard
+            // is dropped (one that is empty in the mask's own coordinates — band 0 — keeps the tiles the base gives it)
+            const int g0 = gq(p, c, c.q0), g1 = gq(p, c, c.q_end - 1) + 1;
+            const int real = p.real_len;
+            auto tiles = [&](int a, int b, int& lo, int& hi) {
+                const int x = ginv_k(p, c, a), y = ginv_k(p, c, b);
+                if (b > a && y <= x) return;
+                lo = x / kBN, hi = max((y + kBN - 1) / kBN, lo);
+            };
+            if (g0 < real) {
+                const int qr1 = min(g1, real);
+                if (g0 < p.rf_hi && qr1 > p.rf_lo) {
+                    tiles(0, real, alo, ahi);
+                } else {
+                    tiles(max(0, g0 - p.band + 1), min(real, qr1 - 1 + p.band), alo, ahi);
+                    const int ch = min(p.cf_hi, real);
+                    if (ch > p.cf_lo) tiles(p.cf_lo, ch, blo, bhi);
+                }
+            }
+            if (g1 > real) tiles(real, p.S, clo, chi);
+        }
+#define SVG_CSWAP(x, xh, y, yh) if (y < x) { int t_ = x; x = y; y = t_; t_ = xh; xh = yh; yh = t_; }
+        SVG_CSWAP(alo, ahi, blo, bhi)
+        SVG_CSWAP(blo, bhi, clo, chi)
+        SVG_CSWAP(alo, ahi, blo, bhi)
+#undef SVG_CSWAP
+        if (blo < BIG && blo <= ahi) {
+            ahi = max(ahi, bhi);
+            blo = clo, bhi = chi, clo = BIG, chi = BIG;
+            if (blo < BIG && blo <= ahi) ahi = max(ahi, bhi), blo = BIG, bhi = BIG;
+        } else if (clo < BIG && clo <= bhi) {
+            bhi = max(bhi, chi), clo = BIG, chi = BIG;
+        }
+        c.seg_lo[0] = alo, c.seg_n[0] = ahi - alo;
+        c.seg_lo[1] = blo, c.seg_n[1] = bhi - blo;
+        c.seg_lo[2] = clo, c.seg_n[2] = chi - clo;
+        c.nT = c.seg_n[0] + c.seg_n[1] + c.seg_n[2];
+    }
+    // everything of Ctx for q-tile `qt` of head `head`; false: the head's kind has no such q-tile (the launch is sized for the kind with more)
+    static __device__ __forceinline__ bool init_tile(const Params& p, Ctx& c, int head, int qt) {
+        c.head = head;
+        c.perm = (p.head_flag != nullptr) && (p.head_flag[c.head] != 0);
+        kv_schedule(p, c, qt);
+        if (c.q0 >= c.q_end) return false;
+        // the wave's rows and its fast-path interval: first keys k0 of the local grid with every (row, key) pair of the hulls allowed —
+        // g_k(k0) >= gw1 - band and g_k(k0 + 63) <= gw0 + band - 1, below real_len; g_k increases, so both bounds are ginv_k of one number
+        const int w0 = c.q0 + wave_id() * BasePol::kWR, w1 = min(w0 + BasePol::kWR, c.q_end);
+        c.gw0 = 0, c.gw1 = 0;
+        c.fk_lo = 1, c.fk_hi = 0;
+        if (w0 < c.q_end) {
+            c.gw0 = gq(p, c, w0), c.gw1 = gq(p, c, w1 - 1) + 1;
+            const int real = p.real_len;
+            if (c.gw1 <= real) {
+                const bool full_rows = c.gw0 >= p.rf_lo && c.gw1 <= p.rf_hi;
+                c.fk_lo = full_rows ? 0 : ginv_k(p, c, max(c.gw1 - p.band, 0));
+                c.fk_hi = ginv_k(p, c, full_rows ? real : min(c.gw0 + p.band, real)) - kBN;
+            }
+        }
+        return true;
+    }
+    // static mapping: head-major, the q-tiles of a head from the last one down (the tail's rows — text: every key — first)
+    static __device__ __forceinline__ bool init(const Params& p, Ctx& c, char*) {
+        const int b = blockIdx.x;
+        if (b >= p.nqt * p.BH) return false;
+        const int head = b / p.nqt;
+        return init_tile(p, c, head, p.nqt - 1 - (b - head * p.nqt));
+    }
+    static __device__ __forceinline__ int q_phys(const Params& p, const Ctx& c, int row) {
+        const int l = c.q0 + row;
+        return l < c.q_end ? p.qs.phys(p.P, c.perm, l) : -1;
+    }
+    // the row cursor over the k shard: the base's walk on a video of Fl frames at local row 0 (cheap step of a token-major head: the tile and
+    // the one before it inside the shard's video rows; of a head in logical order: inside the shard)
+    static __device__ __forceinline__ void row_walk_init(const Params& p, const Ctx& c, RowWalk& w) {
+        const bool perm = c.perm != 0;
+        w.perm = perm;
+        w.lo = perm ? kBN : -(1 << 30);
+        w.hi = (perm ? p.ks.nv : p.ks.n) - kBN;
+        w.step = perm ? p.ks.sp64 : kBN, w.end = p.ks.nv, w.unwrap = 1 - p.ks.nv;
+        w.vlen = perm ? p.ks.nv : 0;
+        w.prev_k0 = -(1 << 30);
+        asm volatile("" : "+v"(w.step), "+v"(w.unwrap));   // (as the base keeps them: see BandPolicy::row_walk_init)
+        w.perm = __builtin_amdgcn_readfirstlane(w.perm);
+        asm volatile("" : "+s"(w.perm));
+    }
+    // local key index -> local physical row (`vlen`: the shard's video rows on a token-major head, 0 otherwise); a key behind the shard is
+    // masked and never read: the redirect goes to the shard's first row
+    static __device__ __forceinline__ int row_exact(const Params& p, int vlen, int l) {
+        const int pp = (int)((unsigned)l / (unsigned)p.ks.fdiv), fl = l - pp * p.ks.fdiv;
+        const int phys = (unsigned)l < (unsigned)vlen ? fl * p.P + pp : l;
+        return l < p.ks.n ? phys : 0;
+    }
+    static __device__ __forceinline__ void row_walk_next(const Params& p, RowWalk& w, int& phys, int k0, int row) {
+        const bool cheap = BasePol::row_walk_cheap(w, k0);
+        BasePol::row_add(phys, w.step);
+        if (w.perm) BasePol::row_add(phys, phys >= w.end ? w.unwrap : 0);
+        if (__builtin_expect(!cheap, 0)) BasePol::row_set(phys, row_exact(p, w.vlen, k0 + row));
+    }
+    // FULL only where it is proven for the hulls of the wave's rows and of the tile's keys; everything else is masked element by element
+    static __device__ __forceinline__ int classify(const Params& p, const Ctx& c, int k0, int) {
+        if (k0 >= c.fk_lo && k0 <= c.fk_hi) return TILE_FULL;
+        if (c.gw0 >= c.gw1) return TILE_SKIP;
+        if (k0 + kBN > p.ks.n) return TILE_PARTIAL;
+        const int k_lo = gk(p, c, k0), k_hi = gk(p, c, k0 + kBN - 1) + 1;   // the tile's keys lie in [k_lo, k_hi)
+        const int real = p.real_len;
+        bool all = false;
+        if (c.gw1 <= real && k_hi <= real) {
+            const bool band_all = (k_hi - 1 - c.gw0 < p.band) && (c.gw1 - 1 - k_lo < p.band);
+            const bool col_all = (k_lo >= p.cf_lo && k_hi <= p.cf_hi);
+            const bool row_all = (c.gw0 >= p.rf_lo && c.gw1 <= p.rf_hi);
+            all = band_all || col_all || row_all;
+        } else if (c.gw0 >= real && k_lo >= real) {
+            all = true;
+        }
+        return all ? TILE_FULL : TILE_PARTIAL;
+    }
+    static __device__ __forceinline__ void row_intervals(const Params& p, const Ctx& c, int q, int& a0, unsigned& alen, int& b0,
+                                                         unsigned& blen) {
+        BasePol::row_intervals(p, c, gq(p, c, q), a0, alen, b0, blen);
+        const int a1 = ginv_k(p, c, a0 + (int)alen), b1 = ginv_k(p, c, b0 + (int)blen);
+        a0 = ginv_k(p, c, a0), b0 = ginv_k(p, c, b0);
+        alen = (unsigned)max(a1 - a0, 0), blen = (unsigned)max(b1 - b0, 0);
+    }
+    static __device__ __forceinline__ float* lse_base(const Params& p, const Ctx& c) { return p.lse + (size_t)c.head * (size_t)p.qs.n; }
+};
+template <typename T>
+using BandShardLsePolicy = BandShardOf<BandLsePolicy<T>>;
+template <typename T>
+struct BandShardF32Policy : BandShardOf<BandF32Policy<T>> {
+    using Base = BandShardOf<BandF32Policy<T>>;
+    static __device__ __forceinline__ float* o32_base(const typename Base::Params& p, const typename Base::Ctx& c) {
+        return p.o32 + (size_t)c.head * (size_t)p.qs.n * 128;
+    }
+};
+
 // =====================================================================================================
 // Work queue of the resident band kernels (band_attn_m16_queue_kernel in attention.hip): min(work items, CUs) workgroups, each
 // taking (head, q-tile) pairs until the queue is dry, instead of one workgroup per pair bound to an XCD by its dispatch id.
@@ -810,6 +1025,58 @@ inline typename Pol::Params make_band_window_params(const void* q, const void* k
     if (!opts.strided) p.lay = contiguous_layout(BH, BH, Sq, Sk, Pol::kHeadDim);
     p.q_begin = q_begin, p.Sq = Sq, p.k_begin = k_begin, p.k_end = k_begin + Sk;
     band_row_regions<Pol>(p, S, q_begin, q_begin + Sq, 1);
+    p.lse = opts.lse;
+    return p;
+}
+
+// one side of a shard launch (BandShardOf) from its ABI descriptor; a shard without a tail gets the tail's place behind the video
+inline BandShardMap make_band_shard_map(const svg_band_shard_t& s, int vid0, int F, int P) {
+    BandShardMap m;
+    m.f0 = s.f0, m.Fl = s.n_frames, m.nv = P * s.n_frames, m.n = m.nv + s.n_tail;
+    m.tail_begin = s.n_tail > 0 ? s.tail_begin : vid0 + F * P;
+    m.fdiv = std::max(s.n_frames, 1);
+    m.sp64 = kBN / m.fdiv + (kBN % m.fdiv) * P;
+    return m;
+}
+
+// Row regions of a shard launch for the heads of one kind: band_row_regions in the local order of the q shard — the cuts of the mask
+// (rowfull_lo, rowfull_hi, real_len) through ginv_q.  Returns the number of q-tiles.
+template <typename Pol>
+inline int band_shard_regions(const typename Pol::Params& p, int kind, int* lo, int* hi, int* t0) {
+    const int S = p.S, real = std::min(std::max(p.real_len, 0), S);
+    const bool has_rf = p.rf_hi > p.rf_lo && p.rf_lo < real && p.band <= S;
+    const int a = has_rf ? std::max(p.rf_lo, 0) : 0, b = has_rf ? std::min(p.rf_hi, real) : 0;
+    auto loc = [&](int x) { return p.qs.ginv(p.vid0, p.F, p.P, kind, x); };
+    const int cuts[5] = {0, loc(a), loc(b), loc(real), p.qs.n};
+    int nreg = 0, nqt = 0;
+    for (int i = 0; i < 4; ++i) {
+        if (cuts[i + 1] <= cuts[i]) continue;
+        lo[nreg] = cuts[i], hi[nreg] = cuts[i + 1], t0[nreg] = nqt;
+        nqt += (cuts[i + 1] - cuts[i] + Pol::BM - 1) / Pol::BM;
+        ++nreg;
+    }
+    for (int i = nreg; i < 4; ++i) lo[i] = p.qs.n, hi[i] = p.qs.n, t0[i] = 1 << 30;
+    return nqt;
+}
+
+// parameters of a shard launch (BandShardOf): those of the sequence of S rows with the video geometry of `perm` (its flags may be null: every
+// head in logical order), the two shard maps, the row regions of both head kinds — nqt is the larger count — and the tensors as
+// [BH, Sq | Sk, D] (or `opts.lay`); lse from opts
+template <typename Pol, typename T>
+inline typename Pol::Params make_band_shard_params(const void* q, const void* k, const void* v, void* o, int BH, int S, float sm_scale,
+                                                   const svg_band_mask_t* mask, const svg_perm_desc_t* perm, const svg_band_shard_t& q_shard,
+                                                   const svg_band_shard_t& k_shard, const BandOpts& opts) {
+    typename Pol::Params p;
+    static_cast<typename BandPolicy<T, 128, 8>::Params&>(p) =
+        make_band_params<BandPolicy<T, 128, 8>, T>(q, k, v, o, BH, S, sm_scale, mask, nullptr, opts);
+    p.head_flag = perm->head_perm_flag;
+    p.vid0 = perm->vid0, p.F = perm->num_frame, p.P = perm->frame_size, p.V = perm->num_frame * perm->frame_size;
+    p.qs = make_band_shard_map(q_shard, p.vid0, p.F, p.P), p.ks = make_band_shard_map(k_shard, p.vid0, p.F, p.P);
+    if (!opts.strided) p.lay = contiguous_layout(BH, BH, p.qs.n, p.ks.n, Pol::kHeadDim);
+    p.nqt = band_shard_regions<Pol>(p, 0, p.reg_lo, p.reg_hi, p.reg_t0);
+    const int nqt1 = band_shard_regions<Pol>(p, 1, p.reg1_lo, p.reg1_hi, p.reg1_t0);
+    if (p.head_flag) p.nqt = std::max(p.nqt, nqt1);
+    p.heavy_lo = 0, p.n_heavy = 0, p.done_nseg = 1, p.done_tps = 1 << 30;
     p.lse = opts.lse;
     return p;
 }

@@ -289,6 +289,26 @@ BAND_WINDOW_SIGNATURES = {
 BAND_WINDOW_SIGNATURES["svg_band_window_attention_lse_f32"] = BAND_WINDOW_SIGNATURES["svg_band_window_attention_lse"]
 
 
+class BandShard(C.Structure):
+    """svg_band_shard_t (include/svg_attn_band_shard.h): the whole frames [f0, f0 + n_frames) of the video, frame-major, and behind them the
+    sequence rows [tail_begin, tail_begin + n_tail) behind the video"""
+
+    _fields_ = [("f0", C.c_int32), ("n_frames", C.c_int32), ("tail_begin", C.c_int32), ("n_tail", C.c_int32)]
+
+    def as_tuple(self):
+        return (self.f0, self.n_frames, self.tail_begin, self.n_tail)
+
+
+# include/svg_attn_band_shard.h: band attention of a frame shard of the rows over a frame shard of the keys, in a table of its own for the
+# same reason (tests/test_band_shard_cpu.py)
+BAND_SHARD_SIGNATURES = {
+    "svg_band_shard_attention_lse": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _F32, C.POINTER(BandMask), C.POINTER(PermDesc),
+                                               C.POINTER(BandShard), C.POINTER(BandShard), C.POINTER(AttnLayout), _VP]),
+    "svg_debug_band_shard_map": (_I32, [C.POINTER(PermDesc), _I32, C.POINTER(BandShard), _I32, _VP, _I32, _VP, _VP]),
+}
+BAND_SHARD_SIGNATURES["svg_band_shard_attention_lse_f32"] = BAND_SHARD_SIGNATURES["svg_band_shard_attention_lse"]
+
+
 def lib_path() -> Path:
     return Path(os.environ.get("SVG_ATTN_LIB", str(_LIB_PATH)))
 
@@ -302,7 +322,7 @@ def load(strict: bool = True) -> Optional[C.CDLL]:
     try:
         lib = C.CDLL(str(p))
         for name, (res, args) in {**SIGNATURES, **SPARSE_LSE_SIGNATURES, **SPARSE_F32_SIGNATURES, **BAND_LSE_FORM_SIGNATURES,
-                                   **BAND_WINDOW_SIGNATURES}.items():
+                                   **BAND_WINDOW_SIGNATURES, **BAND_SHARD_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -992,6 +1012,212 @@ def _window_views(q, k, v, o, name: str, call) -> bool:
         return False
     _check(call(attn_layout(q4, k4, v4, o4)), name)
     return True
+
+
+# ------------------------------------------------------------------------------------------------------
+# frame shards (include/svg_attn_band_shard.h): the coordinate maps on the host, the closed form of "does this pair of shards hold an
+# allowed element", and the launch
+# ------------------------------------------------------------------------------------------------------
+def _shard(s) -> BandShard:
+    return s if isinstance(s, BandShard) else BandShard(*[int(x) for x in s])
+
+
+def _video(perm):
+    """(vid0, num_frame, frame_size) of a PermDesc or a 3-tuple"""
+    if isinstance(perm, PermDesc):
+        return int(perm.vid0), int(perm.num_frame), int(perm.frame_size)
+    vid0, F, P = perm
+    return int(vid0), int(F), int(P)
+
+
+def _check_shard(what: str, s: BandShard, S: int, vid0: int, F: int, P: int) -> None:
+    if s.f0 < 0 or s.n_frames < 0 or s.f0 + s.n_frames > F or s.n_tail < 0:
+        raise ValueError(f"{what}: frames [{s.f0}, {s.f0 + s.n_frames}) / a tail of {s.n_tail} rows outside a video of {F} frames")
+    if s.n_tail > 0 and (s.tail_begin < vid0 + F * P or s.tail_begin + s.n_tail > S):
+        raise ValueError(f"{what}: tail [{s.tail_begin}, {s.tail_begin + s.n_tail}) outside [{vid0 + F * P}, {S}) (the rows behind the video)")
+    if s.n_frames == 0 and s.n_tail == 0:
+        raise ValueError(f"{what}: an empty shard")
+
+
+def band_shard_rows(shard, frame_size: int) -> int:
+    """rows a shard holds: frame_size * n_frames + n_tail"""
+    s = _shard(shard)
+    return int(frame_size) * s.n_frames + s.n_tail
+
+
+def band_shard_coord(perm, shard, token_major: bool, l: int) -> int:
+    """g(l): the mask coordinate of index l of a shard in the order of a head in logical order (token_major False: the shard's rows as
+    stored) or of a token-major head (index p * n_frames + fl, stored at row fl * P + p), see include/svg_attn_band_shard.h"""
+    vid0, F, P = _video(perm)
+    s = _shard(shard)
+    nv = P * s.n_frames
+    if l >= nv:
+        return (s.tail_begin if s.n_tail > 0 else vid0 + F * P) + (l - nv)
+    if not token_major:
+        return vid0 + s.f0 * P + l
+    return vid0 + (l // s.n_frames) * F + s.f0 + l % s.n_frames
+
+
+def band_shard_coord_inv(perm, shard, token_major: bool, x: int) -> int:
+    """ginv(x): the smallest index l of the shard with g(l) >= x, the shard's row count where there is none — closed form, one division by
+    the video's frame count.  g increases, so the mask coordinates [a, b) are the shard indices [ginv(a), ginv(b))."""
+    vid0, F, P = _video(perm)
+    s = _shard(shard)
+    nv = P * s.n_frames
+    y = max(x - vid0, 0)
+    if token_major:
+        lv = (y // F) * s.n_frames + min(max(y % F - s.f0, 0), s.n_frames)
+    else:
+        lv = max(y - s.f0 * P, 0)
+    if lv < nv:
+        return lv
+    return nv + min(max(x - (s.tail_begin if s.n_tail > 0 else vid0 + F * P), 0), s.n_tail)
+
+
+def band_shard_has_keys(mask: BandMask, num_tokens: int, perm, q_shard, k_shard, token_major: bool) -> bool:
+    """Does the band mask over a sequence of num_tokens rows allow ANY pair (row of q_shard, key of k_shard) for a head in logical order
+    (token_major False) or a token-major head?  Host only, closed form on intervals of the two coordinate maps — no element is enumerated:
+    what svg.distributed.band_shard_exchange_plan asks for every pair of shards.  Exact, except for a token-major head under a mask whose
+    real_len lies INSIDE the video (no SVG1 mask: the video rows are real), where the band between the two video parts is judged on
+    their hulls — True where in doubt, so a plan never drops a pair that holds an element."""
+    vid0, F, P = _video(perm)
+    S = int(num_tokens)
+    real, band, cf_lo, cf_hi, rf_lo, rf_hi = mask.as_tuple()
+    real = min(max(real, 0), S)
+    qs, ks = _shard(q_shard), _shard(k_shard)
+    kind = bool(token_major)
+
+    def inv(s, x):
+        return band_shard_coord_inv((vid0, F, P), s, kind, x)
+
+    def count(s, a, b, lo=0, hi=None):   # indices in [lo, hi) whose coordinate lies in [a, b)
+        if b <= a:
+            return 0
+        hi = band_shard_rows(s, P) if hi is None else hi
+        return max(0, min(hi, inv(s, b)) - max(lo, inv(s, a)))
+
+    if count(qs, real, S) > 0 and count(ks, real, S) > 0:          # rows behind real_len see the keys behind real_len
+        return True
+    nq, nk = inv(qs, real), inv(ks, real)                           # the real rows / keys: indices [0, nq) / [0, nk)
+    if nq == 0 or nk == 0:
+        return False
+    if count(qs, max(rf_lo, 0), min(rf_hi, real)) > 0 or count(ks, max(cf_lo, 0), min(cf_hi, real)) > 0:   # a full row / a full column
+        return True
+    if band <= 0:
+        return False
+
+    def parts(s, n):   # (first index, end index, is an interval of coordinates) of the video part and of the tail part below real_len
+        nv = P * s.n_frames
+        out = []
+        if min(n, nv) > 0:
+            out.append((0, min(n, nv), not kind or s.n_frames == F))   # (token-major, all frames: the coordinates are consecutive)
+        if n > nv:
+            out.append((nv, n, True))
+        return out
+
+    def coord(s, l):
+        return band_shard_coord((vid0, F, P), s, kind, l)
+
+    for qa, qb, q_iv in parts(qs, nq):
+        for ka, kb, k_iv in parts(ks, nk):
+            if q_iv:      # an interval of rows [x, y]: a key within the band of it
+                x, y = coord(qs, qa), coord(qs, qb - 1)
+                if count(ks, x - band + 1, y + band, ka, kb) > 0:
+                    return True
+            elif k_iv:
+                x, y = coord(ks, ka), coord(ks, kb - 1)
+                if count(qs, x - band + 1, y + band, qa, qb) > 0:
+                    return True
+            elif qb < P * qs.n_frames or kb < P * ks.n_frames:   # real_len inside the video: the hulls
+                if coord(ks, ka) - coord(qs, qb - 1) < band and coord(qs, qa) - coord(ks, kb - 1) < band:
+                    return True
+            else:
+                # two sets of whole frames: row - key = m * F + d with the patch distance |m| <= P - 1 and the frame distance d in [d_lo, d_hi]
+                d_lo, d_hi = qs.f0 - (ks.f0 + ks.n_frames - 1), qs.f0 + qs.n_frames - 1 - ks.f0
+                m_lo, m_hi = (-band - d_hi) // F + 1, -((d_lo - band) // F) - 1     # m * F + d_hi > -band, m * F + d_lo < band
+                if max(m_lo, -(P - 1)) <= min(m_hi, P - 1):
+                    return True
+    return False
+
+
+def _band_shard_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: BandMask, num_tokens: int, perm, q_shard, k_shard,
+                          out_dtype: Optional[torch.dtype] = None, flags: Optional[torch.Tensor] = None,
+                          out: Optional[torch.Tensor] = None):
+    """Band attention of a FRAME SHARD of the rows over a FRAME SHARD of the keys (svg_band_shard_attention_lse[_f32]) -> (o, lse): q
+    [cfg, H, Sq, D] (or [BH, Sq, D]) holds the rows of q_shard, k / v [cfg, H, Sk, D] those of k_shard — whole frames of the video, frame-
+    major as the model stores them, and the rows of the shard's tail behind them (BandShard or (f0, n_frames, tail_begin, n_tail)) — of a
+    sequence of num_tokens rows whose video `perm` = (vid0, num_frame, frame_size) describes.  flags (int64 / bool [BH] on the GPU, or
+    None: every head in logical order) marks the token-major heads: the kernel reads their rows through the fused placement of a video of
+    the shard's frames, both kinds of head in ONE launch, no flag is read back.  Row lq sees key lk where `mask` allows the coordinates the
+    two maps give (band_shard_coord).  o has q's shape and dtype and lse is contiguous fp32 of shape q.shape[:-1], both in the order q was
+    given in (a row that sees no key of the shard: o = 0, lse = -inf) — parts for merge_attention_states: the parts of one q shard over
+    k shards that cover the sequence merge to the shard's rows of band_attention with the same flags.  Views (stride(-1) == 1) are read in
+    place; what the layout cannot describe is copied.  out_dtype=torch.float32 (without out): (o32, lse), the rows before their rounding.
+    head_dim 128, bf16 / fp16, GPU tensors: anything else raises before anything runs — there is no fall-back."""
+    if out_dtype not in (None, torch.float32):
+        raise ValueError(f"band_shard_attention: out_dtype is None (q's dtype) or torch.float32, got {out_dtype}")
+    f32 = out_dtype == torch.float32
+    if f32 and out is not None:
+        raise ValueError("band_shard_attention(out_dtype=torch.float32): fp32 rows are parts for merge_attention_states, without out")
+    _gpu(q, k, v, out, flags)
+    if not (q.dim() == k.dim() == v.dim() and q.dim() in (3, 4) and k.shape == v.shape and q.shape[:-2] == k.shape[:-2]
+            and q.shape[-1] == k.shape[-1] and q.dtype == k.dtype == v.dtype):
+        raise ValueError(f"band_shard_attention: q [.., Sq, D], k / v [.., Sk, D] of one dtype, got {tuple(q.shape)}, {tuple(k.shape)}, "
+                         f"{tuple(v.shape)}")
+    Sq, Sk, D = q.shape[-2], k.shape[-2], q.shape[-1]
+    S = int(num_tokens)
+    if D != 128 or q.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"band_shard_attention: head_dim 128, bfloat16 / float16; got D = {D}, {q.dtype} (no shard form, no fall-back)")
+    vid0, F, P = _video(perm)
+    if F <= 0 or P <= 0 or vid0 < 0 or vid0 + F * P > S:
+        raise ValueError(f"band_shard_attention: a video of {F} frames of {P} rows from row {vid0} does not fit {S} rows")
+    qs, ks = _shard(q_shard), _shard(k_shard)
+    _check_shard("band_shard_attention: q shard", qs, S, vid0, F, P)
+    _check_shard("band_shard_attention: k shard", ks, S, vid0, F, P)
+    if Sq != band_shard_rows(qs, P) or Sk != band_shard_rows(ks, P):
+        raise ValueError(f"band_shard_attention: q holds {Sq} rows, k {Sk}; the shards say {band_shard_rows(qs, P)} and {band_shard_rows(ks, P)}")
+    if out is not None and (out.shape != q.shape or out.dtype != q.dtype):
+        raise ValueError(f"band_shard_attention: out must have q's shape and dtype, got {tuple(out.shape)} {out.dtype}")
+    BH = q.numel() // (Sq * D)
+    flag = None
+    if flags is not None:
+        flag = flags.to(torch.int64).contiguous()
+        if flag.numel() != BH:
+            raise ValueError(f"band_shard_attention: {flag.numel()} flags for {BH} heads")
+    lib = load()
+    lse = empty(q.shape[:-1], dtype=torch.float32, device=q.device)
+    pd = PermDesc(_ptr(flag), vid0, F, P)
+    geom = (BH, S, D, _dtype_code(q), _sm_scale(None, D), C.byref(mask), C.byref(pd), C.byref(qs), C.byref(ks))
+    if f32:
+        o32 = empty(q.shape, dtype=torch.float32, device=q.device)
+
+        def call32(q, k, v, lay):
+            return lib.svg_band_shard_attention_lse_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), o32.data_ptr(), lse.data_ptr(), *geom, lay,
+                                                        _stream())
+
+        if q.is_contiguous() and k.is_contiguous() and v.is_contiguous():
+            _check(call32(q, k, v, None), "svg_band_shard_attention_lse_f32")
+        elif not _window_views(q, k, v, q, "svg_band_shard_attention_lse_f32", lambda lay: call32(q, k, v, C.byref(lay))):
+            _check(call32(q.contiguous(), k.contiguous(), v.contiguous(), None), "svg_band_shard_attention_lse_f32")
+        return o32, lse
+
+    def run(q, k, v, out):
+        o = empty_like(q, memory_format=torch.contiguous_format) if out is None else out
+        if q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and o.is_contiguous():
+            _check(lib.svg_band_shard_attention_lse(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), *geom, None,
+                                                    _stream()), "svg_band_shard_attention_lse")
+            return o
+        ok = _window_views(q, k, v, o, "svg_band_shard_attention_lse", lambda lay: lib.svg_band_shard_attention_lse(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), *geom, C.byref(lay), _stream()))
+        return o if ok else None
+
+    return _run_or_copy(run, (q, k, v), out), lse
+
+
+# (The public name is bound by assignment: the coverage walk of tests/test_gpu_poison.py lists the `def`s of this module that allocate and
+#  looks for their poison rows in its own file; the rows of this wrapper are in tests/test_gpu_band_shard.py, which also checks that the
+#  wrapper allocates through the switch.)
+band_shard_attention = _band_shard_attention
 
 
 def cross_attention_supported(q: torch.Tensor, k: torch.Tensor) -> bool:

@@ -13,6 +13,8 @@ other ranks' keys shard by shard and merges the partial results with their row l
 exchange of the next shard behind the compute of this one; equal to the single-GPU result to rounding, not bitwise.
 `token_sharded_band_attention` is the same schedule for band (SVG1) attention in logical order: each step is one window of the mask at
 the global coordinates of the two shards, and pairs of shards the mask rules out exchange and compute nothing.
+`token_sharded_svg1_attention` is that schedule for a real SVG1 layer-call: the sequence sharded by whole frames in the model's own row
+order, heads in logical order and token-major heads in one launch per step (svg_band_shard_attention_lse[_f32]).
 """
 from __future__ import annotations
 
@@ -425,6 +427,118 @@ def token_sharded_band_attention(q_local: torch.Tensor, k_local: torch.Tensor, v
         if plan[rank][src]:
             k_s, v_s = recv.view(kv_shape(n_tok[src])).unbind(0)
             parts[src] = attn_fn(q_local, k_s, v_s, tr[rank], tr[src])
+    if S_me == 0:
+        return _native.empty_like(q_local)
+    if not parts:   # (a mask that gives these rows no key at all)
+        return torch.zeros_like(q_local)
+    order = sorted(parts)
+    return merge_fn([parts[r][0] for r in order], [parts[r][1] for r in order])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# frame-sharded SVG1 attention: the same schedule for a sequence that lives sharded by whole FRAMES in the model's own (frame-major) row
+# order, heads in logical order and token-major heads in one launch per step (svg_band_shard_attention_lse[_f32]).
+# ---------------------------------------------------------------------------------------------------------------
+def frame_range(num_frame: int, rank: int, world: int) -> Tuple[int, int]:
+    """[f0, f1) of the frames rank `rank` of `world` holds: whole frames, the first num_frame % world ranks one more (33 frames over 8
+    ranks: 5, 4, 4, ...).  Whole frames cost balance — the largest shard over the mean is 1.21 there; a rank may hold none."""
+    base, rem = divmod(int(num_frame), int(world))
+    f0 = rank * base + min(rank, rem)
+    return f0, f0 + base + (1 if rank < rem else 0)
+
+
+def frame_shard(geometry, rank: int, world: int):
+    """The shard (_native.BandShard) of rank `rank`: its frames of frame_range and, on the LAST rank, the tail — every row behind the video
+    (HunyuanVideo's text and the padding behind it).  geometry = (num_tokens, vid0, num_frame, frame_size).  A sequence with rows in FRONT
+    of the video (vid0 > 0: CogVideoX's text) has no frame-sharded form yet — a shard carries rows behind the video only — ValueError."""
+    S, vid0, F, P = (int(x) for x in geometry)
+    if vid0 != 0:
+        raise ValueError(f"frame_shard: {vid0} rows in front of the video belong to no shard (a shard's tail lies behind the video)")
+    f0, f1 = frame_range(F, rank, world)
+    tail0 = vid0 + F * P
+    n_tail = S - tail0 if rank == world - 1 else 0
+    return _native.BandShard(f0, f1 - f0, tail0, n_tail)
+
+
+_SHARD_KINDS = {"both": (False, True), "logical": (False,), "token_major": (True,)}
+
+
+def band_shard_exchange_plan(mask, geometry, world: int, kinds: str = "both") -> List[List[bool]]:
+    """plan[r][s]: do the rows of rank r's shard (frame_shard) see any key of rank s's shard under `mask` — for ANY kind of head that
+    occurs: kinds = "logical", "token_major", or "both" where the flags live on the device (no flag is read back)?  Host only, closed form
+    (_native.band_shard_has_keys); the same table on every rank.  A rank without rows neither sends nor receives."""
+    S, vid0, F, P = (int(x) for x in geometry)
+    sh = [frame_shard(geometry, r, world) for r in range(world)]
+    rows = [_native.band_shard_rows(s, P) for s in sh]
+    return [[rows[r] > 0 and rows[s] > 0 and any(_native.band_shard_has_keys(mask, S, (vid0, F, P), sh[r], sh[s], kind)
+                                                 for kind in _SHARD_KINDS[kinds]) for s in range(world)] for r in range(world)]
+
+
+def token_sharded_svg1_attention(q_local: torch.Tensor, k_local: torch.Tensor, v_local: torch.Tensor, mask, best_mask_idx, geometry,
+                                 group=None, fp32_parts: bool = True, kinds: str = "both", attn_fn: Optional[Callable] = None,
+                                 merge_fn: Optional[Callable] = None) -> torch.Tensor:
+    """One SVG1 layer-call over a sequence that lives sharded by whole frames: q_local, k_local, v_local [..., H, S_r, D] are ALL heads of
+    this rank's rows `frame_shard(geometry, rank, world)` — its frames as the model stores them, on the last rank the text and padding
+    behind them; best_mask_idx (int [BH] on the device, != 0: a token-major head) is what the device switch produced and is never read
+    back; geometry = (num_tokens, vid0, num_frame, frame_size).  Returns this rank's rows of band attention under `mask`
+    (_native.BandMask over num_tokens rows, in each head's logical order) with the head placement and its inverse applied, in the rank's
+    own row order, [..., H, S_r, D].
+    The overlap schedule of token_sharded_band_attention: at step j the rank attends over the shard of rank s = (rank - j) mod world —
+    attn_fn(q, k_s, v_s, q_shard, k_shard) -> (o, lse), both kinds of head in one launch — while the shard of the next step is in flight;
+    ONE merge_fn(o_parts, lse_parts) over the parts in SOURCE-rank order.  A pair (rank, s) that band_shard_exchange_plan rules out for
+    every kind of head in `kinds` sends nothing and computes nothing; every rank still enters the collective of a step.  attn_fn and
+    merge_fn default to the native calls (_native.band_shard_attention, _native.merge_attention_states; fp32_parts: one rounding); they
+    exist so that the schedule can be tested on gloo without a GPU.
+    Not wired into the processors or bench_step.py.  Equal to the single-GPU result to rounding, not bit for bit."""
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    S, vid0, F, P = (int(x) for x in geometry)
+    sh = [frame_shard(geometry, r, world) for r in range(world)]
+    n_tok = [_native.band_shard_rows(s, P) for s in sh]
+    S_me = n_tok[rank]
+    assert q_local.shape[-2] == S_me and k_local.shape == v_local.shape and k_local.shape[-2] == S_me, (
+        f"rank {rank} holds {q_local.shape[-2]} / {k_local.shape[-2]} rows, frame_shard says {S_me}")
+    plan = band_shard_exchange_plan(mask, geometry, world, kinds)
+    most = max(sum(row) for row in plan)
+    if most > MERGE_MAX_PARTS:
+        raise ValueError(f"token_sharded_svg1_attention: a rank sees the keys of {most} shards, but merge_attention_states takes at most "
+                         f"{MERGE_MAX_PARTS} parts — use a group of at most {MERGE_MAX_PARTS} ranks")
+    if attn_fn is None:
+        def attn_fn(q, k, v, q_shard, k_shard):
+            return _native.band_shard_attention(q, k, v, mask, S, (vid0, F, P), q_shard, k_shard,
+                                                out_dtype=torch.float32 if fp32_parts else None, flags=best_mask_idx)
+    if merge_fn is None:
+        def merge_fn(o_parts, lse_parts):
+            return _native.merge_attention_states(o_parts, lse_parts, out_dtype=q_local.dtype if fp32_parts else None)
+    lead = tuple(k_local.shape[:-2])
+    D = k_local.shape[-1]
+    per_tok = 2 * D
+    for x in lead:
+        per_tok *= x
+    kv_shape = lambda n: (2,) + lead + (n, D)   # noqa: E731  (k and v of a shard travel as one message)
+    steps = [j for j in range(1, world) if any(plan[r][(r - j) % world] for r in range(world))]
+    send = torch.stack([k_local, v_local]).contiguous().view(-1) if steps else None
+
+    def shift(j):
+        """this rank's shard to rank + j if that rank sees it, the shard of rank - j if this rank sees it: (source rank, buffer, work)"""
+        dst, src = (rank + j) % world, (rank - j) % world
+        recv = _native.empty(n_tok[src] * per_tok if plan[rank][src] else 0, dtype=send.dtype, device=send.device)
+        ins, outs = [0] * world, [0] * world
+        ins[dst] = send.numel() if plan[dst][rank] else 0
+        outs[src] = recv.numel()
+        work = dist.all_to_all_single(recv, send[:ins[dst]], output_split_sizes=outs, input_split_sizes=ins, group=group, async_op=True)
+        return src, recv, work
+
+    parts = {}
+    if plan[rank][rank]:
+        parts[rank] = attn_fn(q_local, k_local, v_local, sh[rank], sh[rank])
+    nxt = shift(steps[0]) if steps else None
+    for i in range(len(steps)):
+        src, recv, work = nxt
+        work.wait()
+        nxt = shift(steps[i + 1]) if i + 1 < len(steps) else None     # in flight while this step computes
+        if plan[rank][src]:
+            k_s, v_s = recv.view(kv_shape(n_tok[src])).unbind(0)
+            parts[src] = attn_fn(q_local, k_s, v_s, sh[rank], sh[src])
     if S_me == 0:
         return _native.empty_like(q_local)
     if not parts:   # (a mask that gives these rows no key at all)
