@@ -666,11 +666,7 @@ extern "C" int svg_band_window_attention_lse_f32(const void* q, const void* k, c
 // carries flags), the q shard, the k shard — then band_dispatch with the two shards in opts.  `o32` (or nullptr) stands in for o as in
 // svg_band_attention_lse_f32.
 static int check_band_shard(const svg_band_shard_t* s, int32_t S, const svg_perm_desc_t* perm) {
-    const int64_t vend = (int64_t)perm->vid0 + (int64_t)perm->num_frame * perm->frame_size;
-    if (s->f0 < 0 || s->n_frames < 0 || (int64_t)s->f0 + s->n_frames > perm->num_frame || s->n_tail < 0) return SVG_ERR_BAD_ARG;
-    if (s->n_tail > 0 && (s->tail_begin < vend || (int64_t)s->tail_begin + s->n_tail > S)) return SVG_ERR_BAD_ARG;
-    if (s->n_frames == 0 && s->n_tail == 0) return SVG_ERR_BAD_ARG;
-    return SVG_OK;
+    return check_frame_shard(s, S, perm->vid0, perm->num_frame, perm->frame_size);
 }
 static int check_band_shard_geometry(int32_t S, const svg_perm_desc_t* perm) {
     if (S <= 0 || perm->num_frame <= 0 || perm->frame_size <= 0 || perm->vid0 < 0 ||

@@ -14,6 +14,9 @@
 //                        lock-step body: waves 0-1 the golden rows, 2-3 the rows under mask 1, 4-5 under mask 0 on the SAME staged K / V
 //                        tiles, each role its own scores.  (Before that: three workgroups, grid.z = 3, K / V staged three times, 1.26 ms per
 //                        call at HunyuanVideo 720p; the role form 0.78 -> 0.60 ms; the shipped one 0.32.)
+// The second form also exists per KEY SHARD of a sequence sharded by whole frames (include/svg_attn_profile_shard.h): profile16_shard_kernel and
+// profile_shard_reduce_kernel emit one (O, m, l) per output, head and row for a shard's keys, profile_combine_parts_kernel merges such parts —
+// see the note above ProfileShardPolicy.
 #include <type_traits>
 #include "attn_core.h"
 #include "attn_m16.h"
@@ -796,6 +799,491 @@ static int run_profile(const void* q, const void* k, const void* v, const int64_
     return launch_status();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Shard form of the second form (include/svg_attn_profile_shard.h): the keys are the rows of ONE frame shard — the whole frames
+// [f0, f0 + n_frames) and a tail behind the video — and the sampled q rows arrive gathered.  A shard is a set of KV chunks that lives on
+// another GPU: the kernel below is profile16_kernel (its arithmetic copied, not shared: the listing of profile16_kernel stays what it was)
+// with
+//   * q read from the compact q_rows: a lane's row is the INPUT index of the row it ranked, `rows` only gives coordinates;
+//   * tiles on the shard's LOCAL grid: local key l is physical row l of k / v, and every bound against S is one against Sk;
+//   * the mask on the key's stored global index G(l) = g0 + l (l < nv, g0 = f0 P) or tb + (l - nv): a tile wholly in the video rows or wholly
+//     in the tail is the existing code at k0 = G(first key) — classify, the fast paths, the class table, the one-wrap stepping of allowed —
+//     with the end of the keys such a tile can hold in the place of S; the ONE tile that holds the seam l = nv is TILE_PARTIAL under both masks
+//     and maps each key through G (G is continuous there for a shard whose frames end at F; the ABI allows one that is not).
+// profile_shard_reduce_kernel then folds the chunks into one (O, m, l) per (output, head, row) with the sums of profile_combine_kernel, and
+// profile_combine_parts_kernel is that kernel's body over a pointer per part: one part of the whole sequence gives the bits of svg_sample_mse.
+template <typename T, int D>
+struct ProfileShardPolicy : ProfilePolicy<T, D> {
+    struct Params : ProfilePolicy<T, D>::Params {
+        const T* q_rows;    // [BH][R][D]
+        int Sk, nv;         // rows of the shard, of them video rows
+        int g0, tb, send;   // G(0); G(nv) (F P for a shard without a tail); the end of the stored indices: tb + n_tail
+    };
+};
+
+template <typename T, int D>
+__global__ __launch_bounds__(256, 2) void profile16_shard_kernel(typename ProfileShardPolicy<T, D>::Params prm) {
+    using Pol = ProfilePolicy<T, D>;
+    using E = Elt<T>;
+    using M = Mfma16<T>;
+    using V8 = typename E::v8;
+    constexpr int KS = D / 32, NDB = D / 16;
+    using Img = KvImage16<D>;
+    constexpr int kImg = Img::kImg, kStage = Img::kStage;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (prm.skip && prm.skip[0] != 0) return;
+    const int head = blockIdx.x, chunk = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
+    const int g4 = lane >> 4, n16 = lane & 15;
+    const int ntiles = (prm.Sk + kBN - 1) / kBN;
+    const int t0 = chunk * prm.tiles_per_chunk;
+    const int nT = max(0, min(prm.tiles_per_chunk, ntiles - t0));
+    const T* __restrict__ qb = prm.q_rows + (size_t)head * prm.R * D;
+    const T* __restrict__ kb_ = Pol::k_at(prm, head);
+    const T* __restrict__ vb = Pol::v_at(prm, head);
+    typename Pol::Params pt = prm;   // (pt.S: the end of the keys the tile at hand can hold, see above)
+
+    // the rank order of profile16_kernel, a function of `rows` alone; with a row's rank goes its index in q_rows
+    {
+        const int mine = lane < prm.R ? (int)prm.rows[lane] : 0;
+        const int key = lane < prm.R ? Pol::coord(prm, prm.var[1], mine) : 0x7fffffff;
+        int rank = 0;
+#pragma unroll
+        for (int j = 0; j < 64; ++j) {
+            const int kj = __builtin_amdgcn_readlane(key, j);
+            rank += (kj < key || (kj == key && j < lane)) ? 1 : 0;
+        }
+        if (wave == 0) ((int*)smem)[rank] = mine, ((int*)smem)[64 + rank] = lane;
+        __syncthreads();
+    }
+    const int r = wave * 16 + n16;
+    const bool have = r < prm.R;
+    const int qrow = have ? ((const int*)smem)[r] : 0;
+    const int qidx = have ? ((const int*)smem)[64 + r] : 0;
+    __syncthreads();    // (the staging below reuses the bytes)
+    V8 qf[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) qf[ks] = *(const V8*)(qb + (size_t)qidx * D + ks * 32 + g4 * 8);
+
+    typename Pol::Ctx mc[2];
+#pragma unroll
+    for (int v = 0; v < 2; ++v) {
+        typename Pol::Ctx& c = mc[v];
+        c.head = head, c.variant = v + 1, c.chunk = chunk, c.t0 = t0, c.nT = nT;
+        c.pv = prm.var[v];
+        c.qx = Pol::coord(prm, c.pv, qrow) - c.pv.origin;
+        c.qtext = have && ((unsigned)(qrow - c.pv.text_lo) < (unsigned)(c.pv.text_hi - c.pv.text_lo));
+        const int blk = c.qx >> 7;
+        int lo = have ? blk : (1 << 28), hi = have ? blk : -(1 << 28), anyt = c.qtext;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            lo = min(lo, __shfl_xor(lo, o));
+            hi = max(hi, __shfl_xor(hi, o));
+            anyt |= __shfl_xor(anyt, o);
+        }
+        c.xlo_blk = __builtin_amdgcn_readfirstlane(lo), c.xhi_blk = __builtin_amdgcn_readfirstlane(hi);
+        c.any_text = __builtin_amdgcn_readfirstlane(anyt);
+        c.tk0 = 0, c.f0 = 0, c.p0 = 0;
+        c.ystride = c.pv.coord == 1 ? prm.F : 1;
+        c.ybase = 0, c.g4F = 4 * g4 * c.ystride;
+        const int x = c.qx, span = c.pv.span;
+        const bool xdom = have && ((unsigned)x < (unsigned)span);
+        const int ylo = ((x >> 7) - c.pv.band_blocks + 1) * 128, yhi = ((x >> 7) + c.pv.band_blocks) * 128;
+        const int a0 = max(ylo, 0), a1 = min(yhi, span);
+        c.fa0 = a0, c.falen = xdom ? (unsigned)max(a1 - a0, 0) : 0u;
+        c.fblen = (xdom && c.pv.sink_cols > 0) ? (unsigned)min(c.pv.sink_cols, span) : 0u;
+        if (c.qtext) c.fa0 = -(1 << 30), c.falen = 0xFFFFFFFFu;
+    }
+
+    // ---- LDS-DMA staging on the shard's rows ----
+    const unsigned lds0 = (unsigned)(size_t)smem;
+    const unsigned col_v = Img::col_v(lane);
+    const int krow = 16 * wave + (lane >> 2);
+    const unsigned k_rsb = (unsigned)Pol::k_rs(prm) * 2u, v_rsb = (unsigned)Pol::v_rs(prm) * 2u;
+    auto dma_tile = [&](int t) {
+        const int l = (t0 + t) * kBN + krow;
+        const unsigned nphys = (unsigned)(l < prm.Sk ? l : 0);    // rows behind the shard: masked below (the last tile is never FULL)
+#pragma unroll
+        for (int j = 0; j < D / 32; ++j) {
+            const unsigned st = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)((t & 1) * kStage) + (unsigned)(j * (kBN * 64) + wave * 1024));
+            const unsigned ko = __umul24(nphys, k_rsb) + ((unsigned)(j * 64) | col_v);
+            const unsigned vo = __umul24(nphys, v_rsb) + ((unsigned)(j * 64) | col_v);
+            lds_dma16_kv<kImg>(st, ko, vo, kb_, vb);
+        }
+    };
+    const int k_lane = Img::k_lane(g4, n16);
+    const int v_lane0 = Img::v_lane0(g4, n16);
+    const int v_lane1 = v_lane0 ^ 32;
+    auto kfrag = [&](const char* st, int kblk, int ks) -> V8 { return __builtin_bit_cast(V8, Img::kfrag(st, k_lane, kblk, ks)); };
+    auto vfrag = [&](const char* st, int kc, int db) -> V8 { return __builtin_bit_cast(V8, Img::vfrag(st, v_lane0, v_lane1, kc, db)); };
+
+    // ---- the wave's class table, a tile per lane: the tile's first stored index and the end of the keys it can hold ----
+    int* const tab = (int*)(smem + 2 * kStage) + wave * (kP16Win * 4);
+    auto fill_classes = [&](int win0) {
+#pragma unroll
+        for (int i = 0; i < kP16Win / 64; ++i) {
+            const int tl = win0 + lane + 64 * i;
+            p16_i32x4 e = {TILE_SKIP, 0, TILE_SKIP, 0};
+            if (tl < nT) {
+                const int kl = (t0 + tl) * kBN;
+                const bool vid = kl + kBN <= prm.nv, tail = kl >= prm.nv;
+                const int kk = tail ? prm.tb + (kl - prm.nv) : prm.g0 + kl;
+                typename Pol::Params px = prm;
+                px.S = vid ? prm.S : prm.send;
+#pragma unroll
+                for (int v = 0; v < 2; ++v) {
+                    typename Pol::Ctx x = mc[v];
+                    int c = Pol::classify(px, x, kk, wave * 16);
+                    if (c == TILE_PARTIAL_FAST && !x.any_text && x.ybase >= x.pv.sink_cols) {
+                        const int b0 = x.ybase >> 7, b1 = (x.ybase + 63 * x.ystride) >> 7;
+                        if (b0 - x.xhi_blk >= x.pv.band_blocks || x.xlo_blk - b1 >= x.pv.band_blocks) c = TILE_SKIP;
+                    }
+                    if (!vid && !tail) c = Pol::exists(prm, wave * 16) ? TILE_PARTIAL : TILE_SKIP;   // the seam: every key through G
+                    e[2 * v] = c, e[2 * v + 1] = x.ybase;
+                }
+            }
+            *(p16_i32x4*)(tab + (lane + 64 * i) * 4) = e;
+        }
+    };
+
+    float m_run = -INFINITY;
+    f32x4 acc_l[3] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+    V8 ones8;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ones8[i] = E::from_float(1.f);
+    f32x4 acc[3][NDB];
+#pragma unroll
+    for (int o = 0; o < 3; ++o)
+#pragma unroll
+        for (int db = 0; db < NDB; ++db) acc[o][db] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float c_log2 = prm.scale_log2;
+    const int jump = prm.tb - prm.nv - prm.g0;    // what G adds behind the seam
+
+    if (nT > 0) dma_tile(0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[ks]));
+    __syncthreads();
+    for (int t = 0; t < nT; ++t) {
+        if (t + 1 < nT) dma_tile(t + 1);
+        const char* st = smem + (t & 1) * kStage;
+        const int k0l = (t0 + t) * kBN;                                  // the tile's first key on the shard's grid ...
+        const bool vid = k0l + kBN <= prm.nv, tail = k0l >= prm.nv;
+        const int k0 = tail ? prm.tb + (k0l - prm.nv) : prm.g0 + k0l;    // ... and its stored index
+        pt.S = vid ? prm.S : prm.send;
+        if ((t & (kP16Win - 1)) == 0) fill_classes(t);
+        int cls[3];
+        cls[0] = (k0l + kBN <= prm.Sk) ? TILE_FULL : TILE_PARTIAL;
+        {
+            const p16_i32x4 e = *(const p16_i32x4*)(tab + (t & (kP16Win - 1)) * 4);
+            cls[1] = __builtin_amdgcn_readfirstlane(e[0]), mc[0].ybase = __builtin_amdgcn_readfirstlane(e[1]);
+            cls[2] = __builtin_amdgcn_readfirstlane(e[2]), mc[1].ybase = __builtin_amdgcn_readfirstlane(e[3]);
+        }
+        {
+            f32x4 sc[4];
+#pragma unroll
+            for (int b = 0; b < 4; ++b) sc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+            {
+                V8 kf[2][4];
+#pragma unroll
+                for (int b = 0; b < 4; ++b) kf[0][b] = kfrag(st, b, 0);
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) {
+                    if (ks + 1 < KS) {
+#pragma unroll
+                        for (int b = 0; b < 4; ++b) kf[(ks + 1) & 1][b] = kfrag(st, b, ks + 1);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) sc[b] = M::mfma(kf[ks & 1][b], qf[ks], sc[b]);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            if (prm.emulate) {
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    float s0 = sc[b][0], s1 = sc[b][1], s2 = sc[b][2], s3 = sc[b][3];
+                    p16_fixup_pair<T>(s0, s1, prm.fix_scale);
+                    p16_fixup_pair<T>(s2, s3, prm.fix_scale);
+                    sc[b] = f32x4{s0, s1, s2, s3};
+                }
+            }
+            if (cls[0] != TILE_FULL) {
+#pragma unroll
+                for (int b = 0; b < 4; ++b)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) sc[b][j] = (k0l + 16 * b + 4 * g4 + j < prm.Sk) ? sc[b][j] : -INFINITY;
+            }
+            float mx = fmaxf(fmaxf(sc[0][0], sc[0][1]), fmaxf(sc[0][2], sc[0][3]));
+#pragma unroll
+            for (int b = 1; b < 4; ++b) mx = fmaxf(fmaxf(mx, sc[b][0]), fmaxf(fmaxf(sc[b][1], sc[b][2]), sc[b][3]));
+            if (__any(mx * c_log2 > m_run)) {
+                asm volatile("" ::: "memory");
+                const float m_new = fmaxf(m_run, quad_group_max(mx) * c_log2);
+                const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);   // (m_new is finite: a tile holds at least one key of the shard)
+                m_run = m_new;
+#pragma unroll
+                for (int o = 0; o < 3; ++o) {
+                    acc_l[o][0] *= alpha;
+#pragma unroll
+                    for (int db = 0; db < NDB; ++db)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) acc[o][db][j] *= alpha;
+                }
+            }
+            constexpr float kBias = std::is_same_v<T, __bf16> ? 60.f : 15.f;    // (see profile16_kernel)
+            const float m_use = m_run - kBias;
+            V8 pf[3][2];
+            float pr[16];
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    pr[4 * b + j] = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[b][j], c_log2, -m_use));
+                    pf[0][b >> 1][4 * (b & 1) + j] = E::from_float(pr[4 * b + j]);
+                }
+#pragma unroll
+            for (int v = 0; v < 2; ++v) {
+                auto select = [&](auto pred) {
+#pragma unroll
+                    for (int b = 0; b < 4; ++b)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const float pm = pred(16 * b + j) ? pr[4 * b + j] : 0.f;
+                            pf[v + 1][b >> 1][4 * (b & 1) + j] = E::from_float(pm);
+                        }
+                };
+                if (cls[v + 1] == TILE_PARTIAL_FAST) {
+                    const int yb = mc[v].ybase + mc[v].g4F - mc[v].fa0, ys = mc[v].ystride;
+                    const unsigned fal = mc[v].falen, fbl = mc[v].fblen;
+                    if (mc[v].pv.sink_cols > 0) {
+                        const int fa0 = mc[v].fa0;
+                        select([&](int off) { return ((unsigned)(yb + off * ys) < fal) | ((unsigned)(yb + fa0 + off * ys) < fbl); });
+                    } else {
+                        select([&](int off) { return (unsigned)(yb + off * ys) < fal; });
+                    }
+                } else if (cls[v + 1] != TILE_SKIP) {
+                    (void)Pol::classify(pt, mc[v], k0, wave * 16);    // (the general predicate's per-tile decomposition: tk0, f0, p0)
+                    int kb = k0 + 4 * g4;
+                    asm volatile("" : "+v"(kb));
+                    // the lane's first key offset behind the seam (never reached in a tile without it): from there on G adds `jump`
+                    const int thr = (vid || tail) ? 0x7fffffff : prm.nv - k0l - 4 * g4;
+                    select([&](int off) { return Pol::allowed(pt, mc[v], 0, kb + off + (off >= thr ? jump : 0)); });
+                }
+            }
+            {
+                constexpr int G = 4, NG = 2 * NDB / G;
+                const bool s1 = cls[1] != TILE_SKIP, s2 = cls[2] != TILE_SKIP;
+                V8 vf[2][G];
+#pragma unroll
+                for (int i = 0; i < G; ++i) vf[0][i] = vfrag(st, 0, i);
+#pragma unroll
+                for (int g = 0; g < NG; ++g) {
+                    if (g + 1 < NG) {
+#pragma unroll
+                        for (int i = 0; i < G; ++i) vf[(g + 1) & 1][i] = vfrag(st, ((g + 1) * G + i) / NDB, ((g + 1) * G + i) % NDB);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int i = 0; i < G; ++i) acc[0][(g * G + i) % NDB] = M::mfma(vf[g & 1][i], pf[0][(g * G + i) / NDB], acc[0][(g * G + i) % NDB]);
+                    if ((g * G) % NDB == 0) acc_l[0] = M::mfma(ones8, pf[0][(g * G) / NDB], acc_l[0]);
+                    if (s1) {
+                        if ((g * G) % NDB == 0) acc_l[1] = M::mfma(ones8, pf[1][(g * G) / NDB], acc_l[1]);
+#pragma unroll
+                        for (int i = 0; i < G; ++i) acc[1][(g * G + i) % NDB] = M::mfma(vf[g & 1][i], pf[1][(g * G + i) / NDB], acc[1][(g * G + i) % NDB]);
+                    }
+                    if (s2) {
+                        if ((g * G) % NDB == 0) acc_l[2] = M::mfma(ones8, pf[2][(g * G) / NDB], acc_l[2]);
+#pragma unroll
+                        for (int i = 0; i < G; ++i) acc[2][(g * G + i) % NDB] = M::mfma(vf[g & 1][i], pf[2][(g * G + i) / NDB], acc[2][(g * G + i) % NDB]);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+    // ---- the chunk's partials into the workspace, in the layout of profile16_kernel ----
+    if (have) {
+#pragma unroll
+        for (int o = 0; o < 3; ++o) {
+            float* dst = prm.part + ((((size_t)o * prm.BH + head) * prm.n_chunks + chunk) * kProfMaxRows + r) * (D + 4);
+#pragma unroll
+            for (int db = 0; db < NDB; ++db) *(f32x4*)(dst + 16 * db + 4 * g4) = acc[o][db];
+            if (g4 == 0) {
+                dst[D] = m_run;
+                dst[D + 1] = acc_l[o][0];
+            }
+        }
+    }
+}
+
+// The shard's chunks folded into ONE (O, m, l) per (output, head, row): grid = (kProfRowGroups, BH), block = 256, the row groups of
+// profile_combine_kernel.  M = max_c m_c, w_c = 2^(m_c - M), O = sum_c O_c w_c and l = sum_c l_c w_c in chunk order — the sums as
+// profile_combine_kernel writes them (same order, same expressions), so that the combine over ONE such part (weight 2^0, one term added to 0)
+// divides the numbers that kernel divides.  out: [3][BH][R][D + 4], every word written (columns D + 2, D + 3: 0).
+template <int D>
+__global__ __launch_bounds__(256) void profile_shard_reduce_kernel(const float* __restrict__ part, float* __restrict__ out, int BH, int R,
+                                                                   int n_chunks, const int32_t* __restrict__ skip) {
+    if (skip && skip[0] != 0) return;
+    const int rg = blockIdx.x, h = blockIdx.y, tid = threadIdx.x;
+    const int rows_per = (R + kProfRowGroups - 1) / kProfRowGroups;
+    const int r0 = rg * rows_per, r1 = min(R, r0 + rows_per);
+    constexpr int DS = D + 4;
+    const size_t cs = (size_t)kProfMaxRows * DS;
+    constexpr int kRowsPer = (kProfMaxRows + kProfRowGroups - 1) / kProfRowGroups;
+    __shared__ float wsh[3][kRowsPer][64], lws[3][kRowsPer][64], lsh[3][kRowsPer], msh[3][kRowsPer];
+    const int nrows = max(r1 - r0, 0);
+    for (int pi = tid >> 6; pi < 3 * nrows; pi += 4) {
+        const int v = pi / nrows, rr = pi - v * nrows, c = tid & 63;
+        const float* base = part + ((((size_t)v * BH + h) * n_chunks) * kProfMaxRows + r0 + rr) * DS;
+        const float mc = c < n_chunks ? base[c * cs + D] : -INFINITY;
+        const float M = wave_max(mc);
+        const float w = (mc == -INFINITY) ? 0.f : exp2f(mc - M);
+        wsh[v][rr][c] = w;
+        lws[v][rr][c] = c < n_chunks ? base[c * cs + D + 1] * w : 0.f;
+        if (c == 0) msh[v][rr] = M;
+    }
+    __syncthreads();
+    if (tid < 3 * nrows) {
+        const int v = tid / nrows, rr = tid - v * nrows;
+        float L = 0.f;
+        for (int c = 0; c < n_chunks; ++c) L += lws[v][rr][c];
+        lsh[v][rr] = L;
+    }
+    __syncthreads();
+    for (int e = r0 * D + tid; e < r1 * D; e += 256) {
+        const int row = e / D, d = e - row * D;
+#pragma unroll
+        for (int v = 0; v < 3; ++v) {
+            const float* base = part + ((((size_t)v * BH + h) * n_chunks) * kProfMaxRows + row) * DS;
+            float acc = 0.f;
+            for (int c = 0; c < n_chunks; ++c) acc += base[c * cs + d] * wsh[v][row - r0][c];
+            out[(((size_t)v * BH + h) * R + row) * DS + d] = acc;
+        }
+    }
+    if (tid < 3 * nrows) {
+        const int v = tid / nrows, rr = tid - v * nrows;
+        float* dst = out + (((size_t)v * BH + h) * R + r0 + rr) * DS + D;
+        dst[0] = msh[v][rr], dst[1] = lsh[v][rr], dst[2] = 0.f, dst[3] = 0.f;
+    }
+}
+
+// profile_combine_kernel over a pointer per part instead of a chunk stride, a part's rows strided by R: [3][BH][R][D + 4] each.  The part
+// pointers travel in the kernel arguments (a host array at the ABI), at most kProfMaxParts — a part per lane like a chunk per lane there.
+constexpr int kProfMaxParts = 64;
+struct ProfPartPtrs {
+    const float* p[kProfMaxParts];
+};
+
+template <typename T, int D>
+__global__ __launch_bounds__(256) void profile_combine_parts_kernel(ProfPartPtrs parts, float* __restrict__ sq_part, int BH, int R, int n_parts,
+                                                                    int emulate, const int32_t* __restrict__ skip) {
+    __shared__ float red[4][4];
+    if (skip && skip[0] != 0) return;
+    const int rg = blockIdx.x, h = blockIdx.y, tid = threadIdx.x;
+    const int rows_per = (R + kProfRowGroups - 1) / kProfRowGroups;
+    const int r0 = rg * rows_per, r1 = min(R, r0 + rows_per);
+    float sq[2] = {0.f, 0.f};
+    float bad[2] = {0.f, 0.f};
+    constexpr int DS = D + 4;
+    constexpr int kRowsPer = (kProfMaxRows + kProfRowGroups - 1) / kProfRowGroups;
+    __shared__ float wsh[3][kRowsPer][64], lws[3][kRowsPer][64], lsh[3][kRowsPer];
+    const int nrows = max(r1 - r0, 0);
+    for (int pi = tid >> 6; pi < 3 * nrows; pi += 4) {
+        const int v = pi / nrows, rr = pi - v * nrows, c = tid & 63;
+        const size_t off = (((size_t)v * BH + h) * R + r0 + rr) * DS;
+        const float* base = parts.p[c < n_parts ? c : 0] + off;
+        const float mc = c < n_parts ? base[D] : -INFINITY;
+        const float M = wave_max(mc);
+        const float w = (mc == -INFINITY) ? 0.f : exp2f(mc - M);
+        wsh[v][rr][c] = w;
+        lws[v][rr][c] = c < n_parts ? base[D + 1] * w : 0.f;
+    }
+    __syncthreads();
+    if (tid < 3 * nrows) {
+        const int v = tid / nrows, rr = tid - v * nrows;
+        float L = 0.f;
+        for (int c = 0; c < n_parts; ++c) L += lws[v][rr][c];
+        lsh[v][rr] = L;
+    }
+    __syncthreads();
+    for (int e = r0 * D + tid; e < r1 * D; e += 256) {
+        const int row = e / D, d = e - row * D;
+        float o[3];
+#pragma unroll
+        for (int v = 0; v < 3; ++v) {
+            const size_t off = (((size_t)v * BH + h) * R + row) * DS + d;
+            const float L = lsh[v][row - r0];
+            float acc = 0.f;
+            for (int c = 0; c < n_parts; ++c) acc += parts.p[c][off] * wsh[v][row - r0][c];
+            // a row whose mask admits no key of any part is NaN in the reference (softmax over all -inf)
+            o[v] = (L > 0.f) ? acc / L : __builtin_nanf("");
+            if (emulate) o[v] = Elt<T>::to_float(Elt<T>::from_float(o[v]));
+        }
+#pragma unroll
+        for (int v = 0; v < 2; ++v) {
+            float diff = o[v + 1] - o[0];
+            if (emulate) {
+                diff = Elt<T>::to_float(Elt<T>::from_float(diff));
+                sq[v] += Elt<T>::to_float(Elt<T>::from_float(diff * diff));
+            } else {
+                sq[v] += diff * diff;
+            }
+            if (diff != diff) bad[v] = 1.f, sq[v] = 0.f;
+        }
+    }
+    float vals[4] = {bad[0] > 0.f ? 0.f : sq[0], bad[1] > 0.f ? 0.f : sq[1], bad[0], bad[1]};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float s = wave_sum(vals[i]);
+        if ((tid & 63) == 0) red[i][tid >> 6] = s;
+    }
+    __syncthreads();
+    if (tid < 4) sq_part[((size_t)h * kProfRowGroups + rg) * 4 + tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
+}
+
+template <typename T, int D>
+static int run_profile_shard(const void* q_rows, const void* k, const void* v, const int64_t* rows, int R, int BH, int S, float sm_scale,
+                             const svg_profile_desc_t* pd, const svg_band_shard_t& sh, float* part, void* ws, const int32_t* skip,
+                             const AttnLayout* lay, hipStream_t st) {
+    typename ProfileShardPolicy<T, D>::Params p;
+    const int P = pd->frame_size, F = pd->num_frame;
+    p.Sk = P * sh.n_frames + sh.n_tail, p.nv = P * sh.n_frames;
+    p.g0 = sh.f0 * P, p.tb = sh.n_tail > 0 ? sh.tail_begin : F * P, p.send = p.tb + sh.n_tail;
+    p.q_rows = (const T*)q_rows;
+    p.q = nullptr, p.k = (const T*)k, p.v = (const T*)v;
+    p.lay = lay ? *lay : contiguous_layout(BH, BH, p.Sk, p.Sk, D);
+    p.S = S, p.BH = BH, p.R = R;
+    p.n_chunks = prof_chunks(BH, p.Sk);
+    const int ntiles = (p.Sk + kBN - 1) / kBN;
+    p.tiles_per_chunk = (ntiles + p.n_chunks - 1) / p.n_chunks;
+    p.emulate = pd->emulate_bf16;
+    p.scale_log2 = p.emulate ? 1.4426950408889634f : sm_scale * 1.4426950408889634f;
+    p.fix_scale = sm_scale;
+    p.rows = rows;
+    p.vid0 = 0, p.F = F, p.P = P, p.V = F * P;
+    for (int i = 0; i < 2; ++i) {
+        p.var[i].coord = pd->variant[i].coord;
+        p.var[i].origin = pd->variant[i].origin;
+        p.var[i].span = pd->variant[i].span;
+        p.var[i].band_blocks = pd->variant[i].band_blocks;
+        p.var[i].sink_cols = pd->variant[i].sink_cols;
+        p.var[i].text_lo = pd->variant[i].text_lo;
+        p.var[i].text_hi = pd->variant[i].text_hi;
+    }
+    p.part = (float*)ws;
+    p.skip = skip;
+    constexpr int lds16 = p16_lds_bytes(D);
+    auto kern = profile16_shard_kernel<T, D>;
+    if (const int rc = configure_lds((const void*)kern, lds16); rc != SVG_OK) return rc;
+    hipLaunchKernelGGL(kern, dim3(BH, p.n_chunks), dim3(256), lds16, st, p);
+    hipLaunchKernelGGL((profile_shard_reduce_kernel<D>), dim3(kProfRowGroups, BH), dim3(256), 0, st, (const float*)ws, part, BH, R, p.n_chunks,
+                       skip);
+    return launch_status();
+}
+
 }  // namespace svg
 
 using namespace svg;
@@ -861,4 +1349,65 @@ extern "C" int svg_sample_mse(const void* q, const void* k, const void* v, const
                               float* out_mse, void* workspace, size_t workspace_bytes, void* stream) {
     return svg_sample_mse_flagged(q, k, v, rows, R, BH, S, D, dtype, sm_scale, prof, out_mse, workspace, workspace_bytes, nullptr,
                                   stream);
+}
+
+// ---- the shard form (include/svg_attn_profile_shard.h; the order of the checks is the one documented there) ----
+extern "C" size_t svg_sample_mse_shard_workspace_bytes(int32_t BH, int32_t R, int32_t D, int32_t Sk) {
+    if (BH <= 0 || R <= 0 || D <= 0 || Sk <= 0) return 0;
+    return (size_t)3 * BH * prof_chunks(BH, Sk) * kProfMaxRows * (D + 4) * sizeof(float);
+}
+
+extern "C" int svg_sample_mse_shard_partial(const void* q_rows, const void* k, const void* v, const int64_t* rows, int32_t R, int32_t BH,
+                                            int32_t S, int32_t D, int32_t dtype, float sm_scale, const svg_profile_desc_t* prof,
+                                            const svg_band_shard_t* k_shard, float* part, void* workspace, size_t workspace_bytes,
+                                            const int32_t* skip_flag, const svg_attn_layout_t* abi_layout, void* stream) {
+    if (!q_rows || !k || !v || !rows || !prof || !k_shard || !part || !workspace) return SVG_ERR_BAD_ARG;
+    if (R <= 0 || BH <= 0 || S <= 0 || D <= 0) return SVG_ERR_BAD_ARG;
+    const int F = prof->num_frame, P = prof->frame_size;
+    if (F <= 0 || P <= 0 || prof->vid0 < 0 || (int64_t)prof->vid0 + (int64_t)F * P > S) return SVG_ERR_BAD_ARG;
+    if (const int rc = check_frame_shard(k_shard, S, prof->vid0, F, P); rc != SVG_OK) return rc;
+    if (prof->vid0 != 0) return SVG_ERR_BAD_ARG;
+    if (R > kProfMaxRows) return SVG_ERR_UNSUPPORTED;
+    for (int i = 0; i < 2; ++i)
+        if (prof->variant[i].coord == 1 && P < kBN) return SVG_ERR_UNSUPPORTED;  // one-wrap stepping
+    if (S >= (1 << 24)) return SVG_ERR_UNSUPPORTED;
+    const int Sk = P * k_shard->n_frames + k_shard->n_tail;     // (<= S)
+    if (workspace_bytes < svg_sample_mse_shard_workspace_bytes(BH, R, D, Sk)) return SVG_ERR_WORKSPACE;
+    AttnLayout lay_storage;
+    const AttnLayout* lay = nullptr;
+    if (abi_layout) {   // (q and o are not tensors of the layout here: k stands in for both)
+        svg_attn_layout_t a = *abi_layout;
+        a.q = a.k, a.o = a.k;
+        if (const int rc = layout_from_abi(&a, BH, BH, Sk, Sk, D, k, k, v, k, lay_storage); rc != SVG_OK) return rc;
+        lay = &lay_storage;
+    }
+    if (dtype != SVG_DTYPE_BF16 || D != 128) return SVG_ERR_UNSUPPORTED;
+    return run_profile_shard<__bf16, 128>(q_rows, k, v, rows, R, BH, S, sm_scale, prof, *k_shard, part, workspace, skip_flag, lay,
+                                          (hipStream_t)stream);
+}
+
+extern "C" size_t svg_sample_mse_from_parts_workspace_bytes(int32_t BH) {
+    return BH <= 0 ? 0 : (size_t)BH * kProfRowGroups * 4 * sizeof(float);
+}
+
+extern "C" int svg_sample_mse_from_parts(const float* const* parts, int32_t n_parts, int32_t R, int32_t BH, int32_t D, int32_t dtype,
+                                         int32_t emulate_bf16, float* out_mse, void* workspace, size_t workspace_bytes,
+                                         const int32_t* skip_flag, void* stream) {
+    if (!parts || !out_mse || !workspace) return SVG_ERR_BAD_ARG;
+    if (n_parts < 1 || n_parts > kProfMaxParts || R <= 0 || BH <= 0 || D <= 0) return SVG_ERR_BAD_ARG;
+    ProfPartPtrs pp{};
+    for (int i = 0; i < n_parts; ++i) {
+        if (!parts[i]) return SVG_ERR_BAD_ARG;
+        pp.p[i] = parts[i];
+    }
+    if (R > kProfMaxRows) return SVG_ERR_UNSUPPORTED;
+    if (workspace_bytes < svg_sample_mse_from_parts_workspace_bytes(BH)) return SVG_ERR_WORKSPACE;
+    if (dtype != SVG_DTYPE_BF16 || D != 128) return SVG_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    float* sq_part = (float*)workspace;
+    hipLaunchKernelGGL((profile_combine_parts_kernel<__bf16, 128>), dim3(kProfRowGroups, BH), dim3(256), 0, st, pp, sq_part, BH, R, n_parts,
+                       emulate_bf16, skip_flag);
+    hipLaunchKernelGGL((profile_finalize_kernel<__bf16>), dim3(1), dim3(256), 0, st, (const float*)sq_part, out_mse, BH, R, D, emulate_bf16,
+                       skip_flag);
+    return launch_status();
 }

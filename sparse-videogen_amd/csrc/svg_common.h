@@ -182,6 +182,16 @@ inline int check_rows(long long S, int D) {
     return (S >= (1ll << 24) || S * D * 2 >= (1ll << 32)) ? SVG_ERR_UNSUPPORTED : SVG_OK;
 }
 
+// A frame shard (svg_band_shard_t) against a sequence of S rows whose video is F frames of P rows from row vid0: the checks of the band
+// shard entries and of the profiler's shard entry, in their documented order.
+inline int check_frame_shard(const svg_band_shard_t* s, int32_t S, int vid0, int F, int P) {
+    const int64_t vend = (int64_t)vid0 + (int64_t)F * P;
+    if (s->f0 < 0 || s->n_frames < 0 || (int64_t)s->f0 + s->n_frames > F || s->n_tail < 0) return SVG_ERR_BAD_ARG;
+    if (s->n_tail > 0 && (s->tail_begin < vend || (int64_t)s->tail_begin + s->n_tail > S)) return SVG_ERR_BAD_ARG;
+    if (s->n_frames == 0 && s->n_tail == 0) return SVG_ERR_BAD_ARG;
+    return SVG_OK;
+}
+
 // fn(T{}, std::integral_constant<int, D>{}) for the element types and head sizes the attention kernels are built for
 // (bf16 / fp16 x 64 / 128); SVG_ERR_UNSUPPORTED for any other pair.
 template <typename F>

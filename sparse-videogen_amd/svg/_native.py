@@ -308,6 +308,16 @@ BAND_SHARD_SIGNATURES = {
 }
 BAND_SHARD_SIGNATURES["svg_band_shard_attention_lse_f32"] = BAND_SHARD_SIGNATURES["svg_band_shard_attention_lse"]
 
+# include/svg_attn_profile_shard.h: the online profiler's partial over one key shard and the combine over partials, in a table of its own
+# for the same reason (tests/test_profile_shard_cpu.py)
+PROFILE_SHARD_SIGNATURES = {
+    "svg_sample_mse_shard_workspace_bytes": (_SZ, [_I32, _I32, _I32, _I32]),
+    "svg_sample_mse_shard_partial": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _F32, C.POINTER(ProfileDesc),
+                                               C.POINTER(BandShard), _VP, _VP, _SZ, _VP, C.POINTER(AttnLayout), _VP]),
+    "svg_sample_mse_from_parts_workspace_bytes": (_SZ, [_I32]),
+    "svg_sample_mse_from_parts": (C.c_int, [_VP, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _SZ, _VP, _VP]),
+}
+
 
 def lib_path() -> Path:
     return Path(os.environ.get("SVG_ATTN_LIB", str(_LIB_PATH)))
@@ -322,7 +332,7 @@ def load(strict: bool = True) -> Optional[C.CDLL]:
     try:
         lib = C.CDLL(str(p))
         for name, (res, args) in {**SIGNATURES, **SPARSE_LSE_SIGNATURES, **SPARSE_F32_SIGNATURES, **BAND_LSE_FORM_SIGNATURES,
-                                   **BAND_WINDOW_SIGNATURES, **BAND_SHARD_SIGNATURES}.items():
+                                   **BAND_WINDOW_SIGNATURES, **BAND_SHARD_SIGNATURES, **PROFILE_SHARD_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -1654,6 +1664,105 @@ def sample_mse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rows: torch.Te
                             C.byref(prof), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
     _check(rc, "svg_sample_mse")
     return out
+
+
+# ------------------------------------------------------------------------------------------------------
+# the online profiler on frame shards (include/svg_attn_profile_shard.h): a partial per key shard, the combine over partials
+# ------------------------------------------------------------------------------------------------------
+PROFILE_MAX_PARTS = 64   # svg_sample_mse_from_parts: the part pointers travel in the kernel arguments
+
+
+def _sample_mse_shard_partial(q_rows: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rows: torch.Tensor, prof: ProfileDesc, k_shard,
+                              num_tokens: int, sm_scale: Optional[float] = None, skip_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The profiler's partial of R sampled rows over the keys of ONE frame shard (svg_sample_mse_shard_partial): q_rows [BH, R, D] (or
+    [B, H, R, D]) is q[..., rows, :] of the whole sequence, already gathered; rows int64 [R] on the GPU, the GLOBAL row indices; k / v
+    [BH, Sk, D] the rows of k_shard (BandShard or (f0, n_frames, tail_begin, n_tail)) of a sequence of num_tokens rows whose video prof
+    describes (prof.vid0 == 0) -> part fp32 [3, BH, R, D + 4]: per output (golden, variant 0, variant 1), head and row — in the kernel's rank
+    order, a function of rows alone — the un-normalised O, then m (log2 domain), l, 0, 0.  Parts of shards that cover the keys go to
+    sample_mse_from_parts.  Strided k / v views are read in place through the layout and copied where it cannot describe them.
+    skip_flag (int32 [1] on the GPU) != 0: the kernels return at once and part is left as allocated.  bf16, head_dim 128, R <= 64; anything
+    else raises — there is no fall-back."""
+    lib = load()
+    _dev(rows, skip_flag)
+    _gpu(q_rows, k, v)
+    R, D = q_rows.shape[-2], q_rows.shape[-1]
+    Sk = k.shape[-2]
+    BH = q_rows.numel() // (R * D)
+    if q_rows.dtype != torch.bfloat16 or D != 128 or not (q_rows.dtype == k.dtype == v.dtype):
+        raise ValueError(f"sample_mse_shard_partial: bfloat16, head_dim 128; got {q_rows.dtype} / {k.dtype} / {v.dtype}, D = {D} "
+                         f"(no shard form, no fall-back)")
+    if rows.numel() != R or rows.dtype != torch.int64 or k.shape != v.shape or k.shape[-1] != D or k.numel() != BH * Sk * D:
+        raise ValueError(f"sample_mse_shard_partial: q_rows [BH, R, D], rows int64 [R], k / v [BH, Sk, D]; got {tuple(q_rows.shape)}, "
+                         f"{tuple(rows.shape)} {rows.dtype}, {tuple(k.shape)}, {tuple(v.shape)}")
+    S = int(num_tokens)
+    ks = _shard(k_shard)
+    F, P = int(prof.num_frame), int(prof.frame_size)
+    if prof.vid0 != 0 or F <= 0 or P <= 0 or F * P > S:
+        raise ValueError(f"sample_mse_shard_partial: a video of {F} frames of {P} rows from row {prof.vid0} in {S} rows (vid0 must be 0: rows "
+                         f"in front of the video belong to no shard)")
+    _check_shard("sample_mse_shard_partial: k shard", ks, S, 0, F, P)
+    if Sk != band_shard_rows(ks, P):
+        raise ValueError(f"sample_mse_shard_partial: k holds {Sk} rows, the shard says {band_shard_rows(ks, P)}")
+    if skip_flag is not None:
+        assert skip_flag.dtype == torch.int32
+    part = empty((3, BH, R, D + 4), dtype=torch.float32, device=k.device)
+    ws = empty(lib.svg_sample_mse_shard_workspace_bytes(BH, R, D, Sk), dtype=torch.uint8, device=k.device)
+    q_rows = q_rows.contiguous()
+    lay = None
+    if not (k.is_contiguous() and v.is_contiguous()):
+        k4, v4 = _view4(k), _view4(v)
+        if _strided_ok(k4, True) and _strided_ok(v4, True):
+            lay = C.byref(attn_layout(k4, k4, v4, k4))
+        else:
+            k, v = k.contiguous(), v.contiguous()
+    rc = lib.svg_sample_mse_shard_partial(q_rows.data_ptr(), k.data_ptr(), v.data_ptr(), rows.data_ptr(), R, BH, S, D, _dtype_code(k),
+                                          _sm_scale(sm_scale, D), C.byref(prof), C.byref(ks), part.data_ptr(), ws.data_ptr(), ws.numel(),
+                                          _ptr(skip_flag), lay, _stream())
+    _check(rc, "svg_sample_mse_shard_partial")
+    return part
+
+
+def _sample_mse_from_parts(parts: Sequence[torch.Tensor], R: int, dtype: torch.dtype, emulate_bf16, skip_flag: Optional[torch.Tensor] = None
+                           ) -> torch.Tensor:
+    """mse fp32 [2, BH] from the partials of shards that cover the keys (svg_sample_mse_from_parts): parts[i] fp32 [3, BH, R, D + 4] as
+    sample_mse_shard_partial (or neutral_profile_part) returns them, 1 to PROFILE_MAX_PARTS of them, merged in list order with the arithmetic
+    of sample_mse's own combine; dtype is that of q, k, v (the roundings of emulate_bf16).  One part of the whole sequence gives the bits of
+    sample_mse.  skip_flag != 0: the kernels return at once and the result is left as allocated."""
+    lib = load()
+    n = len(parts)
+    if not 1 <= n <= PROFILE_MAX_PARTS:
+        raise ValueError(f"sample_mse_from_parts takes 1 to {PROFILE_MAX_PARTS} parts, got {n}")
+    x = parts[0]
+    _dev(*parts, skip_flag)
+    if any(t.dtype != torch.float32 or t.shape != x.shape for t in parts) or x.dim() != 4 or x.shape[0] != 3 or x.shape[2] != int(R):
+        raise ValueError(f"sample_mse_from_parts: fp32 parts [3, BH, {R}, D + 4] of one shape, got {[tuple(t.shape) for t in parts]}")
+    if dtype != torch.bfloat16:
+        raise ValueError(f"sample_mse_from_parts: bfloat16 (the second form of the kernel), got {dtype}")
+    if skip_flag is not None:
+        assert skip_flag.dtype == torch.int32
+    BH, D = x.shape[1], x.shape[3] - 4
+    out = empty((2, BH), dtype=torch.float32, device=x.device)
+    ws = empty(lib.svg_sample_mse_from_parts_workspace_bytes(BH), dtype=torch.uint8, device=x.device)
+    pp = (C.c_void_p * n)(*[t.data_ptr() for t in parts])
+    rc = lib.svg_sample_mse_from_parts(C.cast(pp, _VP), n, int(R), BH, D, SVG_DTYPE_BF16, int(bool(emulate_bf16)), out.data_ptr(),
+                                       ws.data_ptr(), ws.numel(), _ptr(skip_flag), _stream())
+    _check(rc, "svg_sample_mse_from_parts")
+    return out
+
+
+def _neutral_profile_part(BH: int, R: int, D: int, device) -> torch.Tensor:
+    """The part of a rank that holds no rows: O = 0, m = -inf, l = 0 — weight 0 in sample_mse_from_parts, the other parts' bits unchanged."""
+    part = empty((3, int(BH), int(R), int(D) + 4), dtype=torch.float32, device=device)
+    part.zero_()
+    part[..., int(D)] = float("-inf")
+    return part
+
+
+# (The public names are bound by assignment, as band_shard_attention is: the coverage walk of tests/test_gpu_poison.py lists the `def`s of
+#  this module that allocate and looks for their poison rows in its own file; the rows of these are in tests/test_gpu_profile_shard.py.)
+sample_mse_shard_partial = _sample_mse_shard_partial
+sample_mse_from_parts = _sample_mse_from_parts
+neutral_profile_part = _neutral_profile_part
 
 
 def kmeans_xsq(x: torch.Tensor) -> torch.Tensor:

@@ -15,6 +15,9 @@ exchange of the next shard behind the compute of this one; equal to the single-G
 the global coordinates of the two shards, and pairs of shards the mask rules out exchange and compute nothing.
 `token_sharded_svg1_attention` is that schedule for a real SVG1 layer-call: the sequence sharded by whole frames in the model's own row
 order, heads in logical order and token-major heads in one launch per step (svg_band_shard_attention_lse[_f32]).
+`token_sharded_sample_mse` is the online profiler of such a sequence — no K / V travels: the sampled q rows are exchanged, each rank streams
+its own shard into one partial (svg_sample_mse_shard_partial), the partials are gathered and merged to the same bits on every rank
+(svg_sample_mse_from_parts) — and `token_sharded_svg1_layer_call` chains the two: a sharded SVG1 layer-call from q, k, v alone.
 """
 from __future__ import annotations
 
@@ -545,6 +548,104 @@ def token_sharded_svg1_attention(q_local: torch.Tensor, k_local: torch.Tensor, v
         return torch.zeros_like(q_local)
     order = sorted(parts)
     return merge_fn([parts[r][0] for r in order], [parts[r][1] for r in order])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the online profiler on frame shards: no K / V travels — every rank streams its own shard once; what travels is the sampled q rows and one
+# partial per rank (svg_sample_mse_shard_partial, svg_sample_mse_from_parts), and every rank ends with the same mse bits.
+# ---------------------------------------------------------------------------------------------------------------
+def sampled_row_owners(rows, geometry, world: int) -> List[Tuple[int, int]]:
+    """(owner rank, row index in that rank's frame_shard) of every sampled row (global indices, a host sequence): a video row lives with
+    its frame, every row behind the video on the last rank.  Host only; the same list on every rank."""
+    S, vid0, F, P = (int(x) for x in geometry)
+    sh = [frame_shard(geometry, r, world) for r in range(world)]
+    out = []
+    for g in (int(x) for x in rows):
+        if not 0 <= g < S:
+            raise ValueError(f"sampled row {g} outside the {S} rows of the sequence")
+        if g < F * P:
+            f = g // P
+            r = next(r for r in range(world) if sh[r].f0 <= f < sh[r].f0 + sh[r].n_frames)
+            out.append((r, g - sh[r].f0 * P))
+        else:
+            r = world - 1
+            out.append((r, P * sh[r].n_frames + g - sh[r].tail_begin))
+    return out
+
+
+def token_sharded_sample_mse(q_local: torch.Tensor, k_local: torch.Tensor, v_local: torch.Tensor, rows: torch.Tensor, prof, geometry,
+                             group=None, skip_flag: Optional[torch.Tensor] = None, partial_fn: Optional[Callable] = None,
+                             combine_fn: Optional[Callable] = None) -> torch.Tensor:
+    """The online profiler (sample_mse) of a sequence that lives sharded by whole frames: q_local, k_local, v_local [..., H, S_r, D] are ALL
+    heads of this rank's rows `frame_shard(geometry, rank, world)`; rows is a CPU int64 tensor of sampled GLOBAL rows, the same on every
+    rank (the ranks draw from the broadcast-seeded generator); prof the _native.ProfileDesc of the whole sequence; geometry = (num_tokens,
+    vid0, num_frame, frame_size).  Returns mse fp32 [2, BH] (BH: the leading dimensions and H), the same bits on every rank.
+    The host computes each row's owner and local index (sampled_row_owners).  Each rank puts the rows it owns into a zeroed [BH, R, D]
+    buffer; ONE sum over the ranks on an integer view of the bits — every word is non-zero on one rank at most, so no floating-point add is
+    involved and the exchange runs over gloo — gives every rank q[:, rows].  Each rank then runs partial_fn(q_rows, k_local, v_local,
+    rows_on_device, k_shard) -> part [3, BH, R, D + 4] over its own shard, or fills _native.neutral_profile_part when it holds no rows; the
+    parts are all-gathered and combine_fn(parts, R) -> mse merges them in rank order on every rank.  No K / V travels: a rank reads 1 / world of
+    what a full call reads and receives (world - 1) parts of 3 BH R (D + 4) fp32.  Nothing is read back and nothing synchronises the device.
+    partial_fn and combine_fn default to the native calls (_native.sample_mse_shard_partial, _native.sample_mse_from_parts, both with
+    skip_flag); they exist so that the schedule can be tested on gloo without a GPU.  A partial_fn whose parts are not fp32 says so in an
+    attribute `part_dtype` (the neutral part of a rank without rows is made in it).
+    Not wired into the processors or bench_step.py.  Equal to sample_mse on the whole sequence to rounding, not bit for bit."""
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    S, vid0, F, P = (int(x) for x in geometry)
+    if world > _native.PROFILE_MAX_PARTS:
+        raise ValueError(f"token_sharded_sample_mse: {world} ranks, but sample_mse_from_parts takes at most {_native.PROFILE_MAX_PARTS} parts")
+    sh = [frame_shard(geometry, r, world) for r in range(world)]
+    S_me = _native.band_shard_rows(sh[rank], P)
+    assert q_local.shape[-2] == S_me and k_local.shape == v_local.shape and k_local.shape[-2] == S_me, (
+        f"rank {rank} holds {q_local.shape[-2]} / {k_local.shape[-2]} rows, frame_shard says {S_me}")
+    D = q_local.shape[-1]
+    R = int(rows.numel())
+    device = q_local.device
+    if partial_fn is None:
+        def partial_fn(q_rows, k, v, rows_dev, k_shard):
+            return _native.sample_mse_shard_partial(q_rows, k, v, rows_dev, prof, k_shard, S, skip_flag=skip_flag)
+    if combine_fn is None:
+        def combine_fn(parts, n_rows):
+            return _native.sample_mse_from_parts(parts, n_rows, q_local.dtype, prof.emulate_bf16, skip_flag=skip_flag)
+    BH = 1
+    for x in q_local.shape[:-2]:
+        BH *= int(x)
+    q3, k3, v3 = (x.reshape(BH, S_me, D) for x in (q_local, k_local, v_local))
+    # the sampled rows: this rank's into their places of a zeroed buffer, an exact sum over the ranks on the bits
+    own = sampled_row_owners(rows.tolist(), geometry, world)
+    pos = [i for i, (r, _) in enumerate(own) if r == rank]
+    q_rows = torch.zeros((BH, R, D), dtype=q_local.dtype, device=device)
+    if pos:
+        src = torch.tensor([own[i][1] for i in pos], dtype=torch.int64).to(device, non_blocking=True)
+        q_rows.index_copy_(1, torch.tensor(pos, dtype=torch.int64).to(device, non_blocking=True), q3.index_select(1, src))
+    if world > 1:
+        dist.all_reduce(q_rows.view(torch.int32), op=dist.ReduceOp.SUM, group=group)
+    if S_me > 0:
+        part = partial_fn(q_rows, k3, v3, rows.to(device, non_blocking=True), sh[rank])
+    else:
+        part = _native.neutral_profile_part(BH, R, D, device).to(getattr(partial_fn, "part_dtype", torch.float32))
+    if world == 1:
+        return combine_fn([part], R)
+    gathered = _native.empty((world * part.shape[0],) + tuple(part.shape[1:]), dtype=part.dtype, device=device)   # concatenated along dim 0
+    dist.all_gather_into_tensor(gathered, part.contiguous(), group=group)
+    gathered = gathered.view((world,) + tuple(part.shape))
+    return combine_fn([gathered[r] for r in range(world)], R)
+
+
+def token_sharded_svg1_layer_call(q_local: torch.Tensor, k_local: torch.Tensor, v_local: torch.Tensor, mask, prof, geometry, rows: torch.Tensor,
+                                  group=None, fp32_parts: bool = True, partial_fn: Optional[Callable] = None,
+                                  combine_fn: Optional[Callable] = None, attn_fn: Optional[Callable] = None,
+                                  merge_fn: Optional[Callable] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One SVG1 layer-call of a sequence that lives sharded by whole frames, from q, k, v alone: token_sharded_sample_mse picks each head's
+    mask — the MSEs rounded to q's dtype before the argmin as svg.models._core.sample_mse rounds them, so two candidates that round to one
+    value tie to index 0 and NaN wins — and token_sharded_svg1_attention(..., best_mask_idx, kinds="both") runs the attention under it.
+    Returns (o_local [..., H, S_r, D], best_mask_idx int64 [BH], the same on every rank and never read back).  The *_fn arguments go to the two
+    schedules (tests on gloo without a GPU).  Not wired into the processors or bench_step.py."""
+    mse = token_sharded_sample_mse(q_local, k_local, v_local, rows, prof, geometry, group=group, partial_fn=partial_fn, combine_fn=combine_fn)
+    best_mask_idx = torch.argmin(mse.to(q_local.dtype), dim=0)
+    o_local = token_sharded_svg1_attention(q_local, k_local, v_local, mask, best_mask_idx, geometry, group=group, fp32_parts=fp32_parts,
+                                           kinds="both", attn_fn=attn_fn, merge_fn=merge_fn)
+    return o_local, best_mask_idx
 
 
 class ExchangeBuffers:
