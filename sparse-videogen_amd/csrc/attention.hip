@@ -122,6 +122,26 @@ __global__ __launch_bounds__(512, 2) void band_shard_f32_m16_kernel(typename Ban
     extern __shared__ __attribute__((aligned(16))) char smem[];
     attn_body_m16<T, BandShardF32Policy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
 }
+// Device switch of the shard forms (svg_band_shard_attention_switch_lse[_f32], include/svg_attn_band_shard_switch.h): `flag[0] != 0`
+// selects prm_alt — the alternate mask on the same two shards, every head in logical order (no head flags) — as
+// band_attn_lse_m16_switch_kernel does on the whole sequence; the template arguments of the two kernels above, so either flag value keeps
+// their bits.  Static mapping over the q-tiles of the larger block; o / lse (o32) at the shard row q was read from under either block.
+template <typename T>
+__global__ __launch_bounds__(512, 2) void band_shard_lse_m16_switch_kernel(typename BandShardLsePolicy<T>::Params prm,
+                                                                           typename BandShardLsePolicy<T>::Params prm_alt,
+                                                                           const int32_t* __restrict__ flag) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (flag[0] != 0) attn_body_m16<T, BandShardLsePolicy<T>, false, 1, false, true>(prm_alt, smem, nullptr, &g_band_replays);
+    else attn_body_m16<T, BandShardLsePolicy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
+}
+template <typename T>
+__global__ __launch_bounds__(512, 2) void band_shard_f32_m16_switch_kernel(typename BandShardF32Policy<T>::Params prm,
+                                                                           typename BandShardF32Policy<T>::Params prm_alt,
+                                                                           const int32_t* __restrict__ flag) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (flag[0] != 0) attn_body_m16<T, BandShardF32Policy<T>, false, 1, false, true>(prm_alt, smem, nullptr, &g_band_replays);
+    else attn_body_m16<T, BandShardF32Policy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
+}
 // pre-scaled q on the 16x16x32 body (PRE form of attn_body_m16)
 template <typename T>
 __global__ __launch_bounds__(512, 2) void band_attn_m16q_kernel(typename BandPolicy<T, 128, 8>::Params prm) {
@@ -444,14 +464,32 @@ static int band_dispatch(const void* q, const void* k, const void* v, void* o, i
                     return SVG_ERR_UNSUPPORTED;
                 } else {
                     const int lds = attn_m16_lds_bytes() + kTailLds;
+                    // the device switch: the alternate mask on the same shards, every head in logical order (perm's geometry, no flags)
+                    svg_perm_desc_t perm_alt = *perm;
+                    perm_alt.head_perm_flag = nullptr;
                     if (opts.o32) {
                         using Pol = BandShardF32Policy<T>;
                         typename Pol::Params p = make_band_shard_params<Pol, T>(q, k, v, nullptr, BH, S, sm_scale, mask, perm, *opts.q_shard,
                                                                                 *opts.k_shard, opts);
                         p.o32 = opts.o32;
+                        if (opts.use_alt) {
+                            typename Pol::Params b = make_band_shard_params<Pol, T>(q, k, v, nullptr, BH, S, sm_scale, opts.alt_mask, &perm_alt,
+                                                                                    *opts.q_shard, *opts.k_shard, opts);
+                            b.o32 = opts.o32;
+                            return launch_attn(band_shard_f32_m16_switch_kernel<T>, dim3(std::max(p.nqt, b.nqt) * BH), 512, lds, st, p, b,
+                                               opts.use_alt);
+                        }
                         return launch_attn(band_shard_f32_m16_kernel<T>, dim3(p.nqt * BH), 512, lds, st, p);
                     }
                     using Pol = BandShardLsePolicy<T>;
+                    if (opts.use_alt) {
+                        const typename Pol::Params a = make_band_shard_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, *opts.q_shard,
+                                                                                      *opts.k_shard, opts);
+                        const typename Pol::Params b = make_band_shard_params<Pol, T>(q, k, v, o, BH, S, sm_scale, opts.alt_mask, &perm_alt,
+                                                                                      *opts.q_shard, *opts.k_shard, opts);
+                        return launch_attn(band_shard_lse_m16_switch_kernel<T>, dim3(std::max(a.nqt, b.nqt) * BH), 512, lds, st, a, b,
+                                           opts.use_alt);
+                    }
                     const typename Pol::Params p = make_band_shard_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, *opts.q_shard,
                                                                                   *opts.k_shard, opts);
                     return launch_attn(band_shard_lse_m16_kernel<T>, dim3(p.nqt * BH), 512, lds, st, p);
@@ -665,6 +703,7 @@ extern "C" int svg_band_window_attention_lse_f32(const void* q, const void* k, c
 // The shard entries (include/svg_attn_band_shard.h): the checks of their own arguments — perm's geometry (checked whether or not it
 // carries flags), the q shard, the k shard — then band_dispatch with the two shards in opts.  `o32` (or nullptr) stands in for o as in
 // svg_band_attention_lse_f32.
+static BandOpts switch_opts(const svg_band_mask_t* alt_mask, const int32_t* use_alt_flag);
 static int check_band_shard(const svg_band_shard_t* s, int32_t S, const svg_perm_desc_t* perm) {
     return check_frame_shard(s, S, perm->vid0, perm->num_frame, perm->frame_size);
 }
@@ -676,13 +715,15 @@ static int check_band_shard_geometry(int32_t S, const svg_perm_desc_t* perm) {
 }
 static int band_shard_entry(const void* q, const void* k, const void* v, void* o, float* o32, float* lse, int32_t BH, int32_t S, int32_t D,
                             int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
-                            const svg_band_shard_t* q_shard, const svg_band_shard_t* k_shard, const svg_attn_layout_t* layout, void* stream) {
+                            const svg_band_shard_t* q_shard, const svg_band_shard_t* k_shard, const svg_attn_layout_t* layout, void* stream,
+                            const BandOpts* sw = nullptr /* the switch entries: alt_mask and use_alt, both set */) {
     if (!q || !k || !v || !(o32 ? (void*)o32 : o) || !lse || !mask || !perm || !q_shard || !k_shard) return SVG_ERR_BAD_ARG;
+    if (sw && (!sw->alt_mask || !sw->use_alt)) return SVG_ERR_BAD_ARG;
     int rc = BH <= 0 ? SVG_ERR_BAD_ARG : check_band_shard_geometry(S, perm);
     if (rc == SVG_OK) rc = check_band_shard(q_shard, S, perm);
     if (rc == SVG_OK) rc = check_band_shard(k_shard, S, perm);
     if (rc != SVG_OK) return rc;
-    BandOpts opts;
+    BandOpts opts = sw ? *sw : BandOpts();
     opts.lse = lse, opts.o32 = o32, opts.q_shard = q_shard, opts.k_shard = k_shard;
     opts.strided = layout != nullptr;
     svg_attn_layout_t abi{};
@@ -704,6 +745,27 @@ extern "C" int svg_band_shard_attention_lse_f32(const void* q, const void* k, co
                                                 const svg_band_shard_t* k_shard, const svg_attn_layout_t* layout, void* stream) {
     if (!o32) return SVG_ERR_BAD_ARG;
     return band_shard_entry(q, k, v, nullptr, o32, lse, BH, S, D, dtype, sm_scale, mask, perm, q_shard, k_shard, layout, stream);
+}
+
+// The device switch of the shard entries (include/svg_attn_band_shard_switch.h): alt_mask and use_alt_flag join the first NULL check,
+// alt_mask is checked against S where band_dispatch checks mask.
+extern "C" int svg_band_shard_attention_switch_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S,
+                                                   int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
+                                                   const svg_perm_desc_t* perm, const svg_band_mask_t* alt_mask, const int32_t* use_alt_flag,
+                                                   const svg_band_shard_t* q_shard, const svg_band_shard_t* k_shard,
+                                                   const svg_attn_layout_t* layout, void* stream) {
+    const BandOpts sw = switch_opts(alt_mask, use_alt_flag);
+    return band_shard_entry(q, k, v, o, nullptr, lse, BH, S, D, dtype, sm_scale, mask, perm, q_shard, k_shard, layout, stream, &sw);
+}
+
+extern "C" int svg_band_shard_attention_switch_lse_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t BH,
+                                                       int32_t S, int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
+                                                       const svg_perm_desc_t* perm, const svg_band_mask_t* alt_mask,
+                                                       const int32_t* use_alt_flag, const svg_band_shard_t* q_shard,
+                                                       const svg_band_shard_t* k_shard, const svg_attn_layout_t* layout, void* stream) {
+    if (!o32) return SVG_ERR_BAD_ARG;
+    const BandOpts sw = switch_opts(alt_mask, use_alt_flag);
+    return band_shard_entry(q, k, v, nullptr, o32, lse, BH, S, D, dtype, sm_scale, mask, perm, q_shard, k_shard, layout, stream, &sw);
 }
 
 extern "C" int32_t svg_debug_band_shard_map(const svg_perm_desc_t* perm, int32_t S, const svg_band_shard_t* shard, int32_t token_major,

@@ -308,6 +308,15 @@ BAND_SHARD_SIGNATURES = {
 }
 BAND_SHARD_SIGNATURES["svg_band_shard_attention_lse_f32"] = BAND_SHARD_SIGNATURES["svg_band_shard_attention_lse"]
 
+# include/svg_attn_band_shard_switch.h: the device switch between two masks of the shard form, in a table of its own for the same reason
+# (tests/test_band_shard_switch_cpu.py)
+BAND_SHARD_SWITCH_SIGNATURES = {
+    "svg_band_shard_attention_switch_lse": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _F32, C.POINTER(BandMask),
+                                                      C.POINTER(PermDesc), C.POINTER(BandMask), _VP, C.POINTER(BandShard),
+                                                      C.POINTER(BandShard), C.POINTER(AttnLayout), _VP]),
+}
+BAND_SHARD_SWITCH_SIGNATURES["svg_band_shard_attention_switch_lse_f32"] = BAND_SHARD_SWITCH_SIGNATURES["svg_band_shard_attention_switch_lse"]
+
 # include/svg_attn_profile_shard.h: the online profiler's partial over one key shard and the combine over partials, in a table of its own
 # for the same reason (tests/test_profile_shard_cpu.py)
 PROFILE_SHARD_SIGNATURES = {
@@ -332,7 +341,8 @@ def load(strict: bool = True) -> Optional[C.CDLL]:
     try:
         lib = C.CDLL(str(p))
         for name, (res, args) in {**SIGNATURES, **SPARSE_LSE_SIGNATURES, **SPARSE_F32_SIGNATURES, **BAND_LSE_FORM_SIGNATURES,
-                                   **BAND_WINDOW_SIGNATURES, **BAND_SHARD_SIGNATURES, **PROFILE_SHARD_SIGNATURES}.items():
+                                   **BAND_WINDOW_SIGNATURES, **BAND_SHARD_SIGNATURES, **BAND_SHARD_SWITCH_SIGNATURES,
+                                   **PROFILE_SHARD_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -1152,7 +1162,7 @@ def band_shard_has_keys(mask: BandMask, num_tokens: int, perm, q_shard, k_shard,
 
 def _band_shard_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: BandMask, num_tokens: int, perm, q_shard, k_shard,
                           out_dtype: Optional[torch.dtype] = None, flags: Optional[torch.Tensor] = None,
-                          out: Optional[torch.Tensor] = None):
+                          out: Optional[torch.Tensor] = None, _switch=None):
     """Band attention of a FRAME SHARD of the rows over a FRAME SHARD of the keys (svg_band_shard_attention_lse[_f32]) -> (o, lse): q
     [cfg, H, Sq, D] (or [BH, Sq, D]) holds the rows of q_shard, k / v [cfg, H, Sk, D] those of k_shard — whole frames of the video, frame-
     major as the model stores them, and the rows of the shard's tail behind them (BandShard or (f0, n_frames, tail_begin, n_tail)) — of a
@@ -1163,13 +1173,20 @@ def _band_shard_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
     given in (a row that sees no key of the shard: o = 0, lse = -inf) — parts for merge_attention_states: the parts of one q shard over
     k shards that cover the sequence merge to the shard's rows of band_attention with the same flags.  Views (stride(-1) == 1) are read in
     place; what the layout cannot describe is copied.  out_dtype=torch.float32 (without out): (o32, lse), the rows before their rounding.
-    head_dim 128, bf16 / fp16, GPU tensors: anything else raises before anything runs — there is no fall-back."""
+    head_dim 128, bf16 / fp16, GPU tensors: anything else raises before anything runs — there is no fall-back.
+    _switch: (alt_mask, use_alt_flag) of band_shard_attention_switch — the svg_band_shard_attention_switch_lse[_f32] entries."""
     if out_dtype not in (None, torch.float32):
         raise ValueError(f"band_shard_attention: out_dtype is None (q's dtype) or torch.float32, got {out_dtype}")
     f32 = out_dtype == torch.float32
     if f32 and out is not None:
         raise ValueError("band_shard_attention(out_dtype=torch.float32): fp32 rows are parts for merge_attention_states, without out")
     _gpu(q, k, v, out, flags)
+    if _switch is not None:
+        alt_mask, use_alt_flag = _switch
+        _dev(use_alt_flag)
+        if use_alt_flag.dtype != torch.int32 or use_alt_flag.numel() < 1:
+            raise ValueError(f"band_shard_attention_switch: use_alt_flag is int32 [1] on the GPU, got {use_alt_flag.dtype} "
+                             f"{tuple(use_alt_flag.shape)}")
     if not (q.dim() == k.dim() == v.dim() and q.dim() in (3, 4) and k.shape == v.shape and q.shape[:-2] == k.shape[:-2]
             and q.shape[-1] == k.shape[-1] and q.dtype == k.dtype == v.dtype):
         raise ValueError(f"band_shard_attention: q [.., Sq, D], k / v [.., Sk, D] of one dtype, got {tuple(q.shape)}, {tuple(k.shape)}, "
@@ -1197,27 +1214,33 @@ def _band_shard_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
     lib = load()
     lse = empty(q.shape[:-1], dtype=torch.float32, device=q.device)
     pd = PermDesc(_ptr(flag), vid0, F, P)
-    geom = (BH, S, D, _dtype_code(q), _sm_scale(None, D), C.byref(mask), C.byref(pd), C.byref(qs), C.byref(ks))
+    geom = (BH, S, D, _dtype_code(q), _sm_scale(None, D), C.byref(mask), C.byref(pd))
+    name = "svg_band_shard_attention_lse"
+    if _switch is not None:   # the device switch: alt_mask and the flag behind perm, the entries of include/svg_attn_band_shard_switch.h
+        geom += (C.byref(alt_mask), use_alt_flag.data_ptr())
+        name = "svg_band_shard_attention_switch_lse"
+    geom += (C.byref(qs), C.byref(ks))
     if f32:
+        name += "_f32"
+        entry32 = getattr(lib, name)
         o32 = empty(q.shape, dtype=torch.float32, device=q.device)
 
         def call32(q, k, v, lay):
-            return lib.svg_band_shard_attention_lse_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), o32.data_ptr(), lse.data_ptr(), *geom, lay,
-                                                        _stream())
+            return entry32(q.data_ptr(), k.data_ptr(), v.data_ptr(), o32.data_ptr(), lse.data_ptr(), *geom, lay, _stream())
 
         if q.is_contiguous() and k.is_contiguous() and v.is_contiguous():
-            _check(call32(q, k, v, None), "svg_band_shard_attention_lse_f32")
-        elif not _window_views(q, k, v, q, "svg_band_shard_attention_lse_f32", lambda lay: call32(q, k, v, C.byref(lay))):
-            _check(call32(q.contiguous(), k.contiguous(), v.contiguous(), None), "svg_band_shard_attention_lse_f32")
+            _check(call32(q, k, v, None), name)
+        elif not _window_views(q, k, v, q, name, lambda lay: call32(q, k, v, C.byref(lay))):
+            _check(call32(q.contiguous(), k.contiguous(), v.contiguous(), None), name)
         return o32, lse
+    entry = getattr(lib, name)
 
     def run(q, k, v, out):
         o = empty_like(q, memory_format=torch.contiguous_format) if out is None else out
         if q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and o.is_contiguous():
-            _check(lib.svg_band_shard_attention_lse(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), *geom, None,
-                                                    _stream()), "svg_band_shard_attention_lse")
+            _check(entry(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), *geom, None, _stream()), name)
             return o
-        ok = _window_views(q, k, v, o, "svg_band_shard_attention_lse", lambda lay: lib.svg_band_shard_attention_lse(
+        ok = _window_views(q, k, v, o, name, lambda lay: entry(
             q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), *geom, C.byref(lay), _stream()))
         return o if ok else None
 
@@ -1228,6 +1251,23 @@ def _band_shard_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
 #  looks for their poison rows in its own file; the rows of this wrapper are in tests/test_gpu_band_shard.py, which also checks that the
 #  wrapper allocates through the switch.)
 band_shard_attention = _band_shard_attention
+
+
+def _band_shard_attention_switch(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: BandMask, alt_mask: BandMask,
+                                 use_alt_flag: torch.Tensor, num_tokens: int, perm, q_shard, k_shard,
+                                 out_dtype: Optional[torch.dtype] = None, flags: Optional[torch.Tensor] = None,
+                                 out: Optional[torch.Tensor] = None):
+    """band_shard_attention with a device-side switch (svg_band_shard_attention_switch_lse[_f32]) -> (o, lse) or, with
+    out_dtype=torch.float32, (o32, lse): `use_alt_flag` (int32 [1] on the GPU) == 0 gives band_shard_attention(mask, flags) bit for bit,
+    != 0 band_shard_attention(alt_mask, flags=None) — the alternate mask over the num_tokens rows of the whole sequence, every head in
+    logical order, `flags` not read — on the same two shards; no host read of the flag.  What a frame-sharded rank launches where an SVG1
+    processor switches between its sparse mask with the head placement and the dense warm-up mask without it.  Everything else — shapes,
+    views, out, what is refused — as band_shard_attention."""
+    return _band_shard_attention(q, k, v, mask, num_tokens, perm, q_shard, k_shard, out_dtype, flags, out, _switch=(alt_mask, use_alt_flag))
+
+
+# (bound by assignment like band_shard_attention; its poison rows are in tests/test_gpu_band_shard_switch.py)
+band_shard_attention_switch = _band_shard_attention_switch
 
 
 def cross_attention_supported(q: torch.Tensor, k: torch.Tensor) -> bool:

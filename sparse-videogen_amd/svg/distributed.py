@@ -17,7 +17,10 @@ the global coordinates of the two shards, and pairs of shards the mask rules out
 order, heads in logical order and token-major heads in one launch per step (svg_band_shard_attention_lse[_f32]).
 `token_sharded_sample_mse` is the online profiler of such a sequence — no K / V travels: the sampled q rows are exchanged, each rank streams
 its own shard into one partial (svg_sample_mse_shard_partial), the partials are gathered and merged to the same bits on every rank
-(svg_sample_mse_from_parts) — and `token_sharded_svg1_layer_call` chains the two: a sharded SVG1 layer-call from q, k, v alone.
+(svg_sample_mse_from_parts) — and `token_sharded_svg1_layer_call` chains the two: a sharded SVG1 layer-call from q, k, v alone.  Both
+carry the processors' device switch between the sparse and the dense warm-up mask (dense_mask / dense_flag:
+svg_band_shard_attention_switch_lse[_f32]), and `enable_frame_shards` is the mode in which the SVG1 processors of HunyuanVideo and Wan run
+them (svg/models/_core.py).
 """
 from __future__ import annotations
 
@@ -32,7 +35,7 @@ from . import _native
 # opt-in switch for the processors (svg/models/_core.py): svg.distributed.enable(group) makes every SVG1 / SVG2 layer-call run
 # this rank's heads only and all-gather the result; nothing changes for a process that never calls it.
 # ---------------------------------------------------------------------------------------------------------------
-_STATE: Dict[str, object] = {"enabled": False, "group": None}
+_STATE: Dict[str, object] = {"enabled": False, "group": None, "frames": False, "frames_group": None}
 
 
 def enable(group=None) -> None:
@@ -41,11 +44,36 @@ def enable(group=None) -> None:
     `shard_heads(H, rank, world)` and the outputs are all-gathered, so the caller sees the same tensors as on one GPU —
     bitwise, because nothing in the path mixes heads (the k-means stopping rule, a maximum over all heads, is all-reduced)."""
     assert dist.is_available() and dist.is_initialized(), "svg.distributed.enable: call torch.distributed.init_process_group first"
+    if _STATE["frames"]:
+        raise RuntimeError("svg.distributed.enable: frame-shard mode (enable_frame_shards) is on; disable() it first — one mode at a time")
     _STATE["enabled"], _STATE["group"] = True, group
 
 
+def enable_frame_shards(group=None) -> None:
+    """The second, separate mode: the SVG1 processors of HunyuanVideo and Wan receive q, k, v of ALL heads of this rank's whole frames
+    (`frame_shard(geometry, rank, world)`; the rows behind the video on the last rank) and run every layer-call through
+    token_sharded_svg1_layer_call / token_sharded_svg1_attention over the ranks of `group` — activations stay sharded by rows from one layer
+    to the next, K / V shards and the profiler's parts are what travels.  Equal to the single-GPU result to rounding.  The rotary tables
+    and the text are the caller's: its own rows of the tables, HunyuanVideo's text on the last rank.  Head sharding (enable) must be off."""
+    assert dist.is_available() and dist.is_initialized(), "svg.distributed.enable_frame_shards: call torch.distributed.init_process_group first"
+    if _STATE["enabled"]:
+        raise RuntimeError("svg.distributed.enable_frame_shards: head sharding (enable) is on; disable() it first — one mode at a time")
+    _STATE["frames"], _STATE["frames_group"] = True, group
+
+
 def disable() -> None:
+    """both modes off"""
     _STATE["enabled"], _STATE["group"] = False, None
+    _STATE["frames"], _STATE["frames_group"] = False, None
+
+
+def frame_shards_active() -> bool:
+    """frame-shard mode is on (whatever the group's size: a group of one rank holds the whole sequence and runs the same calls)"""
+    return bool(_STATE["frames"]) and dist.is_initialized()
+
+
+def frame_shards_group():
+    return _STATE["frames_group"]
 
 
 def active() -> bool:
@@ -466,20 +494,26 @@ def frame_shard(geometry, rank: int, world: int):
 _SHARD_KINDS = {"both": (False, True), "logical": (False,), "token_major": (True,)}
 
 
-def band_shard_exchange_plan(mask, geometry, world: int, kinds: str = "both") -> List[List[bool]]:
+def band_shard_exchange_plan(mask, geometry, world: int, kinds: str = "both", dense_mask=None) -> List[List[bool]]:
     """plan[r][s]: do the rows of rank r's shard (frame_shard) see any key of rank s's shard under `mask` — for ANY kind of head that
     occurs: kinds = "logical", "token_major", or "both" where the flags live on the device (no flag is read back)?  Host only, closed form
-    (_native.band_shard_has_keys); the same table on every rank.  A rank without rows neither sends nor receives."""
+    (_native.band_shard_has_keys); the same table on every rank.  A rank without rows neither sends nor receives.
+    dense_mask: the alternate mask of a device switch, whose flag is not read back either — the element-wise OR with the plan of
+    `dense_mask` for heads in logical order: a pair that either setting of the flag needs is kept."""
     S, vid0, F, P = (int(x) for x in geometry)
     sh = [frame_shard(geometry, r, world) for r in range(world)]
     rows = [_native.band_shard_rows(s, P) for s in sh]
-    return [[rows[r] > 0 and rows[s] > 0 and any(_native.band_shard_has_keys(mask, S, (vid0, F, P), sh[r], sh[s], kind)
+    plan = [[rows[r] > 0 and rows[s] > 0 and any(_native.band_shard_has_keys(mask, S, (vid0, F, P), sh[r], sh[s], kind)
                                                  for kind in _SHARD_KINDS[kinds]) for s in range(world)] for r in range(world)]
+    if dense_mask is not None:
+        alt = band_shard_exchange_plan(dense_mask, geometry, world, "logical")
+        plan = [[a or b for a, b in zip(ra, rb)] for ra, rb in zip(plan, alt)]
+    return plan
 
 
 def token_sharded_svg1_attention(q_local: torch.Tensor, k_local: torch.Tensor, v_local: torch.Tensor, mask, best_mask_idx, geometry,
                                  group=None, fp32_parts: bool = True, kinds: str = "both", attn_fn: Optional[Callable] = None,
-                                 merge_fn: Optional[Callable] = None) -> torch.Tensor:
+                                 merge_fn: Optional[Callable] = None, dense_mask=None, dense_flag=None) -> torch.Tensor:
     """One SVG1 layer-call over a sequence that lives sharded by whole frames: q_local, k_local, v_local [..., H, S_r, D] are ALL heads of
     this rank's rows `frame_shard(geometry, rank, world)` — its frames as the model stores them, on the last rank the text and padding
     behind them; best_mask_idx (int [BH] on the device, != 0: a token-major head) is what the device switch produced and is never read
@@ -492,7 +526,16 @@ def token_sharded_svg1_attention(q_local: torch.Tensor, k_local: torch.Tensor, v
     every kind of head in `kinds` sends nothing and computes nothing; every rank still enters the collective of a step.  attn_fn and
     merge_fn default to the native calls (_native.band_shard_attention, _native.merge_attention_states; fp32_parts: one rounding); they
     exist so that the schedule can be tested on gloo without a GPU.
-    Not wired into the processors or bench_step.py.  Equal to the single-GPU result to rounding, not bit for bit."""
+    dense_mask, dense_flag (both or neither, ValueError otherwise): the processors' device switch — dense_flag (int32 [1] on the device)
+    != 0 runs `dense_mask` (over num_tokens rows) with every head in logical order instead, decided by the kernel
+    (_native.band_shard_attention_switch); the flag is never read back, so the exchange keeps a pair that EITHER setting needs: the plan
+    is the element-wise OR of the plan of `mask` under `kinds` and the plan of `dense_mask` with heads in logical order
+    (band_shard_exchange_plan(..., dense_mask=dense_mask)), and the limit of MERGE_MAX_PARTS is checked on that.  An injected attn_fn
+    keeps its five arguments and looks after the flag itself.
+    What svg.models._core runs in frame-shard mode (enable_frame_shards); not wired into bench_step.py.  Equal to the single-GPU result
+    to rounding, not bit for bit."""
+    if (dense_mask is None) != (dense_flag is None):
+        raise ValueError("token_sharded_svg1_attention: dense_mask and dense_flag go together (the device switch), or neither")
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     S, vid0, F, P = (int(x) for x in geometry)
     sh = [frame_shard(geometry, r, world) for r in range(world)]
@@ -500,13 +543,16 @@ def token_sharded_svg1_attention(q_local: torch.Tensor, k_local: torch.Tensor, v
     S_me = n_tok[rank]
     assert q_local.shape[-2] == S_me and k_local.shape == v_local.shape and k_local.shape[-2] == S_me, (
         f"rank {rank} holds {q_local.shape[-2]} / {k_local.shape[-2]} rows, frame_shard says {S_me}")
-    plan = band_shard_exchange_plan(mask, geometry, world, kinds)
+    plan = band_shard_exchange_plan(mask, geometry, world, kinds, dense_mask=dense_mask)
     most = max(sum(row) for row in plan)
     if most > MERGE_MAX_PARTS:
         raise ValueError(f"token_sharded_svg1_attention: a rank sees the keys of {most} shards, but merge_attention_states takes at most "
                          f"{MERGE_MAX_PARTS} parts — use a group of at most {MERGE_MAX_PARTS} ranks")
     if attn_fn is None:
         def attn_fn(q, k, v, q_shard, k_shard):
+            if dense_mask is not None:
+                return _native.band_shard_attention_switch(q, k, v, mask, dense_mask, dense_flag, S, (vid0, F, P), q_shard, k_shard,
+                                                           out_dtype=torch.float32 if fp32_parts else None, flags=best_mask_idx)
             return _native.band_shard_attention(q, k, v, mask, S, (vid0, F, P), q_shard, k_shard,
                                                 out_dtype=torch.float32 if fp32_parts else None, flags=best_mask_idx)
     if merge_fn is None:
@@ -589,7 +635,7 @@ def token_sharded_sample_mse(q_local: torch.Tensor, k_local: torch.Tensor, v_loc
     partial_fn and combine_fn default to the native calls (_native.sample_mse_shard_partial, _native.sample_mse_from_parts, both with
     skip_flag); they exist so that the schedule can be tested on gloo without a GPU.  A partial_fn whose parts are not fp32 says so in an
     attribute `part_dtype` (the neutral part of a rank without rows is made in it).
-    Not wired into the processors or bench_step.py.  Equal to sample_mse on the whole sequence to rounding, not bit for bit."""
+    Not wired into bench_step.py.  Equal to sample_mse on the whole sequence to rounding, not bit for bit."""
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     S, vid0, F, P = (int(x) for x in geometry)
     if world > _native.PROFILE_MAX_PARTS:
@@ -635,16 +681,25 @@ def token_sharded_sample_mse(q_local: torch.Tensor, k_local: torch.Tensor, v_loc
 def token_sharded_svg1_layer_call(q_local: torch.Tensor, k_local: torch.Tensor, v_local: torch.Tensor, mask, prof, geometry, rows: torch.Tensor,
                                   group=None, fp32_parts: bool = True, partial_fn: Optional[Callable] = None,
                                   combine_fn: Optional[Callable] = None, attn_fn: Optional[Callable] = None,
-                                  merge_fn: Optional[Callable] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                                  merge_fn: Optional[Callable] = None, dense_mask=None, dense_flag=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """One SVG1 layer-call of a sequence that lives sharded by whole frames, from q, k, v alone: token_sharded_sample_mse picks each head's
     mask — the MSEs rounded to q's dtype before the argmin as svg.models._core.sample_mse rounds them, so two candidates that round to one
     value tie to index 0 and NaN wins — and token_sharded_svg1_attention(..., best_mask_idx, kinds="both") runs the attention under it.
     Returns (o_local [..., H, S_r, D], best_mask_idx int64 [BH], the same on every rank and never read back).  The *_fn arguments go to the two
-    schedules (tests on gloo without a GPU).  Not wired into the processors or bench_step.py."""
-    mse = token_sharded_sample_mse(q_local, k_local, v_local, rows, prof, geometry, group=group, partial_fn=partial_fn, combine_fn=combine_fn)
+    schedules (tests on gloo without a GPU).
+    dense_mask, dense_flag (both or neither): the processors' device switch — dense_flag (int32 [1] on the device, never read back and
+    nothing synchronises) is the profiler's skip_flag and the attention's switch (token_sharded_svg1_attention); the returned best_mask_idx
+    is -1 on a dense step, as svg.models._core.svg1_attention_device_switch returns it.
+    What svg.models._core runs in frame-shard mode; not wired into bench_step.py."""
+    if (dense_mask is None) != (dense_flag is None):
+        raise ValueError("token_sharded_svg1_layer_call: dense_mask and dense_flag go together (the device switch), or neither")
+    mse = token_sharded_sample_mse(q_local, k_local, v_local, rows, prof, geometry, group=group, skip_flag=dense_flag, partial_fn=partial_fn,
+                                   combine_fn=combine_fn)
     best_mask_idx = torch.argmin(mse.to(q_local.dtype), dim=0)
     o_local = token_sharded_svg1_attention(q_local, k_local, v_local, mask, best_mask_idx, geometry, group=group, fp32_parts=fp32_parts,
-                                           kinds="both", attn_fn=attn_fn, merge_fn=merge_fn)
+                                           kinds="both", attn_fn=attn_fn, merge_fn=merge_fn, dense_mask=dense_mask, dense_flag=dense_flag)
+    if dense_flag is not None:
+        best_mask_idx = torch.where(dense_flag.reshape(()) != 0, torch.full_like(best_mask_idx, -1), best_mask_idx)
     return o_local, best_mask_idx
 
 

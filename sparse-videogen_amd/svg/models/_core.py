@@ -158,15 +158,120 @@ def _state_kw(what: str, return_lse: bool, out_dtype, q_prescaled: bool, token_m
     return dict(return_lse=True, out_dtype=out_dtype, token_major_out=token_major_out and out_dtype is None)
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# Frame-shard mode (svg.distributed.enable_frame_shards): q, k, v are [cfg, H, S_r, D] — ALL heads of this rank's rows
+# frame_shard((geo.seq_len, geo.vid0, geo.num_frame, geo.frame_size), rank, world) — and every layer-call is one of the token-sharded
+# schedules of svg/distributed.py.  What has no shard form is refused here, on the host, before any collective: every condition is the
+# same on every rank, so all ranks raise together.
+# ---------------------------------------------------------------------------------------------------------------
+FRAME_SHARD_MAX_SAMPLED_ROWS = 64   # svg_sample_mse_shard_partial (include/svg_attn_profile_shard.h): sampled rows of one call
+
+
+def rows_of_this_rank(what: str, geo: Geometry, shard_form: bool = True) -> int:
+    """The rows an attention_core_logic receives: geo.seq_len — or, in frame-shard mode, the rows of this rank's frame_shard of the
+    sequence.  shard_form False (the SVG2 processors, CogVideoX, Cosmos): frame-shard mode is refused."""
+    if not _dist.frame_shards_active():
+        return geo.seq_len
+    if not shard_form:
+        raise NotImplementedError(f"{what}: frame-shard mode (svg.distributed.enable_frame_shards) exists for the SVG1 processors of "
+                                  f"HunyuanVideo and Wan only")
+    if geo.vid0 > 0:
+        raise NotImplementedError(f"{what}: frame-shard mode needs the video at row 0; {geo.vid0} rows in front of it belong to no shard")
+    group = _dist.frame_shards_group()
+    shard = _dist.frame_shard((geo.seq_len, geo.vid0, geo.num_frame, geo.frame_size), torch.distributed.get_rank(group),
+                              torch.distributed.get_world_size(group))
+    return _native.band_shard_rows(shard, geo.frame_size)
+
+
+def _one_mask(what: str, mask, cfg: int):
+    """the one mask of a batch in frame-shard mode: per-video masks must be equal"""
+    pm = per_video(mask, cfg, what)
+    if pm is None:
+        return mask
+    vals, _ = video_groups(pm)
+    if len(vals) > 1:
+        raise NotImplementedError(f"{what}: frame-shard mode takes ONE mask (one text length) for the batch; per-video masks that differ "
+                                  f"have no shard form")
+    return vals[0]
+
+
+def _frame_shard_setup(what: str, q, k, v, geo: Geometry, num_sampled_rows: Optional[int] = None, q_prescaled: bool = False,
+                       return_lse: bool = False, out_dtype=None, fused: bool = True):
+    """The refusals of frame-shard mode, each naming its limit; -> (geometry, group).  num_sampled_rows None: a call without the profiler
+    (dense_attention), which also takes fp16."""
+    if q_prescaled:
+        raise ValueError(f"{what}: frame-shard mode takes a plain q (the shard kernels have no pre-scaled form); got q_prescaled = True")
+    if _use_fp8(q):
+        raise NotImplementedError(f"{what}: frame-shard mode runs the 16-bit kernels only; fp8 attention (set_attention_dtype('fp8')) has no "
+                                  f"shard form")
+    if not fused:
+        raise NotImplementedError(f"{what}: frame-shard mode is the fused path only (fused=False places heads over the whole sequence)")
+    if return_lse or out_dtype is not None:
+        raise NotImplementedError(f"{what}: frame-shard mode returns o only (return_lse / out_dtype: the merged rows carry no lse)")
+    dtypes = (torch.bfloat16,) if num_sampled_rows is not None else (torch.bfloat16, torch.float16)
+    if q.dtype not in dtypes or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise NotImplementedError(f"{what}: frame-shard mode takes {' / '.join(str(d) for d in dtypes)} (the shard profiler is bfloat16 "
+                                  f"only), got {q.dtype}")
+    if q.shape[-1] != 128:
+        raise NotImplementedError(f"{what}: frame-shard mode takes head_dim 128 (the shard kernels), got {q.shape[-1]}")
+    if num_sampled_rows is not None and min(num_sampled_rows, geo.seq_len) > FRAME_SHARD_MAX_SAMPLED_ROWS:
+        raise NotImplementedError(f"{what}: frame-shard mode samples at most {FRAME_SHARD_MAX_SAMPLED_ROWS} rows (the shard profiler), got "
+                                  f"{min(num_sampled_rows, geo.seq_len)}")
+    if geo.vid0 > 0:
+        raise NotImplementedError(f"{what}: frame-shard mode needs the video at row 0; {geo.vid0} rows in front of it (CogVideoX's text) "
+                                  f"belong to no shard")
+    group = _dist.frame_shards_group()
+    world = torch.distributed.get_world_size(group)
+    if world > _dist.MERGE_MAX_PARTS:
+        raise ValueError(f"{what}: frame-shard mode over {world} ranks, but merge_attention_states takes at most {_dist.MERGE_MAX_PARTS} parts — "
+                         f"use a group of at most {_dist.MERGE_MAX_PARTS} ranks")
+    _require_gpu(q, what)
+    return (geo.seq_len, geo.vid0, geo.num_frame, geo.frame_size), group
+
+
+def _frame_shard_svg1(what: str, q, k, v, geo: Geometry, mask, dense_mask, prof, num_sampled_rows: int, sample_max_row: int, dense_flag,
+                      **refusable):
+    """svg1_attention_device_switch (dense_mask, dense_flag given) / svg1_sparse_attention (both None) in frame-shard mode:
+    -> (out [cfg, H, S_r, D], best_mask_idx [cfg, H]).  The sampled rows are GLOBAL rows of the whole sequence, drawn from the
+    broadcast-seeded generator of the switched path on both: every rank draws the same."""
+    cfg, H = q.shape[0], q.shape[1]
+    mask = _one_mask(f"{what}(mask)", mask, cfg)
+    if dense_mask is not None:
+        dense_mask = _one_mask(f"{what}(dense_mask)", dense_mask, cfg)
+    geometry, group = _frame_shard_setup(what, q, k, v, geo, num_sampled_rows, **refusable)
+    n = min(num_sampled_rows, geo.seq_len)
+    rows = torch.randint(low=0, high=sample_max_row, size=(n,), generator=_switch_generator())
+    out, best = _dist.token_sharded_svg1_layer_call(q, k, v, mask, prof, geometry, rows, group=group, dense_mask=dense_mask,
+                                                    dense_flag=dense_flag)
+    return out, best.reshape(cfg, H)
+
+
 @time_logging_decorator("Level 3 - Dense Flash Attention")
 def dense_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, valid_len=None, q_prescaled: bool = False, return_lse: bool = False,
-                    out_dtype=None):
+                    out_dtype=None, geometry: Optional[Geometry] = None):
     """Dense attention [cfg, H, S, D].  valid_len < S: two independent segments [0, valid) and [valid, S) — what the
     reference gets from flash_attn_varlen_func with cu_seqlens [0, valid, S] (hyvideo/attention.py:452-470).
     valid_len: one int for the batch, or a sequence of cfg ints, one per video (see video_groups).
     q_prescaled: q carries sm_scale * log2(e) (see qkv_from_projections(q_scale=...)); GPU only.
     return_lse: (out, lse), the softmax state of every row as _native.band_attention returns it; out_dtype=torch.float32: fp32 rows.  GPU,
-    head_dim 128, plain q (ValueError), not under svg.distributed (NotImplementedError)."""
+    head_dim 128, plain q (ValueError), not under svg.distributed (NotImplementedError).
+    geometry: the Geometry of the WHOLE sequence — required in frame-shard mode (svg.distributed.enable_frame_shards; ValueError without
+    it), where q, k, v hold this rank's rows and the call is token_sharded_svg1_attention under the dense mask with every head in logical
+    order; ignored otherwise."""
+    if _dist.frame_shards_active():
+        if geometry is None:
+            raise ValueError("dense_attention: frame-shard mode needs geometry= (the Geometry of the whole sequence; the tensors hold this "
+                             "rank's rows only)")
+        lens = per_video(valid_len, q.shape[0], "dense_attention(valid_len)")
+        if lens is not None:
+            vals, _ = video_groups([int(x) for x in lens])
+            if len(vals) > 1:
+                raise NotImplementedError("dense_attention: frame-shard mode takes ONE valid_len for the batch; per-video lengths that "
+                                          "differ have no shard form")
+            valid_len = vals[0]
+        geo_t, group = _frame_shard_setup("dense_attention", q, k, v, geometry, None, q_prescaled, return_lse, out_dtype)
+        return _dist.token_sharded_svg1_attention(q, k, v, _dense_band_mask(geometry.seq_len, valid_len), None, geo_t, group=group,
+                                                  kinds="logical")
     S = q.shape[2]
     kw = _state_kw("dense_attention", return_lse, out_dtype, q_prescaled, TOKEN_MAJOR_IO and not _dist.active())
     lens = per_video(valid_len, q.shape[0], "dense_attention(valid_len)")
@@ -286,19 +391,19 @@ _SWITCH_SEED = None
 def reseed_switch_generator(seed: Optional[int] = None) -> None:
     """(Re)build the CPU generator of the device-switched path from `seed` (default: the global seed, torch.initial_seed()).
     Called by svg.utils.seed.seed_everything and by the replace_*_attention install hooks, so that seeding a second video in the
-    same process resets the sampled profiler rows exactly like a fresh process.  Under svg.distributed.enable() the seed of rank
-    0 is broadcast: every rank draws the same rows, whatever it was seeded with (the sharded result equals the single-GPU one)."""
+    same process resets the sampled profiler rows exactly like a fresh process.  Under svg.distributed.enable() (and
+    enable_frame_shards()) the seed of rank 0 is broadcast: every rank draws the same rows, whatever it was seeded with (the sharded result equals the single-GPU one)."""
     global _SWITCH_GEN, _SWITCH_SEED
     base = torch.initial_seed() if seed is None else int(seed)
     use = base
-    if _dist.active():
-        grp = _dist.current_group()
+    if _dist.active() or _dist.frame_shards_active():
+        grp = _dist.current_group() if _dist.active() else _dist.frame_shards_group()
         on_gpu = torch.distributed.get_backend(grp) == "nccl"
         t = torch.tensor([base % (2 ** 63)], dtype=torch.int64, device="cuda" if on_gpu else "cpu")
         torch.distributed.broadcast(t, src=torch.distributed.get_global_rank(grp, 0) if grp is not None else 0, group=grp)
         use = int(t.item())
     _SWITCH_GEN = torch.Generator().manual_seed(use % (2 ** 63))
-    _SWITCH_SEED = (base, _dist.active())
+    _SWITCH_SEED = (base, _dist.active() or _dist.frame_shards_active())
 
 
 def _switch_generator():
@@ -308,7 +413,7 @@ def _switch_generator():
     torch.initial_seed() changes (a later torch.manual_seed) or sharding is switched on, and by `reseed_switch_generator()`, which
     the seeding / install hooks call (re-seeding with the SAME seed cannot be seen from the seed alone).  (Deviation: at equal seeds
     the sampled rows differ from the reference's; every other consumer of the global CPU RNG sees the reference's stream.)"""
-    if _SWITCH_GEN is None or _SWITCH_SEED != (torch.initial_seed(), _dist.active()):
+    if _SWITCH_GEN is None or _SWITCH_SEED != (torch.initial_seed(), _dist.active() or _dist.frame_shards_active()):
         reseed_switch_generator()
     return _SWITCH_GEN
 
@@ -331,7 +436,13 @@ def svg1_attention_device_switch(q, k, v, geo: Geometry, mask: "_native.BandMask
     mask, dense_mask: one BandMask for the batch, or a sequence of cfg of them, one per video (see video_groups).
     return_lse: (out, best_mask_idx, lse) with the softmax state of every row under the mask the flag selects, as
     _native.band_attention_switch returns it — the layer-call as one part of a partitioned attention (merge_attention_states);
-    out_dtype=torch.float32: fp32 rows.  Plain q only (ValueError), not under svg.distributed (NotImplementedError)."""
+    out_dtype=torch.float32: fp32 rows.  Plain q only (ValueError), not under svg.distributed (NotImplementedError).
+    Frame-shard mode (svg.distributed.enable_frame_shards): q, k, v [cfg, H, S_r, D] are all heads of this rank's frame_shard of the
+    sequence `geo` describes, the call is token_sharded_svg1_layer_call with dense_mask / dense_flag, -> (out [cfg, H, S_r, D], best);
+    what has no shard form raises before any collective (_frame_shard_setup)."""
+    if _dist.frame_shards_active():   # q, k, v: this rank's rows; -> (out [cfg, H, S_r, D], best_mask_idx)
+        return _frame_shard_svg1("svg1_attention_device_switch", q, k, v, geo, mask, dense_mask, prof, num_sampled_rows, sample_max_row,
+                                 dense_flag, q_prescaled=q_prescaled, return_lse=return_lse, out_dtype=out_dtype)
     kw = _state_kw("svg1_attention_device_switch", return_lse, out_dtype, q_prescaled, TOKEN_MAJOR_IO)
     _require_gpu(q, "SVG1 attention")
     cfg, H = q.shape[0], q.shape[1]
@@ -374,7 +485,12 @@ def svg1_sparse_attention(q, k, v, geo: Geometry, mask: "_native.BandMask", prof
     on the prompt length, so the profiling pass is the same either way.
     return_lse: (out, best_mask_idx, lse) with the softmax state of every row, as _native.band_attention returns it;
     out_dtype=torch.float32: fp32 rows.  The fused 16-bit path with a plain q only (ValueError), not under svg.distributed
-    (NotImplementedError)."""
+    (NotImplementedError).
+    Frame-shard mode: as svg1_attention_device_switch, without a flag; the rows come from the switched path's generator (every rank
+    draws the same)."""
+    if _dist.frame_shards_active():   # q, k, v: this rank's rows; -> (out [cfg, H, S_r, D], best_mask_idx)
+        return _frame_shard_svg1("svg1_sparse_attention", q, k, v, geo, mask, None, prof, num_sampled_rows, sample_max_row, None,
+                                 q_prescaled=q_prescaled, return_lse=return_lse, out_dtype=out_dtype, fused=fused)
     kw = _state_kw("svg1_sparse_attention", return_lse, out_dtype, q_prescaled, TOKEN_MAJOR_IO, fp8=_use_fp8(q), fused=fused)
     _require_gpu(q, "SVG1 sparse attention")
     groups = None

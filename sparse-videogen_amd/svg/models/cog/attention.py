@@ -101,7 +101,8 @@ class CogVideoX_SparseAttn_Processor2_0:
     def attention_core_logic(self, query, key, value, timestep):
         cfg, num_heads, seq_len, dim = query.size()
         geo = self.geometry()
-        assert seq_len == geo.seq_len, (
+        # (frame-shard mode, svg.distributed.enable_frame_shards, is refused: the text in FRONT of the video belongs to no shard)
+        assert seq_len == _core.rows_of_this_rank(type(self).__name__, geo, shard_form=False), (
             f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
         # ref :173-176 — Cog's warm-up thresholds are fractions of 42 layers / 1000 timesteps
         first_layers, first_times = 42 * self.first_layers_fp, 1000 * (1 - self.first_times_fp)

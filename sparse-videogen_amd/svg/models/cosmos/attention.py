@@ -32,6 +32,8 @@ def apply_rotary_emb_half(x: torch.Tensor, freqs_cis) -> torch.Tensor:
 class _CosmosPlumbing:
     """QKV / per-head RMSNorm / half-split RoPE / output projection of the Cosmos processors (ref :40-124)."""
 
+    frame_shard_form = False   # (svg.distributed.enable_frame_shards: HunyuanVideo and Wan only; refused in attention_core_logic)
+
     @time_logging_decorator("Level 2 - qkv")
     def get_qkv(self, attn, hidden_states, encoder_hidden_states):
         return attn.to_q(hidden_states), attn.to_k(encoder_hidden_states), attn.to_v(encoder_hidden_states)

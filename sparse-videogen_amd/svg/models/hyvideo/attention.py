@@ -280,6 +280,9 @@ class Hunyuan_SVGAttn_Processor2_0(_HunyuanProcessorBase):
     block_mask = None      # svg_band_mask_t descriptor (what the reference's flex BlockMask encodes)
     fused_placement = True  # fold both layout transformations into the attention kernel (bit-identical result)
     device_switch = True    # dense / sparse decision on the device when the timestep is a GPU tensor (no read-back per forward)
+    # frame-shard mode (svg.distributed.enable_frame_shards): query, key, value hold all heads of this rank's whole frames, on the last rank
+    # the text behind them; the masks, the profiler and the sampled rows stay those of the whole sequence.  False (SVG2): refused.
+    frame_shard_form = True
     prescale_q = False      # opt-in (flex_attention's PRESCALE_QK trade-off, see _HunyuanProcessorBase.prescale_q): q leaves the fused prologue carrying the softmax scale
 
     def __init__(self, layer_idx):
@@ -301,8 +304,9 @@ class Hunyuan_SVGAttn_Processor2_0(_HunyuanProcessorBase):
     def attention_core_logic(self, query, key, value, timestep, layer_idx, cu_max_seqlens):
         cfg, num_heads, seq_len, dim = query.size()
         geo = self.geometry()
-        assert seq_len == geo.seq_len, (
+        assert seq_len == _core.rows_of_this_rank(type(self).__name__, geo, self.frame_shard_form), (
             f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
+        total = geo.seq_len   # (seq_len, except in frame-shard mode: the masks and the sampled rows are the whole sequence's)
         valid = self.video_valid_lens(cu_max_seqlens, cfg, geo.video_length)
         # the layer test is host data; the timestep test stays on the device when the timestep is a GPU tensor (device_switch)
         dense_flag = None
@@ -311,7 +315,7 @@ class Hunyuan_SVGAttn_Processor2_0(_HunyuanProcessorBase):
             dense_flag = _core.dense_flag_on_device(timestep, self.first_times_fp)
         pre = self._q_prescaled
         if dense_flag is None and _core.is_full_attention(self.layer_idx, timestep, self.first_layers_fp, self.first_times_fp):
-            return _core.dense_attention(query, key, value, valid, q_prescaled=pre).reshape(cfg, num_heads, seq_len, dim)
+            return _core.dense_attention(query, key, value, valid, q_prescaled=pre, geometry=geo).reshape(cfg, num_heads, seq_len, dim)
         mask = self.block_mask   # (a tuple: one mask per video, as prompt_length)
         if mask is None:
             raise RuntimeError("Hunyuan_SVGAttn_Processor2_0.block_mask is not set: call replace_hyvideo_attention first")
@@ -319,14 +323,14 @@ class Hunyuan_SVGAttn_Processor2_0(_HunyuanProcessorBase):
             raise ValueError(f"Hunyuan_SVGAttn_Processor2_0: block_mask has {len(mask)} entries for a batch of {cfg} videos")
         prof = profile_desc(geo.context_length, geo.num_frame, geo.frame_size)
         if dense_flag is not None:
-            dense = tuple(dense_mask(seq_len, int(x)) for x in valid) if isinstance(valid, tuple) else dense_mask(seq_len, int(valid))
+            dense = tuple(dense_mask(total, int(x)) for x in valid) if isinstance(valid, tuple) else dense_mask(total, int(valid))
             out, best = _core.svg1_attention_device_switch(query, key, value, geo, mask, dense, prof,
-                                                           self.num_sampled_rows, min(self.sample_mse_max_row, seq_len), dense_flag,
+                                                           self.num_sampled_rows, min(self.sample_mse_max_row, total), dense_flag,
                                                            q_prescaled=pre)
             self.last_best_mask_idx = best
             return out.reshape(cfg, num_heads, seq_len, dim)
         out, best = _core.svg1_sparse_attention(query, key, value, geo, mask, prof, self.num_sampled_rows,
-                                                min(self.sample_mse_max_row, seq_len), fused=self.fused_placement, q_prescaled=pre)
+                                                min(self.sample_mse_max_row, total), fused=self.fused_placement, q_prescaled=pre)
         self.last_best_mask_idx = best
         return out.reshape(cfg, num_heads, seq_len, dim)
 
@@ -357,6 +361,7 @@ class Hunyuan_SAPAttn_Processor2_0(Hunyuan_SVGAttn_Processor2_0):
 
     logging_file = None
     prescale_q = False   # k-means and the block map work on the plain q
+    frame_shard_form = False   # (k-means over the whole video: no frame-shard mode)
     centroid_store = CentroidStore()  # class-level like the reference's dicts; `reset_state()` clears it
 
     @classmethod
@@ -368,7 +373,7 @@ class Hunyuan_SAPAttn_Processor2_0(Hunyuan_SVGAttn_Processor2_0):
     def attention_core_logic(self, query, key, value, timestep, layer_idx, cu_max_seqlens):
         cfg, num_heads, seq_len, dim = query.size()
         geo = self.geometry()
-        assert seq_len == geo.seq_len, (
+        assert seq_len == _core.rows_of_this_rank(type(self).__name__, geo, self.frame_shard_form), (
             f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
         valid = self.video_valid_lens(cu_max_seqlens, cfg, geo.video_length)
         if _core.is_full_attention(self.layer_idx, timestep, self.first_layers_fp, self.first_times_fp):

@@ -241,16 +241,21 @@ class WanAttn_SVGAttn_Processor2_0:
         return _core.sample_mse(query, key, value, geo, profile_desc(geo.context_length, geo.num_frame, geo.frame_size),
                                 self.num_sampled_rows, min(self.sample_mse_max_row, query.shape[2]), q_prescaled=self._q_prescaled)
 
+    # frame-shard mode (svg.distributed.enable_frame_shards): query, key, value hold all heads of this rank's whole frames; the masks, the
+    # profiler and the sampled rows stay those of the whole sequence (geometry()).  False (SVG2, Cosmos): the mode is refused.
+    frame_shard_form = True
+
     @time_logging_decorator("Level 3 - Dense Flash Attention")
     def flash_attention(self, query, key, value):
-        return _core.dense_attention(query, key, value, q_prescaled=self._q_prescaled)
+        return _core.dense_attention(query, key, value, q_prescaled=self._q_prescaled, geometry=self.geometry())
 
     @time_logging_decorator("Level 2 - attention core logic")
     def attention_core_logic(self, query, key, value, timestep):
         cfg, num_heads, seq_len, dim = query.size()
         geo = self.geometry()
-        assert seq_len == geo.seq_len, (
+        assert seq_len == _core.rows_of_this_rank(type(self).__name__, geo, self.frame_shard_form), (
             f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
+        total = geo.seq_len   # (seq_len, except in frame-shard mode: the masks and the sampled rows are the whole sequence's)
         dense_flag = None   # (device-side dense / sparse switch, see the Hunyuan processor)
         if self.device_switch and _core.attention_dtype() == "bf16" and self.fused_placement and self.layer_idx >= self.first_layers_fp and self.block_mask is not None \
                 and query.is_cuda:
@@ -261,13 +266,13 @@ class WanAttn_SVGAttn_Processor2_0:
             raise RuntimeError("WanAttn_SVGAttn_Processor2_0.block_mask is not set: call replace_wan_attention first")
         prof = profile_desc(geo.context_length, geo.num_frame, geo.frame_size)
         if dense_flag is not None:
-            out, best = _core.svg1_attention_device_switch(query, key, value, geo, self.block_mask, dense_mask(seq_len), prof,
-                                                           self.num_sampled_rows, min(self.sample_mse_max_row, seq_len), dense_flag,
+            out, best = _core.svg1_attention_device_switch(query, key, value, geo, self.block_mask, dense_mask(total), prof,
+                                                           self.num_sampled_rows, min(self.sample_mse_max_row, total), dense_flag,
                                                            q_prescaled=self._q_prescaled)
             self.last_best_mask_idx = best
             return out.reshape(cfg, num_heads, seq_len, dim)
         out, best = _core.svg1_sparse_attention(query, key, value, geo, self.block_mask, prof, self.num_sampled_rows,
-                                                min(self.sample_mse_max_row, seq_len), fused=self.fused_placement,
+                                                min(self.sample_mse_max_row, total), fused=self.fused_placement,
                                                 q_prescaled=self._q_prescaled)
         self.last_best_mask_idx = best
         return out.reshape(cfg, num_heads, seq_len, dim)
@@ -307,6 +312,7 @@ class WanAttn_SAPAttn_Processor(WanAttn_SVGAttn_Processor2_0):
 
     logging_file = None
     prescale_q = False   # k-means and the block map work on the plain q
+    frame_shard_form = False   # (k-means over the whole video: no frame-shard mode)
 
     def __init__(self, layer_idx):
         super().__init__(layer_idx)
@@ -319,7 +325,7 @@ class WanAttn_SAPAttn_Processor(WanAttn_SVGAttn_Processor2_0):
     def attention_core_logic(self, query, key, value, timestep):
         cfg, num_heads, seq_len, dim = query.size()
         geo = self.geometry()
-        assert seq_len == geo.seq_len, (
+        assert seq_len == _core.rows_of_this_rank(type(self).__name__, geo, self.frame_shard_form), (
             f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
         if _core.is_full_attention(self.layer_idx, timestep, self.first_layers_fp, self.first_times_fp):
             if self.zero_step_kmeans_init and query.is_cuda:
