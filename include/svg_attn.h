@@ -741,7 +741,20 @@ int svg_band_attention_prescaled_notify_seg(const void* q_scaled, const void* k,
  * keys k0[0 .. n) are resolved in this order as a wave of the kernel resolves them — a tile that follows the latest one by 64 keys and
  * lies wholly inside the range takes the stepped form, every other tile the division — and out[64 * i + r] receives the physical row of
  * row r of tile i (0 for rows behind S); cheap (or NULL) receives per tile whether the stepped form was taken.  Returns n; -1: bad
- * arguments or out_words < 64 * n. */
+ * arguments or out_words < 64 * n.
+ * svg_debug_band_tile_run: the tile run of the 16x16x32 band kernels, on the host (no GPU needed).  For wave `wave` (0 .. 7) of q-tile qt
+ * (row order) of a head over S rows under `mask` — video rows [vid0, vid0 + num_frame * frame_size), token-major or contiguous;
+ * num_frame = 0: no video — and a request distance dist (2 for the leading, 3 for the lagging waves of the kernel), out4 receives
+ * { run_lo, run_n, key tiles of the q-tile, q-tiles per head }: the key tiles [run_lo, run_lo + run_n) are the ones whose vector phase
+ * makes no per-tile decision — the tile is unmasked by the wave's fast-path interval and follows its predecessor by 64 keys, and the
+ * tile that phase resolves, dist + 1 further, lies in the same segment and takes the stepped form of the row cursor.  tiles (or NULL)
+ * receives four words per key tile, each evaluated with the per-tile functions the kernel uses outside a run: { first key, unmasked by
+ * the fast-path interval, follows its predecessor by 64 keys, the tile dist + 1 further exists and takes the stepped form }.  rows (or
+ * NULL) receives rows[64 * t + r], the physical row of row r of key tile t as the kernel's walk — run form inside the run — resolves
+ * it.  Returns the number of key tiles; -1: bad arguments, tiles_words < 4 * tiles or rows_words < 64 * tiles. */
+int32_t svg_debug_band_tile_run(int32_t S, const svg_band_mask_t* mask, int32_t vid0, int32_t num_frame, int32_t frame_size,
+                                int32_t token_major, int32_t qt, int32_t wave, int32_t dist, int32_t* out4, int32_t* tiles,
+                                int32_t tiles_words, int32_t* rows, int32_t rows_words);
 int32_t svg_band_queue_order(int32_t BH, int32_t S, const svg_band_mask_t* mask, int32_t* out, int32_t out_words);
 int svg_debug_band_queue_cap(int32_t max_workgroups);
 int64_t svg_debug_band_replays(int32_t reset);

@@ -1093,6 +1093,68 @@ extern "C" int32_t svg_debug_band_row_cursor(int32_t S, int32_t vid0, int32_t nu
     return n;
 }
 
+// the tile run of one wave of one q-tile of the 16x16x32 band body and the walk that uses it, on the host with the parameters a launch would
+// build and the functions the kernel calls (see include/svg_attn.h)
+extern "C" int32_t svg_debug_band_tile_run(int32_t S, const svg_band_mask_t* mask, int32_t vid0, int32_t num_frame, int32_t frame_size,
+                                           int32_t token_major, int32_t qt, int32_t wave, int32_t dist, int32_t* out4, int32_t* tiles,
+                                           int32_t tiles_words, int32_t* rows, int32_t rows_words) {
+    using Pol = svg::BandPolicy<__bf16, 128, 8>;
+    if (S <= 0 || !mask || !out4 || wave < 0 || wave >= 8 || dist < 1 || dist > 8 || qt < 0) return -1;
+    if (num_frame <= 0 && token_major) return -1;
+    const int64_t flag = 1;   // (never read: the builder only asks whether the call names token-major heads)
+    const svg_perm_desc_t perm{&flag, vid0, num_frame, frame_size};
+    const svg_perm_desc_t* pd = num_frame > 0 ? &perm : nullptr;
+    if (check_band_mask(S, mask, pd) != SVG_OK) return -1;
+    const Pol::Params p = svg::make_band_params<Pol, __bf16>(nullptr, nullptr, nullptr, nullptr, 1, S, 1.f, mask, pd);
+    if (qt >= p.nqt) return -1;
+    Pol::Ctx c{};
+    c.perm = token_major != 0;
+    Pol::kv_schedule(p, c, qt);
+    Pol::wave_fast_interval(p, c, wave, c.fk_lo, c.fk_hi);
+    const int nT = c.nT;
+    if ((tiles && (int64_t)tiles_words < (int64_t)nT * 4) || (rows && (int64_t)rows_words < (int64_t)nT * kBN)) return -1;
+    Pol::RowWalk w0;
+    Pol::row_walk_init(p, c, w0);
+    int run_lo = 0, run_n = 0;
+    Pol::tile_run(c, w0, dist, run_lo, run_n);
+    out4[0] = run_lo, out4[1] = run_n, out4[2] = nT, out4[3] = p.nqt;
+    if (tiles) {   // per tile, with the generic functions: first key, FULL by the fast-path interval, follows its predecessor, N(t)'s tile steps
+        for (int t = 0; t < nT; ++t) {
+            const int k0 = Pol::tile_key0(c, t);
+            tiles[4 * t] = k0;
+            tiles[4 * t + 1] = Pol::fast_full(c, k0) ? 1 : 0;
+            tiles[4 * t + 2] = (t > 0 && k0 == Pol::tile_key0(c, t - 1) + kBN) ? 1 : 0;
+            int cheap = 0;
+            if (t + dist + 1 < nT) {
+                Pol::RowWalk probe = w0;
+                probe.prev_k0 = Pol::tile_key0(c, t + dist);   // the latest resolved tile when N(t) runs
+                cheap = Pol::row_walk_cheap(probe, Pol::tile_key0(c, t + dist + 1)) ? 1 : 0;
+            }
+            tiles[4 * t + 3] = cheap;
+        }
+    }
+    if (rows) {   // one lane's walk per row of a tile, in the kernel's order: tiles 0 .. dist in front of the loop, tile t + dist + 1 in N(t)
+        for (int row = 0; row < kBN; ++row) {
+            Pol::RowWalk w = w0;
+            int phys = 0;
+            for (int t = 0; t <= dist && t < nT; ++t) {
+                Pol::row_walk_next(p, w, phys, Pol::tile_key0(c, t), row);
+                rows[(size_t)t * kBN + row] = phys;
+            }
+            for (int t = 0; t + dist + 1 < nT; ++t) {   // (all of these lie in the unguarded loop; the guarded tail resolves nothing)
+                Pol::row_walk_step(w, phys);
+                if ((unsigned)(t - run_lo) < (unsigned)run_n) Pol::row_walk_in_run(w);
+                else {   // (as attn_m16_tile spells it)
+                    const int k_next = Pol::tile_key0(c, t + dist + 1);
+                    if (!Pol::row_walk_cheap(w, k_next)) Pol::row_walk_exact(p, w, phys, k_next, row);
+                }
+                rows[(size_t)(t + dist + 1) * kBN + row] = phys;
+            }
+        }
+    }
+    return nT;
+}
+
 // the traces of the last traced launch (diagnostics builds; SVG_ERR_UNSUPPORTED otherwise)
 extern "C" int svg_debug_wg_trace(uint64_t* out, int n_workgroups) { return g_trace_reader(out, true, n_workgroups); }
 extern "C" int svg_debug_pp_trace(uint64_t* out104) { return g_trace_reader(out104, false, 0); }

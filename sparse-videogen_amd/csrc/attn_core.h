@@ -68,6 +68,11 @@ __device__ __forceinline__ i16x8 lds_read_tr16x2(const char* p_lo, const char* p
 //        (physical row >= 0; rows that do not exist return 0 and MUST be masked by classify/allowed)
 //   optional, kRowCursor (attn_m16.h HasRowCursor): struct RowWalk; row_walk_init(prm, ctx, walk);
 //        row_walk_next(prm, walk, phys, tile_key0, row_in_tile) steps the lane's row in place — tiles in increasing order, as kv_phys
+//   optional, with kRowCursor: kTileRun == true (attn_m16.h HasTileRun; false or absent: every tile decides for itself) and
+//        tile_run(ctx, walk, dist, run_lo, run_n): the tiles [run_lo, run_lo + run_n) of this wave are FULL, follow their predecessor, and
+//        the tile dist + 1 further takes the cheap step; row_walk_next in its parts for the body that skips the decisions there —
+//        row_walk_step(walk, phys) the per-lane step of every tile, row_walk_in_run(walk) the bookkeeping of a tile inside the run,
+//        bool row_walk_cheap(walk, tile_key0) / row_walk_exact(prm, walk, phys, tile_key0, row_in_tile) the decision and the exact path outside it
 //   int  tile_key0(ctx, t)                                       logical index of the first key of tile t
 //   int  classify(prm, ctx, tile_key0, wave_row0)                wave-uniform TileClass
 //   bool allowed(prm, ctx, q_logical, k_logical)                 element predicate for PARTIAL tiles

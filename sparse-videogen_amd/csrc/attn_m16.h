@@ -183,6 +183,34 @@ struct HasRowCursor : std::false_type {};
 template <typename P>
 struct HasRowCursor<P, std::void_t<decltype(P::kRowCursor)>> : std::true_type {};
 
+// Tile run (detected: a policy whose kTileRun is true, band_policy.h BandPolicy::tile_run; every other policy — those without the member and
+// those that set it to false — compiles the per-tile decisions it had): inside [run_lo, run_lo + run_n), computed once per q-tile and wave,
+// the vector phase knows that its tile is FULL and that the tile it resolves takes the cheap step, so the scalar unit runs one compare and
+// one add there instead of tile_key0 twice, row_walk_cheap and classify.
+template <typename P, typename = void>
+struct HasTileRun : std::false_type {};
+template <typename P>
+struct HasTileRun<P, std::enable_if_t<P::kTileRun>> : std::true_type {};
+// the parts of the cursor's step the run form calls: P's for a policy with tile runs; for every other policy stand-ins that are never executed
+// (the run form is compiled out by a constant there) and only have to compile inside the generic lambda of the vector phase
+template <typename P, bool = HasTileRun<P>::value>
+struct TileRunOps {
+    template <typename... A> static __device__ __forceinline__ void step(A&...) {}
+    template <typename... A> static __device__ __forceinline__ void in_run(A&...) {}
+    template <typename... A> static __device__ __forceinline__ bool cheap(A&...) { return true; }
+    template <typename... A> static __device__ __forceinline__ void exact(A&...) {}
+};
+template <typename P>
+struct TileRunOps<P, true> {
+    using W = typename P::RowWalk;
+    static __device__ __forceinline__ void step(const W& w, int& phys) { P::row_walk_step(w, phys); }
+    static __device__ __forceinline__ void in_run(W& w) { P::row_walk_in_run(w); }
+    static __device__ __forceinline__ bool cheap(W& w, const int& k0) { return P::row_walk_cheap(w, k0); }
+    static __device__ __forceinline__ void exact(const typename P::Params& p, const W& w, int& phys, const int& k0, const int& row) {
+        P::row_walk_exact(p, w, phys, k0, row);
+    }
+};
+
 // pp_barrier_if for a predicate that is already a scalar: the workgroup barrier where (flag != 0) == when_set.  One scalar serves
 // both barriers of a tile (leading / lagging waves keep opposite ones), and nothing is fetched from a VGPR.
 template <bool when_set>
@@ -331,6 +359,12 @@ __device__ __forceinline__ bool attn_m16_tile(const typename P::Params& prm, con
         dma_piece(t, std::integral_constant<int, 1>{});
     };
     const int dist = lagging ? 3 : 2;   // tile u + dist is requested in N(u)
+    constexpr bool kRun = kCursor && HasTileRun<P>::value;
+    int run_lo = 0, run_n = 0;          // tile run of this wave: two scalars of the q-tile
+    if constexpr (kRun) {
+        P::tile_run(ctx, cur, dist, run_lo, run_n);
+        run_lo = __builtin_amdgcn_readfirstlane(run_lo), run_n = __builtin_amdgcn_readfirstlane(run_n);
+    }
     for (int t = 0; t < dist; ++t) {
         resolve(t, kGuarded);
         take();
@@ -439,11 +473,37 @@ __device__ __forceinline__ bool attn_m16_tile(const typename P::Params& prm, con
     // vector phase of tile t on sc: mask, probabilities, sum check, (rare) exact path, DMA requests, DMA wait
     auto vector_phase = [&](int t, auto guard_c) {
         constexpr bool guard = decltype(guard_c)::value;
-        stage_resolve_next(t, guard_c);
+        constexpr bool run_form = kRun && !guard;   // (runs lie inside the unguarded loop)
+        int tk0 = 0, cls = TILE_FULL;
+        if constexpr (run_form) {
+            // The per-lane step is common to the tiles inside and outside the run; the scalar decisions — which tile comes next, whether it
+            // steps, what this tile's class is — are made outside the run only.  The exact path stays the one-armed branch around an
+            // in-place write that row_walk_next has: what it tests is a scalar both ways.
+            using R = TileRunOps<P>;
+            const bool in_run = (unsigned)(t - run_lo) < (unsigned)run_n;
+            take();
+            R::step(cur, nnext);
+            dma_piece(t + dist, std::integral_constant<int, 0>{});
+            bool cheap = true;
+            int k_next = 0;
+            if (__builtin_expect(in_run, 1)) {
+                R::in_run(cur);
+            } else {
+                k_next = P::tile_key0(ctx, t + dist + 1);
+                cheap = R::cheap(cur, k_next);
+                tk0 = P::tile_key0(ctx, t);
+                cls = P::classify(prm, ctx, tk0, wave * 32);
+            }
+            if (__builtin_expect(!cheap, 0)) R::exact(prm, cur, nnext, k_next, krow);
+        } else {
+            stage_resolve_next(t, guard_c);
+        }
         const bool more = !guard || t + dist < nT;
-        if (more) dma_piece(t + dist, std::integral_constant<int, 0>{});
-        const int tk0 = P::tile_key0(ctx, t);
-        const int cls = P::classify(prm, ctx, tk0, wave * 32);
+        if constexpr (!run_form) {
+            if (more) dma_piece(t + dist, std::integral_constant<int, 0>{});
+            tk0 = P::tile_key0(ctx, t);
+            cls = P::classify(prm, ctx, tk0, wave * 32);
+        }
         if (cls != TILE_FULL) {
             const bool part = (cls == TILE_PARTIAL);  // a tile this wave does not need at all is processed fully masked
 #pragma unroll

@@ -142,15 +142,24 @@ struct BandPolicy : LayoutAccess<BandPolicy<T, D, NW, RB>> {
         c.head = head;
         c.perm = (p.head_flag != nullptr) && (p.head_flag[c.head] != 0);
         kv_schedule(p, c, qt);
-        const int real = p.real_len;
         // fast-path classification: inside the band, away from its edges, every (row, key) pair of a wave x tile
         // rectangle is allowed; those tiles (98-99 % of all) are recognised with two scalar compares.
-        const int w0 = c.q0 + wave_id() * kWR, w1 = min(w0 + kWR, c.q_end);
-        c.fk_lo = 1, c.fk_hi = 0;
+        wave_fast_interval(p, c, wave_id(), c.fk_lo, c.fk_hi);
+    }
+    // the fast-path interval [lo, hi] of first keys for the rows of wave `wave` of the q-tile c describes (empty: lo > hi).  Also evaluated on
+    // the host (svg_debug_band_tile_run).
+    static __host__ __device__ __forceinline__ void wave_fast_interval(const Params& p, const Ctx& c, int wave, int& lo, int& hi) {
+#ifndef __HIP_DEVICE_COMPILE__   // (device: HIP's min / max, as init_tile always used them — std's select the other way round, and the
+        using std::max;            //  listings of every kernel on this policy would move)
+        using std::min;
+#endif
+        const int real = p.real_len;
+        const int w0 = c.q0 + wave * kWR, w1 = min(w0 + kWR, c.q_end);
+        lo = 1, hi = 0;
         if (w0 < c.q_end && w1 <= real) {
             const bool full_rows = w0 >= p.rf_lo && w1 <= p.rf_hi;   // a wave of full (text) rows: every key tile below real_len
-            c.fk_lo = full_rows ? 0 : max(w1 - p.band, 0);
-            c.fk_hi = min(full_rows ? real : w0 + p.band - kBN, min(real, p.S) - kBN);
+            lo = full_rows ? 0 : max(w1 - p.band, 0);
+            hi = min(full_rows ? real : w0 + p.band - kBN, min(real, p.S) - kBN);
         }
     }
 
@@ -213,7 +222,7 @@ struct BandPolicy : LayoutAccess<BandPolicy<T, D, NW, RB>> {
         const int l = c.q0 + row;
         return l < c.q_end ? phys_row(p, c, l) : -1;
     }
-    static __device__ __forceinline__ int tile_key0(const Ctx& c, int t) {
+    static __host__ __device__ __forceinline__ int tile_key0(const Ctx& c, int t) {
         // selects, not branches: this runs once per tile on the scalar unit of every wave
         const int n01 = c.seg_n[0] + c.seg_n[1];
         const int a = c.seg_lo[0] + t, b = c.seg_lo[1] + (t - c.seg_n[0]), d = c.seg_lo[2] + (t - n01);
@@ -282,7 +291,7 @@ struct BandPolicy : LayoutAccess<BandPolicy<T, D, NW, RB>> {
         return st.l < p.S ? phys : 0;
     }
     // wave-uniform: every (row, key) pair of this wave's rows x the tile at key k0 is allowed (the per-wave interval of init())
-    static __device__ __forceinline__ bool fast_full(const Ctx& c, int k0) { return k0 >= c.fk_lo && k0 <= c.fk_hi; }
+    static __host__ __device__ __forceinline__ bool fast_full(const Ctx& c, int k0) { return k0 >= c.fk_lo && k0 <= c.fk_hi; }
     static __device__ __forceinline__ void kv_cursor_init(const Params&, const Ctx&, KvCursor& cu, int) {
         cu.physv = 0, cu.f = 0, cu.prev_k0 = -(1 << 30);
     }
@@ -395,9 +404,53 @@ struct BandPolicy : LayoutAccess<BandPolicy<T, D, NW, RB>> {
     // "divided" costs two copies of the cursor per tile.  A tile of the exact path steps first and overwrites the result.)
     static __host__ __device__ __forceinline__ void row_walk_next(const Params& p, RowWalk& w, int& phys, int k0, int row) {
         const bool cheap = row_walk_cheap(w, k0);
+        row_walk_step(w, phys);
+        if (__builtin_expect(!cheap, 0)) row_set(phys, row_exact(p, w.vlen, k0 + row));
+    }
+    // row_walk_next in its two halves, for a caller that knows of some tiles that they take the cheap step (tile_run below): the per-lane
+    // step, which every tile takes, then row_walk_cheap and, where it says no, row_walk_exact; inside a run row_walk_in_run stands for those two.
+    static __host__ __device__ __forceinline__ void row_walk_step(const RowWalk& w, int& phys) {
         row_add(phys, w.step);
         if (w.perm) row_add(phys, phys >= w.end ? w.unwrap : 0);
-        if (__builtin_expect(!cheap, 0)) row_set(phys, row_exact(p, w.vlen, k0 + row));
+    }
+    static __host__ __device__ __forceinline__ void row_walk_exact(const Params& p, const RowWalk& w, int& phys, int k0, int row) {
+        row_set(phys, row_exact(p, w.vlen, k0 + row));
+    }
+    static __host__ __device__ __forceinline__ void row_walk_in_run(RowWalk& w) { w.prev_k0 += kBN; }
+
+    // Tile run of the 16x16x32 body (attn_m16.h picks it by HasTileRun; a policy that overrides classify or row_walk_next sets kTileRun =
+    // false).  For one wave of a q-tile the tiles t for which the vector phase N(t) has nothing to decide form one interval
+    // [run_lo, run_lo + run_n):
+    //   (a) tile t is FULL by the fast-path interval, fk_lo <= tile_key0(t) <= fk_hi;
+    //   (b) tile t follows tile t - 1 in its segment, tile_key0(t) == tile_key0(t - 1) + kBN;
+    //   (c) the tile N(t) resolves, t + dist + 1, lies in the same segment (so it exists and follows t + dist, the latest resolved one)
+    //       and takes the cheap step: its first key lies in [w.lo, w.hi].
+    // All three are intervals of the tile's index inside a segment.  The fast-path interval lies inside ONE segment of a band q-tile (the
+    // band's, with which a neighbouring column range has been merged; text rows have one segment), so there is one run; written per segment,
+    // the longest wins.  A tile of a run has t + dist + 1 < nT: runs lie inside the unguarded steady-state loop.
+    static constexpr bool kTileRun = true;
+    static __host__ __device__ __forceinline__ void tile_run(const Ctx& c, const RowWalk& w, int dist, int& run_lo, int& run_n) {
+        using std::max;
+        using std::min;
+        static_assert(kBN == 64, "tile_run divides by the tile size with a shift");
+        run_lo = 0, run_n = 0;
+        const int ahead = (dist + 1) * kBN;
+        const int k_lo = max(c.fk_lo, w.lo - ahead), k_hi = min(c.fk_hi, w.hi - ahead);   // first keys that satisfy (a) and the range of (c)
+        int t0 = 0;
+        // (written out per segment: a loop index into the arrays of Ctx could send them through scratch.  x >> 6: the floor for a negative x)
+#define SVG_RUN_SEG(i)                                                                         \
+    {                                                                                          \
+        const int n = c.seg_n[i];                                                              \
+        if (n > dist + 2) {                                                                    \
+            const int kf = c.seg_lo[i] * kBN;                                                  \
+            const int j_lo = max(1, (k_lo - kf + kBN - 1) >> 6);                               \
+            const int j_hi = min(n - dist - 2, (k_hi - kf) >> 6);                              \
+            if (j_hi - j_lo + 1 > run_n) run_lo = t0 + j_lo, run_n = j_hi - j_lo + 1;          \
+        }                                                                                      \
+        t0 += n;                                                                               \
+    }
+        SVG_RUN_SEG(0) SVG_RUN_SEG(1) SVG_RUN_SEG(2)
+#undef SVG_RUN_SEG
     }
 
     static __device__ __forceinline__ int classify(const Params& p, const Ctx& c, int k0, int wrow0) {
@@ -528,6 +581,7 @@ template <typename BasePol>
 struct BandWindowOf : BasePol {
     using Ctx = typename BasePol::Ctx;
     using RowWalk = typename BasePol::RowWalk;
+    static constexpr bool kTileRun = false;   // classify and row_walk_next are this policy's own: the per-tile decisions stay
     struct Params : BasePol::Params {
         int q_begin, Sq;       // row window [q_begin, q_begin + Sq): what q / o / lse / o32 hold
         int k_begin, k_end;    // key window [k_begin, k_end): what k / v hold; k_begin % kBN == 0
@@ -647,6 +701,7 @@ struct BandShardMap {
 template <typename BasePol>
 struct BandShardOf : BasePol {
     using RowWalk = typename BasePol::RowWalk;
+    static constexpr bool kTileRun = false;   // classify and row_walk_next are this policy's own: the per-tile decisions stay
     struct Ctx : BasePol::Ctx {
         int gw0, gw1;   // per WAVE: the coordinates of its rows lie in [gw0, gw1) (gw0 >= gw1: an idle wave)
     };

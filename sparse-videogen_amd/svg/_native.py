@@ -145,6 +145,7 @@ SIGNATURES = {
     "svg_debug_band_queue_cap": (C.c_int, [_I32]),
     "svg_debug_band_replays": (C.c_int64, [_I32]),
     "svg_debug_band_row_cursor": (_I32, [_I32, _I32, _I32, _I32, _I32, _VP, _I32, _VP, _I32, _VP]),
+    "svg_debug_band_tile_run": (_I32, [_I32, C.POINTER(BandMask), _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _VP, _I32]),
     "svg_rms_norm_forward": (C.c_int, [_VP, _VP, C.c_int64, _I32, _I32, C.c_float, _VP]),
     "svg_layer_norm_forward": (C.c_int, [_VP, _VP, _VP, C.c_int64, _I32, _I32, _VP]),
     "svg_apply_qk_rope_inplace_cossin": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP]),
