@@ -72,75 +72,23 @@ __global__ __launch_bounds__(512, 2) void band_attn_pp2_frozen_kernel(typename B
 // softmax on every eighth tile and validate the q-tile after its loop (SPEC, attn_m16.h); fp16 and the pre-scaled forms do not.
 static __device__ unsigned g_band_replays;   // q-tiles that failed the validation and were replayed (svg_debug_band_replays)
 constexpr int kTailLds = 16;                 // bytes behind the stages: the queue's slot (two words), the word of the validation, one free
-template <typename T>
-__global__ __launch_bounds__(512, 2) void band_attn_m16_kernel(typename BandPolicy<T, 128, 8>::Params prm) {
+// One template for every form on the static mapping; the policy is the only thing that differs between the instantiations, and each
+// instantiation's listing is compared with the one it had as a kernel of its own (tools/asm_diff.py --pair, profiles/kernel_templates_asm_diff.txt).
+//   BandPolicy<T, 128, 8>                          svg_band_attention: the plain kernel
+//   BandLsePolicy / BandF32Policy                  svg_band_attention_lse[_f32]: the epilogue of attn_m16_tile also stores one fp32 per query
+//                                                  row; the fp32 policy stores the rows as fp32, before their rounding, and no 16-bit o
+//   BandWindowLsePolicy / BandWindowF32Policy      svg_band_window_attention_lse[_f32]: a row window of q / o / lse and a key window of k / v
+//                                                  under the mask at its global coordinates, over the q-tiles of the row window
+//   BandShardLsePolicy / BandShardF32Policy        svg_band_shard_attention_lse[_f32]: a frame shard of the rows over a frame shard of the keys,
+//                                                  heads in logical order and token-major heads in one launch, the mask at the coordinates the
+//                                                  shard maps give, over the q-tiles of the q shard
+// The same template arguments of the body for all of them, SPEC and the replay counter included, so o keeps the bits of the plain entry — also
+// where a window or two shards are the whole sequence.  A q-tile that fails its validation returns before the epilogue and stores nothing
+// (neither o nor lse nor o32); its replay stores them all.
+template <typename T, typename Pol>
+__global__ __launch_bounds__(512, 2) void band_attn_m16_kernel(typename Pol::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_body_m16<T, BandPolicy<T, 128, 8>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
-}
-// LSE form (svg_band_attention_lse): band_attn_m16_kernel on BandLsePolicy — the same template arguments, SPEC and the replay counter
-// included, so o keeps the bits of the plain entry; the epilogue of attn_m16_tile also stores one fp32 per query row.  A q-tile that fails
-// its validation returns before the epilogue and stores neither o nor lse; its replay stores both.  The static mapping; the queue form is
-// band_attn_lse_m16_queue_kernel below.  (Its own kernel template: the kernels above and below keep their symbols and their listings.)
-template <typename T>
-__global__ __launch_bounds__(512, 2) void band_attn_lse_m16_kernel(typename BandLsePolicy<T>::Params prm) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_body_m16<T, BandLsePolicy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
-}
-// fp32 form (svg_band_attention_lse_f32): the LSE kernel on BandF32Policy — the same template arguments, SPEC and the replay counter
-// included; the epilogue stores the rows as fp32, before their rounding, and no 16-bit o.  A q-tile that fails its validation stores
-// nothing; its replay stores o32 and lse.  (Its own kernel template: the other kernels keep their symbols and their listings.)
-template <typename T>
-__global__ __launch_bounds__(512, 2) void band_attn_f32_m16_kernel(typename BandF32Policy<T>::Params prm) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_body_m16<T, BandF32Policy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
-}
-// Window forms (svg_band_window_attention_lse[_f32]): the two kernels above on BandWindowLsePolicy / BandWindowF32Policy (band_policy.h) —
-// a row window of q / o / lse and a key window of k / v under the mask at its global coordinates; the same template arguments, SPEC and
-// the replay counter included, so a window that is the whole sequence keeps the siblings' bits.  Static mapping over the q-tiles of the
-// row window.  (Their own kernel templates: the other kernels keep their symbols and their listings.)
-template <typename T>
-__global__ __launch_bounds__(512, 2) void band_window_lse_m16_kernel(typename BandWindowLsePolicy<T>::Params prm) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_body_m16<T, BandWindowLsePolicy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
-}
-template <typename T>
-__global__ __launch_bounds__(512, 2) void band_window_f32_m16_kernel(typename BandWindowF32Policy<T>::Params prm) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_body_m16<T, BandWindowF32Policy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
-}
-// Shard forms (svg_band_shard_attention_lse[_f32]): the same two kernels on BandShardLsePolicy / BandShardF32Policy (band_policy.h) — a
-// frame shard of the rows over a frame shard of the keys, heads in logical order and token-major heads in one launch, the mask at the
-// coordinates the shard maps give; the same template arguments, SPEC and the replay counter included, so two shards that are the whole
-// sequence keep the siblings' bits.  Static mapping over the q-tiles of the q shard.  (Their own kernel templates, as above.)
-template <typename T>
-__global__ __launch_bounds__(512, 2) void band_shard_lse_m16_kernel(typename BandShardLsePolicy<T>::Params prm) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_body_m16<T, BandShardLsePolicy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
-}
-template <typename T>
-__global__ __launch_bounds__(512, 2) void band_shard_f32_m16_kernel(typename BandShardF32Policy<T>::Params prm) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_body_m16<T, BandShardF32Policy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
-}
-// Device switch of the shard forms (svg_band_shard_attention_switch_lse[_f32], include/svg_attn_band_shard_switch.h): `flag[0] != 0`
-// selects prm_alt — the alternate mask on the same two shards, every head in logical order (no head flags) — as
-// band_attn_lse_m16_switch_kernel does on the whole sequence; the template arguments of the two kernels above, so either flag value keeps
-// their bits.  Static mapping over the q-tiles of the larger block; o / lse (o32) at the shard row q was read from under either block.
-template <typename T>
-__global__ __launch_bounds__(512, 2) void band_shard_lse_m16_switch_kernel(typename BandShardLsePolicy<T>::Params prm,
-                                                                           typename BandShardLsePolicy<T>::Params prm_alt,
-                                                                           const int32_t* __restrict__ flag) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (flag[0] != 0) attn_body_m16<T, BandShardLsePolicy<T>, false, 1, false, true>(prm_alt, smem, nullptr, &g_band_replays);
-    else attn_body_m16<T, BandShardLsePolicy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
-}
-template <typename T>
-__global__ __launch_bounds__(512, 2) void band_shard_f32_m16_switch_kernel(typename BandShardF32Policy<T>::Params prm,
-                                                                           typename BandShardF32Policy<T>::Params prm_alt,
-                                                                           const int32_t* __restrict__ flag) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (flag[0] != 0) attn_body_m16<T, BandShardF32Policy<T>, false, 1, false, true>(prm_alt, smem, nullptr, &g_band_replays);
-    else attn_body_m16<T, BandShardF32Policy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
+    attn_body_m16<T, Pol, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
 }
 // pre-scaled q on the 16x16x32 body (PRE form of attn_body_m16)
 template <typename T>
@@ -152,10 +100,14 @@ __global__ __launch_bounds__(512, 2) void band_attn_m16q_kernel(typename BandPol
 // running one q-tile after another until the queue is dry.  What band_dispatch launches for head_dim 128 when there are more q-tiles
 // than compute units, unless the call counts completions (those rely on the head-major order of the static mapping) or no counter
 // block is to be had; the device-switched kernel below keeps the static mapping.  Per row the same keys in the same order with the same arithmetic: bit-identical output.
-template <typename T, bool PRE = false>
-__global__ __launch_bounds__(512, 2) void band_attn_m16_queue_kernel(typename BandPolicy<T, 128, 8>::Params prm, BandQueue qd) {
+// One template, and so one copy of the loop: the policy (BandPolicy<T, 128, 8>, plain and PRE; BandLsePolicy where svg_band_attention_lse takes
+// the queue) is the only thing that differs between the instantiations, and each one's listing is checked as for band_attn_m16_kernel.  The
+// policy is an argument of the kernel and the loop is NOT a function the kernels share: with the loop factored out the listings came out
+// different.  The fp32 policy has no queue form: its instantiation reserved 36 bytes of scratch per lane, so svg_band_attention_lse_f32 keeps
+// the static mapping.
+template <typename T, typename Pol, bool PRE = false>
+__global__ __launch_bounds__(512, 2) void band_attn_m16_queue_kernel(typename Pol::Params prm, BandQueue qd) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    using Pol = BandPolicy<T, 128, 8>;
     int* const slot = (int*)(smem + attn_m16_lds_bytes());   // (head, q-tile) of the next work item, from lane 0 to the workgroup
     // SPEC of attn_m16_tile (plain bf16): a q-tile whose validation failed leaves slot[2] = 1 and stores nothing.  Lane 0 then takes no
     // new work item and marks the slot 2 — the same (head, q-tile) once more, with the overflow test on every tile — and after that
@@ -197,78 +149,22 @@ __global__ __launch_bounds__(512, 2) void band_attn_m16_queue_kernel(typename Ba
     }
     if (threadIdx.x == 0) qd.leave(gridDim.x);
 }
-// LSE form of the queue kernel (svg_band_attention_lse where band_dispatch takes the queue): the loop of band_attn_m16_queue_kernel<T, false>
-// on BandLsePolicy — the same slot protocol, take / decode / leave and replay; bit-identical to band_attn_lse_m16_kernel.  (A copy of
-// the loop, not a function both kernels share: with the loop factored out the listings of the kernel above came out different.  The
-// fp32 policy has no queue form: its instantiation reserved 36 bytes of scratch per lane, so svg_band_attention_lse_f32 keeps the static
-// mapping.)
-template <typename T>
-__global__ __launch_bounds__(512, 2) void band_attn_lse_m16_queue_kernel(typename BandLsePolicy<T>::Params prm, BandQueue qd) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    using Pol = BandLsePolicy<T>;
-    int* const slot = (int*)(smem + attn_m16_lds_bytes());   // (head, q-tile) of the next work item, from lane 0 to the workgroup
-    // (slot[2]: the verdict of the validation, 0 / 1 / 2 as in band_attn_m16_queue_kernel)
-    constexpr bool kSpec = std::is_same_v<T, __bf16>;
-    int dry = 0;
-    if constexpr (kSpec) {
-        if (threadIdx.x == 0) slot[2] = 0;
-    }
-    for (;;) {
-        if (threadIdx.x == 0) {
-            bool fresh = true;
-            if constexpr (kSpec) {
-                fresh = __builtin_amdgcn_readfirstlane(slot[2]) != 1;   // (a scalar: one lane is active here)
-                slot[2] = fresh ? 0 : 2;
-            }
-            if (fresh) {
-                const int xcd = __builtin_amdgcn_s_getreg((31 << 11) | 20) & (kNumXCD - 1);   // HW_REG_XCC_ID
-                int head = -1, qt = 0;
-                const int w = qd.take(xcd, dry);
-                if (w >= 0) qd.decode(w, head, qt);
-                slot[0] = head, slot[1] = qt;
-            }
-        }
-        __syncthreads();
-        const int head = __builtin_amdgcn_readfirstlane(slot[0]), qt = __builtin_amdgcn_readfirstlane(slot[1]);
-        if (head < 0) break;
-        typename Pol::Ctx ctx;
-        Pol::init_tile(prm, ctx, head, qt);
-        if constexpr (kSpec) {
-            const int check_mask = __builtin_amdgcn_readfirstlane(slot[2]) == 2 ? 0 : kCheckEvery - 1;
-            attn_m16_tile<T, Pol, false, 1, false, true>(prm, ctx, smem, check_mask, &g_band_replays);
-        } else {
-            attn_m16_tile<T, Pol, false, 1, false>(prm, ctx, smem);
-        }
-    }
-    if (threadIdx.x == 0) qd.leave(gridDim.x);
-}
-// device-side switch between two masks on the 16x16x32 body (svg_band_attention_switch[_prescaled] at head_dim 128): `flag[0] != 0` selects prm_alt
-template <typename T, bool PRE = false>
-__global__ __launch_bounds__(512, 2) void band_attn_m16_switch_kernel(typename BandPolicy<T, 128, 8>::Params prm,
-                                                                      typename BandPolicy<T, 128, 8>::Params prm_alt,
+// Device-side switch between two masks on the 16x16x32 body: `flag[0] != 0` selects prm_alt.  Static mapping over the q-tiles of the
+// larger block; SPEC and the replay counter as in band_attn_m16_kernel (not in the PRE form), so either flag value keeps the bits of the
+// single-mask kernel.  One template; the policy is the only thing that differs between the instantiations, and each one's listing is
+// checked as for band_attn_m16_kernel:
+//   BandPolicy<T, 128, 8>, plain and PRE           svg_band_attention_switch[_prescaled] at head_dim 128
+//   BandLsePolicy / BandF32Policy                  svg_band_attention_switch_lse[_f32]: lse (and o32) are indexed by the physical q row under the
+//                                                  parameter block the flag selects — prm_alt carries no head permutation, so its rows are the logical ones
+//   BandShardLsePolicy / BandShardF32Policy        svg_band_shard_attention_switch_lse[_f32] (include/svg_attn_band_shard_switch.h): the alternate
+//                                                  mask on the same two shards, every head in logical order (no head flags); o / lse (o32) at
+//                                                  the shard row q was read from under either block
+template <typename T, typename Pol, bool PRE = false>
+__global__ __launch_bounds__(512, 2) void band_attn_m16_switch_kernel(typename Pol::Params prm, typename Pol::Params prm_alt,
                                                                       const int32_t* __restrict__ flag) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (flag[0] != 0) attn_body_m16<T, BandPolicy<T, 128, 8>, false, 1, PRE, !PRE>(prm_alt, smem, nullptr, &g_band_replays);
-    else attn_body_m16<T, BandPolicy<T, 128, 8>, false, 1, PRE, !PRE>(prm, smem, nullptr, &g_band_replays);
-}
-// LSE / fp32 forms of the device switch (svg_band_attention_switch_lse[_f32]): band_attn_m16_switch_kernel<T, false> on BandLsePolicy /
-// BandF32Policy — static mapping over the q-tiles of the larger mask, SPEC and the replay counter as there.  lse (and o32) are indexed by
-// the physical q row under the parameter block the flag selects: prm_alt carries no head permutation, so its rows are the logical ones.
-template <typename T>
-__global__ __launch_bounds__(512, 2) void band_attn_lse_m16_switch_kernel(typename BandLsePolicy<T>::Params prm,
-                                                                          typename BandLsePolicy<T>::Params prm_alt,
-                                                                          const int32_t* __restrict__ flag) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (flag[0] != 0) attn_body_m16<T, BandLsePolicy<T>, false, 1, false, true>(prm_alt, smem, nullptr, &g_band_replays);
-    else attn_body_m16<T, BandLsePolicy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
-}
-template <typename T>
-__global__ __launch_bounds__(512, 2) void band_attn_f32_m16_switch_kernel(typename BandF32Policy<T>::Params prm,
-                                                                          typename BandF32Policy<T>::Params prm_alt,
-                                                                          const int32_t* __restrict__ flag) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (flag[0] != 0) attn_body_m16<T, BandF32Policy<T>, false, 1, false, true>(prm_alt, smem, nullptr, &g_band_replays);
-    else attn_body_m16<T, BandF32Policy<T>, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
+    if (flag[0] != 0) attn_body_m16<T, Pol, false, 1, PRE, !PRE>(prm_alt, smem, nullptr, &g_band_replays);
+    else attn_body_m16<T, Pol, false, 1, PRE, !PRE>(prm, smem, nullptr, &g_band_replays);
 }
 // the same for q that carries sm_scale * log2(e) (svg_band_attention_prescaled): no scale-and-shift per score
 template <typename T, int D>
@@ -430,14 +326,38 @@ static int launch_band_queue(KQ kern_q, K kern, const typename Pol::Params& p, i
     return launch_attn(kern_q, dim3(n_wg), 512, lds, st, p, qd);
 }
 
-// parameters of an LSE / fp32 launch: those of the band policy plus lse (and o32, in the place of the 16-bit o)
-template <typename Pol, typename T>
-static typename Pol::Params band_lse_params(const void* q, const void* k, const void* v, void* o, int BH, int S, float sm_scale,
-                                            const svg_band_mask_t* mask, const svg_perm_desc_t* perm, const BandOpts& opts) {
-    typename Pol::Params p = make_band_params<Pol, T>(q, k, v, opts.o32 ? nullptr : o, BH, S, sm_scale, mask, perm, opts);
-    p.lse = opts.lse;
-    if constexpr (HasRowO32<Pol>::value) p.o32 = opts.o32;
-    return p;
+// One launch of the 16x16x32 body on policy Pol, for every entry that takes it; `params(mask, perm)` builds a parameter block of the form.
+// The device switch (opts.use_alt) gets the blocks of both masks — the alternate one with `perm_alt` — and runs over the q-tiles of the
+// larger; a single mask goes to the work queue where the form has one (launch_band_queue), else to the static mapping over its q-tiles.
+template <typename T, typename Pol, bool PRE = false, typename F>
+static int launch_band_m16(F params, const svg_band_mask_t* mask, const svg_perm_desc_t* perm, const svg_perm_desc_t* perm_alt,
+                           const BandOpts& opts, hipStream_t st) {
+    // (only what is launched is instantiated: the window forms have no device switch; the fp32, window and shard forms have no queue)
+    constexpr bool kSwitch = !std::is_same_v<Pol, BandWindowLsePolicy<T>> && !std::is_same_v<Pol, BandWindowF32Policy<T>>;
+    constexpr bool kQueue = std::is_same_v<Pol, BandPolicy<T, 128, 8>> || std::is_same_v<Pol, BandLsePolicy<T>>;
+    const int lds = attn_m16_lds_bytes() + kTailLds;
+    const typename Pol::Params p = params(mask, perm);
+    if constexpr (kSwitch) {
+        if (opts.use_alt) {
+            const typename Pol::Params b = params(opts.alt_mask, perm_alt);
+            return launch_attn(band_attn_m16_switch_kernel<T, Pol, PRE>, dim3(std::max(p.nqt, b.nqt) * p.BH), 512, lds, st, p, b, opts.use_alt);
+        }
+    }
+    auto kern = [] {
+        if constexpr (PRE) return band_attn_m16q_kernel<T>;
+        else return band_attn_m16_kernel<T, Pol>;
+    }();
+    if constexpr (kQueue) return launch_band_queue<Pol>(band_attn_m16_queue_kernel<T, Pol, PRE>, kern, p, lds, opts.done != nullptr, st);
+    else return launch_attn(kern, dim3(p.nqt * p.BH), 512, lds, st, p);
+}
+
+// The fp32 entries: o32 travels in the place of o through the null checks and the layout checks of the 16-bit entries.  With a layout q
+// stands in and the o member of the layout, which these entries do not read, takes q's strides (`abi` holds that copy; `layout` then
+// points to it); without one, o32 itself.
+static void* band_f32_stand_in(const void* q, float* o32, const svg_attn_layout_t*& layout, svg_attn_layout_t& abi) {
+    if (!layout) return o32;
+    abi = *layout, abi.o = abi.q, layout = &abi;
+    return const_cast<void*>(q);
 }
 
 // Every svg_band_attention* entry, after the null checks of its own arguments: validation, then the kernel of `variant` for
@@ -457,67 +377,30 @@ static int band_dispatch(const void* q, const void* k, const void* v, void* o, i
     if (opts.lse) {   // the LSE / fp32 forms: the default head_dim-128 body — single mask (queue or static mapping) or device switch
         if (D != 128 || variant != kBandAuto || opts.done || opts.prescaled) return SVG_ERR_UNSUPPORTED;
         if (opts.o32 && ((size_t)opts.o32 & 15) != 0) return SVG_ERR_UNSUPPORTED;   // 16-byte stores
-        if (opts.q_shard) {   // the shard forms: static mapping over the q-tiles of the q shard
-            return dispatch_td(dtype, D, [&](auto t, auto d) -> int {
-                using T = decltype(t);
-                if constexpr (decltype(d)::value != 128) {
-                    return SVG_ERR_UNSUPPORTED;
-                } else {
-                    const int lds = attn_m16_lds_bytes() + kTailLds;
-                    // the device switch: the alternate mask on the same shards, every head in logical order (perm's geometry, no flags)
-                    svg_perm_desc_t perm_alt = *perm;
-                    perm_alt.head_perm_flag = nullptr;
-                    if (opts.o32) {
-                        using Pol = BandShardF32Policy<T>;
-                        typename Pol::Params p = make_band_shard_params<Pol, T>(q, k, v, nullptr, BH, S, sm_scale, mask, perm, *opts.q_shard,
-                                                                                *opts.k_shard, opts);
-                        p.o32 = opts.o32;
-                        if (opts.use_alt) {
-                            typename Pol::Params b = make_band_shard_params<Pol, T>(q, k, v, nullptr, BH, S, sm_scale, opts.alt_mask, &perm_alt,
-                                                                                    *opts.q_shard, *opts.k_shard, opts);
-                            b.o32 = opts.o32;
-                            return launch_attn(band_shard_f32_m16_switch_kernel<T>, dim3(std::max(p.nqt, b.nqt) * BH), 512, lds, st, p, b,
-                                               opts.use_alt);
-                        }
-                        return launch_attn(band_shard_f32_m16_kernel<T>, dim3(p.nqt * BH), 512, lds, st, p);
-                    }
-                    using Pol = BandShardLsePolicy<T>;
-                    if (opts.use_alt) {
-                        const typename Pol::Params a = make_band_shard_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, *opts.q_shard,
-                                                                                      *opts.k_shard, opts);
-                        const typename Pol::Params b = make_band_shard_params<Pol, T>(q, k, v, o, BH, S, sm_scale, opts.alt_mask, &perm_alt,
-                                                                                      *opts.q_shard, *opts.k_shard, opts);
-                        return launch_attn(band_shard_lse_m16_switch_kernel<T>, dim3(std::max(a.nqt, b.nqt) * BH), 512, lds, st, a, b,
-                                           opts.use_alt);
-                    }
-                    const typename Pol::Params p = make_band_shard_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, *opts.q_shard,
-                                                                                  *opts.k_shard, opts);
-                    return launch_attn(band_shard_lse_m16_kernel<T>, dim3(p.nqt * BH), 512, lds, st, p);
-                }
-            });
-        }
         return dispatch_td(dtype, D, [&](auto t, auto d) -> int {
             using T = decltype(t);
             if constexpr (decltype(d)::value != 128) {
                 return SVG_ERR_UNSUPPORTED;
             } else {
-                const int lds = attn_m16_lds_bytes() + kTailLds;
-                auto run_switch = [&](auto pol, auto kern_sw) -> int {
+                auto whole = [&](auto pol) -> int {   // the alternate mask of the device switch: no head permutation
                     using Pol = decltype(pol);
-                    const typename Pol::Params a = band_lse_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
-                    const typename Pol::Params b = band_lse_params<Pol, T>(q, k, v, o, BH, S, sm_scale, opts.alt_mask, nullptr, opts);
-                    return launch_attn(kern_sw, dim3(std::max(a.nqt, b.nqt) * BH), 512, lds, st, a, b, opts.use_alt);
+                    auto params = [&](const svg_band_mask_t* m, const svg_perm_desc_t* pm) {
+                        return make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, m, pm, opts);
+                    };
+                    return launch_band_m16<T, Pol>(params, mask, perm, nullptr, opts, st);
                 };
-                if (opts.o32) {   // the *_f32 entries: `o` is o32 here, the kernel gets no 16-bit o; static mapping only
-                    using Pol = BandF32Policy<T>;
-                    if (opts.use_alt) return run_switch(Pol(), band_attn_f32_m16_switch_kernel<T>);
-                    const typename Pol::Params p = band_lse_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
-                    return launch_attn(band_attn_f32_m16_kernel<T>, dim3(p.nqt * BH), 512, lds, st, p);
-                }
-                using Pol = BandLsePolicy<T>;
-                if (opts.use_alt) return run_switch(Pol(), band_attn_lse_m16_switch_kernel<T>);
-                const typename Pol::Params p = band_lse_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
-                return launch_band_queue<Pol>(band_attn_lse_m16_queue_kernel<T>, band_attn_lse_m16_kernel<T>, p, lds, false, st);
+                auto shard = [&](auto pol) -> int {   // ... on the same shards, every head in logical order (perm's geometry, no flags)
+                    using Pol = decltype(pol);
+                    svg_perm_desc_t perm_alt = *perm;
+                    perm_alt.head_perm_flag = nullptr;
+                    auto params = [&](const svg_band_mask_t* m, const svg_perm_desc_t* pm) {
+                        return make_band_shard_params<Pol, T>(q, k, v, o, BH, S, sm_scale, m, pm, *opts.q_shard, *opts.k_shard, opts);
+                    };
+                    return launch_band_m16<T, Pol>(params, mask, perm, &perm_alt, opts, st);
+                };
+                // (the *_f32 entries: `o` is the stand-in of o32 here, the kernel gets no 16-bit o)
+                if (opts.q_shard) return opts.o32 ? shard(BandShardF32Policy<T>()) : shard(BandShardLsePolicy<T>());
+                return opts.o32 ? whole(BandF32Policy<T>()) : whole(BandLsePolicy<T>());
             }
         });
     }
@@ -541,21 +424,17 @@ static int band_dispatch(const void* q, const void* k, const void* v, void* o, i
         using T = decltype(t);
         constexpr int DD = decltype(d)::value;
         using Pol = BandPolicy<T, DD, 8>;
-        auto launch = [&](auto kern, int lds) {   // 8 waves over the q-tiles of every head
-            const typename Pol::Params p = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
-            return launch_attn(kern, dim3(p.nqt * BH), 512, lds, st, p);
+        auto params = [&](const svg_band_mask_t* m, const svg_perm_desc_t* pm) {
+            return make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, m, pm, opts);
         };
-        // the 16x16x32 kernels: resident workgroups on a work queue (band_attn_m16_queue_kernel), or `kern` on the static mapping
-        // where the call counts completions or no counter block is to be had
-        auto launch_queue = [&](auto kern_q, auto kern, int lds) {
-            const typename Pol::Params p = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
-            return launch_band_queue<Pol>(kern_q, kern, p, lds, opts.done != nullptr, st);
+        auto launch = [&](auto kern, int lds) {   // 8 waves over the q-tiles of every head
+            const typename Pol::Params p = params(mask, perm);
+            return launch_attn(kern, dim3(p.nqt * BH), 512, lds, st, p);
         };
         // a device-switch kernel: the parameters of both masks (the alternate one without the head permutation) and the flag, over
         // the q-tiles of the larger of the two
         auto launch_switch = [&](auto kern, int lds) {
-            const typename Pol::Params a = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
-            const typename Pol::Params b = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, opts.alt_mask, nullptr, opts);
+            const typename Pol::Params a = params(mask, perm), b = params(opts.alt_mask, nullptr);
             return launch_attn(kern, dim3(std::max(a.nqt, b.nqt) * BH), 512, lds, st, a, b, opts.use_alt);
         };
         switch (variant) {
@@ -592,13 +471,10 @@ static int band_dispatch(const void* q, const void* k, const void* v, void* o, i
                 }
                 return SVG_ERR_UNSUPPORTED;
             default:   // kBandM16: two-phase body on 16x16x32 MFMAs (attn_m16.h), head_dim 128; PRE forms for a q that carries the scale
+                // (switch, work queue — the static mapping where the call counts completions or no counter block is to be had: launch_band_m16)
                 if constexpr (DD == 128) {
-                    if (opts.use_alt)
-                        return launch_switch(opts.prescaled ? band_attn_m16_switch_kernel<T, true> : band_attn_m16_switch_kernel<T>,
-                                             attn_m16_lds_bytes() + kTailLds);
-                    if (opts.prescaled)
-                        return launch_queue(band_attn_m16_queue_kernel<T, true>, band_attn_m16q_kernel<T>, attn_m16_lds_bytes() + kTailLds);
-                    return launch_queue(band_attn_m16_queue_kernel<T>, band_attn_m16_kernel<T>, attn_m16_lds_bytes() + kTailLds);
+                    if (opts.prescaled) return launch_band_m16<T, Pol, true>(params, mask, perm, nullptr, opts, st);
+                    return launch_band_m16<T, Pol>(params, mask, perm, nullptr, opts, st);
                 }
                 return SVG_ERR_UNSUPPORTED;
         }
@@ -629,7 +505,6 @@ extern "C" int svg_band_attention_lse(const void* q, const void* k, const void* 
     return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, 0, layout, stream);
 }
 
-// o32 travels in the place of o through band_dispatch (its null check); of `layout` the o member is not read: it takes q's strides
 extern "C" int svg_band_attention_lse_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t BH, int32_t S,
                                           int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
                                           const svg_perm_desc_t* perm, const svg_attn_layout_t* layout, void* stream) {
@@ -637,19 +512,20 @@ extern "C" int svg_band_attention_lse_f32(const void* q, const void* k, const vo
     BandOpts opts;
     opts.lse = lse, opts.o32 = o32;
     opts.strided = layout != nullptr;
-    svg_attn_layout_t abi{};
-    if (layout) abi = *layout, abi.o = abi.q;
-    return band_dispatch(q, k, v, layout ? const_cast<void*>(q) : (void*)o32, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, 0,
-                         layout ? &abi : nullptr, stream);
+    svg_attn_layout_t abi;
+    void* const o = band_f32_stand_in(q, o32, layout, abi);
+    return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, 0, layout, stream);
 }
 
 // The window entries (include/svg_attn_band_window.h): a sibling of band_dispatch for the LSE / fp32 forms over a row window and a key
 // window — its checks in its order (check_band_mask and the size limits against S, the layout against the windows), then the window
-// kernels on the static mapping.  `o32` (or nullptr) stands in for o as in svg_band_attention_lse_f32.
+// kernels on the static mapping.  `o32` (or nullptr) stands in for o (band_f32_stand_in).
 static int band_window_dispatch(const void* q, const void* k, const void* v, void* o, float* o32, float* lse, int32_t BH, int32_t S,
                                 int32_t q_begin, int32_t Sq, int32_t k_begin, int32_t Sk, int32_t D, int32_t dtype, float sm_scale,
                                 const svg_band_mask_t* mask, const svg_attn_layout_t* layout, void* stream) {
-    if (!q || !k || !v || !(o32 ? (void*)o32 : o) || !lse || !mask) return SVG_ERR_BAD_ARG;
+    svg_attn_layout_t abi;
+    if (o32) o = band_f32_stand_in(q, o32, layout, abi);
+    if (!q || !k || !v || !o || !lse || !mask) return SVG_ERR_BAD_ARG;
     if (BH <= 0 || S <= 0 || Sq <= 0 || Sk <= 0 || q_begin < 0 || k_begin < 0 || (int64_t)q_begin + Sq > S || (int64_t)k_begin + Sk > S)
         return SVG_ERR_BAD_ARG;
     int rc = check_band_mask(S, mask, nullptr);
@@ -657,11 +533,7 @@ static int band_window_dispatch(const void* q, const void* k, const void* v, voi
     BandOpts opts;
     opts.lse = lse, opts.o32 = o32;
     opts.strided = layout != nullptr;
-    if (layout) {   // (of a layout the o member is not read by the fp32 form: it takes q's strides)
-        svg_attn_layout_t abi = *layout;
-        if (o32) abi.o = abi.q;
-        if ((rc = layout_from_abi(&abi, BH, BH, Sq, Sk, D, q, k, v, o32 ? q : o, opts.lay)) != SVG_OK) return rc;
-    }
+    if (layout && (rc = layout_from_abi(layout, BH, BH, Sq, Sk, D, q, k, v, o, opts.lay)) != SVG_OK) return rc;
     if (D != 128 || k_begin % kBN != 0) return SVG_ERR_UNSUPPORTED;   // key tiles stay aligned to the mask's coordinates
     if ((rc = band_check_size(BH, S, D)) != SVG_OK) return rc;
     if (o32 && ((size_t)o32 & 15) != 0) return SVG_ERR_UNSUPPORTED;   // 16-byte stores
@@ -671,16 +543,14 @@ static int band_window_dispatch(const void* q, const void* k, const void* v, voi
         if constexpr (decltype(d)::value != 128) {
             return SVG_ERR_UNSUPPORTED;
         } else {
-            const int lds = attn_m16_lds_bytes() + kTailLds;
-            if (o32) {
-                using Pol = BandWindowF32Policy<T>;
-                typename Pol::Params p = make_band_window_params<Pol, T>(q, k, v, nullptr, BH, S, q_begin, Sq, k_begin, Sk, sm_scale, mask, opts);
-                p.o32 = o32;
-                return launch_attn(band_window_f32_m16_kernel<T>, dim3(p.nqt * BH), 512, lds, st, p);
-            }
-            using Pol = BandWindowLsePolicy<T>;
-            const typename Pol::Params p = make_band_window_params<Pol, T>(q, k, v, o, BH, S, q_begin, Sq, k_begin, Sk, sm_scale, mask, opts);
-            return launch_attn(band_window_lse_m16_kernel<T>, dim3(p.nqt * BH), 512, lds, st, p);
+            auto run = [&](auto pol) -> int {
+                using Pol = decltype(pol);
+                auto params = [&](const svg_band_mask_t* m, const svg_perm_desc_t*) {
+                    return make_band_window_params<Pol, T>(q, k, v, o, BH, S, q_begin, Sq, k_begin, Sk, sm_scale, m, opts);
+                };
+                return launch_band_m16<T, Pol>(params, mask, nullptr, nullptr, opts, st);
+            };
+            return o32 ? run(BandWindowF32Policy<T>()) : run(BandWindowLsePolicy<T>());
         }
     });
 }
@@ -701,8 +571,8 @@ extern "C" int svg_band_window_attention_lse_f32(const void* q, const void* k, c
 }
 
 // The shard entries (include/svg_attn_band_shard.h): the checks of their own arguments — perm's geometry (checked whether or not it
-// carries flags), the q shard, the k shard — then band_dispatch with the two shards in opts.  `o32` (or nullptr) stands in for o as in
-// svg_band_attention_lse_f32.
+// carries flags), the q shard, the k shard — then band_dispatch with the two shards in opts.  `o32` (or nullptr) stands in for o
+// (band_f32_stand_in).
 static BandOpts switch_opts(const svg_band_mask_t* alt_mask, const int32_t* use_alt_flag);
 static int check_band_shard(const svg_band_shard_t* s, int32_t S, const svg_perm_desc_t* perm) {
     return check_frame_shard(s, S, perm->vid0, perm->num_frame, perm->frame_size);
@@ -726,9 +596,8 @@ static int band_shard_entry(const void* q, const void* k, const void* v, void* o
     BandOpts opts = sw ? *sw : BandOpts();
     opts.lse = lse, opts.o32 = o32, opts.q_shard = q_shard, opts.k_shard = k_shard;
     opts.strided = layout != nullptr;
-    svg_attn_layout_t abi{};
-    if (layout && o32) abi = *layout, abi.o = abi.q, layout = &abi;
-    if (o32) o = layout ? const_cast<void*>(q) : (void*)o32;
+    svg_attn_layout_t abi;
+    if (o32) o = band_f32_stand_in(q, o32, layout, abi);
     return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, 0, layout, stream);
 }
 
@@ -894,7 +763,7 @@ extern "C" int svg_band_attention_switch_prescaled(const void* q_scaled, const v
 }
 
 // LSE / fp32 forms of the device switch (include/svg_attn_band_lse_forms.h): the null checks of the plain switch entry behind the one of
-// lse / o32, then band_dispatch with opts.lse (and opts.o32).  o32 travels in the place of o as in svg_band_attention_lse_f32.
+// lse / o32, then band_dispatch with opts.lse (and opts.o32).  o32 travels in the place of o (band_f32_stand_in).
 static int band_switch_lse(const void* q, const void* k, const void* v, void* o, float* o32, float* lse, int32_t BH, int32_t S, int32_t D,
                            int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
                            const svg_band_mask_t* alt_mask, const int32_t* use_alt_flag, const svg_attn_layout_t* layout, void* stream) {
@@ -902,9 +771,8 @@ static int band_switch_lse(const void* q, const void* k, const void* v, void* o,
     BandOpts opts = switch_opts(alt_mask, use_alt_flag);
     opts.lse = lse, opts.o32 = o32;
     opts.strided = layout != nullptr;
-    svg_attn_layout_t abi{};
-    if (layout && o32) abi = *layout, abi.o = abi.q, layout = &abi;
-    if (o32) o = layout ? const_cast<void*>(q) : (void*)o32;
+    svg_attn_layout_t abi;
+    if (o32) o = band_f32_stand_in(q, o32, layout, abi);
     return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, 0, layout, stream);
 }
 
@@ -953,17 +821,14 @@ BandGroup band_group_at(const void* q, const void* k, const void* v, void* o, in
 }
 }  // namespace
 
-// every groups entry.  lse (and o32): the LSE / fp32 forms — o32 then stands in for o as in svg_band_attention_lse_f32, and both
+// every groups entry.  lse (and o32): the LSE / fp32 forms — o32 then stands in for o (band_f32_stand_in), and both
 // advance to a group's first head as contiguous [BH, S] / [BH, S, D] fp32 whatever the layout.
 static int band_groups_run(const void* q, const void* k, const void* v, void* o, float* o32, float* lse, int32_t BH, int32_t S, int32_t D,
                            int32_t dtype, float sm_scale, const svg_band_mask_t* masks, const svg_band_mask_t* alt_masks,
                            const int32_t* group_heads, int32_t n_groups, const svg_perm_desc_t* perm, const int32_t* use_alt_flag,
                            int32_t q_prescaled, const svg_attn_layout_t* layout, void* stream) {
-    svg_attn_layout_t abi{};
-    if (o32) {
-        if (layout) abi = *layout, abi.o = abi.q, layout = &abi;
-        o = layout ? const_cast<void*>(q) : (void*)o32;
-    }
+    svg_attn_layout_t abi;
+    if (o32) o = band_f32_stand_in(q, o32, layout, abi);
     if (!q || !k || !v || !o || !masks || !group_heads || n_groups < 1 || BH <= 0 || S <= 0) return SVG_ERR_BAD_ARG;
     if ((alt_masks != nullptr) != (use_alt_flag != nullptr)) return SVG_ERR_BAD_ARG;
     int64_t heads = 0;

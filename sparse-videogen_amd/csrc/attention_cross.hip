@@ -14,42 +14,13 @@ namespace svg {
 // the stages the second fills).  Per row the keys are visited in ascending order: the result does not depend on the grid size.
 // Windowed (svg_cross_attention_keyrange): an item costs the key tiles of its video's window, so the static stride is balanced only within
 // a video; the same loop all the same (no queue): the tail is bounded by one item of the longest window, see DESIGN 3.1.4.
-template <typename T, bool Windowed = false>
-__global__ __launch_bounds__(512, 2) void cross_attn_m16_kernel(typename CrossPolicy<T, Windowed>::Params prm) {
+// One template: the policy is the only thing that differs between the instantiations — CrossPolicy, CrossLsePolicy (svg_cross_attention_lse: the
+// epilogue of attn_m16_tile also stores one fp32 per query row) and CrossF32Policy (svg_cross_attention_lse_f32: it stores the rows as fp32, before
+// their rounding, and no 16-bit o), each windowed or not — and each instantiation's listing is compared with the one it had as a kernel of
+// its own (tools/asm_diff.py --pair, profiles/kernel_templates_asm_diff.txt).
+template <typename T, typename Pol>
+__global__ __launch_bounds__(512, 2) void cross_attn_m16_kernel(typename Pol::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    using Pol = CrossPolicy<T, Windowed>;
-    const int n_items = prm.BH * prm.nqt;
-    for (int w = blockIdx.x; w < n_items; w += gridDim.x) {
-        if (w != (int)blockIdx.x) __syncthreads();
-        const int head = w / prm.nqt;
-        typename Pol::Ctx ctx;
-        Pol::init_tile(prm, ctx, head, w - head * prm.nqt);
-        attn_m16_tile<T, Pol, false, 1>(prm, ctx, smem);
-    }
-}
-
-// LSE form (svg_cross_attention_lse): the loop above on CrossLsePolicy — the epilogue of attn_m16_tile also stores one fp32 per query row.
-// (Its own kernel template, not a third argument of the one above: the plain and windowed kernels keep their symbols and their listings.)
-template <typename T, bool Windowed>
-__global__ __launch_bounds__(512, 2) void cross_attn_lse_m16_kernel(typename CrossLsePolicy<T, Windowed>::Params prm) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    using Pol = CrossLsePolicy<T, Windowed>;
-    const int n_items = prm.BH * prm.nqt;
-    for (int w = blockIdx.x; w < n_items; w += gridDim.x) {
-        if (w != (int)blockIdx.x) __syncthreads();
-        const int head = w / prm.nqt;
-        typename Pol::Ctx ctx;
-        Pol::init_tile(prm, ctx, head, w - head * prm.nqt);
-        attn_m16_tile<T, Pol, false, 1>(prm, ctx, smem);
-    }
-}
-
-// fp32 form (svg_cross_attention_lse_f32): the LSE kernel on CrossF32Policy — the epilogue stores the rows as fp32, before their rounding,
-// and no 16-bit o.  (Its own kernel template: the kernels above keep their symbols and their listings.)
-template <typename T, bool Windowed>
-__global__ __launch_bounds__(512, 2) void cross_attn_f32_m16_kernel(typename CrossF32Policy<T, Windowed>::Params prm) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    using Pol = CrossF32Policy<T, Windowed>;
     const int n_items = prm.BH * prm.nqt;
     for (int w = blockIdx.x; w < n_items; w += gridDim.x) {
         if (w != (int)blockIdx.x) __syncthreads();
@@ -118,47 +89,51 @@ static int device_cus() {
 
 using namespace svg;
 
-// the checks and the launch of the plain, keyrange and LSE entries; kv_end == nullptr: the plain kernel; lse != nullptr: the LSE form
-static int cross_attention_launch(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t Sq, int32_t Skv, int32_t D, int32_t dtype,
-                                  float sm_scale, const int32_t* kv_begin, const int32_t* kv_end, int32_t heads_per_window,
-                                  const svg_attn_layout_t* layout, void* stream) {
+// the checks and the launch of the plain, keyrange, LSE and fp32 entries; kv_end == nullptr: not windowed; lse != nullptr: the LSE form;
+// o32 != nullptr: the fp32 form — 16-byte aligned, `o` is then q, which stands in through the null and layout checks (the o member of
+// `layout` is not read: it takes q's strides), and the kernel gets no 16-bit o
+static int cross_attention_launch(const void* q, const void* k, const void* v, void* o, float* lse, float* o32, int32_t BH, int32_t Sq, int32_t Skv,
+                                  int32_t D, int32_t dtype, float sm_scale, const int32_t* kv_begin, const int32_t* kv_end,
+                                  int32_t heads_per_window, const svg_attn_layout_t* layout, void* stream) {
     if (!q || !k || !v || !o || BH <= 0 || Sq <= 0 || Skv <= 0) return SVG_ERR_BAD_ARG;
     if (D != 128) return SVG_ERR_UNSUPPORTED;
     if (check_rows(Sq, D) != SVG_OK || check_rows(Skv, D) != SVG_OK) return SVG_ERR_UNSUPPORTED;
     if ((int64_t)BH * Sq * D >= (1ll << 40)) return SVG_ERR_UNSUPPORTED;
+    if (((size_t)o32 & 15) != 0) return SVG_ERR_UNSUPPORTED;
     AttnLayout lay = contiguous_layout(BH, BH, Sq, Skv, D);
     if (layout) {
-        if (const int rc = layout_from_abi(layout, BH, BH, Sq, Skv, D, q, k, v, o, lay); rc != SVG_OK) return rc;
+        svg_attn_layout_t abi = *layout;
+        if (o32) abi.o = abi.q;
+        if (const int rc = layout_from_abi(&abi, BH, BH, Sq, Skv, D, q, k, v, o, lay); rc != SVG_OK) return rc;
     }
     return dispatch_td(dtype, D, [&](auto t, auto d) -> int {
         using T = decltype(t);
         if constexpr (decltype(d)::value != 128) {
             return SVG_ERR_UNSUPPORTED;
         } else {
-            auto launch = [&](auto windowed_c, auto lse_c) -> int {
-                constexpr bool kWindowed = decltype(windowed_c)::value;
-                constexpr bool kLse = decltype(lse_c)::value;
-                using Pol = std::conditional_t<kLse, CrossLsePolicy<T, kWindowed>, CrossPolicy<T, kWindowed>>;
+            auto launch = [&](auto pol) -> int {
+                using Pol = decltype(pol);
                 typename Pol::Params p;
-                if constexpr (kLse) p.lse = lse;
-                if constexpr (kWindowed) p.kv_begin = kv_begin, p.kv_end = kv_end, p.heads_per_window = heads_per_window;
                 p.q = (const T*)q, p.k = (const T*)k, p.v = (const T*)v, p.o = (T*)o;
+                if constexpr (HasRowLse<Pol>::value) p.lse = lse;
+                if constexpr (HasRowO32<Pol>::value) p.o32 = o32, p.o = nullptr;
+                if constexpr (std::is_base_of_v<CrossPolicy<T, true>, Pol>) p.kv_begin = kv_begin, p.kv_end = kv_end, p.heads_per_window = heads_per_window;
                 p.Sq = Sq, p.Skv = Skv, p.BH = BH, p.nqt = (Sq + Pol::BM - 1) / Pol::BM;
                 p.scale_log2 = sm_scale * 1.4426950408889634f;
                 p.lay = lay;
                 const int n_wg = (int)std::min<int64_t>((int64_t)BH * p.nqt, device_cus());
-                if constexpr (kLse) return launch_attn(cross_attn_lse_m16_kernel<T, kWindowed>, dim3(n_wg), 512, attn_m16_lds_bytes(), (hipStream_t)stream, p);
-                else return launch_attn(cross_attn_m16_kernel<T, kWindowed>, dim3(n_wg), 512, attn_m16_lds_bytes(), (hipStream_t)stream, p);
+                return launch_attn(cross_attn_m16_kernel<T, Pol>, dim3(n_wg), 512, attn_m16_lds_bytes(), (hipStream_t)stream, p);
             };
-            if (lse) return kv_end ? launch(std::true_type{}, std::true_type{}) : launch(std::false_type{}, std::true_type{});
-            return kv_end ? launch(std::true_type{}, std::false_type{}) : launch(std::false_type{}, std::false_type{});
+            if (o32) return kv_end ? launch(CrossF32Policy<T, true>()) : launch(CrossF32Policy<T, false>());
+            if (lse) return kv_end ? launch(CrossLsePolicy<T, true>()) : launch(CrossLsePolicy<T, false>());
+            return kv_end ? launch(CrossPolicy<T, true>()) : launch(CrossPolicy<T, false>());
         }
     });
 }
 
 extern "C" int svg_cross_attention(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t Sq, int32_t Skv, int32_t D,
                                    int32_t dtype, float sm_scale, const svg_attn_layout_t* layout, void* stream) {
-    return cross_attention_launch(q, k, v, o, nullptr, BH, Sq, Skv, D, dtype, sm_scale, nullptr, nullptr, 1, layout, stream);
+    return cross_attention_launch(q, k, v, o, nullptr, nullptr, BH, Sq, Skv, D, dtype, sm_scale, nullptr, nullptr, 1, layout, stream);
 }
 
 extern "C" int svg_cross_attention_pair(const void* q, const void* k_a, const void* v_a, const void* k_b, const void* v_b, void* o, int32_t BH,
@@ -200,44 +175,13 @@ extern "C" int svg_cross_attention_pair(const void* q, const void* k_a, const vo
     });
 }
 
-// the checks of cross_attention_launch (o32 in the place of o: 16-byte aligned; the o member of `layout` is not read) and the fp32 kernel
 extern "C" int svg_cross_attention_lse_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t BH, int32_t Sq,
                                            int32_t Skv, int32_t D, int32_t dtype, float sm_scale, const int32_t* kv_begin,
                                            const int32_t* kv_end, int32_t heads_per_window, const svg_attn_layout_t* layout, void* stream) {
     if (!o32 || !lse) return SVG_ERR_BAD_ARG;
     if (kv_end && (heads_per_window <= 0 || (BH > 0 && BH % heads_per_window != 0))) return SVG_ERR_BAD_ARG;
-    if (!q || !k || !v || BH <= 0 || Sq <= 0 || Skv <= 0) return SVG_ERR_BAD_ARG;
-    if (D != 128) return SVG_ERR_UNSUPPORTED;
-    if (check_rows(Sq, D) != SVG_OK || check_rows(Skv, D) != SVG_OK) return SVG_ERR_UNSUPPORTED;
-    if ((int64_t)BH * Sq * D >= (1ll << 40)) return SVG_ERR_UNSUPPORTED;
-    if (((size_t)o32 & 15) != 0) return SVG_ERR_UNSUPPORTED;
-    AttnLayout lay = contiguous_layout(BH, BH, Sq, Skv, D);
-    if (layout) {
-        svg_attn_layout_t abi = *layout;
-        abi.o = abi.q;
-        if (const int rc = layout_from_abi(&abi, BH, BH, Sq, Skv, D, q, k, v, q, lay); rc != SVG_OK) return rc;
-    }
-    return dispatch_td(dtype, D, [&](auto t, auto d) -> int {
-        using T = decltype(t);
-        if constexpr (decltype(d)::value != 128) {
-            return SVG_ERR_UNSUPPORTED;
-        } else {
-            auto launch = [&](auto windowed_c) -> int {
-                constexpr bool kWindowed = decltype(windowed_c)::value;
-                using Pol = CrossF32Policy<T, kWindowed>;
-                typename Pol::Params p;
-                p.lse = lse, p.o32 = o32;
-                if constexpr (kWindowed) p.kv_begin = kv_begin, p.kv_end = kv_end, p.heads_per_window = heads_per_window;
-                p.q = (const T*)q, p.k = (const T*)k, p.v = (const T*)v, p.o = nullptr;
-                p.Sq = Sq, p.Skv = Skv, p.BH = BH, p.nqt = (Sq + Pol::BM - 1) / Pol::BM;
-                p.scale_log2 = sm_scale * 1.4426950408889634f;
-                p.lay = lay;
-                const int n_wg = (int)std::min<int64_t>((int64_t)BH * p.nqt, device_cus());
-                return launch_attn(cross_attn_f32_m16_kernel<T, kWindowed>, dim3(n_wg), 512, attn_m16_lds_bytes(), (hipStream_t)stream, p);
-            };
-            return kv_end ? launch(std::true_type{}) : launch(std::false_type{});
-        }
-    });
+    return cross_attention_launch(q, k, v, const_cast<void*>(q), lse, o32, BH, Sq, Skv, D, dtype, sm_scale, kv_begin, kv_end, heads_per_window, layout,
+                                  stream);
 }
 
 extern "C" int svg_cross_attention_keyrange(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t Sq, int32_t Skv, int32_t D,
@@ -245,7 +189,7 @@ extern "C" int svg_cross_attention_keyrange(const void* q, const void* k, const 
                                             int32_t heads_per_window, const svg_attn_layout_t* layout, void* stream) {
     if (!kv_end || heads_per_window <= 0) return SVG_ERR_BAD_ARG;
     if (BH > 0 && BH % heads_per_window != 0) return SVG_ERR_BAD_ARG;
-    return cross_attention_launch(q, k, v, o, nullptr, BH, Sq, Skv, D, dtype, sm_scale, kv_begin, kv_end, heads_per_window, layout, stream);
+    return cross_attention_launch(q, k, v, o, nullptr, nullptr, BH, Sq, Skv, D, dtype, sm_scale, kv_begin, kv_end, heads_per_window, layout, stream);
 }
 
 extern "C" int svg_cross_attention_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t Sq, int32_t Skv,
@@ -253,5 +197,5 @@ extern "C" int svg_cross_attention_lse(const void* q, const void* k, const void*
                                        int32_t heads_per_window, const svg_attn_layout_t* layout, void* stream) {
     if (!lse) return SVG_ERR_BAD_ARG;
     if (kv_end && (heads_per_window <= 0 || (BH > 0 && BH % heads_per_window != 0))) return SVG_ERR_BAD_ARG;
-    return cross_attention_launch(q, k, v, o, lse, BH, Sq, Skv, D, dtype, sm_scale, kv_end ? kv_begin : nullptr, kv_end, heads_per_window, layout, stream);
+    return cross_attention_launch(q, k, v, o, lse, nullptr, BH, Sq, Skv, D, dtype, sm_scale, kv_end ? kv_begin : nullptr, kv_end, heads_per_window, layout, stream);
 }

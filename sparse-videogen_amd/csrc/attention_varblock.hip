@@ -22,27 +22,15 @@ __global__ __launch_bounds__(512, 2) void varblock_attn_pp2_kernel(typename Varb
     attn_body_pp2<T, D, VarblockPolicy<T, D, 8>>(prm, smem, smem + attn_pp2_lds_bytes<D>());
 }
 
-// the two-phase body on 16x16x32 MFMAs (attn_m16.h) for the variable-block policy: head_dim 128; svg_varblock_attention variant 8
-template <typename T>
-__global__ __launch_bounds__(512, 2) void varblock_attn_m16_kernel(typename VarblockPolicy<T, 128, 8>::Params prm) {
+// the two-phase body on 16x16x32 MFMAs (attn_m16.h) for the variable-block policies: head_dim 128; svg_varblock_attention variant 8.  One
+// template: the policy is the only thing that differs between the instantiations — VarblockPolicy<T, 128, 8>, VarblockLsePolicy
+// (svg_varblock_attention_lse: the epilogue of attn_m16_tile also stores one fp32 per query row) and VarblockF32Policy
+// (svg_varblock_attention_lse_f32: it stores the rows as fp32, before their rounding, and no 16-bit o) — and each instantiation's listing is
+// compared with the one it had as a kernel of its own (tools/asm_diff.py --pair, profiles/kernel_templates_asm_diff.txt).
+template <typename T, typename Pol>
+__global__ __launch_bounds__(512, 2) void varblock_attn_m16_kernel(typename Pol::Params prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_body_m16<T, VarblockPolicy<T, 128, 8>>(prm, smem, smem + attn_m16_lds_bytes());
-}
-
-// LSE form (svg_varblock_attention_lse): the kernel above on VarblockLsePolicy — the epilogue of attn_m16_tile also stores one fp32 per
-// query row.  (Its own kernel template: varblock_attn_m16_kernel keeps its symbol and its listing.)
-template <typename T>
-__global__ __launch_bounds__(512, 2) void varblock_attn_lse_m16_kernel(typename VarblockLsePolicy<T>::Params prm) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_body_m16<T, VarblockLsePolicy<T>>(prm, smem, smem + attn_m16_lds_bytes());
-}
-
-// fp32 form (svg_varblock_attention_lse_f32): the LSE kernel on VarblockF32Policy — the epilogue stores the rows as fp32, before their
-// rounding, and no 16-bit o.  (Its own kernel template: the kernels above keep their symbols and their listings.)
-template <typename T>
-__global__ __launch_bounds__(512, 2) void varblock_attn_f32_m16_kernel(typename VarblockF32Policy<T>::Params prm) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_body_m16<T, VarblockF32Policy<T>>(prm, smem, smem + attn_m16_lds_bytes());
+    attn_body_m16<T, Pol>(prm, smem, smem + attn_m16_lds_bytes());
 }
 
 #ifdef SVG_ABLATIONS
@@ -624,19 +612,18 @@ static int run_varblock(const VbCall& c) {
                 return SVG_ERR_UNSUPPORTED;   // diagnostics builds only (-DSVG_ABLATIONS)
             }
             if constexpr (D == 128) {
-                if (body == VbBody::kM16 && c.lse && c.o32) {   // ... and the policy that stores fp32 rows and no 16-bit o
-                    typename VarblockF32Policy<T>::Params pf;
-                    static_cast<typename VarblockPolicy<T, 128, 8>::Params&>(pf) = p;
-                    pf.o = nullptr, pf.lse = c.lse, pf.o32 = c.o32;
-                    return launch_attn(varblock_attn_f32_m16_kernel<T>, grid, 512, attn_m16_lds_bytes() + lds_vb, st, pf);
+                if (body == VbBody::kM16) {   // the same plan, launch order and grid for the policies that also store lse, or fp32 rows and no 16-bit o
+                    auto launch = [&](auto pol) {
+                        using Pol = decltype(pol);
+                        typename Pol::Params px;
+                        static_cast<typename VarblockPolicy<T, 128, 8>::Params&>(px) = p;
+                        if constexpr (HasRowLse<Pol>::value) px.lse = c.lse;
+                        if constexpr (HasRowO32<Pol>::value) px.o32 = c.o32, px.o = nullptr;
+                        return launch_attn(varblock_attn_m16_kernel<T, Pol>, grid, 512, attn_m16_lds_bytes() + lds_vb, st, px);
+                    };
+                    if (c.lse) return c.o32 ? launch(VarblockF32Policy<T>()) : launch(VarblockLsePolicy<T>());
+                    return launch(VarblockPolicy<T, 128, 8>());
                 }
-                if (body == VbBody::kM16 && c.lse) {   // the same plan, launch order and grid; the policy that also stores lse
-                    typename VarblockLsePolicy<T>::Params pl;
-                    static_cast<typename VarblockPolicy<T, 128, 8>::Params&>(pl) = p;
-                    pl.lse = c.lse;
-                    return launch_attn(varblock_attn_lse_m16_kernel<T>, grid, 512, attn_m16_lds_bytes() + lds_vb, st, pl);
-                }
-                if (body == VbBody::kM16) return launch_attn(varblock_attn_m16_kernel<T>, grid, 512, attn_m16_lds_bytes() + lds_vb, st, p);
             }
             if (c.lse) return SVG_ERR_UNSUPPORTED;
             return launch_attn(varblock_attn_pp2_kernel<T, D>, grid, 512, attn_pp2_lds_bytes<D>() + lds_vb, st, p);

@@ -1066,21 +1066,21 @@ inline typename Pol::Params make_band_params(const void* q, const void* k, const
     p.sp64 = p.q64 + p.r64 * p.P, p.sp128 = p.q128 + p.r128 * p.P;
     p.wrap_phys = 1 - p.F * p.P;
     band_row_regions<Pol>(p, S, 0, S, opts.done_nseg);
+    // what the LSE / fp32 policies (BandLsePolicy, BandF32Policy and what is built on them) add: lse, and o32 in the place of the 16-bit o
+    if constexpr (std::is_base_of_v<BandLsePolicy<T>, Pol>) p.lse = opts.lse;
+    if constexpr (std::is_base_of_v<BandF32Policy<T>, Pol>) p.o32 = opts.o32, p.o = nullptr;
     return p;
 }
 
 // parameters of a window launch (BandWindowOf): those of the sequence of S rows, the row regions intersected with the row window — heavy_lo,
-// n_heavy and nqt follow the clipped regions — and the tensors as [BH, Sq | Sk, D] (or `opts.lay`); lse (and o32) from opts
+// n_heavy and nqt follow the clipped regions — and the tensors as [BH, Sq | Sk, D] (or `opts.lay`)
 template <typename Pol, typename T>
 inline typename Pol::Params make_band_window_params(const void* q, const void* k, const void* v, void* o, int BH, int S, int q_begin, int Sq,
                                                     int k_begin, int Sk, float sm_scale, const svg_band_mask_t* mask, const BandOpts& opts) {
-    typename Pol::Params p;
-    static_cast<typename BandPolicy<T, 128, 8>::Params&>(p) =
-        make_band_params<BandPolicy<T, 128, 8>, T>(q, k, v, o, BH, S, sm_scale, mask, nullptr, opts);
+    typename Pol::Params p = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, nullptr, opts);
     if (!opts.strided) p.lay = contiguous_layout(BH, BH, Sq, Sk, Pol::kHeadDim);
     p.q_begin = q_begin, p.Sq = Sq, p.k_begin = k_begin, p.k_end = k_begin + Sk;
     band_row_regions<Pol>(p, S, q_begin, q_begin + Sq, 1);
-    p.lse = opts.lse;
     return p;
 }
 
@@ -1116,14 +1116,12 @@ inline int band_shard_regions(const typename Pol::Params& p, int kind, int* lo, 
 
 // parameters of a shard launch (BandShardOf): those of the sequence of S rows with the video geometry of `perm` (its flags may be null: every
 // head in logical order), the two shard maps, the row regions of both head kinds — nqt is the larger count — and the tensors as
-// [BH, Sq | Sk, D] (or `opts.lay`); lse from opts
+// [BH, Sq | Sk, D] (or `opts.lay`)
 template <typename Pol, typename T>
 inline typename Pol::Params make_band_shard_params(const void* q, const void* k, const void* v, void* o, int BH, int S, float sm_scale,
                                                    const svg_band_mask_t* mask, const svg_perm_desc_t* perm, const svg_band_shard_t& q_shard,
                                                    const svg_band_shard_t& k_shard, const BandOpts& opts) {
-    typename Pol::Params p;
-    static_cast<typename BandPolicy<T, 128, 8>::Params&>(p) =
-        make_band_params<BandPolicy<T, 128, 8>, T>(q, k, v, o, BH, S, sm_scale, mask, nullptr, opts);
+    typename Pol::Params p = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, nullptr, opts);
     p.head_flag = perm->head_perm_flag;
     p.vid0 = perm->vid0, p.F = perm->num_frame, p.P = perm->frame_size, p.V = perm->num_frame * perm->frame_size;
     p.qs = make_band_shard_map(q_shard, p.vid0, p.F, p.P), p.ks = make_band_shard_map(k_shard, p.vid0, p.F, p.P);
@@ -1132,7 +1130,6 @@ inline typename Pol::Params make_band_shard_params(const void* q, const void* k,
     const int nqt1 = band_shard_regions<Pol>(p, 1, p.reg1_lo, p.reg1_hi, p.reg1_t0);
     if (p.head_flag) p.nqt = std::max(p.nqt, nqt1);
     p.heavy_lo = 0, p.n_heavy = 0, p.done_nseg = 1, p.done_tps = 1 << 30;
-    p.lse = opts.lse;
     return p;
 }
 

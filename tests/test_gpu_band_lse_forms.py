@@ -1,5 +1,5 @@
 """The LSE / fp32 forms of the production launch forms of band attention on the GPU (include/svg_attn_band_lse_forms.h; csrc/attention.hip:
-band_attn_lse_m16_switch_kernel, band_attn_f32_m16_switch_kernel, band_attn_lse_m16_queue_kernel, the groups entries): the device switch
+band_attn_m16_switch_kernel and band_attn_m16_queue_kernel on BandLsePolicy / BandF32Policy, the groups entries): the device switch
 under either flag, the switch under replay, svg_band_attention_lse through the work queue, groups of heads under masks of their own, the
 fp32 rows of each, rows without keys and rows behind real_len, and the protocol the forms exist for — a layer-call on the device switch
 over the video keys merged with dense attention over the text keys, against the float64 statement of the whole.
@@ -216,7 +216,7 @@ def static_lse_results(nat, subset):
 @pytest.mark.parametrize("cap", C.QUEUE_CAPS)
 @pytest.mark.parametrize("subset", C.QUEUE_SUBSETS)
 def test_lse_entry_through_the_queue_equals_the_static_mapping(nat, subset, cap):
-    """14 work items on 1, 2 or 3 resident workgroups of band_attn_lse_m16_queue_kernel, replayed q-tiles among them: o and lse have
+    """14 work items on 1, 2 or 3 resident workgroups of band_attn_m16_queue_kernel on BandLsePolicy, replayed q-tiles among them: o and lse have
     the bits of the static mapping, and the replays are the same.  (svg_band_attention_lse_f32 has no queue form and keeps the static
     mapping under any cap: its results must not move either.)"""
     case = C.queue_case(subset)

@@ -1,5 +1,5 @@
 """Band attention of a frame shard of the rows over a frame shard of the keys on the GPU (include/svg_attn_band_shard.h; csrc/attention.hip:
-band_shard_lse_m16_kernel, band_shard_f32_m16_kernel on BandShardOf of csrc/band_policy.h): the whole sequence as both shards against the
+band_attn_m16_kernel on BandShardLsePolicy / BandShardF32Policy, BandShardOf of csrc/band_policy.h): the whole sequence as both shards against the
 device-switch entries bit for bit, every (q shard, k shard) pair of the cases of tests/band_shard_cases.py against float64 with the inputs
 inside NaN frames, the parts of a q shard over the k shards merged against the float64 statement over all keys and against the single
 switch call, a launch of mixed head kinds against two launches of one kind, strided views, svg.distributed.token_sharded_svg1_attention on

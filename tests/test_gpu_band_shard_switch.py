@@ -1,5 +1,5 @@
 """The device switch of band attention on frame shards on the GPU (include/svg_attn_band_shard_switch.h; csrc/attention.hip:
-band_shard_lse_m16_switch_kernel, band_shard_f32_m16_switch_kernel): for every (q shard, k shard) pair of the cases of
+band_attn_m16_switch_kernel on BandShardLsePolicy / BandShardF32Policy): for every (q shard, k shard) pair of the cases of
 tests/band_shard_cases.py a flag of 0 against the plain shard entry under the sparse mask and the head flags, a flag of 1 against the plain
 shard entry under the alternate mask without flags — bit for bit, 16-bit and fp32 forms, bf16 and fp16 — and both against float64; the whole
 sequence as both shards against svg_band_attention_switch_lse[_f32]; one set of arguments launched twice with the flag flipped on the

@@ -1,5 +1,5 @@
 """Band attention over a row window and a key window of the mask on the GPU (include/svg_attn_band_window.h; csrc/attention.hip:
-band_window_lse_m16_kernel, band_window_f32_m16_kernel on BandWindowOf of csrc/band_policy.h): every (row window, key window) pair of the
+band_attn_m16_kernel on BandWindowLsePolicy / BandWindowF32Policy, BandWindowOf of csrc/band_policy.h): every (row window, key window) pair of the
 four band models against float64, the whole-sequence window against the sibling entries bit for bit, windows that sit inside larger
 buffers full of NaN, strided views, the protocol the form exists for — the parts of a row window over the key windows merged, against
 the float64 statement over all keys — a replayed q-tile inside a key window, and svg.distributed.token_sharded_band_attention on two

@@ -19,7 +19,8 @@ for f in glob.glob(out + "/p*/**/*counter_collection.csv", recursive=True):
                 continue
         elif "attn_" not in k or "profile" in k:
             continue
-        agg[k[:60]][r["Counter_Name"]].append(float(r["Counter_Value"]))
+        # (the name up to its parameter list: the policy is a template argument of the 16x16x32 kernels, and 60 characters end inside it)
+        agg[k.split("(")[0][:120]][r["Counter_Name"]].append(float(r["Counter_Value"]))
 with open(out + "/summary.txt", "w") as fo:
     for k, d in agg.items():
         fo.write(k + "\n")
