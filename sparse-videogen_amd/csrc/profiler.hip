@@ -14,9 +14,9 @@
 //                        lock-step body: waves 0-1 the golden rows, 2-3 the rows under mask 1, 4-5 under mask 0 on the SAME staged K / V
 //                        tiles, each role its own scores.  (Before that: three workgroups, grid.z = 3, K / V staged three times, 1.26 ms per
 //                        call at HunyuanVideo 720p; the role form 0.78 -> 0.60 ms; the shipped one 0.32.)
-// The second form also exists per KEY SHARD of a sequence sharded by whole frames (include/svg_attn_profile_shard.h): profile16_shard_kernel and
-// profile_shard_reduce_kernel emit one (O, m, l) per output, head and row for a shard's keys, profile_combine_parts_kernel merges such parts —
-// see the note above ProfileShardPolicy.
+// The second form also runs per KEY SHARD of a sequence sharded by whole frames (include/svg_attn_profile_shard.h): profile16_kernel on
+// ProfileShardPolicy and profile_shard_reduce_kernel emit one (O, m, l) per output, head and row for a shard's keys,
+// profile_combine_parts_kernel merges such parts — see the note above ProfileShardPolicy.
 #include <type_traits>
 #include "attn_core.h"
 #include "attn_m16.h"
@@ -35,6 +35,13 @@ struct ProfVariant {
 constexpr int kProfNW = 8;      // waves per workgroup: 3 roles x 2 waves x 32 sampled rows, the last two waves have no rows
 constexpr int kProfMaxRows = 64;
 constexpr int kProfRoleRows = 3 * kProfMaxRows;   // workgroup rows [64 v, 64 v + 64) belong to role v
+
+// a key tile of profile16_kernel as its masks see it: the stored index of its first key, the end of the keys it may hold, and whether it
+// holds a shard's seam between video rows and tail (its keys' indices are then not consecutive)
+struct ProfTile {
+    int k0, send;
+    bool seam;
+};
 
 template <typename T, int D>
 struct ProfilePolicy : LayoutAccess<ProfilePolicy<T, D>> {
@@ -245,6 +252,45 @@ struct ProfilePolicy : LayoutAccess<ProfilePolicy<T, D>> {
         }
     }
     static __device__ __forceinline__ void notify(const Params&, const Ctx&) {}
+
+    // ---- what profile16_kernel asks of its policy beyond the above (ProfileShardPolicy answers for one shard of the keys) ----
+    static constexpr bool kShard = false;
+    static __device__ __forceinline__ int key_rows(const Params& p) { return p.S; }   // rows of k / v: every tile bound is one against it
+    static __device__ __forceinline__ const T* q_rows_at(const Params& p, int head) { return ProfilePolicy::q_at(p, head); }
+    static __device__ __forceinline__ int q_rows_rs(const Params& p) { return ProfilePolicy::q_rs(p); }
+    // (send is read on a shard only.  Not p.S here: the unused read alone moves the register assignment of the whole kernel.)
+    static __device__ __forceinline__ ProfTile tile(const Params&, int k0l) { return {k0l, 0, false}; }
+};
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Shard form of the second form (include/svg_attn_profile_shard.h): the keys are the rows of ONE frame shard — the whole frames
+// [f0, f0 + n_frames) and a tail behind the video — and the sampled q rows arrive gathered.  A shard is a set of KV chunks that lives on
+// another GPU: profile16_kernel runs on it with
+//   * q read from the compact q_rows: a lane's row is the INPUT index of the row it ranked, `rows` only gives coordinates;
+//   * tiles on the shard's LOCAL grid: local key l is physical row l of k / v, and every bound against S is one against Sk;
+//   * the mask on the key's stored global index G(l) = g0 + l (l < nv, g0 = f0 P) or tb + (l - nv): a tile wholly in the video rows or wholly
+//     in the tail is the whole-sequence code at k0 = G(first key) — classify, the fast paths, the class table, the one-wrap stepping of allowed —
+//     with the end of the keys such a tile can hold in the place of S; the ONE tile that holds the seam l = nv is TILE_PARTIAL under both masks
+//     and maps each key through G (G is continuous there for a shard whose frames end at F; the ABI allows one that is not).
+// profile_shard_reduce_kernel then folds the chunks into one (O, m, l) per (output, head, row) with the sums of profile_combine_kernel, and
+// profile_combine_parts_kernel runs that kernel's body over a pointer per part: one part of the whole sequence gives the bits of svg_sample_mse.
+template <typename T, int D>
+struct ProfileShardPolicy : ProfilePolicy<T, D> {
+    struct Params : ProfilePolicy<T, D>::Params {
+        const T* q_rows;    // [BH][R][D]
+        int Sk, nv;         // rows of the shard, of them video rows
+        int g0, tb, send;   // G(0); G(nv) (F P for a shard without a tail); the end of the stored indices: tb + n_tail
+    };
+    static constexpr bool kShard = true;
+    static __device__ __forceinline__ int key_rows(const Params& p) { return p.Sk; }
+    static __device__ __forceinline__ const T* q_rows_at(const Params& p, int head) { return p.q_rows + (size_t)head * p.R * D; }
+    static __device__ __forceinline__ int q_rows_rs(const Params&) { return D; }
+    static __device__ __forceinline__ ProfTile tile(const Params& p, int k0l) {
+        const bool vid = k0l + kBN <= p.nv, tail = k0l >= p.nv;
+        return {tail ? p.tb + (k0l - p.nv) : p.g0 + k0l, vid ? p.S : p.send, !vid && !tail};
+    }
+    // what G adds behind the seam
+    static __device__ __forceinline__ int seam_jump(const Params& p) { return p.tb - p.nv - p.g0; }
 };
 
 // (The two-phase ping-pong body was tried here and is slower, 1.89 ms vs 1.22 ms: it walks every wave through every tile, and a
@@ -315,9 +361,10 @@ __device__ __forceinline__ void p16_fixup_pair(float& a, float& b, float fs) {
         b = Elt<T>::to_float(Elt<T>::from_float(Elt<T>::to_float(Elt<T>::from_float(b)) * fs));
     }
 }
-template <typename T, int D>
-__global__ __launch_bounds__(256, 2) void profile16_kernel(typename ProfilePolicy<T, D>::Params prm) {
-    using Pol = ProfilePolicy<T, D>;
+// PP: ProfilePolicy (the keys of the whole sequence) or ProfileShardPolicy (the keys of one frame shard, see the note above it)
+template <typename T, int D, typename PP>
+__global__ __launch_bounds__(256, 2) void profile16_kernel(typename PP::Params prm) {
+    using Pol = PP;
     using E = Elt<T>;
     using M = Mfma16<T>;
     using V8 = typename E::v8;
@@ -336,15 +383,20 @@ __global__ __launch_bounds__(256, 2) void profile16_kernel(typename ProfilePolic
     const int head = blockIdx.x, chunk = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
     const int g4 = lane >> 4, n16 = lane & 15;
-    const int ntiles = (prm.S + kBN - 1) / kBN;
+    const int ntiles = (Pol::key_rows(prm) + kBN - 1) / kBN;
     const int t0 = chunk * prm.tiles_per_chunk;
     const int nT = max(0, min(prm.tiles_per_chunk, ntiles - t0));
-    const T* __restrict__ qb = Pol::q_at(prm, head);
+    const T* __restrict__ qb = Pol::q_rows_at(prm, head);
     const T* __restrict__ kb_ = Pol::k_at(prm, head);
     const T* __restrict__ vb = Pol::v_at(prm, head);
+    // what classify / allowed read as the parameters: on a shard a copy whose S is the end of the keys the tile at hand can hold
+    using MaskParams = typename ProfilePolicy<T, D>::Params;
+    using TileParams = std::conditional_t<Pol::kShard, MaskParams, const MaskParams&>;
+    TileParams pt = prm;
 
     // The sampled rows in the order of their coordinate under the second mask (token-major in every model of the reference).  The squared
-    // errors are summed over the rows: their order is free.  Rank by counting, through LDS.
+    // errors are summed over the rows: their order is free.  Rank by counting, through LDS — a function of `rows` alone; on a shard a row's
+    // index in q_rows goes with its rank.
     {
         const int mine = lane < prm.R ? (int)prm.rows[lane] : 0;
         const int key = lane < prm.R ? Pol::coord(prm, prm.var[1], mine) : 0x7fffffff;
@@ -354,17 +406,23 @@ __global__ __launch_bounds__(256, 2) void profile16_kernel(typename ProfilePolic
             const int kj = __builtin_amdgcn_readlane(key, j);
             rank += (kj < key || (kj == key && j < lane)) ? 1 : 0;
         }
-        if (wave == 0) ((int*)smem)[rank] = mine;
+        if (wave == 0) {
+            ((int*)smem)[rank] = mine;
+            if constexpr (Pol::kShard) ((int*)smem)[64 + rank] = lane;
+        }
         __syncthreads();
     }
-    // this lane's sampled row (rows >= R do not exist: they read row 0 and are never stored)
+    // this lane's sampled row (rows >= R do not exist: they read row 0 and are never stored) and where its q is: the row itself, or on a
+    // shard its input index
     const int r = wave * 16 + n16;
     const bool have = r < prm.R;
     const int qrow = have ? ((const int*)smem)[r] : 0;
+    int qsrc = qrow;
+    if constexpr (Pol::kShard) qsrc = have ? ((const int*)smem)[64 + r] : 0;
     __syncthreads();    // (the staging below reuses the bytes)
     V8 qf[KS];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) qf[ks] = *(const V8*)(qb + (size_t)qrow * Pol::q_rs(prm) + ks * 32 + g4 * 8);
+    for (int ks = 0; ks < KS; ++ks) qf[ks] = *(const V8*)(qb + (size_t)qsrc * Pol::q_rows_rs(prm) + ks * 32 + g4 * 8);
 
     // the two masks' per-lane / per-wave state, as ProfilePolicy::init computes it (output 1 <- var[0], output 2 <- var[1])
     typename Pol::Ctx mc[2];
@@ -404,7 +462,7 @@ __global__ __launch_bounds__(256, 2) void profile16_kernel(typename ProfilePolic
     const unsigned k_rsb = (unsigned)Pol::k_rs(prm) * 2u, v_rsb = (unsigned)Pol::v_rs(prm) * 2u;
     auto dma_tile = [&](int t) {
         const int l = (t0 + t) * kBN + krow;
-        const unsigned nphys = (unsigned)(l < prm.S ? l : 0);    // rows behind the sequence: masked below (the last tile is never FULL)
+        const unsigned nphys = (unsigned)(l < Pol::key_rows(prm) ? l : 0);    // rows behind the keys: masked below (the last tile is never FULL)
 #pragma unroll
         for (int j = 0; j < D / 32; ++j) {
             const unsigned st = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)((t & 1) * kStage) + (unsigned)(j * (kBN * 64) + wave * 1024));
@@ -419,7 +477,8 @@ __global__ __launch_bounds__(256, 2) void profile16_kernel(typename ProfilePolic
     auto kfrag = [&](const char* st, int kblk, int ks) -> V8 { return __builtin_bit_cast(V8, Img::kfrag(st, k_lane, kblk, ks)); };
     auto vfrag = [&](const char* st, int kc, int db) -> V8 { return __builtin_bit_cast(V8, Img::vfrag(st, v_lane0, v_lane1, kc, db)); };
 
-    // ---- the wave's class table: { class under mask 0, first coordinate, class under mask 1, first coordinate } per tile of the window ----
+    // ---- the wave's class table: { class under mask 0, first coordinate, class under mask 1, first coordinate } per tile of the window,
+    //      a tile per lane ----
     int* const tab = (int*)(smem + 2 * kStage) + wave * (kP16Win * 4);
     auto fill_classes = [&](int win0) {
 #pragma unroll
@@ -427,15 +486,20 @@ __global__ __launch_bounds__(256, 2) void profile16_kernel(typename ProfilePolic
             const int tl = win0 + lane + 64 * i;
             p16_i32x4 e = {TILE_SKIP, 0, TILE_SKIP, 0};
             if (tl < nT) {
-                const int kk = (t0 + tl) * kBN;
+                const ProfTile ti = Pol::tile(prm, (t0 + tl) * kBN);
+                TileParams px = prm;
+                if constexpr (Pol::kShard) px.S = ti.send;
 #pragma unroll
                 for (int v = 0; v < 2; ++v) {
                     typename Pol::Ctx x = mc[v];
-                    int c = Pol::classify(prm, x, kk, wave * 16);
+                    int c = Pol::classify(px, x, ti.k0, wave * 16);
                     // a fast tile (64 keys at coordinates ybase + [0, 63] * ystride, none of them text) farther than the band from every row of the wave
                     if (c == TILE_PARTIAL_FAST && !x.any_text && x.ybase >= x.pv.sink_cols) {
                         const int b0 = x.ybase >> 7, b1 = (x.ybase + 63 * x.ystride) >> 7;
                         if (b0 - x.xhi_blk >= x.pv.band_blocks || x.xlo_blk - b1 >= x.pv.band_blocks) c = TILE_SKIP;
+                    }
+                    if constexpr (Pol::kShard) {
+                        if (ti.seam) c = Pol::exists(prm, wave * 16) ? TILE_PARTIAL : TILE_SKIP;   // every key through G
                     }
                     e[2 * v] = c, e[2 * v + 1] = x.ybase;
                 }
@@ -457,6 +521,8 @@ __global__ __launch_bounds__(256, 2) void profile16_kernel(typename ProfilePolic
 #pragma unroll
         for (int db = 0; db < NDB; ++db) acc[o][db] = f32x4{0.f, 0.f, 0.f, 0.f};
     const float c_log2 = prm.scale_log2;
+    int jump = 0;
+    if constexpr (Pol::kShard) jump = Pol::seam_jump(prm);
 
     if (nT > 0) dma_tile(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -469,10 +535,13 @@ __global__ __launch_bounds__(256, 2) void profile16_kernel(typename ProfilePolic
         P16_MARK(tr_wait)
         if (t + 1 < nT) dma_tile(t + 1);      // into the stage every wave finished reading one barrier ago
         const char* st = smem + (t & 1) * kStage;
-        const int k0 = (t0 + t) * kBN;
+        const int k0l = (t0 + t) * kBN;             // the tile's first key as a row of k / v ...
+        const ProfTile ti = Pol::tile(prm, k0l);
+        const int k0 = ti.k0;                       // ... and its stored index (the same number for the whole sequence)
+        if constexpr (Pol::kShard) pt.S = ti.send;
         if ((t & (kP16Win - 1)) == 0) fill_classes(t);
         int cls[3];     // (a wave without sampled rows — R < 64 — walks the tiles like the others and stores nothing)
-        cls[0] = (k0 + kBN <= prm.S) ? TILE_FULL : TILE_PARTIAL;
+        cls[0] = (k0l + kBN <= Pol::key_rows(prm)) ? TILE_FULL : TILE_PARTIAL;
         {
             const p16_i32x4 e = *(const p16_i32x4*)(tab + (t & (kP16Win - 1)) * 4);
             cls[1] = __builtin_amdgcn_readfirstlane(e[0]), mc[0].ybase = __builtin_amdgcn_readfirstlane(e[1]);
@@ -514,7 +583,7 @@ __global__ __launch_bounds__(256, 2) void profile16_kernel(typename ProfilePolic
 #pragma unroll
                 for (int b = 0; b < 4; ++b)
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) sc[b][j] = (k0 + 16 * b + 4 * g4 + j < prm.S) ? sc[b][j] : -INFINITY;
+                    for (int j = 0; j < 4; ++j) sc[b][j] = (k0l + 16 * b + 4 * g4 + j < Pol::key_rows(prm)) ? sc[b][j] : -INFINITY;
             }
             float mx = fmaxf(fmaxf(sc[0][0], sc[0][1]), fmaxf(sc[0][2], sc[0][3]));
 #pragma unroll
@@ -524,7 +593,7 @@ __global__ __launch_bounds__(256, 2) void profile16_kernel(typename ProfilePolic
             if (__any(mx * c_log2 > m_run)) {
                 asm volatile("" ::: "memory");   // (keeps the branch: x * 1 is exact, so the optimiser would rather multiply every tile)
                 const float m_new = fmaxf(m_run, quad_group_max(mx) * c_log2);
-                const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);   // (m_new is finite: a tile holds at least one key of the sequence)
+                const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);   // (m_new is finite: a tile holds at least one of the keys)
                 m_run = m_new;
 #pragma unroll
                 for (int o = 0; o < 3; ++o) {
@@ -575,10 +644,16 @@ __global__ __launch_bounds__(256, 2) void profile16_kernel(typename ProfilePolic
                         select([&](int off) { return (unsigned)(yb + off * ys) < fal; });
                     }
                 } else if (cls[v + 1] != TILE_SKIP) {
-                    (void)Pol::classify(prm, mc[v], k0, wave * 16);    // (the general predicate's per-tile decomposition: tk0, f0, p0)
+                    (void)Pol::classify(pt, mc[v], k0, wave * 16);    // (the general predicate's per-tile decomposition: tk0, f0, p0)
                     int kb = k0 + 4 * g4;
                     asm volatile("" : "+v"(kb));   // (opaque: or the optimiser computes the two masks' common sub-tests for every tile, ahead of the branch)
-                    select([&](int off) { return Pol::allowed(prm, mc[v], 0, kb + off); });
+                    if constexpr (Pol::kShard) {
+                        // the lane's first key offset behind the seam (never reached in a tile without it): from there on G adds `jump`
+                        const int thr = ti.seam ? prm.nv - k0l - 4 * g4 : 0x7fffffff;
+                        select([&](int off) { return Pol::allowed(pt, mc[v], 0, kb + off + (off >= thr ? jump : 0)); });
+                    } else {
+                        select([&](int off) { return Pol::allowed(pt, mc[v], 0, kb + off); });
+                    }
                 }
             }
             P16_MARK(tr_sm)
@@ -647,54 +722,86 @@ __global__ __launch_bounds__(256, 2) void profile16_kernel(typename ProfilePolic
     }
 }
 
-// merge the split-KV partials, normalise, and reduce squared errors.  grid = (kProfRowGroups, BH), block = 256:
-// row group rg of head h -> sq_part[h][rg][0..1] (sum of squared errors of the two masks), [2..3] NaN flags
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The merges of (O, m, l) terms.  grid = (kProfRowGroups, BH), block = 256 for all three kernels: row group rg of head h.  The terms of a
+// sampled row are either the KV chunks of ONE launch in its workspace, a chunk stride apart (ProfChunkSrc), or one buffer per part of the
+// keys, as profile_shard_reduce_kernel writes it (ProfPartSrc).  A source gives row(v, h, r), a handle of output v, head h, sampled row r,
+// term(c), one of term c < 64 (no memory of the term is touched: c may lie behind the last term), and at(row, term, j), word j of that
+// term of that row: words [0, D) are O, D is m, D + 1 is l.
 constexpr int kProfRowGroups = 32;   // (8 until round 5: 192 workgroups read 51 MB of partials in 0.112 ms; 32: 768 workgroups)
+constexpr int kProfRowsPer = (kProfMaxRows + kProfRowGroups - 1) / kProfRowGroups;
+constexpr int kProfMaxParts = 64;    // a term per lane, parts like chunks
+struct ProfPartPtrs {                // the part pointers travel in the kernel arguments (a host array at the ABI)
+    const float* p[kProfMaxParts];
+};
 
-template <typename T, int D>
-__global__ __launch_bounds__(256) void profile_combine_kernel(const float* __restrict__ part, float* __restrict__ sq_part, int BH,
-                                                              int R, int n_chunks, int emulate, const int32_t* __restrict__ skip) {
-    __shared__ float red[4][4];
-    if (skip && skip[0] != 0) return;
-    const int rg = blockIdx.x, h = blockIdx.y, tid = threadIdx.x;
-    const int rows_per = (R + kProfRowGroups - 1) / kProfRowGroups;
-    const int r0 = rg * rows_per, r1 = min(R, r0 + rows_per);
-    float sq[2] = {0.f, 0.f};
-    float bad[2] = {0.f, 0.f};
-    constexpr int DS = D + 4;
-    const size_t cs = (size_t)kProfMaxRows * DS;
-    // the chunks' weights 2^(m_c - M) and the denominators once per (output, row) — a chunk per lane — instead of per element (every one of a row's
-    // D threads re-read its chunks' m twice and l once: 0.033 ms of a 0.355 ms call); the sums in the same order as before: the same bits
-    constexpr int kRowsPer = (kProfMaxRows + kProfRowGroups - 1) / kProfRowGroups;
-    __shared__ float wsh[3][kRowsPer][64], lws[3][kRowsPer][64], lsh[3][kRowsPer];
-    const int nrows = max(r1 - r0, 0);
+template <int D>
+struct ProfChunkSrc {   // [3][BH][n][kProfMaxRows][D + 4]
+    const float* __restrict__ part;
+    int BH, n;
+    static constexpr size_t cs = (size_t)kProfMaxRows * (D + 4);
+    __device__ __forceinline__ const float* row(int v, int h, int r) const { return part + ((((size_t)v * BH + h) * n) * kProfMaxRows + r) * (D + 4); }
+    __device__ __forceinline__ size_t term(int c) const { return c * cs; }
+    __device__ __forceinline__ float at(const float* base, size_t t, int j) const { return base[t + j]; }
+};
+template <int D>
+struct ProfPartSrc {    // n buffers [3][BH][R][D + 4]
+    const ProfPartPtrs& parts;
+    int BH, R, n;
+    __device__ __forceinline__ size_t row(int v, int h, int r) const { return (((size_t)v * BH + h) * R + r) * (D + 4); }
+    __device__ __forceinline__ const float* term(int c) const { return parts.p[c]; }
+    __device__ __forceinline__ float at(size_t off, const float* t, int j) const { return t[off + j]; }
+};
+
+// The terms' weights w_c = 2^(m_c - M), M = max_c m_c, into wsh and the denominators l = sum_c l_c w_c (in term order) into lsh, once per
+// (output, row) of the row group [r0, r0 + nrows) — a term per lane — instead of per element (every one of a row's D threads re-read its
+// terms' m twice and l once: 0.033 ms of a 0.355 ms call); msh, where given, receives M.  Ends behind a barrier.
+template <int D, typename Src>
+__device__ __forceinline__ void prof_term_weights(const Src& src, int h, int r0, int nrows, float (*wsh)[kProfRowsPer][64],
+                                                  float (*lws)[kProfRowsPer][64], float (*lsh)[kProfRowsPer], float (*msh)[kProfRowsPer]) {
+    const int tid = threadIdx.x, c = tid & 63;
+    const auto term = src.term(c);
     for (int pi = tid >> 6; pi < 3 * nrows; pi += 4) {
-        const int v = pi / nrows, rr = pi - v * nrows, c = tid & 63;
-        const float* base = part + ((((size_t)v * BH + h) * n_chunks) * kProfMaxRows + r0 + rr) * DS;
-        const float mc = c < n_chunks ? base[c * cs + D] : -INFINITY;
+        const int v = pi / nrows, rr = pi - v * nrows;
+        const auto base = src.row(v, h, r0 + rr);
+        const float mc = c < src.n ? src.at(base, term, D) : -INFINITY;
         const float M = wave_max(mc);
         const float w = (mc == -INFINITY) ? 0.f : exp2f(mc - M);
         wsh[v][rr][c] = w;
-        lws[v][rr][c] = c < n_chunks ? base[c * cs + D + 1] * w : 0.f;
+        lws[v][rr][c] = c < src.n ? src.at(base, term, D + 1) * w : 0.f;
+        if (msh && c == 0) msh[v][rr] = M;
     }
     __syncthreads();
     if (tid < 3 * nrows) {
         const int v = tid / nrows, rr = tid - v * nrows;
         float L = 0.f;
-        for (int c = 0; c < n_chunks; ++c) L += lws[v][rr][c];
+        for (int c = 0; c < src.n; ++c) L += lws[v][rr][c];
         lsh[v][rr] = L;
     }
     __syncthreads();
+}
+
+// merge the terms, normalise, and reduce squared errors: -> sq_part[h][rg][0..1] (sum of squared errors of the two masks), [2..3] NaN flags
+template <typename T, int D, typename Src>
+__device__ __forceinline__ void prof_combine_body(const Src& src, float* __restrict__ sq_part, int R, int emulate) {
+    __shared__ float red[4][4];
+    __shared__ float wsh[3][kProfRowsPer][64], lws[3][kProfRowsPer][64], lsh[3][kProfRowsPer];
+    const int rg = blockIdx.x, h = blockIdx.y, tid = threadIdx.x;
+    const int rows_per = (R + kProfRowGroups - 1) / kProfRowGroups;
+    const int r0 = rg * rows_per, r1 = min(R, r0 + rows_per);
+    float sq[2] = {0.f, 0.f};
+    float bad[2] = {0.f, 0.f};
+    prof_term_weights<D>(src, h, r0, max(r1 - r0, 0), wsh, lws, lsh, nullptr);
     for (int e = r0 * D + tid; e < r1 * D; e += 256) {
         const int row = e / D, d = e - row * D;
         float o[3];
 #pragma unroll
         for (int v = 0; v < 3; ++v) {
-            const float* base = part + ((((size_t)v * BH + h) * n_chunks) * kProfMaxRows + row) * DS;
+            const auto base = src.row(v, h, row);
             const float L = lsh[v][row - r0];
             float acc = 0.f;
-            for (int c = 0; c < n_chunks; ++c) acc += base[c * cs + d] * wsh[v][row - r0][c];
-            // a row whose mask admits no key is NaN in the reference (softmax over all -inf)
+            for (int c = 0; c < src.n; ++c) acc += src.at(base, src.term(c), d) * wsh[v][row - r0][c];   // (the sums in term order: the bits depend on it)
+            // a row whose mask admits no key of any term is NaN in the reference (softmax over all -inf)
             o[v] = (L > 0.f) ? acc / L : __builtin_nanf("");
             if (emulate) o[v] = Elt<T>::to_float(Elt<T>::from_float(o[v]));
         }
@@ -718,6 +825,55 @@ __global__ __launch_bounds__(256) void profile_combine_kernel(const float* __res
     }
     __syncthreads();
     if (tid < 4) sq_part[((size_t)h * kProfRowGroups + rg) * 4 + tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
+}
+
+// the split-KV partials of one launch
+template <typename T, int D>
+__global__ __launch_bounds__(256) void profile_combine_kernel(const float* __restrict__ part, float* __restrict__ sq_part, int BH,
+                                                              int R, int n_chunks, int emulate, const int32_t* __restrict__ skip) {
+    if (skip && skip[0] != 0) return;
+    prof_combine_body<T, D>(ProfChunkSrc<D>{part, BH, n_chunks}, sq_part, R, emulate);
+}
+
+// a pointer per part, at most kProfMaxParts: one part of the whole sequence gives the bits of profile_combine_kernel (weight 2^0, one term
+// added to 0: it divides the numbers that kernel divides)
+template <typename T, int D>
+__global__ __launch_bounds__(256) void profile_combine_parts_kernel(ProfPartPtrs parts, float* __restrict__ sq_part, int BH, int R, int n_parts,
+                                                                    int emulate, const int32_t* __restrict__ skip) {
+    if (skip && skip[0] != 0) return;
+    prof_combine_body<T, D>(ProfPartSrc<D>{parts, BH, R, n_parts}, sq_part, R, emulate);
+}
+
+// A shard's chunks folded into ONE (O, m, l) per (output, head, row): O = sum_c O_c w_c in chunk order and the M and l of prof_term_weights —
+// the sums as prof_combine_body writes them (same order, same expressions).  out: [3][BH][R][D + 4], every word written (columns D + 2,
+// D + 3: 0).
+template <int D>
+__global__ __launch_bounds__(256) void profile_shard_reduce_kernel(const float* __restrict__ part, float* __restrict__ out, int BH, int R,
+                                                                   int n_chunks, const int32_t* __restrict__ skip) {
+    if (skip && skip[0] != 0) return;
+    __shared__ float wsh[3][kProfRowsPer][64], lws[3][kProfRowsPer][64], lsh[3][kProfRowsPer], msh[3][kProfRowsPer];
+    const ProfChunkSrc<D> src{part, BH, n_chunks};
+    const int rg = blockIdx.x, h = blockIdx.y, tid = threadIdx.x;
+    const int rows_per = (R + kProfRowGroups - 1) / kProfRowGroups;
+    const int r0 = rg * rows_per, r1 = min(R, r0 + rows_per);
+    const int nrows = max(r1 - r0, 0);
+    constexpr int DS = D + 4;
+    prof_term_weights<D>(src, h, r0, nrows, wsh, lws, lsh, msh);
+    for (int e = r0 * D + tid; e < r1 * D; e += 256) {
+        const int row = e / D, d = e - row * D;
+#pragma unroll
+        for (int v = 0; v < 3; ++v) {
+            const float* base = src.row(v, h, row);
+            float acc = 0.f;
+            for (int c = 0; c < n_chunks; ++c) acc += src.at(base, src.term(c), d) * wsh[v][row - r0][c];
+            out[(((size_t)v * BH + h) * R + row) * DS + d] = acc;
+        }
+    }
+    if (tid < 3 * nrows) {
+        const int v = tid / nrows, rr = tid - v * nrows;
+        float* dst = out + (((size_t)v * BH + h) * R + r0 + rr) * DS + D;
+        dst[0] = msh[v][rr], dst[1] = lsh[v][rr], dst[2] = 0.f, dst[3] = 0.f;
+    }
 }
 
 // grid = (1), block = 256: out_mse[v][h] = mean over rows and D (NaN when any sampled row had no visible key)
@@ -747,16 +903,14 @@ static int prof_chunks(int BH, int S) {
     return n;
 }
 
-template <typename T, int D>
-static int run_profile(const void* q, const void* k, const void* v, const int64_t* rows, int R, int BH, int S, float sm_scale,
-                       const svg_profile_desc_t* pd, float* out_mse, void* ws, const int32_t* skip, const AttnLayout* lay, hipStream_t st) {
-    using Pol = ProfilePolicy<T, D>;
-    typename Pol::Params p;
-    p.q = (const T*)q, p.k = (const T*)k, p.v = (const T*)v;
-    p.lay = lay ? *lay : contiguous_layout(BH, BH, S, S, D);
+// What a launch over the whole sequence and one over a shard both set: the split of `key_rows` rows of k / v into chunks, the scale and its
+// emulation, the sampled rows, the video's geometry, the two masks, the workspace and the skip flag.  (q, k, v and their layout: the caller.)
+template <typename Prm>
+static void prof_fill_params(Prm& p, const int64_t* rows, int R, int BH, int S, int key_rows, float sm_scale, const svg_profile_desc_t* pd,
+                             void* ws, const int32_t* skip) {
     p.S = S, p.BH = BH, p.R = R;
-    p.n_chunks = prof_chunks(BH, S);
-    const int ntiles = (S + kBN - 1) / kBN;
+    p.n_chunks = prof_chunks(BH, key_rows);
+    const int ntiles = (key_rows + kBN - 1) / kBN;
     p.tiles_per_chunk = (ntiles + p.n_chunks - 1) / p.n_chunks;
     p.emulate = pd->emulate_bf16;
     p.scale_log2 = p.emulate ? 1.4426950408889634f : sm_scale * 1.4426950408889634f;
@@ -774,6 +928,16 @@ static int run_profile(const void* q, const void* k, const void* v, const int64_
     }
     p.part = (float*)ws;
     p.skip = skip;
+}
+
+template <typename T, int D>
+static int run_profile(const void* q, const void* k, const void* v, const int64_t* rows, int R, int BH, int S, float sm_scale,
+                       const svg_profile_desc_t* pd, float* out_mse, void* ws, const int32_t* skip, const AttnLayout* lay, hipStream_t st) {
+    using Pol = ProfilePolicy<T, D>;
+    typename Pol::Params p;
+    p.q = (const T*)q, p.k = (const T*)k, p.v = (const T*)v;
+    p.lay = lay ? *lay : contiguous_layout(BH, BH, S, S, D);
+    prof_fill_params(p, rows, R, BH, S, S, sm_scale, pd, ws, skip);
     // bf16: the second form.  fp16: the first form — the second one exponentiates the masked rows against the golden rows' maximum, and an fp16
     // probability only reaches 39 binades (27 in logit) below it: a sampled row whose best in-mask key sits further down would lose its row sum
     // (NaN for the whole head, where the reference is finite).  bf16 probabilities reach 186 binades (129 in logit); the first form keeps a
@@ -782,7 +946,7 @@ static int run_profile(const void* q, const void* k, const void* v, const int64_
     if (!kSecondForm && !p.lay.rows_contiguous(D)) return SVG_ERR_UNSUPPORTED;   // row strides: the second form only (svg_attn_layout_t)
     if constexpr (kSecondForm) {   // one score tile for the three outputs, two workgroups per CU
         constexpr int lds16 = p16_lds_bytes(D);
-        auto kern16 = profile16_kernel<T, D>;
+        auto kern16 = profile16_kernel<T, D, Pol>;
         if (const int rc = configure_lds((const void*)kern16, lds16); rc != SVG_OK) return rc;
         hipLaunchKernelGGL(kern16, dim3(BH, p.n_chunks), dim3(256), lds16, st, p);
     } else {   // three roles x two waves of the lock-step body, each role its own scores and running maximum
@@ -799,451 +963,6 @@ static int run_profile(const void* q, const void* k, const void* v, const int64_
     return launch_status();
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------------
-// Shard form of the second form (include/svg_attn_profile_shard.h): the keys are the rows of ONE frame shard — the whole frames
-// [f0, f0 + n_frames) and a tail behind the video — and the sampled q rows arrive gathered.  A shard is a set of KV chunks that lives on
-// another GPU: the kernel below is profile16_kernel (its arithmetic copied, not shared: the listing of profile16_kernel stays what it was)
-// with
-//   * q read from the compact q_rows: a lane's row is the INPUT index of the row it ranked, `rows` only gives coordinates;
-//   * tiles on the shard's LOCAL grid: local key l is physical row l of k / v, and every bound against S is one against Sk;
-//   * the mask on the key's stored global index G(l) = g0 + l (l < nv, g0 = f0 P) or tb + (l - nv): a tile wholly in the video rows or wholly
-//     in the tail is the existing code at k0 = G(first key) — classify, the fast paths, the class table, the one-wrap stepping of allowed —
-//     with the end of the keys such a tile can hold in the place of S; the ONE tile that holds the seam l = nv is TILE_PARTIAL under both masks
-//     and maps each key through G (G is continuous there for a shard whose frames end at F; the ABI allows one that is not).
-// profile_shard_reduce_kernel then folds the chunks into one (O, m, l) per (output, head, row) with the sums of profile_combine_kernel, and
-// profile_combine_parts_kernel is that kernel's body over a pointer per part: one part of the whole sequence gives the bits of svg_sample_mse.
-template <typename T, int D>
-struct ProfileShardPolicy : ProfilePolicy<T, D> {
-    struct Params : ProfilePolicy<T, D>::Params {
-        const T* q_rows;    // [BH][R][D]
-        int Sk, nv;         // rows of the shard, of them video rows
-        int g0, tb, send;   // G(0); G(nv) (F P for a shard without a tail); the end of the stored indices: tb + n_tail
-    };
-};
-
-template <typename T, int D>
-__global__ __launch_bounds__(256, 2) void profile16_shard_kernel(typename ProfileShardPolicy<T, D>::Params prm) {
-    using Pol = ProfilePolicy<T, D>;
-    using E = Elt<T>;
-    using M = Mfma16<T>;
-    using V8 = typename E::v8;
-    constexpr int KS = D / 32, NDB = D / 16;
-    using Img = KvImage16<D>;
-    constexpr int kImg = Img::kImg, kStage = Img::kStage;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (prm.skip && prm.skip[0] != 0) return;
-    const int head = blockIdx.x, chunk = blockIdx.y;
-    const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
-    const int g4 = lane >> 4, n16 = lane & 15;
-    const int ntiles = (prm.Sk + kBN - 1) / kBN;
-    const int t0 = chunk * prm.tiles_per_chunk;
-    const int nT = max(0, min(prm.tiles_per_chunk, ntiles - t0));
-    const T* __restrict__ qb = prm.q_rows + (size_t)head * prm.R * D;
-    const T* __restrict__ kb_ = Pol::k_at(prm, head);
-    const T* __restrict__ vb = Pol::v_at(prm, head);
-    typename Pol::Params pt = prm;   // (pt.S: the end of the keys the tile at hand can hold, see above)
-
-    // the rank order of profile16_kernel, a function of `rows` alone; with a row's rank goes its index in q_rows
-    {
-        const int mine = lane < prm.R ? (int)prm.rows[lane] : 0;
-        const int key = lane < prm.R ? Pol::coord(prm, prm.var[1], mine) : 0x7fffffff;
-        int rank = 0;
-#pragma unroll
-        for (int j = 0; j < 64; ++j) {
-            const int kj = __builtin_amdgcn_readlane(key, j);
-            rank += (kj < key || (kj == key && j < lane)) ? 1 : 0;
-        }
-        if (wave == 0) ((int*)smem)[rank] = mine, ((int*)smem)[64 + rank] = lane;
-        __syncthreads();
-    }
-    const int r = wave * 16 + n16;
-    const bool have = r < prm.R;
-    const int qrow = have ? ((const int*)smem)[r] : 0;
-    const int qidx = have ? ((const int*)smem)[64 + r] : 0;
-    __syncthreads();    // (the staging below reuses the bytes)
-    V8 qf[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) qf[ks] = *(const V8*)(qb + (size_t)qidx * D + ks * 32 + g4 * 8);
-
-    typename Pol::Ctx mc[2];
-#pragma unroll
-    for (int v = 0; v < 2; ++v) {
-        typename Pol::Ctx& c = mc[v];
-        c.head = head, c.variant = v + 1, c.chunk = chunk, c.t0 = t0, c.nT = nT;
-        c.pv = prm.var[v];
-        c.qx = Pol::coord(prm, c.pv, qrow) - c.pv.origin;
-        c.qtext = have && ((unsigned)(qrow - c.pv.text_lo) < (unsigned)(c.pv.text_hi - c.pv.text_lo));
-        const int blk = c.qx >> 7;
-        int lo = have ? blk : (1 << 28), hi = have ? blk : -(1 << 28), anyt = c.qtext;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            lo = min(lo, __shfl_xor(lo, o));
-            hi = max(hi, __shfl_xor(hi, o));
-            anyt |= __shfl_xor(anyt, o);
-        }
-        c.xlo_blk = __builtin_amdgcn_readfirstlane(lo), c.xhi_blk = __builtin_amdgcn_readfirstlane(hi);
-        c.any_text = __builtin_amdgcn_readfirstlane(anyt);
-        c.tk0 = 0, c.f0 = 0, c.p0 = 0;
-        c.ystride = c.pv.coord == 1 ? prm.F : 1;
-        c.ybase = 0, c.g4F = 4 * g4 * c.ystride;
-        const int x = c.qx, span = c.pv.span;
-        const bool xdom = have && ((unsigned)x < (unsigned)span);
-        const int ylo = ((x >> 7) - c.pv.band_blocks + 1) * 128, yhi = ((x >> 7) + c.pv.band_blocks) * 128;
-        const int a0 = max(ylo, 0), a1 = min(yhi, span);
-        c.fa0 = a0, c.falen = xdom ? (unsigned)max(a1 - a0, 0) : 0u;
-        c.fblen = (xdom && c.pv.sink_cols > 0) ? (unsigned)min(c.pv.sink_cols, span) : 0u;
-        if (c.qtext) c.fa0 = -(1 << 30), c.falen = 0xFFFFFFFFu;
-    }
-
-    // ---- LDS-DMA staging on the shard's rows ----
-    const unsigned lds0 = (unsigned)(size_t)smem;
-    const unsigned col_v = Img::col_v(lane);
-    const int krow = 16 * wave + (lane >> 2);
-    const unsigned k_rsb = (unsigned)Pol::k_rs(prm) * 2u, v_rsb = (unsigned)Pol::v_rs(prm) * 2u;
-    auto dma_tile = [&](int t) {
-        const int l = (t0 + t) * kBN + krow;
-        const unsigned nphys = (unsigned)(l < prm.Sk ? l : 0);    // rows behind the shard: masked below (the last tile is never FULL)
-#pragma unroll
-        for (int j = 0; j < D / 32; ++j) {
-            const unsigned st = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)((t & 1) * kStage) + (unsigned)(j * (kBN * 64) + wave * 1024));
-            const unsigned ko = __umul24(nphys, k_rsb) + ((unsigned)(j * 64) | col_v);
-            const unsigned vo = __umul24(nphys, v_rsb) + ((unsigned)(j * 64) | col_v);
-            lds_dma16_kv<kImg>(st, ko, vo, kb_, vb);
-        }
-    };
-    const int k_lane = Img::k_lane(g4, n16);
-    const int v_lane0 = Img::v_lane0(g4, n16);
-    const int v_lane1 = v_lane0 ^ 32;
-    auto kfrag = [&](const char* st, int kblk, int ks) -> V8 { return __builtin_bit_cast(V8, Img::kfrag(st, k_lane, kblk, ks)); };
-    auto vfrag = [&](const char* st, int kc, int db) -> V8 { return __builtin_bit_cast(V8, Img::vfrag(st, v_lane0, v_lane1, kc, db)); };
-
-    // ---- the wave's class table, a tile per lane: the tile's first stored index and the end of the keys it can hold ----
-    int* const tab = (int*)(smem + 2 * kStage) + wave * (kP16Win * 4);
-    auto fill_classes = [&](int win0) {
-#pragma unroll
-        for (int i = 0; i < kP16Win / 64; ++i) {
-            const int tl = win0 + lane + 64 * i;
-            p16_i32x4 e = {TILE_SKIP, 0, TILE_SKIP, 0};
-            if (tl < nT) {
-                const int kl = (t0 + tl) * kBN;
-                const bool vid = kl + kBN <= prm.nv, tail = kl >= prm.nv;
-                const int kk = tail ? prm.tb + (kl - prm.nv) : prm.g0 + kl;
-                typename Pol::Params px = prm;
-                px.S = vid ? prm.S : prm.send;
-#pragma unroll
-                for (int v = 0; v < 2; ++v) {
-                    typename Pol::Ctx x = mc[v];
-                    int c = Pol::classify(px, x, kk, wave * 16);
-                    if (c == TILE_PARTIAL_FAST && !x.any_text && x.ybase >= x.pv.sink_cols) {
-                        const int b0 = x.ybase >> 7, b1 = (x.ybase + 63 * x.ystride) >> 7;
-                        if (b0 - x.xhi_blk >= x.pv.band_blocks || x.xlo_blk - b1 >= x.pv.band_blocks) c = TILE_SKIP;
-                    }
-                    if (!vid && !tail) c = Pol::exists(prm, wave * 16) ? TILE_PARTIAL : TILE_SKIP;   // the seam: every key through G
-                    e[2 * v] = c, e[2 * v + 1] = x.ybase;
-                }
-            }
-            *(p16_i32x4*)(tab + (lane + 64 * i) * 4) = e;
-        }
-    };
-
-    float m_run = -INFINITY;
-    f32x4 acc_l[3] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-    V8 ones8;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ones8[i] = E::from_float(1.f);
-    f32x4 acc[3][NDB];
-#pragma unroll
-    for (int o = 0; o < 3; ++o)
-#pragma unroll
-        for (int db = 0; db < NDB; ++db) acc[o][db] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const float c_log2 = prm.scale_log2;
-    const int jump = prm.tb - prm.nv - prm.g0;    // what G adds behind the seam
-
-    if (nT > 0) dma_tile(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[ks]));
-    __syncthreads();
-    for (int t = 0; t < nT; ++t) {
-        if (t + 1 < nT) dma_tile(t + 1);
-        const char* st = smem + (t & 1) * kStage;
-        const int k0l = (t0 + t) * kBN;                                  // the tile's first key on the shard's grid ...
-        const bool vid = k0l + kBN <= prm.nv, tail = k0l >= prm.nv;
-        const int k0 = tail ? prm.tb + (k0l - prm.nv) : prm.g0 + k0l;    // ... and its stored index
-        pt.S = vid ? prm.S : prm.send;
-        if ((t & (kP16Win - 1)) == 0) fill_classes(t);
-        int cls[3];
-        cls[0] = (k0l + kBN <= prm.Sk) ? TILE_FULL : TILE_PARTIAL;
-        {
-            const p16_i32x4 e = *(const p16_i32x4*)(tab + (t & (kP16Win - 1)) * 4);
-            cls[1] = __builtin_amdgcn_readfirstlane(e[0]), mc[0].ybase = __builtin_amdgcn_readfirstlane(e[1]);
-            cls[2] = __builtin_amdgcn_readfirstlane(e[2]), mc[1].ybase = __builtin_amdgcn_readfirstlane(e[3]);
-        }
-        {
-            f32x4 sc[4];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) sc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
-            {
-                V8 kf[2][4];
-#pragma unroll
-                for (int b = 0; b < 4; ++b) kf[0][b] = kfrag(st, b, 0);
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-                    if (ks + 1 < KS) {
-#pragma unroll
-                        for (int b = 0; b < 4; ++b) kf[(ks + 1) & 1][b] = kfrag(st, b, ks + 1);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) sc[b] = M::mfma(kf[ks & 1][b], qf[ks], sc[b]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            if (prm.emulate) {
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    float s0 = sc[b][0], s1 = sc[b][1], s2 = sc[b][2], s3 = sc[b][3];
-                    p16_fixup_pair<T>(s0, s1, prm.fix_scale);
-                    p16_fixup_pair<T>(s2, s3, prm.fix_scale);
-                    sc[b] = f32x4{s0, s1, s2, s3};
-                }
-            }
-            if (cls[0] != TILE_FULL) {
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) sc[b][j] = (k0l + 16 * b + 4 * g4 + j < prm.Sk) ? sc[b][j] : -INFINITY;
-            }
-            float mx = fmaxf(fmaxf(sc[0][0], sc[0][1]), fmaxf(sc[0][2], sc[0][3]));
-#pragma unroll
-            for (int b = 1; b < 4; ++b) mx = fmaxf(fmaxf(mx, sc[b][0]), fmaxf(fmaxf(sc[b][1], sc[b][2]), sc[b][3]));
-            if (__any(mx * c_log2 > m_run)) {
-                asm volatile("" ::: "memory");
-                const float m_new = fmaxf(m_run, quad_group_max(mx) * c_log2);
-                const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);   // (m_new is finite: a tile holds at least one key of the shard)
-                m_run = m_new;
-#pragma unroll
-                for (int o = 0; o < 3; ++o) {
-                    acc_l[o][0] *= alpha;
-#pragma unroll
-                    for (int db = 0; db < NDB; ++db)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) acc[o][db][j] *= alpha;
-                }
-            }
-            constexpr float kBias = std::is_same_v<T, __bf16> ? 60.f : 15.f;    // (see profile16_kernel)
-            const float m_use = m_run - kBias;
-            V8 pf[3][2];
-            float pr[16];
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    pr[4 * b + j] = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[b][j], c_log2, -m_use));
-                    pf[0][b >> 1][4 * (b & 1) + j] = E::from_float(pr[4 * b + j]);
-                }
-#pragma unroll
-            for (int v = 0; v < 2; ++v) {
-                auto select = [&](auto pred) {
-#pragma unroll
-                    for (int b = 0; b < 4; ++b)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const float pm = pred(16 * b + j) ? pr[4 * b + j] : 0.f;
-                            pf[v + 1][b >> 1][4 * (b & 1) + j] = E::from_float(pm);
-                        }
-                };
-                if (cls[v + 1] == TILE_PARTIAL_FAST) {
-                    const int yb = mc[v].ybase + mc[v].g4F - mc[v].fa0, ys = mc[v].ystride;
-                    const unsigned fal = mc[v].falen, fbl = mc[v].fblen;
-                    if (mc[v].pv.sink_cols > 0) {
-                        const int fa0 = mc[v].fa0;
-                        select([&](int off) { return ((unsigned)(yb + off * ys) < fal) | ((unsigned)(yb + fa0 + off * ys) < fbl); });
-                    } else {
-                        select([&](int off) { return (unsigned)(yb + off * ys) < fal; });
-                    }
-                } else if (cls[v + 1] != TILE_SKIP) {
-                    (void)Pol::classify(pt, mc[v], k0, wave * 16);    // (the general predicate's per-tile decomposition: tk0, f0, p0)
-                    int kb = k0 + 4 * g4;
-                    asm volatile("" : "+v"(kb));
-                    // the lane's first key offset behind the seam (never reached in a tile without it): from there on G adds `jump`
-                    const int thr = (vid || tail) ? 0x7fffffff : prm.nv - k0l - 4 * g4;
-                    select([&](int off) { return Pol::allowed(pt, mc[v], 0, kb + off + (off >= thr ? jump : 0)); });
-                }
-            }
-            {
-                constexpr int G = 4, NG = 2 * NDB / G;
-                const bool s1 = cls[1] != TILE_SKIP, s2 = cls[2] != TILE_SKIP;
-                V8 vf[2][G];
-#pragma unroll
-                for (int i = 0; i < G; ++i) vf[0][i] = vfrag(st, 0, i);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) {
-                    if (g + 1 < NG) {
-#pragma unroll
-                        for (int i = 0; i < G; ++i) vf[(g + 1) & 1][i] = vfrag(st, ((g + 1) * G + i) / NDB, ((g + 1) * G + i) % NDB);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int i = 0; i < G; ++i) acc[0][(g * G + i) % NDB] = M::mfma(vf[g & 1][i], pf[0][(g * G + i) / NDB], acc[0][(g * G + i) % NDB]);
-                    if ((g * G) % NDB == 0) acc_l[0] = M::mfma(ones8, pf[0][(g * G) / NDB], acc_l[0]);
-                    if (s1) {
-                        if ((g * G) % NDB == 0) acc_l[1] = M::mfma(ones8, pf[1][(g * G) / NDB], acc_l[1]);
-#pragma unroll
-                        for (int i = 0; i < G; ++i) acc[1][(g * G + i) % NDB] = M::mfma(vf[g & 1][i], pf[1][(g * G + i) / NDB], acc[1][(g * G + i) % NDB]);
-                    }
-                    if (s2) {
-                        if ((g * G) % NDB == 0) acc_l[2] = M::mfma(ones8, pf[2][(g * G) / NDB], acc_l[2]);
-#pragma unroll
-                        for (int i = 0; i < G; ++i) acc[2][(g * G + i) % NDB] = M::mfma(vf[g & 1][i], pf[2][(g * G + i) / NDB], acc[2][(g * G + i) % NDB]);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-    // ---- the chunk's partials into the workspace, in the layout of profile16_kernel ----
-    if (have) {
-#pragma unroll
-        for (int o = 0; o < 3; ++o) {
-            float* dst = prm.part + ((((size_t)o * prm.BH + head) * prm.n_chunks + chunk) * kProfMaxRows + r) * (D + 4);
-#pragma unroll
-            for (int db = 0; db < NDB; ++db) *(f32x4*)(dst + 16 * db + 4 * g4) = acc[o][db];
-            if (g4 == 0) {
-                dst[D] = m_run;
-                dst[D + 1] = acc_l[o][0];
-            }
-        }
-    }
-}
-
-// The shard's chunks folded into ONE (O, m, l) per (output, head, row): grid = (kProfRowGroups, BH), block = 256, the row groups of
-// profile_combine_kernel.  M = max_c m_c, w_c = 2^(m_c - M), O = sum_c O_c w_c and l = sum_c l_c w_c in chunk order — the sums as
-// profile_combine_kernel writes them (same order, same expressions), so that the combine over ONE such part (weight 2^0, one term added to 0)
-// divides the numbers that kernel divides.  out: [3][BH][R][D + 4], every word written (columns D + 2, D + 3: 0).
-template <int D>
-__global__ __launch_bounds__(256) void profile_shard_reduce_kernel(const float* __restrict__ part, float* __restrict__ out, int BH, int R,
-                                                                   int n_chunks, const int32_t* __restrict__ skip) {
-    if (skip && skip[0] != 0) return;
-    const int rg = blockIdx.x, h = blockIdx.y, tid = threadIdx.x;
-    const int rows_per = (R + kProfRowGroups - 1) / kProfRowGroups;
-    const int r0 = rg * rows_per, r1 = min(R, r0 + rows_per);
-    constexpr int DS = D + 4;
-    const size_t cs = (size_t)kProfMaxRows * DS;
-    constexpr int kRowsPer = (kProfMaxRows + kProfRowGroups - 1) / kProfRowGroups;
-    __shared__ float wsh[3][kRowsPer][64], lws[3][kRowsPer][64], lsh[3][kRowsPer], msh[3][kRowsPer];
-    const int nrows = max(r1 - r0, 0);
-    for (int pi = tid >> 6; pi < 3 * nrows; pi += 4) {
-        const int v = pi / nrows, rr = pi - v * nrows, c = tid & 63;
-        const float* base = part + ((((size_t)v * BH + h) * n_chunks) * kProfMaxRows + r0 + rr) * DS;
-        const float mc = c < n_chunks ? base[c * cs + D] : -INFINITY;
-        const float M = wave_max(mc);
-        const float w = (mc == -INFINITY) ? 0.f : exp2f(mc - M);
-        wsh[v][rr][c] = w;
-        lws[v][rr][c] = c < n_chunks ? base[c * cs + D + 1] * w : 0.f;
-        if (c == 0) msh[v][rr] = M;
-    }
-    __syncthreads();
-    if (tid < 3 * nrows) {
-        const int v = tid / nrows, rr = tid - v * nrows;
-        float L = 0.f;
-        for (int c = 0; c < n_chunks; ++c) L += lws[v][rr][c];
-        lsh[v][rr] = L;
-    }
-    __syncthreads();
-    for (int e = r0 * D + tid; e < r1 * D; e += 256) {
-        const int row = e / D, d = e - row * D;
-#pragma unroll
-        for (int v = 0; v < 3; ++v) {
-            const float* base = part + ((((size_t)v * BH + h) * n_chunks) * kProfMaxRows + row) * DS;
-            float acc = 0.f;
-            for (int c = 0; c < n_chunks; ++c) acc += base[c * cs + d] * wsh[v][row - r0][c];
-            out[(((size_t)v * BH + h) * R + row) * DS + d] = acc;
-        }
-    }
-    if (tid < 3 * nrows) {
-        const int v = tid / nrows, rr = tid - v * nrows;
-        float* dst = out + (((size_t)v * BH + h) * R + r0 + rr) * DS + D;
-        dst[0] = msh[v][rr], dst[1] = lsh[v][rr], dst[2] = 0.f, dst[3] = 0.f;
-    }
-}
-
-// profile_combine_kernel over a pointer per part instead of a chunk stride, a part's rows strided by R: [3][BH][R][D + 4] each.  The part
-// pointers travel in the kernel arguments (a host array at the ABI), at most kProfMaxParts — a part per lane like a chunk per lane there.
-constexpr int kProfMaxParts = 64;
-struct ProfPartPtrs {
-    const float* p[kProfMaxParts];
-};
-
-template <typename T, int D>
-__global__ __launch_bounds__(256) void profile_combine_parts_kernel(ProfPartPtrs parts, float* __restrict__ sq_part, int BH, int R, int n_parts,
-                                                                    int emulate, const int32_t* __restrict__ skip) {
-    __shared__ float red[4][4];
-    if (skip && skip[0] != 0) return;
-    const int rg = blockIdx.x, h = blockIdx.y, tid = threadIdx.x;
-    const int rows_per = (R + kProfRowGroups - 1) / kProfRowGroups;
-    const int r0 = rg * rows_per, r1 = min(R, r0 + rows_per);
-    float sq[2] = {0.f, 0.f};
-    float bad[2] = {0.f, 0.f};
-    constexpr int DS = D + 4;
-    constexpr int kRowsPer = (kProfMaxRows + kProfRowGroups - 1) / kProfRowGroups;
-    __shared__ float wsh[3][kRowsPer][64], lws[3][kRowsPer][64], lsh[3][kRowsPer];
-    const int nrows = max(r1 - r0, 0);
-    for (int pi = tid >> 6; pi < 3 * nrows; pi += 4) {
-        const int v = pi / nrows, rr = pi - v * nrows, c = tid & 63;
-        const size_t off = (((size_t)v * BH + h) * R + r0 + rr) * DS;
-        const float* base = parts.p[c < n_parts ? c : 0] + off;
-        const float mc = c < n_parts ? base[D] : -INFINITY;
-        const float M = wave_max(mc);
-        const float w = (mc == -INFINITY) ? 0.f : exp2f(mc - M);
-        wsh[v][rr][c] = w;
-        lws[v][rr][c] = c < n_parts ? base[D + 1] * w : 0.f;
-    }
-    __syncthreads();
-    if (tid < 3 * nrows) {
-        const int v = tid / nrows, rr = tid - v * nrows;
-        float L = 0.f;
-        for (int c = 0; c < n_parts; ++c) L += lws[v][rr][c];
-        lsh[v][rr] = L;
-    }
-    __syncthreads();
-    for (int e = r0 * D + tid; e < r1 * D; e += 256) {
-        const int row = e / D, d = e - row * D;
-        float o[3];
-#pragma unroll
-        for (int v = 0; v < 3; ++v) {
-            const size_t off = (((size_t)v * BH + h) * R + row) * DS + d;
-            const float L = lsh[v][row - r0];
-            float acc = 0.f;
-            for (int c = 0; c < n_parts; ++c) acc += parts.p[c][off] * wsh[v][row - r0][c];
-            // a row whose mask admits no key of any part is NaN in the reference (softmax over all -inf)
-            o[v] = (L > 0.f) ? acc / L : __builtin_nanf("");
-            if (emulate) o[v] = Elt<T>::to_float(Elt<T>::from_float(o[v]));
-        }
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            float diff = o[v + 1] - o[0];
-            if (emulate) {
-                diff = Elt<T>::to_float(Elt<T>::from_float(diff));
-                sq[v] += Elt<T>::to_float(Elt<T>::from_float(diff * diff));
-            } else {
-                sq[v] += diff * diff;
-            }
-            if (diff != diff) bad[v] = 1.f, sq[v] = 0.f;
-        }
-    }
-    float vals[4] = {bad[0] > 0.f ? 0.f : sq[0], bad[1] > 0.f ? 0.f : sq[1], bad[0], bad[1]};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float s = wave_sum(vals[i]);
-        if ((tid & 63) == 0) red[i][tid >> 6] = s;
-    }
-    __syncthreads();
-    if (tid < 4) sq_part[((size_t)h * kProfRowGroups + rg) * 4 + tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
-}
-
 template <typename T, int D>
 static int run_profile_shard(const void* q_rows, const void* k, const void* v, const int64_t* rows, int R, int BH, int S, float sm_scale,
                              const svg_profile_desc_t* pd, const svg_band_shard_t& sh, float* part, void* ws, const int32_t* skip,
@@ -1255,28 +974,9 @@ static int run_profile_shard(const void* q_rows, const void* k, const void* v, c
     p.q_rows = (const T*)q_rows;
     p.q = nullptr, p.k = (const T*)k, p.v = (const T*)v;
     p.lay = lay ? *lay : contiguous_layout(BH, BH, p.Sk, p.Sk, D);
-    p.S = S, p.BH = BH, p.R = R;
-    p.n_chunks = prof_chunks(BH, p.Sk);
-    const int ntiles = (p.Sk + kBN - 1) / kBN;
-    p.tiles_per_chunk = (ntiles + p.n_chunks - 1) / p.n_chunks;
-    p.emulate = pd->emulate_bf16;
-    p.scale_log2 = p.emulate ? 1.4426950408889634f : sm_scale * 1.4426950408889634f;
-    p.fix_scale = sm_scale;
-    p.rows = rows;
-    p.vid0 = 0, p.F = F, p.P = P, p.V = F * P;
-    for (int i = 0; i < 2; ++i) {
-        p.var[i].coord = pd->variant[i].coord;
-        p.var[i].origin = pd->variant[i].origin;
-        p.var[i].span = pd->variant[i].span;
-        p.var[i].band_blocks = pd->variant[i].band_blocks;
-        p.var[i].sink_cols = pd->variant[i].sink_cols;
-        p.var[i].text_lo = pd->variant[i].text_lo;
-        p.var[i].text_hi = pd->variant[i].text_hi;
-    }
-    p.part = (float*)ws;
-    p.skip = skip;
+    prof_fill_params(p, rows, R, BH, S, p.Sk, sm_scale, pd, ws, skip);   // (vid0 is 0 here: the entry point refuses any other)
     constexpr int lds16 = p16_lds_bytes(D);
-    auto kern = profile16_shard_kernel<T, D>;
+    auto kern = profile16_kernel<T, D, ProfileShardPolicy<T, D>>;
     if (const int rc = configure_lds((const void*)kern, lds16); rc != SVG_OK) return rc;
     hipLaunchKernelGGL(kern, dim3(BH, p.n_chunks), dim3(256), lds16, st, p);
     hipLaunchKernelGGL((profile_shard_reduce_kernel<D>), dim3(kProfRowGroups, BH), dim3(256), 0, st, (const float*)ws, part, BH, R, p.n_chunks,

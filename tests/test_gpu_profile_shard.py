@@ -1,5 +1,5 @@
-"""The online profiler on frame shards on the GPU (include/svg_attn_profile_shard.h; csrc/profiler.hip: profile16_shard_kernel,
-profile_shard_reduce_kernel, profile_combine_parts_kernel): one part of the whole sequence against svg_sample_mse bit for bit, the parts of
+"""The online profiler on frame shards on the GPU (include/svg_attn_profile_shard.h; csrc/profiler.hip: profile16_kernel on
+ProfileShardPolicy, profile_shard_reduce_kernel, profile_combine_parts_kernel): one part of the whole sequence against svg_sample_mse bit for bit, the parts of
 frame shards merged against the oracle, shards whose stored index jumps inside a key tile, a sampled text row, a shard no sampled row sees
 under the spatial mask, strided k / v, the skip flag, the poison rows of the two entries and their wrappers, and
 svg.distributed.token_sharded_svg1_layer_call on two ranks sharing the GPU.

@@ -17,13 +17,17 @@ their spreads (max - min), for a partial the GB/s over the shard's K and V (B) a
 tiles per workgroup where the full call has about 88, so the per-workgroup prologue — row ranking, class-table fill, first DMA — weighs more;
 the line says what was found.  The 8 parts merged are compared with the full call's mse (rtol of the tests, not bits: other tiles).
 This is ONE GPU running one rank's launches: no exchange is timed and no multi-GPU run exists.  The shader clock is not recorded.
---parent: one more line, svg_sample_mse of this build (B) against the parent's (A) on the same tensors: its listings are unchanged, so the
-same bits and a difference inside A's own spread are expected; anything else is a finding.
+--parent: both libraries in this process, the parent's always A, on the same tensors.  The shard form first: each of the 8 ranks' parts and
+the merged result of the two libraries compared bit for bit (parts_equal_all_ranks, same_bits, merged_equal), then parent against this build
+for the three partial cases and for from_parts (pairs *_vs_parent).  Last, svg_sample_mse of this build against the parent's
+(plain_vs_parent): its attention listings are unchanged.  Expected everywhere: the same bits, and the median over the alternations of
+(B - A) inside A's own spread; anything else is a finding.
 --tiny: small shapes, two alternations (a rehearsal of the script, not a measurement)."""
 import argparse
 import ctypes as C
 import json
 import math
+import statistics
 import sys
 from pathlib import Path
 
@@ -97,7 +101,7 @@ def partial_call(nat, lib, w, shard):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--parent", default=None, help="libsvgattn.so built from the parent commit (adds the plain_vs_parent line)")
+    ap.add_argument("--parent", default=None, help="libsvgattn.so built from the parent commit (adds the *_vs_parent lines)")
     ap.add_argument("--alternations", type=int, default=7)
     ap.add_argument("--min-ms", type=float, default=500.0)
     ap.add_argument("--out", default=None, help="default: profiles/profiler_shard_ab.jsonl (appended to)")
@@ -171,7 +175,53 @@ def main():
         rec.update(NOTE)
         emit(rec)
         if a.parent:
-            old = typed(nat, a.parent, ["svg_sample_mse", "svg_sample_mse_workspace_bytes"])
+            old = typed(nat, a.parent, ["svg_sample_mse", "svg_sample_mse_workspace_bytes", "svg_sample_mse_shard_partial",
+                                        "svg_sample_mse_shard_workspace_bytes", "svg_sample_mse_from_parts",
+                                        "svg_sample_mse_from_parts_workspace_bytes"])
+
+            def parent_line(pair, what, fo, fn, extra):
+                wa, wb, calls = alternate(fo, fn, alternations, min_ms)
+                rec = {"pair": pair, "a": f"parent: {what}", "b": f"this build: {what}"}
+                rec.update(w.cfg)
+                rec.update({"alternations": alternations, "repetitions_per_window": calls})
+                rec.update(stats(wa, wb))
+                med = statistics.median(y - x for x, y in zip(wa, wb))
+                rec.update({"b_over_a": round(rec["b_ms"] / rec["a_ms"], 4), "median_diff_ms": round(med, 6),
+                            "a_spread_unrounded_ms": round(max(wa) - min(wa), 6),
+                            "median_diff_inside_a_spread": bool(abs(med) <= max(wa) - min(wa))})
+                rec.update(extra)
+                rec["shader_clock"] = "not recorded"
+                emit(rec)
+
+            # the shard form: every rank's part and the merged result of the two libraries bit for bit, then parent against this build
+            parts_old, equal = {}, []
+            for r in range(WORLD):
+                run, parts_old[r], keep = partial_call(nat, old, w, sh[r])
+                run()
+                torch.cuda.synchronize()
+                equal.append(bool(torch.equal(parts_old[r].view(torch.int32), parts[r].view(torch.int32))))
+                del keep
+            for rank, label in ((0, "first_rank"), (WORLD // 2 - 1, "middle_rank"), (WORLD - 1, "last_rank")):
+                fo, part_o, keep_o = partial_call(nat, old, w, sh[rank])
+                fn, part_n, keep_n = partial_call(nat, new, w, sh[rank])
+                fo()
+                fn()
+                torch.cuda.synchronize()
+                parent_line(f"{label}_vs_parent", f"svg_sample_mse_shard_partial, the shard of rank {rank}", fo, fn,
+                            {"rank": rank, "rows": rows[rank], "parts_equal_all_ranks": equal,
+                             "same_bits": bool(torch.equal(part_o.view(torch.int32), part_n.view(torch.int32)))})
+                del keep_o, keep_n
+            mse_o = torch.empty(2, w.H, dtype=torch.float32, device="cuda")
+            ws_o = torch.empty(old.svg_sample_mse_from_parts_workspace_bytes(w.H), dtype=torch.uint8, device="cuda")
+            pp_o = (C.c_void_p * WORLD)(*[parts_old[r].data_ptr() for r in range(WORLD)])
+            fco = checked(old.svg_sample_mse_from_parts, (C.cast(pp_o, C.c_void_p), WORLD, w.R, w.H, w.D, 0, 0, mse_o.data_ptr(), ws_o.data_ptr(),
+                                                          ws_o.numel(), None, torch.cuda.current_stream().cuda_stream),
+                          "parent svg_sample_mse_from_parts")
+            fco()
+            fc()
+            torch.cuda.synchronize()
+            parent_line("from_parts_vs_parent", f"svg_sample_mse_from_parts over {WORLD} parts", fco, fc,
+                        {"parts_equal_all_ranks": equal, "merged_equal": bool(torch.equal(mse_o.view(torch.int32), mse.view(torch.int32)))})
             mse_old = torch.empty(2, w.H, dtype=torch.float32, device="cuda")
             fo, keep_o = full_call(old, w, mse_old)
             fo()
@@ -184,8 +234,11 @@ def main():
             rec.update({"alternations": alternations, "repetitions_per_window": calls})
             rec.update(stats(wa, wb))
             diff = rec["b_ms"] - rec["a_ms"]
+            med = statistics.median(y - x for x, y in zip(wa, wb))
             rec.update({"b_over_a": round(rec["b_ms"] / rec["a_ms"], 4), "diff_ms": round(diff, 4),
-                        "inside_a_spread": bool(abs(diff) <= rec["a_spread_ms"]), "same_bits": same, "shader_clock": "not recorded"})
+                        "inside_a_spread": bool(abs(diff) <= rec["a_spread_ms"]), "median_diff_ms": round(med, 6),
+                        "a_spread_unrounded_ms": round(max(wa) - min(wa), 6),
+                        "median_diff_inside_a_spread": bool(abs(med) <= max(wa) - min(wa)), "same_bits": same, "shader_clock": "not recorded"})
             emit(rec)
 
 
