@@ -795,6 +795,8 @@ int svg_debug_wg_trace(uint64_t* out, int32_t n_workgroups);
 #include "svg_attn_band_shard.h"
 /* ... and the device switch between two masks of that shard form (the sparse and the dense warm-up steps of a processor), likewise */
 #include "svg_attn_band_shard_switch.h"
+/* ... and the pack / unpack layouts of the token-shard exchanges as one batched strided copy, likewise */
+#include "svg_attn_shard_exchange.h"
 /* ... and the online profiler on frame shards: a partial per key shard and the combine over the partials, likewise */
 #include "svg_attn_profile_shard.h"
 #endif /* SVG_ATTN_H_ */

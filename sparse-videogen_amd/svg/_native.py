@@ -329,6 +329,27 @@ PROFILE_SHARD_SIGNATURES = {
 }
 
 
+class CopyBox(C.Structure):
+    """svg_copy_box_t (include/svg_attn_shard_exchange.h): extent[0] * extent[1] * extent[2] rows of D contiguous elements; offsets and
+    strides in elements"""
+
+    _fields_ = [("src_offset", C.c_int64), ("dst_offset", C.c_int64), ("extent", C.c_int32 * 3), ("reserved", C.c_int32),
+                ("src_stride", C.c_int64 * 3), ("dst_stride", C.c_int64 * 3)]
+
+
+class CopyTensor(C.Structure):
+    """svg_copy_tensor_t: the two base pointers of one tensor of a launch and the boxes [box_begin, box_begin + box_count) it copies"""
+
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("box_begin", C.c_int32), ("box_count", C.c_int32)]
+
+
+# include/svg_attn_shard_exchange.h: the pack / unpack layouts of the token-shard exchanges as one batched strided copy, in a table of its
+# own for the same reason (tests/test_token_shards_cpu.py)
+SHARD_EXCHANGE_SIGNATURES = {
+    "svg_copy_boxes": (C.c_int, [C.POINTER(CopyTensor), _I32, C.POINTER(CopyBox), _I32, _I32, _I32, _VP]),
+}
+
+
 def lib_path() -> Path:
     return Path(os.environ.get("SVG_ATTN_LIB", str(_LIB_PATH)))
 
@@ -343,7 +364,7 @@ def load(strict: bool = True) -> Optional[C.CDLL]:
         lib = C.CDLL(str(p))
         for name, (res, args) in {**SIGNATURES, **SPARSE_LSE_SIGNATURES, **SPARSE_F32_SIGNATURES, **BAND_LSE_FORM_SIGNATURES,
                                    **BAND_WINDOW_SIGNATURES, **BAND_SHARD_SIGNATURES, **BAND_SHARD_SWITCH_SIGNATURES,
-                                   **PROFILE_SHARD_SIGNATURES}.items():
+                                   **PROFILE_SHARD_SIGNATURES, **SHARD_EXCHANGE_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -2270,3 +2291,162 @@ def bsr_to_block_map(indptr: torch.Tensor, indices: torch.Tensor, MB: int, NB: i
     _check(lib.svg_bsr_to_block_map(indptr.data_ptr(), indices.data_ptr(), MB, NB, row_block, col_block, len_text, heads,
                                     bm.data_ptr(), qs.data_ptr(), ks.data_ptr(), _stream()), "svg_bsr_to_block_map")
     return bm, qs, ks
+
+
+# ------------------------------------------------------------------------------------------------------
+# svg_copy_boxes (include/svg_attn_shard_exchange.h): the pack / unpack layouts either side of the two all-to-all exchanges of a
+# token-sharded layer-call (svg/distributed.py run_token_sharded).  One builder per layout returns its boxes from (cfg, head counts, row
+# ranges, strides); copy_boxes runs them as one launch, copy_boxes_torch is the torch statement of the same copies — what CPU tensors take
+# and what the GPU test compares the kernel with.
+# ------------------------------------------------------------------------------------------------------
+COPY_MAX_TENSORS, COPY_MAX_BOXES = 3, 16
+
+
+class Box(NamedTuple):
+    """one svg_copy_box_t: rows of D contiguous elements, offsets and strides in elements from the tensors' first elements"""
+    src_offset: int
+    dst_offset: int
+    extent: tuple        # (n0, n1, n2): the kernel's tiles run along n2 — the rows of a shard
+    src_stride: tuple
+    dst_stride: tuple
+
+
+def inbound_pack_boxes(cfg: int, head_counts: Sequence[int], n_rows: int, D: int, strides: Sequence[int]):
+    """Before the inbound exchange: x [cfg, H, S_r, D] with element strides `strides` = (video, head, row) -> the send buffer, one block
+    [cfg, H_j, S_r, D] per destination rank j, in rank order."""
+    boxes, h0, off = [], 0, 0
+    for hj in head_counts:
+        boxes.append(Box(h0 * strides[1], off, (cfg, hj, n_rows), tuple(strides), (hj * n_rows * D, n_rows * D, D)))
+        h0, off = h0 + hj, off + cfg * hj * n_rows * D
+    return boxes
+
+
+def inbound_unpack_boxes(cfg: int, n_heads_local: int, row_ranges: Sequence[Sequence[int]], D: int):
+    """Behind the inbound exchange: the receive buffer, one block [cfg, H_l, S_i, D] per source rank i -> contiguous [cfg, H_l, S, D], the
+    rows of rank i at row_ranges[i] = (a_i, b_i)."""
+    S = row_ranges[-1][1]
+    boxes, off = [], 0
+    for a, b in row_ranges:
+        n = b - a
+        boxes.append(Box(off, a * D, (cfg, n_heads_local, n), (n_heads_local * n * D, n * D, D), (n_heads_local * S * D, S * D, D)))
+        off += cfg * n_heads_local * n * D
+    return boxes
+
+
+def outbound_pack_boxes(cfg: int, n_heads_local: int, row_ranges: Sequence[Sequence[int]], D: int, strides: Sequence[int]):
+    """Before the outbound exchange: o [cfg, H_l, S, D] with element strides `strides` = (video, head, row) — head-major or token-major
+    storage — -> the send buffer, one token-major block [cfg, S_j, H_l, D] per destination rank j."""
+    boxes, off = [], 0
+    for a, b in row_ranges:
+        n = b - a
+        boxes.append(Box(a * strides[2], off, (cfg, n_heads_local, n), tuple(strides), (n * n_heads_local * D, D, n_heads_local * D)))
+        off += cfg * n * n_heads_local * D
+    return boxes
+
+
+def outbound_unpack_boxes(cfg: int, head_counts: Sequence[int], n_rows: int, D: int):
+    """Behind the outbound exchange: the receive buffer, one block [cfg, S_r, H_i, D] per source rank i -> the storage [cfg, S_r, H, D]
+    (the heads of rank i interleaved at their place of every row)."""
+    H = sum(head_counts)
+    boxes, h0, off = [], 0, 0
+    for hi in head_counts:
+        boxes.append(Box(off, h0 * D, (cfg, hi, n_rows), (n_rows * hi * D, D, hi * D), (n_rows * H * D, D, H * D)))
+        h0, off = h0 + hi, off + cfg * n_rows * hi * D
+    return boxes
+
+
+def _elements_behind(t: torch.Tensor) -> int:
+    return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+
+
+def _check_boxes(src: torch.Tensor, dst: torch.Tensor, boxes: Sequence[Box], D: int) -> None:
+    """every row of every box inside the two allocations (ValueError before anything runs: the kernel itself cannot know)"""
+    if src.dtype != dst.dtype or src.device != dst.device:
+        raise ValueError(f"copy_boxes: source {src.dtype} on {src.device}, destination {dst.dtype} on {dst.device}")
+    for b in boxes:
+        if min(b.extent) < 0 or min(b.src_stride) < 0 or min(b.dst_stride) < 0 or b.src_offset < 0 or b.dst_offset < 0:
+            raise ValueError(f"copy_boxes: negative member in {b}")
+        if min(b.extent) == 0:
+            continue
+        for t, off, st, side in ((src, b.src_offset, b.src_stride, "source"), (dst, b.dst_offset, b.dst_stride, "destination")):
+            last = off + sum((n - 1) * s for n, s in zip(b.extent, st)) + D
+            if last > _elements_behind(t):
+                raise ValueError(f"copy_boxes: {b} ends {last} elements behind the {side}'s first, which has {_elements_behind(t)}")
+
+
+def copy_boxes_torch(pairs, boxes: Sequence[Box], D: int, ranges=None) -> None:
+    """The torch statement of copy_boxes: one strided copy_ per tensor and box."""
+    for i, (src, dst) in enumerate(pairs):
+        b0, nb = ranges[i] if ranges is not None else (0, len(boxes))
+        _check_boxes(src, dst, boxes[b0:b0 + nb], D)
+        for b in boxes[b0:b0 + nb]:
+            if min(b.extent) == 0:
+                continue
+            d = torch.as_strided(dst, tuple(b.extent) + (D,), tuple(b.dst_stride) + (1,), dst.storage_offset() + b.dst_offset)
+            d.copy_(torch.as_strided(src, tuple(b.extent) + (D,), tuple(b.src_stride) + (1,), src.storage_offset() + b.src_offset))
+
+
+def copy_boxes(pairs, boxes: Sequence[Box], D: int, ranges=None) -> None:
+    """svg_copy_boxes: pairs = up to COPY_MAX_TENSORS (src, dst) tensors (any shape: the boxes address elements behind each tensor's first),
+    boxes = up to COPY_MAX_BOXES Box; ranges[i] = (first box, count) of pair i (default: every pair copies every box).  ONE launch.  CPU
+    tensors take copy_boxes_torch."""
+    pairs = list(pairs)
+    if not pairs[0][0].is_cuda:
+        return copy_boxes_torch(pairs, boxes, D, ranges)
+    lib = load()
+    for i, (src, dst) in enumerate(pairs):
+        _gpu(src, dst)
+        b0, nb = ranges[i] if ranges is not None else (0, len(boxes))
+        _check_boxes(src, dst, boxes[b0:b0 + nb], D)
+    ts = (CopyTensor * len(pairs))()
+    for i, (src, dst) in enumerate(pairs):
+        b0, nb = ranges[i] if ranges is not None else (0, len(boxes))
+        ts[i] = CopyTensor(src.data_ptr(), dst.data_ptr(), b0, nb)
+    bs = (CopyBox * len(boxes))()
+    for i, b in enumerate(boxes):
+        bs[i] = CopyBox(b.src_offset, b.dst_offset, (C.c_int32 * 3)(*b.extent), 0, (C.c_int64 * 3)(*b.src_stride), (C.c_int64 * 3)(*b.dst_stride))
+    _check(lib.svg_copy_boxes(ts, len(pairs), bs, len(boxes), D, _dtype_code(pairs[0][0]), _stream()), "svg_copy_boxes")
+
+
+# The layouts that run through svg_copy_boxes on the GPU; one that is not listed takes the torch copies (tools/ab_token_shards.py compares
+# the two, profiles/token_shards_ab.jsonl holds what it found).
+COPY_BOX_LAYOUTS = {"inbound_pack", "inbound_unpack", "outbound_pack", "outbound_unpack"}
+
+
+def copy_box_jobs(jobs, D: int, layout: str) -> int:
+    """jobs = [(src, dst, boxes)]: the copies of one step of a layer-call, in as few launches as COPY_MAX_TENSORS and COPY_MAX_BOXES allow —
+    one where the world has at most COPY_MAX_BOXES ranks (tensors with equal boxes share them; a tensor with strides of its own, a v that
+    is a view of a fused projection, brings its own).  -> launches (the torch statement: copies).  A tensor without elements is skipped."""
+    jobs = [(s, d, list(b)) for s, d, b in jobs if s.numel() and d.numel() and any(min(x.extent) > 0 for x in b)]
+    if not jobs:
+        return 0
+    native = jobs[0][0].is_cuda and layout in COPY_BOX_LAYOUTS
+    if not native:
+        for s, d, b in jobs:
+            copy_boxes_torch([(s, d)], b, D)
+        return sum(len(b) for _, _, b in jobs)
+    # a tensor with more boxes than one launch takes is several jobs; the first COPY_MAX_BOXES boxes of every tensor first, so that tensors
+    # with equal boxes still share them
+    most = max(len(b) for _, _, b in jobs)
+    chunks = [(s, d, b[i:i + COPY_MAX_BOXES]) for i in range(0, most, COPY_MAX_BOXES) for s, d, b in jobs if b[i:i + COPY_MAX_BOXES]]
+    launches, pairs, boxes, ranges = 0, [], [], []
+
+    def flush():
+        nonlocal launches, pairs, boxes, ranges
+        if pairs:
+            copy_boxes(pairs, boxes, D, ranges)
+            launches += 1
+        pairs, boxes, ranges = [], [], []
+
+    for s, d, b in chunks:
+        at = next((r for r in ranges if boxes[r[0]:r[0] + r[1]] == b), None)
+        if len(pairs) == COPY_MAX_TENSORS or (at is None and len(boxes) + len(b) > COPY_MAX_BOXES):
+            flush()
+            at = None
+        if at is None:
+            at = (len(boxes), len(b))
+            boxes += b
+        pairs.append((s, d))
+        ranges.append(at)
+    flush()
+    return launches

@@ -21,6 +21,11 @@ its own shard into one partial (svg_sample_mse_shard_partial), the partials are 
 carry the processors' device switch between the sparse and the dense warm-up mask (dense_mask / dense_flag:
 svg_band_shard_attention_switch_lse[_f32]), and `enable_frame_shards` is the mode in which the SVG1 processors of HunyuanVideo and Wan run
 them (svg/models/_core.py).
+
+`enable_token_shards` is the third mode and the one every processor has: activations sharded by rows, `run_token_sharded` exchanges rows for
+whole heads in front of the attention core (one all_to_all_single per tensor), runs the single-GPU core on this rank's heads of the whole
+sequence and exchanges back — bit for bit the single-GPU result; the layouts either side of the exchanges are one svg_copy_boxes launch
+each (_native.copy_box_jobs).
 """
 from __future__ import annotations
 
@@ -35,7 +40,8 @@ from . import _native
 # opt-in switch for the processors (svg/models/_core.py): svg.distributed.enable(group) makes every SVG1 / SVG2 layer-call run
 # this rank's heads only and all-gather the result; nothing changes for a process that never calls it.
 # ---------------------------------------------------------------------------------------------------------------
-_STATE: Dict[str, object] = {"enabled": False, "group": None, "frames": False, "frames_group": None}
+_STATE: Dict[str, object] = {"enabled": False, "group": None, "frames": False, "frames_group": None,
+                             "tokens": False, "tokens_group": None, "tokens_unit": 128, "tokens_counts": None}
 
 
 def enable(group=None) -> None:
@@ -46,7 +52,77 @@ def enable(group=None) -> None:
     assert dist.is_available() and dist.is_initialized(), "svg.distributed.enable: call torch.distributed.init_process_group first"
     if _STATE["frames"]:
         raise RuntimeError("svg.distributed.enable: frame-shard mode (enable_frame_shards) is on; disable() it first — one mode at a time")
+    if _STATE["tokens"]:
+        raise RuntimeError("svg.distributed.enable: token-shard mode (enable_token_shards) is on; disable() it first — one mode at a time")
     _STATE["enabled"], _STATE["group"] = True, group
+
+
+def enable_token_shards(group=None, unit: int = 128, row_counts: Optional[Sequence[int]] = None) -> None:
+    """The third mode: the processors receive q, k, v of ALL heads of this rank's ROWS — `token_range(seq_len, rank, world, unit)` of the
+    model's own row order, or with `row_counts` (world ints that sum to the sequence length) the contiguous ranges those counts give, so that
+    a caller who shards by `frame_shard` switches modes without re-sharding — and every self-attention layer-call runs through
+    run_token_sharded over the ranks of `group`: one all-to-all to whole heads of the whole sequence, the single-GPU core on this rank's
+    heads, one all-to-all back.  Nothing needs frames kept together (CogVideoX's text in front of the video is just rows, HunyuanVideo's
+    text falls on the last ranks), so it covers what the single-GPU core covers — SVG1 and SVG2, all four model families, bf16 / fp16,
+    head_dim 64 / 128, fp8, a pre-scaled q — and the result is the single-GPU one bit for bit.  The rotary tables are the caller's: its own
+    rows of them (token_shard_range).  Cross attention stays local.  enable and enable_frame_shards must be off."""
+    assert dist.is_available() and dist.is_initialized(), "svg.distributed.enable_token_shards: call torch.distributed.init_process_group first"
+    if _STATE["enabled"] or _STATE["frames"]:
+        raise RuntimeError(f"svg.distributed.enable_token_shards: {'head sharding (enable)' if _STATE['enabled'] else 'frame-shard mode'} is on; "
+                           f"disable() it first — one mode at a time")
+    if int(unit) < 1:
+        raise ValueError(f"svg.distributed.enable_token_shards: unit must be positive, got {unit}")
+    if row_counts is not None:
+        row_counts = tuple(int(x) for x in row_counts)
+        if len(row_counts) != dist.get_world_size(group) or min(row_counts) < 0:
+            raise ValueError(f"svg.distributed.enable_token_shards: row_counts {row_counts} for a group of {dist.get_world_size(group)} ranks")
+    _STATE["tokens"], _STATE["tokens_group"], _STATE["tokens_unit"], _STATE["tokens_counts"] = True, group, int(unit), row_counts
+
+
+def token_shards_active() -> bool:
+    """token-shard mode is on (whatever the group's size: a group of one rank holds the whole sequence and runs the same calls)"""
+    return bool(_STATE["tokens"]) and dist.is_initialized()
+
+
+def token_shards_group():
+    return _STATE["tokens_group"]
+
+
+def token_shard_row_counts() -> Optional[Tuple[int, ...]]:
+    """the row_counts token-shard mode was enabled with, or None (rows by token_range)"""
+    return _STATE["tokens_counts"]
+
+
+def token_shard_ranges(seq_len: int) -> List[Tuple[int, int]]:
+    """[a, b) of every rank's rows of a sequence of seq_len rows in token-shard mode; the same list on every rank"""
+    world = dist.get_world_size(_STATE["tokens_group"])
+    counts = _STATE["tokens_counts"]
+    if counts is None:
+        return [token_range(int(seq_len), r, world, int(_STATE["tokens_unit"])) for r in range(world)]
+    if sum(counts) != int(seq_len):
+        raise ValueError(f"svg.distributed: row_counts {counts} add up to {sum(counts)}, the sequence has {seq_len} rows")
+    out, a = [], 0
+    for n in counts:
+        out.append((a, a + n))
+        a += n
+    return out
+
+
+def token_shard_range(seq_len: int, rank: Optional[int] = None) -> Tuple[int, int]:
+    """[a, b): the rows of a sequence of seq_len rows that `rank` (default: this rank) holds in token-shard mode — what a caller slices its
+    hidden states and its rotary tables with"""
+    rank = dist.get_rank(_STATE["tokens_group"]) if rank is None else int(rank)
+    return token_shard_ranges(seq_len)[rank]
+
+
+def head_mode():
+    """(on, group) of the mode in which a rank computes whole HEADS — enable() with more than one rank, or token-shard mode: the modes in
+    which the k-means stopping rule is reduced, the switch generator's seed is broadcast and the density log is gathered"""
+    if active():
+        return True, _STATE["group"]
+    if token_shards_active():
+        return True, _STATE["tokens_group"]
+    return False, None
 
 
 def enable_frame_shards(group=None) -> None:
@@ -58,13 +134,17 @@ def enable_frame_shards(group=None) -> None:
     assert dist.is_available() and dist.is_initialized(), "svg.distributed.enable_frame_shards: call torch.distributed.init_process_group first"
     if _STATE["enabled"]:
         raise RuntimeError("svg.distributed.enable_frame_shards: head sharding (enable) is on; disable() it first — one mode at a time")
+    if _STATE["tokens"]:
+        raise RuntimeError("svg.distributed.enable_frame_shards: token-shard mode (enable_token_shards) is on; disable() it first — one mode "
+                           "at a time")
     _STATE["frames"], _STATE["frames_group"] = True, group
 
 
 def disable() -> None:
-    """both modes off"""
+    """all three modes off"""
     _STATE["enabled"], _STATE["group"] = False, None
     _STATE["frames"], _STATE["frames_group"] = False, None
+    _STATE["tokens"], _STATE["tokens_group"], _STATE["tokens_unit"], _STATE["tokens_counts"] = False, None, 128, None
 
 
 def frame_shards_active() -> bool:
@@ -87,8 +167,9 @@ def current_group():
 def all_reduce_max_(t: torch.Tensor) -> torch.Tensor:
     """in-place MAX over the ranks of the enabled group (identity when sharding is off) — the k-means stopping rule's
     `center_shift` is a maximum over ALL heads (ref: svg/kmeans_utils.py:721-723)"""
-    if active():
-        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=_STATE["group"])
+    on, group = head_mode()   # (token-shard mode: its ranks hold whole heads inside run_token_sharded, as those of enable())
+    if on:
+        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
     return t
 
 
@@ -141,6 +222,131 @@ def all_gather_heads(o_local: torch.Tensor, num_heads: int, group=None) -> torch
     dist.all_gather_into_tensor(out, pad, group=group)
     out = out.view(world, cfg, mx, S, D)
     return torch.cat([out[r, :, : counts[r]] for r in range(world)], dim=1)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# token-shard mode (enable_token_shards): activations sharded by rows, one all-to-all to head shards in front of the attention core and
+# one back behind it — the shape of the reference's context-parallel code (svg/models/wan_orig/distributed/xdit_context_parallel.py:120-169)
+# ---------------------------------------------------------------------------------------------------------------
+EXCHANGE_STATS: Dict[str, int] = {}   # of the last run_token_sharded on this rank: elements received from OTHER ranks, layout launches
+
+
+def _all_to_all(recv: torch.Tensor, send: torch.Tensor, out_splits: List[int], in_splits: List[int], group) -> int:
+    """one all_to_all_single of flat buffers; on a backend that cannot exchange device tensors (gloo) staged through host memory.
+    -> elements received from other ranks"""
+    if send.is_cuda and dist.get_backend(group) == "gloo":
+        host = _native.empty(recv.numel(), dtype=recv.dtype, device="cpu")
+        dist.all_to_all_single(host, send.cpu(), output_split_sizes=out_splits, input_split_sizes=in_splits, group=group)
+        recv.copy_(host)
+    else:
+        dist.all_to_all_single(recv, send, output_split_sizes=out_splits, input_split_sizes=in_splits, group=group)
+    return sum(out_splits) - out_splits[dist.get_rank(group)]
+
+
+def _boxable(t: torch.Tensor) -> bool:
+    """can the copy kernel address this [cfg, H, S, D] view in place?  (unit stride on D, every other stride and the base 16-byte aligned)"""
+    return t.stride(3) == 1 and all(s % 8 == 0 for s in t.stride()[:3]) and t.data_ptr() % 16 == 0
+
+
+def run_token_sharded(fn: Callable[..., Tuple[torch.Tensor, ...]], head_tensors: Sequence[torch.Tensor], seq_len: int, group=None,
+                      ranges: Optional[Sequence[Tuple[int, int]]] = None):
+    """The counterpart of run_sharded for activations that live sharded by ROWS.  head_tensors (q, k, v) are [cfg, H, S_r, D] — all heads
+    of this rank's rows `ranges[rank]` (default: token_shard_ranges(seq_len), the rows of token-shard mode), unit stride on D only: v may be
+    the head view of to_v's output.
+    Inbound: each becomes [cfg, H_l, S, D] with the heads shard_heads(H, rank, world) — ONE all_to_all_single per tensor (send block for
+    destination j [cfg, H_j, S_r, D], receive block from source i [cfg, H_l, S_i, D]).  Core: fn(q_h, k_h, v_h) on the head shard -> o
+    [cfg, H_l, S, D], or a tuple whose further members are per-head tensors (best_mask_idx [cfg, H_l]) that are all-gathered as by
+    run_sharded.  Outbound: o becomes [cfg, H, S_r, D]: send block for destination j [cfg, S_j, H_l, D] — when fn returns o stored
+    token-major ([cfg, S, H_l, D]: token_major_out of the _native wrappers) and cfg == 1, every send block is a contiguous row slice and
+    nothing is packed — the received [cfg, S_r, H_i, D] blocks are interleaved into [cfg, S_r, H, D] and the result is the
+    [cfg, H, S_r, D] VIEW of that storage, so a processor's `.transpose(1, 2).flatten(2, 3)` stays a view.
+    The layouts either side of the exchanges are _native.copy_box_jobs: one svg_copy_boxes launch per step on the GPU (inbound unpack of
+    q, k, v: one; inbound pack, only for a send buffer that is not contiguous already — cfg > 1, v as a head view: one; outbound unpack:
+    one; outbound pack, only without token-major storage or with cfg > 1: one), the torch statement of the same boxes on CPU tensors.
+    Ragged head counts and ragged row counts are allowed.  A world in which some rank owns no head raises ValueError on every rank before
+    any collective; every rank enters every collective.
+    gloo cannot all_to_all device tensors: there (the tests: ranks that share one GPU) each exchange is staged through host memory, as
+    bench_step.py's host_staged does.  RCCL exchanges the device buffers directly.  No exchange was ever timed: no multi-GPU run exists."""
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    ts = list(head_tensors)
+    cfg, H, S_r, D = ts[0].shape
+    counts = head_counts(H, world)
+    if min(counts) == 0:
+        raise ValueError(f"svg.distributed: {world} ranks but {H} heads — some rank owns no head; token-shard mode needs num_heads >= world "
+                         f"size (use a smaller process group for this model)")
+    if ranges is None:
+        ranges = token_shard_ranges(seq_len) if _STATE["tokens"] else [token_range(int(seq_len), r, world, 128) for r in range(world)]
+    ranges = [(int(a), int(b)) for a, b in ranges]
+    S = int(seq_len)
+    if len(ranges) != world or ranges[0][0] != 0 or ranges[-1][1] != S or any(ranges[i][1] != ranges[i + 1][0] for i in range(world - 1)):
+        raise ValueError(f"svg.distributed.run_token_sharded: row ranges {ranges} do not tile the {S} rows over {world} ranks")
+    if any(tuple(t.shape) != (cfg, H, ranges[rank][1] - ranges[rank][0], D) for t in ts):
+        raise ValueError(f"svg.distributed.run_token_sharded: rank {rank} holds rows {ranges[rank]} of {H} heads, got "
+                         f"{[tuple(t.shape) for t in ts]}")
+    H_l = counts[rank]
+    n_rows = [b - a for a, b in ranges]
+    dev, stats = ts[0].device, {"received_elements": 0, "launches": 0}
+    kernel_ok = ts[0].is_cuda and D in (64, 128) and ts[0].dtype in (torch.bfloat16, torch.float16)
+    how = lambda layout: layout if kernel_ok else "torch"   # noqa: E731  (what the kernel does not take: the torch copies)
+
+    # ---- inbound: [cfg, H, S_r, D] -> [cfg, H_l, S, D]
+    sends, jobs = [], []
+    for t in ts:
+        if not _boxable(t):
+            t = t.contiguous()
+        if cfg == 1 and t.is_contiguous():
+            sends.append(t.reshape(-1))   # (a view: the blocks [H_j, S_r, D] lie behind one another already)
+            continue
+        send = _native.empty(cfg * H * S_r * D, dtype=t.dtype, device=dev)
+        jobs.append((t, send, _native.inbound_pack_boxes(cfg, counts, S_r, D, t.stride()[:3])))
+        sends.append(send)
+    stats["launches"] += _native.copy_box_jobs(jobs, D, how("inbound_pack"))
+    recvs = []
+    for send in sends:
+        recv = _native.empty(cfg * H_l * S * D, dtype=send.dtype, device=dev)
+        stats["received_elements"] += _all_to_all(recv, send, [cfg * H_l * n * D for n in n_rows], [cfg * c * S_r * D for c in counts], group)
+        recvs.append(recv)
+    if world == 1:
+        heads = [r.view(cfg, H_l, S, D) for r in recvs]
+    else:
+        heads = [_native.empty((cfg, H_l, S, D), dtype=r.dtype, device=dev) for r in recvs]
+        boxes = _native.inbound_unpack_boxes(cfg, H_l, ranges, D)
+        stats["launches"] += _native.copy_box_jobs([(r, x, boxes) for r, x in zip(recvs, heads)], D, how("inbound_unpack"))
+
+    # ---- the core, on whole heads of the whole sequence
+    res = fn(*heads)
+    single = not isinstance(res, (tuple, list))
+    res = [res] if single else list(res)
+    o = res[0]
+    if tuple(o.shape) != (cfg, H_l, S, D):
+        raise ValueError(f"svg.distributed.run_token_sharded: fn returned {tuple(o.shape)}, expected {(cfg, H_l, S, D)}")
+
+    # ---- outbound: [cfg, H_l, S, D] -> [cfg, H, S_r, D], stored [cfg, S_r, H, D]
+    if not _boxable(o):
+        o = o.contiguous()
+    if cfg == 1 and o.permute(0, 2, 1, 3).is_contiguous():
+        send = o.permute(0, 2, 1, 3).reshape(-1)   # (token-major storage: the blocks [S_j, H_l, D] are row slices of it)
+    else:
+        send = _native.empty(cfg * H_l * S * D, dtype=o.dtype, device=dev)
+        stats["launches"] += _native.copy_box_jobs([(o, send, _native.outbound_pack_boxes(cfg, H_l, ranges, D, o.stride()[:3]))], D,
+                                                   how("outbound_pack"))
+    recv = _native.empty(cfg * S_r * H * D, dtype=o.dtype, device=dev)
+    stats["received_elements"] += _all_to_all(recv, send, [cfg * S_r * c * D for c in counts], [cfg * n * H_l * D for n in n_rows], group)
+    if world == 1:
+        store = recv.view(cfg, S_r, H, D)
+    else:
+        store = _native.empty((cfg, S_r, H, D), dtype=o.dtype, device=dev)
+        stats["launches"] += _native.copy_box_jobs([(recv, store, _native.outbound_unpack_boxes(cfg, counts, S_r, D))], D,
+                                                   how("outbound_unpack"))
+    outs = [store.permute(0, 2, 1, 3)]
+    for r in res[1:]:   # per-head extras: gathered to all heads, as run_sharded does
+        extra = r.shape[2:]
+        r4 = r.reshape(r.shape[0], r.shape[1], -1, 1) if r.dim() != 4 else r
+        g = all_gather_heads(r4, H, group)
+        outs.append(g.reshape(g.shape[0], H, *extra))
+    EXCHANGE_STATS.clear()
+    EXCHANGE_STATS.update(stats)
+    return outs[0] if single else tuple(outs)
 
 
 def sharded_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_fn: Callable[..., torch.Tensor],

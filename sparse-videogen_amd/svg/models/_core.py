@@ -121,6 +121,9 @@ def per_video(x, cfg: int, what: str):
 
 
 def _no_sharding_of_groups(what: str) -> None:
+    if _dist.token_shards_active():
+        raise NotImplementedError(f"{what}: token-shard mode (svg.distributed.enable_token_shards) with per-video masks or lengths that differ "
+                                  f"is not implemented; give every video the same length")
     if _dist.active():
         raise NotImplementedError(f"{what}: head sharding (svg.distributed) with per-video lengths that differ is not implemented; "
                                   f"run the batch on one GPU or give every video the same length")
@@ -153,8 +156,8 @@ def _state_kw(what: str, return_lse: bool, out_dtype, q_prescaled: bool, token_m
     if q_prescaled or fp8 or not fused:
         raise ValueError(f"{what}(return_lse=True): the fused 16-bit path with a plain q; got q_prescaled = {q_prescaled}, fp8 = {fp8}, "
                          f"fused = {fused}")
-    if _dist.active():
-        raise NotImplementedError(f"{what}(return_lse=True): head sharding (svg.distributed) gathers o only")
+    if _dist.active() or _dist.token_shards_active():
+        raise NotImplementedError(f"{what}(return_lse=True): head sharding and token-shard mode (svg.distributed) exchange o only")
     return dict(return_lse=True, out_dtype=out_dtype, token_major_out=token_major_out and out_dtype is None)
 
 
@@ -169,7 +172,11 @@ FRAME_SHARD_MAX_SAMPLED_ROWS = 64   # svg_sample_mse_shard_partial (include/svg_
 
 def rows_of_this_rank(what: str, geo: Geometry, shard_form: bool = True) -> int:
     """The rows an attention_core_logic receives: geo.seq_len — or, in frame-shard mode, the rows of this rank's frame_shard of the
-    sequence.  shard_form False (the SVG2 processors, CogVideoX, Cosmos): frame-shard mode is refused."""
+    sequence.  shard_form False (the SVG2 processors, CogVideoX, Cosmos): frame-shard mode is refused.  In token-shard mode
+    (svg.distributed.enable_token_shards): the rows of token_shard_range(geo.seq_len), for every processor."""
+    if _dist.token_shards_active():
+        a, b = _dist.token_shard_range(geo.seq_len)
+        return b - a
     if not _dist.frame_shards_active():
         return geo.seq_len
     if not shard_form:
@@ -248,7 +255,7 @@ def _frame_shard_svg1(what: str, q, k, v, geo: Geometry, mask, dense_mask, prof,
 
 @time_logging_decorator("Level 3 - Dense Flash Attention")
 def dense_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, valid_len=None, q_prescaled: bool = False, return_lse: bool = False,
-                    out_dtype=None, geometry: Optional[Geometry] = None):
+                    out_dtype=None, geometry: Optional[Geometry] = None, _local: bool = False):
     """Dense attention [cfg, H, S, D].  valid_len < S: two independent segments [0, valid) and [valid, S) — what the
     reference gets from flash_attn_varlen_func with cu_seqlens [0, valid, S] (hyvideo/attention.py:452-470).
     valid_len: one int for the batch, or a sequence of cfg ints, one per video (see video_groups).
@@ -257,7 +264,24 @@ def dense_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, valid_len
     head_dim 128, plain q (ValueError), not under svg.distributed (NotImplementedError).
     geometry: the Geometry of the WHOLE sequence — required in frame-shard mode (svg.distributed.enable_frame_shards; ValueError without
     it), where q, k, v hold this rank's rows and the call is token_sharded_svg1_attention under the dense mask with every head in logical
-    order; ignored otherwise."""
+    order; ignored otherwise.
+    Token-shard mode (svg.distributed.enable_token_shards): q, k, v hold this rank's rows token_shard_range(S) of all heads and the call
+    goes through run_token_sharded — whole heads of the whole sequence on every rank, bit for bit the single-GPU rows; return_lse, out_dtype
+    and per-video lengths that differ are refused before any collective, as under enable()."""
+    if _dist.token_shards_active() and not _local:
+        _state_kw("dense_attention", return_lse, out_dtype, q_prescaled, True)
+        lens = per_video(valid_len, q.shape[0], "dense_attention(valid_len)")
+        if lens is not None:
+            vals, _ = video_groups([int(x) for x in lens])
+            if len(vals) > 1:
+                _no_sharding_of_groups("dense_attention")
+            valid_len = vals[0]
+        if geometry is None and _dist.token_shard_row_counts() is None:
+            raise ValueError("dense_attention: token-shard mode needs geometry= (the Geometry of the whole sequence) or a mode enabled with "
+                             "row_counts: the tensors hold this rank's rows only")
+        total = geometry.seq_len if geometry is not None else sum(_dist.token_shard_row_counts())
+        return _dist.run_token_sharded(lambda qh, kh, vh: dense_attention(qh, kh, vh, valid_len, q_prescaled, _local=True), (q, k, v),
+                                       total, _dist.token_shards_group())
     if _dist.frame_shards_active():
         if geometry is None:
             raise ValueError("dense_attention: frame-shard mode needs geometry= (the Geometry of the whole sequence; the tensors hold this "
@@ -287,6 +311,17 @@ def dense_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, valid_len
         return _native.band_attention(q, k, v, _dense_band_mask(S, valid_len), q_prescaled=q_prescaled, **kw)
     assert not q_prescaled, "a pre-scaled q only exists on the GPU path"
     return _dense_sdpa(q, k, v, valid_len)
+
+
+def self_attention_without_timestep(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attention_mask=None, geometry: Optional[Geometry] = None):
+    """The processors' self-attention branch for a call without a timestep: the reference's scaled_dot_product_attention call.  In token-shard
+    mode (svg.distributed.enable_token_shards) q, k, v hold this rank's rows only, and SDPA over them would attend within the shard: there
+    the call is dense_attention through run_token_sharded (a mask has no sharded form: NotImplementedError)."""
+    if _dist.token_shards_active():
+        if attention_mask is not None:
+            raise NotImplementedError("self attention without a timestep: token-shard mode takes no attention_mask")
+        return dense_attention(q, k, v, geometry=geometry)
+    return F.scaled_dot_product_attention(q, k, v, attn_mask=attention_mask, dropout_p=0.0, is_causal=False)
 
 
 @time_logging_decorator("Level 3 - Cross Attention")
@@ -392,18 +427,23 @@ def reseed_switch_generator(seed: Optional[int] = None) -> None:
     """(Re)build the CPU generator of the device-switched path from `seed` (default: the global seed, torch.initial_seed()).
     Called by svg.utils.seed.seed_everything and by the replace_*_attention install hooks, so that seeding a second video in the
     same process resets the sampled profiler rows exactly like a fresh process.  Under svg.distributed.enable() (and
-    enable_frame_shards()) the seed of rank 0 is broadcast: every rank draws the same rows, whatever it was seeded with (the sharded result equals the single-GPU one)."""
+    enable_frame_shards(), enable_token_shards()) the seed of rank 0 is broadcast: every rank draws the same rows, whatever it was seeded with (the sharded result equals the single-GPU one)."""
     global _SWITCH_GEN, _SWITCH_SEED
     base = torch.initial_seed() if seed is None else int(seed)
     use = base
-    if _dist.active() or _dist.frame_shards_active():
-        grp = _dist.current_group() if _dist.active() else _dist.frame_shards_group()
+    if _sharded_draws():
+        grp = _dist.head_mode()[1] if _dist.head_mode()[0] else _dist.frame_shards_group()
         on_gpu = torch.distributed.get_backend(grp) == "nccl"
         t = torch.tensor([base % (2 ** 63)], dtype=torch.int64, device="cuda" if on_gpu else "cpu")
         torch.distributed.broadcast(t, src=torch.distributed.get_global_rank(grp, 0) if grp is not None else 0, group=grp)
         use = int(t.item())
     _SWITCH_GEN = torch.Generator().manual_seed(use % (2 ** 63))
-    _SWITCH_SEED = (base, _dist.active() or _dist.frame_shards_active())
+    _SWITCH_SEED = (base, _sharded_draws())
+
+
+def _sharded_draws() -> bool:
+    """a mode of svg.distributed is on in which every rank must draw the same rows (enable, enable_frame_shards, enable_token_shards)"""
+    return _dist.active() or _dist.frame_shards_active() or _dist.token_shards_active()
 
 
 def _switch_generator():
@@ -413,7 +453,7 @@ def _switch_generator():
     torch.initial_seed() changes (a later torch.manual_seed) or sharding is switched on, and by `reseed_switch_generator()`, which
     the seeding / install hooks call (re-seeding with the SAME seed cannot be seen from the seed alone).  (Deviation: at equal seeds
     the sampled rows differ from the reference's; every other consumer of the global CPU RNG sees the reference's stream.)"""
-    if _SWITCH_GEN is None or _SWITCH_SEED != (torch.initial_seed(), _dist.active() or _dist.frame_shards_active()):
+    if _SWITCH_GEN is None or _SWITCH_SEED != (torch.initial_seed(), _sharded_draws()):
         reseed_switch_generator()
     return _SWITCH_GEN
 
@@ -454,6 +494,10 @@ def svg1_attention_device_switch(q, k, v, geo: Geometry, mask: "_native.BandMask
         if len(pairs) > 1:
             _no_sharding_of_groups("SVG1 attention")
             groups = ([m for m, _ in pairs], [d for _, d in pairs], heads)
+    if _dist.token_shards_active() and not _local:   # q, k, v: this rank's rows; whole heads of the whole sequence inside, rows back
+        return _dist.run_token_sharded(lambda qh, kh, vh: svg1_attention_device_switch(
+            qh, kh, vh, geo, mask, dense_mask, prof, num_sampled_rows, sample_max_row, dense_flag, _local=True,
+            q_prescaled=q_prescaled), (q, k, v), geo.seq_len, _dist.token_shards_group())
     if _dist.active() and not _local:   # svg.distributed.enable(): this rank's heads only, outputs all-gathered
         return _dist.run_sharded(lambda qh, kh, vh: svg1_attention_device_switch(
             qh, kh, vh, geo, mask, dense_mask, prof, num_sampled_rows, sample_max_row, dense_flag, _local=True,
@@ -466,8 +510,8 @@ def svg1_attention_device_switch(q, k, v, geo: Geometry, mask: "_native.BandMask
                                             head_perm_flag=best_mask_idx, vid0=geo.vid0, num_frame=geo.num_frame,
                                             frame_size=geo.frame_size, q_prescaled=q_prescaled, **kw)
     else:
-        if _local:
-            kw["token_major_out"] = False
+        if _local:   # (enable(): contiguous head slices are gathered; token-shard mode: token-major rows are what the outbound exchange sends)
+            kw["token_major_out"] = TOKEN_MAJOR_IO and _dist.token_shards_active()
         out = _native.band_attention_switch(q, k, v, mask, dense_mask, dense_flag, head_perm_flag=best_mask_idx, vid0=geo.vid0,
                                             num_frame=geo.num_frame, frame_size=geo.frame_size, q_prescaled=q_prescaled, **kw)
     best = torch.where(dense_flag.reshape(()) != 0, torch.full_like(best_mask_idx, -1), best_mask_idx)
@@ -501,6 +545,10 @@ def svg1_sparse_attention(q, k, v, geo: Geometry, mask: "_native.BandMask", prof
         if len(masks) > 1:
             _no_sharding_of_groups("SVG1 sparse attention")
             groups = (masks, heads)
+    if _dist.token_shards_active() and not _local:   # q, k, v: this rank's rows; whole heads of the whole sequence inside, rows back
+        return _dist.run_token_sharded(lambda qh, kh, vh: svg1_sparse_attention(
+            qh, kh, vh, geo, mask, prof, num_sampled_rows, sample_max_row, fused, _local=True, q_prescaled=q_prescaled), (q, k, v),
+            geo.seq_len, _dist.token_shards_group())
     if _dist.active() and not _local:   # svg.distributed.enable(): this rank's heads only, outputs all-gathered
         return _dist.run_sharded(lambda qh, kh, vh: svg1_sparse_attention(
             qh, kh, vh, geo, mask, prof, num_sampled_rows, sample_max_row, fused, _local=True, q_prescaled=q_prescaled), (q, k, v),
@@ -518,7 +566,7 @@ def svg1_sparse_attention(q, k, v, geo: Geometry, mask: "_native.BandMask", prof
                 out = _native.band_attention_fp8(q.contiguous(), k.contiguous(), v.contiguous(), mask, sm_scale=LN2 if q_prescaled else None, **pk)
             else:
                 if _local:
-                    kw["token_major_out"] = False
+                    kw["token_major_out"] = TOKEN_MAJOR_IO and _dist.token_shards_active()
                 out = _native.band_attention(q, k, v, mask, q_prescaled=q_prescaled, **kw, **pk)
         return (out[0], best_mask_idx, out[1]) if return_lse else (out, best_mask_idx)
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
@@ -594,6 +642,9 @@ def kmeans_clustering(store: CentroidStore, layer_idx: int, q_video, k_video, nu
     all-reduced — so that the result does not depend on the sharding.
     cfg > 1: one stopping rule per video (the loops run with group = H, the heads of one video; sharded: this rank's heads of one
     video, the per-video maxima all-reduced), so that each video's clustering is the one it gets alone."""
+    if _dist.token_shards_active() and head_shard is None:
+        raise NotImplementedError("kmeans_clustering: token-shard mode clusters inside svg2_sparse_attention only (whole heads of the whole "
+                                  "sequence); a call on this rank's rows (zero_step_kmeans_init) has no sharded form")
     cfg, H, N, D = q_video.shape
     first = not store.has(layer_idx, cfg, H)
     iters = iter_init if first else iter_step
@@ -665,10 +716,15 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
         prompt_length = pl[0] if len(set(pl)) == 1 else tuple(pl)
         if isinstance(prompt_length, tuple):
             _no_sharding_of_groups("SVG2 sparse attention")
-    if _dist.active() and _head_shard is None:   # svg.distributed.enable(): this rank's heads only, outputs all-gathered
-        grp = _dist.current_group()
+    if (_dist.active() or _dist.token_shards_active()) and _head_shard is None:
+        grp = _dist.head_mode()[1]
         mine = _dist.shard_heads(q.shape[1], torch.distributed.get_rank(grp), torch.distributed.get_world_size(grp))
         shard = (mine[0], mine[-1] + 1, q.shape[1]) if mine else (0, 0, q.shape[1])
+        if _dist.token_shards_active():   # q, k, v: this rank's rows; whole heads of the whole sequence inside, rows back
+            return _dist.run_token_sharded(lambda qh, kh, vh: svg2_sparse_attention(
+                qh, kh, vh, geo, store, layer_idx, num_q_centroids, num_k_centroids, top_p, min_kc_ratio, iter_init, iter_step,
+                prompt_length, logging_file, timestep, _head_shard=shard), (q, k, v), geo.seq_len, grp)
+        # svg.distributed.enable(): this rank's heads only, outputs all-gathered
         return _dist.run_sharded(lambda qh, kh, vh: svg2_sparse_attention(
             qh, kh, vh, geo, store, layer_idx, num_q_centroids, num_k_centroids, top_p, min_kc_ratio, iter_init, iter_step,
             prompt_length, logging_file, timestep, _head_shard=shard), (q, k, v), grp)
@@ -702,14 +758,15 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
     out = _native.varblock_attention(q, k, v, dyn_map.view(cfg * H, QB, KB).contiguous(),
                                      q_sizes.view(cfg * H, QB).contiguous(), k_sizes.view(cfg * H, KB).contiguous(),
                                      q_row_idx=qidx.contiguous(), kv_row_idx=kidx.contiguous(), fp8=f8,
-                                     token_major_out=TOKEN_MAJOR_IO and _head_shard is None, rows_covered=True)
+                                     token_major_out=TOKEN_MAJOR_IO and (_head_shard is None or _dist.token_shards_active()),
+                                     rows_covered=True)
     if logging_file is not None:
         from .context import timestep_value
 
         densities = density_calculation(dyn_map, q_sizes, k_sizes)
         if _head_shard is not None:   # one log line per layer-call with all heads, written by rank 0
-            densities = _dist.all_gather_heads(densities.reshape(cfg, H, 1, 1), _head_shard[2], _dist.current_group()).reshape(cfg, -1)
-        if _head_shard is None or torch.distributed.get_rank(_dist.current_group()) == 0:
+            densities = _dist.all_gather_heads(densities.reshape(cfg, H, 1, 1), _head_shard[2], _dist.head_mode()[1]).reshape(cfg, -1)
+        if _head_shard is None or torch.distributed.get_rank(_dist.head_mode()[1]) == 0:
             DENSITY_LOG.push(logging_file, {"timestep": timestep_value(timestep) if timestep is not None else None,
                                             "layer": layer_idx}, densities)
     return out.reshape(cfg, H, S, D)   # (out is [cfg, H, S, D] already, in either storage order: a view)
@@ -894,7 +951,8 @@ def prescale_supported(query) -> bool:
 
 def value_in_place(value: torch.Tensor, heads: int):
     """The v projection's output [bsz, S, heads * D] as the [bsz, heads, S, D] VIEW the attention kernels read in place
-    (svg_attn_layout_t; TOKEN_MAJOR_IO, one GPU, head_dim 64 / 128, 16-bit, on the GPU) — or None: the caller makes the head-major copy."""
+    (svg_attn_layout_t; TOKEN_MAJOR_IO, one GPU, head_dim 64 / 128, 16-bit, on the GPU) — or None: the caller makes the head-major copy.
+    Token-shard mode (svg.distributed.enable_token_shards) takes the view as well: run_token_sharded's inbound pack reads it in place."""
     if not (TOKEN_MAJOR_IO and value.is_cuda and value.dim() == 3 and value.is_contiguous() and not _dist.active()):
         return None
     if value.dtype not in (torch.bfloat16, torch.float16) or value.shape[-1] not in (heads * 64, heads * 128):

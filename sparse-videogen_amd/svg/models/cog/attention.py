@@ -90,7 +90,7 @@ class CogVideoX_SparseAttn_Processor2_0:
         return hidden_states.split([text_seq_length, hidden_states.size(1) - text_seq_length], dim=1)
 
     def flash_attention(self, query, key, value):
-        return _core.dense_attention(query, key, value, q_prescaled=self._q_prescaled)
+        return _core.dense_attention(query, key, value, q_prescaled=self._q_prescaled, geometry=self.geometry())
 
     def sample_mse(self, query, key, value):
         """Cog samples rows from the WHOLE sequence (ref :126)"""
@@ -115,12 +115,13 @@ class CogVideoX_SparseAttn_Processor2_0:
         if self.block_mask is None:
             raise RuntimeError("CogVideoX_SparseAttn_Processor2_0.block_mask is not set: call replace_cog_attention first")
         prof = profile_desc(geo.context_length, geo.num_frame, geo.frame_size)
+        total = geo.seq_len   # (seq_len, except in token-shard mode: the masks and the sampled rows are the whole sequence's)
         if dense_flag is not None:
-            out, best = _core.svg1_attention_device_switch(query, key, value, geo, self.block_mask, dense_mask(seq_len), prof,
-                                                           self.num_sampled_rows, seq_len, dense_flag, q_prescaled=self._q_prescaled)
+            out, best = _core.svg1_attention_device_switch(query, key, value, geo, self.block_mask, dense_mask(total), prof,
+                                                           self.num_sampled_rows, total, dense_flag, q_prescaled=self._q_prescaled)
             self.last_best_mask_idx = best
             return out.reshape(cfg, num_heads, seq_len, dim)
-        out, best = _core.svg1_sparse_attention(query, key, value, geo, self.block_mask, prof, self.num_sampled_rows, seq_len,
+        out, best = _core.svg1_sparse_attention(query, key, value, geo, self.block_mask, prof, self.num_sampled_rows, total,
                                                 fused=self.fused_placement, q_prescaled=self._q_prescaled)
         self.last_best_mask_idx = best
         return out.reshape(cfg, num_heads, seq_len, dim)

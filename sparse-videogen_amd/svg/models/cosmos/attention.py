@@ -7,7 +7,6 @@ from __future__ import annotations
 from typing import Optional
 
 import torch
-import torch.nn.functional as F
 
 from ...timer import time_logging_decorator
 from .. import _core
@@ -119,9 +118,8 @@ class _CosmosPlumbing:
             hidden_states = _core.cross_attention_key_masked(query, key, value, attention_mask)
         elif cross:   # cross attention in Cosmos (ref :104-107): svg_cross_attention, SDPA where that does not apply
             hidden_states = _core.cross_attention(query, key, value, attention_mask)
-        elif timestep is None:
-            hidden_states = F.scaled_dot_product_attention(query, key, value, attn_mask=attention_mask, dropout_p=0.0,
-                                                           is_causal=False)
+        elif timestep is None:   # (SDPA; in token-shard mode the rows of the other ranks are keys too: _core.dense_attention)
+            hidden_states = _core.self_attention_without_timestep(query, key, value, attention_mask, self.geometry())
         else:
             # (v may be the head view of to_v's output: the attention kernels read it in place, as from the Wan processors)
             assert query.is_contiguous() and key.is_contiguous() and value.stride(-1) == 1, "Query, key must be contiguous, value row-contiguous"

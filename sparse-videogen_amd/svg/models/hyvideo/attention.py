@@ -382,7 +382,7 @@ class Hunyuan_SAPAttn_Processor2_0(Hunyuan_SVGAttn_Processor2_0):
                 _core.kmeans_clustering(self.centroid_store, layer_idx, query[:, :, :V], key[:, :, :V],   # (views: read in place)
                                         self.num_q_centroids, self.num_k_centroids,
                                         self.kmeans_iter_init, self.kmeans_iter_step)
-            return _core.dense_attention(query, key, value, valid).reshape(cfg, num_heads, seq_len, dim)
+            return _core.dense_attention(query, key, value, valid, geometry=geo).reshape(cfg, num_heads, seq_len, dim)
         out = _core.svg2_sparse_attention(query, key, value, geo, self.centroid_store, layer_idx, self.num_q_centroids,
                                           self.num_k_centroids, self.top_p_kmeans, self.min_kc_ratio, self.kmeans_iter_init,
                                           self.kmeans_iter_step, prompt_length=self.prompt_length if isinstance(self.prompt_length, tuple) else int(self.prompt_length),

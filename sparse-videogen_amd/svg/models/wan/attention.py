@@ -6,7 +6,6 @@ from __future__ import annotations
 from typing import Optional
 
 import torch
-import torch.nn.functional as F
 
 from ...kernels.triton.rmsnorm import triton_rmsnorm_forward
 from ...timer import time_logging_decorator
@@ -224,9 +223,8 @@ class WanAttn_SVGAttn_Processor2_0:
             hidden_states = _core.cross_attention_pair(query, key, value, key_img, value_img, attention_mask)
         elif cross:  # cross attention in Wan (ref :198-201): svg_cross_attention on the head views, SDPA where that does not apply
             hidden_states = _core.cross_attention(query, key, value, attention_mask)
-        elif timestep is None:
-            hidden_states = F.scaled_dot_product_attention(query, key, value, attn_mask=attention_mask, dropout_p=0.0,
-                                                           is_causal=False)
+        elif timestep is None:   # (SDPA; in token-shard mode the rows of the other ranks are keys too: _core.dense_attention)
+            hidden_states = _core.self_attention_without_timestep(query, key, value, attention_mask, self.geometry())
         else:
             self._q_prescaled = self._rope_scaled
             try:
