@@ -328,6 +328,14 @@ PROFILE_SHARD_SIGNATURES = {
     "svg_sample_mse_from_parts": (C.c_int, [_VP, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _SZ, _VP, _VP]),
 }
 
+# include/svg_attn_sample_rows.h: the quality probe's dense rows, in a table of its own for the same reason (tests/test_sample_rows_cpu.py;
+# the allocating wrapper is svg/_probe.py sample_dense_rows)
+SAMPLE_ROWS_SIGNATURES = {
+    "svg_sample_dense_rows_workspace_bytes": (_SZ, [_I32, _I32, _I32, _I32]),
+    "svg_sample_dense_rows": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _F32, _I32, _VP, _VP, _VP, _SZ,
+                                        C.POINTER(AttnLayout), _VP]),
+}
+
 
 class CopyBox(C.Structure):
     """svg_copy_box_t (include/svg_attn_shard_exchange.h): extent[0] * extent[1] * extent[2] rows of D contiguous elements; offsets and
@@ -364,7 +372,7 @@ def load(strict: bool = True) -> Optional[C.CDLL]:
         lib = C.CDLL(str(p))
         for name, (res, args) in {**SIGNATURES, **SPARSE_LSE_SIGNATURES, **SPARSE_F32_SIGNATURES, **BAND_LSE_FORM_SIGNATURES,
                                    **BAND_WINDOW_SIGNATURES, **BAND_SHARD_SIGNATURES, **BAND_SHARD_SWITCH_SIGNATURES,
-                                   **PROFILE_SHARD_SIGNATURES, **SHARD_EXCHANGE_SIGNATURES}.items():
+                                   **PROFILE_SHARD_SIGNATURES, **SAMPLE_ROWS_SIGNATURES, **SHARD_EXCHANGE_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

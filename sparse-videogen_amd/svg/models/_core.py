@@ -439,6 +439,7 @@ def reseed_switch_generator(seed: Optional[int] = None) -> None:
         use = int(t.item())
     _SWITCH_GEN = torch.Generator().manual_seed(use % (2 ** 63))
     _SWITCH_SEED = (base, _sharded_draws())
+    reseed_probe_generator(base)   # (the quality probe's rows start over with the video as well; a stream of its own, see _probe_generator)
 
 
 def _sharded_draws() -> bool:
@@ -468,7 +469,8 @@ def dense_flag_on_device(timestep, first_times_fp):
 
 def svg1_attention_device_switch(q, k, v, geo: Geometry, mask: "_native.BandMask", dense_mask: "_native.BandMask",
                                  prof: "_native.ProfileDesc", num_sampled_rows: int, sample_max_row: int, dense_flag,
-                                 _local: bool = False, q_prescaled: bool = False, return_lse: bool = False, out_dtype=None):
+                                 _local: bool = False, q_prescaled: bool = False, return_lse: bool = False, out_dtype=None,
+                                 quality: Optional["QualityRequest"] = None):
     """Dense warm-up step or sparse step, decided on the device: the profiler and the attention kernel read
     `dense_flag`; on a dense step the profiler returns at once and the kernel runs `dense_mask` without the head placement.
     Same attention results as the host-side branch of attention_core_logic (ref: hyvideo/attention.py:491-524) for the same sampled
@@ -479,11 +481,17 @@ def svg1_attention_device_switch(q, k, v, geo: Geometry, mask: "_native.BandMask
     out_dtype=torch.float32: fp32 rows.  Plain q only (ValueError), not under svg.distributed (NotImplementedError).
     Frame-shard mode (svg.distributed.enable_frame_shards): q, k, v [cfg, H, S_r, D] are all heads of this rank's frame_shard of the
     sequence `geo` describes, the call is token_sharded_svg1_layer_call with dense_mask / dense_flag, -> (out [cfg, H, S_r, D], best);
-    what has no shard form raises before any collective (_frame_shard_setup)."""
+    what has no shard form raises before any collective (_frame_shard_setup).
+    quality: a QualityRequest (quality_request): the call is probed as well and its record queued (log_quality) — on EVERY call, the host
+    does not know whether the step is dense; the record carries dense_flag and the writer drops those of dense steps.  Where the launch has
+    an LSE form the call goes through it (the same o).  Refused under svg.distributed."""
+    if quality is not None:
+        _refuse_quality_when_sharded("svg1_attention_device_switch")
     if _dist.frame_shards_active():   # q, k, v: this rank's rows; -> (out [cfg, H, S_r, D], best_mask_idx)
         return _frame_shard_svg1("svg1_attention_device_switch", q, k, v, geo, mask, dense_mask, prof, num_sampled_rows, sample_max_row,
                                  dense_flag, q_prescaled=q_prescaled, return_lse=return_lse, out_dtype=out_dtype)
-    kw = _state_kw("svg1_attention_device_switch", return_lse, out_dtype, q_prescaled, TOKEN_MAJOR_IO)
+    probe_lse = quality is not None and not return_lse and _quality_lse_form(q, q_prescaled)
+    kw = _state_kw("svg1_attention_device_switch", return_lse or probe_lse, out_dtype, q_prescaled, TOKEN_MAJOR_IO)
     _require_gpu(q, "SVG1 attention")
     cfg, H = q.shape[0], q.shape[1]
     pm, pd = per_video(mask, cfg, "svg1_attention_device_switch(mask)"), per_video(dense_mask, cfg, "svg1_attention_device_switch(dense_mask)")
@@ -515,12 +523,18 @@ def svg1_attention_device_switch(q, k, v, geo: Geometry, mask: "_native.BandMask
         out = _native.band_attention_switch(q, k, v, mask, dense_mask, dense_flag, head_perm_flag=best_mask_idx, vid0=geo.vid0,
                                             num_frame=geo.num_frame, frame_size=geo.frame_size, q_prescaled=q_prescaled, **kw)
     best = torch.where(dense_flag.reshape(()) != 0, torch.full_like(best_mask_idx, -1), best_mask_idx)
+    if quality is not None:
+        o_p, lse_p = out if (return_lse or probe_lse) else (out, None)
+        log_quality(quality, o_p, lse_p, q, k, v, q_prescaled, dense_flag=dense_flag)
+        if probe_lse:
+            out = o_p
     return (out[0], best, out[1]) if return_lse else (out, best)
 
 
 def svg1_sparse_attention(q, k, v, geo: Geometry, mask: "_native.BandMask", prof: "_native.ProfileDesc",
                           num_sampled_rows: int, sample_max_row: int, fused: bool = True, _local: bool = False,
-                          q_prescaled: bool = False, return_lse: bool = False, out_dtype=None):
+                          q_prescaled: bool = False, return_lse: bool = False, out_dtype=None,
+                          quality: Optional["QualityRequest"] = None):
     """The sparse branch of attention_core_logic (ref: hyvideo/attention.py:507-524):
     online profiling -> best_mask_idx -> placement -> block-sparse attention -> inverse placement.
     fused=True folds both placements into the attention kernel (bit-identical result, ~5.9 GB less HBM traffic at
@@ -531,11 +545,17 @@ def svg1_sparse_attention(q, k, v, geo: Geometry, mask: "_native.BandMask", prof
     out_dtype=torch.float32: fp32 rows.  The fused 16-bit path with a plain q only (ValueError), not under svg.distributed
     (NotImplementedError).
     Frame-shard mode: as svg1_attention_device_switch, without a flag; the rows come from the switched path's generator (every rank
-    draws the same)."""
+    draws the same).
+    quality: a QualityRequest (quality_request): the call is probed as well and its record queued (log_quality); where the launch has an
+    LSE form — head_dim 128, 16-bit, plain q, fused — it goes through it (the same o) and the kept mass is logged, elsewhere the error
+    alone.  Refused under svg.distributed."""
+    if quality is not None:
+        _refuse_quality_when_sharded("svg1_sparse_attention")
     if _dist.frame_shards_active():   # q, k, v: this rank's rows; -> (out [cfg, H, S_r, D], best_mask_idx)
         return _frame_shard_svg1("svg1_sparse_attention", q, k, v, geo, mask, None, prof, num_sampled_rows, sample_max_row, None,
                                  q_prescaled=q_prescaled, return_lse=return_lse, out_dtype=out_dtype, fused=fused)
-    kw = _state_kw("svg1_sparse_attention", return_lse, out_dtype, q_prescaled, TOKEN_MAJOR_IO, fp8=_use_fp8(q), fused=fused)
+    probe_lse = quality is not None and not return_lse and _quality_lse_form(q, q_prescaled, fused)
+    kw = _state_kw("svg1_sparse_attention", return_lse or probe_lse, out_dtype, q_prescaled, TOKEN_MAJOR_IO, fp8=_use_fp8(q), fused=fused)
     _require_gpu(q, "SVG1 sparse attention")
     groups = None
     pm = per_video(mask, q.shape[0], "svg1_sparse_attention(mask)")
@@ -568,6 +588,11 @@ def svg1_sparse_attention(q, k, v, geo: Geometry, mask: "_native.BandMask", prof
                 if _local:
                     kw["token_major_out"] = TOKEN_MAJOR_IO and _dist.token_shards_active()
                 out = _native.band_attention(q, k, v, mask, q_prescaled=q_prescaled, **kw, **pk)
+        if quality is not None:
+            o_p, lse_p = out if (return_lse or probe_lse) else (out, None)
+            log_quality(quality, o_p, lse_p, q, k, v, q_prescaled)
+            if probe_lse:
+                out = o_p
         return (out[0], best_mask_idx, out[1]) if return_lse else (out, best_mask_idx)
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     qo, ko, vo = _native.empty_like(q), _native.empty_like(k), _native.empty_like(v)
@@ -583,6 +608,8 @@ def svg1_sparse_attention(q, k, v, geo: Geometry, mask: "_native.BandMask", prof
     with time_logging_decorator("Level 3 - fast_hidden_states_placement"):
         _native.head_placement([hs], [out], best_mask_idx, geo.context_length, geo.num_frame, geo.frame_size, geo.text_first,
                                inverse=True)
+    if quality is not None:   # (the three-kernel pipeline has no LSE form: the error alone)
+        log_quality(quality, out, None, q, k, v, q_prescaled)
     return out, best_mask_idx
 
 
@@ -701,14 +728,20 @@ def kmeans_clustering(store: CentroidStore, layer_idx: int, q_video, k_video, nu
 
 def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_idx: int, num_q_centroids: int,
                           num_k_centroids: int, top_p: float, min_kc_ratio: float, iter_init: int, iter_step: int,
-                          prompt_length=0, logging_file: Optional[str] = None, timestep=None, _head_shard=None):
+                          prompt_length=0, logging_file: Optional[str] = None, timestep=None, _head_shard=None,
+                          quality: Optional["QualityRequest"] = None):
     """The sparse branch of the SAP processors (ref: hyvideo/attention.py:747-804, wan/attention.py:529-559):
     k-means on the video tokens -> top-p block map -> (Hunyuan) two pseudo clusters for prompt / unused prompt ->
     variable-block attention with the token permutation fused in (the result is already in the original order).
     q, k, v: [cfg, H, S, D]; cfg > 1 (several videos: a list of prompts, num_videos_per_prompt > 1) clusters each video with its own
     stopping rule, so every video's output, labels and block map are the ones a cfg = 1 call on that video alone gives.
     prompt_length: one int for the batch, or a sequence of cfg ints, one per video — the sizes of the two text pseudo-clusters are per
-    head in the kernel already, so the videos still share one launch."""
+    head in the kernel already, so the videos still share one launch.
+    quality: a QualityRequest (quality_request): the call is probed as well and its record, with the per-head densities, queued
+    (log_quality).  The kept mass is logged where svg_varblock_attention_lse runs the body the plain call runs — head_dim 128, 16-bit,
+    block-rows large enough for the two-phase body (S >= 160 block-rows) — elsewhere the error alone.  Refused under svg.distributed."""
+    if quality is not None:
+        _refuse_quality_when_sharded("svg2_sparse_attention")
     _require_gpu(q, "SVG2 sparse attention")
     pl = per_video(prompt_length, q.shape[0], "svg2_sparse_attention(prompt_length)")
     if pl is not None:
@@ -755,11 +788,16 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
     # (rows_covered: the cluster sizes of every head add up to S — k-means counts over the V video tokens plus the text pseudo-clusters of
     #  dynamic_map_post_processing — so the kernel writes every output row and the wrapper skips the zero fill)
     # (one launch over the cfg * H heads; the token-major output is [cfg, S, H, D] in memory: svg_attn_layout_t with heads_per_batch = H)
+    # (the LSE entry always runs the two-phase 16x16x32 body; the plain call picks it from S >= 160 QB on: only there is its o the same)
+    probe_lse = quality is not None and _quality_lse_form(q, False) and S >= 160 * QB
     out = _native.varblock_attention(q, k, v, dyn_map.view(cfg * H, QB, KB).contiguous(),
                                      q_sizes.view(cfg * H, QB).contiguous(), k_sizes.view(cfg * H, KB).contiguous(),
                                      q_row_idx=qidx.contiguous(), kv_row_idx=kidx.contiguous(), fp8=f8,
                                      token_major_out=TOKEN_MAJOR_IO and (_head_shard is None or _dist.token_shards_active()),
-                                     rows_covered=True)
+                                     rows_covered=True, return_lse=probe_lse)
+    if quality is not None:
+        out, lse_p = out if probe_lse else (out, None)
+        log_quality(quality, out, lse_p, q, k, v, density=density_calculation(dyn_map, q_sizes, k_sizes))
     if logging_file is not None:
         from .context import timestep_value
 
@@ -819,6 +857,189 @@ def flush_density_log() -> None:
 import atexit  # noqa: E402
 
 atexit.register(flush_density_log)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Quality probe: what a sparse layer-call cost in accuracy.  The density log says how much compute was kept; this says how much ATTENTION
+# was kept and what the output lost, on a few sampled rows per head: the dense truth of those rows from one pass over K and V
+# (svg/_probe.py sample_dense_rows), the sparse call's own output and — where the launch has an LSE form — its row log-sum-exp.
+#   kept mass of a row = exp(lse_sparse - lse_dense): the share of the dense softmax row on the keys the sparse form kept
+#   output error       = o_sparse - o_dense
+# ---------------------------------------------------------------------------------------------------------------
+def quality_figures(o_s: torch.Tensor, lse_s, o_d: torch.Tensor, lse_d: torch.Tensor) -> dict:
+    """The figures of sparse_quality from the gathered rows: o_s [cfg, H, R, D] (any float type), lse_s [cfg, H, R] or None, o_d / lse_d
+    the dense rows.  A row the sparse form gives no key (lse_s = -inf) has kept mass 0."""
+    diff = o_s.float() - o_d.float()
+    num = diff.square().sum(dim=(-2, -1))
+    out = {"rel_l2": torch.sqrt(num / o_d.float().square().sum(dim=(-2, -1))), "mse": diff.square().mean(dim=(-2, -1)), "kept_mass": None}
+    if lse_s is not None:
+        out["kept_mass"] = torch.exp(lse_s.float() - lse_d.float()).mean(dim=-1)
+    return out
+
+
+def sparse_quality(o_sparse: torch.Tensor, lse_sparse, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rows: torch.Tensor, valid_len=None,
+                   sm_scale: Optional[float] = None) -> dict:
+    """A sparse attention result against dense attention on the sampled `rows` (int64 [R], R <= 64, CPU or device):
+    {"rel_l2" [cfg, H]: sqrt(sum_rows |o_s - o_d|^2 / sum_rows |o_d|^2), "mse" [cfg, H]: mean squared difference over rows and D,
+    "kept_mass" [cfg, H]: mean over rows of exp(lse_s - lse_d), None when lse_sparse is None} — device tensors, no host synchronisation.
+    o_sparse [cfg, H, S, D] and lse_sparse [cfg, H, S] (or [cfg * H, S]) are the sparse call's FULL outputs in the caller's row order,
+    head-major or token-major storage alike (views); the rows are gathered here.  q, k, v [cfg, H, S, D] views, valid_len as in
+    dense_attention (one int), sm_scale as in the attention wrappers (LN2 for a q that carries the softmax scale).  GPU only."""
+    from .. import _probe
+
+    cfg, H, S, D = q.shape
+    o_d, lse_d = _probe.sample_dense_rows(q, k, v, rows, valid_len, sm_scale)
+    idx = rows.to(q.device, non_blocking=True)
+    o_s = o_sparse.reshape(cfg, H, S, D).index_select(2, idx) if o_sparse.dim() != 4 else o_sparse.index_select(2, idx)
+    lse_s = None if lse_sparse is None else lse_sparse.reshape(cfg, H, S).index_select(2, idx)
+    return quality_figures(o_s, lse_s, o_d, lse_d)
+
+
+_PROBE_GEN = None
+_PROBE_SEED = None
+_PROBE_SALT = 0x51A17E   # the probe's stream is the global seed's, offset: never the rows the switched path draws
+
+
+def reseed_probe_generator(seed: Optional[int] = None) -> None:
+    """(Re)build the CPU generator of the quality probe's rows from `seed` (default: the global seed, torch.initial_seed())."""
+    global _PROBE_GEN, _PROBE_SEED
+    base = torch.initial_seed() if seed is None else int(seed)
+    _PROBE_GEN = torch.Generator().manual_seed((base + _PROBE_SALT) % (2 ** 63))
+    _PROBE_SEED = torch.initial_seed()
+
+
+def _probe_generator():
+    """CPU generator of the quality probe's rows, beside `_switch_generator`: derived from the global seed, re-derived when
+    torch.initial_seed() changes.  Drawing from it advances neither the global CPU stream nor the switched path's generator, so a
+    processor with `quality_log` set computes the attention output and best_mask_idx it computes without."""
+    if _PROBE_GEN is None or _PROBE_SEED != torch.initial_seed():
+        reseed_probe_generator()
+    return _PROBE_GEN
+
+
+@dataclass
+class QualityRequest:
+    """What a processor with `quality_log` set hands its core call: where to log, how many rows to probe, the dense `valid` of the call
+    (an int, a tuple with one entry per video, or None) and the record's timestep / layer."""
+    path: str
+    rows: int = 64
+    valid_len: object = None
+    timestep: object = None
+    layer: Optional[int] = None
+
+
+def _refuse_quality_when_sharded(what: str) -> None:
+    # (the modes' own switches, whatever the group's size: a group of one rank refuses like every other, so all ranks raise together)
+    if _dist._STATE["enabled"] or _dist.frame_shards_active() or _dist.token_shards_active():
+        raise NotImplementedError(f"{what}: quality_log under svg.distributed (enable, enable_frame_shards, enable_token_shards) is not "
+                                  f"implemented: the probe reads whole heads of the whole sequence; unset quality_log or run on one GPU")
+
+
+def quality_request(what: str, path, rows: int, valid_len=None, timestep=None, layer=None) -> Optional[QualityRequest]:
+    """The processors' hook: None without a path (nothing changes); with one, the request — refused under every mode of svg.distributed,
+    on the host, before any collective, on every rank alike."""
+    if path is None:
+        return None
+    _refuse_quality_when_sharded(what)
+    return QualityRequest(str(path), int(rows), valid_len, timestep, layer)
+
+
+def _quality_lse_form(q: torch.Tensor, q_prescaled: bool, fused: bool = True) -> bool:
+    """does the sparse launch have a form that also returns the row log-sum-exp (with the same o)?  head_dim 128, 16-bit, plain q, fused"""
+    return bool(fused and not q_prescaled and not _use_fp8(q) and q.shape[-1] == 128 and q.dtype in (torch.bfloat16, torch.float16))
+
+
+class _QualityLog:
+    """The deferred writer of the quality records, the machinery of _DensityLog: the figures of a layer-call travel to pinned host memory
+    in one asynchronous copy and the JSON line {"timestep", "layer", "rel_l2", "mse", "kept_mass" (null without an LSE form), "density"
+    (SVG2)} is written once the copy has completed — opportunistically on later calls, and by flush().  A record that carries the
+    device-switch flag of a DENSE step is dropped: the host does not know the step's kind when it launches the probe."""
+
+    def __init__(self):
+        self.pending = []   # (path, meta, shape, has kept mass, has density, has flag, has timestep, pinned host tensor, event)
+
+    def push(self, path: str, meta: dict, figures: dict, density=None, dense_flag=None, timestep=None) -> None:
+        """timestep: a device tensor whose first element is the record's timestep, read with the figures (no read-back on the host)"""
+        rel = figures["rel_l2"]
+        parts = [rel.float().reshape(-1), figures["mse"].float().reshape(-1)]
+        kept = figures.get("kept_mass")
+        if kept is not None:
+            parts.append(kept.float().reshape(-1))
+        if density is not None:
+            parts.append(density.float().reshape(-1))
+        if dense_flag is not None:
+            parts.append(dense_flag.reshape(-1)[:1].float())
+        if timestep is not None:
+            parts.append(timestep.reshape(-1)[:1].float())
+        flat = torch.cat(parts)
+        host = _native.empty(flat.shape, dtype=torch.float32, pin_memory=flat.is_cuda)
+        host.copy_(flat, non_blocking=True)
+        ev = None
+        if flat.is_cuda:
+            ev = torch.cuda.Event()
+            ev.record()
+        self.pending.append((path, meta, tuple(rel.shape), kept is not None, density is not None, dense_flag is not None,
+                             timestep is not None, host, ev))
+        self.flush(wait=False)
+
+    def flush(self, wait: bool = True) -> None:
+        while self.pending:
+            path, meta, shape, has_kept, has_density, has_flag, has_ts, host, ev = self.pending[0]
+            if ev is not None:
+                if wait:
+                    ev.synchronize()
+                elif not ev.query():
+                    return
+            n = 1
+            for s in shape:
+                n *= s
+            take = lambda i: host[i * n:(i + 1) * n].reshape(shape).tolist()   # noqa: E731
+            if not (has_flag and float(host[-1 - int(has_ts)]) != 0.0):
+                if has_ts:
+                    meta = dict(meta, timestep=float(host[-1]))
+                entry = dict(meta, rel_l2=take(0), mse=take(1), kept_mass=take(2) if has_kept else None)
+                if has_density:
+                    entry["density"] = take(2 + int(has_kept))
+                with open(path, "a") as f:
+                    f.write(json.dumps(entry) + "\n")
+            self.pending.pop(0)
+
+
+QUALITY_LOG = _QualityLog()
+
+
+def flush_quality_log() -> None:
+    """Write every pending quality record (see _QualityLog)."""
+    QUALITY_LOG.flush(wait=True)
+
+
+atexit.register(flush_quality_log)
+
+
+def log_quality(quality: QualityRequest, out: torch.Tensor, lse, q, k, v, q_prescaled: bool = False, dense_flag=None, density=None) -> None:
+    """Probe one sparse layer-call (out [cfg, H, S, D] in either storage order, lse [cfg, H, S] or None) and queue its record.  Rows:
+    uniform over the valid rows of the sequence, from the probe's own CPU generator.  Videos whose valid lengths differ are probed group by
+    group (video_groups), one native call per group."""
+    from .context import timestep_value
+
+    cfg, H, S, D = q.shape
+    out = out.reshape(cfg, H, S, D)
+    lse = None if lse is None else lse.reshape(cfg, H, S)
+    lens = per_video(quality.valid_len, cfg, "quality probe(valid_len)")
+    vals, counts = video_groups(lens if lens is not None else [quality.valid_len] * cfg)
+    figs, b0 = [], 0
+    for vl, nb in zip(vals, counts):
+        vl = None if vl is None or int(vl) <= 0 or int(vl) >= S else int(vl)
+        n_valid = S if vl is None else vl
+        rows = torch.randint(low=0, high=n_valid, size=(max(1, min(int(quality.rows), 64)),), generator=_probe_generator())
+        sl = slice(b0, b0 + nb)
+        figs.append(sparse_quality(out[sl], None if lse is None else lse[sl], q[sl], k[sl], v[sl], rows, vl, LN2 if q_prescaled else None))
+        b0 += nb
+    fig = {key: (None if figs[0][key] is None else torch.cat([f[key] for f in figs])) for key in figs[0]}
+    ts = quality.timestep
+    on_device = torch.is_tensor(ts) and ts.is_cuda   # (the switched path never reads the timestep back: it travels with the figures)
+    meta = {"timestep": None if ts is None or on_device else timestep_value(ts), "layer": quality.layer}
+    QUALITY_LOG.push(quality.path, meta, fig, density=density, dense_flag=dense_flag, timestep=ts if on_device else None)
 
 
 _SMALL_TENSORS = {}   # (values, dtype, device) -> tensor: a batch's prompt lengths, uploaded once and not once per layer-call

@@ -56,6 +56,11 @@ class CogVideoX_SparseAttn_Processor2_0:
     fused_placement = True
     device_switch = True    # dense / sparse decision on the device when the timestep is a GPU tensor
     prescale_q = False      # opt-in (flex_attention's PRESCALE_QK trade-off, see Hunyuan's processor): the HIP RoPE pass folds sm_scale * log2(e) into its rounding of q
+    # quality probe (svg/models/_core.py log_quality): a path -> every sparse layer-call is also set against dense attention on
+    # `quality_rows` sampled rows per head and appends one JSON line {"timestep", "layer", "rel_l2", "mse", "kept_mass", "density"?} to the
+    # file (deferred writes: flush_quality_log()).  None: nothing changes.  Refused under svg.distributed.
+    quality_log = None
+    quality_rows = 64
 
     def __init__(self, layer_idx):
         self.layer_idx = layer_idx
@@ -106,6 +111,7 @@ class CogVideoX_SparseAttn_Processor2_0:
             f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
         # ref :173-176 — Cog's warm-up thresholds are fractions of 42 layers / 1000 timesteps
         first_layers, first_times = 42 * self.first_layers_fp, 1000 * (1 - self.first_times_fp)
+        quality = _core.quality_request(type(self).__name__, self.quality_log, self.quality_rows, None, timestep, self.layer_idx)
         dense_flag = None   # (device-side dense / sparse switch, see the Hunyuan processor)
         if self.device_switch and _core.attention_dtype() == "bf16" and self.fused_placement and self.layer_idx >= first_layers and self.block_mask is not None \
                 and query.is_cuda:
@@ -118,11 +124,12 @@ class CogVideoX_SparseAttn_Processor2_0:
         total = geo.seq_len   # (seq_len, except in token-shard mode: the masks and the sampled rows are the whole sequence's)
         if dense_flag is not None:
             out, best = _core.svg1_attention_device_switch(query, key, value, geo, self.block_mask, dense_mask(total), prof,
-                                                           self.num_sampled_rows, total, dense_flag, q_prescaled=self._q_prescaled)
+                                                           self.num_sampled_rows, total, dense_flag, q_prescaled=self._q_prescaled,
+                                                           quality=quality)
             self.last_best_mask_idx = best
             return out.reshape(cfg, num_heads, seq_len, dim)
         out, best = _core.svg1_sparse_attention(query, key, value, geo, self.block_mask, prof, self.num_sampled_rows, total,
-                                                fused=self.fused_placement, q_prescaled=self._q_prescaled)
+                                                fused=self.fused_placement, q_prescaled=self._q_prescaled, quality=quality)
         self.last_best_mask_idx = best
         return out.reshape(cfg, num_heads, seq_len, dim)
 

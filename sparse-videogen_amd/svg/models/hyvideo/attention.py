@@ -284,6 +284,11 @@ class Hunyuan_SVGAttn_Processor2_0(_HunyuanProcessorBase):
     # the text behind them; the masks, the profiler and the sampled rows stay those of the whole sequence.  False (SVG2): refused.
     frame_shard_form = True
     prescale_q = False      # opt-in (flex_attention's PRESCALE_QK trade-off, see _HunyuanProcessorBase.prescale_q): q leaves the fused prologue carrying the softmax scale
+    # quality probe (svg/models/_core.py log_quality): a path -> every sparse layer-call is also set against dense attention on
+    # `quality_rows` sampled rows per head and appends one JSON line {"timestep", "layer", "rel_l2", "mse", "kept_mass", "density"?} to the
+    # file (deferred writes: flush_quality_log()).  None: nothing changes.  Refused under svg.distributed.
+    quality_log = None
+    quality_rows = 64
 
     def __init__(self, layer_idx):
         super().__init__(layer_idx)
@@ -308,6 +313,7 @@ class Hunyuan_SVGAttn_Processor2_0(_HunyuanProcessorBase):
             f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
         total = geo.seq_len   # (seq_len, except in frame-shard mode: the masks and the sampled rows are the whole sequence's)
         valid = self.video_valid_lens(cu_max_seqlens, cfg, geo.video_length)
+        quality = _core.quality_request(type(self).__name__, self.quality_log, self.quality_rows, valid, timestep, self.layer_idx)
         # the layer test is host data; the timestep test stays on the device when the timestep is a GPU tensor (device_switch)
         dense_flag = None
         if self.device_switch and _core.attention_dtype() == "bf16" and self.fused_placement and self.layer_idx >= self.first_layers_fp and self.block_mask is not None \
@@ -326,11 +332,12 @@ class Hunyuan_SVGAttn_Processor2_0(_HunyuanProcessorBase):
             dense = tuple(dense_mask(total, int(x)) for x in valid) if isinstance(valid, tuple) else dense_mask(total, int(valid))
             out, best = _core.svg1_attention_device_switch(query, key, value, geo, mask, dense, prof,
                                                            self.num_sampled_rows, min(self.sample_mse_max_row, total), dense_flag,
-                                                           q_prescaled=pre)
+                                                           q_prescaled=pre, quality=quality)
             self.last_best_mask_idx = best
             return out.reshape(cfg, num_heads, seq_len, dim)
         out, best = _core.svg1_sparse_attention(query, key, value, geo, mask, prof, self.num_sampled_rows,
-                                                min(self.sample_mse_max_row, total), fused=self.fused_placement, q_prescaled=pre)
+                                                min(self.sample_mse_max_row, total), fused=self.fused_placement, q_prescaled=pre,
+                                                quality=quality)
         self.last_best_mask_idx = best
         return out.reshape(cfg, num_heads, seq_len, dim)
 
@@ -376,6 +383,7 @@ class Hunyuan_SAPAttn_Processor2_0(Hunyuan_SVGAttn_Processor2_0):
         assert seq_len == _core.rows_of_this_rank(type(self).__name__, geo, self.frame_shard_form), (
             f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
         valid = self.video_valid_lens(cu_max_seqlens, cfg, geo.video_length)
+        quality = _core.quality_request(type(self).__name__, self.quality_log, self.quality_rows, valid, timestep, self.layer_idx)
         if _core.is_full_attention(self.layer_idx, timestep, self.first_layers_fp, self.first_times_fp):
             if self.zero_step_kmeans_init and query.is_cuda:
                 V = geo.video_length
@@ -386,7 +394,7 @@ class Hunyuan_SAPAttn_Processor2_0(Hunyuan_SVGAttn_Processor2_0):
         out = _core.svg2_sparse_attention(query, key, value, geo, self.centroid_store, layer_idx, self.num_q_centroids,
                                           self.num_k_centroids, self.top_p_kmeans, self.min_kc_ratio, self.kmeans_iter_init,
                                           self.kmeans_iter_step, prompt_length=self.prompt_length if isinstance(self.prompt_length, tuple) else int(self.prompt_length),
-                                          logging_file=self.logging_file, timestep=timestep)
+                                          logging_file=self.logging_file, timestep=timestep, quality=quality)
         return out.reshape(cfg, num_heads, seq_len, dim)
 
 

@@ -242,6 +242,11 @@ class WanAttn_SVGAttn_Processor2_0:
     # frame-shard mode (svg.distributed.enable_frame_shards): query, key, value hold all heads of this rank's whole frames; the masks, the
     # profiler and the sampled rows stay those of the whole sequence (geometry()).  False (SVG2, Cosmos): the mode is refused.
     frame_shard_form = True
+    # quality probe (svg/models/_core.py log_quality): a path -> every sparse layer-call is also set against dense attention on
+    # `quality_rows` sampled rows per head and appends one JSON line {"timestep", "layer", "rel_l2", "mse", "kept_mass", "density"?} to the
+    # file (deferred writes: flush_quality_log()).  None: nothing changes.  Refused under svg.distributed.
+    quality_log = None
+    quality_rows = 64
 
     @time_logging_decorator("Level 3 - Dense Flash Attention")
     def flash_attention(self, query, key, value):
@@ -254,6 +259,7 @@ class WanAttn_SVGAttn_Processor2_0:
         assert seq_len == _core.rows_of_this_rank(type(self).__name__, geo, self.frame_shard_form), (
             f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
         total = geo.seq_len   # (seq_len, except in frame-shard mode: the masks and the sampled rows are the whole sequence's)
+        quality = _core.quality_request(type(self).__name__, self.quality_log, self.quality_rows, None, timestep, self.layer_idx)
         dense_flag = None   # (device-side dense / sparse switch, see the Hunyuan processor)
         if self.device_switch and _core.attention_dtype() == "bf16" and self.fused_placement and self.layer_idx >= self.first_layers_fp and self.block_mask is not None \
                 and query.is_cuda:
@@ -266,12 +272,12 @@ class WanAttn_SVGAttn_Processor2_0:
         if dense_flag is not None:
             out, best = _core.svg1_attention_device_switch(query, key, value, geo, self.block_mask, dense_mask(total), prof,
                                                            self.num_sampled_rows, min(self.sample_mse_max_row, total), dense_flag,
-                                                           q_prescaled=self._q_prescaled)
+                                                           q_prescaled=self._q_prescaled, quality=quality)
             self.last_best_mask_idx = best
             return out.reshape(cfg, num_heads, seq_len, dim)
         out, best = _core.svg1_sparse_attention(query, key, value, geo, self.block_mask, prof, self.num_sampled_rows,
                                                 min(self.sample_mse_max_row, total), fused=self.fused_placement,
-                                                q_prescaled=self._q_prescaled)
+                                                q_prescaled=self._q_prescaled, quality=quality)
         self.last_best_mask_idx = best
         return out.reshape(cfg, num_heads, seq_len, dim)
 
@@ -325,6 +331,7 @@ class WanAttn_SAPAttn_Processor(WanAttn_SVGAttn_Processor2_0):
         geo = self.geometry()
         assert seq_len == _core.rows_of_this_rank(type(self).__name__, geo, self.frame_shard_form), (
             f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
+        quality = _core.quality_request(type(self).__name__, self.quality_log, self.quality_rows, None, timestep, self.layer_idx)
         if _core.is_full_attention(self.layer_idx, timestep, self.first_layers_fp, self.first_times_fp):
             if self.zero_step_kmeans_init and query.is_cuda:
                 V = geo.video_length
@@ -334,5 +341,5 @@ class WanAttn_SAPAttn_Processor(WanAttn_SVGAttn_Processor2_0):
         out = _core.svg2_sparse_attention(query, key, value, geo, self.centroid_store, self.layer_idx, self.num_q_centroids,
                                           self.num_k_centroids, self.top_p_kmeans, self.min_kc_ratio, self.kmeans_iter_init,
                                           self.kmeans_iter_step, prompt_length=0, logging_file=self.logging_file,
-                                          timestep=timestep)
+                                          timestep=timestep, quality=quality)
         return out.reshape(cfg, num_heads, seq_len, dim)
