@@ -21,10 +21,15 @@ namespace svg {
 
 constexpr int kDynThreads = 256;
 
-template <typename T, int D>
+// top_p of a launch: one scalar for every head (svg_identify_dynamic_map), or a device vector with one entry per head
+// (svg_identify_dynamic_map_per_head).  Either way the kernel rounds the head's value to the input dtype (p_cmp) before the compares.
+__device__ __forceinline__ float top_p_of(float p, int) { return p; }
+__device__ __forceinline__ float top_p_of(const float* p, int bh) { return p[bh]; }
+
+template <typename T, int D, typename P = float>
 __global__ __launch_bounds__(kDynThreads) void dynmap_kernel(const T* __restrict__ qc, const T* __restrict__ kc,
                                                              const int32_t* __restrict__ k_sizes, uint8_t* __restrict__ out,
-                                                             int QC, int KC, float sqrt_d, float top_p,
+                                                             int QC, int KC, float sqrt_d, P top_p,
                                                              int preserve) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // LDS: keys[N2] u64 (sort keys; N2 = KC rounded up to a power of two), prob[KC] f64
@@ -124,7 +129,7 @@ __global__ __launch_bounds__(kDynThreads) void dynmap_kernel(const T* __restrict
     //    on a 16-bit tensor).  The prefix is non-decreasing, so everything after the first position whose previous prefix
     //    exceeds p is dropped: one lane walks only that far.
     if (tid == 0) {
-        const float p_cmp = Elt<T>::to_float(Elt<T>::from_float(top_p));
+        const float p_cmp = Elt<T>::to_float(Elt<T>::from_float(top_p_of(top_p, bh)));
         float acc = 0.f, prev_cum = 0.f;
         int r = 0;
         bool done = false;
@@ -206,9 +211,9 @@ __device__ __forceinline__ void wave_bitonic_sort(unsigned (&key)[E], int lane) 
     }
 }
 
-template <typename T, int D>
+template <typename T, int D, typename P = float>
 __global__ __launch_bounds__(64 * kDyn2Waves) void dynmap16_kernel(const T* __restrict__ qc, const T* __restrict__ kc, const int32_t* __restrict__ k_sizes,
-                                                       uint8_t* __restrict__ out, int QC, int KC, float sqrt_d, float top_p, int preserve) {
+                                                       uint8_t* __restrict__ out, int QC, int KC, float sqrt_d, P top_p, int preserve) {
     constexpr int CH = D / 4;                           // contraction elements of a lane group
     __shared__ unsigned short sc16[kDyn2Rows][kDyn2N];  // rounded scores as bit patterns of T
     __shared__ unsigned sorted[kDyn2Waves][kDyn2N];     // a wave's sorted keys (for the walk and the scatter)
@@ -293,7 +298,7 @@ __global__ __launch_bounds__(64 * kDyn2Waves) void dynmap16_kernel(const T* __re
         __builtin_amdgcn_wave_barrier();
         int cut = 0;
         if (lane == 0) {   // the cumulative sum of the first form, on 32-bit keys
-            const float p_cmp = Elt<T>::to_float(Elt<T>::from_float(top_p));
+            const float p_cmp = Elt<T>::to_float(Elt<T>::from_float(top_p_of(top_p, bh)));
             float acc = 0.f, prev_cum = 0.f;
             int r = 0;
             bool done = false;
@@ -331,10 +336,10 @@ __global__ __launch_bounds__(64 * kDyn2Waves) void dynmap16_kernel(const T* __re
 
 using namespace svg;
 
-extern "C" int svg_identify_dynamic_map(const void* qc, const void* kc, const int32_t* k_sizes, uint8_t* out_map, int32_t BH,
-                                        int32_t QC, int32_t KC, int32_t D, int32_t dtype, float top_p,
-                                        int32_t preserve_length, void* stream) {
-    if (!qc || !kc || !k_sizes || !out_map || BH <= 0 || QC <= 0 || KC <= 0) return SVG_ERR_BAD_ARG;
+// the launch of both entries: P = float (one top_p) or const float* (one per head)
+template <typename P>
+static int launch_dynmap(const void* qc, const void* kc, const int32_t* k_sizes, uint8_t* out_map, int32_t BH, int32_t QC, int32_t KC,
+                         int32_t D, int32_t dtype, P top_p, int32_t preserve_length, void* stream) {
     if (KC > 4096) return SVG_ERR_UNSUPPORTED;
     // LDS: keys[N2] u64 (N2 = KC rounded up to a power of two) + prob[KC] f64
     int n2 = 2;
@@ -347,7 +352,7 @@ extern "C" int svg_identify_dynamic_map(const void* qc, const void* kc, const in
     if (KC > 256 && KC <= kDyn2N) {   // (small maps: the first form sorts the next power of two of KC, this one always 1024 keys)
         dim3 grid16((QC + kDyn2Rows - 1) / kDyn2Rows, BH);
 #define SVG_DYN16(T, DD) \
-    hipLaunchKernelGGL((dynmap16_kernel<T, DD>), grid16, dim3(64 * kDyn2Waves), 0, st, (const T*)qc, (const T*)kc, k_sizes, out_map, QC, KC, inv, top_p, preserve_length)
+    hipLaunchKernelGGL((dynmap16_kernel<T, DD, P>), grid16, dim3(64 * kDyn2Waves), 0, st, (const T*)qc, (const T*)kc, k_sizes, out_map, QC, KC, inv, top_p, preserve_length)
         if (dtype == SVG_DTYPE_BF16 && D == 128) SVG_DYN16(__bf16, 128);
         else if (dtype == SVG_DTYPE_BF16 && D == 64) SVG_DYN16(__bf16, 64);
         else if (dtype == SVG_DTYPE_F16 && D == 128) SVG_DYN16(_Float16, 128);
@@ -357,7 +362,7 @@ extern "C" int svg_identify_dynamic_map(const void* qc, const void* kc, const in
         return launch_status();
     }
 #define SVG_DYN(T, DD)                                                                                                   \
-    hipLaunchKernelGGL((dynmap_kernel<T, DD>), grid, dim3(kDynThreads), lds, st, (const T*)qc, (const T*)kc, k_sizes, out_map, \
+    hipLaunchKernelGGL((dynmap_kernel<T, DD, P>), grid, dim3(kDynThreads), lds, st, (const T*)qc, (const T*)kc, k_sizes, out_map, \
                        QC, KC, inv, top_p, preserve_length)
     if (dtype == SVG_DTYPE_BF16 && D == 128) SVG_DYN(__bf16, 128);
     else if (dtype == SVG_DTYPE_BF16 && D == 64) SVG_DYN(__bf16, 64);
@@ -366,4 +371,19 @@ extern "C" int svg_identify_dynamic_map(const void* qc, const void* kc, const in
     else return SVG_ERR_UNSUPPORTED;
 #undef SVG_DYN
     return launch_status();
+}
+
+extern "C" int svg_identify_dynamic_map(const void* qc, const void* kc, const int32_t* k_sizes, uint8_t* out_map, int32_t BH,
+                                        int32_t QC, int32_t KC, int32_t D, int32_t dtype, float top_p,
+                                        int32_t preserve_length, void* stream) {
+    if (!qc || !kc || !k_sizes || !out_map || BH <= 0 || QC <= 0 || KC <= 0) return SVG_ERR_BAD_ARG;
+    return launch_dynmap<float>(qc, kc, k_sizes, out_map, BH, QC, KC, D, dtype, top_p, preserve_length, stream);
+}
+
+// include/svg_attn_adaptive_top_p.h
+extern "C" int svg_identify_dynamic_map_per_head(const void* qc, const void* kc, const int32_t* k_sizes, uint8_t* out_map, int32_t BH,
+                                                 int32_t QC, int32_t KC, int32_t D, int32_t dtype, const float* top_p,
+                                                 int32_t preserve_length, void* stream) {
+    if (!qc || !kc || !k_sizes || !out_map || !top_p || BH <= 0 || QC <= 0 || KC <= 0) return SVG_ERR_BAD_ARG;
+    return launch_dynmap<const float*>(qc, kc, k_sizes, out_map, BH, QC, KC, D, dtype, top_p, preserve_length, stream);
 }

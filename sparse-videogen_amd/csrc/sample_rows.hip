@@ -45,7 +45,10 @@ static int sample_rows_chunks(int BH, int S) {
     return n;
 }
 
-template <typename T, int D>
+// kWithV = false (svg_sample_dense_lse, include/svg_attn_adaptive_top_p.h): the K-only half — no V request, no PV MFMAs, no O accumulators,
+// one LDS image per stage; the partial of a row is (m, l) alone, [BH][n_chunks][R][2].  Everything the log-sum-exp is made of — the tiles,
+// the scores, the running maximum, the row sum — is the same statement, so that both forms give the same lse bits.
+template <typename T, int D, bool kWithV = true>
 __global__ __launch_bounds__(256, 2) void sample_rows_kernel(SampleRowsParams<T> prm) {
     using Acc = SampleRowsAccess;
     using E = Elt<T>;
@@ -53,7 +56,7 @@ __global__ __launch_bounds__(256, 2) void sample_rows_kernel(SampleRowsParams<T>
     using V8 = typename E::v8;
     constexpr int KS = D / 32, NDB = D / 16;
     using Img = KvImage16<D>;
-    constexpr int kImg = Img::kImg, kStage = Img::kStage;
+    constexpr int kImg = Img::kImg, kStage = kWithV ? Img::kStage : Img::kImg;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int head = blockIdx.x, chunk = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
@@ -63,7 +66,7 @@ __global__ __launch_bounds__(256, 2) void sample_rows_kernel(SampleRowsParams<T>
     const int nT = max(0, min(prm.tiles_per_chunk, ntiles - t0));
     const T* __restrict__ qb = Acc::q_at(prm, head);
     const T* __restrict__ kb_ = Acc::k_at(prm, head);
-    const T* __restrict__ vb = Acc::v_at(prm, head);
+    const T* __restrict__ vb = kWithV ? Acc::v_at(prm, head) : nullptr;
 
     // this lane's sampled row (rows >= R do not exist: they read row 0 and are never stored) and the keys it sees
     const int r = wave * 16 + n16;
@@ -79,7 +82,7 @@ __global__ __launch_bounds__(256, 2) void sample_rows_kernel(SampleRowsParams<T>
     const unsigned lds0 = (unsigned)(size_t)smem;
     const unsigned col_v = Img::col_v(lane);
     const int krow = 16 * wave + (lane >> 2);
-    const unsigned k_rsb = (unsigned)Acc::k_rs(prm) * 2u, v_rsb = (unsigned)Acc::v_rs(prm) * 2u;
+    const unsigned k_rsb = (unsigned)Acc::k_rs(prm) * 2u, v_rsb = kWithV ? (unsigned)Acc::v_rs(prm) * 2u : 0u;
     auto dma_tile = [&](int t) {
         const int l = (t0 + t) * kBN + krow;
         const unsigned nphys = (unsigned)(l < prm.S ? l : 0);    // rows behind the keys: row 0 in their place, masked by index below
@@ -87,8 +90,12 @@ __global__ __launch_bounds__(256, 2) void sample_rows_kernel(SampleRowsParams<T>
         for (int j = 0; j < D / 32; ++j) {
             const unsigned st = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)((t & 1) * kStage) + (unsigned)(j * (kBN * 64) + wave * 1024));
             const unsigned ko = __umul24(nphys, k_rsb) + ((unsigned)(j * 64) | col_v);
-            const unsigned vo = __umul24(nphys, v_rsb) + ((unsigned)(j * 64) | col_v);
-            lds_dma16_kv<kImg>(st, ko, vo, kb_, vb);
+            if constexpr (kWithV) {
+                const unsigned vo = __umul24(nphys, v_rsb) + ((unsigned)(j * 64) | col_v);
+                lds_dma16_kv<kImg>(st, ko, vo, kb_, vb);
+            } else {
+                lds_dma16(st, ko, kb_);
+            }
         }
     };
     const int k_lane = Img::k_lane(g4, n16);
@@ -159,10 +166,12 @@ __global__ __launch_bounds__(256, 2) void sample_rows_kernel(SampleRowsParams<T>
                 const float alpha = (m_new == -INFINITY) ? 1.f : __builtin_amdgcn_exp2f(m_run - m_new);   // (-inf -> finite: 2^-inf = 0)
                 m_run = m_new;
                 l_run *= alpha;
+                if constexpr (kWithV) {
 #pragma unroll
-                for (int db = 0; db < NDB; ++db)
+                    for (int db = 0; db < NDB; ++db)
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[db][j] *= alpha;
+                        for (int j = 0; j < 4; ++j) acc[db][j] *= alpha;
+                }
             }
             const float m_use = (m_run == -INFINITY) ? 0.f : m_run;   // a row that has seen no key yet: every p is 2^-inf = 0
             // ---- probabilities: the P fragment is the lane's score accumulators of key blocks 2 kc, 2 kc + 1 ----
@@ -173,10 +182,10 @@ __global__ __launch_bounds__(256, 2) void sample_rows_kernel(SampleRowsParams<T>
                 for (int j = 0; j < 4; ++j) {
                     const float p = __builtin_amdgcn_exp2f(sc[b][j] - m_use);
                     l_run += p;
-                    pf[b >> 1][4 * (b & 1) + j] = E::from_float(p);
+                    if constexpr (kWithV) pf[b >> 1][4 * (b & 1) + j] = E::from_float(p);
                 }
             // ---- O^T += V^T P^T: V^T fragments in groups of four 16-wide d-blocks, two groups in flight ----
-            {
+            if constexpr (kWithV) {
                 constexpr int G = 4, NG = 2 * NDB / G;
                 V8 vf[2][G];
 #pragma unroll
@@ -199,7 +208,12 @@ __global__ __launch_bounds__(256, 2) void sample_rows_kernel(SampleRowsParams<T>
     }
     // ---- the chunk's partial of the row: the four lanes of a row hold 4 + 4 + 4 + 4 keys of every 16-key block ----
     const float l_tot = quad_group_sum(l_run);
-    if (have) {
+    if constexpr (!kWithV) {
+        if (have && g4 == 0) {
+            float2* dst = (float2*)prm.part + ((size_t)head * prm.n_chunks + chunk) * prm.R + r;
+            *dst = float2{m_run, l_tot};
+        }
+    } else if (have) {
         float* dst = prm.part + (((size_t)head * prm.n_chunks + chunk) * prm.R + r) * (D + 4);
 #pragma unroll
         for (int db = 0; db < NDB; ++db) *(f32x4*)(dst + 16 * db + 4 * g4) = acc[db];
@@ -231,6 +245,59 @@ __global__ __launch_bounds__(D) void sample_rows_combine_kernel(const float* __r
     const bool seen = L > 0.f;
     o32[((size_t)h * R + r) * D + d] = seen ? O / L : 0.f;
     if (d == 0) lse[(size_t)h * R + r] = seen ? 0.6931471805599453f * (Mx + log2f(L)) : -INFINITY;
+}
+
+// The combine of the K-only form: grid = BH, block = 64, thread r = sampled row r.  M, the weights and L as above.
+__global__ __launch_bounds__(kSampleMaxRows) void sample_lse_combine_kernel(const float2* __restrict__ part, float* __restrict__ lse, int R,
+                                                                            int n_chunks) {
+    const int r = threadIdx.x, h = blockIdx.x;
+    if (r >= R) return;
+    const float2* base = part + (size_t)h * n_chunks * R + r;
+    float Mx = -INFINITY;
+    for (int c = 0; c < n_chunks; ++c) Mx = fmaxf(Mx, base[(size_t)c * R].x);
+    // L with the arithmetic sample_rows_combine_kernel is COMPILED to, stated here and fenced so that it stays: the file is built with fast
+    // math, and hipcc vectorises that kernel's chunk loop by two — the even chunks and the odd chunks are summed apart by fused
+    // multiply-adds, the two sums added, an odd last chunk fused in behind them.  Still a fixed order, a function of n_chunks alone; the
+    // same source without the fence leaves the choice to the compiler, kernel by kernel, and the two lse would differ in the last bit.
+    float L;
+    {
+#pragma clang fp reassociate(off) contract(off)
+        auto weighted = [&](int c, float acc) {
+            const float2 ml = base[(size_t)c * R];
+            const float w = (ml.x == -INFINITY) ? 0.f : exp2f(ml.x - Mx);
+            return __builtin_fmaf(ml.y, w, acc);
+        };
+        float L0 = 0.f, L1 = 0.f;
+        for (int c = 0; c + 1 < n_chunks; c += 2) {
+            L0 = weighted(c, L0);
+            L1 = weighted(c + 1, L1);
+        }
+        L = L0 + L1;
+        if (n_chunks & 1) L = weighted(n_chunks - 1, L);
+    }
+    lse[(size_t)h * R + r] = (L > 0.f) ? 0.6931471805599453f * (Mx + log2f(L)) : -INFINITY;
+}
+
+template <typename T, int D>
+static int run_sample_lse(const void* q, const void* k, const int64_t* rows, int R, int BH, int S, float sm_scale, int valid_len, float* lse,
+                          void* ws, const AttnLayout* lay, hipStream_t st) {
+    SampleRowsParams<T> p;
+    p.q = (const T*)q, p.k = (const T*)k, p.v = nullptr;
+    p.rows = rows;
+    p.S = S, p.BH = BH, p.R = R;
+    p.n_chunks = sample_rows_chunks(BH, S);
+    const int ntiles = (S + kBN - 1) / kBN;
+    p.tiles_per_chunk = (ntiles + p.n_chunks - 1) / p.n_chunks;
+    p.valid_len = (valid_len <= 0 || valid_len >= S) ? 0 : valid_len;
+    p.scale_log2 = sm_scale * 1.4426950408889634f;
+    p.lay = lay ? *lay : contiguous_layout(BH, BH, S, S, D);
+    p.part = (float*)ws;
+    constexpr int lds = 2 * KvImage16<D>::kImg;    // two stages of a K image
+    auto kern = sample_rows_kernel<T, D, false>;
+    if (const int rc = configure_lds((const void*)kern, lds); rc != SVG_OK) return rc;
+    hipLaunchKernelGGL(kern, dim3(BH, p.n_chunks), dim3(256), lds, st, p);
+    hipLaunchKernelGGL(sample_lse_combine_kernel, dim3(BH), dim3(kSampleMaxRows), 0, st, (const float2*)ws, lse, R, p.n_chunks);
+    return launch_status();
 }
 
 template <typename T, int D>
@@ -289,5 +356,38 @@ extern "C" int svg_sample_dense_rows(const void* q, const void* k, const void* v
     return dispatch_td(dtype, D, [&](auto t, auto d) {
         return run_sample_rows<decltype(t), decltype(d)::value>(q, k, v, rows, R, BH, S, sm_scale, valid_len, o32, lse, workspace, lay,
                                                                 (hipStream_t)stream);
+    });
+}
+
+// include/svg_attn_adaptive_top_p.h.  The bound of svg_sample_dense_rows_workspace_bytes with two words per row.
+extern "C" size_t svg_sample_dense_lse_workspace_bytes(int32_t BH, int32_t R, int32_t S) {
+    if (BH <= 0 || R <= 0 || S <= 0) return 0;
+    const size_t ntiles = ((size_t)S + kBN - 1) / kBN;
+    const size_t per_head = ntiles < 64 ? ntiles : 64;
+    const size_t round = (size_t)BH > 2 * kNumCU ? (size_t)BH : 2 * kNumCU;
+    const size_t terms = (size_t)BH * per_head < round ? (size_t)BH * per_head : round;
+    return ((terms * (size_t)R * 2 * sizeof(float)) + 15) & ~(size_t)15;
+}
+
+extern "C" int svg_sample_dense_lse(const void* q, const void* k, const int64_t* rows, int32_t R, int32_t BH, int32_t S, int32_t D,
+                                    int32_t dtype, float sm_scale, int32_t valid_len, float* lse, void* workspace, size_t workspace_bytes,
+                                    const svg_attn_layout_t* abi_layout, void* stream) {
+    if (!q || !k || !rows || !lse || !workspace) return SVG_ERR_BAD_ARG;
+    if (R < 1 || R > kSampleMaxRows || BH <= 0 || S <= 0) return SVG_ERR_BAD_ARG;
+    if (S >= (1 << 24) || (D > 0 && check_rows(S, D) != SVG_OK)) return SVG_ERR_UNSUPPORTED;
+    if (workspace_bytes < svg_sample_dense_lse_workspace_bytes(BH, R, S)) return SVG_ERR_WORKSPACE;
+    if (((size_t)workspace & 15) != 0) return SVG_ERR_UNSUPPORTED;
+    AttnLayout lay_storage;
+    const AttnLayout* lay = nullptr;
+    if (abi_layout) {   // (v and o are not tensors of this call: k and q stand in for them)
+        svg_attn_layout_t a = *abi_layout;
+        a.v = a.k;
+        a.o = a.q;
+        if (const int rc = layout_from_abi(&a, BH, BH, S, S, D, q, k, k, q, lay_storage); rc != SVG_OK) return rc;
+        lay = &lay_storage;
+    }
+    return dispatch_td(dtype, D, [&](auto t, auto d) {
+        return run_sample_lse<decltype(t), decltype(d)::value>(q, k, rows, R, BH, S, sm_scale, valid_len, lse, workspace, lay,
+                                                               (hipStream_t)stream);
     });
 }

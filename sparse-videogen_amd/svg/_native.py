@@ -336,6 +336,17 @@ SAMPLE_ROWS_SIGNATURES = {
                                         C.POINTER(AttnLayout), _VP]),
 }
 
+# include/svg_attn_adaptive_top_p.h: SVG2's per-head top-p — the block map from a device vector, the K-only probe, the controller step —, in
+# a table of its own for the same reason (tests/test_adaptive_top_p_cpu.py; allocating wrappers: svg/kmeans_utils.py identify_dynamic_map,
+# svg/_probe.py sample_dense_lse)
+ADAPTIVE_TOP_P_SIGNATURES = {
+    "svg_identify_dynamic_map_per_head": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _VP]),
+    "svg_sample_dense_lse_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
+    "svg_sample_dense_lse": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _F32, _I32, _VP, _VP, _SZ, C.POINTER(AttnLayout), _VP]),
+    "svg_top_p_update": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _F32, _F32, _F32, _F32, _F32, _F32, _VP, _VP, _VP]),
+}
+
+
 
 class CopyBox(C.Structure):
     """svg_copy_box_t (include/svg_attn_shard_exchange.h): extent[0] * extent[1] * extent[2] rows of D contiguous elements; offsets and
@@ -372,7 +383,8 @@ def load(strict: bool = True) -> Optional[C.CDLL]:
         lib = C.CDLL(str(p))
         for name, (res, args) in {**SIGNATURES, **SPARSE_LSE_SIGNATURES, **SPARSE_F32_SIGNATURES, **BAND_LSE_FORM_SIGNATURES,
                                    **BAND_WINDOW_SIGNATURES, **BAND_SHARD_SIGNATURES, **BAND_SHARD_SWITCH_SIGNATURES,
-                                   **PROFILE_SHARD_SIGNATURES, **SAMPLE_ROWS_SIGNATURES, **SHARD_EXCHANGE_SIGNATURES}.items():
+                                   **PROFILE_SHARD_SIGNATURES, **SAMPLE_ROWS_SIGNATURES, **SHARD_EXCHANGE_SIGNATURES,
+                                   **ADAPTIVE_TOP_P_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -1968,6 +1980,49 @@ def identify_dynamic_map(qc: torch.Tensor, kc: torch.Tensor, k_sizes: torch.Tens
                                       _dtype_code(qc), float(top_p), int(preserve_length), _stream())
     _check(rc, "svg_identify_dynamic_map")
     return out.view(torch.bool)
+
+
+def _f32_vector(what: str, t: torch.Tensor, n: int) -> None:
+    if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"{what}: a contiguous float32 tensor of {n} elements, got {t.dtype} {tuple(t.shape)}")
+
+
+def identify_dynamic_map_per_head(qc: torch.Tensor, kc: torch.Tensor, k_sizes: torch.Tensor, top_p: torch.Tensor, preserve_length: int,
+                                  out: torch.Tensor) -> torch.Tensor:
+    """identify_dynamic_map with one top_p per head: top_p a device float32 tensor of BH elements (svg_identify_dynamic_map_per_head).
+    out: uint8 [BH, QC, KC], written whole (the allocating caller is svg/kmeans_utils.py identify_dynamic_map) -> its bool view."""
+    BH, QC, D = qc.shape
+    KC = kc.shape[1]
+    _f32_vector("identify_dynamic_map_per_head(top_p)", top_p, BH)
+    if out.dtype != torch.uint8 or out.shape != (BH, QC, KC):
+        raise ValueError(f"identify_dynamic_map_per_head(out): uint8 {(BH, QC, KC)}, got {out.dtype} {tuple(out.shape)}")
+    lib = load()
+    _dev(qc, kc, k_sizes, top_p, out)
+    assert k_sizes.dtype == torch.int32 and k_sizes.shape == (BH, KC)
+    rc = lib.svg_identify_dynamic_map_per_head(qc.data_ptr(), kc.data_ptr(), k_sizes.data_ptr(), out.data_ptr(), BH, QC, KC, D,
+                                               _dtype_code(qc), top_p.data_ptr(), int(preserve_length), _stream())
+    _check(rc, "svg_identify_dynamic_map_per_head")
+    return out.view(torch.bool)
+
+
+def top_p_update(lse_sparse: torch.Tensor, rows: torch.Tensor, lse_dense: torch.Tensor, top_p: torch.Tensor, kept: torch.Tensor,
+                 target: float, gain_up: float, gain_down: float, band: float, p_min: float, p_max: float) -> None:
+    """The controller step (svg_top_p_update): lse_sparse fp32 [BH, S] (any leading shape), rows device int64 [R], lse_dense fp32 [BH, R];
+    kept fp32 [BH] is written, top_p fp32 [BH] stepped in place.  No allocation, no host synchronisation."""
+    if rows.dtype != torch.int64 or rows.dim() != 1 or not 1 <= rows.numel() <= 64:
+        raise ValueError(f"top_p_update: rows is an int64 vector of 1 to 64 rows, got {rows.dtype} {tuple(rows.shape)}")
+    R, BH = rows.numel(), top_p.numel()
+    _f32_vector("top_p_update(top_p)", top_p, BH)
+    _f32_vector("top_p_update(kept)", kept, BH)
+    if BH < 1 or lse_sparse.dtype != torch.float32 or lse_sparse.numel() % BH != 0 or lse_sparse.numel() == 0:
+        raise ValueError(f"top_p_update: lse_sparse is float32 [BH = {BH}, S], got {lse_sparse.dtype} {tuple(lse_sparse.shape)}")
+    _f32_vector("top_p_update(lse_dense)", lse_dense, BH * R)
+    lib = load()
+    _dev(lse_sparse, rows, lse_dense, top_p, kept)
+    rc = lib.svg_top_p_update(lse_sparse.data_ptr(), rows.data_ptr(), lse_dense.data_ptr(), R, BH, lse_sparse.numel() // BH, float(target),
+                              float(gain_up), float(gain_down), float(band), float(p_min), float(p_max), kept.data_ptr(), top_p.data_ptr(),
+                              _stream())
+    _check(rc, "svg_top_p_update")
 
 
 def map_density(block_map: torch.Tensor, q_sizes: torch.Tensor, k_sizes: torch.Tensor) -> torch.Tensor:

@@ -1,5 +1,6 @@
 """The quality probe's native op (include/svg_attn_sample_rows.h): dense attention of a few sampled query rows — fp32 rows and their row
-log-sum-exp — streamed in one pass over K and V.  svg/models/_core.py sparse_quality sets a sparse layer-call against it.
+log-sum-exp — streamed in one pass over K and V.  svg/models/_core.py sparse_quality sets a sparse layer-call against it.  Its K-only half,
+sample_dense_lse (include/svg_attn_adaptive_top_p.h), feeds the controller of the adaptive top-p.
 
 The allocating wrapper lives here, not in svg/_native.py: that module's public functions are the table of tests/test_gpu_poison.py.  Outputs
 and workspace come from _native.empty like every allocation of the package."""
@@ -56,3 +57,8 @@ def sample_dense_rows(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rows: t
                                    _native._stream())
     _native._check(rc, "svg_sample_dense_rows")
     return o32, lse
+
+
+
+# the K-only half of the probe (include/svg_attn_adaptive_top_p.h) lives in svg/_adaptive.py, beside what it feeds; it is reached from here too
+from ._adaptive import sample_dense_lse  # noqa: E402,F401

@@ -202,14 +202,22 @@ def weighted_softmax(scores, weights):
 
 @time_logging_decorator("Level 4 - identify dynamic map")
 def identify_dynamic_map(query_centroids, key_centroids, q_cluster_sizes, k_cluster_sizes, p, min_kc_ratio=0):
-    """ref: svg/kmeans_utils.py:864-896.  centroids [B, H, QC|KC, D], k_cluster_sizes [B, H, KC] -> bool [B, H, QC, KC]"""
+    """ref: svg/kmeans_utils.py:864-896.  centroids [B, H, QC|KC, D], k_cluster_sizes [B, H, KC] -> bool [B, H, QC, KC]
+    p: a float, as in the reference — or a device float32 tensor of B * H elements ([B, H]), one threshold per head: head h gets the map the
+    float p[h] gives it (svg_identify_dynamic_map_per_head; no read-back)."""
     B, H, QC, D = query_centroids.shape
     KC = key_centroids.shape[2]
+    if torch.is_tensor(p) and (p.dtype != torch.float32 or p.numel() != B * H):
+        raise ValueError(f"identify_dynamic_map: a tensor p is float32 [B, H] = {(B, H)}, got {p.dtype} {tuple(p.shape)}")
     assert query_centroids.is_cuda, "identify_dynamic_map requires GPU tensors"
     preserve = int(min_kc_ratio * KC) if min_kc_ratio > 0 else 0
-    m = _native.identify_dynamic_map(query_centroids.reshape(B * H, QC, D).contiguous(),
-                                     key_centroids.reshape(B * H, KC, D).contiguous(),
-                                     k_cluster_sizes.reshape(B * H, KC).to(torch.int32).contiguous(), float(p), preserve)
+    qc, kc = query_centroids.reshape(B * H, QC, D).contiguous(), key_centroids.reshape(B * H, KC, D).contiguous()
+    ks = k_cluster_sizes.reshape(B * H, KC).to(torch.int32).contiguous()
+    if torch.is_tensor(p):
+        out = _native.empty((B * H, QC, KC), dtype=torch.uint8, device=qc.device)
+        m = _native.identify_dynamic_map_per_head(qc, kc, ks, p.reshape(B * H).contiguous(), preserve, out)
+    else:
+        m = _native.identify_dynamic_map(qc, kc, ks, float(p), preserve)
     return m.reshape(B, H, QC, KC)
 
 

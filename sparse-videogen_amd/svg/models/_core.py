@@ -647,6 +647,108 @@ class CentroidStore:
         self.cfg.clear()
 
 
+class TopPStore:
+    """Per-layer state of the adaptive top-p (AdaptiveTopP), beside CentroidStore: `p[layer]`, an fp32 [cfg * H] DEVICE tensor — the
+    threshold of every head for the layer's NEXT sparse call, stepped in place by svg_top_p_update — and `kept[layer]`, fp32 [cfg * H], the
+    kept mass its last sparse call measured.  Nothing here is ever read back by the package.  A call with a different cfg * H (or on
+    another device) starts the layer again from the initial value; `clear()` forgets every layer (call between videos)."""
+
+    def __init__(self):
+        self.p = {}
+        self.kept = {}
+
+    def has(self, layer_idx, n=None) -> bool:
+        return layer_idx in self.p and (n is None or self.p[layer_idx].numel() == n)
+
+    def get(self, layer_idx, n: int, init: float, device) -> torch.Tensor:
+        """The layer's [n] thresholds; filled with `init` (and the last kept mass forgotten) where the layer has none of that size."""
+        t = self.p.get(layer_idx)
+        if t is None or t.numel() != n or t.device != torch.device(device):
+            t = torch.full((n,), float(init), dtype=torch.float32, device=device)
+            self.p[layer_idx] = t
+            self.kept.pop(layer_idx, None)
+        return t
+
+    def clear(self):
+        self.p.clear()
+        self.kept.clear()
+
+
+@dataclass
+class AdaptiveTopP:
+    """The SVG2 knob "keep this much attention mass": every head's top_p is steered, on the device, so that the kept mass measured after each
+    sparse layer-call — mean over probe rows of exp(lse_sparse - lse_dense) — approaches `target` (include/svg_attn_adaptive_top_p.h
+    svg_top_p_update):
+        e = target - kept;  step = gain_up * e if e > 0, gain_down * (e + band) if e < -band, else 0;  top_p = clamp(top_p + step, p_min, p_max)
+    A head below target is raised quickly, a head more than `band` above it is lowered slowly; inside the band nothing moves.  The first
+    sparse call of a layer runs with the processor's scalar top_p.
+    The default gains are UNTUNED: nobody has measured which suit a real model.  gain_up = gain_down = 0 measures and moves nothing.
+    rows: probe rows per head and call (1..64).  valid_len: the dense `valid` of the call as QualityRequest carries it (set by the
+    processors, per call)."""
+    target: float
+    gain_up: float = 1.0
+    gain_down: float = 0.25
+    band: float = 0.02
+    p_min: float = 0.1
+    p_max: float = 1.0
+    rows: int = 64
+    valid_len: object = None
+
+    def __post_init__(self):
+        ok = lambda x: x == x and x >= 0   # noqa: E731  (not NaN, not negative)
+        if not (ok(self.gain_up) and ok(self.gain_down) and ok(self.band)):
+            raise ValueError(f"AdaptiveTopP: gains and band are >= 0, got {self.gain_up}, {self.gain_down}, {self.band}")
+        if not 0 <= self.p_min <= self.p_max <= 1:
+            raise ValueError(f"AdaptiveTopP: 0 <= p_min <= p_max <= 1, got {self.p_min}, {self.p_max}")
+        if not 1 <= int(self.rows) <= 64:
+            raise ValueError(f"AdaptiveTopP: 1 to 64 probe rows, got {self.rows}")
+
+
+def _refuse_adaptive_when_sharded(what: str) -> None:
+    if _dist._STATE["enabled"] or _dist.frame_shards_active() or _dist.token_shards_active():
+        raise NotImplementedError(f"{what}: adaptive_top_p under svg.distributed (enable, enable_frame_shards, enable_token_shards) is not "
+                                  f"implemented: the probe reads whole heads of the whole sequence; unset adaptive_top_p or run on one GPU")
+
+
+def _refuse_adaptive_without_lse(what: str, q: torch.Tensor, block_rows: int) -> None:
+    """ValueError where the variable-block launch of this call has no LSE form with the plain call's o: there is no silent fall-back."""
+    S, D = q.shape[-2], q.shape[-1]
+    if D != 128 or _use_fp8(q) or q.dtype not in (torch.bfloat16, torch.float16) or S < 160 * block_rows:
+        raise ValueError(f"{what}(adaptive=...): the controller needs the row log-sum-exp of the sparse call — head_dim 128, bf16 / fp16 (not "
+                         f"fp8), S >= 160 block-rows; got D = {D}, {q.dtype}, fp8 = {_use_fp8(q)}, S = {S}, block-rows = {block_rows}")
+
+
+def probe_plan(valid_len, n_rows: int, cfg: int, S: int):
+    """The rows a layer-call is probed on: [(videos b0 .. b0 + nb, valid_len of the group or None, rows int64 [R] on the CPU)], one entry
+    per group of videos with one valid length (video_groups).  Rows: uniform over the valid rows, from the probe's own CPU generator."""
+    lens = per_video(valid_len, cfg, "quality probe(valid_len)")
+    vals, counts = video_groups(lens if lens is not None else [valid_len] * cfg)
+    plan, b0 = [], 0
+    for vl, nb in zip(vals, counts):
+        vl = None if vl is None or int(vl) <= 0 or int(vl) >= S else int(vl)
+        rows = torch.randint(low=0, high=S if vl is None else vl, size=(max(1, min(int(n_rows), 64)),), generator=_probe_generator())
+        plan.append((slice(b0, b0 + nb), vl, rows))
+        b0 += nb
+    return plan
+
+
+def adaptive_step(adaptive: AdaptiveTopP, top_p_store: TopPStore, layer_idx, p: torch.Tensor, lse: torch.Tensor, q, k, plan, lse_dense=None):
+    """After a sparse layer-call that ran with the thresholds p [cfg * H] (the store's tensor) and returned lse [cfg, H, S]: probe (K only;
+    lse_dense: what a quality probe on the same plan already measured, one [nb, H, R] per group), then svg_top_p_update — p is stepped in
+    place, the kept mass lands in the store.  No host synchronisation."""
+    from .. import _probe
+
+    cfg, H, S, _ = q.shape
+    lse = lse.reshape(cfg, H, S)
+    kept = _native.empty((cfg * H,), dtype=torch.float32, device=q.device)
+    for i, (sl, vl, rows) in enumerate(plan):
+        ld = lse_dense[i] if lse_dense is not None else _probe.sample_dense_lse(q[sl], k[sl], rows, vl)
+        hs = slice(sl.start * H, sl.stop * H)
+        _native.top_p_update(lse[sl], rows.to(q.device, non_blocking=True), ld, p[hs], kept[hs], adaptive.target, adaptive.gain_up,
+                             adaptive.gain_down, adaptive.band, adaptive.p_min, adaptive.p_max)
+    top_p_store.kept[layer_idx] = kept
+
+
 KMEANS_TWO_STREAMS = True    # q-side and k-side k-means loops on two streams (kmeans_clustering below); False: one after the other
 _SIDE_STREAMS = {}
 
@@ -729,7 +831,8 @@ def kmeans_clustering(store: CentroidStore, layer_idx: int, q_video, k_video, nu
 def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_idx: int, num_q_centroids: int,
                           num_k_centroids: int, top_p: float, min_kc_ratio: float, iter_init: int, iter_step: int,
                           prompt_length=0, logging_file: Optional[str] = None, timestep=None, _head_shard=None,
-                          quality: Optional["QualityRequest"] = None):
+                          quality: Optional["QualityRequest"] = None, adaptive: Optional[AdaptiveTopP] = None,
+                          top_p_store: Optional[TopPStore] = None):
     """The sparse branch of the SAP processors (ref: hyvideo/attention.py:747-804, wan/attention.py:529-559):
     k-means on the video tokens -> top-p block map -> (Hunyuan) two pseudo clusters for prompt / unused prompt ->
     variable-block attention with the token permutation fused in (the result is already in the original order).
@@ -739,9 +842,21 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
     head in the kernel already, so the videos still share one launch.
     quality: a QualityRequest (quality_request): the call is probed as well and its record, with the per-head densities, queued
     (log_quality).  The kept mass is logged where svg_varblock_attention_lse runs the body the plain call runs — head_dim 128, 16-bit,
-    block-rows large enough for the two-phase body (S >= 160 block-rows) — elsewhere the error alone.  Refused under svg.distributed."""
+    block-rows large enough for the two-phase body (S >= 160 block-rows) — elsewhere the error alone.  Refused under svg.distributed.
+    adaptive: an AdaptiveTopP, with top_p_store a TopPStore: the block map of this call is built from the store's per-head thresholds of
+    the layer (its first sparse call fills them with `top_p`), the attention runs its LSE form, K is probed on rows from the probe's
+    generator (neither the global RNG nor the switched path's generator moves) and svg_top_p_update steps the thresholds for the layer's
+    next call — all on the device, no host synchronisation.  With `quality` as well the rows are drawn once and its one dense probe feeds
+    both.  ValueError, before anything runs, where the launch has no LSE form (head_dim other than 128, fp8, S < 160 block-rows);
+    NotImplementedError under svg.distributed.  None: nothing changes."""
     if quality is not None:
         _refuse_quality_when_sharded("svg2_sparse_attention")
+    if adaptive is not None:
+        _refuse_adaptive_when_sharded("svg2_sparse_attention")
+        if top_p_store is None:
+            raise ValueError("svg2_sparse_attention(adaptive=...) needs a top_p_store (TopPStore): the thresholds live there between calls")
+        # (block-rows of the launch: the query clusters, and Hunyuan's two text pseudo-clusters behind them)
+        _refuse_adaptive_without_lse("svg2_sparse_attention", q, num_q_centroids + (2 if geo.context_length else 0))
     _require_gpu(q, "SVG2 sparse attention")
     pl = per_video(prompt_length, q.shape[0], "svg2_sparse_attention(prompt_length)")
     if pl is not None:
@@ -777,8 +892,9 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
                                                                          head_shard=_head_shard)
         q_sizes = qs.view(cfg, H, num_q_centroids)
         k_sizes = ks.view(cfg, H, num_k_centroids)
+        p_heads = None if adaptive is None else top_p_store.get(layer_idx, cfg * H, top_p, q.device)
         dyn_map = identify_dynamic_map(qc.view(cfg, H, num_q_centroids, D), kc.view(cfg, H, num_k_centroids, D), q_sizes,
-                                       k_sizes, top_p, min_kc_ratio)
+                                       k_sizes, top_p if adaptive is None else p_heads.view(cfg, H), min_kc_ratio)
     if ctx:
         with time_logging_decorator("Level 3 - dynamic map post processing"):
             dyn_map, q_sizes, k_sizes, qidx, kidx = dynamic_map_post_processing(dyn_map, q_sizes, k_sizes, qidx, kidx, V, ctx,
@@ -789,15 +905,22 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
     #  dynamic_map_post_processing — so the kernel writes every output row and the wrapper skips the zero fill)
     # (one launch over the cfg * H heads; the token-major output is [cfg, S, H, D] in memory: svg_attn_layout_t with heads_per_batch = H)
     # (the LSE entry always runs the two-phase 16x16x32 body; the plain call picks it from S >= 160 QB on: only there is its o the same)
-    probe_lse = quality is not None and _quality_lse_form(q, False) and S >= 160 * QB
+    probe_lse = adaptive is not None or (quality is not None and _quality_lse_form(q, False) and S >= 160 * QB)
     out = _native.varblock_attention(q, k, v, dyn_map.view(cfg * H, QB, KB).contiguous(),
                                      q_sizes.view(cfg * H, QB).contiguous(), k_sizes.view(cfg * H, KB).contiguous(),
                                      q_row_idx=qidx.contiguous(), kv_row_idx=kidx.contiguous(), fp8=f8,
                                      token_major_out=TOKEN_MAJOR_IO and (_head_shard is None or _dist.token_shards_active()),
                                      rows_covered=True, return_lse=probe_lse)
+    out, lse_p = out if probe_lse else (out, None)
+    plan = lse_d = None
+    if adaptive is not None:   # the rows of this call, drawn once: the quality probe below measures on them as well
+        valid = quality.valid_len if quality is not None else adaptive.valid_len
+        plan = probe_plan(valid, quality.rows if quality is not None else adaptive.rows, cfg, S)
     if quality is not None:
-        out, lse_p = out if probe_lse else (out, None)
-        log_quality(quality, out, lse_p, q, k, v, density=density_calculation(dyn_map, q_sizes, k_sizes))
+        lse_d = log_quality(quality, out, lse_p, q, k, v, density=density_calculation(dyn_map, q_sizes, k_sizes), plan=plan,
+                            top_p=None if adaptive is None else p_heads.clone())
+    if adaptive is not None:
+        adaptive_step(adaptive, top_p_store, layer_idx, p_heads, lse_p, q, k, plan, lse_d)
     if logging_file is not None:
         from .context import timestep_value
 
@@ -878,13 +1001,14 @@ def quality_figures(o_s: torch.Tensor, lse_s, o_d: torch.Tensor, lse_d: torch.Te
 
 
 def sparse_quality(o_sparse: torch.Tensor, lse_sparse, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rows: torch.Tensor, valid_len=None,
-                   sm_scale: Optional[float] = None) -> dict:
+                   sm_scale: Optional[float] = None, dense_lse_out: Optional[list] = None) -> dict:
     """A sparse attention result against dense attention on the sampled `rows` (int64 [R], R <= 64, CPU or device):
     {"rel_l2" [cfg, H]: sqrt(sum_rows |o_s - o_d|^2 / sum_rows |o_d|^2), "mse" [cfg, H]: mean squared difference over rows and D,
     "kept_mass" [cfg, H]: mean over rows of exp(lse_s - lse_d), None when lse_sparse is None} — device tensors, no host synchronisation.
     o_sparse [cfg, H, S, D] and lse_sparse [cfg, H, S] (or [cfg * H, S]) are the sparse call's FULL outputs in the caller's row order,
     head-major or token-major storage alike (views); the rows are gathered here.  q, k, v [cfg, H, S, D] views, valid_len as in
-    dense_attention (one int), sm_scale as in the attention wrappers (LN2 for a q that carries the softmax scale).  GPU only."""
+    dense_attention (one int), sm_scale as in the attention wrappers (LN2 for a q that carries the softmax scale).  GPU only.
+    dense_lse_out: a list that receives the probe's dense lse [cfg, H, R] (the adaptive top-p steers by it)."""
     from .. import _probe
 
     cfg, H, S, D = q.shape
@@ -892,6 +1016,8 @@ def sparse_quality(o_sparse: torch.Tensor, lse_sparse, q: torch.Tensor, k: torch
     idx = rows.to(q.device, non_blocking=True)
     o_s = o_sparse.reshape(cfg, H, S, D).index_select(2, idx) if o_sparse.dim() != 4 else o_sparse.index_select(2, idx)
     lse_s = None if lse_sparse is None else lse_sparse.reshape(cfg, H, S).index_select(2, idx)
+    if dense_lse_out is not None:
+        dense_lse_out.append(lse_d)
     return quality_figures(o_s, lse_s, o_d, lse_d)
 
 
@@ -956,10 +1082,11 @@ class _QualityLog:
     device-switch flag of a DENSE step is dropped: the host does not know the step's kind when it launches the probe."""
 
     def __init__(self):
-        self.pending = []   # (path, meta, shape, has kept mass, has density, has flag, has timestep, pinned host tensor, event)
+        self.pending = []   # (path, meta, shape, has kept mass, has density, has flag, has timestep, pinned host tensor, event[, has top_p])
 
-    def push(self, path: str, meta: dict, figures: dict, density=None, dense_flag=None, timestep=None) -> None:
-        """timestep: a device tensor whose first element is the record's timestep, read with the figures (no read-back on the host)"""
+    def push(self, path: str, meta: dict, figures: dict, density=None, dense_flag=None, timestep=None, top_p=None) -> None:
+        """timestep: a device tensor whose first element is the record's timestep, read with the figures (no read-back on the host).
+        top_p [cfg * H] (the adaptive SVG2 path): the thresholds the call ran with — the record gains a "top_p" list, and only then"""
         rel = figures["rel_l2"]
         parts = [rel.float().reshape(-1), figures["mse"].float().reshape(-1)]
         kept = figures.get("kept_mass")
@@ -967,6 +1094,8 @@ class _QualityLog:
             parts.append(kept.float().reshape(-1))
         if density is not None:
             parts.append(density.float().reshape(-1))
+        if top_p is not None:
+            parts.append(top_p.float().reshape(-1))
         if dense_flag is not None:
             parts.append(dense_flag.reshape(-1)[:1].float())
         if timestep is not None:
@@ -979,12 +1108,13 @@ class _QualityLog:
             ev = torch.cuda.Event()
             ev.record()
         self.pending.append((path, meta, tuple(rel.shape), kept is not None, density is not None, dense_flag is not None,
-                             timestep is not None, host, ev))
+                             timestep is not None, host, ev, top_p is not None))
         self.flush(wait=False)
 
     def flush(self, wait: bool = True) -> None:
         while self.pending:
-            path, meta, shape, has_kept, has_density, has_flag, has_ts, host, ev = self.pending[0]
+            path, meta, shape, has_kept, has_density, has_flag, has_ts, host, ev, *more = self.pending[0]
+            has_top_p = bool(more and more[0])   # (the thresholds of the adaptive SVG2 path, where the record carries them)
             if ev is not None:
                 if wait:
                     ev.synchronize()
@@ -1000,6 +1130,8 @@ class _QualityLog:
                 entry = dict(meta, rel_l2=take(0), mse=take(1), kept_mass=take(2) if has_kept else None)
                 if has_density:
                     entry["density"] = take(2 + int(has_kept))
+                if has_top_p:
+                    entry["top_p"] = take(2 + int(has_kept) + int(has_density))
                 with open(path, "a") as f:
                     f.write(json.dumps(entry) + "\n")
             self.pending.pop(0)
@@ -1016,30 +1148,28 @@ def flush_quality_log() -> None:
 atexit.register(flush_quality_log)
 
 
-def log_quality(quality: QualityRequest, out: torch.Tensor, lse, q, k, v, q_prescaled: bool = False, dense_flag=None, density=None) -> None:
+def log_quality(quality: QualityRequest, out: torch.Tensor, lse, q, k, v, q_prescaled: bool = False, dense_flag=None, density=None,
+                plan=None, top_p=None):
     """Probe one sparse layer-call (out [cfg, H, S, D] in either storage order, lse [cfg, H, S] or None) and queue its record.  Rows:
     uniform over the valid rows of the sequence, from the probe's own CPU generator.  Videos whose valid lengths differ are probed group by
-    group (video_groups), one native call per group."""
+    group (video_groups), one native call per group.
+    plan: the rows, where the caller has drawn them already (probe_plan); top_p [cfg * H]: the thresholds the call ran with, for the record
+    (the adaptive SVG2 path).  -> the dense lse of the probed rows, one [nb, H, R] per group, for a caller that steers by it."""
     from .context import timestep_value
 
     cfg, H, S, D = q.shape
     out = out.reshape(cfg, H, S, D)
     lse = None if lse is None else lse.reshape(cfg, H, S)
-    lens = per_video(quality.valid_len, cfg, "quality probe(valid_len)")
-    vals, counts = video_groups(lens if lens is not None else [quality.valid_len] * cfg)
-    figs, b0 = [], 0
-    for vl, nb in zip(vals, counts):
-        vl = None if vl is None or int(vl) <= 0 or int(vl) >= S else int(vl)
-        n_valid = S if vl is None else vl
-        rows = torch.randint(low=0, high=n_valid, size=(max(1, min(int(quality.rows), 64)),), generator=_probe_generator())
-        sl = slice(b0, b0 + nb)
-        figs.append(sparse_quality(out[sl], None if lse is None else lse[sl], q[sl], k[sl], v[sl], rows, vl, LN2 if q_prescaled else None))
-        b0 += nb
+    figs, lse_dense = [], []
+    for sl, vl, rows in plan if plan is not None else probe_plan(quality.valid_len, quality.rows, cfg, S):
+        want = {} if plan is None else {"dense_lse_out": lse_dense}   # (asked for by the caller that drew the plan, nobody else)
+        figs.append(sparse_quality(out[sl], None if lse is None else lse[sl], q[sl], k[sl], v[sl], rows, vl, LN2 if q_prescaled else None, **want))
     fig = {key: (None if figs[0][key] is None else torch.cat([f[key] for f in figs])) for key in figs[0]}
     ts = quality.timestep
     on_device = torch.is_tensor(ts) and ts.is_cuda   # (the switched path never reads the timestep back: it travels with the figures)
     meta = {"timestep": None if ts is None or on_device else timestep_value(ts), "layer": quality.layer}
-    QUALITY_LOG.push(quality.path, meta, fig, density=density, dense_flag=dense_flag, timestep=ts if on_device else None)
+    QUALITY_LOG.push(quality.path, meta, fig, density=density, dense_flag=dense_flag, timestep=ts if on_device else None, top_p=top_p)
+    return lse_dense
 
 
 _SMALL_TENSORS = {}   # (values, dtype, device) -> tensor: a batch's prompt lengths, uploaded once and not once per layer-call

@@ -7,6 +7,7 @@ are the model's own torch modules, as in the reference's torch fall-back path (h
 """
 from __future__ import annotations
 
+import dataclasses
 import weakref
 from typing import Optional, Tuple
 
@@ -15,7 +16,7 @@ import torch.nn.functional as F
 
 from ...timer import time_logging_decorator
 from .. import _core
-from .._core import CentroidStore, Geometry
+from .._core import CentroidStore, Geometry, TopPStore
 from .utils import dense_mask, generate_temporal_head_mask_mod, profile_desc
 
 
@@ -370,11 +371,17 @@ class Hunyuan_SAPAttn_Processor2_0(Hunyuan_SVGAttn_Processor2_0):
     prescale_q = False   # k-means and the block map work on the plain q
     frame_shard_form = False   # (k-means over the whole video: no frame-shard mode)
     centroid_store = CentroidStore()  # class-level like the reference's dicts; `reset_state()` clears it
+    # adaptive top-p (svg/models/_core.py AdaptiveTopP): an AdaptiveTopP(target=...) -> every head's top_p is steered on the device towards the
+    # kept mass `target`, from `top_p_kmeans` on a layer's first sparse call (state: top_p_store, per layer like the centroids; dense
+    # warm-up steps leave it alone).  None: nothing changes.  Refused under svg.distributed.
+    adaptive_top_p = None
+    top_p_store = TopPStore()
 
     @classmethod
     def reset_state(cls):
-        """Forget the per-layer centroids (call between videos; the reference never resets them)."""
+        """Forget the per-layer centroids and thresholds (call between videos; the reference never resets them)."""
         cls.centroid_store.clear()
+        cls.top_p_store.clear()
 
     @time_logging_decorator("Level 2 - attention core logic")
     def attention_core_logic(self, query, key, value, timestep, layer_idx, cu_max_seqlens):
@@ -384,6 +391,10 @@ class Hunyuan_SAPAttn_Processor2_0(Hunyuan_SVGAttn_Processor2_0):
             f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
         valid = self.video_valid_lens(cu_max_seqlens, cfg, geo.video_length)
         quality = _core.quality_request(type(self).__name__, self.quality_log, self.quality_rows, valid, timestep, self.layer_idx)
+        adaptive = self.adaptive_top_p
+        if adaptive is not None:
+            _core._refuse_adaptive_when_sharded(type(self).__name__)
+            adaptive = dataclasses.replace(adaptive, valid_len=valid)   # (the probe's rows and keys follow the call's valid lengths)
         if _core.is_full_attention(self.layer_idx, timestep, self.first_layers_fp, self.first_times_fp):
             if self.zero_step_kmeans_init and query.is_cuda:
                 V = geo.video_length
@@ -394,7 +405,8 @@ class Hunyuan_SAPAttn_Processor2_0(Hunyuan_SVGAttn_Processor2_0):
         out = _core.svg2_sparse_attention(query, key, value, geo, self.centroid_store, layer_idx, self.num_q_centroids,
                                           self.num_k_centroids, self.top_p_kmeans, self.min_kc_ratio, self.kmeans_iter_init,
                                           self.kmeans_iter_step, prompt_length=self.prompt_length if isinstance(self.prompt_length, tuple) else int(self.prompt_length),
-                                          logging_file=self.logging_file, timestep=timestep, quality=quality)
+                                          logging_file=self.logging_file, timestep=timestep, quality=quality, adaptive=adaptive,
+                                          top_p_store=self.top_p_store)
         return out.reshape(cfg, num_heads, seq_len, dim)
 
 

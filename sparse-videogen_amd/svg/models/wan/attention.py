@@ -10,7 +10,7 @@ import torch
 from ...kernels.triton.rmsnorm import triton_rmsnorm_forward
 from ...timer import time_logging_decorator
 from .. import _core
-from .._core import CentroidStore, Geometry
+from .._core import CentroidStore, Geometry, TopPStore
 from .utils import dense_mask, generate_temporal_head_mask_mod, profile_desc
 
 
@@ -317,13 +317,19 @@ class WanAttn_SAPAttn_Processor(WanAttn_SVGAttn_Processor2_0):
     logging_file = None
     prescale_q = False   # k-means and the block map work on the plain q
     frame_shard_form = False   # (k-means over the whole video: no frame-shard mode)
+    # adaptive top-p (svg/models/_core.py AdaptiveTopP): an AdaptiveTopP(target=...) -> every head's top_p is steered on the device towards the
+    # kept mass `target`, from `top_p_kmeans` on the layer's first sparse call (state: top_p_store; dense warm-up steps leave it alone).
+    # None: nothing changes.  Refused under svg.distributed.
+    adaptive_top_p = None
 
     def __init__(self, layer_idx):
         super().__init__(layer_idx)
         self.centroid_store = CentroidStore()
+        self.top_p_store = TopPStore()
 
     def reset_state(self):
         self.centroid_store.clear()
+        self.top_p_store.clear()
 
     @time_logging_decorator("Level 2 - attention core logic")
     def attention_core_logic(self, query, key, value, timestep):
@@ -332,6 +338,8 @@ class WanAttn_SAPAttn_Processor(WanAttn_SVGAttn_Processor2_0):
         assert seq_len == _core.rows_of_this_rank(type(self).__name__, geo, self.frame_shard_form), (
             f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
         quality = _core.quality_request(type(self).__name__, self.quality_log, self.quality_rows, None, timestep, self.layer_idx)
+        if self.adaptive_top_p is not None:
+            _core._refuse_adaptive_when_sharded(type(self).__name__)
         if _core.is_full_attention(self.layer_idx, timestep, self.first_layers_fp, self.first_times_fp):
             if self.zero_step_kmeans_init and query.is_cuda:
                 V = geo.video_length
@@ -341,5 +349,5 @@ class WanAttn_SAPAttn_Processor(WanAttn_SVGAttn_Processor2_0):
         out = _core.svg2_sparse_attention(query, key, value, geo, self.centroid_store, self.layer_idx, self.num_q_centroids,
                                           self.num_k_centroids, self.top_p_kmeans, self.min_kc_ratio, self.kmeans_iter_init,
                                           self.kmeans_iter_step, prompt_length=0, logging_file=self.logging_file,
-                                          timestep=timestep, quality=quality)
+                                          timestep=timestep, quality=quality, adaptive=self.adaptive_top_p, top_p_store=self.top_p_store)
         return out.reshape(cfg, num_heads, seq_len, dim)

@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """Bit-exactness + timing A/B of the fp8 and the pre-scaled-q attention kernels of two builds of the library, in ONE process on the same inputs:
-    python tools/ab_bitexact.py sparse-videogen_amd/lib/libsvgattn_prev.so [sparse-videogen_amd/lib/libsvgattn.so] [--kmeans]
+    python tools/ab_bitexact.py sparse-videogen_amd/lib/libsvgattn_prev.so [sparse-videogen_amd/lib/libsvgattn.so] [--kmeans | --dynmap]
 Both libraries are loaded side by side (svg._native is re-pointed between the calls); for every case the outputs are compared with
 torch.equal — two builds that differ only in instruction selection / scheduling must agree bit for bit — and the kernel times are
 printed (A, B, A again: the third column shows the drift of the box).
   pre  : svg_band_attention_prescaled (the headline kernel) on the headline workload, head_dim 64 / fp16 / spiky rows, the switch entry
   band : svg_band_attention_fp8 on the headline workload (HunyuanVideo 720p, 24 heads, alternating masks; stage 2 timed alone)
-  vb   : svg_varblock_attention_fp8 on the production-size SVG2 cases of tests/test_gpu_fullsize_svg2.py (fused permutation)"""
+  vb   : svg_varblock_attention_fp8 on the production-size SVG2 cases of tests/test_gpu_fullsize_svg2.py (fused permutation)
+--dynmap: ONLY the entries SVG2's per-head top-p shares kernels with — svg_identify_dynamic_map in both kernel forms and
+svg_sample_dense_rows (o32 and lse) — called through ctypes handles of the two files, so that A may be a library from before the entries
+of include/svg_attn_adaptive_top_p.h existed (svg._native.load() types every table and refuses such a file)."""
 import sys
 from pathlib import Path
 
@@ -66,12 +69,68 @@ def ab(name, fn, n):
     return same
 
 
+def dynmap_cases(dev):
+    """--dynmap: the scalar block-map entry and the full probe of two library files, raw C calls on the same tensors"""
+    import ctypes
+
+    libs = {}
+    for tag in ("A", "B"):
+        lib = ctypes.CDLL(LIBS[tag])
+        for table in (nat.SIGNATURES, nat.SAMPLE_ROWS_SIGNATURES):
+            for name in ("svg_identify_dynamic_map", "svg_sample_dense_rows", "svg_sample_dense_rows_workspace_bytes"):
+                if name in table:
+                    getattr(lib, name).restype, getattr(lib, name).argtypes = table[name]
+        libs[tag] = lib
+    st = lambda: torch.cuda.current_stream().cuda_stream  # noqa: E731
+    ok = True
+    g = torch.Generator(device=dev).manual_seed(2)
+    for BH, QC, KC, D, dt, p, pres in ((40, 300, 1000, 128, torch.bfloat16, 0.9, 100), (5, 20, 1100, 128, torch.bfloat16, 0.6, 0),
+                                       (5, 20, 300, 64, torch.float16, 0.35, 3), (5, 4, 12, 128, torch.bfloat16, 0.6005, 0)):
+        qc = (torch.randn(BH, QC, D, device=dev, generator=g) * 1.2).to(dt)
+        kc = (torch.randn(BH, KC, D, device=dev, generator=g) * 1.2).to(dt)
+        ks = torch.randint(0, 90, (BH, KC), device=dev, generator=g, dtype=torch.int32)
+        outs, ms = {}, {}
+        for tag in ("A", "B", "A2"):
+            out = torch.full((BH, QC, KC), 255, dtype=torch.uint8, device=dev)
+            fn = lambda: libs[tag[0]].svg_identify_dynamic_map(qc.data_ptr(), kc.data_ptr(), ks.data_ptr(), out.data_ptr(), BH, QC, KC, D,  # noqa: E731
+                                                                0 if dt == torch.bfloat16 else 1, p, pres, st())
+            assert fn() == 0
+            ms[tag], outs[tag] = timed(fn, 5), out
+        same = torch.equal(outs["A"], outs["B"]) and torch.equal(outs["A"], outs["A2"]) and int(outs["B"].max()) <= 1
+        print(f"identify_dynamic_map BH={BH} QC={QC} KC={KC} D={D} {str(dt)[6:]} p={p}: A {ms['A']:.4f} ms  B {ms['B']:.4f} ms  A again "
+              f"{ms['A2']:.4f} ms   bit-identical: {same}   kept blocks {int(outs['B'].sum())}", flush=True)
+        ok &= same
+    for BH, S, D, dt, vl in ((3, 4100, 128, torch.bfloat16, 761), (3, 790, 64, torch.float16, 0), (40, 75600, 128, torch.bfloat16, 0)):
+        q, k, v = (torch.randn(BH, S, D, device=dev, generator=g).to(dt) for _ in range(3))
+        rows = torch.randint(0, S, (64,), device=dev, generator=g)
+        outs, ms = {}, {}
+        for tag in ("A", "B", "A2"):
+            lib = libs[tag[0]]
+            o32 = torch.full((BH, 64, D), float("nan"), device=dev)
+            lse = torch.full((BH, 64), float("nan"), device=dev)
+            ws = torch.empty(lib.svg_sample_dense_rows_workspace_bytes(BH, 64, D, S), dtype=torch.uint8, device=dev)
+            fn = lambda: lib.svg_sample_dense_rows(q.data_ptr(), k.data_ptr(), v.data_ptr(), rows.data_ptr(), 64, BH, S, D,  # noqa: E731
+                                                   0 if dt == torch.bfloat16 else 1, D ** -0.5, vl, o32.data_ptr(), lse.data_ptr(),
+                                                   ws.data_ptr(), ws.numel(), None, st())
+            assert fn() == 0
+            ms[tag], outs[tag] = timed(fn, 5), (o32, lse)
+        same = all(torch.equal(outs["A"][i], outs[t][i]) for t in ("B", "A2") for i in (0, 1)) and bool(torch.isfinite(outs["B"][1]).all())
+        print(f"sample_dense_rows BH={BH} S={S} D={D} {str(dt)[6:]} valid_len={vl}: A {ms['A']:.4f} ms  B {ms['B']:.4f} ms  A again "
+              f"{ms['A2']:.4f} ms   bit-identical (o32, lse): {same}", flush=True)
+        ok &= same
+    return ok
+
+
 def main():
     dev = torch.device("cuda", 0)
     LIBS["A"] = str(Path([a for a in sys.argv[1:] if not a.startswith("--")][0]).resolve())
     paths = [a for a in sys.argv[1:] if not a.startswith("--")]
     LIBS["B"] = str(Path(paths[1]).resolve()) if len(paths) > 1 else str(ROOT / "sparse-videogen_amd" / "lib" / "libsvgattn.so")
     print("A =", LIBS["A"], "\nB =", LIBS["B"])
+    if "--dynmap" in sys.argv:
+        ok = dynmap_cases(dev)
+        print("ALL BIT-IDENTICAL" if ok else "MISMATCH")
+        return 0 if ok else 1
     ok = True
     BH, D, F_, P_, ctx = 24, 128, 33, 3600, 256
     S = F_ * P_ + ctx
