@@ -4,7 +4,6 @@ non-allocating bindings (identify_dynamic_map_per_head, top_p_update) are in svg
 like every allocation of the package."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import torch
@@ -30,13 +29,8 @@ def sample_dense_lse(q: torch.Tensor, k: torch.Tensor, rows: torch.Tensor, valid
     ws = _native.empty(lib.svg_sample_dense_lse_workspace_bytes(BH, R, S), dtype=torch.uint8, device=q.device)
     scale = _native._sm_scale(sm_scale, D)
     vl = 0 if valid_len is None else int(valid_len)
-    lay = None
-    if not (q.is_contiguous() and k.is_contiguous()):
-        if _native._strided_ok(q) and _native._strided_ok(k, True):
-            lay = _native.attn_layout(q, k, k, q)
-        else:
-            q, k = q.contiguous(), k.contiguous()
-    rc = lib.svg_sample_dense_lse(q.data_ptr(), k.data_ptr(), rows.data_ptr(), R, BH, S, D, _native._dtype_code(q), scale, vl, lse.data_ptr(),
-                                  ws.data_ptr(), ws.numel(), C.byref(lay) if lay is not None else None, _native._stream())
+    p = _native._layout_plan(q, k, k, o=_native._NO_O)   # (no V: the layout's v member takes k's strides)
+    rc = lib.svg_sample_dense_lse(p.q.data_ptr(), p.k.data_ptr(), rows.data_ptr(), R, BH, S, D, _native._dtype_code(q), scale, vl, lse.data_ptr(),
+                                  ws.data_ptr(), ws.numel(), p.lay, _native._stream())
     _native._check(rc, "svg_sample_dense_lse")
     return lse

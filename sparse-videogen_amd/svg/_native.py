@@ -347,7 +347,6 @@ ADAPTIVE_TOP_P_SIGNATURES = {
 }
 
 
-
 class CopyBox(C.Structure):
     """svg_copy_box_t (include/svg_attn_shard_exchange.h): extent[0] * extent[1] * extent[2] rows of D contiguous elements; offsets and
     strides in elements"""
@@ -471,21 +470,17 @@ def _strided_ok(t4: torch.Tensor, dma: bool = False) -> bool:
     return (not dma) or S * st[2] * 2 < (1 << 32)   # k / v: 32-bit byte offsets per head in the LDS-DMA requests
 
 
-def _is_dense4(t4: torch.Tensor) -> bool:
-    """contiguous [B, H, S, D]: what every entry point without `_strided` takes"""
-    return t4.is_contiguous()
-
-
 def attn_layout(q4: torch.Tensor, k4: torch.Tensor, v4: torch.Tensor, o4: torch.Tensor) -> AttnLayout:
     ts = [TensorStrides(t.stride(0), t.stride(1), t.stride(2)) for t in (q4, k4, v4, o4)]
     return AttnLayout(q4.shape[1], k4.shape[1], *ts)
 
 
-def token_major_empty(like4: torch.Tensor) -> torch.Tensor:
-    """An uninitialised [B, H, S, D] tensor stored token-major ([B, S, H, D] in memory): `out.transpose(1, 2).flatten(2, 3)` — what
-    every processor of the reference does with the attention output before the output projection — is then a view, not a copy."""
+def token_major_empty(like4: torch.Tensor, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """An uninitialised [B, H, S, D] tensor (of like4's dtype, or `dtype`) stored token-major ([B, S, H, D] in memory):
+    `out.transpose(1, 2).flatten(2, 3)` — what every processor of the reference does with the attention output before the output
+    projection — is then a view, not a copy."""
     B, H, S, D = like4.shape
-    return empty((B, S, H, D), dtype=like4.dtype, device=like4.device).permute(0, 2, 1, 3)
+    return empty((B, S, H, D), dtype=dtype or like4.dtype, device=like4.device).permute(0, 2, 1, 3)
 
 
 def strided_attention_supported(q: torch.Tensor, variant: int = 0) -> bool:
@@ -493,16 +488,99 @@ def strided_attention_supported(q: torch.Tensor, variant: int = 0) -> bool:
     return q.shape[-1] in (64, 128) and variant == 0 and q.dtype in (torch.bfloat16, torch.float16)
 
 
-def _try_strided(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: Optional[torch.Tensor], token_major_out: bool, name: str,
-                 call) -> Optional[torch.Tensor]:
-    """Run the *_strided entry point `name` as call(o4, layout) on [B, H, S, D] views of q, k, v and of the output (`out`, or a new
-    tensor, token-major when asked) and return the output; None when the views cannot be read / written in place."""
-    q4, k4, v4 = _view4(q), _view4(k), _view4(v)
-    o4 = _view4(out) if out is not None else (token_major_empty(q4) if token_major_out else empty(q4.shape, dtype=q.dtype, device=q.device))
-    if not (_strided_ok(q4) and _strided_ok(k4, True) and _strided_ok(v4, True) and _strided_ok(o4) and o4.shape == q4.shape):
-        return None
-    _check(call(o4, attn_layout(q4, k4, v4, o4)), name)
-    return out if out is not None else (o4 if q.dim() == 4 else o4.squeeze(0))
+class _LayoutPlan:
+    """What _layout_plan decided: the tensors to launch on (q, k, v, k_b, v_b: the caller's or contiguous copies), the output to launch
+    on (o: the caller's `out`, a new tensor or a stand-in; None for a plan of inputs only), the layout arguments (lay, lay_b: NULL or a
+    reference to an AttnLayout) and the caller's `out`."""
+
+    __slots__ = ("q", "k", "v", "k_b", "v_b", "o", "lay", "lay_b", "out")
+
+    def result(self) -> torch.Tensor:
+        """The wrapper's o: the new tensor, or the caller's `out` — after the copy-back where the launch wrote a stand-in."""
+        if self.out is None:
+            return self.o
+        if self.o is not self.out:
+            self.out.copy_(self.o)
+        return self.out
+
+
+_O16, _O32, _NO_O = "16-bit", "fp32 rows", "inputs only"
+
+
+def _layout_plan(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_b: Optional[torch.Tensor] = None, v_b: Optional[torch.Tensor] = None, *,
+                 o: str = _O16, out: Optional[torch.Tensor] = None, token_major_out: bool = False, o_dtype: Optional[torch.dtype] = None,
+                 null_layout: bool = True, views: bool = True, views_on_copies: bool = True, inputs_as_given: bool = False,
+                 zero_o: bool = False) -> _LayoutPlan:
+    """Where one attention launch reads q / k / v and writes o — decided from shapes, strides and alignment, before anything is called.
+
+    The fall-back of every attention wrapper: tensors are read and written where they lie — without a layout when everything is
+    contiguous (null_layout: the entry takes NULL then; an entry whose strided form has another name is picked by `plan.lay is None`),
+    through an AttnLayout over [B, H, S, D] views where _strided_ok describes every one of them.  What it cannot describe is copied,
+    as the reference copies what its kernels cannot take: first q, k, v (all of them), and an `out` it still cannot write gets a
+    stand-in — the output a call without `out` would make — that plan.result() copies back.
+
+    q and k / v may have different row counts (window, shard, cross); k_b, v_b: the second key set of the pair entry, with its own
+    strides (lay_b) and its own describability.  The same tensor passed twice is copied once (a K-only probe plans q, k, k).
+    o: _O16 — `out`, or a new tensor of q's shape and dtype (o_dtype), token-major when token_major_out and a layout can say so;
+       _O32 — fp32 rows: always new and contiguous, the layout's o member takes q's strides;
+       _NO_O — inputs only (the profilers, the probes).
+    views: may this call take a layout at all (the schedule, q_prescaled, completion counters, groups that split a video's heads,
+    block-rows too small, fp8, a dtype without a strided form)?  Without, a token-major output cannot be made either.
+    views_on_copies=False: the entries with a `_strided` twin take views of the caller's own tensors only — once anything was copied
+    they run their plain form, a new output is head-major whatever token_major_out says and a non-contiguous `out` gets a stand-in.
+    inputs_as_given: q, k, v are neither examined nor copied (merge: its parts are the caller's contract), their strides still fill
+    the layout.  zero_o: zero-fill the tensor the launch writes (rows a kernel may leave out), once."""
+    ins = (q, k, v) if k_b is None else (q, k, v, k_b, v_b)
+    p = _LayoutPlan()
+    p.out, p.lay, p.lay_b = out, None, None
+    p.o = empty(q.shape, dtype=torch.float32, device=q.device) if o is _O32 else None
+    dst, with_views = out, views
+    for attempt in ("as they lie", "inputs copied", "and a stand-in for out"):
+        if attempt == "inputs copied":
+            with_views = views and views_on_copies
+            if not inputs_as_given:
+                copies = {}
+                for t in ins:
+                    if id(t) not in copies:
+                        copies[id(t)] = t.contiguous()
+                ins = tuple([copies[id(t)] for t in ins])
+        elif attempt == "and a stand-in for out":
+            if out is None:
+                continue
+            dst = None
+        if null_layout and (inputs_as_given or not [t for t in ins if not t.is_contiguous()]) and (
+                o is not _O16 or (dst.is_contiguous() if dst is not None else not (token_major_out and with_views))):
+            if o is _O16:   # (everything contiguous: the entry takes no layout)
+                p.o = dst if dst is not None else (empty_like(ins[0]) if o_dtype is None else empty_like(ins[0], dtype=o_dtype))
+            break
+        if not with_views:
+            continue
+        q4, *kv4 = [_view4(t) for t in ins]
+        if not (inputs_as_given or (_strided_ok(q4) and not [t for t in kv4 if not _strided_ok(t, True)])):
+            continue
+        if o is not _O16:
+            o4 = q4
+        elif dst is not None:
+            o4 = _view4(dst)
+        elif token_major_out:
+            o4 = token_major_empty(q4, o_dtype)
+        else:
+            o4 = empty_like(q4, dtype=o_dtype, memory_format=torch.contiguous_format)
+        if _strided_ok(o4) and o4.shape == q4.shape:
+            if o is _O16:
+                p.o = dst if dst is not None else (o4 if q.dim() == 4 else o4.squeeze(0))
+            p.lay = C.byref(attn_layout(q4, kv4[0], kv4[1], o4))
+            if k_b is not None:   # (its k / v strides are what the entry reads)
+                p.lay_b = C.byref(attn_layout(q4, kv4[2], kv4[3], o4))
+            break
+    else:
+        raise RuntimeError("libsvgattn: contiguous copies of q / k / v that the attention layout still cannot describe (16-byte alignment, "
+                           "row stride below 2^23 elements, k / v of less than 4 GiB per head)")
+    p.q, p.k, p.v = ins[:3]
+    p.k_b, p.v_b = ins[3:] if k_b is not None else (None, None)
+    if zero_o:
+        p.o.zero_()
+    return p
 
 
 def _sm_scale(sm_scale: Optional[float], D: int) -> float:
@@ -582,16 +660,6 @@ def _want_f32_parts(what: str, out_dtype, return_lse: bool, out, token_major_out
     return True
 
 
-def _q_views(q, k, v, name: str, call):
-    """The fp32-row entries on [B, H, S, D] views of q, k, v (their output is contiguous whatever q is): call(layout) -> rc, checked;
-    False where the layout cannot describe a view."""
-    q4, k4, v4 = _view4(q), _view4(k), _view4(v)
-    if not (_strided_ok(q4) and _strided_ok(k4, True) and _strided_ok(v4, True)):
-        return False
-    _check(call(attn_layout(q4, k4, v4, q4)), name)
-    return True
-
-
 def band_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: BandMask, sm_scale: Optional[float] = None,
                    head_perm_flag: Optional[torch.Tensor] = None, vid0: int = 0, num_frame: int = 1,
                    frame_size: int = 1, variant: int = 0, out: Optional[torch.Tensor] = None,
@@ -600,7 +668,7 @@ def band_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Band
     """q, k, v: [B, H, S, D] (or [BH, S, D]) bf16/fp16 GPU tensors -> o of the same shape.
     Strided views (last dimension contiguous — e.g. `proj(x).unflatten(2, (H, -1)).transpose(1, 2)`, or a slice of a fused QKV
     projection) are read in place by svg_band_attention_strided where it exists (head_dim 128, default schedule, plain q, no completion
-    counters) and copied otherwise, as the reference does.  token_major_out: the result is a [B, H, S, D] tensor stored [B, S, H, D]
+    counters); layouts and copies: _layout_plan.  token_major_out: the result is a [B, H, S, D] tensor stored [B, S, H, D]
     (token_major_empty), so the processors' `.transpose(1, 2).flatten(2, 3)` is a view.
     q_prescaled: q already carries sm_scale * log2(e) (SOFTMAX_Q_SCALE(D) for the default scale; what qk_norm_rope*(q_scale=...)
     writes): svg_band_attention_prescaled, default schedule only.
@@ -625,8 +693,8 @@ def band_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Band
 
 
 def _band_attention_lse(q, k, v, mask, sm_scale, head_perm_flag, vid0, num_frame, frame_size, out, token_major_out, f32=False):
-    """band_attention(return_lse=True): svg_band_attention_lse (f32: svg_band_attention_lse_f32) — without a layout for contiguous tensors,
-    on views otherwise; what the layout cannot describe is copied.  Never the entry without lse."""
+    """band_attention(return_lse=True): svg_band_attention_lse (f32: svg_band_attention_lse_f32), never the entry without lse.  Layouts
+    and copies: _layout_plan."""
     lib = load()
     _dev(head_perm_flag)
     _gpu(q, k, v, out)
@@ -635,59 +703,15 @@ def _band_attention_lse(q, k, v, mask, sm_scale, head_perm_flag, vid0, num_frame
     BH = q.numel() // (S * D)
     scale = _sm_scale(sm_scale, D)
     perm = _perm_arg(head_perm_flag, BH, vid0, num_frame, frame_size)
-    # (contiguous [BH, S] whatever the layout of q / o; written whole by every launch, so a retry after a layout fall-back reuses it)
-    lse = empty(q.shape[:-1], dtype=torch.float32, device=q.device)
+    lse = empty(q.shape[:-1], dtype=torch.float32, device=q.device)   # (contiguous [BH, S] whatever the layout of q / o)
+    p = _layout_plan(q, k, v, o=_O32 if f32 else _O16, out=out, token_major_out=token_major_out)
     if f32:
-        o32 = empty(q.shape, dtype=torch.float32, device=q.device)
-
-        def call(q, k, v, lay):
-            return lib.svg_band_attention_lse_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), o32.data_ptr(), lse.data_ptr(), BH, S, D,
-                                                  _dtype_code(q), scale, C.byref(mask), perm, lay, _stream())
-
-        if q.is_contiguous() and k.is_contiguous() and v.is_contiguous():
-            _check(call(q, k, v, None), "svg_band_attention_lse_f32")
-        elif not _q_views(q, k, v, "svg_band_attention_lse_f32", lambda lay: call(q, k, v, C.byref(lay))):
-            _check(call(q.contiguous(), k.contiguous(), v.contiguous(), None), "svg_band_attention_lse_f32")
-        return o32, lse
-
-    def run(q, k, v, out):
-        if q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and (out.is_contiguous() if out is not None else not token_major_out):
-            o = empty_like(q) if out is None else out
-            _check(lib.svg_band_attention_lse(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), BH, S, D, _dtype_code(q),
-                                              scale, C.byref(mask), perm, None, _stream()), "svg_band_attention_lse")
-            return o
-        return _try_strided(q, k, v, out, token_major_out, "svg_band_attention_lse", lambda o4, lay: lib.svg_band_attention_lse(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), lse.data_ptr(), BH, S, D, _dtype_code(q), scale, C.byref(mask), perm,
-            C.byref(lay), _stream()))
-
-    return _run_or_copy(run, (q, k, v), out), lse
-
-
-def _band_form_lse(q, k, v, out, token_major_out, f32, name, call, views_ok=True):
-    """The LSE (f32: fp32-row) form `name` of a device-switch or groups launch: call(q, k, v, o, lse, layout) -> rc, with o the 16-bit
-    output or o32 — without a layout for contiguous tensors, on views where the layout describes them (views_ok: the entry takes one for
-    this call), copied otherwise.  Never the entry without lse.  -> (o | o32, lse)"""
-    # (contiguous [BH, S] whatever the layout of q / o; written whole by every launch, so a retry after a layout fall-back reuses it)
-    lse = empty(q.shape[:-1], dtype=torch.float32, device=q.device)
-    if f32:
-        o32 = empty(q.shape, dtype=torch.float32, device=q.device)
-        if q.is_contiguous() and k.is_contiguous() and v.is_contiguous():
-            _check(call(q, k, v, o32, lse, None), name)
-        elif not (views_ok and _q_views(q, k, v, name, lambda lay: call(q, k, v, o32, lse, C.byref(lay)))):
-            _check(call(q.contiguous(), k.contiguous(), v.contiguous(), o32, lse, None), name)
-        return o32, lse
-
-    def run(q, k, v, out):
-        dense = q.is_contiguous() and k.is_contiguous() and v.is_contiguous()
-        if dense and (out.is_contiguous() if out is not None else not (token_major_out and views_ok)):
-            o = empty_like(q) if out is None else out
-            _check(call(q, k, v, o, lse, None), name)
-            return o
-        if not views_ok:
-            return None
-        return _try_strided(q, k, v, out, token_major_out, name, lambda o4, lay: call(q, k, v, o4, lse, C.byref(lay)))
-
-    return _run_or_copy(run, (q, k, v), out), lse
+        _check(lib.svg_band_attention_lse_f32(p.q.data_ptr(), p.k.data_ptr(), p.v.data_ptr(), p.o.data_ptr(), lse.data_ptr(), BH, S, D,
+                                              _dtype_code(q), scale, C.byref(mask), perm, p.lay, _stream()), "svg_band_attention_lse_f32")
+    else:
+        _check(lib.svg_band_attention_lse(p.q.data_ptr(), p.k.data_ptr(), p.v.data_ptr(), p.o.data_ptr(), lse.data_ptr(), BH, S, D,
+                                          _dtype_code(q), scale, C.byref(mask), perm, p.lay, _stream()), "svg_band_attention_lse")
+    return p.result(), lse
 
 
 def _band_form_checks(what, q, k, v, out, q_prescaled, return_lse, out_dtype, token_major_out) -> bool:
@@ -710,30 +734,23 @@ def _band_attention(q, k, v, mask, alt_mask, use_alt_flag, sm_scale, head_perm_f
     scale = _sm_scale(sm_scale, D)
     perm = _perm_arg(head_perm_flag, BH, vid0, num_frame, frame_size)
     switch = use_alt_flag is not None
-    dense_in = q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and (out is None or out.is_contiguous())
-    if (not dense_in or (token_major_out and out is None)) and done is None and not q_prescaled and strided_attention_supported(q, variant):
-        if switch:
-            o = _try_strided(q, k, v, out, token_major_out, "svg_band_attention_switch_strided", lambda o4, lay: lib.svg_band_attention_switch_strided(
-                q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), BH, S, D, _dtype_code(q), scale, C.byref(mask), perm,
-                C.byref(alt_mask), use_alt_flag.data_ptr(), C.byref(lay), _stream()))
-        else:
-            o = _try_strided(q, k, v, out, token_major_out, "svg_band_attention_strided", lambda o4, lay: lib.svg_band_attention_strided(
-                q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), BH, S, D, _dtype_code(q), scale, C.byref(mask), perm, C.byref(lay),
-                _stream()))
-        if o is not None:
-            return o
-    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()   # (what no strided entry point takes is copied, as the reference does)
-    if out is not None and not out.is_contiguous():
-        out.copy_(_band_attention(q, k, v, mask, alt_mask, use_alt_flag, sm_scale, head_perm_flag, vid0, num_frame, frame_size, variant,
-                                  None, done, done_nseg, q_prescaled, False))
-        return out
-    o = empty_like(q) if out is None else out
     if done is not None:
         _dev(done)
         assert done.dtype == torch.int32 and done.is_contiguous() and variant == 0
     if q_prescaled:
         assert variant == 0 and sm_scale is None, "q_prescaled: default-schedule call, the scale lives in q"
-    if switch and q_prescaled:
+    p = _layout_plan(q, k, v, out=out, token_major_out=token_major_out, views_on_copies=False,
+                     views=done is None and not q_prescaled and strided_attention_supported(q, variant))
+    q, k, v, o = p.q, p.k, p.v, p.o
+    if p.lay is not None and switch:
+        rc = lib.svg_band_attention_switch_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), BH, S, D, _dtype_code(q), scale,
+                                                   C.byref(mask), perm, C.byref(alt_mask), use_alt_flag.data_ptr(), p.lay, _stream())
+        _check(rc, "svg_band_attention_switch_strided")
+    elif p.lay is not None:
+        rc = lib.svg_band_attention_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), BH, S, D, _dtype_code(q), scale,
+                                            C.byref(mask), perm, p.lay, _stream())
+        _check(rc, "svg_band_attention_strided")
+    elif switch and q_prescaled:
         rc = lib.svg_band_attention_switch_prescaled(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), BH, S, D, _dtype_code(q),
                                                      C.byref(mask), perm, C.byref(alt_mask), use_alt_flag.data_ptr(), _stream())
         _check(rc, "svg_band_attention_switch_prescaled")
@@ -759,7 +776,7 @@ def _band_attention(q, k, v, mask, alt_mask, use_alt_flag, sm_scale, head_perm_f
         rc = lib.svg_band_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), BH, S, D, _dtype_code(q), scale,
                                     C.byref(mask), perm, variant, _stream())
         _check(rc, "svg_band_attention")
-    return o
+    return p.result()
 
 
 def softmax_q_scale(D: int, sm_scale: Optional[float] = None) -> float:
@@ -911,13 +928,14 @@ def band_attention_switch(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
         BH = q.numel() // (S * D)
         perm = _perm_arg(head_perm_flag, BH, vid0, num_frame, frame_size)
         args = (BH, S, D, _dtype_code(q), _sm_scale(sm_scale, D), C.byref(mask), perm, C.byref(alt_mask), use_alt_flag.data_ptr())
+        lse = empty(q.shape[:-1], dtype=torch.float32, device=q.device)   # (contiguous [BH, S] whatever the layout of q / o)
+        p = _layout_plan(q, k, v, o=_O32 if f32 else _O16, out=out, token_major_out=token_major_out)
+        ptrs = (p.q.data_ptr(), p.k.data_ptr(), p.v.data_ptr(), p.o.data_ptr(), lse.data_ptr())
         if f32:
-            return _band_form_lse(q, k, v, out, token_major_out, True, "svg_band_attention_switch_lse_f32", lambda q, k, v, o, lse, lay:
-                                  lib.svg_band_attention_switch_lse_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(),
-                                                                        *args, lay, _stream()))
-        return _band_form_lse(q, k, v, out, token_major_out, False, "svg_band_attention_switch_lse", lambda q, k, v, o, lse, lay:
-                              lib.svg_band_attention_switch_lse(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), *args,
-                                                                lay, _stream()))
+            _check(lib.svg_band_attention_switch_lse_f32(*ptrs, *args, p.lay, _stream()), "svg_band_attention_switch_lse_f32")
+        else:
+            _check(lib.svg_band_attention_switch_lse(*ptrs, *args, p.lay, _stream()), "svg_band_attention_switch_lse")
+        return p.result(), lse
     return _band_attention(q, k, v, mask, alt_mask, use_alt_flag, sm_scale, head_perm_flag, vid0, num_frame, frame_size, 0, out, None, 1,
                            q_prescaled, token_major_out)
 
@@ -931,7 +949,7 @@ def band_attention_groups(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
     group_heads[g] heads — under masks[g] (alt_masks[g]): svg_band_groups_attention, bit for bit the single-mask call on each group's
     heads.  q, k, v: [B, H, S, D] (or [BH, S, D]), default schedule, default softmax scale.  Strided views, `out` and token_major_out as in
     band_attention: read / written in place where the single-mask strided entry would (plain q, every group a whole number of the H
-    heads of a video), copied otherwise.
+    heads of a video); layouts and copies: _layout_plan.
     return_lse / out_dtype=torch.float32: (o, lse) / (o32, lse) as in band_attention / band_attention_switch, bit for bit that call on
     each group's heads (svg_band_groups_attention_lse[_f32]: head_dim 128, plain q; anything else raises ValueError)."""
     f32 = _band_form_checks("band_attention_groups", q, k, v, out, q_prescaled, return_lse, out_dtype, token_major_out)
@@ -950,34 +968,23 @@ def band_attention_groups(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
     garr = (_I32 * n)(*[int(g) for g in group_heads])
     flag = _ptr(use_alt_flag)
 
-    def call(qq, kk, vv, o, lay):
-        return lib.svg_band_groups_attention(qq.data_ptr(), kk.data_ptr(), vv.data_ptr(), o.data_ptr(), BH, S, D, _dtype_code(q), _sm_scale(None, D),
-                                             marr, aarr, garr, n, perm, flag, int(q_prescaled), lay, _stream())
-
     H = _view4(q).shape[1]
+    whole = all(int(g) % H == 0 for g in group_heads)   # (a layout describes heads per video: no group may split one)
+    args = (BH, S, D, _dtype_code(q), _sm_scale(None, D), marr, aarr, garr, n, perm, flag)
     if return_lse:
-        args = (BH, S, D, _dtype_code(q), _sm_scale(None, D), marr, aarr, garr, n, perm, flag)
-        whole = all(int(g) % H == 0 for g in group_heads)
+        lse = empty(q.shape[:-1], dtype=torch.float32, device=q.device)   # (contiguous [BH, S] whatever the layout of q / o)
+        p = _layout_plan(q, k, v, o=_O32 if f32 else _O16, out=out, token_major_out=token_major_out, views=whole)
+        ptrs = (p.q.data_ptr(), p.k.data_ptr(), p.v.data_ptr(), p.o.data_ptr(), lse.data_ptr())
         if f32:
-            return _band_form_lse(q, k, v, out, token_major_out, True, "svg_band_groups_attention_lse_f32", lambda q, k, v, o, lse, lay:
-                                  lib.svg_band_groups_attention_lse_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(),
-                                                                        *args, lay, _stream()), whole)
-        return _band_form_lse(q, k, v, out, token_major_out, False, "svg_band_groups_attention_lse", lambda q, k, v, o, lse, lay:
-                              lib.svg_band_groups_attention_lse(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), *args,
-                                                                lay, _stream()), whole)
-    dense_in = q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and (out is None or out.is_contiguous())
-    if (not dense_in or (token_major_out and out is None)) and not q_prescaled and strided_attention_supported(q) \
-            and all(int(g) % H == 0 for g in group_heads):
-        o = _try_strided(q, k, v, out, token_major_out, "svg_band_groups_attention", lambda o4, lay: call(q, k, v, o4, C.byref(lay)))
-        if o is not None:
-            return o
-    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()   # (what no strided entry point takes is copied, as the reference does)
-    o = empty_like(q) if out is None or not out.is_contiguous() else out
-    _check(call(q, k, v, o, None), "svg_band_groups_attention")
-    if out is not None and o is not out:
-        out.copy_(o)
-        return out
-    return o
+            _check(lib.svg_band_groups_attention_lse_f32(*ptrs, *args, p.lay, _stream()), "svg_band_groups_attention_lse_f32")
+        else:
+            _check(lib.svg_band_groups_attention_lse(*ptrs, *args, p.lay, _stream()), "svg_band_groups_attention_lse")
+        return p.result(), lse
+    p = _layout_plan(q, k, v, out=out, token_major_out=token_major_out, views_on_copies=False,
+                     views=not q_prescaled and strided_attention_supported(q) and whole)
+    _check(lib.svg_band_groups_attention(p.q.data_ptr(), p.k.data_ptr(), p.v.data_ptr(), p.o.data_ptr(), *args, int(q_prescaled), p.lay,
+                                         _stream()), "svg_band_groups_attention")
+    return p.result()
 
 
 def band_window_has_keys(mask: BandMask, num_tokens: int, q_range, k_range) -> bool:
@@ -1007,7 +1014,7 @@ def band_window_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
     num_tokens rows, in the LOGICAL order of the mask; row i sees key j where the mask allows (q_begin + i, k_begin + j).  o has q's shape
     and dtype, lse is contiguous fp32 of shape q.shape[:-1] (natural log; a row that sees no key of the window: o = 0, lse = -inf) — parts
     for merge_attention_states: the parts of one row window over disjoint key windows covering the sequence merge to band_attention's
-    result.  Views (stride(-1) == 1) are read in place; what the layout cannot describe is copied.
+    result.  Layouts and copies: _layout_plan.
     out_dtype=torch.float32 (without out): (o32, lse), the rows before their rounding, contiguous fp32.
     Sq == 0 or Sk == 0 is answered without a launch.  head_dim 128, bf16 / fp16, GPU tensors, k_begin a multiple of 64: anything else
     raises before anything runs — there is no fall-back and no head permutation (token-major heads need their placement first)."""
@@ -1040,40 +1047,13 @@ def band_window_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
     lib = load()
     BH = q.numel() // (Sq * D)
     geom = (BH, S, q_begin, Sq, k_begin, Sk, D, _dtype_code(q), _sm_scale(None, D), C.byref(mask))
+    p = _layout_plan(q, k, v, o=_O32 if f32 else _O16, out=out)
+    ptrs = (p.q.data_ptr(), p.k.data_ptr(), p.v.data_ptr(), p.o.data_ptr(), lse.data_ptr())
     if f32:
-        o32 = empty(q.shape, dtype=torch.float32, device=q.device)
-
-        def call32(q, k, v, lay):
-            return lib.svg_band_window_attention_lse_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), o32.data_ptr(), lse.data_ptr(), *geom, lay,
-                                                         _stream())
-
-        if q.is_contiguous() and k.is_contiguous() and v.is_contiguous():
-            _check(call32(q, k, v, None), "svg_band_window_attention_lse_f32")
-        elif not _window_views(q, k, v, q, "svg_band_window_attention_lse_f32", lambda lay: call32(q, k, v, C.byref(lay))):
-            _check(call32(q.contiguous(), k.contiguous(), v.contiguous(), None), "svg_band_window_attention_lse_f32")
-        return o32, lse
-
-    def run(q, k, v, out):
-        o = empty_like(q, memory_format=torch.contiguous_format) if out is None else out
-        if q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and o.is_contiguous():
-            _check(lib.svg_band_window_attention_lse(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), *geom, None,
-                                                     _stream()), "svg_band_window_attention_lse")
-            return o
-        ok = _window_views(q, k, v, o, "svg_band_window_attention_lse", lambda lay: lib.svg_band_window_attention_lse(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), *geom, C.byref(lay), _stream()))
-        return o if ok else None
-
-    return _run_or_copy(run, (q, k, v), out), lse
-
-
-def _window_views(q, k, v, o, name: str, call) -> bool:
-    """a window entry on [B, H, S, D] views (q / o with Sq rows, k / v with Sk): call(layout) -> rc, checked; False where the layout
-    cannot describe a view"""
-    q4, k4, v4, o4 = _view4(q), _view4(k), _view4(v), _view4(o)
-    if not (_strided_ok(q4) and _strided_ok(k4, True) and _strided_ok(v4, True) and _strided_ok(o4)):
-        return False
-    _check(call(attn_layout(q4, k4, v4, o4)), name)
-    return True
+        _check(lib.svg_band_window_attention_lse_f32(*ptrs, *geom, p.lay, _stream()), "svg_band_window_attention_lse_f32")
+    else:
+        _check(lib.svg_band_window_attention_lse(*ptrs, *geom, p.lay, _stream()), "svg_band_window_attention_lse")
+    return p.result(), lse
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -1213,8 +1193,8 @@ def _band_shard_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
     the shard's frames, both kinds of head in ONE launch, no flag is read back.  Row lq sees key lk where `mask` allows the coordinates the
     two maps give (band_shard_coord).  o has q's shape and dtype and lse is contiguous fp32 of shape q.shape[:-1], both in the order q was
     given in (a row that sees no key of the shard: o = 0, lse = -inf) — parts for merge_attention_states: the parts of one q shard over
-    k shards that cover the sequence merge to the shard's rows of band_attention with the same flags.  Views (stride(-1) == 1) are read in
-    place; what the layout cannot describe is copied.  out_dtype=torch.float32 (without out): (o32, lse), the rows before their rounding.
+    k shards that cover the sequence merge to the shard's rows of band_attention with the same flags.  Layouts and copies: _layout_plan.
+    out_dtype=torch.float32 (without out): (o32, lse), the rows before their rounding.
     head_dim 128, bf16 / fp16, GPU tensors: anything else raises before anything runs — there is no fall-back.
     _switch: (alt_mask, use_alt_flag) of band_shard_attention_switch — the svg_band_shard_attention_switch_lse[_f32] entries."""
     if out_dtype not in (None, torch.float32):
@@ -1264,29 +1244,9 @@ def _band_shard_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
     geom += (C.byref(qs), C.byref(ks))
     if f32:
         name += "_f32"
-        entry32 = getattr(lib, name)
-        o32 = empty(q.shape, dtype=torch.float32, device=q.device)
-
-        def call32(q, k, v, lay):
-            return entry32(q.data_ptr(), k.data_ptr(), v.data_ptr(), o32.data_ptr(), lse.data_ptr(), *geom, lay, _stream())
-
-        if q.is_contiguous() and k.is_contiguous() and v.is_contiguous():
-            _check(call32(q, k, v, None), name)
-        elif not _window_views(q, k, v, q, name, lambda lay: call32(q, k, v, C.byref(lay))):
-            _check(call32(q.contiguous(), k.contiguous(), v.contiguous(), None), name)
-        return o32, lse
-    entry = getattr(lib, name)
-
-    def run(q, k, v, out):
-        o = empty_like(q, memory_format=torch.contiguous_format) if out is None else out
-        if q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and o.is_contiguous():
-            _check(entry(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), *geom, None, _stream()), name)
-            return o
-        ok = _window_views(q, k, v, o, name, lambda lay: entry(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), *geom, C.byref(lay), _stream()))
-        return o if ok else None
-
-    return _run_or_copy(run, (q, k, v), out), lse
+    p = _layout_plan(q, k, v, o=_O32 if f32 else _O16, out=out)
+    _check(getattr(lib, name)(p.q.data_ptr(), p.k.data_ptr(), p.v.data_ptr(), p.o.data_ptr(), lse.data_ptr(), *geom, p.lay, _stream()), name)
+    return p.result(), lse
 
 
 # (The public name is bound by assignment: the coverage walk of tests/test_gpu_poison.py lists the `def`s of this module that allocate and
@@ -1322,7 +1282,8 @@ def cross_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, sm_scale:
                     out: Optional[torch.Tensor] = None, return_lse: bool = False, out_dtype: Optional[torch.dtype] = None):
     """Dense attention of q [B, H, Sq, D] over k, v [B, H, Skv, D] (or [BH, S, D]; Sq != Skv allowed) -> o of q's shape: softmax(q k^T
     * sm_scale) v per head (svg_cross_attention: head_dim 128, bf16 / fp16).  Strided views with stride(-1) == 1 (projection outputs,
-    slices of a fused k/v projection) are read in place; views the layout cannot describe are copied.  token_major_out: as band_attention.
+    slices of a fused k/v projection) are read in place (always through a layout; layouts and copies: _layout_plan).  token_major_out: as
+    band_attention.
     return_lse: (o, lse) with lse the row log-sum-exp of the scaled scores (natural log), contiguous fp32 of shape q.shape[:-1] — what
     merge_attention_states takes (svg_cross_attention_lse); o has the same bits as without.
     out_dtype=torch.float32 (with return_lse=True, without out / token_major_out; ValueError otherwise): (o32, lse) with o32 the rows
@@ -1361,35 +1322,25 @@ def _cross_attention(q, k, v, kv_begin, kv_end, sm_scale, token_major_out, out, 
         n = kv_end.numel()
         assert kv_end.dtype == torch.int32 and n > 0 and BH % n == 0, "kv_end: int32, BH % numel == 0"
         assert kv_begin is None or (kv_begin.dtype == torch.int32 and kv_begin.numel() == n), "kv_begin: int32, as many entries as kv_end"
-    # (contiguous [BH, Sq] whatever the layout of q / o; written whole by every launch, so a retry after a layout fall-back reuses it)
+    # (contiguous [BH, Sq] whatever the layout of q / o)
     lse = empty(q.shape[:-1], dtype=torch.float32, device=q.device) if return_lse else None
+    p = _layout_plan(q, k, v, o=_O32 if f32 else _O16, out=out, token_major_out=token_major_out, null_layout=False)
+    q, k, v, o = p.q, p.k, p.v, p.o
     if f32:
-        o32 = empty(q.shape, dtype=torch.float32, device=q.device)
-
-        def call(q, k, v):
-            return _q_views(q, k, v, "svg_cross_attention_lse_f32", lambda lay: lib.svg_cross_attention_lse_f32(
-                q.data_ptr(), k.data_ptr(), v.data_ptr(), o32.data_ptr(), lse.data_ptr(), BH, Sq, Skv, D, _dtype_code(q), scale, _ptr(kv_begin),
-                _ptr(kv_end), BH // n, C.byref(lay), _stream()))
-
-        if not call(q, k, v):   # (what the layout cannot describe is copied)
-            ok = call(q.contiguous(), k.contiguous(), v.contiguous())
-            assert ok
-        return o32, lse
-
-    def run(q, k, v, out):
-        if return_lse:
-            return _try_strided(q, k, v, out, token_major_out, "svg_cross_attention_lse", lambda o4, lay: lib.svg_cross_attention_lse(
-                q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), lse.data_ptr(), BH, Sq, Skv, D, _dtype_code(q), scale, _ptr(kv_begin),
-                _ptr(kv_end), BH // n, C.byref(lay), _stream()))
-        if kv_end is None:
-            return _try_strided(q, k, v, out, token_major_out, "svg_cross_attention", lambda o4, lay: lib.svg_cross_attention(
-                q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), BH, Sq, Skv, D, _dtype_code(q), scale, C.byref(lay), _stream()))
-        return _try_strided(q, k, v, out, token_major_out, "svg_cross_attention_keyrange", lambda o4, lay: lib.svg_cross_attention_keyrange(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), BH, Sq, Skv, D, _dtype_code(q), scale, _ptr(kv_begin), kv_end.data_ptr(),
-            BH // n, C.byref(lay), _stream()))
-
-    o = _run_or_copy(run, (q, k, v), out)
-    return (o, lse) if return_lse else o
+        _check(lib.svg_cross_attention_lse_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), BH, Sq, Skv, D,
+                                               _dtype_code(q), scale, _ptr(kv_begin), _ptr(kv_end), BH // n, p.lay, _stream()),
+               "svg_cross_attention_lse_f32")
+    elif return_lse:
+        _check(lib.svg_cross_attention_lse(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), BH, Sq, Skv, D,
+                                           _dtype_code(q), scale, _ptr(kv_begin), _ptr(kv_end), BH // n, p.lay, _stream()),
+               "svg_cross_attention_lse")
+    elif kv_end is None:
+        _check(lib.svg_cross_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), BH, Sq, Skv, D, _dtype_code(q), scale, p.lay,
+                                       _stream()), "svg_cross_attention")
+    else:
+        _check(lib.svg_cross_attention_keyrange(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), BH, Sq, Skv, D, _dtype_code(q), scale,
+                                                _ptr(kv_begin), kv_end.data_ptr(), BH // n, p.lay, _stream()), "svg_cross_attention_keyrange")
+    return (p.result(), lse) if return_lse else p.result()
 
 
 MERGE_MAX_PARTS = 8   # svg_merge_attention_states: the part pointers travel in the kernel arguments
@@ -1431,40 +1382,16 @@ def merge_attention_states(o_parts: Sequence[torch.Tensor], lse_parts: Sequence[
     # (parts are contiguous by contract; one that is not — or not 16-byte aligned — is copied, as the cross-attention entries copy)
     o_c = [t if t.is_contiguous() and t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format) for t in o_parts]
     l_c = [t.contiguous() for t in lse_parts]
-    x4 = _view4(x)
     if out is not None:
         assert out.shape == x.shape and out.dtype == odt
-    if out is not None:
-        o4 = _view4(out)
-    elif token_major_out:   # (token_major_empty, in the output dtype)
-        o4 = empty((x4.shape[0], x4.shape[2], x4.shape[1], x4.shape[3]), dtype=odt, device=x.device).permute(0, 2, 1, 3)
-    else:
-        o4 = empty(x4.shape, dtype=odt, device=x.device)
-    direct = _strided_ok(o4)
-    dst4 = o4 if direct else empty(x4.shape, dtype=odt, device=x.device)
+    p = _layout_plan(x, x, x, out=out, token_major_out=token_major_out, o_dtype=odt, null_layout=False, inputs_as_given=True)
     lse = empty(x.shape[:-1], dtype=torch.float32, device=x.device) if return_lse else None
     op = (C.c_void_p * MERGE_MAX_PARTS)(*[t.data_ptr() for t in o_c], *([None] * (MERGE_MAX_PARTS - n)))
     lp = (C.c_void_p * MERGE_MAX_PARTS)(*[t.data_ptr() for t in l_c], *([None] * (MERGE_MAX_PARTS - n)))
-    lay = attn_layout(x4, x4, x4, dst4)
     name = "svg_merge_attention_states_f32" if f32 else "svg_merge_attention_states"
-    rc = getattr(lib, name)(C.cast(op, _VP), C.cast(lp, _VP), n, dst4.data_ptr(), _ptr(lse), BH, Sq, D, _dtype_code(dst4), C.byref(lay), _stream())
+    rc = getattr(lib, name)(C.cast(op, _VP), C.cast(lp, _VP), n, p.o.data_ptr(), _ptr(lse), BH, Sq, D, _dtype_code(p.o), p.lay, _stream())
     _check(rc, name)
-    if not direct:   # an output the layout cannot describe
-        o4.copy_(dst4)
-    o = out if out is not None else (o4 if x.dim() == 4 else o4.squeeze(0))
-    return (o, lse) if return_lse else o
-
-
-def _run_or_copy(run, tensors, out):
-    """run(*tensors, out) -> o, or None where a layout cannot describe a view: the fall-backs of the cross-attention entries"""
-    o = run(*tensors, out)
-    if o is None:   # (what the layout cannot describe is copied, as the reference does)
-        tensors = tuple(t.contiguous() for t in tensors)
-        o = run(*tensors, out)
-    if o is None:   # ... and so is an output it cannot describe
-        out.copy_(run(*tensors, None))
-        o = out
-    return o
+    return (p.result(), lse) if return_lse else p.result()
 
 
 def cross_attention_pair(q: torch.Tensor, k_a: torch.Tensor, v_a: torch.Tensor, k_b: torch.Tensor, v_b: torch.Tensor,
@@ -1480,19 +1407,11 @@ def cross_attention_pair(q: torch.Tensor, k_a: torch.Tensor, v_a: torch.Tensor, 
     BH = q.numel() // (Sq * D)
     scale = _sm_scale(sm_scale, D)
 
-    def run(q, k_a, v_a, k_b, v_b, out):
-        kb4, vb4 = _view4(k_b), _view4(v_b)
-        if not (_strided_ok(kb4, True) and _strided_ok(vb4, True)):
-            return None
-
-        def call(o4, lay):
-            lay_b = attn_layout(_view4(q), kb4, vb4, o4)   # (its k / v strides are what the entry reads)
-            return lib.svg_cross_attention_pair(q.data_ptr(), k_a.data_ptr(), v_a.data_ptr(), k_b.data_ptr(), v_b.data_ptr(), o4.data_ptr(), BH,
-                                                Sq, k_a.shape[-2], k_b.shape[-2], D, _dtype_code(q), scale, C.byref(lay), C.byref(lay_b), _stream())
-
-        return _try_strided(q, k_a, v_a, out, token_major_out, "svg_cross_attention_pair", call)
-
-    return _run_or_copy(run, (q, k_a, v_a, k_b, v_b), out)
+    p = _layout_plan(q, k_a, v_a, k_b, v_b, out=out, token_major_out=token_major_out, null_layout=False)
+    _check(lib.svg_cross_attention_pair(p.q.data_ptr(), p.k.data_ptr(), p.v.data_ptr(), p.k_b.data_ptr(), p.v_b.data_ptr(), p.o.data_ptr(), BH,
+                                        Sq, k_a.shape[-2], k_b.shape[-2], D, _dtype_code(q), scale, p.lay, p.lay_b, _stream()),
+           "svg_cross_attention_pair")
+    return p.result()
 
 
 def varblock_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_map: torch.Tensor, q_sizes: torch.Tensor,
@@ -1537,25 +1456,9 @@ def varblock_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_
     if kv_row_idx is not None:
         assert kv_row_idx.dtype == torch.int32 and kv_row_idx.shape == (Hkv, Skv)
     scale = _sm_scale(sm_scale, D)
-    dense_in = q.is_contiguous() and k.is_contiguous() and v.is_contiguous()
-    if (not dense_in or token_major_out) and not fp8 and variant == -1 and strided_attention_supported(q) and Sq >= 160 * QB:
-        def call(o4, lay):
-            if not rows_covered:
-                o4.zero_()
-            need = int(lib.svg_varblock_workspace_bytes(Hq, Hkv, QB, KB, Sq))
-            ws = empty(need, dtype=torch.uint8, device=q.device) if workspace is None else workspace
-            _dev(ws)
-            assert ws.dtype == torch.uint8 and ws.numel() >= need
-            return lib.svg_varblock_attention_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), Hq, Hkv, Sq, Skv, D,
-                                                      _dtype_code(q), scale, block_map.data_ptr(), q_sizes.data_ptr(), k_sizes.data_ptr(),
-                                                      QB, KB, _ptr(q_row_idx), _ptr(kv_row_idx), ws.data_ptr(), ws.numel(), C.byref(lay),
-                                                      _stream())
-
-        o = _try_strided(q, k, v, None, token_major_out, "svg_varblock_attention_strided", call)
-        if o is not None:
-            return o
-    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()   # (what the strided entry point does not take is copied)
-    o = empty_like(q) if rows_covered else torch.zeros_like(q)
+    p = _layout_plan(q, k, v, token_major_out=token_major_out, views_on_copies=False, zero_o=not rows_covered,
+                     views=not fp8 and variant == -1 and strided_attention_supported(q) and Sq >= 160 * QB)
+    q, k, v, o = p.q, p.k, p.v, p.o
     if fp8:
         need = int(lib.svg_varblock_attention_fp8_workspace_bytes(Hq, Hkv, QB, KB, Sq, Skv, D))
         if need == 0:
@@ -1573,6 +1476,12 @@ def varblock_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_
     ws = empty(need, dtype=torch.uint8, device=q.device) if workspace is None else workspace
     _dev(ws)
     assert ws.dtype == torch.uint8 and ws.numel() >= need
+    if p.lay is not None:
+        rc = lib.svg_varblock_attention_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), Hq, Hkv, Sq, Skv, D,
+                                                _dtype_code(q), scale, block_map.data_ptr(), q_sizes.data_ptr(), k_sizes.data_ptr(),
+                                                QB, KB, _ptr(q_row_idx), _ptr(kv_row_idx), ws.data_ptr(), ws.numel(), p.lay, _stream())
+        _check(rc, "svg_varblock_attention_strided")
+        return o
     rc = lib.svg_varblock_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), Hq, Hkv, Sq, Skv, D,
                                     _dtype_code(q), scale, block_map.data_ptr(), q_sizes.data_ptr(), k_sizes.data_ptr(),
                                     QB, KB, _ptr(q_row_idx), _ptr(kv_row_idx), ws.data_ptr(), ws.numel(), variant,
@@ -1583,8 +1492,8 @@ def varblock_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_
 
 def _varblock_attention_lse(q, k, v, block_map, q_sizes, k_sizes, sm_scale, q_row_idx, kv_row_idx, workspace, token_major_out, rows_covered,
                             f32=False):
-    """varblock_attention(return_lse=True): svg_varblock_attention_lse (f32: svg_varblock_attention_lse_f32) — without a layout for contiguous tensors, on views otherwise; what
-    the layout cannot describe is copied.  Never an entry without lse."""
+    """varblock_attention(return_lse=True): svg_varblock_attention_lse (f32: svg_varblock_attention_lse_f32), never an entry without lse.
+    Layouts and copies: _layout_plan."""
     lib = load()
     _dev(block_map, q_sizes, k_sizes, q_row_idx, kv_row_idx)
     _gpu(q, k, v)
@@ -1607,38 +1516,19 @@ def _varblock_attention_lse(q, k, v, block_map, q_sizes, k_sizes, sm_scale, q_ro
     lse = empty(q.shape[:-1], dtype=torch.float32, device=q.device)
     if not rows_covered:
         lse.fill_(float("-inf"))
-
+    p = _layout_plan(q, k, v, o=_O32 if f32 else _O16, token_major_out=token_major_out, zero_o=not rows_covered)
+    q, k, v, o = p.q, p.k, p.v, p.o
     if f32:
-        o32 = empty(q.shape, dtype=torch.float32, device=q.device)
-        if not rows_covered:
-            o32.zero_()
-
-        def call(q, k, v, lay):
-            return lib.svg_varblock_attention_lse_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), o32.data_ptr(), lse.data_ptr(), Hq, Hkv, Sq, Skv,
-                                                      D, _dtype_code(q), scale, block_map.data_ptr(), q_sizes.data_ptr(), k_sizes.data_ptr(),
-                                                      QB, KB, _ptr(q_row_idx), _ptr(kv_row_idx), ws.data_ptr(), ws.numel(), lay, _stream())
-
-        if q.is_contiguous() and k.is_contiguous() and v.is_contiguous():
-            _check(call(q, k, v, None), "svg_varblock_attention_lse_f32")
-        elif not _q_views(q, k, v, "svg_varblock_attention_lse_f32", lambda lay: call(q, k, v, C.byref(lay))):
-            _check(call(q.contiguous(), k.contiguous(), v.contiguous(), None), "svg_varblock_attention_lse_f32")
-        return o32, lse
-
-    def launch(q, k, v, o, lay):
-        if not rows_covered:
-            o.zero_()
-        return lib.svg_varblock_attention_lse(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), Hq, Hkv, Sq, Skv, D,
-                                              _dtype_code(q), scale, block_map.data_ptr(), q_sizes.data_ptr(), k_sizes.data_ptr(), QB, KB,
-                                              _ptr(q_row_idx), _ptr(kv_row_idx), ws.data_ptr(), ws.numel(), lay, _stream())
-
-    def run(q, k, v, out):
-        if q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and not token_major_out:
-            o = empty_like(q)
-            _check(launch(q, k, v, o, None), "svg_varblock_attention_lse")
-            return o
-        return _try_strided(q, k, v, None, token_major_out, "svg_varblock_attention_lse", lambda o4, lay: launch(q, k, v, o4, C.byref(lay)))
-
-    return _run_or_copy(run, (q, k, v), None), lse
+        rc = lib.svg_varblock_attention_lse_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), Hq, Hkv, Sq, Skv, D,
+                                                _dtype_code(q), scale, block_map.data_ptr(), q_sizes.data_ptr(), k_sizes.data_ptr(), QB, KB,
+                                                _ptr(q_row_idx), _ptr(kv_row_idx), ws.data_ptr(), ws.numel(), p.lay, _stream())
+        _check(rc, "svg_varblock_attention_lse_f32")
+    else:
+        rc = lib.svg_varblock_attention_lse(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), Hq, Hkv, Sq, Skv, D,
+                                            _dtype_code(q), scale, block_map.data_ptr(), q_sizes.data_ptr(), k_sizes.data_ptr(), QB, KB,
+                                            _ptr(q_row_idx), _ptr(kv_row_idx), ws.data_ptr(), ws.numel(), p.lay, _stream())
+        _check(rc, "svg_varblock_attention_lse")
+    return o, lse
 
 
 def varblock_workspace(Hq: int, Hkv: int, QB: int, KB: int, Sq: int, device) -> torch.Tensor:
@@ -1711,7 +1601,7 @@ def sample_mse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rows: torch.Te
                sm_scale: Optional[float] = None, skip_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q,k,v [BH, S, D] (or [B, H, S, D]: BH = B * H); rows int64 [R] (device) -> mse float32 [2, BH].  skip_flag (int32 [1] on the
     GPU) != 0: the kernels return at once and the result is undefined (a dense step does not use it).
-    Strided views are read in place by svg_sample_mse_strided (bf16: the second form of the kernel) and copied otherwise."""
+    Strided views are read in place by svg_sample_mse_strided (bf16: the second form of the kernel); layouts and copies: _layout_plan."""
     lib = load()
     _dev(rows, skip_flag)
     _gpu(q, k, v)
@@ -1721,30 +1611,24 @@ def sample_mse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rows: torch.Te
     out = empty((2, BH), dtype=torch.float32, device=q.device)
     ws = empty(lib.svg_sample_mse_workspace_bytes(BH, R, D, S), dtype=torch.uint8, device=q.device)
     scale = _sm_scale(sm_scale, D)
-    if not (q.is_contiguous() and k.is_contiguous() and v.is_contiguous()) and q.dtype == torch.bfloat16:
-        q4, k4, v4 = _view4(q), _view4(k), _view4(v)
-        if _strided_ok(q4) and _strided_ok(k4, True) and _strided_ok(v4, True):
-            if skip_flag is not None:
-                assert skip_flag.dtype == torch.int32
-                out.zero_()
-            lay = attn_layout(q4, k4, v4, q4)
-            rc = lib.svg_sample_mse_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(), rows.data_ptr(), R, BH, S, D, _dtype_code(q), scale,
-                                            C.byref(prof), out.data_ptr(), ws.data_ptr(), ws.numel(), _ptr(skip_flag), C.byref(lay),
-                                            _stream())
-            _check(rc, "svg_sample_mse_strided")
-            return out
-    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     if skip_flag is not None:
         assert skip_flag.dtype == torch.int32
         out.zero_()
+    p = _layout_plan(q, k, v, o=_NO_O, views=q.dtype == torch.bfloat16)   # (the strided form is the kernel's second form: bf16)
+    q, k, v = p.q, p.k, p.v
+    if p.lay is not None:
+        rc = lib.svg_sample_mse_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(), rows.data_ptr(), R, BH, S, D, _dtype_code(q), scale,
+                                        C.byref(prof), out.data_ptr(), ws.data_ptr(), ws.numel(), _ptr(skip_flag), p.lay, _stream())
+        _check(rc, "svg_sample_mse_strided")
+    elif skip_flag is not None:
         rc = lib.svg_sample_mse_flagged(q.data_ptr(), k.data_ptr(), v.data_ptr(), rows.data_ptr(), R, BH, S, D, _dtype_code(q),
                                         scale, C.byref(prof), out.data_ptr(), ws.data_ptr(), ws.numel(), skip_flag.data_ptr(),
                                         _stream())
         _check(rc, "svg_sample_mse_flagged")
-        return out
-    rc = lib.svg_sample_mse(q.data_ptr(), k.data_ptr(), v.data_ptr(), rows.data_ptr(), R, BH, S, D, _dtype_code(q), scale,
-                            C.byref(prof), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
-    _check(rc, "svg_sample_mse")
+    else:
+        rc = lib.svg_sample_mse(q.data_ptr(), k.data_ptr(), v.data_ptr(), rows.data_ptr(), R, BH, S, D, _dtype_code(q), scale,
+                                C.byref(prof), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+        _check(rc, "svg_sample_mse")
     return out
 
 
@@ -1761,7 +1645,7 @@ def _sample_mse_shard_partial(q_rows: torch.Tensor, k: torch.Tensor, v: torch.Te
     [BH, Sk, D] the rows of k_shard (BandShard or (f0, n_frames, tail_begin, n_tail)) of a sequence of num_tokens rows whose video prof
     describes (prof.vid0 == 0) -> part fp32 [3, BH, R, D + 4]: per output (golden, variant 0, variant 1), head and row — in the kernel's rank
     order, a function of rows alone — the un-normalised O, then m (log2 domain), l, 0, 0.  Parts of shards that cover the keys go to
-    sample_mse_from_parts.  Strided k / v views are read in place through the layout and copied where it cannot describe them.
+    sample_mse_from_parts.  Layouts and copies of k / v: _layout_plan.
     skip_flag (int32 [1] on the GPU) != 0: the kernels return at once and part is left as allocated.  bf16, head_dim 128, R <= 64; anything
     else raises — there is no fall-back."""
     lib = load()
@@ -1790,16 +1674,10 @@ def _sample_mse_shard_partial(q_rows: torch.Tensor, k: torch.Tensor, v: torch.Te
     part = empty((3, BH, R, D + 4), dtype=torch.float32, device=k.device)
     ws = empty(lib.svg_sample_mse_shard_workspace_bytes(BH, R, D, Sk), dtype=torch.uint8, device=k.device)
     q_rows = q_rows.contiguous()
-    lay = None
-    if not (k.is_contiguous() and v.is_contiguous()):
-        k4, v4 = _view4(k), _view4(v)
-        if _strided_ok(k4, True) and _strided_ok(v4, True):
-            lay = C.byref(attn_layout(k4, k4, v4, k4))
-        else:
-            k, v = k.contiguous(), v.contiguous()
-    rc = lib.svg_sample_mse_shard_partial(q_rows.data_ptr(), k.data_ptr(), v.data_ptr(), rows.data_ptr(), R, BH, S, D, _dtype_code(k),
+    p = _layout_plan(k, k, v, o=_NO_O)   # (k and v alone: the layout's q and o members take k's strides)
+    rc = lib.svg_sample_mse_shard_partial(q_rows.data_ptr(), p.k.data_ptr(), p.v.data_ptr(), rows.data_ptr(), R, BH, S, D, _dtype_code(k),
                                           _sm_scale(sm_scale, D), C.byref(prof), C.byref(ks), part.data_ptr(), ws.data_ptr(), ws.numel(),
-                                          _ptr(skip_flag), lay, _stream())
+                                          _ptr(skip_flag), p.lay, _stream())
     _check(rc, "svg_sample_mse_shard_partial")
     return part
 

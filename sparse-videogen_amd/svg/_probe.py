@@ -6,7 +6,6 @@ The allocating wrapper lives here, not in svg/_native.py: that module's public f
 and workspace come from _native.empty like every allocation of the package."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import torch
@@ -29,8 +28,8 @@ def check_rows(rows: torch.Tensor, S: int) -> None:
 
 def sample_dense_rows(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rows: torch.Tensor, valid_len: Optional[int] = None,
                       sm_scale: Optional[float] = None):
-    """q, k, v [cfg, H, S, D] views (bf16 / fp16, head_dim 64 / 128; token-major views are read in place, anything the strided entry cannot
-    take is copied); rows int64 [R], R <= 64, CPU (checked against [0, S), then uploaded) or device (the caller's fault) -> (o32 [cfg, H, R, D]
+    """q, k, v [cfg, H, S, D] views (bf16 / fp16, head_dim 64 / 128; token-major views are read in place, what the layout cannot describe is
+    copied: _native._layout_plan); rows int64 [R], R <= 64, CPU (checked against [0, S), then uploaded) or device (the caller's fault) -> (o32 [cfg, H, R, D]
     fp32, lse [cfg, H, R] fp32): dense attention of the sampled rows over the keys dense_attention(valid_len=) gives them, natural-log lse.
     Duplicate rows are allowed, the order is kept."""
     if q.dim() != 4 or k.shape != q.shape or v.shape != q.shape:
@@ -46,15 +45,9 @@ def sample_dense_rows(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rows: t
     ws = _native.empty(lib.svg_sample_dense_rows_workspace_bytes(BH, R, D, S), dtype=torch.uint8, device=q.device)
     scale = _native._sm_scale(sm_scale, D)
     vl = 0 if valid_len is None else int(valid_len)
-    lay = None
-    if not (q.is_contiguous() and k.is_contiguous() and v.is_contiguous()):
-        if _native._strided_ok(q) and _native._strided_ok(k, True) and _native._strided_ok(v, True):
-            lay = _native.attn_layout(q, k, v, q)
-        else:
-            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-    rc = lib.svg_sample_dense_rows(q.data_ptr(), k.data_ptr(), v.data_ptr(), rows.data_ptr(), R, BH, S, D, _native._dtype_code(q), scale, vl,
-                                   o32.data_ptr(), lse.data_ptr(), ws.data_ptr(), ws.numel(), C.byref(lay) if lay is not None else None,
-                                   _native._stream())
+    p = _native._layout_plan(q, k, v, o=_native._NO_O)
+    rc = lib.svg_sample_dense_rows(p.q.data_ptr(), p.k.data_ptr(), p.v.data_ptr(), rows.data_ptr(), R, BH, S, D, _native._dtype_code(q), scale, vl,
+                                   o32.data_ptr(), lse.data_ptr(), ws.data_ptr(), ws.numel(), p.lay, _native._stream())
     _native._check(rc, "svg_sample_dense_rows")
     return o32, lse
 

@@ -67,7 +67,7 @@ def test_sparse_lse_header_prototypes_match_the_ctypes_signatures_and_call_sites
         if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr in nat.SPARSE_LSE_SIGNATURES:
             assert not node.keywords and len(node.args) == len(nat.SPARSE_LSE_SIGNATURES[node.func.attr][1]), (node.func.attr, node.lineno)
             checked += 1
-    assert checked == 3                                  # band: without and with a layout; variable-block: one call
+    assert checked == 2                                  # one call site per entry: the layout (or NULL) is an argument
 
 
 # ---------------------------------------------------------------------------------------------------------
