@@ -346,7 +346,9 @@ __global__ __launch_bounds__(256) void kmeans_update_kernel(const T* __restrict_
         __syncthreads();
         if (tid == 0) {
             const float nr = sqrtf(nrm[0] + nrm[1] + nrm[2] + nrm[3]);
-            atomicMax((int*)(shift + b), __float_as_int(nr));  // non-negative floats order like ints
+            // non-negative floats order like ints, and so does a NaN whose sign bit is clear — above all of them; one whose sign bit is set
+            // (it keeps the sign of the input's) is a negative int and would lose against the 0 the shift starts from: the canonical NaN
+            atomicMax((int*)(shift + b), nr != nr ? 0x7FC00000 : __float_as_int(nr));
         }
         if (kn >= K) break;
         k = kn, cnt = cnt_n, start = start_n;

@@ -899,6 +899,9 @@ def _centroid_like(BH, QC, KC, D, dtype, seed):
     (2, 33, 257, 64, 0.95, 0.05, torch.float16), (2, 64, 4096, 128, 0.9, 0.0, torch.bfloat16),
     (24, 400, 1000, 128, 0.9, 0.1, torch.bfloat16),     # HunyuanVideo 720p SAP: scripts/hyvideo/hyvideo_t2v_720p_sap.sh
     (40, 300, 1000, 128, 0.9, 0.1, torch.bfloat16),     # Wan 2.1 720p SAP: scripts/wan/wan_t2v_720p_sap.sh
+    # the edges of the two kernel forms (256 < KC <= 1024: one workgroup per 16 query clusters; otherwise one per row)
+    (2, 17, 256, 64, 0.9, 0.1, torch.bfloat16), (2, 17, 257, 128, 0.9, 0.1, torch.float16), (2, 16, 1024, 128, 0.9, 0.0, torch.bfloat16),
+    (2, 3, 1025, 64, 0.95, 0.05, torch.float16), (2, 1, 300, 128, 0.9, 0.1, torch.bfloat16),
 ])
 def test_identify_dynamic_map(nat, BH, QC, KC, D, p, ratio, dtype):
     """Block-map indices are BIT-EXACT (north_star): the kernel equals the oracle's exact mode entry for entry — random and
@@ -925,3 +928,28 @@ def test_identify_dynamic_map(nat, BH, QC, KC, D, p, ratio, dtype):
     d = nat.map_density(dev(ref), dev(torch.full((BH, QC), 5, dtype=torch.int32)), dev(ksz)).cpu()
     dref = O.density_calculation(ref[None], torch.full((1, BH, QC), 5), ksz[None].long())[0]
     torch.testing.assert_close(d, dref.float(), rtol=1e-5, atol=1e-6)
+
+
+def _all_tied_map_case(KC, D, dtype):
+    """head 0: every key centroid the same vector and every size equal — all KC probabilities of a row tie; head 1: random.  -> the inputs,
+    the oracle's exact-mode map"""
+    BH, QC, p = 2, 17, 0.5
+    g = torch.Generator().manual_seed(KC + D)
+    qc, kc = torch.randn(BH, QC, D, generator=g).to(dtype), torch.randn(BH, KC, D, generator=g).to(dtype)
+    kc[0] = kc[0, :1]
+    ksz = torch.randint(1, 300, (BH, KC), dtype=torch.int32, generator=g)
+    ksz[0] = 37
+    return qc, kc, ksz, p, O.identify_dynamic_map(qc[None], kc[None], None, ksz[None], p, 0.0, exact=True)[0]
+
+
+@pytest.mark.parametrize("KC,D,dtype", [(100, 64, torch.bfloat16), (300, 128, torch.float16)])   # one case per kernel form
+def test_identify_dynamic_map_all_probabilities_tie(nat, KC, D, dtype):
+    """ties -> the lower cluster index (the stable sort of the reference's order): with every probability of a row equal, the kept set is
+    the lowest indices up to the cut"""
+    qc, kc, ksz, p, ref = _all_tied_map_case(KC, D, dtype)
+    kept = ref[0].sum(-1)
+    assert (kept > 1).all() and (kept < KC).all()                                           # the cut is inside the row
+    assert torch.equal(ref[0], torch.arange(KC)[None, :] < kept[:, None])                   # the oracle: a prefix of the indices
+    got = nat.identify_dynamic_map(dev(qc), dev(kc), dev(ksz), p, 0).cpu()
+    assert torch.equal(got[0], ref[0]), f"tied head: kept {got[0].sum(-1).tolist()}, a prefix of {kept.tolist()} expected"
+    assert torch.equal(got, ref)

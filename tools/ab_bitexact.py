@@ -16,6 +16,7 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "sparse-videogen_amd"))
 sys.path.insert(0, str(ROOT))
+sys.path.append(str(ROOT / "tests"))   # tests.test_gpu_fullsize_svg2 (the SVG2 cases) imports its neighbours (poisoned) by their bare names
 import torch  # noqa: E402
 from svg import _native as nat  # noqa: E402
 from svg.models.hyvideo import utils as hy  # noqa: E402
