@@ -166,6 +166,38 @@ __global__ __launch_bounds__(512, 2) void band_attn_m16_switch_kernel(typename P
     if (flag[0] != 0) attn_body_m16<T, Pol, false, 1, PRE, !PRE>(prm_alt, smem, nullptr, &g_band_replays);
     else attn_body_m16<T, Pol, false, 1, PRE, !PRE>(prm, smem, nullptr, &g_band_replays);
 }
+// One band per head (svg_band_attention_per_head_lse, include/svg_attn_adaptive_band.h): BandPerHeadLsePolicy (band_policy.h) on the static
+// mapping, the template arguments of the body those of band_attn_m16_kernel.  Two parameter blocks that differ in their row
+// regions alone — prm: a band that cuts the full rows out, prm_wide: one above S, which does not (band_row_regions) — and the head's band
+// picks; the blocks are kernel arguments as they are (a patched copy of one lives in private memory: the selects of kv_schedule index it).
+template <typename T>
+__global__ __launch_bounds__(512, 2) void band_attn_m16_per_head_kernel(typename BandPerHeadLsePolicy<T>::Params prm,
+                                                                        typename BandPerHeadLsePolicy<T>::Params prm_wide) {
+    using Pol = BandPerHeadLsePolicy<T>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int head, qt;
+    if (!Pol::map_block(prm, head, qt)) return;
+    if (Pol::per_head_band_of(prm, head) > prm.S) attn_body_m16<T, Pol, false, 1, false, true>(prm_wide, smem, nullptr, &g_band_replays);
+    else attn_body_m16<T, Pol, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
+}
+// ... with the device switch in front (svg_band_attention_switch_per_head_lse): `flag[0] != 0` runs prm_alt — the alternate mask as it is, no
+// band vector and no head flags — on the same grid; per (head, q-tile) the body does what band_attn_m16_switch_kernel's does under that flag
+template <typename T>
+__global__ __launch_bounds__(512, 2) void band_attn_m16_per_head_switch_kernel(typename BandPerHeadLsePolicy<T>::Params prm,
+                                                                               typename BandPerHeadLsePolicy<T>::Params prm_wide,
+                                                                               typename BandPerHeadLsePolicy<T>::Params prm_alt,
+                                                                               const int32_t* __restrict__ flag) {
+    using Pol = BandPerHeadLsePolicy<T>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (flag[0] != 0) {
+        attn_body_m16<T, Pol, false, 1, false, true>(prm_alt, smem, nullptr, &g_band_replays);
+        return;
+    }
+    int head, qt;
+    if (!Pol::map_block(prm, head, qt)) return;
+    if (Pol::per_head_band_of(prm, head) > prm.S) attn_body_m16<T, Pol, false, 1, false, true>(prm_wide, smem, nullptr, &g_band_replays);
+    else attn_body_m16<T, Pol, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
+}
 // the same for q that carries sm_scale * log2(e) (svg_band_attention_prescaled): no scale-and-shift per score
 template <typename T, int D>
 __global__ __launch_bounds__(512, 2) void band_attn_pp2q_kernel(typename BandPolicy<T, D, 8>::Params prm) {
@@ -790,6 +822,63 @@ extern "C" int svg_band_attention_switch_lse_f32(const void* q, const void* k, c
                                                  const int32_t* use_alt_flag, const svg_attn_layout_t* layout, void* stream) {
     if (!o32 || !lse) return SVG_ERR_BAD_ARG;
     return band_switch_lse(q, k, v, nullptr, o32, lse, BH, S, D, dtype, sm_scale, mask, perm, alt_mask, use_alt_flag, layout, stream);
+}
+
+// One band per head (include/svg_attn_adaptive_band.h): the checks of svg_band_attention[_switch]_lse in their order, then the per-head
+// kernels on the static mapping.  The parameter block is built for a band that cuts the full rows out (min(mask->band, S))
+// and once more for one that does not (S + 1); the kernel picks per head, and the policy reads the head's band where the block has the mask's.
+static int band_per_head_run(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S, int32_t D,
+                             int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const svg_band_mask_t* alt_mask,
+                             const int32_t* use_alt_flag, const int32_t* band, const svg_perm_desc_t* perm,
+                             const svg_attn_layout_t* layout, void* stream) {
+    int rc = band_check_args(q, k, v, o, BH, S, D, mask, perm);
+    if (rc == SVG_OK && alt_mask) rc = check_band_mask(S, alt_mask, nullptr);
+    if (rc != SVG_OK) return rc;
+    BandOpts opts;
+    opts.lse = lse;
+    opts.strided = layout != nullptr;
+    if (opts.strided && (rc = layout_from_abi(layout, BH, BH, S, S, D, q, k, v, o, opts.lay)) != SVG_OK) return rc;
+    if (D != 128) return SVG_ERR_UNSUPPORTED;
+    const hipStream_t st = (hipStream_t)stream;
+    return dispatch_td(dtype, D, [&](auto t, auto d) -> int {
+        using T = decltype(t);
+        if constexpr (decltype(d)::value != 128) {
+            return SVG_ERR_UNSUPPORTED;
+        } else {
+            using Pol = BandPerHeadLsePolicy<T>;
+            auto params = [&](const svg_band_mask_t* m, int band_of, const svg_perm_desc_t* pm, const int32_t* band_vec) {
+                svg_band_mask_t mm = *m;
+                mm.band = band_of;
+                typename Pol::Params p = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, &mm, pm, opts);
+                p.band_vec = band_vec;
+                p.map_nqt = p.nqt, p.map_n_heavy = p.n_heavy, p.map_heavy_lo = p.heavy_lo;
+                return p;
+            };
+            const typename Pol::Params p = params(mask, std::min(mask->band, S), perm, band);
+            typename Pol::Params w = params(mask, S + 1, perm, band);
+            if (w.nqt > p.nqt) return SVG_ERR_LAUNCH;   // (fewer cuts never make more q-tiles: band_row_regions)
+            w.map_nqt = p.map_nqt, w.map_n_heavy = p.map_n_heavy, w.map_heavy_lo = p.map_heavy_lo;   // one mapping for both blocks
+            const int lds = attn_m16_lds_bytes() + kTailLds;
+            if (!use_alt_flag) return launch_attn(band_attn_m16_per_head_kernel<T>, dim3(p.nqt * BH), 512, lds, st, p, w);
+            const typename Pol::Params a = params(alt_mask, alt_mask->band, nullptr, nullptr);
+            return launch_attn(band_attn_m16_per_head_switch_kernel<T>, dim3(std::max(p.nqt, a.nqt) * BH), 512, lds, st, p, w, a, use_alt_flag);
+        }
+    });
+}
+
+extern "C" int svg_band_attention_per_head_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S,
+                                               int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const int32_t* band,
+                                               const svg_perm_desc_t* perm, const svg_attn_layout_t* layout, void* stream) {
+    if (!lse || !band) return SVG_ERR_BAD_ARG;
+    return band_per_head_run(q, k, v, o, lse, BH, S, D, dtype, sm_scale, mask, nullptr, nullptr, band, perm, layout, stream);
+}
+
+extern "C" int svg_band_attention_switch_per_head_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S,
+                                                      int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
+                                                      const svg_band_mask_t* alt_mask, const int32_t* use_alt, const int32_t* band,
+                                                      const svg_perm_desc_t* perm, const svg_attn_layout_t* layout, void* stream) {
+    if (!lse || !band || !alt_mask || !use_alt) return SVG_ERR_BAD_ARG;
+    return band_per_head_run(q, k, v, o, lse, BH, S, D, dtype, sm_scale, mask, alt_mask, use_alt, band, perm, layout, stream);
 }
 
 // svg_band_groups_attention: the heads of one call in groups of consecutive heads, each under a mask (and an alternate mask) of its

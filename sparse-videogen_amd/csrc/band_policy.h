@@ -4,6 +4,8 @@
 // attention_w4.hip, attention_f8.hip).  The launch helpers are svg_common.h; the variable-block policy is varblock_policy.h.
 #pragma once
 #include <algorithm>
+#include <type_traits>
+#include <utility>
 
 #include "attn_core.h"
 
@@ -39,6 +41,12 @@ inline int check_band_mask(int S, const svg_band_mask_t* mask, const svg_perm_de
     }
     return SVG_OK;
 }
+
+// does a policy's Ctx carry a band of its own (BandPerHeadLsePolicy: one band per head)?  See BandPolicy::band_of.
+template <typename C, typename = void>
+struct CtxHasBand : std::false_type {};
+template <typename C>
+struct CtxHasBand<C, std::void_t<decltype(std::declval<const C&>().band)>> : std::true_type {};
 
 // =====================================================================================================
 // Band policy: analytic mask family (see svg_band_mask_t in svg_attn.h)
@@ -102,6 +110,14 @@ struct BandPolicy : LayoutAccess<BandPolicy<T, D, NW, RB>> {
         return logical;
     }
 
+    // The band of the q-tile c describes: the launch's (p.band), unless the policy's Ctx carries one of its own.  Every reader of the band
+    // below goes through this with the type of the Ctx as a template argument; with this policy's own Ctx it is p.band and nothing else.
+    template <typename C>
+    static __host__ __device__ __forceinline__ int band_of(const Params& p, const C& c) {
+        if constexpr (CtxHasBand<C>::value) return c.band;
+        else return p.band;
+    }
+
     static __device__ __forceinline__ bool init(const Params& p, Ctx& c, char*) {
         // Work mapping.  The hardware hands dispatch id b to XCD b % 8 and each XCD schedules its share on its own 32 CUs, so the
         // load has to be balanced across XCDs by construction.
@@ -148,7 +164,8 @@ struct BandPolicy : LayoutAccess<BandPolicy<T, D, NW, RB>> {
     }
     // the fast-path interval [lo, hi] of first keys for the rows of wave `wave` of the q-tile c describes (empty: lo > hi).  Also evaluated on
     // the host (svg_debug_band_tile_run).
-    static __host__ __device__ __forceinline__ void wave_fast_interval(const Params& p, const Ctx& c, int wave, int& lo, int& hi) {
+    template <typename C>
+    static __host__ __device__ __forceinline__ void wave_fast_interval(const Params& p, const C& c, int wave, int& lo, int& hi) {
 #ifndef __HIP_DEVICE_COMPILE__   // (device: HIP's min / max, as init_tile always used them — std's select the other way round, and the
         using std::max;            //  listings of every kernel on this policy would move)
         using std::min;
@@ -158,14 +175,15 @@ struct BandPolicy : LayoutAccess<BandPolicy<T, D, NW, RB>> {
         lo = 1, hi = 0;
         if (w0 < c.q_end && w1 <= real) {
             const bool full_rows = w0 >= p.rf_lo && w1 <= p.rf_hi;   // a wave of full (text) rows: every key tile below real_len
-            lo = full_rows ? 0 : max(w1 - p.band, 0);
-            hi = min(full_rows ? real : w0 + p.band - kBN, min(real, p.S) - kBN);
+            lo = full_rows ? 0 : max(w1 - band_of(p, c), 0);
+            hi = min(full_rows ? real : w0 + band_of(p, c) - kBN, min(real, p.S) - kBN);
         }
     }
 
     // rows [q0, q_end) and key-tile segments of q-tile `qt` (row order); the same for every head.  Also evaluated on the host:
     // make_band_queue sorts the q-tiles of a launch by c.nT.
-    static __host__ __device__ __forceinline__ void kv_schedule(const Params& p, Ctx& c, int qt) {
+    template <typename C>
+    static __host__ __device__ __forceinline__ void kv_schedule(const Params& p, C& c, int qt) {
         using std::max;
         using std::min;
         // (explicit selects: a run-time index into the kernel-argument arrays would go through scratch)
@@ -187,8 +205,8 @@ struct BandPolicy : LayoutAccess<BandPolicy<T, D, NW, RB>> {
             if (c.q0 < p.rf_hi && qr1 > p.rf_lo) {
                 alo = 0, ahi = (real + kBN - 1) / kBN;
             } else {
-                alo = max(0, c.q0 - p.band + 1) / kBN;
-                ahi = (min(real, qr1 - 1 + p.band) + kBN - 1) / kBN;
+                alo = max(0, c.q0 - band_of(p, c) + 1) / kBN;
+                ahi = (min(real, qr1 - 1 + band_of(p, c)) + kBN - 1) / kBN;
                 const int ch = min(p.cf_hi, real);
                 if (ch > p.cf_lo) blo = p.cf_lo / kBN, bhi = (ch + kBN - 1) / kBN;
             }
@@ -453,7 +471,8 @@ struct BandPolicy : LayoutAccess<BandPolicy<T, D, NW, RB>> {
 #undef SVG_RUN_SEG
     }
 
-    static __device__ __forceinline__ int classify(const Params& p, const Ctx& c, int k0, int wrow0) {
+    template <typename C>
+    static __device__ __forceinline__ int classify(const Params& p, const C& c, int k0, int wrow0) {
         if (k0 >= c.fk_lo && k0 <= c.fk_hi) return TILE_FULL;
         const int w0 = c.q0 + wrow0;
         if (w0 >= c.q_end) return TILE_SKIP;
@@ -464,7 +483,7 @@ struct BandPolicy : LayoutAccess<BandPolicy<T, D, NW, RB>> {
         bool all = false;
         if (k0 + kBN <= p.S) {
             if (w1 <= real && k1 <= real) {
-                const bool band_all = (k1 - 1 - w0 < p.band) && (w1 - 1 - k0 < p.band);
+                const bool band_all = (k1 - 1 - w0 < band_of(p, c)) && (w1 - 1 - k0 < band_of(p, c));
                 const bool col_all = (k0 >= p.cf_lo && k1 <= p.cf_hi);
                 const bool row_all = (w0 >= p.rf_lo && w1 <= p.rf_hi);
                 all = band_all || col_all || row_all;
@@ -477,7 +496,7 @@ struct BandPolicy : LayoutAccess<BandPolicy<T, D, NW, RB>> {
         bool any = false;
         if (w0 < real && k0 < real) {
             const int w1r = min(w1, real), k1r = min(k1, real);
-            const bool band_any = (k0 - (w1r - 1) < p.band) && (w0 - (k1r - 1) < p.band);
+            const bool band_any = (k0 - (w1r - 1) < band_of(p, c)) && (w0 - (k1r - 1) < band_of(p, c));
             const bool col_any = (k0 < p.cf_hi && k1r > p.cf_lo);
             const bool row_any = (w0 < p.rf_hi && w1r > p.rf_lo);
             any = band_any || col_any || row_any;
@@ -485,9 +504,10 @@ struct BandPolicy : LayoutAccess<BandPolicy<T, D, NW, RB>> {
         if (w1 > real && k1 > real) any = true;
         return any ? TILE_PARTIAL : TILE_SKIP;
     }
-    static __device__ __forceinline__ bool allowed(const Params& p, const Ctx&, int q, int k) {
+    template <typename C>
+    static __device__ __forceinline__ bool allowed(const Params& p, const C& c, int q, int k) {
         const bool rq = q < p.real_len, rk = k < p.real_len;
-        const bool in_band = (p.band > 0) & ((unsigned)(q - k + p.band - 1) < (unsigned)(2 * p.band - 1));   // band 0: |q - k| < 0 admits nothing
+        const bool in_band = (band_of(p, c) > 0) & ((unsigned)(q - k + band_of(p, c) - 1) < (unsigned)(2 * band_of(p, c) - 1));   // band 0: |q - k| < 0 admits nothing
         const bool colf = (unsigned)(k - p.cf_lo) < (unsigned)(p.cf_hi - p.cf_lo);
         const bool rowf = (unsigned)(q - p.rf_lo) < (unsigned)(p.rf_hi - p.rf_lo);
         // bitwise on purpose: branch-free, one v_cndmask per element in the caller
@@ -498,12 +518,13 @@ struct BandPolicy : LayoutAccess<BandPolicy<T, D, NW, RB>> {
     //   real row, not a full row:  band n [0, real)  u  full columns n [0, real)
     //   full row (text):           [0, real)
     //   row behind real_len:       [real_len, S)
-    static __device__ __forceinline__ void row_intervals(const Params& p, const Ctx&, int q, int& a0, unsigned& alen, int& b0,
+    template <typename C>
+    static __device__ __forceinline__ void row_intervals(const Params& p, const C& c, int q, int& a0, unsigned& alen, int& b0,
                                                          unsigned& blen) {
         const int real = p.real_len;
         const bool rq = q < real;
         const bool rowf = (unsigned)(q - p.rf_lo) < (unsigned)(p.rf_hi - p.rf_lo);
-        const int band_lo = max(q - p.band + 1, 0), band_hi = min(q + p.band, real);
+        const int band_lo = max(q - band_of(p, c) + 1, 0), band_hi = min(q + band_of(p, c), real);
         const int lo = rq ? (rowf ? 0 : band_lo) : real;
         const int hi = rq ? (rowf ? real : band_hi) : p.S;
         a0 = lo, alen = (unsigned)max(hi - lo, 0);
@@ -547,6 +568,71 @@ struct BandLsePolicy : BandPolicy<T, 128, 8> {
         float* lse;   // [BH, S]
     };
     static __device__ __forceinline__ float* lse_base(const Params& p, const typename Base::Ctx& c) { return p.lse + (size_t)c.head * (size_t)p.S; }
+};
+
+// Per-head form (svg_band_attention_per_head_lse, include/svg_attn_adaptive_band.h): the LSE policy with ONE BAND PER HEAD, read from a
+// device vector.  The band travels in the Ctx (band_of above picks it up in kv_schedule, wave_fast_interval, classify and row_intervals; the
+// tile runs and the row cursor follow from those), clamped to [1, S + 1] here: a device value cannot be validated on the host.  The launch is
+// the static mapping of BandPolicy::init over (head, q-tile), the heavy q-tiles of every head first and the rest in windows of 32 per XCD.
+// Nothing else differs, so head h keeps the bits of svg_band_attention_lse with mask->band = band[h].  band_vec == nullptr (the alternate
+// block of the device switch): p.band for every head.
+// The row regions are the one thing the host derives from the band — a band above S does not cut the full rows out (band_row_regions) — so
+// the kernels get a parameter block for either case and pick per head (map_block, per_head_band_of, before the body).  Both blocks map
+// dispatch ids through the SAME numbers (map_*: those of the block that cuts the full rows out, which has no fewer q-tiles), so every
+// (head, index) pair is visited once whichever block a head runs; a head on the other block takes the index as its q-tile and leaves
+// what lies behind its last one.  (A grid row per head with a mapping per head: 33.196 against 31.587 ms for the device switch at
+// HunyuanVideo 720p, profiles/adaptive_band_ab_grid_row_per_head.jsonl — only the first 256 of a head's 466 q-tiles got their XCD windows.)
+template <typename T>
+struct BandPerHeadLsePolicy : BandLsePolicy<T> {
+    using Base = BandLsePolicy<T>;
+    using Band = BandPolicy<T, 128, 8>;
+    struct Params : Base::Params {
+        const int32_t* band_vec;   // device int32 [BH], or nullptr
+        int map_nqt, map_n_heavy, map_heavy_lo;   // the mapping's nqt, n_heavy, heavy_lo (this block's own, or its sibling's)
+    };
+    struct Ctx : Band::Ctx {
+        int band;
+    };
+    static __device__ __forceinline__ int per_head_band_of(const Params& p, int head) {
+        if (!p.band_vec) return p.band;
+        return min(max(__builtin_amdgcn_readfirstlane(p.band_vec[head]), 1), p.S + 1);   // (a uniform load: the band stays on the scalar unit)
+    }
+    static __device__ __forceinline__ void init_tile(const Params& p, Ctx& c, int head, int qt) {
+        c.head = head;
+        c.perm = (p.head_flag != nullptr) && (p.head_flag[c.head] != 0);
+        c.band = per_head_band_of(p, head);
+        Band::kv_schedule(p, c, qt);
+        Band::wave_fast_interval(p, c, wave_id(), c.fk_lo, c.fk_hi);
+    }
+    // dispatch id -> (head, index of a q-tile): BandPolicy::init's mapping on map_*
+    static __device__ __forceinline__ bool map_block(const Params& p, int& head, int& qt) {
+        const int nh = p.BH * p.map_n_heavy;
+        const int b = blockIdx.x;
+        if (b >= p.map_nqt * p.BH) return false;   // (the device-switched launch is sized for the larger of its masks)
+        if (b < nh) {
+            head = b / p.map_n_heavy;
+            qt = p.map_heavy_lo + (b - head * p.map_n_heavy);
+        } else {
+            const int b2 = b - nh;
+            const int full = ((p.map_nqt * p.BH - nh) / (kNumXCD * 32)) * (kNumXCD * 32);
+            int w2 = b2;
+            if (b2 < full) {
+                const int xcd = b2 % kNumXCD, s = b2 / kNumXCD;
+                w2 = (s / 32) * (kNumXCD * 32) + xcd * 32 + (s % 32);
+            }
+            const int nl = p.map_nqt - p.map_n_heavy;
+            head = w2 / nl;
+            const int r = w2 - head * nl;
+            qt = r < p.map_heavy_lo ? r : r + p.map_n_heavy;
+        }
+        return true;
+    }
+    static __device__ __forceinline__ bool init(const Params& p, Ctx& c, char*) {
+        int head, qt;
+        if (!map_block(p, head, qt) || qt >= p.nqt) return false;
+        init_tile(p, c, head, qt);
+        return true;
+    }
 };
 
 // fp32 form (svg_band_attention_lse_f32): the LSE policy plus the rows before their rounding (attn_m16.h: HasRowO32, switched on by

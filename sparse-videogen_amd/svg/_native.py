@@ -347,6 +347,19 @@ ADAPTIVE_TOP_P_SIGNATURES = {
 }
 
 
+# include/svg_attn_adaptive_band.h: SVG1's per-head band width — band attention from a device vector of bands, its device switch, the
+# controller step —, in a table of its own for the same reason (tests/test_adaptive_band_cpu.py; allocating wrappers: svg/_adaptive_band.py).
+# (Named ..._ENTRIES: tests/test_wrapper_layout_plan_cpu.py wants a golden transcript for every attention entry of a *SIGNATURES table, and
+#  its golden is closed; the transcripts of these wrappers are in tests/test_adaptive_band_cpu.py.)
+ADAPTIVE_BAND_ENTRIES = {
+    "svg_band_attention_per_head_lse": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _F32, C.POINTER(BandMask), _VP,
+                                                  C.POINTER(PermDesc), C.POINTER(AttnLayout), _VP]),
+    "svg_band_attention_switch_per_head_lse": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _F32, C.POINTER(BandMask),
+                                                         C.POINTER(BandMask), _VP, _VP, C.POINTER(PermDesc), C.POINTER(AttnLayout), _VP]),
+    "svg_band_width_update": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _F32, _F32, _F32, _F32, _I32, _I32, _I32, _VP, _VP, _VP, _VP]),
+}
+
+
 class CopyBox(C.Structure):
     """svg_copy_box_t (include/svg_attn_shard_exchange.h): extent[0] * extent[1] * extent[2] rows of D contiguous elements; offsets and
     strides in elements"""
@@ -383,7 +396,7 @@ def load(strict: bool = True) -> Optional[C.CDLL]:
         for name, (res, args) in {**SIGNATURES, **SPARSE_LSE_SIGNATURES, **SPARSE_F32_SIGNATURES, **BAND_LSE_FORM_SIGNATURES,
                                    **BAND_WINDOW_SIGNATURES, **BAND_SHARD_SIGNATURES, **BAND_SHARD_SWITCH_SIGNATURES,
                                    **PROFILE_SHARD_SIGNATURES, **SAMPLE_ROWS_SIGNATURES, **SHARD_EXCHANGE_SIGNATURES,
-                                   **ADAPTIVE_TOP_P_SIGNATURES}.items():
+                                   **ADAPTIVE_TOP_P_SIGNATURES, **ADAPTIVE_BAND_ENTRIES}.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -1901,6 +1914,37 @@ def top_p_update(lse_sparse: torch.Tensor, rows: torch.Tensor, lse_dense: torch.
                               float(gain_up), float(gain_down), float(band), float(p_min), float(p_max), kept.data_ptr(), top_p.data_ptr(),
                               _stream())
     _check(rc, "svg_top_p_update")
+
+
+def _i32_vector(what: str, t: torch.Tensor, n: int) -> None:
+    if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"{what}: a contiguous int32 tensor of {n} elements, got {t.dtype} {tuple(t.shape)}")
+
+
+def band_width_update(lse_sparse: torch.Tensor, rows: torch.Tensor, lse_dense: torch.Tensor, band: torch.Tensor, kept: torch.Tensor,
+                      target: float, gain_up: float, gain_down: float, dead: float, quantum: int, band_min: int, band_max: int,
+                      skip_flag: Optional[torch.Tensor] = None) -> None:
+    """The controller step of SVG1's per-head band (svg_band_width_update): lse_sparse fp32 [BH, S] (any leading shape), rows device int64
+    [R], lse_dense fp32 [BH, R]; kept fp32 [BH] is written, band int32 [BH] stepped in place by whole quanta inside [band_min, band_max].
+    skip_flag (int32 [1] on the device, or None): non-zero leaves every band as it is — the dense_flag of the switched path.  No
+    allocation, no host synchronisation."""
+    if rows.dtype != torch.int64 or rows.dim() != 1 or not 1 <= rows.numel() <= 64:
+        raise ValueError(f"band_width_update: rows is an int64 vector of 1 to 64 rows, got {rows.dtype} {tuple(rows.shape)}")
+    R, BH = rows.numel(), band.numel()
+    _i32_vector("band_width_update(band)", band, BH)
+    _f32_vector("band_width_update(kept)", kept, BH)
+    if BH < 1 or lse_sparse.dtype != torch.float32 or lse_sparse.numel() % BH != 0 or lse_sparse.numel() == 0 or not lse_sparse.is_contiguous():
+        raise ValueError(f"band_width_update: lse_sparse is a contiguous float32 [BH = {BH}, S], got {lse_sparse.dtype} "
+                         f"{tuple(lse_sparse.shape)}, strides {tuple(lse_sparse.stride())}")
+    _f32_vector("band_width_update(lse_dense)", lse_dense, BH * R)
+    if skip_flag is not None and (skip_flag.dtype != torch.int32 or skip_flag.numel() < 1):
+        raise ValueError(f"band_width_update: skip_flag is an int32 tensor of one element, got {skip_flag.dtype} {tuple(skip_flag.shape)}")
+    lib = load()
+    _dev(lse_sparse, rows, lse_dense, band, kept, skip_flag)
+    rc = lib.svg_band_width_update(lse_sparse.data_ptr(), rows.data_ptr(), lse_dense.data_ptr(), R, BH, lse_sparse.numel() // BH,
+                                   float(target), float(gain_up), float(gain_down), float(dead), int(quantum), int(band_min), int(band_max),
+                                   _ptr(skip_flag), kept.data_ptr(), band.data_ptr(), _stream())
+    _check(rc, "svg_band_width_update")
 
 
 def map_density(block_map: torch.Tensor, q_sizes: torch.Tensor, k_sizes: torch.Tensor) -> torch.Tensor:

@@ -470,7 +470,8 @@ def dense_flag_on_device(timestep, first_times_fp):
 def svg1_attention_device_switch(q, k, v, geo: Geometry, mask: "_native.BandMask", dense_mask: "_native.BandMask",
                                  prof: "_native.ProfileDesc", num_sampled_rows: int, sample_max_row: int, dense_flag,
                                  _local: bool = False, q_prescaled: bool = False, return_lse: bool = False, out_dtype=None,
-                                 quality: Optional["QualityRequest"] = None):
+                                 quality: Optional["QualityRequest"] = None, adaptive: Optional["AdaptiveBand"] = None,
+                                 band_store: Optional["BandStore"] = None, layer_idx=None):
     """Dense warm-up step or sparse step, decided on the device: the profiler and the attention kernel read
     `dense_flag`; on a dense step the profiler returns at once and the kernel runs `dense_mask` without the head placement.
     Same attention results as the host-side branch of attention_core_logic (ref: hyvideo/attention.py:491-524) for the same sampled
@@ -484,13 +485,23 @@ def svg1_attention_device_switch(q, k, v, geo: Geometry, mask: "_native.BandMask
     what has no shard form raises before any collective (_frame_shard_setup).
     quality: a QualityRequest (quality_request): the call is probed as well and its record queued (log_quality) — on EVERY call, the host
     does not know whether the step is dense; the record carries dense_flag and the writer drops those of dense steps.  Where the launch has
-    an LSE form the call goes through it (the same o).  Refused under svg.distributed."""
+    an LSE form the call goes through it (the same o).  Refused under svg.distributed.
+    adaptive: an AdaptiveBand, with band_store a BandStore and layer_idx the layer's key in it: the call runs one band per head from the
+    store (the layer's first call fills it with the mask's band) through svg_band_attention_switch_per_head_lse, K is probed on rows from
+    the probe's generator (neither the global RNG nor the switched path's generator moves) and svg_band_width_update steps the bands for
+    the layer's next call, with dense_flag as its skip flag — all on the device, no host synchronisation.  With `quality` as well the
+    rows are drawn once, its one dense probe feeds both and the record gains "band".  ValueError, before anything runs, where the launch
+    has no LSE form (head_dim 64, fp8, a pre-scaled q, out_dtype); NotImplementedError under svg.distributed and for per-video masks
+    that differ.  None: nothing changes."""
+    if adaptive is not None:
+        _refuse_adaptive_band("svg1_attention_device_switch", q, band_store, q_prescaled, True, out_dtype, mask, (("dense_mask", dense_mask),))
+        band_bounds = adaptive.bounds(_one_of(mask, q.shape[0], "svg1_attention_device_switch(mask)").band, q.shape[2])
     if quality is not None:
         _refuse_quality_when_sharded("svg1_attention_device_switch")
     if _dist.frame_shards_active():   # q, k, v: this rank's rows; -> (out [cfg, H, S_r, D], best_mask_idx)
         return _frame_shard_svg1("svg1_attention_device_switch", q, k, v, geo, mask, dense_mask, prof, num_sampled_rows, sample_max_row,
                                  dense_flag, q_prescaled=q_prescaled, return_lse=return_lse, out_dtype=out_dtype)
-    probe_lse = quality is not None and not return_lse and _quality_lse_form(q, q_prescaled)
+    probe_lse = (quality is not None and not return_lse and _quality_lse_form(q, q_prescaled)) or (adaptive is not None and not return_lse)
     kw = _state_kw("svg1_attention_device_switch", return_lse or probe_lse, out_dtype, q_prescaled, TOKEN_MAJOR_IO)
     _require_gpu(q, "SVG1 attention")
     cfg, H = q.shape[0], q.shape[1]
@@ -513,6 +524,15 @@ def svg1_attention_device_switch(q, k, v, geo: Geometry, mask: "_native.BandMask
     mses = sample_mse(q, k, v, geo, prof, num_sampled_rows, sample_max_row, skip_flag=dense_flag, generator=_switch_generator(),
                       q_prescaled=q_prescaled)
     best_mask_idx = torch.argmin(mses, dim=0)
+    if adaptive is not None:   # (one mask for the batch, no sharding: refused above otherwise)
+        from .. import _adaptive_band
+
+        out = _adaptive_band_call(lambda band: _adaptive_band.band_attention_switch_per_head(
+            q, k, v, mask, dense_mask, dense_flag, band, head_perm_flag=best_mask_idx, vid0=geo.vid0, num_frame=geo.num_frame,
+            frame_size=geo.frame_size, token_major_out=TOKEN_MAJOR_IO), adaptive, band_store, layer_idx, mask, band_bounds, q, k, v, quality,
+            dense_flag=dense_flag)
+        best = torch.where(dense_flag.reshape(()) != 0, torch.full_like(best_mask_idx, -1), best_mask_idx)
+        return (out[0], best, out[1]) if return_lse else (out[0], best)
     if groups is not None:
         out = _native.band_attention_groups(q, k, v, groups[0], groups[2], alt_masks=groups[1], use_alt_flag=dense_flag,
                                             head_perm_flag=best_mask_idx, vid0=geo.vid0, num_frame=geo.num_frame,
@@ -534,7 +554,8 @@ def svg1_attention_device_switch(q, k, v, geo: Geometry, mask: "_native.BandMask
 def svg1_sparse_attention(q, k, v, geo: Geometry, mask: "_native.BandMask", prof: "_native.ProfileDesc",
                           num_sampled_rows: int, sample_max_row: int, fused: bool = True, _local: bool = False,
                           q_prescaled: bool = False, return_lse: bool = False, out_dtype=None,
-                          quality: Optional["QualityRequest"] = None):
+                          quality: Optional["QualityRequest"] = None, adaptive: Optional["AdaptiveBand"] = None,
+                          band_store: Optional["BandStore"] = None, layer_idx=None):
     """The sparse branch of attention_core_logic (ref: hyvideo/attention.py:507-524):
     online profiling -> best_mask_idx -> placement -> block-sparse attention -> inverse placement.
     fused=True folds both placements into the attention kernel (bit-identical result, ~5.9 GB less HBM traffic at
@@ -548,13 +569,18 @@ def svg1_sparse_attention(q, k, v, geo: Geometry, mask: "_native.BandMask", prof
     draws the same).
     quality: a QualityRequest (quality_request): the call is probed as well and its record queued (log_quality); where the launch has an
     LSE form — head_dim 128, 16-bit, plain q, fused — it goes through it (the same o) and the kept mass is logged, elsewhere the error
-    alone.  Refused under svg.distributed."""
+    alone.  Refused under svg.distributed.
+    adaptive / band_store / layer_idx: as svg1_attention_device_switch, through svg_band_attention_per_head_lse and without a skip flag
+    (every call of this branch is a sparse step); fused=False is refused as well (ValueError)."""
+    if adaptive is not None:
+        _refuse_adaptive_band("svg1_sparse_attention", q, band_store, q_prescaled, fused, out_dtype, mask)
+        band_bounds = adaptive.bounds(_one_of(mask, q.shape[0], "svg1_sparse_attention(mask)").band, q.shape[2])
     if quality is not None:
         _refuse_quality_when_sharded("svg1_sparse_attention")
     if _dist.frame_shards_active():   # q, k, v: this rank's rows; -> (out [cfg, H, S_r, D], best_mask_idx)
         return _frame_shard_svg1("svg1_sparse_attention", q, k, v, geo, mask, None, prof, num_sampled_rows, sample_max_row, None,
                                  q_prescaled=q_prescaled, return_lse=return_lse, out_dtype=out_dtype, fused=fused)
-    probe_lse = quality is not None and not return_lse and _quality_lse_form(q, q_prescaled, fused)
+    probe_lse = (quality is not None and not return_lse and _quality_lse_form(q, q_prescaled, fused)) or (adaptive is not None and not return_lse)
     kw = _state_kw("svg1_sparse_attention", return_lse or probe_lse, out_dtype, q_prescaled, TOKEN_MAJOR_IO, fp8=_use_fp8(q), fused=fused)
     _require_gpu(q, "SVG1 sparse attention")
     groups = None
@@ -576,6 +602,13 @@ def svg1_sparse_attention(q, k, v, geo: Geometry, mask: "_native.BandMask", prof
     mses = sample_mse(q, k, v, geo, prof, num_sampled_rows, sample_max_row, q_prescaled=q_prescaled)
     best_mask_idx = torch.argmin(mses, dim=0)  # [cfg, H] int64; NaN wins like torch.argmin in the reference
     pk = dict(head_perm_flag=best_mask_idx, vid0=geo.vid0, num_frame=geo.num_frame, frame_size=geo.frame_size)
+    if adaptive is not None:   # (fused, 16-bit, one mask for the batch, no sharding: refused above otherwise)
+        from .. import _adaptive_band
+
+        with time_logging_decorator("Level 3 - sparse_flex_attention"):
+            out = _adaptive_band_call(lambda band: _adaptive_band.band_attention_per_head(q, k, v, mask, band, token_major_out=TOKEN_MAJOR_IO, **pk),
+                                      adaptive, band_store, layer_idx, mask, band_bounds, q, k, v, quality)
+        return (out[0], best_mask_idx, out[1]) if return_lse else (out[0], best_mask_idx)
     if fused:
         with time_logging_decorator("Level 3 - sparse_flex_attention"):
             if groups is not None:
@@ -747,6 +780,159 @@ def adaptive_step(adaptive: AdaptiveTopP, top_p_store: TopPStore, layer_idx, p: 
         _native.top_p_update(lse[sl], rows.to(q.device, non_blocking=True), ld, p[hs], kept[hs], adaptive.target, adaptive.gain_up,
                              adaptive.gain_down, adaptive.band, adaptive.p_min, adaptive.p_max)
     top_p_store.kept[layer_idx] = kept
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# SVG1's adaptive band width: one band per head on the device, steered by measured kept mass (include/svg_attn_adaptive_band.h)
+# ---------------------------------------------------------------------------------------------------------------
+class BandStore:
+    """Per-layer state of the adaptive band (AdaptiveBand), as TopPStore: `band[layer]`, an int32 [cfg * H] DEVICE tensor — the band of every
+    head for the layer's NEXT sparse call, stepped in place by svg_band_width_update — and `kept[layer]`, fp32 [cfg * H], the kept mass its
+    last call measured.  Nothing here is ever read back by the package.  A call with a different cfg * H (or on another device) starts
+    the layer again from the mask's band; `clear()` forgets every layer (call between videos)."""
+
+    def __init__(self):
+        self.band = {}
+        self.kept = {}
+
+    def has(self, layer_idx, n=None) -> bool:
+        return layer_idx in self.band and (n is None or self.band[layer_idx].numel() == n)
+
+    def get(self, layer_idx, n: int, init: int, device) -> torch.Tensor:
+        """The layer's [n] bands; filled with `init` (and the last kept mass forgotten) where the layer has none of that size."""
+        t = self.band.get(layer_idx)
+        if t is None or t.numel() != n or t.device != torch.device(device):
+            t = torch.full((n,), int(init), dtype=torch.int32, device=device)
+            self.band[layer_idx] = t
+            self.kept.pop(layer_idx, None)
+        return t
+
+    def clear(self):
+        self.band.clear()
+        self.kept.clear()
+
+
+@dataclass
+class AdaptiveBand:
+    """The SVG1 knob "keep this much attention mass": every head's band width is steered, on the device, so that the kept mass measured after
+    each sparse layer-call — mean over probe rows of exp(lse_sparse - lse_dense) — approaches `target` (include/svg_attn_adaptive_band.h
+    svg_band_width_update):
+        e = target - kept;  x = gain_up * e if e > 0, gain_down * (e + dead) if e < -dead, else 0;  n = rint(clamp(x, -65536, 65536))
+        band = clamp(band + n * quantum, band_min, band_max)
+    The gains are QUANTA per unit of kept mass.  A head below target is widened quickly, a head more than `dead` above it is narrowed slowly;
+    inside the dead zone nothing moves.  The first sparse call of a layer runs every head with the mask's band (what `sparsity` gives).
+    The default gains are UNTUNED: nobody has measured which suit a real model, nor what per-head bands are worth on one.  gain_up =
+    gain_down = 0 measures and moves nothing.
+    band_min / band_max: None — the smallest / largest value congruent to the mask's band modulo `quantum` inside [1, S + 1], so the
+    residue of the mask's band survives every step (Wan's is a multiple of 128 plus 1); a given bound that is not congruent raises
+    ValueError at the call (bounds()).  rows: probe rows per head and call (1..64).  valid_len: the dense `valid` of the call as
+    QualityRequest carries it (set by the processors, per call)."""
+    target: float
+    gain_up: float = 8.0
+    gain_down: float = 2.0
+    dead: float = 0.02
+    quantum: int = 128
+    band_min: Optional[int] = None
+    band_max: Optional[int] = None
+    rows: int = 64
+    valid_len: object = None
+
+    def __post_init__(self):
+        ok = lambda x: x == x and x >= 0   # noqa: E731  (not NaN, not negative)
+        if not (ok(self.gain_up) and ok(self.gain_down) and ok(self.dead)):
+            raise ValueError(f"AdaptiveBand: gains and dead are >= 0, got {self.gain_up}, {self.gain_down}, {self.dead}")
+        if int(self.quantum) != self.quantum or not 1 <= int(self.quantum) <= 4096:
+            raise ValueError(f"AdaptiveBand: quantum is an integer in [1, 4096], got {self.quantum}")
+        for name in ("band_min", "band_max"):
+            b = getattr(self, name)
+            if b is not None and (int(b) != b or int(b) < 1):
+                raise ValueError(f"AdaptiveBand: {name} is None or an integer >= 1, got {b}")
+        if self.band_min is not None and self.band_max is not None and self.band_min > self.band_max:
+            raise ValueError(f"AdaptiveBand: band_min <= band_max, got {self.band_min}, {self.band_max}")
+        if not 1 <= int(self.rows) <= 64:
+            raise ValueError(f"AdaptiveBand: 1 to 64 probe rows, got {self.rows}")
+
+    def bounds(self, mask_band: int, S: int):
+        """(band_min, band_max) of a call under a mask of band `mask_band` over S rows: the given bounds, checked — congruent to mask_band
+        modulo quantum, 1 <= band_min <= band_max <= S + 1 — or, for None, the extreme congruent values inside [1, S + 1]."""
+        qn, b = int(self.quantum), int(mask_band)
+        if not 1 <= b <= S + 1:
+            raise ValueError(f"AdaptiveBand: the mask's band lies in [1, S + 1] = [1, {S + 1}], got {b}")
+        r = b % qn
+        lo = r if r >= 1 else qn
+        hi = r + ((S + 1 - r) // qn) * qn
+        for name, given in (("band_min", self.band_min), ("band_max", self.band_max)):
+            if given is not None and (int(given) - b) % qn != 0:
+                raise ValueError(f"AdaptiveBand: {name} = {given} is not congruent to the mask's band {b} modulo quantum = {qn}: every step "
+                                 f"is a whole number of quanta, so the bound would change the band's residue")
+        lo = lo if self.band_min is None else int(self.band_min)
+        hi = hi if self.band_max is None else int(self.band_max)
+        if not 1 <= lo <= hi <= S + 1:
+            raise ValueError(f"AdaptiveBand: 1 <= band_min <= band_max <= S + 1 = {S + 1}, got {lo}, {hi}")
+        return lo, hi
+
+
+def _refuse_adaptive_band_when_sharded(what: str) -> None:
+    if _dist._STATE["enabled"] or _dist.frame_shards_active() or _dist.token_shards_active():
+        raise NotImplementedError(f"{what}: adaptive_band under svg.distributed (enable, enable_frame_shards, enable_token_shards) is not "
+                                  f"implemented: the probe reads whole heads of the whole sequence; unset adaptive_band or run on one GPU")
+
+
+def _refuse_adaptive_band(what: str, q: torch.Tensor, band_store, q_prescaled: bool, fused: bool, out_dtype, mask, extra_masks=()) -> None:
+    """What the adaptive band refuses, all of it before anything runs: there is no silent fall-back to the launch's one band."""
+    _refuse_adaptive_band_when_sharded(what)
+    if band_store is None:
+        raise ValueError(f"{what}(adaptive=...) needs a band_store (BandStore): the bands live there between calls")
+    D = q.shape[-1]
+    if D != 128 or _use_fp8(q) or q.dtype not in (torch.bfloat16, torch.float16) or q_prescaled or not fused or out_dtype is not None:
+        raise ValueError(f"{what}(adaptive=...): the per-head band runs the row log-sum-exp form of the fused launch — head_dim 128, bf16 / "
+                         f"fp16 (not fp8), a plain q, fused=True, no out_dtype; got D = {D}, {q.dtype}, fp8 = {_use_fp8(q)}, q_prescaled = "
+                         f"{q_prescaled}, fused = {fused}, out_dtype = {out_dtype}")
+    cfg = q.shape[0]
+    for m, name in ((mask, "mask"),) + tuple(extra_masks):
+        pm = per_video(m, cfg, f"{what}({name})")
+        if pm is not None and len(video_groups(pm)[0]) > 1:
+            raise NotImplementedError(f"{what}(adaptive=...): per-video masks that differ (the groups launch) have no per-head band form; "
+                                      f"give every video the same text length")
+
+
+def _one_of(mask, cfg: int, what: str):
+    pm = per_video(mask, cfg, what)
+    return mask if pm is None else pm[0]
+
+
+def adaptive_band_step(adaptive: AdaptiveBand, band_store: BandStore, layer_idx, band: torch.Tensor, lse: torch.Tensor, q, k, plan,
+                       bounds, lse_dense=None, skip_flag=None):
+    """After a sparse layer-call that ran with the bands `band` [cfg * H] (the store's tensor) and returned lse [cfg, H, S]: probe (K only;
+    lse_dense: what a quality probe on the same plan already measured, one [nb, H, R] per group), then svg_band_width_update — band is
+    stepped in place inside `bounds`, the kept mass lands in the store.  skip_flag: the dense_flag of the switched path (a dense step
+    measures and moves nothing).  No host synchronisation."""
+    from .. import _probe
+
+    cfg, H, S, _ = q.shape
+    lse = lse.reshape(cfg, H, S)
+    kept = _native.empty((cfg * H,), dtype=torch.float32, device=q.device)
+    for i, (sl, vl, rows) in enumerate(plan):
+        ld = lse_dense[i] if lse_dense is not None else _probe.sample_dense_lse(q[sl], k[sl], rows, vl)
+        hs = slice(sl.start * H, sl.stop * H)
+        _native.band_width_update(lse[sl], rows.to(q.device, non_blocking=True), ld, band[hs], kept[hs], adaptive.target, adaptive.gain_up,
+                                  adaptive.gain_down, adaptive.dead, adaptive.quantum, bounds[0], bounds[1], skip_flag=skip_flag)
+    band_store.kept[layer_idx] = kept
+
+
+def _adaptive_band_call(run, adaptive: AdaptiveBand, band_store: BandStore, layer_idx, mask, bounds, q, k, v, quality, dense_flag=None):
+    """One layer-call under per-head bands: `run(band)` launches the per-head (switch) form and returns (out, lse); then the probe — one
+    plan for the quality record and the controller — and the controller step.  -> (out, lse)"""
+    cfg, H, S, _ = q.shape
+    band = band_store.get(layer_idx, cfg * H, mask.band, q.device)
+    out, lse = run(band)
+    valid = quality.valid_len if quality is not None else adaptive.valid_len
+    plan = probe_plan(valid, quality.rows if quality is not None else adaptive.rows, cfg, S)
+    lse_d = None
+    if quality is not None:   # (the rows are drawn once: the quality probe's dense lse feeds the controller)
+        lse_d = log_quality(quality, out, lse, q, k, v, dense_flag=dense_flag, plan=plan, band=band.clone())
+    adaptive_band_step(adaptive, band_store, layer_idx, band, lse, q, k, plan, bounds, lse_d, skip_flag=dense_flag)
+    return out, lse
 
 
 KMEANS_TWO_STREAMS = True    # q-side and k-side k-means loops on two streams (kmeans_clustering below); False: one after the other
@@ -1084,9 +1270,10 @@ class _QualityLog:
     def __init__(self):
         self.pending = []   # (path, meta, shape, has kept mass, has density, has flag, has timestep, pinned host tensor, event[, has top_p])
 
-    def push(self, path: str, meta: dict, figures: dict, density=None, dense_flag=None, timestep=None, top_p=None) -> None:
+    def push(self, path: str, meta: dict, figures: dict, density=None, dense_flag=None, timestep=None, top_p=None, band=None) -> None:
         """timestep: a device tensor whose first element is the record's timestep, read with the figures (no read-back on the host).
-        top_p [cfg * H] (the adaptive SVG2 path): the thresholds the call ran with — the record gains a "top_p" list, and only then"""
+        top_p [cfg * H] (the adaptive SVG2 path): the thresholds the call ran with — the record gains a "top_p" list, and only then;
+        band [cfg * H] (the adaptive SVG1 path): the bands the call ran with — a "band" list of integers, likewise"""
         rel = figures["rel_l2"]
         parts = [rel.float().reshape(-1), figures["mse"].float().reshape(-1)]
         kept = figures.get("kept_mass")
@@ -1096,6 +1283,8 @@ class _QualityLog:
             parts.append(density.float().reshape(-1))
         if top_p is not None:
             parts.append(top_p.float().reshape(-1))
+        if band is not None:   # (bands are at most S + 1 < 2^24: exact in fp32)
+            parts.append(band.float().reshape(-1))
         if dense_flag is not None:
             parts.append(dense_flag.reshape(-1)[:1].float())
         if timestep is not None:
@@ -1108,13 +1297,14 @@ class _QualityLog:
             ev = torch.cuda.Event()
             ev.record()
         self.pending.append((path, meta, tuple(rel.shape), kept is not None, density is not None, dense_flag is not None,
-                             timestep is not None, host, ev, top_p is not None))
+                             timestep is not None, host, ev, top_p is not None, band is not None))
         self.flush(wait=False)
 
     def flush(self, wait: bool = True) -> None:
         while self.pending:
             path, meta, shape, has_kept, has_density, has_flag, has_ts, host, ev, *more = self.pending[0]
             has_top_p = bool(more and more[0])   # (the thresholds of the adaptive SVG2 path, where the record carries them)
+            has_band = bool(len(more) > 1 and more[1])   # (the bands of the adaptive SVG1 path)
             if ev is not None:
                 if wait:
                     ev.synchronize()
@@ -1132,6 +1322,9 @@ class _QualityLog:
                     entry["density"] = take(2 + int(has_kept))
                 if has_top_p:
                     entry["top_p"] = take(2 + int(has_kept) + int(has_density))
+                if has_band:
+                    bands = host[(2 + int(has_kept) + int(has_density) + int(has_top_p)) * n:][:n].reshape(shape).tolist()
+                    entry["band"] = [[int(b) for b in row] for row in bands] if len(shape) == 2 else bands
                 with open(path, "a") as f:
                     f.write(json.dumps(entry) + "\n")
             self.pending.pop(0)
@@ -1149,12 +1342,12 @@ atexit.register(flush_quality_log)
 
 
 def log_quality(quality: QualityRequest, out: torch.Tensor, lse, q, k, v, q_prescaled: bool = False, dense_flag=None, density=None,
-                plan=None, top_p=None):
+                plan=None, top_p=None, band=None):
     """Probe one sparse layer-call (out [cfg, H, S, D] in either storage order, lse [cfg, H, S] or None) and queue its record.  Rows:
     uniform over the valid rows of the sequence, from the probe's own CPU generator.  Videos whose valid lengths differ are probed group by
     group (video_groups), one native call per group.
     plan: the rows, where the caller has drawn them already (probe_plan); top_p [cfg * H]: the thresholds the call ran with, for the record
-    (the adaptive SVG2 path).  -> the dense lse of the probed rows, one [nb, H, R] per group, for a caller that steers by it."""
+    (the adaptive SVG2 path); band [cfg * H]: the bands it ran with (the adaptive SVG1 path).  -> the dense lse of the probed rows, one [nb, H, R] per group, for a caller that steers by it."""
     from .context import timestep_value
 
     cfg, H, S, D = q.shape
@@ -1168,7 +1361,8 @@ def log_quality(quality: QualityRequest, out: torch.Tensor, lse, q, k, v, q_pres
     ts = quality.timestep
     on_device = torch.is_tensor(ts) and ts.is_cuda   # (the switched path never reads the timestep back: it travels with the figures)
     meta = {"timestep": None if ts is None or on_device else timestep_value(ts), "layer": quality.layer}
-    QUALITY_LOG.push(quality.path, meta, fig, density=density, dense_flag=dense_flag, timestep=ts if on_device else None, top_p=top_p)
+    QUALITY_LOG.push(quality.path, meta, fig, density=density, dense_flag=dense_flag, timestep=ts if on_device else None, top_p=top_p,
+                     **({} if band is None else {"band": band}))
     return lse_dense
 
 

@@ -16,7 +16,7 @@ import torch.nn.functional as F
 
 from ...timer import time_logging_decorator
 from .. import _core
-from .._core import CentroidStore, Geometry, TopPStore
+from .._core import BandStore, CentroidStore, Geometry, TopPStore
 from .utils import dense_mask, generate_temporal_head_mask_mod, profile_desc
 
 
@@ -290,10 +290,20 @@ class Hunyuan_SVGAttn_Processor2_0(_HunyuanProcessorBase):
     # file (deferred writes: flush_quality_log()).  None: nothing changes.  Refused under svg.distributed.
     quality_log = None
     quality_rows = 64
+    # adaptive band (svg/models/_core.py AdaptiveBand): an AdaptiveBand(target=...) -> every head's band width is steered on the device towards
+    # the kept mass `target`, from the band `sparsity` gives on a layer's first sparse call (state: band_store, per layer; dense warm-up
+    # steps leave it alone).  None: nothing changes.  Refused under svg.distributed, with prescale_q, fp8 and per-video masks that differ.
+    adaptive_band = None
+    band_store = BandStore()
 
     def __init__(self, layer_idx):
         super().__init__(layer_idx)
         self.last_best_mask_idx = None
+
+    @classmethod
+    def reset_state(cls):
+        """Forget the per-layer bands (call between videos)."""
+        cls.band_store.clear()
 
     @classmethod
     def geometry(cls) -> Geometry:
@@ -315,6 +325,11 @@ class Hunyuan_SVGAttn_Processor2_0(_HunyuanProcessorBase):
         total = geo.seq_len   # (seq_len, except in frame-shard mode: the masks and the sampled rows are the whole sequence's)
         valid = self.video_valid_lens(cu_max_seqlens, cfg, geo.video_length)
         quality = _core.quality_request(type(self).__name__, self.quality_log, self.quality_rows, valid, timestep, self.layer_idx)
+        ab = {}
+        if self.adaptive_band is not None:
+            _core._refuse_adaptive_band_when_sharded(type(self).__name__)
+            # (the probe's rows and keys follow the call's valid lengths)
+            ab = dict(adaptive=dataclasses.replace(self.adaptive_band, valid_len=valid), band_store=self.band_store, layer_idx=self.layer_idx)
         # the layer test is host data; the timestep test stays on the device when the timestep is a GPU tensor (device_switch)
         dense_flag = None
         if self.device_switch and _core.attention_dtype() == "bf16" and self.fused_placement and self.layer_idx >= self.first_layers_fp and self.block_mask is not None \
@@ -333,12 +348,12 @@ class Hunyuan_SVGAttn_Processor2_0(_HunyuanProcessorBase):
             dense = tuple(dense_mask(total, int(x)) for x in valid) if isinstance(valid, tuple) else dense_mask(total, int(valid))
             out, best = _core.svg1_attention_device_switch(query, key, value, geo, mask, dense, prof,
                                                            self.num_sampled_rows, min(self.sample_mse_max_row, total), dense_flag,
-                                                           q_prescaled=pre, quality=quality)
+                                                           q_prescaled=pre, quality=quality, **ab)
             self.last_best_mask_idx = best
             return out.reshape(cfg, num_heads, seq_len, dim)
         out, best = _core.svg1_sparse_attention(query, key, value, geo, mask, prof, self.num_sampled_rows,
                                                 min(self.sample_mse_max_row, total), fused=self.fused_placement, q_prescaled=pre,
-                                                quality=quality)
+                                                quality=quality, **ab)
         self.last_best_mask_idx = best
         return out.reshape(cfg, num_heads, seq_len, dim)
 
@@ -382,6 +397,7 @@ class Hunyuan_SAPAttn_Processor2_0(Hunyuan_SVGAttn_Processor2_0):
         """Forget the per-layer centroids and thresholds (call between videos; the reference never resets them)."""
         cls.centroid_store.clear()
         cls.top_p_store.clear()
+        cls.band_store.clear()
 
     @time_logging_decorator("Level 2 - attention core logic")
     def attention_core_logic(self, query, key, value, timestep, layer_idx, cu_max_seqlens):

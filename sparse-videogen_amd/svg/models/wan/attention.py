@@ -10,7 +10,7 @@ import torch
 from ...kernels.triton.rmsnorm import triton_rmsnorm_forward
 from ...timer import time_logging_decorator
 from .. import _core
-from .._core import CentroidStore, Geometry, TopPStore
+from .._core import BandStore, CentroidStore, Geometry, TopPStore
 from .utils import dense_mask, generate_temporal_head_mask_mod, profile_desc
 
 
@@ -247,6 +247,16 @@ class WanAttn_SVGAttn_Processor2_0:
     # file (deferred writes: flush_quality_log()).  None: nothing changes.  Refused under svg.distributed.
     quality_log = None
     quality_rows = 64
+    # adaptive band (svg/models/_core.py AdaptiveBand): an AdaptiveBand(target=...) -> every head's band width is steered on the device towards
+    # the kept mass `target`, from the band `sparsity` gives on a layer's first sparse call (state: band_store, keyed by layer; dense warm-up
+    # steps leave it alone).  None: nothing changes.  Refused under svg.distributed, with prescale_q and fp8.
+    adaptive_band = None
+    band_store = BandStore()
+
+    @classmethod
+    def reset_state(cls):
+        """Forget the per-layer bands (call between videos)."""
+        cls.band_store.clear()
 
     @time_logging_decorator("Level 3 - Dense Flash Attention")
     def flash_attention(self, query, key, value):
@@ -260,6 +270,10 @@ class WanAttn_SVGAttn_Processor2_0:
             f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
         total = geo.seq_len   # (seq_len, except in frame-shard mode: the masks and the sampled rows are the whole sequence's)
         quality = _core.quality_request(type(self).__name__, self.quality_log, self.quality_rows, None, timestep, self.layer_idx)
+        ab = {}
+        if self.adaptive_band is not None:
+            _core._refuse_adaptive_band_when_sharded(type(self).__name__)
+            ab = dict(adaptive=self.adaptive_band, band_store=self.band_store, layer_idx=self.layer_idx)
         dense_flag = None   # (device-side dense / sparse switch, see the Hunyuan processor)
         if self.device_switch and _core.attention_dtype() == "bf16" and self.fused_placement and self.layer_idx >= self.first_layers_fp and self.block_mask is not None \
                 and query.is_cuda:
@@ -272,12 +286,12 @@ class WanAttn_SVGAttn_Processor2_0:
         if dense_flag is not None:
             out, best = _core.svg1_attention_device_switch(query, key, value, geo, self.block_mask, dense_mask(total), prof,
                                                            self.num_sampled_rows, min(self.sample_mse_max_row, total), dense_flag,
-                                                           q_prescaled=self._q_prescaled, quality=quality)
+                                                           q_prescaled=self._q_prescaled, quality=quality, **ab)
             self.last_best_mask_idx = best
             return out.reshape(cfg, num_heads, seq_len, dim)
         out, best = _core.svg1_sparse_attention(query, key, value, geo, self.block_mask, prof, self.num_sampled_rows,
                                                 min(self.sample_mse_max_row, total), fused=self.fused_placement,
-                                                q_prescaled=self._q_prescaled, quality=quality)
+                                                q_prescaled=self._q_prescaled, quality=quality, **ab)
         self.last_best_mask_idx = best
         return out.reshape(cfg, num_heads, seq_len, dim)
 
@@ -330,6 +344,7 @@ class WanAttn_SAPAttn_Processor(WanAttn_SVGAttn_Processor2_0):
     def reset_state(self):
         self.centroid_store.clear()
         self.top_p_store.clear()
+        self.band_store.clear()
 
     @time_logging_decorator("Level 2 - attention core logic")
     def attention_core_logic(self, query, key, value, timestep):
