@@ -1896,54 +1896,53 @@ def identify_dynamic_map_per_head(qc: torch.Tensor, kc: torch.Tensor, k_sizes: t
     return out.view(torch.bool)
 
 
-def top_p_update(lse_sparse: torch.Tensor, rows: torch.Tensor, lse_dense: torch.Tensor, top_p: torch.Tensor, kept: torch.Tensor,
-                 target: float, gain_up: float, gain_down: float, band: float, p_min: float, p_max: float) -> None:
-    """The controller step (svg_top_p_update): lse_sparse fp32 [BH, S] (any leading shape), rows device int64 [R], lse_dense fp32 [BH, R];
-    kept fp32 [BH] is written, top_p fp32 [BH] stepped in place.  No allocation, no host synchronisation."""
-    if rows.dtype != torch.int64 or rows.dim() != 1 or not 1 <= rows.numel() <= 64:
-        raise ValueError(f"top_p_update: rows is an int64 vector of 1 to 64 rows, got {rows.dtype} {tuple(rows.shape)}")
-    R, BH = rows.numel(), top_p.numel()
-    _f32_vector("top_p_update(top_p)", top_p, BH)
-    _f32_vector("top_p_update(kept)", kept, BH)
-    if BH < 1 or lse_sparse.dtype != torch.float32 or lse_sparse.numel() % BH != 0 or lse_sparse.numel() == 0:
-        raise ValueError(f"top_p_update: lse_sparse is float32 [BH = {BH}, S], got {lse_sparse.dtype} {tuple(lse_sparse.shape)}")
-    _f32_vector("top_p_update(lse_dense)", lse_dense, BH * R)
-    lib = load()
-    _dev(lse_sparse, rows, lse_dense, top_p, kept)
-    rc = lib.svg_top_p_update(lse_sparse.data_ptr(), rows.data_ptr(), lse_dense.data_ptr(), R, BH, lse_sparse.numel() // BH, float(target),
-                              float(gain_up), float(gain_down), float(band), float(p_min), float(p_max), kept.data_ptr(), top_p.data_ptr(),
-                              _stream())
-    _check(rc, "svg_top_p_update")
-
-
 def _i32_vector(what: str, t: torch.Tensor, n: int) -> None:
     if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous():
         raise ValueError(f"{what}: a contiguous int32 tensor of {n} elements, got {t.dtype} {tuple(t.shape)}")
 
 
+def _kept_mass_operands(what: str, lse_sparse: torch.Tensor, rows: torch.Tensor, lse_dense: torch.Tensor, state: torch.Tensor, kept: torch.Tensor):
+    """The operands both controller steps share, beside the knob's own state [BH] (its binding checks that): rows int64 [R], R in 1..64, and
+    contiguous fp32 kept [BH], lse_sparse of BH * S elements (the kernel indexes it h * S + row) and lse_dense of BH * R.  -> (R, BH, S)"""
+    if rows.dtype != torch.int64 or rows.dim() != 1 or not 1 <= rows.numel() <= 64:
+        raise ValueError(f"{what}: rows is an int64 vector of 1 to 64 rows, got {rows.dtype} {tuple(rows.shape)}")
+    R, BH = rows.numel(), state.numel()
+    _f32_vector(f"{what}(kept)", kept, BH)
+    if BH < 1 or lse_sparse.dtype != torch.float32 or lse_sparse.numel() % BH != 0 or lse_sparse.numel() == 0 or not lse_sparse.is_contiguous():
+        raise ValueError(f"{what}: lse_sparse is a contiguous float32 [BH = {BH}, S], got {lse_sparse.dtype} "
+                         f"{tuple(lse_sparse.shape)}, strides {tuple(lse_sparse.stride())}")
+    _f32_vector(f"{what}(lse_dense)", lse_dense, BH * R)
+    return R, BH, lse_sparse.numel() // BH
+
+
+def top_p_update(lse_sparse: torch.Tensor, rows: torch.Tensor, lse_dense: torch.Tensor, top_p: torch.Tensor, kept: torch.Tensor,
+                 target: float, gain_up: float, gain_down: float, band: float, p_min: float, p_max: float) -> None:
+    """The controller step (svg_top_p_update): lse_sparse fp32 [BH, S] (any leading shape), rows device int64 [R], lse_dense fp32 [BH, R];
+    kept fp32 [BH] is written, top_p fp32 [BH] stepped in place.  No allocation, no host synchronisation."""
+    R, BH, S = _kept_mass_operands("top_p_update", lse_sparse, rows, lse_dense, top_p, kept)
+    _f32_vector("top_p_update(top_p)", top_p, BH)
+    lib = load()
+    _dev(lse_sparse, rows, lse_dense, top_p, kept)
+    rc = lib.svg_top_p_update(lse_sparse.data_ptr(), rows.data_ptr(), lse_dense.data_ptr(), R, BH, S, float(target), float(gain_up),
+                              float(gain_down), float(band), float(p_min), float(p_max), kept.data_ptr(), top_p.data_ptr(), _stream())
+    _check(rc, "svg_top_p_update")
+
+
 def band_width_update(lse_sparse: torch.Tensor, rows: torch.Tensor, lse_dense: torch.Tensor, band: torch.Tensor, kept: torch.Tensor,
                       target: float, gain_up: float, gain_down: float, dead: float, quantum: int, band_min: int, band_max: int,
                       skip_flag: Optional[torch.Tensor] = None) -> None:
-    """The controller step of SVG1's per-head band (svg_band_width_update): lse_sparse fp32 [BH, S] (any leading shape), rows device int64
-    [R], lse_dense fp32 [BH, R]; kept fp32 [BH] is written, band int32 [BH] stepped in place by whole quanta inside [band_min, band_max].
-    skip_flag (int32 [1] on the device, or None): non-zero leaves every band as it is — the dense_flag of the switched path.  No
-    allocation, no host synchronisation."""
-    if rows.dtype != torch.int64 or rows.dim() != 1 or not 1 <= rows.numel() <= 64:
-        raise ValueError(f"band_width_update: rows is an int64 vector of 1 to 64 rows, got {rows.dtype} {tuple(rows.shape)}")
-    R, BH = rows.numel(), band.numel()
+    """The controller step of SVG1's per-head band (svg_band_width_update), operands as top_p_update: kept fp32 [BH] is written, band int32
+    [BH] stepped in place by whole quanta inside [band_min, band_max].  skip_flag (int32 [1] on the device, or None): non-zero leaves
+    every band as it is — the dense_flag of the switched path.  No allocation, no host synchronisation."""
+    R, BH, S = _kept_mass_operands("band_width_update", lse_sparse, rows, lse_dense, band, kept)
     _i32_vector("band_width_update(band)", band, BH)
-    _f32_vector("band_width_update(kept)", kept, BH)
-    if BH < 1 or lse_sparse.dtype != torch.float32 or lse_sparse.numel() % BH != 0 or lse_sparse.numel() == 0 or not lse_sparse.is_contiguous():
-        raise ValueError(f"band_width_update: lse_sparse is a contiguous float32 [BH = {BH}, S], got {lse_sparse.dtype} "
-                         f"{tuple(lse_sparse.shape)}, strides {tuple(lse_sparse.stride())}")
-    _f32_vector("band_width_update(lse_dense)", lse_dense, BH * R)
     if skip_flag is not None and (skip_flag.dtype != torch.int32 or skip_flag.numel() < 1):
         raise ValueError(f"band_width_update: skip_flag is an int32 tensor of one element, got {skip_flag.dtype} {tuple(skip_flag.shape)}")
     lib = load()
     _dev(lse_sparse, rows, lse_dense, band, kept, skip_flag)
-    rc = lib.svg_band_width_update(lse_sparse.data_ptr(), rows.data_ptr(), lse_dense.data_ptr(), R, BH, lse_sparse.numel() // BH,
-                                   float(target), float(gain_up), float(gain_down), float(dead), int(quantum), int(band_min), int(band_max),
-                                   _ptr(skip_flag), kept.data_ptr(), band.data_ptr(), _stream())
+    rc = lib.svg_band_width_update(lse_sparse.data_ptr(), rows.data_ptr(), lse_dense.data_ptr(), R, BH, S, float(target), float(gain_up),
+                                   float(gain_down), float(dead), int(quantum), int(band_min), int(band_max), _ptr(skip_flag),
+                                   kept.data_ptr(), band.data_ptr(), _stream())
     _check(rc, "svg_band_width_update")
 
 

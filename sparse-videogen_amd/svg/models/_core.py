@@ -680,31 +680,49 @@ class CentroidStore:
         self.cfg.clear()
 
 
-class TopPStore:
-    """Per-layer state of the adaptive top-p (AdaptiveTopP), beside CentroidStore: `p[layer]`, an fp32 [cfg * H] DEVICE tensor — the
-    threshold of every head for the layer's NEXT sparse call, stepped in place by svg_top_p_update — and `kept[layer]`, fp32 [cfg * H], the
-    kept mass its last sparse call measured.  Nothing here is ever read back by the package.  A call with a different cfg * H (or on
-    another device) starts the layer again from the initial value; `clear()` forgets every layer (call between videos)."""
+class _KeptMassStore:
+    """Per-layer state of a knob steered by kept mass (TopPStore, BandStore): `state[layer]`, a [cfg * H] DEVICE tensor of the subclass's
+    `dtype` — the value of every head for the layer's NEXT sparse call, stepped in place by the knob's controller — and `kept[layer]`,
+    fp32 [cfg * H], the kept mass its last sparse call measured.  Nothing here is ever read back by the package.  A call with a different
+    cfg * H (or on another device) starts the layer again from the initial value; `clear()` forgets every layer (call between videos)."""
+    dtype = as_init = None   # (the subclass: the vector's dtype and the Python type `init` is converted to)
 
     def __init__(self):
-        self.p = {}
+        self.state = {}
         self.kept = {}
 
     def has(self, layer_idx, n=None) -> bool:
-        return layer_idx in self.p and (n is None or self.p[layer_idx].numel() == n)
+        return layer_idx in self.state and (n is None or self.state[layer_idx].numel() == n)
 
-    def get(self, layer_idx, n: int, init: float, device) -> torch.Tensor:
-        """The layer's [n] thresholds; filled with `init` (and the last kept mass forgotten) where the layer has none of that size."""
-        t = self.p.get(layer_idx)
+    def get(self, layer_idx, n: int, init, device) -> torch.Tensor:
+        """The layer's [n] values; filled with `init` (and the last kept mass forgotten) where the layer has none of that size."""
+        t = self.state.get(layer_idx)
         if t is None or t.numel() != n or t.device != torch.device(device):
-            t = torch.full((n,), float(init), dtype=torch.float32, device=device)
-            self.p[layer_idx] = t
+            t = torch.full((n,), self.as_init(init), dtype=self.dtype, device=device)
+            self.state[layer_idx] = t
             self.kept.pop(layer_idx, None)
         return t
 
     def clear(self):
-        self.p.clear()
+        self.state.clear()
         self.kept.clear()
+
+
+class TopPStore(_KeptMassStore):
+    """The state of the adaptive top-p (AdaptiveTopP), beside CentroidStore: `p[layer]`, fp32 — the thresholds svg_top_p_update steps; the
+    initial value is the processor's scalar top_p."""
+    dtype, as_init = torch.float32, float
+    p = property(lambda self: self.state)
+
+
+def _check_kept_mass_knob(knob, dead_name: str) -> None:
+    """What AdaptiveTopP and AdaptiveBand check alike: gains and dead zone not NaN and >= 0, 1 to 64 probe rows"""
+    name, dead = type(knob).__name__, getattr(knob, dead_name)
+    ok = lambda x: x == x and x >= 0   # noqa: E731  (not NaN, not negative)
+    if not (ok(knob.gain_up) and ok(knob.gain_down) and ok(dead)):
+        raise ValueError(f"{name}: gains and {dead_name} are >= 0, got {knob.gain_up}, {knob.gain_down}, {dead}")
+    if not 1 <= int(knob.rows) <= 64:
+        raise ValueError(f"{name}: 1 to 64 probe rows, got {knob.rows}")
 
 
 @dataclass
@@ -728,19 +746,16 @@ class AdaptiveTopP:
     valid_len: object = None
 
     def __post_init__(self):
-        ok = lambda x: x == x and x >= 0   # noqa: E731  (not NaN, not negative)
-        if not (ok(self.gain_up) and ok(self.gain_down) and ok(self.band)):
-            raise ValueError(f"AdaptiveTopP: gains and band are >= 0, got {self.gain_up}, {self.gain_down}, {self.band}")
+        _check_kept_mass_knob(self, "band")
         if not 0 <= self.p_min <= self.p_max <= 1:
             raise ValueError(f"AdaptiveTopP: 0 <= p_min <= p_max <= 1, got {self.p_min}, {self.p_max}")
-        if not 1 <= int(self.rows) <= 64:
-            raise ValueError(f"AdaptiveTopP: 1 to 64 probe rows, got {self.rows}")
 
 
-def _refuse_adaptive_when_sharded(what: str) -> None:
+def _refuse_kept_mass_knob_when_sharded(what: str, knob: str) -> None:
+    """knob: the processors' option, adaptive_top_p or adaptive_band"""
     if _dist._STATE["enabled"] or _dist.frame_shards_active() or _dist.token_shards_active():
-        raise NotImplementedError(f"{what}: adaptive_top_p under svg.distributed (enable, enable_frame_shards, enable_token_shards) is not "
-                                  f"implemented: the probe reads whole heads of the whole sequence; unset adaptive_top_p or run on one GPU")
+        raise NotImplementedError(f"{what}: {knob} under svg.distributed (enable, enable_frame_shards, enable_token_shards) is not "
+                                  f"implemented: the probe reads whole heads of the whole sequence; unset {knob} or run on one GPU")
 
 
 def _refuse_adaptive_without_lse(what: str, q: torch.Tensor, block_rows: int) -> None:
@@ -765,10 +780,18 @@ def probe_plan(valid_len, n_rows: int, cfg: int, S: int):
     return plan
 
 
-def adaptive_step(adaptive: AdaptiveTopP, top_p_store: TopPStore, layer_idx, p: torch.Tensor, lse: torch.Tensor, q, k, plan, lse_dense=None):
-    """After a sparse layer-call that ran with the thresholds p [cfg * H] (the store's tensor) and returned lse [cfg, H, S]: probe (K only;
-    lse_dense: what a quality probe on the same plan already measured, one [nb, H, R] per group), then svg_top_p_update — p is stepped in
-    place, the kept mass lands in the store.  No host synchronisation."""
+def _knob_probe_plan(quality, adaptive, cfg: int, S: int):
+    """The probe_plan of a layer-call under a kept-mass knob, drawn once: where the call is also probed for `quality`, that request's valid
+    length and row count (its one dense probe then feeds the controller as well), else the knob's."""
+    src = quality if quality is not None else adaptive
+    return probe_plan(src.valid_len, src.rows, cfg, S)
+
+
+def _kept_mass_step(update, store: _KeptMassStore, layer_idx, state: torch.Tensor, lse: torch.Tensor, q, k, plan, lse_dense=None):
+    """After a sparse layer-call that ran with the per-head values state [cfg * H] (the store's tensor) and returned lse [cfg, H, S]: probe
+    (K only; lse_dense: what a quality probe on the same plan already measured, one [nb, H, R] per group), then the knob's controller —
+    update(lse_sparse, rows, lse_dense, state, kept) on every group's heads: state is stepped in place, the kept mass lands in the store.
+    No host synchronisation."""
     from .. import _probe
 
     cfg, H, S, _ = q.shape
@@ -777,39 +800,25 @@ def adaptive_step(adaptive: AdaptiveTopP, top_p_store: TopPStore, layer_idx, p: 
     for i, (sl, vl, rows) in enumerate(plan):
         ld = lse_dense[i] if lse_dense is not None else _probe.sample_dense_lse(q[sl], k[sl], rows, vl)
         hs = slice(sl.start * H, sl.stop * H)
-        _native.top_p_update(lse[sl], rows.to(q.device, non_blocking=True), ld, p[hs], kept[hs], adaptive.target, adaptive.gain_up,
-                             adaptive.gain_down, adaptive.band, adaptive.p_min, adaptive.p_max)
-    top_p_store.kept[layer_idx] = kept
+        update(lse[sl], rows.to(q.device, non_blocking=True), ld, state[hs], kept[hs])
+    store.kept[layer_idx] = kept
+
+
+def adaptive_step(adaptive: AdaptiveTopP, top_p_store: TopPStore, layer_idx, p: torch.Tensor, lse: torch.Tensor, q, k, plan, lse_dense=None):
+    """_kept_mass_step with svg_top_p_update: the thresholds p [cfg * H] of the call are stepped in place."""
+    a = adaptive
+    _kept_mass_step(lambda *t: _native.top_p_update(*t, a.target, a.gain_up, a.gain_down, a.band, a.p_min, a.p_max),
+                    top_p_store, layer_idx, p, lse, q, k, plan, lse_dense)
 
 
 # ---------------------------------------------------------------------------------------------------------------
 # SVG1's adaptive band width: one band per head on the device, steered by measured kept mass (include/svg_attn_adaptive_band.h)
 # ---------------------------------------------------------------------------------------------------------------
-class BandStore:
-    """Per-layer state of the adaptive band (AdaptiveBand), as TopPStore: `band[layer]`, an int32 [cfg * H] DEVICE tensor — the band of every
-    head for the layer's NEXT sparse call, stepped in place by svg_band_width_update — and `kept[layer]`, fp32 [cfg * H], the kept mass its
-    last call measured.  Nothing here is ever read back by the package.  A call with a different cfg * H (or on another device) starts
-    the layer again from the mask's band; `clear()` forgets every layer (call between videos)."""
-
-    def __init__(self):
-        self.band = {}
-        self.kept = {}
-
-    def has(self, layer_idx, n=None) -> bool:
-        return layer_idx in self.band and (n is None or self.band[layer_idx].numel() == n)
-
-    def get(self, layer_idx, n: int, init: int, device) -> torch.Tensor:
-        """The layer's [n] bands; filled with `init` (and the last kept mass forgotten) where the layer has none of that size."""
-        t = self.band.get(layer_idx)
-        if t is None or t.numel() != n or t.device != torch.device(device):
-            t = torch.full((n,), int(init), dtype=torch.int32, device=device)
-            self.band[layer_idx] = t
-            self.kept.pop(layer_idx, None)
-        return t
-
-    def clear(self):
-        self.band.clear()
-        self.kept.clear()
+class BandStore(_KeptMassStore):
+    """The state of the adaptive band (AdaptiveBand): `band[layer]`, int32 — the bands svg_band_width_update steps; the initial value is
+    the mask's band."""
+    dtype, as_init = torch.int32, int
+    band = property(lambda self: self.state)
 
 
 @dataclass
@@ -838,9 +847,7 @@ class AdaptiveBand:
     valid_len: object = None
 
     def __post_init__(self):
-        ok = lambda x: x == x and x >= 0   # noqa: E731  (not NaN, not negative)
-        if not (ok(self.gain_up) and ok(self.gain_down) and ok(self.dead)):
-            raise ValueError(f"AdaptiveBand: gains and dead are >= 0, got {self.gain_up}, {self.gain_down}, {self.dead}")
+        _check_kept_mass_knob(self, "dead")
         if int(self.quantum) != self.quantum or not 1 <= int(self.quantum) <= 4096:
             raise ValueError(f"AdaptiveBand: quantum is an integer in [1, 4096], got {self.quantum}")
         for name in ("band_min", "band_max"):
@@ -849,8 +856,6 @@ class AdaptiveBand:
                 raise ValueError(f"AdaptiveBand: {name} is None or an integer >= 1, got {b}")
         if self.band_min is not None and self.band_max is not None and self.band_min > self.band_max:
             raise ValueError(f"AdaptiveBand: band_min <= band_max, got {self.band_min}, {self.band_max}")
-        if not 1 <= int(self.rows) <= 64:
-            raise ValueError(f"AdaptiveBand: 1 to 64 probe rows, got {self.rows}")
 
     def bounds(self, mask_band: int, S: int):
         """(band_min, band_max) of a call under a mask of band `mask_band` over S rows: the given bounds, checked — congruent to mask_band
@@ -872,15 +877,9 @@ class AdaptiveBand:
         return lo, hi
 
 
-def _refuse_adaptive_band_when_sharded(what: str) -> None:
-    if _dist._STATE["enabled"] or _dist.frame_shards_active() or _dist.token_shards_active():
-        raise NotImplementedError(f"{what}: adaptive_band under svg.distributed (enable, enable_frame_shards, enable_token_shards) is not "
-                                  f"implemented: the probe reads whole heads of the whole sequence; unset adaptive_band or run on one GPU")
-
-
 def _refuse_adaptive_band(what: str, q: torch.Tensor, band_store, q_prescaled: bool, fused: bool, out_dtype, mask, extra_masks=()) -> None:
     """What the adaptive band refuses, all of it before anything runs: there is no silent fall-back to the launch's one band."""
-    _refuse_adaptive_band_when_sharded(what)
+    _refuse_kept_mass_knob_when_sharded(what, "adaptive_band")
     if band_store is None:
         raise ValueError(f"{what}(adaptive=...) needs a band_store (BandStore): the bands live there between calls")
     D = q.shape[-1]
@@ -903,21 +902,11 @@ def _one_of(mask, cfg: int, what: str):
 
 def adaptive_band_step(adaptive: AdaptiveBand, band_store: BandStore, layer_idx, band: torch.Tensor, lse: torch.Tensor, q, k, plan,
                        bounds, lse_dense=None, skip_flag=None):
-    """After a sparse layer-call that ran with the bands `band` [cfg * H] (the store's tensor) and returned lse [cfg, H, S]: probe (K only;
-    lse_dense: what a quality probe on the same plan already measured, one [nb, H, R] per group), then svg_band_width_update — band is
-    stepped in place inside `bounds`, the kept mass lands in the store.  skip_flag: the dense_flag of the switched path (a dense step
-    measures and moves nothing).  No host synchronisation."""
-    from .. import _probe
-
-    cfg, H, S, _ = q.shape
-    lse = lse.reshape(cfg, H, S)
-    kept = _native.empty((cfg * H,), dtype=torch.float32, device=q.device)
-    for i, (sl, vl, rows) in enumerate(plan):
-        ld = lse_dense[i] if lse_dense is not None else _probe.sample_dense_lse(q[sl], k[sl], rows, vl)
-        hs = slice(sl.start * H, sl.stop * H)
-        _native.band_width_update(lse[sl], rows.to(q.device, non_blocking=True), ld, band[hs], kept[hs], adaptive.target, adaptive.gain_up,
-                                  adaptive.gain_down, adaptive.dead, adaptive.quantum, bounds[0], bounds[1], skip_flag=skip_flag)
-    band_store.kept[layer_idx] = kept
+    """_kept_mass_step with svg_band_width_update: the bands `band` [cfg * H] of the call are stepped in place inside `bounds`.  skip_flag: the
+    dense_flag of the switched path (a dense step measures and moves nothing)."""
+    a = adaptive
+    _kept_mass_step(lambda *t: _native.band_width_update(*t, a.target, a.gain_up, a.gain_down, a.dead, a.quantum, bounds[0], bounds[1],
+                                                         skip_flag=skip_flag), band_store, layer_idx, band, lse, q, k, plan, lse_dense)
 
 
 def _adaptive_band_call(run, adaptive: AdaptiveBand, band_store: BandStore, layer_idx, mask, bounds, q, k, v, quality, dense_flag=None):
@@ -926,8 +915,7 @@ def _adaptive_band_call(run, adaptive: AdaptiveBand, band_store: BandStore, laye
     cfg, H, S, _ = q.shape
     band = band_store.get(layer_idx, cfg * H, mask.band, q.device)
     out, lse = run(band)
-    valid = quality.valid_len if quality is not None else adaptive.valid_len
-    plan = probe_plan(valid, quality.rows if quality is not None else adaptive.rows, cfg, S)
+    plan = _knob_probe_plan(quality, adaptive, cfg, S)
     lse_d = None
     if quality is not None:   # (the rows are drawn once: the quality probe's dense lse feeds the controller)
         lse_d = log_quality(quality, out, lse, q, k, v, dense_flag=dense_flag, plan=plan, band=band.clone())
@@ -1038,7 +1026,7 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
     if quality is not None:
         _refuse_quality_when_sharded("svg2_sparse_attention")
     if adaptive is not None:
-        _refuse_adaptive_when_sharded("svg2_sparse_attention")
+        _refuse_kept_mass_knob_when_sharded("svg2_sparse_attention", "adaptive_top_p")
         if top_p_store is None:
             raise ValueError("svg2_sparse_attention(adaptive=...) needs a top_p_store (TopPStore): the thresholds live there between calls")
         # (block-rows of the launch: the query clusters, and Hunyuan's two text pseudo-clusters behind them)
@@ -1100,8 +1088,7 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
     out, lse_p = out if probe_lse else (out, None)
     plan = lse_d = None
     if adaptive is not None:   # the rows of this call, drawn once: the quality probe below measures on them as well
-        valid = quality.valid_len if quality is not None else adaptive.valid_len
-        plan = probe_plan(valid, quality.rows if quality is not None else adaptive.rows, cfg, S)
+        plan = _knob_probe_plan(quality, adaptive, cfg, S)
     if quality is not None:
         lse_d = log_quality(quality, out, lse_p, q, k, v, density=density_calculation(dyn_map, q_sizes, k_sizes), plan=plan,
                             top_p=None if adaptive is None else p_heads.clone())

@@ -327,7 +327,7 @@ class Hunyuan_SVGAttn_Processor2_0(_HunyuanProcessorBase):
         quality = _core.quality_request(type(self).__name__, self.quality_log, self.quality_rows, valid, timestep, self.layer_idx)
         ab = {}
         if self.adaptive_band is not None:
-            _core._refuse_adaptive_band_when_sharded(type(self).__name__)
+            _core._refuse_kept_mass_knob_when_sharded(type(self).__name__, "adaptive_band")
             # (the probe's rows and keys follow the call's valid lengths)
             ab = dict(adaptive=dataclasses.replace(self.adaptive_band, valid_len=valid), band_store=self.band_store, layer_idx=self.layer_idx)
         # the layer test is host data; the timestep test stays on the device when the timestep is a GPU tensor (device_switch)
@@ -409,7 +409,7 @@ class Hunyuan_SAPAttn_Processor2_0(Hunyuan_SVGAttn_Processor2_0):
         quality = _core.quality_request(type(self).__name__, self.quality_log, self.quality_rows, valid, timestep, self.layer_idx)
         adaptive = self.adaptive_top_p
         if adaptive is not None:
-            _core._refuse_adaptive_when_sharded(type(self).__name__)
+            _core._refuse_kept_mass_knob_when_sharded(type(self).__name__, "adaptive_top_p")
             adaptive = dataclasses.replace(adaptive, valid_len=valid)   # (the probe's rows and keys follow the call's valid lengths)
         if _core.is_full_attention(self.layer_idx, timestep, self.first_layers_fp, self.first_times_fp):
             if self.zero_step_kmeans_init and query.is_cuda:

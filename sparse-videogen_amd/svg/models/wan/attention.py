@@ -272,7 +272,7 @@ class WanAttn_SVGAttn_Processor2_0:
         quality = _core.quality_request(type(self).__name__, self.quality_log, self.quality_rows, None, timestep, self.layer_idx)
         ab = {}
         if self.adaptive_band is not None:
-            _core._refuse_adaptive_band_when_sharded(type(self).__name__)
+            _core._refuse_kept_mass_knob_when_sharded(type(self).__name__, "adaptive_band")
             ab = dict(adaptive=self.adaptive_band, band_store=self.band_store, layer_idx=self.layer_idx)
         dense_flag = None   # (device-side dense / sparse switch, see the Hunyuan processor)
         if self.device_switch and _core.attention_dtype() == "bf16" and self.fused_placement and self.layer_idx >= self.first_layers_fp and self.block_mask is not None \
@@ -354,7 +354,7 @@ class WanAttn_SAPAttn_Processor(WanAttn_SVGAttn_Processor2_0):
             f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
         quality = _core.quality_request(type(self).__name__, self.quality_log, self.quality_rows, None, timestep, self.layer_idx)
         if self.adaptive_top_p is not None:
-            _core._refuse_adaptive_when_sharded(type(self).__name__)
+            _core._refuse_kept_mass_knob_when_sharded(type(self).__name__, "adaptive_top_p")
         if _core.is_full_attention(self.layer_idx, timestep, self.first_layers_fp, self.first_times_fp):
             if self.zero_step_kmeans_init and query.is_cuda:
                 V = geo.video_length

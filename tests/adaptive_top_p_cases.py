@@ -1,18 +1,11 @@
 """Float64 statements shared by tests/test_adaptive_top_p_cpu.py and tests/test_gpu_adaptive_top_p.py: the controller law of
-svg_top_p_update (include/svg_attn_adaptive_top_p.h) and the per-head oracle of the block map."""
+svg_top_p_update (include/svg_attn_adaptive_top_p.h) and the per-head oracle of the block map.  kept_mass, params32 and ulps32 live in
+tests/kept_mass_cases.py (both controllers' tests share them) and are re-exported here."""
 import numpy as np
 import torch
 
+from kept_mass_cases import kept_mass, params32, ulps32  # noqa: F401
 from oracle import svg_oracle as O
-
-
-def kept_mass(lse_sparse, rows, lse_dense):
-    """float64 [BH]: mean_i exp(lse_sparse[h, rows[i]] - lse_dense[h, i]); a -inf in lse_sparse counts 0.  numpy in, numpy out."""
-    ls = np.asarray(lse_sparse, dtype=np.float64)[:, np.asarray(rows)]
-    ld = np.asarray(lse_dense, dtype=np.float64)
-    with np.errstate(invalid="ignore", over="ignore"):
-        term = np.where(np.isneginf(ls), 0.0, np.exp(ls - ld))
-    return term.mean(axis=1)
 
 
 def law(p, kept, target, gain_up=1.0, gain_down=0.25, band=0.02, p_min=0.1, p_max=1.0):
@@ -23,18 +16,6 @@ def law(p, kept, target, gain_up=1.0, gain_down=0.25, band=0.02, p_min=0.1, p_ma
         step = np.where(e > 0, gain_up * e, np.where(e < -band, gain_down * (e + band), 0.0))
         new = np.clip(p + step, p_min, p_max)
     return np.where(np.isfinite(kept), new, p)
-
-
-def params32(kw):
-    """the law's parameters as the C ABI's floats carry them"""
-    return {name: float(np.float32(val)) for name, val in kw.items()}
-
-
-def ulps32(a, b):
-    """distance in fp32 units in the last place between two float32 arrays of finite values of one sign (0 included)"""
-    ia = np.asarray(a, dtype=np.float32).view(np.int32).astype(np.int64)
-    ib = np.asarray(b, dtype=np.float32).view(np.int32).astype(np.int64)
-    return np.abs(ia - ib)
 
 
 def per_head_map(qc, kc, q_sizes, k_sizes, p_heads, min_kc_ratio=0.0):

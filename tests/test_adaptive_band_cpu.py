@@ -86,7 +86,9 @@ def test_the_controller_file_is_built_without_contraction():
     spec = importlib.util.spec_from_file_location("svg_build_for_test", ROOT / "sparse-videogen_amd" / "build.py")
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    assert {"band_width_control.hip", "top_p_control.hip", "dynmap.hip"} <= mod.STRICT_FP
+    assert {"kept_mass_control.hip", "dynmap.hip"} <= mod.STRICT_FP
+    csrc = ROOT / "sparse-videogen_amd" / "csrc"                   # both controllers live in that one file
+    assert (csrc / "kept_mass_control.hip").exists() and not (csrc / "band_width_control.hip").exists() and not (csrc / "top_p_control.hip").exists()
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -268,6 +268,8 @@ def test_wrappers_refuse_on_cpu_tensors():
         nat.top_p_update(ls, ok, ld, p, torch.zeros(3), 0.9, 1.0, 0.25, 0.02, 0.1, 1.0)
     with pytest.raises(ValueError, match="lse_sparse"):
         nat.top_p_update(ls.double(), ok, ld, p, kept, 0.9, 1.0, 0.25, 0.02, 0.1, 1.0)
+    with pytest.raises(ValueError, match="contiguous"):       # a strided view is refused, not read wrongly (the kernel indexes h * S + row)
+        nat.top_p_update(torch.zeros(2, 140)[:, ::2], ok, ld, p, kept, 0.9, 1.0, 0.25, 0.02, 0.1, 1.0)
 
 
 def test_the_allocating_wrappers_are_not_public_functions_of_the_native_module():

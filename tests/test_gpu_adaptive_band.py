@@ -17,6 +17,7 @@ import torch
 
 import adaptive_band_cases as BC
 import adaptive_top_p_cases as AC
+import kept_mass_cases as KM
 import sparse_lse_cases as SC
 from oracle import svg_oracle as O
 from poisoned import load_native, unwritten
@@ -209,9 +210,6 @@ def controller_case(R):
     """7 heads over S = 790: far below target (up, to band_max), everything kept (down, to band_min), a -inf row, a NaN head, a head in the
     dead zone, one just below target (a small step up), one above the dead zone (a small step down)"""
     BHu, S = 7, 790
-    g = torch.Generator().manual_seed(200 + R)
-    rows = [S - 1] if R == 1 else ([0, S - 1, 5, 5] + torch.randint(0, S, (64,), generator=g).tolist())[:R]
-    ls = torch.randn(BHu, S, generator=g) * 3
     delta = torch.zeros(BHu, R)
     delta[0] = 5.0                                              # keeps < 1 %
     delta[1] = 0.0                                              # keeps everything
@@ -219,9 +217,7 @@ def controller_case(R):
     delta[4] = -math.log(0.91)                                  # kept 0.91: inside the dead zone [0.9, 0.92]
     delta[5] = -math.log(0.80)                                  # kept 0.80: e = 0.1 -> 1.6 quanta -> 2
     delta[6] = -math.log(0.99)                                  # kept 0.99: e + dead = -0.07 -> -1.12 quanta -> -1
-    ld = ls[:, rows] + delta
-    ls[2, rows[-1]] = -math.inf                                 # a row the sparse form gave no key: counts 0
-    ls[3] = math.nan                                            # a head without a usable measurement
+    rows, ls, ld = KM.controller_inputs(200 + R, BHu, S, R, lambda g: delta)    # (head 2: a -inf row, head 3: NaN)
     band0 = [384, 128, 256, 640, 512, 384, 768]
     return S, rows, ls, ld, band0
 

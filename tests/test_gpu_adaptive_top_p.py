@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import adaptive_top_p_cases as AC
+import kept_mass_cases as KM
 import sparse_lse_cases as SC
 from poisoned import load_native, unwritten
 from test_gpu_processors import _clustered
@@ -148,15 +149,14 @@ LAW = dict(target=0.8, gain_up=1.0, gain_down=0.5, band=0.02, p_min=0.2, p_max=0
 @pytest.mark.parametrize("R", [1, 17, 64])
 def test_top_p_update_against_the_float64_law(nat, R):
     BHu, S = 7, 300
-    g = torch.Generator().manual_seed(100 + R)
-    rows = [S - 1] if R == 1 else ([0, S - 1, 5, 5] + torch.randint(0, S, (64,), generator=g).tolist())[:R]
-    ls = torch.randn(BHu, S, generator=g) * 3
-    delta = torch.rand(BHu, R, generator=g)                     # lse_dense - lse_sparse >= 0: a kept mass in (1 / e, 1]
-    delta[0] = 5.0                                              # head 0 keeps < 1 %: far below target, driven to p_max
-    delta[1] = 0.0                                              # head 1 keeps everything: far above the band, driven to p_min
-    ld = ls[:, rows] + delta
-    ls[2, rows[-1]] = -math.inf                                 # a row the sparse form gave no key: counts 0
-    ls[3] = math.nan                                            # a head without a usable measurement
+
+    def delta(g):
+        d = torch.rand(BHu, R, generator=g)                     # lse_dense - lse_sparse >= 0: a kept mass in (1 / e, 1]
+        d[0] = 5.0                                              # head 0 keeps < 1 %: far below target, driven to p_max
+        d[1] = 0.0                                              # head 1 keeps everything: far above the band, driven to p_min
+        return d
+
+    rows, ls, ld = KM.controller_inputs(100 + R, BHu, S, R, delta)      # (head 2: a -inf row, head 3: NaN)
     p0 = torch.tensor([0.5, 0.25, 0.3, 0.77, 0.9, 0.2, 0.61])
 
     def run():
