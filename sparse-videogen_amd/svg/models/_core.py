@@ -7,6 +7,8 @@ branch raises: there is no CPU fallback for the sparse hot path.
 """
 from __future__ import annotations
 
+import contextlib
+import dataclasses
 import json
 import weakref
 from dataclasses import dataclass
@@ -191,7 +193,7 @@ def rows_of_this_rank(what: str, geo: Geometry, shard_form: bool = True) -> int:
 
 
 def _one_mask(what: str, mask, cfg: int):
-    """the one mask of a batch in frame-shard mode: per-video masks must be equal"""
+    """the one mask of a batch where per-video masks must be equal: frame-shard mode (and the adaptive band, which has refused others already)"""
     pm = per_video(mask, cfg, what)
     if pm is None:
         return mask
@@ -234,23 +236,6 @@ def _frame_shard_setup(what: str, q, k, v, geo: Geometry, num_sampled_rows: Opti
                          f"use a group of at most {_dist.MERGE_MAX_PARTS} ranks")
     _require_gpu(q, what)
     return (geo.seq_len, geo.vid0, geo.num_frame, geo.frame_size), group
-
-
-def _frame_shard_svg1(what: str, q, k, v, geo: Geometry, mask, dense_mask, prof, num_sampled_rows: int, sample_max_row: int, dense_flag,
-                      **refusable):
-    """svg1_attention_device_switch (dense_mask, dense_flag given) / svg1_sparse_attention (both None) in frame-shard mode:
-    -> (out [cfg, H, S_r, D], best_mask_idx [cfg, H]).  The sampled rows are GLOBAL rows of the whole sequence, drawn from the
-    broadcast-seeded generator of the switched path on both: every rank draws the same."""
-    cfg, H = q.shape[0], q.shape[1]
-    mask = _one_mask(f"{what}(mask)", mask, cfg)
-    if dense_mask is not None:
-        dense_mask = _one_mask(f"{what}(dense_mask)", dense_mask, cfg)
-    geometry, group = _frame_shard_setup(what, q, k, v, geo, num_sampled_rows, **refusable)
-    n = min(num_sampled_rows, geo.seq_len)
-    rows = torch.randint(low=0, high=sample_max_row, size=(n,), generator=_switch_generator())
-    out, best = _dist.token_sharded_svg1_layer_call(q, k, v, mask, prof, geometry, rows, group=group, dense_mask=dense_mask,
-                                                    dense_flag=dense_flag)
-    return out, best.reshape(cfg, H)
 
 
 @time_logging_decorator("Level 3 - Dense Flash Attention")
@@ -482,7 +467,7 @@ def svg1_attention_device_switch(q, k, v, geo: Geometry, mask: "_native.BandMask
     out_dtype=torch.float32: fp32 rows.  Plain q only (ValueError), not under svg.distributed (NotImplementedError).
     Frame-shard mode (svg.distributed.enable_frame_shards): q, k, v [cfg, H, S_r, D] are all heads of this rank's frame_shard of the
     sequence `geo` describes, the call is token_sharded_svg1_layer_call with dense_mask / dense_flag, -> (out [cfg, H, S_r, D], best);
-    what has no shard form raises before any collective (_frame_shard_setup).
+    the sampled rows are GLOBAL rows of the whole sequence; what has no shard form raises before any collective (_frame_shard_setup).
     quality: a QualityRequest (quality_request): the call is probed as well and its record queued (log_quality) — on EVERY call, the host
     does not know whether the step is dense; the record carries dense_flag and the writer drops those of dense steps.  Where the launch has
     an LSE form the call goes through it (the same o).  Refused under svg.distributed.
@@ -493,62 +478,9 @@ def svg1_attention_device_switch(q, k, v, geo: Geometry, mask: "_native.BandMask
     rows are drawn once, its one dense probe feeds both and the record gains "band".  ValueError, before anything runs, where the launch
     has no LSE form (head_dim 64, fp8, a pre-scaled q, out_dtype); NotImplementedError under svg.distributed and for per-video masks
     that differ.  None: nothing changes."""
-    if adaptive is not None:
-        _refuse_adaptive_band("svg1_attention_device_switch", q, band_store, q_prescaled, True, out_dtype, mask, (("dense_mask", dense_mask),))
-        band_bounds = adaptive.bounds(_one_of(mask, q.shape[0], "svg1_attention_device_switch(mask)").band, q.shape[2])
-    if quality is not None:
-        _refuse_quality_when_sharded("svg1_attention_device_switch")
-    if _dist.frame_shards_active():   # q, k, v: this rank's rows; -> (out [cfg, H, S_r, D], best_mask_idx)
-        return _frame_shard_svg1("svg1_attention_device_switch", q, k, v, geo, mask, dense_mask, prof, num_sampled_rows, sample_max_row,
-                                 dense_flag, q_prescaled=q_prescaled, return_lse=return_lse, out_dtype=out_dtype)
-    probe_lse = (quality is not None and not return_lse and _quality_lse_form(q, q_prescaled)) or (adaptive is not None and not return_lse)
-    kw = _state_kw("svg1_attention_device_switch", return_lse or probe_lse, out_dtype, q_prescaled, TOKEN_MAJOR_IO)
-    _require_gpu(q, "SVG1 attention")
-    cfg, H = q.shape[0], q.shape[1]
-    pm, pd = per_video(mask, cfg, "svg1_attention_device_switch(mask)"), per_video(dense_mask, cfg, "svg1_attention_device_switch(dense_mask)")
-    groups = None
-    if pm is not None or pd is not None:
-        pairs, heads = video_groups(list(zip(pm or [mask] * cfg, pd or [dense_mask] * cfg)), H)
-        mask, dense_mask = pairs[0]
-        if len(pairs) > 1:
-            _no_sharding_of_groups("SVG1 attention")
-            groups = ([m for m, _ in pairs], [d for _, d in pairs], heads)
-    if _dist.token_shards_active() and not _local:   # q, k, v: this rank's rows; whole heads of the whole sequence inside, rows back
-        return _dist.run_token_sharded(lambda qh, kh, vh: svg1_attention_device_switch(
-            qh, kh, vh, geo, mask, dense_mask, prof, num_sampled_rows, sample_max_row, dense_flag, _local=True,
-            q_prescaled=q_prescaled), (q, k, v), geo.seq_len, _dist.token_shards_group())
-    if _dist.active() and not _local:   # svg.distributed.enable(): this rank's heads only, outputs all-gathered
-        return _dist.run_sharded(lambda qh, kh, vh: svg1_attention_device_switch(
-            qh, kh, vh, geo, mask, dense_mask, prof, num_sampled_rows, sample_max_row, dense_flag, _local=True,
-            q_prescaled=q_prescaled), (q, k, v), _dist.current_group())
-    mses = sample_mse(q, k, v, geo, prof, num_sampled_rows, sample_max_row, skip_flag=dense_flag, generator=_switch_generator(),
-                      q_prescaled=q_prescaled)
-    best_mask_idx = torch.argmin(mses, dim=0)
-    if adaptive is not None:   # (one mask for the batch, no sharding: refused above otherwise)
-        from .. import _adaptive_band
-
-        out = _adaptive_band_call(lambda band: _adaptive_band.band_attention_switch_per_head(
-            q, k, v, mask, dense_mask, dense_flag, band, head_perm_flag=best_mask_idx, vid0=geo.vid0, num_frame=geo.num_frame,
-            frame_size=geo.frame_size, token_major_out=TOKEN_MAJOR_IO), adaptive, band_store, layer_idx, mask, band_bounds, q, k, v, quality,
-            dense_flag=dense_flag)
-        best = torch.where(dense_flag.reshape(()) != 0, torch.full_like(best_mask_idx, -1), best_mask_idx)
-        return (out[0], best, out[1]) if return_lse else (out[0], best)
-    if groups is not None:
-        out = _native.band_attention_groups(q, k, v, groups[0], groups[2], alt_masks=groups[1], use_alt_flag=dense_flag,
-                                            head_perm_flag=best_mask_idx, vid0=geo.vid0, num_frame=geo.num_frame,
-                                            frame_size=geo.frame_size, q_prescaled=q_prescaled, **kw)
-    else:
-        if _local:   # (enable(): contiguous head slices are gathered; token-shard mode: token-major rows are what the outbound exchange sends)
-            kw["token_major_out"] = TOKEN_MAJOR_IO and _dist.token_shards_active()
-        out = _native.band_attention_switch(q, k, v, mask, dense_mask, dense_flag, head_perm_flag=best_mask_idx, vid0=geo.vid0,
-                                            num_frame=geo.num_frame, frame_size=geo.frame_size, q_prescaled=q_prescaled, **kw)
-    best = torch.where(dense_flag.reshape(()) != 0, torch.full_like(best_mask_idx, -1), best_mask_idx)
-    if quality is not None:
-        o_p, lse_p = out if (return_lse or probe_lse) else (out, None)
-        log_quality(quality, o_p, lse_p, q, k, v, q_prescaled, dense_flag=dense_flag)
-        if probe_lse:
-            out = o_p
-    return (out[0], best, out[1]) if return_lse else (out, best)
+    return _svg1_layer_call("svg1_attention_device_switch", True, q, k, v, geo, mask, prof, num_sampled_rows, sample_max_row,
+                            dense_mask=dense_mask, dense_flag=dense_flag, _local=_local, q_prescaled=q_prescaled, return_lse=return_lse,
+                            out_dtype=out_dtype, quality=quality, adaptive=adaptive, band_store=band_store, layer_idx=layer_idx)
 
 
 def svg1_sparse_attention(q, k, v, geo: Geometry, mask: "_native.BandMask", prof: "_native.ProfileDesc",
@@ -562,71 +494,104 @@ def svg1_sparse_attention(q, k, v, geo: Geometry, mask: "_native.BandMask", prof
     Hunyuan 720p); fused=False runs the three kernels of the reference pipeline.
     mask: one BandMask for the batch, or a sequence of cfg of them, one per video (see video_groups); the profiler's masks do not depend
     on the prompt length, so the profiling pass is the same either way.
-    return_lse: (out, best_mask_idx, lse) with the softmax state of every row, as _native.band_attention returns it;
-    out_dtype=torch.float32: fp32 rows.  The fused 16-bit path with a plain q only (ValueError), not under svg.distributed
-    (NotImplementedError).
-    Frame-shard mode: as svg1_attention_device_switch, without a flag; the rows come from the switched path's generator (every rank
-    draws the same).
-    quality: a QualityRequest (quality_request): the call is probed as well and its record queued (log_quality); where the launch has an
-    LSE form — head_dim 128, 16-bit, plain q, fused — it goes through it (the same o) and the kept mass is logged, elsewhere the error
-    alone.  Refused under svg.distributed.
-    adaptive / band_store / layer_idx: as svg1_attention_device_switch, through svg_band_attention_per_head_lse and without a skip flag
-    (every call of this branch is a sparse step); fused=False is refused as well (ValueError)."""
+    return_lse, out_dtype, frame-shard mode, quality, adaptive / band_store / layer_idx: as svg1_attention_device_switch, without a flag —
+    every call of this branch is a sparse step, the launches are _native.band_attention and svg_band_attention_per_head_lse — and on the
+    fused 16-bit path only: fp8 and fused=False have no LSE form (return_lse, adaptive: ValueError; quality: the error alone, no kept mass)
+    and no shard form.  The rows come from the global CPU generator like the reference's, in frame-shard mode from the switched path's
+    (every rank draws the same)."""
+    return _svg1_layer_call("svg1_sparse_attention", False, q, k, v, geo, mask, prof, num_sampled_rows, sample_max_row, fused=fused,
+                            _local=_local, q_prescaled=q_prescaled, return_lse=return_lse, out_dtype=out_dtype, quality=quality,
+                            adaptive=adaptive, band_store=band_store, layer_idx=layer_idx)
+
+
+def _svg1_layer_call(what: str, switched: bool, q, k, v, geo: Geometry, mask, prof, num_sampled_rows: int, sample_max_row: int, *,
+                     dense_mask=None, dense_flag=None, fused: bool = True, _local: bool = False, q_prescaled: bool = False,
+                     return_lse: bool = False, out_dtype=None, quality=None, adaptive=None, band_store=None, layer_idx=None):
+    """The SVG1 layer-call, once: refusals -> frame shards, token shards or head shards -> profiler -> band launch ->
+    probes.  switched: svg1_attention_device_switch (dense_mask and dense_flag given, fused) / svg1_sparse_attention; what the two do
+    differently is decided on the five lines below and nowhere else."""
+    what_gpu = "SVG1 attention" if switched else "SVG1 sparse attention"   # (as _require_gpu and the groups' refusals name the call)
+    fp8 = not switched and _use_fp8(q)   # (the switched launch has no fp8 form: the processors switch on the device at bf16 only)
+    flag_kw = dict(dense_flag=dense_flag) if switched else {}   # (what the probes get of the flag: the host branch passes none)
+    timer = time_logging_decorator("Level 3 - sparse_flex_attention") if not switched else contextlib.nullcontext()   # (the switched launch: no label)
+    rows_from = _switch_generator if switched else (lambda: None)   # (None: the global CPU generator, as the reference draws)
     if adaptive is not None:
-        _refuse_adaptive_band("svg1_sparse_attention", q, band_store, q_prescaled, fused, out_dtype, mask)
-        band_bounds = adaptive.bounds(_one_of(mask, q.shape[0], "svg1_sparse_attention(mask)").band, q.shape[2])
+        _refuse_adaptive_band(what, q, band_store, q_prescaled, fused, out_dtype, mask, (("dense_mask", dense_mask),) if switched else ())
+        band_bounds = adaptive.bounds(_one_mask(f"{what}(mask)", mask, q.shape[0]).band, q.shape[2])   # (masks that differ: refused above)
     if quality is not None:
-        _refuse_quality_when_sharded("svg1_sparse_attention")
+        _refuse_quality_when_sharded(what)
+    cfg, H = q.shape[0], q.shape[1]
     if _dist.frame_shards_active():   # q, k, v: this rank's rows; -> (out [cfg, H, S_r, D], best_mask_idx)
-        return _frame_shard_svg1("svg1_sparse_attention", q, k, v, geo, mask, None, prof, num_sampled_rows, sample_max_row, None,
-                                 q_prescaled=q_prescaled, return_lse=return_lse, out_dtype=out_dtype, fused=fused)
+        mask = _one_mask(f"{what}(mask)", mask, cfg)
+        if dense_mask is not None:
+            dense_mask = _one_mask(f"{what}(dense_mask)", dense_mask, cfg)
+        geometry, group = _frame_shard_setup(what, q, k, v, geo, num_sampled_rows, q_prescaled, return_lse, out_dtype, fused)
+        # (global rows, from the broadcast-seeded generator of the switched path on both branches: every rank draws the same)
+        rows = torch.randint(low=0, high=sample_max_row, size=(min(num_sampled_rows, geo.seq_len),), generator=_switch_generator())
+        out, best = _dist.token_sharded_svg1_layer_call(q, k, v, mask, prof, geometry, rows, group=group, dense_mask=dense_mask,
+                                                        dense_flag=dense_flag)
+        return out, best.reshape(cfg, H)
     probe_lse = (quality is not None and not return_lse and _quality_lse_form(q, q_prescaled, fused)) or (adaptive is not None and not return_lse)
-    kw = _state_kw("svg1_sparse_attention", return_lse or probe_lse, out_dtype, q_prescaled, TOKEN_MAJOR_IO, fp8=_use_fp8(q), fused=fused)
-    _require_gpu(q, "SVG1 sparse attention")
+    kw = _state_kw(what, return_lse or probe_lse, out_dtype, q_prescaled, TOKEN_MAJOR_IO, fp8=fp8, fused=fused)
+    _require_gpu(q, what_gpu)
+    pm, pd = per_video(mask, cfg, f"{what}(mask)"), per_video(dense_mask, cfg, f"{what}(dense_mask)")
     groups = None
-    pm = per_video(mask, q.shape[0], "svg1_sparse_attention(mask)")
-    if pm is not None:
-        masks, heads = video_groups(pm, q.shape[1])
-        mask = masks[0]
-        if len(masks) > 1:
-            _no_sharding_of_groups("SVG1 sparse attention")
-            groups = (masks, heads)
-    if _dist.token_shards_active() and not _local:   # q, k, v: this rank's rows; whole heads of the whole sequence inside, rows back
-        return _dist.run_token_sharded(lambda qh, kh, vh: svg1_sparse_attention(
-            qh, kh, vh, geo, mask, prof, num_sampled_rows, sample_max_row, fused, _local=True, q_prescaled=q_prescaled), (q, k, v),
-            geo.seq_len, _dist.token_shards_group())
-    if _dist.active() and not _local:   # svg.distributed.enable(): this rank's heads only, outputs all-gathered
-        return _dist.run_sharded(lambda qh, kh, vh: svg1_sparse_attention(
-            qh, kh, vh, geo, mask, prof, num_sampled_rows, sample_max_row, fused, _local=True, q_prescaled=q_prescaled), (q, k, v),
-            _dist.current_group())
-    mses = sample_mse(q, k, v, geo, prof, num_sampled_rows, sample_max_row, q_prescaled=q_prescaled)
+    if pm is not None or pd is not None:   # (mask, dense_mask) pairs; the host branch's dense_mask is None: it groups masks
+        pairs, heads = video_groups(list(zip(pm or [mask] * cfg, pd or [dense_mask] * cfg)), H)
+        mask, dense_mask = pairs[0]
+        if len(pairs) > 1:
+            _no_sharding_of_groups(what_gpu)
+            groups = ([m for m, _ in pairs], [d for _, d in pairs], heads)
+    if not _local and (_dist.token_shards_active() or _dist.active()):
+        def whole_heads(qh, kh, vh):   # (quality, adaptive, return_lse: refused above in these modes)
+            return _svg1_layer_call(what, switched, qh, kh, vh, geo, mask, prof, num_sampled_rows, sample_max_row, dense_mask=dense_mask,
+                                    dense_flag=dense_flag, fused=fused, _local=True, q_prescaled=q_prescaled)
+
+        if _dist.token_shards_active():   # q, k, v: this rank's rows; whole heads of the whole sequence inside, rows back
+            return _dist.run_token_sharded(whole_heads, (q, k, v), geo.seq_len, _dist.token_shards_group())
+        return _dist.run_sharded(whole_heads, (q, k, v), _dist.current_group())   # enable(): this rank's heads only, outputs all-gathered
+    mses = sample_mse(q, k, v, geo, prof, num_sampled_rows, sample_max_row, skip_flag=dense_flag, generator=rows_from(), q_prescaled=q_prescaled)
     best_mask_idx = torch.argmin(mses, dim=0)  # [cfg, H] int64; NaN wins like torch.argmin in the reference
     pk = dict(head_perm_flag=best_mask_idx, vid0=geo.vid0, num_frame=geo.num_frame, frame_size=geo.frame_size)
+
+    def final_best():   # (-1 on a dense step, which only the device knows; computed after the launch)
+        return torch.where(dense_flag.reshape(()) != 0, torch.full_like(best_mask_idx, -1), best_mask_idx) if switched else best_mask_idx
+
     if adaptive is not None:   # (fused, 16-bit, one mask for the batch, no sharding: refused above otherwise)
         from .. import _adaptive_band
 
-        with time_logging_decorator("Level 3 - sparse_flex_attention"):
-            out = _adaptive_band_call(lambda band: _adaptive_band.band_attention_per_head(q, k, v, mask, band, token_major_out=TOKEN_MAJOR_IO, **pk),
-                                      adaptive, band_store, layer_idx, mask, band_bounds, q, k, v, quality)
-        return (out[0], best_mask_idx, out[1]) if return_lse else (out[0], best_mask_idx)
+        if switched:
+            run = lambda band: _adaptive_band.band_attention_switch_per_head(q, k, v, mask, dense_mask, dense_flag, band,   # noqa: E731
+                                                                             token_major_out=TOKEN_MAJOR_IO, **pk)
+        else:
+            run = lambda band: _adaptive_band.band_attention_per_head(q, k, v, mask, band, token_major_out=TOKEN_MAJOR_IO, **pk)   # noqa: E731
+        with timer:
+            out = _adaptive_band_call(run, adaptive, band_store, layer_idx, mask, band_bounds, q, k, v, quality, **flag_kw)
+        return (out[0], final_best(), out[1]) if return_lse else (out[0], final_best())
     if fused:
-        with time_logging_decorator("Level 3 - sparse_flex_attention"):
+        with timer:
             if groups is not None:
-                if _use_fp8(q):
+                if fp8:
                     raise NotImplementedError("SVG1 sparse attention: fp8 attention with per-video lengths that differ is not implemented")
-                out = _native.band_attention_groups(q, k, v, groups[0], groups[1], q_prescaled=q_prescaled, **kw, **pk)
-            elif _use_fp8(q):   # (the fp8 pre-pass folds whatever scale it is given into its quantisation of q)
+                alt = dict(alt_masks=groups[1], use_alt_flag=dense_flag) if switched else {}
+                out = _native.band_attention_groups(q, k, v, groups[0], groups[2], q_prescaled=q_prescaled, **alt, **kw, **pk)
+            elif fp8:   # (the fp8 pre-pass folds whatever scale it is given into its quantisation of q)
                 out = _native.band_attention_fp8(q.contiguous(), k.contiguous(), v.contiguous(), mask, sm_scale=LN2 if q_prescaled else None, **pk)
             else:
-                if _local:
+                if _local:   # (enable(): contiguous head slices are gathered; token-shard mode: token-major rows are what the outbound exchange sends)
                     kw["token_major_out"] = TOKEN_MAJOR_IO and _dist.token_shards_active()
-                out = _native.band_attention(q, k, v, mask, q_prescaled=q_prescaled, **kw, **pk)
+                if switched:
+                    out = _native.band_attention_switch(q, k, v, mask, dense_mask, dense_flag, q_prescaled=q_prescaled, **kw, **pk)
+                else:
+                    out = _native.band_attention(q, k, v, mask, q_prescaled=q_prescaled, **kw, **pk)
+        best_idx = final_best()
         if quality is not None:
             o_p, lse_p = out if (return_lse or probe_lse) else (out, None)
-            log_quality(quality, o_p, lse_p, q, k, v, q_prescaled)
+            log_quality(quality, o_p, lse_p, q, k, v, q_prescaled, **flag_kw)
             if probe_lse:
                 out = o_p
-        return (out[0], best_mask_idx, out[1]) if return_lse else (out, best_mask_idx)
+        return (out[0], best_idx, out[1]) if return_lse else (out, best_idx)
+    # the three kernels of the reference pipeline (the host branch only; no LSE form, no shard form)
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     qo, ko, vo = _native.empty_like(q), _native.empty_like(k), _native.empty_like(v)
     with time_logging_decorator("Level 3 - fast_sparse_head_placement"):
@@ -634,14 +599,14 @@ def svg1_sparse_attention(q, k, v, geo: Geometry, mask: "_native.BandMask", prof
                                geo.text_first, inverse=False)
     with time_logging_decorator("Level 3 - sparse_flex_attention"):
         if groups is not None:
-            hs = _native.band_attention_groups(qo, ko, vo, groups[0], groups[1], q_prescaled=q_prescaled)
+            hs = _native.band_attention_groups(qo, ko, vo, groups[0], groups[2], q_prescaled=q_prescaled)
         else:
             hs = _native.band_attention(qo, ko, vo, mask, q_prescaled=q_prescaled)
     out = _native.empty_like(hs)
     with time_logging_decorator("Level 3 - fast_hidden_states_placement"):
         _native.head_placement([hs], [out], best_mask_idx, geo.context_length, geo.num_frame, geo.frame_size, geo.text_first,
                                inverse=True)
-    if quality is not None:   # (the three-kernel pipeline has no LSE form: the error alone)
+    if quality is not None:   # (no LSE form: the error alone)
         log_quality(quality, out, None, q, k, v, q_prescaled)
     return out, best_mask_idx
 
@@ -895,11 +860,6 @@ def _refuse_adaptive_band(what: str, q: torch.Tensor, band_store, q_prescaled: b
                                       f"give every video the same text length")
 
 
-def _one_of(mask, cfg: int, what: str):
-    pm = per_video(mask, cfg, what)
-    return mask if pm is None else pm[0]
-
-
 def adaptive_band_step(adaptive: AdaptiveBand, band_store: BandStore, layer_idx, band: torch.Tensor, lse: torch.Tensor, q, k, plan,
                        bounds, lse_dense=None, skip_flag=None):
     """_kept_mass_step with svg_band_width_update: the bands `band` [cfg * H] of the call are stepped in place inside `bounds`.  skip_flag: the
@@ -1104,6 +1064,97 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
             DENSITY_LOG.push(logging_file, {"timestep": timestep_value(timestep) if timestep is not None else None,
                                             "layer": layer_idx}, densities)
     return out.reshape(cfg, H, S, D)   # (out is [cfg, H, S, D] already, in either storage order: a view)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# attention_core_logic of the processors, one body per method.  What a model family does differently is an argument of
+# its processor's one call:
+#   valid_lens(cfg, geo) HunyuanVideo: the dense `valid` of the call (video_valid_lens) — the quality probe, the dense masks of the
+#                        switch, the knob's probe and the dense call follow it — and with it masks per video (a block_mask tuple)
+#   dense(q, k, v, valid, geo)  HunyuanVideo: _core.dense_attention itself; without it the processor's flash_attention (Wan, Cosmos,
+#                        CogVideoX), whose decorator enters dense_attention's timer label a second time
+#   shard_form           the frame-shard form of rows_of_this_rank: the class's frame_shard_form; CogVideoX has none and passes False
+# ---------------------------------------------------------------------------------------------------------------
+def _core_logic_setup(proc, query, timestep, shard_form, valid_lens):
+    """What every attention_core_logic starts with -> (geometry, valid, quality request)"""
+    cfg, seq_len = query.shape[0], query.shape[2]
+    geo, name = proc.geometry(), type(proc).__name__
+    assert seq_len == rows_of_this_rank(name, geo, shard_form), (
+        f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
+    valid = valid_lens(cfg, geo) if valid_lens is not None else None
+    return geo, valid, quality_request(name, proc.quality_log, proc.quality_rows, valid, timestep, proc.layer_idx)
+
+
+def _knob(proc, option: str, valid_lens, valid):
+    """The processor's kept-mass knob (adaptive_band / adaptive_top_p) for this call, refused when sharded; HunyuanVideo: the probe's rows and
+    keys follow the call's valid lengths"""
+    knob = getattr(proc, option)
+    if knob is None:
+        return None
+    _refuse_kept_mass_knob_when_sharded(type(proc).__name__, option)
+    return knob if valid_lens is None else dataclasses.replace(knob, valid_len=valid)
+
+
+def svg1_core_logic(proc, query, key, value, timestep, profile_desc, owner: str, install_hook: str, *, valid_lens=None, dense=None,
+                    shard_form=None, thresholds=None, band_knob: bool = True, whole_sequence_rows: bool = False):
+    """attention_core_logic of the SVG1 processors: the warm-up test — on the host by layer, on the device by timestep where the
+    timestep is a GPU tensor (device_switch) — then the dense call, svg1_attention_device_switch or svg1_sparse_attention.
+    profile_desc: the model's (its utils); owner, install_hook: the class and function the "block_mask is not set" error names.
+    thresholds: (first_layers, first_times) where they are not the class's own (CogVideoX scales them); band_knob False: no adaptive_band
+    (CogVideoX); whole_sequence_rows: the profiler's rows come from the whole sequence, not from the first sample_mse_max_row (CogVideoX)."""
+    shape = query.size()
+    geo, valid, quality = _core_logic_setup(proc, query, timestep, proc.frame_shard_form if shard_form is None else shard_form, valid_lens)
+    cfg, total = shape[0], geo.seq_len   # (total: seq_len, except in the sharded modes: the masks and the sampled rows are the whole sequence's)
+    first_layers, first_times = thresholds if thresholds is not None else (proc.first_layers_fp, proc.first_times_fp)
+    ab = {}
+    if band_knob and proc.adaptive_band is not None:
+        ab = dict(adaptive=_knob(proc, "adaptive_band", valid_lens, valid), band_store=proc.band_store, layer_idx=proc.layer_idx)
+    # the layer test is host data; the timestep test stays on the device when the timestep is a GPU tensor (device_switch)
+    dense_flag = None
+    if proc.device_switch and attention_dtype() == "bf16" and proc.fused_placement and proc.layer_idx >= first_layers \
+            and proc.block_mask is not None and query.is_cuda:
+        dense_flag = dense_flag_on_device(timestep, first_times)
+    if dense_flag is None and is_full_attention(proc.layer_idx, timestep, first_layers, first_times):
+        out = proc.flash_attention(query, key, value) if dense is None else dense(query, key, value, valid, geo)
+        return out.reshape(shape)
+    mask = proc.block_mask   # (HunyuanVideo: or a tuple, one mask per video, as prompt_length)
+    if mask is None:
+        raise RuntimeError(f"{owner}.block_mask is not set: call {install_hook} first")
+    if valid_lens is not None and isinstance(mask, tuple) and len(mask) != cfg:
+        raise ValueError(f"{owner}: block_mask has {len(mask)} entries for a batch of {cfg} videos")
+    prof = profile_desc(geo.context_length, geo.num_frame, geo.frame_size)
+    max_row = total if whole_sequence_rows else min(proc.sample_mse_max_row, total)
+    if dense_flag is not None:
+        dense_masks = tuple(_dense_band_mask(total, x) for x in valid) if isinstance(valid, tuple) else _dense_band_mask(total, valid)
+        out, best = svg1_attention_device_switch(query, key, value, geo, mask, dense_masks, prof, proc.num_sampled_rows, max_row, dense_flag,
+                                                 q_prescaled=proc._q_prescaled, quality=quality, **ab)
+    else:
+        out, best = svg1_sparse_attention(query, key, value, geo, mask, prof, proc.num_sampled_rows, max_row, fused=proc.fused_placement,
+                                          q_prescaled=proc._q_prescaled, quality=quality, **ab)
+    proc.last_best_mask_idx = best
+    return out.reshape(shape)
+
+
+def svg2_core_logic(proc, query, key, value, timestep, layer_idx, prompt_length, *, valid_lens=None, dense=None):
+    """attention_core_logic of the SAP processors: the warm-up test on the host, then the dense call (zero_step_kmeans_init: the layer's
+    k-means runs on dense steps too) or svg2_sparse_attention.  layer_idx: the key of the layer's centroids and thresholds — the stores
+    are the processor's, class-level or per instance as the family keeps them; prompt_length: 0, the class's integer or a tuple with one entry
+    per video."""
+    shape = query.size()
+    geo, valid, quality = _core_logic_setup(proc, query, timestep, proc.frame_shard_form, valid_lens)
+    adaptive = _knob(proc, "adaptive_top_p", valid_lens, valid)
+    if is_full_attention(proc.layer_idx, timestep, proc.first_layers_fp, proc.first_times_fp):
+        if proc.zero_step_kmeans_init and query.is_cuda:
+            V = geo.video_length
+            kmeans_clustering(proc.centroid_store, layer_idx, query[:, :, :V], key[:, :, :V],   # (views: read in place)
+                              proc.num_q_centroids, proc.num_k_centroids, proc.kmeans_iter_init, proc.kmeans_iter_step)
+        out = proc.flash_attention(query, key, value) if dense is None else dense(query, key, value, valid, geo)
+        return out.reshape(shape)
+    out = svg2_sparse_attention(query, key, value, geo, proc.centroid_store, layer_idx, proc.num_q_centroids, proc.num_k_centroids,
+                                proc.top_p_kmeans, proc.min_kc_ratio, proc.kmeans_iter_init, proc.kmeans_iter_step,
+                                prompt_length=prompt_length if isinstance(prompt_length, tuple) else int(prompt_length),
+                                logging_file=proc.logging_file, timestep=timestep, quality=quality, adaptive=adaptive, top_p_store=proc.top_p_store)
+    return out.reshape(shape)
 
 
 class _DensityLog:

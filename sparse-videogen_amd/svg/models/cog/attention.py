@@ -9,7 +9,7 @@ import torch
 from .. import _core
 from .._core import Geometry
 from ..hyvideo.attention import apply_rotary_emb
-from .utils import dense_mask, generate_temporal_head_mask_mod, profile_desc
+from .utils import generate_temporal_head_mask_mod, profile_desc
 
 
 def qk_norm(attn, query, key):
@@ -104,34 +104,12 @@ class CogVideoX_SparseAttn_Processor2_0:
                                 self.num_sampled_rows, query.shape[2], q_prescaled=self._q_prescaled)
 
     def attention_core_logic(self, query, key, value, timestep):
-        cfg, num_heads, seq_len, dim = query.size()
-        geo = self.geometry()
-        # (frame-shard mode, svg.distributed.enable_frame_shards, is refused: the text in FRONT of the video belongs to no shard)
-        assert seq_len == _core.rows_of_this_rank(type(self).__name__, geo, shard_form=False), (
-            f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
-        # ref :173-176 — Cog's warm-up thresholds are fractions of 42 layers / 1000 timesteps
-        first_layers, first_times = 42 * self.first_layers_fp, 1000 * (1 - self.first_times_fp)
-        quality = _core.quality_request(type(self).__name__, self.quality_log, self.quality_rows, None, timestep, self.layer_idx)
-        dense_flag = None   # (device-side dense / sparse switch, see the Hunyuan processor)
-        if self.device_switch and _core.attention_dtype() == "bf16" and self.fused_placement and self.layer_idx >= first_layers and self.block_mask is not None \
-                and query.is_cuda:
-            dense_flag = _core.dense_flag_on_device(timestep, first_times)
-        if dense_flag is None and _core.is_full_attention(self.layer_idx, timestep, first_layers, first_times):
-            return self.flash_attention(query, key, value).reshape(cfg, num_heads, seq_len, dim)
-        if self.block_mask is None:
-            raise RuntimeError("CogVideoX_SparseAttn_Processor2_0.block_mask is not set: call replace_cog_attention first")
-        prof = profile_desc(geo.context_length, geo.num_frame, geo.frame_size)
-        total = geo.seq_len   # (seq_len, except in token-shard mode: the masks and the sampled rows are the whole sequence's)
-        if dense_flag is not None:
-            out, best = _core.svg1_attention_device_switch(query, key, value, geo, self.block_mask, dense_mask(total), prof,
-                                                           self.num_sampled_rows, total, dense_flag, q_prescaled=self._q_prescaled,
-                                                           quality=quality)
-            self.last_best_mask_idx = best
-            return out.reshape(cfg, num_heads, seq_len, dim)
-        out, best = _core.svg1_sparse_attention(query, key, value, geo, self.block_mask, prof, self.num_sampled_rows, total,
-                                                fused=self.fused_placement, q_prescaled=self._q_prescaled, quality=quality)
-        self.last_best_mask_idx = best
-        return out.reshape(cfg, num_heads, seq_len, dim)
+        # ref :173-176 — Cog's warm-up thresholds are fractions of 42 layers / 1000 timesteps; ref :126 — the profiler's rows come from the
+        # WHOLE sequence.  No frame-shard form (svg.distributed.enable_frame_shards is refused: the text in FRONT of the video belongs to
+        # no shard) and no adaptive band.
+        return _core.svg1_core_logic(self, query, key, value, timestep, profile_desc, "CogVideoX_SparseAttn_Processor2_0", "replace_cog_attention",
+                                     thresholds=(42 * self.first_layers_fp, 1000 * (1 - self.first_times_fp)), shard_form=False,
+                                     band_knob=False, whole_sequence_rows=True)
 
     def __call__(self, attn, hidden_states: torch.Tensor, encoder_hidden_states: torch.Tensor,
                  attention_mask: Optional[torch.Tensor] = None, image_rotary_emb=None, timestep=None):

@@ -7,7 +7,6 @@ are the model's own torch modules, as in the reference's torch fall-back path (h
 """
 from __future__ import annotations
 
-import dataclasses
 import weakref
 from typing import Optional, Tuple
 
@@ -17,7 +16,7 @@ import torch.nn.functional as F
 from ...timer import time_logging_decorator
 from .. import _core
 from .._core import BandStore, CentroidStore, Geometry, TopPStore
-from .utils import dense_mask, generate_temporal_head_mask_mod, profile_desc
+from .utils import generate_temporal_head_mask_mod, profile_desc
 
 
 # ---- pre-attention helpers (torch; ref: hyvideo/attention.py:195-225) -------------------------------------------
@@ -318,44 +317,10 @@ class Hunyuan_SVGAttn_Processor2_0(_HunyuanProcessorBase):
 
     @time_logging_decorator("Level 2 - attention core logic")
     def attention_core_logic(self, query, key, value, timestep, layer_idx, cu_max_seqlens):
-        cfg, num_heads, seq_len, dim = query.size()
-        geo = self.geometry()
-        assert seq_len == _core.rows_of_this_rank(type(self).__name__, geo, self.frame_shard_form), (
-            f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
-        total = geo.seq_len   # (seq_len, except in frame-shard mode: the masks and the sampled rows are the whole sequence's)
-        valid = self.video_valid_lens(cu_max_seqlens, cfg, geo.video_length)
-        quality = _core.quality_request(type(self).__name__, self.quality_log, self.quality_rows, valid, timestep, self.layer_idx)
-        ab = {}
-        if self.adaptive_band is not None:
-            _core._refuse_kept_mass_knob_when_sharded(type(self).__name__, "adaptive_band")
-            # (the probe's rows and keys follow the call's valid lengths)
-            ab = dict(adaptive=dataclasses.replace(self.adaptive_band, valid_len=valid), band_store=self.band_store, layer_idx=self.layer_idx)
-        # the layer test is host data; the timestep test stays on the device when the timestep is a GPU tensor (device_switch)
-        dense_flag = None
-        if self.device_switch and _core.attention_dtype() == "bf16" and self.fused_placement and self.layer_idx >= self.first_layers_fp and self.block_mask is not None \
-                and query.is_cuda:
-            dense_flag = _core.dense_flag_on_device(timestep, self.first_times_fp)
-        pre = self._q_prescaled
-        if dense_flag is None and _core.is_full_attention(self.layer_idx, timestep, self.first_layers_fp, self.first_times_fp):
-            return _core.dense_attention(query, key, value, valid, q_prescaled=pre, geometry=geo).reshape(cfg, num_heads, seq_len, dim)
-        mask = self.block_mask   # (a tuple: one mask per video, as prompt_length)
-        if mask is None:
-            raise RuntimeError("Hunyuan_SVGAttn_Processor2_0.block_mask is not set: call replace_hyvideo_attention first")
-        if isinstance(mask, tuple) and len(mask) != cfg:
-            raise ValueError(f"Hunyuan_SVGAttn_Processor2_0: block_mask has {len(mask)} entries for a batch of {cfg} videos")
-        prof = profile_desc(geo.context_length, geo.num_frame, geo.frame_size)
-        if dense_flag is not None:
-            dense = tuple(dense_mask(total, int(x)) for x in valid) if isinstance(valid, tuple) else dense_mask(total, int(valid))
-            out, best = _core.svg1_attention_device_switch(query, key, value, geo, mask, dense, prof,
-                                                           self.num_sampled_rows, min(self.sample_mse_max_row, total), dense_flag,
-                                                           q_prescaled=pre, quality=quality, **ab)
-            self.last_best_mask_idx = best
-            return out.reshape(cfg, num_heads, seq_len, dim)
-        out, best = _core.svg1_sparse_attention(query, key, value, geo, mask, prof, self.num_sampled_rows,
-                                                min(self.sample_mse_max_row, total), fused=self.fused_placement, q_prescaled=pre,
-                                                quality=quality, **ab)
-        self.last_best_mask_idx = best
-        return out.reshape(cfg, num_heads, seq_len, dim)
+        return _core.svg1_core_logic(
+            self, query, key, value, timestep, profile_desc, "Hunyuan_SVGAttn_Processor2_0", "replace_hyvideo_attention",
+            valid_lens=lambda cfg, geo: self.video_valid_lens(cu_max_seqlens, cfg, geo.video_length),
+            dense=lambda q, k, v, valid, geo: _core.dense_attention(q, k, v, valid, q_prescaled=self._q_prescaled, geometry=geo))
 
 
 def prepare_flexattention(cfg_size, num_head, head_dim, dtype, device, context_length, prompt_length, num_frame, frame_size,
@@ -401,29 +366,10 @@ class Hunyuan_SAPAttn_Processor2_0(Hunyuan_SVGAttn_Processor2_0):
 
     @time_logging_decorator("Level 2 - attention core logic")
     def attention_core_logic(self, query, key, value, timestep, layer_idx, cu_max_seqlens):
-        cfg, num_heads, seq_len, dim = query.size()
-        geo = self.geometry()
-        assert seq_len == _core.rows_of_this_rank(type(self).__name__, geo, self.frame_shard_form), (
-            f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
-        valid = self.video_valid_lens(cu_max_seqlens, cfg, geo.video_length)
-        quality = _core.quality_request(type(self).__name__, self.quality_log, self.quality_rows, valid, timestep, self.layer_idx)
-        adaptive = self.adaptive_top_p
-        if adaptive is not None:
-            _core._refuse_kept_mass_knob_when_sharded(type(self).__name__, "adaptive_top_p")
-            adaptive = dataclasses.replace(adaptive, valid_len=valid)   # (the probe's rows and keys follow the call's valid lengths)
-        if _core.is_full_attention(self.layer_idx, timestep, self.first_layers_fp, self.first_times_fp):
-            if self.zero_step_kmeans_init and query.is_cuda:
-                V = geo.video_length
-                _core.kmeans_clustering(self.centroid_store, layer_idx, query[:, :, :V], key[:, :, :V],   # (views: read in place)
-                                        self.num_q_centroids, self.num_k_centroids,
-                                        self.kmeans_iter_init, self.kmeans_iter_step)
-            return _core.dense_attention(query, key, value, valid, geometry=geo).reshape(cfg, num_heads, seq_len, dim)
-        out = _core.svg2_sparse_attention(query, key, value, geo, self.centroid_store, layer_idx, self.num_q_centroids,
-                                          self.num_k_centroids, self.top_p_kmeans, self.min_kc_ratio, self.kmeans_iter_init,
-                                          self.kmeans_iter_step, prompt_length=self.prompt_length if isinstance(self.prompt_length, tuple) else int(self.prompt_length),
-                                          logging_file=self.logging_file, timestep=timestep, quality=quality, adaptive=adaptive,
-                                          top_p_store=self.top_p_store)
-        return out.reshape(cfg, num_heads, seq_len, dim)
+        return _core.svg2_core_logic(
+            self, query, key, value, timestep, layer_idx, self.prompt_length,
+            valid_lens=lambda cfg, geo: self.video_valid_lens(cu_max_seqlens, cfg, geo.video_length),
+            dense=lambda q, k, v, valid, geo: _core.dense_attention(q, k, v, valid, geometry=geo))   # (k-means works on the plain q)
 
 
 def replace_hyvideo_flashattention(pipe):

@@ -11,7 +11,7 @@ from ...kernels.triton.rmsnorm import triton_rmsnorm_forward
 from ...timer import time_logging_decorator
 from .. import _core
 from .._core import BandStore, CentroidStore, Geometry, TopPStore
-from .utils import dense_mask, generate_temporal_head_mask_mod, profile_desc
+from .utils import generate_temporal_head_mask_mod, profile_desc
 
 
 def apply_rotary_emb(query: torch.Tensor, key: torch.Tensor, freqs, q_scale: float = 1.0, scaled: Optional[list] = None):
@@ -264,36 +264,7 @@ class WanAttn_SVGAttn_Processor2_0:
 
     @time_logging_decorator("Level 2 - attention core logic")
     def attention_core_logic(self, query, key, value, timestep):
-        cfg, num_heads, seq_len, dim = query.size()
-        geo = self.geometry()
-        assert seq_len == _core.rows_of_this_rank(type(self).__name__, geo, self.frame_shard_form), (
-            f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
-        total = geo.seq_len   # (seq_len, except in frame-shard mode: the masks and the sampled rows are the whole sequence's)
-        quality = _core.quality_request(type(self).__name__, self.quality_log, self.quality_rows, None, timestep, self.layer_idx)
-        ab = {}
-        if self.adaptive_band is not None:
-            _core._refuse_kept_mass_knob_when_sharded(type(self).__name__, "adaptive_band")
-            ab = dict(adaptive=self.adaptive_band, band_store=self.band_store, layer_idx=self.layer_idx)
-        dense_flag = None   # (device-side dense / sparse switch, see the Hunyuan processor)
-        if self.device_switch and _core.attention_dtype() == "bf16" and self.fused_placement and self.layer_idx >= self.first_layers_fp and self.block_mask is not None \
-                and query.is_cuda:
-            dense_flag = _core.dense_flag_on_device(timestep, self.first_times_fp)
-        if dense_flag is None and _core.is_full_attention(self.layer_idx, timestep, self.first_layers_fp, self.first_times_fp):
-            return self.flash_attention(query, key, value).reshape(cfg, num_heads, seq_len, dim)
-        if self.block_mask is None:
-            raise RuntimeError("WanAttn_SVGAttn_Processor2_0.block_mask is not set: call replace_wan_attention first")
-        prof = profile_desc(geo.context_length, geo.num_frame, geo.frame_size)
-        if dense_flag is not None:
-            out, best = _core.svg1_attention_device_switch(query, key, value, geo, self.block_mask, dense_mask(total), prof,
-                                                           self.num_sampled_rows, min(self.sample_mse_max_row, total), dense_flag,
-                                                           q_prescaled=self._q_prescaled, quality=quality, **ab)
-            self.last_best_mask_idx = best
-            return out.reshape(cfg, num_heads, seq_len, dim)
-        out, best = _core.svg1_sparse_attention(query, key, value, geo, self.block_mask, prof, self.num_sampled_rows,
-                                                min(self.sample_mse_max_row, total), fused=self.fused_placement,
-                                                q_prescaled=self._q_prescaled, quality=quality, **ab)
-        self.last_best_mask_idx = best
-        return out.reshape(cfg, num_heads, seq_len, dim)
+        return _core.svg1_core_logic(self, query, key, value, timestep, profile_desc, "WanAttn_SVGAttn_Processor2_0", "replace_wan_attention")
 
 
 def prepare_flexattention(cfg_size, num_head, head_dim, dtype, device, context_length, prompt_length, num_frame, frame_size,
@@ -348,21 +319,4 @@ class WanAttn_SAPAttn_Processor(WanAttn_SVGAttn_Processor2_0):
 
     @time_logging_decorator("Level 2 - attention core logic")
     def attention_core_logic(self, query, key, value, timestep):
-        cfg, num_heads, seq_len, dim = query.size()
-        geo = self.geometry()
-        assert seq_len == _core.rows_of_this_rank(type(self).__name__, geo, self.frame_shard_form), (
-            f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
-        quality = _core.quality_request(type(self).__name__, self.quality_log, self.quality_rows, None, timestep, self.layer_idx)
-        if self.adaptive_top_p is not None:
-            _core._refuse_kept_mass_knob_when_sharded(type(self).__name__, "adaptive_top_p")
-        if _core.is_full_attention(self.layer_idx, timestep, self.first_layers_fp, self.first_times_fp):
-            if self.zero_step_kmeans_init and query.is_cuda:
-                V = geo.video_length
-                _core.kmeans_clustering(self.centroid_store, self.layer_idx, query[:, :, :V], key[:, :, :V],   # (views: read in place)
-                                        self.num_q_centroids, self.num_k_centroids, self.kmeans_iter_init, self.kmeans_iter_step)
-            return self.flash_attention(query, key, value).reshape(cfg, num_heads, seq_len, dim)
-        out = _core.svg2_sparse_attention(query, key, value, geo, self.centroid_store, self.layer_idx, self.num_q_centroids,
-                                          self.num_k_centroids, self.top_p_kmeans, self.min_kc_ratio, self.kmeans_iter_init,
-                                          self.kmeans_iter_step, prompt_length=0, logging_file=self.logging_file,
-                                          timestep=timestep, quality=quality, adaptive=self.adaptive_top_p, top_p_store=self.top_p_store)
-        return out.reshape(cfg, num_heads, seq_len, dim)
+        return _core.svg2_core_logic(self, query, key, value, timestep, self.layer_idx, 0)   # (prompt_length 0: Wan has no text rows)
