@@ -11,8 +11,9 @@ single-GPU result, which is bitwise because per-head arithmetic does not change.
 Dense attention can also stay TOKEN-sharded (`token_sharded_dense_attention`): every rank keeps all heads of its tokens, sees the
 other ranks' keys shard by shard and merges the partial results with their row log-sum-exp — any head count, every rank busy, the
 exchange of the next shard behind the compute of this one; equal to the single-GPU result to rounding, not bitwise.
-`token_sharded_band_attention` is the same schedule for band (SVG1) attention in logical order: each step is one window of the mask at
-the global coordinates of the two shards, and pairs of shards the mask rules out exchange and compute nothing.
+`token_sharded_band_attention` is the same schedule (_attend_over_key_shards, stated there once) for band (SVG1) attention in logical
+order: each step is one window of the mask at the global coordinates of the two shards, and pairs of shards the mask rules out exchange
+and compute nothing.
 `token_sharded_svg1_attention` is that schedule for a real SVG1 layer-call: the sequence sharded by whole frames in the model's own row
 order, heads in logical order and token-major heads in one launch per step (svg_band_shard_attention_lse[_f32]).
 `token_sharded_sample_mse` is the online profiler of such a sequence — no K / V travels: the sampled q rows are exchanged, each rank streams
@@ -29,6 +30,7 @@ each (_native.copy_box_jobs).
 """
 from __future__ import annotations
 
+import math
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -185,12 +187,7 @@ def run_sharded(fn: Callable[..., Tuple[torch.Tensor, ...]], head_tensors: Seque
     sl = slice(mine[0], mine[-1] + 1)
     res = fn(*[t[:, sl].contiguous() for t in head_tensors])
     single = not isinstance(res, (tuple, list))
-    outs = []
-    for r in ([res] if single else res):
-        extra = r.shape[2:]
-        r4 = r.reshape(r.shape[0], r.shape[1], -1, 1) if r.dim() != 4 else r
-        g = all_gather_heads(r4, H, group)
-        outs.append(g.reshape(g.shape[0], H, *extra))
+    outs = [_gather_per_head(r, H, group) for r in ([res] if single else res)]
     return outs[0] if single else tuple(outs)
 
 
@@ -222,6 +219,14 @@ def all_gather_heads(o_local: torch.Tensor, num_heads: int, group=None) -> torch
     dist.all_gather_into_tensor(out, pad, group=group)
     out = out.view(world, cfg, mx, S, D)
     return torch.cat([out[r, :, : counts[r]] for r in range(world)], dim=1)
+
+
+def _gather_per_head(r: torch.Tensor, num_heads: int, group=None) -> torch.Tensor:
+    """[cfg, H_local, ...] on every rank (o, or a per-head extra such as best_mask_idx [cfg, H_local]) -> [cfg, H, ...] on every rank"""
+    extra = r.shape[2:]
+    r4 = r.reshape(r.shape[0], r.shape[1], -1, 1) if r.dim() != 4 else r
+    g = all_gather_heads(r4, num_heads, group)
+    return g.reshape(g.shape[0], num_heads, *extra)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -338,12 +343,7 @@ def run_token_sharded(fn: Callable[..., Tuple[torch.Tensor, ...]], head_tensors:
         store = _native.empty((cfg, S_r, H, D), dtype=o.dtype, device=dev)
         stats["launches"] += _native.copy_box_jobs([(recv, store, _native.outbound_unpack_boxes(cfg, counts, S_r, D))], D,
                                                    how("outbound_unpack"))
-    outs = [store.permute(0, 2, 1, 3)]
-    for r in res[1:]:   # per-head extras: gathered to all heads, as run_sharded does
-        extra = r.shape[2:]
-        r4 = r.reshape(r.shape[0], r.shape[1], -1, 1) if r.dim() != 4 else r
-        g = all_gather_heads(r4, H, group)
-        outs.append(g.reshape(g.shape[0], H, *extra))
+    outs = [store.permute(0, 2, 1, 3)] + [_gather_per_head(r, H, group) for r in res[1:]]   # per-head extras: as run_sharded gathers them
     EXCHANGE_STATS.clear()
     EXCHANGE_STATS.update(stats)
     return outs[0] if single else tuple(outs)
@@ -394,9 +394,7 @@ def tokens_to_heads(x_local: torch.Tensor, num_tokens: int, group=None, unit: in
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     H = x_local.shape[0]
     rest = tuple(x_local.shape[2:])
-    E = 1
-    for r_ in rest:
-        E *= r_
+    E = math.prod(rest)
     owners = _owner_lists(H, world, head_lists)
     tr = [token_range(num_tokens, r, world, unit) for r in range(world)]
     S_me = tr[rank][1] - tr[rank][0]
@@ -432,9 +430,7 @@ def heads_to_tokens(o_local: torch.Tensor, num_heads: int, group=None, unit: int
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     S = o_local.shape[1]
     rest = tuple(o_local.shape[2:])
-    E = 1
-    for r_ in rest:
-        E *= r_
+    E = math.prod(rest)
     owners = _owner_lists(num_heads, world, head_lists)
     tr = [token_range(S, r, world, unit) for r in range(world)]
     Hl = len(owners[rank])
@@ -472,7 +468,7 @@ def heads_to_tokens(o_local: torch.Tensor, num_heads: int, group=None, unit: int
 # ref: the context-parallel dense attention of svg/models/wan_orig/distributed/xdit_context_parallel.py:120-169 (xfuser ring / Ulysses),
 #      flashinfer's run(..., return_lse=True) + merge_state in svg/kernels/ops/attention_ops.py:178-188
 # ---------------------------------------------------------------------------------------------------------------
-MERGE_MAX_PARTS = 8   # svg_merge_attention_states (include/svg_attn.h): parts of one N-way merge
+MERGE_MAX_PARTS = _native.MERGE_MAX_PARTS   # svg_merge_attention_states (include/svg_attn.h): parts of one N-way merge
 
 
 def _native_attn(q, k, v, return_lse=False):
@@ -490,6 +486,74 @@ def _native_attn_f32(q, k, v, return_lse=False):
     return _native.cross_attention(q, k, v, return_lse=True, out_dtype=torch.float32)
 
 
+def _attend_over_key_shards(q_local: torch.Tensor, k_local: torch.Tensor, v_local: torch.Tensor, n_rows: Sequence[int],
+                            plan: Sequence[Sequence[bool]], step: Callable, merge_fn: Callable, group, who: str,
+                            post_before_own_part: bool) -> torch.Tensor:
+    """The key-shard exchange schedule of token_sharded_dense_attention(overlap=True), token_sharded_band_attention and
+    token_sharded_svg1_attention: this rank's rows q_local attend over the K / V shard of every rank whose keys they need, one part per
+    shard, and the parts are merged with their row log-sum-exp.
+    n_rows[r]: the rows rank r holds (k_local, v_local [..., H, n_rows[rank], D]).  plan[r][s]: do rank r's rows need rank s's shard —
+    the same table on every rank.  step(src_rank, k_s, v_s) -> (o, lse): this rank's rows over the shard of src_rank.
+    k and v of a shard travel as ONE message.  At step j every rank sends its OWN shard directly to rank + j and receives the shard of
+    rank - j from its owner (all_to_all_single with one non-empty split each way: a shift by j; no forwarding around a ring, every link
+    carries a shard once).  A pair the plan rules out sends nothing and receives nothing — every rank still enters the collective of the
+    step, with zero-size splits — and a step in which no rank receives keys is skipped by all ranks.  While a step's part is computed the
+    exchange of the next step is in flight.  A part is computed only where the plan keeps the pair and both shards have rows.
+    post_before_own_part: the first exchange is posted before the part over the rank's own shard is computed (dense) or after it (band,
+    SVG1); the own part is the first one computed either way.
+    At the end ONE merge_fn(o_parts, lse_parts) over the parts ordered by SOURCE rank, so the arithmetic of a row does not depend on the
+    rank that computed it.  More than MERGE_MAX_PARTS parts on some rank: ValueError on every rank, in the name of `who`, before the first
+    collective and before any step.  A rank without rows returns an empty tensor, rows that see no key at all zeros."""
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    most = max(sum(row) for row in plan)
+    if most > MERGE_MAX_PARTS:
+        raise ValueError(f"{who}: a rank sees the keys of {most} shards, but merge_attention_states takes at most "
+                         f"{MERGE_MAX_PARTS} parts — use a group of at most {MERGE_MAX_PARTS} ranks")
+    lead, D = tuple(k_local.shape[:-2]), k_local.shape[-1]
+    per_tok = 2 * D * math.prod(lead)
+    # the steps in which some rank receives keys, the same list on every rank
+    steps = [j for j in range(1, world) if any(plan[r][(r - j) % world] for r in range(world))]
+    send = torch.stack([k_local, v_local]).contiguous().view(-1) if steps else None
+
+    def shift(j):
+        """this rank's shard to rank + j if that rank needs it, the shard of rank - j if this rank needs it: (source rank, buffer, work)"""
+        dst, src = (rank + j) % world, (rank - j) % world
+        recv = _native.empty(n_rows[src] * per_tok if plan[rank][src] else 0, dtype=send.dtype, device=send.device)
+        ins, outs = [0] * world, [0] * world
+        ins[dst] = send.numel() if plan[dst][rank] else 0
+        outs[src] = recv.numel()
+        work = dist.all_to_all_single(recv, send[:ins[dst]], output_split_sizes=outs, input_split_sizes=ins, group=group, async_op=True)
+        return src, recv, work
+
+    def has_part(src):
+        return plan[rank][src] and n_rows[rank] > 0 and n_rows[src] > 0   # (an empty shard has no keys: no part)
+
+    parts = {}
+    nxt = shift(steps[0]) if steps and post_before_own_part else None
+    if has_part(rank):
+        parts[rank] = step(rank, k_local, v_local)
+    if steps and not post_before_own_part:
+        nxt = shift(steps[0])
+    for i in range(len(steps)):
+        src, recv, work = nxt
+        work.wait()
+        nxt = shift(steps[i + 1]) if i + 1 < len(steps) else None     # in flight while this step computes
+        if has_part(src):
+            k_s, v_s = recv.view((2,) + lead + (n_rows[src], D)).unbind(0)
+            parts[src] = step(src, k_s, v_s)
+    if n_rows[rank] == 0:
+        return _native.empty_like(q_local)
+    if not parts:   # (a plan that gives these rows no key at all)
+        return torch.zeros_like(q_local)
+    order = sorted(parts)
+    return merge_fn([parts[r][0] for r in order], [parts[r][1] for r in order])
+
+
+def _check_device_switch_pair(who: str, dense_mask, dense_flag) -> None:
+    if (dense_mask is None) != (dense_flag is None):
+        raise ValueError(f"{who}: dense_mask and dense_flag go together (the device switch), or neither")
+
+
 def token_sharded_dense_attention(q_local: torch.Tensor, k_local: torch.Tensor, v_local: torch.Tensor, num_tokens: int, group=None,
                                   unit: int = 1, overlap: bool = True, attn_fn: Optional[Callable] = None,
                                   merge_fn: Optional[Callable] = None, fp32_parts: bool = False) -> torch.Tensor:
@@ -498,11 +562,9 @@ def token_sharded_dense_attention(q_local: torch.Tensor, k_local: torch.Tensor, 
     ALL num_tokens keys, [..., H, S_r, D].  Nothing is sharded by heads, so it works for any head count (12 heads on 8 GPUs) and leaves
     no rank idle.
     overlap=False (the baseline): k and v are all-gathered, then ONE attn_fn(q, k, v) launch.
-    overlap=True: world steps; at step j the rank computes (o_j, lse_j) = attn_fn(q, k_s, v_s, True) of its rows over the shard of rank
-    s = (rank - j) mod world while the shard of step j + 1 is already in flight — every rank sends its OWN shard directly to the rank
-    that needs it next (all_to_all_single with one non-empty split: a shift by j; no forwarding around a ring, every link carries a
-    shard once).  At the end ONE merge_fn(o_parts, lse_parts) over the parts ordered by SOURCE rank, so the arithmetic of a row does not
-    depend on the rank that computed it.  world > MERGE_MAX_PARTS: ValueError (the N-way merge takes at most 8 parts).
+    overlap=True: the schedule of _attend_over_key_shards under a plan that is true for every pair — world steps; at step j the rank
+    computes (o_j, lse_j) = attn_fn(q, k_s, v_s, True) of its rows over the shard of rank s = (rank - j) mod world, and the first exchange
+    is posted before the own part.  world > MERGE_MAX_PARTS: ValueError (the N-way merge takes at most 8 parts).
     attn_fn(q, k, v, return_lse=False) -> o or (o, lse) and merge_fn(o_parts, lse_parts) -> o default to the native calls
     (_native.cross_attention, _native.merge_attention_states); they exist so that the schedule can be tested without a GPU.
     fp32_parts (the native default functions with overlap=True; nothing else changes): the steps return their rows BEFORE the rounding
@@ -532,55 +594,23 @@ def token_sharded_dense_attention(q_local: torch.Tensor, k_local: torch.Tensor, 
                          f"{MERGE_MAX_PARTS} parts — use a group of at most {MERGE_MAX_PARTS} ranks or overlap=False")
     if world == 1:
         return attn_fn(q_local, k_local, v_local)
-    lead = tuple(k_local.shape[:-2])
-    D = k_local.shape[-1]
-    per_tok = 2 * D
-    for x in lead:
-        per_tok *= x
-    kv_shape = lambda n: (2,) + lead + (n, D)   # noqa: E731  (k and v of a shard travel as one message)
-
     if not overlap:
-        mx = max(n_tok)
-        pad = torch.zeros(kv_shape(mx), dtype=k_local.dtype, device=k_local.device)
+        kv = (2,) + tuple(k_local.shape[:-2]) + (max(n_tok), k_local.shape[-1])   # k and v of a shard, padded to the largest, as one message
+        pad = torch.zeros(kv, dtype=k_local.dtype, device=k_local.device)
         pad[0][..., :S_me, :] = k_local
         pad[1][..., :S_me, :] = v_local
-        full = _native.empty((world * 2,) + kv_shape(mx)[1:], dtype=k_local.dtype, device=k_local.device)   # concatenated along dim 0
+        full = _native.empty((world * 2,) + kv[1:], dtype=k_local.dtype, device=k_local.device)   # concatenated along dim 0
         dist.all_gather_into_tensor(full, pad, group=group, async_op=True).wait()
-        full = full.view((world,) + kv_shape(mx))
+        full = full.view((world,) + kv)
         if S_me == 0:
             return _native.empty_like(q_local)
         k_all = torch.cat([full[r, 0][..., :n_tok[r], :] for r in range(world)], dim=-2)
         v_all = torch.cat([full[r, 1][..., :n_tok[r], :] for r in range(world)], dim=-2)
         return attn_fn(q_local, k_all, v_all)
-
-    send = torch.stack([k_local, v_local]).contiguous().view(-1)
-    empty = send[:0]
-
-    def shift(j):
-        """this rank's shard to rank + j, the shard of rank - j from its owner: (source rank, receive buffer, work handle)"""
-        dst, src = (rank + j) % world, (rank - j) % world
-        recv = _native.empty(n_tok[src] * per_tok, dtype=send.dtype, device=send.device)
-        ins, outs = [0] * world, [0] * world
-        ins[dst], outs[src] = send.numel(), recv.numel()
-        work = dist.all_to_all_single(recv, send, output_split_sizes=outs, input_split_sizes=ins, group=group, async_op=True)
-        return src, recv, work
-
-    parts = {}
-    nxt = shift(1)
-    for j in range(world):
-        if j == 0:
-            src, k_s, v_s = rank, k_local, v_local
-        else:
-            src, recv, work = nxt
-            work.wait()
-            nxt = shift(j + 1) if j + 1 < world else None     # in flight while step j computes
-            k_s, v_s = recv.view(kv_shape(n_tok[src])).unbind(0)
-        if S_me > 0 and n_tok[src] > 0:                        # (an empty shard has no keys: no part)
-            parts[src] = attn_fn(q_local, k_s, v_s, True)
-    if S_me == 0:
-        return _native.empty_like(q_local)
-    order = sorted(parts)
-    return merge_fn([parts[r][0] for r in order], [parts[r][1] for r in order])
+    # every pair exchanges, a pair with an empty shard included: a rank without rows still receives the shards it does not use
+    return _attend_over_key_shards(q_local, k_local, v_local, n_tok, [[True] * world] * world,
+                                   lambda src, k_s, v_s: attn_fn(q_local, k_s, v_s, True), merge_fn, group,
+                                   "token_sharded_dense_attention(overlap=True)", post_before_own_part=True)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -601,11 +631,9 @@ def token_sharded_band_attention(q_local: torch.Tensor, k_local: torch.Tensor, v
     """Band (SVG1) attention over a sequence that lives token-sharded, in the LOGICAL order of the mask: q_local, k_local, v_local
     [..., H, S_r, D] are ALL heads of this rank's tokens `token_range(num_tokens, rank, world, unit)` (ragged shards allowed); returns this
     rank's rows of band attention under `mask` (_native.BandMask over num_tokens rows), [..., H, S_r, D].  Any head count, no rank idle.
-    The overlap schedule of token_sharded_dense_attention: at step j the rank attends over the shard of rank s = (rank - j) mod world —
-    attn_fn(q, k_s, v_s, (q0, q1), (k0, k1)) -> (o, lse) with the two token ranges — while the shard of the next step is in flight; at
-    the end ONE merge_fn(o_parts, lse_parts) over the parts in SOURCE-rank order.  What the mask rules out does not happen: a pair
-    (rank, s) whose window holds no allowed element (band_exchange_plan) sends nothing and computes nothing — every rank still enters
-    the collective of a step, with zero-size splits — and a step in which no pair has keys is skipped by all ranks.
+    The schedule of _attend_over_key_shards under band_exchange_plan: a step is attn_fn(q, k_s, v_s, (q0, q1), (k0, k1)) -> (o, lse)
+    with the token ranges of this rank and of the shard's owner, and the own part is computed before the first exchange is posted.  What
+    the mask rules out does not happen: a pair (rank, s) whose window holds no allowed element exchanges and computes nothing.
     attn_fn and merge_fn default to the native calls (_native.band_window_attention, _native.merge_attention_states; fp32_parts: the
     parts travel to the merge before their rounding, so the result is rounded once); they exist so that the schedule can be tested
     on gloo without a GPU.  unit must be a multiple of 64 (ValueError): the key windows start on the mask's key tiles.  More ranks than
@@ -621,11 +649,6 @@ def token_sharded_band_attention(q_local: torch.Tensor, k_local: torch.Tensor, v
     S_me = n_tok[rank]
     assert q_local.shape[-2] == S_me and k_local.shape == v_local.shape and k_local.shape[-2] == S_me, (
         f"rank {rank} holds {q_local.shape[-2]} / {k_local.shape[-2]} tokens, token_range says {S_me}")
-    plan = band_exchange_plan(mask, num_tokens, world, unit)
-    most = max(sum(row) for row in plan)
-    if most > MERGE_MAX_PARTS:
-        raise ValueError(f"token_sharded_band_attention: a rank sees the keys of {most} shards, but merge_attention_states takes at most "
-                         f"{MERGE_MAX_PARTS} parts — use a group of at most {MERGE_MAX_PARTS} ranks")
     if attn_fn is None:
         def attn_fn(q, k, v, q_range, k_range):
             return _native.band_window_attention(q, k, v, mask, num_tokens, q_range[0], k_range[0],
@@ -633,43 +656,9 @@ def token_sharded_band_attention(q_local: torch.Tensor, k_local: torch.Tensor, v
     if merge_fn is None:
         def merge_fn(o_parts, lse_parts):
             return _native.merge_attention_states(o_parts, lse_parts, out_dtype=q_local.dtype if fp32_parts else None)
-    lead = tuple(k_local.shape[:-2])
-    D = k_local.shape[-1]
-    per_tok = 2 * D
-    for x in lead:
-        per_tok *= x
-    kv_shape = lambda n: (2,) + lead + (n, D)   # noqa: E731  (k and v of a shard travel as one message)
-    # the steps in which some rank receives keys, the same list on every rank
-    steps = [j for j in range(1, world) if any(plan[r][(r - j) % world] for r in range(world))]
-    send = torch.stack([k_local, v_local]).contiguous().view(-1) if steps else None
-
-    def shift(j):
-        """this rank's shard to rank + j if that rank sees it, the shard of rank - j if this rank sees it: (source rank, buffer, work)"""
-        dst, src = (rank + j) % world, (rank - j) % world
-        recv = _native.empty(n_tok[src] * per_tok if plan[rank][src] else 0, dtype=send.dtype, device=send.device)
-        ins, outs = [0] * world, [0] * world
-        ins[dst] = send.numel() if plan[dst][rank] else 0
-        outs[src] = recv.numel()
-        work = dist.all_to_all_single(recv, send[:ins[dst]], output_split_sizes=outs, input_split_sizes=ins, group=group, async_op=True)
-        return src, recv, work
-
-    parts = {}
-    if plan[rank][rank]:
-        parts[rank] = attn_fn(q_local, k_local, v_local, tr[rank], tr[rank])
-    nxt = shift(steps[0]) if steps else None
-    for i in range(len(steps)):
-        src, recv, work = nxt
-        work.wait()
-        nxt = shift(steps[i + 1]) if i + 1 < len(steps) else None     # in flight while this step computes
-        if plan[rank][src]:
-            k_s, v_s = recv.view(kv_shape(n_tok[src])).unbind(0)
-            parts[src] = attn_fn(q_local, k_s, v_s, tr[rank], tr[src])
-    if S_me == 0:
-        return _native.empty_like(q_local)
-    if not parts:   # (a mask that gives these rows no key at all)
-        return torch.zeros_like(q_local)
-    order = sorted(parts)
-    return merge_fn([parts[r][0] for r in order], [parts[r][1] for r in order])
+    return _attend_over_key_shards(q_local, k_local, v_local, n_tok, band_exchange_plan(mask, num_tokens, world, unit),
+                                   lambda src, k_s, v_s: attn_fn(q_local, k_s, v_s, tr[rank], tr[src]), merge_fn, group,
+                                   "token_sharded_band_attention", post_before_own_part=False)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -697,6 +686,12 @@ def frame_shard(geometry, rank: int, world: int):
     return _native.BandShard(f0, f1 - f0, tail0, n_tail)
 
 
+def _frame_shards(geometry, world: int):
+    """(frame_shard of every rank, the rows each of them holds)"""
+    shards = [frame_shard(geometry, r, world) for r in range(world)]
+    return shards, [_native.band_shard_rows(s, int(geometry[3])) for s in shards]
+
+
 _SHARD_KINDS = {"both": (False, True), "logical": (False,), "token_major": (True,)}
 
 
@@ -707,8 +702,7 @@ def band_shard_exchange_plan(mask, geometry, world: int, kinds: str = "both", de
     dense_mask: the alternate mask of a device switch, whose flag is not read back either — the element-wise OR with the plan of
     `dense_mask` for heads in logical order: a pair that either setting of the flag needs is kept."""
     S, vid0, F, P = (int(x) for x in geometry)
-    sh = [frame_shard(geometry, r, world) for r in range(world)]
-    rows = [_native.band_shard_rows(s, P) for s in sh]
+    sh, rows = _frame_shards(geometry, world)
     plan = [[rows[r] > 0 and rows[s] > 0 and any(_native.band_shard_has_keys(mask, S, (vid0, F, P), sh[r], sh[s], kind)
                                                  for kind in _SHARD_KINDS[kinds]) for s in range(world)] for r in range(world)]
     if dense_mask is not None:
@@ -726,10 +720,9 @@ def token_sharded_svg1_attention(q_local: torch.Tensor, k_local: torch.Tensor, v
     back; geometry = (num_tokens, vid0, num_frame, frame_size).  Returns this rank's rows of band attention under `mask`
     (_native.BandMask over num_tokens rows, in each head's logical order) with the head placement and its inverse applied, in the rank's
     own row order, [..., H, S_r, D].
-    The overlap schedule of token_sharded_band_attention: at step j the rank attends over the shard of rank s = (rank - j) mod world —
-    attn_fn(q, k_s, v_s, q_shard, k_shard) -> (o, lse), both kinds of head in one launch — while the shard of the next step is in flight;
-    ONE merge_fn(o_parts, lse_parts) over the parts in SOURCE-rank order.  A pair (rank, s) that band_shard_exchange_plan rules out for
-    every kind of head in `kinds` sends nothing and computes nothing; every rank still enters the collective of a step.  attn_fn and
+    The schedule of _attend_over_key_shards under band_shard_exchange_plan: a step is attn_fn(q, k_s, v_s, q_shard, k_shard) -> (o, lse)
+    with the shards of this rank and of the keys' owner, both kinds of head in one launch, and the own part is computed before the first
+    exchange is posted.  A pair (rank, s) that the plan rules out for every kind of head in `kinds` exchanges and computes nothing.  attn_fn and
     merge_fn default to the native calls (_native.band_shard_attention, _native.merge_attention_states; fp32_parts: one rounding); they
     exist so that the schedule can be tested on gloo without a GPU.
     dense_mask, dense_flag (both or neither, ValueError otherwise): the processors' device switch — dense_flag (int32 [1] on the device)
@@ -740,20 +733,13 @@ def token_sharded_svg1_attention(q_local: torch.Tensor, k_local: torch.Tensor, v
     keeps its five arguments and looks after the flag itself.
     What svg.models._core runs in frame-shard mode (enable_frame_shards); not wired into bench_step.py.  Equal to the single-GPU result
     to rounding, not bit for bit."""
-    if (dense_mask is None) != (dense_flag is None):
-        raise ValueError("token_sharded_svg1_attention: dense_mask and dense_flag go together (the device switch), or neither")
+    _check_device_switch_pair("token_sharded_svg1_attention", dense_mask, dense_flag)
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     S, vid0, F, P = (int(x) for x in geometry)
-    sh = [frame_shard(geometry, r, world) for r in range(world)]
-    n_tok = [_native.band_shard_rows(s, P) for s in sh]
+    sh, n_tok = _frame_shards(geometry, world)
     S_me = n_tok[rank]
     assert q_local.shape[-2] == S_me and k_local.shape == v_local.shape and k_local.shape[-2] == S_me, (
         f"rank {rank} holds {q_local.shape[-2]} / {k_local.shape[-2]} rows, frame_shard says {S_me}")
-    plan = band_shard_exchange_plan(mask, geometry, world, kinds, dense_mask=dense_mask)
-    most = max(sum(row) for row in plan)
-    if most > MERGE_MAX_PARTS:
-        raise ValueError(f"token_sharded_svg1_attention: a rank sees the keys of {most} shards, but merge_attention_states takes at most "
-                         f"{MERGE_MAX_PARTS} parts — use a group of at most {MERGE_MAX_PARTS} ranks")
     if attn_fn is None:
         def attn_fn(q, k, v, q_shard, k_shard):
             if dense_mask is not None:
@@ -764,42 +750,10 @@ def token_sharded_svg1_attention(q_local: torch.Tensor, k_local: torch.Tensor, v
     if merge_fn is None:
         def merge_fn(o_parts, lse_parts):
             return _native.merge_attention_states(o_parts, lse_parts, out_dtype=q_local.dtype if fp32_parts else None)
-    lead = tuple(k_local.shape[:-2])
-    D = k_local.shape[-1]
-    per_tok = 2 * D
-    for x in lead:
-        per_tok *= x
-    kv_shape = lambda n: (2,) + lead + (n, D)   # noqa: E731  (k and v of a shard travel as one message)
-    steps = [j for j in range(1, world) if any(plan[r][(r - j) % world] for r in range(world))]
-    send = torch.stack([k_local, v_local]).contiguous().view(-1) if steps else None
-
-    def shift(j):
-        """this rank's shard to rank + j if that rank sees it, the shard of rank - j if this rank sees it: (source rank, buffer, work)"""
-        dst, src = (rank + j) % world, (rank - j) % world
-        recv = _native.empty(n_tok[src] * per_tok if plan[rank][src] else 0, dtype=send.dtype, device=send.device)
-        ins, outs = [0] * world, [0] * world
-        ins[dst] = send.numel() if plan[dst][rank] else 0
-        outs[src] = recv.numel()
-        work = dist.all_to_all_single(recv, send[:ins[dst]], output_split_sizes=outs, input_split_sizes=ins, group=group, async_op=True)
-        return src, recv, work
-
-    parts = {}
-    if plan[rank][rank]:
-        parts[rank] = attn_fn(q_local, k_local, v_local, sh[rank], sh[rank])
-    nxt = shift(steps[0]) if steps else None
-    for i in range(len(steps)):
-        src, recv, work = nxt
-        work.wait()
-        nxt = shift(steps[i + 1]) if i + 1 < len(steps) else None     # in flight while this step computes
-        if plan[rank][src]:
-            k_s, v_s = recv.view(kv_shape(n_tok[src])).unbind(0)
-            parts[src] = attn_fn(q_local, k_s, v_s, sh[rank], sh[src])
-    if S_me == 0:
-        return _native.empty_like(q_local)
-    if not parts:   # (a mask that gives these rows no key at all)
-        return torch.zeros_like(q_local)
-    order = sorted(parts)
-    return merge_fn([parts[r][0] for r in order], [parts[r][1] for r in order])
+    return _attend_over_key_shards(q_local, k_local, v_local, n_tok,
+                                   band_shard_exchange_plan(mask, geometry, world, kinds, dense_mask=dense_mask),
+                                   lambda src, k_s, v_s: attn_fn(q_local, k_s, v_s, sh[rank], sh[src]), merge_fn, group,
+                                   "token_sharded_svg1_attention", post_before_own_part=False)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -810,7 +764,7 @@ def sampled_row_owners(rows, geometry, world: int) -> List[Tuple[int, int]]:
     """(owner rank, row index in that rank's frame_shard) of every sampled row (global indices, a host sequence): a video row lives with
     its frame, every row behind the video on the last rank.  Host only; the same list on every rank."""
     S, vid0, F, P = (int(x) for x in geometry)
-    sh = [frame_shard(geometry, r, world) for r in range(world)]
+    sh, _ = _frame_shards(geometry, world)
     out = []
     for g in (int(x) for x in rows):
         if not 0 <= g < S:
@@ -846,8 +800,8 @@ def token_sharded_sample_mse(q_local: torch.Tensor, k_local: torch.Tensor, v_loc
     S, vid0, F, P = (int(x) for x in geometry)
     if world > _native.PROFILE_MAX_PARTS:
         raise ValueError(f"token_sharded_sample_mse: {world} ranks, but sample_mse_from_parts takes at most {_native.PROFILE_MAX_PARTS} parts")
-    sh = [frame_shard(geometry, r, world) for r in range(world)]
-    S_me = _native.band_shard_rows(sh[rank], P)
+    sh, n_rows = _frame_shards(geometry, world)
+    S_me = n_rows[rank]
     assert q_local.shape[-2] == S_me and k_local.shape == v_local.shape and k_local.shape[-2] == S_me, (
         f"rank {rank} holds {q_local.shape[-2]} / {k_local.shape[-2]} rows, frame_shard says {S_me}")
     D = q_local.shape[-1]
@@ -859,9 +813,7 @@ def token_sharded_sample_mse(q_local: torch.Tensor, k_local: torch.Tensor, v_loc
     if combine_fn is None:
         def combine_fn(parts, n_rows):
             return _native.sample_mse_from_parts(parts, n_rows, q_local.dtype, prof.emulate_bf16, skip_flag=skip_flag)
-    BH = 1
-    for x in q_local.shape[:-2]:
-        BH *= int(x)
+    BH = math.prod(q_local.shape[:-2])
     q3, k3, v3 = (x.reshape(BH, S_me, D) for x in (q_local, k_local, v_local))
     # the sampled rows: this rank's into their places of a zeroed buffer, an exact sum over the ranks on the bits
     own = sampled_row_owners(rows.tolist(), geometry, world)
@@ -897,8 +849,7 @@ def token_sharded_svg1_layer_call(q_local: torch.Tensor, k_local: torch.Tensor, 
     nothing synchronises) is the profiler's skip_flag and the attention's switch (token_sharded_svg1_attention); the returned best_mask_idx
     is -1 on a dense step, as svg.models._core.svg1_attention_device_switch returns it.
     What svg.models._core runs in frame-shard mode; not wired into bench_step.py."""
-    if (dense_mask is None) != (dense_flag is None):
-        raise ValueError("token_sharded_svg1_layer_call: dense_mask and dense_flag go together (the device switch), or neither")
+    _check_device_switch_pair("token_sharded_svg1_layer_call", dense_mask, dense_flag)
     mse = token_sharded_sample_mse(q_local, k_local, v_local, rows, prof, geometry, group=group, skip_flag=dense_flag, partial_fn=partial_fn,
                                    combine_fn=combine_fn)
     best_mask_idx = torch.argmin(mse.to(q_local.dtype), dim=0)

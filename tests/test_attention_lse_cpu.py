@@ -6,19 +6,14 @@ schedule of svg.distributed.token_sharded_dense_attention on gloo CPU ranks with
 ref: flashinfer's run(..., return_lse=True) + merge_state, svg/kernels/ops/attention_ops.py:178-188; the context-parallel dense attention
 of svg/models/wan_orig/distributed/xdit_context_parallel.py:120-169."""
 import ctypes as C
-import os
-import sys
-from pathlib import Path
 
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
+from gloo_ranks import run_ranks
 from lse_ops_torch import attention_lse, merge_states
 from svg import _native as nat
 
-ROOT = Path(__file__).resolve().parent.parent
 BAD_ARG, UNSUPPORTED = -1, -2
 PH = 0x10000          # placeholder device pointer (16-byte aligned; never dereferenced by a call that is rejected)
 S_ROWS = 1 << 24
@@ -158,15 +153,9 @@ def test_merge_statement_edge_cases():
 # ---------------------------------------------------------------------------------------------------------
 # token_sharded_dense_attention on gloo CPU ranks
 # ---------------------------------------------------------------------------------------------------------
-def _worker(rank, world, port, ret):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    for p in (str(ROOT / "sparse-videogen_amd"), str(ROOT / "tests")):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    from lse_ops_torch import attention_lse, merge_states
+def _worker(rank, world):
     from svg.distributed import token_range, token_sharded_dense_attention
 
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     calls = []
 
     def attn_fn(q, k, v, return_lse=False):
@@ -195,21 +184,14 @@ def _worker(rank, world, port, ret):
             worst = max(worst, (o - ref[:, :, a:b]).abs().max().item())
             outs[overlap] = o
         worst = max(worst, (outs[True] - outs[False]).abs().max().item())
-    ret[rank] = (bool(ok), worst)
-    dist.destroy_process_group()
+    return bool(ok), worst
 
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_token_sharded_dense_attention_gloo(world):
     """ragged token_range (700 tokens on three ranks: unit 1 -> 234 / 233 / 233, unit 128 -> 256 / 256 / 188), both overlap settings: every
     rank's rows equal the single-process result to 1e-5, and the two settings agree to the same bound"""
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    port = 41500 + (os.getpid() % 2000) + world
-    mp.spawn(_worker, args=(world, port, ret), nprocs=world, join=True)
-    got = dict(ret)
-    assert sorted(got) == list(range(world))
-    for rank, (ok, worst) in got.items():
+    for rank, (ok, worst) in run_ranks(_worker, world, 41500).items():
         assert ok, rank
         assert worst <= 1e-5, (rank, worst)
 

@@ -10,19 +10,16 @@ ref: the context-parallel attention of svg/models/wan_orig/distributed/xdit_cont
 of svg/models/hyvideo/placement.py:156-184."""
 import bisect
 import ctypes as C
-import os
 import random
 import re
-import sys
 from pathlib import Path
 
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 import band_shard_cases as BC
 import sparse_lse_cases as SC
+from gloo_ranks import CountingAllToAll, run_ranks
 from lse_ops_torch import merge_states
 from oracle import svg_oracle as O
 from svg import _native as nat
@@ -441,28 +438,10 @@ def test_shard_parts_merge_to_the_whole_float64(name):
 # ---------------------------------------------------------------------------------------------------------
 # token_sharded_svg1_attention on gloo CPU ranks
 # ---------------------------------------------------------------------------------------------------------
-def _worker(rank, world, port, ret):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    for p in (str(ROOT / "sparse-videogen_amd"), str(ROOT / "tests"), str(ROOT)):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    import band_shard_cases as BC
-    import sparse_lse_cases as SC
-    from lse_ops_torch import merge_states
-    from oracle import svg_oracle as O
-    from svg import _native as nat
+def _worker(rank, world):
     from svg import distributed as sd
 
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    received = [0]
-    real_a2a = dist.all_to_all_single
-
-    def counting_a2a(out, inp, output_split_sizes=None, input_split_sizes=None, **kw):
-        received[0] += sum(output_split_sizes) * out.element_size()
-        assert out.numel() == sum(output_split_sizes) and inp.numel() == sum(input_split_sizes)
-        return real_a2a(out, inp, output_split_sizes=output_split_sizes, input_split_sizes=input_split_sizes, **kw)
-
-    sd.dist.all_to_all_single = counting_a2a
+    a2a = CountingAllToAll()
     H, D = 4, 16
     out = {}
     for name, flags, kinds in (("hy", (0, 1, 0, 1), "both"), ("wan", (0, 1, 0, 1), "both"), ("wan", (0, 0, 0, 0), "logical")):
@@ -488,7 +467,7 @@ def _worker(rank, world, port, ret):
                      for h in range(H)]                                                   # both kinds of head in one call
             return torch.cat([o for o, _ in parts], dim=1), torch.cat([l for _, l in parts], dim=1)
 
-        received[0] = 0
+        a2a.reset()
         o = sd.token_sharded_svg1_attention(q[:, :, rows].contiguous(), k[:, :, rows].contiguous(), v[:, :, rows].contiguous(), mask, fl, geo,
                                             kinds=kinds, attn_fn=attn_fn, merge_fn=merge_states)
         plan = sd.band_shard_exchange_plan(mask, geo, world, kinds)
@@ -497,11 +476,10 @@ def _worker(rank, world, port, ret):
         want_bytes = sum(n_rows[s] * per_tok for s in range(world) if s != rank and plan[rank][s])
         all_bytes = sum(n_rows[s] * per_tok for s in range(world) if s != rank)
         want_calls = sorted((sh[rank], sh[s]) for s in range(world) if plan[rank][s])
-        out[name, kinds] = dict(err=(o - ref[:, :, rows]).abs().max().item(), shape_ok=o.shape == (1, H, len(rows), D), received=received[0],
+        out[name, kinds] = dict(err=(o - ref[:, :, rows]).abs().max().item(), shape_ok=o.shape == (1, H, len(rows), D), received=a2a.received,
                                 want_bytes=want_bytes, all_bytes=all_bytes, calls_ok=sorted(calls) == want_calls,
                                 own_first=(not calls) or calls[0] == (sh[rank], sh[rank]), skipped=sum(not x for row in plan for x in row))
-    ret[rank] = out
-    dist.destroy_process_group()
+    return out
 
 
 @pytest.mark.parametrize("world", [2, 3])
@@ -514,12 +492,7 @@ def test_token_sharded_svg1_attention_gloo(world):
     from svg.distributed import band_shard_exchange_plan
     wan = nat.BandMask(**BC.CASES["wan"]["mask"])
     assert band_shard_exchange_plan(wan, BC.geometry("wan"), 3, "logical")[0][2] is False
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    port = 46500 + (os.getpid() % 2000) + world
-    mp.spawn(_worker, args=(world, port, ret), nprocs=world, join=True)
-    got = dict(ret)
-    assert sorted(got) == list(range(world))
+    got = run_ranks(_worker, world, 46500)
     for rank, res in got.items():
         for key, r in res.items():
             assert r["shape_ok"] and r["calls_ok"] and r["own_first"], (rank, key, r)

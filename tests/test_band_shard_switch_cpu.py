@@ -11,17 +11,18 @@ svg/models/hyvideo/placement.py:156-184."""
 import ctypes as C
 import os
 import re
-import sys
 from pathlib import Path
 
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
 import band_shard_cases as BC
+import sparse_lse_cases as SC
 import test_band_shard_cpu as B
 import test_profile_shard_cpu as PS
+from gloo_ranks import CountingAllToAll, run_ranks
+from lse_ops_torch import merge_states
 from oracle import svg_oracle as O
 from svg import _native as nat
 
@@ -211,27 +212,10 @@ def test_too_many_parts_is_judged_on_the_ored_plan(monkeypatch):
 # ---------------------------------------------------------------------------------------------------------
 # the schedules on gloo CPU ranks, float64 statements, mixed head kinds
 # ---------------------------------------------------------------------------------------------------------
-def _attention_worker(rank, world, port, ret):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    for p in (str(ROOT / "sparse-videogen_amd"), str(ROOT / "tests"), str(ROOT)):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    import band_shard_cases as BC
-    import sparse_lse_cases as SC
-    from lse_ops_torch import merge_states
-    from oracle import svg_oracle as O
-    from svg import _native as nat
+def _attention_worker(rank, world):
     from svg import distributed as sd
 
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    received = [0]
-    real_a2a = dist.all_to_all_single
-
-    def counting_a2a(out, inp, output_split_sizes=None, input_split_sizes=None, **kw):
-        received[0] += sum(output_split_sizes) * out.element_size()
-        return real_a2a(out, inp, output_split_sizes=output_split_sizes, input_split_sizes=input_split_sizes, **kw)
-
-    sd.dist.all_to_all_single = counting_a2a
+    a2a = CountingAllToAll()
     H, D = 4, 16
     out = {}
     for name, flags, kinds in (("hy", BC.FLAGS, "both"), ("wan", BC.FLAGS, "both"), ("wan", (0, 0, 0, 0), "logical")):
@@ -268,17 +252,16 @@ def _attention_worker(rank, world, port, ret):
                     parts.append(SC.masked_attention_lse(q_[:, h:h + 1], k_[:, h:h + 1], v_[:, h:h + 1], pm))
                 return torch.cat([o for o, _ in parts], dim=1), torch.cat([l for _, l in parts], dim=1)
 
-            received[0] = 0
+            a2a.reset()
             o = sd.token_sharded_svg1_attention(q[:, :, rows].contiguous(), k[:, :, rows].contiguous(), v[:, :, rows].contiguous(), mask, fl,
                                                 geo, kinds=kinds, attn_fn=attn_fn, merge_fn=merge_states, dense_mask=dense,
                                                 dense_flag=torch.full((1,), flag, dtype=torch.int32))
             out[name, kinds, flag] = dict(
-                err=(o - ref[flag][:, :, rows]).abs().max().item(), shape_ok=o.shape == (1, H, len(rows), D), received=received[0],
+                err=(o - ref[flag][:, :, rows]).abs().max().item(), shape_ok=o.shape == (1, H, len(rows), D), received=a2a.received,
                 want_bytes=sum(n_rows[s] * per_tok for s in range(world) if s != rank and plan[rank][s]),
                 sparse_bytes=sum(n_rows[s] * per_tok for s in range(world) if s != rank and sparse_plan[rank][s]),
                 calls_ok=sorted(calls) == sorted((sh[rank], sh[s]) for s in range(world) if plan[rank][s]))
-    ret[rank] = out
-    dist.destroy_process_group()
+    return out
 
 
 @pytest.mark.parametrize("world", [2, 3])
@@ -287,12 +270,7 @@ def test_token_sharded_svg1_attention_switch_gloo(world):
     flag of 0 every rank's rows equal the single-process placement -> mask -> inverse placement, with a flag of 1 dense-masked attention
     without placement, to 1e-5; the bytes a rank received are those of the OR-ed plan under either flag — on three ranks with heads in
     logical order more than the narrow Wan mask alone would have moved"""
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    port = 40500 + (os.getpid() % 2000) + world
-    mp.spawn(_attention_worker, args=(world, port, ret), nprocs=world, join=True)
-    got = dict(ret)
-    assert sorted(got) == list(range(world))
+    got = run_ranks(_attention_worker, world, 40500)
     for rank, res in got.items():
         assert len(res) == 6
         for key, r in res.items():
@@ -305,19 +283,9 @@ def test_token_sharded_svg1_attention_switch_gloo(world):
             assert r["sparse_bytes"] < r["received"]                # the pair the sparse mask drops travels: the flag is not read
 
 
-def _layer_worker(rank, world, port, ret):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    for p in (str(ROOT / "sparse-videogen_amd"), str(ROOT / "tests"), str(ROOT)):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    import sparse_lse_cases as SC
-    import test_profile_shard_cpu as PS
-    from lse_ops_torch import merge_states
-    from oracle import svg_oracle as O
-    from svg import _native as nat
+def _layer_worker(rank, world):
     from svg import distributed as sd
 
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     model, F, P, ctx = "hy", 5, 150, 20
     H = PS.H_
     S = F * P + ctx
@@ -358,8 +326,7 @@ def _layer_worker(rank, world, port, ret):
         ref = torch.cat(refs, dim=1)[0]
         res[flag] = dict(idx=idx, err=(o - ref).abs().max().item(), shape_ok=o.shape == (H, len(mine), PS.D_))
     res["best"] = best
-    ret[rank] = res
-    dist.destroy_process_group()
+    return res
 
 
 @pytest.mark.parametrize("world", [2, 3])
@@ -367,12 +334,7 @@ def test_token_sharded_svg1_layer_call_switch_gloo(world):
     """the layer-call with the device switch: with a flag of 0 best_mask_idx is the single-process argmin (head 0 token-major, head 1 in
     logical order) and the rows are the attention under it; with a flag of 1 best_mask_idx is -1 for every head and the rows are
     dense-masked attention without placement"""
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    port = 38500 + (os.getpid() % 2000) + world
-    mp.spawn(_layer_worker, args=(world, port, ret), nprocs=world, join=True)
-    got = dict(ret)
-    assert sorted(got) == list(range(world))
+    got = run_ranks(_layer_worker, world, 38500)
     for rank, r in got.items():
         assert r[0]["idx"].dtype == torch.int64 and torch.equal(r[0]["idx"], r["best"]) and r[0]["idx"][:2].tolist() == [1, 0], (rank, r)
         assert r[1]["idx"].dtype == torch.int64 and r[1]["idx"].tolist() == [-1] * PS.H_, (rank, r)

@@ -8,19 +8,16 @@ tests/test_gpu_band_window.py rests on, and the schedule of token_sharded_band_a
 ref: the context-parallel attention of svg/models/wan_orig/distributed/xdit_context_parallel.py:120-169 (dense only); flashinfer's
 run(..., return_lse=True) + merge_state, svg/kernels/ops/attention_ops.py:178-188."""
 import ctypes as C
-import os
 import random
 import re
-import sys
 from pathlib import Path
 
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 import sparse_lse_cases as SC
-from lse_ops_torch import merge_states
+from gloo_ranks import CountingAllToAll, run_ranks
+from lse_ops_torch import attention_lse, merge_states
 from oracle import svg_oracle as O
 from svg import _native as nat
 
@@ -291,27 +288,10 @@ GLOO_MASKS = {
 }
 
 
-def _worker(rank, world, port, ret):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    for p in (str(ROOT / "sparse-videogen_amd"), str(ROOT / "tests"), str(ROOT)):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    import sparse_lse_cases as SC
-    from lse_ops_torch import merge_states
-    from oracle import svg_oracle as O
-    from svg import _native as nat
+def _worker(rank, world):
     from svg import distributed as sd
 
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    received = [0]
-    real_a2a = dist.all_to_all_single
-
-    def counting_a2a(out, inp, output_split_sizes=None, input_split_sizes=None, **kw):
-        received[0] += sum(output_split_sizes) * out.element_size()
-        assert out.numel() == sum(output_split_sizes) and inp.numel() == sum(input_split_sizes)
-        return real_a2a(out, inp, output_split_sizes=output_split_sizes, input_split_sizes=input_split_sizes, **kw)
-
-    sd.dist.all_to_all_single = counting_a2a
+    a2a = CountingAllToAll()
     H, D, unit = 2, 16, 128
     out = {}
     for name, make in GLOO_MASKS.items():
@@ -330,7 +310,7 @@ def _worker(rank, world, port, ret):
             assert q_.shape[-2] == q_range[1] - q_range[0] and k_.shape[-2] == k_range[1] - k_range[0] and k_range[0] % 64 == 0
             return SC.masked_attention_lse(q_, k_, v_, em[q_range[0]:q_range[1], k_range[0]:k_range[1]])
 
-        received[0] = 0
+        a2a.reset()
         o = sd.token_sharded_band_attention(q[:, :, a:b].contiguous(), k[:, :, a:b].contiguous(), v[:, :, a:b].contiguous(), S, mask,
                                             unit=unit, attn_fn=attn_fn, merge_fn=merge_states)
         plan = sd.band_exchange_plan(mask, S, world, unit)
@@ -338,11 +318,10 @@ def _worker(rank, world, port, ret):
         want_bytes = sum((tr[s][1] - tr[s][0]) * per_tok for s in range(world) if s != rank and plan[rank][s])
         all_bytes = sum((tr[s][1] - tr[s][0]) * per_tok for s in range(world) if s != rank)
         want_calls = sorted((tr[rank], tr[s]) for s in range(world) if plan[rank][s])
-        out[name] = dict(err=(o - ref[:, :, a:b]).abs().max().item(), shape_ok=o.shape == (1, H, b - a, D), received=received[0],
+        out[name] = dict(err=(o - ref[:, :, a:b]).abs().max().item(), shape_ok=o.shape == (1, H, b - a, D), received=a2a.received,
                          want_bytes=want_bytes, all_bytes=all_bytes, calls_ok=sorted(calls) == want_calls,
                          own_first=(not calls) or calls[0] == (tr[rank], tr[rank]), skipped=sum(not x for row in plan for x in row))
-    ret[rank] = out
-    dist.destroy_process_group()
+    return out
 
 
 @pytest.mark.parametrize("world", [2, 3])
@@ -350,12 +329,7 @@ def test_token_sharded_band_attention_gloo(world):
     """ragged shards (790 rows: 384 / 406 and 256 / 256 / 278; 750 rows: 384 / 366 and 256 / 256 / 238), unit 128, float64 statements as
     attn_fn / merge_fn: every rank's rows equal the single-process result to 1e-5, the bytes a rank received are those of the shards
     band_exchange_plan keeps for it, attn_fn ran for exactly those pairs, and the narrow wan mask skips a pair on three ranks"""
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    port = 45500 + (os.getpid() % 2000) + world
-    mp.spawn(_worker, args=(world, port, ret), nprocs=world, join=True)
-    got = dict(ret)
-    assert sorted(got) == list(range(world))
+    got = run_ranks(_worker, world, 45500)
     for rank, res in got.items():
         for name, r in res.items():
             assert r["shape_ok"] and r["calls_ok"] and r["own_first"], (rank, name, r)
@@ -388,3 +362,45 @@ def test_token_sharded_band_attention_refuses_a_unit_off_the_key_tiles_and_too_m
         sd.token_sharded_band_attention(x, x, x, S, _mask(S, band=100), attn_fn=lambda *a: seen.append(a[3:]) or (a[0], a[0][..., 0]),
                                         merge_fn=lambda o, l: o[0])
     assert seen == [((0, 128), (0, 128))]               # past the part-count check: the own shard ran, then the first exchange
+
+
+# ---------------------------------------------------------------------------------------------------------
+# one schedule: dense is band under a mask that allows everything
+# ---------------------------------------------------------------------------------------------------------
+def _dense_is_band_worker(rank, world):
+    from svg import distributed as sd
+
+    a2a = CountingAllToAll()
+    H, D, unit = 3, 32, 128
+    S = {3: 700, 4: 300}[world]
+    g = torch.Generator().manual_seed(7)
+    q, k, v = (torch.randn(1, H, S, D, generator=g) for _ in range(3))
+    ref = attention_lse(q.double(), k.double(), v.double(), return_lse=False).float()
+    tr = [sd.token_range(S, r, world, unit) for r in range(world)]
+    a, b = tr[rank]
+    ql, kl, vl = (x[:, :, a:b].contiguous() for x in (q, k, v))
+    o_dense = sd.token_sharded_dense_attention(ql, kl, vl, S, unit=unit, overlap=True, merge_fn=merge_states,
+                                               attn_fn=lambda q_, k_, v_, return_lse=False: attention_lse(q_, k_, v_, return_lse=return_lse))
+    dense_splits = a2a.splits
+    a2a.reset()
+    o_band = sd.token_sharded_band_attention(ql, kl, vl, S, nat.BandMask(**O.dense_band_params(S)), unit=unit, merge_fn=merge_states,
+                                             attn_fn=lambda q_, k_, v_, q_range, k_range: attention_lse(q_, k_, v_, return_lse=True))
+    return dict(rows=[hi - lo for lo, hi in tr], shapes=(tuple(o_dense.shape), tuple(o_band.shape)), equal=torch.equal(o_dense, o_band),
+                err=max((o - ref[:, :, a:b]).abs().max().item() if b > a else 0.0 for o in (o_dense, o_band)),
+                dense_splits=dense_splits, band_splits=a2a.splits)
+
+
+@pytest.mark.parametrize("world,rows", [(3, [256, 256, 188]), (4, [128, 128, 0, 44])])
+def test_token_sharded_dense_attention_is_band_attention_under_a_dense_mask_gloo(world, rows):
+    """float32 inputs, the torch statements as attn_fn / merge_fn of both: on every rank token_sharded_dense_attention(overlap=True) and
+    token_sharded_band_attention under a mask that allows everything return the same bits, within 1e-5 of the single-process float64
+    result.  Three ranks (700 rows): both post the same exchanges.  Four ranks (300 rows, one rank without rows, which returns
+    [1, 3, 0, 32] from both): dense sends to the empty rank and band does not, so the split lists are not compared there."""
+    got = run_ranks(_dense_is_band_worker, world, 27500)
+    for rank, r in got.items():
+        assert r["rows"] == rows
+        assert r["shapes"] == ((1, 3, rows[rank], 32),) * 2, (rank, r["shapes"])
+        assert r["equal"], rank
+        assert r["err"] <= 1e-5, (rank, r["err"])
+        if world == 3:
+            assert r["dense_splits"] == r["band_splits"] and len(r["dense_splits"]) == 2, (rank, r["dense_splits"], r["band_splits"])

@@ -7,16 +7,13 @@ schedules on gloo CPU ranks with float64 statements of the partial and the combi
 ref: sample_mse, svg/models/hyvideo/attention.py:376-399 with the profiling masks of get_attention_mask, svg/models/hyvideo/utils.py:47-93
 (wan/utils.py:63-110)."""
 import ctypes as C
-import os
 import re
-import sys
 from pathlib import Path
 
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
+from gloo_ranks import run_ranks
 from oracle import svg_oracle as O
 from svg import _native as nat
 
@@ -363,14 +360,9 @@ def profile_inputs(model, F, P, ctx, seed=11):
 SCHEDULE_CASES = [("hy", 5, 150, 20), ("wan", 5, 150, 0), ("hy", 2, 150, 20), ("wan", 2, 150, 0)]
 
 
-def _mse_worker(rank, world, port, ret):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    for p in (str(ROOT / "sparse-videogen_amd"), str(ROOT / "tests"), str(ROOT)):
-        if p not in sys.path:
-            sys.path.insert(0, p)
+def _mse_worker(rank, world):
     from svg import distributed as sd
 
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     out = {}
     for model, F, P, ctx in SCHEDULE_CASES:
         S = F * P + ctx
@@ -397,8 +389,7 @@ def _mse_worker(rank, world, port, ret):
         mse = sd.token_sharded_sample_mse(q[:, mine].contiguous(), k[:, mine].contiguous(), v[:, mine].contiguous(), rows, prof, geo,
                                           partial_fn=partial_fn, combine_fn=combine_fn)
         out[model, F] = dict(mse=mse, rows_held=len(mine), seen=dict(seen), n_parts=n_parts)
-    ret[rank] = out
-    dist.destroy_process_group()
+    return out
 
 
 @pytest.mark.parametrize("world", [2, 3])
@@ -407,12 +398,7 @@ def test_token_sharded_sample_mse_gloo(world):
     nothing at all (wan: the neutral part) —, the text on the last rank: the merged MSEs equal sample_mse_fp32 of the whole sequence to 1e-9
     (and the float64 statement of it to 1e-12 of the largest), are identical on every rank, the gathered q rows are q[:, rows] bit for bit, and every rank
     combined `world` parts"""
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    port = 44500 + (os.getpid() % 2000) + world
-    mp.spawn(_mse_worker, args=(world, port, ret), nprocs=world, join=True)
-    got = dict(ret)
-    assert sorted(got) == list(range(world))
+    got = run_ranks(_mse_worker, world, 44500)
     for model, F, P, ctx in SCHEDULE_CASES:
         q, k, v, rows = profile_inputs(model, F, P, ctx)
         masks = list(O.profile_masks(model, ctx, F, P))
@@ -436,16 +422,11 @@ def test_token_sharded_sample_mse_gloo(world):
             assert torch.equal(ref64.argmin(0)[:2], torch.tensor([1, 0])), (model, ref64)  # head 0 temporal, head 1 spatial, as constructed
 
 
-def _layer_worker(rank, world, port, ret):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    for p in (str(ROOT / "sparse-videogen_amd"), str(ROOT / "tests"), str(ROOT)):
-        if p not in sys.path:
-            sys.path.insert(0, p)
+def _layer_worker(rank, world):
     import sparse_lse_cases as SC
     from lse_ops_torch import merge_states
     from svg import distributed as sd
 
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     model, F, P, ctx = "hy", 5, 150, 20
     S = F * P + ctx
     geo = (S, 0, F, P)
@@ -478,20 +459,14 @@ def _layer_worker(rank, world, port, ret):
         c = coords(torch.arange(S), bool(best[h]))
         refs.append(SC.masked_attention_lse(q[None, h:h + 1, mine], k[None, h:h + 1], v[None, h:h + 1], em[c[mine]][:, c])[0])
     ref = torch.cat(refs, dim=1)[0]
-    ret[rank] = dict(idx=idx, best=best, err=(o - ref).abs().max().item(), shape_ok=o.shape == (H_, len(mine), D_))
-    dist.destroy_process_group()
+    return dict(idx=idx, best=best, err=(o - ref).abs().max().item(), shape_ok=o.shape == (H_, len(mine), D_))
 
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_token_sharded_svg1_layer_call_gloo(world):
     """the layer-call from q, k, v alone: best_mask_idx is the single-process argmin on every rank (head 0 token-major, head 1 in logical
     order, as constructed), and the rank's rows of the attention under it equal the float64 statement over all keys"""
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    port = 42500 + (os.getpid() % 2000) + world
-    mp.spawn(_layer_worker, args=(world, port, ret), nprocs=world, join=True)
-    got = dict(ret)
-    assert sorted(got) == list(range(world))
+    got = run_ranks(_layer_worker, world, 42500)
     for rank, r in got.items():
         assert r["idx"].dtype == torch.int64 and torch.equal(r["idx"], r["best"]) and r["idx"][:2].tolist() == [1, 0], (rank, r)
         assert r["shape_ok"] and r["err"] <= 1e-9, (rank, r["err"])
