@@ -407,6 +407,10 @@ static int run_kmeans_iter(const void* x, const float* xsq, const void* c_in, vo
 // commit kernel reads the flags of the iteration before, one thread per group writes the flag for the next), state[2G + g]: n_iters of
 // group g, state[3G + g]: which centroid buffer holds group g's result (0 initial, 1 / 2 the two work buffers).  With G = 1 this is the
 // layout of the ungrouped loop: [flag0, flag1, n_iters, selector].
+// kGivenMaxima = false: `shift` is the float [B] of the iteration and the group maxima are reduced here (svg_kmeans_loop*);
+// true: `shift` is the float [G] of group maxima the caller hands in (svg_kmeans_stepped_commit: a collective may have sat between the
+// iteration and this launch) — the same rule, `conv = !(m != m) && m < tol`, applied to it.
+template <bool kGivenMaxima>
 __global__ __launch_bounds__(256) void kmeans_commit_kernel(const int32_t* __restrict__ labels, const int32_t* __restrict__ sorted_idx,
                                                             const int32_t* __restrict__ counts, int32_t* __restrict__ labels_r,
                                                             int32_t* __restrict__ sorted_r, int32_t* __restrict__ counts_r,
@@ -427,13 +431,18 @@ __global__ __launch_bounds__(256) void kmeans_commit_kernel(const int32_t* __res
         for (int g = threadIdx.x >> 6; g < G; g += 4) {
             float mx = 0.f;
             bool nan = false;   // fmaxf drops a NaN operand; the reference's `shift.max()` propagates it, and `NaN < tol` is False (:723)
-            for (int b = g * group + lane; b < (g + 1) * group; b += 64) {
-                const float sft = shift[b];
-                nan |= sft != sft;
-                mx = fmaxf(mx, sft);
+            if constexpr (kGivenMaxima) {
+                mx = shift[g];
+                nan = mx != mx;
+            } else {
+                for (int b = g * group + lane; b < (g + 1) * group; b += 64) {
+                    const float sft = shift[b];
+                    nan |= sft != sft;
+                    mx = fmaxf(mx, sft);
+                }
+                mx = wave_max(mx);
+                nan = __builtin_amdgcn_ballot_w64(nan) != 0ull;
             }
-            mx = wave_max(mx);
-            nan = __builtin_amdgcn_ballot_w64(nan) != 0ull;
             if (lane == 0) {
                 const bool stopped = stopped_in[g] != 0;
                 const bool conv = !nan && mx < tol;   // `center_shift < tol` (:723): a NaN shift never converges, the loop runs to max_iters
@@ -444,6 +453,23 @@ __global__ __launch_bounds__(256) void kmeans_commit_kernel(const int32_t* __res
                 state[((it + 1) & 1) * G + g] = (stopped || conv) ? 1 : 0;
             }
         }
+    }
+}
+// maxima[g] = the largest shift of group g's batches, a NaN among them propagated as torch.max propagates it (the stepped loop: what
+// kmeans_commit_kernel<false> reduces for itself, written out so that the caller can reduce it further).  One wave per group.
+__global__ __launch_bounds__(256) void kmeans_group_maxima_kernel(const float* __restrict__ shift, float* __restrict__ maxima, int G, int group) {
+    const int lane = threadIdx.x & 63;
+    for (int g = blockIdx.x * 4 + (threadIdx.x >> 6); g < G; g += gridDim.x * 4) {
+        float mx = 0.f;
+        bool nan = false;
+        for (int b = g * group + lane; b < (g + 1) * group; b += 64) {
+            const float sft = shift[b];
+            nan |= sft != sft;
+            mx = fmaxf(mx, sft);
+        }
+        mx = wave_max(mx);
+        nan = __builtin_amdgcn_ballot_w64(nan) != 0ull;
+        if (lane == 0) maxima[g] = nan ? __builtin_nanf("") : mx;
     }
 }
 template <typename T>
@@ -579,6 +605,73 @@ extern "C" size_t svg_kmeans_loop_workspace_bytes(int32_t B, int32_t N, int32_t 
     return B > 0 ? svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, B) : 0;
 }
 
+// ---- the host steps of the Lloyd loop, shared by svg_kmeans_loop* (all of them in one call) and svg_kmeans_stepped_* (one per call) ----
+// scratch of one loop: the per-iteration scratch of svg_kmeans_iter, one iteration's labels / sorted indices / counts / shift, the state words
+struct KmeansLoopScratch {
+    void* it_ws;
+    size_t it_bytes;
+    int32_t *t_labels, *t_sorted, *t_counts;
+    float* t_shift;
+    int32_t* state;
+};
+static size_t kmeans_state_bytes(int G) { return ((size_t)G * 4 * sizeof(int32_t) + 255) / 256 * 256; }
+// state_first = false: the layout of svg_kmeans_loop_grouped_workspace_bytes (state words last); true: the stepped entries' (state words
+// first: svg_kmeans_stepped_finish has no N and finds them there)
+static KmeansLoopScratch kmeans_loop_scratch(void* workspace, int B, int N, int K, int D, int G, bool state_first) {
+    KmeansLoopScratch s;
+    s.it_bytes = (svg_kmeans_workspace_bytes(B, N, K, D) + 255) / 256 * 256;
+    const size_t a = ((size_t)B * N * 4 + 255) / 256 * 256, c = ((size_t)B * K * 4 + 255) / 256 * 256, sh = ((size_t)B * 4 + 255) / 256 * 256;
+    char* w = (char*)workspace + (state_first ? kmeans_state_bytes(G) : 0);
+    s.it_ws = w;
+    s.t_labels = (int32_t*)(w + s.it_bytes);
+    s.t_sorted = (int32_t*)(w + s.it_bytes + a);
+    s.t_counts = (int32_t*)(w + s.it_bytes + 2 * a);
+    s.t_shift = (float*)(w + s.it_bytes + 2 * a + c);
+    s.state = state_first ? (int32_t*)workspace : (int32_t*)(w + s.it_bytes + 2 * a + c + sh);
+    return s;
+}
+
+// iteration `it` into the scratch: it == 0 clears the state words and reads c_init, writing c_work_a; odd iterations write c_work_b
+static int kmeans_loop_iterate(const KmeansLoopScratch& s, const void* x, long long x_bs, const float* xsq, const void* c_init, void* c_work_a,
+                               void* c_work_b, int it, int B, int N, int K, int D, int dtype, int G, void* stream) {
+    if (it == 0 && hipMemsetAsync(s.state, 0, (size_t)4 * G * sizeof(int32_t), (hipStream_t)stream) != hipSuccess) return SVG_ERR_LAUNCH;
+    const void* cur = it == 0 ? c_init : ((it & 1) ? c_work_a : c_work_b);
+    void* out = (it & 1) ? c_work_b : c_work_a;
+    return kmeans_iter_impl(x, x_bs, xsq, cur, out, s.t_labels, s.t_counts, s.t_sorted, s.t_shift, B, N, K, D, dtype, s.it_ws, s.it_bytes, stream);
+}
+
+// the commit of iteration `it`; maxima == NULL: the group maxima are reduced from the scratch shift inside the kernel
+static void kmeans_loop_commit(const KmeansLoopScratch& s, const float* maxima, int32_t* labels, int32_t* counts, int32_t* sorted_idx, int it,
+                               float tol, int B, int N, int K, int group, hipStream_t st) {
+    const int G = B / group;
+    const int sel_cur = it == 0 ? 0 : ((it & 1) ? 1 : 2), sel_out = (it & 1) ? 2 : 1;   // 0 initial, 1 / 2 the two work buffers
+    const long long gn = (long long)group * N, gk = (long long)group * K;
+    // (G = 1: the grid of the ungrouped loop; more groups share about as many workgroups, a stopped group's return at once)
+    const dim3 grid((unsigned)std::min<long long>((2048 + G - 1) / G, (gn + 255) / 256), (unsigned)G);
+    if (maxima)
+        hipLaunchKernelGGL(kmeans_commit_kernel<true>, grid, dim3(256), 0, st, s.t_labels, s.t_sorted, s.t_counts, labels, sorted_idx, counts,
+                           maxima, s.state, gn, gk, group, tol, it, sel_cur, sel_out);
+    else
+        hipLaunchKernelGGL(kmeans_commit_kernel<false>, grid, dim3(256), 0, st, s.t_labels, s.t_sorted, s.t_counts, labels, sorted_idx, counts,
+                           s.t_shift, s.state, gn, gk, group, tol, it, sel_cur, sel_out);
+}
+
+// every group's centroids from the buffer its selector names, and the n_iters words
+static int kmeans_loop_finish(const KmeansLoopScratch& s, const void* c_init, const void* c_work_a, const void* c_work_b, void* centroids_out,
+                              int32_t* n_iters, int B, int K, int D, int dtype, int group, hipStream_t st) {
+    const int G = B / group;
+    const long long gn8 = (long long)group * K * D / 8;
+    const dim3 g2((unsigned)std::min<long long>((1024 + G - 1) / G, (gn8 + 255) / 256), (unsigned)G);
+    if (dtype == SVG_DTYPE_BF16)
+        hipLaunchKernelGGL((kmeans_select_kernel<__bf16>), g2, dim3(256), 0, st, (const __bf16*)c_init, (const __bf16*)c_work_a,
+                           (const __bf16*)c_work_b, (__bf16*)centroids_out, s.state + 3 * G, gn8);
+    else
+        hipLaunchKernelGGL((kmeans_select_kernel<_Float16>), g2, dim3(256), 0, st, (const _Float16*)c_init, (const _Float16*)c_work_a,
+                           (const _Float16*)c_work_b, (_Float16*)centroids_out, s.state + 3 * G, gn8);
+    if (hipMemcpyAsync(n_iters, s.state + 2 * G, (size_t)G * sizeof(int32_t), hipMemcpyDeviceToDevice, st) != hipSuccess) return SVG_ERR_LAUNCH;
+    return launch_status();
+}
+
 // svg_kmeans_loop (x_bs = N * D, group = B), svg_kmeans_loop_strided (group = B) and their grouped forms
 static int kmeans_loop_impl(const void* x, long long x_bs, const float* xsq, const void* c_init, void* c_work_a, void* c_work_b, int32_t* labels,
                             int32_t* counts, int32_t* sorted_idx, void* centroids_out, int32_t* n_iters, int32_t B, int32_t N,
@@ -593,40 +686,12 @@ static int kmeans_loop_impl(const void* x, long long x_bs, const float* xsq, con
         return SVG_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int G = B / group;
-    const size_t it_bytes = (svg_kmeans_workspace_bytes(B, N, K, D) + 255) / 256 * 256;
-    const size_t a = ((size_t)B * N * 4 + 255) / 256 * 256, c = ((size_t)B * K * 4 + 255) / 256 * 256, sh = ((size_t)B * 4 + 255) / 256 * 256;
-    char* w = (char*)workspace;
-    void* it_ws = w;
-    int32_t* t_labels = (int32_t*)(w + it_bytes);
-    int32_t* t_sorted = (int32_t*)(w + it_bytes + a);
-    int32_t* t_counts = (int32_t*)(w + it_bytes + 2 * a);
-    float* t_shift = (float*)(w + it_bytes + 2 * a + c);
-    int32_t* state = (int32_t*)(w + it_bytes + 2 * a + c + sh);
-    if (hipMemsetAsync(state, 0, (size_t)4 * G * sizeof(int32_t), st) != hipSuccess) return SVG_ERR_LAUNCH;
-    const void* cur = c_init;
-    int sel_cur = 0;
-    const long long gn = (long long)group * N, gk = (long long)group * K;
-    // (G = 1: the grid of the ungrouped loop; more groups share about as many workgroups, a stopped group's return at once)
-    const dim3 grid((unsigned)std::min<long long>((2048 + G - 1) / G, (gn + 255) / 256), (unsigned)G);
+    const KmeansLoopScratch s = kmeans_loop_scratch(workspace, B, N, K, D, G, false);
     for (int it = 0; it < max_iters; ++it) {
-        void* out = (it & 1) ? c_work_b : c_work_a;
-        const int sel_out = (it & 1) ? 2 : 1;
-        const int rc = kmeans_iter_impl(x, x_bs, xsq, cur, out, t_labels, t_counts, t_sorted, t_shift, B, N, K, D, dtype, it_ws, it_bytes, stream);
-        if (rc != SVG_OK) return rc;
-        hipLaunchKernelGGL(kmeans_commit_kernel, grid, dim3(256), 0, st, t_labels, t_sorted, t_counts, labels, sorted_idx, counts,
-                           t_shift, state, gn, gk, (int)group, tol, it, sel_cur, sel_out);
-        cur = out, sel_cur = sel_out;
+        if (const int rc = kmeans_loop_iterate(s, x, x_bs, xsq, c_init, c_work_a, c_work_b, it, B, N, K, D, dtype, G, stream); rc != SVG_OK) return rc;
+        kmeans_loop_commit(s, nullptr, labels, counts, sorted_idx, it, tol, B, N, K, group, st);
     }
-    const long long gn8 = gk * D / 8;
-    const dim3 g2((unsigned)std::min<long long>((1024 + G - 1) / G, (gn8 + 255) / 256), (unsigned)G);
-    if (dtype == SVG_DTYPE_BF16)
-        hipLaunchKernelGGL((kmeans_select_kernel<__bf16>), g2, dim3(256), 0, st, (const __bf16*)c_init, (const __bf16*)c_work_a,
-                           (const __bf16*)c_work_b, (__bf16*)centroids_out, state + 3 * G, gn8);
-    else
-        hipLaunchKernelGGL((kmeans_select_kernel<_Float16>), g2, dim3(256), 0, st, (const _Float16*)c_init, (const _Float16*)c_work_a,
-                           (const _Float16*)c_work_b, (_Float16*)centroids_out, state + 3 * G, gn8);
-    if (hipMemcpyAsync(n_iters, state + 2 * G, (size_t)G * sizeof(int32_t), hipMemcpyDeviceToDevice, st) != hipSuccess) return SVG_ERR_LAUNCH;
-    return launch_status();
+    return kmeans_loop_finish(s, c_init, c_work_a, c_work_b, centroids_out, n_iters, B, K, D, dtype, group, st);
 }
 
 static int check_strided(const void* x, int64_t x_batch_stride, int32_t N, int32_t D) {
@@ -667,4 +732,56 @@ extern "C" int svg_kmeans_loop_grouped_strided(const void* x, int64_t x_batch_st
     if (const int rc = check_strided(x, x_batch_stride, N, D); rc != SVG_OK) return rc;
     return kmeans_loop_impl(x, (long long)x_batch_stride, nullptr, c_init, c_work_a, c_work_b, labels, counts, sorted_idx, centroids_out, n_iters,
                             B, N, K, D, dtype, group, max_iters, tol, workspace, workspace_bytes, stream);
+}
+
+// ---- the Lloyd loop in steps (include/svg_attn_kmeans_stepped.h): the host steps above, one per call, with the group maxima handed out
+// by iterate and taken back by commit ----
+extern "C" size_t svg_kmeans_stepped_workspace_bytes(int32_t B, int32_t N, int32_t K, int32_t D, int32_t group) {
+    if (K > 8192 || (D != 64 && D != 128)) return 0;
+    return svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, group);   // (the same blocks, the state words in front)
+}
+
+extern "C" int svg_kmeans_stepped_iterate(const void* x, int64_t x_batch_stride, const void* c_init, void* c_work_a, void* c_work_b, int32_t it,
+                                          float* maxima, int32_t B, int32_t N, int32_t K, int32_t D, int32_t dtype, int32_t group,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+    if (!x || !c_init || !c_work_a || !c_work_b || !maxima || !workspace) return SVG_ERR_BAD_ARG;
+    if (B <= 0 || N <= 0 || K <= 0 || group <= 0 || B % group != 0 || it < 0) return SVG_ERR_BAD_ARG;
+    if (K > 8192 || (D != 64 && D != 128) || (dtype != SVG_DTYPE_BF16 && dtype != SVG_DTYPE_F16)) return SVG_ERR_UNSUPPORTED;
+    if (workspace_bytes < svg_kmeans_stepped_workspace_bytes(B, N, K, D, group)) return SVG_ERR_WORKSPACE;
+    if (c_init == c_work_a || c_init == c_work_b || c_work_a == c_work_b) return SVG_ERR_BAD_ARG;
+    if (const int rc = check_strided(x, x_batch_stride, N, D); rc != SVG_OK) return rc;
+    const int G = B / group;
+    const KmeansLoopScratch s = kmeans_loop_scratch(workspace, B, N, K, D, G, true);
+    if (const int rc = kmeans_loop_iterate(s, x, (long long)x_batch_stride, nullptr, c_init, c_work_a, c_work_b, it, B, N, K, D, dtype, G, stream);
+        rc != SVG_OK)
+        return rc;
+    hipLaunchKernelGGL(kmeans_group_maxima_kernel, dim3((unsigned)std::min(256, (G + 3) / 4)), dim3(256), 0, (hipStream_t)stream, s.t_shift, maxima,
+                       G, (int)group);
+    return launch_status();
+}
+
+extern "C" int svg_kmeans_stepped_commit(const float* maxima, int32_t* labels, int32_t* counts, int32_t* sorted_idx, int32_t it, float tol, int32_t B,
+                                         int32_t N, int32_t K, int32_t group, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!maxima || !labels || !counts || !sorted_idx || !workspace) return SVG_ERR_BAD_ARG;
+    if (B <= 0 || N <= 0 || K <= 0 || group <= 0 || B % group != 0 || it < 0) return SVG_ERR_BAD_ARG;
+    if (K > 8192) return SVG_ERR_UNSUPPORTED;
+    // (no head_dim here: none of the blocks' sizes depends on it)
+    if (workspace_bytes < svg_kmeans_stepped_workspace_bytes(B, N, K, 128, group)) return SVG_ERR_WORKSPACE;
+    const KmeansLoopScratch s = kmeans_loop_scratch(workspace, B, N, K, 128, B / group, true);
+    kmeans_loop_commit(s, maxima, labels, counts, sorted_idx, it, tol, B, N, K, group, (hipStream_t)stream);
+    return launch_status();
+}
+
+extern "C" int svg_kmeans_stepped_finish(const void* c_init, const void* c_work_a, const void* c_work_b, void* centroids_out, int32_t* n_iters,
+                                         int32_t B, int32_t K, int32_t D, int32_t dtype, int32_t group, void* workspace, size_t workspace_bytes,
+                                         void* stream) {
+    if (!c_init || !c_work_a || !c_work_b || !centroids_out || !n_iters || !workspace) return SVG_ERR_BAD_ARG;
+    if (B <= 0 || K <= 0 || group <= 0 || B % group != 0) return SVG_ERR_BAD_ARG;
+    if (K > 8192 || (D != 64 && D != 128) || (dtype != SVG_DTYPE_BF16 && dtype != SVG_DTYPE_F16)) return SVG_ERR_UNSUPPORTED;
+    // (no N here: the smallest workspace an iterate of these B, K, D, group took — the state words finish reads lie in front of it)
+    if (workspace_bytes < svg_kmeans_stepped_workspace_bytes(B, 1, K, D, group)) return SVG_ERR_WORKSPACE;
+    if (c_init == c_work_a || c_init == c_work_b || c_work_a == c_work_b || centroids_out == c_work_a || centroids_out == c_work_b)
+        return SVG_ERR_BAD_ARG;
+    const KmeansLoopScratch s = kmeans_loop_scratch(workspace, B, 1, K, D, B / group, true);
+    return kmeans_loop_finish(s, c_init, c_work_a, c_work_b, centroids_out, n_iters, B, K, D, dtype, group, (hipStream_t)stream);
 }

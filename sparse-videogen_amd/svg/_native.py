@@ -360,6 +360,17 @@ ADAPTIVE_BAND_ENTRIES = {
 }
 
 
+# include/svg_attn_kmeans_stepped.h: the Lloyd loop of svg_kmeans_loop_grouped in steps — iterate hands the group maxima out, commit takes
+# them back —, in a table of its own for the same reason (tests/test_kmeans_stepped_cpu.py; bindings on the caller's buffers:
+# kmeans_stepped_* below; the allocating side: svg/_kmeans_stepped.py KmeansSteppedSide)
+KMEANS_STEPPED_SIGNATURES = {
+    "svg_kmeans_stepped_workspace_bytes": (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    "svg_kmeans_stepped_iterate": (C.c_int, [_VP, _I64, _VP, _VP, _VP, _I32, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _SZ, _VP]),
+    "svg_kmeans_stepped_commit": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _F32, _I32, _I32, _I32, _I32, _VP, _SZ, _VP]),
+    "svg_kmeans_stepped_finish": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _SZ, _VP]),
+}
+
+
 class CopyBox(C.Structure):
     """svg_copy_box_t (include/svg_attn_shard_exchange.h): extent[0] * extent[1] * extent[2] rows of D contiguous elements; offsets and
     strides in elements"""
@@ -396,7 +407,7 @@ def load(strict: bool = True) -> Optional[C.CDLL]:
         for name, (res, args) in {**SIGNATURES, **SPARSE_LSE_SIGNATURES, **SPARSE_F32_SIGNATURES, **BAND_LSE_FORM_SIGNATURES,
                                    **BAND_WINDOW_SIGNATURES, **BAND_SHARD_SIGNATURES, **BAND_SHARD_SWITCH_SIGNATURES,
                                    **PROFILE_SHARD_SIGNATURES, **SAMPLE_ROWS_SIGNATURES, **SHARD_EXCHANGE_SIGNATURES,
-                                   **ADAPTIVE_TOP_P_SIGNATURES, **ADAPTIVE_BAND_ENTRIES}.items():
+                                   **ADAPTIVE_TOP_P_SIGNATURES, **ADAPTIVE_BAND_ENTRIES, **KMEANS_STEPPED_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -1856,6 +1867,52 @@ def kmeans_loop(x: torch.Tensor, xsq: Optional[torch.Tensor], c_init: torch.Tens
     rc = lib.svg_kmeans_loop(x.data_ptr(), _ptr(xsq), *cs, *outs, *tail)
     _check(rc, "svg_kmeans_loop")
     return labels, cent, counts, n_it, sorted_idx
+
+
+def kmeans_stepped_workspace_bytes(B: int, N: int, K: int, D: int, group: int) -> int:
+    return int(load().svg_kmeans_stepped_workspace_bytes(B, N, K, D, group))
+
+
+def kmeans_stepped_iterate(x: torch.Tensor, c_init: torch.Tensor, c_work_a: torch.Tensor, c_work_b: torch.Tensor, it: int,
+                           maxima: torch.Tensor, group: int, ws: torch.Tensor) -> None:
+    """svg_kmeans_stepped_iterate on the caller's buffers (the allocating side: svg/_kmeans_stepped.py KmeansSteppedSide).  x [B, N, D]:
+    rows of a batch contiguous, batches x.stride(0) elements apart; maxima float32 [B // group], written."""
+    _dev(c_init, c_work_a, c_work_b, maxima)
+    _gpu(x, ws)
+    B, N, D = x.shape
+    K = c_init.shape[1]
+    assert x.stride(2) == 1 and x.stride(1) == D and c_init.shape == c_work_a.shape == c_work_b.shape == (B, K, D)
+    assert c_init.dtype == c_work_a.dtype == c_work_b.dtype == x.dtype
+    _f32_vector("kmeans_stepped_iterate(maxima)", maxima, B // group)
+    _check(load().svg_kmeans_stepped_iterate(x.data_ptr(), int(x.stride(0)), c_init.data_ptr(), c_work_a.data_ptr(), c_work_b.data_ptr(),
+                                             int(it), maxima.data_ptr(), B, N, K, D, _dtype_code(x), int(group), ws.data_ptr(), ws.numel(),
+                                             _stream()), "svg_kmeans_stepped_iterate")
+
+
+def kmeans_stepped_commit(maxima: torch.Tensor, labels: torch.Tensor, counts: torch.Tensor, sorted_idx: torch.Tensor, it: int, tol: float,
+                          group: int, ws: torch.Tensor) -> None:
+    """svg_kmeans_stepped_commit: the stopping rule of iteration `it` from whatever maxima [B // group] holds; labels / sorted_idx int32
+    [B, N] and counts int32 [B, K] take the iteration's results for the groups still running."""
+    _dev(maxima, labels, counts, sorted_idx)
+    _gpu(ws)
+    (B, N), K = labels.shape, counts.shape[1]
+    assert labels.dtype == counts.dtype == sorted_idx.dtype == torch.int32 and sorted_idx.shape == (B, N) and counts.shape == (B, K)
+    _f32_vector("kmeans_stepped_commit(maxima)", maxima, B // group)
+    _check(load().svg_kmeans_stepped_commit(maxima.data_ptr(), labels.data_ptr(), counts.data_ptr(), sorted_idx.data_ptr(), int(it),
+                                            float(tol), B, N, K, int(group), ws.data_ptr(), ws.numel(), _stream()), "svg_kmeans_stepped_commit")
+
+
+def kmeans_stepped_finish(c_init: torch.Tensor, c_work_a: torch.Tensor, c_work_b: torch.Tensor, centroids_out: torch.Tensor,
+                          n_iters: torch.Tensor, group: int, ws: torch.Tensor) -> None:
+    """svg_kmeans_stepped_finish: every group's centroids [B, K, D] from the buffer its loop ended on, n_iters int32 [B // group]"""
+    _dev(c_init, c_work_a, c_work_b, centroids_out, n_iters)
+    _gpu(ws)
+    B, K, D = c_init.shape
+    assert c_work_a.shape == c_work_b.shape == centroids_out.shape == (B, K, D) and centroids_out.dtype == c_init.dtype
+    assert n_iters.dtype == torch.int32 and n_iters.numel() == B // group
+    _check(load().svg_kmeans_stepped_finish(c_init.data_ptr(), c_work_a.data_ptr(), c_work_b.data_ptr(), centroids_out.data_ptr(),
+                                            n_iters.data_ptr(), B, K, D, _dtype_code(c_init), int(group), ws.data_ptr(), ws.numel(),
+                                            _stream()), "svg_kmeans_stepped_finish")
 
 
 def identify_dynamic_map(qc: torch.Tensor, kc: torch.Tensor, k_sizes: torch.Tensor, top_p: float,

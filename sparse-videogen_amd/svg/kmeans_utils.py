@@ -17,6 +17,7 @@ from typing import Optional
 import torch
 
 from . import _native
+from ._kmeans_stepped import KmeansSteppedSide
 from .timer import time_logging_decorator
 
 
@@ -51,6 +52,14 @@ class KMeansState:
 # the other workspaces (svg._native.WorkspaceCache) — two streams on one shape never share a KMeansState
 _STATE_CACHE = _native.WorkspaceCache()
 _LOOP_WORK = _native._KMEANS_WS   # scratch of svg_kmeans_loop per (B, N, K, D, dtype, device, stream), bounded (svg._native.WorkspaceCache)
+
+# A device-side stopping rule with a shift_reduce (the head-sharded layer-call: an all-reduce(MAX) between the iterations) runs
+#   True:  the library's loop in steps (svg_kmeans_stepped_*, lloyd_stepped below): per iteration the iteration's launches, one launch for the
+#          group maxima, the reduce, one commit launch; the q side and the k side of a layer-call in lock-step under ONE reduce;
+#   False: the torch statement lloyd_device_rule on svg_kmeans_iter: about a dozen framework launches per iteration and side, one reduce each.
+# The same bits either way (tests/test_gpu_kmeans_stepped.py).  The default follows the A/B of tools/ab_kmeans_stepped.py by the rule of
+# on only if every case is won by more than 3 x the spread of the torch-statement side (profiles/kmeans_stepped_ab.jsonl).
+STEPPED_LOOP_UNDER_SHARDS = True
 
 
 @time_logging_decorator("Level 4 - batch kmeans euclid")
@@ -89,12 +98,13 @@ def batch_kmeans_Euclid(x, n_clusters, max_iters=100, tol=1e-4, init_centroids=N
         group = int(group)
         assert group >= 1 and B % group == 0, f"batch_kmeans_Euclid: group = {group} must divide B = {B}"
     loop_in_library = not check_every and shift_reduce is None and not verbose
+    stepped = not check_every and shift_reduce is not None and not verbose and STEPPED_LOOP_UNDER_SHARDS   # (reads views in place as well)
     # (the library loop reads batches that lie further apart than N * D in place — svg_kmeans_loop_strided: the video tokens of a
     #  [H, S, D] tensor with text rows behind them; every other path takes the contiguous copy the reference makes)
-    if not (loop_in_library and x.dim() == 3 and x.stride(2) == 1 and x.stride(1) == D and x.stride(0) >= N * D):
+    if not ((loop_in_library or stepped) and x.dim() == 3 and x.stride(2) == 1 and x.stride(1) == D and x.stride(0) >= N * D):
         x = x.contiguous()
     st = None
-    if not loop_in_library:     # (the svg_kmeans_loop path keeps its own scratch: no KMeansState for it)
+    if not (loop_in_library or stepped):     # (the svg_kmeans_loop / stepped paths keep their own scratch: no KMeansState for them)
         key = _native.WorkspaceCache.key(B, N, n_clusters, D, x.dtype, device=x.device)
         st = _STATE_CACHE.get(key)
         if st is None:
@@ -128,6 +138,14 @@ def batch_kmeans_Euclid(x, n_clusters, max_iters=100, tol=1e-4, init_centroids=N
         # device — the same result as the torch statement below (kept for the sharded path, whose stopping rule needs an all-reduce
         # between the iterations), without its ~10 framework launches per iteration
         labels_r, cent_r, counts_r, n_r, sorted_r = _native.kmeans_loop(x, xsq, c_in, max_iters, tol, work=_LOOP_WORK, group=group)
+        out = (labels_r.to(torch.int64), cent_r, counts_r, n_r.to(torch.int64))
+        return out + (sorted_r,) if return_sorted_indices else out
+    if stepped:
+        # the same loop in steps, the reduce between an iteration and its commit: one side, its maxima the whole vector.  (group None: the
+        # reduce sees the 0-dim maximum, as under lloyd_device_rule)
+        side = KmeansSteppedSide(x, c_in, tol, group=group)
+        red = shift_reduce if group is not None else (lambda t: shift_reduce(t.view(())))
+        (labels_r, cent_r, counts_r, n_r, sorted_r), = lloyd_stepped([side], side.maxima, max_iters, shift_reduce=red)
         out = (labels_r.to(torch.int64), cent_r, counts_r, n_r.to(torch.int64))
         return out + (sorted_r,) if return_sorted_indices else out
 
@@ -187,6 +205,34 @@ def lloyd_device_rule(step, c_in, max_iters, tol, group=None, shift_reduce=None,
         if check_every and (it + 1) % check_every == 0 and bool(stopped.all()):
             break
     return labels_r, cent_r, counts_r, sorted_r, n_r
+
+
+def lloyd_stepped(sides, maxima, max_iters, shift_reduce=None, beside=None):
+    """The stepped twin of lloyd_device_rule: one or more Lloyd loops ("sides": the q side and the k side of a layer-call) in lock-step
+    under ONE shift_reduce per iteration.  Device-agnostic.  A side has iterate(it) — run iteration `it` and write the side's group maxima
+    into ITS slice of `maxima` —, commit(it) — apply `maximum < tol` per group to whatever its slice holds by then, keep the iteration's
+    labels / counts / sorted indices for the groups still running — and finish() -> its results (svg._kmeans_stepped.KmeansSteppedSide: (labels,
+    centroids, counts, n_iters, sorted indices)).  maxima: float [sum of the sides' G]; the sides were built on consecutive slices of it, so
+    nothing is concatenated.  Per iteration: every side's iterate, shift_reduce(maxima) (in place, or a tensor that is copied back), every
+    side's commit.  An element-wise reduce (MAX over ranks) keeps every side's and every group's rule its own, so each side's result is what a
+    loop of its own under the same reduce gives.
+    beside: None, or a callable taking the list of the sides' iterate calls of one iteration: it runs them all (next to each other, where
+    it can) and returns with their work ordered in front of whatever is launched next; the reduce and the commits are issued after it, by
+    this function, in the same order on every rank.  -> [side.finish() for side in sides]"""
+    for it in range(max_iters):
+        runs = [(lambda s=s: s.iterate(it)) for s in sides]
+        if beside is None:
+            for f in runs:
+                f()
+        else:
+            beside(runs)
+        if shift_reduce is not None:
+            r = shift_reduce(maxima)
+            if r is not None and r.data_ptr() != maxima.data_ptr():
+                maxima.copy_(r.reshape(maxima.shape))
+        for s in sides:
+            s.commit(it)
+    return [s.finish() for s in sides]
 
 
 @time_logging_decorator("Level 4 - weighted softmax")

@@ -19,6 +19,8 @@ import torch.nn.functional as F
 
 from .. import _native
 from .. import distributed as _dist
+from .. import kmeans_utils as _kmeans_utils
+from .._kmeans_stepped import KmeansSteppedSide
 from ..kmeans_utils import batch_kmeans_Euclid, density_calculation, identify_dynamic_map
 from ..timer import time_logging_decorator
 
@@ -938,7 +940,32 @@ def kmeans_clustering(store: CentroidStore, layer_idx: int, q_video, k_video, nu
         return batch_kmeans_Euclid(k_video.reshape(cfg * H, N, D), num_k_centroids, max_iters=iters, init_centroids=ki,
                                    return_sorted_indices=True, check_every=0, shift_reduce=red, group=grp)
 
-    if KMEANS_TWO_STREAMS and red is None and q_video.is_cuda:
+    if red is not None and _kmeans_utils.STEPPED_LOOP_UNDER_SHARDS and q_video.is_cuda:
+        # Sharded: the library's loop in steps (svg_kmeans_stepped_*), the two sides in lock-step.  Per iteration the q side's launches run on
+        # the side stream beside the k side's; the ONE all-reduce over both sides' group maxima and the two commits follow on the current
+        # stream, in the same order on every rank.  The element-wise MAX keeps each side's and each group's rule its own: the bits of the two
+        # separate loops of the switch-off path below.
+        xq, xk = q_video.reshape(cfg * H, N, D), k_video.reshape(cfg * H, N, D)
+        G = 1 if grp is None else cfg   # (1e-4 below: the tol the loops of the other paths run with, batch_kmeans_Euclid's default)
+        maxima = _native.empty((2 * G,), dtype=torch.float32, device=q_video.device)
+        sides = [KmeansSteppedSide(xq, qi.reshape(cfg * H, num_q_centroids, D).contiguous(), 1e-4, group=grp, maxima=maxima[:G]),
+                 KmeansSteppedSide(xk, ki.reshape(cfg * H, num_k_centroids, D).contiguous(), 1e-4, group=grp, maxima=maxima[G:])]
+        beside = None
+        if KMEANS_TWO_STREAMS:
+            cur = torch.cuda.current_stream(q_video.device)
+            side = _side_stream(q_video.device)
+
+            def beside(runs):   # (every tensor of the q side is allocated on the current stream and outlives the last join)
+                side.wait_stream(cur)
+                with torch.cuda.stream(side):
+                    runs[0]()
+                runs[1]()
+                cur.wait_stream(side)
+
+        (ql, qc, qs, qit, qidx), (kl, kc, ks, kit, kidx) = (
+            (lab.to(torch.int64), cent, cnt, n_it.to(torch.int64), srt)
+            for lab, cent, cnt, n_it, srt in _kmeans_utils.lloyd_stepped(sides, maxima, iters, shift_reduce=red, beside=beside))
+    elif KMEANS_TWO_STREAMS and red is None and q_video.is_cuda:
         # The two Lloyd loops are independent until the block map: the q side runs on a side stream beside the k side, so that the
         # HBM-bound update / sort / commit launches of one side share the chip with the MFMA-bound assignment of the other
         # (Wan 2.1 720p: 3.5 instead of 3.9 - 4.1 ms per layer-call, 86 instead of 99 ms for the 50-iteration init; bit-identical results —
@@ -1015,9 +1042,10 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
     V, ctx = geo.video_length, geo.context_length
     q, k = q.contiguous(), k.contiguous()   # (the k-means reads them as [H, N, D]; v may stay a strided view: only the attention kernel reads it)
     # the video tokens as VIEWS when the loop runs inside the library (svg_kmeans_loop[_grouped]_strided reads heads S * D apart in place:
-    # the cfg * H heads of a contiguous [cfg, H, S, D] are uniformly S * D apart); the head-sharded path (torch statement of the loop,
-    # all-reduced stopping rule) takes the copies the reference makes
-    in_place = ctx and _head_shard is None and not _dist.active()
+    # the cfg * H heads of a contiguous [cfg, H, S, D] are uniformly S * D apart), and when a shard's loop runs in steps
+    # (svg_kmeans_stepped_iterate reads the same views); the torch statement of the loop (sharded, STEPPED_LOOP_UNDER_SHARDS off) takes the
+    # copies the reference makes
+    in_place = ctx and ((_head_shard is None and not _dist.active()) or (_head_shard is not None and _kmeans_utils.STEPPED_LOOP_UNDER_SHARDS))
     qv = (q[:, :, :V] if in_place else q[:, :, :V].contiguous()) if ctx else q
     kv = (k[:, :, :V] if in_place else k[:, :, :V].contiguous()) if ctx else k
     with time_logging_decorator("Level 3 - semantic aware permutation"):

@@ -9,7 +9,9 @@ printed (A, B, A again: the third column shows the drift of the box).
   vb   : svg_varblock_attention_fp8 on the production-size SVG2 cases of tests/test_gpu_fullsize_svg2.py (fused permutation)
 --dynmap: ONLY the entries SVG2's per-head top-p shares kernels with — svg_identify_dynamic_map in both kernel forms and
 svg_sample_dense_rows (o32 and lse) — called through ctypes handles of the two files, so that A may be a library from before the entries
-of include/svg_attn_adaptive_top_p.h existed (svg._native.load() types every table and refuses such a file)."""
+of include/svg_attn_adaptive_top_p.h existed (svg._native.load() types every table and refuses such a file).
+--kmeans-loop: ONLY svg_kmeans_loop and svg_kmeans_loop_grouped_strided, through ctypes handles of the two files for the same reason (A: a
+library from before include/svg_attn_kmeans_stepped.h, whose host steps those loops now share with the stepped entries)."""
 import sys
 from pathlib import Path
 
@@ -122,14 +124,63 @@ def dynmap_cases(dev):
     return ok
 
 
+def kmeans_loop_cases(dev):
+    """--kmeans-loop: svg_kmeans_loop and svg_kmeans_loop_grouped_strided of two library files, raw C calls on the same tensors — all five
+    results compared, poisoned outputs and workspaces"""
+    import ctypes
+
+    from tests.test_gpu_fullsize_svg2 import clustered
+
+    names = ("svg_kmeans_loop", "svg_kmeans_loop_grouped_strided", "svg_kmeans_loop_grouped_workspace_bytes")
+    libs = {}
+    for tag in ("A", "B"):
+        lib = ctypes.CDLL(LIBS[tag])
+        for name in names:
+            getattr(lib, name).restype, getattr(lib, name).argtypes = nat.SIGNATURES[name]
+        libs[tag] = lib
+    st = lambda: torch.cuda.current_stream().cuda_stream  # noqa: E731
+    gen = torch.Generator(device="cuda").manual_seed(3)
+    ok = True
+    # (heads, N, K, group, iterations, rows behind every batch): the 2-iteration stage of Wan 720p at both cluster counts, a grouped loop over a
+    # view with text rows behind the video tokens, and a loop long enough for groups to stop
+    for B, N, K, group, iters, pad in ((8, 75600, 1000, 8, 2, 0), (8, 75600, 300, 8, 2, 0), (6, 30000, 400, 3, 2, 256), (4, 20000, 64, 2, 12, 0)):
+        base = clustered(B, N + pad, 128, 64, gen)
+        x = base[:, :N]
+        init = x[:, :K].contiguous()
+        outs, ms = {}, {}
+        for tag in ("A", "B", "A2"):
+            lib = libs[tag[0]]
+            mk = lambda *s, dt=torch.int32: nat.poison_storage(torch.empty(*s, dtype=dt, device=dev))  # noqa: E731
+            lab, srt, cnt, n_it = mk(B, N), mk(B, N), mk(B, K), mk(B // group)
+            cent, ca, cb = (mk(B, K, 128, dt=x.dtype) for _ in range(3))
+            ws = mk(lib.svg_kmeans_loop_grouped_workspace_bytes(B, N, K, 128, group), dt=torch.uint8)
+            tail = (B, N, K, 128, 0)
+            if pad or group != B:
+                fn = lambda: lib.svg_kmeans_loop_grouped_strided(x.data_ptr(), x.stride(0), init.data_ptr(), ca.data_ptr(), cb.data_ptr(),  # noqa: E731
+                                                                 lab.data_ptr(), cnt.data_ptr(), srt.data_ptr(), cent.data_ptr(), n_it.data_ptr(),
+                                                                 *tail, group, iters, 1e-4, ws.data_ptr(), ws.numel(), st())
+            else:
+                fn = lambda: lib.svg_kmeans_loop(x.data_ptr(), None, init.data_ptr(), ca.data_ptr(), cb.data_ptr(), lab.data_ptr(),  # noqa: E731
+                                                 cnt.data_ptr(), srt.data_ptr(), cent.data_ptr(), n_it.data_ptr(), *tail, iters, 1e-4,
+                                                 ws.data_ptr(), ws.numel(), st())
+            assert fn() == 0
+            ms[tag], outs[tag] = timed(fn, 5), (lab, cnt, srt, cent.view(torch.int16), n_it)
+        same = all(torch.equal(a, b) for t in ("B", "A2") for a, b in zip(outs["A"], outs[t]))
+        print(f"k-means loop B={B} N={N} K={K} group={group} iterations={iters} batch stride {x.stride(0)}: A {ms['A']:.4f} ms  B {ms['B']:.4f} ms  "
+              f"A again {ms['A2']:.4f} ms   B/A {ms['B'] / (0.5 * (ms['A'] + ms['A2'])):.4f}   bit-identical (labels, counts, sorted, centroids, "
+              f"n_iters): {same}   n_iters {outs['B'][4].tolist()}", flush=True)
+        ok &= same
+    return ok
+
+
 def main():
     dev = torch.device("cuda", 0)
     LIBS["A"] = str(Path([a for a in sys.argv[1:] if not a.startswith("--")][0]).resolve())
     paths = [a for a in sys.argv[1:] if not a.startswith("--")]
     LIBS["B"] = str(Path(paths[1]).resolve()) if len(paths) > 1 else str(ROOT / "sparse-videogen_amd" / "lib" / "libsvgattn.so")
     print("A =", LIBS["A"], "\nB =", LIBS["B"])
-    if "--dynmap" in sys.argv:
-        ok = dynmap_cases(dev)
+    if "--dynmap" in sys.argv or "--kmeans-loop" in sys.argv:
+        ok = dynmap_cases(dev) if "--dynmap" in sys.argv else kmeans_loop_cases(dev)
         print("ALL BIT-IDENTICAL" if ok else "MISMATCH")
         return 0 if ok else 1
     ok = True
