@@ -71,7 +71,7 @@ __global__ __launch_bounds__(512, 2) void band_attn_pp2_frozen_kernel(typename B
 // The plain bf16 forms of this kernel, of the queue kernel and of the device-switched kernel run the overflow test of the max-free
 // softmax on every eighth tile and validate the q-tile after its loop (SPEC, attn_m16.h); fp16 and the pre-scaled forms do not.
 static __device__ unsigned g_band_replays;   // q-tiles that failed the validation and were replayed (svg_debug_band_replays)
-constexpr int kTailLds = 16;                 // bytes behind the stages: the queue's slot (two words), the word of the validation, one free
+constexpr int kTailLds = 16;                 // bytes behind the stages: the queue's slot (two words), the word of the validation, the block of a per-head queue item
 // One template for every form on the static mapping; the policy is the only thing that differs between the instantiations, and each
 // instantiation's listing is compared with the one it had as a kernel of its own (tools/asm_diff.py --pair, profiles/kernel_templates_asm_diff.txt).
 //   BandPolicy<T, 128, 8>                          svg_band_attention: the plain kernel
@@ -197,6 +197,137 @@ __global__ __launch_bounds__(512, 2) void band_attn_m16_per_head_switch_kernel(t
     if (!Pol::map_block(prm, head, qt)) return;
     if (Pol::per_head_band_of(prm, head) > prm.S) attn_body_m16<T, Pol, false, 1, false, true>(prm_wide, smem, nullptr, &g_band_replays);
     else attn_body_m16<T, Pol, false, 1, false, true>(prm, smem, nullptr, &g_band_replays);
+}
+// The per-head kernel as resident workgroups on the work queue (svg_band_attention_per_head_queue_lse,
+// include/svg_attn_band_per_head_queue.h): the loop, the slot and the replay hand-shake of band_attn_m16_queue_kernel, restated here with the
+// policy visible to it for the reason given there.  The queue is the one of prm — the hint's block, built through its BandLsePolicy base — so
+// decode() yields (head, index) in prm's numbering, the pairs map_block yields under the static mapping.  A head on the wide block takes the
+// index as its q-tile; an index behind its last one is no work, and lane 0 resolves that inside its take loop (one uniform load of the
+// head's band, a compare, the next take), so the workgroup only ever sees real work items and the barriers are those of the plain queue
+// kernel.  Lane 0 publishes which block the head runs in the slot's free word (0: prm, 1: prm_wide, 2: prm_alt).
+// The blocks are kernel arguments as they are, and the q-tile's one is picked BY ADDRESS in the kernarg segment, not by branch: inside the
+// loop a copy of the tile body per block keeps every block's scalars live across it — 284 (bf16) / 240 (fp16) bytes of scratch per lane
+// here and 496 / 432 with the device switch —, where one body on the block at slot[3] * sizeof(Params) is the plain queue kernel's loop
+// with its block read through a pointer: no scratch (profiles/adaptive_band_queue_kernel_stats.txt).  The explicit arguments of a kernel
+// lie in its kernarg segment from offset 0 in their order at their natural alignment, so the leading blocks are an array there.
+template <typename P>
+static __device__ __forceinline__ const P& kernarg_block(int i) {
+    static_assert(sizeof(P) % 8 == 0 && alignof(P) == 8, "the leading blocks of the arguments lie back to back");
+#if defined(__HIP_DEVICE_COMPILE__)
+    return ((const __attribute__((address_space(4))) P*)__builtin_amdgcn_kernarg_segment_ptr())[i];
+#else
+    const P* const none = nullptr;   // (the host pass only parses the kernels)
+    return none[i];
+#endif
+}
+template <typename T>
+__global__ __launch_bounds__(512, 2) void band_attn_m16_per_head_queue_kernel(typename BandPerHeadLsePolicy<T>::Params prm,
+                                                                              typename BandPerHeadLsePolicy<T>::Params prm_wide,
+                                                                              BandQueue qd) {
+    using Pol = BandPerHeadLsePolicy<T>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int* const slot = (int*)(smem + attn_m16_lds_bytes());   // (head, q-tile) of the next work item, the word of the validation, the block
+    constexpr bool kSpec = std::is_same_v<T, __bf16>;
+    int dry = 0;
+    if constexpr (kSpec) {
+        if (threadIdx.x == 0) slot[2] = 0;
+    }
+    for (;;) {
+        if (threadIdx.x == 0) {
+            bool fresh = true;
+            if constexpr (kSpec) {
+                fresh = __builtin_amdgcn_readfirstlane(slot[2]) != 1;   // (a scalar: one lane is active here)
+                slot[2] = fresh ? 0 : 2;
+            }
+            if (fresh) {
+                const int xcd = __builtin_amdgcn_s_getreg((31 << 11) | 20) & (kNumXCD - 1);   // HW_REG_XCC_ID
+                int head = -1, qt = 0, wide = 0;
+                for (;;) {
+                    const int w = qd.take(xcd, dry);
+                    if (w < 0) {
+                        head = -1;
+                        break;
+                    }
+                    qd.decode(w, head, qt);
+                    wide = Pol::per_head_band_of(prm, head) > prm.S;
+                    if (!wide || qt < prm_wide.nqt) break;   // (else: behind the wide head's last q-tile; prm_wide.nqt <= prm.nqt, checked on the host)
+                }
+                slot[0] = head, slot[1] = qt, slot[3] = wide;
+            }
+        }
+        __syncthreads();   // (what this barrier orders: band_attn_m16_queue_kernel)
+        const int head = __builtin_amdgcn_readfirstlane(slot[0]), qt = __builtin_amdgcn_readfirstlane(slot[1]);
+        if (head < 0) break;
+        const typename Pol::Params& p = kernarg_block<typename Pol::Params>(__builtin_amdgcn_readfirstlane(slot[3]));
+        typename Pol::Ctx ctx;
+        Pol::init_tile(p, ctx, head, qt);
+        if constexpr (kSpec) {
+            const int check_mask = __builtin_amdgcn_readfirstlane(slot[2]) == 2 ? 0 : kCheckEvery - 1;
+            attn_m16_tile<T, Pol, false, 1, false, true>(p, ctx, smem, check_mask, &g_band_replays);
+        } else {
+            attn_m16_tile<T, Pol, false, 1, false>(p, ctx, smem);
+        }
+    }
+    if (threadIdx.x == 0) qd.leave(gridDim.x);
+}
+// ... with the device switch in front (svg_band_attention_switch_per_head_queue_lse): `flag[0] != 0` selects the alternate mask's queue and
+// block for the whole launch — no band vector, no head flags, nothing dropped.  One counter block: one descriptor is live per launch.
+template <typename T>
+__global__ __launch_bounds__(512, 2) void band_attn_m16_per_head_switch_queue_kernel(typename BandPerHeadLsePolicy<T>::Params prm,
+                                                                                     typename BandPerHeadLsePolicy<T>::Params prm_wide,
+                                                                                     typename BandPerHeadLsePolicy<T>::Params prm_alt,
+                                                                                     const int32_t* __restrict__ flag, BandQueue qd,
+                                                                                     BandQueue qd_alt) {
+    using Pol = BandPerHeadLsePolicy<T>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int* const slot = (int*)(smem + attn_m16_lds_bytes());
+    constexpr bool kSpec = std::is_same_v<T, __bf16>;
+    int dry = 0;
+    if constexpr (kSpec) {
+        if (threadIdx.x == 0) slot[2] = 0;
+    }
+    for (;;) {
+        if (threadIdx.x == 0) {
+            bool fresh = true;
+            if constexpr (kSpec) {
+                fresh = __builtin_amdgcn_readfirstlane(slot[2]) != 1;
+                slot[2] = fresh ? 0 : 2;
+            }
+            if (fresh) {
+                const int xcd = __builtin_amdgcn_s_getreg((31 << 11) | 20) & (kNumXCD - 1);   // HW_REG_XCC_ID
+                int head = -1, qt = 0, sel = 2;
+                if (flag[0] != 0) {
+                    const int w = qd_alt.take(xcd, dry);
+                    if (w >= 0) qd_alt.decode(w, head, qt);
+                } else {
+                    for (;;) {
+                        const int w = qd.take(xcd, dry);
+                        if (w < 0) {
+                            head = -1;
+                            break;
+                        }
+                        qd.decode(w, head, qt);
+                        sel = Pol::per_head_band_of(prm, head) > prm.S;
+                        if (!sel || qt < prm_wide.nqt) break;
+                    }
+                }
+                slot[0] = head, slot[1] = qt, slot[3] = sel;
+            }
+        }
+        __syncthreads();
+        const int head = __builtin_amdgcn_readfirstlane(slot[0]), qt = __builtin_amdgcn_readfirstlane(slot[1]);
+        if (head < 0) break;
+        const typename Pol::Params& p = kernarg_block<typename Pol::Params>(__builtin_amdgcn_readfirstlane(slot[3]));
+        typename Pol::Ctx ctx;
+        Pol::init_tile(p, ctx, head, qt);
+        if constexpr (kSpec) {
+            const int check_mask = __builtin_amdgcn_readfirstlane(slot[2]) == 2 ? 0 : kCheckEvery - 1;
+            attn_m16_tile<T, Pol, false, 1, false, true>(p, ctx, smem, check_mask, &g_band_replays);
+        } else {
+            attn_m16_tile<T, Pol, false, 1, false>(p, ctx, smem);
+        }
+    }
+    if (threadIdx.x == 0) qd.leave(gridDim.x);
 }
 // the same for q that carries sm_scale * log2(e) (svg_band_attention_prescaled): no scale-and-shift per score
 template <typename T, int D>
@@ -830,7 +961,7 @@ extern "C" int svg_band_attention_switch_lse_f32(const void* q, const void* k, c
 static int band_per_head_run(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S, int32_t D,
                              int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const svg_band_mask_t* alt_mask,
                              const int32_t* use_alt_flag, const int32_t* band, const svg_perm_desc_t* perm,
-                             const svg_attn_layout_t* layout, void* stream) {
+                             const svg_attn_layout_t* layout, void* stream, bool queue = false) {
     int rc = band_check_args(q, k, v, o, BH, S, D, mask, perm);
     if (rc == SVG_OK && alt_mask) rc = check_band_mask(S, alt_mask, nullptr);
     if (rc != SVG_OK) return rc;
@@ -859,8 +990,27 @@ static int band_per_head_run(const void* q, const void* k, const void* v, void* 
             if (w.nqt > p.nqt) return SVG_ERR_LAUNCH;   // (fewer cuts never make more q-tiles: band_row_regions)
             w.map_nqt = p.map_nqt, w.map_n_heavy = p.map_n_heavy, w.map_heavy_lo = p.map_heavy_lo;   // one mapping for both blocks
             const int lds = attn_m16_lds_bytes() + kTailLds;
+            typename Pol::Params a{};
+            if (use_alt_flag) a = params(alt_mask, alt_mask->band, nullptr, nullptr);
+            // queue: resident workgroups where launch_band_queue would launch them (include/svg_attn_band_per_head_queue.h).  The queues are
+            // built through the LSE base of the blocks: the per-head Ctx carries a band kv_schedule would read and no host sets.
+            if (queue) {
+                int n_cu = 0;
+                int32_t* const block = band_queue_block(st, n_cu);
+                const int cap = band_queue_cap();
+                const int items = (use_alt_flag ? std::max(p.nqt, a.nqt) : p.nqt) * BH;
+                if (block && !(items <= n_cu && cap == 0)) {
+                    BandQueue qd = make_band_queue<BandLsePolicy<T>>(p);
+                    qd.ctr = block;
+                    int n_wg = std::min(items, n_cu);
+                    if (cap > 0) n_wg = std::min(n_wg, cap);
+                    if (!use_alt_flag) return launch_attn(band_attn_m16_per_head_queue_kernel<T>, dim3(n_wg), 512, lds, st, p, w, qd);
+                    BandQueue qa = make_band_queue<BandLsePolicy<T>>(a);
+                    qa.ctr = block;
+                    return launch_attn(band_attn_m16_per_head_switch_queue_kernel<T>, dim3(n_wg), 512, lds, st, p, w, a, use_alt_flag, qd, qa);
+                }
+            }
             if (!use_alt_flag) return launch_attn(band_attn_m16_per_head_kernel<T>, dim3(p.nqt * BH), 512, lds, st, p, w);
-            const typename Pol::Params a = params(alt_mask, alt_mask->band, nullptr, nullptr);
             return launch_attn(band_attn_m16_per_head_switch_kernel<T>, dim3(std::max(p.nqt, a.nqt) * BH), 512, lds, st, p, w, a, use_alt_flag);
         }
     });
@@ -879,6 +1029,22 @@ extern "C" int svg_band_attention_switch_per_head_lse(const void* q, const void*
                                                       const svg_perm_desc_t* perm, const svg_attn_layout_t* layout, void* stream) {
     if (!lse || !band || !alt_mask || !use_alt) return SVG_ERR_BAD_ARG;
     return band_per_head_run(q, k, v, o, lse, BH, S, D, dtype, sm_scale, mask, alt_mask, use_alt, band, perm, layout, stream);
+}
+
+extern "C" int svg_band_attention_per_head_queue_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S,
+                                                     int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
+                                                     const int32_t* band, const svg_perm_desc_t* perm, const svg_attn_layout_t* layout,
+                                                     void* stream) {
+    if (!lse || !band) return SVG_ERR_BAD_ARG;
+    return band_per_head_run(q, k, v, o, lse, BH, S, D, dtype, sm_scale, mask, nullptr, nullptr, band, perm, layout, stream, true);
+}
+
+extern "C" int svg_band_attention_switch_per_head_queue_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH,
+                                                            int32_t S, int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
+                                                            const svg_band_mask_t* alt_mask, const int32_t* use_alt, const int32_t* band,
+                                                            const svg_perm_desc_t* perm, const svg_attn_layout_t* layout, void* stream) {
+    if (!lse || !band || !alt_mask || !use_alt) return SVG_ERR_BAD_ARG;
+    return band_per_head_run(q, k, v, o, lse, BH, S, D, dtype, sm_scale, mask, alt_mask, use_alt, band, perm, layout, stream, true);
 }
 
 // svg_band_groups_attention: the heads of one call in groups of consecutive heads, each under a mask (and an alternate mask) of its
@@ -1002,6 +1168,39 @@ extern "C" int32_t svg_band_queue_order(int32_t BH, int32_t S, const svg_band_ma
             Pol::Ctx c;
             Pol::kv_schedule(p, c, qt);
             out[3 * n] = x, out[3 * n + 1] = head * p.nqt + qt, out[3 * n + 2] = c.nT;
+            ++n;
+        }
+    return n;
+}
+
+// the order of the per-head queue launches on the host (include/svg_attn_band_per_head_queue.h): the blocks and queues band_per_head_run builds,
+// walked list by list, with the drop lane 0 of the kernels resolves
+extern "C" int32_t svg_band_per_head_queue_order(int32_t BH, int32_t S, const svg_band_mask_t* mask, const svg_band_mask_t* alt_mask,
+                                                 int32_t use_alt, const int32_t* band, int32_t* out, int32_t out_words) {
+    if (!mask || !band || BH <= 0 || S <= 0 || check_band_mask(S, mask, nullptr) != SVG_OK) return -1;
+    if (alt_mask && check_band_mask(S, alt_mask, nullptr) != SVG_OK) return -1;
+    if (use_alt && !alt_mask) return -1;
+    using Pol = svg::BandLsePolicy<__bf16>;
+    auto params = [&](const svg_band_mask_t* m, int band_of) {
+        svg_band_mask_t mm = *m;
+        mm.band = band_of;
+        return svg::make_band_params<Pol, __bf16>(nullptr, nullptr, nullptr, nullptr, BH, S, 1.f, &mm, nullptr);
+    };
+    const auto p = use_alt ? params(alt_mask, alt_mask->band) : params(mask, std::min(mask->band, S));
+    const auto w = params(mask, S + 1);
+    if (!use_alt && w.nqt > p.nqt) return -1;
+    const BandQueue qd = svg::make_band_queue<Pol>(p);
+    if (!out) return qd.n_items;
+    int n = 0;
+    for (int x = 0; x <= kNumXCD; ++x)   // the eight lists, then the tail
+        for (unsigned i = 0;; ++i) {
+            const int item = x < kNumXCD ? qd.item(x, i) : qd.tail_item(i);
+            if (item < 0) break;
+            if (4 * (int64_t)(n + 1) > out_words) return -1;
+            int head, qt;
+            qd.decode(item, head, qt);
+            const bool wide = !use_alt && std::min(std::max(band[head], 1), S + 1) > S;
+            out[4 * n] = x, out[4 * n + 1] = head, out[4 * n + 2] = wide && qt >= w.nqt ? -1 : qt, out[4 * n + 3] = use_alt ? 2 : (wide ? 1 : 0);
             ++n;
         }
     return n;

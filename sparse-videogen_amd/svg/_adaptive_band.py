@@ -27,29 +27,32 @@ def _checked(what: str, q, k, v, band, head_perm_flag, out):
 def band_attention_per_head(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: _native.BandMask, band: torch.Tensor,
                             sm_scale: Optional[float] = None, head_perm_flag: Optional[torch.Tensor] = None, vid0: int = 0,
                             num_frame: int = 1, frame_size: int = 1, out: Optional[torch.Tensor] = None, token_major_out: bool = False,
-                            return_lse: bool = True):
+                            return_lse: bool = True, work_queue: bool = False):
     """band_attention(return_lse=True) with one band per head: band is a device int32 tensor of BH elements, and head h runs `mask` with its
     band replaced by min(max(band[h], 1), S + 1) — the bits of that call (svg_band_attention_per_head_lse: head_dim 128, bf16 / fp16; anything
     else raises ValueError).  The band is read on the device and never written.  -> (o, lse), or o alone with return_lse=False (the same
-    launch)."""
+    launch).  work_queue=True: the same bits from resident workgroups on the work queue (svg_band_attention_per_head_queue_lse,
+    include/svg_attn_band_per_head_queue.h)."""
     BH, S, D = _checked("band_attention_per_head", q, k, v, band, head_perm_flag, out)
     lib = _native.load()
     perm = _native._perm_arg(head_perm_flag, BH, vid0, num_frame, frame_size)
     lse = _native.empty(q.shape[:-1], dtype=torch.float32, device=q.device)   # (contiguous [BH, S] whatever the layout of q / o)
     p = _native._layout_plan(q, k, v, out=out, token_major_out=token_major_out)
-    rc = lib.svg_band_attention_per_head_lse(p.q.data_ptr(), p.k.data_ptr(), p.v.data_ptr(), p.o.data_ptr(), lse.data_ptr(), BH, S, D,
-                                             _native._dtype_code(q), _native._sm_scale(sm_scale, D), C.byref(mask), band.data_ptr(), perm,
-                                             p.lay, _native._stream())
-    _native._check(rc, "svg_band_attention_per_head_lse")
+    name = "svg_band_attention_per_head_queue_lse" if work_queue else "svg_band_attention_per_head_lse"
+    rc = getattr(lib, name)(p.q.data_ptr(), p.k.data_ptr(), p.v.data_ptr(), p.o.data_ptr(), lse.data_ptr(), BH, S, D, _native._dtype_code(q),
+                            _native._sm_scale(sm_scale, D), C.byref(mask), band.data_ptr(), perm, p.lay, _native._stream())
+    _native._check(rc, name)
     return (p.result(), lse) if return_lse else p.result()
 
 
 def band_attention_switch_per_head(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: _native.BandMask, alt_mask: _native.BandMask,
                                    use_alt_flag: torch.Tensor, band: torch.Tensor, sm_scale: Optional[float] = None,
                                    head_perm_flag: Optional[torch.Tensor] = None, vid0: int = 0, num_frame: int = 1, frame_size: int = 1,
-                                   out: Optional[torch.Tensor] = None, token_major_out: bool = False, return_lse: bool = True):
+                                   out: Optional[torch.Tensor] = None, token_major_out: bool = False, return_lse: bool = True,
+                                   work_queue: bool = False):
     """band_attention_switch(return_lse=True) with one band per head: `use_alt_flag` (int32 [1] on the GPU) != 0 runs `alt_mask` as it is,
-    without the head placement, and ignores `band`; otherwise band_attention_per_head (svg_band_attention_switch_per_head_lse)."""
+    without the head placement, and ignores `band`; otherwise band_attention_per_head (svg_band_attention_switch_per_head_lse).  work_queue=True: the same bits from
+    resident workgroups on the work queue (svg_band_attention_switch_per_head_queue_lse)."""
     BH, S, D = _checked("band_attention_switch_per_head", q, k, v, band, head_perm_flag, out)
     _native._dev(use_alt_flag)
     assert use_alt_flag.dtype == torch.int32 and use_alt_flag.numel() >= 1
@@ -57,9 +60,9 @@ def band_attention_switch_per_head(q: torch.Tensor, k: torch.Tensor, v: torch.Te
     perm = _native._perm_arg(head_perm_flag, BH, vid0, num_frame, frame_size)
     lse = _native.empty(q.shape[:-1], dtype=torch.float32, device=q.device)
     p = _native._layout_plan(q, k, v, out=out, token_major_out=token_major_out)
-    rc = lib.svg_band_attention_switch_per_head_lse(p.q.data_ptr(), p.k.data_ptr(), p.v.data_ptr(), p.o.data_ptr(), lse.data_ptr(), BH, S, D,
-                                                    _native._dtype_code(q), _native._sm_scale(sm_scale, D), C.byref(mask),
-                                                    C.byref(alt_mask), use_alt_flag.data_ptr(), band.data_ptr(), perm, p.lay,
-                                                    _native._stream())
-    _native._check(rc, "svg_band_attention_switch_per_head_lse")
+    name = "svg_band_attention_switch_per_head_queue_lse" if work_queue else "svg_band_attention_switch_per_head_lse"
+    rc = getattr(lib, name)(p.q.data_ptr(), p.k.data_ptr(), p.v.data_ptr(), p.o.data_ptr(), lse.data_ptr(), BH, S, D, _native._dtype_code(q),
+                            _native._sm_scale(sm_scale, D), C.byref(mask), C.byref(alt_mask), use_alt_flag.data_ptr(), band.data_ptr(), perm,
+                            p.lay, _native._stream())
+    _native._check(rc, name)
     return (p.result(), lse) if return_lse else p.result()

@@ -359,6 +359,15 @@ ADAPTIVE_BAND_ENTRIES = {
     "svg_band_width_update": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _F32, _F32, _F32, _F32, _I32, _I32, _I32, _VP, _VP, _VP, _VP]),
 }
 
+# include/svg_attn_band_per_head_queue.h: the two attention entries above as resident workgroups on the work queue — the arguments of their
+# static siblings — and the host statement of the order, in a table of its own (tests/test_band_per_head_queue_cpu.py; the wrappers of
+# svg/_adaptive_band.py take them with work_queue=True).  Named ..._ENTRIES for the reason given above.
+ADAPTIVE_BAND_QUEUE_ENTRIES = {
+    "svg_band_attention_per_head_queue_lse": ADAPTIVE_BAND_ENTRIES["svg_band_attention_per_head_lse"],
+    "svg_band_attention_switch_per_head_queue_lse": ADAPTIVE_BAND_ENTRIES["svg_band_attention_switch_per_head_lse"],
+    "svg_band_per_head_queue_order": (_I32, [_I32, _I32, C.POINTER(BandMask), C.POINTER(BandMask), _I32, _VP, _VP, _I32]),
+}
+
 
 # include/svg_attn_kmeans_stepped.h: the Lloyd loop of svg_kmeans_loop_grouped in steps — iterate hands the group maxima out, commit takes
 # them back —, in a table of its own for the same reason (tests/test_kmeans_stepped_cpu.py; bindings on the caller's buffers:
@@ -407,7 +416,8 @@ def load(strict: bool = True) -> Optional[C.CDLL]:
         for name, (res, args) in {**SIGNATURES, **SPARSE_LSE_SIGNATURES, **SPARSE_F32_SIGNATURES, **BAND_LSE_FORM_SIGNATURES,
                                    **BAND_WINDOW_SIGNATURES, **BAND_SHARD_SIGNATURES, **BAND_SHARD_SWITCH_SIGNATURES,
                                    **PROFILE_SHARD_SIGNATURES, **SAMPLE_ROWS_SIGNATURES, **SHARD_EXCHANGE_SIGNATURES,
-                                   **ADAPTIVE_TOP_P_SIGNATURES, **ADAPTIVE_BAND_ENTRIES, **KMEANS_STEPPED_SIGNATURES}.items():
+                                   **ADAPTIVE_TOP_P_SIGNATURES, **ADAPTIVE_BAND_ENTRIES, **ADAPTIVE_BAND_QUEUE_ENTRIES,
+                                   **KMEANS_STEPPED_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

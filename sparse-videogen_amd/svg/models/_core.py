@@ -87,6 +87,11 @@ LN2 = 0.6931471805599453   # sm_scale of a kernel that applies sm_scale * log2(e
 # path gathers contiguous head slices); anything else falls back to copies inside svg/_native.py.  False: every output is contiguous.
 TOKEN_MAJOR_IO = True
 
+# The per-head band launches of `adaptive_band` as resident workgroups on the work queue (include/svg_attn_band_per_head_queue.h): the same
+# bits, another mapping of q-tiles to workgroups.  Read at the adaptive branch of _svg1_layer_call, so every SVG1 processor with
+# adaptive_band set follows it.  Off: the static mapping (figures: DESIGN §3.1.3 "One band per head"; on a real model unmeasured).
+PER_HEAD_BAND_QUEUE = False
+
 
 # ---------------------------------------------------------------------------------------------------------------
 # Batches whose videos differ in their text length (HunyuanVideo: a list of prompts).  A length, or a mask built from one, may be given
@@ -562,11 +567,12 @@ def _svg1_layer_call(what: str, switched: bool, q, k, v, geo: Geometry, mask, pr
     if adaptive is not None:   # (fused, 16-bit, one mask for the batch, no sharding: refused above otherwise)
         from .. import _adaptive_band
 
+        qk = dict(work_queue=True) if PER_HEAD_BAND_QUEUE else {}   # (off: nothing new is passed)
         if switched:
             run = lambda band: _adaptive_band.band_attention_switch_per_head(q, k, v, mask, dense_mask, dense_flag, band,   # noqa: E731
-                                                                             token_major_out=TOKEN_MAJOR_IO, **pk)
+                                                                             token_major_out=TOKEN_MAJOR_IO, **pk, **qk)
         else:
-            run = lambda band: _adaptive_band.band_attention_per_head(q, k, v, mask, band, token_major_out=TOKEN_MAJOR_IO, **pk)   # noqa: E731
+            run = lambda band: _adaptive_band.band_attention_per_head(q, k, v, mask, band, token_major_out=TOKEN_MAJOR_IO, **pk, **qk)   # noqa: E731
         with timer:
             out = _adaptive_band_call(run, adaptive, band_store, layer_idx, mask, band_bounds, q, k, v, quality, **flag_kw)
         return (out[0], final_best(), out[1]) if return_lse else (out[0], final_best())

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B on one box, one process: what SVG1's per-head band costs and that time follows the bands.
 
-    python tools/ab_adaptive_band.py [--alternations 7] [--min-ms 300] [--out profiles/adaptive_band_ab.jsonl] [--tiny]
+    python tools/ab_adaptive_band.py [--alternations 7] [--min-ms 300] [--out profiles/adaptive_band_ab.jsonl] [--tiny] [--queue]
 
 The HunyuanVideo 720p layer-call of bench.py (24 heads, S = 119 056, F = 33, P = 3600, ctx = 256, prompt 64, sparsity 0.25, bf16, every second
 head token-major), all sides from the same library.
@@ -14,7 +14,17 @@ head token-major), all sides from the same library.
   (c) bands        the launch of (a) with every second head at half the band: time follows the bands.
 A warm-up of both sides, then `alternations` (at least 5) rounds of (A window, B window); a window is as many calls between two device
 events as make at least `min-ms` of work.  One JSON line per part, appended to --out.  Synthetic data; no claim about what per-head bands are
-worth on a real model.  --tiny: small shapes, two alternations (a rehearsal of the script, not a measurement)."""
+worth on a real model.  --tiny: small shapes, two alternations (a rehearsal of the script, not a measurement).
+
+--queue: instead of (a) - (c), the per-head launches on the work queue (include/svg_attn_band_per_head_queue.h, work_queue=True) against the
+statically mapped per-head entries of the same library — the parent's code, untouched (profiles/adaptive_band_queue_asm_diff.txt) —, appended
+to profiles/adaptive_band_queue_ab.jsonl unless --out says otherwise:
+  (q1) svg_band_attention_per_head_queue_lse against svg_band_attention_per_head_lse at (i) uniform bands, (ii) every second head at half
+       the band, (iii) bands spread linearly from a quarter of the mask's band to the mask's band over the heads;
+  (q2) svg_band_attention_switch_per_head_queue_lse against svg_band_attention_switch_per_head_lse at flag 0 and at flag 1, and at flag 1
+       also against svg_band_attention_switch_lse.
+Per row: ms, spread, ratio, same_bits, and the shader clock granted to each side's windows (nat.ClockProbe) where it can be read.  No
+threshold: the rows are figures to set beside 32.391 ms (static per-head, uniform) and 31.147 ms (plain queue, uniform) of DESIGN §3.1.3."""
 import argparse
 import json
 import math
@@ -54,13 +64,78 @@ def stats(w):
     return {"ms": round(sum(w) / len(w), 4), "windows": [round(x, 4) for x in w], "spread_ms": round(max(w) - min(w), 4)}
 
 
+def alternate_clocked(fns, alternations, min_ms, probe):
+    """alternate() with the granted shader clock of every window beside its ms (None where the probe's counters did not move)"""
+    for fn in list(fns) * 2:
+        fn()
+    torch.cuda.synchronize()
+    calls = [max(1, math.ceil(min_ms / max(window(fn, 1), 1e-3))) for fn in fns]
+    ws, mhz = [[] for _ in fns], [[] for _ in fns]
+    for _ in range(alternations):
+        for w, m, fn, c in zip(ws, mhz, fns, calls):
+            probe.start(max_ms=20000)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(c):
+                fn()
+            e1.record()
+            probe.arm_stop()
+            e1.synchronize()
+            m.append(probe.result())
+            w.append(e0.elapsed_time(e1) / c)
+    return ws, mhz, calls
+
+
+def queue_rows(a, nat, ab, q, k, v, mask, dense, pk, H, workload, alternations):
+    """the --queue rows: every pair is (static entry, queue entry) on the same inputs"""
+    dev = q.device
+    probe = nat.ClockProbe(dev)   # (one probe for the whole run: tools/ab_band_queue.py)
+    hint = mask.band
+    uniform = torch.full((H,), hint, dtype=torch.int32, device=dev)
+    halved = uniform.clone()
+    halved[1::2] = hint // 2
+    spread = torch.linspace(hint / 4, hint, H).round().to(torch.int32).to(dev)
+    flags = {f: torch.full((1,), f, dtype=torch.int32, device=dev) for f in (0, 1)}
+    recs = []
+
+    def row(metric, sides, extra):
+        out = {}
+        fns = [lambda n=n, f=f: out.__setitem__(n, f()) for n, f in sides]
+        ws, mhz, calls = alternate_clocked(fns, alternations, a.min_ms, probe)
+        st = {n: dict(stats(w), sclk_mhz=m) for (n, _), w, m in zip(sides, ws, mhz)}
+        base, new = sides[0][0], sides[-1][0]
+        rec = {"metric": metric, "workload": workload, "alternations": alternations, "calls_per_window": calls, **extra, **st,
+               f"{new}_minus_{base}_ms": round(st[new]["ms"] - st[base]["ms"], 4), f"{new}_over_{base}": round(st[new]["ms"] / st[base]["ms"], 4),
+               "queue_faster_in_every_alternation": bool(all(y < x for x, y in zip(ws[0], ws[-1]))),
+               "same_bits": bool(all(torch.equal(out[new][i], out[n][i]) for n, _ in sides[:-1] for i in (0, 1)))}
+        if len(sides) == 3:
+            mid = sides[1][0]
+            rec[f"{new}_over_{mid}"] = round(st[new]["ms"] / st[mid]["ms"], 4)
+        recs.append(rec)
+        print(json.dumps(rec), flush=True)
+
+    for name, band in (("uniform", uniform), ("every_second_head_half_band", halved), ("linear_quarter_to_full", spread)):
+        row("per_head_queue_vs_static", [("static", lambda b=band: ab.band_attention_per_head(q, k, v, mask, b, **pk)),
+                                         ("queue", lambda b=band: ab.band_attention_per_head(q, k, v, mask, b, work_queue=True, **pk))],
+            {"bands": name, "band_min_max": [int(band.min()), int(band.max())]})
+    for f in (0, 1):
+        sides = [("static", lambda f=f: ab.band_attention_switch_per_head(q, k, v, mask, dense, flags[f], uniform, **pk))]
+        if f:
+            sides.append(("switch_lse", lambda f=f: nat.band_attention_switch(q, k, v, mask, dense, flags[f], return_lse=True, **pk)))
+        sides.append(("queue", lambda f=f: ab.band_attention_switch_per_head(q, k, v, mask, dense, flags[f], uniform, work_queue=True, **pk)))
+        row("switch_per_head_queue_vs_static", sides, {"flag": f, "bands": "uniform"})
+    return recs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--alternations", type=int, default=7)
     ap.add_argument("--min-ms", type=float, default=300.0)
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "adaptive_band_ab.jsonl"))
+    ap.add_argument("--out", default="")
     ap.add_argument("--tiny", action="store_true")
+    ap.add_argument("--queue", action="store_true", help="the rows of the per-head work-queue entries instead of (a) - (c)")
     a = ap.parse_args()
+    a.out = a.out or str(ROOT / "profiles" / ("adaptive_band_queue_ab.jsonl" if a.queue else "adaptive_band_ab.jsonl"))
     from svg import _adaptive_band as ab
     from svg import _native as nat
     from svg.models import _core
@@ -81,6 +156,11 @@ def main():
     flag = torch.zeros(1, dtype=torch.int32, device=dev)
     pk = dict(head_perm_flag=best, vid0=0, num_frame=F_, frame_size=P_)
     workload = f"{'tiny' if a.tiny else 'hy720p'} cfg=1 H={H} D={D} S={S} band={mask.band} bf16, every second head token-major"
+    if a.queue:
+        recs = queue_rows(a, nat, ab, q, k, v, mask, dense, pk, H, workload, alternations)
+        with open(a.out, "a") as f:
+            f.write("".join(json.dumps(r) + "\n" for r in recs))
+        return
     recs = []
 
     # ---- (a) the launch forms, every band the mask's ----
