@@ -97,7 +97,7 @@ __global__ __launch_bounds__(512, 2) void band_attn_m16q_kernel(typename BandPol
     attn_body_m16<T, BandPolicy<T, 128, 8>, false, 1, true>(prm, smem, nullptr);
 }
 // The same two kernels as resident workgroups on a work queue (BandQueue, band_policy.h): min(work items, CUs) workgroups, each
-// running one q-tile after another until the queue is dry.  What band_dispatch launches for head_dim 128 when there are more q-tiles
+// running one q-tile after another until the queue is dry.  What band_run launches for head_dim 128 when there are more q-tiles
 // than compute units, unless the call counts completions (those rely on the head-major order of the static mapping) or no counter
 // block is to be had; the device-switched kernel below keeps the static mapping.  Per row the same keys in the same order with the same arithmetic: bit-identical output.
 // One template, and so one copy of the loop: the policy (BandPolicy<T, 128, 8>, plain and PRE; BandLsePolicy where svg_band_attention_lse takes
@@ -455,155 +455,226 @@ int32_t* svg::band_queue_block(hipStream_t st, int& n_cu) {
 
 int svg::band_queue_cap() { return g_queue_cap.load(std::memory_order_relaxed); }
 
-// the sizes a band launch can address (SVG_ERR_UNSUPPORTED beyond them)
-static int band_check_size(int32_t BH, int32_t S, int32_t D) {
-    if ((int64_t)BH * S * D >= (1ll << 40)) return SVG_ERR_UNSUPPORTED;
-    return check_rows(S, D);
+// The sizes a band launch can address (SVG_ERR_UNSUPPORTED beyond them), and the only place that states them.
+// (S >= 2^24 ought to be refused here for every form; that changes the contract and gets a pull request of its own.)
+static int band_check_size(const BandCall& c) {
+    if ((int64_t)c.BH * c.S * c.D >= (1ll << 40)) return SVG_ERR_UNSUPPORTED;
+    return check_rows(c.S, c.D);
 }
 
-// rows of a (checked) shard of the video `perm` describes
-static int band_shard_rows(const svg_band_shard_t* s, const svg_perm_desc_t* perm) { return perm->frame_size * s->n_frames + s->n_tail; }
-
-// pointers, mask, head permutation and sizes: the checks every svg_band_attention* entry shares
-static int band_check_args(const void* q, const void* k, const void* v, const void* o, int32_t BH, int32_t S, int32_t D,
-                           const svg_band_mask_t* mask, const svg_perm_desc_t* perm) {
-    if (!q || !k || !v || !o || !mask || BH <= 0 || S <= 0) return SVG_ERR_BAD_ARG;
-    if (const int rc = check_band_mask(S, mask, perm); rc != SVG_OK) return rc;
-    return band_check_size(BH, S, D);
-}
-
-// The 16x16x32 kernels of a single-mask launch: resident workgroups on a work queue (kern_q), or `kern` on the static mapping where the
-// call counts completions (`counts`), no counter block is to be had, or one round of workgroups covers the launch.
-template <typename Pol, typename KQ, typename K>
-static int launch_band_queue(KQ kern_q, K kern, const typename Pol::Params& p, int lds, bool counts, hipStream_t st) {
+// The queue decision of a launch of `items` work items on `st`: the counter block and the number of resident workgroups, or no block —
+// the static mapping — where none is to be had or one round of workgroups covers the launch.
+// (a launch of one round has nothing to balance, and a workgroup pays nine atomics to find the queue dry: 0.068 against
+//  0.064 ms on the 52 q-tiles of the benchmark's tiny workload)
+struct BandQueueLaunch {
+    int32_t* block;
+    int n_wg;
+};
+static BandQueueLaunch band_queue_decision(int items, hipStream_t st) {
     int n_cu = 0;
-    int32_t* const block = counts ? nullptr : band_queue_block(st, n_cu);
+    int32_t* const block = band_queue_block(st, n_cu);
     const int cap = band_queue_cap();
-    // (a launch of one round has nothing to balance, and a workgroup pays nine atomics to find the queue dry: 0.068 against
-    //  0.064 ms on the 52 q-tiles of the benchmark's tiny workload)
-    if (!block || (p.nqt * p.BH <= n_cu && cap == 0)) return launch_attn(kern, dim3(p.nqt * p.BH), 512, lds, st, p);
-    BandQueue qd = make_band_queue<Pol>(p);
-    qd.ctr = block;
-    int n_wg = std::min(qd.n_items, n_cu);
-    if (cap > 0) n_wg = std::min(n_wg, cap);
-    return launch_attn(kern_q, dim3(n_wg), 512, lds, st, p, qd);
+    if (!block || (items <= n_cu && cap == 0)) return {nullptr, 0};
+    const int n_wg = std::min(items, n_cu);
+    return {block, cap > 0 ? std::min(n_wg, cap) : n_wg};
 }
 
-// One launch of the 16x16x32 body on policy Pol, for every entry that takes it; `params(mask, perm)` builds a parameter block of the form.
-// The device switch (opts.use_alt) gets the blocks of both masks — the alternate one with `perm_alt` — and runs over the q-tiles of the
-// larger; a single mask goes to the work queue where the form has one (launch_band_queue), else to the static mapping over its q-tiles.
-template <typename T, typename Pol, bool PRE = false, typename F>
-static int launch_band_m16(F params, const svg_band_mask_t* mask, const svg_perm_desc_t* perm, const svg_perm_desc_t* perm_alt,
-                           const BandOpts& opts, hipStream_t st) {
+// the alternate call of a device switch: alt_mask, and no head permutation — a shard call keeps perm's geometry (in `pm`), without its flags
+static BandCall band_alt_call(const BandCall& c, svg_perm_desc_t& pm) {
+    BandCall b = c;
+    b.mask = c.alt_mask, b.perm = nullptr;
+    if (c.form == kBandShard) pm = *c.perm, pm.head_perm_flag = nullptr, b.perm = &pm;
+    return b;
+}
+
+// One launch of the 16x16x32 body on policy Pol, for every form that takes it.  The device switch (c.use_alt) gets the blocks of both masks
+// (band_alt_call) and runs over the q-tiles of the larger; a single mask goes to the work queue where the form has one and the call does
+// not count completions (band_queue_decision), else to the static mapping over its q-tiles.
+template <typename T, typename Pol, bool PRE = false>
+static int launch_band_m16(const BandCall& c) {
     // (only what is launched is instantiated: the window forms have no device switch; the fp32, window and shard forms have no queue)
-    constexpr bool kSwitch = !std::is_same_v<Pol, BandWindowLsePolicy<T>> && !std::is_same_v<Pol, BandWindowF32Policy<T>>;
+    constexpr bool kWindow = std::is_same_v<Pol, BandWindowLsePolicy<T>> || std::is_same_v<Pol, BandWindowF32Policy<T>>;
+    constexpr bool kShard = std::is_same_v<Pol, BandShardLsePolicy<T>> || std::is_same_v<Pol, BandShardF32Policy<T>>;
     constexpr bool kQueue = std::is_same_v<Pol, BandPolicy<T, 128, 8>> || std::is_same_v<Pol, BandLsePolicy<T>>;
+    auto params = [](const BandCall& b) {
+        if constexpr (kWindow) return make_band_window_params<Pol, T>(b);
+        else if constexpr (kShard) return make_band_shard_params<Pol, T>(b);
+        else return make_band_params<Pol, T>(b);
+    };
     const int lds = attn_m16_lds_bytes() + kTailLds;
-    const typename Pol::Params p = params(mask, perm);
-    if constexpr (kSwitch) {
-        if (opts.use_alt) {
-            const typename Pol::Params b = params(opts.alt_mask, perm_alt);
-            return launch_attn(band_attn_m16_switch_kernel<T, Pol, PRE>, dim3(std::max(p.nqt, b.nqt) * p.BH), 512, lds, st, p, b, opts.use_alt);
+    const hipStream_t st = c.stream;
+    const typename Pol::Params p = params(c);
+    if constexpr (!kWindow) {
+        if (c.use_alt) {
+            svg_perm_desc_t pm;
+            const typename Pol::Params b = params(band_alt_call(c, pm));
+            return launch_attn(band_attn_m16_switch_kernel<T, Pol, PRE>, dim3(std::max(p.nqt, b.nqt) * p.BH), 512, lds, st, p, b, c.use_alt);
         }
     }
     auto kern = [] {
         if constexpr (PRE) return band_attn_m16q_kernel<T>;
         else return band_attn_m16_kernel<T, Pol>;
     }();
-    if constexpr (kQueue) return launch_band_queue<Pol>(band_attn_m16_queue_kernel<T, Pol, PRE>, kern, p, lds, opts.done != nullptr, st);
-    else return launch_attn(kern, dim3(p.nqt * p.BH), 512, lds, st, p);
+    if constexpr (kQueue) {
+        if (const BandQueueLaunch ql = c.done ? BandQueueLaunch{nullptr, 0} : band_queue_decision(p.nqt * p.BH, st); ql.block) {
+            BandQueue qd = make_band_queue<Pol>(p);
+            qd.ctr = ql.block;
+            return launch_attn(band_attn_m16_queue_kernel<T, Pol, PRE>, dim3(ql.n_wg), 512, lds, st, p, qd);
+        }
+    }
+    return launch_attn(kern, dim3(p.nqt * p.BH), 512, lds, st, p);
+}
+
+// One band per head (include/svg_attn_adaptive_band.h): the per-head kernels.  The parameter block is built for a band that cuts the full
+// rows out (min(mask->band, S)) and once more for one that does not (S + 1); the kernel picks per head, and the policy reads the head's
+// band where the block has the mask's.
+template <typename T>
+static int launch_band_per_head(const BandCall& c) {
+    using Pol = BandPerHeadLsePolicy<T>;
+    const int S = c.S, BH = c.BH;
+    const hipStream_t st = c.stream;
+    auto params = [&](const svg_band_mask_t* m, int band_of, const svg_perm_desc_t* pm, const int32_t* band_vec) {
+        svg_band_mask_t mm = *m;
+        mm.band = band_of;
+        BandCall b = c;
+        b.mask = &mm, b.perm = pm;
+        typename Pol::Params p = make_band_params<Pol, T>(b);
+        p.band_vec = band_vec;
+        p.map_nqt = p.nqt, p.map_n_heavy = p.n_heavy, p.map_heavy_lo = p.heavy_lo;
+        return p;
+    };
+    const typename Pol::Params p = params(c.mask, std::min(c.mask->band, S), c.perm, c.band);
+    typename Pol::Params w = params(c.mask, S + 1, c.perm, c.band);
+    if (w.nqt > p.nqt) return SVG_ERR_LAUNCH;   // (fewer cuts never make more q-tiles: band_row_regions)
+    w.map_nqt = p.map_nqt, w.map_n_heavy = p.map_n_heavy, w.map_heavy_lo = p.map_heavy_lo;   // one mapping for both blocks
+    const int lds = attn_m16_lds_bytes() + kTailLds;
+    typename Pol::Params a{};
+    if (c.use_alt) a = params(c.alt_mask, c.alt_mask->band, nullptr, nullptr);
+    const int items = (c.use_alt ? std::max(p.nqt, a.nqt) : p.nqt) * BH;
+    // queue: resident workgroups where a single-mask launch would run them (include/svg_attn_band_per_head_queue.h).  The queues are
+    // built through the LSE base of the blocks: the per-head Ctx carries a band kv_schedule would read and no host sets.
+    if (const BandQueueLaunch ql = c.queue ? band_queue_decision(items, st) : BandQueueLaunch{nullptr, 0}; ql.block) {
+        BandQueue qd = make_band_queue<BandLsePolicy<T>>(p);
+        qd.ctr = ql.block;
+        if (!c.use_alt) return launch_attn(band_attn_m16_per_head_queue_kernel<T>, dim3(ql.n_wg), 512, lds, st, p, w, qd);
+        BandQueue qa = make_band_queue<BandLsePolicy<T>>(a);
+        qa.ctr = ql.block;
+        return launch_attn(band_attn_m16_per_head_switch_queue_kernel<T>, dim3(ql.n_wg), 512, lds, st, p, w, a, c.use_alt, qd, qa);
+    }
+    if (!c.use_alt) return launch_attn(band_attn_m16_per_head_kernel<T>, dim3(p.nqt * BH), 512, lds, st, p, w);
+    return launch_attn(band_attn_m16_per_head_switch_kernel<T>, dim3(items), 512, lds, st, p, w, a, c.use_alt);
 }
 
 // The fp32 entries: o32 travels in the place of o through the null checks and the layout checks of the 16-bit entries.  With a layout q
-// stands in and the o member of the layout, which these entries do not read, takes q's strides (`abi` holds that copy; `layout` then
-// points to it); without one, o32 itself.
-static void* band_f32_stand_in(const void* q, float* o32, const svg_attn_layout_t*& layout, svg_attn_layout_t& abi) {
-    if (!layout) return o32;
-    abi = *layout, abi.o = abi.q, layout = &abi;
-    return const_cast<void*>(q);
+// stands in and the o member of the layout, which these entries do not read, takes q's strides (`abi` holds that copy, which is the
+// layout to check); without one, o32 itself.
+static const svg_attn_layout_t* band_f32_stand_in(BandCall& c, svg_attn_layout_t& abi) {
+    c.o = c.layout ? const_cast<void*>(c.q) : c.o32;
+    if (!c.layout) return nullptr;
+    abi = *c.layout, abi.o = abi.q;
+    return &abi;
 }
 
-// Every svg_band_attention* entry, after the null checks of its own arguments: validation, then the kernel of `variant` for
-// (dtype, D).  opts carries what the entry adds: pre-scaled q, completion counters (`done_words` of them), the device switch (its
-// alternate mask is checked here too) and strided tensors (opts.strided: `layout` describes them).
-static int band_dispatch(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t S, int32_t D, int32_t dtype,
-                         float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm, int32_t variant, BandOpts opts,
-                         int32_t done_words, const svg_attn_layout_t* layout, void* stream) {
-    int rc = band_check_args(q, k, v, o, BH, S, D, mask, perm);
-    if (rc == SVG_OK && opts.alt_mask) rc = check_band_mask(S, opts.alt_mask, nullptr);
+static int check_band_shard(const svg_band_shard_t* s, int32_t S, const svg_perm_desc_t* perm) {
+    return check_frame_shard(s, S, perm->vid0, perm->num_frame, perm->frame_size);
+}
+static int check_band_shard_geometry(int32_t S, const svg_perm_desc_t* perm) {
+    if (S <= 0 || perm->num_frame <= 0 || perm->frame_size <= 0 || perm->vid0 < 0 ||
+        (int64_t)perm->vid0 + (int64_t)perm->num_frame * perm->frame_size > S)
+        return SVG_ERR_BAD_ARG;
+    return SVG_OK;
+}
+
+// The argument checks of every band call, in the order the entry tables pin (tests/test_entry_validation_cpu.py and the per-header tables):
+// pointers and counts, what the form adds, the masks, the sizes, the counters, the layout (into c.lay) against the call's Sq / Sk.
+static int band_check_call(BandCall& c) {
+    svg_attn_layout_t abi;
+    const svg_attn_layout_t* const layout = c.o32 ? band_f32_stand_in(c, abi) : c.layout;
+    if (c.layout) c.strided = true;
+    if (!c.q || !c.k || !c.v || !c.o || !c.mask || c.BH <= 0 || c.S <= 0) return SVG_ERR_BAD_ARG;
+    int rc = SVG_OK;
+    if (c.form == kBandShard) {   // perm's geometry (checked whether or not it carries flags), the q shard, the k shard
+        if (!c.perm || !c.q_shard || !c.k_shard) return SVG_ERR_BAD_ARG;
+        rc = check_band_shard_geometry(c.S, c.perm);
+        if (rc == SVG_OK) rc = check_band_shard(c.q_shard, c.S, c.perm);
+        if (rc == SVG_OK) rc = check_band_shard(c.k_shard, c.S, c.perm);
+    } else if (c.form == kBandWindow) {
+        if (c.win_Sq <= 0 || c.win_Sk <= 0 || c.q_begin < 0 || c.k_begin < 0 || (int64_t)c.q_begin + c.win_Sq > c.S ||
+            (int64_t)c.k_begin + c.win_Sk > c.S)
+            return SVG_ERR_BAD_ARG;
+    }
+    if (rc == SVG_OK) rc = check_band_mask(c.S, c.mask, c.perm);
+    // (the window form states its sizes behind its layout and its head size: band_run)
+    if (rc == SVG_OK && c.form != kBandWindow) rc = band_check_size(c);
+    if (rc == SVG_OK && c.alt_mask) rc = check_band_mask(c.S, c.alt_mask, nullptr);
     if (rc != SVG_OK) return rc;
-    if (opts.done && (int64_t)done_words < (int64_t)BH * (opts.done_nseg + 1)) return SVG_ERR_WORKSPACE;   // segment counters + one hidden counter per head
-    // (a shard launch: q / o hold the rows of the q shard, k / v those of the k shard — checked by band_shard_entry)
-    const int Sq = opts.q_shard ? band_shard_rows(opts.q_shard, perm) : S, Sk = opts.k_shard ? band_shard_rows(opts.k_shard, perm) : S;
-    if (opts.strided && (rc = layout_from_abi(layout, BH, BH, Sq, Sk, D, q, k, v, o, opts.lay)) != SVG_OK) return rc;
-    const hipStream_t st = (hipStream_t)stream;
-    if (opts.lse) {   // the LSE / fp32 forms: the default head_dim-128 body — single mask (queue or static mapping) or device switch
-        if (D != 128 || variant != kBandAuto || opts.done || opts.prescaled) return SVG_ERR_UNSUPPORTED;
-        if (opts.o32 && ((size_t)opts.o32 & 15) != 0) return SVG_ERR_UNSUPPORTED;   // 16-byte stores
-        return dispatch_td(dtype, D, [&](auto t, auto d) -> int {
+    if (c.done && (int64_t)c.done_words < (int64_t)c.BH * (c.done_nseg + 1)) return SVG_ERR_WORKSPACE;   // segment counters + one hidden counter per head
+    return c.strided ? layout_from_abi(layout, c.BH, c.BH, c.Sq(), c.Sk(), c.D, c.q, c.k, c.v, c.o, c.lay) : (int)SVG_OK;
+}
+
+// Every svg_band_attention* entry, after the null checks of its own arguments: validation, then the kernel of the call's form and
+// `variant` for (dtype, D).
+static int band_run(BandCall c) {
+    int rc = band_check_call(c);
+    if (rc != SVG_OK) return rc;
+    const int32_t BH = c.BH;
+    const hipStream_t st = c.stream;
+    if (c.lse) {   // the LSE / fp32 forms: the default head_dim-128 body — single mask (queue or static mapping) or device switch
+        if (c.D != 128 || c.variant != kBandAuto || c.done || c.prescaled) return SVG_ERR_UNSUPPORTED;
+        if (c.form == kBandWindow) {   // key tiles stay aligned to the mask's coordinates; and the sizes, which this form states here
+            if (c.k_begin % kBN != 0) return SVG_ERR_UNSUPPORTED;
+            if ((rc = band_check_size(c)) != SVG_OK) return rc;
+        }
+        if (c.o32 && ((size_t)c.o32 & 15) != 0) return SVG_ERR_UNSUPPORTED;   // 16-byte stores
+        return dispatch_td(c.dtype, c.D, [&](auto t, auto d) -> int {
             using T = decltype(t);
             if constexpr (decltype(d)::value != 128) {
                 return SVG_ERR_UNSUPPORTED;
-            } else {
-                auto whole = [&](auto pol) -> int {   // the alternate mask of the device switch: no head permutation
-                    using Pol = decltype(pol);
-                    auto params = [&](const svg_band_mask_t* m, const svg_perm_desc_t* pm) {
-                        return make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, m, pm, opts);
-                    };
-                    return launch_band_m16<T, Pol>(params, mask, perm, nullptr, opts, st);
-                };
-                auto shard = [&](auto pol) -> int {   // ... on the same shards, every head in logical order (perm's geometry, no flags)
-                    using Pol = decltype(pol);
-                    svg_perm_desc_t perm_alt = *perm;
-                    perm_alt.head_perm_flag = nullptr;
-                    auto params = [&](const svg_band_mask_t* m, const svg_perm_desc_t* pm) {
-                        return make_band_shard_params<Pol, T>(q, k, v, o, BH, S, sm_scale, m, pm, *opts.q_shard, *opts.k_shard, opts);
-                    };
-                    return launch_band_m16<T, Pol>(params, mask, perm, &perm_alt, opts, st);
-                };
-                // (the *_f32 entries: `o` is the stand-in of o32 here, the kernel gets no 16-bit o)
-                if (opts.q_shard) return opts.o32 ? shard(BandShardF32Policy<T>()) : shard(BandShardLsePolicy<T>());
-                return opts.o32 ? whole(BandF32Policy<T>()) : whole(BandLsePolicy<T>());
+            } else {   // (the *_f32 entries: c.o is the stand-in of o32 here, the kernel gets no 16-bit o)
+                switch (c.form) {
+                    case kBandWindow: return c.o32 ? launch_band_m16<T, BandWindowF32Policy<T>>(c) : launch_band_m16<T, BandWindowLsePolicy<T>>(c);
+                    case kBandShard: return c.o32 ? launch_band_m16<T, BandShardF32Policy<T>>(c) : launch_band_m16<T, BandShardLsePolicy<T>>(c);
+                    case kBandPerHead: return launch_band_per_head<T>(c);
+                    default: return c.o32 ? launch_band_m16<T, BandF32Policy<T>>(c) : launch_band_m16<T, BandLsePolicy<T>>(c);
+                }
             }
         });
     }
-    int trace_abl = -1;
+    int variant = c.variant, trace_abl = -1;
     if ((variant & 0xFF) == 32) {   // diagnostics builds: traced one-wave-per-SIMD kernel, bits 8..11 = its timing ablation
-        opts.trace = true;
-        opts.trace_abl = (variant >> 8) & 15;
-        return run_band_w4(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, opts, st);
+        c.trace = true;
+        c.trace_abl = (variant >> 8) & 15;
+        return run_band_w4(c);
     }
     if (variant & 64) {   // diagnostics builds: bit 6 = traced two-phase kernel, bits 8..11 = its timing ablation
         trace_abl = (variant >> 8) & 15;
         variant = kBandPingPong;
         g_trace_reader = read_trace_here;
     }
-    if (variant == kBandAuto) variant = band_default(D);
-    if (opts.done && band_waves_per_tile(variant) < 0) return SVG_ERR_UNSUPPORTED;
-    if (opts.strided && variant != kBandM16 && variant != kBandPingPong) return SVG_ERR_UNSUPPORTED;   // strided tensors: the two-phase bodies only (see svg_attn_layout_t)
-    if (variant == kBandW4) return run_band_w4(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, opts, st);
+    if (variant == kBandAuto) variant = band_default(c.D);
+    if (c.done && band_waves_per_tile(variant) < 0) return SVG_ERR_UNSUPPORTED;
+    if (c.strided && variant != kBandM16 && variant != kBandPingPong) return SVG_ERR_UNSUPPORTED;   // strided tensors: the two-phase bodies only (see svg_attn_layout_t)
+    if (variant == kBandW4) return run_band_w4(c);
     if (variant != kBandLockstep4 && variant != kBandPingPong && variant != kBandFrozen && variant != kBandM16) return SVG_ERR_BAD_ARG;
-    return dispatch_td(dtype, D, [&](auto t, auto d) -> int {
+    return dispatch_td(c.dtype, c.D, [&](auto t, auto d) -> int {
         using T = decltype(t);
         constexpr int DD = decltype(d)::value;
         using Pol = BandPolicy<T, DD, 8>;
-        auto params = [&](const svg_band_mask_t* m, const svg_perm_desc_t* pm) {
-            return make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, m, pm, opts);
-        };
         auto launch = [&](auto kern, int lds) {   // 8 waves over the q-tiles of every head
-            const typename Pol::Params p = params(mask, perm);
+            const typename Pol::Params p = make_band_params<Pol, T>(c);
             return launch_attn(kern, dim3(p.nqt * BH), 512, lds, st, p);
         };
         // a device-switch kernel: the parameters of both masks (the alternate one without the head permutation) and the flag, over
         // the q-tiles of the larger of the two
         auto launch_switch = [&](auto kern, int lds) {
-            const typename Pol::Params a = params(mask, perm), b = params(opts.alt_mask, nullptr);
-            return launch_attn(kern, dim3(std::max(a.nqt, b.nqt) * BH), 512, lds, st, a, b, opts.use_alt);
+            svg_perm_desc_t pm;
+            const typename Pol::Params a = make_band_params<Pol, T>(c), b = make_band_params<Pol, T>(band_alt_call(c, pm));
+            return launch_attn(kern, dim3(std::max(a.nqt, b.nqt) * BH), 512, lds, st, a, b, c.use_alt);
         };
         switch (variant) {
             case kBandLockstep4: {
                 using Pol4 = BandPolicy<T, DD, 4>;
-                const typename Pol4::Params p = make_band_params<Pol4, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
+                const typename Pol4::Params p = make_band_params<Pol4, T>(c);
                 return launch_attn(band_attn_kernel<T, DD, 4>, dim3(p.nqt * BH), 256, attn_lds_bytes<DD, 4>(), st, p);
             }
             case kBandPingPong:
@@ -621,173 +692,117 @@ static int band_dispatch(const void* q, const void* k, const void* v, void* o, i
                 }
 #endif
                 if (trace_abl >= 0) return SVG_ERR_UNSUPPORTED;   // the trace / ablation kernels exist in -DSVG_ABLATIONS builds only
-                if (opts.use_alt) {
-                    if (opts.prescaled) return launch_switch(band_attn_pp2q_switch_kernel<T, DD>, attn_pp2_lds_bytes<DD>());
+                if (c.use_alt) {
+                    if (c.prescaled) return launch_switch(band_attn_pp2q_switch_kernel<T, DD>, attn_pp2_lds_bytes<DD>());
                     if constexpr (DD == 64) return launch_switch(band_attn_pp2_switch64_kernel<T>, attn_pp2_lds_bytes<64>());
                     return SVG_ERR_UNSUPPORTED;
                 }
-                return launch(opts.prescaled ? band_attn_pp2q_kernel<T, DD> : band_attn_pp2_kernel<T, DD>, attn_pp2_lds_bytes<DD>());
+                return launch(c.prescaled ? band_attn_pp2q_kernel<T, DD> : band_attn_pp2_kernel<T, DD>, attn_pp2_lds_bytes<DD>());
             case kBandFrozen:   // bf16 / head_dim 128 only
                 if constexpr (DD == 128 && std::is_same<T, __bf16>::value) {
-                    if (opts.done || opts.prescaled) return SVG_ERR_UNSUPPORTED;
+                    if (c.done || c.prescaled) return SVG_ERR_UNSUPPORTED;
                     return launch(band_attn_pp2_frozen_kernel, attn_pp2_lds_bytes<128>());
                 }
                 return SVG_ERR_UNSUPPORTED;
             default:   // kBandM16: two-phase body on 16x16x32 MFMAs (attn_m16.h), head_dim 128; PRE forms for a q that carries the scale
                 // (switch, work queue — the static mapping where the call counts completions or no counter block is to be had: launch_band_m16)
                 if constexpr (DD == 128) {
-                    if (opts.prescaled) return launch_band_m16<T, Pol, true>(params, mask, perm, nullptr, opts, st);
-                    return launch_band_m16<T, Pol>(params, mask, perm, nullptr, opts, st);
+                    return c.prescaled ? launch_band_m16<T, Pol, true>(c) : launch_band_m16<T, Pol>(c);
                 }
                 return SVG_ERR_UNSUPPORTED;
         }
     });
 }
 
+// a call without tensors, for the parameter blocks the host walks (launch geometry, queue order, the svg_debug_* entries)
+static BandCall band_shape_call(int32_t BH, int32_t S, const svg_band_mask_t* mask, const svg_perm_desc_t* perm) {
+    return BandCall{nullptr, nullptr, nullptr, nullptr, BH, S, 128, SVG_DTYPE_BF16, 1.f, mask, perm};
+}
+
 extern "C" int svg_band_attention(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t S, int32_t D,
                                   int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
                                   const svg_perm_desc_t* perm, int32_t variant, void* stream) {
-    return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, variant, BandOpts(), 0, nullptr, stream);
+    return band_run(BandCall{q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, nullptr, (hipStream_t)stream, variant});
 }
 
 extern "C" int svg_band_attention_strided(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t S, int32_t D,
                                           int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
                                           const svg_attn_layout_t* layout, void* stream) {
-    BandOpts opts;
-    opts.strided = true;
-    return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, 0, layout, stream);
+    BandCall c{q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, layout, (hipStream_t)stream};
+    c.strided = true;   // (a null layout is refused where the layout is checked)
+    return band_run(c);
 }
 
 extern "C" int svg_band_attention_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S, int32_t D,
                                       int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
                                       const svg_attn_layout_t* layout, void* stream) {
     if (!lse) return SVG_ERR_BAD_ARG;
-    BandOpts opts;
-    opts.lse = lse;
-    opts.strided = layout != nullptr;
-    return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, 0, layout, stream);
+    BandCall c{q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, layout, (hipStream_t)stream};
+    c.lse = lse;
+    return band_run(c);
 }
 
 extern "C" int svg_band_attention_lse_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t BH, int32_t S,
                                           int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
                                           const svg_perm_desc_t* perm, const svg_attn_layout_t* layout, void* stream) {
     if (!o32 || !lse) return SVG_ERR_BAD_ARG;
-    BandOpts opts;
-    opts.lse = lse, opts.o32 = o32;
-    opts.strided = layout != nullptr;
-    svg_attn_layout_t abi;
-    void* const o = band_f32_stand_in(q, o32, layout, abi);
-    return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, 0, layout, stream);
+    BandCall c{q, k, v, nullptr, BH, S, D, dtype, sm_scale, mask, perm, layout, (hipStream_t)stream};
+    c.lse = lse, c.o32 = o32;
+    return band_run(c);
 }
 
-// The window entries (include/svg_attn_band_window.h): a sibling of band_dispatch for the LSE / fp32 forms over a row window and a key
-// window — its checks in its order (check_band_mask and the size limits against S, the layout against the windows), then the window
-// kernels on the static mapping.  `o32` (or nullptr) stands in for o (band_f32_stand_in).
-static int band_window_dispatch(const void* q, const void* k, const void* v, void* o, float* o32, float* lse, int32_t BH, int32_t S,
-                                int32_t q_begin, int32_t Sq, int32_t k_begin, int32_t Sk, int32_t D, int32_t dtype, float sm_scale,
-                                const svg_band_mask_t* mask, const svg_attn_layout_t* layout, void* stream) {
-    svg_attn_layout_t abi;
-    if (o32) o = band_f32_stand_in(q, o32, layout, abi);
-    if (!q || !k || !v || !o || !lse || !mask) return SVG_ERR_BAD_ARG;
-    if (BH <= 0 || S <= 0 || Sq <= 0 || Sk <= 0 || q_begin < 0 || k_begin < 0 || (int64_t)q_begin + Sq > S || (int64_t)k_begin + Sk > S)
-        return SVG_ERR_BAD_ARG;
-    int rc = check_band_mask(S, mask, nullptr);
-    if (rc != SVG_OK) return rc;
-    BandOpts opts;
-    opts.lse = lse, opts.o32 = o32;
-    opts.strided = layout != nullptr;
-    if (layout && (rc = layout_from_abi(layout, BH, BH, Sq, Sk, D, q, k, v, o, opts.lay)) != SVG_OK) return rc;
-    if (D != 128 || k_begin % kBN != 0) return SVG_ERR_UNSUPPORTED;   // key tiles stay aligned to the mask's coordinates
-    if ((rc = band_check_size(BH, S, D)) != SVG_OK) return rc;
-    if (o32 && ((size_t)o32 & 15) != 0) return SVG_ERR_UNSUPPORTED;   // 16-byte stores
-    const hipStream_t st = (hipStream_t)stream;
-    return dispatch_td(dtype, D, [&](auto t, auto d) -> int {
-        using T = decltype(t);
-        if constexpr (decltype(d)::value != 128) {
-            return SVG_ERR_UNSUPPORTED;
-        } else {
-            auto run = [&](auto pol) -> int {
-                using Pol = decltype(pol);
-                auto params = [&](const svg_band_mask_t* m, const svg_perm_desc_t*) {
-                    return make_band_window_params<Pol, T>(q, k, v, o, BH, S, q_begin, Sq, k_begin, Sk, sm_scale, m, opts);
-                };
-                return launch_band_m16<T, Pol>(params, mask, nullptr, nullptr, opts, st);
-            };
-            return o32 ? run(BandWindowF32Policy<T>()) : run(BandWindowLsePolicy<T>());
-        }
-    });
-}
-
+// The window entries (include/svg_attn_band_window.h): the LSE / fp32 forms over a row window and a key window, on the static mapping.
 extern "C" int svg_band_window_attention_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S,
                                              int32_t q_begin, int32_t Sq, int32_t k_begin, int32_t Sk, int32_t D, int32_t dtype,
                                              float sm_scale, const svg_band_mask_t* mask, const svg_attn_layout_t* layout, void* stream) {
-    if (!o) return SVG_ERR_BAD_ARG;
-    return band_window_dispatch(q, k, v, o, nullptr, lse, BH, S, q_begin, Sq, k_begin, Sk, D, dtype, sm_scale, mask, layout, stream);
+    if (!o || !lse) return SVG_ERR_BAD_ARG;
+    BandCall c{q, k, v, o, BH, S, D, dtype, sm_scale, mask, nullptr, layout, (hipStream_t)stream};
+    c.lse = lse, c.form = kBandWindow, c.q_begin = q_begin, c.win_Sq = Sq, c.k_begin = k_begin, c.win_Sk = Sk;
+    return band_run(c);
 }
 
 extern "C" int svg_band_window_attention_lse_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t BH, int32_t S,
                                                  int32_t q_begin, int32_t Sq, int32_t k_begin, int32_t Sk, int32_t D, int32_t dtype,
                                                  float sm_scale, const svg_band_mask_t* mask, const svg_attn_layout_t* layout,
                                                  void* stream) {
-    if (!o32) return SVG_ERR_BAD_ARG;
-    return band_window_dispatch(q, k, v, nullptr, o32, lse, BH, S, q_begin, Sq, k_begin, Sk, D, dtype, sm_scale, mask, layout, stream);
+    if (!o32 || !lse) return SVG_ERR_BAD_ARG;
+    BandCall c{q, k, v, nullptr, BH, S, D, dtype, sm_scale, mask, nullptr, layout, (hipStream_t)stream};
+    c.lse = lse, c.o32 = o32, c.form = kBandWindow, c.q_begin = q_begin, c.win_Sq = Sq, c.k_begin = k_begin, c.win_Sk = Sk;
+    return band_run(c);
 }
 
-// The shard entries (include/svg_attn_band_shard.h): the checks of their own arguments — perm's geometry (checked whether or not it
-// carries flags), the q shard, the k shard — then band_dispatch with the two shards in opts.  `o32` (or nullptr) stands in for o
-// (band_f32_stand_in).
-static BandOpts switch_opts(const svg_band_mask_t* alt_mask, const int32_t* use_alt_flag);
-static int check_band_shard(const svg_band_shard_t* s, int32_t S, const svg_perm_desc_t* perm) {
-    return check_frame_shard(s, S, perm->vid0, perm->num_frame, perm->frame_size);
-}
-static int check_band_shard_geometry(int32_t S, const svg_perm_desc_t* perm) {
-    if (S <= 0 || perm->num_frame <= 0 || perm->frame_size <= 0 || perm->vid0 < 0 ||
-        (int64_t)perm->vid0 + (int64_t)perm->num_frame * perm->frame_size > S)
-        return SVG_ERR_BAD_ARG;
-    return SVG_OK;
-}
-static int band_shard_entry(const void* q, const void* k, const void* v, void* o, float* o32, float* lse, int32_t BH, int32_t S, int32_t D,
-                            int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
-                            const svg_band_shard_t* q_shard, const svg_band_shard_t* k_shard, const svg_attn_layout_t* layout, void* stream,
-                            const BandOpts* sw = nullptr /* the switch entries: alt_mask and use_alt, both set */) {
-    if (!q || !k || !v || !(o32 ? (void*)o32 : o) || !lse || !mask || !perm || !q_shard || !k_shard) return SVG_ERR_BAD_ARG;
-    if (sw && (!sw->alt_mask || !sw->use_alt)) return SVG_ERR_BAD_ARG;
-    int rc = BH <= 0 ? SVG_ERR_BAD_ARG : check_band_shard_geometry(S, perm);
-    if (rc == SVG_OK) rc = check_band_shard(q_shard, S, perm);
-    if (rc == SVG_OK) rc = check_band_shard(k_shard, S, perm);
-    if (rc != SVG_OK) return rc;
-    BandOpts opts = sw ? *sw : BandOpts();
-    opts.lse = lse, opts.o32 = o32, opts.q_shard = q_shard, opts.k_shard = k_shard;
-    opts.strided = layout != nullptr;
-    svg_attn_layout_t abi;
-    if (o32) o = band_f32_stand_in(q, o32, layout, abi);
-    return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, 0, layout, stream);
-}
-
+// The shard entries (include/svg_attn_band_shard.h) and their device switch (include/svg_attn_band_shard_switch.h): perm's geometry and the
+// two shards are checked with the call (band_check_call); alt_mask and use_alt_flag join the first NULL check, alt_mask is checked against S
+// where every switch entry's is.
 extern "C" int svg_band_shard_attention_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S, int32_t D,
                                             int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
                                             const svg_band_shard_t* q_shard, const svg_band_shard_t* k_shard,
                                             const svg_attn_layout_t* layout, void* stream) {
-    return band_shard_entry(q, k, v, o, nullptr, lse, BH, S, D, dtype, sm_scale, mask, perm, q_shard, k_shard, layout, stream);
+    if (!lse) return SVG_ERR_BAD_ARG;
+    BandCall c{q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, layout, (hipStream_t)stream};
+    c.lse = lse, c.form = kBandShard, c.q_shard = q_shard, c.k_shard = k_shard;
+    return band_run(c);
 }
 
 extern "C" int svg_band_shard_attention_lse_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t BH, int32_t S,
                                                 int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
                                                 const svg_perm_desc_t* perm, const svg_band_shard_t* q_shard,
                                                 const svg_band_shard_t* k_shard, const svg_attn_layout_t* layout, void* stream) {
-    if (!o32) return SVG_ERR_BAD_ARG;
-    return band_shard_entry(q, k, v, nullptr, o32, lse, BH, S, D, dtype, sm_scale, mask, perm, q_shard, k_shard, layout, stream);
+    if (!o32 || !lse) return SVG_ERR_BAD_ARG;
+    BandCall c{q, k, v, nullptr, BH, S, D, dtype, sm_scale, mask, perm, layout, (hipStream_t)stream};
+    c.lse = lse, c.o32 = o32, c.form = kBandShard, c.q_shard = q_shard, c.k_shard = k_shard;
+    return band_run(c);
 }
 
-// The device switch of the shard entries (include/svg_attn_band_shard_switch.h): alt_mask and use_alt_flag join the first NULL check,
-// alt_mask is checked against S where band_dispatch checks mask.
 extern "C" int svg_band_shard_attention_switch_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S,
                                                    int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
                                                    const svg_perm_desc_t* perm, const svg_band_mask_t* alt_mask, const int32_t* use_alt_flag,
                                                    const svg_band_shard_t* q_shard, const svg_band_shard_t* k_shard,
                                                    const svg_attn_layout_t* layout, void* stream) {
-    const BandOpts sw = switch_opts(alt_mask, use_alt_flag);
-    return band_shard_entry(q, k, v, o, nullptr, lse, BH, S, D, dtype, sm_scale, mask, perm, q_shard, k_shard, layout, stream, &sw);
+    if (!lse || !alt_mask || !use_alt_flag) return SVG_ERR_BAD_ARG;
+    BandCall c{q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, layout, (hipStream_t)stream};
+    c.lse = lse, c.form = kBandShard, c.q_shard = q_shard, c.k_shard = k_shard, c.alt_mask = alt_mask, c.use_alt = use_alt_flag;
+    return band_run(c);
 }
 
 extern "C" int svg_band_shard_attention_switch_lse_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t BH,
@@ -795,9 +810,10 @@ extern "C" int svg_band_shard_attention_switch_lse_f32(const void* q, const void
                                                        const svg_perm_desc_t* perm, const svg_band_mask_t* alt_mask,
                                                        const int32_t* use_alt_flag, const svg_band_shard_t* q_shard,
                                                        const svg_band_shard_t* k_shard, const svg_attn_layout_t* layout, void* stream) {
-    if (!o32) return SVG_ERR_BAD_ARG;
-    const BandOpts sw = switch_opts(alt_mask, use_alt_flag);
-    return band_shard_entry(q, k, v, nullptr, o32, lse, BH, S, D, dtype, sm_scale, mask, perm, q_shard, k_shard, layout, stream, &sw);
+    if (!o32 || !lse || !alt_mask || !use_alt_flag) return SVG_ERR_BAD_ARG;
+    BandCall c{q, k, v, nullptr, BH, S, D, dtype, sm_scale, mask, perm, layout, (hipStream_t)stream};
+    c.lse = lse, c.o32 = o32, c.form = kBandShard, c.q_shard = q_shard, c.k_shard = k_shard, c.alt_mask = alt_mask, c.use_alt = use_alt_flag;
+    return band_run(c);
 }
 
 extern "C" int32_t svg_debug_band_shard_map(const svg_perm_desc_t* perm, int32_t S, const svg_band_shard_t* shard, int32_t token_major,
@@ -815,15 +831,15 @@ extern "C" int32_t svg_debug_band_shard_map(const svg_perm_desc_t* perm, int32_t
 extern "C" int svg_band_attention_prescaled(const void* q_scaled, const void* k, const void* v, void* o, int32_t BH, int32_t S,
                                             int32_t D, int32_t dtype, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
                                             void* stream) {
-    BandOpts opts;
-    opts.prescaled = true;
-    return band_dispatch(q_scaled, k, v, o, BH, S, D, dtype, 1.f, mask, perm, kBandAuto, opts, 0, nullptr, stream);
+    BandCall c{q_scaled, k, v, o, BH, S, D, dtype, 1.f, mask, perm, nullptr, (hipStream_t)stream};
+    c.prescaled = true;
+    return band_run(c);
 }
 
 extern "C" int32_t svg_band_attention_notify_target(int32_t S, const svg_band_mask_t* mask) {
     if (!mask || S <= 0) return -1;
     using Pol = svg::BandPolicy<__bf16, 128, 8>;
-    const auto p = svg::make_band_params<Pol, __bf16>(nullptr, nullptr, nullptr, nullptr, 1, S, 1.f, mask, nullptr);
+    const auto p = svg::make_band_params<Pol, __bf16>(band_shape_call(1, S, mask, nullptr));
     return p.nqt * band_waves_per_tile(kBandAuto);   // every wave of every q-tile of a head reports once
 }
 
@@ -831,9 +847,9 @@ extern "C" int32_t svg_band_attention_notify_layout(int32_t S, const svg_band_ma
                                                     int32_t* targets) {
     if (!mask || S <= 0 || nseg <= 0 || !row_bounds || !targets) return -1;
     using Pol = svg::BandPolicy<__bf16, 128, 8>;   // (q-tiles are 256 rows in every schedule that counts)
-    BandOpts opts;
-    opts.done_nseg = nseg;
-    const auto p = svg::make_band_params<Pol, __bf16>(nullptr, nullptr, nullptr, nullptr, 1, S, 1.f, mask, nullptr, opts);
+    BandCall c = band_shape_call(1, S, mask, nullptr);
+    c.done_nseg = nseg;
+    const auto p = svg::make_band_params<Pol, __bf16>(c);
     auto tile_row = [&](int t) {   // first row of q-tile t (row order), S behind the last tile
         if (t >= p.nqt) return S;
         int r = 0;
@@ -861,9 +877,9 @@ extern "C" int svg_band_attention_notify_seg(const void* q, const void* k, const
                                              const svg_perm_desc_t* perm, int32_t* done, int32_t done_words, int32_t nseg,
                                              void* stream) {
     if (!done || nseg <= 0) return SVG_ERR_BAD_ARG;
-    BandOpts opts;
-    opts.done = done, opts.done_nseg = nseg;
-    return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, done_words, nullptr, stream);
+    BandCall c{q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, nullptr, (hipStream_t)stream};
+    c.done = done, c.done_words = done_words, c.done_nseg = nseg;
+    return band_run(c);
 }
 
 extern "C" int svg_band_attention_prescaled_notify_seg(const void* q_scaled, const void* k, const void* v, void* o, int32_t BH,
@@ -871,9 +887,9 @@ extern "C" int svg_band_attention_prescaled_notify_seg(const void* q_scaled, con
                                                        const svg_perm_desc_t* perm, int32_t* done, int32_t done_words, int32_t nseg,
                                                        void* stream) {
     if (!done || nseg <= 0) return SVG_ERR_BAD_ARG;
-    BandOpts opts;
-    opts.done = done, opts.done_nseg = nseg, opts.prescaled = true;
-    return band_dispatch(q_scaled, k, v, o, BH, S, D, dtype, 1.f, mask, perm, kBandAuto, opts, done_words, nullptr, stream);
+    BandCall c{q_scaled, k, v, o, BH, S, D, dtype, 1.f, mask, perm, nullptr, (hipStream_t)stream};
+    c.done = done, c.done_words = done_words, c.done_nseg = nseg, c.prescaled = true;
+    return band_run(c);
 }
 
 extern "C" int svg_wait_counters(const int32_t* counters, int32_t n, int32_t target, void* stream) {
@@ -892,18 +908,13 @@ extern "C" int svg_wait_counters_deadline(const int32_t* counters, int32_t n, in
 
 // the device switch runs on the default schedule of the head size: the 16x16x32 body at head_dim 128 (attn_m16.h), the LEAN 32x32x16
 // one at 64 (band_attn_pp2_kernel<T, 64>); strided tensors as in svg_band_attention_strided
-static BandOpts switch_opts(const svg_band_mask_t* alt_mask, const int32_t* use_alt_flag) {
-    BandOpts opts;
-    opts.alt_mask = alt_mask, opts.use_alt = use_alt_flag;
-    return opts;
-}
-
 extern "C" int svg_band_attention_switch(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t S, int32_t D,
                                          int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
                                          const svg_band_mask_t* alt_mask, const int32_t* use_alt_flag, void* stream) {
     if (!alt_mask || !use_alt_flag) return SVG_ERR_BAD_ARG;
-    return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, switch_opts(alt_mask, use_alt_flag), 0, nullptr,
-                         stream);
+    BandCall c{q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, nullptr, (hipStream_t)stream};
+    c.alt_mask = alt_mask, c.use_alt = use_alt_flag;
+    return band_run(c);
 }
 
 extern "C" int svg_band_attention_switch_strided(const void* q, const void* k, const void* v, void* o, int32_t BH, int32_t S, int32_t D,
@@ -911,116 +922,50 @@ extern "C" int svg_band_attention_switch_strided(const void* q, const void* k, c
                                                  const svg_band_mask_t* alt_mask, const int32_t* use_alt_flag,
                                                  const svg_attn_layout_t* layout, void* stream) {
     if (!layout || !alt_mask || !use_alt_flag) return SVG_ERR_BAD_ARG;
-    BandOpts opts = switch_opts(alt_mask, use_alt_flag);
-    opts.strided = true;
-    return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, 0, layout, stream);
+    BandCall c{q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, layout, (hipStream_t)stream};
+    c.alt_mask = alt_mask, c.use_alt = use_alt_flag;
+    return band_run(c);
 }
 
 extern "C" int svg_band_attention_switch_prescaled(const void* q_scaled, const void* k, const void* v, void* o, int32_t BH, int32_t S,
                                                    int32_t D, int32_t dtype, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
                                                    const svg_band_mask_t* alt_mask, const int32_t* use_alt_flag, void* stream) {
     if (!alt_mask || !use_alt_flag) return SVG_ERR_BAD_ARG;
-    BandOpts opts = switch_opts(alt_mask, use_alt_flag);
-    opts.prescaled = true;
-    return band_dispatch(q_scaled, k, v, o, BH, S, D, dtype, 1.f, mask, perm, kBandAuto, opts, 0, nullptr, stream);
+    BandCall c{q_scaled, k, v, o, BH, S, D, dtype, 1.f, mask, perm, nullptr, (hipStream_t)stream};
+    c.alt_mask = alt_mask, c.use_alt = use_alt_flag, c.prescaled = true;
+    return band_run(c);
 }
 
-// LSE / fp32 forms of the device switch (include/svg_attn_band_lse_forms.h): the null checks of the plain switch entry behind the one of
-// lse / o32, then band_dispatch with opts.lse (and opts.o32).  o32 travels in the place of o (band_f32_stand_in).
-static int band_switch_lse(const void* q, const void* k, const void* v, void* o, float* o32, float* lse, int32_t BH, int32_t S, int32_t D,
-                           int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
-                           const svg_band_mask_t* alt_mask, const int32_t* use_alt_flag, const svg_attn_layout_t* layout, void* stream) {
-    if (!alt_mask || !use_alt_flag) return SVG_ERR_BAD_ARG;
-    BandOpts opts = switch_opts(alt_mask, use_alt_flag);
-    opts.lse = lse, opts.o32 = o32;
-    opts.strided = layout != nullptr;
-    svg_attn_layout_t abi;
-    if (o32) o = band_f32_stand_in(q, o32, layout, abi);
-    return band_dispatch(q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, kBandAuto, opts, 0, layout, stream);
-}
-
+// LSE / fp32 forms of the device switch (include/svg_attn_band_lse_forms.h)
 extern "C" int svg_band_attention_switch_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S,
                                              int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
                                              const svg_perm_desc_t* perm, const svg_band_mask_t* alt_mask, const int32_t* use_alt_flag,
                                              const svg_attn_layout_t* layout, void* stream) {
-    if (!lse) return SVG_ERR_BAD_ARG;
-    return band_switch_lse(q, k, v, o, nullptr, lse, BH, S, D, dtype, sm_scale, mask, perm, alt_mask, use_alt_flag, layout, stream);
+    if (!lse || !alt_mask || !use_alt_flag) return SVG_ERR_BAD_ARG;
+    BandCall c{q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, layout, (hipStream_t)stream};
+    c.lse = lse, c.alt_mask = alt_mask, c.use_alt = use_alt_flag;
+    return band_run(c);
 }
 
 extern "C" int svg_band_attention_switch_lse_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t BH, int32_t S,
                                                  int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
                                                  const svg_perm_desc_t* perm, const svg_band_mask_t* alt_mask,
                                                  const int32_t* use_alt_flag, const svg_attn_layout_t* layout, void* stream) {
-    if (!o32 || !lse) return SVG_ERR_BAD_ARG;
-    return band_switch_lse(q, k, v, nullptr, o32, lse, BH, S, D, dtype, sm_scale, mask, perm, alt_mask, use_alt_flag, layout, stream);
+    if (!o32 || !lse || !alt_mask || !use_alt_flag) return SVG_ERR_BAD_ARG;
+    BandCall c{q, k, v, nullptr, BH, S, D, dtype, sm_scale, mask, perm, layout, (hipStream_t)stream};
+    c.lse = lse, c.o32 = o32, c.alt_mask = alt_mask, c.use_alt = use_alt_flag;
+    return band_run(c);
 }
 
-// One band per head (include/svg_attn_adaptive_band.h): the checks of svg_band_attention[_switch]_lse in their order, then the per-head
-// kernels on the static mapping.  The parameter block is built for a band that cuts the full rows out (min(mask->band, S))
-// and once more for one that does not (S + 1); the kernel picks per head, and the policy reads the head's band where the block has the mask's.
-static int band_per_head_run(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S, int32_t D,
-                             int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const svg_band_mask_t* alt_mask,
-                             const int32_t* use_alt_flag, const int32_t* band, const svg_perm_desc_t* perm,
-                             const svg_attn_layout_t* layout, void* stream, bool queue = false) {
-    int rc = band_check_args(q, k, v, o, BH, S, D, mask, perm);
-    if (rc == SVG_OK && alt_mask) rc = check_band_mask(S, alt_mask, nullptr);
-    if (rc != SVG_OK) return rc;
-    BandOpts opts;
-    opts.lse = lse;
-    opts.strided = layout != nullptr;
-    if (opts.strided && (rc = layout_from_abi(layout, BH, BH, S, S, D, q, k, v, o, opts.lay)) != SVG_OK) return rc;
-    if (D != 128) return SVG_ERR_UNSUPPORTED;
-    const hipStream_t st = (hipStream_t)stream;
-    return dispatch_td(dtype, D, [&](auto t, auto d) -> int {
-        using T = decltype(t);
-        if constexpr (decltype(d)::value != 128) {
-            return SVG_ERR_UNSUPPORTED;
-        } else {
-            using Pol = BandPerHeadLsePolicy<T>;
-            auto params = [&](const svg_band_mask_t* m, int band_of, const svg_perm_desc_t* pm, const int32_t* band_vec) {
-                svg_band_mask_t mm = *m;
-                mm.band = band_of;
-                typename Pol::Params p = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, &mm, pm, opts);
-                p.band_vec = band_vec;
-                p.map_nqt = p.nqt, p.map_n_heavy = p.n_heavy, p.map_heavy_lo = p.heavy_lo;
-                return p;
-            };
-            const typename Pol::Params p = params(mask, std::min(mask->band, S), perm, band);
-            typename Pol::Params w = params(mask, S + 1, perm, band);
-            if (w.nqt > p.nqt) return SVG_ERR_LAUNCH;   // (fewer cuts never make more q-tiles: band_row_regions)
-            w.map_nqt = p.map_nqt, w.map_n_heavy = p.map_n_heavy, w.map_heavy_lo = p.map_heavy_lo;   // one mapping for both blocks
-            const int lds = attn_m16_lds_bytes() + kTailLds;
-            typename Pol::Params a{};
-            if (use_alt_flag) a = params(alt_mask, alt_mask->band, nullptr, nullptr);
-            // queue: resident workgroups where launch_band_queue would launch them (include/svg_attn_band_per_head_queue.h).  The queues are
-            // built through the LSE base of the blocks: the per-head Ctx carries a band kv_schedule would read and no host sets.
-            if (queue) {
-                int n_cu = 0;
-                int32_t* const block = band_queue_block(st, n_cu);
-                const int cap = band_queue_cap();
-                const int items = (use_alt_flag ? std::max(p.nqt, a.nqt) : p.nqt) * BH;
-                if (block && !(items <= n_cu && cap == 0)) {
-                    BandQueue qd = make_band_queue<BandLsePolicy<T>>(p);
-                    qd.ctr = block;
-                    int n_wg = std::min(items, n_cu);
-                    if (cap > 0) n_wg = std::min(n_wg, cap);
-                    if (!use_alt_flag) return launch_attn(band_attn_m16_per_head_queue_kernel<T>, dim3(n_wg), 512, lds, st, p, w, qd);
-                    BandQueue qa = make_band_queue<BandLsePolicy<T>>(a);
-                    qa.ctr = block;
-                    return launch_attn(band_attn_m16_per_head_switch_queue_kernel<T>, dim3(n_wg), 512, lds, st, p, w, a, use_alt_flag, qd, qa);
-                }
-            }
-            if (!use_alt_flag) return launch_attn(band_attn_m16_per_head_kernel<T>, dim3(p.nqt * BH), 512, lds, st, p, w);
-            return launch_attn(band_attn_m16_per_head_switch_kernel<T>, dim3(std::max(p.nqt, a.nqt) * BH), 512, lds, st, p, w, a, use_alt_flag);
-        }
-    });
-}
-
+// One band per head (include/svg_attn_adaptive_band.h, include/svg_attn_band_per_head_queue.h): the checks of
+// svg_band_attention[_switch]_lse in their order, then launch_band_per_head.
 extern "C" int svg_band_attention_per_head_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S,
                                                int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const int32_t* band,
                                                const svg_perm_desc_t* perm, const svg_attn_layout_t* layout, void* stream) {
     if (!lse || !band) return SVG_ERR_BAD_ARG;
-    return band_per_head_run(q, k, v, o, lse, BH, S, D, dtype, sm_scale, mask, nullptr, nullptr, band, perm, layout, stream);
+    BandCall c{q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, layout, (hipStream_t)stream};
+    c.lse = lse, c.form = kBandPerHead, c.band = band;
+    return band_run(c);
 }
 
 extern "C" int svg_band_attention_switch_per_head_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S,
@@ -1028,7 +973,9 @@ extern "C" int svg_band_attention_switch_per_head_lse(const void* q, const void*
                                                       const svg_band_mask_t* alt_mask, const int32_t* use_alt, const int32_t* band,
                                                       const svg_perm_desc_t* perm, const svg_attn_layout_t* layout, void* stream) {
     if (!lse || !band || !alt_mask || !use_alt) return SVG_ERR_BAD_ARG;
-    return band_per_head_run(q, k, v, o, lse, BH, S, D, dtype, sm_scale, mask, alt_mask, use_alt, band, perm, layout, stream);
+    BandCall c{q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, layout, (hipStream_t)stream};
+    c.lse = lse, c.form = kBandPerHead, c.band = band, c.alt_mask = alt_mask, c.use_alt = use_alt;
+    return band_run(c);
 }
 
 extern "C" int svg_band_attention_per_head_queue_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S,
@@ -1036,7 +983,9 @@ extern "C" int svg_band_attention_per_head_queue_lse(const void* q, const void* 
                                                      const int32_t* band, const svg_perm_desc_t* perm, const svg_attn_layout_t* layout,
                                                      void* stream) {
     if (!lse || !band) return SVG_ERR_BAD_ARG;
-    return band_per_head_run(q, k, v, o, lse, BH, S, D, dtype, sm_scale, mask, nullptr, nullptr, band, perm, layout, stream, true);
+    BandCall c{q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, layout, (hipStream_t)stream};
+    c.lse = lse, c.form = kBandPerHead, c.band = band, c.queue = true;
+    return band_run(c);
 }
 
 extern "C" int svg_band_attention_switch_per_head_queue_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH,
@@ -1044,81 +993,70 @@ extern "C" int svg_band_attention_switch_per_head_queue_lse(const void* q, const
                                                             const svg_band_mask_t* alt_mask, const int32_t* use_alt, const int32_t* band,
                                                             const svg_perm_desc_t* perm, const svg_attn_layout_t* layout, void* stream) {
     if (!lse || !band || !alt_mask || !use_alt) return SVG_ERR_BAD_ARG;
-    return band_per_head_run(q, k, v, o, lse, BH, S, D, dtype, sm_scale, mask, alt_mask, use_alt, band, perm, layout, stream, true);
+    BandCall c{q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, layout, (hipStream_t)stream};
+    c.lse = lse, c.form = kBandPerHead, c.band = band, c.alt_mask = alt_mask, c.use_alt = use_alt, c.queue = true;
+    return band_run(c);
 }
 
 // svg_band_groups_attention: the heads of one call in groups of consecutive heads, each under a mask (and an alternate mask) of its
 // own — the videos of a batch whose text lengths differ.  Every group is checked before the first launches; the launches are those of
-// the single-mask entry the arguments select, one pass through band_dispatch per group.  (One launch per group and not a mask per head
+// the single-mask entry the arguments select, one pass through band_run per group.  (One launch per group and not a mask per head
 // inside one launch: DESIGN §3.1.3.)
-namespace {
-struct BandGroup {
-    const void *q, *k, *v;
-    void* o;
-    svg_perm_desc_t perm;
-};
-// tensor bases and head-permutation flags of the group behind `h0` heads (byte offsets in 64 bits; 16-bit elements)
-BandGroup band_group_at(const void* q, const void* k, const void* v, void* o, int64_t h0, int32_t S, int32_t D, const svg_perm_desc_t* perm,
-                        const svg_attn_layout_t* layout) {
-    auto at = [](const void* p, int64_t elements) -> const void* { return (const char*)p + elements * 2; };
-    BandGroup g;
-    if (layout) {   // whole videos: the base moves by batch strides
-        const int64_t b0 = h0 / layout->heads_per_batch;
-        g.q = at(q, b0 * layout->q.batch), g.k = at(k, b0 * layout->k.batch), g.v = at(v, b0 * layout->v.batch);
-        g.o = (void*)at(o, b0 * layout->o.batch);
+// The call of the group of `heads` heads behind `h0` heads of call `c`: tensor bases (byte offsets in 64 bits; 16-bit elements; a null o —
+// the fp32 forms — stays null), lse and o32 as contiguous [BH, S] / [BH, S, D] fp32 whatever the layout, and the head-permutation flags (in `pm`).
+static BandCall band_group_at(const BandCall& c, int64_t h0, int32_t heads, svg_perm_desc_t& pm) {
+    auto at = [](const void* p, int64_t elements) -> const void* { return p ? (const char*)p + elements * 2 : nullptr; };
+    BandCall g = c;
+    g.BH = heads;
+    if (c.layout) {   // whole videos: the base moves by batch strides
+        const int64_t b0 = h0 / c.layout->heads_per_batch;
+        g.q = at(c.q, b0 * c.layout->q.batch), g.k = at(c.k, b0 * c.layout->k.batch), g.v = at(c.v, b0 * c.layout->v.batch);
+        g.o = (void*)at(c.o, b0 * c.layout->o.batch);
     } else {
-        const int64_t off = h0 * (int64_t)S * D;
-        g.q = at(q, off), g.k = at(k, off), g.v = at(v, off), g.o = (void*)at(o, off);
+        const int64_t off = h0 * (int64_t)c.S * c.D;
+        g.q = at(c.q, off), g.k = at(c.k, off), g.v = at(c.v, off), g.o = (void*)at(c.o, off);
     }
-    g.perm = perm ? *perm : svg_perm_desc_t{nullptr, 0, 1, 1};
-    if (g.perm.head_perm_flag) g.perm.head_perm_flag += h0;
+    if (c.lse) g.lse = c.lse + (size_t)h0 * (size_t)c.S;
+    if (c.o32) g.o32 = c.o32 + (size_t)h0 * (size_t)c.S * (size_t)c.D;
+    if (c.perm) {
+        pm = *c.perm, g.perm = &pm;
+        if (pm.head_perm_flag) pm.head_perm_flag += h0;
+    }
     return g;
 }
-}  // namespace
 
-// every groups entry.  lse (and o32): the LSE / fp32 forms — o32 then stands in for o (band_f32_stand_in), and both
-// advance to a group's first head as contiguous [BH, S] / [BH, S, D] fp32 whatever the layout.
-static int band_groups_run(const void* q, const void* k, const void* v, void* o, float* o32, float* lse, int32_t BH, int32_t S, int32_t D,
-                           int32_t dtype, float sm_scale, const svg_band_mask_t* masks, const svg_band_mask_t* alt_masks,
-                           const int32_t* group_heads, int32_t n_groups, const svg_perm_desc_t* perm, const int32_t* use_alt_flag,
-                           int32_t q_prescaled, const svg_attn_layout_t* layout, void* stream) {
-    svg_attn_layout_t abi;
-    if (o32) o = band_f32_stand_in(q, o32, layout, abi);
-    if (!q || !k || !v || !o || !masks || !group_heads || n_groups < 1 || BH <= 0 || S <= 0) return SVG_ERR_BAD_ARG;
-    if ((alt_masks != nullptr) != (use_alt_flag != nullptr)) return SVG_ERR_BAD_ARG;
+// every groups entry, with the call of all heads in `c` (c.use_alt with alt_masks, or neither)
+static int band_groups_run(BandCall c, const svg_band_mask_t* masks, const svg_band_mask_t* alt_masks, const int32_t* group_heads,
+                           int32_t n_groups) {
+    if (!c.q || !c.k || !c.v || !(c.o32 ? (void*)c.o32 : c.o) || !masks || !group_heads || n_groups < 1 || c.BH <= 0 || c.S <= 0)
+        return SVG_ERR_BAD_ARG;
+    if ((alt_masks != nullptr) != (c.use_alt != nullptr)) return SVG_ERR_BAD_ARG;
     int64_t heads = 0;
     for (int g = 0; g < n_groups; ++g) {
         if (group_heads[g] < 1) return SVG_ERR_BAD_ARG;
-        if (layout && (layout->heads_per_batch <= 0 || group_heads[g] % layout->heads_per_batch != 0)) return SVG_ERR_BAD_ARG;
+        if (c.layout && (c.layout->heads_per_batch <= 0 || group_heads[g] % c.layout->heads_per_batch != 0)) return SVG_ERR_BAD_ARG;
         heads += group_heads[g];
     }
-    if (heads != BH) return SVG_ERR_BAD_ARG;
-    BandOpts opts = alt_masks ? switch_opts(nullptr, use_alt_flag) : BandOpts();
-    opts.prescaled = q_prescaled != 0, opts.strided = layout != nullptr;
-    const float scale = opts.prescaled ? 1.f : sm_scale;
+    if (heads != c.BH) return SVG_ERR_BAD_ARG;
+    if (c.prescaled) c.sm_scale = 1.f;
+    svg_perm_desc_t pm;
+    auto group = [&](int g, int64_t h0) {
+        BandCall gc = band_group_at(c, h0, group_heads[g], pm);
+        gc.mask = masks + g, gc.alt_mask = alt_masks ? alt_masks + g : nullptr;
+        return gc;
+    };
     // what the single-mask entries check, for every group, before anything is launched
     int64_t h0 = 0;
     for (int g = 0; g < n_groups; h0 += group_heads[g++]) {
-        const BandGroup gr = band_group_at(q, k, v, o, h0, S, D, perm, layout);
-        int rc = band_check_args(gr.q, gr.k, gr.v, gr.o, group_heads[g], S, D, masks + g, perm ? &gr.perm : nullptr);
-        if (rc == SVG_OK && alt_masks) rc = check_band_mask(S, alt_masks + g, nullptr);
-        AttnLayout lay;
-        if (rc == SVG_OK && layout) rc = layout_from_abi(layout, group_heads[g], group_heads[g], S, S, D, gr.q, gr.k, gr.v, gr.o, lay);
-        if (rc != SVG_OK) return rc;
+        BandCall gc = group(g, h0);
+        if (const int rc = band_check_call(gc); rc != SVG_OK) return rc;
     }
-    if (opts.prescaled && opts.strided) return SVG_ERR_UNSUPPORTED;   // (no single-mask entry takes a pre-scaled q with a layout)
-    if (const int rc = dispatch_td(dtype, D, [](auto, auto) { return (int)SVG_OK; }); rc != SVG_OK) return rc;
-    if (lse && (D != 128 || ((size_t)o32 & 15) != 0)) return SVG_ERR_UNSUPPORTED;
+    if (c.prescaled && c.layout) return SVG_ERR_UNSUPPORTED;   // (no single-mask entry takes a pre-scaled q with a layout)
+    if (const int rc = dispatch_td(c.dtype, c.D, [](auto, auto) { return (int)SVG_OK; }); rc != SVG_OK) return rc;
+    if (c.lse && (c.D != 128 || ((size_t)c.o32 & 15) != 0)) return SVG_ERR_UNSUPPORTED;
     h0 = 0;
-    for (int g = 0; g < n_groups; h0 += group_heads[g++]) {
-        const BandGroup gr = band_group_at(q, k, v, o, h0, S, D, perm, layout);
-        if (alt_masks) opts.alt_mask = alt_masks + g;
-        if (lse) opts.lse = lse + (size_t)h0 * (size_t)S;
-        if (o32) opts.o32 = o32 + (size_t)h0 * (size_t)S * (size_t)D;
-        const int rc = band_dispatch(gr.q, gr.k, gr.v, gr.o, group_heads[g], S, D, dtype, scale, masks + g, perm ? &gr.perm : nullptr,
-                                     kBandAuto, opts, 0, layout, stream);
-        if (rc != SVG_OK) return rc;   // (a failed launch: SVG_ERR_LAUNCH)
-    }
+    for (int g = 0; g < n_groups; h0 += group_heads[g++])
+        if (const int rc = band_run(group(g, h0)); rc != SVG_OK) return rc;   // (a failed launch: SVG_ERR_LAUNCH)
     return SVG_OK;
 }
 
@@ -1127,8 +1065,9 @@ extern "C" int svg_band_groups_attention(const void* q, const void* k, const voi
                                          const int32_t* group_heads, int32_t n_groups, const svg_perm_desc_t* perm,
                                          const int32_t* use_alt_flag, int32_t q_prescaled, const svg_attn_layout_t* layout,
                                          void* stream) {
-    return band_groups_run(q, k, v, o, nullptr, nullptr, BH, S, D, dtype, sm_scale, masks, alt_masks, group_heads, n_groups, perm,
-                           use_alt_flag, q_prescaled, layout, stream);
+    BandCall c{q, k, v, o, BH, S, D, dtype, sm_scale, nullptr, perm, layout, (hipStream_t)stream};
+    c.use_alt = use_alt_flag, c.prescaled = q_prescaled != 0;
+    return band_groups_run(c, masks, alt_masks, group_heads, n_groups);
 }
 
 extern "C" int svg_band_groups_attention_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S,
@@ -1137,8 +1076,9 @@ extern "C" int svg_band_groups_attention_lse(const void* q, const void* k, const
                                              const svg_perm_desc_t* perm, const int32_t* use_alt_flag, const svg_attn_layout_t* layout,
                                              void* stream) {
     if (!lse) return SVG_ERR_BAD_ARG;
-    return band_groups_run(q, k, v, o, nullptr, lse, BH, S, D, dtype, sm_scale, masks, alt_masks, group_heads, n_groups, perm,
-                           use_alt_flag, 0, layout, stream);
+    BandCall c{q, k, v, o, BH, S, D, dtype, sm_scale, nullptr, perm, layout, (hipStream_t)stream};
+    c.lse = lse, c.use_alt = use_alt_flag;
+    return band_groups_run(c, masks, alt_masks, group_heads, n_groups);
 }
 
 extern "C" int svg_band_groups_attention_lse_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t BH, int32_t S,
@@ -1147,14 +1087,15 @@ extern "C" int svg_band_groups_attention_lse_f32(const void* q, const void* k, c
                                                  const svg_perm_desc_t* perm, const int32_t* use_alt_flag,
                                                  const svg_attn_layout_t* layout, void* stream) {
     if (!o32 || !lse) return SVG_ERR_BAD_ARG;
-    return band_groups_run(q, k, v, nullptr, o32, lse, BH, S, D, dtype, sm_scale, masks, alt_masks, group_heads, n_groups, perm,
-                           use_alt_flag, 0, layout, stream);
+    BandCall c{q, k, v, nullptr, BH, S, D, dtype, sm_scale, nullptr, perm, layout, (hipStream_t)stream};
+    c.lse = lse, c.o32 = o32, c.use_alt = use_alt_flag;
+    return band_groups_run(c, masks, alt_masks, group_heads, n_groups);
 }
 
 extern "C" int32_t svg_band_queue_order(int32_t BH, int32_t S, const svg_band_mask_t* mask, int32_t* out, int32_t out_words) {
     if (!mask || BH <= 0 || S <= 0 || check_band_mask(S, mask, nullptr) != SVG_OK) return -1;
     using Pol = svg::BandPolicy<__bf16, 128, 8>;
-    const auto p = svg::make_band_params<Pol, __bf16>(nullptr, nullptr, nullptr, nullptr, BH, S, 1.f, mask, nullptr);
+    const auto p = svg::make_band_params<Pol, __bf16>(band_shape_call(BH, S, mask, nullptr));
     const BandQueue qd = svg::make_band_queue<Pol>(p);
     if (!out) return qd.n_items;
     int n = 0;
@@ -1173,7 +1114,7 @@ extern "C" int32_t svg_band_queue_order(int32_t BH, int32_t S, const svg_band_ma
     return n;
 }
 
-// the order of the per-head queue launches on the host (include/svg_attn_band_per_head_queue.h): the blocks and queues band_per_head_run builds,
+// the order of the per-head queue launches on the host (include/svg_attn_band_per_head_queue.h): the blocks and queues launch_band_per_head builds,
 // walked list by list, with the drop lane 0 of the kernels resolves
 extern "C" int32_t svg_band_per_head_queue_order(int32_t BH, int32_t S, const svg_band_mask_t* mask, const svg_band_mask_t* alt_mask,
                                                  int32_t use_alt, const int32_t* band, int32_t* out, int32_t out_words) {
@@ -1184,7 +1125,7 @@ extern "C" int32_t svg_band_per_head_queue_order(int32_t BH, int32_t S, const sv
     auto params = [&](const svg_band_mask_t* m, int band_of) {
         svg_band_mask_t mm = *m;
         mm.band = band_of;
-        return svg::make_band_params<Pol, __bf16>(nullptr, nullptr, nullptr, nullptr, BH, S, 1.f, &mm, nullptr);
+        return svg::make_band_params<Pol, __bf16>(band_shape_call(BH, S, &mm, nullptr));
     };
     const auto p = use_alt ? params(alt_mask, alt_mask->band) : params(mask, std::min(mask->band, S));
     const auto w = params(mask, S + 1);
@@ -1229,7 +1170,7 @@ extern "C" int32_t svg_debug_band_row_cursor(int32_t S, int32_t vid0, int32_t nu
     const int64_t flag = 1;   // (never read: the builder only asks whether the call names token-major heads)
     const svg_perm_desc_t perm{&flag, vid0, num_frame, frame_size};
     if (check_band_mask(S, &mask, &perm) != SVG_OK) return -1;
-    const Pol::Params p = svg::make_band_params<Pol, __bf16>(nullptr, nullptr, nullptr, nullptr, 1, S, 1.f, &mask, &perm);
+    const Pol::Params p = svg::make_band_params<Pol, __bf16>(band_shape_call(1, S, &mask, &perm));
     Pol::Ctx c{};
     c.perm = token_major != 0;
     for (int row = 0; row < kBN; ++row) {   // one lane's walk over the tiles, as the kernel does it
@@ -1258,7 +1199,7 @@ extern "C" int32_t svg_debug_band_tile_run(int32_t S, const svg_band_mask_t* mas
     const svg_perm_desc_t perm{&flag, vid0, num_frame, frame_size};
     const svg_perm_desc_t* pd = num_frame > 0 ? &perm : nullptr;
     if (check_band_mask(S, mask, pd) != SVG_OK) return -1;
-    const Pol::Params p = svg::make_band_params<Pol, __bf16>(nullptr, nullptr, nullptr, nullptr, 1, S, 1.f, mask, pd);
+    const Pol::Params p = svg::make_band_params<Pol, __bf16>(band_shape_call(1, S, mask, pd));
     if (qt >= p.nqt) return -1;
     Pol::Ctx c{};
     c.perm = token_major != 0;

@@ -228,7 +228,7 @@ static size_t f8_ws_bytes(int BH, int S) {
 // what = 1: pre-pass only, 2: attention on a workspace the pre-pass has filled (same BH, S, perm), 3: both
 template <typename T>
 static int run_f8(const void* q, const void* k, const void* v, void* o, int BH, int S, float sm_scale, const svg_band_mask_t* mask,
-                  const svg_perm_desc_t* perm, void* ws, const BandOpts& opts, int what, hipStream_t st) {
+                  const svg_perm_desc_t* perm, void* ws, int what, hipStream_t st) {
     using Pol = BandF8<T>;
     constexpr int D = 128;
     const int S_pad = (S + kBN - 1) / kBN * kBN;
@@ -247,7 +247,7 @@ static int run_f8(const void* q, const void* k, const void* v, void* o, int BH, 
                        has_perm ? perm->num_frame * perm->frame_size : 0, sm_scale * 1.4426950408889634f);
     }
     if (!(what & 2)) return launch_status();
-    const typename Pol::Params p = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
+    const typename Pol::Params p = make_band_params<Pol, T>(BandCall{q, k, v, o, BH, S, D, 0, sm_scale, mask, perm});
     F8Args fa{q8, k8, vt8, scales, S_pad};
     return launch_attn(band_attn_f8_kernel<T>, dim3(p.nqt * BH), 512, attn_f8_lds_bytes<D, 8, 4>(), st, p, fa);
 }
@@ -270,7 +270,7 @@ static int f8_entry(const void* q, const void* k, const void* v, void* o, int32_
     if (const int rc = check_rows(S, D); rc != SVG_OK) return rc;
     if (workspace_bytes < f8_ws_bytes(BH, S)) return SVG_ERR_WORKSPACE;
     return dispatch_td(dtype, D, [&](auto t, auto) {
-        return run_f8<decltype(t)>(q, k, v, o, BH, S, sm_scale, mask, perm, workspace, BandOpts(), what, (hipStream_t)stream);
+        return run_f8<decltype(t)>(q, k, v, o, BH, S, sm_scale, mask, perm, workspace, what, (hipStream_t)stream);
     });
 }
 

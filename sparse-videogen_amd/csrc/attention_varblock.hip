@@ -457,7 +457,7 @@ enum class VbBody {
     kF8,            // fp8 gathering body (attn_f8.h; head_dim 128), kVbF8Waves x 32-row q tiles (launch order)
 };
 
-// One variable-block call (the counterpart of BandOpts): the arguments of the entries in their order, then how to run them
+// One variable-block call (the counterpart of BandCall): the arguments of the entries in their order, then how to run them
 struct VbCall {
     const void *q, *k, *v;
     void* o;

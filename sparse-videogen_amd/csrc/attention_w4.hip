@@ -25,16 +25,17 @@ __global__ __launch_bounds__(256, 1) void band_attn_w4_trace_kernel(typename Ban
 #endif
 
 template <typename T, int D>
-static int run_w4(const void* q, const void* k, const void* v, void* o, int BH, int S, float sm_scale, const svg_band_mask_t* mask,
-                  const svg_perm_desc_t* perm, const BandOpts& opts, hipStream_t st) {
+static int run_w4(const BandCall& c) {
     using Pol = BandW4<T, D>;
-    const typename Pol::Params p = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, perm, opts);
-    if (opts.trace) {
+    const int BH = c.BH;
+    const hipStream_t st = c.stream;
+    const typename Pol::Params p = make_band_params<Pol, T>(c);
+    if (c.trace) {
 #ifdef SVG_ABLATIONS
         if constexpr (D == 128 && std::is_same<T, __bf16>::value) {
             g_trace_reader = read_trace_here;
 #define SVG_W4_TRACE(A) case A: return launch_attn(band_attn_w4_trace_kernel<T, D, A>, dim3(p.nqt * BH), 256, attn_w4_lds_bytes<D>(), st, p);
-            switch (opts.trace_abl) {
+            switch (c.trace_abl) {
                 SVG_W4_TRACE(0) SVG_W4_TRACE(1) SVG_W4_TRACE(2) SVG_W4_TRACE(3) SVG_W4_TRACE(4) SVG_W4_TRACE(5) SVG_W4_TRACE(6)
                 default: return SVG_ERR_UNSUPPORTED;
             }
@@ -46,11 +47,8 @@ static int run_w4(const void* q, const void* k, const void* v, void* o, int BH, 
     return launch_attn(band_attn_w4_kernel<T, D>, dim3(p.nqt * BH), 256, attn_w4_lds_bytes<D>(), st, p);
 }
 
-int run_band_w4(const void* q, const void* k, const void* v, void* o, int BH, int S, int D, int dtype, float sm_scale,
-                const svg_band_mask_t* mask, const svg_perm_desc_t* perm, const BandOpts& opts, hipStream_t st) {
-    return dispatch_td(dtype, D, [&](auto t, auto d) {
-        return run_w4<decltype(t), decltype(d)::value>(q, k, v, o, BH, S, sm_scale, mask, perm, opts, st);
-    });
+int run_band_w4(const BandCall& c) {
+    return dispatch_td(c.dtype, c.D, [&](auto t, auto d) { return run_w4<decltype(t), decltype(d)::value>(c); });
 }
 
 }  // namespace svg

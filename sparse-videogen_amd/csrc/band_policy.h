@@ -11,23 +11,47 @@
 
 namespace svg {
 
-// per-call options of a band launch (no process- or thread-global state)
-struct BandOpts {
+// One band call, from its entry to its launch (no process- or thread-global state): what every svg_band_attention* entry is given, in the
+// entries' order, then what single entries add.  An entry fills one and hands it to band_run (attention.hip); the parameter builders below
+// and the launchers read it.
+enum BandForm : int { kBandWhole = 0, kBandWindow, kBandShard, kBandPerHead };
+struct BandCall {
+    const void *q = nullptr, *k = nullptr, *v = nullptr;
+    void* o = nullptr;         // (the *_f32 entries leave it null: band_run puts a stand-in of o32 here)
+    int32_t BH = 0, S = 0, D = 0, dtype = 0;
+    float sm_scale = 1.f;
+    const svg_band_mask_t* mask = nullptr;
+    const svg_perm_desc_t* perm = nullptr;
+    const svg_attn_layout_t* layout = nullptr;   // the tensors as the ABI describes them, or nullptr: contiguous [BH, S, D]
+    hipStream_t stream = nullptr;
+    int32_t variant = 0;       // schedule (svg_band_attention); 0: the default of the head size
     int32_t* done = nullptr;   // completion counters (svg_band_attention_notify*), or nullptr
+    int32_t done_words = 0;    // ... as many words
     int done_nseg = 1;         // counters per head
     bool prescaled = false;    // q carries sm_scale * log2(e) (svg_band_attention_prescaled; two-phase body only)
     bool trace = false;        // diagnostics builds: the traced kernel (svg_debug_pp_trace)
     int trace_abl = 0;         // ... and its timing ablation
-    bool strided = false;      // `lay` describes the tensors (svg_band_attention_strided); otherwise contiguous [BH, S, D]
-    AttnLayout lay{};
+    bool strided = false;      // `lay` describes the tensors (set with `layout`; svg_band_attention_strided sets it whatever `layout` is)
+    AttnLayout lay{};          // `layout`, checked (band_run)
     // device switch (svg_band_attention_switch*): `*use_alt != 0` on the device selects alt_mask without the layout permutation
     const svg_band_mask_t* alt_mask = nullptr;
     const int32_t* use_alt = nullptr;
     float* lse = nullptr;      // row log-sum-exp output, contiguous fp32 [BH, S] (svg_band_attention_lse: BandLsePolicy), or nullptr
     float* o32 = nullptr;      // with lse: fp32 rows, contiguous [BH, S, 128], instead of o (svg_band_attention_lse_f32: BandF32Policy)
-    // with lse: q / o / lse / o32 hold the rows of q_shard, k / v those of k_shard (svg_band_shard_attention_lse[_f32]: BandShardOf); both or none
+    BandForm form = kBandWhole;
+    // kBandWindow (with lse): q / o / lse / o32 hold the rows [q_begin, q_begin + win_Sq), k / v the keys [k_begin, k_begin + win_Sk)
+    int32_t q_begin = 0, win_Sq = 0, k_begin = 0, win_Sk = 0;
+    // kBandShard (with lse): q / o / lse / o32 hold the rows of q_shard, k / v those of k_shard (BandShardOf)
     const svg_band_shard_t* q_shard = nullptr;
     const svg_band_shard_t* k_shard = nullptr;
+    // kBandPerHead (with lse): one band per head (BandPerHeadLsePolicy), on the work queue where `queue` is set and a queue is to be had
+    const int32_t* band = nullptr;
+    bool queue = false;
+
+    // rows of q / o and of k / v: the window's, the (checked) shard's of the video `perm` describes, or S
+    static int shard_rows(const svg_band_shard_t* s, const svg_perm_desc_t* perm) { return perm->frame_size * s->n_frames + s->n_tail; }
+    int Sq() const { return form == kBandWindow ? win_Sq : form == kBandShard ? shard_rows(q_shard, perm) : S; }
+    int Sk() const { return form == kBandWindow ? win_Sk : form == kBandShard ? shard_rows(k_shard, perm) : S; }
 };
 
 // the mask and the head permutation of a band call over S rows (mask != nullptr)
@@ -1131,17 +1155,20 @@ inline void band_row_regions(typename Pol::Params& p, int S, int row_lo, int row
     }
 }
 
+// parameters of a launch of call `c` under c.mask and c.perm (the tensors may be null: the host-side walks of the svg_debug_* entries)
 template <typename Pol, typename T>
-inline typename Pol::Params make_band_params(const void* q, const void* k, const void* v, void* o, int BH, int S, float sm_scale,
-                                             const svg_band_mask_t* mask, const svg_perm_desc_t* perm, const BandOpts& opts = BandOpts()) {
+inline typename Pol::Params make_band_params(const BandCall& c) {
+    const int BH = c.BH, S = c.S;
+    const svg_band_mask_t* const mask = c.mask;
+    const svg_perm_desc_t* const perm = c.perm;
     typename Pol::Params p;
-    p.q = (const T*)q, p.k = (const T*)k, p.v = (const T*)v, p.o = (T*)o;
-    p.lay = opts.strided ? opts.lay : contiguous_layout(BH, BH, S, S, Pol::kHeadDim);
+    p.q = (const T*)c.q, p.k = (const T*)c.k, p.v = (const T*)c.v, p.o = (T*)c.o;
+    p.lay = c.strided ? c.lay : contiguous_layout(BH, BH, S, S, Pol::kHeadDim);
     p.S = S, p.BH = BH, p.nqt = (S + Pol::BM - 1) / Pol::BM;
-    p.scale_log2 = sm_scale * 1.4426950408889634f;
+    p.scale_log2 = c.sm_scale * 1.4426950408889634f;
     p.real_len = mask->real_len, p.band = mask->band;
     p.cf_lo = mask->colfull_lo, p.cf_hi = mask->colfull_hi, p.rf_lo = mask->rowfull_lo, p.rf_hi = mask->rowfull_hi;
-    p.done = opts.done, p.done_nseg = 1, p.done_tps = 1 << 30;   // (done_tps is set once nqt is known, below)
+    p.done = c.done, p.done_nseg = 1, p.done_tps = 1 << 30;   // (done_tps is set once nqt is known, below)
     p.head_flag = nullptr, p.vid0 = 0, p.F = 1, p.P = 1, p.V = 0;
     if (perm && perm->head_perm_flag) {
         p.head_flag = perm->head_perm_flag;
@@ -1151,22 +1178,21 @@ inline typename Pol::Params make_band_params(const void* q, const void* k, const
     p.q128 = 2 * kBN / p.F, p.r128 = 2 * kBN % p.F;
     p.sp64 = p.q64 + p.r64 * p.P, p.sp128 = p.q128 + p.r128 * p.P;
     p.wrap_phys = 1 - p.F * p.P;
-    band_row_regions<Pol>(p, S, 0, S, opts.done_nseg);
+    band_row_regions<Pol>(p, S, 0, S, c.done_nseg);
     // what the LSE / fp32 policies (BandLsePolicy, BandF32Policy and what is built on them) add: lse, and o32 in the place of the 16-bit o
-    if constexpr (std::is_base_of_v<BandLsePolicy<T>, Pol>) p.lse = opts.lse;
-    if constexpr (std::is_base_of_v<BandF32Policy<T>, Pol>) p.o32 = opts.o32, p.o = nullptr;
+    if constexpr (std::is_base_of_v<BandLsePolicy<T>, Pol>) p.lse = c.lse;
+    if constexpr (std::is_base_of_v<BandF32Policy<T>, Pol>) p.o32 = c.o32, p.o = nullptr;
     return p;
 }
 
 // parameters of a window launch (BandWindowOf): those of the sequence of S rows, the row regions intersected with the row window — heavy_lo,
-// n_heavy and nqt follow the clipped regions — and the tensors as [BH, Sq | Sk, D] (or `opts.lay`)
+// n_heavy and nqt follow the clipped regions — and the tensors as [BH, Sq | Sk, D] (or `c.lay`)
 template <typename Pol, typename T>
-inline typename Pol::Params make_band_window_params(const void* q, const void* k, const void* v, void* o, int BH, int S, int q_begin, int Sq,
-                                                    int k_begin, int Sk, float sm_scale, const svg_band_mask_t* mask, const BandOpts& opts) {
-    typename Pol::Params p = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, nullptr, opts);
-    if (!opts.strided) p.lay = contiguous_layout(BH, BH, Sq, Sk, Pol::kHeadDim);
-    p.q_begin = q_begin, p.Sq = Sq, p.k_begin = k_begin, p.k_end = k_begin + Sk;
-    band_row_regions<Pol>(p, S, q_begin, q_begin + Sq, 1);
+inline typename Pol::Params make_band_window_params(const BandCall& c) {
+    typename Pol::Params p = make_band_params<Pol, T>(c);   // (the window entries take no head permutation: c.perm is null)
+    if (!c.strided) p.lay = contiguous_layout(c.BH, c.BH, c.win_Sq, c.win_Sk, Pol::kHeadDim);
+    p.q_begin = c.q_begin, p.Sq = c.win_Sq, p.k_begin = c.k_begin, p.k_end = c.k_begin + c.win_Sk;
+    band_row_regions<Pol>(p, c.S, c.q_begin, c.q_begin + c.win_Sq, 1);
     return p;
 }
 
@@ -1202,16 +1228,17 @@ inline int band_shard_regions(const typename Pol::Params& p, int kind, int* lo, 
 
 // parameters of a shard launch (BandShardOf): those of the sequence of S rows with the video geometry of `perm` (its flags may be null: every
 // head in logical order), the two shard maps, the row regions of both head kinds — nqt is the larger count — and the tensors as
-// [BH, Sq | Sk, D] (or `opts.lay`)
+// [BH, Sq | Sk, D] (or `c.lay`)
 template <typename Pol, typename T>
-inline typename Pol::Params make_band_shard_params(const void* q, const void* k, const void* v, void* o, int BH, int S, float sm_scale,
-                                                   const svg_band_mask_t* mask, const svg_perm_desc_t* perm, const svg_band_shard_t& q_shard,
-                                                   const svg_band_shard_t& k_shard, const BandOpts& opts) {
-    typename Pol::Params p = make_band_params<Pol, T>(q, k, v, o, BH, S, sm_scale, mask, nullptr, opts);
+inline typename Pol::Params make_band_shard_params(const BandCall& c) {
+    const svg_perm_desc_t* const perm = c.perm;
+    BandCall whole = c;   // (the strides of the row cursor are those of a call without a head permutation)
+    whole.perm = nullptr;
+    typename Pol::Params p = make_band_params<Pol, T>(whole);
     p.head_flag = perm->head_perm_flag;
     p.vid0 = perm->vid0, p.F = perm->num_frame, p.P = perm->frame_size, p.V = perm->num_frame * perm->frame_size;
-    p.qs = make_band_shard_map(q_shard, p.vid0, p.F, p.P), p.ks = make_band_shard_map(k_shard, p.vid0, p.F, p.P);
-    if (!opts.strided) p.lay = contiguous_layout(BH, BH, p.qs.n, p.ks.n, Pol::kHeadDim);
+    p.qs = make_band_shard_map(*c.q_shard, p.vid0, p.F, p.P), p.ks = make_band_shard_map(*c.k_shard, p.vid0, p.F, p.P);
+    if (!c.strided) p.lay = contiguous_layout(c.BH, c.BH, p.qs.n, p.ks.n, Pol::kHeadDim);
     p.nqt = band_shard_regions<Pol>(p, 0, p.reg_lo, p.reg_hi, p.reg_t0);
     const int nqt1 = band_shard_regions<Pol>(p, 1, p.reg1_lo, p.reg1_hi, p.reg1_t0);
     if (p.head_flag) p.nqt = std::max(p.nqt, nqt1);
@@ -1220,8 +1247,7 @@ inline typename Pol::Params make_band_shard_params(const void* q, const void* k,
 }
 
 // 4 waves x 64 rows, one wave per SIMD (attn_body_w4, attention_w4.hip)
-int run_band_w4(const void* q, const void* k, const void* v, void* o, int BH, int S, int D, int dtype, float sm_scale,
-                const svg_band_mask_t* mask, const svg_perm_desc_t* perm, const BandOpts& opts, hipStream_t st);
+int run_band_w4(const BandCall& c);
 // waves that report per 256-row q-tile of the kernel `variant` selects (completion-counter targets); -1: no counters
 int band_waves_per_tile(int variant);
 

@@ -34,14 +34,12 @@ def band_attention_per_head(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, m
     launch).  work_queue=True: the same bits from resident workgroups on the work queue (svg_band_attention_per_head_queue_lse,
     include/svg_attn_band_per_head_queue.h)."""
     BH, S, D = _checked("band_attention_per_head", q, k, v, band, head_perm_flag, out)
-    lib = _native.load()
+    _native.load()
     perm = _native._perm_arg(head_perm_flag, BH, vid0, num_frame, frame_size)
     lse = _native.empty(q.shape[:-1], dtype=torch.float32, device=q.device)   # (contiguous [BH, S] whatever the layout of q / o)
     p = _native._layout_plan(q, k, v, out=out, token_major_out=token_major_out)
     name = "svg_band_attention_per_head_queue_lse" if work_queue else "svg_band_attention_per_head_lse"
-    rc = getattr(lib, name)(p.q.data_ptr(), p.k.data_ptr(), p.v.data_ptr(), p.o.data_ptr(), lse.data_ptr(), BH, S, D, _native._dtype_code(q),
-                            _native._sm_scale(sm_scale, D), C.byref(mask), band.data_ptr(), perm, p.lay, _native._stream())
-    _native._check(rc, name)
+    _native._call_lse(name, False, p, lse, BH, S, D, _native._dtype_code(q), _native._sm_scale(sm_scale, D), C.byref(mask), band.data_ptr(), perm)
     return (p.result(), lse) if return_lse else p.result()
 
 
@@ -56,13 +54,11 @@ def band_attention_switch_per_head(q: torch.Tensor, k: torch.Tensor, v: torch.Te
     BH, S, D = _checked("band_attention_switch_per_head", q, k, v, band, head_perm_flag, out)
     _native._dev(use_alt_flag)
     assert use_alt_flag.dtype == torch.int32 and use_alt_flag.numel() >= 1
-    lib = _native.load()
+    _native.load()
     perm = _native._perm_arg(head_perm_flag, BH, vid0, num_frame, frame_size)
     lse = _native.empty(q.shape[:-1], dtype=torch.float32, device=q.device)
     p = _native._layout_plan(q, k, v, out=out, token_major_out=token_major_out)
     name = "svg_band_attention_switch_per_head_queue_lse" if work_queue else "svg_band_attention_switch_per_head_lse"
-    rc = getattr(lib, name)(p.q.data_ptr(), p.k.data_ptr(), p.v.data_ptr(), p.o.data_ptr(), lse.data_ptr(), BH, S, D, _native._dtype_code(q),
-                            _native._sm_scale(sm_scale, D), C.byref(mask), C.byref(alt_mask), use_alt_flag.data_ptr(), band.data_ptr(), perm,
-                            p.lay, _native._stream())
-    _native._check(rc, name)
+    _native._call_lse(name, False, p, lse, BH, S, D, _native._dtype_code(q), _native._sm_scale(sm_scale, D), C.byref(mask), C.byref(alt_mask),
+                      use_alt_flag.data_ptr(), band.data_ptr(), perm)
     return (p.result(), lse) if return_lse else p.result()

@@ -726,6 +726,16 @@ def band_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Band
                            q_prescaled, token_major_out)
 
 
+def _call_lse(name: str, f32: bool, p, lse: torch.Tensor, *geom) -> None:
+    """The launch of LSE entry `name` (f32: of its *_f32 form) on layout plan p: the five pointers, the entry's own arguments `geom`, the
+    layout, the stream; a failure raises under the entry's name.  Allocates nothing: lse is the caller's.  For the window, shard and per-head
+    wrappers; band_attention, band_attention_switch and band_attention_groups spell their calls out, which the call-site walks of
+    tests/test_sparse_attention_lse_cpu.py, test_attention_f32_parts_cpu.py and test_band_lse_forms_cpu.py read."""
+    if f32:
+        name += "_f32"
+    _check(getattr(load(), name)(p.q.data_ptr(), p.k.data_ptr(), p.v.data_ptr(), p.o.data_ptr(), lse.data_ptr(), *geom, p.lay, _stream()), name)
+
+
 def _band_attention_lse(q, k, v, mask, sm_scale, head_perm_flag, vid0, num_frame, frame_size, out, token_major_out, f32=False):
     """band_attention(return_lse=True): svg_band_attention_lse (f32: svg_band_attention_lse_f32), never the entry without lse.  Layouts
     and copies: _layout_plan."""
@@ -1078,15 +1088,10 @@ def band_window_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
         o.zero_()
         lse.fill_(float("-inf"))
         return o, lse
-    lib = load()
+    load()
     BH = q.numel() // (Sq * D)
-    geom = (BH, S, q_begin, Sq, k_begin, Sk, D, _dtype_code(q), _sm_scale(None, D), C.byref(mask))
     p = _layout_plan(q, k, v, o=_O32 if f32 else _O16, out=out)
-    ptrs = (p.q.data_ptr(), p.k.data_ptr(), p.v.data_ptr(), p.o.data_ptr(), lse.data_ptr())
-    if f32:
-        _check(lib.svg_band_window_attention_lse_f32(*ptrs, *geom, p.lay, _stream()), "svg_band_window_attention_lse_f32")
-    else:
-        _check(lib.svg_band_window_attention_lse(*ptrs, *geom, p.lay, _stream()), "svg_band_window_attention_lse")
+    _call_lse("svg_band_window_attention_lse", f32, p, lse, BH, S, q_begin, Sq, k_begin, Sk, D, _dtype_code(q), _sm_scale(None, D), C.byref(mask))
     return p.result(), lse
 
 
@@ -1267,7 +1272,7 @@ def _band_shard_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
         flag = flags.to(torch.int64).contiguous()
         if flag.numel() != BH:
             raise ValueError(f"band_shard_attention: {flag.numel()} flags for {BH} heads")
-    lib = load()
+    load()
     lse = empty(q.shape[:-1], dtype=torch.float32, device=q.device)
     pd = PermDesc(_ptr(flag), vid0, F, P)
     geom = (BH, S, D, _dtype_code(q), _sm_scale(None, D), C.byref(mask), C.byref(pd))
@@ -1275,11 +1280,8 @@ def _band_shard_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mas
     if _switch is not None:   # the device switch: alt_mask and the flag behind perm, the entries of include/svg_attn_band_shard_switch.h
         geom += (C.byref(alt_mask), use_alt_flag.data_ptr())
         name = "svg_band_shard_attention_switch_lse"
-    geom += (C.byref(qs), C.byref(ks))
-    if f32:
-        name += "_f32"
     p = _layout_plan(q, k, v, o=_O32 if f32 else _O16, out=out)
-    _check(getattr(lib, name)(p.q.data_ptr(), p.k.data_ptr(), p.v.data_ptr(), p.o.data_ptr(), lse.data_ptr(), *geom, p.lay, _stream()), name)
+    _call_lse(name, f32, p, lse, *geom, C.byref(qs), C.byref(ks))
     return p.result(), lse
 
 

@@ -79,7 +79,7 @@ def test_header_prototypes_match_the_ctypes_signatures():
 
 # ---------------------------------------------------------------------------------------------------------
 # argument validation: the table of the shard entries (tests/test_band_shard_cpu.py), every row with the same code, and the rows of the
-# two new arguments — NULL with the first check, alt_mask against S where band_dispatch checks it (behind mask and the size limits)
+# two new arguments — NULL with the first check, alt_mask against S where band_run checks it (behind mask and the size limits)
 # ---------------------------------------------------------------------------------------------------------
 def switch_args(alt="ok", null_alt=False, flag=PH, **kw):
     args = B.shard_args(**kw)
