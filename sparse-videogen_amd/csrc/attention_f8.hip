@@ -58,11 +58,6 @@ __device__ __forceinline__ int f8_phys_row(int logical, bool perm, int vid0, int
     return logical;
 }
 
-__device__ __forceinline__ unsigned f8_pack4(float a, float b, float c, float d) {
-    int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-    return (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void f8_quantize_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
                                                           uint8_t* __restrict__ q8, uint8_t* __restrict__ k8, uint8_t* __restrict__ vt8,

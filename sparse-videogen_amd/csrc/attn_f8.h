@@ -46,6 +46,25 @@ __device__ __forceinline__ f32x16 mfma_f8(i32x8 a, i32x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 0, 0, 0, kF8Scale127, 0, kF8Scale127);
 }
 
+// four floats -> four e4m3 bytes (round to nearest even), byte i = argument i
+__device__ __forceinline__ unsigned f8_pack4(float a, float b, float c, float d) {
+    int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+    return (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
+}
+
+// Per-ROW power-of-two scales (the e4m3 k-means assignment, kmeans.hip): the largest e with m * 2^e <= 448 for a row maximum m > 0,
+// e = floor(log2(448 / m)), from the bits of m — m = f * 2^x with f in [0.5, 1) and 448 = 0.875 * 2^9, so e = 9 - x for f <= 0.875 and
+// 8 - x above.  0 for m = 0; at most 127 (a row maximum below 2^-118: its bytes are then smaller than they could be, never larger), so that
+// 127 - e is an E8M0 block scale in [0, 248].  The row's bytes are e4m3_rne(r_d * 2^e): they never saturate.
+__device__ __forceinline__ int f8_row_exponent(float m) {
+    if (!(m > 0.f)) return 0;
+    const unsigned u = __float_as_uint(m);
+    const int e = ((u & 0x7fffffu) <= 0x600000u ? 9 : 8) - ((int)(u >> 23) - 126);
+    return e < 127 ? e : 127;
+}
+// the E8M0 scale word of a row quantised with exponent e: 2^-e in every byte (whatever op_sel picks)
+__device__ __forceinline__ int f8_row_scale_word(int e) { return (127 - e) * 0x01010101; }
+
 template <int D, int NW = 8, int NS = 2>
 constexpr int attn_f8_lds_bytes() {
     constexpr int stages = NS * (2 * kBN * D);           // NS stages of [K image | V^T image], one byte per element

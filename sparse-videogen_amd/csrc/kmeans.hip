@@ -12,7 +12,7 @@
 //            (fp32), so centroids are bit-reproducible run to run (the reference's atomics are not).
 #include <algorithm>
 
-#include "attn_core.h"
+#include "attn_f8.h"
 
 extern "C" size_t svg_argsort_workspace_bytes(int32_t B, int32_t N, int32_t K);
 extern "C" int svg_argsort_labels(const int32_t* labels, int32_t* sorted_idx, int32_t* counts, int32_t B, int32_t N,
@@ -483,6 +483,239 @@ __global__ __launch_bounds__(256) void kmeans_select_kernel(const T* __restrict_
         ((V8*)out)[o + i] = ((const V8*)src)[o + i];
 }
 
+
+// =====================================================================================================================================
+// e4m3 assignment (include/svg_attn_kmeans_e4m3.h): the scores of kmeans_assign_kernel on v_mfma_scale_f32_32x32x64_f8f6f4 — 4 MFMAs per
+// 64-centroid tile in place of 16, at twice the 16-bit rate per MFMA cycle.  Per batch, with a centre mu[128] (fp32; the caller's, or the
+// channel mean of the loop's initial centroids — |x - c|^2 does not depend on it, it only keeps a common offset out of the 3-bit mantissa):
+//   a row r = x_n - mu or c_k - mu (fp32) is quantised with a power-of-two scale of its own, e = f8_row_exponent(max_d |r_d|),
+//   q(r)_d = e4m3_rne(r_d 2^e), and stands for q(r) 2^-e: the exponents travel as the instruction's E8M0 block scales (a lane's 32 bytes are
+//   one block: half a row), so  s_k = fp32 sum_d q(x - mu)_d q(c_k - mu)_d 2^-(e_x + e_k) - csq'_k / 2,  csq'_k the fp32 |c_k - mu|^2 of the
+//   UNquantised row.  The label is the lowest index of the maximum, through the epilogue of kmeans_assign_kernel.
+// Points are centred and quantised in registers when a workgroup loads them (the two lanes of a point share the row maximum); centroids
+// by a pre-pass per call into an image [B, K, 128] + scale bytes + csq' (they are read by every workgroup of the batch).
+// =====================================================================================================================================
+// mu[b][d] = mean_k c[b][k][d] in fp32: grid = B, block = 256 = 16 row slots x 16 lanes, the slots' partial sums added in a fixed order
+template <typename T>
+__global__ __launch_bounds__(256) void kmeans_centre_kernel(const T* __restrict__ c, float* __restrict__ mu, int K) {
+    constexpr int D = 128, LPR = D / 8, SLOTS = 256 / LPR;
+    __shared__ float red[SLOTS][D + 4];
+    using V8 = typename Elt<T>::v8;
+    const int b = blockIdx.x, tid = threadIdx.x, slot = tid / LPR, li = tid - slot * LPR;
+    const T* cb = c + (size_t)b * K * D;
+    float acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+    for (int k = slot; k < K; k += SLOTS) {
+        const V8 v = *(const V8*)(cb + (size_t)k * D + li * 8);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] += Elt<T>::to_float(v[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) red[slot][li * 8 + j] = acc[j];
+    __syncthreads();
+    if (tid < D) {
+        float s = 0.f;
+        for (int sl = 0; sl < SLOTS; ++sl) s += red[sl][tid];
+        mu[(size_t)b * D + tid] = s / (float)K;
+    }
+}
+
+// the centroid pre-pass of one e4m3 assignment: c8 [B, K, 128] e4m3, cscale int32 [B, K] (the E8M0 byte 127 - e), csq float [B, K]
+// (|c - mu|^2 of the unquantised row).  16 lanes per row, 8 channels each.
+template <typename T>
+__global__ __launch_bounds__(256) void kmeans_e4m3_centroids_kernel(const T* __restrict__ c, const float* __restrict__ mu /* [B, 128] or NULL */,
+                                                                    uint8_t* __restrict__ c8, int32_t* __restrict__ cscale,
+                                                                    float* __restrict__ csq, int K, long long rows) {
+    constexpr int D = 128;
+    using V8 = typename Elt<T>::v8;
+    const int sub = threadIdx.x >> 4, li = threadIdx.x & 15;
+    for (long long r = (long long)blockIdx.x * 16 + sub; r < rows; r += (long long)gridDim.x * 16) {
+        const V8 v = *(const V8*)(c + r * D + li * 8);
+        f32x4 m0 = {0.f, 0.f, 0.f, 0.f}, m1 = m0;
+        if (mu) {
+            const float* mp = mu + (r / K) * D + li * 8;
+            m0 = *(const f32x4*)mp, m1 = *(const f32x4*)(mp + 4);
+        }
+        float d[8], s = 0.f, mx = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            d[j] = Elt<T>::to_float(v[j]) - (j < 4 ? m0[j] : m1[j - 4]);
+            s += d[j] * d[j];
+            mx = fmaxf(mx, fabsf(d[j]));
+        }
+#pragma unroll
+        for (int o = 8; o >= 1; o >>= 1) s += __shfl_xor(s, o), mx = fmaxf(mx, __shfl_xor(mx, o));
+        const int e = f8_row_exponent(mx);
+        *(u32x2*)(c8 + r * D + li * 8) = u32x2{f8_pack4(ldexpf(d[0], e), ldexpf(d[1], e), ldexpf(d[2], e), ldexpf(d[3], e)),
+                                               f8_pack4(ldexpf(d[4], e), ldexpf(d[5], e), ldexpf(d[6], e), ldexpf(d[7], e))};
+        if (li == 0) cscale[r] = 127 - e, csq[r] = s;
+    }
+}
+
+// ---- e4m3 assignment: grid = (ceil(N / 256), B), block = 512: the staging, double buffer and arg-max of kmeans_assign_kernel<T, 128, 8> ----
+// LDS stage: the tile's centroid image [64][128] bytes in the K layout of attn_f8.h (f8_k_off), its 64 start values -csq' / 2 (-inf behind K)
+// and its 64 scale words.  Operands: A = centroid row 32 bb + ql, bytes [64 ks + 32 g, +32), B = the point's bytes of the same channels.
+template <typename T>
+__global__ __launch_bounds__(512, 2) void kmeans_assign_e4m3_kernel(const T* __restrict__ x, const float* __restrict__ mu,
+                                                                    const uint8_t* __restrict__ c8, const int32_t* __restrict__ cscale,
+                                                                    const float* __restrict__ csq, int32_t* __restrict__ labels, int N, int K,
+                                                                    long long x_bs /* elements between the batches of x */) {
+    using E = Elt<T>;
+    using V8 = typename E::v8;
+    constexpr int D = 128, NW = 8, KS = D / 64;
+    constexpr int kKBytes = kBN * D;                   // one byte per element
+    constexpr int kStage = kKBytes + kBN * 4 + kBN * 4;
+    static_assert(kBN * (D / 16) == NW * 64, "one 16-byte chunk of a centroid tile per thread");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+
+    const int b = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
+    const int g = lane >> 5, ql = lane & 31;
+    const int n = blockIdx.x * (NW * 32) + wave * 32 + ql;
+    const T* xb = x + (size_t)b * (size_t)x_bs;
+    const uint8_t* c8b = c8 + (size_t)b * K * D;
+    const float* csqb = csq + (size_t)b * K;
+    const int32_t* cscb = cscale + (size_t)b * K;
+
+    // the point: channels [64 ks + 32 g, +32) centred in fp32, the row maximum from both lanes, quantised in place
+    i32x8 xf[KS];
+    int x_scale;
+    {
+        const T* xrow = xb + (size_t)(n < N ? n : 0) * D + g * 32;
+        const float* mub = mu ? mu + (size_t)b * D + g * 32 : nullptr;
+        float r[KS][32], mx = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const V8 v = *(const V8*)(xrow + ks * 64 + c * 8);
+                f32x4 m0 = {0.f, 0.f, 0.f, 0.f}, m1 = m0;
+                if (mub) m0 = *(const f32x4*)(mub + ks * 64 + c * 8), m1 = *(const f32x4*)(mub + ks * 64 + c * 8 + 4);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float d = E::to_float(v[j]) - (j < 4 ? m0[j] : m1[j - 4]);
+                    r[ks][c * 8 + j] = d;
+                    mx = fmaxf(mx, fabsf(d));
+                }
+            }
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        const int e = f8_row_exponent(mx);
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+            for (int w = 0; w < 8; ++w)
+                xf[ks][w] = (int)f8_pack4(ldexpf(r[ks][4 * w], e), ldexpf(r[ks][4 * w + 1], e), ldexpf(r[ks][4 * w + 2], e),
+                                          ldexpf(r[ks][4 * w + 3], e));
+        x_scale = f8_row_scale_word(e);
+    }
+
+    const int srow = tid >> 3, scol = tid & 7;
+    const int k_dst = f8_k_off(srow, scol);
+    u32x4 creg;
+    float sreg = 0.f;
+    int ereg = 0;
+    bool sreg_ok = false;
+    const int nT = (K + kBN - 1) / kBN;
+    auto issue = [&](int t) {
+        const int c = t * kBN + srow;
+        creg = *(const u32x4*)(c8b + (size_t)(c < K ? c : 0) * D + scol * 16);
+        if (tid < kBN) {   // (used in write() only, like kmeans_assign_kernel's |c|^2)
+            const int ck = t * kBN + tid;
+            sreg = csqb[ck < K ? ck : 0];
+            ereg = cscb[ck < K ? ck : 0];
+            sreg_ok = ck < K;
+        }
+    };
+    auto write = [&](int buf) {
+        char* base = smem + buf * kStage;
+        *(u32x4*)(base + k_dst) = creg;
+        if (tid < kBN) {
+            *(float*)(base + kKBytes + tid * 4) = sreg_ok ? -0.5f * sreg : -INFINITY;   // centroids behind K can never win
+            *(int*)(base + kKBytes + kBN * 4 + tid * 4) = ereg * 0x01010101;
+        }
+    };
+
+    issue(0);
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(xf[ks]));
+    write(0);
+    if (nT > 1) issue(1);
+    __syncthreads();
+
+    const int ksw = (ql >> 1) & 7;
+    float best = -INFINITY;
+    int best_idx = 0;
+    for (int t = 0; t < nT; ++t) {
+        const int buf = t & 1;
+        const char* kbuf = smem + buf * kStage;
+        const float* h_t = (const float*)(kbuf + kKBytes);
+        const int* e_t = (const int*)(kbuf + kKBytes + kBN * 4);
+        f32x16 s[2];
+        int c_scale[2];
+#pragma unroll
+        for (int bb = 0; bb < 2; ++bb) {
+#pragma unroll
+            for (int rq = 0; rq < 4; ++rq) {
+                const f32x4 h4 = *(const f32x4*)(h_t + 32 * bb + 8 * rq + 4 * g);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) s[bb][rq * 4 + j] = h4[j];
+            }
+            c_scale[bb] = e_t[32 * bb + ql];
+        }
+        i32x8 af[KS][2];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+            for (int bb = 0; bb < 2; ++bb) {
+                const char* rowp = kbuf + (32 * bb + ql) * D;
+                const u32x4 lo = *(const u32x4*)(rowp + (((4 * ks + 2 * g) ^ ksw) << 4));
+                const u32x4 hi = *(const u32x4*)(rowp + (((4 * ks + 2 * g + 1) ^ ksw) << 4));
+                af[ks][bb] = i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+            }
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+            for (int bb = 0; bb < 2; ++bb)
+                s[bb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(af[ks][bb], xf[ks], s[bb], 0, 0, 0, c_scale[bb], 0, x_scale);
+        // the arg-max of kmeans_assign_kernel: four chains of eight registers, merged in index order with the same strict compare
+        float cb_[4];
+        int ci_[4];
+#pragma unroll
+        for (int ch = 0; ch < 4; ++ch) {
+            const int bb = ch >> 1, r0 = (ch & 1) * 8;
+            cb_[ch] = s[bb][r0];
+            ci_[ch] = 32 * bb + 8 * (r0 >> 2) + (r0 & 3) + 4 * g;
+#pragma unroll
+            for (int r = r0 + 1; r < r0 + 8; ++r) {
+                const int c = 32 * bb + 8 * (r >> 2) + (r & 3);
+                const bool upd = s[bb][r] > cb_[ch];
+                cb_[ch] = upd ? s[bb][r] : cb_[ch];
+                ci_[ch] = upd ? c + 4 * g : ci_[ch];
+            }
+        }
+        float tb = cb_[0];
+        int ti = ci_[0];
+#pragma unroll
+        for (int ch = 1; ch < 4; ++ch) {
+            const bool upd = cb_[ch] > tb;
+            tb = upd ? cb_[ch] : tb;
+            ti = upd ? ci_[ch] : ti;
+        }
+        const bool upd = tb > best;
+        best = upd ? tb : best;
+        best_idx = upd ? t * kBN + ti : best_idx;
+        if (t + 1 < nT) write(buf ^ 1);
+        if (t + 2 < nT) issue(t + 2);
+        __syncthreads();
+    }
+    // the two lanes of a point cover disjoint centroid subsets: merge, lowest index wins ties
+    const float ob = __shfl_xor(best, 32);
+    const int oi = __shfl_xor(best_idx, 32);
+    if (ob > best || (ob == best && oi < best_idx)) best = ob, best_idx = oi;
+    if (g == 0 && n < N) labels[(size_t)b * N + n] = best_idx;
+}
+
 }  // namespace svg
 
 using namespace svg;
@@ -784,4 +1017,122 @@ extern "C" int svg_kmeans_stepped_finish(const void* c_init, const void* c_work_
         return SVG_ERR_BAD_ARG;
     const KmeansLoopScratch s = kmeans_loop_scratch(workspace, B, 1, K, D, B / group, true);
     return kmeans_loop_finish(s, c_init, c_work_a, c_work_b, centroids_out, n_iters, B, K, D, dtype, group, (hipStream_t)stream);
+}
+
+// ---- the e4m3 assignment and the Lloyd loop that uses it for its first iterations (include/svg_attn_kmeans_e4m3.h) ----
+// scratch of one e4m3 assignment: the centroid image, its scale bytes (one int32 each) and csq'
+struct KmeansE4m3Scratch {
+    uint8_t* c8;
+    int32_t* cscale;
+    float* csq;
+};
+static size_t kmeans_e4m3_image_bytes(int B, int K) { return ((size_t)B * K * 128 + 255) / 256 * 256; }
+static size_t kmeans_e4m3_row_bytes(int B, int K) { return ((size_t)B * K * 4 + 255) / 256 * 256; }
+static size_t kmeans_e4m3_mu_bytes(int B) { return ((size_t)B * 128 * sizeof(float) + 255) / 256 * 256; }
+static KmeansE4m3Scratch kmeans_e4m3_scratch(void* w, int B, int K) {
+    KmeansE4m3Scratch s;
+    s.c8 = (uint8_t*)w;
+    s.cscale = (int32_t*)((char*)w + kmeans_e4m3_image_bytes(B, K));
+    s.csq = (float*)((char*)w + kmeans_e4m3_image_bytes(B, K) + kmeans_e4m3_row_bytes(B, K));
+    return s;
+}
+
+template <typename T>
+static int run_kmeans_assign_e4m3(const void* x, const float* mu, const void* c_in, int32_t* labels, int B, int N, int K,
+                                  const KmeansE4m3Scratch& s, hipStream_t st, long long x_bs) {
+    const long long rows = (long long)B * K;
+    hipLaunchKernelGGL((kmeans_e4m3_centroids_kernel<T>), dim3((unsigned)std::min<long long>(2048, (rows + 15) / 16)), dim3(256), 0, st,
+                       (const T*)c_in, mu, s.c8, s.cscale, s.csq, K, rows);
+    constexpr int lds = 2 * (kBN * 128 + kBN * 8);
+    hipLaunchKernelGGL((kmeans_assign_e4m3_kernel<T>), dim3((N + 255) / 256, B), dim3(512), lds, st, (const T*)x, mu, s.c8, s.cscale, s.csq,
+                       labels, N, K, x_bs);
+    return launch_status();
+}
+
+static bool kmeans_e4m3_covers(int32_t K, int32_t D, int32_t dtype) {
+    return K <= 8192 && D == 128 && (dtype == SVG_DTYPE_BF16 || dtype == SVG_DTYPE_F16);
+}
+
+extern "C" int svg_kmeans_centre(const void* centroids, float* mu, int32_t B, int32_t K, int32_t D, int32_t dtype, void* stream) {
+    if (!centroids || !mu || B <= 0 || K <= 0) return SVG_ERR_BAD_ARG;
+    if (!kmeans_e4m3_covers(K, D, dtype)) return SVG_ERR_UNSUPPORTED;
+    if (dtype == SVG_DTYPE_BF16)
+        hipLaunchKernelGGL((kmeans_centre_kernel<__bf16>), dim3(B), dim3(256), 0, (hipStream_t)stream, (const __bf16*)centroids, mu, K);
+    else
+        hipLaunchKernelGGL((kmeans_centre_kernel<_Float16>), dim3(B), dim3(256), 0, (hipStream_t)stream, (const _Float16*)centroids, mu, K);
+    return launch_status();
+}
+
+extern "C" size_t svg_kmeans_assign_e4m3_workspace_bytes(int32_t B, int32_t N, int32_t K, int32_t D) {
+    if (B <= 0 || N <= 0 || K <= 0 || K > 8192 || D != 128) return 0;
+    return kmeans_e4m3_image_bytes(B, K) + 2 * kmeans_e4m3_row_bytes(B, K);
+}
+
+extern "C" int svg_kmeans_assign_e4m3(const void* x, const void* centroids, const float* mu, int32_t* labels, int32_t B, int32_t N, int32_t K,
+                                      int32_t D, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!x || !centroids || !labels || !workspace || B <= 0 || N <= 0 || K <= 0) return SVG_ERR_BAD_ARG;   // (mu may be NULL: zeros)
+    if (!kmeans_e4m3_covers(K, D, dtype)) return SVG_ERR_UNSUPPORTED;
+    if (workspace_bytes < svg_kmeans_assign_e4m3_workspace_bytes(B, N, K, D)) return SVG_ERR_WORKSPACE;
+    if ((((size_t)x | (size_t)mu) & 15) != 0) return SVG_ERR_UNSUPPORTED;   // (16-byte loads of rows and of mu)
+    const KmeansE4m3Scratch s = kmeans_e4m3_scratch(workspace, B, K);
+    if (dtype == SVG_DTYPE_BF16)
+        return run_kmeans_assign_e4m3<__bf16>(x, mu, centroids, labels, B, N, K, s, (hipStream_t)stream, (long long)N * D);
+    return run_kmeans_assign_e4m3<_Float16>(x, mu, centroids, labels, B, N, K, s, (hipStream_t)stream, (long long)N * D);
+}
+
+// the blocks of svg_kmeans_loop_grouped_workspace_bytes in front (fp8_iters = 0 IS svg_kmeans_loop_grouped_strided on them), then mu and
+// the scratch of one e4m3 assignment
+extern "C" size_t svg_kmeans_loop_e4m3_workspace_bytes(int32_t B, int32_t N, int32_t K, int32_t D, int32_t group) {
+    const size_t loop = svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, group);
+    if (loop == 0 || K > 8192 || D != 128) return 0;
+    return (loop + 255) / 256 * 256 + kmeans_e4m3_mu_bytes(B) + svg_kmeans_assign_e4m3_workspace_bytes(B, N, K, D);
+}
+
+extern "C" int svg_kmeans_loop_e4m3(const void* x, int64_t x_batch_stride, const void* c_init, void* c_work_a, void* c_work_b, int32_t* labels,
+                                    int32_t* counts, int32_t* sorted_idx, void* centroids_out, int32_t* n_iters, int32_t B, int32_t N,
+                                    int32_t K, int32_t D, int32_t dtype, int32_t group, int32_t max_iters, float tol, int32_t fp8_iters,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+    if (!x || !c_init || !c_work_a || !c_work_b || !labels || !counts || !sorted_idx || !centroids_out || !n_iters || !workspace)
+        return SVG_ERR_BAD_ARG;
+    if (B <= 0 || N <= 0 || K <= 0 || max_iters <= 0 || group <= 0 || B % group != 0 || fp8_iters < 0 || fp8_iters > max_iters)
+        return SVG_ERR_BAD_ARG;
+    if (!kmeans_e4m3_covers(K, D, dtype)) return SVG_ERR_UNSUPPORTED;
+    if (workspace_bytes < svg_kmeans_loop_e4m3_workspace_bytes(B, N, K, D, group)) return SVG_ERR_WORKSPACE;
+    if (c_init == c_work_a || c_init == c_work_b || c_work_a == c_work_b || centroids_out == c_work_a || centroids_out == c_work_b)
+        return SVG_ERR_BAD_ARG;
+    if (const int rc = check_strided(x, x_batch_stride, N, D); rc != SVG_OK) return rc;
+    const long long x_bs = (long long)x_batch_stride;
+    if (fp8_iters == 0)   // today's loop, call for call
+        return kmeans_loop_impl(x, x_bs, nullptr, c_init, c_work_a, c_work_b, labels, counts, sorted_idx, centroids_out, n_iters, B, N, K, D, dtype,
+                                group, max_iters, tol, workspace, workspace_bytes, stream);
+    hipStream_t st = (hipStream_t)stream;
+    const int G = B / group;
+    const KmeansLoopScratch s = kmeans_loop_scratch(workspace, B, N, K, D, G, false);
+    char* extra = (char*)workspace + (svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, group) + 255) / 256 * 256;
+    float* mu = (float*)extra;
+    const KmeansE4m3Scratch es = kmeans_e4m3_scratch(extra + kmeans_e4m3_mu_bytes(B), B, K);
+    if (const int rc = svg_kmeans_centre(c_init, mu, B, K, D, dtype, stream); rc != SVG_OK) return rc;
+    if (hipMemsetAsync(s.state, 0, (size_t)4 * G * sizeof(int32_t), st) != hipSuccess) return SVG_ERR_LAUNCH;
+    for (int it = 0; it < max_iters; ++it) {
+        if (it < fp8_iters) {   // the centroids rotate as in kmeans_loop_iterate; the update, sort and commit are the 16-bit loop's
+            const void* cur = it == 0 ? c_init : ((it & 1) ? c_work_a : c_work_b);
+            void* out = (it & 1) ? c_work_b : c_work_a;
+            int rc;
+            if (dtype == SVG_DTYPE_BF16) {
+                rc = run_kmeans_assign_e4m3<__bf16>(x, mu, cur, s.t_labels, B, N, K, es, st, x_bs);
+                if (rc == SVG_OK) rc = run_kmeans_update<__bf16, 128>(x, cur, out, s.t_labels, s.t_counts, s.t_sorted, s.t_shift, B, N, K, s.it_ws, st, x_bs);
+            } else {
+                rc = run_kmeans_assign_e4m3<_Float16>(x, mu, cur, s.t_labels, B, N, K, es, st, x_bs);
+                if (rc == SVG_OK) rc = run_kmeans_update<_Float16, 128>(x, cur, out, s.t_labels, s.t_counts, s.t_sorted, s.t_shift, B, N, K, s.it_ws, st, x_bs);
+            }
+            if (rc != SVG_OK) return rc;
+            // an e4m3 iteration never stops a group: a shift is >= 0 or NaN, so nothing is below a tol of -1
+            kmeans_loop_commit(s, nullptr, labels, counts, sorted_idx, it, -1.f, B, N, K, group, st);
+        } else {
+            if (const int rc = kmeans_loop_iterate(s, x, x_bs, nullptr, c_init, c_work_a, c_work_b, it, B, N, K, D, dtype, G, stream); rc != SVG_OK)
+                return rc;
+            kmeans_loop_commit(s, nullptr, labels, counts, sorted_idx, it, tol, B, N, K, group, st);
+        }
+    }
+    return kmeans_loop_finish(s, c_init, c_work_a, c_work_b, centroids_out, n_iters, B, K, D, dtype, group, st);
 }

@@ -380,6 +380,19 @@ KMEANS_STEPPED_SIGNATURES = {
 }
 
 
+# include/svg_attn_kmeans_e4m3.h: the centre, the e4m3 assignment and the Lloyd loop whose first iterations use it, in a table of its own
+# for the same reason (tests/test_kmeans_e4m3_cpu.py; the allocating wrappers kmeans_centre, kmeans_assign_e4m3, kmeans_loop_e4m3: svg/_kmeans_e4m3.py,
+# reachable as attributes of this module — __getattr__ at its end)
+KMEANS_E4M3_SIGNATURES = {
+    "svg_kmeans_centre": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _I32, _VP]),
+    "svg_kmeans_assign_e4m3_workspace_bytes": (_SZ, [_I32, _I32, _I32, _I32]),
+    "svg_kmeans_assign_e4m3": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _SZ, _VP]),
+    "svg_kmeans_loop_e4m3_workspace_bytes": (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    "svg_kmeans_loop_e4m3": (C.c_int, [_VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F32, _I32,
+                                       _VP, _SZ, _VP]),
+}
+
+
 class CopyBox(C.Structure):
     """svg_copy_box_t (include/svg_attn_shard_exchange.h): extent[0] * extent[1] * extent[2] rows of D contiguous elements; offsets and
     strides in elements"""
@@ -417,7 +430,7 @@ def load(strict: bool = True) -> Optional[C.CDLL]:
                                    **BAND_WINDOW_SIGNATURES, **BAND_SHARD_SIGNATURES, **BAND_SHARD_SWITCH_SIGNATURES,
                                    **PROFILE_SHARD_SIGNATURES, **SAMPLE_ROWS_SIGNATURES, **SHARD_EXCHANGE_SIGNATURES,
                                    **ADAPTIVE_TOP_P_SIGNATURES, **ADAPTIVE_BAND_ENTRIES, **ADAPTIVE_BAND_QUEUE_ENTRIES,
-                                   **KMEANS_STEPPED_SIGNATURES}.items():
+                                   **KMEANS_STEPPED_SIGNATURES, **KMEANS_E4M3_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -2503,3 +2516,14 @@ def copy_box_jobs(jobs, D: int, layout: str) -> int:
         ranges.append(at)
     flush()
     return launches
+
+
+def __getattr__(name: str):
+    """kmeans_centre, kmeans_assign_e4m3, kmeans_loop_e4m3: the allocating wrappers of include/svg_attn_kmeans_e4m3.h live in
+    svg/_kmeans_e4m3.py (a module of its own like svg/_kmeans_stepped.py; their poison rows: tests/test_gpu_kmeans_e4m3.py) and are
+    attributes of this module all the same."""
+    if name in ("kmeans_centre", "kmeans_assign_e4m3", "kmeans_loop_e4m3"):
+        from . import _kmeans_e4m3
+
+        return getattr(_kmeans_e4m3, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

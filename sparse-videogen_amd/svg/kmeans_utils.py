@@ -64,7 +64,7 @@ STEPPED_LOOP_UNDER_SHARDS = True
 
 @time_logging_decorator("Level 4 - batch kmeans euclid")
 def batch_kmeans_Euclid(x, n_clusters, max_iters=100, tol=1e-4, init_centroids=None, verbose=False, check_every=1,
-                        return_sorted_indices=False, shift_reduce=None, group=None):
+                        return_sorted_indices=False, shift_reduce=None, group=None, fp8_iters=0):
     """ref: batch_kmeans_Euclid, svg/kmeans_utils.py:684-733.
 
     x: [B, N, D] bf16/fp16 GPU tensor.  Returns (cluster_ids int64 [B, N], centroids [B, K, D], cluster_sizes int32 [B, K],
@@ -89,7 +89,19 @@ def batch_kmeans_Euclid(x, n_clusters, max_iters=100, tol=1e-4, init_centroids=N
         batches only: its result never depends on the other groups.  n_iters is then per group: int64 [B // group] (a GPU tensor with
         check_every = 0, a list of ints otherwise); shift_reduce receives the [B // group] vector of per-group maxima.  The per-group
         rule is evaluated after every iteration on the device; check_every >= 1 only sets how often the host reads back whether every
-        group has stopped (no overshoot)."""
+        group has stopped (no overshoot).
+    fp8_iters: 0 — the paths above, call for call.  n > 0 — iterations it < n assign with e4m3 operands around the channel mean of the
+        initial centroids (svg_kmeans_loop_e4m3, include/svg_attn_kmeans_e4m3.h; head_dim 128) and never stop the loop; the others are
+        the 16-bit iterations under the rule above, so with n < max_iters the returned labels are still the 16-bit arg-max against the
+        centroids that entered the last iteration.  Needs the loop inside the library: check_every = 0 and no shift_reduce, else
+        ValueError (the per-iteration and the stepped loops have no e4m3 form)."""
+    fp8_iters = int(fp8_iters)
+    if fp8_iters:
+        if fp8_iters < 0 or fp8_iters > max_iters:
+            raise ValueError(f"batch_kmeans_Euclid: fp8_iters = {fp8_iters} outside [0, max_iters = {max_iters}]")
+        if check_every or shift_reduce is not None or verbose:
+            raise ValueError("batch_kmeans_Euclid(fp8_iters > 0) runs inside the library only: it needs check_every=0, no shift_reduce and "
+                             "verbose=False (the per-iteration loop and the stepped, sharded loop have no e4m3 form)")
     _red = shift_reduce if shift_reduce is not None else (lambda t: t)
     assert x.is_cuda, "batch_kmeans_Euclid requires GPU tensors"
     assert max_iters >= 1, "max_iters must be >= 1 (the reference raises NameError for 0)"
@@ -137,7 +149,10 @@ def batch_kmeans_Euclid(x, n_clusters, max_iters=100, tol=1e-4, init_centroids=N
         # the whole loop inside the library (svg_kmeans_loop): the iterations and a commit kernel that applies the stopping rule on the
         # device — the same result as the torch statement below (kept for the sharded path, whose stopping rule needs an all-reduce
         # between the iterations), without its ~10 framework launches per iteration
-        labels_r, cent_r, counts_r, n_r, sorted_r = _native.kmeans_loop(x, xsq, c_in, max_iters, tol, work=_LOOP_WORK, group=group)
+        if fp8_iters:
+            labels_r, cent_r, counts_r, n_r, sorted_r = _native.kmeans_loop_e4m3(x, c_in, max_iters, tol, fp8_iters, work=_LOOP_WORK, group=group)
+        else:
+            labels_r, cent_r, counts_r, n_r, sorted_r = _native.kmeans_loop(x, xsq, c_in, max_iters, tol, work=_LOOP_WORK, group=group)
         out = (labels_r.to(torch.int64), cent_r, counts_r, n_r.to(torch.int64))
         return out + (sorted_r,) if return_sorted_indices else out
     if stepped:

@@ -724,6 +724,13 @@ class AdaptiveTopP:
             raise ValueError(f"AdaptiveTopP: 0 <= p_min <= p_max <= 1, got {self.p_min}, {self.p_max}")
 
 
+def _refuse_kmeans_e4m3_when_sharded(what: str, head_shard=None) -> None:
+    """on the host, before any collective, on every rank alike"""
+    if head_shard is not None or _dist._STATE["enabled"] or _dist.frame_shards_active() or _dist.token_shards_active():
+        raise NotImplementedError(f"{what}: kmeans_e4m3 under svg.distributed (enable, enable_frame_shards, enable_token_shards) is not "
+                                  f"implemented: the stepped Lloyd loop of a head shard has no e4m3 form; unset kmeans_e4m3 or run on one GPU")
+
+
 def _refuse_kept_mass_knob_when_sharded(what: str, knob: str) -> None:
     """knob: the processors' option, adaptive_top_p or adaptive_band"""
     if _dist._STATE["enabled"] or _dist.frame_shards_active() or _dist.token_shards_active():
@@ -905,20 +912,25 @@ def _side_stream(device) -> "torch.cuda.Stream":
 
 @time_logging_decorator("Level 3.5 - kmeans clustering")
 def kmeans_clustering(store: CentroidStore, layer_idx: int, q_video, k_video, num_q_centroids, num_k_centroids, iter_init,
-                      iter_step, head_shard=None):
+                      iter_step, head_shard=None, e4m3=False):
     """ref: kmeans_init / kmeans_step / kmeans_clustering, hyvideo/attention.py:576-626: random init from the data on the
     first call of a layer, warm start from the previous denoise step's centroids afterwards.
     head_shard = (h0, h1, H): q_video / k_video hold heads [h0, h1) of H (svg.distributed) — the random initial points are drawn
     for all H heads, in the order of the unsharded call, and this rank keeps its rows; the stopping rule's maximum centre shift is
     all-reduced — so that the result does not depend on the sharding.
     cfg > 1: one stopping rule per video (the loops run with group = H, the heads of one video; sharded: this rank's heads of one
-    video, the per-video maxima all-reduced), so that each video's clustering is the one it gets alone."""
+    video, the per-video maxima all-reduced), so that each video's clustering is the one it gets alone.
+    e4m3: all but the last iteration of the call assign with e4m3 operands (batch_kmeans_Euclid(fp8_iters=iters - 1): the returned labels
+    stay the 16-bit arg-max against the centroids that entered the last iteration).  Refused under svg.distributed."""
+    if e4m3:
+        _refuse_kmeans_e4m3_when_sharded("kmeans_clustering", head_shard)
     if _dist.token_shards_active() and head_shard is None:
         raise NotImplementedError("kmeans_clustering: token-shard mode clusters inside svg2_sparse_attention only (whole heads of the whole "
                                   "sequence); a call on this rank's rows (zero_step_kmeans_init) has no sharded form")
     cfg, H, N, D = q_video.shape
     first = not store.has(layer_idx, cfg, H)
     iters = iter_init if first else iter_step
+    f8 = dict(fp8_iters=iters - 1) if e4m3 and iters > 1 else {}   # (off: the call of before, argument for argument)
     qi = None if first else store.q[layer_idx]
     ki = None if first else store.k[layer_idx]
     red = _dist.all_reduce_max_ if head_shard is not None else None
@@ -940,11 +952,11 @@ def kmeans_clustering(store: CentroidStore, layer_idx: int, q_video, k_video, nu
 
     def run_q():
         return batch_kmeans_Euclid(q_video.reshape(cfg * H, N, D), num_q_centroids, max_iters=iters, init_centroids=qi,
-                                   return_sorted_indices=True, check_every=0, shift_reduce=red, group=grp)
+                                   return_sorted_indices=True, check_every=0, shift_reduce=red, group=grp, **f8)
 
     def run_k():
         return batch_kmeans_Euclid(k_video.reshape(cfg * H, N, D), num_k_centroids, max_iters=iters, init_centroids=ki,
-                                   return_sorted_indices=True, check_every=0, shift_reduce=red, group=grp)
+                                   return_sorted_indices=True, check_every=0, shift_reduce=red, group=grp, **f8)
 
     if red is not None and _kmeans_utils.STEPPED_LOOP_UNDER_SHARDS and q_video.is_cuda:
         # Sharded: the library's loop in steps (svg_kmeans_stepped_*), the two sides in lock-step.  Per iteration the q side's launches run on
@@ -999,7 +1011,7 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
                           num_k_centroids: int, top_p: float, min_kc_ratio: float, iter_init: int, iter_step: int,
                           prompt_length=0, logging_file: Optional[str] = None, timestep=None, _head_shard=None,
                           quality: Optional["QualityRequest"] = None, adaptive: Optional[AdaptiveTopP] = None,
-                          top_p_store: Optional[TopPStore] = None):
+                          top_p_store: Optional[TopPStore] = None, kmeans_e4m3: bool = False):
     """The sparse branch of the SAP processors (ref: hyvideo/attention.py:747-804, wan/attention.py:529-559):
     k-means on the video tokens -> top-p block map -> (Hunyuan) two pseudo clusters for prompt / unused prompt ->
     variable-block attention with the token permutation fused in (the result is already in the original order).
@@ -1015,7 +1027,11 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
     generator (neither the global RNG nor the switched path's generator moves) and svg_top_p_update steps the thresholds for the layer's
     next call — all on the device, no host synchronisation.  With `quality` as well the rows are drawn once and its one dense probe feeds
     both.  ValueError, before anything runs, where the launch has no LSE form (head_dim other than 128, fp8, S < 160 block-rows);
-    NotImplementedError under svg.distributed.  None: nothing changes."""
+    NotImplementedError under svg.distributed.  None: nothing changes.
+    kmeans_e4m3: the k-means of this call assigns with e4m3 operands in all but its last iteration (kmeans_clustering(e4m3=True));
+    NotImplementedError under svg.distributed.  False: nothing changes."""
+    if kmeans_e4m3:
+        _refuse_kmeans_e4m3_when_sharded("svg2_sparse_attention", _head_shard)
     if quality is not None:
         _refuse_quality_when_sharded("svg2_sparse_attention")
     if adaptive is not None:
@@ -1057,7 +1073,7 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
     with time_logging_decorator("Level 3 - semantic aware permutation"):
         (ql, qc, qs, _, qidx), (kl, kc, ks, _, kidx) = kmeans_clustering(store, layer_idx, qv, kv, num_q_centroids,
                                                                          num_k_centroids, iter_init, iter_step,
-                                                                         head_shard=_head_shard)
+                                                                         head_shard=_head_shard, **({"e4m3": True} if kmeans_e4m3 else {}))
         q_sizes = qs.view(cfg, H, num_q_centroids)
         k_sizes = ks.view(cfg, H, num_k_centroids)
         p_heads = None if adaptive is None else top_p_store.get(layer_idx, cfg * H, top_p, q.device)
@@ -1177,17 +1193,22 @@ def svg2_core_logic(proc, query, key, value, timestep, layer_idx, prompt_length,
     shape = query.size()
     geo, valid, quality = _core_logic_setup(proc, query, timestep, proc.frame_shard_form, valid_lens)
     adaptive = _knob(proc, "adaptive_top_p", valid_lens, valid)
+    e4m3 = {}   # (off: the calls below are the calls of before, argument for argument)
+    if proc.kmeans_e4m3:
+        _refuse_kmeans_e4m3_when_sharded(type(proc).__name__)
+        e4m3 = dict(e4m3=True)
     if is_full_attention(proc.layer_idx, timestep, proc.first_layers_fp, proc.first_times_fp):
         if proc.zero_step_kmeans_init and query.is_cuda:
             V = geo.video_length
             kmeans_clustering(proc.centroid_store, layer_idx, query[:, :, :V], key[:, :, :V],   # (views: read in place)
-                              proc.num_q_centroids, proc.num_k_centroids, proc.kmeans_iter_init, proc.kmeans_iter_step)
+                              proc.num_q_centroids, proc.num_k_centroids, proc.kmeans_iter_init, proc.kmeans_iter_step, **e4m3)
         out = proc.flash_attention(query, key, value) if dense is None else dense(query, key, value, valid, geo)
         return out.reshape(shape)
     out = svg2_sparse_attention(query, key, value, geo, proc.centroid_store, layer_idx, proc.num_q_centroids, proc.num_k_centroids,
                                 proc.top_p_kmeans, proc.min_kc_ratio, proc.kmeans_iter_init, proc.kmeans_iter_step,
                                 prompt_length=prompt_length if isinstance(prompt_length, tuple) else int(prompt_length),
-                                logging_file=proc.logging_file, timestep=timestep, quality=quality, adaptive=adaptive, top_p_store=proc.top_p_store)
+                                logging_file=proc.logging_file, timestep=timestep, quality=quality, adaptive=adaptive, top_p_store=proc.top_p_store,
+                                **({"kmeans_e4m3": True} if e4m3 else {}))
     return out.reshape(shape)
 
 

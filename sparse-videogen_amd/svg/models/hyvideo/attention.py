@@ -346,6 +346,10 @@ class Hunyuan_SAPAttn_Processor2_0(Hunyuan_SVGAttn_Processor2_0):
     kmeans_iter_init = 0
     kmeans_iter_step = 0
     zero_step_kmeans_init = False
+    # k-means with e4m3 assignments (include/svg_attn_kmeans_e4m3.h): True -> all but the last Lloyd iteration of every call assign on the
+    # scaled fp8 MFMA; the labels a call returns stay the 16-bit arg-max against the centroids of its last iteration.  Refused under
+    # svg.distributed.  False: nothing changes.
+    kmeans_e4m3 = False
 
     logging_file = None
     prescale_q = False   # k-means and the block map work on the plain q
