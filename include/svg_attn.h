@@ -803,6 +803,8 @@ int svg_debug_wg_trace(uint64_t* out, int32_t n_workgroups);
 #include "svg_attn_kmeans_stepped.h"
 /* ... and flash-kmeans with an e4m3 assignment: the centre, the assignment and the Lloyd loop that uses it for its first iterations, likewise */
 #include "svg_attn_kmeans_e4m3.h"
+/* ... and SVG2's centroid tail: the means of the key clusters and the attention state over the clusters a block map leaves out, likewise */
+#include "svg_attn_centroid_tail.h"
 /* ... and the per-head band launch below and its device switch as resident workgroups on the work queue, with the order on the host, likewise */
 #include "svg_attn_band_per_head_queue.h"
 /* ... and SVG1's per-head band width: band attention from a device vector of bands, its device switch and the controller step, likewise */

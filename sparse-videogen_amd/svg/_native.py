@@ -393,6 +393,19 @@ KMEANS_E4M3_SIGNATURES = {
 }
 
 
+# include/svg_attn_centroid_tail.h: the cluster means and the attention state over the key clusters a block map leaves out, in a table of its
+# own for the same reason (tests/test_centroid_tail_cpu.py; the allocating wrappers cluster_means, centroid_tail_attention:
+# svg/_centroid_tail.py, reachable as attributes of this module — __getattr__ at its end; named ..._ENTRIES for the reason ADAPTIVE_BAND_ENTRIES
+# gives: the golden of tests/test_wrapper_layout_plan_cpu.py is closed; what these wrappers pass is checked on the GPU, in
+# tests/test_gpu_centroid_tail.py)
+CENTROID_TAIL_ENTRIES = {
+    "svg_cluster_means": (C.c_int, [_VP, C.POINTER(TensorStrides), _I32, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP]),
+    "svg_centroid_tail_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
+    "svg_centroid_tail_attention_lse": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _F32, _VP, _I32, _VP, _VP, _I32, _VP,
+                                                  _VP, _SZ, C.POINTER(AttnLayout), _VP]),
+}
+
+
 class CopyBox(C.Structure):
     """svg_copy_box_t (include/svg_attn_shard_exchange.h): extent[0] * extent[1] * extent[2] rows of D contiguous elements; offsets and
     strides in elements"""
@@ -430,7 +443,7 @@ def load(strict: bool = True) -> Optional[C.CDLL]:
                                    **BAND_WINDOW_SIGNATURES, **BAND_SHARD_SIGNATURES, **BAND_SHARD_SWITCH_SIGNATURES,
                                    **PROFILE_SHARD_SIGNATURES, **SAMPLE_ROWS_SIGNATURES, **SHARD_EXCHANGE_SIGNATURES,
                                    **ADAPTIVE_TOP_P_SIGNATURES, **ADAPTIVE_BAND_ENTRIES, **ADAPTIVE_BAND_QUEUE_ENTRIES,
-                                   **KMEANS_STEPPED_SIGNATURES, **KMEANS_E4M3_SIGNATURES}.items():
+                                   **KMEANS_STEPPED_SIGNATURES, **KMEANS_E4M3_SIGNATURES, **CENTROID_TAIL_ENTRIES}.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -2526,4 +2539,8 @@ def __getattr__(name: str):
         from . import _kmeans_e4m3
 
         return getattr(_kmeans_e4m3, name)
+    if name in ("cluster_means", "centroid_tail_attention"):   # (include/svg_attn_centroid_tail.h, likewise: svg/_centroid_tail.py)
+        from . import _centroid_tail
+
+        return getattr(_centroid_tail, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

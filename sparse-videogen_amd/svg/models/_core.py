@@ -731,6 +731,25 @@ def _refuse_kmeans_e4m3_when_sharded(what: str, head_shard=None) -> None:
                                   f"implemented: the stepped Lloyd loop of a head shard has no e4m3 form; unset kmeans_e4m3 or run on one GPU")
 
 
+def _refuse_centroid_tail_when_sharded(what: str, head_shard=None) -> None:
+    """on the host, before any collective, on every rank alike"""
+    if head_shard is not None or _dist._STATE["enabled"] or _dist.frame_shards_active() or _dist.token_shards_active():
+        raise NotImplementedError(f"{what}: centroid_tail under svg.distributed (enable, enable_frame_shards, enable_token_shards) is not "
+                                  f"implemented: the means and the tail read whole heads of the whole sequence; unset centroid_tail or run on one GPU")
+
+
+def _refuse_centroid_tail(what: str, q: torch.Tensor, block_rows: int, adaptive=None, head_shard=None) -> None:
+    """What the centroid tail refuses, all of it before anything runs: there is no silent fall-back to the sparse part alone."""
+    _refuse_centroid_tail_when_sharded(what, head_shard)
+    if adaptive is not None:
+        raise ValueError(f"{what}: centroid_tail together with adaptive_top_p is not implemented — the controller steers on the kept mass of "
+                         f"the sparse part alone; unset one of them")
+    S, D = q.shape[-2], q.shape[-1]
+    if D != 128 or _use_fp8(q) or q.dtype not in (torch.bfloat16, torch.float16) or S < 160 * block_rows:
+        raise ValueError(f"{what}(centroid_tail=True): the tail is merged with the sparse call through its row log-sum-exp — head_dim 128, bf16 / "
+                         f"fp16 (not fp8), S >= 160 block-rows; got D = {D}, {q.dtype}, fp8 = {_use_fp8(q)}, S = {S}, block-rows = {block_rows}")
+
+
 def _refuse_kept_mass_knob_when_sharded(what: str, knob: str) -> None:
     """knob: the processors' option, adaptive_top_p or adaptive_band"""
     if _dist._STATE["enabled"] or _dist.frame_shards_active() or _dist.token_shards_active():
@@ -1007,11 +1026,35 @@ def kmeans_clustering(store: CentroidStore, layer_idx: int, q_video, k_video, nu
     return (ql, qc, qs, qit, qidx), (kl, kc, ks, kit, kidx)
 
 
+def _sparse_plus_centroid_tail(q, k, v, dyn_map, q_sizes, k_sizes, qidx, kidx, tail_k, KC: int, token_major: bool):
+    """svg2_sparse_attention(centroid_tail=True) from the block map on: the sparse launch in its LSE form into a contiguous head-major
+    part, the means of the call's own key clusters, the tail launch into the second part, and the merge — token-major wherever the plain
+    call's output would be.  tail_k = (the video keys [cfg, H, V, D], their cluster sizes [cfg * H, KC], their sorted indices [cfg * H, V])
+    as the k-means returned them.  -> (out, merged lse [cfg, H, S])"""
+    cfg, H, S, D = q.shape
+    QB, KB = q_sizes.shape[-1], k_sizes.shape[-1]
+    maps = dyn_map.view(cfg * H, QB, KB).contiguous()
+    qsz, rows = q_sizes.view(cfg * H, QB).contiguous(), qidx.contiguous()
+    o_s, lse_s = _native.varblock_attention(q, k, v, maps, qsz, k_sizes.view(cfg * H, KB).contiguous(), q_row_idx=rows,
+                                            kv_row_idx=kidx.contiguous(), rows_covered=True, return_lse=True)
+    kv, ks, kidx_v = tail_k
+    V = kv.shape[2]
+    ks, kidx_v = ks.reshape(cfg * H, KC).contiguous(), kidx_v.reshape(cfg * H, V).contiguous()
+    kbar = _native.cluster_means(kv, kidx_v, ks)
+    vbar = _native.cluster_means(v[:, :, :V], kidx_v, ks)   # (a view of the caller's v: read in place, token-major or not)
+    if KB != KC:   # HunyuanVideo: the last block-row — the unused prompt — selects nothing but itself; its rows get no tail
+        maps = maps.clone()
+        maps[:, -1, :] = True
+    o_t, lse_t = _native.centroid_tail_attention(q, kbar, vbar, maps, qsz, ks, q_row_idx=rows)
+    return _native.merge_attention_states([o_s.reshape(cfg, H, S, D), o_t.reshape(cfg, H, S, D)],
+                                          [lse_s.reshape(cfg, H, S), lse_t.reshape(cfg, H, S)], token_major_out=token_major, return_lse=True)
+
+
 def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_idx: int, num_q_centroids: int,
                           num_k_centroids: int, top_p: float, min_kc_ratio: float, iter_init: int, iter_step: int,
                           prompt_length=0, logging_file: Optional[str] = None, timestep=None, _head_shard=None,
                           quality: Optional["QualityRequest"] = None, adaptive: Optional[AdaptiveTopP] = None,
-                          top_p_store: Optional[TopPStore] = None, kmeans_e4m3: bool = False):
+                          top_p_store: Optional[TopPStore] = None, kmeans_e4m3: bool = False, centroid_tail: bool = False):
     """The sparse branch of the SAP processors (ref: hyvideo/attention.py:747-804, wan/attention.py:529-559):
     k-means on the video tokens -> top-p block map -> (Hunyuan) two pseudo clusters for prompt / unused prompt ->
     variable-block attention with the token permutation fused in (the result is already in the original order).
@@ -1029,9 +1072,17 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
     both.  ValueError, before anything runs, where the launch has no LSE form (head_dim other than 128, fp8, S < 160 block-rows);
     NotImplementedError under svg.distributed.  None: nothing changes.
     kmeans_e4m3: the k-means of this call assigns with e4m3 operands in all but its last iteration (kmeans_clustering(e4m3=True));
-    NotImplementedError under svg.distributed.  False: nothing changes."""
+    NotImplementedError under svg.distributed.  False: nothing changes.
+    centroid_tail: the key clusters the block map does not select are not dropped: each enters its rows as one pseudo key — the mean key and
+    the mean value of the cluster (cluster_means of THIS call's labels: Jensen's bound needs the mean, the stored centroids may be one
+    update away), weighted with the cluster's size (include/svg_attn_centroid_tail.h) — and that state is merged with the sparse call's
+    (merge_attention_states).  HunyuanVideo: the video clusters only, and the unused-prompt rows get no tail.  A `quality` record is then
+    measured on the merged output and lse and carries "centroid_tail": true.  NotImplementedError under svg.distributed; ValueError
+    together with `adaptive`, and where the launch has no LSE form (the rule of `adaptive`).  False: nothing changes."""
     if kmeans_e4m3:
         _refuse_kmeans_e4m3_when_sharded("svg2_sparse_attention", _head_shard)
+    if centroid_tail:
+        _refuse_centroid_tail("svg2_sparse_attention", q, num_q_centroids + (2 if geo.context_length else 0), adaptive, _head_shard)
     if quality is not None:
         _refuse_quality_when_sharded("svg2_sparse_attention")
     if adaptive is not None:
@@ -1079,6 +1130,7 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
         p_heads = None if adaptive is None else top_p_store.get(layer_idx, cfg * H, top_p, q.device)
         dyn_map = identify_dynamic_map(qc.view(cfg, H, num_q_centroids, D), kc.view(cfg, H, num_k_centroids, D), q_sizes,
                                        k_sizes, top_p if adaptive is None else p_heads.view(cfg, H), min_kc_ratio)
+    tail_k = (kv, ks, kidx) if centroid_tail else None   # (the video keys, their cluster sizes and sorted indices, before the text clusters)
     if ctx:
         with time_logging_decorator("Level 3 - dynamic map post processing"):
             dyn_map, q_sizes, k_sizes, qidx, kidx = dynamic_map_post_processing(dyn_map, q_sizes, k_sizes, qidx, kidx, V, ctx,
@@ -1090,18 +1142,21 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
     # (one launch over the cfg * H heads; the token-major output is [cfg, S, H, D] in memory: svg_attn_layout_t with heads_per_batch = H)
     # (the LSE entry always runs the two-phase 16x16x32 body; the plain call picks it from S >= 160 QB on: only there is its o the same)
     probe_lse = adaptive is not None or (quality is not None and _quality_lse_form(q, False) and S >= 160 * QB)
-    out = _native.varblock_attention(q, k, v, dyn_map.view(cfg * H, QB, KB).contiguous(),
-                                     q_sizes.view(cfg * H, QB).contiguous(), k_sizes.view(cfg * H, KB).contiguous(),
-                                     q_row_idx=qidx.contiguous(), kv_row_idx=kidx.contiguous(), fp8=f8,
-                                     token_major_out=TOKEN_MAJOR_IO and (_head_shard is None or _dist.token_shards_active()),
-                                     rows_covered=True, return_lse=probe_lse)
-    out, lse_p = out if probe_lse else (out, None)
+    token_major = TOKEN_MAJOR_IO and (_head_shard is None or _dist.token_shards_active())
+    if centroid_tail:
+        out, lse_p = _sparse_plus_centroid_tail(q, k, v, dyn_map, q_sizes, k_sizes, qidx, kidx, tail_k, num_k_centroids, token_major)
+    else:
+        out = _native.varblock_attention(q, k, v, dyn_map.view(cfg * H, QB, KB).contiguous(),
+                                         q_sizes.view(cfg * H, QB).contiguous(), k_sizes.view(cfg * H, KB).contiguous(),
+                                         q_row_idx=qidx.contiguous(), kv_row_idx=kidx.contiguous(), fp8=f8, token_major_out=token_major,
+                                         rows_covered=True, return_lse=probe_lse)
+        out, lse_p = out if probe_lse else (out, None)
     plan = lse_d = None
     if adaptive is not None:   # the rows of this call, drawn once: the quality probe below measures on them as well
         plan = _knob_probe_plan(quality, adaptive, cfg, S)
     if quality is not None:
         lse_d = log_quality(quality, out, lse_p, q, k, v, density=density_calculation(dyn_map, q_sizes, k_sizes), plan=plan,
-                            top_p=None if adaptive is None else p_heads.clone())
+                            top_p=None if adaptive is None else p_heads.clone(), **({"centroid_tail": True} if centroid_tail else {}))
     if adaptive is not None:
         adaptive_step(adaptive, top_p_store, layer_idx, p_heads, lse_p, q, k, plan, lse_d)
     if logging_file is not None:
@@ -1197,6 +1252,8 @@ def svg2_core_logic(proc, query, key, value, timestep, layer_idx, prompt_length,
     if proc.kmeans_e4m3:
         _refuse_kmeans_e4m3_when_sharded(type(proc).__name__)
         e4m3 = dict(e4m3=True)
+    if proc.centroid_tail:   # (on dense steps too: every rank refuses on its first call)
+        _refuse_centroid_tail_when_sharded(type(proc).__name__)
     if is_full_attention(proc.layer_idx, timestep, proc.first_layers_fp, proc.first_times_fp):
         if proc.zero_step_kmeans_init and query.is_cuda:
             V = geo.video_length
@@ -1208,7 +1265,7 @@ def svg2_core_logic(proc, query, key, value, timestep, layer_idx, prompt_length,
                                 proc.top_p_kmeans, proc.min_kc_ratio, proc.kmeans_iter_init, proc.kmeans_iter_step,
                                 prompt_length=prompt_length if isinstance(prompt_length, tuple) else int(prompt_length),
                                 logging_file=proc.logging_file, timestep=timestep, quality=quality, adaptive=adaptive, top_p_store=proc.top_p_store,
-                                **({"kmeans_e4m3": True} if e4m3 else {}))
+                                **({"kmeans_e4m3": True} if e4m3 else {}), **({"centroid_tail": True} if proc.centroid_tail else {}))
     return out.reshape(shape)
 
 
@@ -1435,7 +1492,7 @@ atexit.register(flush_quality_log)
 
 
 def log_quality(quality: QualityRequest, out: torch.Tensor, lse, q, k, v, q_prescaled: bool = False, dense_flag=None, density=None,
-                plan=None, top_p=None, band=None):
+                plan=None, top_p=None, band=None, centroid_tail: bool = False):
     """Probe one sparse layer-call (out [cfg, H, S, D] in either storage order, lse [cfg, H, S] or None) and queue its record.  Rows:
     uniform over the valid rows of the sequence, from the probe's own CPU generator.  Videos whose valid lengths differ are probed group by
     group (video_groups), one native call per group.
@@ -1454,6 +1511,8 @@ def log_quality(quality: QualityRequest, out: torch.Tensor, lse, q, k, v, q_pres
     ts = quality.timestep
     on_device = torch.is_tensor(ts) and ts.is_cuda   # (the switched path never reads the timestep back: it travels with the figures)
     meta = {"timestep": None if ts is None or on_device else timestep_value(ts), "layer": quality.layer}
+    if centroid_tail:   # (the record of a call whose output and lse are the merged ones; without the option the record is the one of before)
+        meta["centroid_tail"] = True
     QUALITY_LOG.push(quality.path, meta, fig, density=density, dense_flag=dense_flag, timestep=ts if on_device else None, top_p=top_p,
                      **({} if band is None else {"band": band}))
     return lse_dense

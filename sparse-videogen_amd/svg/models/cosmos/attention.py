@@ -136,3 +136,4 @@ class Cosmos_SAPAttn_Processor(_CosmosPlumbing, WanAttn_SAPAttn_Processor):
     """Sparse VideoGen 2 for Cosmos (ref: cosmos/attention.py:289-469)."""
 
     kmeans_e4m3 = False   # (its own switch, as on the Wan and HunyuanVideo SAP processors)
+    centroid_tail = False   # (likewise)

@@ -302,6 +302,10 @@ class WanAttn_SAPAttn_Processor(WanAttn_SVGAttn_Processor2_0):
     # scaled fp8 MFMA; the labels a call returns stay the 16-bit arg-max against the centroids of its last iteration.  Refused under
     # svg.distributed.  False: nothing changes.
     kmeans_e4m3 = False
+    # centroid tail (include/svg_attn_centroid_tail.h): True -> the key clusters the top-p map leaves out enter every row as one pseudo key
+    # each (mean key, mean value, weighted with the cluster's size) and that state is merged with the sparse call's.  Refused under
+    # svg.distributed and together with adaptive_top_p.  False: nothing changes.
+    centroid_tail = False
 
     logging_file = None
     prescale_q = False   # k-means and the block map work on the plain q
