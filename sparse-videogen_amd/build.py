@@ -48,6 +48,10 @@ STRICT_FP = {"prologue.hip", "glue.hip", "dynmap.hip", "kept_mass_control.hip"}
 # (attention.hip: the pre-scaled-q bodies, E::mfma_keep_c; attention_varblock.hip / attention_f8.hip: the first contraction step of a
 #  tile of the fp8 bodies, csrc/attn_f8.h mfma_qk_first)
 KEEP_ASM = {"attention_w4.hip", "attention.hip", "attention_varblock.hip", "attention_f8.hip"}
+# Files compiled without the packed fp32 instructions (v_pk_mul_f32, v_pk_add_f32, v_pk_fma_f32): every fp32 product and sum is a scalar
+# instruction, so what a row rounds does not depend on which pairs the vectoriser found.  (The older units keep their flags: their listings
+# and output bits are pinned as they are.)
+NO_PACKED_FP32 = {"attention_band_d64.hip"}
 
 
 def _newest_header() -> float:
@@ -63,6 +67,8 @@ def _compile(src: Path, force: bool, asm: bool, ablations: bool = False, tag: st
     flags = list(FLAGS) + os.environ.get("SVG_EXTRA_HIPCC_FLAGS", "").split()   # (experiments: -DSVG_... switches of the kernels)
     if src.name in STRICT_FP:
         flags = [f for f in flags if f not in ("-ffast-math", "-fno-finite-math-only")] + ["-fno-fast-math", "-ffp-contract=off"]
+    if src.name in NO_PACKED_FP32:
+        flags += ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
     if ablations:
         flags.append("-DSVG_ABLATIONS")
     cmd = [HIPCC, *flags, "-c", str(src), "-o", str(obj)]

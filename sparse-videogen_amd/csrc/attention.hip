@@ -620,12 +620,13 @@ static int band_run(BandCall c) {
     const int32_t BH = c.BH;
     const hipStream_t st = c.stream;
     if (c.lse) {   // the LSE / fp32 forms: the default head_dim-128 body — single mask (queue or static mapping) or device switch
-        if (c.D != 128 || c.variant != kBandAuto || c.done || c.prescaled) return SVG_ERR_UNSUPPORTED;
+        if (c.D != (c.d64 ? 64 : 128) || c.variant != kBandAuto || c.done || c.prescaled) return SVG_ERR_UNSUPPORTED;
         if (c.form == kBandWindow) {   // key tiles stay aligned to the mask's coordinates; and the sizes, which this form states here
             if (c.k_begin % kBN != 0) return SVG_ERR_UNSUPPORTED;
             if ((rc = band_check_size(c)) != SVG_OK) return rc;
         }
         if (c.o32 && ((size_t)c.o32 & 15) != 0) return SVG_ERR_UNSUPPORTED;   // 16-byte stores
+        if (c.d64) return run_band_lse_d64(c);   // the 32x32x16 body at four waves per SIMD (attention_band_d64.hip)
         return dispatch_td(c.dtype, c.D, [&](auto t, auto d) -> int {
             using T = decltype(t);
             if constexpr (decltype(d)::value != 128) {
@@ -955,6 +956,41 @@ extern "C" int svg_band_attention_switch_lse_f32(const void* q, const void* k, c
     BandCall c{q, k, v, nullptr, BH, S, D, dtype, sm_scale, mask, perm, layout, (hipStream_t)stream};
     c.lse = lse, c.o32 = o32, c.alt_mask = alt_mask, c.use_alt = use_alt_flag;
     return band_run(c);
+}
+
+// Their head_dim-64 namesakes (include/svg_attn_band_lse_d64.h): the same calls marked d64 — the checks of the namesake in its order, the
+// head size last — for the kernels of attention_band_d64.hip.
+static int band_run_d64(BandCall c, float* lse, float* o32, const svg_band_mask_t* alt_mask, const int32_t* use_alt_flag) {
+    c.lse = lse, c.o32 = o32, c.alt_mask = alt_mask, c.use_alt = use_alt_flag, c.d64 = true;
+    return band_run(c);
+}
+extern "C" int svg_band_attention_lse_d64(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S, int32_t D,
+                                          int32_t dtype, float sm_scale, const svg_band_mask_t* mask, const svg_perm_desc_t* perm,
+                                          const svg_attn_layout_t* layout, void* stream) {
+    if (!lse) return SVG_ERR_BAD_ARG;
+    return band_run_d64(BandCall{q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, layout, (hipStream_t)stream}, lse, nullptr, nullptr, nullptr);
+}
+extern "C" int svg_band_attention_lse_d64_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t BH, int32_t S,
+                                              int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
+                                              const svg_perm_desc_t* perm, const svg_attn_layout_t* layout, void* stream) {
+    if (!o32 || !lse) return SVG_ERR_BAD_ARG;
+    return band_run_d64(BandCall{q, k, v, nullptr, BH, S, D, dtype, sm_scale, mask, perm, layout, (hipStream_t)stream}, lse, o32, nullptr, nullptr);
+}
+extern "C" int svg_band_attention_switch_lse_d64(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S,
+                                                 int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
+                                                 const svg_perm_desc_t* perm, const svg_band_mask_t* alt_mask, const int32_t* use_alt_flag,
+                                                 const svg_attn_layout_t* layout, void* stream) {
+    if (!lse || !alt_mask || !use_alt_flag) return SVG_ERR_BAD_ARG;
+    return band_run_d64(BandCall{q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, layout, (hipStream_t)stream}, lse, nullptr, alt_mask,
+                        use_alt_flag);
+}
+extern "C" int svg_band_attention_switch_lse_d64_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t BH,
+                                                     int32_t S, int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
+                                                     const svg_perm_desc_t* perm, const svg_band_mask_t* alt_mask,
+                                                     const int32_t* use_alt_flag, const svg_attn_layout_t* layout, void* stream) {
+    if (!o32 || !lse || !alt_mask || !use_alt_flag) return SVG_ERR_BAD_ARG;
+    return band_run_d64(BandCall{q, k, v, nullptr, BH, S, D, dtype, sm_scale, mask, perm, layout, (hipStream_t)stream}, lse, o32, alt_mask,
+                        use_alt_flag);
 }
 
 // One band per head (include/svg_attn_adaptive_band.h, include/svg_attn_band_per_head_queue.h): the checks of

@@ -530,6 +530,111 @@ static inline int read_trace_here(uint64_t* out, bool wg, int n_workgroups) {
 }
 
 
+// Row log-sum-exp (detected: a policy with a static lse_base(prm, ctx), cross_policy.h CrossLsePolicy; every other policy
+// compiles the epilogue it had): the epilogue also stores, per query row, lse = log sum_j exp(sm_scale * q.k_j) over the keys the row saw,
+// natural log, fp32, at lse_base(prm, ctx)[physical q row].  At the end of the tile loop the probabilities of a row are
+// 2^(s * scale_log2 - m_use - kBias) and l_tot is their sum, so lse = ln2 * (m_use + kBias + log2(l_tot)); a row without keys (l_tot == 0)
+// gives -inf.  Lanes 0..15 of a wave store (one lane per row, 2 x 16 stores per wave and q-tile), rows behind the q-tile's end are not
+// written; no LDS, no barrier.
+template <typename P, typename = void>
+struct HasRowLse : std::false_type {};
+template <typename P>
+struct HasRowLse<P, std::void_t<decltype(&P::lse_base)>> : std::true_type {};
+
+// fp32 rows (detected: a policy with a static o32_base(prm, ctx), the *F32Policy of cross_policy.h / band_policy.h / varblock_policy.h;
+// every other policy compiles the epilogue it had): the epilogue stores acc_o * inv — the value the 16-bit store rounds — as fp32 at
+// o32_base(prm, ctx)[physical q row * D + column], a contiguous [heads, rows, D] in the caller's row order (the row index of the lse
+// store), and writes no 16-bit o.  What a merge over parts of the keys takes without a rounding per part (svg_merge_attention_states_f32).
+// Straight from the accumulator registers: a lane holds four consecutive floats per (db, rb) at column 16 * db + 4 * g4, so one 16-byte
+// store per (db, rb) — the four lanes of a row's quad group fill one 64-byte run; no LDS (the staging region holds 16-bit rows) and no
+// barrier.  Rows behind the q-tile's end (q_phys < 0) store nothing, a row without keys stores zeros (inv == 0).
+template <typename P, typename = void>
+struct HasRowO32 : std::false_type {};
+template <typename P>
+struct HasRowO32<P, std::void_t<decltype(&P::o32_base)>> : std::true_type {};
+// The four fp32 values of one (db, rb).  bf16: the 16-bit store rounds the fp32 product, so the product is the value.  fp16: the 16-bit
+// store of the same accumulators is compiled (-ffast-math contraction) to a mix of v_fma_mixlo_f16 — the exact product rounded once — and
+// v_pk_mul_f32 + v_cvt_pk_f16_f32 — rounded twice — so the fp32 product rounded again by the caller differs from it where the product lies
+// exactly on the midpoint of two fp16 values and the store took the other neighbour (about 3e-5 of the elements).  So the fp16 form
+// also evaluates the 16-bit store's own expression, and where the fp32 product does not round to that value it moves ONE fp32 step
+// towards it: o32 rounded to nearest even is then the 16-bit o, and o32 stays within one fp32 step of acc * inv.  (The empty asm
+// statements keep the two evaluations apart: without them the compiler folds both into one and the comparison is always true.)
+template <typename T, typename E>
+__device__ __forceinline__ f32x4 o32_values(const f32x4& acc, float inv) {
+    f32x4 o4;
+    if constexpr (std::is_same_v<T, _Float16>) {
+        typename E::v4 h4;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) h4[j] = E::from_float(acc[j] * inv);   // the expression of the 16-bit store
+        u32x2 hb = __builtin_bit_cast(u32x2, h4);
+        asm("" : "+v"(hb));
+        h4 = __builtin_bit_cast(typename E::v4, hb);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float a = acc[j];
+            asm("" : "+v"(a));
+            float p = a * inv;
+            asm("" : "+v"(p));
+            const float h = (float)h4[j];
+            if ((float)(_Float16)p != h)   // p is a midpoint and the store took the other neighbour (false for 0 against -0; a NaN stays one)
+                p = __uint_as_float(fabsf(h) > fabsf(p) ? __float_as_uint(p) + 1u : __float_as_uint(p) - 1u);
+            o4[j] = p;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o4[j] = acc[j] * inv;
+    }
+    return o4;
+}
+// (The three paragraphs above speak of attn_body_m16, attn_m16.h, where the hooks came from; attn_body_pp2 below detects the same two and
+//  says at its epilogue which lane stores what.)
+
+// The 16-bit values of four accumulators of attn_body_pp2's LSE / fp32 forms: o of the plain kernels, bit for bit, without leaning on what
+// a compiler makes of `E::from_float(acc * inv)`.  bf16: the fp32 product rounded to nearest even, whatever instructions do it.  fp16: the
+// plain head_dim-64 kernels (attention.hip: band_attn_pp2_kernel, band_attn_pp2_switch64_kernel) round elements 0 and 3 of every four
+// ONCE — v_fma_mixlo_f16 on fp32 sources, the exact product to fp16 — and elements 1 and 2 TWICE — the fp32 product, then its conversion;
+// the two differ where the product lies within half an fp32 step of the midpoint of two fp16 values.  Written out here per element, so a
+// translation unit with other code-generation flags stores the same bits.
+template <typename T, typename E>
+__device__ __forceinline__ typename E::v4 pp2_row16_values(const f32x4& acc, float inv) {
+    typename E::v4 h4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if constexpr (std::is_same_v<T, _Float16>) {
+            if (j == 0 || j == 3) {
+                unsigned d = 0;   // (the instruction writes the low half of d and keeps the high one)
+                asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "+v"(d) : "v"(inv), "v"(acc[j]));
+                h4[j] = __builtin_bit_cast(_Float16, (unsigned short)d);
+            } else {
+                float p = acc[j] * inv;
+                asm("" : "+v"(p));   // the fp32 product is a value of its own: no contraction into the conversion
+                h4[j] = (_Float16)p;
+            }
+        } else {
+            h4[j] = E::from_float(acc[j] * inv);
+        }
+    }
+    return h4;
+}
+// ... and their fp32 values: acc * inv, at fp16 moved ONE fp32 step towards the 16-bit value where it does not round to it (o32_values
+// above, against pp2_row16_values): o32 rounded to nearest even is the 16-bit o.
+template <typename T, typename E>
+__device__ __forceinline__ f32x4 pp2_row32_values(const f32x4& acc, float inv) {
+    f32x4 o4;
+    const typename E::v4 h4 = pp2_row16_values<T, E>(acc, inv);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float p = acc[j] * inv;
+        if constexpr (std::is_same_v<T, _Float16>) {
+            asm("" : "+v"(p));
+            const float h = (float)h4[j];
+            if ((float)(_Float16)p != h) p = __uint_as_float(fabsf(h) > fabsf(p) ? __float_as_uint(p) + 1u : __float_as_uint(p) - 1u);
+        }
+        o4[j] = p;
+    }
+    return o4;
+}
+
 // =====================================================================================================================
 // attn_body_pp2 — two-phase ping-pong: per tile every wave runs ONE matrix phase and ONE vector phase, and the two waves
 // of a SIMD are always in opposite phases (waves 4..7 run one phase behind waves 0..3; two barriers per tile).
@@ -1043,6 +1148,47 @@ __device__ __forceinline__ void attn_body_pp2(const typename P::Params& prm, cha
         return;
     } else {
         const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
+        // Row log-sum-exp (HasRowLse).  The probabilities of a row are 2^(s * scale_log2 - m_use) — the max-free scheme folds no bias in, and
+        // m_use is the reference O and l are scaled to, the same in both lanes of a row (the exact path exchanges the maximum) — and l_tot is
+        // their sum, in lane l and in lane l ^ 32 alike: lse = ln2 * (m_use + log2 l_tot), -inf for a row without keys (whose o is zero: inv).
+        // Lane ql of the lower half stores row ql of the wave, 32 stores per wave: no LDS, no barrier.  A row behind the q-tile's end has
+        // q_phys < 0 and stores nothing (a wave of such rows only never gets here: `idle`).
+        if constexpr (HasRowLse<P>::value) {
+            static_assert(kMaxFree && !PRE, "row log-sum-exp: the reference of the plain max-free softmax");
+            const int qp = P::q_phys(prm, ctx, row_in_wg);
+            if (g == 0 && qp >= 0)
+                P::lse_base(prm, ctx)[qp] = l_tot > 0.f ? 0.6931471805599453f * (m_use + __builtin_amdgcn_logf(l_tot)) : -INFINITY;
+        }
+        // fp32 rows (HasRowO32) instead of 16-bit ones.  A row of D = 64 floats is 256 bytes, sixteen 16-byte chunks; a lane holds chunk
+        // 2 (4 db + rq) + g of row ql per (db, rq).  Staged per wave like the 16-bit rows, rows 256 bytes apart (8 waves x 32 rows fill the
+        // four stages exactly) with chunk c of row r at position c ^ (r & 15), so that the 16 rows a write instruction's quarter touches
+        // spread over all banks; then sixteen lanes read one row back and store it: four whole rows, 4 x 256 contiguous bytes, per
+        // instruction, eight instructions per wave.
+        if constexpr (HasRowO32<P>::value) {
+            static_assert(D == 64 && 8 * 32 * D * 4 <= attn_pp2_lds_bytes<D>(), "fp32 rows: staged in the stages of head_dim 64");
+            char* const erow32 = smem + (size_t)(wave * 32) * (D * 4);
+#pragma unroll
+            for (int db = 0; db < DB; ++db)
+#pragma unroll
+                for (int rq = 0; rq < 4; ++rq) {
+                    const f32x4 a4 = {acc_o[db][rq * 4], acc_o[db][rq * 4 + 1], acc_o[db][rq * 4 + 2], acc_o[db][rq * 4 + 3]};
+                    const int c = 2 * (4 * db + rq) + g;
+                    *(f32x4*)(erow32 + ql * (D * 4) + ((c ^ (ql & 15)) << 4)) = pp2_row32_values<T, E>(a4, inv);
+                }
+            __builtin_amdgcn_s_waitcnt(0xc07f);
+            __builtin_amdgcn_wave_barrier();
+            float* __restrict__ ob32 = P::o32_base(prm, ctx);
+            const int sub = lane >> 4, c = lane & 15;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int rr = 4 * i + sub;
+                const int qp = P::q_phys(prm, ctx, wave * 32 + rr);
+                const f32x4 val = *(const f32x4*)(erow32 + rr * (D * 4) + ((c ^ (rr & 15)) << 4));
+                if (qp >= 0) *(f32x4*)(ob32 + (size_t)qp * D + 4 * c) = val;
+            }
+            P::notify(prm, ctx);
+            return;
+        }
         constexpr int kEpiStride = D * 2 + 8;
         char* erow = smem + (size_t)(wave * 32) * kEpiStride;
 #pragma unroll
@@ -1050,8 +1196,13 @@ __device__ __forceinline__ void attn_body_pp2(const typename P::Params& prm, cha
 #pragma unroll
             for (int rq = 0; rq < 4; ++rq) {
                 typename E::v4 o4;
+                if constexpr (HasRowLse<P>::value) {   // (the bits of the plain kernels, spelled out: pp2_row16_values)
+                    const f32x4 a4 = {acc_o[db][rq * 4], acc_o[db][rq * 4 + 1], acc_o[db][rq * 4 + 2], acc_o[db][rq * 4 + 3]};
+                    o4 = pp2_row16_values<T, E>(a4, inv);
+                } else {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) o4[j] = E::from_float(acc_o[db][rq * 4 + j] * inv);
+                    for (int j = 0; j < 4; ++j) o4[j] = E::from_float(acc_o[db][rq * 4 + j] * inv);
+                }
                 const int d0 = 32 * db + 8 * rq + 4 * g;
                 *(typename E::v4*)(erow + ql * kEpiStride + d0 * 2) = o4;
             }

@@ -118,62 +118,8 @@ struct HasAddOnStore : std::false_type {};
 template <typename P>
 struct HasAddOnStore<P, std::void_t<decltype(&P::add_on_store)>> : std::true_type {};
 
-// Row log-sum-exp (detected: a policy with a static lse_base(prm, ctx), cross_policy.h CrossLsePolicy; every other policy
-// compiles the epilogue it had): the epilogue also stores, per query row, lse = log sum_j exp(sm_scale * q.k_j) over the keys the row saw,
-// natural log, fp32, at lse_base(prm, ctx)[physical q row].  At the end of the tile loop the probabilities of a row are
-// 2^(s * scale_log2 - m_use - kBias) and l_tot is their sum, so lse = ln2 * (m_use + kBias + log2(l_tot)); a row without keys (l_tot == 0)
-// gives -inf.  Lanes 0..15 of a wave store (one lane per row, 2 x 16 stores per wave and q-tile), rows behind the q-tile's end are not
-// written; no LDS, no barrier.
-template <typename P, typename = void>
-struct HasRowLse : std::false_type {};
-template <typename P>
-struct HasRowLse<P, std::void_t<decltype(&P::lse_base)>> : std::true_type {};
-
-// fp32 rows (detected: a policy with a static o32_base(prm, ctx), the *F32Policy of cross_policy.h / band_policy.h / varblock_policy.h;
-// every other policy compiles the epilogue it had): the epilogue stores acc_o * inv — the value the 16-bit store rounds — as fp32 at
-// o32_base(prm, ctx)[physical q row * D + column], a contiguous [heads, rows, D] in the caller's row order (the row index of the lse
-// store), and writes no 16-bit o.  What a merge over parts of the keys takes without a rounding per part (svg_merge_attention_states_f32).
-// Straight from the accumulator registers: a lane holds four consecutive floats per (db, rb) at column 16 * db + 4 * g4, so one 16-byte
-// store per (db, rb) — the four lanes of a row's quad group fill one 64-byte run; no LDS (the staging region holds 16-bit rows) and no
-// barrier.  Rows behind the q-tile's end (q_phys < 0) store nothing, a row without keys stores zeros (inv == 0).
-template <typename P, typename = void>
-struct HasRowO32 : std::false_type {};
-template <typename P>
-struct HasRowO32<P, std::void_t<decltype(&P::o32_base)>> : std::true_type {};
-// The four fp32 values of one (db, rb).  bf16: the 16-bit store rounds the fp32 product, so the product is the value.  fp16: the 16-bit
-// store of the same accumulators is compiled (-ffast-math contraction) to a mix of v_fma_mixlo_f16 — the exact product rounded once — and
-// v_pk_mul_f32 + v_cvt_pk_f16_f32 — rounded twice — so the fp32 product rounded again by the caller differs from it where the product lies
-// exactly on the midpoint of two fp16 values and the store took the other neighbour (about 3e-5 of the elements).  So the fp16 form
-// also evaluates the 16-bit store's own expression, and where the fp32 product does not round to that value it moves ONE fp32 step
-// towards it: o32 rounded to nearest even is then the 16-bit o, and o32 stays within one fp32 step of acc * inv.  (The empty asm
-// statements keep the two evaluations apart: without them the compiler folds both into one and the comparison is always true.)
-template <typename T, typename E>
-__device__ __forceinline__ f32x4 o32_values(const f32x4& acc, float inv) {
-    f32x4 o4;
-    if constexpr (std::is_same_v<T, _Float16>) {
-        typename E::v4 h4;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) h4[j] = E::from_float(acc[j] * inv);   // the expression of the 16-bit store
-        u32x2 hb = __builtin_bit_cast(u32x2, h4);
-        asm("" : "+v"(hb));
-        h4 = __builtin_bit_cast(typename E::v4, hb);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float a = acc[j];
-            asm("" : "+v"(a));
-            float p = a * inv;
-            asm("" : "+v"(p));
-            const float h = (float)h4[j];
-            if ((float)(_Float16)p != h)   // p is a midpoint and the store took the other neighbour (false for 0 against -0; a NaN stays one)
-                p = __uint_as_float(fabsf(h) > fabsf(p) ? __float_as_uint(p) + 1u : __float_as_uint(p) - 1u);
-            o4[j] = p;
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o4[j] = acc[j] * inv;
-    }
-    return o4;
-}
+// (HasRowLse, HasRowO32 and o32_values, the row log-sum-exp and fp32-row hooks of the epilogue below, live in attn_core.h: the 32x32x16
+//  two-phase body detects them too)
 
 // Row cursor (detected: a policy with kRowCursor, band_policy.h BandPolicy; every other policy keeps kv_cursor_init / kv_phys and compiles
 // the request pipeline it had): the lane's key row is ONE variable stepped in place by P::row_walk_next, the decision between the

@@ -38,6 +38,7 @@ struct BandCall {
     const int32_t* use_alt = nullptr;
     float* lse = nullptr;      // row log-sum-exp output, contiguous fp32 [BH, S] (svg_band_attention_lse: BandLsePolicy), or nullptr
     float* o32 = nullptr;      // with lse: fp32 rows, contiguous [BH, S, 128], instead of o (svg_band_attention_lse_f32: BandF32Policy)
+    bool d64 = false;          // with lse: the head_dim-64 entries (include/svg_attn_band_lse_d64.h: BandLsePolicy64 / BandF32Policy64, rows of 64)
     BandForm form = kBandWhole;
     // kBandWindow (with lse): q / o / lse / o32 hold the rows [q_begin, q_begin + win_Sq), k / v the keys [k_begin, k_begin + win_Sk)
     int32_t q_begin = 0, win_Sq = 0, k_begin = 0, win_Sk = 0;
@@ -673,6 +674,28 @@ struct BandF32Policy : BandLsePolicy<T> {
     }
 };
 
+// Head_dim 64 (svg_band_attention[_switch]_lse_d64[_f32], include/svg_attn_band_lse_d64.h): the two forms on the band policy of the
+// 32x32x16 two-phase body at its head_dim-64 wave count — what CogVideoX runs.  attn_body_pp2 (attn_core.h) detects lse_base / o32_base as
+// attn_body_m16 does; lse and o32 are contiguous fp32 [BH, S] / [BH, S, 64] indexed by the physical q row, as above.
+template <typename T>
+struct BandLsePolicy64 : BandPolicy<T, 64, 8> {
+    using Base = BandPolicy<T, 64, 8>;
+    struct Params : Base::Params {
+        float* lse;   // [BH, S]
+    };
+    static __device__ __forceinline__ float* lse_base(const Params& p, const typename Base::Ctx& c) { return p.lse + (size_t)c.head * (size_t)p.S; }
+};
+template <typename T>
+struct BandF32Policy64 : BandLsePolicy64<T> {
+    using Base = BandLsePolicy64<T>;
+    struct Params : Base::Params {
+        float* o32;   // [BH, S, 64]
+    };
+    static __device__ __forceinline__ float* o32_base(const Params& p, const typename Base::Ctx& c) {
+        return p.o32 + (size_t)c.head * (size_t)p.S * 64;
+    }
+};
+
 // Window forms (svg_band_window_attention_lse[_f32], include/svg_attn_band_window.h): the LSE / fp32 policy over a ROW window and a KEY
 // window of the mask — q / o / lse / o32 hold the rows [q_begin, q_begin + Sq), k / v the keys [k_begin, k_end) of a sequence of S rows, and
 // the mask is evaluated at the global coordinates.  A window is a clip, not a new mask:
@@ -1180,8 +1203,8 @@ inline typename Pol::Params make_band_params(const BandCall& c) {
     p.wrap_phys = 1 - p.F * p.P;
     band_row_regions<Pol>(p, S, 0, S, c.done_nseg);
     // what the LSE / fp32 policies (BandLsePolicy, BandF32Policy and what is built on them) add: lse, and o32 in the place of the 16-bit o
-    if constexpr (std::is_base_of_v<BandLsePolicy<T>, Pol>) p.lse = c.lse;
-    if constexpr (std::is_base_of_v<BandF32Policy<T>, Pol>) p.o32 = c.o32, p.o = nullptr;
+    if constexpr (std::is_base_of_v<BandLsePolicy<T>, Pol> || std::is_base_of_v<BandLsePolicy64<T>, Pol>) p.lse = c.lse;
+    if constexpr (std::is_base_of_v<BandF32Policy<T>, Pol> || std::is_base_of_v<BandF32Policy64<T>, Pol>) p.o32 = c.o32, p.o = nullptr;
     return p;
 }
 
@@ -1248,6 +1271,8 @@ inline typename Pol::Params make_band_shard_params(const BandCall& c) {
 
 // 4 waves x 64 rows, one wave per SIMD (attn_body_w4, attention_w4.hip)
 int run_band_w4(const BandCall& c);
+// attention_band_d64.hip: a validated head_dim-64 LSE / fp32 call (c.d64), single mask or device switch, on the static mapping
+int run_band_lse_d64(const BandCall& c);
 // waves that report per 256-row q-tile of the kernel `variant` selects (completion-counter targets); -1: no counters
 int band_waves_per_tile(int variant);
 

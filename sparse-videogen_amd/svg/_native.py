@@ -281,6 +281,18 @@ BAND_LSE_FORM_SIGNATURES["svg_band_attention_switch_lse_f32"] = BAND_LSE_FORM_SI
 BAND_LSE_FORM_SIGNATURES["svg_band_groups_attention_lse_f32"] = BAND_LSE_FORM_SIGNATURES["svg_band_groups_attention_lse"]
 
 
+# include/svg_attn_band_lse_d64.h: the head_dim-64 namesakes of svg_band_attention_lse[_f32] and svg_band_attention_switch_lse[_f32] — their
+# argument lists — in a table of their own for the same reason (tests/test_band_lse_d64_cpu.py; the allocating wrappers band_attention_lse_d64,
+# band_attention_switch_lse_d64: svg/_band_lse_d64.py, reachable as attributes of this module — __getattr__ at its end; named ..._ENTRIES
+# for the reason ADAPTIVE_BAND_ENTRIES gives; what the wrappers pass is checked on the GPU, in tests/test_gpu_band_lse_d64.py)
+BAND_LSE_D64_ENTRIES = {
+    "svg_band_attention_lse_d64": SPARSE_LSE_SIGNATURES["svg_band_attention_lse"],
+    "svg_band_attention_lse_d64_f32": SPARSE_LSE_SIGNATURES["svg_band_attention_lse"],
+    "svg_band_attention_switch_lse_d64": BAND_LSE_FORM_SIGNATURES["svg_band_attention_switch_lse"],
+    "svg_band_attention_switch_lse_d64_f32": BAND_LSE_FORM_SIGNATURES["svg_band_attention_switch_lse"],
+}
+
+
 # include/svg_attn_band_window.h: band attention over a row window and a key window of the mask, in a table of its own for the same reason
 # (tests/test_band_window_cpu.py)
 BAND_WINDOW_SIGNATURES = {
@@ -443,7 +455,7 @@ def load(strict: bool = True) -> Optional[C.CDLL]:
                                    **BAND_WINDOW_SIGNATURES, **BAND_SHARD_SIGNATURES, **BAND_SHARD_SWITCH_SIGNATURES,
                                    **PROFILE_SHARD_SIGNATURES, **SAMPLE_ROWS_SIGNATURES, **SHARD_EXCHANGE_SIGNATURES,
                                    **ADAPTIVE_TOP_P_SIGNATURES, **ADAPTIVE_BAND_ENTRIES, **ADAPTIVE_BAND_QUEUE_ENTRIES,
-                                   **KMEANS_STEPPED_SIGNATURES, **KMEANS_E4M3_SIGNATURES, **CENTROID_TAIL_ENTRIES}.items():
+                                   **KMEANS_STEPPED_SIGNATURES, **KMEANS_E4M3_SIGNATURES, **CENTROID_TAIL_ENTRIES, **BAND_LSE_D64_ENTRIES}.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -2543,4 +2555,8 @@ def __getattr__(name: str):
         from . import _centroid_tail
 
         return getattr(_centroid_tail, name)
+    if name in ("band_attention_lse_d64", "band_attention_switch_lse_d64"):   # (include/svg_attn_band_lse_d64.h, likewise: svg/_band_lse_d64.py)
+        from . import _band_lse_d64
+
+        return getattr(_band_lse_d64, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -559,6 +559,9 @@ def _svg1_layer_call(what: str, switched: bool, q, k, v, geo: Geometry, mask, pr
         return _dist.run_sharded(whole_heads, (q, k, v), _dist.current_group())   # enable(): this rank's heads only, outputs all-gathered
     mses = sample_mse(q, k, v, geo, prof, num_sampled_rows, sample_max_row, skip_flag=dense_flag, generator=rows_from(), q_prescaled=q_prescaled)
     best_mask_idx = torch.argmin(mses, dim=0)  # [cfg, H] int64; NaN wins like torch.argmin in the reference
+    # head_dim 64 with a quality request that asks for the kept mass: one mask for the batch, no fp8, no sharding (quality: refused above)
+    probe_d64 = (not return_lse and adaptive is None and groups is None and not fp8 and not _local
+                 and _quality_lse_d64_form(quality, q, q_prescaled, fused))
     pk = dict(head_perm_flag=best_mask_idx, vid0=geo.vid0, num_frame=geo.num_frame, frame_size=geo.frame_size)
 
     def final_best():   # (-1 on a dense step, which only the device knows; computed after the launch)
@@ -588,15 +591,17 @@ def _svg1_layer_call(what: str, switched: bool, q, k, v, geo: Geometry, mask, pr
             else:
                 if _local:   # (enable(): contiguous head slices are gathered; token-shard mode: token-major rows are what the outbound exchange sends)
                     kw["token_major_out"] = TOKEN_MAJOR_IO and _dist.token_shards_active()
-                if switched:
+                if probe_d64:   # (quality asked for the kept mass at head_dim 64: the LSE launch of that head size, the same o)
+                    out = _band_lse_d64(switched, q, k, v, mask, dense_mask, dense_flag, **kw, **pk)
+                elif switched:
                     out = _native.band_attention_switch(q, k, v, mask, dense_mask, dense_flag, q_prescaled=q_prescaled, **kw, **pk)
                 else:
                     out = _native.band_attention(q, k, v, mask, q_prescaled=q_prescaled, **kw, **pk)
         best_idx = final_best()
         if quality is not None:
-            o_p, lse_p = out if (return_lse or probe_lse) else (out, None)
+            o_p, lse_p = out if (return_lse or probe_lse or probe_d64) else (out, None)
             log_quality(quality, o_p, lse_p, q, k, v, q_prescaled, **flag_kw)
-            if probe_lse:
+            if probe_lse or probe_d64:
                 out = o_p
         return (out[0], best_idx, out[1]) if return_lse else (out, best_idx)
     # the three kernels of the reference pipeline (the host branch only; no LSE form, no shard form)
@@ -1187,7 +1192,10 @@ def _core_logic_setup(proc, query, timestep, shard_form, valid_lens):
     assert seq_len == rows_of_this_rank(name, geo, shard_form), (
         f"Query Shape: {seq_len} is not equivalent to {geo.context_length} + {geo.num_frame} * {geo.frame_size}")
     valid = valid_lens(cfg, geo) if valid_lens is not None else None
-    return geo, valid, quality_request(name, proc.quality_log, proc.quality_rows, valid, timestep, proc.layer_idx)
+    quality = quality_request(name, proc.quality_log, proc.quality_rows, valid, timestep, proc.layer_idx)
+    if quality is not None:   # (a processor's opt-in to the head_dim-64 LSE launch, see QualityRequest)
+        quality.kept_mass_d64 = bool(getattr(proc, "quality_kept_mass_d64", False))
+    return geo, valid, quality
 
 
 def _knob(proc, option: str, valid_lens, valid):
@@ -1388,6 +1396,10 @@ class QualityRequest:
     valid_len: object = None
     timestep: object = None
     layer: Optional[int] = None
+    # head_dim 64 (CogVideoX): take (o, lse) from the LSE launch of that head size (_native.band_attention[_switch]_lse_d64, the bits of the
+    # plain launch) so that the record carries the kept mass.  Off: the plain launch and "kept_mass": null, as before there was such a launch.
+    # (A class attribute that an instance overrides, not a field: the request's fields, and so its repr and equality, stay as they were.)
+    kept_mass_d64 = False
 
 
 def _refuse_quality_when_sharded(what: str) -> None:
@@ -1404,6 +1416,19 @@ def quality_request(what: str, path, rows: int, valid_len=None, timestep=None, l
         return None
     _refuse_quality_when_sharded(what)
     return QualityRequest(str(path), int(rows), valid_len, timestep, layer)
+
+
+def _quality_lse_d64_form(quality, q: torch.Tensor, q_prescaled: bool, fused: bool = True) -> bool:
+    """does the request ask for the kept mass at head_dim 64, and is the call one the LSE launch of that head size takes?  16-bit, plain q, fused"""
+    return bool(quality is not None and quality.kept_mass_d64 and fused and not q_prescaled and q.shape[-1] == 64
+                and q.dtype in (torch.bfloat16, torch.float16))
+
+
+def _band_lse_d64(switched: bool, q, k, v, mask, dense_mask, dense_flag, **kw):
+    """(o, lse) of the fused SVG1 launch at head_dim 64: the LSE entries of that head size, which _native.band_attention[_switch] refuse"""
+    if switched:
+        return _native.band_attention_switch_lse_d64(q, k, v, mask, dense_mask, dense_flag, **kw)
+    return _native.band_attention_lse_d64(q, k, v, mask, **kw)
 
 
 def _quality_lse_form(q: torch.Tensor, q_prescaled: bool, fused: bool = True) -> bool:

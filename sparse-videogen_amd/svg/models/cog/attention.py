@@ -61,6 +61,9 @@ class CogVideoX_SparseAttn_Processor2_0:
     # file (deferred writes: flush_quality_log()).  None: nothing changes.  Refused under svg.distributed.
     quality_log = None
     quality_rows = 64
+    # head_dim 64 has an LSE launch of its own (_native.band_attention[_switch]_lse_d64, the bits of the plain launch): True -> the records
+    # carry "kept_mass"; False (default): the plain launch, "kept_mass": null
+    quality_kept_mass_d64 = False
 
     def __init__(self, layer_idx):
         self.layer_idx = layer_idx
