@@ -51,7 +51,7 @@ KEEP_ASM = {"attention_w4.hip", "attention.hip", "attention_varblock.hip", "atte
 # Files compiled without the packed fp32 instructions (v_pk_mul_f32, v_pk_add_f32, v_pk_fma_f32): every fp32 product and sum is a scalar
 # instruction, so what a row rounds does not depend on which pairs the vectoriser found.  (The older units keep their flags: their listings
 # and output bits are pinned as they are.)
-NO_PACKED_FP32 = {"attention_band_d64.hip"}
+NO_PACKED_FP32 = {"attention_band_d64.hip", "attention_varblock_lse.hip"}
 
 
 def _newest_header() -> float:

@@ -477,6 +477,7 @@ struct VbCall {
     F8GArgs f8{};                                   // kF8: the quantised tensors and scales of f8g_quantize
     float* lse = nullptr;                           // kM16: row log-sum-exp output, contiguous fp32 [Hq, Sq] (svg_varblock_attention_lse), or nullptr
     float* o32 = nullptr;                           // with lse: fp32 rows, contiguous [Hq, Sq, 128], instead of o (svg_varblock_attention_lse_f32)
+    bool lse_auto = false;                          // with lse: svg_varblock_attention_lse_auto[_f32] — also kLockstep128, and kPP2 at head_dim 64 (o32: [Hq, Sq, D])
 };
 
 // The workspace of a call, and the one definition of its layout (_native.varblock_launch_order / varblock_partners read it at fixed
@@ -576,6 +577,10 @@ static int run_varblock(const VbCall& c) {
     };
     auto lockstep = [&](auto nw_c, int mode, const int32_t* toff, int max_tiles) {
         constexpr int W = decltype(nw_c)::value;
+        if (c.lse) {   // the same plan, tile table and grid for the policies that also store lse, or fp32 rows (attention_varblock_lse.hip)
+            if constexpr (W == 4) return launch_varblock_lockstep_lse<T, D>(params(nw_c, mode, toff, max_tiles), c.lse, c.o32, dim3(max_tiles, Hq), lds_vb, st);
+            else return SVG_ERR_UNSUPPORTED;
+        }
         return launch_attn(varblock_attn_kernel<T, D, W>, dim3(max_tiles, Hq), W * 64, attn_lds_bytes<D, W>() + lds_vb, st,
                            params(nw_c, mode, toff, max_tiles));
     };
@@ -625,7 +630,10 @@ static int run_varblock(const VbCall& c) {
                     return launch(VarblockPolicy<T, 128, 8>());
                 }
             }
-            if (c.lse) return SVG_ERR_UNSUPPORTED;
+            if (c.lse) {   // head_dim 64: likewise (attention_varblock_lse.hip)
+                if constexpr (D == 64) return launch_varblock_pp2_lse_d64<T>(p, c.lse, c.o32, grid, lds_vb, st);
+                else return SVG_ERR_UNSUPPORTED;
+            }
             return launch_attn(varblock_attn_pp2_kernel<T, D>, grid, 512, attn_pp2_lds_bytes<D>() + lds_vb, st, p);
         }
     }
@@ -693,7 +701,13 @@ static int varblock_entry(VbCall& c, int variant, const svg_attn_layout_t* layou
         c.lay = &lay;
     }
     if (!vb_decode_variant(variant, c)) return SVG_ERR_BAD_ARG;
-    if (c.lse && (c.D != 128 || c.body != VbBody::kM16 || c.trace || c.block_row_order)) return SVG_ERR_UNSUPPORTED;   // (fp32 etc.: dispatch_td)
+    // the softmax state: from the 16x16x32 body, and for the _auto entries from the 128-row lock-step body and the 32x32x16 body at head_dim
+    // 64 as well; no form with a trace, in block-row order, on the 256-row lock-step or mixed tilings (fp32 tensors etc.: dispatch_td)
+    if (c.lse) {
+        const bool form = (c.body == VbBody::kM16 && c.D == 128) ||
+                          (c.lse_auto && (c.body == VbBody::kLockstep128 || (c.body == VbBody::kPP2 && c.D == 64)));
+        if (!form || c.trace || c.block_row_order) return SVG_ERR_UNSUPPORTED;
+    }
     if (c.o32 && ((size_t)c.o32 & 15) != 0) return SVG_ERR_UNSUPPORTED;   // 16-byte stores
     const bool two_phase = c.body == VbBody::kM16 || c.body == VbBody::kPP2;
     if (c.lay && !(two_phase && !c.trace)) return SVG_ERR_UNSUPPORTED;   // strided tensors: the two-phase bodies only (see svg_attn_layout_t)
@@ -747,6 +761,33 @@ extern "C" int svg_varblock_attention_lse_f32(const void* q, const void* k, cons
     svg_attn_layout_t abi{};
     if (layout) abi = *layout, abi.o = abi.q;
     return varblock_entry(c, 3, layout ? &abi : nullptr);
+}
+
+// include/svg_attn_varblock_lse_auto.h: the two entries above with the body chosen as svg_varblock_attention(variant = -1) chooses it
+extern "C" int svg_varblock_attention_lse_auto(const void* q, const void* k, const void* v, void* o, float* lse, int32_t Hq, int32_t Hkv,
+                                               int32_t Sq, int32_t Skv, int32_t D, int32_t dtype, float sm_scale, const uint8_t* block_map,
+                                               const int32_t* q_sizes, const int32_t* k_sizes, int32_t QB, int32_t KB,
+                                               const int32_t* q_row_idx, const int32_t* kv_row_idx, void* workspace, size_t workspace_bytes,
+                                               const svg_attn_layout_t* layout, void* stream) {
+    if (!lse) return SVG_ERR_BAD_ARG;
+    VbCall c{q, k, v, o, Hq, Hkv, Sq, Skv, D, dtype, sm_scale, block_map, q_sizes, k_sizes, QB, KB, q_row_idx, kv_row_idx, workspace,
+             workspace_bytes, (hipStream_t)stream};
+    c.lse = lse, c.lse_auto = true;
+    return varblock_entry(c, -1, layout);
+}
+
+extern "C" int svg_varblock_attention_lse_auto_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t Hq,
+                                                   int32_t Hkv, int32_t Sq, int32_t Skv, int32_t D, int32_t dtype, float sm_scale,
+                                                   const uint8_t* block_map, const int32_t* q_sizes, const int32_t* k_sizes, int32_t QB,
+                                                   int32_t KB, const int32_t* q_row_idx, const int32_t* kv_row_idx, void* workspace,
+                                                   size_t workspace_bytes, const svg_attn_layout_t* layout, void* stream) {
+    if (!o32 || !lse) return SVG_ERR_BAD_ARG;
+    VbCall c{q, k, v, layout ? const_cast<void*>(q) : (void*)o32, Hq, Hkv, Sq, Skv, D, dtype, sm_scale, block_map, q_sizes, k_sizes, QB, KB,
+             q_row_idx, kv_row_idx, workspace, workspace_bytes, (hipStream_t)stream};
+    c.lse = lse, c.o32 = o32, c.lse_auto = true;
+    svg_attn_layout_t abi{};
+    if (layout) abi = *layout, abi.o = abi.q;   // (as svg_varblock_attention_lse_f32: o32 is contiguous, the o member is not read)
+    return varblock_entry(c, -1, layout ? &abi : nullptr);
 }
 
 extern "C" int svg_varblock_attention_fp8(const void* q, const void* k, const void* v, void* o, int32_t Hq, int32_t Hkv, int32_t Sq,

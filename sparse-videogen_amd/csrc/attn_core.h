@@ -59,6 +59,13 @@ __device__ __forceinline__ i16x8 lds_read_tr16x2(const char* p_lo, const char* p
     return __builtin_shufflevector(lds_read_tr16(p_lo), lds_read_tr16(p_hi), 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
+// Row log-sum-exp and fp32 rows of the lock-step body (declared here, defined with the hooks' other users behind the body)
+template <typename P, typename = void>
+struct HasRowLse;
+template <typename T, int D, int NW, typename P>
+__device__ __forceinline__ void lockstep_state_epilogue(const typename P::Params& prm, const typename P::Ctx& ctx, char* smem,
+                                                        const f32x16 (&acc_o)[D / 32], float m_run, float l_tot);
+
 // The attention kernel body.  Policy P supplies (all functions static __device__):
 //   struct Params; struct Ctx (workgroup-uniform);
 //   bool init(const Params&, Ctx&, char* policy_lds)            -> false: nothing to do (uniform exit)
@@ -350,6 +357,9 @@ __device__ __forceinline__ void attn_body(const typename P::Params& prm, char* s
         for (int rb = 0; rb < RB; ++rb)
             P::store_partial(prm, ctx, wave * WR + rb * 32 + ql, g, acc_o[rb], m_run[rb], l_tot[rb]);
         return;
+    } else if constexpr (HasRowLse<P>::value) {
+        lockstep_state_epilogue<T, D, NW, P>(prm, ctx, smem, acc_o[0], m_run[0], l_tot[0]);   // (below the body; RB == 1)
+        return;
     } else {
     // transpose through LDS (all waves are past the last barrier, stage buffers are free): row stride D*2+8 bytes
     constexpr int kEpiStride = D * 2 + 8;
@@ -536,7 +546,7 @@ static inline int read_trace_here(uint64_t* out, bool wg, int n_workgroups) {
 // 2^(s * scale_log2 - m_use - kBias) and l_tot is their sum, so lse = ln2 * (m_use + kBias + log2(l_tot)); a row without keys (l_tot == 0)
 // gives -inf.  Lanes 0..15 of a wave store (one lane per row, 2 x 16 stores per wave and q-tile), rows behind the q-tile's end are not
 // written; no LDS, no barrier.
-template <typename P, typename = void>
+template <typename P, typename>   // (the default argument: at the declaration in front of attn_body)
 struct HasRowLse : std::false_type {};
 template <typename P>
 struct HasRowLse<P, std::void_t<decltype(&P::lse_base)>> : std::true_type {};
@@ -633,6 +643,99 @@ __device__ __forceinline__ f32x4 pp2_row32_values(const f32x4& acc, float inv) {
         o4[j] = p;
     }
     return o4;
+}
+
+// The epilogue of the lock-step body attn_body (NW waves x 32 rows, one row block per wave) for a policy with lse_base (HasRowLse), and
+// with o32_base (HasRowO32): what the plain epilogue stores, plus the softmax state.  Called behind the body's last barrier, so every
+// stage is free.  The plain fp16 lock-step kernels (attention_varblock.hip: varblock_attn_kernel<_Float16, 128 / 64, 4>) round elements
+// 0 and 3 of every four once and 1 and 2 twice, as the head_dim-64 two-phase kernels do — their listings show v_fma_mixlo_f16 on the
+// former and v_pk_mul_f32 + v_cvt_pk_f16_f32 on the latter — so pp2_row16_values / pp2_row32_values above state this body's bits too.
+//   lse   m_run is the row's running maximum in the log2 domain (-inf before its first key), the same in lane l and lane l ^ 32 (the
+//         maximum is exchanged every tile); the probabilities are 2^(s * scale_log2 - m_use) with m_use = m_run (0 for -inf), and l_tot
+//         is their sum, the two half-row sums already added: lse = ln2 * (m_use + log2 l_tot), -inf for a row without keys (o: zeros).
+//         In the 32x32x16 accumulator layout lane (ql, g) owns query row ql of its wave for the whole kernel, g = 0 / 1 the halves of the
+//         key and d ranges, and both lanes hold the row's statistics in registers: the g == 0 lane stores, 32 stores per wave, no LDS,
+//         no barrier.  (The other half would store the same value; one store per row is enough.)
+//   o32   a row of D floats is D / 4 16-byte chunks (32 at D = 128: 512 bytes; 16 at D = 64: 256 bytes); per (db, rq) the lane holds
+//         columns 32 db + 8 rq + 4 g + [0, 4): chunk c = 8 db + 2 rq + g of row ql.  The wave stages its 32 rows in the stages, rows D * 4
+//         bytes apart — NW x 32 x D x 4 bytes are exactly the two stages, so there is no room for a pad — with chunk c of row r at
+//         position c ^ (r & 15).  Derivation (64 banks of 4 bytes: a 16-byte access of 16 lanes is one pass without a conflict when the
+//         16 addresses differ in bits 4..7): the row pitch is a multiple of 256 bytes, so bits 4..7 of an address are the low four bits
+//         of the chunk position, (c & 15) ^ (r & 15).  A stage WRITE is one instruction per (db, rq): its four quarters are lanes
+//         (ql 0..15, g), (ql 16..31, g) — c fixed, sixteen different r & 15: sixteen different bank groups.  A row READ is D / 4 lanes
+//         per row: a quarter reads sixteen consecutive chunks of ONE row — r fixed, c & 15 all different: again sixteen.  Both are
+//         conflict-free, at either head size.  The rows leave whole: 64 lanes x 16 bytes = two rows of 512 bytes (D = 128) or four of
+//         256 (D = 64) per store instruction, sixteen / eight instructions per wave; the wave's own LDS writes only, so a wave barrier.
+//   o     the 16-bit rows (no o32_base): staged and stored as the plain epilogue does, values from pp2_row16_values.
+// Rows behind the tile's end (q_phys < 0) store nothing.
+template <typename T, int D, int NW, typename P>
+__device__ __forceinline__ void lockstep_state_epilogue(const typename P::Params& prm, const typename P::Ctx& ctx, char* smem,
+                                                        const f32x16 (&acc_o)[D / 32], float m_run, float l_tot) {
+    using E = Elt<T>;
+    constexpr int DB = D / 32;
+    static_assert(P::kRowBlocks == 1 && !P::kFixup && !P::kPartialOut, "softmax state: plain scores, one row block per wave");
+    const int lane = threadIdx.x & 63, wave = wave_id(), g = lane >> 5, ql = lane & 31;
+    const float inv = l_tot > 0.f ? __builtin_amdgcn_rcpf(l_tot) : 0.f;   // (v_rcp_f32, what the plain epilogue's 1 / l_tot compiles to)
+    {
+        const int qp = P::q_phys(prm, ctx, wave * 32 + ql);
+        const float m_use = (m_run == -INFINITY) ? 0.f : m_run;
+        if (g == 0 && qp >= 0)
+            P::lse_base(prm, ctx)[qp] = l_tot > 0.f ? 0.6931471805599453f * (m_use + __builtin_amdgcn_logf(l_tot)) : -INFINITY;
+    }
+    if constexpr (HasRowO32<P>::value) {
+        constexpr int kRow = D * 4;   // bytes
+        static_assert(NW * 32 * kRow <= attn_lds_bytes<D, NW>(), "fp32 rows: staged in the two K/V stages");
+        char* const erow32 = smem + (size_t)(wave * 32) * kRow;
+#pragma unroll
+        for (int db = 0; db < DB; ++db)
+#pragma unroll
+            for (int rq = 0; rq < 4; ++rq) {
+                const f32x4 a4 = {acc_o[db][rq * 4], acc_o[db][rq * 4 + 1], acc_o[db][rq * 4 + 2], acc_o[db][rq * 4 + 3]};
+                const int c = 8 * db + 2 * rq + g;
+                *(f32x4*)(erow32 + ql * kRow + ((c ^ (ql & 15)) << 4)) = pp2_row32_values<T, E>(a4, inv);
+            }
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_wave_barrier();
+        float* __restrict__ ob32 = P::o32_base(prm, ctx);
+        constexpr int kLanesPerRow = D / 4;   // 16 B per lane
+        constexpr int kRowsPerPass = 64 / kLanesPerRow;
+        constexpr int kPasses = 32 / kRowsPerPass;
+        const int sub = lane / kLanesPerRow, c = lane - sub * kLanesPerRow;
+        int ephys[kPasses];
+#pragma unroll
+        for (int i = 0; i < kPasses; ++i) ephys[i] = P::q_phys(prm, ctx, wave * 32 + i * kRowsPerPass + sub);
+#pragma unroll
+        for (int i = 0; i < kPasses; ++i) {
+            const int rr = i * kRowsPerPass + sub;
+            const f32x4 val = *(const f32x4*)(erow32 + rr * kRow + ((c ^ (rr & 15)) << 4));
+            if (ephys[i] >= 0) *(f32x4*)(ob32 + (size_t)ephys[i] * D + 4 * c) = val;
+        }
+    } else {
+        constexpr int kEpiStride = D * 2 + 8;
+        char* erow = smem + (size_t)(wave * 32) * kEpiStride;
+#pragma unroll
+        for (int db = 0; db < DB; ++db)
+#pragma unroll
+            for (int rq = 0; rq < 4; ++rq) {
+                const f32x4 a4 = {acc_o[db][rq * 4], acc_o[db][rq * 4 + 1], acc_o[db][rq * 4 + 2], acc_o[db][rq * 4 + 3]};
+                *(typename E::v4*)(erow + ql * kEpiStride + (32 * db + 8 * rq + 4 * g) * 2) = pp2_row16_values<T, E>(a4, inv);
+            }
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_wave_barrier();
+        T* __restrict__ ob = P::o_base(prm, ctx);
+        constexpr int kLanesPerRow = D * 2 / 8;   // 8 B per lane
+        constexpr int kRowsPerPass = 64 / kLanesPerRow;
+        constexpr int kPasses = 32 / kRowsPerPass;
+        const int sub = lane / kLanesPerRow, colb = (lane - sub * kLanesPerRow) * 8;
+        int ephys[kPasses];
+#pragma unroll
+        for (int i = 0; i < kPasses; ++i) ephys[i] = P::q_phys(prm, ctx, wave * 32 + i * kRowsPerPass + sub);
+#pragma unroll
+        for (int i = 0; i < kPasses; ++i) {
+            const u32x2 val = *(const u32x2*)(erow + (i * kRowsPerPass + sub) * kEpiStride + colb);
+            if (ephys[i] >= 0) *(u32x2*)((char*)(ob + (size_t)ephys[i] * D) + colb) = val;
+        }
+    }
 }
 
 // =====================================================================================================================

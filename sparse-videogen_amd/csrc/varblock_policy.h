@@ -263,6 +263,37 @@ struct VarblockF32Policy : VarblockLsePolicy<T> {
     }
 };
 
+// The same two forms for the other bodies `variant = -1` picks (svg_varblock_attention_lse_auto[_f32], include/svg_attn_varblock_lse_auto.h):
+// the lock-step body on 128-row q-tiles (attn_body, NW = 4; D = 128 and 64 — attn_core.h lockstep_state_epilogue) and the 32x32x16
+// two-phase body at head_dim 64 (attn_body_pp2, NW = 8).  lse [Hq, Sq] and o32 [Hq, Sq, D] as above; both bodies detect lse_base / o32_base.
+template <typename T, int D, int NW>
+struct VarblockLsePolicyOf : VarblockPolicy<T, D, NW> {
+    using Base = VarblockPolicy<T, D, NW>;
+    struct Params : Base::Params {
+        float* lse;   // [Hq, Sq]
+    };
+    static __device__ __forceinline__ float* lse_base(const Params& p, const typename Base::Ctx& c) { return p.lse + (size_t)c.hq * (size_t)p.Sq; }
+};
+template <typename T, int D, int NW>
+struct VarblockF32PolicyOf : VarblockLsePolicyOf<T, D, NW> {
+    using Base = VarblockLsePolicyOf<T, D, NW>;
+    struct Params : Base::Params {
+        float* o32;   // [Hq, Sq, D]
+    };
+    static __device__ __forceinline__ float* o32_base(const Params& p, const typename Base::Ctx& c) {
+        return p.o32 + (size_t)c.hq * (size_t)p.Sq * D;
+    }
+};
+
+// attention_varblock_lse.hip: the kernels of these policies and their launches — `p` is the plain call's parameter block (plan, launch
+// order, tile table), grid and policy LDS the plain launch's; o32 != nullptr: the fp32 form (p.o is then not used)
+template <typename T, int D>
+int launch_varblock_lockstep_lse(const typename VarblockPolicy<T, D, 4>::Params& p, float* lse, float* o32, dim3 grid, int lds_policy,
+                                 hipStream_t st);
+template <typename T>
+int launch_varblock_pp2_lse_d64(const typename VarblockPolicy<T, 64, 8>::Params& p, float* lse, float* o32, dim3 grid, int lds_policy,
+                                hipStream_t st);
+
 static inline int vb_policy_lds(int kb_cap) { return (2 * (kb_cap + 2) + 32) * (int)sizeof(int32_t); }
 
 }  // namespace svg

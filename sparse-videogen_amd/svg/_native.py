@@ -293,6 +293,16 @@ BAND_LSE_D64_ENTRIES = {
 }
 
 
+# include/svg_attn_varblock_lse_auto.h: svg_varblock_attention_lse[_f32] — their argument list — on the body variant -1 picks, in a table
+# of their own for the same reason (tests/test_varblock_lse_auto_cpu.py; the allocating wrapper varblock_attention_lse_auto:
+# svg/_varblock_lse_auto.py, reachable as an attribute of this module — __getattr__ at its end — and through
+# varblock_attention(return_lse=True, body="auto"); what it passes is checked on the GPU, in tests/test_gpu_varblock_lse_auto.py)
+VARBLOCK_LSE_AUTO_ENTRIES = {
+    "svg_varblock_attention_lse_auto": SPARSE_LSE_SIGNATURES["svg_varblock_attention_lse"],
+    "svg_varblock_attention_lse_auto_f32": SPARSE_LSE_SIGNATURES["svg_varblock_attention_lse"],
+}
+
+
 # include/svg_attn_band_window.h: band attention over a row window and a key window of the mask, in a table of its own for the same reason
 # (tests/test_band_window_cpu.py)
 BAND_WINDOW_SIGNATURES = {
@@ -455,7 +465,8 @@ def load(strict: bool = True) -> Optional[C.CDLL]:
                                    **BAND_WINDOW_SIGNATURES, **BAND_SHARD_SIGNATURES, **BAND_SHARD_SWITCH_SIGNATURES,
                                    **PROFILE_SHARD_SIGNATURES, **SAMPLE_ROWS_SIGNATURES, **SHARD_EXCHANGE_SIGNATURES,
                                    **ADAPTIVE_TOP_P_SIGNATURES, **ADAPTIVE_BAND_ENTRIES, **ADAPTIVE_BAND_QUEUE_ENTRIES,
-                                   **KMEANS_STEPPED_SIGNATURES, **KMEANS_E4M3_SIGNATURES, **CENTROID_TAIL_ENTRIES, **BAND_LSE_D64_ENTRIES}.items():
+                                   **KMEANS_STEPPED_SIGNATURES, **KMEANS_E4M3_SIGNATURES, **CENTROID_TAIL_ENTRIES, **BAND_LSE_D64_ENTRIES,
+                                   **VARBLOCK_LSE_AUTO_ENTRIES}.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -1492,7 +1503,8 @@ def varblock_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_
                        k_sizes: torch.Tensor, sm_scale: Optional[float] = None, q_row_idx: Optional[torch.Tensor] = None,
                        kv_row_idx: Optional[torch.Tensor] = None, variant: int = -1, fp8: bool = False,
                        workspace: Optional[torch.Tensor] = None, token_major_out: bool = False,
-                       rows_covered: bool = False, return_lse: bool = False, out_dtype: Optional[torch.dtype] = None):
+                       rows_covered: bool = False, return_lse: bool = False, out_dtype: Optional[torch.dtype] = None,
+                       body: Optional[str] = None):
     """q: [Hq, Sq, D], k/v: [Hkv, Skv, D] (or [B, H, S, D]: heads = B * H); block_map bool [Hkv, QB, KB]; sizes int32 [Hkv, QB] /
     [Hkv, KB].  -> o of q's shape.
     fp8=True: e4m3 QK^T / PV (svg_varblock_attention_fp8, D = 128, default schedule only).
@@ -1508,8 +1520,20 @@ def varblock_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_
     3 — variant -1, 3 or 8; anything else raises ValueError); o has the bits of variant 3.
     out_dtype=torch.float32 (with return_lse=True, without token_major_out; ValueError otherwise): (o32, lse) with o32 the rows before
     their rounding, contiguous fp32 of q's shape (svg_varblock_attention_lse_f32), zero-filled first unless rows_covered — parts for
-    merge_attention_states, which then rounds once; o32.to(q.dtype) is the o of return_lse=True."""
+    merge_attention_states, which then rounds once; o32.to(q.dtype) is the o of return_lse=True.
+    body="auto" (with return_lse=True and variant -1; None: the above): the state comes from the body the plain variant -1 call runs —
+    128-row lock-step tiles below Sq = 160 QB, the two-phase bodies from there on — at head_dim 128 and 64, and o has the bits of that
+    plain call (svg_varblock_attention_lse_auto[_f32]; svg/_varblock_lse_auto.py)."""
     f32 = _want_f32_parts("varblock_attention", out_dtype, return_lse, None, token_major_out)
+    if body is not None:
+        if body != "auto" or not return_lse or fp8 or variant != -1:
+            raise ValueError('varblock_attention(body=...): None, or "auto" with return_lse=True, variant -1 and 16-bit tensors; '
+                             f"got body = {body!r}, return_lse = {return_lse}, variant = {variant}, fp8 = {fp8}")
+        from . import _varblock_lse_auto
+
+        return _varblock_lse_auto.varblock_attention_lse_auto(q, k, v, block_map, q_sizes, k_sizes, sm_scale=sm_scale, q_row_idx=q_row_idx,
+                                                              kv_row_idx=kv_row_idx, workspace=workspace, token_major_out=token_major_out,
+                                                              rows_covered=rows_covered, out_dtype=out_dtype)
     if return_lse:
         if fp8 or variant not in (-1, 3, 8) or q.shape[-1] != 128:
             raise ValueError("varblock_attention(return_lse=True): head_dim 128, 16-bit, variant -1 / 3 / 8 (the two-phase 16x16x32 body); "
@@ -2559,4 +2583,8 @@ def __getattr__(name: str):
         from . import _band_lse_d64
 
         return getattr(_band_lse_d64, name)
+    if name == "varblock_attention_lse_auto":   # (include/svg_attn_varblock_lse_auto.h, likewise: svg/_varblock_lse_auto.py)
+        from . import _varblock_lse_auto
+
+        return _varblock_lse_auto.varblock_attention_lse_auto
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

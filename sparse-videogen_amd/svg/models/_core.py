@@ -743,14 +743,25 @@ def _refuse_centroid_tail_when_sharded(what: str, head_shard=None) -> None:
                                   f"implemented: the means and the tail read whole heads of the whole sequence; unset centroid_tail or run on one GPU")
 
 
-def _refuse_centroid_tail(what: str, q: torch.Tensor, block_rows: int, adaptive=None, head_shard=None) -> None:
-    """What the centroid tail refuses, all of it before anything runs: there is no silent fall-back to the sparse part alone."""
+def _varblock_lse_auto_form(q: torch.Tensor) -> bool:
+    """does svg_varblock_attention_lse_auto take this call — the state from whatever body the plain call runs, at any S / block-rows?
+    head_dim 128 or 64, 16-bit (not fp8)"""
+    return bool(q.shape[-1] in (64, 128) and not _use_fp8(q) and q.dtype in (torch.bfloat16, torch.float16))
+
+
+def _refuse_centroid_tail(what: str, q: torch.Tensor, block_rows: int, adaptive=None, head_shard=None, lse_auto: bool = False) -> None:
+    """What the centroid tail refuses, all of it before anything runs: there is no silent fall-back to the sparse part alone.
+    lse_auto: the sparse part runs its auto LSE form, so S >= 160 block-rows is not asked for; head_dim 128 stays — the tail kernel has no
+    other — and so does the refusal of fp8."""
     _refuse_centroid_tail_when_sharded(what, head_shard)
     if adaptive is not None:
         raise ValueError(f"{what}: centroid_tail together with adaptive_top_p is not implemented — the controller steers on the kept mass of "
                          f"the sparse part alone; unset one of them")
     S, D = q.shape[-2], q.shape[-1]
-    if D != 128 or _use_fp8(q) or q.dtype not in (torch.bfloat16, torch.float16) or S < 160 * block_rows:
+    if lse_auto and (D != 128 or not _varblock_lse_auto_form(q)):
+        raise ValueError(f"{what}(centroid_tail=True, lse_auto=True): the tail kernel is head_dim 128, bf16 / fp16 (not fp8) — head_dim 64 has "
+                         f"none; got D = {D}, {q.dtype}, fp8 = {_use_fp8(q)}")
+    if not lse_auto and (D != 128 or _use_fp8(q) or q.dtype not in (torch.bfloat16, torch.float16) or S < 160 * block_rows):
         raise ValueError(f"{what}(centroid_tail=True): the tail is merged with the sparse call through its row log-sum-exp — head_dim 128, bf16 / "
                          f"fp16 (not fp8), S >= 160 block-rows; got D = {D}, {q.dtype}, fp8 = {_use_fp8(q)}, S = {S}, block-rows = {block_rows}")
 
@@ -762,9 +773,15 @@ def _refuse_kept_mass_knob_when_sharded(what: str, knob: str) -> None:
                                   f"implemented: the probe reads whole heads of the whole sequence; unset {knob} or run on one GPU")
 
 
-def _refuse_adaptive_without_lse(what: str, q: torch.Tensor, block_rows: int) -> None:
-    """ValueError where the variable-block launch of this call has no LSE form with the plain call's o: there is no silent fall-back."""
+def _refuse_adaptive_without_lse(what: str, q: torch.Tensor, block_rows: int, lse_auto: bool = False) -> None:
+    """ValueError where the variable-block launch of this call has no LSE form with the plain call's o: there is no silent fall-back.
+    lse_auto: the auto LSE form — any S / block-rows, head_dim 128 and 64; fp8 is still refused."""
     S, D = q.shape[-2], q.shape[-1]
+    if lse_auto:
+        if not _varblock_lse_auto_form(q):
+            raise ValueError(f"{what}(adaptive=..., lse_auto=True): the controller needs the row log-sum-exp of the sparse call — head_dim 128 or "
+                             f"64, bf16 / fp16 (not fp8); got D = {D}, {q.dtype}, fp8 = {_use_fp8(q)}")
+        return
     if D != 128 or _use_fp8(q) or q.dtype not in (torch.bfloat16, torch.float16) or S < 160 * block_rows:
         raise ValueError(f"{what}(adaptive=...): the controller needs the row log-sum-exp of the sparse call — head_dim 128, bf16 / fp16 (not "
                          f"fp8), S >= 160 block-rows; got D = {D}, {q.dtype}, fp8 = {_use_fp8(q)}, S = {S}, block-rows = {block_rows}")
@@ -1031,17 +1048,19 @@ def kmeans_clustering(store: CentroidStore, layer_idx: int, q_video, k_video, nu
     return (ql, qc, qs, qit, qidx), (kl, kc, ks, kit, kidx)
 
 
-def _sparse_plus_centroid_tail(q, k, v, dyn_map, q_sizes, k_sizes, qidx, kidx, tail_k, KC: int, token_major: bool):
+def _sparse_plus_centroid_tail(q, k, v, dyn_map, q_sizes, k_sizes, qidx, kidx, tail_k, KC: int, token_major: bool, lse_auto: bool = False):
     """svg2_sparse_attention(centroid_tail=True) from the block map on: the sparse launch in its LSE form into a contiguous head-major
     part, the means of the call's own key clusters, the tail launch into the second part, and the merge — token-major wherever the plain
     call's output would be.  tail_k = (the video keys [cfg, H, V, D], their cluster sizes [cfg * H, KC], their sorted indices [cfg * H, V])
-    as the k-means returned them.  -> (out, merged lse [cfg, H, S])"""
+    as the k-means returned them.  lse_auto: the sparse part's state comes from the body the plain call runs (varblock_attention(body="auto")),
+    so the tail merges with it below S = 160 block-rows too.  -> (out, merged lse [cfg, H, S])"""
     cfg, H, S, D = q.shape
     QB, KB = q_sizes.shape[-1], k_sizes.shape[-1]
     maps = dyn_map.view(cfg * H, QB, KB).contiguous()
     qsz, rows = q_sizes.view(cfg * H, QB).contiguous(), qidx.contiguous()
     o_s, lse_s = _native.varblock_attention(q, k, v, maps, qsz, k_sizes.view(cfg * H, KB).contiguous(), q_row_idx=rows,
-                                            kv_row_idx=kidx.contiguous(), rows_covered=True, return_lse=True)
+                                            kv_row_idx=kidx.contiguous(), rows_covered=True, return_lse=True,
+                                            **({"body": "auto"} if lse_auto else {}))
     kv, ks, kidx_v = tail_k
     V = kv.shape[2]
     ks, kidx_v = ks.reshape(cfg * H, KC).contiguous(), kidx_v.reshape(cfg * H, V).contiguous()
@@ -1059,7 +1078,8 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
                           num_k_centroids: int, top_p: float, min_kc_ratio: float, iter_init: int, iter_step: int,
                           prompt_length=0, logging_file: Optional[str] = None, timestep=None, _head_shard=None,
                           quality: Optional["QualityRequest"] = None, adaptive: Optional[AdaptiveTopP] = None,
-                          top_p_store: Optional[TopPStore] = None, kmeans_e4m3: bool = False, centroid_tail: bool = False):
+                          top_p_store: Optional[TopPStore] = None, kmeans_e4m3: bool = False, centroid_tail: bool = False,
+                          lse_auto: bool = False):
     """The sparse branch of the SAP processors (ref: hyvideo/attention.py:747-804, wan/attention.py:529-559):
     k-means on the video tokens -> top-p block map -> (Hunyuan) two pseudo clusters for prompt / unused prompt ->
     variable-block attention with the token permutation fused in (the result is already in the original order).
@@ -1083,11 +1103,17 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
     update away), weighted with the cluster's size (include/svg_attn_centroid_tail.h) — and that state is merged with the sparse call's
     (merge_attention_states).  HunyuanVideo: the video clusters only, and the unused-prompt rows get no tail.  A `quality` record is then
     measured on the merged output and lse and carries "centroid_tail": true.  NotImplementedError under svg.distributed; ValueError
-    together with `adaptive`, and where the launch has no LSE form (the rule of `adaptive`).  False: nothing changes."""
+    together with `adaptive`, and where the launch has no LSE form (the rule of `adaptive`).  False: nothing changes.
+    lse_auto (the processors' varblock_lse_auto): wherever this call asks for the row log-sum-exp it runs the auto LSE form
+    (svg_varblock_attention_lse_auto: the state from the body the plain call runs, o the plain call's bits), so the kept mass is logged and
+    `adaptive` works at any S / block-rows — Cosmos at its production cluster count, a raised num_q_centroids — and at head_dim 64, and
+    `centroid_tail` at any S / block-rows (head_dim 128: the tail kernel has no other).  Still refused: fp8, and head_dim 64 for the tail.
+    False: the refusals and the launches of before."""
     if kmeans_e4m3:
         _refuse_kmeans_e4m3_when_sharded("svg2_sparse_attention", _head_shard)
     if centroid_tail:
-        _refuse_centroid_tail("svg2_sparse_attention", q, num_q_centroids + (2 if geo.context_length else 0), adaptive, _head_shard)
+        _refuse_centroid_tail("svg2_sparse_attention", q, num_q_centroids + (2 if geo.context_length else 0), adaptive, _head_shard,
+                              **({"lse_auto": True} if lse_auto else {}))
     if quality is not None:
         _refuse_quality_when_sharded("svg2_sparse_attention")
     if adaptive is not None:
@@ -1095,7 +1121,8 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
         if top_p_store is None:
             raise ValueError("svg2_sparse_attention(adaptive=...) needs a top_p_store (TopPStore): the thresholds live there between calls")
         # (block-rows of the launch: the query clusters, and Hunyuan's two text pseudo-clusters behind them)
-        _refuse_adaptive_without_lse("svg2_sparse_attention", q, num_q_centroids + (2 if geo.context_length else 0))
+        _refuse_adaptive_without_lse("svg2_sparse_attention", q, num_q_centroids + (2 if geo.context_length else 0),
+                                     **({"lse_auto": True} if lse_auto else {}))
     _require_gpu(q, "SVG2 sparse attention")
     pl = per_video(prompt_length, q.shape[0], "svg2_sparse_attention(prompt_length)")
     if pl is not None:
@@ -1146,15 +1173,19 @@ def svg2_sparse_attention(q, k, v, geo: Geometry, store: CentroidStore, layer_id
     #  dynamic_map_post_processing — so the kernel writes every output row and the wrapper skips the zero fill)
     # (one launch over the cfg * H heads; the token-major output is [cfg, S, H, D] in memory: svg_attn_layout_t with heads_per_batch = H)
     # (the LSE entry always runs the two-phase 16x16x32 body; the plain call picks it from S >= 160 QB on: only there is its o the same)
-    probe_lse = adaptive is not None or (quality is not None and _quality_lse_form(q, False) and S >= 160 * QB)
+    # (lse_auto: the auto LSE entry runs the plain call's body whatever S / QB is, at head_dim 64 too)
+    probe_lse = adaptive is not None or (quality is not None and (_varblock_lse_auto_form(q) if lse_auto
+                                                                  else _quality_lse_form(q, False) and S >= 160 * QB))
+    auto = {"body": "auto"} if lse_auto and probe_lse else {}
     token_major = TOKEN_MAJOR_IO and (_head_shard is None or _dist.token_shards_active())
     if centroid_tail:
-        out, lse_p = _sparse_plus_centroid_tail(q, k, v, dyn_map, q_sizes, k_sizes, qidx, kidx, tail_k, num_k_centroids, token_major)
+        out, lse_p = _sparse_plus_centroid_tail(q, k, v, dyn_map, q_sizes, k_sizes, qidx, kidx, tail_k, num_k_centroids, token_major,
+                                                **({"lse_auto": True} if lse_auto else {}))
     else:
         out = _native.varblock_attention(q, k, v, dyn_map.view(cfg * H, QB, KB).contiguous(),
                                          q_sizes.view(cfg * H, QB).contiguous(), k_sizes.view(cfg * H, KB).contiguous(),
                                          q_row_idx=qidx.contiguous(), kv_row_idx=kidx.contiguous(), fp8=f8, token_major_out=token_major,
-                                         rows_covered=True, return_lse=probe_lse)
+                                         rows_covered=True, return_lse=probe_lse, **auto)
         out, lse_p = out if probe_lse else (out, None)
     plan = lse_d = None
     if adaptive is not None:   # the rows of this call, drawn once: the quality probe below measures on them as well
@@ -1273,7 +1304,8 @@ def svg2_core_logic(proc, query, key, value, timestep, layer_idx, prompt_length,
                                 proc.top_p_kmeans, proc.min_kc_ratio, proc.kmeans_iter_init, proc.kmeans_iter_step,
                                 prompt_length=prompt_length if isinstance(prompt_length, tuple) else int(prompt_length),
                                 logging_file=proc.logging_file, timestep=timestep, quality=quality, adaptive=adaptive, top_p_store=proc.top_p_store,
-                                **({"kmeans_e4m3": True} if e4m3 else {}), **({"centroid_tail": True} if proc.centroid_tail else {}))
+                                **({"kmeans_e4m3": True} if e4m3 else {}), **({"centroid_tail": True} if proc.centroid_tail else {}),
+                                **({"lse_auto": True} if getattr(proc, "varblock_lse_auto", False) else {}))
     return out.reshape(shape)
 
 

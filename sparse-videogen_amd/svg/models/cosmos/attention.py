@@ -137,3 +137,5 @@ class Cosmos_SAPAttn_Processor(_CosmosPlumbing, WanAttn_SAPAttn_Processor):
 
     kmeans_e4m3 = False   # (its own switch, as on the Wan and HunyuanVideo SAP processors)
     centroid_tail = False   # (likewise)
+    # (likewise; Cosmos needs it for all three options: 400 q clusters at S = 56 320 stay below the 256-row body's threshold)
+    varblock_lse_auto = False

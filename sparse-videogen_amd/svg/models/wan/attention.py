@@ -306,6 +306,9 @@ class WanAttn_SAPAttn_Processor(WanAttn_SVGAttn_Processor2_0):
     # each (mean key, mean value, weighted with the cluster's size) and that state is merged with the sparse call's.  Refused under
     # svg.distributed and together with adaptive_top_p.  False: nothing changes.
     centroid_tail = False
+    # auto LSE form (include/svg_attn_varblock_lse_auto.h): True -> where the layer-call asks for the row log-sum-exp (quality_log's kept mass,
+    # adaptive_top_p, centroid_tail) it comes from the body the plain call runs, at any sequence length per q cluster.  False: nothing changes.
+    varblock_lse_auto = False
 
     logging_file = None
     prescale_q = False   # k-means and the block map work on the plain q
