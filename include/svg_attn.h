@@ -809,6 +809,8 @@ int svg_debug_wg_trace(uint64_t* out, int32_t n_workgroups);
 #include "svg_attn_band_lse_d64.h"
 /* ... and variable-block attention with the row log-sum-exp and with fp32 rows from the body variant -1 picks, likewise */
 #include "svg_attn_varblock_lse_auto.h"
+/* ... and flash-kmeans by direction: the cosine and dot-product assignment, update and Lloyd loop, likewise */
+#include "svg_attn_kmeans_metric.h"
 /* ... and the per-head band launch below and its device switch as resident workgroups on the work queue, with the order on the host, likewise */
 #include "svg_attn_band_per_head_queue.h"
 /* ... and SVG1's per-head band width: band attention from a device vector of bands, its device switch and the controller step, likewise */

@@ -13,6 +13,7 @@
 #include <algorithm>
 
 #include "attn_f8.h"
+#include "kmeans_metric.h"
 
 extern "C" size_t svg_argsort_workspace_bytes(int32_t B, int32_t N, int32_t K);
 extern "C" int svg_argsort_labels(const int32_t* labels, int32_t* sorted_idx, int32_t* counts, int32_t B, int32_t N,
@@ -63,7 +64,9 @@ __global__ __launch_bounds__(256) void csq_kernel(const T* __restrict__ c, float
 static __device__ unsigned long long g_km_trace[8 * 8];   // diagnostics build: per wave of workgroup (7, 0): cycles in { init, mfma, epilogue, stage, barrier }, tiles
 #endif
 // ---- assignment: grid = (ceil(N / (NW*32)), B), block = NW*64 ----
-template <typename T, int D, int NW>
+// kBias = false is the assignment of the cosine and dot-product metrics (include/svg_attn_kmeans_metric.h): argmax_c <x, c>.  The
+// accumulators start at 0 (-inf behind K), so |c|^2 is neither computed, loaded nor staged: a stage is the centroid tile alone.
+template <typename T, int D, int NW, bool kBias = true>
 __global__ __launch_bounds__(NW * 64, 2) void kmeans_assign_kernel(const T* __restrict__ x, const T* __restrict__ cent,
                                                                     const float* __restrict__ xsq,
                                                                     const float* __restrict__ csq, int32_t* __restrict__ labels,
@@ -74,7 +77,7 @@ __global__ __launch_bounds__(NW * 64, 2) void kmeans_assign_kernel(const T* __re
     constexpr int NT = NW * 64;
     constexpr int KS = D / 16;
     constexpr int NCH = (kBN * L::kCPR) / NT;
-    constexpr int kStage = L::kKBytes + kBN * 4;  // centroid tile + its 64 squared norms
+    constexpr int kStage = L::kKBytes + (kBias ? kBN * 4 : 0);  // centroid tile + its 64 squared norms
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int b = blockIdx.y;
@@ -111,7 +114,7 @@ __global__ __launch_bounds__(NW * 64, 2) void kmeans_assign_kernel(const T* __re
             const int c = t * kBN + srow[i];
             creg[i] = *(const u32x4*)(cb + (size_t)(c < K ? c : 0) * D + scol[i] * 8);
         }
-        if (tid < kBN) {   // |c|^2, RAW: the multiply sits in write() — used here it makes hipcc wait (vmcnt(0)) for the loads it has just issued
+        if (kBias && tid < kBN) {   // |c|^2, RAW: the multiply sits in write() — used here it makes hipcc wait (vmcnt(0)) for the loads it has just issued
             const int c = t * kBN + tid;
             sreg = csqb[c < K ? c : 0];
             sreg_ok = c < K;
@@ -122,7 +125,7 @@ __global__ __launch_bounds__(NW * 64, 2) void kmeans_assign_kernel(const T* __re
 #pragma unroll
         for (int i = 0; i < NCH; ++i) *(u32x4*)(base + k_dst[i]) = creg[i];
         // -|c|^2 / 2 (the accumulator's start value, see below); centroids behind K can never win
-        if (tid < kBN) *(float*)(base + L::kKBytes + tid * 4) = sreg_ok ? -0.5f * sreg : -INFINITY;
+        if (kBias && tid < kBN) *(float*)(base + L::kKBytes + tid * 4) = sreg_ok ? -0.5f * sreg : -INFINITY;
     };
 
     issue(0);
@@ -155,14 +158,25 @@ __global__ __launch_bounds__(NW * 64, 2) void kmeans_assign_kernel(const T* __re
         const char* kbuf = smem + buf * kStage;
         const float* h_t = (const float*)(kbuf + L::kKBytes);
         f32x16 s[2];
+        if constexpr (kBias) {
 #pragma unroll
-        for (int bb = 0; bb < 2; ++bb)
+            for (int bb = 0; bb < 2; ++bb)
 #pragma unroll
-            for (int rq = 0; rq < 4; ++rq) {
-                const f32x4 h4 = *(const f32x4*)(h_t + 32 * bb + 8 * rq + 4 * g);
+                for (int rq = 0; rq < 4; ++rq) {
+                    const f32x4 h4 = *(const f32x4*)(h_t + 32 * bb + 8 * rq + 4 * g);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) s[bb][rq * 4 + j] = h4[j];
-            }
+                    for (int j = 0; j < 4; ++j) s[bb][rq * 4 + j] = h4[j];
+                }
+        } else {
+            // no bias: the scores start at 0.  Only the last tile can have centroids behind K, and the test is uniform over the workgroup:
+            // register r of block bb is the tile's centroid 32 bb + 8 (r >> 2) + (r & 3) + 4 g
+            const bool partial = K - t * kBN < kBN;
+            const int left = K - t * kBN - 4 * g;
+#pragma unroll
+            for (int bb = 0; bb < 2; ++bb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) s[bb][r] = (partial && 32 * bb + 8 * (r >> 2) + (r & 3) >= left) ? -INFINITY : 0.f;
+        }
         float tb;
         int ti;
         KM_TICK(0)
@@ -359,15 +373,17 @@ __global__ __launch_bounds__(256) void kmeans_update_kernel(const T* __restrict_
 
 // the two halves of an iteration (the reference's euclid_assign_triton / triton_centroid_update_sorted_euclid, svg/kmeans_utils.py:562-627,
 // 375-421) as host functions of their own: svg_kmeans_iter runs one after the other, svg_kmeans_assign / svg_kmeans_update expose them
-template <typename T, int D>
+// (kBias = false: the metrics' assignment — no csq_kernel launch, `ws` is not touched)
+template <typename T, int D, bool kBias = true>
 static int run_kmeans_assign(const void* x, const float* xsq, const void* c_in, int32_t* labels, int B, int N, int K, void* ws,
                              hipStream_t st, long long x_bs) {
     constexpr int NW = 8;
     float* csq = (float*)ws;
-    hipLaunchKernelGGL((csq_kernel<T>), dim3(std::min<long long>(2048, ((long long)B * K + 15) / 16)), dim3(256), 0, st,
-                       (const T*)c_in, csq, (long long)B * K, D);
-    constexpr int lds = 2 * (LdsLayout<D>::kKBytes + kBN * 4);
-    auto kern = kmeans_assign_kernel<T, D, NW>;
+    if constexpr (kBias)
+        hipLaunchKernelGGL((csq_kernel<T>), dim3(std::min<long long>(2048, ((long long)B * K + 15) / 16)), dim3(256), 0, st,
+                           (const T*)c_in, csq, (long long)B * K, D);
+    constexpr int lds = 2 * (LdsLayout<D>::kKBytes + (kBias ? kBN * 4 : 0));
+    auto kern = kmeans_assign_kernel<T, D, NW, kBias>;
     hipLaunchKernelGGL(kern, dim3((N + NW * 32 - 1) / (NW * 32), B), dim3(NW * 64), lds, st, (const T*)x, (const T*)c_in, xsq,
                        csq, labels, N, K, x_bs);
     return launch_status();
@@ -748,11 +764,16 @@ extern "C" size_t svg_kmeans_workspace_bytes(int32_t B, int32_t N, int32_t K, in
     return csq_bytes + svg_argsort_workspace_bytes(B, N, K);
 }
 
+// the sort scratch inside that workspace, behind the csq block (run_kmeans_update)
+static void* kmeans_sort_ws(void* ws, int B, int K) { return (char*)ws + ((size_t)B * K * sizeof(float) + 255) / 256 * 256; }
+
 // one Lloyd iteration on x whose batches are x_bs elements apart (rows contiguous inside a batch): svg_kmeans_iter (x_bs = N * D) and the
-// iterations of svg_kmeans_loop[_strided]
+// iterations of svg_kmeans_loop[_strided].  metric (include/svg_attn_kmeans_metric.h): SVG_KMEANS_EUCLID is the path below; cosine / dot
+// assign without the bias (no csq_kernel launch) and update with kmeans_update_sphere_kernel (csrc/kmeans_metric.hip) on the same workspace
 static int kmeans_iter_impl(const void* x, long long x_bs, const float* xsq, const void* centroids_in, void* centroids_out,
                             int32_t* labels, int32_t* counts, int32_t* sorted_idx, float* shift, int32_t B, int32_t N,
-                            int32_t K, int32_t D, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
+                            int32_t K, int32_t D, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream,
+                            int metric = SVG_KMEANS_EUCLID) {
     // (xsq may be NULL: the argmax form of the assignment does not use |x|^2 — see kmeans_assign_kernel; the parameter stays in the
     //  signature because the reference's distance form carries it, svg/kmeans_utils.py:704)
     if (!x || !centroids_in || !centroids_out || !labels || !counts || !sorted_idx || !shift || !workspace)
@@ -761,6 +782,14 @@ static int kmeans_iter_impl(const void* x, long long x_bs, const float* xsq, con
     if (K > 8192) return SVG_ERR_UNSUPPORTED;
     if (workspace_bytes < svg_kmeans_workspace_bytes(B, N, K, D)) return SVG_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
+    if (metric != SVG_KMEANS_EUCLID) {
+        const int rc = dispatch_td(dtype, D, [&](auto t, auto d) {
+            return run_kmeans_assign<decltype(t), decltype(d)::value, false>(x, nullptr, centroids_in, labels, B, N, K, workspace, st, x_bs);
+        });
+        if (rc != SVG_OK) return rc;
+        return run_kmeans_update_metric(x, x_bs, centroids_in, centroids_out, labels, counts, sorted_idx, shift, B, N, K, D, dtype, metric,
+                                        kmeans_sort_ws(workspace, B, K), st);
+    }
     if (dtype == SVG_DTYPE_BF16) {
         if (D == 128)
             return run_kmeans_iter<__bf16, 128>(x, xsq, centroids_in, centroids_out, labels, counts, sorted_idx, shift, B, N,
@@ -866,11 +895,13 @@ static KmeansLoopScratch kmeans_loop_scratch(void* workspace, int B, int N, int 
 
 // iteration `it` into the scratch: it == 0 clears the state words and reads c_init, writing c_work_a; odd iterations write c_work_b
 static int kmeans_loop_iterate(const KmeansLoopScratch& s, const void* x, long long x_bs, const float* xsq, const void* c_init, void* c_work_a,
-                               void* c_work_b, int it, int B, int N, int K, int D, int dtype, int G, void* stream) {
+                               void* c_work_b, int it, int B, int N, int K, int D, int dtype, int G, void* stream,
+                               int metric = SVG_KMEANS_EUCLID) {
     if (it == 0 && hipMemsetAsync(s.state, 0, (size_t)4 * G * sizeof(int32_t), (hipStream_t)stream) != hipSuccess) return SVG_ERR_LAUNCH;
     const void* cur = it == 0 ? c_init : ((it & 1) ? c_work_a : c_work_b);
     void* out = (it & 1) ? c_work_b : c_work_a;
-    return kmeans_iter_impl(x, x_bs, xsq, cur, out, s.t_labels, s.t_counts, s.t_sorted, s.t_shift, B, N, K, D, dtype, s.it_ws, s.it_bytes, stream);
+    return kmeans_iter_impl(x, x_bs, xsq, cur, out, s.t_labels, s.t_counts, s.t_sorted, s.t_shift, B, N, K, D, dtype, s.it_ws, s.it_bytes, stream,
+                            metric);
 }
 
 // the commit of iteration `it`; maxima == NULL: the group maxima are reduced from the scratch shift inside the kernel
@@ -909,19 +940,29 @@ static int kmeans_loop_finish(const KmeansLoopScratch& s, const void* c_init, co
 static int kmeans_loop_impl(const void* x, long long x_bs, const float* xsq, const void* c_init, void* c_work_a, void* c_work_b, int32_t* labels,
                             int32_t* counts, int32_t* sorted_idx, void* centroids_out, int32_t* n_iters, int32_t B, int32_t N,
                             int32_t K, int32_t D, int32_t dtype, int32_t group, int32_t max_iters, float tol, void* workspace,
-                            size_t workspace_bytes, void* stream) {
+                            size_t workspace_bytes, void* stream, int metric = SVG_KMEANS_EUCLID) {
     if (!x || !c_init || !c_work_a || !c_work_b || !labels || !counts || !sorted_idx || !centroids_out || !n_iters || !workspace)
         return SVG_ERR_BAD_ARG;   // (xsq may be NULL, see svg_kmeans_iter)
     if (B <= 0 || N <= 0 || K <= 0 || max_iters <= 0 || group <= 0 || B % group != 0) return SVG_ERR_BAD_ARG;
     if (K > 8192 || (D != 64 && D != 128) || (dtype != SVG_DTYPE_BF16 && dtype != SVG_DTYPE_F16)) return SVG_ERR_UNSUPPORTED;
-    if (workspace_bytes < svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, group)) return SVG_ERR_WORKSPACE;
+    const size_t loop_bytes = svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, group);
+    if (workspace_bytes < (metric == SVG_KMEANS_EUCLID ? loop_bytes : svg_kmeans_loop_metric_workspace_bytes(B, N, K, D, group)))
+        return SVG_ERR_WORKSPACE;
     if (c_init == c_work_a || c_init == c_work_b || c_work_a == c_work_b || centroids_out == c_work_a || centroids_out == c_work_b)
         return SVG_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int G = B / group;
     const KmeansLoopScratch s = kmeans_loop_scratch(workspace, B, N, K, D, G, false);
+    if (metric == SVG_KMEANS_COSINE) {
+        // the unit rows of c_init, behind the blocks of the Euclidean loop: from here on they ARE the initial centroids (selector 0), so a
+        // group that converges at once returns them, and c_init is never written
+        void* c_unit = (char*)workspace + (loop_bytes + 255) / 256 * 256;
+        if (const int rc = run_kmeans_unit_rows(c_init, c_unit, (long long)B * K, D, dtype, st); rc != SVG_OK) return rc;
+        c_init = c_unit;
+    }
     for (int it = 0; it < max_iters; ++it) {
-        if (const int rc = kmeans_loop_iterate(s, x, x_bs, xsq, c_init, c_work_a, c_work_b, it, B, N, K, D, dtype, G, stream); rc != SVG_OK) return rc;
+        if (const int rc = kmeans_loop_iterate(s, x, x_bs, xsq, c_init, c_work_a, c_work_b, it, B, N, K, D, dtype, G, stream, metric); rc != SVG_OK)
+            return rc;
         kmeans_loop_commit(s, nullptr, labels, counts, sorted_idx, it, tol, B, N, K, group, st);
     }
     return kmeans_loop_finish(s, c_init, c_work_a, c_work_b, centroids_out, n_iters, B, K, D, dtype, group, st);
@@ -1135,4 +1176,56 @@ extern "C" int svg_kmeans_loop_e4m3(const void* x, int64_t x_batch_stride, const
         }
     }
     return kmeans_loop_finish(s, c_init, c_work_a, c_work_b, centroids_out, n_iters, B, K, D, dtype, group, st);
+}
+
+// ---- the cosine and dot-product metrics (include/svg_attn_kmeans_metric.h): the bias-free assignment above, the update of
+// csrc/kmeans_metric.hip, and kmeans_loop_impl with a metric.  The checks stand in the order the header documents. ----
+static bool kmeans_metric_ok(int32_t metric) { return metric == SVG_KMEANS_COSINE || metric == SVG_KMEANS_DOT; }
+static bool kmeans_metric_covers(int32_t K, int32_t D, int32_t dtype) {
+    return K <= 8192 && (D == 64 || D == 128) && (dtype == SVG_DTYPE_BF16 || dtype == SVG_DTYPE_F16);
+}
+
+extern "C" int svg_kmeans_assign_metric(const void* x, const void* centroids, int32_t* labels, int32_t B, int32_t N, int32_t K, int32_t D,
+                                        int32_t dtype, int32_t metric, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!x || !centroids || !labels || !workspace || B <= 0 || N <= 0 || K <= 0 || !kmeans_metric_ok(metric)) return SVG_ERR_BAD_ARG;
+    if (!kmeans_metric_covers(K, D, dtype)) return SVG_ERR_UNSUPPORTED;
+    if (workspace_bytes < svg_kmeans_workspace_bytes(B, N, K, D)) return SVG_ERR_WORKSPACE;
+    return dispatch_td(dtype, D, [&](auto t, auto d) {
+        constexpr int DD = decltype(d)::value;
+        return run_kmeans_assign<decltype(t), DD, false>(x, nullptr, centroids, labels, B, N, K, workspace, (hipStream_t)stream, (long long)N * DD);
+    });
+}
+
+extern "C" int svg_kmeans_update_metric(const void* x, const int32_t* labels, const void* centroids_in, void* centroids_out, int32_t* counts,
+                                        int32_t* sorted_idx, float* shift, int32_t B, int32_t N, int32_t K, int32_t D, int32_t dtype,
+                                        int32_t metric, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!x || !labels || !centroids_in || !centroids_out || !counts || !sorted_idx || !shift || !workspace) return SVG_ERR_BAD_ARG;
+    if (B <= 0 || N <= 0 || K <= 0 || !kmeans_metric_ok(metric)) return SVG_ERR_BAD_ARG;
+    if (!kmeans_metric_covers(K, D, dtype)) return SVG_ERR_UNSUPPORTED;
+    if (workspace_bytes < svg_kmeans_workspace_bytes(B, N, K, D)) return SVG_ERR_WORKSPACE;
+    return run_kmeans_update_metric(x, (long long)N * D, centroids_in, centroids_out, labels, counts, sorted_idx, shift, B, N, K, D, dtype, metric,
+                                    kmeans_sort_ws(workspace, B, K), (hipStream_t)stream);
+}
+
+// the blocks of svg_kmeans_loop_grouped_workspace_bytes in front, then the unit rows of c_init (cosine; the dot metric leaves them unused)
+extern "C" size_t svg_kmeans_loop_metric_workspace_bytes(int32_t B, int32_t N, int32_t K, int32_t D, int32_t group) {
+    const size_t loop = svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, group);
+    if (loop == 0 || K > 8192 || (D != 64 && D != 128)) return 0;
+    return (loop + 255) / 256 * 256 + ((size_t)B * K * D * 2 + 255) / 256 * 256;
+}
+
+extern "C" int svg_kmeans_loop_metric(const void* x, int64_t x_batch_stride, const void* c_init, void* c_work_a, void* c_work_b, int32_t* labels,
+                                      int32_t* counts, int32_t* sorted_idx, void* centroids_out, int32_t* n_iters, int32_t B, int32_t N,
+                                      int32_t K, int32_t D, int32_t dtype, int32_t metric, int32_t group, int32_t max_iters, float tol,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    if (!x || !c_init || !c_work_a || !c_work_b || !labels || !counts || !sorted_idx || !centroids_out || !n_iters || !workspace)
+        return SVG_ERR_BAD_ARG;
+    if (B <= 0 || N <= 0 || K <= 0 || max_iters <= 0 || group <= 0 || B % group != 0 || !kmeans_metric_ok(metric)) return SVG_ERR_BAD_ARG;
+    if (!kmeans_metric_covers(K, D, dtype)) return SVG_ERR_UNSUPPORTED;
+    if (workspace_bytes < svg_kmeans_loop_metric_workspace_bytes(B, N, K, D, group)) return SVG_ERR_WORKSPACE;
+    if (c_init == c_work_a || c_init == c_work_b || c_work_a == c_work_b || centroids_out == c_work_a || centroids_out == c_work_b)
+        return SVG_ERR_BAD_ARG;
+    if (const int rc = check_strided(x, x_batch_stride, N, D); rc != SVG_OK) return rc;
+    return kmeans_loop_impl(x, (long long)x_batch_stride, nullptr, c_init, c_work_a, c_work_b, labels, counts, sorted_idx, centroids_out, n_iters,
+                            B, N, K, D, dtype, group, max_iters, tol, workspace, workspace_bytes, stream, metric);
 }

@@ -415,6 +415,20 @@ KMEANS_E4M3_SIGNATURES = {
 }
 
 
+# include/svg_attn_kmeans_metric.h: the assignment, the update and the Lloyd loop of the cosine and dot-product metrics, in a table of its
+# own for the same reason (tests/test_kmeans_metric_cpu.py; the allocating wrappers kmeans_assign_metric, kmeans_update_metric,
+# kmeans_loop_metric: svg/_kmeans_metric.py, reachable as attributes of this module — __getattr__ at its end; named ..._ENTRIES for the reason
+# ADAPTIVE_BAND_ENTRIES gives; what the wrappers pass is checked on the GPU, in tests/test_gpu_kmeans_metric.py)
+KMEANS_COSINE, KMEANS_DOT = 1, 2   # SVG_KMEANS_COSINE / SVG_KMEANS_DOT
+KMEANS_METRIC_ENTRIES = {
+    "svg_kmeans_assign_metric": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _SZ, _VP]),
+    "svg_kmeans_update_metric": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _SZ, _VP]),
+    "svg_kmeans_loop_metric_workspace_bytes": (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    "svg_kmeans_loop_metric": (C.c_int, [_VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F32,
+                                         _VP, _SZ, _VP]),
+}
+
+
 # include/svg_attn_centroid_tail.h: the cluster means and the attention state over the key clusters a block map leaves out, in a table of its
 # own for the same reason (tests/test_centroid_tail_cpu.py; the allocating wrappers cluster_means, centroid_tail_attention:
 # svg/_centroid_tail.py, reachable as attributes of this module — __getattr__ at its end; named ..._ENTRIES for the reason ADAPTIVE_BAND_ENTRIES
@@ -466,7 +480,7 @@ def load(strict: bool = True) -> Optional[C.CDLL]:
                                    **PROFILE_SHARD_SIGNATURES, **SAMPLE_ROWS_SIGNATURES, **SHARD_EXCHANGE_SIGNATURES,
                                    **ADAPTIVE_TOP_P_SIGNATURES, **ADAPTIVE_BAND_ENTRIES, **ADAPTIVE_BAND_QUEUE_ENTRIES,
                                    **KMEANS_STEPPED_SIGNATURES, **KMEANS_E4M3_SIGNATURES, **CENTROID_TAIL_ENTRIES, **BAND_LSE_D64_ENTRIES,
-                                   **VARBLOCK_LSE_AUTO_ENTRIES}.items():
+                                   **VARBLOCK_LSE_AUTO_ENTRIES, **KMEANS_METRIC_ENTRIES}.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -2575,6 +2589,10 @@ def __getattr__(name: str):
         from . import _kmeans_e4m3
 
         return getattr(_kmeans_e4m3, name)
+    if name in ("kmeans_assign_metric", "kmeans_update_metric", "kmeans_loop_metric"):   # (include/svg_attn_kmeans_metric.h, likewise)
+        from . import _kmeans_metric
+
+        return getattr(_kmeans_metric, name)
     if name in ("cluster_means", "centroid_tail_attention"):   # (include/svg_attn_centroid_tail.h, likewise: svg/_centroid_tail.py)
         from . import _centroid_tail
 
