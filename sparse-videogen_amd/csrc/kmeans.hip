@@ -374,47 +374,33 @@ __global__ __launch_bounds__(256) void kmeans_update_kernel(const T* __restrict_
 // the two halves of an iteration (the reference's euclid_assign_triton / triton_centroid_update_sorted_euclid, svg/kmeans_utils.py:562-627,
 // 375-421) as host functions of their own: svg_kmeans_iter runs one after the other, svg_kmeans_assign / svg_kmeans_update expose them
 // (kBias = false: the metrics' assignment — no csq_kernel launch, `ws` is not touched)
-template <typename T, int D, bool kBias = true>
-static int run_kmeans_assign(const void* x, const float* xsq, const void* c_in, int32_t* labels, int B, int N, int K, void* ws,
-                             hipStream_t st, long long x_bs) {
+template <typename T, int D, bool kBias>
+static int run_kmeans_assign(const KmeansCall& a, const KmeansStep& s) {
     constexpr int NW = 8;
-    float* csq = (float*)ws;
     if constexpr (kBias)
-        hipLaunchKernelGGL((csq_kernel<T>), dim3(std::min<long long>(2048, ((long long)B * K + 15) / 16)), dim3(256), 0, st,
-                           (const T*)c_in, csq, (long long)B * K, D);
+        hipLaunchKernelGGL((csq_kernel<T>), dim3(std::min<long long>(2048, ((long long)a.B * a.K + 15) / 16)), dim3(256), 0, a.st,
+                           (const T*)s.c_in, s.ws.csq, (long long)a.B * a.K, D);
     constexpr int lds = 2 * (LdsLayout<D>::kKBytes + (kBias ? kBN * 4 : 0));
     auto kern = kmeans_assign_kernel<T, D, NW, kBias>;
-    hipLaunchKernelGGL(kern, dim3((N + NW * 32 - 1) / (NW * 32), B), dim3(NW * 64), lds, st, (const T*)x, (const T*)c_in, xsq,
-                       csq, labels, N, K, x_bs);
+    hipLaunchKernelGGL(kern, dim3((a.N + NW * 32 - 1) / (NW * 32), a.B), dim3(NW * 64), lds, a.st, (const T*)a.x, (const T*)s.c_in, a.xsq,
+                       s.ws.csq, s.labels, a.N, a.K, a.x_bs);
     return launch_status();
 }
 
 template <typename T, int D>
-static int run_kmeans_update(const void* x, const void* c_in, void* c_out, const int32_t* labels, int32_t* counts, int32_t* sorted_idx,
-                             float* shift, int B, int N, int K, void* ws, hipStream_t st, long long x_bs) {
-    const size_t csq_bytes = ((size_t)B * K * sizeof(float) + 255) / 256 * 256;
-    char* sort_ws = (char*)ws + csq_bytes;
-    const size_t sort_bytes = svg_argsort_workspace_bytes(B, N, K);
-    int rc = svg_argsort_labels(labels, sorted_idx, counts, B, N, K, sort_ws, sort_bytes, (void*)st);
+static int run_kmeans_update(const KmeansCall& a, const KmeansStep& s) {
+    const int B = a.B, N = a.N, K = a.K;
+    int rc = svg_argsort_labels(s.labels, s.sorted_idx, s.counts, B, N, K, s.ws.sort, s.ws.sort_bytes, (void*)a.st);
     if (rc) return rc;
-    (void)hipMemsetAsync(shift, 0, (size_t)B * sizeof(float), st);
+    (void)hipMemsetAsync(s.shift, 0, (size_t)B * sizeof(float), a.st);
     const int nchunks = (N + 1023) / 1024;
     // workgroups per batch: three per CU over the whole launch.  Measured at Wan 720p (40 heads, K = 300 and 1000 on two streams, the 2-iteration
     // stage): 6 per head 3.49 ms, 8 3.27, 12 3.14, 16 3.05, 20 3.02, 26 3.13, 32 3.17, 52 3.22, 100 3.36, one per cluster 3.37; the kernel of
     // round 4 (one workgroup per cluster, no prefetch) 3.39 (profiles/r05zw_kmeans_update_groups.txt).
     const int groups = std::max(1, std::min(K, (3 * kNumCU + B - 1) / B));
-    hipLaunchKernelGGL((kmeans_update_kernel<T, D>), dim3(groups, B), dim3(256), 0, st, (const T*)x, (const T*)c_in, (T*)c_out,
-                       sorted_idx, (const int32_t*)sort_ws, counts, shift, N, K, (size_t)nchunks * K, x_bs);
+    hipLaunchKernelGGL((kmeans_update_kernel<T, D>), dim3(groups, B), dim3(256), 0, a.st, (const T*)a.x, (const T*)s.c_in, (T*)s.c_out,
+                       s.sorted_idx, (const int32_t*)s.ws.sort, s.counts, s.shift, N, K, (size_t)nchunks * K, a.x_bs);
     return launch_status();
-}
-
-template <typename T, int D>
-static int run_kmeans_iter(const void* x, const float* xsq, const void* c_in, void* c_out, int32_t* labels, int32_t* counts,
-                           int32_t* sorted_idx, float* shift, int B, int N, int K, void* ws, size_t ws_bytes,
-                           hipStream_t st, long long x_bs) {
-    (void)ws_bytes;
-    if (const int rc = run_kmeans_assign<T, D>(x, xsq, c_in, labels, B, N, K, ws, st, x_bs); rc != SVG_OK) return rc;
-    return run_kmeans_update<T, D>(x, c_in, c_out, labels, counts, sorted_idx, shift, B, N, K, ws, st, x_bs);
 }
 
 // ---- the Lloyd loop on the device (svg_kmeans_loop[_grouped]): commit of one iteration's result under the reference's stopping rule ----
@@ -732,6 +718,17 @@ __global__ __launch_bounds__(512, 2) void kmeans_assign_e4m3_kernel(const T* __r
     if (g == 0 && n < N) labels[(size_t)b * N + n] = best_idx;
 }
 
+template <typename T>
+static int run_kmeans_assign_e4m3(const KmeansCall& a, const KmeansStep& s) {
+    const long long rows = (long long)a.B * a.K;
+    hipLaunchKernelGGL((kmeans_e4m3_centroids_kernel<T>), dim3((unsigned)std::min<long long>(2048, (rows + 15) / 16)), dim3(256), 0, a.st,
+                       (const T*)s.c_in, s.mu, s.e4m3.c8, s.e4m3.cscale, s.e4m3.csq, a.K, rows);
+    constexpr int lds = 2 * (kBN * 128 + kBN * 8);
+    hipLaunchKernelGGL((kmeans_assign_e4m3_kernel<T>), dim3((a.N + 255) / 256, a.B), dim3(512), lds, a.st, (const T*)a.x, s.mu, s.e4m3.c8,
+                       s.e4m3.cscale, s.e4m3.csq, s.labels, a.N, a.K, a.x_bs);
+    return launch_status();
+}
+
 }  // namespace svg
 
 using namespace svg;
@@ -742,99 +739,258 @@ extern "C" int svg_debug_kmeans_trace(uint64_t* out64) {
 }
 #endif
 
-extern "C" int svg_kmeans_xsq(const void* x, float* xsq, int32_t B, int32_t N, int32_t D, int32_t dtype, void* stream) {
-    if (!x || !xsq || B <= 0 || N <= 0) return SVG_ERR_BAD_ARG;
-    if (D != 64 && D != 128) return SVG_ERR_UNSUPPORTED;
-    const long long rows = (long long)B * N;
-    const int rpb = 256 / (D / 8);
-    dim3 grid((unsigned)std::min<long long>(4096, (rows + rpb - 1) / rpb));
-    if (dtype == SVG_DTYPE_BF16)
-        hipLaunchKernelGGL((xsq_kernel<__bf16>), grid, dim3(256), 0, (hipStream_t)stream, (const __bf16*)x, xsq, rows, D);
-    else if (dtype == SVG_DTYPE_F16)
-        hipLaunchKernelGGL((xsq_kernel<_Float16>), grid, dim3(256), 0, (hipStream_t)stream, (const _Float16*)x, xsq, rows, D);
+// ---- the call record (csrc/kmeans_metric.h) as the entries fill it ----
+static KmeansCall kmeans_shape(int32_t B, int32_t N, int32_t K, int32_t D, int32_t group) {
+    KmeansCall a;
+    a.B = B, a.N = N, a.K = K, a.D = D, a.group = group, a.x_bs = (long long)N * D;
+    return a;
+}
+static KmeansCall kmeans_call(KmeansCall a, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    a.dtype = dtype, a.workspace = workspace, a.workspace_bytes = workspace_bytes, a.st = (hipStream_t)stream;
+    return a;
+}
+
+// ---- the checks, each written once.  An entry lists the ones it applies in the order its header documents; the first that fails is the
+// return code (all of them are host arithmetic on the record: none touches memory or launches) ----
+static int first_failure(std::initializer_list<int> rcs) {
+    for (const int rc : rcs)
+        if (rc != SVG_OK) return rc;
+    return SVG_OK;
+}
+static int need(bool ok, int rc) { return ok ? SVG_OK : rc; }
+static int check_pointers(std::initializer_list<const void*> required) {
+    for (const void* p : required)
+        if (!p) return SVG_ERR_BAD_ARG;
+    return SVG_OK;
+}
+static int check_positive(std::initializer_list<int32_t> sizes) {
+    for (const int32_t n : sizes)
+        if (n <= 0) return SVG_ERR_BAD_ARG;
+    return SVG_OK;
+}
+static int check_group(const KmeansCall& a) { return need(a.group > 0 && a.B % a.group == 0, SVG_ERR_BAD_ARG); }
+static int check_metric(const KmeansCall& a) { return need(a.metric == SVG_KMEANS_COSINE || a.metric == SVG_KMEANS_DOT, SVG_ERR_BAD_ARG); }
+// the covered (K, D, dtype): the e4m3 entries are head_dim 128 only
+static int check_K(int32_t K) { return K > 8192 ? SVG_ERR_UNSUPPORTED : SVG_OK; }
+static int check_D(int32_t D) { return D != 64 && D != 128 ? SVG_ERR_UNSUPPORTED : SVG_OK; }
+static int check_dtype(int32_t dtype) { return need(dtype == SVG_DTYPE_BF16 || dtype == SVG_DTYPE_F16, SVG_ERR_UNSUPPORTED); }
+static int check_covers(const KmeansCall& a) { return first_failure({check_K(a.K), check_D(a.D), check_dtype(a.dtype)}); }
+static int check_e4m3_covers(const KmeansCall& a) { return first_failure({check_K(a.K), need(a.D == 128, SVG_ERR_UNSUPPORTED), check_dtype(a.dtype)}); }
+static int check_workspace(const KmeansCall& a, size_t bytes) { return need(a.workspace_bytes >= bytes, SVG_ERR_WORKSPACE); }
+// the three centroid buffers are distinct and the result is neither work buffer (an entry without centroids_out leaves it NULL; the work
+// buffers are required pointers)
+static int check_alias(const KmeansCall& a) {
+    return need(a.c_init != a.c_work_a && a.c_init != a.c_work_b && a.c_work_a != a.c_work_b && a.centroids_out != a.c_work_a &&
+                    a.centroids_out != a.c_work_b, SVG_ERR_BAD_ARG);
+}
+static int check_strided(const KmeansCall& a) {
+    if (a.x_bs < (long long)a.N * a.D) return SVG_ERR_BAD_ARG;
+    if (a.x_bs % 8 != 0 || ((size_t)a.x & 15) != 0) return SVG_ERR_UNSUPPORTED;
+    return SVG_OK;
+}
+static int check_loop_pointers(const KmeansCall& a) {   // (xsq may be NULL, see KmeansCall)
+    return check_pointers({a.x, a.c_init, a.c_work_a, a.c_work_b, a.labels, a.counts, a.sorted_idx, a.centroids_out, a.n_iters, a.workspace});
+}
+static int check_loop_sizes(const KmeansCall& a) { return first_failure({check_positive({a.B, a.N, a.K, a.max_iters}), check_group(a)}); }
+
+// ---- the workspace layouts: one function per kind yields the byte count (from a record without a workspace: the *_workspace_bytes
+// entries) and the block pointers.  Every block starts on a multiple of 256 bytes. ----
+struct Blocks {   // hands out consecutive 256-byte-rounded blocks from `base` (integer arithmetic: base may be 0)
+    uintptr_t base;
+    size_t off = 0;
+    void* take(size_t n) {
+        void* p = (void*)(base + off);
+        off += up256(n);
+        return p;
+    }
+};
+// bytes = 0 where a size is not positive
+static KmeansIterWs kmeans_iter_ws(const KmeansCall& a, void* base) {
+    KmeansIterWs w{};
+    if (a.B <= 0 || a.N <= 0 || a.K <= 0) return w;
+    Blocks b{(uintptr_t)base};
+    w.csq = (float*)b.take((size_t)a.B * a.K * sizeof(float));
+    w.sort = b.take(0);
+    w.sort_bytes = svg_argsort_workspace_bytes(a.B, a.N, a.K);
+    w.bytes = b.off + w.sort_bytes;
+    return w;
+}
+static KmeansE4m3Ws kmeans_e4m3_ws(const KmeansCall& a, void* base) {
+    Blocks b{(uintptr_t)base};
+    const size_t row = (size_t)a.B * a.K * 4;
+    KmeansE4m3Ws w;
+    w.c8 = (uint8_t*)b.take((size_t)a.B * a.K * 128);
+    w.cscale = (int32_t*)b.take(row);
+    w.csq = (float*)b.take(row);
+    w.bytes = b.off;
+    return w;
+}
+// scratch of one loop: the per-iteration scratch of svg_kmeans_iter, one iteration's labels / sorted indices / counts / shift and 4 state
+// words per stopping group (one 256-byte block for up to 16 groups: the ungrouped loop's size).
+//   kLoopStateLast : the layout of svg_kmeans_loop_grouped_workspace_bytes
+//   kLoopStateFirst: the stepped entries' (the same blocks, the state words in front: svg_kmeans_stepped_finish has no N and finds them there)
+//   kLoopE4m3      : kLoopStateLast (fp8_iters = 0 IS svg_kmeans_loop_grouped_strided on it), then mu and the scratch of one e4m3 assignment
+//   kLoopMetric    : kLoopStateLast, then the unit rows of c_init (cosine; the dot metric leaves them unused)
+enum KmeansLoopKind { kLoopStateLast, kLoopStateFirst, kLoopE4m3, kLoopMetric };
+struct KmeansLoopWs {
+    KmeansIterWs it;
+    int32_t *t_labels, *t_sorted, *t_counts;
+    float* t_shift;
+    int32_t* state;
+    float* mu;
+    KmeansE4m3Ws e4m3;
+    void* c_unit;
+    size_t bytes;   // 0: no loop of these sizes and this group
+};
+static KmeansLoopWs kmeans_loop_ws(const KmeansCall& a, KmeansLoopKind kind) {
+    KmeansLoopWs w{};
+    const size_t it_bytes = kmeans_iter_ws(a, nullptr).bytes;
+    if (it_bytes == 0 || a.group <= 0 || a.B % a.group != 0) return w;
+    Blocks b{(uintptr_t)a.workspace};
+    const size_t rows = (size_t)a.B * a.N * 4, state = (size_t)(a.B / a.group) * 4 * sizeof(int32_t);
+    if (kind == kLoopStateFirst) w.state = (int32_t*)b.take(state);
+    w.it = kmeans_iter_ws(a, b.take(it_bytes));
+    w.t_labels = (int32_t*)b.take(rows);
+    w.t_sorted = (int32_t*)b.take(rows);
+    w.t_counts = (int32_t*)b.take((size_t)a.B * a.K * 4);
+    w.t_shift = (float*)b.take((size_t)a.B * 4);
+    if (kind != kLoopStateFirst) w.state = (int32_t*)b.take(state);
+    if (kind == kLoopE4m3) {
+        w.mu = (float*)b.take((size_t)a.B * 128 * sizeof(float));
+        w.e4m3 = kmeans_e4m3_ws(a, b.take(0));
+        b.off += w.e4m3.bytes;
+    }
+    if (kind == kLoopMetric) w.c_unit = b.take((size_t)a.B * a.K * a.D * 2);
+    w.bytes = b.off;
+    return w;
+}
+
+// ---- one iteration: an assignment (Euclidean with the |c|^2 bias, bias-free for the metrics, or e4m3) followed by an update
+// (kmeans_update_kernel, or kmeans_update_sphere_kernel of csrc/kmeans_metric.hip for the metrics) ----
+static int kmeans_assign(const KmeansCall& a, const KmeansStep& s) {
+    return dispatch_td(a.dtype, a.D, [&](auto t, auto d) {
+        using T = decltype(t);
+        constexpr int D = decltype(d)::value;
+        return a.metric == SVG_KMEANS_EUCLID ? run_kmeans_assign<T, D, true>(a, s) : run_kmeans_assign<T, D, false>(a, s);
+    });
+}
+static int kmeans_assign_e4m3(const KmeansCall& a, const KmeansStep& s) {
+    return dispatch_td(a.dtype, a.D, [&](auto t, auto) { return run_kmeans_assign_e4m3<decltype(t)>(a, s); });
+}
+static int kmeans_update(const KmeansCall& a, const KmeansStep& s) {
+    if (a.metric != SVG_KMEANS_EUCLID) return run_kmeans_update_metric(a, s);
+    return dispatch_td(a.dtype, a.D, [&](auto t, auto d) { return run_kmeans_update<decltype(t), decltype(d)::value>(a, s); });
+}
+// iteration `it` of the record: the first a.fp8_iters iterations assign with the e4m3 scores
+static int kmeans_iteration(const KmeansCall& a, const KmeansStep& s, int it) {
+    if (const int rc = it < a.fp8_iters ? kmeans_assign_e4m3(a, s) : kmeans_assign(a, s); rc != SVG_OK) return rc;
+    return kmeans_update(a, s);
+}
+static int kmeans_centre(const KmeansCall& a, float* mu) {   // mu = the channel mean of a.c_init
+    return dispatch_td(a.dtype, a.D, [&](auto t, auto) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((kmeans_centre_kernel<T>), dim3(a.B), dim3(256), 0, a.st, (const T*)a.c_init, mu, a.K);
+        return launch_status();
+    });
+}
+
+// ---- the host steps of the Lloyd loop, shared by svg_kmeans_loop* (all of them in one call) and svg_kmeans_stepped_* (one per call) ----
+// iteration `it` into the scratch: it == 0 clears the state words and reads c_init, writing c_work_a; odd iterations write c_work_b
+static int kmeans_loop_iterate(const KmeansCall& a, const KmeansLoopWs& w, int it) {
+    const int G = a.B / a.group;
+    if (it == 0 && hipMemsetAsync(w.state, 0, (size_t)4 * G * sizeof(int32_t), a.st) != hipSuccess) return SVG_ERR_LAUNCH;
+    const void* cur = it == 0 ? a.c_init : ((it & 1) ? a.c_work_a : a.c_work_b);
+    void* out = (it & 1) ? a.c_work_b : a.c_work_a;
+    return kmeans_iteration(a, KmeansStep{cur, out, w.t_labels, w.t_counts, w.t_sorted, w.t_shift, w.it, w.mu, w.e4m3}, it);
+}
+
+// the commit of iteration `it`; a.maxima == NULL: the group maxima are reduced from the scratch shift inside the kernel
+static void kmeans_loop_commit(const KmeansCall& a, const KmeansLoopWs& w, int it, float tol) {
+    const int group = a.group, G = a.B / group;
+    const int sel_cur = it == 0 ? 0 : ((it & 1) ? 1 : 2), sel_out = (it & 1) ? 2 : 1;   // 0 initial, 1 / 2 the two work buffers
+    const long long gn = (long long)group * a.N, gk = (long long)group * a.K;
+    // (G = 1: the grid of the ungrouped loop; more groups share about as many workgroups, a stopped group's return at once)
+    const dim3 grid((unsigned)std::min<long long>((2048 + G - 1) / G, (gn + 255) / 256), (unsigned)G);
+    if (a.maxima)
+        hipLaunchKernelGGL(kmeans_commit_kernel<true>, grid, dim3(256), 0, a.st, w.t_labels, w.t_sorted, w.t_counts, a.labels, a.sorted_idx,
+                           a.counts, a.maxima, w.state, gn, gk, group, tol, it, sel_cur, sel_out);
     else
-        return SVG_ERR_UNSUPPORTED;
+        hipLaunchKernelGGL(kmeans_commit_kernel<false>, grid, dim3(256), 0, a.st, w.t_labels, w.t_sorted, w.t_counts, a.labels, a.sorted_idx,
+                           a.counts, w.t_shift, w.state, gn, gk, group, tol, it, sel_cur, sel_out);
+}
+
+// every group's centroids from the buffer its selector names, and the n_iters words
+static int kmeans_loop_finish(const KmeansCall& a, const KmeansLoopWs& w) {
+    const int G = a.B / a.group;
+    const long long gn8 = (long long)a.group * a.K * a.D / 8;
+    const dim3 g2((unsigned)std::min<long long>((1024 + G - 1) / G, (gn8 + 255) / 256), (unsigned)G);
+    const int rc = dispatch_td(a.dtype, a.D, [&](auto t, auto) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((kmeans_select_kernel<T>), g2, dim3(256), 0, a.st, (const T*)a.c_init, (const T*)a.c_work_a, (const T*)a.c_work_b,
+                           (T*)a.centroids_out, w.state + 3 * G, gn8);
+        return SVG_OK;
+    });
+    if (rc != SVG_OK) return rc;
+    if (hipMemcpyAsync(a.n_iters, w.state + 2 * G, (size_t)G * sizeof(int32_t), hipMemcpyDeviceToDevice, a.st) != hipSuccess) return SVG_ERR_LAUNCH;
     return launch_status();
 }
 
+// The loop driver of svg_kmeans_loop*, svg_kmeans_loop_e4m3 and svg_kmeans_loop_metric on a checked record: state clear -> iterate ->
+// commit -> ... -> finish.
+static int kmeans_loop_run(KmeansCall a, const KmeansLoopWs& w) {
+    if (a.metric == SVG_KMEANS_COSINE) {
+        // the unit rows of c_init, behind the blocks of the Euclidean loop: from here on they ARE the initial centroids (selector 0), so a
+        // group that converges at once returns them, and c_init is never written
+        if (const int rc = run_kmeans_unit_rows(a, w.c_unit); rc != SVG_OK) return rc;
+        a.c_init = w.c_unit;
+    }
+    if (a.fp8_iters > 0)   // (fp8_iters = 0: svg_kmeans_loop_grouped_strided, call for call)
+        if (const int rc = kmeans_centre(a, w.mu); rc != SVG_OK) return rc;
+    for (int it = 0; it < a.max_iters; ++it) {
+        if (const int rc = kmeans_loop_iterate(a, w, it); rc != SVG_OK) return rc;
+        // an e4m3 iteration never stops a group: a shift is >= 0 or NaN, so nothing is below a tol of -1
+        kmeans_loop_commit(a, w, it, it < a.fp8_iters ? -1.f : a.tol);
+    }
+    return kmeans_loop_finish(a, w);
+}
+
+// ---- the entries ----
+extern "C" int svg_kmeans_xsq(const void* x, float* xsq, int32_t B, int32_t N, int32_t D, int32_t dtype, void* stream) {
+    if (const int rc = first_failure({check_pointers({x, xsq}), check_positive({B, N}), check_D(D)}); rc != SVG_OK) return rc;
+    const long long rows = (long long)B * N;
+    const int rpb = 256 / (D / 8);
+    dim3 grid((unsigned)std::min<long long>(4096, (rows + rpb - 1) / rpb));
+    return dispatch_td(dtype, D, [&](auto t, auto) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((xsq_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)x, xsq, rows, D);
+        return launch_status();
+    });
+}
+
 extern "C" size_t svg_kmeans_workspace_bytes(int32_t B, int32_t N, int32_t K, int32_t D) {
-    (void)D;
-    if (B <= 0 || N <= 0 || K <= 0) return 0;
-    const size_t csq_bytes = ((size_t)B * K * sizeof(float) + 255) / 256 * 256;
-    return csq_bytes + svg_argsort_workspace_bytes(B, N, K);
+    return kmeans_iter_ws(kmeans_shape(B, N, K, D, B), nullptr).bytes;
 }
 
-// the sort scratch inside that workspace, behind the csq block (run_kmeans_update)
-static void* kmeans_sort_ws(void* ws, int B, int K) { return (char*)ws + ((size_t)B * K * sizeof(float) + 255) / 256 * 256; }
-
-// one Lloyd iteration on x whose batches are x_bs elements apart (rows contiguous inside a batch): svg_kmeans_iter (x_bs = N * D) and the
-// iterations of svg_kmeans_loop[_strided].  metric (include/svg_attn_kmeans_metric.h): SVG_KMEANS_EUCLID is the path below; cosine / dot
-// assign without the bias (no csq_kernel launch) and update with kmeans_update_sphere_kernel (csrc/kmeans_metric.hip) on the same workspace
-static int kmeans_iter_impl(const void* x, long long x_bs, const float* xsq, const void* centroids_in, void* centroids_out,
-                            int32_t* labels, int32_t* counts, int32_t* sorted_idx, float* shift, int32_t B, int32_t N,
-                            int32_t K, int32_t D, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream,
-                            int metric = SVG_KMEANS_EUCLID) {
-    // (xsq may be NULL: the argmax form of the assignment does not use |x|^2 — see kmeans_assign_kernel; the parameter stays in the
-    //  signature because the reference's distance form carries it, svg/kmeans_utils.py:704)
-    if (!x || !centroids_in || !centroids_out || !labels || !counts || !sorted_idx || !shift || !workspace)
-        return SVG_ERR_BAD_ARG;
-    if (B <= 0 || N <= 0 || K <= 0) return SVG_ERR_BAD_ARG;
-    if (K > 8192) return SVG_ERR_UNSUPPORTED;
-    if (workspace_bytes < svg_kmeans_workspace_bytes(B, N, K, D)) return SVG_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (metric != SVG_KMEANS_EUCLID) {
-        const int rc = dispatch_td(dtype, D, [&](auto t, auto d) {
-            return run_kmeans_assign<decltype(t), decltype(d)::value, false>(x, nullptr, centroids_in, labels, B, N, K, workspace, st, x_bs);
-        });
-        if (rc != SVG_OK) return rc;
-        return run_kmeans_update_metric(x, x_bs, centroids_in, centroids_out, labels, counts, sorted_idx, shift, B, N, K, D, dtype, metric,
-                                        kmeans_sort_ws(workspace, B, K), st);
-    }
-    if (dtype == SVG_DTYPE_BF16) {
-        if (D == 128)
-            return run_kmeans_iter<__bf16, 128>(x, xsq, centroids_in, centroids_out, labels, counts, sorted_idx, shift, B, N,
-                                                K, workspace, workspace_bytes, st, x_bs);
-        if (D == 64)
-            return run_kmeans_iter<__bf16, 64>(x, xsq, centroids_in, centroids_out, labels, counts, sorted_idx, shift, B, N, K,
-                                               workspace, workspace_bytes, st, x_bs);
-    } else if (dtype == SVG_DTYPE_F16) {
-        if (D == 128)
-            return run_kmeans_iter<_Float16, 128>(x, xsq, centroids_in, centroids_out, labels, counts, sorted_idx, shift, B, N,
-                                                  K, workspace, workspace_bytes, st, x_bs);
-        if (D == 64)
-            return run_kmeans_iter<_Float16, 64>(x, xsq, centroids_in, centroids_out, labels, counts, sorted_idx, shift, B, N,
-                                                 K, workspace, workspace_bytes, st, x_bs);
-    }
-    return SVG_ERR_UNSUPPORTED;
-}
-
+// One Lloyd iteration.  The workspace is sized before the (dtype, head_dim) pair is looked at: an uncovered pair is the dispatch's answer.
 extern "C" int svg_kmeans_iter(const void* x, const float* xsq, const void* centroids_in, void* centroids_out,
                                int32_t* labels, int32_t* counts, int32_t* sorted_idx, float* shift, int32_t B, int32_t N,
                                int32_t K, int32_t D, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
-    return kmeans_iter_impl(x, (long long)N * D, xsq, centroids_in, centroids_out, labels, counts, sorted_idx, shift, B, N, K, D, dtype,
-                            workspace, workspace_bytes, stream);
+    KmeansCall a = kmeans_call(kmeans_shape(B, N, K, D, B), dtype, workspace, workspace_bytes, stream);
+    a.x = x, a.xsq = xsq;
+    const KmeansIterWs ws = kmeans_iter_ws(a, workspace);
+    const int rc = first_failure({check_pointers({x, centroids_in, centroids_out, labels, counts, sorted_idx, shift, workspace}),
+                                  check_positive({B, N, K}), check_K(K), check_workspace(a, ws.bytes)});
+    return rc != SVG_OK ? rc : kmeans_iteration(a, KmeansStep{centroids_in, centroids_out, labels, counts, sorted_idx, shift, ws}, 0);
 }
-
-#define SVG_KM_DISPATCH(CALL)                                                                  \
-    if (dtype == SVG_DTYPE_BF16) {                                                             \
-        if (D == 128) return CALL(__bf16, 128);                                                \
-        if (D == 64) return CALL(__bf16, 64);                                                  \
-    } else if (dtype == SVG_DTYPE_F16) {                                                       \
-        if (D == 128) return CALL(_Float16, 128);                                              \
-        if (D == 64) return CALL(_Float16, 64);                                                \
-    }                                                                                          \
-    return SVG_ERR_UNSUPPORTED;
 
 // labels[b, n] = argmin_k |x[b, n] - centroids[b, k]|^2 (lowest index on ties): the assignment half of svg_kmeans_iter on its own.
 extern "C" int svg_kmeans_assign(const void* x, const void* centroids, int32_t* labels, int32_t B, int32_t N, int32_t K, int32_t D,
                                  int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !centroids || !labels || !workspace || B <= 0 || N <= 0 || K <= 0) return SVG_ERR_BAD_ARG;
-    if (K > 8192) return SVG_ERR_UNSUPPORTED;
-    if (workspace_bytes < svg_kmeans_workspace_bytes(B, N, K, D)) return SVG_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-#define SVG_KM_ASSIGN(T, DD) run_kmeans_assign<T, DD>(x, nullptr, centroids, labels, B, N, K, workspace, st, (long long)N * DD)
-    SVG_KM_DISPATCH(SVG_KM_ASSIGN)
-#undef SVG_KM_ASSIGN
+    KmeansCall a = kmeans_call(kmeans_shape(B, N, K, D, B), dtype, workspace, workspace_bytes, stream);
+    a.x = x;
+    const KmeansIterWs ws = kmeans_iter_ws(a, workspace);
+    const int rc = first_failure({check_pointers({x, centroids, labels, workspace}), check_positive({B, N, K}), check_K(K), check_workspace(a, ws.bytes)});
+    return rc != SVG_OK ? rc : kmeans_assign(a, KmeansStep{centroids, nullptr, labels, nullptr, nullptr, nullptr, ws});
 }
 
 // The update half on GIVEN labels: stable sort of the labels, per-cluster fp32 means in a fixed order, empty clusters keep
@@ -842,390 +998,202 @@ extern "C" int svg_kmeans_assign(const void* x, const void* centroids, int32_t* 
 extern "C" int svg_kmeans_update(const void* x, const int32_t* labels, const void* centroids_in, void* centroids_out, int32_t* counts,
                                  int32_t* sorted_idx, float* shift, int32_t B, int32_t N, int32_t K, int32_t D, int32_t dtype,
                                  void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !labels || !centroids_in || !centroids_out || !counts || !sorted_idx || !shift || !workspace) return SVG_ERR_BAD_ARG;
-    if (B <= 0 || N <= 0 || K <= 0) return SVG_ERR_BAD_ARG;
-    if (K > 8192) return SVG_ERR_UNSUPPORTED;
-    if (workspace_bytes < svg_kmeans_workspace_bytes(B, N, K, D)) return SVG_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-#define SVG_KM_UPDATE(T, DD) run_kmeans_update<T, DD>(x, centroids_in, centroids_out, labels, counts, sorted_idx, shift, B, N, K, workspace, st, (long long)N * DD)
-    SVG_KM_DISPATCH(SVG_KM_UPDATE)
-#undef SVG_KM_UPDATE
+    KmeansCall a = kmeans_call(kmeans_shape(B, N, K, D, B), dtype, workspace, workspace_bytes, stream);
+    a.x = x;
+    const KmeansIterWs ws = kmeans_iter_ws(a, workspace);
+    const int rc = first_failure({check_pointers({x, labels, centroids_in, centroids_out, counts, sorted_idx, shift, workspace}),
+                                  check_positive({B, N, K}), check_K(K), check_workspace(a, ws.bytes)});
+    // (the step's labels are only read by an update)
+    return rc != SVG_OK ? rc : kmeans_update(a, KmeansStep{centroids_in, centroids_out, const_cast<int32_t*>(labels), counts, sorted_idx, shift, ws});
 }
-#undef SVG_KM_DISPATCH
 
-// scratch of svg_kmeans_loop_grouped: per-iteration scratch of svg_kmeans_iter + scratch labels / sorted indices / counts / shift of one
-// iteration + 4 state words per stopping group (one 256-byte block for up to 16 groups: the ungrouped loop's size)
 extern "C" size_t svg_kmeans_loop_grouped_workspace_bytes(int32_t B, int32_t N, int32_t K, int32_t D, int32_t group) {
-    const size_t it = svg_kmeans_workspace_bytes(B, N, K, D);
-    if (it == 0 || group <= 0 || B % group != 0) return 0;
-    const size_t a = ((size_t)B * N * 4 + 255) / 256 * 256, c = ((size_t)B * K * 4 + 255) / 256 * 256, sh = ((size_t)B * 4 + 255) / 256 * 256;
-    const size_t st = ((size_t)(B / group) * 4 * sizeof(int32_t) + 255) / 256 * 256;
-    return (it + 255) / 256 * 256 + 2 * a + c + sh + st;
+    return kmeans_loop_ws(kmeans_shape(B, N, K, D, group), kLoopStateLast).bytes;
 }
 
 extern "C" size_t svg_kmeans_loop_workspace_bytes(int32_t B, int32_t N, int32_t K, int32_t D) {
     return B > 0 ? svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, B) : 0;
 }
 
-// ---- the host steps of the Lloyd loop, shared by svg_kmeans_loop* (all of them in one call) and svg_kmeans_stepped_* (one per call) ----
-// scratch of one loop: the per-iteration scratch of svg_kmeans_iter, one iteration's labels / sorted indices / counts / shift, the state words
-struct KmeansLoopScratch {
-    void* it_ws;
-    size_t it_bytes;
-    int32_t *t_labels, *t_sorted, *t_counts;
-    float* t_shift;
-    int32_t* state;
-};
-static size_t kmeans_state_bytes(int G) { return ((size_t)G * 4 * sizeof(int32_t) + 255) / 256 * 256; }
-// state_first = false: the layout of svg_kmeans_loop_grouped_workspace_bytes (state words last); true: the stepped entries' (state words
-// first: svg_kmeans_stepped_finish has no N and finds them there)
-static KmeansLoopScratch kmeans_loop_scratch(void* workspace, int B, int N, int K, int D, int G, bool state_first) {
-    KmeansLoopScratch s;
-    s.it_bytes = (svg_kmeans_workspace_bytes(B, N, K, D) + 255) / 256 * 256;
-    const size_t a = ((size_t)B * N * 4 + 255) / 256 * 256, c = ((size_t)B * K * 4 + 255) / 256 * 256, sh = ((size_t)B * 4 + 255) / 256 * 256;
-    char* w = (char*)workspace + (state_first ? kmeans_state_bytes(G) : 0);
-    s.it_ws = w;
-    s.t_labels = (int32_t*)(w + s.it_bytes);
-    s.t_sorted = (int32_t*)(w + s.it_bytes + a);
-    s.t_counts = (int32_t*)(w + s.it_bytes + 2 * a);
-    s.t_shift = (float*)(w + s.it_bytes + 2 * a + c);
-    s.state = state_first ? (int32_t*)workspace : (int32_t*)(w + s.it_bytes + 2 * a + c + sh);
-    return s;
-}
-
-// iteration `it` into the scratch: it == 0 clears the state words and reads c_init, writing c_work_a; odd iterations write c_work_b
-static int kmeans_loop_iterate(const KmeansLoopScratch& s, const void* x, long long x_bs, const float* xsq, const void* c_init, void* c_work_a,
-                               void* c_work_b, int it, int B, int N, int K, int D, int dtype, int G, void* stream,
-                               int metric = SVG_KMEANS_EUCLID) {
-    if (it == 0 && hipMemsetAsync(s.state, 0, (size_t)4 * G * sizeof(int32_t), (hipStream_t)stream) != hipSuccess) return SVG_ERR_LAUNCH;
-    const void* cur = it == 0 ? c_init : ((it & 1) ? c_work_a : c_work_b);
-    void* out = (it & 1) ? c_work_b : c_work_a;
-    return kmeans_iter_impl(x, x_bs, xsq, cur, out, s.t_labels, s.t_counts, s.t_sorted, s.t_shift, B, N, K, D, dtype, s.it_ws, s.it_bytes, stream,
-                            metric);
-}
-
-// the commit of iteration `it`; maxima == NULL: the group maxima are reduced from the scratch shift inside the kernel
-static void kmeans_loop_commit(const KmeansLoopScratch& s, const float* maxima, int32_t* labels, int32_t* counts, int32_t* sorted_idx, int it,
-                               float tol, int B, int N, int K, int group, hipStream_t st) {
-    const int G = B / group;
-    const int sel_cur = it == 0 ? 0 : ((it & 1) ? 1 : 2), sel_out = (it & 1) ? 2 : 1;   // 0 initial, 1 / 2 the two work buffers
-    const long long gn = (long long)group * N, gk = (long long)group * K;
-    // (G = 1: the grid of the ungrouped loop; more groups share about as many workgroups, a stopped group's return at once)
-    const dim3 grid((unsigned)std::min<long long>((2048 + G - 1) / G, (gn + 255) / 256), (unsigned)G);
-    if (maxima)
-        hipLaunchKernelGGL(kmeans_commit_kernel<true>, grid, dim3(256), 0, st, s.t_labels, s.t_sorted, s.t_counts, labels, sorted_idx, counts,
-                           maxima, s.state, gn, gk, group, tol, it, sel_cur, sel_out);
-    else
-        hipLaunchKernelGGL(kmeans_commit_kernel<false>, grid, dim3(256), 0, st, s.t_labels, s.t_sorted, s.t_counts, labels, sorted_idx, counts,
-                           s.t_shift, s.state, gn, gk, group, tol, it, sel_cur, sel_out);
-}
-
-// every group's centroids from the buffer its selector names, and the n_iters words
-static int kmeans_loop_finish(const KmeansLoopScratch& s, const void* c_init, const void* c_work_a, const void* c_work_b, void* centroids_out,
-                              int32_t* n_iters, int B, int K, int D, int dtype, int group, hipStream_t st) {
-    const int G = B / group;
-    const long long gn8 = (long long)group * K * D / 8;
-    const dim3 g2((unsigned)std::min<long long>((1024 + G - 1) / G, (gn8 + 255) / 256), (unsigned)G);
-    if (dtype == SVG_DTYPE_BF16)
-        hipLaunchKernelGGL((kmeans_select_kernel<__bf16>), g2, dim3(256), 0, st, (const __bf16*)c_init, (const __bf16*)c_work_a,
-                           (const __bf16*)c_work_b, (__bf16*)centroids_out, s.state + 3 * G, gn8);
-    else
-        hipLaunchKernelGGL((kmeans_select_kernel<_Float16>), g2, dim3(256), 0, st, (const _Float16*)c_init, (const _Float16*)c_work_a,
-                           (const _Float16*)c_work_b, (_Float16*)centroids_out, s.state + 3 * G, gn8);
-    if (hipMemcpyAsync(n_iters, s.state + 2 * G, (size_t)G * sizeof(int32_t), hipMemcpyDeviceToDevice, st) != hipSuccess) return SVG_ERR_LAUNCH;
-    return launch_status();
-}
-
-// svg_kmeans_loop (x_bs = N * D, group = B), svg_kmeans_loop_strided (group = B) and their grouped forms
-static int kmeans_loop_impl(const void* x, long long x_bs, const float* xsq, const void* c_init, void* c_work_a, void* c_work_b, int32_t* labels,
-                            int32_t* counts, int32_t* sorted_idx, void* centroids_out, int32_t* n_iters, int32_t B, int32_t N,
-                            int32_t K, int32_t D, int32_t dtype, int32_t group, int32_t max_iters, float tol, void* workspace,
-                            size_t workspace_bytes, void* stream, int metric = SVG_KMEANS_EUCLID) {
-    if (!x || !c_init || !c_work_a || !c_work_b || !labels || !counts || !sorted_idx || !centroids_out || !n_iters || !workspace)
-        return SVG_ERR_BAD_ARG;   // (xsq may be NULL, see svg_kmeans_iter)
-    if (B <= 0 || N <= 0 || K <= 0 || max_iters <= 0 || group <= 0 || B % group != 0) return SVG_ERR_BAD_ARG;
-    if (K > 8192 || (D != 64 && D != 128) || (dtype != SVG_DTYPE_BF16 && dtype != SVG_DTYPE_F16)) return SVG_ERR_UNSUPPORTED;
-    const size_t loop_bytes = svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, group);
-    if (workspace_bytes < (metric == SVG_KMEANS_EUCLID ? loop_bytes : svg_kmeans_loop_metric_workspace_bytes(B, N, K, D, group)))
-        return SVG_ERR_WORKSPACE;
-    if (c_init == c_work_a || c_init == c_work_b || c_work_a == c_work_b || centroids_out == c_work_a || centroids_out == c_work_b)
-        return SVG_ERR_BAD_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    const int G = B / group;
-    const KmeansLoopScratch s = kmeans_loop_scratch(workspace, B, N, K, D, G, false);
-    if (metric == SVG_KMEANS_COSINE) {
-        // the unit rows of c_init, behind the blocks of the Euclidean loop: from here on they ARE the initial centroids (selector 0), so a
-        // group that converges at once returns them, and c_init is never written
-        void* c_unit = (char*)workspace + (loop_bytes + 255) / 256 * 256;
-        if (const int rc = run_kmeans_unit_rows(c_init, c_unit, (long long)B * K, D, dtype, st); rc != SVG_OK) return rc;
-        c_init = c_unit;
-    }
-    for (int it = 0; it < max_iters; ++it) {
-        if (const int rc = kmeans_loop_iterate(s, x, x_bs, xsq, c_init, c_work_a, c_work_b, it, B, N, K, D, dtype, G, stream, metric); rc != SVG_OK)
-            return rc;
-        kmeans_loop_commit(s, nullptr, labels, counts, sorted_idx, it, tol, B, N, K, group, st);
-    }
-    return kmeans_loop_finish(s, c_init, c_work_a, c_work_b, centroids_out, n_iters, B, K, D, dtype, group, st);
-}
-
-static int check_strided(const void* x, int64_t x_batch_stride, int32_t N, int32_t D) {
-    if (x_batch_stride < (int64_t)N * D) return SVG_ERR_BAD_ARG;
-    if (x_batch_stride % 8 != 0 || ((size_t)x & 15) != 0) return SVG_ERR_UNSUPPORTED;
-    return SVG_OK;
-}
-
-extern "C" int svg_kmeans_loop(const void* x, const float* xsq, const void* c_init, void* c_work_a, void* c_work_b, int32_t* labels,
-                               int32_t* counts, int32_t* sorted_idx, void* centroids_out, int32_t* n_iters, int32_t B, int32_t N,
-                               int32_t K, int32_t D, int32_t dtype, int32_t max_iters, float tol, void* workspace,
-                               size_t workspace_bytes, void* stream) {
-    return kmeans_loop_impl(x, (long long)N * D, xsq, c_init, c_work_a, c_work_b, labels, counts, sorted_idx, centroids_out, n_iters, B, N, K, D,
-                            dtype, B, max_iters, tol, workspace, workspace_bytes, stream);
-}
-
-extern "C" int svg_kmeans_loop_strided(const void* x, int64_t x_batch_stride, const void* c_init, void* c_work_a, void* c_work_b,
-                                       int32_t* labels, int32_t* counts, int32_t* sorted_idx, void* centroids_out, int32_t* n_iters,
-                                       int32_t B, int32_t N, int32_t K, int32_t D, int32_t dtype, int32_t max_iters, float tol,
-                                       void* workspace, size_t workspace_bytes, void* stream) {
-    if (const int rc = check_strided(x, x_batch_stride, N, D); rc != SVG_OK) return rc;
-    return kmeans_loop_impl(x, (long long)x_batch_stride, nullptr, c_init, c_work_a, c_work_b, labels, counts, sorted_idx, centroids_out, n_iters,
-                            B, N, K, D, dtype, B, max_iters, tol, workspace, workspace_bytes, stream);
+// the record of a loop entry: the part every loop entry takes (x_bs and xsq, metric, fp8_iters are the entry's)
+static KmeansCall kmeans_loop_call(KmeansCall a, const void* x, const void* const (&cents)[4], int32_t* const (&outs)[4]) {
+    a.x = x, a.c_init = cents[0], a.c_work_a = const_cast<void*>(cents[1]), a.c_work_b = const_cast<void*>(cents[2]);
+    a.centroids_out = const_cast<void*>(cents[3]);
+    a.labels = outs[0], a.counts = outs[1], a.sorted_idx = outs[2], a.n_iters = outs[3];
+    return a;
 }
 
 extern "C" int svg_kmeans_loop_grouped(const void* x, const float* xsq, const void* c_init, void* c_work_a, void* c_work_b, int32_t* labels,
                                        int32_t* counts, int32_t* sorted_idx, void* centroids_out, int32_t* n_iters, int32_t B, int32_t N,
                                        int32_t K, int32_t D, int32_t dtype, int32_t group, int32_t max_iters, float tol, void* workspace,
                                        size_t workspace_bytes, void* stream) {
-    return kmeans_loop_impl(x, (long long)N * D, xsq, c_init, c_work_a, c_work_b, labels, counts, sorted_idx, centroids_out, n_iters, B, N, K, D,
-                            dtype, group, max_iters, tol, workspace, workspace_bytes, stream);
+    KmeansCall a = kmeans_loop_call(kmeans_call(kmeans_shape(B, N, K, D, group), dtype, workspace, workspace_bytes, stream), x,
+                                    {c_init, c_work_a, c_work_b, centroids_out}, {labels, counts, sorted_idx, n_iters});
+    a.xsq = xsq, a.max_iters = max_iters, a.tol = tol;
+    const KmeansLoopWs w = kmeans_loop_ws(a, kLoopStateLast);
+    const int rc = first_failure({check_loop_pointers(a), check_loop_sizes(a), check_covers(a), check_workspace(a, w.bytes), check_alias(a)});
+    return rc != SVG_OK ? rc : kmeans_loop_run(a, w);
 }
 
 extern "C" int svg_kmeans_loop_grouped_strided(const void* x, int64_t x_batch_stride, const void* c_init, void* c_work_a, void* c_work_b,
                                                int32_t* labels, int32_t* counts, int32_t* sorted_idx, void* centroids_out, int32_t* n_iters,
                                                int32_t B, int32_t N, int32_t K, int32_t D, int32_t dtype, int32_t group, int32_t max_iters,
                                                float tol, void* workspace, size_t workspace_bytes, void* stream) {
-    if (const int rc = check_strided(x, x_batch_stride, N, D); rc != SVG_OK) return rc;
-    return kmeans_loop_impl(x, (long long)x_batch_stride, nullptr, c_init, c_work_a, c_work_b, labels, counts, sorted_idx, centroids_out, n_iters,
-                            B, N, K, D, dtype, group, max_iters, tol, workspace, workspace_bytes, stream);
+    KmeansCall a = kmeans_loop_call(kmeans_call(kmeans_shape(B, N, K, D, group), dtype, workspace, workspace_bytes, stream), x,
+                                    {c_init, c_work_a, c_work_b, centroids_out}, {labels, counts, sorted_idx, n_iters});
+    a.x_bs = (long long)x_batch_stride, a.max_iters = max_iters, a.tol = tol;
+    const KmeansLoopWs w = kmeans_loop_ws(a, kLoopStateLast);
+    const int rc = first_failure({check_strided(a), check_loop_pointers(a), check_loop_sizes(a), check_covers(a), check_workspace(a, w.bytes),
+                                  check_alias(a)});
+    return rc != SVG_OK ? rc : kmeans_loop_run(a, w);
+}
+
+// svg_kmeans_loop and svg_kmeans_loop_strided: one stopping group of all B batches
+extern "C" int svg_kmeans_loop(const void* x, const float* xsq, const void* c_init, void* c_work_a, void* c_work_b, int32_t* labels,
+                               int32_t* counts, int32_t* sorted_idx, void* centroids_out, int32_t* n_iters, int32_t B, int32_t N,
+                               int32_t K, int32_t D, int32_t dtype, int32_t max_iters, float tol, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    return svg_kmeans_loop_grouped(x, xsq, c_init, c_work_a, c_work_b, labels, counts, sorted_idx, centroids_out, n_iters, B, N, K, D, dtype, B,
+                                   max_iters, tol, workspace, workspace_bytes, stream);
+}
+
+extern "C" int svg_kmeans_loop_strided(const void* x, int64_t x_batch_stride, const void* c_init, void* c_work_a, void* c_work_b,
+                                       int32_t* labels, int32_t* counts, int32_t* sorted_idx, void* centroids_out, int32_t* n_iters,
+                                       int32_t B, int32_t N, int32_t K, int32_t D, int32_t dtype, int32_t max_iters, float tol,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    return svg_kmeans_loop_grouped_strided(x, x_batch_stride, c_init, c_work_a, c_work_b, labels, counts, sorted_idx, centroids_out, n_iters, B, N,
+                                           K, D, dtype, B, max_iters, tol, workspace, workspace_bytes, stream);
 }
 
 // ---- the Lloyd loop in steps (include/svg_attn_kmeans_stepped.h): the host steps above, one per call, with the group maxima handed out
 // by iterate and taken back by commit ----
 extern "C" size_t svg_kmeans_stepped_workspace_bytes(int32_t B, int32_t N, int32_t K, int32_t D, int32_t group) {
-    if (K > 8192 || (D != 64 && D != 128)) return 0;
-    return svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, group);   // (the same blocks, the state words in front)
+    if (first_failure({check_K(K), check_D(D)}) != SVG_OK) return 0;
+    return kmeans_loop_ws(kmeans_shape(B, N, K, D, group), kLoopStateFirst).bytes;
 }
 
 extern "C" int svg_kmeans_stepped_iterate(const void* x, int64_t x_batch_stride, const void* c_init, void* c_work_a, void* c_work_b, int32_t it,
                                           float* maxima, int32_t B, int32_t N, int32_t K, int32_t D, int32_t dtype, int32_t group,
                                           void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !c_init || !c_work_a || !c_work_b || !maxima || !workspace) return SVG_ERR_BAD_ARG;
-    if (B <= 0 || N <= 0 || K <= 0 || group <= 0 || B % group != 0 || it < 0) return SVG_ERR_BAD_ARG;
-    if (K > 8192 || (D != 64 && D != 128) || (dtype != SVG_DTYPE_BF16 && dtype != SVG_DTYPE_F16)) return SVG_ERR_UNSUPPORTED;
-    if (workspace_bytes < svg_kmeans_stepped_workspace_bytes(B, N, K, D, group)) return SVG_ERR_WORKSPACE;
-    if (c_init == c_work_a || c_init == c_work_b || c_work_a == c_work_b) return SVG_ERR_BAD_ARG;
-    if (const int rc = check_strided(x, x_batch_stride, N, D); rc != SVG_OK) return rc;
+    KmeansCall a = kmeans_call(kmeans_shape(B, N, K, D, group), dtype, workspace, workspace_bytes, stream);
+    a.x = x, a.x_bs = (long long)x_batch_stride, a.c_init = c_init, a.c_work_a = c_work_a, a.c_work_b = c_work_b;
+    const KmeansLoopWs w = kmeans_loop_ws(a, kLoopStateFirst);
+    const int rc = first_failure({check_pointers({x, c_init, c_work_a, c_work_b, maxima, workspace}), check_positive({B, N, K}), check_group(a),
+                                  need(it >= 0, SVG_ERR_BAD_ARG), check_covers(a), check_workspace(a, w.bytes), check_alias(a), check_strided(a)});
+    if (rc != SVG_OK) return rc;
+    if (const int rc2 = kmeans_loop_iterate(a, w, it); rc2 != SVG_OK) return rc2;
     const int G = B / group;
-    const KmeansLoopScratch s = kmeans_loop_scratch(workspace, B, N, K, D, G, true);
-    if (const int rc = kmeans_loop_iterate(s, x, (long long)x_batch_stride, nullptr, c_init, c_work_a, c_work_b, it, B, N, K, D, dtype, G, stream);
-        rc != SVG_OK)
-        return rc;
-    hipLaunchKernelGGL(kmeans_group_maxima_kernel, dim3((unsigned)std::min(256, (G + 3) / 4)), dim3(256), 0, (hipStream_t)stream, s.t_shift, maxima,
-                       G, (int)group);
+    hipLaunchKernelGGL(kmeans_group_maxima_kernel, dim3((unsigned)std::min(256, (G + 3) / 4)), dim3(256), 0, a.st, w.t_shift, maxima, G, (int)group);
     return launch_status();
 }
 
 extern "C" int svg_kmeans_stepped_commit(const float* maxima, int32_t* labels, int32_t* counts, int32_t* sorted_idx, int32_t it, float tol, int32_t B,
                                          int32_t N, int32_t K, int32_t group, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!maxima || !labels || !counts || !sorted_idx || !workspace) return SVG_ERR_BAD_ARG;
-    if (B <= 0 || N <= 0 || K <= 0 || group <= 0 || B % group != 0 || it < 0) return SVG_ERR_BAD_ARG;
-    if (K > 8192) return SVG_ERR_UNSUPPORTED;
-    // (no head_dim here: none of the blocks' sizes depends on it)
-    if (workspace_bytes < svg_kmeans_stepped_workspace_bytes(B, N, K, 128, group)) return SVG_ERR_WORKSPACE;
-    const KmeansLoopScratch s = kmeans_loop_scratch(workspace, B, N, K, 128, B / group, true);
-    kmeans_loop_commit(s, maxima, labels, counts, sorted_idx, it, tol, B, N, K, group, (hipStream_t)stream);
+    // (no head_dim here: none of the blocks' sizes depends on it — the record carries 128)
+    KmeansCall a = kmeans_call(kmeans_shape(B, N, K, 128, group), 0, workspace, workspace_bytes, stream);
+    a.maxima = maxima, a.labels = labels, a.counts = counts, a.sorted_idx = sorted_idx;
+    const KmeansLoopWs w = kmeans_loop_ws(a, kLoopStateFirst);
+    const int rc = first_failure({check_pointers({maxima, labels, counts, sorted_idx, workspace}), check_positive({B, N, K}), check_group(a),
+                                  need(it >= 0, SVG_ERR_BAD_ARG), check_K(K), check_workspace(a, w.bytes)});
+    if (rc != SVG_OK) return rc;
+    kmeans_loop_commit(a, w, it, tol);
     return launch_status();
 }
 
 extern "C" int svg_kmeans_stepped_finish(const void* c_init, const void* c_work_a, const void* c_work_b, void* centroids_out, int32_t* n_iters,
                                          int32_t B, int32_t K, int32_t D, int32_t dtype, int32_t group, void* workspace, size_t workspace_bytes,
                                          void* stream) {
-    if (!c_init || !c_work_a || !c_work_b || !centroids_out || !n_iters || !workspace) return SVG_ERR_BAD_ARG;
-    if (B <= 0 || K <= 0 || group <= 0 || B % group != 0) return SVG_ERR_BAD_ARG;
-    if (K > 8192 || (D != 64 && D != 128) || (dtype != SVG_DTYPE_BF16 && dtype != SVG_DTYPE_F16)) return SVG_ERR_UNSUPPORTED;
-    // (no N here: the smallest workspace an iterate of these B, K, D, group took — the state words finish reads lie in front of it)
-    if (workspace_bytes < svg_kmeans_stepped_workspace_bytes(B, 1, K, D, group)) return SVG_ERR_WORKSPACE;
-    if (c_init == c_work_a || c_init == c_work_b || c_work_a == c_work_b || centroids_out == c_work_a || centroids_out == c_work_b)
-        return SVG_ERR_BAD_ARG;
-    const KmeansLoopScratch s = kmeans_loop_scratch(workspace, B, 1, K, D, B / group, true);
-    return kmeans_loop_finish(s, c_init, c_work_a, c_work_b, centroids_out, n_iters, B, K, D, dtype, group, (hipStream_t)stream);
+    // (no N here: the record carries 1 — the smallest workspace an iterate of these B, K, D, group took; the state words finish reads lie
+    //  in front of it)
+    KmeansCall a = kmeans_call(kmeans_shape(B, 1, K, D, group), dtype, workspace, workspace_bytes, stream);
+    a.c_init = c_init, a.c_work_a = const_cast<void*>(c_work_a), a.c_work_b = const_cast<void*>(c_work_b);   // (read only here)
+    a.centroids_out = centroids_out, a.n_iters = n_iters;
+    const KmeansLoopWs w = kmeans_loop_ws(a, kLoopStateFirst);
+    const int rc = first_failure({check_pointers({c_init, c_work_a, c_work_b, centroids_out, n_iters, workspace}), check_positive({B, K}),
+                                  check_group(a), check_covers(a), check_workspace(a, w.bytes), check_alias(a)});
+    return rc != SVG_OK ? rc : kmeans_loop_finish(a, w);
 }
 
 // ---- the e4m3 assignment and the Lloyd loop that uses it for its first iterations (include/svg_attn_kmeans_e4m3.h) ----
-// scratch of one e4m3 assignment: the centroid image, its scale bytes (one int32 each) and csq'
-struct KmeansE4m3Scratch {
-    uint8_t* c8;
-    int32_t* cscale;
-    float* csq;
-};
-static size_t kmeans_e4m3_image_bytes(int B, int K) { return ((size_t)B * K * 128 + 255) / 256 * 256; }
-static size_t kmeans_e4m3_row_bytes(int B, int K) { return ((size_t)B * K * 4 + 255) / 256 * 256; }
-static size_t kmeans_e4m3_mu_bytes(int B) { return ((size_t)B * 128 * sizeof(float) + 255) / 256 * 256; }
-static KmeansE4m3Scratch kmeans_e4m3_scratch(void* w, int B, int K) {
-    KmeansE4m3Scratch s;
-    s.c8 = (uint8_t*)w;
-    s.cscale = (int32_t*)((char*)w + kmeans_e4m3_image_bytes(B, K));
-    s.csq = (float*)((char*)w + kmeans_e4m3_image_bytes(B, K) + kmeans_e4m3_row_bytes(B, K));
-    return s;
-}
-
-template <typename T>
-static int run_kmeans_assign_e4m3(const void* x, const float* mu, const void* c_in, int32_t* labels, int B, int N, int K,
-                                  const KmeansE4m3Scratch& s, hipStream_t st, long long x_bs) {
-    const long long rows = (long long)B * K;
-    hipLaunchKernelGGL((kmeans_e4m3_centroids_kernel<T>), dim3((unsigned)std::min<long long>(2048, (rows + 15) / 16)), dim3(256), 0, st,
-                       (const T*)c_in, mu, s.c8, s.cscale, s.csq, K, rows);
-    constexpr int lds = 2 * (kBN * 128 + kBN * 8);
-    hipLaunchKernelGGL((kmeans_assign_e4m3_kernel<T>), dim3((N + 255) / 256, B), dim3(512), lds, st, (const T*)x, mu, s.c8, s.cscale, s.csq,
-                       labels, N, K, x_bs);
-    return launch_status();
-}
-
-static bool kmeans_e4m3_covers(int32_t K, int32_t D, int32_t dtype) {
-    return K <= 8192 && D == 128 && (dtype == SVG_DTYPE_BF16 || dtype == SVG_DTYPE_F16);
-}
-
 extern "C" int svg_kmeans_centre(const void* centroids, float* mu, int32_t B, int32_t K, int32_t D, int32_t dtype, void* stream) {
-    if (!centroids || !mu || B <= 0 || K <= 0) return SVG_ERR_BAD_ARG;
-    if (!kmeans_e4m3_covers(K, D, dtype)) return SVG_ERR_UNSUPPORTED;
-    if (dtype == SVG_DTYPE_BF16)
-        hipLaunchKernelGGL((kmeans_centre_kernel<__bf16>), dim3(B), dim3(256), 0, (hipStream_t)stream, (const __bf16*)centroids, mu, K);
-    else
-        hipLaunchKernelGGL((kmeans_centre_kernel<_Float16>), dim3(B), dim3(256), 0, (hipStream_t)stream, (const _Float16*)centroids, mu, K);
-    return launch_status();
+    KmeansCall a = kmeans_call(kmeans_shape(B, 1, K, D, B), dtype, nullptr, 0, stream);
+    a.c_init = centroids;
+    const int rc = first_failure({check_pointers({centroids, mu}), check_positive({B, K}), check_e4m3_covers(a)});
+    return rc != SVG_OK ? rc : kmeans_centre(a, mu);
 }
 
 extern "C" size_t svg_kmeans_assign_e4m3_workspace_bytes(int32_t B, int32_t N, int32_t K, int32_t D) {
-    if (B <= 0 || N <= 0 || K <= 0 || K > 8192 || D != 128) return 0;
-    return kmeans_e4m3_image_bytes(B, K) + 2 * kmeans_e4m3_row_bytes(B, K);
+    if (check_positive({B, N, K}) != SVG_OK || check_K(K) != SVG_OK || D != 128) return 0;
+    return kmeans_e4m3_ws(kmeans_shape(B, N, K, D, B), nullptr).bytes;
 }
 
 extern "C" int svg_kmeans_assign_e4m3(const void* x, const void* centroids, const float* mu, int32_t* labels, int32_t B, int32_t N, int32_t K,
                                       int32_t D, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !centroids || !labels || !workspace || B <= 0 || N <= 0 || K <= 0) return SVG_ERR_BAD_ARG;   // (mu may be NULL: zeros)
-    if (!kmeans_e4m3_covers(K, D, dtype)) return SVG_ERR_UNSUPPORTED;
-    if (workspace_bytes < svg_kmeans_assign_e4m3_workspace_bytes(B, N, K, D)) return SVG_ERR_WORKSPACE;
-    if ((((size_t)x | (size_t)mu) & 15) != 0) return SVG_ERR_UNSUPPORTED;   // (16-byte loads of rows and of mu)
-    const KmeansE4m3Scratch s = kmeans_e4m3_scratch(workspace, B, K);
-    if (dtype == SVG_DTYPE_BF16)
-        return run_kmeans_assign_e4m3<__bf16>(x, mu, centroids, labels, B, N, K, s, (hipStream_t)stream, (long long)N * D);
-    return run_kmeans_assign_e4m3<_Float16>(x, mu, centroids, labels, B, N, K, s, (hipStream_t)stream, (long long)N * D);
+    KmeansCall a = kmeans_call(kmeans_shape(B, N, K, D, B), dtype, workspace, workspace_bytes, stream);
+    a.x = x;
+    KmeansStep s{};
+    s.c_in = centroids, s.labels = labels, s.mu = mu, s.e4m3 = kmeans_e4m3_ws(a, workspace);   // (mu may be NULL: zeros)
+    const int rc = first_failure({check_pointers({x, centroids, labels, workspace}), check_positive({B, N, K}), check_e4m3_covers(a),
+                                  check_workspace(a, s.e4m3.bytes),
+                                  need((((size_t)x | (size_t)mu) & 15) == 0, SVG_ERR_UNSUPPORTED)});   // (16-byte loads of rows and of mu)
+    return rc != SVG_OK ? rc : kmeans_assign_e4m3(a, s);
 }
 
-// the blocks of svg_kmeans_loop_grouped_workspace_bytes in front (fp8_iters = 0 IS svg_kmeans_loop_grouped_strided on them), then mu and
-// the scratch of one e4m3 assignment
 extern "C" size_t svg_kmeans_loop_e4m3_workspace_bytes(int32_t B, int32_t N, int32_t K, int32_t D, int32_t group) {
-    const size_t loop = svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, group);
-    if (loop == 0 || K > 8192 || D != 128) return 0;
-    return (loop + 255) / 256 * 256 + kmeans_e4m3_mu_bytes(B) + svg_kmeans_assign_e4m3_workspace_bytes(B, N, K, D);
+    if (check_K(K) != SVG_OK || D != 128) return 0;
+    return kmeans_loop_ws(kmeans_shape(B, N, K, D, group), kLoopE4m3).bytes;
 }
 
 extern "C" int svg_kmeans_loop_e4m3(const void* x, int64_t x_batch_stride, const void* c_init, void* c_work_a, void* c_work_b, int32_t* labels,
                                     int32_t* counts, int32_t* sorted_idx, void* centroids_out, int32_t* n_iters, int32_t B, int32_t N,
                                     int32_t K, int32_t D, int32_t dtype, int32_t group, int32_t max_iters, float tol, int32_t fp8_iters,
                                     void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !c_init || !c_work_a || !c_work_b || !labels || !counts || !sorted_idx || !centroids_out || !n_iters || !workspace)
-        return SVG_ERR_BAD_ARG;
-    if (B <= 0 || N <= 0 || K <= 0 || max_iters <= 0 || group <= 0 || B % group != 0 || fp8_iters < 0 || fp8_iters > max_iters)
-        return SVG_ERR_BAD_ARG;
-    if (!kmeans_e4m3_covers(K, D, dtype)) return SVG_ERR_UNSUPPORTED;
-    if (workspace_bytes < svg_kmeans_loop_e4m3_workspace_bytes(B, N, K, D, group)) return SVG_ERR_WORKSPACE;
-    if (c_init == c_work_a || c_init == c_work_b || c_work_a == c_work_b || centroids_out == c_work_a || centroids_out == c_work_b)
-        return SVG_ERR_BAD_ARG;
-    if (const int rc = check_strided(x, x_batch_stride, N, D); rc != SVG_OK) return rc;
-    const long long x_bs = (long long)x_batch_stride;
-    if (fp8_iters == 0)   // today's loop, call for call
-        return kmeans_loop_impl(x, x_bs, nullptr, c_init, c_work_a, c_work_b, labels, counts, sorted_idx, centroids_out, n_iters, B, N, K, D, dtype,
-                                group, max_iters, tol, workspace, workspace_bytes, stream);
-    hipStream_t st = (hipStream_t)stream;
-    const int G = B / group;
-    const KmeansLoopScratch s = kmeans_loop_scratch(workspace, B, N, K, D, G, false);
-    char* extra = (char*)workspace + (svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, group) + 255) / 256 * 256;
-    float* mu = (float*)extra;
-    const KmeansE4m3Scratch es = kmeans_e4m3_scratch(extra + kmeans_e4m3_mu_bytes(B), B, K);
-    if (const int rc = svg_kmeans_centre(c_init, mu, B, K, D, dtype, stream); rc != SVG_OK) return rc;
-    if (hipMemsetAsync(s.state, 0, (size_t)4 * G * sizeof(int32_t), st) != hipSuccess) return SVG_ERR_LAUNCH;
-    for (int it = 0; it < max_iters; ++it) {
-        if (it < fp8_iters) {   // the centroids rotate as in kmeans_loop_iterate; the update, sort and commit are the 16-bit loop's
-            const void* cur = it == 0 ? c_init : ((it & 1) ? c_work_a : c_work_b);
-            void* out = (it & 1) ? c_work_b : c_work_a;
-            int rc;
-            if (dtype == SVG_DTYPE_BF16) {
-                rc = run_kmeans_assign_e4m3<__bf16>(x, mu, cur, s.t_labels, B, N, K, es, st, x_bs);
-                if (rc == SVG_OK) rc = run_kmeans_update<__bf16, 128>(x, cur, out, s.t_labels, s.t_counts, s.t_sorted, s.t_shift, B, N, K, s.it_ws, st, x_bs);
-            } else {
-                rc = run_kmeans_assign_e4m3<_Float16>(x, mu, cur, s.t_labels, B, N, K, es, st, x_bs);
-                if (rc == SVG_OK) rc = run_kmeans_update<_Float16, 128>(x, cur, out, s.t_labels, s.t_counts, s.t_sorted, s.t_shift, B, N, K, s.it_ws, st, x_bs);
-            }
-            if (rc != SVG_OK) return rc;
-            // an e4m3 iteration never stops a group: a shift is >= 0 or NaN, so nothing is below a tol of -1
-            kmeans_loop_commit(s, nullptr, labels, counts, sorted_idx, it, -1.f, B, N, K, group, st);
-        } else {
-            if (const int rc = kmeans_loop_iterate(s, x, x_bs, nullptr, c_init, c_work_a, c_work_b, it, B, N, K, D, dtype, G, stream); rc != SVG_OK)
-                return rc;
-            kmeans_loop_commit(s, nullptr, labels, counts, sorted_idx, it, tol, B, N, K, group, st);
-        }
-    }
-    return kmeans_loop_finish(s, c_init, c_work_a, c_work_b, centroids_out, n_iters, B, K, D, dtype, group, st);
+    KmeansCall a = kmeans_loop_call(kmeans_call(kmeans_shape(B, N, K, D, group), dtype, workspace, workspace_bytes, stream), x,
+                                    {c_init, c_work_a, c_work_b, centroids_out}, {labels, counts, sorted_idx, n_iters});
+    a.x_bs = (long long)x_batch_stride, a.max_iters = max_iters, a.tol = tol, a.fp8_iters = fp8_iters;
+    const KmeansLoopWs w = kmeans_loop_ws(a, kLoopE4m3);
+    const int rc = first_failure({check_loop_pointers(a), check_loop_sizes(a), need(fp8_iters >= 0 && fp8_iters <= max_iters, SVG_ERR_BAD_ARG),
+                                  check_e4m3_covers(a), check_workspace(a, w.bytes), check_alias(a), check_strided(a)});
+    return rc != SVG_OK ? rc : kmeans_loop_run(a, w);
 }
 
-// ---- the cosine and dot-product metrics (include/svg_attn_kmeans_metric.h): the bias-free assignment above, the update of
-// csrc/kmeans_metric.hip, and kmeans_loop_impl with a metric.  The checks stand in the order the header documents. ----
-static bool kmeans_metric_ok(int32_t metric) { return metric == SVG_KMEANS_COSINE || metric == SVG_KMEANS_DOT; }
-static bool kmeans_metric_covers(int32_t K, int32_t D, int32_t dtype) {
-    return K <= 8192 && (D == 64 || D == 128) && (dtype == SVG_DTYPE_BF16 || dtype == SVG_DTYPE_F16);
-}
-
+// ---- the cosine and dot-product metrics (include/svg_attn_kmeans_metric.h): the bias-free assignment, the update of
+// csrc/kmeans_metric.hip, and the loop driver with a metric ----
 extern "C" int svg_kmeans_assign_metric(const void* x, const void* centroids, int32_t* labels, int32_t B, int32_t N, int32_t K, int32_t D,
                                         int32_t dtype, int32_t metric, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !centroids || !labels || !workspace || B <= 0 || N <= 0 || K <= 0 || !kmeans_metric_ok(metric)) return SVG_ERR_BAD_ARG;
-    if (!kmeans_metric_covers(K, D, dtype)) return SVG_ERR_UNSUPPORTED;
-    if (workspace_bytes < svg_kmeans_workspace_bytes(B, N, K, D)) return SVG_ERR_WORKSPACE;
-    return dispatch_td(dtype, D, [&](auto t, auto d) {
-        constexpr int DD = decltype(d)::value;
-        return run_kmeans_assign<decltype(t), DD, false>(x, nullptr, centroids, labels, B, N, K, workspace, (hipStream_t)stream, (long long)N * DD);
-    });
+    KmeansCall a = kmeans_call(kmeans_shape(B, N, K, D, B), dtype, workspace, workspace_bytes, stream);
+    a.x = x, a.metric = metric;
+    const KmeansIterWs ws = kmeans_iter_ws(a, workspace);
+    const int rc = first_failure({check_pointers({x, centroids, labels, workspace}), check_positive({B, N, K}), check_metric(a), check_covers(a),
+                                  check_workspace(a, ws.bytes)});
+    return rc != SVG_OK ? rc : kmeans_assign(a, KmeansStep{centroids, nullptr, labels, nullptr, nullptr, nullptr, ws});
 }
 
 extern "C" int svg_kmeans_update_metric(const void* x, const int32_t* labels, const void* centroids_in, void* centroids_out, int32_t* counts,
                                         int32_t* sorted_idx, float* shift, int32_t B, int32_t N, int32_t K, int32_t D, int32_t dtype,
                                         int32_t metric, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !labels || !centroids_in || !centroids_out || !counts || !sorted_idx || !shift || !workspace) return SVG_ERR_BAD_ARG;
-    if (B <= 0 || N <= 0 || K <= 0 || !kmeans_metric_ok(metric)) return SVG_ERR_BAD_ARG;
-    if (!kmeans_metric_covers(K, D, dtype)) return SVG_ERR_UNSUPPORTED;
-    if (workspace_bytes < svg_kmeans_workspace_bytes(B, N, K, D)) return SVG_ERR_WORKSPACE;
-    return run_kmeans_update_metric(x, (long long)N * D, centroids_in, centroids_out, labels, counts, sorted_idx, shift, B, N, K, D, dtype, metric,
-                                    kmeans_sort_ws(workspace, B, K), (hipStream_t)stream);
+    KmeansCall a = kmeans_call(kmeans_shape(B, N, K, D, B), dtype, workspace, workspace_bytes, stream);
+    a.x = x, a.metric = metric;
+    const KmeansIterWs ws = kmeans_iter_ws(a, workspace);
+    const int rc = first_failure({check_pointers({x, labels, centroids_in, centroids_out, counts, sorted_idx, shift, workspace}),
+                                  check_positive({B, N, K}), check_metric(a), check_covers(a), check_workspace(a, ws.bytes)});
+    return rc != SVG_OK ? rc : kmeans_update(a, KmeansStep{centroids_in, centroids_out, const_cast<int32_t*>(labels), counts, sorted_idx, shift, ws});
 }
 
-// the blocks of svg_kmeans_loop_grouped_workspace_bytes in front, then the unit rows of c_init (cosine; the dot metric leaves them unused)
 extern "C" size_t svg_kmeans_loop_metric_workspace_bytes(int32_t B, int32_t N, int32_t K, int32_t D, int32_t group) {
-    const size_t loop = svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, group);
-    if (loop == 0 || K > 8192 || (D != 64 && D != 128)) return 0;
-    return (loop + 255) / 256 * 256 + ((size_t)B * K * D * 2 + 255) / 256 * 256;
+    if (first_failure({check_K(K), check_D(D)}) != SVG_OK) return 0;
+    return kmeans_loop_ws(kmeans_shape(B, N, K, D, group), kLoopMetric).bytes;
 }
 
 extern "C" int svg_kmeans_loop_metric(const void* x, int64_t x_batch_stride, const void* c_init, void* c_work_a, void* c_work_b, int32_t* labels,
                                       int32_t* counts, int32_t* sorted_idx, void* centroids_out, int32_t* n_iters, int32_t B, int32_t N,
                                       int32_t K, int32_t D, int32_t dtype, int32_t metric, int32_t group, int32_t max_iters, float tol,
                                       void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !c_init || !c_work_a || !c_work_b || !labels || !counts || !sorted_idx || !centroids_out || !n_iters || !workspace)
-        return SVG_ERR_BAD_ARG;
-    if (B <= 0 || N <= 0 || K <= 0 || max_iters <= 0 || group <= 0 || B % group != 0 || !kmeans_metric_ok(metric)) return SVG_ERR_BAD_ARG;
-    if (!kmeans_metric_covers(K, D, dtype)) return SVG_ERR_UNSUPPORTED;
-    if (workspace_bytes < svg_kmeans_loop_metric_workspace_bytes(B, N, K, D, group)) return SVG_ERR_WORKSPACE;
-    if (c_init == c_work_a || c_init == c_work_b || c_work_a == c_work_b || centroids_out == c_work_a || centroids_out == c_work_b)
-        return SVG_ERR_BAD_ARG;
-    if (const int rc = check_strided(x, x_batch_stride, N, D); rc != SVG_OK) return rc;
-    return kmeans_loop_impl(x, (long long)x_batch_stride, nullptr, c_init, c_work_a, c_work_b, labels, counts, sorted_idx, centroids_out, n_iters,
-                            B, N, K, D, dtype, group, max_iters, tol, workspace, workspace_bytes, stream, metric);
+    KmeansCall a = kmeans_loop_call(kmeans_call(kmeans_shape(B, N, K, D, group), dtype, workspace, workspace_bytes, stream), x,
+                                    {c_init, c_work_a, c_work_b, centroids_out}, {labels, counts, sorted_idx, n_iters});
+    a.x_bs = (long long)x_batch_stride, a.metric = metric, a.max_iters = max_iters, a.tol = tol;
+    const KmeansLoopWs w = kmeans_loop_ws(a, kLoopMetric);
+    const int rc = first_failure({check_loop_pointers(a), check_loop_sizes(a), check_metric(a), check_covers(a), check_workspace(a, w.bytes),
+                                  check_alias(a), check_strided(a)});
+    return rc != SVG_OK ? rc : kmeans_loop_run(a, w);
 }

@@ -1,7 +1,7 @@
 // flash-kmeans by direction (include/svg_attn_kmeans_metric.h): the centroid update of the cosine and dot-product metrics and the
 // initial normalisation of the cosine loop.  ref: triton_centroid_update_cosine, svg/kmeans_utils.py:143-190 (sums by atomics, then
 // `sums / counts`, `.to(x.dtype)`, F.normalize) and batch_kmeans_Cosine :769.  The assignment of both metrics is the bias-free form of
-// kmeans_assign_kernel and the loop is kmeans_loop_impl with a metric: both in csrc/kmeans.hip.
+// kmeans_assign_kernel and the loop is kmeans_loop_run on a record with a metric: both in csrc/kmeans.hip.
 // This file is built with IEEE arithmetic (build.py STRICT_FP: no fast-math, no contraction; correctly rounded sqrt and division):
 // every norm and quotient below is what the float64 statement of tests/test_gpu_kmeans_metric.py rounds, and scaling a row by a power
 // of two scales its weight by the inverse power exactly.
@@ -9,7 +9,6 @@
 
 #include "kmeans_metric.h"
 
-extern "C" size_t svg_argsort_workspace_bytes(int32_t B, int32_t N, int32_t K);
 extern "C" int svg_argsort_labels(const int32_t* labels, int32_t* sorted_idx, int32_t* counts, int32_t B, int32_t N, int32_t K,
                                   void* workspace, size_t workspace_bytes, void* stream);
 
@@ -190,22 +189,20 @@ __global__ __launch_bounds__(256) void kmeans_clear_shift_kernel(float* __restri
     if (i < B) shift[i] = 0.f;
 }
 
-int run_kmeans_update_metric(const void* x, long long x_bs, const void* c_in, void* c_out, const int32_t* labels, int32_t* counts,
-                             int32_t* sorted_idx, float* shift, int B, int N, int K, int D, int dtype, int metric, void* sort_ws,
-                             hipStream_t st) {
-    if (const int rc = svg_argsort_labels(labels, sorted_idx, counts, B, N, K, sort_ws, svg_argsort_workspace_bytes(B, N, K), (void*)st); rc)
-        return rc;
-    hipLaunchKernelGGL(kmeans_clear_shift_kernel, dim3((B + 255) / 256), dim3(256), 0, st, shift, B);
+int run_kmeans_update_metric(const KmeansCall& a, const KmeansStep& s) {
+    const int B = a.B, N = a.N, K = a.K;
+    if (const int rc = svg_argsort_labels(s.labels, s.sorted_idx, s.counts, B, N, K, s.ws.sort, s.ws.sort_bytes, (void*)a.st); rc) return rc;
+    hipLaunchKernelGGL(kmeans_clear_shift_kernel, dim3((B + 255) / 256), dim3(256), 0, a.st, s.shift, B);
     const int nchunks = (N + 1023) / 1024;
     const int groups = std::max(1, std::min(K, (3 * kNumCU + B - 1) / B));   // (the workgroups per batch of kmeans_update_kernel)
-    return dispatch_td(dtype, D, [&](auto t, auto d) {
+    return dispatch_td(a.dtype, a.D, [&](auto t, auto d) {
         using T = decltype(t);
         constexpr int DD = decltype(d)::value;
         auto launch = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(groups, B), dim3(256), 0, st, (const T*)x, (const T*)c_in, (T*)c_out, sorted_idx,
-                               (const int32_t*)sort_ws, counts, shift, N, K, (size_t)nchunks * K, x_bs);
+            hipLaunchKernelGGL(kern, dim3(groups, B), dim3(256), 0, a.st, (const T*)a.x, (const T*)s.c_in, (T*)s.c_out, s.sorted_idx,
+                               (const int32_t*)s.ws.sort, s.counts, s.shift, N, K, (size_t)nchunks * K, a.x_bs);
         };
-        if (metric == SVG_KMEANS_COSINE)
+        if (a.metric == SVG_KMEANS_COSINE)
             launch(kmeans_update_sphere_kernel<T, DD, true>);
         else
             launch(kmeans_update_sphere_kernel<T, DD, false>);
@@ -213,13 +210,14 @@ int run_kmeans_update_metric(const void* x, long long x_bs, const void* c_in, vo
     });
 }
 
-int run_kmeans_unit_rows(const void* c, void* out, long long rows, int D, int dtype, hipStream_t st) {
-    return dispatch_td(dtype, D, [&](auto t, auto d) {
+int run_kmeans_unit_rows(const KmeansCall& a, void* out) {
+    const long long rows = (long long)a.B * a.K;
+    return dispatch_td(a.dtype, a.D, [&](auto t, auto d) {
         using T = decltype(t);
         constexpr int DD = decltype(d)::value;
         constexpr int RPB = 256 / (DD / 8);
-        hipLaunchKernelGGL((kmeans_unit_rows_kernel<T, DD>), dim3((unsigned)std::min<long long>(2048, (rows + RPB - 1) / RPB)), dim3(256), 0, st,
-                           (const T*)c, (T*)out, rows);
+        hipLaunchKernelGGL((kmeans_unit_rows_kernel<T, DD>), dim3((unsigned)std::min<long long>(2048, (rows + RPB - 1) / RPB)), dim3(256), 0, a.st,
+                           (const T*)a.c_init, (T*)out, rows);
         return launch_status();
     });
 }

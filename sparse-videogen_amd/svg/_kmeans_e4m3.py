@@ -44,30 +44,5 @@ def kmeans_loop_e4m3(x: torch.Tensor, c_init: torch.Tensor, max_iters: int, tol:
     """kmeans_loop whose first fp8_iters iterations assign with the e4m3 scores (svg_kmeans_loop_e4m3; fp8_iters = 0: the bits of
     kmeans_loop) -> (labels int32 [B, N], centroids [B, K, D], counts int32 [B, K], n_iters int32 [] or [B // group] on the device,
     sorted_idx int32 [B, N]).  x: contiguous, or batches further apart with contiguous rows (read in place); head_dim 128 only."""
-    lib = _native.load()
-    _native._dev(c_init)
-    _native._gpu(x)
-    B, N, D = x.shape
-    K = c_init.shape[1]
-    assert c_init.shape == (B, K, D) and c_init.dtype == x.dtype
-    g = B if group is None else int(group)
-    assert g >= 1 and B % g == 0, f"kmeans_loop_e4m3: group = {group} must divide B = {B}"
-    if not (x.stride(2) == 1 and x.stride(1) == D and x.stride(0) >= N * D and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0):
-        x = x.contiguous()
-    key = _native.WorkspaceCache.key("kmeans_e4m3", B, N, K, D, x.dtype, g, device=x.device)
-    w = None if work is None else work.get(key)
-    if w is None:
-        nb = lib.svg_kmeans_loop_e4m3_workspace_bytes(B, N, K, D, g)
-        w = dict(ca=_native.empty_like(c_init), cb=_native.empty_like(c_init), ws=_native.empty(nb, dtype=torch.uint8, device=x.device))
-        if work is not None:
-            work[key] = w
-    labels = _native.empty((B, N), dtype=torch.int32, device=x.device)
-    sorted_idx = _native.empty((B, N), dtype=torch.int32, device=x.device)
-    counts = _native.empty((B, K), dtype=torch.int32, device=x.device)
-    cent = _native.empty_like(c_init)
-    n_it = _native.empty(() if group is None else (B // g,), dtype=torch.int32, device=x.device)
-    _native._check(lib.svg_kmeans_loop_e4m3(x.data_ptr(), int(x.stride(0)), c_init.data_ptr(), w["ca"].data_ptr(), w["cb"].data_ptr(),
-                                    labels.data_ptr(), counts.data_ptr(), sorted_idx.data_ptr(), cent.data_ptr(), n_it.data_ptr(), B, N, K, D,
-                                    _native._dtype_code(x), g, int(max_iters), float(tol), int(fp8_iters), w["ws"].data_ptr(), w["ws"].numel(),
-                                    _native._stream()), "svg_kmeans_loop_e4m3")
-    return labels, cent, counts, n_it, sorted_idx
+    return _native._kmeans_strided_loop("kmeans_loop_e4m3", "kmeans_e4m3", x, c_init, work, group,
+                                        lambda g: (g, int(max_iters), float(tol), int(fp8_iters)))

@@ -27,8 +27,7 @@ class KmeansSteppedSide:
         group = B if group is None else int(group)
         assert group >= 1 and B % group == 0, f"KmeansSteppedSide: group = {group} must divide B = {B}"
         G = B // group
-        in_place = x.stride(2) == 1 and x.stride(1) == D and x.stride(0) >= N * D and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0
-        self.x = x if in_place else x.contiguous()
+        self.x = x if _native._kmeans_x_in_place(x) else x.contiguous()
         self.c_init, self.tol, self.group, self.G = c_init, float(tol), group, G
         self.maxima = _native.empty((G,), dtype=torch.float32, device=x.device) if maxima is None else maxima
         self.ca, self.cb = _native.empty_like(c_init), _native.empty_like(c_init)

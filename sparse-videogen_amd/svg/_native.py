@@ -1871,38 +1871,99 @@ def kmeans_iter(x: torch.Tensor, xsq: Optional[torch.Tensor], c_in: torch.Tensor
     _check(rc, "svg_kmeans_iter")
 
 
-def kmeans_assign(x: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
-    """labels int32 [B, N] of the nearest centroid (lowest index on ties): the assignment half of kmeans_iter (svg_kmeans_assign)"""
+def _kmeans_assign_call(entry: str, x: torch.Tensor, centroids: torch.Tensor, *extra) -> torch.Tensor:
+    """labels and per-iteration workspace of kmeans_assign / kmeans_assign_metric, and the call; `extra`: what the entry takes behind dtype"""
     lib = load()
-    _dev(x, centroids)
     B, N, D = x.shape
     K = centroids.shape[1]
-    assert centroids.shape == (B, K, D) and centroids.dtype == x.dtype and x.is_contiguous() and centroids.is_contiguous()
     labels = empty((B, N), dtype=torch.int32, device=x.device)
     ws = empty(lib.svg_kmeans_workspace_bytes(B, N, K, D), dtype=torch.uint8, device=x.device)
-    _check(lib.svg_kmeans_assign(x.data_ptr(), centroids.data_ptr(), labels.data_ptr(), B, N, K, D, _dtype_code(x), ws.data_ptr(),
-                                 ws.numel(), _stream()), "svg_kmeans_assign")
+    _check(getattr(lib, entry)(x.data_ptr(), centroids.data_ptr(), labels.data_ptr(), B, N, K, D, _dtype_code(x), *extra, ws.data_ptr(),
+                               ws.numel(), _stream()), entry)
     return labels
 
 
-def kmeans_update(x: torch.Tensor, labels: torch.Tensor, centroids_in: torch.Tensor):
-    """The update half on given labels (svg_kmeans_update) -> (centroids [B, K, D] of x.dtype, counts int32 [B, K], sorted_idx int32
-    [B, N], shift float32 [B]); empty clusters keep centroids_in."""
+def kmeans_assign(x: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
+    """labels int32 [B, N] of the nearest centroid (lowest index on ties): the assignment half of kmeans_iter (svg_kmeans_assign)"""
+    load()
+    _dev(x, centroids)
+    (B, N, D), K = x.shape, centroids.shape[1]
+    assert centroids.shape == (B, K, D) and centroids.dtype == x.dtype and x.is_contiguous() and centroids.is_contiguous()
+    return _kmeans_assign_call("svg_kmeans_assign", x, centroids)
+
+
+def _kmeans_update_call(entry: str, x: torch.Tensor, labels: torch.Tensor, centroids_in: torch.Tensor, *extra):
+    """outputs and per-iteration workspace of kmeans_update / kmeans_update_metric, and the call -> (centroids, counts, sorted_idx, shift)"""
     lib = load()
-    _dev(x, labels, centroids_in)
     B, N, D = x.shape
     K = centroids_in.shape[1]
-    assert labels.dtype == torch.int32 and labels.shape == (B, N) and labels.is_contiguous()
-    assert centroids_in.shape == (B, K, D) and centroids_in.dtype == x.dtype and x.is_contiguous() and centroids_in.is_contiguous()
+    assert labels.dtype == torch.int32 and labels.shape == (B, N)
+    assert centroids_in.shape == (B, K, D) and centroids_in.dtype == x.dtype
     cent = empty_like(centroids_in)
     counts = empty((B, K), dtype=torch.int32, device=x.device)
     sorted_idx = empty((B, N), dtype=torch.int32, device=x.device)
     shift = empty((B,), dtype=torch.float32, device=x.device)
     ws = empty(lib.svg_kmeans_workspace_bytes(B, N, K, D), dtype=torch.uint8, device=x.device)
-    _check(lib.svg_kmeans_update(x.data_ptr(), labels.data_ptr(), centroids_in.data_ptr(), cent.data_ptr(), counts.data_ptr(),
-                                 sorted_idx.data_ptr(), shift.data_ptr(), B, N, K, D, _dtype_code(x), ws.data_ptr(), ws.numel(), _stream()),
-           "svg_kmeans_update")
+    _check(getattr(lib, entry)(x.data_ptr(), labels.data_ptr(), centroids_in.data_ptr(), cent.data_ptr(), counts.data_ptr(),
+                               sorted_idx.data_ptr(), shift.data_ptr(), B, N, K, D, _dtype_code(x), *extra, ws.data_ptr(), ws.numel(), _stream()),
+           entry)
     return cent, counts, sorted_idx, shift
+
+
+def kmeans_update(x: torch.Tensor, labels: torch.Tensor, centroids_in: torch.Tensor):
+    """The update half on given labels (svg_kmeans_update) -> (centroids [B, K, D] of x.dtype, counts int32 [B, K], sorted_idx int32
+    [B, N], shift float32 [B]); empty clusters keep centroids_in."""
+    load()
+    _dev(x, labels, centroids_in)
+    assert labels.is_contiguous() and x.is_contiguous() and centroids_in.is_contiguous()
+    return _kmeans_update_call("svg_kmeans_update", x, labels, centroids_in)
+
+
+def _kmeans_x_in_place(x: torch.Tensor) -> bool:
+    """x [B, N, D] is read in place by the entries that take a batch stride: contiguous rows (last stride 1, row stride D), batches
+    x.stride(0) >= N * D elements apart, a multiple of 8, from a 16-byte aligned base (the video tokens `q[:, :V]` of a [H, S, D] tensor)"""
+    _, N, D = x.shape
+    return x.stride(2) == 1 and x.stride(1) == D and x.stride(0) >= N * D and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0
+
+
+def _kmeans_loop_call(entry: str, ws_entry: str, tag: str, x: torch.Tensor, second, c_init: torch.Tensor, work, group: tuple, grouped: bool,
+                      mid: tuple):
+    """The scratch (from `work`, a WorkspaceCache, under `tag`; or fresh per call), the five outputs and the call of a Lloyd-loop entry:
+    entry(x, second, c_init, work a, work b, labels, counts, sorted_idx, centroids, n_iters, B, N, K, D, dtype, *mid, workspace, bytes,
+    stream).  second: xsq or the batch stride of x; group: () or (group,) — what ws_entry takes behind D and the cache key carries;
+    grouped: n_iters is [B // group], else 0-dim."""
+    lib = load()
+    (B, N, D), K, dev = x.shape, c_init.shape[1], x.device
+    key = WorkspaceCache.key(tag, B, N, K, D, x.dtype, *(group or (None,)), device=dev)
+    w = None if work is None else work.get(key)
+    if w is None:
+        nb = getattr(lib, ws_entry)(B, N, K, D, *group)
+        w = dict(ca=empty_like(c_init), cb=empty_like(c_init), ws=empty(nb, dtype=torch.uint8, device=dev))
+        if work is not None:
+            work[key] = w
+    labels = empty((B, N), dtype=torch.int32, device=dev)
+    sorted_idx = empty((B, N), dtype=torch.int32, device=dev)
+    counts = empty((B, K), dtype=torch.int32, device=dev)
+    cent = empty_like(c_init)
+    n_it = empty((B // group[0],) if grouped else (), dtype=torch.int32, device=dev)   # (copied from the loop's state by every call)
+    _check(getattr(lib, entry)(x.data_ptr(), second, c_init.data_ptr(), w["ca"].data_ptr(), w["cb"].data_ptr(), labels.data_ptr(), counts.data_ptr(),
+                               sorted_idx.data_ptr(), cent.data_ptr(), n_it.data_ptr(), B, N, K, D, _dtype_code(x), *mid,
+                               w["ws"].data_ptr(), w["ws"].numel(), _stream()), entry)
+    return labels, cent, counts, n_it, sorted_idx
+
+
+def _kmeans_strided_loop(name: str, tag: str, x: torch.Tensor, c_init: torch.Tensor, work, group: Optional[int], mid):
+    """kmeans_loop_e4m3 / kmeans_loop_metric: svg_<name> on x in place or on a copy; mid(g): the entry's arguments from group to tol"""
+    load()
+    _dev(c_init)
+    _gpu(x)
+    (B, N, D), K = x.shape, c_init.shape[1]
+    assert c_init.shape == (B, K, D) and c_init.dtype == x.dtype
+    g = B if group is None else int(group)
+    assert g >= 1 and B % g == 0, f"{name}: group = {group} must divide B = {B}"
+    if not _kmeans_x_in_place(x):
+        x = x.contiguous()
+    return _kmeans_loop_call("svg_" + name, f"svg_{name}_workspace_bytes", tag, x, int(x.stride(0)), c_init, work, (g,), group is not None, mid(g))
 
 
 def kmeans_loop(x: torch.Tensor, xsq: Optional[torch.Tensor], c_init: torch.Tensor, max_iters: int, tol: float, work=None,
@@ -1912,7 +1973,7 @@ def kmeans_loop(x: torch.Tensor, xsq: Optional[torch.Tensor], c_init: torch.Tens
     scratch per call) that keeps the scratch tensors of a (B, N, K, D) shape per device AND stream between calls.
     group: None — one stopping rule over all B batches; an integer dividing B — one stopping rule per `group` consecutive batches
     (svg_kmeans_loop_grouped), n_iters is then int32 [B // group]."""
-    lib = load()
+    load()
     _dev(xsq, c_init)
     _gpu(x)
     B, N, D = x.shape
@@ -1921,40 +1982,14 @@ def kmeans_loop(x: torch.Tensor, xsq: Optional[torch.Tensor], c_init: torch.Tens
     if group is not None:
         group = int(group)
         assert group >= 1 and B % group == 0, f"kmeans_loop: group = {group} must divide B = {B}"
-    # x: contiguous, or batches further apart than N * D with contiguous rows inside (the video tokens `q[:, :V]` of a [H, S, D] tensor):
-    # svg_kmeans_loop_strided reads them in place
-    batch_strided = (not x.is_contiguous()) and x.stride(2) == 1 and x.stride(1) == D and x.stride(0) >= N * D and x.stride(0) % 8 == 0 \
-        and x.data_ptr() % 16 == 0
+    # x: contiguous (the entries with xsq), or a view svg_kmeans_loop[_grouped]_strided reads in place; anything else is copied
+    batch_strided = (not x.is_contiguous()) and _kmeans_x_in_place(x)
     if not x.is_contiguous() and not batch_strided:
         x = x.contiguous()
-    key = WorkspaceCache.key("kmeans", B, N, K, D, x.dtype, group, device=x.device)
-    w = None if work is None else work.get(key)
-    if w is None:
-        nb = lib.svg_kmeans_loop_workspace_bytes(B, N, K, D) if group is None else lib.svg_kmeans_loop_grouped_workspace_bytes(B, N, K, D, group)
-        w = dict(ca=empty_like(c_init), cb=empty_like(c_init), ws=empty(nb, dtype=torch.uint8, device=x.device))
-        if work is not None:
-            work[key] = w
-    labels = empty((B, N), dtype=torch.int32, device=x.device)
-    sorted_idx = empty((B, N), dtype=torch.int32, device=x.device)
-    counts = empty((B, K), dtype=torch.int32, device=x.device)
-    cent = empty_like(c_init)
-    n_it = empty(() if group is None else (B // group,), dtype=torch.int32, device=x.device)   # (copied from the loop's state by every call)
-    outs = (labels.data_ptr(), counts.data_ptr(), sorted_idx.data_ptr(), cent.data_ptr(), n_it.data_ptr(), B, N, K, D, _dtype_code(x))
-    tail = (int(max_iters), float(tol), w["ws"].data_ptr(), w["ws"].numel(), _stream())
-    cs = (c_init.data_ptr(), w["ca"].data_ptr(), w["cb"].data_ptr())
-    if group is not None:
-        if batch_strided:
-            _check(lib.svg_kmeans_loop_grouped_strided(x.data_ptr(), int(x.stride(0)), *cs, *outs, group, *tail), "svg_kmeans_loop_grouped_strided")
-        else:
-            _check(lib.svg_kmeans_loop_grouped(x.data_ptr(), _ptr(xsq), *cs, *outs, group, *tail), "svg_kmeans_loop_grouped")
-        return labels, cent, counts, n_it, sorted_idx
-    if batch_strided:
-        rc = lib.svg_kmeans_loop_strided(x.data_ptr(), int(x.stride(0)), *cs, *outs, *tail)
-        _check(rc, "svg_kmeans_loop_strided")
-        return labels, cent, counts, n_it, sorted_idx
-    rc = lib.svg_kmeans_loop(x.data_ptr(), _ptr(xsq), *cs, *outs, *tail)
-    _check(rc, "svg_kmeans_loop")
-    return labels, cent, counts, n_it, sorted_idx
+    stem = "svg_kmeans_loop" if group is None else "svg_kmeans_loop_grouped"
+    g = () if group is None else (group,)
+    return _kmeans_loop_call(stem + "_strided" * batch_strided, stem + "_workspace_bytes", "kmeans", x, int(x.stride(0)) if batch_strided else _ptr(xsq),
+                             c_init, work, g, group is not None, (*g, int(max_iters), float(tol)))
 
 
 def kmeans_stepped_workspace_bytes(B: int, N: int, K: int, D: int, group: int) -> int:

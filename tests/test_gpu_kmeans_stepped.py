@@ -1,5 +1,5 @@
 """The Lloyd loop in steps on the GPU (include/svg_attn_kmeans_stepped.h; csrc/kmeans.hip: kmeans_commit_kernel<true>,
-kmeans_group_maxima_kernel and the host steps kmeans_loop_impl shares with the three entries; svg._kmeans_stepped.KmeansSteppedSide,
+kmeans_group_maxima_kernel and the host steps kmeans_loop_run shares with the three entries; svg._kmeans_stepped.KmeansSteppedSide,
 svg.kmeans_utils.lloyd_stepped, svg.models._core.kmeans_clustering under a head shard).
 
 1. With the maxima untouched the five results are those of _native.kmeans_loop(group=), bit for bit: shapes that are no multiple of a tile

@@ -10,8 +10,8 @@ printed (A, B, A again: the third column shows the drift of the box).
 --dynmap: ONLY the entries SVG2's per-head top-p shares kernels with — svg_identify_dynamic_map in both kernel forms and
 svg_sample_dense_rows (o32 and lse) — called through ctypes handles of the two files, so that A may be a library from before the entries
 of include/svg_attn_adaptive_top_p.h existed (svg._native.load() types every table and refuses such a file).
---kmeans-loop: ONLY svg_kmeans_loop and svg_kmeans_loop_grouped_strided, through ctypes handles of the two files for the same reason (A: a
-library from before include/svg_attn_kmeans_stepped.h, whose host steps those loops now share with the stepped entries)."""
+--kmeans-loop [--production [--jsonl FILE]]: ONLY the k-means entries — every Lloyd loop, the single iteration and its halves, their metric
+and e4m3 siblings — through ctypes handles of the two files (A: a library built from the parent of a change to the k-means host path)."""
 import sys
 from pathlib import Path
 
@@ -125,51 +125,152 @@ def dynmap_cases(dev):
 
 
 def kmeans_loop_cases(dev):
-    """--kmeans-loop: svg_kmeans_loop and svg_kmeans_loop_grouped_strided of two library files, raw C calls on the same tensors — all five
-    results compared, poisoned outputs and workspaces"""
+    """--kmeans-loop: every k-means entry of two library files, raw C calls on the same seeded tensors with poisoned outputs and workspaces.
+    Small shapes where the host path can go wrong: every loop entry (five results each) over contiguous and batch-strided x, bf16 and fp16,
+    max_iters = 5 with the first stopping group built to stop before the others (tests/test_gpu_kmeans_stepped.py
+    test_a_group_that_stops_while_another_runs_on), fp8_iters in {0, 2, 4} at head_dim 128; the single iteration and its halves with their
+    metric and e4m3 siblings (labels / centroids / counts / sorted indices / shift).  With --production: A / B / A-again times of
+    svg_kmeans_loop_strided at the k-means shape of bench_svg2.py (Wan 2.1 720p: 40 heads, 75 600 tokens, K = 300 and 1000, 2 iterations),
+    windows of at least a second, appended to the file behind --jsonl."""
     import ctypes
+    import json
 
+    from test_gpu_kernels import _blobs
     from tests.test_gpu_fullsize_svg2 import clustered
 
-    names = ("svg_kmeans_loop", "svg_kmeans_loop_grouped_strided", "svg_kmeans_loop_grouped_workspace_bytes")
     libs = {}
     for tag in ("A", "B"):
         lib = ctypes.CDLL(LIBS[tag])
-        for name in names:
-            getattr(lib, name).restype, getattr(lib, name).argtypes = nat.SIGNATURES[name]
+        for table in (nat.SIGNATURES, nat.KMEANS_E4M3_SIGNATURES, nat.KMEANS_METRIC_ENTRIES):
+            for name, sig in table.items():
+                if name.startswith("svg_kmeans"):
+                    getattr(lib, name).restype, getattr(lib, name).argtypes = sig
         libs[tag] = lib
     st = lambda: torch.cuda.current_stream().cuda_stream  # noqa: E731
-    gen = torch.Generator(device="cuda").manual_seed(3)
-    ok = True
-    # (heads, N, K, group, iterations, rows behind every batch): the 2-iteration stage of Wan 720p at both cluster counts, a grouped loop over a
-    # view with text rows behind the video tokens, and a loop long enough for groups to stop
-    for B, N, K, group, iters, pad in ((8, 75600, 1000, 8, 2, 0), (8, 75600, 300, 8, 2, 0), (6, 30000, 400, 3, 2, 256), (4, 20000, 64, 2, 12, 0)):
-        base = clustered(B, N + pad, 128, 64, gen)
-        x = base[:, :N]
-        init = x[:, :K].contiguous()
-        outs, ms = {}, {}
+    mk = lambda *s, dt=torch.int32: nat.poison_storage(torch.empty(*s, dtype=dt, device=dev))  # noqa: E731
+    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    bits = lambda t: t.view(torch.int16) if t.dtype in (torch.bfloat16, torch.float16) else t  # noqa: E731
+    ok, rows = True, 0
+
+    def compare(title, run):
+        """run(lib) -> tuple of result tensors; under A, B and A again"""
+        nonlocal ok, rows
+        outs = {}
         for tag in ("A", "B", "A2"):
-            lib = libs[tag[0]]
-            mk = lambda *s, dt=torch.int32: nat.poison_storage(torch.empty(*s, dtype=dt, device=dev))  # noqa: E731
-            lab, srt, cnt, n_it = mk(B, N), mk(B, N), mk(B, K), mk(B // group)
-            cent, ca, cb = (mk(B, K, 128, dt=x.dtype) for _ in range(3))
-            ws = mk(lib.svg_kmeans_loop_grouped_workspace_bytes(B, N, K, 128, group), dt=torch.uint8)
-            tail = (B, N, K, 128, 0)
-            if pad or group != B:
-                fn = lambda: lib.svg_kmeans_loop_grouped_strided(x.data_ptr(), x.stride(0), init.data_ptr(), ca.data_ptr(), cb.data_ptr(),  # noqa: E731
-                                                                 lab.data_ptr(), cnt.data_ptr(), srt.data_ptr(), cent.data_ptr(), n_it.data_ptr(),
-                                                                 *tail, group, iters, 1e-4, ws.data_ptr(), ws.numel(), st())
-            else:
-                fn = lambda: lib.svg_kmeans_loop(x.data_ptr(), None, init.data_ptr(), ca.data_ptr(), cb.data_ptr(), lab.data_ptr(),  # noqa: E731
-                                                 cnt.data_ptr(), srt.data_ptr(), cent.data_ptr(), n_it.data_ptr(), *tail, iters, 1e-4,
-                                                 ws.data_ptr(), ws.numel(), st())
-            assert fn() == 0
-            ms[tag], outs[tag] = timed(fn, 5), (lab, cnt, srt, cent.view(torch.int16), n_it)
+            outs[tag] = [bits(t) for t in run(libs[tag[0]])]
+            torch.cuda.synchronize()
         same = all(torch.equal(a, b) for t in ("B", "A2") for a, b in zip(outs["A"], outs[t]))
-        print(f"k-means loop B={B} N={N} K={K} group={group} iterations={iters} batch stride {x.stride(0)}: A {ms['A']:.4f} ms  B {ms['B']:.4f} ms  "
-              f"A again {ms['A2']:.4f} ms   B/A {ms['B'] / (0.5 * (ms['A'] + ms['A2'])):.4f}   bit-identical (labels, counts, sorted, centroids, "
-              f"n_iters): {same}   n_iters {outs['B'][4].tolist()}", flush=True)
+        rows += 1
         ok &= same
+        return same, outs["B"]
+
+    def loop_run(entry, ws_entry, x, second, c0, shape, mid, ws_extra=()):
+        B, N, K, D, code = shape
+
+        def run(lib):
+            lab, srt, cnt, n_it = mk(B, N), mk(B, N), mk(B, K), mk(B // ws_extra[0] if ws_extra else 1)
+            cent, ca, cb = (mk(B, K, D, dt=x.dtype) for _ in range(3))
+            ws = mk(getattr(lib, ws_entry)(B, N, K, D, *ws_extra), dt=torch.uint8)
+            rc = getattr(lib, entry)(x.data_ptr(), second, c0.data_ptr(), ca.data_ptr(), cb.data_ptr(), lab.data_ptr(), cnt.data_ptr(), srt.data_ptr(),
+                                     cent.data_ptr(), n_it.data_ptr(), B, N, K, D, code, *mid, ws.data_ptr(), ws.numel(), st())
+            assert rc == 0, (entry, rc)
+            return lab, cent, cnt, n_it, srt
+        return run
+
+    for B, N, K, D, group in ((2, 257, 65, 128, 2), (4, 700, 129, 64, 2), (3, 1025, 24, 128, 3), (4, 700, 129, 128, 1)):
+        for dt in (torch.bfloat16, torch.float16):
+            code = 0 if dt == torch.bfloat16 else 1
+            # group 0: separated blobs started next to their centres (stops early); the others: spread 1.2, started from their first rows
+            xa, ca_ = _blobs(group, N, K, D, 0.3, seed=5, dtype=dt)
+            c0a = (ca_.float() + 0.2 * torch.randn(group, K, D, generator=torch.Generator().manual_seed(6))).to(dt)
+            xs, cs = [xa], [c0a]
+            if B > group:
+                xb, _ = _blobs(B - group, N, K, D, 1.2, seed=7, dtype=dt)
+                xs, cs = xs + [xb], cs + [xb[:, :K]]
+            xc, c0 = torch.cat(xs).to(dev), torch.cat(cs).to(dev).contiguous()
+            padded = torch.zeros(B, N + 40, D, dtype=dt, device=dev)
+            padded[:, :N] = xc
+            shape = (B, N, K, D, code)
+            for lay, x in (("contiguous", xc), ("batch-strided", padded[:, :N])):
+                tail, gw = (5, 1e-4), "svg_kmeans_loop_grouped_workspace_bytes"
+                todo = [("svg_kmeans_loop_strided", loop_run("svg_kmeans_loop_strided", "svg_kmeans_loop_workspace_bytes", x, x.stride(0), c0, shape, tail)),
+                        ("svg_kmeans_loop_grouped_strided", loop_run("svg_kmeans_loop_grouped_strided", gw, x, x.stride(0), c0, shape, (group, *tail), (group,)))]
+                if lay == "contiguous":
+                    todo += [("svg_kmeans_loop", loop_run("svg_kmeans_loop", "svg_kmeans_loop_workspace_bytes", x, None, c0, shape, tail)),
+                             ("svg_kmeans_loop_grouped", loop_run("svg_kmeans_loop_grouped", gw, x, None, c0, shape, (group, *tail), (group,)))]
+                todo += [(f"svg_kmeans_loop_metric metric={m}", loop_run("svg_kmeans_loop_metric", "svg_kmeans_loop_metric_workspace_bytes", x, x.stride(0), c0,
+                                                                        shape, (m, group, *tail), (group,))) for m in (1, 2)]
+                if D == 128:
+                    todo += [(f"svg_kmeans_loop_e4m3 fp8_iters={f}", loop_run("svg_kmeans_loop_e4m3", "svg_kmeans_loop_e4m3_workspace_bytes", x, x.stride(0), c0,
+                                                                             shape, (group, *tail, f), (group,))) for f in (0, 2, 4)]
+                for title, run in todo:
+                    same, out = compare(title, run)
+                    print(f"B={B} N={N} K={K} D={D} group={group} {str(dt)[6:]} {lay}: {title}: bit-identical (labels, centroids, counts, n_iters, "
+                          f"sorted): {same}   n_iters {out[3].reshape(-1).tolist()}", flush=True)
+
+            def half(entry, lead, outs, extra=(), ws_entry="svg_kmeans_workspace_bytes"):
+                """entry(*lead, *outs, B, N, K, D, dtype, *extra, ws, bytes, stream) -> the outputs"""
+                def run(lib):
+                    o = [mk(*s, dt=d) for s, d in outs]
+                    ws = mk(getattr(lib, ws_entry)(B, N, K, D), dt=torch.uint8)
+                    rc = getattr(lib, entry)(*[p(t) for t in lead], *[t.data_ptr() for t in o], B, N, K, D, code, *extra, ws.data_ptr(), ws.numel(), st())
+                    assert rc == 0, (entry, rc)
+                    return o
+                return run
+
+            LAB, CNT, CEN, SH = ((B, N), torch.int32), ((B, K), torch.int32), ((B, K, D), dt), ((B,), torch.float32)
+            _, (labels,) = compare("assign", half("svg_kmeans_assign", (xc, c0), [LAB]))
+            labels = labels.clone()
+            todo = [("svg_kmeans_iter", half("svg_kmeans_iter", (xc, None, c0), [CEN, LAB, CNT, LAB, SH])),
+                    ("svg_kmeans_assign", half("svg_kmeans_assign", (xc, c0), [LAB])),
+                    ("svg_kmeans_update", half("svg_kmeans_update", (xc, labels, c0), [CEN, CNT, LAB, SH]))]
+            for m in (1, 2):
+                todo += [(f"svg_kmeans_assign_metric metric={m}", half("svg_kmeans_assign_metric", (xc, c0), [LAB], (m,))),
+                         (f"svg_kmeans_update_metric metric={m}", half("svg_kmeans_update_metric", (xc, labels, c0), [CEN, CNT, LAB, SH], (m,)))]
+            if D == 128:
+                def centre(lib):
+                    mu = mk(B, D, dt=torch.float32)
+                    assert lib.svg_kmeans_centre(c0.data_ptr(), mu.data_ptr(), B, K, D, code, st()) == 0
+                    return (mu,)
+                _, (mu,) = compare("centre", centre)
+                mu = mu.clone()
+                todo += [("svg_kmeans_centre", centre)] + [(f"svg_kmeans_assign_e4m3 mu={'given' if m is not None else 'NULL'}",
+                                                           half("svg_kmeans_assign_e4m3", (xc, c0, m), [LAB], (), "svg_kmeans_assign_e4m3_workspace_bytes"))
+                                                          for m in (None, mu)]
+            for title, run in todo:
+                same, _ = compare(title, run)
+                print(f"B={B} N={N} K={K} D={D} {str(dt)[6:]} contiguous: {title}: bit-identical (every output, the shift included): {same}", flush=True)
+    print(f"{rows} rows compared", flush=True)
+
+    if "--production" in sys.argv:
+        jsonl = sys.argv[sys.argv.index("--jsonl") + 1] if "--jsonl" in sys.argv else None
+        gen = torch.Generator(device="cuda").manual_seed(3)
+        B, N, D, iters = 40, 75600, 128, 2
+        x = clustered(B, N, D, 64, gen)
+        for K in (300, 1000):
+            init = x[:, :K].contiguous()
+            outs, ms = {}, {}
+            for tag in ("A", "B", "A2"):
+                lib = libs[tag[0]]
+                lab, srt, cnt, n_it = mk(B, N), mk(B, N), mk(B, K), mk(1)
+                cent, ca, cb = (mk(B, K, D, dt=x.dtype) for _ in range(3))
+                ws = mk(lib.svg_kmeans_loop_workspace_bytes(B, N, K, D), dt=torch.uint8)
+                fn = lambda: lib.svg_kmeans_loop_strided(x.data_ptr(), x.stride(0), init.data_ptr(), ca.data_ptr(), cb.data_ptr(), lab.data_ptr(),  # noqa: E731
+                                                         cnt.data_ptr(), srt.data_ptr(), cent.data_ptr(), n_it.data_ptr(), B, N, K, D, 0, iters, 1e-4,
+                                                         ws.data_ptr(), ws.numel(), st())
+                assert fn() == 0
+                n = max(5, int(1200.0 / timed(fn, 3)) + 1)      # (timed warms up with a call of its own) a window of at least 1.2 s
+                ms[tag], outs[tag] = timed(fn, n), (lab, cnt, srt, bits(cent), n_it)
+            same = all(torch.equal(a, b) for t in ("B", "A2") for a, b in zip(outs["A"], outs[t]))
+            ok &= same
+            ref, drift = 0.5 * (ms["A"] + ms["A2"]), abs(ms["A"] - ms["A2"])
+            rec = dict(case=f"svg_kmeans_loop_strided wan720p B={B} N={N} K={K} D={D} bf16 iterations={iters}", repetitions=n, A_ms=round(ms["A"], 4),
+                       B_ms=round(ms["B"], 4), A_again_ms=round(ms["A2"], 4), B_over_A=round(ms["B"] / ref, 4), B_minus_A_ms=round(ms["B"] - ref, 4),
+                       A_drift_ms=round(drift, 4), inside_drift=bool(abs(ms["B"] - ref) <= drift), bit_identical=same)
+            print(json.dumps(rec), flush=True)
+            if jsonl:
+                with open(jsonl, "a") as f:
+                    f.write(json.dumps(rec) + "\n")
     return ok
 
 
