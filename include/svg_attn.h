@@ -805,6 +805,8 @@ int svg_debug_wg_trace(uint64_t* out, int32_t n_workgroups);
 #include "svg_attn_kmeans_e4m3.h"
 /* ... and SVG2's centroid tail: the means of the key clusters and the attention state over the clusters a block map leaves out, likewise */
 #include "svg_attn_centroid_tail.h"
+/* ... and that tail merged with the sparse launch's state in the tail kernel's epilogue, 16-bit and fp32 parts, likewise */
+#include "svg_attn_centroid_tail_merged.h"
 /* ... and band attention at head_dim 64 with the row log-sum-exp and with fp32 rows, single mask and device switch, likewise */
 #include "svg_attn_band_lse_d64.h"
 /* ... and variable-block attention with the row log-sum-exp and with fp32 rows from the body variant -1 picks, likewise */

@@ -10,6 +10,8 @@
 //                                   v_mfma_f32_16x16x32, centroid tiles of 64 keys staged by LDS-DMA in two stages (KvImage16,
 //                                   lds_dma16_kv), S^T = K Q^T so that a lane owns query rows and its score accumulators are its P fragment,
 //                                   online softmax against the row's running maximum, fp32 accumulators.
+//   svg_centroid_tail_merged_attention_lse[_f32] (include/svg_attn_centroid_tail_merged.h): the same kernel body with the merge of
+//                                   svg_merge_attention_states[_f32] as its epilogue — TailMergePolicy below.
 // The mask is uniform over a workgroup (no two block-rows share one), so mask and bias are ONE fp32 vector of KC entries in LDS, built once
 // per workgroup: -inf where the map selects the cluster, where the cluster is empty and behind KC, log2 n_c elsewhere — one add per score.
 // A tile whose 64 entries are all -inf costs a wave four LDS reads and a vote.  Every block-row of a head streams the same 2 x KC x 256 bytes
@@ -145,14 +147,136 @@ struct CentroidTailParams {
 
 constexpr int kTailRows = 64;   // query rows per workgroup pass: 4 waves x 16
 
-// grid = (QB, Z, H): workgroup (a, z, h) runs the 64-row sub-tiles z, z + Z, ... of block-row a of head h
+// ---- epilogue policies of centroid_tail_kernel.  At the end of the online softmax lane (g4, n16) of a wave holds, of query row n16 of the
+// wave, the 32 accumulators of columns 16 db + 4 g4 + [0, 4), db < 8, and — after one quad sum — the row sum; the row's running maximum is
+// in all four of its lanes.  A policy says what the lane fetches for its row while the LAST key tile is still to be worked (prefetch: issued
+// at the top of that tile, so the latency of the loads lies behind the tile's QK, softmax and PV) and what it stores (finish).
+
+// svg_centroid_tail_attention_lse: o (contiguous) and lse of the tail alone; nothing is fetched
 template <typename T>
-__global__ __launch_bounds__(256, 2) void centroid_tail_kernel(CentroidTailParams<T> prm) {
+struct TailStorePolicy {
+    using E = Elt<T>;
+    using V4 = typename E::v4;
+    struct Params : CentroidTailParams<T> {};
+    struct Row {};
+    static __device__ __forceinline__ void prefetch(const Params&, Row&, int, int, int) {}
+    static __device__ __forceinline__ void finish(const Params& prm, const Row&, int head, int qrow, int g4, const f32x4 (&acc)[8], float l_tot,
+                                                  float m_run) {
+        const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;   // no key: zeros and -inf
+        T* dst = prm.o + ((size_t)head * prm.Sq + qrow) * 128 + 4 * g4;
+#pragma unroll
+        for (int db = 0; db < 8; ++db) {
+            V4 w;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) w[j] = E::from_float(acc[db][j] * inv);
+            *(V4*)(dst + 16 * db) = w;
+        }
+        if (g4 == 0)
+            prm.lse[(size_t)head * prm.Sq + qrow] = l_tot > 0.f ? 0.6931471805599453f * (m_run + __builtin_amdgcn_logf(l_tot)) : -INFINITY;
+    }
+};
+
+// a * b rounded to T at a stated rounding point.  For fp16 hipcc folds the product into the conversion (v_fma_mixlo / mixhi_f16: the exact
+// product rounded ONCE) for the first and the last element of a vector of rounded products and rounds twice (v_mul_f32, then
+// v_cvt_pk_f16_f32) for the elements between them — in the 4-vectors TailStorePolicy stores and in the 8-vectors merge_states_kernel stores
+// alike; the two differ by one step of fp16 in about one element of 2^15.  The 16-bit merged epilogue owes the bits of those two kernels, so
+// it says per element which rounding it is instead of leaving it to where the element sits in a vector.  bf16 has no folded form.
+template <typename T>
+__device__ __forceinline__ T round_product(float a, float b, bool once) {
+    float p = a * b;
+    if constexpr (std::is_same_v<T, _Float16>) {
+        unsigned lo;   // (the low half is the result)
+        asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(lo) : "v"(a), "v"(b));
+        asm volatile("" : "+v"(p));   // (p stays an fp32 product of its own)
+        const _Float16 twice = (_Float16)p;
+        return once ? __builtin_bit_cast(_Float16, (unsigned short)lo) : twice;
+    } else {
+        return Elt<T>::from_float(p);
+    }
+}
+
+// svg_centroid_tail_merged_attention_lse (F32 = false) / ..._f32 (true): the row is merged with the sparse launch's state of the same row
+// where it stands, in the registers of the wave that owns it, and stored once.  The arithmetic is that of merge_states_kernel /
+// merge_states_f32_kernel (merge_states.hip) for n = 2 in that kernel's operation order, part 0 the sparse state, part 1 the tail:
+//     m = max(l0, l1),  w_i = l_i == -inf ? 0 : exp2((l_i - m) log2 e),  a part with w_i > 0 adds w_i to the weight sum and enters the row —
+//     the first one by w x, the second by fma(w, x, .) —,  o = row / sum rounded to T,  lse = m + ln 2 log2(sum);  no part: zeros and -inf.
+//   F32 = false: part 1 is the tail row ROUNDED to T in registers — the value TailStorePolicy stores — and part 0 a T row: the bits of
+//                svg_centroid_tail_attention_lse followed by svg_merge_attention_states.
+//   F32 = true:  part 1 is the tail row as it leaves the accumulators, part 0 an fp32 row (svg_varblock_attention_lse[_auto]_f32): ONE
+//                rounding between the accumulators of both launches and the merged o.
+// In place: o may be o_sparse and lse may be lse_sparse.  A row's four lanes read exactly the columns they write, all of them in ONE wave,
+// and that wave has waited for its loads (the vmcnt(0) that ends the last tile) before it stores; no other wave touches the row.
+template <typename T, bool F32>
+struct TailMergePolicy {
+    using E = Elt<T>;
+    using V4 = typename E::v4;
+    using X4 = std::conditional_t<F32, f32x4, V4>;
+    struct Params : CentroidTailParams<T> {
+        const void* o_sparse;       // T, addressed as o (F32 = false) / fp32 contiguous [H, Sq, 128] (true)
+        const float* lse_sparse;    // [H, Sq]
+        int hpb_o, o_rs;            // o, and o_sparse where it is 16-bit: the o member of the layout
+        long long o_bs, o_hs;
+    };
+    struct Row {
+        X4 x[8];
+        float l;
+    };
+    static __device__ __forceinline__ size_t o_off(const Params& prm, int head, int qrow, int g4) {
+        return layout_head_off(prm.o_bs, prm.o_hs, prm.hpb_o, head) + (size_t)qrow * prm.o_rs + 4 * g4;
+    }
+    static __device__ __forceinline__ void prefetch(const Params& prm, Row& r, int head, int qrow, int g4) {
+        r.l = prm.lse_sparse[(size_t)head * prm.Sq + qrow];
+        const X4* src;
+        if constexpr (F32) src = (const X4*)((const float*)prm.o_sparse + ((size_t)head * prm.Sq + qrow) * 128 + 4 * g4);
+        else src = (const X4*)((const T*)prm.o_sparse + o_off(prm, head, qrow, g4));
+#pragma unroll
+        for (int db = 0; db < 8; ++db) r.x[db] = src[4 * db];   // (16 columns on)
+    }
+    static __device__ __forceinline__ void finish(const Params& prm, const Row& r, int head, int qrow, int g4, const f32x4 (&acc)[8], float l_tot,
+                                                  float m_run) {
+        // part 1: the tail's state of the row, as TailStorePolicy states it
+        const float inv_t = l_tot > 0.f ? 1.f / l_tot : 0.f;
+        const float l[2] = {r.l, l_tot > 0.f ? 0.6931471805599453f * (m_run + __builtin_amdgcn_logf(l_tot)) : -INFINITY};
+        float m = -INFINITY, w[2], sw = 0.f;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) m = fmaxf(m, l[i]);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            w[i] = (l[i] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((l[i] - m) * 1.4426950408889634f);
+            if (w[i] > 0.f) sw += w[i];   // (false for a NaN too)
+        }
+        // (the two tests are the same for the lanes of a row, not for the rows of a wave: selects, no branches — and a part that does not
+        //  enter is not looked at: whatever its registers hold is selected away)
+        const bool in0 = w[0] > 0.f, in1 = w[1] > 0.f;
+        const float inv = sw > 0.f ? 1.f / sw : 0.f;
+        T* dst = prm.o + o_off(prm, head, qrow, g4);
+#pragma unroll
+        for (int db = 0; db < 8; ++db) {
+            V4 out;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float x[2];
+                if constexpr (F32) x[0] = r.x[db][j], x[1] = acc[db][j] * inv_t;
+                else x[0] = E::to_float(r.x[db][j]), x[1] = E::to_float(round_product<T>(acc[db][j], inv_t, j == 0 || j == 3));   // (the ends of TailStorePolicy's 4-vector)
+                // the first part that enters sets (a -0 stays one), the other adds
+                const float p0 = w[0] * x[0], p1 = w[1] * x[1], both = fmaf(w[1], x[1], p0);
+                const float a = in1 ? (in0 ? both : p1) : (in0 ? p0 : 0.f);
+                if constexpr (F32) out[j] = E::from_float(a * inv);
+                else out[j] = round_product<T>(a, inv, j == ((g4 & 1) ? 3 : 0));   // (columns 0 and 7 of merge_states_kernel's 8-vector)
+            }
+            *(V4*)(dst + 16 * db) = out;
+        }
+        if (g4 == 0) prm.lse[(size_t)head * prm.Sq + qrow] = sw > 0.f ? m + 0.6931471805599453f * __builtin_amdgcn_logf(sw) : -INFINITY;
+    }
+};
+
+// grid = (QB, Z, H): workgroup (a, z, h) runs the 64-row sub-tiles z, z + Z, ... of block-row a of head h
+template <typename T, typename Epi>
+__global__ __launch_bounds__(256, 2) void centroid_tail_kernel(typename Epi::Params prm) {
     constexpr int D = 128;
     using E = Elt<T>;
     using M = Mfma16<T>;
     using V8 = typename E::v8;
-    using V4 = typename E::v4;
     constexpr int KS = D / 32, NDB = D / 16;
     using Img = KvImage16<D>;
     constexpr int kImg = Img::kImg, kStage = Img::kStage;
@@ -225,6 +349,7 @@ __global__ __launch_bounds__(256, 2) void centroid_tail_kernel(CentroidTailParam
         f32x4 acc[NDB];
 #pragma unroll
         for (int db = 0; db < NDB; ++db) acc[db] = f32x4{0.f, 0.f, 0.f, 0.f};
+        typename Epi::Row fetched{};
 
         dma_tile(0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -234,6 +359,7 @@ __global__ __launch_bounds__(256, 2) void centroid_tail_kernel(CentroidTailParam
         __syncthreads();   // (the first pass: the bias vector as well)
         for (int t = 0; t < nT; ++t) {
             if (t + 1 < nT) dma_tile(t + 1);      // into the stage every wave finished reading one barrier ago
+            else if (have) Epi::prefetch(prm, fetched, head, qrow, g4);   // what the epilogue merges with: in flight behind the last tile
             const char* st = smem + (t & 1) * kStage;
             // the lane's 16 bias entries: keys 16 b + 4 g4 + [0, 4) of the tile — the 64 lanes of a wave cover the tile's 64 keys
             f32x4 bs[4];
@@ -317,19 +443,7 @@ __global__ __launch_bounds__(256, 2) void centroid_tail_kernel(CentroidTailParam
         }
         // ---- the row: the four lanes of a row hold 4 + 4 + 4 + 4 keys of every 16-key block; lane (g4, n16) holds d 16 db + 4 g4 + [0, 4) ----
         const float l_tot = quad_group_sum(l_run);
-        if (have) {
-            const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;   // no key: zeros and -inf
-            T* dst = prm.o + ((size_t)head * prm.Sq + qrow) * D + 4 * g4;
-#pragma unroll
-            for (int db = 0; db < NDB; ++db) {
-                V4 w;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) w[j] = E::from_float(acc[db][j] * inv);
-                *(V4*)(dst + 16 * db) = w;
-            }
-            if (g4 == 0)
-                prm.lse[(size_t)head * prm.Sq + qrow] = l_tot > 0.f ? 0.6931471805599453f * (m_run + __builtin_amdgcn_logf(l_tot)) : -INFINITY;
-        }
+        if (have) Epi::finish(prm, fetched, head, qrow, g4, acc, l_tot, m_run);
     }
 }
 
@@ -370,25 +484,33 @@ extern "C" size_t svg_centroid_tail_workspace_bytes(int32_t H, int32_t QB, int32
     return tail_ws_bytes(H, QB);
 }
 
-extern "C" int svg_centroid_tail_attention_lse(const void* q, const void* kbar, const void* vbar, void* o, float* lse, int32_t H, int32_t Sq,
-                                               int32_t KC, int32_t D, int32_t dtype, float sm_scale, const uint8_t* block_map, int32_t map_cols,
-                                               const int32_t* q_sizes, const int32_t* k_sizes, int32_t QB, const int32_t* q_row_idx,
-                                               void* workspace, size_t workspace_bytes, const svg_attn_layout_t* layout, void* stream) {
+// The checks and the launch of the three tail entries.  form 0: svg_centroid_tail_attention_lse (o contiguous); 1 / 2: the merged entries
+// (include/svg_attn_centroid_tail_merged.h; 2: the sparse part as fp32 rows) — o is addressed through the o member of the layout, and the
+// sparse part is looked at behind every check of form 0, in their order.
+static int tail_launch(int form, const void* q, const void* kbar, const void* vbar, const void* o_sparse, const float* lse_sparse, void* o,
+                       float* lse, int32_t H, int32_t Sq, int32_t KC, int32_t D, int32_t dtype, float sm_scale, const uint8_t* block_map,
+                       int32_t map_cols, const int32_t* q_sizes, const int32_t* k_sizes, int32_t QB, const int32_t* q_row_idx, void* workspace,
+                       size_t workspace_bytes, const svg_attn_layout_t* layout, void* stream) {
     if (!q || !kbar || !vbar || !o || !lse || !block_map || !q_sizes || !k_sizes || !workspace) return SVG_ERR_BAD_ARG;
     if (H <= 0 || Sq <= 0 || KC <= 0 || QB <= 0) return SVG_ERR_BAD_ARG;
     if (map_cols < KC) return SVG_ERR_BAD_ARG;
     AttnLayout lay = contiguous_layout(H, H, Sq, KC, D);
-    if (layout) {   // of the caller's layout only heads_per_batch and the q strides are read; they pass the checks of every *_strided entry
+    if (layout) {   // of the caller's layout heads_per_batch, the q strides and — merged forms — the o strides are read; they pass the checks of every *_strided entry
         svg_attn_layout_t abi = *layout;
         const int hpb = abi.heads_per_batch > 0 ? abi.heads_per_batch : 1;
         abi.kv_heads_per_batch = 0;
-        abi.k = abi.v = abi.o = {(int64_t)hpb * D, (int64_t)D, D};
-        if (const int rc = layout_from_abi(&abi, H, H, Sq, 1, D, q, q, q, q, lay); rc != SVG_OK) return rc;
+        abi.k = abi.v = {(int64_t)hpb * D, (int64_t)D, D};
+        if (form == 0) abi.o = abi.k;
+        if (const int rc = layout_from_abi(&abi, H, H, Sq, 1, D, q, q, q, form == 0 ? q : o, lay); rc != SVG_OK) return rc;
     }
     if (workspace_bytes < svg_centroid_tail_workspace_bytes(H, QB, KC)) return SVG_ERR_WORKSPACE;
     if (D != 128 || (dtype != SVG_DTYPE_BF16 && dtype != SVG_DTYPE_F16) || KC > kVbMaxKB) return SVG_ERR_UNSUPPORTED;
     if (Sq >= (1 << 24) || H > 65535) return SVG_ERR_UNSUPPORTED;   // (H: the grid's z extent)
     if ((((size_t)q | (size_t)kbar | (size_t)vbar | (size_t)o | (size_t)workspace) & 15) != 0) return SVG_ERR_UNSUPPORTED;
+    if (form != 0) {
+        if (!o_sparse || !lse_sparse) return SVG_ERR_BAD_ARG;
+        if (((size_t)o_sparse & 15) != 0) return SVG_ERR_UNSUPPORTED;
+    }
     return dispatch_td(dtype, D, [&](auto t, auto d) -> int {
         using T = decltype(t);
         if constexpr (decltype(d)::value != 128) {
@@ -397,18 +519,59 @@ extern "C" int svg_centroid_tail_attention_lse(const void* q, const void* kbar, 
             hipStream_t st = (hipStream_t)stream;
             int32_t* row_start = (int32_t*)workspace;
             hipLaunchKernelGGL(tail_row_start_kernel, dim3(H), dim3(256), 0, st, q_sizes, row_start, QB);
-            CentroidTailParams<T> p;
-            p.q = (const T*)q, p.kbar = (const T*)kbar, p.vbar = (const T*)vbar, p.o = (T*)o, p.lse = lse;
-            p.block_map = block_map, p.q_sizes = q_sizes, p.k_sizes = k_sizes, p.q_row_idx = q_row_idx, p.row_start = row_start;
-            p.Sq = Sq, p.KC = KC, p.QB = QB, p.map_cols = map_cols, p.nT = (KC + kBN - 1) / kBN;
-            p.scale_log2 = sm_scale * 1.4426950408889634f;
-            p.hpb_q = lay.hpb_q, p.q_rs = lay.q_rs, p.q_bs = lay.q_bs, p.q_hs = lay.q_hs;
             // sub-tile slots per block-row: twice what an average block-row needs; a larger one walks its sub-tiles slot by slot, a smaller
             // one's spare workgroups leave at once
             const long long avg = ((long long)Sq + (long long)QB * kTailRows - 1) / ((long long)QB * kTailRows);
             const int Z = (int)std::max<long long>(1, std::min<long long>(2 * avg, 1024));
-            const int lds = 2 * KvImage16<128>::kStage + p.nT * kBN * (int)sizeof(float);
-            return launch_attn(centroid_tail_kernel<T>, dim3(QB, Z, H), 256, lds, st, p);
+            const int nT = (KC + kBN - 1) / kBN;
+            const int lds = 2 * KvImage16<128>::kStage + nT * kBN * (int)sizeof(float);
+            auto fill = [&](CentroidTailParams<T>& p) {
+                p.q = (const T*)q, p.kbar = (const T*)kbar, p.vbar = (const T*)vbar, p.o = (T*)o, p.lse = lse;
+                p.block_map = block_map, p.q_sizes = q_sizes, p.k_sizes = k_sizes, p.q_row_idx = q_row_idx, p.row_start = row_start;
+                p.Sq = Sq, p.KC = KC, p.QB = QB, p.map_cols = map_cols, p.nT = nT;
+                p.scale_log2 = sm_scale * 1.4426950408889634f;
+                p.hpb_q = lay.hpb_q, p.q_rs = lay.q_rs, p.q_bs = lay.q_bs, p.q_hs = lay.q_hs;
+            };
+            auto merged = [&](auto epi) -> int {
+                using Epi = decltype(epi);
+                typename Epi::Params p;
+                fill(p);
+                p.o_sparse = o_sparse, p.lse_sparse = lse_sparse;
+                p.hpb_o = lay.hpb_q, p.o_rs = lay.o_rs, p.o_bs = lay.o_bs, p.o_hs = lay.o_hs;
+                return launch_attn(centroid_tail_kernel<T, Epi>, dim3(QB, Z, H), 256, lds, st, p);
+            };
+            if (form == 1) return merged(TailMergePolicy<T, false>{});
+            if (form == 2) return merged(TailMergePolicy<T, true>{});
+            typename TailStorePolicy<T>::Params p;
+            fill(p);
+            return launch_attn(centroid_tail_kernel<T, TailStorePolicy<T>>, dim3(QB, Z, H), 256, lds, st, p);
         }
     });
+}
+
+extern "C" int svg_centroid_tail_attention_lse(const void* q, const void* kbar, const void* vbar, void* o, float* lse, int32_t H, int32_t Sq,
+                                               int32_t KC, int32_t D, int32_t dtype, float sm_scale, const uint8_t* block_map, int32_t map_cols,
+                                               const int32_t* q_sizes, const int32_t* k_sizes, int32_t QB, const int32_t* q_row_idx,
+                                               void* workspace, size_t workspace_bytes, const svg_attn_layout_t* layout, void* stream) {
+    return tail_launch(0, q, kbar, vbar, nullptr, nullptr, o, lse, H, Sq, KC, D, dtype, sm_scale, block_map, map_cols, q_sizes, k_sizes, QB,
+                       q_row_idx, workspace, workspace_bytes, layout, stream);
+}
+
+extern "C" int svg_centroid_tail_merged_attention_lse(const void* q, const void* kbar, const void* vbar, const void* o_sparse,
+                                                      const float* lse_sparse, void* o, float* lse, int32_t H, int32_t Sq, int32_t KC, int32_t D,
+                                                      int32_t dtype, float sm_scale, const uint8_t* block_map, int32_t map_cols,
+                                                      const int32_t* q_sizes, const int32_t* k_sizes, int32_t QB, const int32_t* q_row_idx,
+                                                      void* workspace, size_t workspace_bytes, const svg_attn_layout_t* layout, void* stream) {
+    return tail_launch(1, q, kbar, vbar, o_sparse, lse_sparse, o, lse, H, Sq, KC, D, dtype, sm_scale, block_map, map_cols, q_sizes, k_sizes, QB,
+                       q_row_idx, workspace, workspace_bytes, layout, stream);
+}
+
+extern "C" int svg_centroid_tail_merged_attention_lse_f32(const void* q, const void* kbar, const void* vbar, const float* o32_sparse,
+                                                          const float* lse_sparse, void* o, float* lse, int32_t H, int32_t Sq, int32_t KC,
+                                                          int32_t D, int32_t dtype, float sm_scale, const uint8_t* block_map, int32_t map_cols,
+                                                          const int32_t* q_sizes, const int32_t* k_sizes, int32_t QB, const int32_t* q_row_idx,
+                                                          void* workspace, size_t workspace_bytes, const svg_attn_layout_t* layout,
+                                                          void* stream) {
+    return tail_launch(2, q, kbar, vbar, o32_sparse, lse_sparse, o, lse, H, Sq, KC, D, dtype, sm_scale, block_map, map_cols, q_sizes, k_sizes, QB,
+                       q_row_idx, workspace, workspace_bytes, layout, stream);
 }

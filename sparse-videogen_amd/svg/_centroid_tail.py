@@ -1,11 +1,12 @@
 """The allocating wrappers of the centroid-tail entries (include/svg_attn_centroid_tail.h: svg_cluster_means,
-svg_centroid_tail_attention_lse), reachable as svg._native.cluster_means / centroid_tail_attention.  A module of its own, like
+svg_centroid_tail_attention_lse) and of its merged forms (include/svg_attn_centroid_tail_merged.h: centroid_tail_attention(merge_with=...)),
+reachable as svg._native.cluster_means / centroid_tail_attention.  A module of its own, like
 svg/_kmeans_e4m3.py: every allocation goes through svg._native.empty, so the wrappers run poisoned under _native.poison_allocations
 (tests/test_gpu_centroid_tail.py checks what they write and what they leave)."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 
@@ -50,7 +51,8 @@ def cluster_means(x: torch.Tensor, sorted_idx: torch.Tensor, counts: torch.Tenso
 
 
 def centroid_tail_attention(q: torch.Tensor, kbar: torch.Tensor, vbar: torch.Tensor, block_map: torch.Tensor, q_sizes: torch.Tensor,
-                            k_sizes: torch.Tensor, q_row_idx: Optional[torch.Tensor] = None, sm_scale: Optional[float] = None):
+                            k_sizes: torch.Tensor, q_row_idx: Optional[torch.Tensor] = None, sm_scale: Optional[float] = None,
+                            merge_with: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, out: Optional[torch.Tensor] = None):
     """The attention state of every query row over the key clusters its block-row's map row does NOT select, each cluster one pseudo key
     (kbar_c, vbar_c) of weight k_sizes[c] (svg_centroid_tail_attention_lse) -> (o, lse): o contiguous of q's shape and dtype, lse fp32 of
     shape q.shape[:-1], natural logarithm, both in the caller's row order — a part for merge_attention_states beside
@@ -59,7 +61,15 @@ def centroid_tail_attention(q: torch.Tensor, kbar: torch.Tensor, vbar: torch.Ten
     kbar, vbar [H, KC, 128] (cluster_means); block_map bool / uint8 [H, QB, C] with C >= KC — only columns [0, KC) are read; q_sizes int32
     [H, QB]; k_sizes int32 [H, KC]; q_row_idx int32 [H, Sq] or None.
     A row whose clusters are all selected or empty: o = 0, lse = -inf.  A row no block-row covers is NOT written (the caller's
-    q_sizes cover every row where k-means made them)."""
+    q_sizes cover every row where k-means made them).
+    merge_with = (o_s, lse_s): the state that varblock_attention(..., return_lse=True) returned for the same rows — the tail is merged with
+    it in the tail kernel's epilogue (include/svg_attn_centroid_tail_merged.h) and (o, lse) is the MERGED state, without a tail output and
+    without a merge launch.  o_s of q's shape; of q's dtype: the bits of centroid_tail_attention followed by merge_attention_states([o_s,
+    o_t], [lse_s, lse_t]) (svg_centroid_tail_merged_attention_lse); float32, contiguous (out_dtype=torch.float32 of the sparse call): one
+    rounding for the merged row (..._lse_f32).  lse_s fp32 contiguous of shape q.shape[:-1].
+    out (with merge_with only): where the merged o goes — of q's shape and dtype, contiguous or any view the attention layout describes
+    (token-major); in the 16-bit form o_s is addressed as out is, so their strides agree, and out may BE o_s: the merge in place.  None: a
+    new contiguous tensor (the 16-bit form then wants a contiguous o_s)."""
     what = "centroid_tail_attention"
     _refuse(what, q.dim() in (3, 4), f"q is [H, Sq, D] or [cfg, H, Sq, D], got {tuple(q.shape)}")
     Sq, D = q.shape[-2], q.shape[-1]
@@ -77,21 +87,42 @@ def centroid_tail_attention(q: torch.Tensor, kbar: torch.Tensor, vbar: torch.Ten
             f"block_map is bool / uint8 [H, QB, >= KC] = [{H}, {QB}, >= {KC}], got {tuple(block_map.shape)} {block_map.dtype}")
     if q_row_idx is not None:
         _refuse(what, q_row_idx.shape == (H, Sq) and q_row_idx.dtype == torch.int32, f"q_row_idx is int32 [H, Sq], got {tuple(q_row_idx.shape)} {q_row_idx.dtype}")
+    f32 = False
+    if merge_with is None:
+        _refuse(what, out is None, "out goes with merge_with: the tail alone writes a new contiguous o")
+    else:
+        o_s, lse_s = merge_with
+        f32 = o_s.dtype == torch.float32
+        _refuse(what, o_s.shape == q.shape and (o_s.dtype == q.dtype or (f32 and o_s.is_contiguous())),
+                f"merge_with: o of q's shape {tuple(q.shape)}, of q's dtype or contiguous float32; got {tuple(o_s.shape)} {o_s.dtype}")
+        _refuse(what, lse_s.shape == q.shape[:-1] and lse_s.dtype == torch.float32 and lse_s.is_contiguous(),
+                f"merge_with: lse is contiguous float32 {tuple(q.shape[:-1])}, got {tuple(lse_s.shape)} {lse_s.dtype}")
+        dst = o_s if out is None and not f32 else out
+        _refuse(what, dst is None or (dst.shape == q.shape and dst.dtype == q.dtype and _native._strided_ok(_native._view4(dst))),
+                f"out of q's shape and dtype, in a layout the attention kernels address; got {None if dst is None else (tuple(dst.shape), dst.dtype, dst.stride())}")
+        _refuse(what, f32 or (o_s.stride() == dst.stride() and (out is not None or o_s.is_contiguous())),
+                "merge_with: the 16-bit o is addressed as out is — equal strides (out=o merges in place); without out, a contiguous o")
     lib = _native.load()
     _native._dev(kbar, vbar, block_map, q_sizes, k_sizes, q_row_idx)
-    _native._gpu(q)
+    _native._gpu(q, out, *(merge_with or ()))
     q4 = _native._view4(q)
+    if not q.is_contiguous() and not _native._strided_ok(q4):
+        q4 = q4.contiguous()
+    o = out if out is not None else _native.empty(q.shape, dtype=q.dtype, device=q.device)
     lay = None
-    if not q.is_contiguous():
-        if _native._strided_ok(q4):
-            lay = C.byref(_native.attn_layout(q4, q4, q4, q4))
-        else:
-            q4 = q4.contiguous()
-    o = _native.empty(q.shape, dtype=q.dtype, device=q.device)
+    if not (q4.is_contiguous() and o.is_contiguous()):
+        lay = C.byref(_native.attn_layout(q4, q4, q4, _native._view4(o)))
     lse = _native.empty(q.shape[:-1], dtype=torch.float32, device=q.device)
     ws = _native.empty(int(lib.svg_centroid_tail_workspace_bytes(H, QB, KC)), dtype=torch.uint8, device=q.device)
-    _native._check(lib.svg_centroid_tail_attention_lse(q4.data_ptr(), kbar.data_ptr(), vbar.data_ptr(), o.data_ptr(), lse.data_ptr(), H, Sq, KC, D,
-                                                       _native._dtype_code(q), _native._sm_scale(sm_scale, D), block_map.data_ptr(),
-                                                       block_map.shape[2], q_sizes.data_ptr(), k_sizes.data_ptr(), QB, _native._ptr(q_row_idx),
-                                                       ws.data_ptr(), ws.numel(), lay, _native._stream()), "svg_centroid_tail_attention_lse")
+    tail = (block_map.data_ptr(), block_map.shape[2], q_sizes.data_ptr(), k_sizes.data_ptr(), QB, _native._ptr(q_row_idx), ws.data_ptr(),
+            ws.numel(), lay, _native._stream())
+    head = (H, Sq, KC, D, _native._dtype_code(q), _native._sm_scale(sm_scale, D))
+    if merge_with is None:
+        _native._check(lib.svg_centroid_tail_attention_lse(q4.data_ptr(), kbar.data_ptr(), vbar.data_ptr(), o.data_ptr(), lse.data_ptr(), *head,
+                                                           *tail), "svg_centroid_tail_attention_lse")
+        return o, lse
+    name = "svg_centroid_tail_merged_attention_lse" + ("_f32" if f32 else "")
+    _native._check(getattr(lib, name)(q4.data_ptr(), kbar.data_ptr(), vbar.data_ptr(), o_s.data_ptr(), lse_s.data_ptr(), o.data_ptr(),
+                                      lse.data_ptr(), *head, *tail), name)
     return o, lse
+

@@ -442,6 +442,17 @@ CENTROID_TAIL_ENTRIES = {
 }
 
 
+# include/svg_attn_centroid_tail_merged.h: the tail launch with the two-part merge as its epilogue, the sparse part 16-bit or fp32 rows, in
+# a table of its own for the same reason (tests/test_centroid_tail_merged_cpu.py; reached through centroid_tail_attention(merge_with=...)
+# of svg/_centroid_tail.py; what it passes is checked on the GPU, in tests/test_gpu_centroid_tail_merged.py)
+_TAIL_MERGED = (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _F32, _VP, _I32, _VP, _VP, _I32, _VP, _VP, _SZ,
+                          C.POINTER(AttnLayout), _VP])
+CENTROID_TAIL_MERGED_ENTRIES = {
+    "svg_centroid_tail_merged_attention_lse": _TAIL_MERGED,
+    "svg_centroid_tail_merged_attention_lse_f32": _TAIL_MERGED,
+}
+
+
 class CopyBox(C.Structure):
     """svg_copy_box_t (include/svg_attn_shard_exchange.h): extent[0] * extent[1] * extent[2] rows of D contiguous elements; offsets and
     strides in elements"""
@@ -480,7 +491,7 @@ def load(strict: bool = True) -> Optional[C.CDLL]:
                                    **PROFILE_SHARD_SIGNATURES, **SAMPLE_ROWS_SIGNATURES, **SHARD_EXCHANGE_SIGNATURES,
                                    **ADAPTIVE_TOP_P_SIGNATURES, **ADAPTIVE_BAND_ENTRIES, **ADAPTIVE_BAND_QUEUE_ENTRIES,
                                    **KMEANS_STEPPED_SIGNATURES, **KMEANS_E4M3_SIGNATURES, **CENTROID_TAIL_ENTRIES, **BAND_LSE_D64_ENTRIES,
-                                   **VARBLOCK_LSE_AUTO_ENTRIES, **KMEANS_METRIC_ENTRIES}.items():
+                                   **VARBLOCK_LSE_AUTO_ENTRIES, **KMEANS_METRIC_ENTRIES, **CENTROID_TAIL_MERGED_ENTRIES}.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -1048,19 +1048,31 @@ def kmeans_clustering(store: CentroidStore, layer_idx: int, q_video, k_video, nu
     return (ql, qc, qs, qit, qidx), (kl, kc, ks, kit, kidx)
 
 
+# svg2_sparse_attention(centroid_tail=True): the merge of the tail with the sparse launch's state in the tail kernel's epilogue
+# (include/svg_attn_centroid_tail_merged.h) instead of a tail output and a merge launch of their own — one launch and two output-sized HBM
+# passes less per layer-call.  True: 16-bit parts, the sparse launch's o merged in place: the bits of the False path.  "f32": the sparse
+# launch hands fp32 rows and the merged row is rounded once (no launch sequence of the False path gives those bits).  False: the launches
+# of before, call for call; whether the default moves is decided on profiles/centroid_tail_ab.jsonl.
+CENTROID_TAIL_MERGED = False
+
+
 def _sparse_plus_centroid_tail(q, k, v, dyn_map, q_sizes, k_sizes, qidx, kidx, tail_k, KC: int, token_major: bool, lse_auto: bool = False):
     """svg2_sparse_attention(centroid_tail=True) from the block map on: the sparse launch in its LSE form into a contiguous head-major
     part, the means of the call's own key clusters, the tail launch into the second part, and the merge — token-major wherever the plain
     call's output would be.  tail_k = (the video keys [cfg, H, V, D], their cluster sizes [cfg * H, KC], their sorted indices [cfg * H, V])
     as the k-means returned them.  lse_auto: the sparse part's state comes from the body the plain call runs (varblock_attention(body="auto")),
-    so the tail merges with it below S = 160 block-rows too.  -> (out, merged lse [cfg, H, S])"""
+    so the tail merges with it below S = 160 block-rows too.  CENTROID_TAIL_MERGED: the tail launch merges in its epilogue, onto the sparse
+    launch's o.  -> (out, merged lse [cfg, H, S])"""
     cfg, H, S, D = q.shape
     QB, KB = q_sizes.shape[-1], k_sizes.shape[-1]
     maps = dyn_map.view(cfg * H, QB, KB).contiguous()
     qsz, rows = q_sizes.view(cfg * H, QB).contiguous(), qidx.contiguous()
+    f32 = CENTROID_TAIL_MERGED == "f32"
+    # (merged: the sparse launch writes where the layer's output goes — token-major wherever the plain call's would be — or fp32 rows)
+    form = {} if not CENTROID_TAIL_MERGED else {"out_dtype": torch.float32} if f32 else {"token_major_out": token_major}
     o_s, lse_s = _native.varblock_attention(q, k, v, maps, qsz, k_sizes.view(cfg * H, KB).contiguous(), q_row_idx=rows,
                                             kv_row_idx=kidx.contiguous(), rows_covered=True, return_lse=True,
-                                            **({"body": "auto"} if lse_auto else {}))
+                                            **({"body": "auto"} if lse_auto else {}), **form)
     kv, ks, kidx_v = tail_k
     V = kv.shape[2]
     ks, kidx_v = ks.reshape(cfg * H, KC).contiguous(), kidx_v.reshape(cfg * H, V).contiguous()
@@ -1069,6 +1081,10 @@ def _sparse_plus_centroid_tail(q, k, v, dyn_map, q_sizes, k_sizes, qidx, kidx, t
     if KB != KC:   # HunyuanVideo: the last block-row — the unused prompt — selects nothing but itself; its rows get no tail
         maps = maps.clone()
         maps[:, -1, :] = True
+    if CENTROID_TAIL_MERGED:   # the merge in the tail kernel's epilogue, onto the sparse launch's o (fp32 parts: into a new o, rounded once)
+        out = o_s if not f32 else _native.token_major_empty(q) if token_major else None
+        o, lse = _native.centroid_tail_attention(q, kbar, vbar, maps, qsz, ks, q_row_idx=rows, merge_with=(o_s, lse_s), out=out)
+        return o.reshape(cfg, H, S, D), lse.reshape(cfg, H, S)
     o_t, lse_t = _native.centroid_tail_attention(q, kbar, vbar, maps, qsz, ks, q_row_idx=rows)
     return _native.merge_attention_states([o_s.reshape(cfg, H, S, D), o_t.reshape(cfg, H, S, D)],
                                           [lse_s.reshape(cfg, H, S), lse_t.reshape(cfg, H, S)], token_major_out=token_major, return_lse=True)

@@ -13,6 +13,9 @@ Per workload, at top_p 0.9 / 0.8 / 0.7 (min_kc_ratio 0.1), one JSON line each:
     window of either side (svg._native.ClockProbe; null where the counters do not move);
   * the quality probe's figures of that call off and on (svg2_sparse_attention(quality=...): kept mass, rel. L2 against dense attention
     on 64 sampled rows per head, density), from the same seeds;
+at top_p 0.9 two "layer_call_merged" lines: the option on both sides, A = its three launches (sparse, tail, merge), B = the merge in the tail
+kernel's epilogue (svg.models._core.CENTROID_TAIL_MERGED: 16-bit parts in place — same_bits says whether B's output equals A's —, then fp32
+parts), the same alternating windows and clocks;
 and at top_p 0.9 a "stages" line: the operands of one call captured, then every launch of the option alone — the sparse launch in its
 plain and in its LSE form, the two svg_cluster_means, the tail launch, the merge — ms per call over three windows, the tail's algorithmic
 TFLOP/s (4 S KC D H: every centroid, selected or not) beside the sparse launch's (4 S^2 D H x density), and the clock of the tail launch.
@@ -138,6 +141,29 @@ def main():
                             "a_clock_mhz": clock_of(nat, dev, fa, calls), "b_clock_mhz": clock_of(nat, dev, fb, calls)})
                 results[top_p] = rec
                 emit(rec)
+                del sa, sb
+
+            # ---- the merge in the tail kernel's epilogue (svg.models._core.CENTROID_TAIL_MERGED) against the option's own three launches ----
+            for form, label in ((True, "16-bit parts, the sparse o merged in place"), ("f32", "fp32 sparse rows, one rounding")):
+                sa, sb = warm_store(), warm_store()
+                fa = lambda: layer_call(sa, TOP_PS[0], True)   # noqa: E731
+
+                def fb():
+                    _core.CENTROID_TAIL_MERGED = form
+                    try:
+                        return layer_call(sb, TOP_PS[0], True)
+                    finally:
+                        _core.CENTROID_TAIL_MERGED = False
+
+                same = bool(torch.equal(fa(), fb()))
+                wa, wb, calls = alternate(fa, fb, alternations, min_ms)
+                a_ms, b_ms = sum(wa) / len(wa), sum(wb) / len(wb)
+                emit(dict(base, what="layer_call_merged", top_p=TOP_PS[0], a="centroid_tail on: sparse, tail, merge (CENTROID_TAIL_MERGED off)",
+                          b=f"centroid_tail on, merged in the tail's epilogue: {label}", form="f32" if form == "f32" else "16-bit",
+                          same_bits=same, alternations=alternations, calls_per_window=calls, a_ms=round(a_ms, 4), b_ms=round(b_ms, 4),
+                          a_windows=r4(wa), b_windows=r4(wb), a_spread_ms=round(max(wa) - min(wa), 4), b_spread_ms=round(max(wb) - min(wb), 4),
+                          saved_ms=round(a_ms - b_ms, 4), b_over_a=round(b_ms / a_ms, 4), a_clock_mhz=clock_of(nat, dev, fa, calls),
+                          b_clock_mhz=clock_of(nat, dev, fb, calls)))
                 del sa, sb
 
             # ---- the launches of the option one by one, on the operands of one call at top_p 0.9 ----
