@@ -813,6 +813,8 @@ int svg_debug_wg_trace(uint64_t* out, int32_t n_workgroups);
 #include "svg_attn_varblock_lse_auto.h"
 /* ... and flash-kmeans by direction: the cosine and dot-product assignment, update and Lloyd loop, likewise */
 #include "svg_attn_kmeans_metric.h"
+/* ... and that shard form of band attention on shards of any contiguous range of the video's rows (balanced ranks), likewise */
+#include "svg_attn_band_row_shard.h"
 /* ... and the per-head band launch below and its device switch as resident workgroups on the work queue, with the order on the host, likewise */
 #include "svg_attn_band_per_head_queue.h"
 /* ... and SVG1's per-head band width: band attention from a device vector of bands, its device switch and the controller step, likewise */

@@ -82,6 +82,8 @@ constexpr int kTailLds = 16;                 // bytes behind the stages: the que
 //   BandShardLsePolicy / BandShardF32Policy        svg_band_shard_attention_lse[_f32]: a frame shard of the rows over a frame shard of the keys,
 //                                                  heads in logical order and token-major heads in one launch, the mask at the coordinates the
 //                                                  shard maps give, over the q-tiles of the q shard
+//   BandRowShardLsePolicy / BandRowShardF32Policy  svg_band_row_shard_attention_lse[_f32]: the same launch on shards of any contiguous rows of the
+//                                                  video — the three-piece maps of BandRowShardMap, a row cursor that walks one piece at a time
 // The same template arguments of the body for all of them, SPEC and the replay counter included, so o keeps the bits of the plain entry — also
 // where a window or two shards are the whole sequence.  A q-tile that fails its validation returns before the epilogue and stores nothing
 // (neither o nor lse nor o32); its replay stores them all.
@@ -492,9 +494,10 @@ static BandCall band_alt_call(const BandCall& c, svg_perm_desc_t& pm) {
 // not count completions (band_queue_decision), else to the static mapping over its q-tiles.
 template <typename T, typename Pol, bool PRE = false>
 static int launch_band_m16(const BandCall& c) {
-    // (only what is launched is instantiated: the window forms have no device switch; the fp32, window and shard forms have no queue)
+    // (only what is launched is instantiated: the window and row-shard forms have no device switch; the fp32, window and shard forms have no queue)
     constexpr bool kWindow = std::is_same_v<Pol, BandWindowLsePolicy<T>> || std::is_same_v<Pol, BandWindowF32Policy<T>>;
-    constexpr bool kShard = std::is_same_v<Pol, BandShardLsePolicy<T>> || std::is_same_v<Pol, BandShardF32Policy<T>>;
+    constexpr bool kRowShard = std::is_same_v<Pol, BandRowShardLsePolicy<T>> || std::is_same_v<Pol, BandRowShardF32Policy<T>>;
+    constexpr bool kShard = kRowShard || std::is_same_v<Pol, BandShardLsePolicy<T>> || std::is_same_v<Pol, BandShardF32Policy<T>>;
     constexpr bool kQueue = std::is_same_v<Pol, BandPolicy<T, 128, 8>> || std::is_same_v<Pol, BandLsePolicy<T>>;
     auto params = [](const BandCall& b) {
         if constexpr (kWindow) return make_band_window_params<Pol, T>(b);
@@ -504,7 +507,7 @@ static int launch_band_m16(const BandCall& c) {
     const int lds = attn_m16_lds_bytes() + kTailLds;
     const hipStream_t st = c.stream;
     const typename Pol::Params p = params(c);
-    if constexpr (!kWindow) {
+    if constexpr (!kWindow && !kRowShard) {
         if (c.use_alt) {
             svg_perm_desc_t pm;
             const typename Pol::Params b = params(band_alt_call(c, pm));
@@ -578,6 +581,14 @@ static const svg_attn_layout_t* band_f32_stand_in(BandCall& c, svg_attn_layout_t
 static int check_band_shard(const svg_band_shard_t* s, int32_t S, const svg_perm_desc_t* perm) {
     return check_frame_shard(s, S, perm->vid0, perm->num_frame, perm->frame_size);
 }
+// a row shard (include/svg_attn_band_row_shard.h): its rows inside the video, its tail behind it, not empty
+static int check_band_row_shard(const svg_band_row_shard_t* s, int32_t S, const svg_perm_desc_t* perm) {
+    const int64_t V = (int64_t)perm->num_frame * perm->frame_size, vend = perm->vid0 + V;
+    if (s->row0 < 0 || s->n_rows < 0 || (int64_t)s->row0 + s->n_rows > V || s->n_tail < 0) return SVG_ERR_BAD_ARG;
+    if (s->n_tail > 0 && (s->tail_begin < vend || (int64_t)s->tail_begin + s->n_tail > S)) return SVG_ERR_BAD_ARG;
+    if (s->n_rows == 0 && s->n_tail == 0) return SVG_ERR_BAD_ARG;
+    return SVG_OK;
+}
 static int check_band_shard_geometry(int32_t S, const svg_perm_desc_t* perm) {
     if (S <= 0 || perm->num_frame <= 0 || perm->frame_size <= 0 || perm->vid0 < 0 ||
         (int64_t)perm->vid0 + (int64_t)perm->num_frame * perm->frame_size > S)
@@ -598,6 +609,11 @@ static int band_check_call(BandCall& c) {
         rc = check_band_shard_geometry(c.S, c.perm);
         if (rc == SVG_OK) rc = check_band_shard(c.q_shard, c.S, c.perm);
         if (rc == SVG_OK) rc = check_band_shard(c.k_shard, c.S, c.perm);
+    } else if (c.form == kBandRowShard) {   // the same, on row shards
+        if (!c.perm || !c.q_rows || !c.k_rows) return SVG_ERR_BAD_ARG;
+        rc = check_band_shard_geometry(c.S, c.perm);
+        if (rc == SVG_OK) rc = check_band_row_shard(c.q_rows, c.S, c.perm);
+        if (rc == SVG_OK) rc = check_band_row_shard(c.k_rows, c.S, c.perm);
     } else if (c.form == kBandWindow) {
         if (c.win_Sq <= 0 || c.win_Sk <= 0 || c.q_begin < 0 || c.k_begin < 0 || (int64_t)c.q_begin + c.win_Sq > c.S ||
             (int64_t)c.k_begin + c.win_Sk > c.S)
@@ -635,6 +651,8 @@ static int band_run(BandCall c) {
                 switch (c.form) {
                     case kBandWindow: return c.o32 ? launch_band_m16<T, BandWindowF32Policy<T>>(c) : launch_band_m16<T, BandWindowLsePolicy<T>>(c);
                     case kBandShard: return c.o32 ? launch_band_m16<T, BandShardF32Policy<T>>(c) : launch_band_m16<T, BandShardLsePolicy<T>>(c);
+                    case kBandRowShard:
+                        return c.o32 ? launch_band_m16<T, BandRowShardF32Policy<T>>(c) : launch_band_m16<T, BandRowShardLsePolicy<T>>(c);
                     case kBandPerHead: return launch_band_per_head<T>(c);
                     default: return c.o32 ? launch_band_m16<T, BandF32Policy<T>>(c) : launch_band_m16<T, BandLsePolicy<T>>(c);
                 }
@@ -824,6 +842,40 @@ extern "C" int32_t svg_debug_band_shard_map(const svg_perm_desc_t* perm, int32_t
     for (int i = 0; i < n; ++i) {
         if (g_out) g_out[i] = m.g(perm->vid0, perm->num_frame, perm->frame_size, token_major != 0, x[i]);
         if (ginv_out) ginv_out[i] = m.ginv(perm->vid0, perm->num_frame, perm->frame_size, token_major != 0, x[i]);
+    }
+    return n;
+}
+
+// The row-shard entries (include/svg_attn_band_row_shard.h): the shard entries above on shards of any rows of the video.
+extern "C" int svg_band_row_shard_attention_lse(const void* q, const void* k, const void* v, void* o, float* lse, int32_t BH, int32_t S,
+                                                int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
+                                                const svg_perm_desc_t* perm, const svg_band_row_shard_t* q_shard,
+                                                const svg_band_row_shard_t* k_shard, const svg_attn_layout_t* layout, void* stream) {
+    if (!lse) return SVG_ERR_BAD_ARG;
+    BandCall c{q, k, v, o, BH, S, D, dtype, sm_scale, mask, perm, layout, (hipStream_t)stream};
+    c.lse = lse, c.form = kBandRowShard, c.q_rows = q_shard, c.k_rows = k_shard;
+    return band_run(c);
+}
+
+extern "C" int svg_band_row_shard_attention_lse_f32(const void* q, const void* k, const void* v, float* o32, float* lse, int32_t BH, int32_t S,
+                                                    int32_t D, int32_t dtype, float sm_scale, const svg_band_mask_t* mask,
+                                                    const svg_perm_desc_t* perm, const svg_band_row_shard_t* q_shard,
+                                                    const svg_band_row_shard_t* k_shard, const svg_attn_layout_t* layout, void* stream) {
+    if (!o32 || !lse) return SVG_ERR_BAD_ARG;
+    BandCall c{q, k, v, nullptr, BH, S, D, dtype, sm_scale, mask, perm, layout, (hipStream_t)stream};
+    c.lse = lse, c.o32 = o32, c.form = kBandRowShard, c.q_rows = q_shard, c.k_rows = k_shard;
+    return band_run(c);
+}
+
+extern "C" int32_t svg_debug_band_row_shard_map(const svg_perm_desc_t* perm, int32_t S, const svg_band_row_shard_t* shard, int32_t token_major,
+                                                const int32_t* x, int32_t n, int32_t* g_out, int32_t* ginv_out, int32_t* phys_out) {
+    if (!perm || !shard || !x || n < 0 || check_band_shard_geometry(S, perm) != SVG_OK || check_band_row_shard(shard, S, perm) != SVG_OK)
+        return -1;
+    const BandRowShardMap m = svg::make_band_row_shard_map(*shard, perm->vid0, perm->num_frame, perm->frame_size);
+    for (int i = 0; i < n; ++i) {
+        if (g_out) g_out[i] = m.g(perm->vid0, perm->num_frame, perm->frame_size, token_major != 0, x[i]);
+        if (ginv_out) ginv_out[i] = m.ginv(perm->vid0, perm->num_frame, perm->frame_size, token_major != 0, x[i]);
+        if (phys_out) phys_out[i] = m.phys(perm->frame_size, token_major != 0, x[i]);
     }
     return n;
 }

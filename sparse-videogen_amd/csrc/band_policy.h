@@ -14,7 +14,7 @@ namespace svg {
 // One band call, from its entry to its launch (no process- or thread-global state): what every svg_band_attention* entry is given, in the
 // entries' order, then what single entries add.  An entry fills one and hands it to band_run (attention.hip); the parameter builders below
 // and the launchers read it.
-enum BandForm : int { kBandWhole = 0, kBandWindow, kBandShard, kBandPerHead };
+enum BandForm : int { kBandWhole = 0, kBandWindow, kBandShard, kBandPerHead, kBandRowShard };
 struct BandCall {
     const void *q = nullptr, *k = nullptr, *v = nullptr;
     void* o = nullptr;         // (the *_f32 entries leave it null: band_run puts a stand-in of o32 here)
@@ -45,14 +45,22 @@ struct BandCall {
     // kBandShard (with lse): q / o / lse / o32 hold the rows of q_shard, k / v those of k_shard (BandShardOf)
     const svg_band_shard_t* q_shard = nullptr;
     const svg_band_shard_t* k_shard = nullptr;
+    // kBandRowShard (with lse): the same on shards of any rows of the video (BandRowShardOf, include/svg_attn_band_row_shard.h)
+    const svg_band_row_shard_t* q_rows = nullptr;
+    const svg_band_row_shard_t* k_rows = nullptr;
     // kBandPerHead (with lse): one band per head (BandPerHeadLsePolicy), on the work queue where `queue` is set and a queue is to be had
     const int32_t* band = nullptr;
     bool queue = false;
 
     // rows of q / o and of k / v: the window's, the (checked) shard's of the video `perm` describes, or S
     static int shard_rows(const svg_band_shard_t* s, const svg_perm_desc_t* perm) { return perm->frame_size * s->n_frames + s->n_tail; }
-    int Sq() const { return form == kBandWindow ? win_Sq : form == kBandShard ? shard_rows(q_shard, perm) : S; }
-    int Sk() const { return form == kBandWindow ? win_Sk : form == kBandShard ? shard_rows(k_shard, perm) : S; }
+    static int shard_rows(const svg_band_row_shard_t* s) { return s->n_rows + s->n_tail; }
+    int Sq() const {
+        return form == kBandWindow ? win_Sq : form == kBandShard ? shard_rows(q_shard, perm) : form == kBandRowShard ? shard_rows(q_rows) : S;
+    }
+    int Sk() const {
+        return form == kBandWindow ? win_Sk : form == kBandShard ? shard_rows(k_shard, perm) : form == kBandRowShard ? shard_rows(k_rows) : S;
+    }
 };
 
 // the mask and the head permutation of a band call over S rows (mask != nullptr)
@@ -831,15 +839,79 @@ struct BandShardMap {
     }
 };
 
-template <typename BasePol>
-struct BandShardOf : BasePol {
+// Row shards (svg_band_row_shard_attention_lse[_f32], include/svg_attn_band_row_shard.h): the video rows [row0, row0 + nv) of the frame-major
+// video, any contiguous range, and the tail.  A head in logical order keeps g(l) = vid0 + row0 + l.  A token-major head takes the shard's rows
+// (f, p) in the order of (p, f), and with a = row0 % P, fa = row0 / P, e = row0 + nv, fb = (e - 1) / P, b = e - fb * P position p owns the
+// frames fa + (p < a) .. fb - (p >= b): the positions fall into at most three PIECES [pb, pb') with one frame count c and one first frame fs
+// each — [0, min(a, b)), [min, max), [max, P) — so that inside a piece the order is the fused placement of a video of c frames:
+//   g(l)     the piece of l (two compares against the pieces' first indices L), r = l - L, pp = r / c: position pb + pp, frame fs + r % c,
+//            mask row vid0 + (pb + pp) * F + fs + r % c, read from local row (fs + r % c) * P + pb + pp - row0 — one division, as the whole-frame map;
+//   ginv(x)  position x / F, its piece (two compares against the breakpoints), L + (p - pb) * c + clamp(x % F - fs, 0, c) — one division by F.
+// The pieces are launch constants (make_band_row_shard_map); a piece may be empty or hold positions without a frame (c = 0: a shard inside one
+// frame).  The row cursor of a token-major head walks ONE piece at a time: inside a piece the cheap step of the base holds with the piece's
+// constants — step 64 / c + (64 % c) * P, and with phys + row0 = f * P + p the frame index has wrapped exactly when phys >= (fs + c) * P - row0:
+// add 1 - c * P — for a tile that lies in the piece together with the tile before it.  Every other tile takes the exact path, which already
+// is a branch of its own, and only there the constants of the tile's piece are loaded (BandRowShardOf::row_walk_next): the tile-to-tile path
+// keeps the instructions of the whole-frame form.  A whole-frame shard is one piece [0, P) and gives the whole-frame map value for value.
+struct BandRowShardMap {
+    int row0, nv, n, tail_begin;   // video rows [row0, row0 + nv) counted from vid0; n rows in all, the tail = global rows [tail_begin, ..)
+    // piece j: positions [pb[j], pb[j + 1]) (pb[0] = 0, pb[3] = P) of c[j] frames from frame fs[j], local indices [L[j], L[j + 1]) (L[0] = 0,
+    // L[3] = nv); sp[j]: physical-row step of a 64-row tile.  (Scalars, not arrays: kernel arguments indexed at run time go through scratch.)
+    int pb1, pb2, L1, L2;
+    int c0, c1, c2, fs0, fs1, fs2, sp0, sp1, sp2;
+    struct Piece {
+        int L, Lend, pb, c, fs, sp;
+    };
+    // (every constant is read before the selects: a select between two reads becomes a read through a per-lane address of the arguments)
+    __host__ __device__ __forceinline__ Piece piece(bool in1, bool in2) const {
+        const int l1 = L1, l2 = L2, le = nv, p1 = pb1, p2 = pb2, n0 = c0, n1 = c1, n2 = c2;
+        const int f0 = fs0, f1 = fs1, f2 = fs2, s0 = sp0, s1 = sp1, s2 = sp2;
+        return {in2 ? l2 : in1 ? l1 : 0, in2 ? le : in1 ? l2 : l1, in2 ? p2 : in1 ? p1 : 0,
+                in2 ? n2 : in1 ? n1 : n0, in2 ? f2 : in1 ? f1 : f0, in2 ? s2 : in1 ? s1 : s0};
+    }
+    // (an empty piece is never picked for an index below nv: the next one starts at the same index)
+    __host__ __device__ __forceinline__ Piece piece_of_index(int l) const { return piece(l >= L1, l >= L2); }
+    // position and frame of local index l < nv of a token-major head
+    __host__ __device__ __forceinline__ void pos_frame(int l, int& p, int& f) const {
+        using std::max;
+        const Piece pc = piece_of_index(l);
+        const int r = l - pc.L, pp = (int)((unsigned)r / (unsigned)max(pc.c, 1));
+        p = pc.pb + pp, f = pc.fs + r - pp * pc.c;
+    }
+    __host__ __device__ __forceinline__ int g(int vid0, int F, int P, int kind, int l) const {
+        int p, f;
+        pos_frame(l, p, f);
+        const int gv = kind ? vid0 + p * F + f : vid0 + row0 + l;
+        return l < nv ? gv : tail_begin + (l - nv);
+    }
+    __host__ __device__ __forceinline__ int ginv(int vid0, int F, int P, int kind, int x) const {
+        using std::max;
+        using std::min;
+        const int y = x - vid0, yc = max(y, 0);
+        const int p = (int)((unsigned)yc / (unsigned)F), r = yc - p * F;
+        const Piece pc = piece(p >= pb1, p >= pb2);
+        const int l1 = pc.L + (min(p, P) - pc.pb) * pc.c + min(max(r - pc.fs, 0), pc.c);
+        const int lv = min(kind ? l1 : max(y - row0, 0), nv);
+        const int lt = nv + min(max(x - tail_begin, 0), n - nv);
+        return lv < nv ? lv : lt;
+    }
+    __host__ __device__ __forceinline__ int phys(int P, int kind, int l) const {
+        int p, f;
+        pos_frame(l, p, f);
+        return (kind && l < nv) ? f * P + p - row0 : l;
+    }
+};
+
+// the shard policy over a pair of maps of one kind: BandShardMap (whole frames) or BandRowShardMap (any rows)
+template <typename BasePol, typename Map>
+struct BandShardBody : BasePol {
     using RowWalk = typename BasePol::RowWalk;
     static constexpr bool kTileRun = false;   // classify and row_walk_next are this policy's own: the per-tile decisions stay
     struct Ctx : BasePol::Ctx {
         int gw0, gw1;   // per WAVE: the coordinates of its rows lie in [gw0, gw1) (gw0 >= gw1: an idle wave)
     };
     struct Params : BasePol::Params {
-        BandShardMap qs, ks;                       // what q / o / lse / o32 hold, what k / v hold
+        Map qs, ks;                                // what q / o / lse / o32 hold, what k / v hold
         int reg1_lo[4], reg1_hi[4], reg1_t0[4];    // row regions of the token-major heads (reg_* of the base: heads in logical order)
     };
     static __device__ __forceinline__ int gq(const Params& p, const Ctx& c, int l) { return p.qs.g(p.vid0, p.F, p.P, c.perm, l); }
@@ -933,33 +1005,6 @@ struct BandShardOf : BasePol {
         const int l = c.q0 + row;
         return l < c.q_end ? p.qs.phys(p.P, c.perm, l) : -1;
     }
-    // the row cursor over the k shard: the base's walk on a video of Fl frames at local row 0 (cheap step of a token-major head: the tile and
-    // the one before it inside the shard's video rows; of a head in logical order: inside the shard)
-    static __device__ __forceinline__ void row_walk_init(const Params& p, const Ctx& c, RowWalk& w) {
-        const bool perm = c.perm != 0;
-        w.perm = perm;
-        w.lo = perm ? kBN : -(1 << 30);
-        w.hi = (perm ? p.ks.nv : p.ks.n) - kBN;
-        w.step = perm ? p.ks.sp64 : kBN, w.end = p.ks.nv, w.unwrap = 1 - p.ks.nv;
-        w.vlen = perm ? p.ks.nv : 0;
-        w.prev_k0 = -(1 << 30);
-        asm volatile("" : "+v"(w.step), "+v"(w.unwrap));   // (as the base keeps them: see BandPolicy::row_walk_init)
-        w.perm = __builtin_amdgcn_readfirstlane(w.perm);
-        asm volatile("" : "+s"(w.perm));
-    }
-    // local key index -> local physical row (`vlen`: the shard's video rows on a token-major head, 0 otherwise); a key behind the shard is
-    // masked and never read: the redirect goes to the shard's first row
-    static __device__ __forceinline__ int row_exact(const Params& p, int vlen, int l) {
-        const int pp = (int)((unsigned)l / (unsigned)p.ks.fdiv), fl = l - pp * p.ks.fdiv;
-        const int phys = (unsigned)l < (unsigned)vlen ? fl * p.P + pp : l;
-        return l < p.ks.n ? phys : 0;
-    }
-    static __device__ __forceinline__ void row_walk_next(const Params& p, RowWalk& w, int& phys, int k0, int row) {
-        const bool cheap = BasePol::row_walk_cheap(w, k0);
-        BasePol::row_add(phys, w.step);
-        if (w.perm) BasePol::row_add(phys, phys >= w.end ? w.unwrap : 0);
-        if (__builtin_expect(!cheap, 0)) BasePol::row_set(phys, row_exact(p, w.vlen, k0 + row));
-    }
     // FULL only where it is proven for the hulls of the wave's rows and of the tile's keys; everything else is masked element by element
     static __device__ __forceinline__ int classify(const Params& p, const Ctx& c, int k0, int) {
         if (k0 >= c.fk_lo && k0 <= c.fk_hi) return TILE_FULL;
@@ -987,11 +1032,98 @@ struct BandShardOf : BasePol {
     }
     static __device__ __forceinline__ float* lse_base(const Params& p, const Ctx& c) { return p.lse + (size_t)c.head * (size_t)p.qs.n; }
 };
+// whole-frame shards, and their row cursor over the k shard: the base's walk on a video of Fl frames at local row 0 (cheap step of a token-major
+// head: the tile and the one before it inside the shard's video rows; of a head in logical order: inside the shard)
+template <typename BasePol>
+struct BandShardOf : BandShardBody<BasePol, BandShardMap> {
+    using Body = BandShardBody<BasePol, BandShardMap>;
+    using Params = typename Body::Params;
+    using Ctx = typename Body::Ctx;
+    using RowWalk = typename Body::RowWalk;
+    static __device__ __forceinline__ void row_walk_init(const Params& p, const Ctx& c, RowWalk& w) {
+        const bool perm = c.perm != 0;
+        w.perm = perm;
+        w.lo = perm ? kBN : -(1 << 30);
+        w.hi = (perm ? p.ks.nv : p.ks.n) - kBN;
+        w.step = perm ? p.ks.sp64 : kBN, w.end = p.ks.nv, w.unwrap = 1 - p.ks.nv;
+        w.vlen = perm ? p.ks.nv : 0;
+        w.prev_k0 = -(1 << 30);
+        asm volatile("" : "+v"(w.step), "+v"(w.unwrap));   // (as the base keeps them: see BandPolicy::row_walk_init)
+        w.perm = __builtin_amdgcn_readfirstlane(w.perm);
+        asm volatile("" : "+s"(w.perm));
+    }
+    // local key index -> local physical row (`vlen`: the shard's video rows on a token-major head, 0 otherwise); a key behind the shard is
+    // masked and never read: the redirect goes to the shard's first row
+    static __device__ __forceinline__ int row_exact(const Params& p, int vlen, int l) {
+        const int pp = (int)((unsigned)l / (unsigned)p.ks.fdiv), fl = l - pp * p.ks.fdiv;
+        const int phys = (unsigned)l < (unsigned)vlen ? fl * p.P + pp : l;
+        return l < p.ks.n ? phys : 0;
+    }
+    static __device__ __forceinline__ void row_walk_next(const Params& p, RowWalk& w, int& phys, int k0, int row) {
+        const bool cheap = BasePol::row_walk_cheap(w, k0);
+        BasePol::row_add(phys, w.step);
+        if (w.perm) BasePol::row_add(phys, phys >= w.end ? w.unwrap : 0);
+        if (__builtin_expect(!cheap, 0)) BasePol::row_set(phys, row_exact(p, w.vlen, k0 + row));
+    }
+};
+// Row shards, and their row cursor.  A head in logical order steps by the tile inside the shard.  A token-major head walks ONE PIECE of the k
+// shard's map at a time (BandRowShardMap): it starts without a piece — no first key admits the cheap step — and every tile of the exact
+// path, the q-tile's first one included, loads the constants of the piece it starts in, so the next tile takes the cheap step where it ends
+// inside that piece: phys += step and, the frame index having wrapped, += unwrap — inside a position the cursor moves by P, at a position's
+// last frame it jumps back to the piece's first frame of the next position.  The tile-to-tile path is that of the whole-frame form,
+// instruction for instruction; what a piece boundary costs is scalar work on the exact path, which is a branch of its own already.
+template <typename BasePol>
+struct BandRowShardOf : BandShardBody<BasePol, BandRowShardMap> {
+    using Body = BandShardBody<BasePol, BandRowShardMap>;
+    using Params = typename Body::Params;
+    using Ctx = typename Body::Ctx;
+    using RowWalk = typename Body::RowWalk;
+    static __device__ __forceinline__ void row_walk_init(const Params& p, const Ctx& c, RowWalk& w) {
+        const bool perm = c.perm != 0;
+        w.perm = perm;
+        w.lo = perm ? (1 << 30) : -(1 << 30);
+        w.hi = perm ? -(1 << 30) : p.ks.n - kBN;
+        w.step = kBN, w.end = p.ks.nv, w.unwrap = 0;
+        w.vlen = perm ? p.ks.nv : 0;
+        w.prev_k0 = -(1 << 30);
+        asm volatile("" : "+v"(w.step), "+v"(w.unwrap));   // (as the base keeps them: see BandPolicy::row_walk_init)
+        w.perm = __builtin_amdgcn_readfirstlane(w.perm);
+        asm volatile("" : "+s"(w.perm));
+    }
+    static __device__ __forceinline__ int row_exact(const Params& p, int vlen, int l) {
+        int pos, f;
+        p.ks.pos_frame(l, pos, f);
+        const int phys = (unsigned)l < (unsigned)vlen ? f * p.P + pos - p.ks.row0 : l;
+        return l < p.ks.n ? phys : 0;
+    }
+    static __device__ __forceinline__ void row_walk_next(const Params& p, RowWalk& w, int& phys, int k0, int row) {
+        const bool cheap = BasePol::row_walk_cheap(w, k0);
+        BasePol::row_add(phys, w.step);
+        if (w.perm) BasePol::row_add(phys, phys >= w.end ? w.unwrap : 0);
+        if (__builtin_expect(!cheap, 0)) {
+            BasePol::row_set(phys, row_exact(p, w.vlen, k0 + row));
+            if (w.perm) {   // the piece the tile at k0 starts in (k0 behind the video rows: the last piece, which admits no cheap step there)
+                const BandRowShardMap::Piece pc = p.ks.piece_of_index(k0);
+                w.lo = pc.L + kBN, w.hi = pc.Lend - kBN;
+                w.step = pc.sp, w.end = (pc.fs + pc.c) * p.P - p.ks.row0, w.unwrap = 1 - pc.c * p.P;
+            }
+        }
+    }
+};
 template <typename T>
 using BandShardLsePolicy = BandShardOf<BandLsePolicy<T>>;
 template <typename T>
 struct BandShardF32Policy : BandShardOf<BandF32Policy<T>> {
     using Base = BandShardOf<BandF32Policy<T>>;
+    static __device__ __forceinline__ float* o32_base(const typename Base::Params& p, const typename Base::Ctx& c) {
+        return p.o32 + (size_t)c.head * (size_t)p.qs.n * 128;
+    }
+};
+template <typename T>
+using BandRowShardLsePolicy = BandRowShardOf<BandLsePolicy<T>>;
+template <typename T>
+struct BandRowShardF32Policy : BandRowShardOf<BandF32Policy<T>> {
+    using Base = BandRowShardOf<BandF32Policy<T>>;
     static __device__ __forceinline__ float* o32_base(const typename Base::Params& p, const typename Base::Ctx& c) {
         return p.o32 + (size_t)c.head * (size_t)p.qs.n * 128;
     }
@@ -1228,6 +1360,26 @@ inline BandShardMap make_band_shard_map(const svg_band_shard_t& s, int vid0, int
     m.sp64 = kBN / m.fdiv + (kBN % m.fdiv) * P;
     return m;
 }
+// ... of a row-shard launch (BandRowShardOf): the three pieces of the token-major order, once per launch
+inline BandRowShardMap make_band_row_shard_map(const svg_band_row_shard_t& s, int vid0, int F, int P) {
+    BandRowShardMap m{};
+    m.row0 = s.row0, m.nv = s.n_rows, m.n = s.n_rows + s.n_tail;
+    m.tail_begin = s.n_tail > 0 ? s.tail_begin : vid0 + F * P;
+    int a = 0, b = P, fa = 0, C = 0;   // (no video row: every position holds no frame)
+    if (s.n_rows > 0) {
+        const int e = s.row0 + s.n_rows, fb = (e - 1) / P;
+        a = s.row0 % P, fa = s.row0 / P, b = e - fb * P, C = fb - fa + 1;
+    }
+    // position p owns C - (p < a) - (p >= b) frames from frame fa + (p < a)
+    m.pb1 = std::min(a, b), m.pb2 = std::max(a, b);
+    m.c0 = std::max(C - 1, 0), m.fs0 = fa + 1;
+    m.c1 = a < b ? C : std::max(C - 2, 0), m.fs1 = a < b ? fa : fa + 1;
+    m.c2 = std::max(C - 1, 0), m.fs2 = fa;
+    m.L1 = m.pb1 * m.c0, m.L2 = m.L1 + (m.pb2 - m.pb1) * m.c1;
+    auto sp = [P](int c) { return kBN / std::max(c, 1) + (kBN % std::max(c, 1)) * P; };
+    m.sp0 = sp(m.c0), m.sp1 = sp(m.c1), m.sp2 = sp(m.c2);
+    return m;
+}
 
 // Row regions of a shard launch for the heads of one kind: band_row_regions in the local order of the q shard — the cuts of the mask
 // (rowfull_lo, rowfull_hi, real_len) through ginv_q.  Returns the number of q-tiles.
@@ -1249,9 +1401,9 @@ inline int band_shard_regions(const typename Pol::Params& p, int kind, int* lo, 
     return nqt;
 }
 
-// parameters of a shard launch (BandShardOf): those of the sequence of S rows with the video geometry of `perm` (its flags may be null: every
-// head in logical order), the two shard maps, the row regions of both head kinds — nqt is the larger count — and the tensors as
-// [BH, Sq | Sk, D] (or `c.lay`)
+// parameters of a shard launch (BandShardOf, or BandRowShardOf with the maps of row shards): those of the sequence of S rows with the video
+// geometry of `perm` (its flags may be null: every head in logical order), the two shard maps, the row regions of both head kinds —
+// nqt is the larger count — and the tensors as [BH, Sq | Sk, D] (or `c.lay`)
 template <typename Pol, typename T>
 inline typename Pol::Params make_band_shard_params(const BandCall& c) {
     const svg_perm_desc_t* const perm = c.perm;
@@ -1260,7 +1412,10 @@ inline typename Pol::Params make_band_shard_params(const BandCall& c) {
     typename Pol::Params p = make_band_params<Pol, T>(whole);
     p.head_flag = perm->head_perm_flag;
     p.vid0 = perm->vid0, p.F = perm->num_frame, p.P = perm->frame_size, p.V = perm->num_frame * perm->frame_size;
-    p.qs = make_band_shard_map(*c.q_shard, p.vid0, p.F, p.P), p.ks = make_band_shard_map(*c.k_shard, p.vid0, p.F, p.P);
+    if constexpr (std::is_same_v<decltype(p.qs), BandRowShardMap>)
+        p.qs = make_band_row_shard_map(*c.q_rows, p.vid0, p.F, p.P), p.ks = make_band_row_shard_map(*c.k_rows, p.vid0, p.F, p.P);
+    else
+        p.qs = make_band_shard_map(*c.q_shard, p.vid0, p.F, p.P), p.ks = make_band_shard_map(*c.k_shard, p.vid0, p.F, p.P);
     if (!c.strided) p.lay = contiguous_layout(c.BH, c.BH, p.qs.n, p.ks.n, Pol::kHeadDim);
     p.nqt = band_shard_regions<Pol>(p, 0, p.reg_lo, p.reg_hi, p.reg_t0);
     const int nqt1 = band_shard_regions<Pol>(p, 1, p.reg1_lo, p.reg1_hi, p.reg1_t0);

@@ -2647,6 +2647,10 @@ def __getattr__(name: str):
         from . import _band_lse_d64
 
         return getattr(_band_lse_d64, name)
+    if name in ("band_row_shard_attention", "BandRowShard"):   # (include/svg_attn_band_row_shard.h, likewise: svg/_band_row_shard.py)
+        from . import _band_row_shard
+
+        return getattr(_band_row_shard, name)
     if name == "varblock_attention_lse_auto":   # (include/svg_attn_varblock_lse_auto.h, likewise: svg/_varblock_lse_auto.py)
         from . import _varblock_lse_auto
 

@@ -21,7 +21,9 @@ its own shard into one partial (svg_sample_mse_shard_partial), the partials are 
 (svg_sample_mse_from_parts) — and `token_sharded_svg1_layer_call` chains the two: a sharded SVG1 layer-call from q, k, v alone.  Both
 carry the processors' device switch between the sparse and the dense warm-up mask (dense_mask / dense_flag:
 svg_band_shard_attention_switch_lse[_f32]), and `enable_frame_shards` is the mode in which the SVG1 processors of HunyuanVideo and Wan run
-them (svg/models/_core.py).
+them (svg/models/_core.py).  `enable_frame_shards(balance="rows")` shards the video by equal rows instead (`row_shard`: shards that cut
+through frames, svg_band_row_shard_attention_lse[_f32] — svg/_band_row_shard.py): `token_sharded_svg1_attention` runs on them, the
+profiler and the device switch do not yet.
 
 `enable_token_shards` is the third mode and the one every processor has: activations sharded by rows, `run_token_sharded` exchanges rows for
 whole heads in front of the attention core (one all_to_all_single per tensor), runs the single-GPU core on this rank's heads of the whole
@@ -36,13 +38,13 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
-from . import _native
+from . import _band_row_shard, _native
 
 # ---------------------------------------------------------------------------------------------------------------
 # opt-in switch for the processors (svg/models/_core.py): svg.distributed.enable(group) makes every SVG1 / SVG2 layer-call run
 # this rank's heads only and all-gather the result; nothing changes for a process that never calls it.
 # ---------------------------------------------------------------------------------------------------------------
-_STATE: Dict[str, object] = {"enabled": False, "group": None, "frames": False, "frames_group": None,
+_STATE: Dict[str, object] = {"enabled": False, "group": None, "frames": False, "frames_group": None, "frames_balance": "frames",
                              "tokens": False, "tokens_group": None, "tokens_unit": 128, "tokens_counts": None}
 
 
@@ -127,25 +129,31 @@ def head_mode():
     return False, None
 
 
-def enable_frame_shards(group=None) -> None:
+def enable_frame_shards(group=None, balance: str = "frames") -> None:
     """The second, separate mode: the SVG1 processors of HunyuanVideo and Wan receive q, k, v of ALL heads of this rank's whole frames
     (`frame_shard(geometry, rank, world)`; the rows behind the video on the last rank) and run every layer-call through
     token_sharded_svg1_layer_call / token_sharded_svg1_attention over the ranks of `group` — activations stay sharded by rows from one layer
     to the next, K / V shards and the profiler's parts are what travels.  Equal to the single-GPU result to rounding.  The rotary tables
-    and the text are the caller's: its own rows of the tables, HunyuanVideo's text on the last rank.  Head sharding (enable) must be off."""
+    and the text are the caller's: its own rows of the tables, HunyuanVideo's text on the last rank.  Head sharding (enable) must be off.
+    balance="rows": a rank holds `row_shard(geometry, rank, world)` instead — an equal share of the video's rows, cut through frames (33
+    frames over 8 ranks: the largest shard is the mean, not 1.21 x the mean) — and token_sharded_svg1_attention runs on row shards
+    (svg_band_row_shard_attention_lse[_f32]).  The shard profiler and the device switch have no row-shard form: the processors, whose
+    layer-call needs both, refuse the mode with NotImplementedError; token_sharded_svg1_attention is what runs under it."""
+    if balance not in ("frames", "rows"):
+        raise ValueError(f'svg.distributed.enable_frame_shards: balance is "frames" or "rows", got {balance!r}')
     assert dist.is_available() and dist.is_initialized(), "svg.distributed.enable_frame_shards: call torch.distributed.init_process_group first"
     if _STATE["enabled"]:
         raise RuntimeError("svg.distributed.enable_frame_shards: head sharding (enable) is on; disable() it first — one mode at a time")
     if _STATE["tokens"]:
         raise RuntimeError("svg.distributed.enable_frame_shards: token-shard mode (enable_token_shards) is on; disable() it first — one mode "
                            "at a time")
-    _STATE["frames"], _STATE["frames_group"] = True, group
+    _STATE["frames"], _STATE["frames_group"], _STATE["frames_balance"] = True, group, balance
 
 
 def disable() -> None:
     """all three modes off"""
     _STATE["enabled"], _STATE["group"] = False, None
-    _STATE["frames"], _STATE["frames_group"] = False, None
+    _STATE["frames"], _STATE["frames_group"], _STATE["frames_balance"] = False, None, "frames"
     _STATE["tokens"], _STATE["tokens_group"], _STATE["tokens_unit"], _STATE["tokens_counts"] = False, None, 128, None
 
 
@@ -156,6 +164,11 @@ def frame_shards_active() -> bool:
 
 def frame_shards_group():
     return _STATE["frames_group"]
+
+
+def frame_shards_balance() -> str:
+    """"frames" (whole frames per rank) or "rows" (row_shard: equal rows per rank), as enable_frame_shards set it"""
+    return str(_STATE["frames_balance"])
 
 
 def active() -> bool:
@@ -686,8 +699,30 @@ def frame_shard(geometry, rank: int, world: int):
     return _native.BandShard(f0, f1 - f0, tail0, n_tail)
 
 
-def _frame_shards(geometry, world: int):
-    """(frame_shard of every rank, the rows each of them holds)"""
+def row_shard(geometry, rank: int, world: int, unit: int = 128):
+    """The row shard (_band_row_shard.BandRowShard) of rank `rank` under balance="rows": the video's rows in multiples of `unit`, as even
+    as units go (token_range: the first ranks one unit more), the last rank the remainder — and the tail, every row behind the video.  A
+    shard begins and ends inside frames; geometry = (num_tokens, vid0, num_frame, frame_size), vid0 = 0 as for frame_shard."""
+    S, vid0, F, P = (int(x) for x in geometry)
+    if vid0 != 0:
+        raise ValueError(f"row_shard: {vid0} rows in front of the video belong to no shard (a shard's tail lies behind the video)")
+    a, b = token_range(F * P, rank, world, unit)
+    return _band_row_shard.BandRowShard(a, b - a, F * P, S - F * P if rank == world - 1 else 0)
+
+
+def _balance(balance: Optional[str]) -> str:
+    """the balance of a call: its own argument, or the one enable_frame_shards set"""
+    balance = frame_shards_balance() if balance is None else balance
+    if balance not in ("frames", "rows"):
+        raise ValueError(f'balance is "frames" or "rows", got {balance!r}')
+    return balance
+
+
+def _frame_shards(geometry, world: int, balance: str = "frames"):
+    """(frame_shard — balance "rows": row_shard — of every rank, the rows each of them holds)"""
+    if balance == "rows":
+        shards = [row_shard(geometry, r, world) for r in range(world)]
+        return shards, [_band_row_shard.band_row_shard_rows(s) for s in shards]
     shards = [frame_shard(geometry, r, world) for r in range(world)]
     return shards, [_native.band_shard_rows(s, int(geometry[3])) for s in shards]
 
@@ -695,25 +730,28 @@ def _frame_shards(geometry, world: int):
 _SHARD_KINDS = {"both": (False, True), "logical": (False,), "token_major": (True,)}
 
 
-def band_shard_exchange_plan(mask, geometry, world: int, kinds: str = "both", dense_mask=None) -> List[List[bool]]:
+def band_shard_exchange_plan(mask, geometry, world: int, kinds: str = "both", dense_mask=None, balance: str = "frames") -> List[List[bool]]:
     """plan[r][s]: do the rows of rank r's shard (frame_shard) see any key of rank s's shard under `mask` — for ANY kind of head that
     occurs: kinds = "logical", "token_major", or "both" where the flags live on the device (no flag is read back)?  Host only, closed form
     (_native.band_shard_has_keys); the same table on every rank.  A rank without rows neither sends nor receives.
     dense_mask: the alternate mask of a device switch, whose flag is not read back either — the element-wise OR with the plan of
-    `dense_mask` for heads in logical order: a pair that either setting of the flag needs is kept."""
+    `dense_mask` for heads in logical order: a pair that either setting of the flag needs is kept.
+    balance="rows": the same table for the row shards (row_shard; _band_row_shard.band_row_shard_has_keys)."""
     S, vid0, F, P = (int(x) for x in geometry)
-    sh, rows = _frame_shards(geometry, world)
-    plan = [[rows[r] > 0 and rows[s] > 0 and any(_native.band_shard_has_keys(mask, S, (vid0, F, P), sh[r], sh[s], kind)
+    sh, rows = _frame_shards(geometry, world, balance)
+    has_keys = _band_row_shard.band_row_shard_has_keys if balance == "rows" else _native.band_shard_has_keys
+    plan = [[rows[r] > 0 and rows[s] > 0 and any(has_keys(mask, S, (vid0, F, P), sh[r], sh[s], kind)
                                                  for kind in _SHARD_KINDS[kinds]) for s in range(world)] for r in range(world)]
     if dense_mask is not None:
-        alt = band_shard_exchange_plan(dense_mask, geometry, world, "logical")
+        alt = band_shard_exchange_plan(dense_mask, geometry, world, "logical", balance=balance)
         plan = [[a or b for a, b in zip(ra, rb)] for ra, rb in zip(plan, alt)]
     return plan
 
 
 def token_sharded_svg1_attention(q_local: torch.Tensor, k_local: torch.Tensor, v_local: torch.Tensor, mask, best_mask_idx, geometry,
                                  group=None, fp32_parts: bool = True, kinds: str = "both", attn_fn: Optional[Callable] = None,
-                                 merge_fn: Optional[Callable] = None, dense_mask=None, dense_flag=None) -> torch.Tensor:
+                                 merge_fn: Optional[Callable] = None, dense_mask=None, dense_flag=None,
+                                 balance: Optional[str] = None) -> torch.Tensor:
     """One SVG1 layer-call over a sequence that lives sharded by whole frames: q_local, k_local, v_local [..., H, S_r, D] are ALL heads of
     this rank's rows `frame_shard(geometry, rank, world)` — its frames as the model stores them, on the last rank the text and padding
     behind them; best_mask_idx (int [BH] on the device, != 0: a token-major head) is what the device switch produced and is never read
@@ -731,15 +769,28 @@ def token_sharded_svg1_attention(q_local: torch.Tensor, k_local: torch.Tensor, v
     is the element-wise OR of the plan of `mask` under `kinds` and the plan of `dense_mask` with heads in logical order
     (band_shard_exchange_plan(..., dense_mask=dense_mask)), and the limit of MERGE_MAX_PARTS is checked on that.  An injected attn_fn
     keeps its five arguments and looks after the flag itself.
+    balance ("frames" / "rows"; None: what enable_frame_shards set, "frames" without it): "rows" — this rank's rows are
+    `row_shard(geometry, rank, world)`, equal shares of the video's rows that cut through frames; the steps are
+    _band_row_shard.band_row_shard_attention on the two row shards and the plan is that of the row shards.  The device switch has no
+    row-shard form: dense_mask with the native step raises NotImplementedError (an injected attn_fn looks after it as before).
     What svg.models._core runs in frame-shard mode (enable_frame_shards); not wired into bench_step.py.  Equal to the single-GPU result
     to rounding, not bit for bit."""
     _check_device_switch_pair("token_sharded_svg1_attention", dense_mask, dense_flag)
+    balance = _balance(balance)
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     S, vid0, F, P = (int(x) for x in geometry)
-    sh, n_tok = _frame_shards(geometry, world)
+    sh, n_tok = _frame_shards(geometry, world, balance)
     S_me = n_tok[rank]
     assert q_local.shape[-2] == S_me and k_local.shape == v_local.shape and k_local.shape[-2] == S_me, (
-        f"rank {rank} holds {q_local.shape[-2]} / {k_local.shape[-2]} rows, frame_shard says {S_me}")
+        f"rank {rank} holds {q_local.shape[-2]} / {k_local.shape[-2]} rows, {'row' if balance == 'rows' else 'frame'}_shard says {S_me}")
+    if attn_fn is None and balance == "rows":
+        if dense_mask is not None:
+            raise NotImplementedError('token_sharded_svg1_attention(balance="rows"): the device switch (dense_mask / dense_flag) has no '
+                                      "row-shard form; run the dense mask as `mask` or use balance=\"frames\"")
+
+        def attn_fn(q, k, v, q_shard, k_shard):
+            return _band_row_shard.band_row_shard_attention(q, k, v, mask, (S, vid0, F, P), q_shard, k_shard,
+                                                            torch.float32 if fp32_parts else None, flags=best_mask_idx)
     if attn_fn is None:
         def attn_fn(q, k, v, q_shard, k_shard):
             if dense_mask is not None:
@@ -751,7 +802,7 @@ def token_sharded_svg1_attention(q_local: torch.Tensor, k_local: torch.Tensor, v
         def merge_fn(o_parts, lse_parts):
             return _native.merge_attention_states(o_parts, lse_parts, out_dtype=q_local.dtype if fp32_parts else None)
     return _attend_over_key_shards(q_local, k_local, v_local, n_tok,
-                                   band_shard_exchange_plan(mask, geometry, world, kinds, dense_mask=dense_mask),
+                                   band_shard_exchange_plan(mask, geometry, world, kinds, dense_mask=dense_mask, balance=balance),
                                    lambda src, k_s, v_s: attn_fn(q_local, k_s, v_s, sh[rank], sh[src]), merge_fn, group,
                                    "token_sharded_svg1_attention", post_before_own_part=False)
 
@@ -760,16 +811,22 @@ def token_sharded_svg1_attention(q_local: torch.Tensor, k_local: torch.Tensor, v
 # the online profiler on frame shards: no K / V travels — every rank streams its own shard once; what travels is the sampled q rows and one
 # partial per rank (svg_sample_mse_shard_partial, svg_sample_mse_from_parts), and every rank ends with the same mse bits.
 # ---------------------------------------------------------------------------------------------------------------
-def sampled_row_owners(rows, geometry, world: int) -> List[Tuple[int, int]]:
+def sampled_row_owners(rows, geometry, world: int, balance: str = "frames") -> List[Tuple[int, int]]:
     """(owner rank, row index in that rank's frame_shard) of every sampled row (global indices, a host sequence): a video row lives with
-    its frame, every row behind the video on the last rank.  Host only; the same list on every rank."""
+    its frame (balance="rows": in the row_shard that holds it), every row behind the video on the last rank.  Host only; the same list on
+    every rank."""
     S, vid0, F, P = (int(x) for x in geometry)
-    sh, _ = _frame_shards(geometry, world)
+    sh, _ = _frame_shards(geometry, world, balance)
     out = []
     for g in (int(x) for x in rows):
         if not 0 <= g < S:
             raise ValueError(f"sampled row {g} outside the {S} rows of the sequence")
-        if g < F * P:
+        if g < F * P and balance == "rows":
+            r = next(r for r in range(world) if sh[r].row0 <= g < sh[r].row0 + sh[r].n_rows)
+            out.append((r, g - sh[r].row0))
+        elif g >= F * P and balance == "rows":
+            out.append((world - 1, sh[-1].n_rows + g - sh[-1].tail_begin))
+        elif g < F * P:
             f = g // P
             r = next(r for r in range(world) if sh[r].f0 <= f < sh[r].f0 + sh[r].n_frames)
             out.append((r, g - sh[r].f0 * P))
@@ -781,7 +838,7 @@ def sampled_row_owners(rows, geometry, world: int) -> List[Tuple[int, int]]:
 
 def token_sharded_sample_mse(q_local: torch.Tensor, k_local: torch.Tensor, v_local: torch.Tensor, rows: torch.Tensor, prof, geometry,
                              group=None, skip_flag: Optional[torch.Tensor] = None, partial_fn: Optional[Callable] = None,
-                             combine_fn: Optional[Callable] = None) -> torch.Tensor:
+                             combine_fn: Optional[Callable] = None, balance: Optional[str] = None) -> torch.Tensor:
     """The online profiler (sample_mse) of a sequence that lives sharded by whole frames: q_local, k_local, v_local [..., H, S_r, D] are ALL
     heads of this rank's rows `frame_shard(geometry, rank, world)`; rows is a CPU int64 tensor of sampled GLOBAL rows, the same on every
     rank (the ranks draw from the broadcast-seeded generator); prof the _native.ProfileDesc of the whole sequence; geometry = (num_tokens,
@@ -795,12 +852,19 @@ def token_sharded_sample_mse(q_local: torch.Tensor, k_local: torch.Tensor, v_loc
     partial_fn and combine_fn default to the native calls (_native.sample_mse_shard_partial, _native.sample_mse_from_parts, both with
     skip_flag); they exist so that the schedule can be tested on gloo without a GPU.  A partial_fn whose parts are not fp32 says so in an
     attribute `part_dtype` (the neutral part of a rank without rows is made in it).
+    balance="rows" (None: what enable_frame_shards set): the rows and owners are those of row_shard, and partial_fn is given the rank's row
+    shard — the native partial (svg_sample_mse_shard_partial) has no row-shard form: without an injected partial_fn, NotImplementedError.
     Not wired into bench_step.py.  Equal to sample_mse on the whole sequence to rounding, not bit for bit."""
+    balance = _balance(balance)
+    if balance == "rows" and partial_fn is None:
+        raise NotImplementedError('token_sharded_sample_mse(balance="rows"): the shard profiler (svg_sample_mse_shard_partial) takes whole-'
+                                  'frame key shards only; profile under balance="frames", or pass best_mask_idx to '
+                                  "token_sharded_svg1_attention yourself")
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     S, vid0, F, P = (int(x) for x in geometry)
     if world > _native.PROFILE_MAX_PARTS:
         raise ValueError(f"token_sharded_sample_mse: {world} ranks, but sample_mse_from_parts takes at most {_native.PROFILE_MAX_PARTS} parts")
-    sh, n_rows = _frame_shards(geometry, world)
+    sh, n_rows = _frame_shards(geometry, world, balance)
     S_me = n_rows[rank]
     assert q_local.shape[-2] == S_me and k_local.shape == v_local.shape and k_local.shape[-2] == S_me, (
         f"rank {rank} holds {q_local.shape[-2]} / {k_local.shape[-2]} rows, frame_shard says {S_me}")
@@ -816,7 +880,7 @@ def token_sharded_sample_mse(q_local: torch.Tensor, k_local: torch.Tensor, v_loc
     BH = math.prod(q_local.shape[:-2])
     q3, k3, v3 = (x.reshape(BH, S_me, D) for x in (q_local, k_local, v_local))
     # the sampled rows: this rank's into their places of a zeroed buffer, an exact sum over the ranks on the bits
-    own = sampled_row_owners(rows.tolist(), geometry, world)
+    own = sampled_row_owners(rows.tolist(), geometry, world, balance)
     pos = [i for i, (r, _) in enumerate(own) if r == rank]
     q_rows = torch.zeros((BH, R, D), dtype=q_local.dtype, device=device)
     if pos:
@@ -839,7 +903,8 @@ def token_sharded_sample_mse(q_local: torch.Tensor, k_local: torch.Tensor, v_loc
 def token_sharded_svg1_layer_call(q_local: torch.Tensor, k_local: torch.Tensor, v_local: torch.Tensor, mask, prof, geometry, rows: torch.Tensor,
                                   group=None, fp32_parts: bool = True, partial_fn: Optional[Callable] = None,
                                   combine_fn: Optional[Callable] = None, attn_fn: Optional[Callable] = None,
-                                  merge_fn: Optional[Callable] = None, dense_mask=None, dense_flag=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                                  merge_fn: Optional[Callable] = None, dense_mask=None, dense_flag=None,
+                                  balance: Optional[str] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """One SVG1 layer-call of a sequence that lives sharded by whole frames, from q, k, v alone: token_sharded_sample_mse picks each head's
     mask — the MSEs rounded to q's dtype before the argmin as svg.models._core.sample_mse rounds them, so two candidates that round to one
     value tie to index 0 and NaN wins — and token_sharded_svg1_attention(..., best_mask_idx, kinds="both") runs the attention under it.
@@ -848,13 +913,17 @@ def token_sharded_svg1_layer_call(q_local: torch.Tensor, k_local: torch.Tensor, 
     dense_mask, dense_flag (both or neither): the processors' device switch — dense_flag (int32 [1] on the device, never read back and
     nothing synchronises) is the profiler's skip_flag and the attention's switch (token_sharded_svg1_attention); the returned best_mask_idx
     is -1 on a dense step, as svg.models._core.svg1_attention_device_switch returns it.
+    balance: that of the two schedules — "rows": q, k, v are the rows of row_shard; the profiler step then needs an injected partial_fn
+    (token_sharded_sample_mse refuses the native one with NotImplementedError) and the attention runs on row shards.
     What svg.models._core runs in frame-shard mode; not wired into bench_step.py."""
     _check_device_switch_pair("token_sharded_svg1_layer_call", dense_mask, dense_flag)
+    balance = _balance(balance)
     mse = token_sharded_sample_mse(q_local, k_local, v_local, rows, prof, geometry, group=group, skip_flag=dense_flag, partial_fn=partial_fn,
-                                   combine_fn=combine_fn)
+                                   combine_fn=combine_fn, balance=balance)
     best_mask_idx = torch.argmin(mse.to(q_local.dtype), dim=0)
     o_local = token_sharded_svg1_attention(q_local, k_local, v_local, mask, best_mask_idx, geometry, group=group, fp32_parts=fp32_parts,
-                                           kinds="both", attn_fn=attn_fn, merge_fn=merge_fn, dense_mask=dense_mask, dense_flag=dense_flag)
+                                           kinds="both", attn_fn=attn_fn, merge_fn=merge_fn, dense_mask=dense_mask, dense_flag=dense_flag,
+                                           balance=balance)
     if dense_flag is not None:
         best_mask_idx = torch.where(dense_flag.reshape(()) != 0, torch.full_like(best_mask_idx, -1), best_mask_idx)
     return o_local, best_mask_idx

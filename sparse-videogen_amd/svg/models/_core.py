@@ -193,6 +193,9 @@ def rows_of_this_rank(what: str, geo: Geometry, shard_form: bool = True) -> int:
                                   f"HunyuanVideo and Wan only")
     if geo.vid0 > 0:
         raise NotImplementedError(f"{what}: frame-shard mode needs the video at row 0; {geo.vid0} rows in front of it belong to no shard")
+    if _dist.frame_shards_balance() == "rows":
+        raise NotImplementedError(f'{what}: enable_frame_shards(balance="rows") has no processor form yet — the shard profiler and the device '
+                                  f"switch run on whole-frame shards only; svg.distributed.token_sharded_svg1_attention takes row shards")
     group = _dist.frame_shards_group()
     shard = _dist.frame_shard((geo.seq_len, geo.vid0, geo.num_frame, geo.frame_size), torch.distributed.get_rank(group),
                               torch.distributed.get_world_size(group))

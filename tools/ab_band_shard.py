@@ -31,6 +31,12 @@ launches of a rank run over the shards the OR-ed plan keeps (band_shard_exchange
 With --parent two more lines: the plain svg_band_attention launch and the plain shard launches of the first rank, this build (B) against
 the parent's library (A) in the same process: bit-identical, the difference inside A's spread.
 Again ONE GPU running one rank's launches: no exchange is timed and no multi-GPU run exists.
+--rows: row shards (include/svg_attn_band_row_shard.h) beside frame shards, one line appended to profiles/band_row_shard_ab.jsonl: the
+launches of the rank with the most rows under balance="rows" (svg.distributed.row_shard: 14 848 video rows each, the last rank 16 more and
+the text), the same under balance="frames" (the first rank's 5 frames, 18 000 rows), a middle rank of each (the band on both sides of its
+rows) and the full-S call, as five alternating windows with the shader clock granted to each (svg._native.ClockProbe; null where the
+counters do not move): frames_over_full_eighth, rows_over_full_eighth, rows_over_frames for the ranks with the most rows, and
+slowest_rows_over_slowest_frames over the measured ranks.  The expectation is the row ratio, 1.21 -> about 1.0; no threshold is set.
 --tiny: small shapes, two alternations (a rehearsal of the script, not a measurement)."""
 import argparse
 import ctypes as C
@@ -263,8 +269,77 @@ def shard_parent_line(nat, new, old, w, alternations, min_ms):
     return rec
 
 
+def rows_line(nat, lib, w, alternations, min_ms):
+    """--rows: the launches of the LARGEST rank under balance="rows" (svg_band_row_shard_attention_lse on svg.distributed.row_shard) and
+    under balance="frames" (svg_band_shard_attention_lse on frame_shard) beside the full-S call, in alternating windows with the granted
+    shader clock of each"""
+    from ab_adaptive_band import alternate_clocked
+    from ab_adaptive_band import stats as side
+    from svg import _band_row_shard as rs
+    from svg.distributed import band_shard_exchange_plan, frame_shard, row_shard
+
+    st = torch.cuda.current_stream().cuda_stream
+    scale = 1.0 / math.sqrt(w.D)
+    perm = nat.PermDesc(w.flags.data_ptr(), 0, w.F, w.P)
+    rlib = rs.load()
+
+    def rows_of(x, s):   # the rows of a shard of either kind as a buffer of its own
+        if isinstance(s, rs.BandRowShard):
+            return torch.cat([x[:, :, s.row0:s.row0 + s.n_rows], x[:, :, s.tail_begin:s.tail_begin + s.n_tail]], dim=2).contiguous()
+        return shard_of(x, s, w)
+
+    def rank_launches_of(balance, rank=None):
+        make, entry = (row_shard, rlib.svg_band_row_shard_attention_lse) if balance == "rows" else (frame_shard, lib.svg_band_shard_attention_lse)
+        sh = [make(w.geo, r, WORLD) for r in range(WORLD)]
+        n = [rs.band_row_shard_rows(s) if balance == "rows" else nat.band_shard_rows(s, w.P) for s in sh]
+        rank = max(range(WORLD), key=lambda r: n[r]) if rank is None else rank
+        plan = band_shard_exchange_plan(w.mask, w.geo, WORLD, "both", balance=balance)
+        kept = [s for s in range(WORLD) if plan[rank][s]]
+        q_r = rows_of(w.q, sh[rank])
+        kv = {s: (rows_of(w.k, sh[s]), rows_of(w.v, sh[s])) for s in kept}
+        outs = {s: (torch.empty_like(q_r), torch.empty(1, w.H, n[rank], dtype=torch.float32, device="cuda")) for s in kept}
+        run = all_of([checked(entry, (q_r.data_ptr(), kv[s][0].data_ptr(), kv[s][1].data_ptr(), outs[s][0].data_ptr(), outs[s][1].data_ptr(), w.H,
+                                      w.S, w.D, 0, scale, C.byref(w.mask), C.byref(perm), C.byref(sh[rank]), C.byref(sh[s]), None, st),
+                              f"{balance} rank {rank} over {s}") for s in kept])
+        return run, (q_r, kv, outs), dict(rank=rank, rows=n[rank], parts_kept=len(kept), largest_shard_over_mean=round(max(n) / (sum(n) / WORLD), 4),
+                                          shard=list(sh[rank].as_tuple()))
+
+    dense, use_alt = nat.BandMask(w.S, w.S + 1, 0, 0, 0, 0), torch.zeros(1, dtype=torch.int32, device="cuda")
+    o_full, lse_full = torch.empty_like(w.q), torch.empty(1, w.H, w.S, dtype=torch.float32, device="cuda")
+    full = checked(lib.svg_band_attention_switch_lse,
+                   (w.q.data_ptr(), w.k.data_ptr(), w.v.data_ptr(), o_full.data_ptr(), lse_full.data_ptr(), w.H, w.S, w.D, 0, scale,
+                    C.byref(w.mask), C.byref(perm), C.byref(dense), use_alt.data_ptr(), None, st), "svg_band_attention_switch_lse")
+    (fr, keep_f, info_f), (ro, keep_r, info_r) = rank_launches_of("frames"), rank_launches_of("rows")
+    mid = WORLD // 2 - 1   # (a middle rank sees the whole band on both sides; the first and the last one half of it)
+    (fm, keep_fm, info_fm), (rm, keep_rm, info_rm) = rank_launches_of("frames", mid), rank_launches_of("rows", mid)
+    full(), fr(), ro(), fm(), rm()
+    torch.cuda.synchronize()
+    outs, s0 = keep_r[2], info_r["shard"]
+    merged = nat.merge_attention_states([outs[s][0] for s in sorted(outs)], [outs[s][1] for s in sorted(outs)])
+    ref = torch.cat([o_full[:, :, s0[0]:s0[0] + s0[1]], o_full[:, :, s0[2]:s0[2] + s0[3]]], dim=2).float()
+    ws, mhz, calls = alternate_clocked([full, fr, ro, fm, rm], alternations, min_ms, nat.ClockProbe(torch.device("cuda")))
+    sides = [dict(side(x), sclk_mhz=m) for x, m in zip(ws, mhz)]
+    eighth = sides[0]["ms"] / WORLD
+    rec = {"pair": "rows_vs_frames_largest_rank", "workload": "tiny" if w.S < 10000 else "hunyuan_720p",
+           "full": "svg_band_attention_switch_lse over all S rows",
+           "frames_launches": "svg_band_shard_attention_lse, a frame_shard over its kept shards: the rank with the most rows, a middle rank",
+           "rows_launches": "svg_band_row_shard_attention_lse, a row_shard over its kept shards: the rank with the most rows, a middle rank",
+           "token_major_heads": int(w.flags.sum())}
+    rec.update(w.cfg)
+    rec.update({"alternations": alternations, "repetitions_per_window": calls, "full_side": sides[0], "frames_side": dict(sides[1], **info_f),
+                "rows_side": dict(sides[2], **info_r), "frames_middle_side": dict(sides[3], **info_fm),
+                "rows_middle_side": dict(sides[4], **info_rm),
+                "slowest_rows_over_slowest_frames": round(max(sides[2]["ms"], sides[4]["ms"]) / max(sides[1]["ms"], sides[3]["ms"]), 4),
+                "frames_over_full_eighth": round(sides[1]["ms"] / eighth, 4),
+                "rows_over_full_eighth": round(sides[2]["ms"] / eighth, 4), "rows_over_frames": round(sides[2]["ms"] / sides[1]["ms"], 4),
+                "rows_merged_vs_full_call_rel_l2": round(((merged.float() - ref).norm() / ref.norm()).item(), 6),
+                "multi_gpu_timing": "none: one GPU runs one rank's launches, no exchange was timed"})
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", action="store_true", help="row shards beside frame shards (default output: profiles/band_row_shard_ab.jsonl)")
     ap.add_argument("--parent", default=None, help="libsvgattn.so built from the parent commit (adds the plain_vs_parent line)")
     ap.add_argument("--alternations", type=int, default=7)
     ap.add_argument("--min-ms", type=float, default=500.0)
@@ -279,7 +354,8 @@ def main():
     nat.load()
     new = typed(nat, nat.lib_path(), ["svg_band_attention", "svg_band_attention_switch_lse", "svg_band_shard_attention_lse",
                                       "svg_band_shard_attention_switch_lse"])
-    out = Path(a.out or ROOT / "profiles" / ("band_shard_switch_ab.jsonl" if a.switch else "band_shard_ab.jsonl"))
+    out = Path(a.out or ROOT / "profiles" / ("band_row_shard_ab.jsonl" if a.rows else "band_shard_switch_ab.jsonl" if a.switch
+                                             else "band_shard_ab.jsonl"))
     out.parent.mkdir(parents=True, exist_ok=True)
     alternations = 2 if a.tiny else max(a.alternations, 5)
     min_ms = 20.0 if a.tiny else a.min_ms
@@ -291,6 +367,9 @@ def main():
             f.write(line + "\n")
             f.flush()
 
+        if a.rows:
+            emit(rows_line(nat, new, w, alternations, min_ms))
+            return
         if a.switch:
             for rank, label in ((0, "first_rank"), (WORLD // 2 - 1, "middle_rank"), (WORLD - 1, "last_rank")):
                 for rec in switch_lines(nat, new, w, rank, label, alternations, min_ms):
